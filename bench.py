@@ -2,7 +2,16 @@
 """bench.py -- BASELINE.json metric: QPS @ recall@10 >= 0.95 on SIFT-1M-shaped data (d=128, beam=64)
 with the achieved fraction of the HBM roofline, 1..8 GPUs, one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode query|c4|c3build|c5build]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mode query|c4|c3build|c5build] [--full] [--dump-outputs DIR]
+
+A plain run does only what the headline line needs: set up (data, index built on the device), warm up, time exactly --steps
+steps, check the recall the metric is quoted at, write --dump-outputs if given, print the line.  `--full` adds what takes runs of
+its own beside the headline: the CPU baseline (`cpu_baseline`) and, for the default workload, the HBM-resident second leg
+(`roofline.hbm_resident`); `--no-cpu-baseline` / `--no-hbm-leg` drop one of them again.
+
+`--dump-outputs DIR` writes what the timed path returned in its last step, one DIR/<name>.npy per array (float32, or float64 for
+integer arrays), at most 64 MB in all: a larger output is cut to a fixed, seeded sample of its rows, whose indices are written as
+DIR/sample_rows.npy.  The inputs depend only on the arguments, so two builds can be compared output for output.
 
 `--gpus N` with N > 1 and no RANK in the environment: this process only LAUNCHES -- it starts N fresh child
 processes (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set) before anything here has touched the GPU,
@@ -42,6 +51,43 @@ def log(*a):
     print(*a, file=sys.stderr, flush=True)
 
 
+DUMP_BUDGET_BYTES = 60_000_000   # array bytes of --dump-outputs; the .npy headers stay well inside the 64 MB ceiling
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: `arrays` (name -> array with one row per query / point, all of the same length) as out_dir/<name>.npy.
+    Floats keep float32 / float64, integers become float64 (exact for 32-bit values: ids as the product's uint32).  Over the
+    budget, the same fixed, seeded sample of rows is taken from every array and its indices are written as sample_rows.npy."""
+    import numpy as np
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        conv[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    n_rows = {len(a) for a in conv.values()}
+    assert len(n_rows) == 1, "dump_outputs: arrays of different lengths"
+    n_rows = n_rows.pop()
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_BUDGET_BYTES:
+        m = int(DUMP_BUDGET_BYTES // (total / n_rows + 8))       # + 8 B per row for its index
+        rows = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_rows, m, replace=False))
+        conv = {name: a[rows] for name, a in conv.items()}
+        conv["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in conv.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+    log(f"bench.py: outputs of the last timed step written to {out_dir} ({', '.join(sorted(conv))}"
+        f"{f'; {len(conv[next(iter(conv))])} of {n_rows} rows sampled' if 'sample_rows' in conv else ''})")
+
+
+def search_outputs(outs):
+    """the arrays pann_batch_search_dev returns, from search_leg's device buffers; ids as the product's uint32"""
+    import numpy as np
+    d = {name: t.cpu().numpy() for name, t in outs.items()}
+    d["ids"] = d["ids"].view(np.uint32)
+    return d
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -60,9 +106,13 @@ def parse_args(argv=None):
     ap.add_argument("--trees", type=int, default=30)
     ap.add_argument("--dtype", default="f16", choices=["f16", "u8", "f32"],
                     help="element type of the device copy (default f16 = BASELINE config[1]); the others are for comparison runs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what is not the headline: the CPU baseline and, for the default workload, the HBM-resident leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the timed path returned in its last step to DIR/<name>.npy (float32/float64, <= 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-hbm-leg", action="store_true",
-                    help="skip the second, labelled leg of the default run (the same kernel on a 12.5M-point, 3.2 GB table)")
+                    help="with --full: skip the second, labelled leg of the default run (the same kernel on a 12.5M-point, 3.2 GB table)")
     ap.add_argument("--hbm-n", type=int, default=12_500_000)
     ap.add_argument("--hbm-noise", type=float, default=None, help="noise scale of the HBM leg's generator (calibration runs)")
     ap.add_argument("--data", default="sift1m_like", choices=["sift1m_like", "sift_like"],
@@ -262,7 +312,7 @@ def search_leg(rk, ix, Q, args, beam, steps, warmup):
     alg_bytes = int(bytes_q.sum())
     return {"elapsed_s": elapsed, "ms_per_step": elapsed * 1e3 / steps, "kernel_ms": kern_ms, "alg_bytes": alg_bytes,
             "achieved_gbps": alg_bytes / (kern_ms / 1e3) / 1e9, "avg_visited": float(vis.mean()), "avg_cmps": float(cmps.mean()),
-            "ids": d_ids}
+            "ids": d_ids, "outputs": {"ids": d_ids, "dists": d_dists, "visited_count": d_vis, "dist_cmps": d_cmps, "degree_sum": d_deg}}
 
 
 def committed_traffic(args, key=None):
@@ -289,7 +339,7 @@ def committed_traffic(args, key=None):
 HBM_LEG_NOISE = 10.0
 
 
-def hbm_resident_leg(rk, args):
+def hbm_resident_leg(rk, args, dump_dir=None):
     """The headline's 256 MB table is about the size of the 256 MiB Infinity Cache, so its rate is not an HBM number.  This leg
     runs the SAME kernel, beam and k on a table 12x the cache (12.5M x 128 fp16 = 3.2 GB = one C4 shard), built on the device,
     and is reported beside the headline as roofline.hbm_resident -- measured in this run, never `value`."""
@@ -307,6 +357,8 @@ def hbm_resident_leg(rk, args):
     build_s = time.time() - t0
     log(f"[hbm leg] {args.hbm_n}x128 f16 generated in {tgen:.1f}s, built in {build_s:.1f}s")
     r = search_leg(rk, ix, Q, args, 64, args.steps, args.warmup)
+    if dump_dir and rk.rank == 0:
+        dump_outputs(dump_dir, search_outputs(r["outputs"]))
     gt_ids, gt_d = ix.bruteforce_knn(Q, 100)
     rec = recall_at_k(r["ids"].cpu().numpy().view(np.uint32), gt_ids, gt_d, args.k)
     ix.close()
@@ -382,12 +434,14 @@ def mode_query(rk, args):
                          "kernel": kernel_name(args.beam), "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": r["alg_bytes"]},
             "ranks_seen": rk.ranks_seen, "devices_seen": rk.devices_seen, "backend": rk.backend if world > 1 or "RANK" in os.environ else None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, search_outputs(r["outputs"]))
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(ix, Xf, Q.astype(np.float32), args)
     del Xf, X
     ix.close()
     if rank == 0:
-        if world == 1 and default_workload and not args.no_hbm_leg:
+        if args.full and world == 1 and default_workload and not args.no_hbm_leg:
             res["roofline"]["hbm_resident"] = hbm_resident_leg(rk, args)
         print(json.dumps(res), flush=True)
         if res["recall_at_10"] < 0.95 and (args.strict or default_workload):
@@ -434,7 +488,9 @@ def mode_c4(rk, args):
     alg_all = rk.sum_over_ranks([alg_local])[0]
     gt_i, gt_d = sh.bruteforce(Q, 100)                                  # exact ground truth over all shards, same exchange
     if rank == 0:
-        oi, _ = last[0]
+        oi, od = last[0]
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"ids": oi.cpu().numpy().view(np.uint32), "dists": od.cpu().numpy()})
         rec = recall_at_k(oi.cpu().numpy().view(np.uint32), gt_i.cpu().numpy().view(np.uint32), gt_d.cpu().numpy(), args.k)
         achieved = alg_all / (ms_per_step / 1e3) / 1e9
         print(json.dumps({
@@ -481,6 +537,8 @@ def mode_c3build(rk, args):
     info = last[0]; st = info["stats"]
     cs = graph_checksum(ix.get_graph()) if args.n <= 20_000_000 else None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"graph": ix.get_graph()})
         r = ix.batch_search(Q, k=args.k, beam=args.beam)
         gt, gd = ix.bruteforce_knn(Q, 100)
         rec = recall_at_k(r["ids"], gt, gd, args.k)
@@ -528,6 +586,8 @@ def mode_c5build(rk, args):
     info = last[0]
     G = ix.get_graph()
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"graph": G})
         r = ix.batch_search(Q, k=args.k, beam=args.beam)
         gt, gd = ix.bruteforce_knn(Q, 100)
         rec = recall_at_k(r["ids"], gt, gd, args.k)
@@ -549,7 +609,7 @@ def mode_c5build(rk, args):
 
 def mode_hbm_leg(rk, args):
     args.hbm_n = args.n
-    leg = hbm_resident_leg(rk, args)
+    leg = hbm_resident_leg(rk, args, dump_dir=args.dump_outputs)
     if rk.rank == 0:
         print(json.dumps({
             "metric": "QPS @ recall@10>=0.95 on the HBM-resident table (second leg of the default run, by itself)",

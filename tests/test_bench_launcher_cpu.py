@@ -45,3 +45,27 @@ def test_world_size_must_match_gpus_flag():
     assert p.returncode != 0 and "--gpus 2" in p.stderr
     p = _run("--gpus", "1", "--mode", "launchcheck", env=e)
     assert p.returncode == 0, p.stderr[-2000:]
+
+
+def test_dump_outputs_converts_and_samples_within_the_budget(tmp_path):
+    """--dump-outputs: integers become float64 exactly, floats stay; an output over the budget is cut to the same seeded
+    sample of rows in every array and on every call, its indices beside it, and the files stay under 64 MB"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    ids = np.arange(20, dtype=np.uint32).reshape(10, 2) + np.uint32(0xFFFFFFF0)
+    bench.dump_outputs(str(tmp_path / "small"), {"ids": ids, "dists": np.full((10, 2), 0.5, np.float32)})
+    assert sorted(os.listdir(tmp_path / "small")) == ["dists.npy", "ids.npy"]
+    got = np.load(tmp_path / "small" / "ids.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, ids.astype(np.float64))
+    assert np.load(tmp_path / "small" / "dists.npy").dtype == np.float32
+    G = np.random.default_rng(0).integers(0, 2**32, (120_000, 65), dtype=np.uint64).astype(np.uint32)    # 62 MB as float64
+    deg = G[:, 0].astype(np.int32)
+    for name in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / name), {"graph": G, "deg": deg})
+        assert sum(os.path.getsize(tmp_path / name / f) for f in os.listdir(tmp_path / name)) <= 64_000_000
+    rows = np.load(tmp_path / "a" / "sample_rows.npy")
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "sample_rows.npy")) and 0 < len(rows) < len(G)
+    r = rows.astype(np.int64)
+    assert np.array_equal(np.load(tmp_path / "a" / "graph.npy"), G[r].astype(np.float64))
+    assert np.array_equal(np.load(tmp_path / "a" / "deg.npy"), deg[r].astype(np.float64))
