@@ -349,6 +349,57 @@ int pann_hcnng_assemble_dev(pann_index* idx, const uint32_t* d_slabs, uint32_t n
 int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes,
                         uint32_t k, uint32_t* out_ids, float* out_dists);
 
+/* ---- scalar quantisation of a float index on the device --------------------------------------
+ * The reference's translating PointRange constructor (point_range.h:54-72: generate_parameters + translate_point per row) and
+ * Point::normalize, for the two one-byte quantisers the drivers use (-quantize_bits 8, -quantize_mode 1, python/graph_index.cpp):
+ *   PANN_QUANT_EUCLID_U8  Euclidian_Point<uint8_t>      parameters euclidian_point.h:211-235, translate :182-209
+ *   PANN_QUANT_MIPS_I8    Quantized_Mips_Point<8, trim> parameters mips_point.h:433-486,      translate :416-430
+ * Results are bit-identical to those loops on finite inputs (std::round, products rounded before they are added, the norm
+ * summed in double in index order).  Sources are f32 rows that are resident on the device: the callers in scope all hold the
+ * full-precision slab there; a float file that is not resident is streamed through pann_quantize_rows by its owner.
+ * Status: a source that is not f32 -> PANN_ERR_UNSUPPORTED; a kind that does not fit the metric (EUCLID_U8 <-> PANN_L2,
+ * MIPS_I8 <-> PANN_MIPS), an unknown kind, n * d == 0, a stride smaller than a row or not a multiple of 4, NULL pointers
+ * -> PANN_ERR_BAD_ARG. */
+enum { PANN_QUANT_EUCLID_U8 = 0, PANN_QUANT_MIPS_I8 = 1 };
+typedef struct pann_quant_params {
+  int32_t kind;
+  int32_t dims;
+  float slope;            /* Euclidian_Point<uint8_t>::parameters (euclidian_point.h:100-110): 255 / (max - min) */
+  int32_t offset;         /*   (int32) round(min * slope); slope == 1 && offset == 0: translate is a plain cast (:194) */
+  float max_val;          /* Quantized_Mips_Point<8>::parameters (mips_point.h:395-403) */
+  float min_seen, max_seen; /* the two values the reference prints ("scalar quantization: min value = ..., max value = ...") */
+} pann_quant_params;
+
+/* Point::normalize (mips_point.h:115-124, euclidian_point.h:150-158) for every row of an f32 handle, in place on the device. */
+int pann_index_normalize(pann_index* idx);
+/* generate_parameters over every coordinate of src (f32).  trim: Quantized_Mips_Point's template flag (the 1e-4 / 1 - 1e-4
+ * order statistics instead of min / max; found exactly, by a radix select, without sorting); ignored for EUCLID_U8. */
+int pann_quantize_params(pann_index* src, int kind, int trim, pann_quant_params* out);
+/* The same over n rows of d floats at a device address (row stride stride_bytes), on `stream` of the current device.  Allocates
+ * a few KB per device on first use and SYNCHRONISES the stream: a handful of words have to come back before the parameters can
+ * be formed.  `out` is a host pointer. */
+int pann_quantize_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride_bytes, int kind, int trim,
+                             pann_quant_params* out, void* stream);
+/* QPR Q_Points(Points) (vamana/neighbors.h:104-110, graph_index.cpp:90-99): a new handle of the same size, max_deg and device
+ * whose points are src's rows translated on the device -- PANN_U8 / PANN_L2 or PANN_I8 / PANN_MIPS by p->kind.  copy_graph != 0:
+ * src's graph is copied device to device; else the graph is empty.  Destroyed with pann_index_destroy like any handle. */
+int pann_index_create_quantized(pann_index** out, pann_index* src, const pann_quant_params* p, int copy_graph);
+/* QPR Q_Query_Points(Query_Points, Q_Points.params): n host rows of p->dims floats -> n rows of p->dims bytes at `out` (host).
+ * normalize_first != 0: every row goes through Point::normalize first (the source is const: never in place).  Runs on device
+ * `device`. */
+int pann_quantize_rows(const pann_quant_params* p, const float* rows, uint64_t n, uint64_t stride_bytes, int normalize_first,
+                       void* out, uint64_t out_stride_bytes, int device);
+/* The same on device pointers, launched on `stream` of the current device; no allocation, no synchronisation.  Bytes
+ * [p->dims, out_stride_bytes) of an output row are not written. */
+int pann_quantize_rows_dev(const pann_quant_params* p, const float* d_rows, uint64_t n, uint64_t stride_bytes,
+                           int normalize_first, void* d_out, uint64_t out_stride_bytes, void* stream);
+/* Counterpart of pann_index_upload_points: rows [first_row, first_row + nrows) of the handle's points back to the host, d
+ * elements of the handle's dtype per row, row stride out_stride_bytes. */
+int pann_index_download_points(pann_index* idx, uint64_t first_row, uint64_t nrows, void* out, uint64_t out_stride_bytes);
+/* host-only helper: the sorted positions generate_parameters reads for len = n * d values (mips_point.h:448-451):
+ * a = (long)(.0001f * len) in float, b = (long)((1.0 - .0001f) * (len - 1)) in double; trim == 0: 0 and len - 1 */
+void pann_quantize_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b);
+
 #ifdef __cplusplus
 }
 #endif

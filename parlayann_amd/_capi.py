@@ -52,6 +52,19 @@ class BuildStats(C.Structure):
                 ("per_point_visited", C.c_void_p), ("per_point_dist_cmps", C.c_void_p)]
 
 
+PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8 = 0, 1
+
+
+class QuantParams(C.Structure):
+    """pann_quant_params: Euclidian_Point<uint8_t>::parameters (slope, offset) / Quantized_Mips_Point<8>::parameters (max_val)."""
+    _fields_ = [("kind", C.c_int32), ("dims", C.c_int32), ("slope", C.c_float), ("offset", C.c_int32),
+                ("max_val", C.c_float), ("min_seen", C.c_float), ("max_seen", C.c_float)]
+
+    @property
+    def identity(self):
+        return self.slope == 1.0 and self.offset == 0
+
+
 # every symbol include/pann.h declares: (restype, argtypes)
 SIGNATURES = {
     "pann_abi_version": (C.c_int, []),
@@ -116,6 +129,17 @@ SIGNATURES = {
     "pann_hcnng_assemble_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "pann_bruteforce_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
                                       C.c_void_p]),
+    "pann_index_normalize": (C.c_int, [C.c_void_p]),
+    "pann_quantize_params": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(QuantParams)]),
+    "pann_quantize_params_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                           C.POINTER(QuantParams), C.c_void_p]),
+    "pann_index_create_quantized": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.POINTER(QuantParams), C.c_int]),
+    "pann_quantize_rows": (C.c_int, [C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p,
+                                     C.c_uint64, C.c_int]),
+    "pann_quantize_rows_dev": (C.c_int, [C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int, C.c_void_p,
+                                         C.c_uint64, C.c_void_p]),
+    "pann_index_download_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "pann_quantize_select_ranks": (None, [C.c_uint64, C.c_int, u64p, u64p]),
 }
 
 _lib = None

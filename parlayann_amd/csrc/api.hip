@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cmath>
 #include <cstring>
+#include <mutex>
 #include <vector>
 
 #include "pann_internal.h"
@@ -1135,6 +1136,165 @@ int pann_hcnng_build(pann_index* idx, uint32_t num_clusters, uint32_t cluster_si
   DeviceGuard g(idx->device);
   idx->ix.codes_valid = 0;
   return hcnng_build_dev(idx->ix, idx->ws2, idx->stream, num_clusters, cluster_size, mst_deg, seed, times3);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// scalar quantisation on the device (quantize.hip)
+// ---------------------------------------------------------------------------------------------
+
+namespace {
+
+int check_quant_kind(int kind, const char* fn) {
+  if (kind != PANN_QUANT_EUCLID_U8 && kind != PANN_QUANT_MIPS_I8) { set_error(std::string(fn) + ": unknown quantisation kind"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+int check_quant_rows(const float* rows, uint64_t n, uint32_t d, uint64_t stride, const char* fn) {
+  if (!rows || n == 0 || d == 0) { set_error(std::string(fn) + ": null/empty rows (n * d == 0)"); return PANN_ERR_BAD_ARG; }
+  if (stride < 4ull * d || stride % 4 != 0) { set_error(std::string(fn) + ": row stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+int check_quant_params(const pann_quant_params* p, const char* fn) {
+  if (!p) { set_error(std::string(fn) + ": null parameters"); return PANN_ERR_BAD_ARG; }
+  if (int rc = check_quant_kind(p->kind, fn)) return rc;
+  if (p->dims <= 0) { set_error(std::string(fn) + ": parameters without dimensions"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+int check_quant_source(const pann_index* src, int kind, const char* fn) {
+  if (int rc = check_idx(src, fn)) return rc;
+  if (src->ix.dtype != PANN_F32) { set_error(std::string(fn) + ": the source index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
+  if (int rc = check_quant_kind(kind, fn)) return rc;
+  if ((kind == PANN_QUANT_EUCLID_U8) != (src->ix.metric == PANN_L2)) {
+    set_error(std::string(fn) + ": kind does not fit the index's metric (EUCLID_U8 <-> L2, MIPS_I8 <-> MIPS)"); return PANN_ERR_BAD_ARG;
+  }
+  return PANN_OK;
+}
+
+// scratch of the handle-less _dev form: one small buffer per device, allocated on first use; the lock is held for the call
+// (pann_quantize_params_dev synchronises anyway)
+std::mutex g_qscratch_mu;
+DevBuf g_qscratch[64];
+
+}  // namespace
+
+extern "C" {
+
+void pann_quantize_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b) {
+  if (!a || !b || len == 0) return;
+  quant_select_ranks(len, trim, a, b);
+}
+
+int pann_index_normalize(pann_index* idx) {
+  if (int rc = check_idx(idx, "pann_index_normalize")) return rc;
+  DeviceIndex& ix = idx->ix;
+  if (ix.dtype != PANN_F32) { set_error("pann_index_normalize: float (PANN_F32) handles only"); return PANN_ERR_UNSUPPORTED; }
+  DeviceGuard g(idx->device);
+  if (int rc = quant_normalize_dev(reinterpret_cast<const float*>(ix.points), ix.n, ix.d, ix.pstride, nullptr, ix.points, ix.pstride, idx->stream)) return rc;
+  PANN_HIP(hipStreamSynchronize(idx->stream));
+  return PANN_OK;
+}
+
+int pann_quantize_params(pann_index* src, int kind, int trim, pann_quant_params* out) {
+  if (int rc = check_quant_source(src, kind, "pann_quantize_params")) return rc;
+  if (!out) { set_error("pann_quantize_params: null output"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(src->device);
+  if (int rc = src->stage[8].ensure(quant_scratch_bytes())) return rc;
+  const DeviceIndex& ix = src->ix;
+  return quant_params_dev(reinterpret_cast<const float*>(ix.points), ix.n, ix.d, ix.pstride, kind, trim, out, src->stage[8].p, src->stream);
+}
+
+int pann_quantize_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride_bytes, int kind, int trim,
+                             pann_quant_params* out, void* stream) {
+  if (int rc = check_quant_kind(kind, "pann_quantize_params_dev")) return rc;
+  if (int rc = check_quant_rows(d_rows, n, d, stride_bytes, "pann_quantize_params_dev")) return rc;
+  if (!out) { set_error("pann_quantize_params_dev: null output"); return PANN_ERR_BAD_ARG; }
+  int dev = 0;
+  PANN_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) { set_error("pann_quantize_params_dev: device ordinal out of range"); return PANN_ERR_BAD_ARG; }
+  std::lock_guard<std::mutex> lk(g_qscratch_mu);
+  if (int rc = g_qscratch[dev].ensure(quant_scratch_bytes())) return rc;
+  return quant_params_dev(d_rows, n, d, stride_bytes, kind, trim, out, g_qscratch[dev].p, (hipStream_t)stream);
+}
+
+int pann_index_create_quantized(pann_index** out, pann_index* src, const pann_quant_params* p, int copy_graph) {
+  if (!out) { set_error("pann_index_create_quantized: null output"); return PANN_ERR_BAD_ARG; }
+  if (int rc = check_quant_params(p, "pann_index_create_quantized")) return rc;
+  if (int rc = check_quant_source(src, p->kind, "pann_index_create_quantized")) return rc;
+  const DeviceIndex& sx = src->ix;
+  if ((uint32_t)p->dims != sx.d) { set_error("pann_index_create_quantized: parameters made for another dimension"); return PANN_ERR_BAD_ARG; }
+  const bool eu = p->kind == PANN_QUANT_EUCLID_U8;
+  pann_index* q = nullptr;
+  if (int rc = index_create_impl(&q, nullptr, sx.n, sx.d, eu ? PANN_U8 : PANN_I8, sx.d, eu ? PANN_L2 : PANN_MIPS, nullptr, sx.max_deg, src->device)) return rc;
+  DeviceGuard g(src->device);
+  auto fail = [&](int rc) { pann_index_destroy(q); return rc; };
+  // the new handle's rows are zero (pad bytes included) and its stream is idle; src's stream orders the reads of src
+  if (int rc = quant_translate_dev(p, reinterpret_cast<const float*>(sx.points), sx.n, sx.d, sx.pstride, q->ix.points, q->ix.pstride, src->stream)) return fail(rc);
+  hipError_t e;
+  if (copy_graph && (e = hipMemcpyAsync(q->ix.graph, sx.graph, (size_t)sx.n * sx.gstride * 4, hipMemcpyDeviceToDevice, src->stream)) != hipSuccess)
+    return fail(hip_fail(e, "hipMemcpyAsync(graph)"));
+  if ((e = hipStreamSynchronize(src->stream)) != hipSuccess) return fail(hip_fail(e, "hipStreamSynchronize"));
+  *out = q;
+  return PANN_OK;
+}
+
+int pann_quantize_rows_dev(const pann_quant_params* p, const float* d_rows, uint64_t n, uint64_t stride_bytes,
+                           int normalize_first, void* d_out, uint64_t out_stride_bytes, void* stream) {
+  if (int rc = check_quant_params(p, "pann_quantize_rows_dev")) return rc;
+  if (int rc = check_quant_rows(d_rows, n, (uint32_t)p->dims, stride_bytes, "pann_quantize_rows_dev")) return rc;
+  if (!d_out) { set_error("pann_quantize_rows_dev: null output"); return PANN_ERR_BAD_ARG; }
+  if (out_stride_bytes < (uint64_t)p->dims) { set_error("pann_quantize_rows_dev: output stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  if (normalize_first) return quant_normalize_dev(d_rows, n, (uint32_t)p->dims, stride_bytes, p, d_out, out_stride_bytes, (hipStream_t)stream);
+  return quant_translate_dev(p, d_rows, n, (uint32_t)p->dims, stride_bytes, d_out, out_stride_bytes, (hipStream_t)stream);
+}
+
+int pann_quantize_rows(const pann_quant_params* p, const float* rows, uint64_t n, uint64_t stride_bytes, int normalize_first,
+                       void* out, uint64_t out_stride_bytes, int device) {
+  if (int rc = check_quant_params(p, "pann_quantize_rows")) return rc;
+  const uint32_t d = (uint32_t)p->dims;
+  if (int rc = check_quant_rows(rows, n, d, stride_bytes, "pann_quantize_rows")) return rc;
+  if (!out) { set_error("pann_quantize_rows: null output"); return PANN_ERR_BAD_ARG; }
+  if (out_stride_bytes < d) { set_error("pann_quantize_rows: output stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  const int ndev = pann_device_count();
+  if (ndev <= 0) { set_error("pann_quantize_rows: no HIP device visible (this library has no CPU path)"); return PANN_ERR_NO_DEVICE; }
+  if (device < 0 || device >= ndev) { set_error("pann_quantize_rows: device ordinal out of range"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(device);
+  if (!g.ok) { set_error("pann_quantize_rows: hipSetDevice failed"); return PANN_ERR_HIP; }
+  // dense device copies of a slice of rows at a time (query sets are small; a base that is not resident streams through here)
+  const uint64_t slice = std::max<uint64_t>(1, (256ull << 20) / (4ull * d));
+  DevBuf in, ob;
+  auto done = [&](int rc) { in.release(); ob.release(); return rc; };
+  const uint64_t cap = std::min(slice, n);
+  if (int rc = in.ensure(cap * d * 4)) return done(rc);
+  if (int rc = ob.ensure(cap * d)) return done(rc);
+  for (uint64_t r0 = 0; r0 < n; r0 += slice) {
+    const uint64_t cnt = std::min(slice, n - r0);
+    hipError_t e = hipMemcpy2D(in.p, (size_t)d * 4, (const uint8_t*)rows + r0 * stride_bytes, stride_bytes, (size_t)d * 4, cnt, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(rows)"));
+    if (int rc = pann_quantize_rows_dev(p, in.as<float>(), cnt, (uint64_t)d * 4, normalize_first, ob.p, d, nullptr)) return done(rc);
+    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
+    e = hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ob.p, d, d, cnt, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(out)"));
+  }
+  return done(PANN_OK);
+}
+
+int pann_index_download_points(pann_index* idx, uint64_t first_row, uint64_t nrows, void* out, uint64_t out_stride_bytes) {
+  if (int rc = check_idx(idx, "pann_index_download_points")) return rc;
+  if (nrows == 0) return PANN_OK;
+  const DeviceIndex& ix = idx->ix;
+  if (!out) { set_error("pann_index_download_points: null output"); return PANN_ERR_BAD_ARG; }
+  if (first_row > ix.n || nrows > ix.n - first_row) { set_error("pann_index_download_points: row range outside the index"); return PANN_ERR_BAD_ARG; }
+  if (out_stride_bytes < ix.dbytes) { set_error("pann_index_download_points: row stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  PANN_HIP(hipStreamSynchronize(idx->stream));
+  const uint64_t slice = std::max<uint64_t>(1, (1ull << 30) / std::max<uint64_t>(out_stride_bytes, 1));
+  for (uint64_t r0 = 0; r0 < nrows; r0 += slice) {
+    const uint64_t cnt = std::min(slice, nrows - r0);
+    PANN_HIP(hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ix.points + (first_row + r0) * ix.pstride, ix.pstride,
+                         ix.dbytes, cnt, hipMemcpyDeviceToHost));
+  }
+  return PANN_OK;
 }
 
 }  // extern "C"

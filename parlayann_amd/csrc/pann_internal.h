@@ -138,6 +138,17 @@ int range_search_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const
                      int starts_per_query, float radius_2, uint32_t cap, uint32_t* d_out_ids, uint32_t* d_out_counts,
                      uint32_t* d_out_cmps, uint32_t* d_out_trunc);
 
+// quantize.hip: scalar quantisation of f32 rows (n rows of d floats, row stride in bytes, a multiple of 4)
+size_t quant_scratch_bytes();                                     // device scratch quant_params_dev needs
+void quant_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b);
+int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, int kind, int trim, pann_quant_params* out,
+                     void* scratch, hipStream_t st);               // synchronises st (reads a few words back)
+int quant_translate_dev(const pann_quant_params* p, const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, void* d_out,
+                        uint64_t out_stride, hipStream_t st);
+// p == nullptr: normalised f32 rows to d_out (may be d_rows: in place); else normalise and translate, bytes to d_out
+int quant_normalize_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, const pann_quant_params* p, void* d_out,
+                        uint64_t out_stride, hipStream_t st);
+
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,
                     uint32_t mst_deg, uint64_t seed, double* times3, uint32_t first_tree = 0, uint32_t tree_step = 1,

@@ -27,19 +27,20 @@ class GraphIndex:
             raise RuntimeError("graph size and point size do not match")
         self.use_quantization = np.dtype(self.T).itemsize > 1     # :86
         self.q_index = None
-        pts = self.points
+        self.device = device
+        # the float base goes to the device once; normalize, generate_parameters and translate_point run there (csrc/quantize.hip)
+        self.index = DeviceIndex(self.points, self.graph, metric=self.metric, device=device)
         if self.use_quantization:
             if self.metric == "Euclidian":
-                self.eparams = quantize.euclid_u8_params(pts)                        # EQuantRange(Points) :90
-                qpts = quantize.euclid_u8_translate(pts, self.eparams)
-                self.q_index = DeviceIndex(qpts, self.graph, metric="Euclidian", device=device)
+                self.q_index, self.qparams = self.index.quantized("euclid_u8")       # EQuantRange(Points) :90
+                self.eparams = quantize.EuclidParams.__new__(quantize.EuclidParams)
+                self.eparams.range, self.eparams.dims = 255, self.qparams.dims
+                self.eparams.slope, self.eparams.offset = np.float32(self.qparams.slope), np.int32(self.qparams.offset)
             else:
-                pts = quantize.normalize_rows(pts)                                   # :94-95
-                self.points = pts
-                self.mmax = quantize.mips_i8_max_val(pts, trim=True)                 # Quantized_Mips_Point<8,true> :69
-                qpts = quantize.mips_i8_translate(pts, self.mmax)
-                self.q_index = DeviceIndex(qpts, self.graph, metric="mips", device=device)
-        self.index = DeviceIndex(pts, self.graph, metric=self.metric, device=device)
+                self.index.normalize()                                               # :94-95
+                self.points = self.index.points()
+                self.q_index, self.qparams = self.index.quantized("mips_i8", trim=True)   # Quantized_Mips_Point<8,true> :69
+                self.mmax = np.float32(self.qparams.max_val)
 
     # QueryParams(knn, beam, 1.35, visit_limit, min(maxDeg, 3*visit_limit))   (:198,:222,:242)
     def _qp(self, knn, beam_width, visit_limit):
@@ -54,7 +55,7 @@ class GraphIndex:
             self._need(r["frontier_size"], knn)
             return r["ids"], r["dists"]
         if self.metric == "Euclidian":
-            qq = quantize.euclid_u8_translate(queries, self.eparams)
+            qq = quantize.device_quantize_rows(queries, self.qparams, device=self.device)
             if self.eparams.identity:                                            # slope == 1: plain search on the u8 copy (:148-152)
                 r = self.q_index.batch_search(qq, out_k=knn, **qp)
                 self._need(r["frontier_size"], knn)
@@ -62,7 +63,7 @@ class GraphIndex:
             full_q = queries
         else:
             full_q = quantize.normalize_rows(queries)                            # q.normalize() :172
-            qq = quantize.mips_i8_translate(full_q, self.mmax)
+            qq = quantize.device_quantize_rows(queries, self.qparams, normalize_first=True, device=self.device)
         # beam_search_rerank (beamSearch.h:390-454): search the quantised copy, re-score the first
         # min(k * rerank_factor, |beam|) with exact distances, sort, keep k
         r = self.q_index.batch_search(qq, out_k=beam_width, **qp)

@@ -8,8 +8,8 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I8, PANN_L2, PANN_MIPS, PANN_U8, BuildStats, QueryParams, SearchOut,
-                    check)
+from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I8, PANN_L2, PANN_MIPS, PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_U8,
+                    BuildStats, QuantParams, QueryParams, SearchOut, check)
 from .bf16 import bfloat16
 
 _DT = {np.dtype(np.uint8): PANN_U8, np.dtype(np.int8): PANN_I8, np.dtype(np.float32): PANN_F32,
@@ -29,6 +29,17 @@ def _metric_code(metric):
     if m in ("mips", "ip"):
         return PANN_MIPS
     raise ValueError(f"unknown metric {metric!r}")
+
+
+def quant_kind(kind):
+    if kind in (PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8):
+        return kind
+    k = str(kind).lower()
+    if k in ("euclid_u8", "euclidian_u8", "u8"):
+        return PANN_QUANT_EUCLID_U8
+    if k in ("mips_i8", "i8"):
+        return PANN_QUANT_MIPS_I8
+    raise ValueError(f"unknown quantisation kind {kind!r}")
 
 
 def _row_stride(a):
@@ -192,6 +203,37 @@ class DeviceIndex:
         g = np.empty((self.n, self.max_degree + 1), dtype=np.uint32)
         check(self._lib.pann_index_get_graph(self._h, _ptr(g)))
         return g
+
+    # ---- points: download, normalize, scalar quantisation on the device (csrc/quantize.hip) ----
+    def points(self, first_row=0, nrows=None):
+        """pann_index_download_points: rows [first_row, first_row + nrows) of the device slab as an nrows x d array"""
+        nrows = self.n - first_row if nrows is None else nrows
+        out = np.empty((nrows, self.d), dtype=self.dtype)
+        check(self._lib.pann_index_download_points(self._h, first_row, nrows, _ptr(out), _row_stride(out)))
+        return out
+
+    def normalize(self):
+        """Point::normalize (mips_point.h:115-124) for every row, in place on the device; float32 handles only"""
+        check(self._lib.pann_index_normalize(self._h))
+
+    def quantize_params(self, kind, trim=True):
+        """generate_parameters (euclidian_point.h:211-235 / mips_point.h:433-486) over the device slab -> QuantParams"""
+        p = QuantParams()
+        check(self._lib.pann_quantize_params(self._h, quant_kind(kind), 1 if trim else 0, C.byref(p)))
+        return p
+
+    def quantized(self, kind, trim=True, params=None, copy_graph=True):
+        """QPR Q_Points(Points): -> (DeviceIndex of uint8 / int8 rows translated on the device, QuantParams).  kind:
+        "euclid_u8" | "mips_i8"; params: translate with these instead of generating them from this index's rows."""
+        p = self.quantize_params(kind, trim) if params is None else params
+        h = C.c_void_p()
+        check(self._lib.pann_index_create_quantized(C.byref(h), self._h, C.byref(p), 1 if copy_graph else 0))
+        q = DeviceIndex.__new__(DeviceIndex)
+        q.n, q.d, q.max_degree = self.n, self.d, self.max_degree
+        eu = p.kind == PANN_QUANT_EUCLID_U8
+        q.dtype, q.metric = np.dtype(np.uint8 if eu else np.int8), (PANN_L2 if eu else PANN_MIPS)
+        q._h, q._lib = h, self._lib
+        return q, p
 
     # ---- batched beam search: the searchAll / qsearchAll seam (beamSearch.h:374,556) ----
     def batch_search(self, queries=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),

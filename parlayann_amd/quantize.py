@@ -82,3 +82,29 @@ def mips_i8_translate(x, max_val, rng=255):
     v = _round_half_away(x * scale)
     v = np.where(x < -F(max_val), -half, np.where(x > F(max_val), half, v))
     return v.astype(np.int8)
+
+
+# ---- device counterparts (csrc/quantize.hip through the C-ABI): bit-identical to the reference's loops, std::round included ----
+
+def device_quantize_rows(x, params, normalize_first=False, device=0):
+    """Q_Query_Points(Query_Points, Q_Points.params): float rows -> uint8 (Euclid) / int8 (MIPS) rows, translated on the device
+    with the QuantParams of DeviceIndex.quantized(); normalize_first: every row goes through Point::normalize first."""
+    import ctypes as C
+
+    from . import _capi
+    x = np.ascontiguousarray(x, dtype=F)
+    if x.ndim != 2 or x.shape[1] != params.dims:
+        raise ValueError(f"rows must be n x {params.dims} float32")
+    out = np.empty(x.shape, np.uint8 if params.kind == _capi.PANN_QUANT_EUCLID_U8 else np.int8)
+    if len(x):
+        _capi.check(_capi.load().pann_quantize_rows(C.byref(params), x.ctypes.data_as(C.c_void_p), len(x), x.shape[1] * 4,
+                                                    1 if normalize_first else 0, out.ctypes.data_as(C.c_void_p), x.shape[1],
+                                                    device))
+    return out
+
+
+def device_params(kind, dims, slope=1.0, offset=0, max_val=0.0):
+    """QuantParams from known values (parameters read from elsewhere, tests)"""
+    from . import _capi
+    from .index import quant_kind
+    return _capi.QuantParams(kind=quant_kind(kind), dims=dims, slope=float(F(slope)), offset=int(offset), max_val=float(F(max_val)))
