@@ -315,7 +315,8 @@ __global__ void __launch_bounds__(256) dense_topk_kernel(DenseArgs A) {
 //   L2 : |a|^2 + |b|^2 - 2 a.b      MIPS : -a.b
 // with the row norms summed in f32 while the tiles are staged.  On integer-valued data every
 // product and partial sum is exact, so the result is bit-identical to the VALU path; on real-valued
-// data the norm form differs from sum((a-b)^2) by cancellation error (DESIGN.md "float order").
+// data the norm form differs from sum((a-b)^2) by cancellation error (bound: DESIGN.md "Float summation order") and is
+// clamped at 0: its three sums round in different orders, so equal rows would come out a few ulp of |a|^2 + |b|^2 below zero.
 typedef _Float16 mf_half8 __attribute__((ext_vector_type(8)));
 typedef __bf16 mf_bf8 __attribute__((ext_vector_type(8)));
 typedef float mf_float4 __attribute__((ext_vector_type(4)));
@@ -427,7 +428,7 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
         const uint32_t bc = t * 16 + (lane & 15);
         const uint32_t bid = Bid[bc];
         float dist;
-        if constexpr (METRIC == PANN_L2) dist = (an + Bn[bc]) - 2.0f * acc[t][r];
+        if constexpr (METRIC == PANN_L2) dist = fmaxf((an + Bn[bc]) - 2.0f * acc[t][r], 0.f);   // (norm form: never below 0)
         else dist = -acc[t][r];
         bool ok = (bc < nb_tile) && (ar < na_tile);
         if (A.exclude_same_id) ok = ok && (bid != Aid[ar]);
@@ -468,7 +469,7 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
         const uint32_t bc = t * 16 + (lane & 15);
         const uint32_t bid = Bid[bc];
         float dist;
-        if constexpr (METRIC == PANN_L2) dist = (an + Bn[bc]) - 2.0f * acc[t][r];
+        if constexpr (METRIC == PANN_L2) dist = fmaxf((an + Bn[bc]) - 2.0f * acc[t][r], 0.f);   // (norm form: never below 0)
         else dist = -acc[t][r];
         key[r][t] = make_key(dist, bid);
         bool ok = (bc < nb_tile) && (ar < na_tile);
@@ -912,12 +913,15 @@ __device__ __forceinline__ void gt_flush(GtSel<NR>& S, const uint64_t* Qw /* thi
 // are empty and a row receives at most 4 x 16 keys from one tile, so pass 2 always fits (GT_QCAP >= 64).
 // NEG: d holds NEGATED distances (the matrix-core kernel computes 2 a.b - (|a|^2 + |b|^2) = -dist with one add and one fma per
 // element and no sign flip of the accumulators; the test is d >= -tau, the sign modifier of the compare is free).
-template <int NR, bool NEG = false>
+// CLAMP0: an L2 distance in the norm form |a|^2 + |b|^2 - 2 a.b, whose three sums are rounded in different orders, can come out
+// a few ulp of |a|^2 + |b|^2 BELOW zero for (nearly) equal rows: the key that is queued is clamped at 0.  The float test above
+// it needs no clamp -- every key in a list is >= 0 then, so tau >= 0 and a value below zero passes exactly when 0 passes.
+template <int NR, bool NEG = false, bool CLAMP0 = false>
 __device__ __forceinline__ void gt_select_queued(GtSel<NR>& S, const float (&d)[4][4], const uint32_t (&bid)[4], const uint32_t (&skip)[4],
                                                  uint32_t pplace, uint32_t* gtau_mine, uint32_t nsplit, uint64_t* Qw, int lane) {
   const int q = lane >> 4;
   auto pass = [&](int r, int t) -> bool { return NEG ? (d[r][t] >= -S.tauf[r]) : (d[r][t] <= S.tauf[r]); };
-  auto dist = [&](int r, int t) -> float { return NEG ? -d[r][t] : d[r][t]; };
+  auto dist = [&](int r, int t) -> float { const float v = NEG ? -d[r][t] : d[r][t]; return CLAMP0 ? fmaxf(v, 0.f) : v; };
   // the common case -- no survivor in the wave's 16 x 64 distances -- is 16 compares whose masks are OR-ed on the scalar side
   // (per row set r first: a wave-tile with a survivor has one in 1.2 of its 4 row sets on average -- 2.4 of 16 groups -- and the
   //  other row sets are skipped on their mask, a scalar test, instead of 4 x (6 vector instructions + a branch) each)
@@ -1142,7 +1146,7 @@ __global__ void __launch_bounds__(256, PANN_GT_WGS) dense_gt_mfma_kernel(DenseAr
     for (int t = 0; t < 4; t++) { const float2 m2 = Bm[buf * DT_B + t * 16 + (lane & 15)]; bn[t] = m2.x; bid[t] = __float_as_uint(m2.y); }
     GT_COUNT(0, 1);
     auto distf = [&](int r, int t) -> float {
-      if constexpr (METRIC == PANN_L2) return (an[r] + bn[t]) - 2.0f * acc[t][r];
+      if constexpr (METRIC == PANN_L2) return fmaxf((an[r] + bn[t]) - 2.0f * acc[t][r], 0.f);
       else return -acc[t][r];
     };
     if constexpr (QUEUED) {
@@ -1164,7 +1168,7 @@ __global__ void __launch_bounds__(256, PANN_GT_WGS) dense_gt_mfma_kernel(DenseAr
           for (int t = 0; t < 4; t++) mx = fmaxf(mx, nd[r][t]);
         S.R[0][0] += (uint64_t)__float_as_uint(mx + __uint_as_float(bid[0])); }
 #else
-      gt_select_queued<NR, true>(S, nd, bid, skip, pplace, gtau_mine, A.nsplit, Qw, lane);
+      gt_select_queued<NR, true, METRIC == PANN_L2>(S, nd, bid, skip, pplace, gtau_mine, A.nsplit, Qw, lane);
 #endif
       // all four waves of the workgroup also empty their queues at the SAME tiles, every GT_FLUSH_EVERY-th: a wave that flushes
       // alone keeps its three siblings at the tile barrier for the whole flush (8 / 32 / 64 / 128 tiles: 10.3 / 10.1 / 10.15 /
