@@ -13,6 +13,8 @@
  *                                                                          -> pann_insert_batch
  *   algorithms/HCNNG/hcnng_index.h:145-181 MSTk all-pairs + per-row 10-NN  -> pann_leaf_knn
  *   data_tools/compute_groundtruth.cpp:22-59 brute-force kNN               -> pann_bruteforce_knn
+ *   data_tools/compute_range_groundtruth.cpp:13-29 brute-force radius join -> pann_bruteforce_range
+ *   algorithms/utils/beamSearch.h:567-614  RangeSearch (beam search + BFS)  -> pann_range_query
  *
  * The reference has no FFI of its own for this path (it is a header-only template library); these
  * entry points are what a cgo/ctypes/pybind binding placed at the parallel_for seams above would
@@ -307,7 +309,7 @@ int pann_index_set_stream(pann_index* idx, void* stream, int use_private);
 /* Per-handle tuning knobs; results never depend on them (0 = the library's own choice).  Unknown names: PANN_ERR_BAD_ARG.
  *   "forest_group": HCNNG -- the independent cluster trees (clusterEdge.h:146-153) are split level by level in groups of this
  *                   many trees (scratch: trees x n positions; default: as many as 2^31 positions allow)
- *   "gt_pieces"   : pann_bruteforce_knn -- the base is cut into this many pieces per 64-query tile (default: the count that
+ *   "gt_pieces"   : pann_bruteforce_knn, pann_bruteforce_range -- the base is cut into this many pieces per 64-query tile (default: the count that
  *                   fills whole rounds of the 256 CUs best)
  *   "locality_order": 1 (default) / 0 -- on tables beyond the Infinity Cache (> 1 GB of points) the Vamana builder launches the
  *                   searches of a batch ordered by the locality cell of the inserted point (nearest of 256 pivots, one pass per
@@ -348,6 +350,29 @@ int pann_hcnng_assemble_dev(pann_index* idx, const uint32_t* d_slabs, uint32_t n
  * out rows sorted by (dist,id). Host pointers. */
 int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes,
                         uint32_t k, uint32_t* out_ids, float* out_dists);
+
+/* compute_range_groundtruth (data_tools/compute_range_groundtruth.cpp:13-29): for each of nq external queries every base
+ * point with distance <= radius (the handle's distance: PANN_L2, or PANN_MIPS = -q.x, where the radius may be negative; == is
+ * inside), as CSR: ids of query i are out_ids[out_offsets[i] .. out_offsets[i + 1]), ascending, each once.  Host pointers.
+ * out_offsets: nq + 1 entries, always written (out_offsets[nq] = number of matches).  out_ids == NULL: count only.  Otherwise
+ * ids_capacity entries are available: fewer than out_offsets[nq] -> PANN_ERR_OVERFLOW, out_ids untouched, out_offsets valid.
+ * Exact for the one-byte types and in exact-float-order mode; in default mode a float distance within its rounding bound of
+ * the radius may fall on either side (DESIGN.md "Float summation order").  "gt_pieces" steers how the base is cut; results never
+ * depend on it.  NaN radius, NULL queries / out_offsets, a stride shorter than a row -> PANN_ERR_BAD_ARG; nq == 0 -> PANN_OK. */
+int pann_bruteforce_range(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, float radius,
+                          uint64_t* out_offsets, uint32_t* out_ids, uint64_t ids_capacity);
+
+/* RangeSearch (beamSearch.h:567-614) with its second round live: beam search with *qp from `starts` (shared), then the BFS of
+ * range_search (:245-306) seeded PER QUERY with that query's final frontier (all of it, in frontier order), radius_2 =
+ * radius.  Exactly one of queries / query_ids.  The queries go to the device once and the frontiers never leave it: results
+ * equal pann_batch_search (out_k = beam) followed by pann_range_search (starts_per_query) on its ids.
+ * out_ids: nq x max_results in BFS order; counts / truncated as pann_range_search; out_search_cmps / out_visited: the beam
+ * search's dist_cmps / visited_count; out_range_cmps: the BFS's comparisons.  Any of the last four may be NULL. */
+int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                     uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                     float radius, uint32_t max_results, uint32_t* out_ids, uint32_t* out_counts,
+                     uint32_t* out_search_cmps, uint32_t* out_visited, uint32_t* out_range_cmps,
+                     uint32_t* out_truncated);
 
 /* ---- scalar quantisation of a float index on the device --------------------------------------
  * The reference's translating PointRange constructor (point_range.h:54-72: generate_parameters + translate_point per row) and

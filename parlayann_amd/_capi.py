@@ -129,6 +129,11 @@ SIGNATURES = {
     "pann_hcnng_assemble_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "pann_bruteforce_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
                                       C.c_void_p]),
+    "pann_bruteforce_range": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p,
+                                        C.c_uint64]),
+    "pann_range_query": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                   C.POINTER(QueryParams), C.c_float, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_void_p]),
     "pann_index_normalize": (C.c_int, [C.c_void_p]),
     "pann_quantize_params": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(QuantParams)]),
     "pann_quantize_params_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int,

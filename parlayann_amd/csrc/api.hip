@@ -1108,6 +1108,141 @@ int pann_range_search(pann_index* idx, const void* queries, const uint32_t* quer
 }
 
 
+// a NULL handle where no device exists is the missing device, not a caller's mistake: the two entry points below say so
+static int check_idx_or_device(const pann_index* idx, const char* fn) {
+  if (!idx && pann_device_count() <= 0) { set_error(std::string(fn) + ": no HIP device visible (this library has no CPU path)"); return PANN_ERR_NO_DEVICE; }
+  return check_idx(idx, fn);
+}
+
+int pann_bruteforce_range(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, float radius,
+                          uint64_t* out_offsets, uint32_t* out_ids, uint64_t ids_capacity) {
+  if (int rc = check_idx_or_device(idx, "pann_bruteforce_range")) return rc;
+  if (std::isnan(radius)) { set_error("pann_bruteforce_range: radius is NaN"); return PANN_ERR_BAD_ARG; }
+  if (!out_offsets) { set_error("pann_bruteforce_range: null out_offsets"); return PANN_ERR_BAD_ARG; }
+  if (nq == 0) { out_offsets[0] = 0; return PANN_OK; }
+  if (!queries) { set_error("pann_bruteforce_range: null queries"); return PANN_ERR_BAD_ARG; }
+  if (q_stride_bytes < idx->ix.dbytes) { set_error("pann_bruteforce_range: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  hipStream_t st = idx->stream;
+  const DeviceIndex& ix = idx->ix;
+  if (int rc = idx->stage[2].ensure(nq * q_stride_bytes + 16)) return rc;
+  if (int rc = idx->stage[7].ensure((nq + 1) * 8)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + ix.dbytes, hipMemcpyHostToDevice, st));
+  const uint32_t nsplit = range_join_pieces(ix, nq, idx->gt_pieces);       // pann_index_set_option("gt_pieces")
+  if (int rc = range_join_count_dev(ix, idx->ws2, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nq, radius, nsplit,
+                                    idx->stage[7].as<uint64_t>())) return rc;
+  PANN_HIP(hipMemcpyAsync(out_offsets, idx->stage[7].p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  const uint64_t total = out_offsets[nq];
+  if (!out_ids) return PANN_OK;                                            // count only
+  if (ids_capacity < total) {
+    set_error("pann_bruteforce_range: " + std::to_string(total) + " matches, room for " + std::to_string(ids_capacity));
+    return PANN_ERR_OVERFLOW;
+  }
+  if (total == 0) return PANN_OK;
+  if (int rc = idx->stage[6].ensure(total * 4)) return rc;
+  if (int rc = range_join_fill_dev(ix, idx->ws2, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nq, radius, nsplit,
+                                   idx->stage[6].as<uint32_t>())) return rc;
+  PANN_HIP(hipMemcpyAsync(out_ids, idx->stage[6].p, total * 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  return PANN_OK;
+}
+
+int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                     uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                     float radius, uint32_t max_results, uint32_t* out_ids, uint32_t* out_counts,
+                     uint32_t* out_search_cmps, uint32_t* out_visited, uint32_t* out_range_cmps,
+                     uint32_t* out_truncated) {
+  if (int rc = check_idx_or_device(idx, "pann_range_query")) return rc;
+  const DeviceIndex& ix = idx->ix;
+  if (!qp) { set_error("pann_range_query: null params"); return PANN_ERR_BAD_ARG; }
+  if (qp->k > qp->beam) {  // beamSearch.h:368-372, :549-553
+    set_error("Error: beam search parameter Q = " + std::to_string(qp->beam) + " same size or smaller than k = " + std::to_string(qp->k));
+    return PANN_ERR_BAD_ARG;
+  }
+  if (qp->beam < 1 || qp->beam > 0x7FFFFFFF) { set_error("pann_range_query: beam out of range"); return PANN_ERR_BAD_ARG; }
+  if ((queries == nullptr) == (query_ids == nullptr)) { set_error("pann_range_query: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
+  if (!starts || nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
+  if (std::isnan(radius) || !out_ids || !out_counts || max_results == 0) { set_error("pann_range_query: null, empty or NaN argument"); return PANN_ERR_BAD_ARG; }
+  if (queries && q_stride_bytes < ix.dbytes) { set_error("pann_range_query: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  for (uint32_t i = 0; i < nstarts; i++)
+    if (starts[i] >= ix.n) { set_error("pann_range_query: start point out of range"); return PANN_ERR_BAD_ARG; }
+  if (query_ids)
+    for (uint64_t i = 0; i < nq; i++)
+      if (query_ids[i] >= ix.n) { set_error("pann_range_query: query id out of range"); return PANN_ERR_BAD_ARG; }
+  if (nq == 0) return PANN_OK;
+  DeviceGuard g(idx->device);
+  hipStream_t st = idx->stream;
+  const uint32_t beam = (uint32_t)qp->beam;
+  // ---- inputs go up once: the queries (or their ids) and the shared starts ----
+  const size_t qbytes = queries ? nq * q_stride_bytes + 16 : nq * 4;
+  if (int rc = idx->stage[2].ensure(qbytes)) return rc;
+  if (int rc = idx->stage[3].ensure((size_t)nstarts * 4)) return rc;
+  if (int rc = idx->stage[8].ensure(nq * (uint64_t)beam * 4)) return rc;      // the frontiers: never leave the device
+  if (int rc = idx->stage[9].ensure(nq * 4)) return rc;                       // dist_cmps of the beam search
+  if (int rc = idx->stage[10].ensure(nq * 4)) return rc;                      // visited_count
+  if (int rc = idx->stage[4].ensure(nq * (uint64_t)max_results * 4)) return rc;
+  if (int rc = idx->stage[5].ensure(nq * 4)) return rc;
+  if (int rc = idx->stage[6].ensure(nq * 4)) return rc;
+  if (int rc = idx->stage[7].ensure(nq * 4)) return rc;
+  if (queries) PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + ix.dbytes, hipMemcpyHostToDevice, st));
+  else PANN_HIP(hipMemcpyAsync(idx->stage[2].p, query_ids, nq * 4, hipMemcpyHostToDevice, st));
+  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, starts, (size_t)nstarts * 4, hipMemcpyHostToDevice, st));
+  const uint8_t* d_q = queries ? idx->stage[2].as<uint8_t>() : nullptr;
+  const uint32_t* d_qid = queries ? nullptr : idx->stage[2].as<uint32_t>();
+  // ---- round 1: the beam search; a launch that reports a full dropped list is grown and repeated (as batch_search_host) ----
+  constexpr uint64_t kDropBudget = 1ull << 30;
+  constexpr uint32_t kDropKeep = 2048;
+  const uint64_t dneed = (uint64_t)std::min<int64_t>(std::max<int64_t>(qp->limit, 1), (int64_t)ix.n);
+  uint32_t dcap = idx->dcap;
+  for (;;) {
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, kDropBudget / ((uint64_t)std::max<uint32_t>(dcap, 64) * 8)));
+    uint32_t status = 0;
+    for (uint64_t q0 = 0; q0 < nq && !(status & PANN_STATUS_DROPPED_OVERFLOW); q0 += chunk) {
+      const uint64_t cnt = std::min(chunk, nq - q0);
+      SearchArgs a;
+      a.queries = d_q ? d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
+      a.query_ids = d_qid ? d_qid + q0 : nullptr;
+      a.nq = cnt; a.starts = idx->stage[3].as<uint32_t>(); a.nstarts = nstarts;
+      a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
+      a.dcap = dcap;
+      a.out = pann_search_out{};
+      a.out.ids = idx->stage[8].as<uint32_t>() + q0 * beam; a.out.out_k = beam;
+      a.out.dist_cmps = idx->stage[9].as<uint32_t>() + q0;
+      a.out.visited_count = idx->stage[10].as<uint32_t>() + q0;
+      if (int rc = idx->ws.ensure(search_workspace_bytes(ix, a))) return rc;
+      if (int rc = launch_beam_search(ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
+      uint32_t st_word = 0;      // the launch's status word (the next launch clears it)
+      PANN_HIP(hipMemcpyAsync(&st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
+      PANN_HIP(hipStreamSynchronize(st));
+      status |= st_word;
+    }
+    if (!(status & PANN_STATUS_DROPPED_OVERFLOW)) break;
+    if ((uint64_t)dcap >= dneed) { set_error("pann_range_query: internal dropped-list overflow"); return PANN_ERR_OVERFLOW; }
+    dcap = (uint32_t)std::min<uint64_t>((uint64_t)dcap * 8, (dneed + 63) / 64 * 64);
+  }
+  idx->dcap = std::max(idx->dcap, std::min(dcap, kDropKeep));
+  // ---- round 2: the BFS, seeded per query with its frontier as it lies on the device (SENTINEL padding is skipped) ----
+  if (int rc = range_search_dev(ix, idx->ws, st, d_q, q_stride_bytes, d_qid, nq, idx->stage[8].as<uint32_t>(), beam, 1, radius,
+                                max_results, idx->stage[4].as<uint32_t>(), idx->stage[5].as<uint32_t>(), idx->stage[6].as<uint32_t>(),
+                                idx->stage[7].as<uint32_t>())) return rc;
+  PANN_HIP(hipMemcpyAsync(out_counts, idx->stage[5].p, nq * 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  uint32_t widest = 0;
+  for (uint64_t i = 0; i < nq; i++) widest = std::max(widest, out_counts[i]);
+  widest = std::min(widest, max_results);
+  if (widest)         // only the columns any query filled come back (entries past a row's count are unspecified)
+    PANN_HIP(hipMemcpy2DAsync(out_ids, (size_t)max_results * 4, idx->stage[4].p, (size_t)max_results * 4, (size_t)widest * 4, nq,
+                              hipMemcpyDeviceToHost, st));
+  if (out_search_cmps) PANN_HIP(hipMemcpyAsync(out_search_cmps, idx->stage[9].p, nq * 4, hipMemcpyDeviceToHost, st));
+  if (out_visited) PANN_HIP(hipMemcpyAsync(out_visited, idx->stage[10].p, nq * 4, hipMemcpyDeviceToHost, st));
+  if (out_range_cmps) PANN_HIP(hipMemcpyAsync(out_range_cmps, idx->stage[6].p, nq * 4, hipMemcpyDeviceToHost, st));
+  if (out_truncated) PANN_HIP(hipMemcpyAsync(out_truncated, idx->stage[7].p, nq * 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  if (idx->ws.bytes > (2ull << 30)) idx->ws.release();          // a one-off worst-case scratch is not kept on the handle
+  return PANN_OK;
+}
+
 int pann_hcnng_build_trees_dev(pann_index* idx, uint32_t first_tree, uint32_t tree_step, uint32_t ntrees, uint32_t cluster_size,
                                uint32_t mst_deg, uint64_t seed, uint32_t* d_slab, uint32_t slab_stride, double* times3) {
   if (int rc = check_idx(idx, "pann_hcnng_build_trees_dev")) return rc;

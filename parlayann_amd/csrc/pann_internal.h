@@ -138,6 +138,14 @@ int range_search_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const
                      int starts_per_query, float radius_2, uint32_t cap, uint32_t* d_out_ids, uint32_t* d_out_counts,
                      uint32_t* d_out_cmps, uint32_t* d_out_trunc);
 
+// range_gt.hip: dense radius join (every point within `radius` of every external query, CSR, ids ascending).  Two calls that
+// share `ws`: count (pass 1 + scan -> d_offsets, nq + 1 entries) and fill (pass 2 -> d_out_ids); nothing else may use ws between.
+uint32_t range_join_pieces(const DeviceIndex& ix, uint64_t nq, uint32_t wanted);
+int range_join_count_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq,
+                         float radius, uint32_t nsplit, uint64_t* d_offsets);
+int range_join_fill_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq,
+                        float radius, uint32_t nsplit, uint32_t* d_out_ids);
+
 // quantize.hip: scalar quantisation of f32 rows (n rows of d floats, row stride in bytes, a multiple of 4)
 size_t quant_scratch_bytes();                                     // device scratch quant_params_dev needs
 void quant_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b);

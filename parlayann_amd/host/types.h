@@ -1,5 +1,5 @@
 // types.h -- host mirror of algorithms/utils/types.h (QueryParams :218-231, BuildParams :154-215,
-// groundTruth :38-107).  Same field names, constructor argument orders and defaults.
+// groundTruth :38-107, RangeGroundTruth :109-151, RangeParams :233-245).  Same field names, constructor argument orders and defaults.
 #pragma once
 #include <cstdint>
 #include <cstdio>
@@ -94,6 +94,60 @@ struct groundTruth {
   float distances(long i, long j) const { return dists[(size_t)i * dim + j]; }
   size_t size() const { return (size_t)n; }
   long dimension() const { return dim; }
+};
+
+// range ground truth file: [n:i32][num_matches:i32][sizes n x i32][ids num_matches x i32]   (types.h:119-140; written by
+// compute_range_groundtruth.cpp:64-88).  operator[] gives the matches of query i as a (begin, end) range.
+template <typename T>
+struct RangeGroundTruth {
+  struct slice {
+    const T* b; const T* e;
+    const T* begin() const { return b; }
+    const T* end() const { return e; }
+    size_t size() const { return (size_t)(e - b); }
+    T operator[](size_t j) const { return b[j]; }
+  };
+  std::vector<T> coords;
+  std::vector<size_t> offsets;
+  std::vector<T> sizes;
+  size_t n = 0;
+  size_t num_matches = 0;
+
+  RangeGroundTruth() {}
+  explicit RangeGroundTruth(const char* gtFile) {
+    if (gtFile == nullptr) return;
+    std::ifstream in(gtFile, std::ios::binary);
+    if (!in.is_open()) { std::cout << "range ground truth file " << gtFile << " not found" << std::endl; abort(); }
+    T hdr[2];
+    in.read((char*)hdr, 2 * sizeof(T));
+    n = (size_t)hdr[0]; num_matches = (size_t)hdr[1];
+    sizes.resize(n); coords.resize(num_matches);
+    in.read((char*)sizes.data(), (std::streamsize)(n * sizeof(T)));
+    in.read((char*)coords.data(), (std::streamsize)(num_matches * sizeof(T)));
+    if (!in) { std::cout << "range ground truth file " << gtFile << " is truncated" << std::endl; abort(); }
+    offsets.assign(n + 1, 0);
+    for (size_t i = 0; i < n; i++) offsets[i + 1] = offsets[i] + (size_t)sizes[i];
+    if (offsets[n] != num_matches) { std::cout << "range ground truth file " << gtFile << ": sizes do not add up to num_matches" << std::endl; abort(); }
+    std::cout << "Detected " << n << " points with num matches " << num_matches << std::endl;
+  }
+  // from CSR as pann_bruteforce_range returns it
+  RangeGroundTruth(const std::vector<uint64_t>& off, const std::vector<uint32_t>& ids)
+      : coords(ids.begin(), ids.end()), offsets(off.begin(), off.end()), n(off.size() - 1), num_matches(ids.size()) {
+    sizes.resize(n);
+    for (size_t i = 0; i < n; i++) sizes[i] = (T)(off[i + 1] - off[i]);
+  }
+
+  slice operator[](long i) const { return slice{coords.data() + offsets[(size_t)i], coords.data() + offsets[(size_t)i + 1]}; }
+  size_t size() const { return n; }
+  size_t matches() const { return num_matches; }
+};
+
+struct RangeParams {                                                            // :233-245
+  double rad = 0;
+  long initial_beam = 0;
+  RangeParams(double rad, long ib) : rad(rad), initial_beam(ib) {}
+  RangeParams() {}
+  void print() { std::cout << "Beam: " << initial_beam; }
 };
 
 }  // namespace parlayANN

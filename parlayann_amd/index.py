@@ -362,6 +362,36 @@ class DeviceIndex:
             sub[np.arange(w, dtype=np.uint32)[None, :] >= cnt[:, None]] = 0xFFFFFFFF
         return {"ids": ids, "counts": cnt, "dist_cmps": cmps, "truncated": trunc}
 
+    def range_query(self, queries=None, radius=None, beam=10, max_results=1024, query_ids=None, starts=(0,), k=None, cut=0.0,
+                    limit=None, degree_limit=None):
+        """RangeSearch (beamSearch.h:567-614) in one call (pann_range_query): a beam search from `starts`, then the BFS of
+        range_search seeded per query with its whole final frontier; the frontiers never leave the device.  Defaults are
+        QueryParams(beam, beam, 0.0, n, max_degree) (:587).  Returns range_search's dict (`dist_cmps` = the BFS's comparisons)
+        plus `search_cmps`, `visited` (the beam search's counters) and `range_cmps`."""
+        if radius is None:
+            raise ValueError("radius must be given")
+        if (queries is None) == (query_ids is None):
+            raise ValueError("exactly one of queries / query_ids must be given")
+        if queries is not None:
+            q = self._queries(queries); nq = len(q); qptr, qs, qi = _ptr(q), _row_stride(q), None
+        else:
+            qid = np.ascontiguousarray(query_ids, dtype=np.uint32); nq = len(qid); qptr, qs, qi = None, 0, _ptr(qid)
+        starts = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
+        qp = QueryParams(k=beam if k is None else k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
+                         degree_limit=self.max_degree if degree_limit is None else degree_limit, rerank_factor=100, pad=1.0)
+        ids = np.empty((nq, max_results), np.uint32)
+        cnt = np.zeros(nq, np.uint32); trunc = np.zeros(nq, np.uint32)
+        scmps = np.zeros(nq, np.uint32); vis = np.zeros(nq, np.uint32); rcmps = np.zeros(nq, np.uint32)
+        check(self._lib.pann_range_query(self._h, qptr, qi, nq, qs, _ptr(starts), len(starts), C.byref(qp), float(radius),
+                                         max_results, _ptr(ids), _ptr(cnt), _ptr(scmps), _ptr(vis), _ptr(rcmps), _ptr(trunc)))
+        w = int(cnt.max()) if nq else 0                      # entries past a row's count are unspecified: pad them
+        ids[:, w:] = 0xFFFFFFFF
+        if w:
+            sub = ids[:, :w]
+            sub[np.arange(w, dtype=np.uint32)[None, :] >= cnt[:, None]] = 0xFFFFFFFF
+        return {"ids": ids, "counts": cnt, "dist_cmps": rcmps, "truncated": trunc, "search_cmps": scmps, "visited": vis,
+                "range_cmps": rcmps}
+
     def pair_distances(self, a_ids, b_ids):
         a = np.ascontiguousarray(a_ids, dtype=np.uint32); b = np.ascontiguousarray(b_ids, dtype=np.uint32)
         out = np.empty(len(a), np.float32)
@@ -391,6 +421,18 @@ class DeviceIndex:
         oi = np.empty((len(q), k), np.uint32); od = np.empty((len(q), k), np.float32)
         check(self._lib.pann_bruteforce_knn(self._h, _ptr(q), len(q), _row_stride(q), k, _ptr(oi), _ptr(od)))
         return oi, od
+
+    def bruteforce_range(self, queries, radius):
+        """data_tools/compute_range_groundtruth.cpp:13-29: every base point within `radius` of every query, as CSR ->
+        (offsets uint64[nq + 1], ids uint32[total]); the ids of a query are ascending.  A count call, then a fill call."""
+        q = self._queries(queries)
+        nq = len(q)
+        off = np.zeros(nq + 1, np.uint64)
+        check(self._lib.pann_bruteforce_range(self._h, _ptr(q), nq, _row_stride(q), float(radius), _ptr(off), None, 0))
+        ids = np.empty(int(off[nq]), np.uint32)
+        if len(ids):
+            check(self._lib.pann_bruteforce_range(self._h, _ptr(q), nq, _row_stride(q), float(radius), _ptr(off), _ptr(ids), len(ids)))
+        return off, ids
 
     def pivot_split(self, ids, seg_offsets, pivot_a, pivot_b):
         """clusterEdge.h:66-83: side 0 when d(id, pivot_a) <= d(id, pivot_b)."""
