@@ -425,6 +425,74 @@ int pann_index_download_points(pann_index* idx, uint64_t first_row, uint64_t nro
  * a = (long)(.0001f * len) in float, b = (long)((1.0 - .0001f) * (len - 1)) in double; trim == 0: 0 and len - 1 */
 void pann_quantize_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b);
 
+/* ---- two-level search: bit sketches + filtered_beam_search(..., use_filtering = true) ---------
+ * The reference's low-precision pre-filter (beamSearch.h:98-100,117-123,139-146): while the frontier is full, a neighbour that
+ * passed the hash filter gets its full distance only if a cheap sketch distance to the query is below the running mean of the
+ * sketch distance to the worst frontier entry.  Three of the reference's sketch point types, built on the device from a
+ * resident f32 handle:
+ *   PANN_SKETCH_EUCLID_BIT  Euclidean_Bit_Point (euclidian_point.h:332-420)  median = (long) sorted[n*d/2]; bit = x > (float) median
+ *   PANN_SKETCH_MIPS_BIT    Mips_Bit_Point      (mips_point.h:625-702)       bit = x > 0
+ *   PANN_SKETCH_MIPS_2BIT   Mips_2Bit_Point     (mips_point.h:495-623)       cut = max(sorted[b], -sorted[a]); per 64 dims a sign
+ *                                                                            word and a non-zero-mask word
+ * Host-visible sketch rows have the reference's num_bytes(): 8 * ceil(d / 64) bytes (one-bit kinds), 16 * ceil(d / 64) (2-bit:
+ * word 2i = sign, word 2i + 1 = mask).  Bits the reference leaves uninitialised -- positions >= d, sign bits under a clear mask
+ * bit, mask bits past the first position >= d -- are 0 here; distances never depend on them.
+ * hamming_as_written (one-bit kinds; ignored for 2-bit): 0 = Hamming distance over all 64-bit blocks; 1 = the reference's loop
+ * as written, which never advances its pointers (euclidian_point.h:360-361, mips_point.h:652-653): num_blocks * popcount of
+ * block 0.  pann_sketch_params_generate sets 0.
+ * Status: a source that is not f32, d > 2048 -> PANN_ERR_UNSUPPORTED; no sketch attached, n / d mismatch, a stride shorter than
+ * a row (or not a multiple of 8 for sketch rows, 4 for float rows), NULL pointers, an unknown kind -> PANN_ERR_BAD_ARG. */
+enum { PANN_SKETCH_EUCLID_BIT = 0, PANN_SKETCH_MIPS_BIT = 1, PANN_SKETCH_MIPS_2BIT = 2 };
+#define PANN_SKETCH_MAX_DIMS 2048
+typedef struct pann_sketch_params {
+  int32_t kind;
+  int32_t dims;
+  int64_t median;              /* EUCLID_BIT */
+  float cut;                   /* MIPS_2BIT */
+  uint32_t hamming_as_written; /* one-bit kinds */
+} pann_sketch_params;
+
+/* generate_parameters over every coordinate of src (f32); the order statistics are found exactly by the radix select of
+ * pann_quantize_params, nothing is sorted.  Synchronises src's stream. */
+int pann_sketch_params_generate(pann_index* src, int kind, pann_sketch_params* out);
+/* host-only helper: the sorted positions generate_parameters reads for len = n * d values.  EUCLID_BIT: a = b = len / 2;
+ * MIPS_2BIT (mips_point.h:612-614): a = (long)(.3f * len) in float, b = (long)((1.0 - .3f) * (len - 1)) in double;
+ * MIPS_BIT: none (a = b = 0). */
+void pann_sketch_select_ranks(uint64_t len, int kind, uint64_t* a, uint64_t* b);
+/* Sketch every row of src (f32, same n, d and device as idx; may be idx itself) with *p; the slab belongs to idx, is freed with
+ * it, and replaces a sketch attached earlier.  idx is the handle that will be searched, of any element type. */
+int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch_params* p);
+/* The same from n host-layout sketch rows (row stride stride_bytes) that the caller already holds -- rows downloaded from
+ * another handle, or a host PointRange of sketch points (parlayann_amd/host/sketch.h). */
+int pann_index_upload_sketch(pann_index* idx, const pann_sketch_params* p, const void* rows, uint64_t stride_bytes);
+int pann_index_drop_sketch(pann_index* idx);
+int pann_index_sketch_kind(const pann_index* idx);      /* -1: no sketch attached */
+/* rows [first_row, first_row + nrows) of the attached sketch, host layout, row stride out_stride_bytes */
+int pann_index_download_sketch(pann_index* idx, uint64_t first_row, uint64_t nrows, void* out, uint64_t out_stride_bytes);
+/* Sketches of n host rows of p->dims floats (the queries) -> n host-layout rows at `out`; runs on device `device`. */
+int pann_sketch_rows(const pann_sketch_params* p, const float* rows, uint64_t n, uint64_t stride_bytes, void* out,
+                     uint64_t out_stride_bytes, int device);
+/* The same on device pointers (d_out and out_stride_bytes multiples of 8), on `stream` of the current device; no allocation, no
+ * synchronisation. */
+int pann_sketch_rows_dev(const pann_sketch_params* p, const float* d_rows, uint64_t n, uint64_t stride_bytes, void* d_out,
+                         uint64_t out_stride_bytes, void* stream);
+
+/* pann_batch_search with the sketch filter of the handle's attached sketch.  Exactly one of queries / query_ids is non-NULL.
+ * With queries, sketch_queries is required: nq host-layout sketch rows (pann_sketch_rows), row stride sq_stride_bytes.  With
+ * query_ids, sketch_queries must be NULL: the sketch query is the handle's own sketch row.
+ * out->dist_cmps is the reference's full_dist_cmps (what it returns, beamSearch.h:213): starts + neighbours that got a full
+ * distance.  out_pruned_cmps (optional, nq words) gets its local dist_cmps: starts + neighbours that passed the hash filter
+ * (:83,137).  Every beam width runs the generic kernel.  The plain pann_batch_search* entries never look at the sketch. */
+int pann_batch_search_filtered(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                               uint64_t q_stride_bytes, const void* sketch_queries, uint64_t sq_stride_bytes,
+                               const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                               const pann_search_out* out, uint32_t* out_pruned_cmps);
+/* Device pointers throughout, launched on `stream`; no sync, no alloc beyond the workspace growth of pann_batch_search_dev. */
+int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                   uint64_t q_stride_bytes, const void* d_sketch_queries, uint64_t sq_stride_bytes,
+                                   const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                   const pann_search_out* d_out, uint32_t* d_out_pruned_cmps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,17 @@ class QuantParams(C.Structure):
         return self.slope == 1.0 and self.offset == 0
 
 
+PANN_SKETCH_EUCLID_BIT, PANN_SKETCH_MIPS_BIT, PANN_SKETCH_MIPS_2BIT = 0, 1, 2
+PANN_SKETCH_MAX_DIMS = 2048
+
+
+class SketchParams(C.Structure):
+    """pann_sketch_params: Euclidean_Bit_Point::parameters (median) / Mips_2Bit_Point::parameters (cut); hamming_as_written
+    selects the reference's one-bit distance loop as written (block 0 counted num_blocks times)."""
+    _fields_ = [("kind", C.c_int32), ("dims", C.c_int32), ("median", C.c_int64), ("cut", C.c_float),
+                ("hamming_as_written", C.c_uint32)]
+
+
 # every symbol include/pann.h declares: (restype, argtypes)
 SIGNATURES = {
     "pann_abi_version": (C.c_int, []),
@@ -145,6 +156,21 @@ SIGNATURES = {
                                          C.c_uint64, C.c_void_p]),
     "pann_index_download_points": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]),
     "pann_quantize_select_ranks": (None, [C.c_uint64, C.c_int, u64p, u64p]),
+    "pann_sketch_params_generate": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SketchParams)]),
+    "pann_sketch_select_ranks": (None, [C.c_uint64, C.c_int, u64p, u64p]),
+    "pann_index_attach_sketch": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(SketchParams)]),
+    "pann_index_upload_sketch": (C.c_int, [C.c_void_p, C.POINTER(SketchParams), C.c_void_p, C.c_uint64]),
+    "pann_index_drop_sketch": (C.c_int, [C.c_void_p]),
+    "pann_index_sketch_kind": (C.c_int, [C.c_void_p]),
+    "pann_index_download_sketch": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "pann_sketch_rows": (C.c_int, [C.POINTER(SketchParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int]),
+    "pann_sketch_rows_dev": (C.c_int, [C.POINTER(SketchParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                       C.c_void_p]),
+    "pann_batch_search_filtered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.POINTER(SearchOut), C.c_void_p]),
+    "pann_batch_search_filtered_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                 C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.POINTER(SearchOut), C.c_void_p,
+                                                 C.c_void_p]),
 }
 
 _lib = None

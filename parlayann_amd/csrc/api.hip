@@ -80,6 +80,7 @@ struct pann_index {
   int codes_state = 0;      // 0 not tried, 1 available (rank16 built), -1 unavailable (a slot class has 4 095 or more members) or switched off
   DevBuf stage[12];      // staging for host-pointer calls
   PinnedBuf pin_in, pin_out;   // packed pinned staging of pann_batch_search
+  DevBuf sketch_buf;           // attached bit sketch (pann_index_attach_sketch): ix.sketch points into it
 };
 
 namespace {
@@ -362,6 +363,7 @@ void pann_index_destroy(pann_index* idx) {
   for (auto& s : idx->stage) s.release();
   idx->pin_in.release(); idx->pin_out.release();
   idx->code_rank.release(); idx->code_rows.release(); idx->cell_buf.release();
+  idx->sketch_buf.release();
   if (idx->own_stream) (void)hipStreamDestroy(idx->own_stream);
   delete idx;
 }
@@ -487,10 +489,11 @@ static int search_common_checks(pann_index* idx, uint64_t nq, const pann_query_p
   return PANN_OK;
 }
 
-int pann_batch_search_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids,
-                          uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
-                          uint32_t nstarts, const pann_query_params* qp,
-                          const pann_search_out* d_out, void* stream) {
+static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids,
+                                 uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
+                                 uint32_t nstarts, const pann_query_params* qp,
+                                 const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
+                                 uint64_t sq_stride, uint32_t* d_pruned) {
   if (int rc = search_common_checks(idx, nq, qp, d_out)) return rc;
   if (!d_starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if (d_queries && q_stride_bytes < idx->ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
@@ -501,16 +504,42 @@ int pann_batch_search_dev(pann_index* idx, const void* d_queries, const uint32_t
   a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
   a.dcap = idx->dcap;
   a.out = *d_out;
+  a.filter = filter; a.sketch_queries = (const uint8_t*)d_sketch_queries; a.sq_stride = sq_stride; a.pruned_cmps = d_pruned;
   if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
   return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, (hipStream_t)stream);
+}
+
+int pann_batch_search_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids,
+                          uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
+                          uint32_t nstarts, const pann_query_params* qp,
+                          const pann_search_out* d_out, void* stream) {
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr);
+}
+
+int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                   uint64_t q_stride_bytes, const void* d_sketch_queries, uint64_t sq_stride_bytes,
+                                   const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                   const pann_search_out* d_out, uint32_t* d_out_pruned_cmps, void* stream) {
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 1, d_sketch_queries,
+                               sq_stride_bytes, d_out_pruned_cmps);
 }
 
 }  // extern "C"
 
 static int batch_search_host(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int per_query,
-                             const pann_query_params* qp, const pann_search_out* out) {
+                             const pann_query_params* qp, const pann_search_out* out, int filter = 0,
+                             const void* sketch_queries = nullptr, uint64_t sq_stride = 0, uint32_t* out_pruned = nullptr) {
   if (int rc = search_common_checks(idx, nq, qp, out)) return rc;
+  uint32_t sk_row = 0;
+  if (filter) {
+    if (!idx->ix.sketch) { set_error("pann_batch_search_filtered: no sketch attached to the index"); return PANN_ERR_BAD_ARG; }
+    if ((queries != nullptr) != (sketch_queries != nullptr)) {
+      set_error("pann_batch_search_filtered: sketch_queries go with queries, and only with them"); return PANN_ERR_BAD_ARG;
+    }
+    sk_row = sketch_row_bytes(idx->ix.sk_kind, idx->ix.d);
+    if (sketch_queries && sq_stride < sk_row) { set_error("pann_batch_search_filtered: sketch query stride smaller than a sketch row"); return PANN_ERR_BAD_ARG; }
+  }
   if (!starts || nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if ((queries == nullptr) == (query_ids == nullptr)) { set_error("pann_batch_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
   const uint64_t nst_total = per_query ? nq * nstarts : nstarts;
@@ -536,13 +565,18 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   const void* d_q = queries ? idx->stage[2].p : nullptr;
   const uint32_t* d_qid = queries ? nullptr : idx->stage[2].as<uint32_t>();
   const uint32_t* d_starts = (const uint32_t*)((uint8_t*)idx->stage[2].p + off_st);
+  if (filter && sketch_queries) {      // dense rows of sk_row bytes
+    if (int rc = idx->stage[5].ensure((size_t)nq * sk_row)) return rc;
+    PANN_HIP(hipMemcpy2D(idx->stage[5].p, sk_row, sketch_queries, sq_stride, sk_row, nq, hipMemcpyHostToDevice));
+  }
 
   // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
   const size_t ok = out->out_k, vc = out->visited_cap;
   struct Piece { void* host; size_t bytes; size_t off; };
-  Piece pc[8] = {{out->ids, nq * ok * 4, 0}, {out->dists, nq * ok * 4, 0}, {out->frontier_size, nq * 4, 0},
+  Piece pc[9] = {{out->ids, nq * ok * 4, 0}, {out->dists, nq * ok * 4, 0}, {out->frontier_size, nq * 4, 0},
                  {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {out->degree_sum, nq * 4, 0},
-                 {out->visited_ids, nq * vc * 4, 0}, {out->visited_dists, nq * vc * 4, 0}};
+                 {out->visited_ids, nq * vc * 4, 0}, {out->visited_dists, nq * vc * 4, 0},
+                 {filter ? out_pruned : nullptr, nq * 4, 0}};
   size_t out_bytes = 0;
   for (auto& x : pc) { if (!x.host) x.bytes = 0; x.off = out_bytes; out_bytes += al(x.bytes); }
   if (int rc = idx->stage[4].ensure(out_bytes + 256)) return rc;
@@ -585,6 +619,11 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
       if (a.out.degree_sum) a.out.degree_sum += q0;
       if (a.out.visited_ids) a.out.visited_ids += q0 * vc;
       if (a.out.visited_dists) a.out.visited_dists += q0 * vc;
+      a.filter = filter;
+      if (filter) {
+        a.sketch_queries = sketch_queries ? (const uint8_t*)idx->stage[5].p + q0 * sk_row : nullptr; a.sq_stride = sk_row;
+        a.pruned_cmps = dptr(8) ? (uint32_t*)dptr(8) + q0 : nullptr;
+      }
       if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
       if (int rc = launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
       uint32_t st_word = 0;      // the launch's status word (the next launch clears it)
@@ -625,6 +664,14 @@ int pann_batch_search(pann_index* idx, const void* queries, const uint32_t* quer
                       uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts,
                       const pann_query_params* qp, const pann_search_out* out) {
   return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out);
+}
+
+int pann_batch_search_filtered(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                               uint64_t q_stride_bytes, const void* sketch_queries, uint64_t sq_stride_bytes,
+                               const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                               const pann_search_out* out, uint32_t* out_pruned_cmps) {
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 1, sketch_queries, sq_stride_bytes,
+                           out_pruned_cmps);
 }
 
 int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
@@ -1430,6 +1477,158 @@ int pann_index_download_points(pann_index* idx, uint64_t first_row, uint64_t nro
                          ix.dbytes, cnt, hipMemcpyDeviceToHost));
   }
   return PANN_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// bit sketches (sketch.hip): the second level of the filtered searches
+// ---------------------------------------------------------------------------------------------
+
+namespace {
+
+int check_sketch_params(const pann_sketch_params* p, const char* fn) {
+  if (!p) { set_error(std::string(fn) + ": null parameters"); return PANN_ERR_BAD_ARG; }
+  if (!sketch_kind_ok(p->kind)) { set_error(std::string(fn) + ": unknown sketch kind"); return PANN_ERR_BAD_ARG; }
+  if (p->dims <= 0) { set_error(std::string(fn) + ": parameters without dimensions"); return PANN_ERR_BAD_ARG; }
+  if (p->dims > PANN_SKETCH_MAX_DIMS) { set_error(std::string(fn) + ": sketches of more than 2048 dimensions are not supported"); return PANN_ERR_UNSUPPORTED; }
+  return PANN_OK;
+}
+int check_sketch_source(const pann_index* src, const char* fn) {
+  if (int rc = check_idx(src, fn)) return rc;
+  if (src->ix.dtype != PANN_F32) { set_error(std::string(fn) + ": the source index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
+  if (src->ix.d > PANN_SKETCH_MAX_DIMS) { set_error(std::string(fn) + ": sketches of more than 2048 dimensions are not supported"); return PANN_ERR_UNSUPPORTED; }
+  return PANN_OK;
+}
+int check_sketch_rows_args(const pann_sketch_params* p, const float* rows, uint64_t stride, const void* out, uint64_t out_stride, const char* fn) {
+  if (int rc = check_sketch_params(p, fn)) return rc;
+  if (!rows || !out) { set_error(std::string(fn) + ": null rows / output"); return PANN_ERR_BAD_ARG; }
+  if (stride < 4ull * (uint32_t)p->dims || stride % 4 != 0) { set_error(std::string(fn) + ": row stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }
+  if (out_stride < sketch_row_bytes(p->kind, (uint32_t)p->dims)) { set_error(std::string(fn) + ": output stride smaller than a sketch row"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void pann_sketch_select_ranks(uint64_t len, int kind, uint64_t* a, uint64_t* b) {
+  if (!a || !b || len == 0) return;
+  sketch_select_ranks(len, kind, a, b);
+}
+
+int pann_sketch_params_generate(pann_index* src, int kind, pann_sketch_params* out) {
+  if (!sketch_kind_ok(kind)) { set_error("pann_sketch_params_generate: unknown sketch kind"); return PANN_ERR_BAD_ARG; }
+  if (!out) { set_error("pann_sketch_params_generate: null output"); return PANN_ERR_BAD_ARG; }
+  if (int rc = check_sketch_source(src, "pann_sketch_params_generate")) return rc;
+  const DeviceIndex& ix = src->ix;
+  if (ix.n == 0 || ix.d == 0) { set_error("pann_sketch_params_generate: empty index"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(src->device);
+  if (int rc = src->stage[8].ensure(quant_scratch_bytes())) return rc;
+  return sketch_params_dev(reinterpret_cast<const float*>(ix.points), ix.n, ix.d, ix.pstride, kind, out, src->stage[8].p, src->stream);
+}
+
+int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch_params* p) {
+  if (int rc = check_idx(idx, "pann_index_attach_sketch")) return rc;
+  if (int rc = check_idx(src, "pann_index_attach_sketch")) return rc;
+  if (int rc = check_sketch_params(p, "pann_index_attach_sketch")) return rc;
+  if (int rc = check_sketch_source(src, "pann_index_attach_sketch")) return rc;
+  const DeviceIndex& sx = src->ix;
+  if (sx.n != idx->ix.n || sx.d != idx->ix.d || (uint32_t)p->dims != sx.d || src->device != idx->device) {
+    set_error("pann_index_attach_sketch: source, parameters and index must agree in size, dimension and device"); return PANN_ERR_BAD_ARG;
+  }
+  DeviceGuard g(idx->device);
+  PANN_HIP(hipStreamSynchronize(idx->stream));           // no search of idx may still read the old slab
+  const uint32_t stride = sketch_dev_stride(p->kind, sx.d);
+  idx->ix.sketch = nullptr; idx->ix.sk_kind = -1;
+  if (int rc = idx->sketch_buf.ensure((size_t)sx.n * stride)) return rc;
+  if (int rc = sketch_translate_dev(p, reinterpret_cast<const float*>(sx.points), sx.n, sx.pstride, idx->sketch_buf.p, stride, stride, src->stream)) return rc;
+  PANN_HIP(hipStreamSynchronize(src->stream));
+  idx->ix.sketch = idx->sketch_buf.as<uint8_t>(); idx->ix.sk_stride = stride; idx->ix.sk_kind = p->kind;
+  idx->ix.sk_as_written = (p->kind != PANN_SKETCH_MIPS_2BIT && p->hamming_as_written) ? 1u : 0u;
+  return PANN_OK;
+}
+
+int pann_index_upload_sketch(pann_index* idx, const pann_sketch_params* p, const void* rows, uint64_t stride_bytes) {
+  if (int rc = check_idx(idx, "pann_index_upload_sketch")) return rc;
+  if (int rc = check_sketch_params(p, "pann_index_upload_sketch")) return rc;
+  const DeviceIndex& ix = idx->ix;
+  if (!rows) { set_error("pann_index_upload_sketch: null rows"); return PANN_ERR_BAD_ARG; }
+  if ((uint32_t)p->dims != ix.d) { set_error("pann_index_upload_sketch: parameters made for another dimension"); return PANN_ERR_BAD_ARG; }
+  const uint32_t row = sketch_row_bytes(p->kind, ix.d), stride = sketch_dev_stride(p->kind, ix.d);
+  if (stride_bytes < row) { set_error("pann_index_upload_sketch: row stride smaller than a sketch row"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  PANN_HIP(hipStreamSynchronize(idx->stream));           // no search of idx may still read the old slab
+  idx->ix.sketch = nullptr; idx->ix.sk_kind = -1;
+  if (ix.n == 0) { set_error("pann_index_upload_sketch: empty index"); return PANN_ERR_BAD_ARG; }
+  if (int rc = idx->sketch_buf.ensure((size_t)ix.n * stride)) return rc;
+  if (stride != row) PANN_HIP(hipMemset(idx->sketch_buf.p, 0, (size_t)ix.n * stride));      // the pad bytes of a device row are zero
+  PANN_HIP(hipMemcpy2D(idx->sketch_buf.p, stride, rows, stride_bytes, row, ix.n, hipMemcpyHostToDevice));
+  idx->ix.sketch = idx->sketch_buf.as<uint8_t>(); idx->ix.sk_stride = stride; idx->ix.sk_kind = p->kind;
+  idx->ix.sk_as_written = (p->kind != PANN_SKETCH_MIPS_2BIT && p->hamming_as_written) ? 1u : 0u;
+  return PANN_OK;
+}
+
+int pann_index_drop_sketch(pann_index* idx) {
+  if (int rc = check_idx(idx, "pann_index_drop_sketch")) return rc;
+  DeviceGuard g(idx->device);
+  PANN_HIP(hipStreamSynchronize(idx->stream));
+  idx->ix.sketch = nullptr; idx->ix.sk_kind = -1; idx->ix.sk_stride = 0; idx->ix.sk_as_written = 0;
+  idx->sketch_buf.release();
+  return PANN_OK;
+}
+
+int pann_index_sketch_kind(const pann_index* idx) { return (idx && idx->ix.sketch) ? idx->ix.sk_kind : -1; }
+
+int pann_index_download_sketch(pann_index* idx, uint64_t first_row, uint64_t nrows, void* out, uint64_t out_stride_bytes) {
+  if (int rc = check_idx(idx, "pann_index_download_sketch")) return rc;
+  const DeviceIndex& ix = idx->ix;
+  if (!ix.sketch) { set_error("pann_index_download_sketch: no sketch attached to the index"); return PANN_ERR_BAD_ARG; }
+  if (nrows == 0) return PANN_OK;
+  if (!out) { set_error("pann_index_download_sketch: null output"); return PANN_ERR_BAD_ARG; }
+  if (first_row > ix.n || nrows > ix.n - first_row) { set_error("pann_index_download_sketch: row range outside the index"); return PANN_ERR_BAD_ARG; }
+  const uint32_t row = sketch_row_bytes(ix.sk_kind, ix.d);
+  if (out_stride_bytes < row) { set_error("pann_index_download_sketch: row stride smaller than a sketch row"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  PANN_HIP(hipStreamSynchronize(idx->stream));
+  PANN_HIP(hipMemcpy2D(out, out_stride_bytes, ix.sketch + first_row * ix.sk_stride, ix.sk_stride, row, nrows, hipMemcpyDeviceToHost));
+  return PANN_OK;
+}
+
+int pann_sketch_rows_dev(const pann_sketch_params* p, const float* d_rows, uint64_t n, uint64_t stride_bytes, void* d_out,
+                         uint64_t out_stride_bytes, void* stream) {
+  if (int rc = check_sketch_rows_args(p, d_rows, stride_bytes, d_out, out_stride_bytes, "pann_sketch_rows_dev")) return rc;
+  if (out_stride_bytes % 8 != 0 || (uintptr_t)d_out % 8 != 0) { set_error("pann_sketch_rows_dev: output rows must be 8-byte aligned"); return PANN_ERR_BAD_ARG; }
+  if (n == 0) return PANN_OK;
+  return sketch_translate_dev(p, d_rows, n, stride_bytes, d_out, out_stride_bytes, sketch_row_bytes(p->kind, (uint32_t)p->dims), (hipStream_t)stream);
+}
+
+int pann_sketch_rows(const pann_sketch_params* p, const float* rows, uint64_t n, uint64_t stride_bytes, void* out,
+                     uint64_t out_stride_bytes, int device) {
+  if (int rc = check_sketch_rows_args(p, rows, stride_bytes, out, out_stride_bytes, "pann_sketch_rows")) return rc;
+  const int ndev = pann_device_count();
+  if (ndev <= 0) { set_error("pann_sketch_rows: no HIP device visible (this library has no CPU path)"); return PANN_ERR_NO_DEVICE; }
+  if (device < 0 || device >= ndev) { set_error("pann_sketch_rows: device ordinal out of range"); return PANN_ERR_BAD_ARG; }
+  if (n == 0) return PANN_OK;
+  DeviceGuard g(device);
+  if (!g.ok) { set_error("pann_sketch_rows: hipSetDevice failed"); return PANN_ERR_HIP; }
+  const uint32_t d = (uint32_t)p->dims, row = sketch_row_bytes(p->kind, d);
+  const uint64_t slice = std::max<uint64_t>(1, (256ull << 20) / (4ull * d));
+  DevBuf in, ob;
+  auto done = [&](int rc) { in.release(); ob.release(); return rc; };
+  const uint64_t cap = std::min(slice, n);
+  if (int rc = in.ensure(cap * d * 4)) return done(rc);
+  if (int rc = ob.ensure(cap * row)) return done(rc);
+  for (uint64_t r0 = 0; r0 < n; r0 += slice) {
+    const uint64_t cnt = std::min(slice, n - r0);
+    hipError_t e = hipMemcpy2D(in.p, (size_t)d * 4, (const uint8_t*)rows + r0 * stride_bytes, stride_bytes, (size_t)d * 4, cnt, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(rows)"));
+    if (int rc = pann_sketch_rows_dev(p, in.as<float>(), cnt, (uint64_t)d * 4, ob.p, row, nullptr)) return done(rc);
+    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
+    e = hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ob.p, row, row, cnt, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(out)"));
+  }
+  return done(PANN_OK);
 }
 
 }  // extern "C"

@@ -112,6 +112,12 @@ struct BSParams {
   uint32_t* status;        // [0] |= 1 on visited-list overflow, |= 2 on dropped-list overflow
   pann_search_out out;
   unsigned long long* stamps;   // diagnostic build: [nq][8] cycle sums
+  // second level (FILTER variants of the generic kernel only): bit sketches, see sketch.hip
+  const uint8_t* sketch; uint32_t sk_stride;      // [n] rows of sk_stride bytes (a multiple of 16, zero padded)
+  uint32_t sk_kind, sk_as_written, sk_nblk;       // PANN_SKETCH_*; Hamming loop as written; 64-bit blocks per sketch
+  const uint8_t* sketch_queries; uint64_t sq_stride; uint32_t sk_row_bytes;   // external queries: nq host-layout rows
+  uint32_t sk_lds_off;                            // byte offset of the query sketch in LDS
+  uint32_t* pruned_cmps;                          // [nq] optional: starts + neighbours that passed the hash filter
 };
 
 template <bool HASH_LDS>
@@ -365,8 +371,43 @@ __device__ __forceinline__ uint32_t gather_distances_split(const BSParams& P, co
 }
 
 
+// Sketch distance of base point `a` to the query sketch SQ (LDS, wave-uniform), as the float the reference's distance()
+// returns: Hamming distance (Euclidean_Bit_Point / Mips_Bit_Point; as_written: the reference's loop, which counts block 0
+// num_blocks times, euclidian_point.h:360-361, mips_point.h:652-653) or sum of 2 pop(ne & nz) - pop(nz) over the blocks
+// (Mips_2Bit_Point::distance_8, mips_point.h:530-543; |total| <= d <= 2048 fits its int16).  The lane reads its candidate's
+// row as 16-byte chunks: one for d <= 128 (one-bit) / d <= 64 (2-bit); pad bytes are zero on both sides and add nothing.
+__device__ __forceinline__ float sketch_distance(const BSParams& P, const uint4* SQ, uint32_t a) {
+  const uint4* __restrict__ row = reinterpret_cast<const uint4*>(P.sketch + (uint64_t)a * P.sk_stride);
+  const uint32_t nch = P.sk_stride >> 4;
+  int tot = 0;
+  if (P.sk_kind == PANN_SKETCH_MIPS_2BIT) {             // a chunk = one block: sign word (x, y), mask word (z, w)
+    for (uint32_t j = 0; j < nch; j++) {
+      const uint4 p = row[j], q = SQ[j];
+      const uint64_t ne = (((uint64_t)(p.y ^ q.y)) << 32) | (p.x ^ q.x);
+      const uint64_t nz = (((uint64_t)(p.w & q.w)) << 32) | (p.z & q.z);
+      tot += 2 * __popcll(ne & nz) - __popcll(nz);
+    }
+  } else if (P.sk_as_written) {
+    const uint4 p = row[0], q = SQ[0];
+    const uint64_t x = (((uint64_t)(p.y ^ q.y)) << 32) | (p.x ^ q.x);
+    tot = (int)P.sk_nblk * __popcll(x);
+  } else {                                              // a chunk = two blocks
+    for (uint32_t j = 0; j < nch; j++) {
+      const uint4 p = row[j], q = SQ[j];
+      const uint64_t x0 = (((uint64_t)(p.y ^ q.y)) << 32) | (p.x ^ q.x);
+      const uint64_t x1 = (((uint64_t)(p.w ^ q.w)) << 32) | (p.z ^ q.z);
+      tot += __popcll(x0) + __popcll(x1);
+    }
+  }
+  return (float)tot;
+}
+
 // Generic kernel: any beam (frontier in LDS), filter in LDS or in HBM scratch.
-template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS>
+// FILTER: filtered_beam_search with use_filtering (beamSearch.h:98-100,117-123,139-146) -- while the frontier is full, a
+// neighbour that passed the hash filter gets a full distance only if its sketch distance to the query is below the running
+// mean of the sketch distance to the worst frontier entry.  After the hash-filter replay lane i still owns neighbour i: it
+// reads its own candidate's sketch, and the ballot compaction that follows hands the gather a dense list in row order.
+template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = false>
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(BSParams P) {
   const int lane = threadIdx.x;
   extern __shared__ __align__(16) uint8_t smem[];
@@ -403,6 +444,14 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
     const uint8_t* qrow = P.query_ids ? P.points + (uint64_t)self * P.pstride : P.queries + (uint64_t)qi * P.qstride;
     QReg<DT> qreg{};
     load_query<DT, LPC, NCH1>(qrow, P.dbytes, P.nch, qreg, qlds, lane);
+    [[maybe_unused]] const uint4* SQ = reinterpret_cast<const uint4*>(smem + P.sk_lds_off);   // [sk_stride / 16] query sketch
+    if constexpr (FILTER) {   // qq: the query's sketch -- its own row of the slab, or an external host-layout row (zero padded)
+      uint32_t* sq = reinterpret_cast<uint32_t*>(smem + P.sk_lds_off);
+      const uint32_t* srow = reinterpret_cast<const uint32_t*>(P.query_ids ? P.sketch + (uint64_t)self * P.sk_stride
+                                                                           : P.sketch_queries + (uint64_t)qi * P.sq_stride);
+      const uint32_t valid = (P.query_ids ? P.sk_stride : P.sk_row_bytes) >> 2;
+      for (uint32_t w = lane; w < (P.sk_stride >> 2); w += PANN_WAVE) sq[w] = w < valid ? srow[w] : 0u;
+    }
     hsync<HASH_LDS>();
 
     uint32_t f = 0;        // frontier size
@@ -411,6 +460,9 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
     uint32_t dcmps = P.nstarts;  // dist_cmps == full_dist_cmps (:83-84)
     uint32_t degsum = 0;
     uint32_t ndrop = 0;    // entries in the dropped list
+    [[maybe_unused]] uint32_t pcmps = P.nstarts;   // FILTER: the reference's local dist_cmps (:83,137); dcmps is full_dist_cmps
+    [[maybe_unused]] float fsum = 0.0f, fthr = 0.0f;   // FILTER: filter_threshold_sum / filter_threshold (:98-100)
+    [[maybe_unused]] uint32_t fcount = 0;
 #ifdef PANN_STAMPS
     unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
@@ -466,6 +518,15 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
         const bool full = (f == beam);                      // :115
         uint32_t cutoff_ord = BIG_ORD;                      // :150-152
         if (full) cutoff_ord = (uint32_t)(F[f - 1] >> 32);
+        if constexpr (FILTER) {
+          // ---- running mean of the sketch distance to the worst frontier entry (:119-123): small integers, so the f32 sum is
+          // exact; ONE IEEE-rounded division, as the reference's float / int ----
+          if (full) {
+            fsum += sketch_distance(P, SQ, key_id(F[f - 1]));
+            fcount++;
+            fthr = __fdiv_rn(fsum, (float)fcount);
+          }
+        }
 
         // ---- adjacency row: lane i <- slot i; degree = number of non-sentinel slots ----
         const uint32_t* row = P.graph + (size_t)cur * P.gstride;
@@ -479,7 +540,11 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
           if (am == 0ull) break;
           degsum += __popcll(am);
           const bool seen = filter_update<HASH_LDS>(H, hmask, act, a, lane, reinterpret_cast<uint8_t*>(Hl));
-          const bool keep = act && !seen && ((int64_t)a != self);     // :133
+          bool keep = act && !seen && ((int64_t)a != self);           // :133
+          if constexpr (FILTER) {
+            pcmps += __popcll(__ballot(keep));                        // dist_cmps += pruned.size() (:137)
+            if (full && keep) keep = !(sketch_distance(P, SQ, a) >= fthr);   // :140-145; not full: everything passes (:146)
+          }
           const uint64_t km = __ballot(keep);
           const uint32_t m = __popcll(km);
           if (keep) PANN_PL[lanes_below(km, lane)] = a;
@@ -614,6 +679,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
       if (P.out.visited_count) P.out.visited_count[qi] = nvis;
       if (P.out.dist_cmps) P.out.dist_cmps[qi] = dcmps;
       if (P.out.degree_sum) P.out.degree_sum[qi] = degsum;
+      if constexpr (FILTER) if (P.pruned_cmps) P.pruned_cmps[qi] = pcmps;
     }
     PANN_WSYNC();
     if constexpr (HASH_LDS) break;
@@ -1306,6 +1372,7 @@ struct Plan {
   bool b128_hbm;   // beam 65..128 with the filter in HBM (persistent blocks)
   uint32_t hsplit; // ... of which the part with an LDS share (filter_update split mode)
   uint32_t p24;    // ... stored as planar 24-bit entries
+  bool filter; uint32_t sk_lds_off;   // sketch-filtered search: the generic kernel's FILTER variant, query sketch after its LDS state
 };
 
 static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
@@ -1325,6 +1392,13 @@ static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
   p.hash_lds = (hbytes <= 16384) && (fixed + hbytes <= 64 * 1024);
   p.lds_bytes = (uint32_t)(fixed + (p.hash_lds ? hbytes : 1024));      // HBM filter: 1 KB replay scratch (filter_update)
   p.slots = 256 * 8;
+  p.filter = a.filter != 0; p.sk_lds_off = 0;
+  if (p.filter) {     // every beam width takes the generic kernel; its LDS state, then the query sketch
+    p.b64 = p.b128 = p.b128_codes = p.b128_hbm = false; p.hsplit = 0; p.p24 = 0;
+    p.sk_lds_off = (p.lds_bytes + 15u) & ~15u;
+    p.lds_bytes = p.sk_lds_off + ix.sk_stride;
+    return p;
+  }
   p.b64 = p.hash_lds && p.bcap == 64;
   if (p.b64) {   // register-frontier kernel: scratch[64] + candidates (exact, 8-entry granules) + flags + query + filter
     p.ccap = (std::max<uint32_t>(beam / 8 + p.deg_eff, a.nstarts) + 7) / 8 * 8;
@@ -1373,7 +1447,20 @@ size_t search_workspace_bytes(const DeviceIndex& ix, const SearchArgs& a) {
 
 template <int DT, int METRIC, int LPC, bool NCH1>
 static hipError_t launch_variant(const BSParams& P, const Plan& p, hipStream_t stream) {
-  if (p.b64) {   // frontier in registers
+  if (p.filter) {   // generic kernel with the sketch filter
+    if (p.hash_lds) {
+      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, true>;
+      if (p.lds_bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+      hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    } else {
+      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, true>;
+      if (p.lds_bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+      const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    }
+  } else if (p.b64) {   // frontier in registers
     auto kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
     hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
   } else if (p.b128_codes) {   // two frontier entries per lane, filter of class codes
@@ -1431,6 +1518,15 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   if ((a.queries == nullptr) == (a.query_ids == nullptr)) {
     set_error("pann_batch_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG;
   }
+  if (a.filter) {
+    if (!ix.sketch || !sketch_kind_ok(ix.sk_kind)) { set_error("pann_batch_search_filtered: no sketch attached to the index"); return PANN_ERR_BAD_ARG; }
+    if ((a.queries != nullptr) != (a.sketch_queries != nullptr)) {
+      set_error("pann_batch_search_filtered: sketch_queries go with queries, and only with them"); return PANN_ERR_BAD_ARG;
+    }
+    if (a.sketch_queries && (a.sq_stride < sketch_row_bytes(ix.sk_kind, ix.d) || a.sq_stride % 8 != 0 || (uintptr_t)a.sketch_queries % 8 != 0)) {
+      set_error("pann_batch_search_filtered: sketch query stride smaller than a sketch row, or rows not 8-byte aligned"); return PANN_ERR_BAD_ARG;
+    }
+  }
   Plan p = make_plan(ix, a);
   if (p.lds_bytes > 160 * 1024) { set_error("pann_batch_search: beam/degree too large for LDS state"); return PANN_ERR_UNSUPPORTED; }
   if (search_workspace_bytes(ix, a) > ws_bytes) { set_error("pann_batch_search: workspace too small"); return PANN_ERR_BAD_ARG; }
@@ -1461,6 +1557,11 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   P.hash_global = p.hash_lds ? nullptr : (uint32_t*)(w + 256 + (size_t)a.nq * p.dcap * 8);
   P.out = a.out;
   P.stamps = nullptr;
+  P.sketch = a.filter ? ix.sketch : nullptr; P.sk_stride = a.filter ? ix.sk_stride : 0u;
+  P.sk_kind = (uint32_t)ix.sk_kind; P.sk_as_written = ix.sk_as_written; P.sk_nblk = (ix.d + 63) / 64;
+  P.sketch_queries = a.sketch_queries; P.sq_stride = a.sq_stride;
+  P.sk_row_bytes = a.filter ? sketch_row_bytes(ix.sk_kind, ix.d) : 0u;
+  P.sk_lds_off = p.sk_lds_off; P.pruned_cmps = a.filter ? a.pruned_cmps : nullptr;
 #ifdef PANN_STAMPS
   static unsigned long long* d_stamps = nullptr; static size_t stamps_cap = 0;
   if (stamps_cap < a.nq) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void**)&d_stamps, a.nq * 64); stamps_cap = a.nq; }

@@ -49,6 +49,11 @@ struct DeviceIndex {
   // (vamana_build.hip: queries that run side by side then read rows of the same few regions); null = not computed
   const uint32_t* cell = nullptr;     // [n]
   uint32_t cell_min_batch = 4096;     // batches below this many searches keep the batch order
+  // bit sketch of every point (sketch.hip), the second level of the filtered searches; null = none attached
+  const uint8_t* sketch = nullptr;    // [n] rows of sk_stride bytes (host-layout row, zero padded to a multiple of 16)
+  uint32_t sk_stride = 0;
+  int sk_kind = -1;
+  uint32_t sk_as_written = 0;         // one-bit kinds: the reference's distance loop as written (block 0 counted num_blocks times)
 };
 
 // The kernels come in two families (PANN_LAYOUT_SWITCH): rows that are ONE 16-byte chunk per lane with 8 / 16 / 32
@@ -67,6 +72,11 @@ struct SearchArgs {  // one batched beam search, everything device resident
   uint32_t dcap = 256;                       // dropped-list entries per query (pann_index_reserve_dropped)
   const uint32_t* order = nullptr;           // device, nq entries: launch slot -> query index (a permutation); null = identity
   pann_search_out out;
+  // second level (filtered_beam_search with use_filtering): the handle's sketch decides which neighbours get a full distance
+  int filter = 0;
+  const uint8_t* sketch_queries = nullptr;   // nq host-layout sketch rows (external queries); base-point queries use their own row
+  uint64_t sq_stride = 0;
+  uint32_t* pruned_cmps = nullptr;           // nq, optional: the reference's local dist_cmps (starts + sum of pruned.size())
 };
 
 // per-handle scratch that the search kernels need (grown on demand, never shrunk)
@@ -156,6 +166,20 @@ int quant_translate_dev(const pann_quant_params* p, const float* d_rows, uint64_
 // p == nullptr: normalised f32 rows to d_out (may be d_rows: in place); else normalise and translate, bytes to d_out
 int quant_normalize_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, const pann_quant_params* p, void* d_out,
                         uint64_t out_stride, hipStream_t st);
+
+int quant_select_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, uint64_t rank_a, uint64_t rank_b, float* val_a,
+                     float* val_b, void* scratch, hipStream_t st);  // values at two sorted positions; synchronises st
+
+// sketch.hip: bit sketches of f32 rows
+bool sketch_kind_ok(int kind);
+uint32_t sketch_row_bytes(int kind, uint32_t d);                  // the reference's num_bytes()
+uint32_t sketch_dev_stride(int kind, uint32_t d);                 // ... padded to a multiple of 16
+void sketch_select_ranks(uint64_t len, int kind, uint64_t* a, uint64_t* b);
+int sketch_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, int kind, pann_sketch_params* out, void* scratch,
+                      hipStream_t st);                            // synchronises st
+// out_row_bytes (a multiple of 8, >= sketch_row_bytes) are written per row: the row's words, then zeros
+int sketch_translate_dev(const pann_sketch_params* p, const float* d_rows, uint64_t n, uint64_t stride, void* d_out, uint64_t out_stride,
+                         uint32_t out_row_bytes, hipStream_t st);
 
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,

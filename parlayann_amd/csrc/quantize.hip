@@ -371,10 +371,36 @@ void quant_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b) {
   if (*b >= len) *b = len - 1;
 }
 
+// The values at sorted positions rank_a and rank_b of the n * d floats (exact: three histogram passes, nothing is sorted).
+// Synchronises st: the two keys come back to the host.
+int quant_select_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, uint64_t rank_a, uint64_t rank_b, float* val_a,
+                     float* val_b, void* scratch, hipStream_t st) {
+  uint8_t* sc = static_cast<uint8_t*>(scratch);
+  unsigned long long* hist = reinterpret_cast<unsigned long long*>(sc + SCRATCH_HIST_OFF);
+  View v[2];
+  const int nv = make_views(d_rows, n, d, stride, nullptr, 0, v);
+  hipLaunchKernelGGL(quant_init_kernel, dim3(1), dim3(256), 0, st, sc, (int)PANN_QUANT_MIPS_I8, (unsigned long long)rank_a, (unsigned long long)rank_b);
+  PANN_HIP(hipGetLastError());
+  SelectState* dst = reinterpret_cast<SelectState*>(sc);
+  for (int pass = 1; pass <= 3; pass++) {
+    for (int i = 0; i < nv; i++) {
+      int rc = pass == 1 ? launch_hist<1>(v[i], dst, hist, st) : pass == 2 ? launch_hist<2>(v[i], dst, hist, st) : launch_hist<3>(v[i], dst, hist, st);
+      if (rc) return rc;
+    }
+    hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(256), 0, st, dst, hist, pass);
+    PANN_HIP(hipGetLastError());
+  }
+  SelectState h{};
+  PANN_HIP(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  *val_a = key_to_float(h.prefix[0]);
+  *val_b = key_to_float(h.prefix[1]);
+  return PANN_OK;
+}
+
 int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, int kind, int trim, pann_quant_params* out,
                      void* scratch, hipStream_t st) {
   uint8_t* sc = static_cast<uint8_t*>(scratch);
-  unsigned long long* hist = reinterpret_cast<unsigned long long*>(sc + SCRATCH_HIST_OFF);
   View v[2];
   const int nv = make_views(d_rows, n, d, stride, nullptr, 0, v);
   pann_quant_params p{};
@@ -406,21 +432,8 @@ int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t strid
   } else {
     uint64_t ra, rb;
     quant_select_ranks(n * (uint64_t)d, trim, &ra, &rb);
-    hipLaunchKernelGGL(quant_init_kernel, dim3(1), dim3(256), 0, st, sc, kind, (unsigned long long)ra, (unsigned long long)rb);
-    PANN_HIP(hipGetLastError());
-    SelectState* dst = reinterpret_cast<SelectState*>(sc);
-    for (int pass = 1; pass <= 3; pass++) {
-      for (int i = 0; i < nv; i++) {
-        int rc = pass == 1 ? launch_hist<1>(v[i], dst, hist, st) : pass == 2 ? launch_hist<2>(v[i], dst, hist, st) : launch_hist<3>(v[i], dst, hist, st);
-        if (rc) return rc;
-      }
-      hipLaunchKernelGGL(select_scan_kernel, dim3(1), dim3(256), 0, st, dst, hist, pass);
-      PANN_HIP(hipGetLastError());
-    }
-    SelectState h{};
-    PANN_HIP(hipMemcpyAsync(&h, sc, sizeof(h), hipMemcpyDeviceToHost, st));
-    PANN_HIP(hipStreamSynchronize(st));
-    const float min_val = key_to_float(h.prefix[0]), max_val = key_to_float(h.prefix[1]);
+    float min_val = 0.0f, max_val = 0.0f;
+    if (int rc = quant_select_dev(d_rows, n, d, stride, ra, rb, &min_val, &max_val, scratch, st)) return rc;
     p.max_val = std::max(max_val, -min_val);                                     // mips_point.h:484
     p.min_seen = min_val; p.max_seen = max_val;
   }

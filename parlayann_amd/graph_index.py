@@ -9,7 +9,7 @@ classes python/module.cpp registers (:50-57,150-155), over the C-ABI.
 """
 import numpy as np
 
-from . import io, quantize
+from . import io, quantize, sketch
 from .index import DeviceIndex
 from .recall import recall_at_k
 
@@ -18,9 +18,24 @@ class GraphIndex:
     T = None
     metric = None
 
-    def __init__(self, data_path, index_path, hnsw=False, device=0):
+    def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None):
+        """second_level: None | "bit" | "2bit" -- the three-range beam_search_rerank of graph_index.cpp:156-185: quantised
+        searches (quant=True) of the one-byte copy run with a bit-sketch pre-filter (filtered_beam_search, use_filtering) before
+        the exact rerank.  "bit": Euclidean_Bit_Point / Mips_Bit_Point by the metric; "2bit": Mips_2Bit_Point (mips only).
+        Off by default, so results do not change unless asked for.  It needs float points whose one-byte quantisation is not
+        the identity; anything else raises ValueError instead of searching unfiltered without notice.  The reference switches its second level on by itself for
+        Euclidian data of more than 800 dimensions (a JL sketch, which this build does not provide) and for mips data of more
+        than 200 dimensions (Mips_2Bit_Point: second_level="2bit" here)."""
         if hnsw:
             raise NotImplementedError("HNSW indices are out of scope (SURVEY.md section 2 #17)")
+        if second_level not in (None, "bit", "2bit"):
+            raise ValueError('second_level must be None, "bit" or "2bit"')
+        if second_level == "2bit" and self.metric == "Euclidian":
+            raise ValueError('second_level="2bit" (Mips_2Bit_Point) is a mips sketch')
+        if second_level is not None and np.dtype(self.T).itemsize == 1:
+            raise ValueError("second_level needs float points: one-byte indices are searched directly (no quantised copy to filter)")
+        self.second_level = second_level
+        self.sparams = None
         self.points = io.read_bin(data_path, self.T)
         self.graph = io.read_graph(index_path)
         if len(self.graph) != len(self.points):        # graph_index.cpp:113-116
@@ -41,6 +56,13 @@ class GraphIndex:
                 self.points = self.index.points()
                 self.q_index, self.qparams = self.index.quantized("mips_i8", trim=True)   # Quantized_Mips_Point<8,true> :69
                 self.mmax = np.float32(self.qparams.max_val)
+            if second_level is not None and self.metric == "Euclidian" and self.eparams.identity:
+                raise ValueError("second_level: these points quantise to themselves (slope 1), so quantised searches are plain "
+                                 "searches of the one-byte copy (graph_index.cpp:145-149) and nothing would be filtered")
+            if second_level is not None:                  # QQ range over the (normalised) float rows, owned by the one-byte handle
+                kind = "mips_2bit" if second_level == "2bit" else ("euclid_bit" if self.metric == "Euclidian" else "mips_bit")
+                self.sparams = sketch.sketch_params(self.index, kind)
+                sketch.attach_sketch(self.q_index, self.index, self.sparams)
 
     # QueryParams(knn, beam, 1.35, visit_limit, min(maxDeg, 3*visit_limit))   (:198,:222,:242)
     def _qp(self, knn, beam_width, visit_limit):
@@ -66,7 +88,11 @@ class GraphIndex:
             qq = quantize.device_quantize_rows(queries, self.qparams, normalize_first=True, device=self.device)
         # beam_search_rerank (beamSearch.h:390-454): search the quantised copy, re-score the first
         # min(k * rerank_factor, |beam|) with exact distances, sort, keep k
-        r = self.q_index.batch_search(qq, out_k=beam_width, **qp)
+        if self.sparams is not None:                                             # three ranges: use_filtering (:410)
+            sq = sketch.sketch_rows(full_q, self.sparams, device=self.device)
+            r = self.q_index.batch_search_filtered(qq, sq, out_k=beam_width, **qp)
+        else:
+            r = self.q_index.batch_search(qq, out_k=beam_width, **qp)
         self._need(r["frontier_size"], knn)
         counts = np.minimum(r["frontier_size"], knn * 100).astype(np.uint32)     # QP.rerank_factor = 100 (types.h:224)
         return self.index.rerank(full_q, r["ids"], counts, knn, resort=True)

@@ -1,6 +1,6 @@
 // beam_search.h -- host mirror of the search surface of algorithms/utils/beamSearch.h with the reference's own
 // names and argument lists:
-//   filtered_beam_search (:22-33, use_filtering == false)      beam_search (:217-223, :234-241)   beam_search_impl (:226-231)
+//   filtered_beam_search (:22-33; use_filtering with a sketch range: pann_batch_search_filtered)      beam_search (:217-223, :234-241)   beam_search_impl (:226-231)
 //   range_search (:245-306)      beamSearchRandom (:309-351)   searchAll (:353-387)
 //   beam_search_rerank (:390-454)   beam_search_rerank__ (:499-521)   qsearchAll (:537-565)
 // The CPU loop bodies are gone: every function is one (or, with a rerank, two) C-ABI call on the device mirror of
@@ -13,6 +13,7 @@
 
 #include "device_index.h"
 #include "parlay_compat.h"
+#include "sketch.h"
 #include "stats.h"
 #include "types.h"
 
@@ -42,7 +43,8 @@ inline void check_k_le_beam(const QueryParams& QP) {                       // be
 // one query on handle h: ((frontier, visited sorted by (dist,id)), dist_cmps).  self >= 0: the query is base point `self`
 template <typename indexType>
 beam_result<indexType> search_one(pann_index* h, const void* qvalues, uint64_t qbytes, long self, const indexType* starts,
-                                  size_t nstarts, const QueryParams& QP) {
+                                  size_t nstarts, const QueryParams& QP, bool filter = false, const void* sketch_q = nullptr,
+                                  uint64_t sketch_bytes = 0) {
   using id_dist = std::pair<indexType, float>;
   if (nstarts == 0) { std::cout << "beam search expects at least one start point" << std::endl; abort(); }   // :38-41
   const uint32_t beam = (uint32_t)QP.beamSize;
@@ -57,8 +59,11 @@ beam_result<indexType> search_one(pann_index* h, const void* qvalues, uint64_t q
     const pann_query_params q = to_pann(QP);
     const uint32_t qid = (uint32_t)self;
     std::vector<uint32_t> st(starts, starts + nstarts);
-    const int rc = pann_batch_search(h, self < 0 ? qvalues : nullptr, self < 0 ? nullptr : &qid, 1, qbytes, st.data(),
-                                     (uint32_t)nstarts, &q, &out);
+    // use_filtering: the handle's sketch decides; a base-point query uses its own sketch row (sketch_q is that same row)
+    const int rc = filter ? pann_batch_search_filtered(h, self < 0 ? qvalues : nullptr, self < 0 ? nullptr : &qid, 1, qbytes,
+                                                       self < 0 ? sketch_q : nullptr, sketch_bytes, st.data(), (uint32_t)nstarts, &q, &out, nullptr)
+                          : pann_batch_search(h, self < 0 ? qvalues : nullptr, self < 0 ? nullptr : &qid, 1, qbytes, st.data(),
+                                              (uint32_t)nstarts, &q, &out);
     if (rc == PANN_ERR_OVERFLOW && vc > vcap) { vcap = vc; continue; }
     if (rc == PANN_ERR_OVERFLOW) { vcap *= 4; continue; }
     pann_check(rc);
@@ -108,7 +113,8 @@ template <class PointRange, class QPointRange, typename indexType>
 parlay::sequence<parlay::sequence<indexType>> search_rerank_batch(pann_index* h, pann_index* qh, const PointRange& Query_Points,
                                                                   const QPointRange& Q_Query_Points, stats<indexType>& QueryStats,
                                                                   indexType starting_point, const QueryParams& QP, bool count_stats,
-                                                                  std::vector<float>* dists_out = nullptr) {
+                                                                  std::vector<float>* dists_out = nullptr, const void* sketch_q = nullptr,
+                                                                  uint64_t sketch_stride = 0) {
   check_k_le_beam(QP);
   const size_t nq = Query_Points.size();
   const uint32_t k = (uint32_t)QP.k, beam = (uint32_t)QP.beamSize;
@@ -118,7 +124,10 @@ parlay::sequence<parlay::sequence<indexType>> search_rerank_batch(pann_index* h,
   out.ids = ids.data(); out.out_k = beam; out.frontier_size = fs.data(); out.visited_count = vc.data(); out.dist_cmps = dc.data();
   const pann_query_params q = to_pann(QP);
   const uint32_t start = starting_point;
-  pann_check(pann_batch_search(qh, Q_Query_Points.data(), nullptr, nq, Q_Query_Points.get_aligned_bytes(), &start, 1, &q, &out));
+  // sketch_q: the QQ query rows -- the batch is ONE filtered_beam_search(..., use_filtering = true) launch (:410-414)
+  if (sketch_q) pann_check(pann_batch_search_filtered(qh, Q_Query_Points.data(), nullptr, nq, Q_Query_Points.get_aligned_bytes(), sketch_q,
+                                                      sketch_stride, &start, 1, &q, &out, nullptr));
+  else pann_check(pann_batch_search(qh, Q_Query_Points.data(), nullptr, nq, Q_Query_Points.get_aligned_bytes(), &start, 1, &q, &out));
   std::vector<uint32_t> counts(nq);
   for (size_t i = 0; i < nq; i++) {
     if (fs[i] < k) {                                                                                  // :416-419
@@ -174,14 +183,25 @@ inline uint64_t random_start(uint64_t i, uint64_t n) {
 // the reference's argument lists
 // ============================================================================================================
 
-// filtered_beam_search(G, p, Points, qp, Q_Points, starting_points, QP, use_filtering)   (:22-33).  The second-level
-// filter (use_filtering == true: :119-123,140-146) is outside this build's scope (only reachable
-// with -quantize_mode >= 2 or d > 800); without it qp / Q_Points are not read (:150-159 use p / Points).
+// filtered_beam_search(G, p, Points, qp, Q_Points, starting_points, QP, use_filtering)   (:22-33).  Without the second-level
+// filter qp / Q_Points are not read (:150-159 use p / Points).  With it (:119-123,140-146) Q_Points must be a range of sketch
+// points (sketch.h): its rows become the sketch of the mirror of (G, Points) and the search is pann_batch_search_filtered; the
+// returned count is full_dist_cmps (:213).  A filter range of any other point type is not mirrored.
 template <typename indexType, typename Point, typename PointRange, typename QPoint, typename QPointRange>
-beam_result<indexType> filtered_beam_search(const Graph<indexType>& G, const Point p, const PointRange& Points, const QPoint /*qp*/,
-                                            const QPointRange& /*Q_Points*/, const parlay::sequence<indexType> starting_points,
+beam_result<indexType> filtered_beam_search(const Graph<indexType>& G, const Point p, const PointRange& Points, const QPoint qp,
+                                            const QPointRange& Q_Points, const parlay::sequence<indexType> starting_points,
                                             const QueryParams& QP, bool use_filtering = false) {
-  if (use_filtering) { std::cout << "Error: filtered_beam_search with use_filtering is not mirrored on the device" << std::endl; abort(); }
+  if (use_filtering) {
+    if constexpr (is_sketch_point<typename QPointRange::Point>::value) {
+      auto L = device_mirror(G, Points);
+      ensure_sketch(L, Q_Points);
+      return detail::search_one<indexType>(L.h(), p.values, (uint64_t)p.params.num_bytes(), own_vertex(p, Points), starting_points.data(),
+                                           starting_points.size(), QP, true, qp.values, (uint64_t)qp.params.num_bytes());
+    } else {
+      std::cout << "Error: filtered_beam_search with use_filtering is not mirrored on the device for this filter range (bit sketches are)" << std::endl;
+      abort();
+    }
+  }
   auto L = device_mirror(G, Points);
   return detail::search_one<indexType>(L.h(), p.values, (uint64_t)p.params.num_bytes(), own_vertex(p, Points), starting_points.data(),
                                        starting_points.size(), QP);
@@ -249,23 +269,17 @@ parlay::sequence<parlay::sequence<indexType>> searchAll(PointRange& Query_Points
 }
 
 // beam_search_rerank(p, qp, qqp, G, Base_Points, Q_Base_Points, QQ_Base_Points, QueryStats, starting_points, QP, stats)
-// -> k (id, exact distance) pairs   (:390-454).  QQ ranges must have the Q ranges' num_bytes() (no second-level filter).
+// -> k (id, exact distance) pairs   (:390-454).  QQ ranges whose num_bytes() differ from the Q ranges' switch the sketch
+// filter on (:410) and must be ranges of sketch points (sketch.h).
 template <typename Point, typename QPoint, typename QQPoint, typename PointRange, typename QPointRange, typename QQPointRange,
           typename indexType>
-id_dist_seq<indexType> beam_search_rerank(const Point& p, const QPoint& qp, const QQPoint& /*qqp*/, const Graph<indexType>& G,
+id_dist_seq<indexType> beam_search_rerank(const Point& p, const QPoint& qp, const QQPoint& qqp, const Graph<indexType>& G,
                                           const PointRange& Base_Points, const QPointRange& Q_Base_Points,
                                           const QQPointRange& QQ_Base_Points, stats<indexType>& QueryStats,
                                           const parlay::sequence<indexType> starting_points, const QueryParams& QP, bool stats_ = true) {
-  if (Q_Base_Points.params.num_bytes() != QQ_Base_Points.params.num_bytes()) {
-    std::cout << "Error: beam_search_rerank with a second-level filter range is not mirrored on the device" << std::endl; abort();
-  }
+  const bool use_filtering = Q_Base_Points.params.num_bytes() != QQ_Base_Points.params.num_bytes();    // :410
   const bool use_rerank = Base_Points.params.num_bytes() != Q_Base_Points.params.num_bytes();
-  beam_result<indexType> r;
-  {
-    auto QL = device_mirror(G, Q_Base_Points);
-    r = detail::search_one<indexType>(QL.h(), qp.values, (uint64_t)qp.params.num_bytes(), own_vertex(qp, Q_Base_Points),
-                                      starting_points.data(), starting_points.size(), QP);
-  }
+  beam_result<indexType> r = filtered_beam_search(G, qp, Q_Base_Points, qqp, QQ_Base_Points, starting_points, QP, use_filtering);
   const auto& beamElts = r.first.first;
   if ((long)beamElts.size() < QP.k) {
     std::cout << "Error: for point id " << p.id() << " beam search returned " << beamElts.size() << " elements, which is less than k = " << QP.k << std::endl;
@@ -300,14 +314,29 @@ std::pair<id_dist_seq<indexType>, indexType> beam_search_rerank__(const Point& p
 //            starting_point, QP)   (:537-565)
 template <typename PointRange, typename QPointRange, typename QQPointRange, typename indexType>
 parlay::sequence<parlay::sequence<indexType>> qsearchAll(const PointRange& Query_Points, const QPointRange& Q_Query_Points,
-                                                         const QQPointRange& /*QQ_Query_Points*/, const Graph<indexType>& G,
+                                                         const QQPointRange& QQ_Query_Points, const Graph<indexType>& G,
                                                          const PointRange& Base_Points, const QPointRange& Q_Base_Points,
                                                          const QQPointRange& QQ_Base_Points, stats<indexType>& QueryStats,
                                                          const indexType starting_point, const QueryParams& QP,
                                                          std::vector<float>* dists_out = nullptr) {
   detail::check_k_le_beam(QP);
-  if (Q_Base_Points.params.num_bytes() != QQ_Base_Points.params.num_bytes()) {
-    std::cout << "Error: qsearchAll with a second-level filter range is not mirrored on the device" << std::endl; abort();
+  if (Q_Base_Points.params.num_bytes() != QQ_Base_Points.params.num_bytes()) {      // use_filtering (:410): one filtered launch
+    if constexpr (is_sketch_point<typename QQPointRange::Point>::value) {
+      if (QQ_Query_Points.size() != Query_Points.size()) { std::cout << "Error: qsearchAll: QQ_Query_Points and Query_Points differ in size" << std::endl; abort(); }
+      auto QL = device_mirror(G, Q_Base_Points);
+      ensure_sketch(QL, QQ_Base_Points);
+      if ((const void*)Base_Points.data() == (const void*)Q_Base_Points.data())
+        return detail::search_rerank_batch<PointRange, QPointRange, indexType>(QL.h(), QL.h(), Query_Points, Q_Query_Points, QueryStats, starting_point,
+                                                                                QP, true, dists_out, QQ_Query_Points.data(),
+                                                                                QQ_Query_Points.get_aligned_bytes());
+      auto L = device_mirror(G, Base_Points);
+      return detail::search_rerank_batch<PointRange, QPointRange, indexType>(L.h(), QL.h(), Query_Points, Q_Query_Points, QueryStats, starting_point,
+                                                                              QP, true, dists_out, QQ_Query_Points.data(),
+                                                                              QQ_Query_Points.get_aligned_bytes());
+    } else {
+      std::cout << "Error: qsearchAll with a second-level filter range is not mirrored on the device for this filter range (bit sketches are)" << std::endl;
+      abort();
+    }
   }
   if ((const void*)Base_Points.data() == (const void*)Q_Base_Points.data()) {      // un-quantised: one mirror serves both steps
     auto L = device_mirror(G, Base_Points);

@@ -6,7 +6,7 @@
 // Flags as upstream: -base_path -query_path -gt_path -graph_path -graph_outfile -res_path -data_type {uint8,int8,float}
 //   -dist_func {Euclidian,mips} -k -Q -R -L -alpha -num_passes -two_pass -mst_deg -num_clusters -cluster_size -delta
 //   -quantize_bits {0,8} -quantize_mode {0,1} -verbose -normalize -self -range -radius -radius_2 -rerank_factor
-//   (-quantize_bits 16 and -quantize_mode 2..5 are rejected: out of scope).
+//   (-quantize_mode 2 and, for mips, 3 need -graph_path: vamana/neighbors.h; -quantize_bits 16 and the other modes are rejected.)
 // Added here: -device <ordinal>, -seed <s>, -use_existing (self range search seeded with out-neighbours),
 //   -host_tree (HCNNG cross-check path).
 #include <chrono>
@@ -121,7 +121,7 @@ const FlagSpec kFlags[] = {
     {"-trim", Kind::real, 0, -kAny, kAny, false, ""},
     // transforms and modes
     {"-quantize_bits", Kind::integer, 0, -kAny, kAny, false, "0 | 8"},
-    {"-quantize_mode", Kind::integer, 0, -kAny, kAny, false, "0 | 1"},
+    {"-quantize_mode", Kind::integer, 0, -kAny, kAny, false, "0 | 1 | 2 | 3 (2, 3: with -graph_path)"},
     {"-verbose", Kind::toggle, 0, 0, 0, false, ""},
     {"-normalize", Kind::toggle, 0, 0, 0, false, ""},
     {"-self", Kind::toggle, 0, 0, 0, false, ""},

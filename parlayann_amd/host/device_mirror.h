@@ -40,6 +40,7 @@ struct DeviceMirror {
   pann_index* h = nullptr;
   const void* pts = nullptr; const void* graph = nullptr; int device = 0;
   uint64_t pts_version = 0, graph_version = 0;
+  const void* sketch_src = nullptr; uint64_t sketch_version = 0;   // the QQ range whose rows the handle holds as its sketch (sketch.h)
   std::function<bool()> alive;
   std::mutex busy;
   ~DeviceMirror() { if (h) pann_index_destroy(h); }

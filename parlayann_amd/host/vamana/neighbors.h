@@ -3,8 +3,9 @@
 //   ANN_Quantized<PR, QPR, QQPR, indexType>(G, k, BP, Query_Points, Q_Query_Points, QQ_Query_Points, GT, res_file,
 //                                           graph_built, Points, Q_Points, QQ_Points)                       :42-110
 // Same argument lists, same printed report; build, search and range search run on the device mirrors.
-// BP.quantize: 0 (none) and 1 (one-byte build + first search pass, full-precision rerank) are mirrored; the
-// bit / JL sketches of modes 2-5 (:126-183) are out of scope.
+// BP.quantize: 0 (none) and 1 (one-byte build + first search pass, full-precision rerank) are mirrored; with a prebuilt graph
+// (-graph_path) so are the bit-sketch second levels: 2 (Euclidean_Bit_Point / Mips_Bit_Point by the metric, :128-134,153-159)
+// and, for MIPS, 3 (Mips_2Bit_Point, :160-166).  Sketch-filtered BUILDS and the JL / 4-bit sketches (3 for L2, 4, 5) are not.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -13,6 +14,7 @@
 #include "../check_nn_recall.h"
 #include "../parse_results.h"
 #include "../quantize.h"
+#include "../sketch.h"
 #include "../stats.h"
 #include "../types.h"
 #include "../vamana_index.h"
@@ -95,7 +97,13 @@ void ANN(Graph<indexType>& G, long k, BuildParams& BP, PointRange_& Query_Points
          bool graph_built, PointRange_& Points) {
   if (BP.quantize != 0) {
     std::cout << "quantizing build and first pass of search to 1 byte" << std::endl;
-    if (BP.quantize != 1) { std::cout << "Error: -quantize_mode " << BP.quantize << " (bit / JL sketches) is not mirrored; modes 0 and 1 are" << std::endl; abort(); }
+    const bool sketch_mode = BP.quantize == 2 || (BP.quantize == 3 && Point::metric == PANN_MIPS);
+    if (BP.quantize != 1 && !sketch_mode) {
+      std::cout << "Error: -quantize_mode " << BP.quantize << " (JL / 4-bit sketches) is not mirrored; modes 0, 1, 2 and (mips) 3 are" << std::endl; abort();
+    }
+    if (sketch_mode && !graph_built) {
+      std::cout << "Error: -quantize_mode " << BP.quantize << " without -graph_path: sketch-filtered builds are not mirrored on the device" << std::endl; abort();
+    }
     if constexpr (!std::is_same<typename Point::T, float>::value) {
       std::cout << "Error: -quantize_mode needs float points" << std::endl; abort();
     } else if constexpr (Point::metric == PANN_L2) {
@@ -103,13 +111,32 @@ void ANN(Graph<indexType>& G, long k, BuildParams& BP, PointRange_& Query_Points
       const euclid_u8_parameters pm = generate_parameters_u8(Points);
       QPR Q_Points = quantize_u8(Points, pm);
       QPR Q_Query_Points = quantize_u8(Query_Points, pm);
-      ANN_Quantized(G, k, BP, Query_Points, Q_Query_Points, Q_Query_Points, GT, res_file, graph_built, Points, Q_Points, Q_Points);
+      if (BP.quantize == 1) {
+        ANN_Quantized(G, k, BP, Query_Points, Q_Query_Points, Q_Query_Points, GT, res_file, graph_built, Points, Q_Points, Q_Points);
+      } else {                                                               // :128-134
+        using QQPR = PointRange<Euclidean_Bit_Point>;
+        QQPR QQ_Points(Points);
+        QQPR QQ_Query_Points(Query_Points, QQ_Points.params);
+        ANN_Quantized(G, k, BP, Query_Points, Q_Query_Points, QQ_Query_Points, GT, res_file, graph_built, Points, Q_Points, QQ_Points);
+      }
     } else {
       using QPR = PointRange<Mips_Point<int8_t>>;                            // Quantized_Mips_Point<8,true,255> (:146-149)
       const float mv = generate_max_val_mips_i8(Points, true);
       QPR Q_Points = quantize_mips_i8(Points, mv);
       QPR Q_Query_Points = quantize_mips_i8(Query_Points, mv);
-      ANN_Quantized(G, k, BP, Query_Points, Q_Query_Points, Q_Query_Points, GT, res_file, graph_built, Points, Q_Points, Q_Points);
+      if (BP.quantize == 1) {
+        ANN_Quantized(G, k, BP, Query_Points, Q_Query_Points, Q_Query_Points, GT, res_file, graph_built, Points, Q_Points, Q_Points);
+      } else if (BP.quantize == 2) {                                         // :153-159
+        using QQPR = PointRange<Mips_Bit_Point>;
+        QQPR QQ_Points(Points);
+        QQPR QQ_Query_Points(Query_Points, QQ_Points.params);
+        ANN_Quantized(G, k, BP, Query_Points, Q_Query_Points, QQ_Query_Points, GT, res_file, graph_built, Points, Q_Points, QQ_Points);
+      } else {                                                               // :160-166
+        using QQPR = PointRange<Mips_2Bit_Point>;
+        QQPR QQ_Points(Points);
+        QQPR QQ_Query_Points(Query_Points, QQ_Points.params);
+        ANN_Quantized(G, k, BP, Query_Points, Q_Query_Points, QQ_Query_Points, GT, res_file, graph_built, Points, Q_Points, QQ_Points);
+      }
     }
   } else {
     ANN_Quantized(G, k, BP, Query_Points, Query_Points, Query_Points, GT, res_file, graph_built, Points, Points, Points);

@@ -238,6 +238,21 @@ class DeviceIndex:
     # ---- batched beam search: the searchAll / qsearchAll seam (beamSearch.h:374,556) ----
     def batch_search(self, queries=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
                      query_ids=None, out_k=None, visited_cap=0, want_dists=True):
+        return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists)
+
+    def batch_search_filtered(self, queries=None, sketch_queries=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None,
+                              starts=(0,), query_ids=None, out_k=None, visited_cap=0, want_dists=True):
+        """filtered_beam_search(..., use_filtering = true) (beamSearch.h:117-123,139-146) with the sketch attached to this
+        index (parlayann_amd.sketch.attach_sketch).  queries go with sketch_queries (uint8[nq, num_bytes()], sketch.sketch_rows);
+        query_ids use the index's own sketch rows.  Returns what batch_search returns -- dist_cmps being the reference's
+        full_dist_cmps -- plus "pruned_cmps": starts + neighbours that passed the hash filter."""
+        if (queries is None) != (sketch_queries is None):
+            raise ValueError("sketch_queries go with queries, and only with them")
+        return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
+                                  filtered=True, sketch_queries=sketch_queries)
+
+    def _batch_search(self, queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
+                      filtered=False, sketch_queries=None):
         nq = len(queries) if queries is not None else len(query_ids)
         qp = QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
                          degree_limit=self.max_degree if degree_limit is None else degree_limit,
@@ -270,6 +285,19 @@ class DeviceIndex:
             stride = _row_stride(q)
         else:
             qid = np.ascontiguousarray(query_ids, dtype=np.uint32)
+        if filtered:
+            if per_query:
+                raise ValueError("filtered searches take shared starts")
+            sq = None
+            if sketch_queries is not None:
+                sq = np.ascontiguousarray(sketch_queries, dtype=np.uint8)
+                if sq.ndim != 2 or sq.shape[0] != nq:
+                    raise ValueError("sketch_queries must be nq rows of uint8")
+            res["pruned_cmps"] = np.empty(nq, dtype=np.uint32)
+            check(self._lib.pann_batch_search_filtered(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(sq), 0 if sq is None else sq.shape[1],
+                                                       _ptr(starts), starts.shape[-1], C.byref(qp), C.byref(out),
+                                                       _ptr(res["pruned_cmps"])))
+            return res
         fn = self._lib.pann_batch_search_per_query_starts if per_query else self._lib.pann_batch_search
         check(fn(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1], C.byref(qp), C.byref(out)))
         return res

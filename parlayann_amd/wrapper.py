@@ -53,12 +53,13 @@ def build_hnsw_index(*a, **k):
     raise NotImplementedError("HNSW is out of scope (SURVEY.md section 2 #17)")
 
 
-def load_index(metric, dtype, data_dir, index_dir, hnsw=False):
+def load_index(metric, dtype, data_dir, index_dir, hnsw=False, second_level=None):
+    """second_level: None | "bit" | "2bit", see GraphIndex"""
     _check(metric, dtype)
     cls = {("Euclidian", "uint8"): UInt8EuclidianIndex, ("Euclidian", "int8"): Int8EuclidianIndex,
            ("Euclidian", "float"): FloatEuclidianIndex, ("mips", "uint8"): UInt8MipsIndex,
            ("mips", "int8"): Int8MipsIndex, ("mips", "float"): FloatMipsIndex}[(metric, dtype)]
-    return cls(data_dir, index_dir, hnsw)
+    return cls(data_dir, index_dir, hnsw, second_level=second_level)
 
 
 # ---- HCNNG through the C++ host mirror (parlayann_amd/host/hcnng_index.h), compiled into
