@@ -15,6 +15,7 @@
  *   data_tools/compute_groundtruth.cpp:22-59 brute-force kNN               -> pann_bruteforce_knn
  *   data_tools/compute_range_groundtruth.cpp:13-29 brute-force radius join -> pann_bruteforce_range
  *   algorithms/utils/beamSearch.h:567-614  RangeSearch (beam search + BFS)  -> pann_range_query
+ *   algorithms/utils/beamSearch.h:390-454  beam_search_rerank (quantised)   -> pann_batch_search_rerank*
  *
  * The reference has no FFI of its own for this path (it is a header-only template library); these
  * entry points are what a cgo/ctypes/pybind binding placed at the parallel_for seams above would
@@ -98,6 +99,8 @@ typedef struct pann_search_out {
                                            results of this launch are NOT valid.  The host entry points grow the scratch
                                            and run the batch again by themselves; after a _dev launch that reports it,
                                            call pann_index_reserve_dropped() with a larger capacity and launch again. */
+#define PANN_STATUS_SHORT_FRONTIER 4u   /* pann_batch_search_rerank*: some query's frontier held fewer than k entries
+                                           (beamSearch.h:416-419); its row is padded with 0xFFFFFFFF / +inf */
 
 typedef struct pann_index pann_index;
 
@@ -492,6 +495,46 @@ int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const
                                    uint64_t q_stride_bytes, const void* d_sketch_queries, uint64_t sq_stride_bytes,
                                    const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
                                    const pann_search_out* d_out, uint32_t* d_out_pruned_cmps, void* stream);
+
+/* ---- quantised search + exact rerank in one call: beam_search_rerank (beamSearch.h:390-454) ----
+ * full: the f32 handle; quant: its one-byte copy (pann_index_create_quantized(full, qparams, ...): same n, d, device and
+ * metric).  Per batch of nq float query rows, all on the device and all on one stream:
+ *   1. one kernel reads every query row once and writes its one-byte row (bit-identical to pann_quantize_rows_dev), with
+ *      normalize_first the Point::normalize'd float row the rerank scores against, and with use_filter the sketch row
+ *      (bit-identical to pann_sketch_rows_dev, parameters of the sketch attached to quant);
+ *   2. the beam search of pann_batch_search_dev (use_filter: pann_batch_search_filtered_dev) on quant with *qp;
+ *   3. the first num_check = min(qp->k * qp->rerank_factor, frontier size) (:428) frontier ids get their exact distance on
+ *      `full` (the arithmetic of pann_rerank, exact-float-order flag included), are sorted by (dist, id), and k are kept.
+ * Results equal pann_quantize_rows (+ pann_sketch_rows), pann_batch_search[_filtered] with out_k = beam and pann_rerank
+ * (resort = 1) run one after the other, bit for bit.  A query whose frontier holds fewer than k entries writes what it has
+ * and raises PANN_STATUS_SHORT_FRONTIER (the reference aborts there, :416-419; callers reproduce that).
+ * Scratch (one-byte / sketch / normalised queries, frontiers) belongs to quant and grows on first use. */
+typedef struct pann_rerank_out {
+  uint32_t* ids;            /* nq x k, sorted by (exact dist, id); unused slots 0xFFFFFFFF */
+  float*    dists;          /* nq x k, exact distances on the full-precision handle; unused slots +inf */
+  uint32_t* frontier_size;  /* nq, of the quantised search                      (optional) */
+  uint32_t* visited_count;  /* nq                                               (optional) */
+  uint32_t* dist_cmps;      /* nq, full_dist_cmps of the quantised search       (optional) */
+  uint32_t* pruned_cmps;    /* nq, only with use_filter                         (optional) */
+  uint32_t* status;         /* 1 word: PANN_STATUS_* bits of this call          (optional) */
+} pann_rerank_out;
+
+/* Device pointers throughout, launched on `stream`; no synchronisation, and no allocation once quant's scratch has reached
+ * its size (call once to warm up).  d_out->status is written on the stream, as by pann_batch_search_dev.
+ * Status: NULL handles / qparams / qp / out / ids / dists / queries / starts, k == 0, k > beam, nstarts == 0, handles that
+ * differ in n, d, device or metric, a kind that does not fit quant's element type, use_filter without a sketch attached to
+ * quant, a row stride shorter than a row or not a multiple of 4, beam > 4096 -> PANN_ERR_BAD_ARG; a `full` handle that is
+ * not f32 -> PANN_ERR_UNSUPPORTED; nq == 0 -> PANN_OK.  Nothing is written on an error. */
+int pann_batch_search_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams,
+                                 const float* d_queries, uint64_t nq, uint64_t q_stride_bytes, int normalize_first,
+                                 int use_filter, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                 const pann_rerank_out* d_out, void* stream);
+/* Host pointers: queries and starts go up in one transfer, the outputs come back in one.  A launch that reports
+ * PANN_STATUS_DROPPED_OVERFLOW is grown and run again as by pann_batch_search.  Runs on quant's stream. */
+int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                             uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter,
+                             const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                             const pann_rerank_out* out);
 
 #ifdef __cplusplus
 }

@@ -24,7 +24,7 @@ PANN_L2, PANN_MIPS = 0, 1
 PANN_OK = 0
 PANN_ERR_OVERFLOW = 5
 PANN_ABI_VERSION = 3
-PANN_STATUS_VISITED_OVERFLOW, PANN_STATUS_DROPPED_OVERFLOW = 1, 2
+PANN_STATUS_VISITED_OVERFLOW, PANN_STATUS_DROPPED_OVERFLOW, PANN_STATUS_SHORT_FRONTIER = 1, 2, 4
 
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
@@ -43,6 +43,12 @@ class SearchOut(C.Structure):
                 ("dist_cmps", C.c_void_p), ("degree_sum", C.c_void_p),
                 ("visited_ids", C.c_void_p), ("visited_dists", C.c_void_p),
                 ("visited_cap", C.c_uint32), ("status", C.c_void_p)]
+
+
+class RerankOut(C.Structure):
+    """pann_rerank_out: outputs of pann_batch_search_rerank*; everything but ids and dists is optional."""
+    _fields_ = [("ids", C.c_void_p), ("dists", C.c_void_p), ("frontier_size", C.c_void_p), ("visited_count", C.c_void_p),
+                ("dist_cmps", C.c_void_p), ("pruned_cmps", C.c_void_p), ("status", C.c_void_p)]
 
 
 class BuildStats(C.Structure):
@@ -171,6 +177,11 @@ SIGNATURES = {
     "pann_batch_search_filtered_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                                  C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.POINTER(SearchOut), C.c_void_p,
                                                  C.c_void_p]),
+    "pann_batch_search_rerank": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                           C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.POINTER(RerankOut)]),
+    "pann_batch_search_rerank_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
+                                               C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams),
+                                               C.POINTER(RerankOut), C.c_void_p]),
 }
 
 _lib = None

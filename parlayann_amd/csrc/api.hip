@@ -69,6 +69,7 @@ struct pann_index {
   hipStream_t stream = nullptr;      // the stream every call of this handle runs on: own_stream, or the caller's (pann_index_set_stream)
   hipStream_t own_stream = nullptr;
   Workspace ws, ws2, ws3, ws4;   // kernel scratch (search / prune / re-prune / rows of a batch)
+  Workspace ws_rr;               // pann_batch_search_rerank*: prepared queries and frontiers (search_rerank.hip)
   uint32_t vcap = 0;        // visited-list capacity used by the builder (grows on overflow)
   uint32_t dcap = 256;      // dropped-list capacity of the searches (pann_index_reserve_dropped; grows on overflow)
   uint32_t gt_pieces = 0;   // pann_index_set_option("gt_pieces"): pieces of the base per query tile in pann_bruteforce_knn (0 = auto)
@@ -81,6 +82,7 @@ struct pann_index {
   DevBuf stage[12];      // staging for host-pointer calls
   PinnedBuf pin_in, pin_out;   // packed pinned staging of pann_batch_search
   DevBuf sketch_buf;           // attached bit sketch (pann_index_attach_sketch): ix.sketch points into it
+  pann_sketch_params sk_params{};   // ... and the parameters it was made with (the fused rerank sketches its queries with them)
 };
 
 namespace {
@@ -359,7 +361,7 @@ void pann_index_destroy(pann_index* idx) {
   if (idx->stream) (void)hipStreamSynchronize(idx->stream);
   if (idx->ix.points) (void)hipFree(idx->ix.points);
   if (idx->ix.graph) (void)hipFree(idx->ix.graph);
-  idx->ws.release(); idx->ws2.release(); idx->ws3.release(); idx->ws4.release();
+  idx->ws.release(); idx->ws2.release(); idx->ws3.release(); idx->ws4.release(); idx->ws_rr.release();
   for (auto& s : idx->stage) s.release();
   idx->pin_in.release(); idx->pin_out.release();
   idx->code_rank.release(); idx->code_rows.release(); idx->cell_buf.release();
@@ -526,6 +528,37 @@ int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const
 
 }  // extern "C"
 
+// The "dropped" scratch of a search is nq * dcap * 8 bytes.  When a launch reports that it was too small the list is grown (x8,
+// up to min(limit, n): a query drops at most one entry per visited vertex) and the batch runs again; a grown list that would
+// take more than kDropBudget for the whole batch makes the batch run in ranges of queries instead, and the handle keeps at most
+// kDropKeep entries per query for later calls (10K queries x 2048 x 8 B = 160 MB), not the worst case of one odd batch.
+// launch(q0, cnt, dcap, &word): queries [q0, q0 + cnt) with a list of dcap entries, synchronised, word = the launch's status
+// word.  *status: the bits of the last pass over the batch; *whole: that pass was one launch of all nq queries.
+template <class Launch>
+static int run_with_dropped_growth(pann_index* idx, uint64_t nq, const pann_query_params* qp, const char* fn, uint32_t* status,
+                                   bool* whole, Launch&& launch) {
+  constexpr uint64_t kDropBudget = 1ull << 30;
+  constexpr uint32_t kDropKeep = 2048;
+  const uint64_t dneed = (uint64_t)std::min<int64_t>(std::max<int64_t>(qp->limit, 1), (int64_t)idx->ix.n);
+  uint32_t dcap = idx->dcap;
+  for (;;) {
+    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, kDropBudget / ((uint64_t)std::max<uint32_t>(dcap, 64) * 8)));
+    *status = 0; *whole = chunk >= nq;
+    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
+      uint32_t st_word = 0;      // the launch's status word (the next launch clears it)
+      if (int rc = launch(q0, std::min(chunk, nq - q0), dcap, &st_word)) return rc;
+      *status |= st_word;
+      if (*status & PANN_STATUS_DROPPED_OVERFLOW) break;
+    }
+    if (!(*status & PANN_STATUS_DROPPED_OVERFLOW)) break;
+    // The reference has no such list (its `visited` vector grows as needed, beamSearch.h:80,113): grow ours and run the batch again.
+    if ((uint64_t)dcap >= dneed) { set_error(std::string(fn) + ": internal dropped-list overflow"); return PANN_ERR_OVERFLOW; }
+    dcap = (uint32_t)std::min<uint64_t>((uint64_t)dcap * 8, (dneed + 63) / 64 * 64);
+  }
+  idx->dcap = std::max(idx->dcap, std::min(dcap, kDropKeep));
+  return PANN_OK;
+}
+
 static int batch_search_host(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int per_query,
                              const pann_query_params* qp, const pann_search_out* out, int filter = 0,
@@ -590,20 +623,9 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
 
   d.status = nullptr;   // read from the workspace below
   uint32_t status = 0;
-  // The "dropped" scratch is nq * dcap * 8 bytes.  When a launch reports that it was too small the list is grown (x8, up to
-  // min(limit, n): a query drops at most one entry per visited vertex) and the batch runs again; a grown list that would take
-  // more than kDropBudget for the whole batch makes the batch run in ranges of queries instead, and the handle keeps at most
-  // kDropKeep entries per query for later calls (10K queries x 2048 x 8 B = 160 MB), not the worst case of one odd batch.
-  constexpr uint64_t kDropBudget = 1ull << 30;
-  constexpr uint32_t kDropKeep = 2048;
-  const uint64_t dneed = (uint64_t)std::min<int64_t>(std::max<int64_t>(qp->limit, 1), (int64_t)ix.n);
-  uint32_t dcap = idx->dcap;
   bool results_home = false;        // the packed outputs already sit in pin_out
-  for (;;) {
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, kDropBudget / ((uint64_t)std::max<uint32_t>(dcap, 64) * 8)));
-    status = 0;
-    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
-      const uint64_t cnt = std::min(chunk, nq - q0);
+  if (int rc = run_with_dropped_growth(idx, nq, qp, "pann_batch_search", &status, &results_home,
+      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
       SearchArgs a;
       a.queries = d_q ? (const uint8_t*)d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
       a.query_ids = d_qid ? d_qid + q0 : nullptr;
@@ -626,27 +648,17 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
       }
       if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
       if (int rc = launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
-      uint32_t st_word = 0;      // the launch's status word (the next launch clears it)
       if (cnt == nq) {           // the whole batch in one launch (the normal case): the word travels with the results, ONE transfer
         PANN_HIP(hipMemcpyAsync((uint8_t*)idx->stage[4].p + out_bytes, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToDevice, st));
         PANN_HIP(hipMemcpyAsync(idx->pin_out.p, idx->stage[4].p, out_bytes + 4, hipMemcpyDeviceToHost, st));
         PANN_HIP(hipStreamSynchronize(st));
-        std::memcpy(&st_word, (uint8_t*)idx->pin_out.p + out_bytes, 4);
-        results_home = true;
+        std::memcpy(st_word, (uint8_t*)idx->pin_out.p + out_bytes, 4);
       } else {
-        PANN_HIP(hipMemcpyAsync(&st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
+        PANN_HIP(hipMemcpyAsync(st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
         PANN_HIP(hipStreamSynchronize(st));
-        results_home = false;
       }
-      status |= st_word;
-      if (status & PANN_STATUS_DROPPED_OVERFLOW) break;
-    }
-    if (!(status & PANN_STATUS_DROPPED_OVERFLOW)) break;
-    // The reference has no such list (its `visited` vector grows as needed, beamSearch.h:80,113): grow ours and run the batch again.
-    if ((uint64_t)dcap >= dneed) { set_error("pann_batch_search: internal dropped-list overflow"); return PANN_ERR_OVERFLOW; }
-    dcap = (uint32_t)std::min<uint64_t>((uint64_t)dcap * 8, (dneed + 63) / 64 * 64);
-  }
-  idx->dcap = std::max(idx->dcap, std::min(dcap, kDropKeep));
+      return PANN_OK;
+    })) return rc;
   if (!results_home) {
     PANN_HIP(hipMemcpyAsync(idx->pin_out.p, idx->stage[4].p, out_bytes, hipMemcpyDeviceToHost, st));
     PANN_HIP(hipStreamSynchronize(st));
@@ -1545,6 +1557,7 @@ int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch
   if (int rc = sketch_translate_dev(p, reinterpret_cast<const float*>(sx.points), sx.n, sx.pstride, idx->sketch_buf.p, stride, stride, src->stream)) return rc;
   PANN_HIP(hipStreamSynchronize(src->stream));
   idx->ix.sketch = idx->sketch_buf.as<uint8_t>(); idx->ix.sk_stride = stride; idx->ix.sk_kind = p->kind;
+  idx->sk_params = *p;
   idx->ix.sk_as_written = (p->kind != PANN_SKETCH_MIPS_2BIT && p->hamming_as_written) ? 1u : 0u;
   return PANN_OK;
 }
@@ -1565,6 +1578,7 @@ int pann_index_upload_sketch(pann_index* idx, const pann_sketch_params* p, const
   if (stride != row) PANN_HIP(hipMemset(idx->sketch_buf.p, 0, (size_t)ix.n * stride));      // the pad bytes of a device row are zero
   PANN_HIP(hipMemcpy2D(idx->sketch_buf.p, stride, rows, stride_bytes, row, ix.n, hipMemcpyHostToDevice));
   idx->ix.sketch = idx->sketch_buf.as<uint8_t>(); idx->ix.sk_stride = stride; idx->ix.sk_kind = p->kind;
+  idx->sk_params = *p;
   idx->ix.sk_as_written = (p->kind != PANN_SKETCH_MIPS_2BIT && p->hamming_as_written) ? 1u : 0u;
   return PANN_OK;
 }
@@ -1629,6 +1643,142 @@ int pann_sketch_rows(const pann_sketch_params* p, const float* rows, uint64_t n,
     if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(out)"));
   }
   return done(PANN_OK);
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// quantised search + exact rerank in one call (search_rerank.hip)
+// ---------------------------------------------------------------------------------------------
+
+namespace {
+
+// everything that can be refused before anything is enqueued; `fn` names the entry point in the messages
+int search_rerank_checks(const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                         uint64_t nq, uint64_t q_stride, int use_filter, const uint32_t* starts, uint32_t nstarts,
+                         const pann_query_params* qp, const pann_rerank_out* out, const char* fn) {
+  const std::string f = fn;
+  if (!full || !quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
+  if (!qparams || !qp || !out || !out->ids || !out->dists) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
+  if (qp->k <= 0) { set_error(f + ": k must be at least 1"); return PANN_ERR_BAD_ARG; }
+  if (qp->k > qp->beam) {  // beamSearch.h:368-372, :549-553
+    set_error("Error: beam search parameter Q = " + std::to_string(qp->beam) + " same size or smaller than k = " + std::to_string(qp->k));
+    return PANN_ERR_BAD_ARG;
+  }
+  const DeviceIndex& fx = full->ix;
+  const DeviceIndex& qx = quant->ix;
+  if (fx.dtype != PANN_F32) { set_error(f + ": the full-precision index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
+  if (fx.n != qx.n || fx.d != qx.d || full->device != quant->device || fx.metric != qx.metric) {
+    set_error(f + ": the two indices must agree in size, dimension, device and metric"); return PANN_ERR_BAD_ARG;
+  }
+  if (int rc = check_quant_kind(qparams->kind, fn)) return rc;
+  const bool eu = qparams->kind == PANN_QUANT_EUCLID_U8;
+  if (qx.dtype != (eu ? PANN_U8 : PANN_I8) || qx.metric != (eu ? PANN_L2 : PANN_MIPS) || (uint32_t)qparams->dims != qx.d) {
+    set_error(f + ": the quantisation parameters do not fit the one-byte index (EUCLID_U8 <-> u8 / L2, MIPS_I8 <-> i8 / MIPS, same dimension)");
+    return PANN_ERR_BAD_ARG;
+  }
+  if (use_filter && !qx.sketch) { set_error(f + ": use_filter needs a sketch attached to the one-byte index"); return PANN_ERR_BAD_ARG; }
+  if (q_stride < 4ull * fx.d || q_stride % 4 != 0) { set_error(f + ": query stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }
+  if (!starts || nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
+  if (qp->beam > 4096) { set_error("pann_rerank: candidates per query must be in [1,4096]"); return PANN_ERR_BAD_ARG; }
+  if (nq && !queries) { set_error(f + ": null queries"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+// one launch sequence for nq queries with a dropped list of dcap entries; grows quant's workspaces on first use
+int search_rerank_launch(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                         uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
+                         const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st) {
+  SearchArgs a{};                                  // the fields search_workspace_bytes reads
+  a.queries = reinterpret_cast<const uint8_t*>(d_queries); a.nq = nq; a.nstarts = nstarts;
+  a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
+  a.dcap = dcap; a.filter = use_filter ? 1 : 0;
+  a.out = pann_search_out{}; a.out.out_k = (uint32_t)qp->beam;
+  if (int rc = quant->ws.ensure(search_workspace_bytes(quant->ix, a))) return rc;
+  if (int rc = quant->ws_rr.ensure(search_rerank_scratch_bytes(quant->ix, nq, (uint32_t)qp->beam, normalize_first, use_filter))) return rc;
+  return search_rerank_dev(full->ix, quant->ix, quant->ws.buf, quant->ws.bytes, quant->ws_rr.buf, qparams, &quant->sk_params, d_queries,
+                           nq, q_stride, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d_out, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pann_batch_search_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
+                                 uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* d_starts,
+                                 uint32_t nstarts, const pann_query_params* qp, const pann_rerank_out* d_out, void* stream) {
+  if (int rc = search_rerank_checks(full, quant, qparams, d_queries, nq, q_stride_bytes, use_filter, d_starts, nstarts, qp, d_out,
+                                    "pann_batch_search_rerank_dev")) return rc;
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)d_queries % 4 != 0) { set_error("pann_batch_search_rerank_dev: query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  return search_rerank_launch(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp,
+                              quant->dcap, *d_out, (hipStream_t)stream);
+}
+
+int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                             uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts,
+                             uint32_t nstarts, const pann_query_params* qp, const pann_rerank_out* out) {
+  if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, out,
+                                    "pann_batch_search_rerank")) return rc;
+  for (uint32_t i = 0; i < nstarts; i++)
+    if (starts[i] >= quant->ix.n) { set_error("pann_batch_search_rerank: start point out of range"); return PANN_ERR_BAD_ARG; }
+  if (nq == 0) return PANN_OK;
+  DeviceGuard g(quant->device);
+  hipStream_t st = quant->stream;
+  const DeviceIndex& qx = quant->ix;
+  const uint32_t k = (uint32_t)qp->k;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // ---- inputs: the float rows and the starts, packed in pinned memory, one transfer up ----
+  const size_t qbytes = (nq - 1) * q_stride_bytes + 4ull * qx.d;
+  const size_t off_st = al(qbytes), in_bytes = off_st + al((size_t)nstarts * 4);
+  if (int rc = quant->pin_in.ensure(in_bytes)) return rc;
+  if (int rc = quant->stage[2].ensure(in_bytes)) return rc;
+  std::memcpy(quant->pin_in.p, queries, qbytes);
+  std::memcpy((uint8_t*)quant->pin_in.p + off_st, starts, (size_t)nstarts * 4);
+  PANN_HIP(hipMemcpyAsync(quant->stage[2].p, quant->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
+  const float* d_q = quant->stage[2].as<float>();
+  const uint32_t* d_starts = (const uint32_t*)((uint8_t*)quant->stage[2].p + off_st);
+  // ---- outputs: one packed device region (the status word last), one transfer down ----
+  struct Piece { void* host; size_t bytes; size_t off; };
+  Piece pc[6] = {{out->ids, nq * k * 4, 0}, {out->dists, nq * k * 4, 0}, {out->frontier_size, nq * 4, 0},
+                 {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {use_filter ? out->pruned_cmps : nullptr, nq * 4, 0}};
+  size_t out_bytes = 0;
+  for (auto& x : pc) { if (!x.host) x.bytes = 0; x.off = out_bytes; out_bytes += al(x.bytes); }
+  if (int rc = quant->stage[4].ensure(out_bytes + 256)) return rc;
+  if (int rc = quant->pin_out.ensure(out_bytes + 256)) return rc;
+  auto dptr = [&](int i) -> uint8_t* { return pc[i].bytes ? (uint8_t*)quant->stage[4].p + pc[i].off : nullptr; };
+  uint32_t status = 0;
+  bool results_home = false;
+  if (int rc = run_with_dropped_growth(quant, nq, qp, "pann_batch_search_rerank", &status, &results_home,
+      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
+      pann_rerank_out d{};
+      d.ids = (uint32_t*)dptr(0) + q0 * k; d.dists = (float*)dptr(1) + q0 * k;
+      if (dptr(2)) d.frontier_size = (uint32_t*)dptr(2) + q0;
+      if (dptr(3)) d.visited_count = (uint32_t*)dptr(3) + q0;
+      if (dptr(4)) d.dist_cmps = (uint32_t*)dptr(4) + q0;
+      if (dptr(5)) d.pruned_cmps = (uint32_t*)dptr(5) + q0;
+      d.status = (uint32_t*)((uint8_t*)quant->stage[4].p + out_bytes);
+      if (int rc = search_rerank_launch(full, quant, qparams, (const float*)((const uint8_t*)d_q + q0 * q_stride_bytes), cnt,
+                                        q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d, st)) return rc;
+      if (cnt == nq) {             // the normal case: the word travels with the results
+        PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes + 4, hipMemcpyDeviceToHost, st));
+        PANN_HIP(hipStreamSynchronize(st));
+        std::memcpy(st_word, (uint8_t*)quant->pin_out.p + out_bytes, 4);
+      } else {
+        PANN_HIP(hipMemcpyAsync(st_word, d.status, 4, hipMemcpyDeviceToHost, st));
+        PANN_HIP(hipStreamSynchronize(st));
+      }
+      return PANN_OK;
+    })) return rc;
+  if (!results_home) {
+    PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes, hipMemcpyDeviceToHost, st));
+    PANN_HIP(hipStreamSynchronize(st));
+  }
+  if (quant->ws.bytes > (2ull << 30)) quant->ws.release();          // a one-off worst-case scratch is not kept on the handle
+  for (auto& x : pc) if (x.bytes) std::memcpy(x.host, (uint8_t*)quant->pin_out.p + x.off, x.bytes);
+  if (out->status) *out->status = status;
+  return PANN_OK;
 }
 
 }  // extern "C"

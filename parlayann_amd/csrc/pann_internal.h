@@ -181,6 +181,17 @@ int sketch_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stri
 int sketch_translate_dev(const pann_sketch_params* p, const float* d_rows, uint64_t n, uint64_t stride, void* d_out, uint64_t out_stride,
                          uint32_t out_row_bytes, hipStream_t st);
 
+float sketch_threshold(const pann_sketch_params* p);               // the value a coordinate is compared with (0 for MIPS_BIT)
+
+// search_rerank.hip: beam_search_rerank on the device -- prepare the float queries (one-byte rows, sketch rows, normalised
+// rows), beam search on the one-byte index, exact rerank of the frontier on the f32 index.  `scratch`: search_rerank_scratch_bytes
+// bytes, 256-byte aligned; search_ws: the one-byte handle's search workspace (its status word gets the SHORT_FRONTIER bit).
+size_t search_rerank_scratch_bytes(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int normalize_first, int use_filter);
+int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* search_ws, size_t search_ws_bytes, void* scratch,
+                      const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
+                      uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
+                      const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st);
+
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,
                     uint32_t mst_deg, uint64_t seed, double* times3, uint32_t first_tree = 0, uint32_t tree_step = 1,

@@ -19,6 +19,7 @@
 #include <cstring>
 
 #include "pann_internal.h"
+#include "quant_device.h"
 
 namespace pann {
 namespace {
@@ -181,28 +182,7 @@ __global__ __launch_bounds__(256) void select_scan_kernel(SelectState* st, unsig
   for (uint32_t i = threadIdx.x; i < 2 * QBINS; i += blockDim.x) ghist[i] = 0;
 }
 
-// ---- translate_point ----------------------------------------------------------------------------------------------------------
-struct QParams {
-  int kind, identity;
-  float slope; int32_t offset;      // Euclid u8
-  float max_val, scale;             // MIPS i8: scale = 127 / max_val
-};
-
-__device__ __forceinline__ uint32_t quantize_one(float x, const QParams& q) {
-  if (q.kind == PANN_QUANT_EUCLID_U8) {
-    if (q.identity) return (uint32_t)(int32_t)x & 0xFFu;                        // (uint8_t) x, euclidian_point.h:194
-    long long r = (long long)roundf(x * q.slope) - (long long)q.offset;         // :197
-    r = r < 0 ? 0 : (r > 255 ? 255 : r);
-    return (uint32_t)r;
-  }
-  if (x < -q.max_val) return (uint32_t)(-127) & 0xFFu;                          // mips_point.h:421-424
-  if (x > q.max_val) return 127u;
-  return (uint32_t)(int32_t)roundf(x * q.scale) & 0xFFu;                        // :426-427
-}
-__device__ __forceinline__ uint32_t quantize_four(float4 x, const QParams& q) {
-  return quantize_one(x.x, q) | (quantize_one(x.y, q) << 8) | (quantize_one(x.z, q) << 16) | (quantize_one(x.w, q) << 24);
-}
-
+// ---- translate_point (QParams, quantize_one / quantize_four: quant_device.h) -----------------------------------------------
 // CH floats in, CH bytes out per lane and step: 16 (four 16-byte loads, one 16-byte store), 4 or 1, by the alignment of both
 // sides.  A row's last, partial chunk goes float by float, byte by byte.  Only [0, len) of a destination row is written.
 template <int CH>
@@ -344,16 +324,6 @@ int launch_hist(const View& v, const SelectState* st, unsigned long long* hist, 
   }
   PANN_HIP(hipGetLastError());
   return PANN_OK;
-}
-
-QParams make_qparams(const pann_quant_params* p) {
-  QParams q{};
-  q.kind = p->kind;
-  q.slope = p->slope; q.offset = p->offset;
-  q.identity = (p->slope == 1.0f && p->offset == 0) ? 1 : 0;
-  q.max_val = p->max_val;
-  q.scale = 127 / p->max_val;               // float scale = (range / 2) / max_val, mips_point.h:419
-  return q;
 }
 
 }  // namespace

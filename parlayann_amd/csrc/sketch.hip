@@ -104,10 +104,14 @@ int sketch_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stri
   return PANN_OK;
 }
 
+float sketch_threshold(const pann_sketch_params* p) {
+  return p->kind == PANN_SKETCH_EUCLID_BIT ? (float)p->median : p->kind == PANN_SKETCH_MIPS_BIT ? 0.0f : p->cut;
+}
+
 int sketch_translate_dev(const pann_sketch_params* p, const float* d_rows, uint64_t n, uint64_t stride, void* d_out, uint64_t out_stride,
                          uint32_t out_row_bytes, hipStream_t st) {
   const uint32_t d = (uint32_t)p->dims;
-  const float thr = p->kind == PANN_SKETCH_EUCLID_BIT ? (float)p->median : p->kind == PANN_SKETCH_MIPS_BIT ? 0.0f : p->cut;
+  const float thr = sketch_threshold(p);
   const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((n + 3) / 4, 1), 2048);
   hipLaunchKernelGGL(sketch_translate_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(d_rows), stride, n, d,
                      (int)p->kind, thr, static_cast<uint8_t*>(d_out), out_stride, out_row_bytes / 8);

@@ -76,26 +76,18 @@ class GraphIndex:
             r = self.index.batch_search(queries, out_k=knn, **qp)                # :188
             self._need(r["frontier_size"], knn)
             return r["ids"], r["dists"]
-        if self.metric == "Euclidian":
+        if self.metric == "Euclidian" and self.eparams.identity:                 # slope == 1: plain search on the u8 copy (:148-152)
             qq = quantize.device_quantize_rows(queries, self.qparams, device=self.device)
-            if self.eparams.identity:                                            # slope == 1: plain search on the u8 copy (:148-152)
-                r = self.q_index.batch_search(qq, out_k=knn, **qp)
-                self._need(r["frontier_size"], knn)
-                return r["ids"], r["dists"]
-            full_q = queries
-        else:
-            full_q = quantize.normalize_rows(queries)                            # q.normalize() :172
-            qq = quantize.device_quantize_rows(queries, self.qparams, normalize_first=True, device=self.device)
-        # beam_search_rerank (beamSearch.h:390-454): search the quantised copy, re-score the first
-        # min(k * rerank_factor, |beam|) with exact distances, sort, keep k
-        if self.sparams is not None:                                             # three ranges: use_filtering (:410)
-            sq = sketch.sketch_rows(full_q, self.sparams, device=self.device)
-            r = self.q_index.batch_search_filtered(qq, sq, out_k=beam_width, **qp)
-        else:
-            r = self.q_index.batch_search(qq, out_k=beam_width, **qp)
+            r = self.q_index.batch_search(qq, out_k=knn, **qp)
+            self._need(r["frontier_size"], knn)
+            return r["ids"], r["dists"]
+        # beam_search_rerank (beamSearch.h:390-454) in one call: the queries are quantised (mips: normalised first, :172, and
+        # re-scored as normalised), sketched for the three-range form (use_filtering, :410), searched on the one-byte copy,
+        # and the first min(k * rerank_factor, |beam|) frontier ids are re-scored with exact distances, sorted, k kept
+        r = self.index.search_rerank(self.q_index, self.qparams, queries, normalize_first=self.metric != "Euclidian",
+                                     use_filter=self.sparams is not None, rerank_factor=100, **qp)   # QP.rerank_factor (types.h:224)
         self._need(r["frontier_size"], knn)
-        counts = np.minimum(r["frontier_size"], knn * 100).astype(np.uint32)     # QP.rerank_factor = 100 (types.h:224)
-        return self.index.rerank(full_q, r["ids"], counts, knn, resort=True)
+        return r["ids"], r["dists"]
 
     @staticmethod
     def _need(frontier_size, knn):

@@ -3,11 +3,13 @@
 //   filtered_beam_search (:22-33; use_filtering with a sketch range: pann_batch_search_filtered)      beam_search (:217-223, :234-241)   beam_search_impl (:226-231)
 //   range_search (:245-306)      beamSearchRandom (:309-351)   searchAll (:353-387)
 //   beam_search_rerank (:390-454)   beam_search_rerank__ (:499-521)   qsearchAll (:537-565)
-// The CPU loop bodies are gone: every function is one (or, with a rerank, two) C-ABI call on the device mirror of
+// The CPU loop bodies are gone: every function is one C-ABI call (two for a rerank over ranges that are not a float range and
+// its scalar-quantised copy) on the device mirror of
 // (G, Points) -- the batched ones replace the parallel_for over queries (:374, :556) by ONE launch for the batch.
 // Overloads taking a DeviceIndex (an explicitly managed mirror) end in the same calls.
 #pragma once
 #include <algorithm>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -105,10 +107,33 @@ parlay::sequence<parlay::sequence<indexType>> search_batch(pann_index* h, const 
   return all;
 }
 
-// beam_search_rerank (:390-454) for every query as TWO launches: beam search of the Q_ queries on the quantised mirror
-// qh, then the first min(k * rerank_factor, |beam|) frontier ids re-scored by the full-precision queries on mirror h,
-// sorted by (dist,id), first k kept (:426-444).  Equal num_bytes(): nothing is re-sorted, the first k frontier ids get
-// their exact distances (:445-452).
+// Does beam_search_rerank over (P, Q) run as ONE pann_batch_search_rerank call?  It does when P is a float range and Q the
+// one-byte range quantize_u8 / quantize_mips_i8 (quantize.h) made with parameters that fit its type and metric: the call
+// quantises the float query rows on the device with *qpar, which gives the rows of Q's query range bit for bit (the
+// reference builds that range as QPR(Query_Points, Q_Points.params), vamana/neighbors.h:104-110) -- and, for a filtered
+// search, sketches them with the parameters of the sketch the searched handle holds, which gives the QQ query rows.
+template <class PointRange, class QPointRange>
+inline bool fused_rerank_applies(const QPointRange& Q, pann_quant_params* qpar) {
+  using PT = typename PointRange::Point;
+  using QT = typename QPointRange::Point;
+  if constexpr (std::is_same<typename PT::T, float>::value && !is_sketch_point<QT>::value) {
+    if constexpr (PT::metric == QT::metric && sizeof(typename QT::T) == 1) {
+      const int want = (std::is_same<typename QT::T, uint8_t>::value && QT::metric == PANN_L2) ? (int)PANN_QUANT_EUCLID_U8
+                     : (std::is_same<typename QT::T, int8_t>::value && QT::metric == PANN_MIPS) ? (int)PANN_QUANT_MIPS_I8 : -2;
+      if (Q.params.quant_kind != want) return false;
+      *qpar = Q.params.to_pann_quant();
+      return true;
+    }
+  }
+  return false;
+}
+
+// beam_search_rerank (:390-454) for every query.  A float range searched through its scalar-quantised copy
+// (fused_rerank_applies) is ONE call, pann_batch_search_rerank: the float queries go to the device once, are quantised (and
+// sketched) there, searched on the quantised mirror qh, and the first min(k * rerank_factor, |beam|) frontier ids are
+// re-scored on mirror h, sorted by (dist,id), first k kept (:426-444).  Any other pair of ranges is TWO calls: the beam
+// search of the Q_ queries on qh, then pann_rerank on h.  Equal num_bytes(): nothing is re-sorted, the first k frontier ids
+// get their exact distances (:445-452).
 template <class PointRange, class QPointRange, typename indexType>
 parlay::sequence<parlay::sequence<indexType>> search_rerank_batch(pann_index* h, pann_index* qh, const PointRange& Query_Points,
                                                                   const QPointRange& Q_Query_Points, stats<indexType>& QueryStats,
@@ -119,35 +144,54 @@ parlay::sequence<parlay::sequence<indexType>> search_rerank_batch(pann_index* h,
   const size_t nq = Query_Points.size();
   const uint32_t k = (uint32_t)QP.k, beam = (uint32_t)QP.beamSize;
   const bool use_rerank = Query_Points.params.num_bytes() != Q_Query_Points.params.num_bytes();     // :409
-  std::vector<uint32_t> ids(nq * beam), fs(nq), vc(nq), dc(nq);
-  pann_search_out out{};
-  out.ids = ids.data(); out.out_k = beam; out.frontier_size = fs.data(); out.visited_count = vc.data(); out.dist_cmps = dc.data();
   const pann_query_params q = to_pann(QP);
   const uint32_t start = starting_point;
+  std::vector<uint32_t> fs(nq), vc(nq), dc(nq);
+  auto need_k = [&](size_t i) {                                                                       // :416-419
+    if (fs[i] < k) {
+      std::cout << "Error: for point id " << i << " beam search returned " << fs[i] << " elements, which is less than k = " << k << std::endl;
+      abort();
+    }
+    if (count_stats) {                                                                                // :421-424
+      QueryStats.increment_visited((indexType)i, vc[i]);
+      QueryStats.increment_dist((indexType)i, dc[i]);
+    }
+  };
+  auto rows_of = [&](const std::vector<uint32_t>& rid) {
+    parlay::sequence<parlay::sequence<indexType>> all(nq);
+    for (size_t i = 0; i < nq; i++) all[i] = parlay::sequence<indexType>(rid.begin() + i * k, rid.begin() + (i + 1) * k);
+    return all;
+  };
+  pann_quant_params qpar;
+  if (use_rerank && fused_rerank_applies<PointRange, QPointRange>(Q_Query_Points, &qpar)) {
+    std::vector<uint32_t> rid(nq * k);
+    std::vector<float> rd(nq * k);
+    pann_rerank_out ro{};
+    ro.ids = rid.data(); ro.dists = rd.data(); ro.frontier_size = fs.data(); ro.visited_count = vc.data(); ro.dist_cmps = dc.data();
+    pann_check(pann_batch_search_rerank(h, qh, &qpar, (const float*)Query_Points.data(), nq, Query_Points.get_aligned_bytes(), 0,
+                                        sketch_q ? 1 : 0, &start, 1, &q, &ro));
+    for (size_t i = 0; i < nq; i++) need_k(i);
+    if (dists_out) *dists_out = rd;
+    return rows_of(rid);
+  }
+  std::vector<uint32_t> ids(nq * beam);
+  pann_search_out out{};
+  out.ids = ids.data(); out.out_k = beam; out.frontier_size = fs.data(); out.visited_count = vc.data(); out.dist_cmps = dc.data();
   // sketch_q: the QQ query rows -- the batch is ONE filtered_beam_search(..., use_filtering = true) launch (:410-414)
   if (sketch_q) pann_check(pann_batch_search_filtered(qh, Q_Query_Points.data(), nullptr, nq, Q_Query_Points.get_aligned_bytes(), sketch_q,
                                                       sketch_stride, &start, 1, &q, &out, nullptr));
   else pann_check(pann_batch_search(qh, Q_Query_Points.data(), nullptr, nq, Q_Query_Points.get_aligned_bytes(), &start, 1, &q, &out));
   std::vector<uint32_t> counts(nq);
   for (size_t i = 0; i < nq; i++) {
-    if (fs[i] < k) {                                                                                  // :416-419
-      std::cout << "Error: for point id " << i << " beam search returned " << fs[i] << " elements, which is less than k = " << k << std::endl;
-      abort();
-    }
+    need_k(i);
     counts[i] = use_rerank ? (uint32_t)std::min<long>((long)QP.k * QP.rerank_factor, (long)fs[i]) : k;
-    if (count_stats) {                                                                                // :421-424
-      QueryStats.increment_visited((indexType)i, vc[i]);
-      QueryStats.increment_dist((indexType)i, dc[i]);
-    }
   }
   std::vector<uint32_t> rid(nq * k);
   std::vector<float> rd(nq * k);
   pann_check(pann_rerank(h, Query_Points.data(), nq, Query_Points.get_aligned_bytes(), ids.data(), beam, counts.data(), k,
                          use_rerank ? 1 : 0, rid.data(), rd.data()));
-  parlay::sequence<parlay::sequence<indexType>> all(nq);
-  for (size_t i = 0; i < nq; i++) all[i] = parlay::sequence<indexType>(rid.begin() + i * k, rid.begin() + (i + 1) * k);
   if (dists_out) *dists_out = rd;
-  return all;
+  return rows_of(rid);
 }
 
 template <typename indexType>
@@ -279,6 +323,33 @@ id_dist_seq<indexType> beam_search_rerank(const Point& p, const QPoint& qp, cons
                                           const parlay::sequence<indexType> starting_points, const QueryParams& QP, bool stats_ = true) {
   const bool use_filtering = Q_Base_Points.params.num_bytes() != QQ_Base_Points.params.num_bytes();    // :410
   const bool use_rerank = Base_Points.params.num_bytes() != Q_Base_Points.params.num_bytes();
+  pann_quant_params qpar;
+  if (use_rerank && detail::fused_rerank_applies<PointRange, QPointRange>(Q_Base_Points, &qpar) &&
+      (!use_filtering || is_sketch_point<typename QQPointRange::Point>::value) && own_vertex(qp, Q_Base_Points) < 0) {
+    // a float range searched through its scalar-quantised copy, external query: ONE call (detail::search_rerank_batch); qp and
+    // qqp are what the device makes of p.  (A query that is a base point skips its own vertex: that form keeps two calls.)
+    if (starting_points.size() == 0) { std::cout << "beam search expects at least one start point" << std::endl; abort(); }   // :38-41
+    auto QL = device_mirror(G, Q_Base_Points);
+    if constexpr (is_sketch_point<typename QQPointRange::Point>::value) { if (use_filtering) ensure_sketch(QL, QQ_Base_Points); }
+    auto L = device_mirror(G, Base_Points);
+    const uint32_t k = (uint32_t)QP.k;
+    std::vector<uint32_t> oi(k), st(starting_points.begin(), starting_points.end());
+    std::vector<float> od(k);
+    uint32_t fs = 0, vc = 0, dc = 0;
+    pann_rerank_out ro{};
+    ro.ids = oi.data(); ro.dists = od.data(); ro.frontier_size = &fs; ro.visited_count = &vc; ro.dist_cmps = &dc;
+    const pann_query_params q = to_pann(QP);
+    pann_check(pann_batch_search_rerank(L.h(), QL.h(), &qpar, (const float*)p.values, 1, (uint64_t)p.params.num_bytes(), 0,
+                                        use_filtering ? 1 : 0, st.data(), (uint32_t)st.size(), &q, &ro));
+    if ((long)fs < QP.k) {
+      std::cout << "Error: for point id " << p.id() << " beam search returned " << fs << " elements, which is less than k = " << QP.k << std::endl;
+      abort();
+    }
+    if (stats_) { QueryStats.increment_visited((indexType)p.id(), (indexType)vc); QueryStats.increment_dist((indexType)p.id(), (indexType)dc); }
+    id_dist_seq<indexType> out(QP.k);
+    for (long i = 0; i < QP.k; i++) out[i] = std::make_pair((indexType)oi[i], od[i]);
+    return out;
+  }
   beam_result<indexType> r = filtered_beam_search(G, qp, Q_Base_Points, qqp, QQ_Base_Points, starting_points, QP, use_filtering);
   const auto& beamElts = r.first.first;
   if ((long)beamElts.size() < QP.k) {

@@ -30,9 +30,18 @@ struct Point_ {
   using byte = uint8_t;
   struct parameters {
     int dims = 0;
+    // set by quantize_u8 / quantize_mips_i8 (quantize.h) on the one-byte range they return: the scalar quantiser the rows went
+    // through (Euclidian_Point<uint8_t>::parameters slope / offset, Quantized_Mips_Point<8>::parameters max_val); -1: none
+    int quant_kind = -1;
+    float slope = 1.0f; int32_t offset = 0; float max_val = 0.0f;
     int num_bytes() const { return dims * (int)sizeof(T); }
     parameters() {}
     explicit parameters(int dims) : dims(dims) {}
+    pann_quant_params to_pann_quant() const {
+      pann_quant_params q{};
+      q.kind = quant_kind; q.dims = dims; q.slope = slope; q.offset = offset; q.max_val = max_val;
+      return q;
+    }
   };
   static constexpr int metric = METRIC;
   static bool is_metric() { return METRIC == PANN_L2; }   // euclidian_point.h:112, mips_point.h:82

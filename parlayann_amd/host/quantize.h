@@ -54,7 +54,9 @@ PointRange<Euclidian_Point<uint8_t>> quantize_u8(const FloatRange& pr, const euc
       o[j] = (uint8_t)std::min<int64_t>(std::max<int64_t>(r, 0), 255);
     }
   }
-  return PointRange<Euclidian_Point<uint8_t>>(q.data(), pr.size(), (unsigned int)d);
+  PointRange<Euclidian_Point<uint8_t>> out(q.data(), pr.size(), (unsigned int)d);
+  out.params.quant_kind = PANN_QUANT_EUCLID_U8; out.params.slope = p.slope; out.params.offset = p.offset;
+  return out;
 }
 
 // largest magnitude (or the 1e-4 / 1-1e-4 quantiles when trim) over every coordinate
@@ -99,7 +101,9 @@ PointRange<Mips_Point<int8_t>> quantize_mips_i8(const FloatRange& pr, float max_
       else o[j] = (int8_t)(int32_t)std::round(x * scale);
     }
   }
-  return PointRange<Mips_Point<int8_t>>(q.data(), pr.size(), (unsigned int)d);
+  PointRange<Mips_Point<int8_t>> out(q.data(), pr.size(), (unsigned int)d);
+  out.params.quant_kind = PANN_QUANT_MIPS_I8; out.params.max_val = max_val;
+  return out;
 }
 
 // Point::normalize for every row of a float range (mips_point.h:113-122, euclidian_point.h:150-158; `-normalize`,

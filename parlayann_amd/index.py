@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I8, PANN_L2, PANN_MIPS, PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_U8,
-                    BuildStats, QuantParams, QueryParams, SearchOut, check)
+                    BuildStats, QuantParams, QueryParams, RerankOut, SearchOut, check)
 from .bf16 import bfloat16
 
 _DT = {np.dtype(np.uint8): PANN_U8, np.dtype(np.int8): PANN_I8, np.dtype(np.float32): PANN_F32,
@@ -301,6 +301,53 @@ class DeviceIndex:
         fn = self._lib.pann_batch_search_per_query_starts if per_query else self._lib.pann_batch_search
         check(fn(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1], C.byref(qp), C.byref(out)))
         return res
+
+    # ---- quantised search + exact rerank in one call: beam_search_rerank (beamSearch.h:390-454) ----
+    def _rerank_qp(self, k, beam, cut, limit, degree_limit, rerank_factor):
+        return QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
+                           degree_limit=self.max_degree if degree_limit is None else degree_limit,
+                           rerank_factor=rerank_factor, pad=1.0)
+
+    def search_rerank(self, quant, qparams, queries, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
+                      normalize_first=False, use_filter=False, rerank_factor=100):
+        """pann_batch_search_rerank on this (float32) index: `queries` (float32 rows) are quantised with `qparams` on the
+        device, searched on `quant` (the one-byte DeviceIndex of quantized(); use_filter: through the sketch attached to it),
+        and the first min(k * rerank_factor, frontier size) frontier ids are re-scored here and sorted.  normalize_first:
+        every query goes through Point::normalize first, and the rerank scores against the normalised row.  Returns a dict
+        of numpy arrays: ids, dists (nq x k), frontier_size, visited_count, dist_cmps, status (PANN_STATUS_* bits; a query
+        with fewer than k frontier entries sets PANN_STATUS_SHORT_FRONTIER and pads its row), pruned_cmps with use_filter."""
+        q = self._queries(queries)
+        nq = len(q)
+        qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
+        res = {"ids": np.empty((nq, k), np.uint32), "dists": np.empty((nq, k), np.float32),
+               "frontier_size": np.empty(nq, np.uint32), "visited_count": np.empty(nq, np.uint32),
+               "dist_cmps": np.empty(nq, np.uint32), "status": np.zeros(1, np.uint32)}
+        if use_filter:
+            res["pruned_cmps"] = np.empty(nq, np.uint32)
+        out = RerankOut(ids=_ptr(res["ids"]), dists=_ptr(res["dists"]), frontier_size=_ptr(res["frontier_size"]),
+                        visited_count=_ptr(res["visited_count"]), dist_cmps=_ptr(res["dist_cmps"]),
+                        pruned_cmps=_ptr(res.get("pruned_cmps")), status=_ptr(res["status"]))
+        starts = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
+        check(self._lib.pann_batch_search_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q),
+                                                 1 if normalize_first else 0, 1 if use_filter else 0, _ptr(starts), len(starts),
+                                                 C.byref(qp), C.byref(out)))
+        return res
+
+    def search_rerank_dev(self, quant, qparams, d_queries_ptr, nq, q_stride_bytes, d_starts_ptr, nstarts, d_ids_ptr, d_dists_ptr,
+                          k=10, beam=64, cut=1.35, limit=None, degree_limit=None, normalize_first=False, use_filter=False,
+                          rerank_factor=100, d_frontier_size_ptr=None, d_visited_count_ptr=None, d_dist_cmps_ptr=None,
+                          d_pruned_cmps_ptr=None, d_status_ptr=None, stream_ptr=None):
+        """pann_batch_search_rerank_dev: the same on raw device addresses (integers), enqueued on `stream_ptr` (a hipStream_t as
+        an integer; None / 0 = the device's default stream).  Nothing is synchronised: read the outputs after the stream has
+        been.  The first call grows quant's scratch."""
+        qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
+        vp = lambda a: C.c_void_p(a or None)
+        out = RerankOut(ids=vp(d_ids_ptr), dists=vp(d_dists_ptr), frontier_size=vp(d_frontier_size_ptr),
+                        visited_count=vp(d_visited_count_ptr), dist_cmps=vp(d_dist_cmps_ptr), pruned_cmps=vp(d_pruned_cmps_ptr),
+                        status=vp(d_status_ptr))
+        check(self._lib.pann_batch_search_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
+                                                     1 if normalize_first else 0, 1 if use_filter else 0, vp(d_starts_ptr), nstarts,
+                                                     C.byref(qp), C.byref(out), vp(stream_ptr)))
 
     # ---- robustPrune (vamana/index.h:63-137), batched ----
     def robust_prune_batch(self, owners, cand_ids, cand_offsets, alpha, R, cand_dists=None, add_out_nbrs=True):
