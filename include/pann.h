@@ -54,8 +54,24 @@ extern "C" {
 
 /* element type of the stored vectors (reference: Euclidian_Point<T>/Mips_Point<T>, T in
  * {uint8_t,int8_t,float}; PANN_F16 (IEEE binary16) and PANN_BF16 (bfloat16) are this build's two-byte
- * extensions: values are widened exactly to f32, arithmetic is f32) */
-typedef enum { PANN_U8 = 0, PANN_I8 = 1, PANN_F32 = 2, PANN_F16 = 3, PANN_BF16 = 4 } pann_dtype;
+ * extensions: values are widened exactly to f32, arithmetic is f32).
+ *
+ * Four-bit types (DESIGN.md "Four-bit rows"): two coordinates per byte, packed as Quantized_Mips_Point<4>::assign packs them
+ * (mips_point.h:399-406): a row is ceil(d / 2) bytes, coordinate j sits in byte j / 2, low nibble for even j; for odd d the
+ * high nibble of the last byte must be zero (translate writes it so; rows and queries that are uploaded must keep it so).
+ *   PANN_U4  unsigned nibbles 0..15, PANN_L2 only: the distance is sum (a - q)^2 on the nibble values -- the 4-bit analogue
+ *            of Euclidian_Point<uint8_t>, this build's extension
+ *   PANN_I4  two's-complement nibbles -8..7, PANN_MIPS only: Quantized_Mips_Point<4, trim>.  The distance is what distance_4
+ *            (mips_point.h:342-354) returns as written -- its `<< 4` and `& 240` leave each factor scaled by 16 --, i.e.
+ *            -256 * sum a * q, over ALL d coordinates (the reference's loops stop at dims / 2 bytes and so drop the last
+ *            coordinate of an odd d)
+ * Any other pairing is refused by pann_index_create* with PANN_ERR_UNSUPPORTED.  A 4-bit handle is searched
+ * (pann_batch_search*, as `quant` of pann_batch_search_rerank*), measured (pann_pair_distances, pann_query_distances), and has
+ * its points and graph moved (upload / download / set_graph / update_rows / get_graph); it gets its graph from
+ * pann_index_create_quantized(copy_graph) or pann_index_set_graph.  Every entry point that builds, prunes, ranges, reranks ON
+ * it, filters through a sketch or runs a dense all-pairs pass returns PANN_ERR_UNSUPPORTED before anything is launched,
+ * allocated or written. */
+typedef enum { PANN_U8 = 0, PANN_I8 = 1, PANN_F32 = 2, PANN_F16 = 3, PANN_BF16 = 4, PANN_U4 = 5, PANN_I4 = 6 } pann_dtype;
 
 /* distance functor: euclidian_point.h:54-90 / mips_point.h:43-65 */
 typedef enum { PANN_L2 = 0, PANN_MIPS = 1 } pann_metric;
@@ -387,8 +403,20 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
  * full-precision slab there; a float file that is not resident is streamed through pann_quantize_rows by its owner.
  * Status: a source that is not f32 -> PANN_ERR_UNSUPPORTED; a kind that does not fit the metric (EUCLID_U8 <-> PANN_L2,
  * MIPS_I8 <-> PANN_MIPS), an unknown kind, n * d == 0, a stride smaller than a row or not a multiple of 4, NULL pointers
- * -> PANN_ERR_BAD_ARG. */
-enum { PANN_QUANT_EUCLID_U8 = 0, PANN_QUANT_MIPS_I8 = 1 };
+ * -> PANN_ERR_BAD_ARG.
+ *
+ * And their two four-bit forms, which give PANN_U4 / PANN_L2 and PANN_I4 / PANN_MIPS handles and packed rows of ceil(d / 2)
+ * bytes (wherever "d bytes" is said of an output row below, read ceil(d / 2)):
+ *   PANN_QUANT_EUCLID_U4  min / max as EUCLID_U8 finds them (running min / max that start at 0), WITHOUT the all-integers
+ *                         substitution of euclidian_point.h:227-231 (a plain cast cannot fit 4 bits); slope = 15 / (max - min),
+ *                         offset = (int32) round(min * slope); translate is :193-207 with range = 15:
+ *                         r = (int64) round(x * slope) - offset, clamped to [0, 15] -- never the plain cast of :187-189.
+ *                         Degenerate input (max == min, i.e. all zeros): as EUCLID_U8, slope = 15 / 0 = +inf and nothing is
+ *                         special-cased; every translated value is then unspecified.
+ *   PANN_QUANT_MIPS_I4    Quantized_Mips_Point<4, trim>: parameters exactly those of MIPS_I8 (mips_point.h:433-486, same trim
+ *                         ranks); translate :416-430 with range = 15: scale = 7.0f / max_val, values below -max_val become -7,
+ *                         above max_val +7, otherwise (int32) round(x * scale). */
+enum { PANN_QUANT_EUCLID_U8 = 0, PANN_QUANT_MIPS_I8 = 1, PANN_QUANT_EUCLID_U4 = 2, PANN_QUANT_MIPS_I4 = 3 };
 typedef struct pann_quant_params {
   int32_t kind;
   int32_t dims;
@@ -508,7 +536,9 @@ int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const
  * Results equal pann_quantize_rows (+ pann_sketch_rows), pann_batch_search[_filtered] with out_k = beam and pann_rerank
  * (resort = 1) run one after the other, bit for bit.  A query whose frontier holds fewer than k entries writes what it has
  * and raises PANN_STATUS_SHORT_FRONTIER (the reference aborts there, :416-419; callers reproduce that).
- * Scratch (one-byte / sketch / normalised queries, frontiers) belongs to quant and grows on first use. */
+ * Scratch (one-byte / sketch / normalised queries, frontiers) belongs to quant and grows on first use.
+ * quant may also be a four-bit copy (PANN_U4 / PANN_I4, qparams of kind EUCLID_U4 / MIPS_I4): step 1 then writes packed nibble
+ * rows, the contract is the same.  use_filter != 0 with a four-bit quant -> PANN_ERR_UNSUPPORTED. */
 typedef struct pann_rerank_out {
   uint32_t* ids;            /* nq x k, sorted by (exact dist, id); unused slots 0xFFFFFFFF */
   float*    dists;          /* nq x k, exact distances on the full-precision handle; unused slots +inf */

@@ -19,9 +19,10 @@ LIB_PATH = os.path.join(_HERE, "lib", "libpann.so")
 if os.environ.get("PANN_LIBRARY"):      # A/B runs of diagnostic builds (tools/): same ABI, another file
     LIB_PATH = os.environ["PANN_LIBRARY"]
 
-PANN_U8, PANN_I8, PANN_F32, PANN_F16, PANN_BF16 = 0, 1, 2, 3, 4
+PANN_U8, PANN_I8, PANN_F32, PANN_F16, PANN_BF16, PANN_U4, PANN_I4 = 0, 1, 2, 3, 4, 5, 6
 PANN_L2, PANN_MIPS = 0, 1
 PANN_OK = 0
+PANN_ERR_BAD_ARG, PANN_ERR_UNSUPPORTED = 1, 4
 PANN_ERR_OVERFLOW = 5
 PANN_ABI_VERSION = 3
 PANN_STATUS_VISITED_OVERFLOW, PANN_STATUS_DROPPED_OVERFLOW, PANN_STATUS_SHORT_FRONTIER = 1, 2, 4
@@ -58,17 +59,18 @@ class BuildStats(C.Structure):
                 ("per_point_visited", C.c_void_p), ("per_point_dist_cmps", C.c_void_p)]
 
 
-PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8 = 0, 1
+PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4 = 0, 1, 2, 3
 
 
 class QuantParams(C.Structure):
-    """pann_quant_params: Euclidian_Point<uint8_t>::parameters (slope, offset) / Quantized_Mips_Point<8>::parameters (max_val)."""
+    """pann_quant_params: Euclidian_Point<uint8_t>::parameters (slope, offset) / Quantized_Mips_Point<8>::parameters (max_val);
+    the four-bit kinds use the same fields (range 15)."""
     _fields_ = [("kind", C.c_int32), ("dims", C.c_int32), ("slope", C.c_float), ("offset", C.c_int32),
                 ("max_val", C.c_float), ("min_seen", C.c_float), ("max_seen", C.c_float)]
 
     @property
     def identity(self):
-        return self.slope == 1.0 and self.offset == 0
+        return self.kind != PANN_QUANT_EUCLID_U4 and self.slope == 1.0 and self.offset == 0      # the 4-bit translate never casts
 
 
 PANN_SKETCH_EUCLID_BIT, PANN_SKETCH_MIPS_BIT, PANN_SKETCH_MIPS_2BIT = 0, 1, 2

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "pann_internal.h"
+#include "quant_device.h"
 
 namespace pann {
 
@@ -87,11 +88,6 @@ struct pann_index {
 
 namespace {
 
-static uint32_t esize_of(int dtype) {
-  switch (dtype) { case PANN_U8: case PANN_I8: return 1; case PANN_F16: case PANN_BF16: return 2; case PANN_F32: return 4; }
-  return 0;
-}
-
 struct DeviceGuard {
   int prev = -1; bool ok = true;
   explicit DeviceGuard(int dev) {
@@ -148,6 +144,18 @@ __global__ void fill_u32_kernel(uint32_t* p, uint64_t n, uint32_t v) {
 int check_idx(const pann_index* idx, const char* fn) {
   if (!idx) { set_error(std::string(fn) + ": null index handle"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
+}
+
+// A four-bit handle is searched and measured; everything else refuses it (include/pann.h, pann_dtype) -- first thing after the
+// null check, before anything is launched, allocated or written.  (PANN_TYPE_SWITCH has no four-bit branch.)
+int refuse_4bit(const pann_index* idx, const char* fn) {
+  if (!is_4bit_dtype(idx->ix.dtype)) return PANN_OK;
+  set_error(std::string(fn) + ": not supported on a four-bit (" + dtype_name(idx->ix.dtype) + ") handle");
+  return PANN_ERR_UNSUPPORTED;
+}
+int check_idx_no4(const pann_index* idx, const char* fn) {
+  if (int rc = check_idx(idx, fn)) return rc;
+  return refuse_4bit(idx, fn);
 }
 
 int upload_graph_rows(pann_index* idx, const uint32_t* h_rows, uint64_t m, const uint32_t* h_row_ids) {
@@ -282,7 +290,7 @@ int pann_index_create(pann_index** out, const void* points, uint64_t n, uint32_t
 }
 
 int pann_index_create_empty(pann_index** out, uint64_t n, uint32_t d, int dtype, int metric, uint32_t max_deg, int device) {
-  return index_create_impl(out, nullptr, n, d, dtype, (uint64_t)d * esize_of(dtype), metric, nullptr, max_deg, device);
+  return index_create_impl(out, nullptr, n, d, dtype, row_bytes_of(dtype, d), metric, nullptr, max_deg, device);
 }
 
 int pann_index_upload_points(pann_index* idx, uint64_t first_row, const void* rows, uint64_t nrows, uint64_t row_stride_bytes) {
@@ -307,10 +315,13 @@ static int index_create_impl(pann_index** out, const void* points, uint64_t n, u
                              uint64_t row_stride_bytes, int metric, const uint32_t* graph,
                              uint32_t max_deg, int device) {
   if (!out || n == 0 || d == 0) { set_error("pann_index_create: null/empty argument"); return PANN_ERR_BAD_ARG; }
-  const uint32_t es = esize_of(dtype);
-  if (es == 0) { set_error("pann_index_create: unknown dtype"); return PANN_ERR_BAD_ARG; }
+  if (!dtype_known(dtype)) { set_error("pann_index_create: unknown dtype"); return PANN_ERR_BAD_ARG; }
   if (metric != PANN_L2 && metric != PANN_MIPS) { set_error("pann_index_create: unknown metric"); return PANN_ERR_BAD_ARG; }
-  if (row_stride_bytes < (uint64_t)d * es) { set_error("pann_index_create: row stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  if ((dtype == PANN_U4 && metric != PANN_L2) || (dtype == PANN_I4 && metric != PANN_MIPS)) {
+    set_error(std::string("pann_index_create: ") + dtype_name(dtype) + " goes with " + (dtype == PANN_U4 ? "PANN_L2" : "PANN_MIPS") + " only");
+    return PANN_ERR_UNSUPPORTED;
+  }
+  if (row_stride_bytes < row_bytes_of(dtype, d)) { set_error("pann_index_create: row stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   if (n >= 0x7FFFFFFFull) { set_error("pann_index_create: n must be < 2^31 (robustPrune uses int ids, vamana/index.h:97)"); return PANN_ERR_BAD_ARG; }
   if (max_deg == 0 || max_deg > 4096) { set_error("pann_index_create: max_deg out of range [1,4096]"); return PANN_ERR_BAD_ARG; }
   int ndev = pann_device_count();
@@ -322,7 +333,7 @@ static int index_create_impl(pann_index** out, const void* points, uint64_t n, u
   pann_index* idx = new pann_index();
   idx->device = device;
   DeviceIndex& ix = idx->ix;
-  ix.n = n; ix.d = d; ix.dtype = dtype; ix.metric = metric; ix.esize = es; ix.dbytes = d * es;
+  ix.n = n; ix.d = d; ix.dtype = dtype; ix.metric = metric; ix.esize = esize_of(dtype); ix.dbytes = (uint32_t)row_bytes_of(dtype, d);
   choose_point_layout(ix.dbytes, &ix.lpc, &ix.nch);
   ix.pstride = ix.lpc * ix.nch * 16;
   ix.max_deg = max_deg; ix.gstride = (max_deg + 15) / 16 * 16;
@@ -497,6 +508,7 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
                                  const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
                                  uint64_t sq_stride, uint32_t* d_pruned) {
   if (int rc = search_common_checks(idx, nq, qp, d_out)) return rc;
+  if (filter) { if (int rc = refuse_4bit(idx, "pann_batch_search_filtered_dev")) return rc; }
   if (!d_starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if (d_queries && q_stride_bytes < idx->ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
@@ -566,6 +578,7 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   if (int rc = search_common_checks(idx, nq, qp, out)) return rc;
   uint32_t sk_row = 0;
   if (filter) {
+    if (int rc = refuse_4bit(idx, "pann_batch_search_filtered")) return rc;
     if (!idx->ix.sketch) { set_error("pann_batch_search_filtered: no sketch attached to the index"); return PANN_ERR_BAD_ARG; }
     if ((queries != nullptr) != (sketch_queries != nullptr)) {
       set_error("pann_batch_search_filtered: sketch_queries go with queries, and only with them"); return PANN_ERR_BAD_ARG;
@@ -700,7 +713,7 @@ int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, con
 int pann_robust_prune_batch(pann_index* idx, const uint32_t* owners, uint64_t m, const uint32_t* cand_ids,
                             const float* cand_dists, const uint64_t* cand_offsets, double alpha, uint32_t R,
                             int add_out_nbrs, uint32_t* out_rows, uint32_t* out_dist_cmps) {
-  if (int rc = check_idx(idx, "pann_robust_prune_batch")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_robust_prune_batch")) return rc;
   if (m && (!owners || !cand_offsets || !out_rows)) { set_error("pann_robust_prune_batch: null argument"); return PANN_ERR_BAD_ARG; }
   if (m && cand_offsets[m] && !cand_ids) { set_error("pann_robust_prune_batch: null candidate ids"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
@@ -712,7 +725,7 @@ static uint32_t default_vcap(uint32_t L) { return std::max<uint32_t>(2 * L, 128)
 
 int pann_vamana_insert_batch(pann_index* idx, const uint32_t* batch_ids, uint64_t m, uint32_t start, uint32_t R,
                              uint32_t L, double alpha, pann_build_stats* stats) {
-  if (int rc = check_idx(idx, "pann_vamana_insert_batch")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_vamana_insert_batch")) return rc;
   if (m == 0) return PANN_OK;
   if (!batch_ids) { set_error("pann_vamana_insert_batch: null batch"); return PANN_ERR_BAD_ARG; }
   if (L == 0 || L > 65536) { set_error("pann_vamana_insert_batch: L out of range"); return PANN_ERR_BAD_ARG; }
@@ -734,7 +747,7 @@ int pann_vamana_insert_batch(pann_index* idx, const uint32_t* batch_ids, uint64_
 
 int pann_vamana_search_prune_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, uint32_t start, uint32_t R, uint32_t L,
                                  double alpha, uint32_t* d_rows_out, pann_build_stats* stats) {
-  if (int rc = check_idx(idx, "pann_vamana_search_prune_dev")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_vamana_search_prune_dev")) return rc;
   if (m == 0) return PANN_OK;
   if (!d_batch_ids || !d_rows_out) { set_error("pann_vamana_search_prune_dev: null argument"); return PANN_ERR_BAD_ARG; }
   if (L == 0 || L > 65536) { set_error("pann_vamana_search_prune_dev: L out of range"); return PANN_ERR_BAD_ARG; }
@@ -748,7 +761,7 @@ int pann_vamana_search_prune_dev(pann_index* idx, const uint32_t* d_batch_ids, u
 
 int pann_vamana_apply_rows_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, const uint32_t* d_rows, uint32_t R,
                                double alpha, pann_build_stats* stats) {
-  if (int rc = check_idx(idx, "pann_vamana_apply_rows_dev")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_vamana_apply_rows_dev")) return rc;
   if (m == 0) return PANN_OK;
   if (!d_batch_ids || !d_rows) { set_error("pann_vamana_apply_rows_dev: null argument"); return PANN_ERR_BAD_ARG; }
   if (m > 0xFFFFFFF0ull) { set_error("pann_vamana_apply_rows_dev: batch too large"); return PANN_ERR_BAD_ARG; }
@@ -757,7 +770,7 @@ int pann_vamana_apply_rows_dev(pann_index* idx, const uint32_t* d_batch_ids, uin
 }
 
 int pann_vamana_sort_neighbors(pann_index* idx) {
-  if (int rc = check_idx(idx, "pann_vamana_sort_neighbors")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_vamana_sort_neighbors")) return rc;
   DeviceGuard g(idx->device);
   idx->ix.codes_valid = 0;                              // the rows are permuted without their filter codes
   return sort_neighbors_dev(idx->ix, idx->stream);
@@ -835,7 +848,7 @@ __global__ void random_edges_kernel(uint32_t* graph, uint32_t gstride, uint64_t 
 
 int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint32_t degree,
                                    uint64_t seed, int sort_neighbors, pann_build_stats* stats) {
-  if (int rc = check_idx(idx, "pann_vamana_build_single_batch")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_vamana_build_single_batch")) return rc;
   if (L == 0 || L > 65536 || num_passes < 1) { set_error("pann_vamana_build_single_batch: bad L / num_passes"); return PANN_ERR_BAD_ARG; }
   if (degree == 0 || degree > idx->ix.max_deg) { set_error("pann_vamana_build_single_batch: degree must be in [1, max_deg]"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
@@ -870,7 +883,7 @@ int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, doub
 
 int pann_vamana_build(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint64_t seed,
                       int sort_neighbors, pann_build_stats* stats) {
-  if (int rc = check_idx(idx, "pann_vamana_build")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_vamana_build")) return rc;
   if (L == 0 || L > 65536 || num_passes < 1) { set_error("pann_vamana_build: bad L / num_passes"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
   const uint64_t n = idx->ix.n;
@@ -962,7 +975,7 @@ int pann_query_distances(pann_index* idx, const void* queries, uint64_t nq, uint
 
 int pann_leaf_knn_batch(pann_index* idx, const uint32_t* ids, const uint64_t* leaf_offsets, uint64_t nleaves,
                         uint32_t m, uint32_t* out_ids, float* out_dists) {
-  if (int rc = check_idx(idx, "pann_leaf_knn_batch")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_leaf_knn_batch")) return rc;
   if (nleaves == 0) return PANN_OK;
   if (!ids || !leaf_offsets || !out_ids || !out_dists) { set_error("pann_leaf_knn: null argument"); return PANN_ERR_BAD_ARG; }
   const uint64_t total = leaf_offsets[nleaves];
@@ -1007,7 +1020,7 @@ int pann_leaf_knn(pann_index* idx, const uint32_t* ids, uint32_t N, uint32_t m, 
 
 int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                         uint32_t* out_ids, float* out_dists) {
-  if (int rc = check_idx(idx, "pann_bruteforce_knn")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_bruteforce_knn")) return rc;
   if (nq == 0) return PANN_OK;
   if (!queries || !out_ids || !out_dists) { set_error("pann_bruteforce_knn: null argument"); return PANN_ERR_BAD_ARG; }
   if (q_stride_bytes < idx->ix.dbytes) { set_error("pann_bruteforce_knn: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
@@ -1049,7 +1062,7 @@ int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint6
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,
                      const uint32_t* pivot_a, const uint32_t* pivot_b, uint8_t* out_side) {
-  if (int rc = check_idx(idx, "pann_pivot_split")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_pivot_split")) return rc;
   if (nseg == 0) return PANN_OK;
   if (!ids || !seg_offsets || !pivot_a || !pivot_b || !out_side) { set_error("pann_pivot_split: null argument"); return PANN_ERR_BAD_ARG; }
   const uint64_t total = seg_offsets[nseg];
@@ -1090,7 +1103,7 @@ int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_o
 
 int pann_rerank(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, const uint32_t* cand_ids,
                 uint32_t c, const uint32_t* cand_counts, uint32_t k, int resort, uint32_t* out_ids, float* out_dists) {
-  if (int rc = check_idx(idx, "pann_rerank")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_rerank")) return rc;
   if (nq == 0) return PANN_OK;
   if (!queries || !cand_ids || !out_ids || !out_dists || k == 0) { set_error("pann_rerank: null argument"); return PANN_ERR_BAD_ARG; }
   if (q_stride_bytes < idx->ix.dbytes) { set_error("pann_rerank: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
@@ -1123,7 +1136,7 @@ int pann_range_search(pann_index* idx, const void* queries, const uint32_t* quer
                       uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int starts_per_query,
                       float radius_2, uint32_t max_results, uint32_t* out_ids, uint32_t* out_counts,
                       uint32_t* out_dist_cmps, uint32_t* out_truncated) {
-  if (int rc = check_idx(idx, "pann_range_search")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_range_search")) return rc;
   if (nq == 0) return PANN_OK;
   const DeviceIndex& ix = idx->ix;
   if ((queries == nullptr) == (query_ids == nullptr)) { set_error("pann_range_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
@@ -1176,6 +1189,7 @@ static int check_idx_or_device(const pann_index* idx, const char* fn) {
 int pann_bruteforce_range(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, float radius,
                           uint64_t* out_offsets, uint32_t* out_ids, uint64_t ids_capacity) {
   if (int rc = check_idx_or_device(idx, "pann_bruteforce_range")) return rc;
+  if (int rc = refuse_4bit(idx, "pann_bruteforce_range")) return rc;
   if (std::isnan(radius)) { set_error("pann_bruteforce_range: radius is NaN"); return PANN_ERR_BAD_ARG; }
   if (!out_offsets) { set_error("pann_bruteforce_range: null out_offsets"); return PANN_ERR_BAD_ARG; }
   if (nq == 0) { out_offsets[0] = 0; return PANN_OK; }
@@ -1213,6 +1227,7 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
                      uint32_t* out_search_cmps, uint32_t* out_visited, uint32_t* out_range_cmps,
                      uint32_t* out_truncated) {
   if (int rc = check_idx_or_device(idx, "pann_range_query")) return rc;
+  if (int rc = refuse_4bit(idx, "pann_range_query")) return rc;
   const DeviceIndex& ix = idx->ix;
   if (!qp) { set_error("pann_range_query: null params"); return PANN_ERR_BAD_ARG; }
   if (qp->k > qp->beam) {  // beamSearch.h:368-372, :549-553
@@ -1304,7 +1319,7 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
 
 int pann_hcnng_build_trees_dev(pann_index* idx, uint32_t first_tree, uint32_t tree_step, uint32_t ntrees, uint32_t cluster_size,
                                uint32_t mst_deg, uint64_t seed, uint32_t* d_slab, uint32_t slab_stride, double* times3) {
-  if (int rc = check_idx(idx, "pann_hcnng_build_trees_dev")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_hcnng_build_trees_dev")) return rc;
   if (mst_deg == 0 || tree_step == 0 || !d_slab) { set_error("pann_hcnng_build_trees_dev: null / zero argument"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
   hipLaunchKernelGGL(fill_u32_kernel, dim3(2048), dim3(256), 0, idx->stream, d_slab, idx->ix.n * (uint64_t)slab_stride, SENTINEL);
@@ -1315,7 +1330,7 @@ int pann_hcnng_build_trees_dev(pann_index* idx, uint32_t first_tree, uint32_t tr
 
 int pann_hcnng_assemble_dev(pann_index* idx, const uint32_t* d_slabs, uint32_t nslabs, uint32_t slab_stride, uint32_t ntrees,
                             uint32_t mst_deg) {
-  if (int rc = check_idx(idx, "pann_hcnng_assemble_dev")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_hcnng_assemble_dev")) return rc;
   if (!d_slabs || mst_deg == 0) { set_error("pann_hcnng_assemble_dev: null / zero argument"); return PANN_ERR_BAD_ARG; }
   if ((uint64_t)ntrees * mst_deg > idx->ix.max_deg) { set_error("pann_hcnng_assemble_dev: max_deg < ntrees * mst_deg"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
@@ -1325,7 +1340,7 @@ int pann_hcnng_assemble_dev(pann_index* idx, const uint32_t* d_slabs, uint32_t n
 
 int pann_hcnng_build(pann_index* idx, uint32_t num_clusters, uint32_t cluster_size, uint32_t mst_deg, uint64_t seed,
                      double* times3) {
-  if (int rc = check_idx(idx, "pann_hcnng_build")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_hcnng_build")) return rc;
   if (num_clusters == 0 || mst_deg == 0) { set_error("pann_hcnng_build: num_clusters and mst_deg must be positive"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
   idx->ix.codes_valid = 0;
@@ -1341,7 +1356,7 @@ int pann_hcnng_build(pann_index* idx, uint32_t num_clusters, uint32_t cluster_si
 namespace {
 
 int check_quant_kind(int kind, const char* fn) {
-  if (kind != PANN_QUANT_EUCLID_U8 && kind != PANN_QUANT_MIPS_I8) { set_error(std::string(fn) + ": unknown quantisation kind"); return PANN_ERR_BAD_ARG; }
+  if (kind != PANN_QUANT_EUCLID_U8 && kind != PANN_QUANT_MIPS_I8 && kind != PANN_QUANT_EUCLID_U4 && kind != PANN_QUANT_MIPS_I4) { set_error(std::string(fn) + ": unknown quantisation kind"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
 }
 int check_quant_rows(const float* rows, uint64_t n, uint32_t d, uint64_t stride, const char* fn) {
@@ -1359,8 +1374,8 @@ int check_quant_source(const pann_index* src, int kind, const char* fn) {
   if (int rc = check_idx(src, fn)) return rc;
   if (src->ix.dtype != PANN_F32) { set_error(std::string(fn) + ": the source index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
   if (int rc = check_quant_kind(kind, fn)) return rc;
-  if ((kind == PANN_QUANT_EUCLID_U8) != (src->ix.metric == PANN_L2)) {
-    set_error(std::string(fn) + ": kind does not fit the index's metric (EUCLID_U8 <-> L2, MIPS_I8 <-> MIPS)"); return PANN_ERR_BAD_ARG;
+  if (quant_kind_is_euclid(kind) != (src->ix.metric == PANN_L2)) {
+    set_error(std::string(fn) + ": kind does not fit the index's metric (EUCLID_U8 / EUCLID_U4 <-> L2, MIPS_I8 / MIPS_I4 <-> MIPS)"); return PANN_ERR_BAD_ARG;
   }
   return PANN_OK;
 }
@@ -1380,7 +1395,7 @@ void pann_quantize_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b
 }
 
 int pann_index_normalize(pann_index* idx) {
-  if (int rc = check_idx(idx, "pann_index_normalize")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_index_normalize")) return rc;
   DeviceIndex& ix = idx->ix;
   if (ix.dtype != PANN_F32) { set_error("pann_index_normalize: float (PANN_F32) handles only"); return PANN_ERR_UNSUPPORTED; }
   DeviceGuard g(idx->device);
@@ -1417,9 +1432,10 @@ int pann_index_create_quantized(pann_index** out, pann_index* src, const pann_qu
   if (int rc = check_quant_source(src, p->kind, "pann_index_create_quantized")) return rc;
   const DeviceIndex& sx = src->ix;
   if ((uint32_t)p->dims != sx.d) { set_error("pann_index_create_quantized: parameters made for another dimension"); return PANN_ERR_BAD_ARG; }
-  const bool eu = p->kind == PANN_QUANT_EUCLID_U8;
+  const int qdt = quant_kind_dtype(p->kind);
   pann_index* q = nullptr;
-  if (int rc = index_create_impl(&q, nullptr, sx.n, sx.d, eu ? PANN_U8 : PANN_I8, sx.d, eu ? PANN_L2 : PANN_MIPS, nullptr, sx.max_deg, src->device)) return rc;
+  if (int rc = index_create_impl(&q, nullptr, sx.n, sx.d, qdt, row_bytes_of(qdt, sx.d), quant_kind_is_euclid(p->kind) ? PANN_L2 : PANN_MIPS, nullptr,
+                                 sx.max_deg, src->device)) return rc;
   DeviceGuard g(src->device);
   auto fail = [&](int rc) { pann_index_destroy(q); return rc; };
   // the new handle's rows are zero (pad bytes included) and its stream is idle; src's stream orders the reads of src
@@ -1437,7 +1453,7 @@ int pann_quantize_rows_dev(const pann_quant_params* p, const float* d_rows, uint
   if (int rc = check_quant_params(p, "pann_quantize_rows_dev")) return rc;
   if (int rc = check_quant_rows(d_rows, n, (uint32_t)p->dims, stride_bytes, "pann_quantize_rows_dev")) return rc;
   if (!d_out) { set_error("pann_quantize_rows_dev: null output"); return PANN_ERR_BAD_ARG; }
-  if (out_stride_bytes < (uint64_t)p->dims) { set_error("pann_quantize_rows_dev: output stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  if (out_stride_bytes < row_bytes_of(quant_kind_dtype(p->kind), (uint64_t)p->dims)) { set_error("pann_quantize_rows_dev: output stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   if (normalize_first) return quant_normalize_dev(d_rows, n, (uint32_t)p->dims, stride_bytes, p, d_out, out_stride_bytes, (hipStream_t)stream);
   return quant_translate_dev(p, d_rows, n, (uint32_t)p->dims, stride_bytes, d_out, out_stride_bytes, (hipStream_t)stream);
 }
@@ -1448,7 +1464,8 @@ int pann_quantize_rows(const pann_quant_params* p, const float* rows, uint64_t n
   const uint32_t d = (uint32_t)p->dims;
   if (int rc = check_quant_rows(rows, n, d, stride_bytes, "pann_quantize_rows")) return rc;
   if (!out) { set_error("pann_quantize_rows: null output"); return PANN_ERR_BAD_ARG; }
-  if (out_stride_bytes < d) { set_error("pann_quantize_rows: output stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  const uint64_t ob_row = row_bytes_of(quant_kind_dtype(p->kind), d);     // bytes of one output row: d, or ceil(d / 2) packed
+  if (out_stride_bytes < ob_row) { set_error("pann_quantize_rows: output stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   const int ndev = pann_device_count();
   if (ndev <= 0) { set_error("pann_quantize_rows: no HIP device visible (this library has no CPU path)"); return PANN_ERR_NO_DEVICE; }
   if (device < 0 || device >= ndev) { set_error("pann_quantize_rows: device ordinal out of range"); return PANN_ERR_BAD_ARG; }
@@ -1460,14 +1477,14 @@ int pann_quantize_rows(const pann_quant_params* p, const float* rows, uint64_t n
   auto done = [&](int rc) { in.release(); ob.release(); return rc; };
   const uint64_t cap = std::min(slice, n);
   if (int rc = in.ensure(cap * d * 4)) return done(rc);
-  if (int rc = ob.ensure(cap * d)) return done(rc);
+  if (int rc = ob.ensure(cap * ob_row)) return done(rc);
   for (uint64_t r0 = 0; r0 < n; r0 += slice) {
     const uint64_t cnt = std::min(slice, n - r0);
     hipError_t e = hipMemcpy2D(in.p, (size_t)d * 4, (const uint8_t*)rows + r0 * stride_bytes, stride_bytes, (size_t)d * 4, cnt, hipMemcpyHostToDevice);
     if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(rows)"));
-    if (int rc = pann_quantize_rows_dev(p, in.as<float>(), cnt, (uint64_t)d * 4, normalize_first, ob.p, d, nullptr)) return done(rc);
+    if (int rc = pann_quantize_rows_dev(p, in.as<float>(), cnt, (uint64_t)d * 4, normalize_first, ob.p, ob_row, nullptr)) return done(rc);
     if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
-    e = hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ob.p, d, d, cnt, hipMemcpyDeviceToHost);
+    e = hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ob.p, ob_row, ob_row, cnt, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(out)"));
   }
   return done(PANN_OK);
@@ -1541,7 +1558,7 @@ int pann_sketch_params_generate(pann_index* src, int kind, pann_sketch_params* o
 }
 
 int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch_params* p) {
-  if (int rc = check_idx(idx, "pann_index_attach_sketch")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_index_attach_sketch")) return rc;
   if (int rc = check_idx(src, "pann_index_attach_sketch")) return rc;
   if (int rc = check_sketch_params(p, "pann_index_attach_sketch")) return rc;
   if (int rc = check_sketch_source(src, "pann_index_attach_sketch")) return rc;
@@ -1563,7 +1580,7 @@ int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch
 }
 
 int pann_index_upload_sketch(pann_index* idx, const pann_sketch_params* p, const void* rows, uint64_t stride_bytes) {
-  if (int rc = check_idx(idx, "pann_index_upload_sketch")) return rc;
+  if (int rc = check_idx_no4(idx, "pann_index_upload_sketch")) return rc;
   if (int rc = check_sketch_params(p, "pann_index_upload_sketch")) return rc;
   const DeviceIndex& ix = idx->ix;
   if (!rows) { set_error("pann_index_upload_sketch: null rows"); return PANN_ERR_BAD_ARG; }
@@ -1672,10 +1689,14 @@ int search_rerank_checks(const pann_index* full, const pann_index* quant, const 
     set_error(f + ": the two indices must agree in size, dimension, device and metric"); return PANN_ERR_BAD_ARG;
   }
   if (int rc = check_quant_kind(qparams->kind, fn)) return rc;
-  const bool eu = qparams->kind == PANN_QUANT_EUCLID_U8;
-  if (qx.dtype != (eu ? PANN_U8 : PANN_I8) || qx.metric != (eu ? PANN_L2 : PANN_MIPS) || (uint32_t)qparams->dims != qx.d) {
-    set_error(f + ": the quantisation parameters do not fit the one-byte index (EUCLID_U8 <-> u8 / L2, MIPS_I8 <-> i8 / MIPS, same dimension)");
+  const bool eu = quant_kind_is_euclid(qparams->kind);
+  if (qx.dtype != quant_kind_dtype(qparams->kind) || qx.metric != (eu ? PANN_L2 : PANN_MIPS) || (uint32_t)qparams->dims != qx.d) {
+    set_error(f + ": the quantisation parameters do not fit the one-byte index (EUCLID_U8 <-> u8 / L2, MIPS_I8 <-> i8 / MIPS, EUCLID_U4 <-> "
+                  "u4 / L2, MIPS_I4 <-> i4 / MIPS, same dimension)");
     return PANN_ERR_BAD_ARG;
+  }
+  if (use_filter && is_4bit_dtype(qx.dtype)) {
+    set_error(f + ": use_filter is not supported with a four-bit (" + dtype_name(qx.dtype) + ") quantised index"); return PANN_ERR_UNSUPPORTED;
   }
   if (use_filter && !qx.sketch) { set_error(f + ": use_filter needs a sketch attached to the one-byte index"); return PANN_ERR_BAD_ARG; }
   if (q_stride < 4ull * fx.d || q_stride % 4 != 0) { set_error(f + ": query stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }

@@ -1576,6 +1576,7 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   PANN_DISPATCH(PANN_F32, PANN_L2) PANN_DISPATCH(PANN_F32, PANN_MIPS)
   PANN_DISPATCH(PANN_F16, PANN_L2) PANN_DISPATCH(PANN_F16, PANN_MIPS)
   PANN_DISPATCH(PANN_BF16, PANN_L2) PANN_DISPATCH(PANN_BF16, PANN_MIPS)
+  PANN_DISPATCH(PANN_U4, PANN_L2) PANN_DISPATCH(PANN_I4, PANN_MIPS)      // the only pairings a four-bit handle can have
 #undef PANN_DISPATCH
   if (e != hipSuccess) return hip_fail(e, "beam_search_kernel launch");
   // the status word follows the results on the launch stream (pann_search_out::status, device pointer here)

@@ -1616,7 +1616,10 @@ int query_distances_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_
   const PointsView pv{ix.points, ix.pstride, ix.nch, ix.exact};
   const size_t qb = query_lds_bytes(ix);
 #define CALL_QD(DT, MT, L, N1) hipLaunchKernelGGL((query_distances_kernel<DT, MT, L, N1>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, pv, ix.dbytes, d_q_ext, q_stride, d_q_ids, d_ids, m, paired, d_out)
-  PANN_TYPE_SWITCH(ix, CALL_QD);
+  // four-bit handles reach this kernel only (every other user of PANN_TYPE_SWITCH refuses them at the C-ABI)
+  if (ix.dtype == PANN_U4) PANN_LAYOUT_SWITCH(ix, PANN_U4, PANN_L2, CALL_QD);
+  else if (ix.dtype == PANN_I4) PANN_LAYOUT_SWITCH(ix, PANN_I4, PANN_MIPS, CALL_QD);
+  else PANN_TYPE_SWITCH(ix, CALL_QD);
 #undef CALL_QD
   PANN_HIP(hipGetLastError());
   return PANN_OK;

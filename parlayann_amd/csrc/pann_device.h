@@ -95,6 +95,8 @@ template <> struct QReg<PANN_I8>  { uint4 raw; uint32_t qq; };
 template <> struct QReg<PANN_F32> { float f[4]; };
 template <> struct QReg<PANN_F16> { uint4 raw; };        // halves stay packed; widened inside v_fma_mix
 template <> struct QReg<PANN_BF16> { float f[8]; };      // widened once per query (a shift / a mask per element)
+template <> struct QReg<PANN_U4>  { uint4 raw; uint32_t qq; };   // 32 nibbles; qq = sum of their squares
+template <> struct QReg<PANN_I4>  { uint4 raw; };                // MIPS only: no norm term
 
 template <int DT> struct Acc;           // per-lane partial state
 template <> struct Acc<PANN_U8>  { uint32_t aa, aq; __device__ __forceinline__ void clear() { aa = 0; aq = 0; } };
@@ -102,6 +104,8 @@ template <> struct Acc<PANN_I8>  { int aa, aq;      __device__ __forceinline__ v
 template <> struct Acc<PANN_F32> { float2v s;       __device__ __forceinline__ void clear() { s = float2v{0.f, 0.f}; } };
 template <> struct Acc<PANN_F16> { float2v s;       __device__ __forceinline__ void clear() { s = float2v{0.f, 0.f}; } };
 template <> struct Acc<PANN_BF16> { float2v s;      __device__ __forceinline__ void clear() { s = float2v{0.f, 0.f}; } };
+template <> struct Acc<PANN_U4>  { uint32_t aa, aq; __device__ __forceinline__ void clear() { aa = 0; aq = 0; } };
+template <> struct Acc<PANN_I4>  { int aq;          __device__ __forceinline__ void clear() { aq = 0; } };
 
 template <int DT> struct AccT { using type = int; };             // type that crosses lanes
 template <> struct AccT<PANN_F32> { using type = float; };
@@ -128,6 +132,12 @@ __device__ __forceinline__ QReg<DT> make_qreg(const uint4& q) {
     t = __builtin_amdgcn_sdot4((int)q.z, (int)q.z, t, false);
     t = __builtin_amdgcn_sdot4((int)q.w, (int)q.w, t, false);
     r.qq = (uint32_t)t;
+  } else if constexpr (DT == PANN_U4) {          // v_dot8_u32_u4: eight nibble products per instruction
+    r.raw = q;
+    r.qq = __builtin_amdgcn_udot8(q.x, q.x, 0u, false);
+    r.qq = __builtin_amdgcn_udot8(q.y, q.y, r.qq, false);
+    r.qq = __builtin_amdgcn_udot8(q.z, q.z, r.qq, false);
+    r.qq = __builtin_amdgcn_udot8(q.w, q.w, r.qq, false);
   } else if constexpr (DT == PANN_F32) {
     r.f[0] = __uint_as_float(q.x); r.f[1] = __uint_as_float(q.y);
     r.f[2] = __uint_as_float(q.z); r.f[3] = __uint_as_float(q.w);
@@ -191,6 +201,25 @@ __device__ __forceinline__ void dist_accum(Acc<DT>& acc, const uint4& a, const Q
       acc.aa = __builtin_amdgcn_sdot4((int)a.w, (int)a.w, acc.aa, false);
       acc.aa += (int)q.qq;
     }
+  } else if constexpr (DT == PANN_U4) {
+    // 32 unsigned nibbles per step; L2 only: sum (a-q)^2 = a.a - 2 a.q + q.q on the nibble values, exact in int32
+    static_assert(METRIC == PANN_L2, "PANN_U4 is an L2 type");
+    acc.aq = __builtin_amdgcn_udot8(a.x, q.raw.x, acc.aq, false);
+    acc.aq = __builtin_amdgcn_udot8(a.y, q.raw.y, acc.aq, false);
+    acc.aq = __builtin_amdgcn_udot8(a.z, q.raw.z, acc.aq, false);
+    acc.aq = __builtin_amdgcn_udot8(a.w, q.raw.w, acc.aq, false);
+    acc.aa = __builtin_amdgcn_udot8(a.x, a.x, acc.aa, false);
+    acc.aa = __builtin_amdgcn_udot8(a.y, a.y, acc.aa, false);
+    acc.aa = __builtin_amdgcn_udot8(a.z, a.z, acc.aa, false);
+    acc.aa = __builtin_amdgcn_udot8(a.w, a.w, acc.aa, false);
+    acc.aa += q.qq;
+  } else if constexpr (DT == PANN_I4) {
+    // 32 two's-complement nibbles per step (v_dot8_i32_i4 sign-extends each: 0x8 is -8); MIPS only
+    static_assert(METRIC == PANN_MIPS, "PANN_I4 is a MIPS type");
+    acc.aq = __builtin_amdgcn_sdot8((int)a.x, (int)q.raw.x, acc.aq, false);
+    acc.aq = __builtin_amdgcn_sdot8((int)a.y, (int)q.raw.y, acc.aq, false);
+    acc.aq = __builtin_amdgcn_sdot8((int)a.z, (int)q.raw.z, acc.aq, false);
+    acc.aq = __builtin_amdgcn_sdot8((int)a.w, (int)q.raw.w, acc.aq, false);
   } else if constexpr (DT == PANN_F32) {
     const float2v a01{__uint_as_float(a.x), __uint_as_float(a.y)}, a23{__uint_as_float(a.z), __uint_as_float(a.w)};
     const float2v q01{q.f[0], q.f[1]}, q23{q.f[2], q.f[3]};
@@ -231,6 +260,10 @@ __device__ __forceinline__ typename AccT<DT>::type acc_lane_value(const Acc<DT>&
     if constexpr (METRIC == PANN_L2) return (int)(acc.aa - 2u * acc.aq); else return (int)acc.aq;
   } else if constexpr (DT == PANN_I8) {
     if constexpr (METRIC == PANN_L2) return acc.aa - 2 * acc.aq; else return acc.aq;
+  } else if constexpr (DT == PANN_U4) {
+    return (int)(acc.aa - 2u * acc.aq);
+  } else if constexpr (DT == PANN_I4) {
+    return acc.aq;
   } else {
     return acc.s.x + acc.s.y;
   }
@@ -240,6 +273,9 @@ __device__ __forceinline__ typename AccT<DT>::type acc_lane_value(const Acc<DT>&
 template <int DT, int METRIC>
 __device__ __forceinline__ float dist_finish(typename AccT<DT>::type tot) {
   float f = (float)tot;
+  // Quantized_Mips_Point<4>::distance_4 (mips_point.h:342-354) multiplies (int8_t)(p << 4) and (p & 240): each factor is its
+  // nibble value times 16, so what it returns is 256 x the nibble dot product (exact: a multiple of 256 far below 2^32)
+  if constexpr (DT == PANN_I4) f *= 256.0f;
   if constexpr (METRIC == PANN_MIPS) f = -f;
   return f;
 }

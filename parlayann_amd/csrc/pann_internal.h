@@ -20,8 +20,25 @@ inline const char* ab_env(const char* name) { return getenv(name); }
 inline const char* ab_env(const char*) { return nullptr; }
 #endif
 
+// ---- element types: bytes of one element (0 for the four-bit types: half a byte) and of one host-layout row of d elements.
+// A four-bit row is the reference's num_bytes() = (dims * bits - 1) / 8 + 1 (mips_point.h:297), two coordinates per byte.
+inline bool is_4bit_dtype(int dtype) { return dtype == PANN_U4 || dtype == PANN_I4; }
+inline const char* dtype_name(int dtype) {
+  switch (dtype) {
+    case PANN_U8: return "PANN_U8"; case PANN_I8: return "PANN_I8"; case PANN_F32: return "PANN_F32"; case PANN_F16: return "PANN_F16";
+    case PANN_BF16: return "PANN_BF16"; case PANN_U4: return "PANN_U4"; case PANN_I4: return "PANN_I4";
+  }
+  return "unknown dtype";
+}
+inline uint32_t esize_of(int dtype) {
+  switch (dtype) { case PANN_U8: case PANN_I8: return 1; case PANN_F16: case PANN_BF16: return 2; case PANN_F32: return 4; }
+  return 0;
+}
+inline bool dtype_known(int dtype) { return esize_of(dtype) != 0 || is_4bit_dtype(dtype); }
+inline uint64_t row_bytes_of(int dtype, uint64_t d) { return is_4bit_dtype(dtype) ? (d + 1) / 2 : d * esize_of(dtype); }
+
 // ---- device-side layout of one index (DESIGN.md "Data layout in HBM") ----
-//  points: n rows, row stride pstride = nch * lpc * 16 bytes (>= d*esize), zero padded
+//  points: n rows, row stride pstride = nch * lpc * 16 bytes (>= row_bytes_of(dtype, d)), zero padded
 //  graph : n rows of gstride uint32 (gstride = max_deg rounded up to 16), neighbours packed at the
 //          front, unused slots = SENTINEL; the degree is not stored (it is the count of
 //          non-sentinel slots), so a row of max_deg 64 is exactly one aligned 256-byte read.
@@ -31,8 +48,8 @@ struct DeviceIndex {
   uint64_t n = 0;
   uint32_t d = 0;
   int dtype = 0, metric = 0;
-  uint32_t esize = 0;    // bytes per element
-  uint32_t dbytes = 0;   // d * esize
+  uint32_t esize = 0;    // bytes per element (0 for the four-bit types: sizes of rows come from dbytes)
+  uint32_t dbytes = 0;   // row_bytes_of(dtype, d): bytes of one host-layout row
   uint32_t pstride = 0;  // device row stride in bytes
   uint32_t lpc = 0;      // lanes per candidate in the gather-distance loops (4,8,16,32)
   uint32_t nch = 0;      // 16-byte chunks per lane: pstride = nch*lpc*16

@@ -6,6 +6,7 @@
 //   select_scan_kernel                                                                                  a sort: 11 + 11 + 10 bit radix select)
 //   normalize_rows_kernel  Mips_Point::normalize                           mips_point.h:115-124       (double sum in index order)
 //   translate_kernel       translate_point                                 euclidian_point.h:182-209, mips_point.h:416-430
+//   translate4_kernel      the same with range = 15, two coordinates per output byte (Quantized_Mips_Point<4>::assign, :399-406)
 //
 // Results are bit-identical to the sequential C++ restatement (oracle/) on finite inputs.  Two things that takes:
 //   * products are rounded before anything is added to them -- the pragma below (hipcc contracts a * b + c by default);
@@ -107,7 +108,7 @@ __global__ void quant_init_kernel(uint8_t* scratch, int kind, unsigned long long
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(scratch + SCRATCH_HIST_OFF);
   for (uint32_t i = threadIdx.x; i < 2 * QBINS; i += blockDim.x) hist[i] = 0;
   if (threadIdx.x == 0) {
-    if (kind == PANN_QUANT_EUCLID_U8) {
+    if (quant_kind_is_euclid(kind)) {
       uint32_t* w = reinterpret_cast<uint32_t*>(scratch);
       w[0] = 0x80000000u; w[1] = 0x80000000u; w[2] = 0;
     } else {
@@ -217,12 +218,27 @@ __global__ __launch_bounds__(256) void translate_kernel(const uint8_t* __restric
   }
 }
 
+// Four-bit kinds: one thread produces one whole output byte from two coordinates (the last byte of an odd row from one, its high
+// nibble zero), so no two threads share a byte and every store is a plain byte store.  Thread t -> byte t % rb of row t / rb.
+__global__ __launch_bounds__(256) void translate4_kernel(const uint8_t* __restrict__ src, uint64_t sstride, uint64_t nrows,
+                                                         uint32_t len, QParams q, uint8_t* __restrict__ dst, uint64_t dstride) {
+  const uint32_t rb = (len + 1) / 2;
+  const uint64_t total = nrows * rb;
+  for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (uint64_t)gridDim.x * blockDim.x) {
+    const uint64_t r = t / rb;
+    const uint32_t c = (uint32_t)(t - r * rb);
+    const float* __restrict__ row = reinterpret_cast<const float*>(src + r * sstride);
+    const bool hi = 2 * c + 1 < len;
+    dst[r * dstride + c] = (uint8_t)quantize_pair4(row[2 * c], hi ? row[2 * c + 1] : 0.0f, hi, q);
+  }
+}
+
 // ---- normalize (and, for const sources, normalize + translate in one go) ------------------------------------------------------
 // One wave per block.  A tile of R rows is staged in LDS with coalesced loads (row stride ld floats, odd: lanes that walk
 // different rows hit different banks); lane r then walks row r in index order -- float product, double sum, as the reference's
 // loop does; the order is part of the result -- and the tile is written back scaled, coalesced again.
 // mode 0: f32 rows to dst (dst == src: in place; a tile is read completely before any of it is written);
-// mode 1: the scaled values go through translate_point, bytes to dst.
+// mode 1: the scaled values go through translate_point, bytes to dst (a four-bit kind: one lane per output byte, two values).
 template <int V>
 __global__ __launch_bounds__(64) void normalize_rows_kernel(const uint8_t* src, uint64_t sstride, uint64_t n, uint32_t d,
                                                             uint32_t R, uint32_t ld, int mode, QParams q, uint8_t* dst,
@@ -272,6 +288,11 @@ __global__ __launch_bounds__(64) void normalize_rows_kernel(const uint8_t* src, 
           for (uint32_t c = (full << 2) + lane; c < d; c += 64) o[c] = t[c] * inv;
         } else {
           for (uint32_t c = lane; c < d; c += 64) o[c] = t[c] * inv;
+        }
+      } else if (q.bits4) {
+        for (uint32_t c = lane; c < (d + 1) / 2; c += 64) {
+          const bool hi = 2 * c + 1 < d;
+          orow[c] = (uint8_t)quantize_pair4(t[2 * c] * inv, hi ? t[2 * c + 1] * inv : 0.0f, hi, q);
         }
       } else {
         const uint32_t full = dst_al4 ? (d >> 2) : 0;
@@ -375,7 +396,7 @@ int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t strid
   const int nv = make_views(d_rows, n, d, stride, nullptr, 0, v);
   pann_quant_params p{};
   p.kind = kind; p.dims = (int32_t)d; p.slope = 1.0f; p.offset = 0; p.max_val = 0.0f;
-  if (kind == PANN_QUANT_EUCLID_U8) {
+  if (quant_kind_is_euclid(kind)) {
     hipLaunchKernelGGL(quant_init_kernel, dim3(1), dim3(256), 0, st, sc, kind, 0ull, 0ull);
     PANN_HIP(hipGetLastError());
     for (int i = 0; i < nv; i++) {
@@ -394,8 +415,9 @@ int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t strid
     PANN_HIP(hipMemcpyAsync(w, sc, sizeof(w), hipMemcpyDeviceToHost, st));
     PANN_HIP(hipStreamSynchronize(st));
     float min_val = key_to_float(w[0]) + 0.0f, max_val = key_to_float(w[1]);     // (-0.0f + 0.0f == +0.0f: std::min(0.0f, -0.0f) keeps +0)
-    if (!w[2]) { if (max_val < 256) max_val = 255; min_val = 0; }              // euclidian_point.h:228-231
-    const long range = 255;
+    const bool u4 = kind == PANN_QUANT_EUCLID_U4;
+    if (!w[2] && !u4) { if (max_val < 256) max_val = 255; min_val = 0; }       // euclidian_point.h:228-231 (a cast cannot fit 4 bits)
+    const long range = u4 ? 15 : 255;
     p.slope = range / (max_val - min_val);                                       // :106
     p.offset = (int32_t)std::round(min_val * p.slope);                           // :107
     p.min_seen = min_val; p.max_seen = max_val;
@@ -414,6 +436,14 @@ int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t strid
 int quant_translate_dev(const pann_quant_params* p, const float* d_rows, uint64_t n, uint32_t d, uint64_t stride, void* d_out,
                         uint64_t out_stride, hipStream_t st) {
   const QParams q = make_qparams(p);
+  if (q.bits4) {
+    const uint64_t total = n * (uint64_t)((d + 1) / 2);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((total + 255) / 256, 1), MAX_BLOCKS * 4);
+    hipLaunchKernelGGL(translate4_kernel, dim3(grid), dim3(256), 0, st, reinterpret_cast<const uint8_t*>(d_rows), stride, n, d, q,
+                       static_cast<uint8_t*>(d_out), out_stride);
+    PANN_HIP(hipGetLastError());
+    return PANN_OK;
+  }
   View v[2];
   const int nv = make_views(d_rows, n, d, stride, static_cast<uint8_t*>(d_out), out_stride, v);
   for (int i = 0; i < nv; i++) {

@@ -1,8 +1,8 @@
 // search_rerank.hip -- beam_search_rerank (beamSearch.h:390-454) without leaving the device: float queries in, k exact
 // (id, distance) pairs out.  Three launches on one stream:
 //
-//   prepare_queries_kernel   one pass over the float query rows: the one-byte rows the quantised index is searched with
-//                            (translate_point, as quantize.hip), with normalize_first the Point::normalize'd float rows the
+//   prepare_queries_kernel   one pass over the float query rows: the one-byte (or packed four-bit) rows the quantised index is
+//                            searched with (translate_point, as quantize.hip), with normalize_first the Point::normalize'd float rows the
 //                            rerank scores against (graph_index.cpp:172), and for a filtered search the sketch rows (one
 //                            ballot per 64 coordinates, as sketch.hip)
 //   launch_beam_search       the search kernels of beam_search.hip, unchanged, on the one-byte index; the frontier ids and
@@ -68,7 +68,12 @@ __global__ __launch_bounds__(64) void prepare_queries_kernel(const uint8_t* __re
       if (in) {
         if (normalize) { x = staged[j] * inv; nrow[j] = x; }
         else x = row[j];
-        qrow[j] = (uint8_t)quantize_one(x, q);
+        if (!q.bits4) qrow[j] = (uint8_t)quantize_one(x, q);
+      }
+      if (q.bits4) {      // the even lane of a pair writes the byte: its own nibble low, its neighbour's high (0 past the row's end)
+        const uint32_t v = in ? quantize_one(x, q) : 0u;
+        const uint32_t hi = (uint32_t)__shfl_down((int)v, 1);
+        if (in && !(lane & 1)) qrow[j >> 1] = (uint8_t)(v | (hi << 4));
       }
       if (sk_kind >= 0) {                                          // sketch_translate_kernel's tests, on the same values
         bool s, m = false;
@@ -199,7 +204,7 @@ Scratch cut_scratch(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int no
   Scratch s{};
   uint8_t* p = static_cast<uint8_t*>(base);
   size_t off = 0;
-  s.qb_stride = (quant.d + 15) / 16 * 16;
+  s.qb_stride = (quant.dbytes + 15) / 16 * 16;
   s.qb = p + off; off += al256(nq * s.qb_stride);
   if (use_filter) { s.sk_stride = sketch_row_bytes(quant.sk_kind, quant.d); s.sk = p + off; off += al256(nq * s.sk_stride); }
   if (normalize_first) { s.nr_stride = ((uint64_t)quant.d * 4 + 15) / 16 * 16; s.nr = p + off; off += al256(nq * s.nr_stride); }

@@ -18,8 +18,11 @@ class GraphIndex:
     T = None
     metric = None
 
-    def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None):
-        """second_level: None | "bit" | "2bit" -- the three-range beam_search_rerank of graph_index.cpp:156-185: quantised
+    def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None, quant_bits=8):
+        """quant_bits: 8 | 4 -- bits per coordinate of the quantised copy that quant=True searches (float points only).  4: the
+        four-bit quantisers ("euclid_u4" / "mips_i4", packed rows of ceil(d / 2) bytes) for the copy and for the fused rerank
+        call; it has no second level, and its Euclidian translate is never a plain cast.  The default changes nothing.
+        second_level: None | "bit" | "2bit" -- the three-range beam_search_rerank of graph_index.cpp:156-185: quantised
         searches (quant=True) of the one-byte copy run with a bit-sketch pre-filter (filtered_beam_search, use_filtering) before
         the exact rerank.  "bit": Euclidean_Bit_Point / Mips_Bit_Point by the metric; "2bit": Mips_2Bit_Point (mips only).
         Off by default, so results do not change unless asked for.  It needs float points whose one-byte quantisation is not
@@ -32,6 +35,11 @@ class GraphIndex:
             raise ValueError('second_level must be None, "bit" or "2bit"')
         if second_level == "2bit" and self.metric == "Euclidian":
             raise ValueError('second_level="2bit" (Mips_2Bit_Point) is a mips sketch')
+        if quant_bits not in (8, 4):
+            raise ValueError("quant_bits must be 8 or 4")
+        if quant_bits == 4 and second_level is not None:
+            raise ValueError("quant_bits=4 has no second level: sketches are not attached to four-bit indices")
+        self.quant_bits = quant_bits
         if second_level is not None and np.dtype(self.T).itemsize == 1:
             raise ValueError("second_level needs float points: one-byte indices are searched directly (no quantised copy to filter)")
         self.second_level = second_level
@@ -47,14 +55,14 @@ class GraphIndex:
         self.index = DeviceIndex(self.points, self.graph, metric=self.metric, device=device)
         if self.use_quantization:
             if self.metric == "Euclidian":
-                self.q_index, self.qparams = self.index.quantized("euclid_u8")       # EQuantRange(Points) :90
+                self.q_index, self.qparams = self.index.quantized("euclid_u8" if quant_bits == 8 else "euclid_u4")   # EQuantRange(Points) :90
                 self.eparams = quantize.EuclidParams.__new__(quantize.EuclidParams)
-                self.eparams.range, self.eparams.dims = 255, self.qparams.dims
+                self.eparams.range, self.eparams.dims = (255 if quant_bits == 8 else 15), self.qparams.dims
                 self.eparams.slope, self.eparams.offset = np.float32(self.qparams.slope), np.int32(self.qparams.offset)
             else:
                 self.index.normalize()                                               # :94-95
                 self.points = self.index.points()
-                self.q_index, self.qparams = self.index.quantized("mips_i8", trim=True)   # Quantized_Mips_Point<8,true> :69
+                self.q_index, self.qparams = self.index.quantized("mips_i8" if quant_bits == 8 else "mips_i4", trim=True)   # Quantized_Mips_Point<8,true> :69
                 self.mmax = np.float32(self.qparams.max_val)
             if second_level is not None and self.metric == "Euclidian" and self.eparams.identity:
                 raise ValueError("second_level: these points quantise to themselves (slope 1), so quantised searches are plain "
@@ -76,7 +84,7 @@ class GraphIndex:
             r = self.index.batch_search(queries, out_k=knn, **qp)                # :188
             self._need(r["frontier_size"], knn)
             return r["ids"], r["dists"]
-        if self.metric == "Euclidian" and self.eparams.identity:                 # slope == 1: plain search on the u8 copy (:148-152)
+        if self.metric == "Euclidian" and self.quant_bits == 8 and self.eparams.identity:   # slope == 1: plain search on the u8 copy (:148-152)
             qq = quantize.device_quantize_rows(queries, self.qparams, device=self.device)
             r = self.q_index.batch_search(qq, out_k=knn, **qp)
             self._need(r["frontier_size"], knn)

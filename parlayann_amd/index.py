@@ -8,15 +8,24 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I8, PANN_L2, PANN_MIPS, PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_U8,
-                    BuildStats, QuantParams, QueryParams, RerankOut, SearchOut, check)
+from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I4, PANN_I8, PANN_L2, PANN_MIPS, PANN_QUANT_EUCLID_U4, PANN_QUANT_EUCLID_U8,
+                    PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats, QuantParams, QueryParams, RerankOut, SearchOut,
+                    check)
 from .bf16 import bfloat16
 
 _DT = {np.dtype(np.uint8): PANN_U8, np.dtype(np.int8): PANN_I8, np.dtype(np.float32): PANN_F32,
        np.dtype(np.float16): PANN_F16, bfloat16: PANN_BF16}
 
 
+# four-bit element types have no numpy dtype: they go by name, their rows are packed uint8 (quantize.pack_nibbles)
+_DT4 = {"u4": PANN_U4, "uint4": PANN_U4, "i4": PANN_I4, "int4": PANN_I4}
+_QUANT_DT = {PANN_QUANT_EUCLID_U8: (np.dtype(np.uint8), PANN_L2, None), PANN_QUANT_MIPS_I8: (np.dtype(np.int8), PANN_MIPS, None),
+             PANN_QUANT_EUCLID_U4: (np.dtype(np.uint8), PANN_L2, PANN_U4), PANN_QUANT_MIPS_I4: (np.dtype(np.uint8), PANN_MIPS, PANN_I4)}
+
+
 def dtype_code(dt):
+    if isinstance(dt, str) and dt.lower() in _DT4:
+        return _DT4[dt.lower()]
     return _DT[np.dtype(dt)]
 
 
@@ -32,13 +41,17 @@ def _metric_code(metric):
 
 
 def quant_kind(kind):
-    if kind in (PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8):
+    if kind in (PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4):
         return kind
     k = str(kind).lower()
     if k in ("euclid_u8", "euclidian_u8", "u8"):
         return PANN_QUANT_EUCLID_U8
     if k in ("mips_i8", "i8"):
         return PANN_QUANT_MIPS_I8
+    if k in ("euclid_u4", "euclidian_u4", "u4"):
+        return PANN_QUANT_EUCLID_U4
+    if k in ("mips_i4", "i4"):
+        return PANN_QUANT_MIPS_I4
     raise ValueError(f"unknown quantisation kind {kind!r}")
 
 
@@ -78,6 +91,44 @@ class DeviceIndex:
         self._h, self._lib = h, lib
         if exact_float_order:      # validation mode: bit-identical float results on real-valued data
             check(lib.pann_index_set_exact_float_order(h, 1))
+
+    @classmethod
+    def from_packed(cls, rows, dims, dtype, graph=None, max_degree=None, metric=None, device=0):
+        """A four-bit index from rows that are already packed (quantize.pack_nibbles): rows is n x ceil(dims / 2) uint8, dtype
+        "u4" (unsigned nibbles, Euclidian) or "i4" (two's-complement nibbles, mips).  metric defaults to the one the type goes
+        with; the other one is refused by the library."""
+        lib = _capi.load()
+        code = _DT4.get(str(dtype).lower())
+        if code is None:
+            raise ValueError('dtype must be "u4" or "i4"')
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        dims = int(dims)
+        if rows.ndim != 2 or rows.shape[1] != (dims + 1) // 2:
+            raise ValueError(f"rows must be n x {(dims + 1) // 2} uint8 (two coordinates per byte)")
+        if graph is not None:
+            graph = np.ascontiguousarray(graph, dtype=np.uint32)
+            if graph.ndim != 2 or graph.shape[0] != len(rows):
+                raise ValueError("graph must be n x (max_deg+1) uint32 (reference layout)")
+            max_degree = graph.shape[1] - 1
+        if max_degree is None:
+            raise ValueError("give a graph or max_degree")
+        if metric is None:
+            metric = PANN_L2 if code == PANN_U4 else PANN_MIPS
+        self = cls.__new__(cls)
+        self.n, self.d, self.max_degree = len(rows), dims, int(max_degree)
+        self.dtype, self.metric, self.dtype4 = np.dtype(np.uint8), _metric_code(metric), code
+        h = C.c_void_p()
+        check(lib.pann_index_create(C.byref(h), _ptr(rows), self.n, dims, code, _row_stride(rows), self.metric, _ptr(graph),
+                                    self.max_degree, device))
+        self._h, self._lib = h, lib
+        return self
+
+    dtype4 = None          # PANN_U4 / PANN_I4 for a four-bit index: rows are packed uint8, row_bytes of them per row
+
+    @property
+    def row_bytes(self):
+        """bytes of one host-layout row"""
+        return (self.d + 1) // 2 if self.dtype4 is not None else self.d * np.dtype(self.dtype).itemsize
 
     @classmethod
     def from_files(cls, points_path, dtype, graph_path=None, max_degree=None, metric="Euclidian", device=0, rows=None,
@@ -159,8 +210,9 @@ class DeviceIndex:
         """external query rows: C-contiguous nq x d of the INDEX dtype (a float32 array handed to an f16 index would be
         reinterpreted byte-wise by the C-ABI, which only sees a pointer and a stride)"""
         q = np.ascontiguousarray(queries)
-        if q.dtype != self.dtype or q.ndim != 2 or q.shape[1] != self.d:
-            raise ValueError(f"queries must be nq x {self.d} of dtype {self.dtype}, got {q.shape} {q.dtype}")
+        cols = self.row_bytes if self.dtype4 is not None else self.d        # four-bit: packed rows (quantize.pack_nibbles)
+        if q.dtype != self.dtype or q.ndim != 2 or q.shape[1] != cols:
+            raise ValueError(f"queries must be nq x {cols} of dtype {self.dtype}, got {q.shape} {q.dtype}")
         return q
 
     def reserve_dropped(self, cap):
@@ -206,9 +258,10 @@ class DeviceIndex:
 
     # ---- points: download, normalize, scalar quantisation on the device (csrc/quantize.hip) ----
     def points(self, first_row=0, nrows=None):
-        """pann_index_download_points: rows [first_row, first_row + nrows) of the device slab as an nrows x d array"""
+        """pann_index_download_points: rows [first_row, first_row + nrows) of the device slab as an nrows x d array (a four-bit
+        index: nrows x ceil(d / 2) packed uint8 rows)"""
         nrows = self.n - first_row if nrows is None else nrows
-        out = np.empty((nrows, self.d), dtype=self.dtype)
+        out = np.empty((nrows, self.row_bytes if self.dtype4 is not None else self.d), dtype=self.dtype)
         check(self._lib.pann_index_download_points(self._h, first_row, nrows, _ptr(out), _row_stride(out)))
         return out
 
@@ -224,14 +277,14 @@ class DeviceIndex:
 
     def quantized(self, kind, trim=True, params=None, copy_graph=True):
         """QPR Q_Points(Points): -> (DeviceIndex of uint8 / int8 rows translated on the device, QuantParams).  kind:
-        "euclid_u8" | "mips_i8"; params: translate with these instead of generating them from this index's rows."""
+        "euclid_u8" | "mips_i8" | "euclid_u4" | "mips_i4" (packed four-bit rows); params: translate with these instead of
+        generating them from this index's rows."""
         p = self.quantize_params(kind, trim) if params is None else params
         h = C.c_void_p()
         check(self._lib.pann_index_create_quantized(C.byref(h), self._h, C.byref(p), 1 if copy_graph else 0))
         q = DeviceIndex.__new__(DeviceIndex)
         q.n, q.d, q.max_degree = self.n, self.d, self.max_degree
-        eu = p.kind == PANN_QUANT_EUCLID_U8
-        q.dtype, q.metric = np.dtype(np.uint8 if eu else np.int8), (PANN_L2 if eu else PANN_MIPS)
+        q.dtype, q.metric, q.dtype4 = _QUANT_DT[p.kind]
         q._h, q._lib = h, self._lib
         return q, p
 

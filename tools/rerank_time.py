@@ -15,6 +15,7 @@ Every step has a time limit, but it is a Python alarm: it ends a step that is sl
 call.  Run the tool under `timeout -k 10 <seconds>` so that a hang ends the process too.
 
     python tools/rerank_time.py [--n 1000000] [--d 128] [--nq 10000] [--steps 20] [--json out.json]
+    python tools/rerank_time.py --bits 4 [--beam 128] # the quantised copy holds four-bit rows (DESIGN.md "Four-bit rows")
     python tools/rerank_time.py --profile-steps 5     # only fused steps, for a kernel trace taken in a run of its own
 """
 import argparse
@@ -63,9 +64,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--bits", type=int, choices=(8, 4), default=8, help="bits per coordinate of the quantised copy")
+    ap.add_argument("--beam", type=int, default=BEAM)
     a = ap.parse_args()
     import torch
-    n, d, nq = a.n, a.d, a.nq
+    n, d, nq, beam = a.n, a.d, a.nq, a.beam
+    qrow = d if a.bits == 8 else (d + 1) // 2          # bytes of one row of the quantised copy
     with step("data", 300):                       # real-valued, so that the quantiser is not the identity
         X = (datasets.deep_like(n, d, seed=1) * 2.0).astype(np.float32)
         Q = (datasets.deep_like(nq, d, seed=2) * 2.0).astype(np.float32)
@@ -73,10 +77,10 @@ def main():
         full = DeviceIndex(X, max_degree=64, metric="Euclidian")
         full.vamana_build(64, 128, 1.2, num_passes=1, seed=3)
     with step("quantise", 120):
-        quant, qparams = full.quantized("euclid_u8")
+        quant, qparams = full.quantized("euclid_u8" if a.bits == 8 else "euclid_u4")
         assert not qparams.identity
     lib = _capi.load()
-    qp = _capi.QueryParams(k=K, beam=BEAM, cut=1.35, limit=n, degree_limit=64, rerank_factor=RF, pad=1.0)
+    qp = _capi.QueryParams(k=K, beam=beam, cut=1.35, limit=n, degree_limit=64, rerank_factor=RF, pad=1.0)
     t_q = torch.from_numpy(Q).cuda()
     t_st = torch.zeros(1, dtype=torch.int32, device="cuda")
     t_ids = torch.zeros((nq, K), dtype=torch.int32, device="cuda")
@@ -95,13 +99,13 @@ def main():
 
     def fused_step():
         full.search_rerank_dev(quant, qparams, t_q.data_ptr(), nq, 4 * d, t_st.data_ptr(), 1, t_ids.data_ptr(), t_d.data_ptr(),
-                               k=K, beam=BEAM, limit=n, degree_limit=64, rerank_factor=RF, d_frontier_size_ptr=t_fs.data_ptr(),
+                               k=K, beam=beam, limit=n, degree_limit=64, rerank_factor=RF, d_frontier_size_ptr=t_fs.data_ptr(),
                                d_visited_count_ptr=t_vc.data_ptr(), d_dist_cmps_ptr=t_dc.data_ptr(),
                                d_status_ptr=t_status.data_ptr(), stream_ptr=stream.cuda_stream)
 
     def composed_step():
         qq = quantize.device_quantize_rows(Q, qparams)
-        r = quant.batch_search(qq, k=K, beam=BEAM, out_k=BEAM, limit=n, degree_limit=64)
+        r = quant.batch_search(qq, k=K, beam=beam, out_k=beam, limit=n, degree_limit=64)
         counts = np.minimum(r["frontier_size"], K * RF).astype(np.uint32)
         return r, counts, full.rerank(Q, r["ids"], counts, K, resort=True)
 
@@ -144,20 +148,20 @@ def main():
         for _ in range(max(3, a.steps // 4)):
             t = time.perf_counter(); r, counts, (ids_b, _) = composed_step(); ts.append((time.perf_counter() - t) * 1e3)
         ts.sort()
-        report("composed", ts[len(ts) // 2], ts[0], ts[-1], ids_b, r["dist_cmps"], d, counts.mean())
+        report("composed", ts[len(ts) // 2], ts[0], ts[-1], ids_b, r["dist_cmps"], qrow, counts.mean())
     with step("(c) fused", 300):
         ms = timed_dev(fused_step, a.steps)
         ids_c = t_ids.cpu().numpy().view(np.uint32)
         nc = np.minimum(t_fs.cpu().numpy().view(np.uint32), K * RF)
-        report("fused", *ms, ids_c, t_dc.cpu().numpy().view(np.uint32), d, nc.mean())
+        report("fused", *ms, ids_c, t_dc.cpu().numpy().view(np.uint32), qrow, nc.mean())
     if not np.array_equal(ids_b, ids_c):
         print("ERROR: the fused ids differ from the composed ids", flush=True)
         sys.exit(1)
-    print(f"  fused ids == composed ids; table {n * d * 4 / 2**20:.0f} MiB float / {n * d / 2**20:.0f} MiB one-byte "
-          f"(Infinity Cache: 256 MiB)", flush=True)
+    print(f"  fused ids == composed ids; table {n * d * 4 / 2**20:.0f} MiB float / {n * qrow / 2**20:.0f} MiB "
+          f"{'one-byte' if a.bits == 8 else 'four-bit'} (Infinity Cache: 256 MiB)", flush=True)
     if a.json:
         with open(a.json, "w") as f:
-            json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, rerank_factor=RF, steps=a.steps, rows=rows), f, indent=1)
+            json.dump(dict(n=n, d=d, nq=nq, k=K, beam=beam, bits=a.bits, rerank_factor=RF, steps=a.steps, rows=rows), f, indent=1)
     quant.close(); full.close()
 
 
