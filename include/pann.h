@@ -278,6 +278,33 @@ int pann_vamana_sort_neighbors(pann_index* idx);
 void pann_build_permutation(uint64_t n, uint64_t seed, uint32_t* out);
 uint64_t pann_vamana_batch_schedule(uint64_t n, uint64_t m, uint64_t* bounds, uint64_t cap);
 
+/* ---- deleting points: batched consolidation (DESIGN.md "Deleting points") -------------------- */
+
+typedef struct pann_delete_stats {
+  double t_expand_s, t_prune_s;           /* mark + count + fill ; keys + sort + greedy + row writes */
+  uint64_t deleted, affected, candidates; /* |D| after de-duplication, |A|, total length of the candidate lists */
+  uint64_t prune_dist_cmps;
+  uint32_t* per_point_dist_cmps;          /* optional host array of n entries, ACCUMULATED like pann_build_stats */
+} pann_delete_stats;
+
+/* One batch of deletions.  The reference has none (knn_index::delete_set is never used); the rule is the delete consolidation
+ * of FreshDiskANN (Singh et al. 2021, Algorithm 4) with the snapshot semantics of batch_insert.  With G the graph when the call
+ * starts and D the ids given (duplicates mean nothing): every p not in D with an out-neighbour in D gets
+ *   robustPrune(p, [N(p) \ D in row order] ++ [for v in N(p) & D in row order: N(v) \ D \ {p} in row order], alpha, R)
+ * in the id-only form (distances computed and counted, add_out_nbrs = 0, (dist,id) ties: the rule and the distance_comps of
+ * pann_robust_prune_batch(..., cand_dists = NULL, add_out_nbrs = 0)); all rows are read from G.  Then those rows are
+ * replaced and the rows of D emptied; every other row and all points stay as they were (a freed slot keeps its vector until
+ * pann_index_upload_points replaces it; pann_vamana_insert_batch then inserts it again).  Afterwards no row holds an id of D,
+ * so a search cannot return one -- PROVIDED IT STARTS FROM A LIVE VERTEX: neither call takes or repairs a start vertex, the
+ * caller must search (and insert) from a vertex it has not deleted.
+ * An id >= n, R == 0 or R > max_deg: PANN_ERR_BAD_ARG, nothing written.  m == 0: PANN_OK, nothing changed.  All fields of
+ * stats are added to.  The _dev form takes ids in device memory, checks them on the device, and runs on the handle's stream;
+ * both return after the stream has drained. */
+int pann_vamana_delete_batch(pann_index* idx, const uint32_t* del_ids, uint64_t m, uint32_t R, double alpha,
+                             pann_delete_stats* stats);
+int pann_vamana_delete_batch_dev(pann_index* idx, const uint32_t* d_del_ids, uint64_t m, uint32_t R, double alpha,
+                                 pann_delete_stats* stats);
+
 /* ---- dense all-pairs: HCNNG leaf (hcnng_index.h:145-181) and ground truth ------------------- */
 
 /* For one leaf given by N ids: for each i the m smallest (dist,id) neighbours among the other

@@ -59,6 +59,12 @@ class BuildStats(C.Structure):
                 ("per_point_visited", C.c_void_p), ("per_point_dist_cmps", C.c_void_p)]
 
 
+class DeleteStats(C.Structure):
+    """pann_delete_stats: every field is added to by pann_vamana_delete_batch*"""
+    _fields_ = [("t_expand_s", C.c_double), ("t_prune_s", C.c_double), ("deleted", C.c_uint64), ("affected", C.c_uint64),
+                ("candidates", C.c_uint64), ("prune_dist_cmps", C.c_uint64), ("per_point_dist_cmps", C.c_void_p)]
+
+
 PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4 = 0, 1, 2, 3
 
 
@@ -132,6 +138,9 @@ SIGNATURES = {
     "pann_vamana_apply_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_double,
                                              C.POINTER(BuildStats)]),
     "pann_vamana_sort_neighbors": (C.c_int, [C.c_void_p]),
+    "pann_vamana_delete_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_double, C.POINTER(DeleteStats)]),
+    "pann_vamana_delete_batch_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_double,
+                                               C.POINTER(DeleteStats)]),
     "pann_build_permutation": (None, [C.c_uint64, C.c_uint64, C.c_void_p]),
     "pann_vamana_batch_schedule": (C.c_uint64, [C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64]),
     "pann_leaf_knn": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),

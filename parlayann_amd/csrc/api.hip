@@ -73,6 +73,7 @@ struct pann_index {
   Workspace ws_rr;               // pann_batch_search_rerank*: prepared queries and frontiers (search_rerank.hip)
   uint32_t vcap = 0;        // visited-list capacity used by the builder (grows on overflow)
   uint32_t dcap = 256;      // dropped-list capacity of the searches (pann_index_reserve_dropped; grows on overflow)
+  uint32_t delete_range_keys = 0;   // pann_index_set_option("delete_range_keys"): most keys one prune of a delete consolidation takes (0 = what the key index allows)
   uint32_t gt_pieces = 0;   // pann_index_set_option("gt_pieces"): pieces of the base per query tile in pann_bruteforce_knn (0 = auto)
   DevBuf cell_buf;          // locality cell of every point (ensure_locality_cells)
   uint32_t locality_groups = 32;    // ... whose pivots are grouped by their nearest of this many top pivots (0 / 1: no grouping)
@@ -433,6 +434,7 @@ int64_t pann_index_get_option(const pann_index* idx, const char* name) {
   const std::string nm = name;
   if (nm == "forest_group") return idx->ix.forest_group;
   if (nm == "gt_pieces") return idx->gt_pieces;
+  if (nm == "delete_range_keys") return idx->delete_range_keys;
   if (nm == "locality_order") return idx->ix.cell ? 1 : 0;
   if (nm == "filter_codes") return idx->ix.codes_valid ? 1 : 0;         // are the class codes in step with the graph right now?
   return -1;
@@ -452,6 +454,7 @@ int pann_index_set_option(pann_index* idx, const char* name, int64_t value) {
   if (value < 0 || value > 0x7FFFFFFF) { set_error("pann_index_set_option: value out of range"); return PANN_ERR_BAD_ARG; }
   if (nm == "forest_group") idx->ix.forest_group = (uint32_t)value;
   else if (nm == "gt_pieces") idx->gt_pieces = (uint32_t)value;
+  else if (nm == "delete_range_keys") idx->delete_range_keys = (uint32_t)value;
   else if (nm == "locality_pivots") { idx->locality_pivots = std::max<uint32_t>(2, std::min<uint32_t>((uint32_t)value, 65536)); idx->ix.cell = nullptr; idx->cells_state = idx->cells_state < 0 ? idx->cells_state : 0; }
   else if (nm == "locality_groups") { idx->locality_groups = (uint32_t)std::min<int64_t>(value, 4096); idx->ix.cell = nullptr; idx->cells_state = idx->cells_state < 0 ? idx->cells_state : 0; }
   else if (nm == "locality_order") {        // 0: the builder launches a batch's searches in batch order
@@ -767,6 +770,40 @@ int pann_vamana_apply_rows_dev(pann_index* idx, const uint32_t* d_batch_ids, uin
   if (m > 0xFFFFFFF0ull) { set_error("pann_vamana_apply_rows_dev: batch too large"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
   return vamana_apply_rows_dev(idx->ix, idx->ws2, idx->ws3, idx->stream, d_batch_ids, (uint32_t)m, d_rows, R, alpha, stats);
+}
+
+// ---- deleting points (vamana_delete.hip) ----
+
+static int delete_batch_checks(const pann_index* idx, const char* fn, const uint32_t* ids, uint64_t m, uint32_t R) {
+  if (!idx && pann_device_count() <= 0) { set_error(std::string(fn) + ": no HIP device visible (this library has no CPU path)"); return PANN_ERR_NO_DEVICE; }
+  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (R == 0 || R > idx->ix.max_deg || R > 1024) { set_error(std::string(fn) + ": R must be in [1, min(max_deg,1024)]"); return PANN_ERR_BAD_ARG; }
+  if (m > 0xFFFFFFF0ull) { set_error(std::string(fn) + ": batch too large"); return PANN_ERR_BAD_ARG; }
+  if (m && !ids) { set_error(std::string(fn) + ": null ids"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+int pann_vamana_delete_batch(pann_index* idx, const uint32_t* del_ids, uint64_t m, uint32_t R, double alpha,
+                             pann_delete_stats* stats) {
+  if (int rc = delete_batch_checks(idx, "pann_vamana_delete_batch", del_ids, m, R)) return rc;
+  if (m == 0) return PANN_OK;
+  for (uint64_t i = 0; i < m; i++)
+    if (del_ids[i] >= idx->ix.n) {
+      set_error("pann_vamana_delete_batch: id " + std::to_string(del_ids[i]) + " out of range; nothing was changed"); return PANN_ERR_BAD_ARG;
+    }
+  DeviceGuard g(idx->device);
+  if (int rc = idx->stage[2].ensure(m * 4)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, del_ids, m * 4, hipMemcpyHostToDevice, idx->stream));
+  return vamana_delete_batch_dev(idx->ix, idx->ws3, idx->ws2, idx->ws4, idx->stream, idx->stage[2].as<uint32_t>(), m, R, alpha,
+                                 idx->delete_range_keys, stats);
+}
+
+int pann_vamana_delete_batch_dev(pann_index* idx, const uint32_t* d_del_ids, uint64_t m, uint32_t R, double alpha,
+                                 pann_delete_stats* stats) {
+  if (int rc = delete_batch_checks(idx, "pann_vamana_delete_batch_dev", d_del_ids, m, R)) return rc;
+  if (m == 0) return PANN_OK;
+  DeviceGuard g(idx->device);
+  return vamana_delete_batch_dev(idx->ix, idx->ws3, idx->ws2, idx->ws4, idx->stream, d_del_ids, m, R, alpha, idx->delete_range_keys, stats);
 }
 
 int pann_vamana_sort_neighbors(pann_index* idx) {

@@ -129,6 +129,19 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
 int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, hipStream_t st, const uint32_t* d_batch, uint32_t m,
                           const uint32_t* d_rows, uint32_t R, double alpha, pann_build_stats* stats);
 int sort_neighbors_dev(const DeviceIndex& ix, hipStream_t st);
+// robustPrune, id-only form without the owner's out-neighbours, over a device CSR slab of candidate ids (vamana_build.hip);
+// d_rows: m x R uint32, SENTINEL padded; d_dc is accumulated.  Nothing reaches the graph.
+int prune_csr_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint32_t* d_owners, uint32_t m,
+                  const uint32_t* d_cand_ids, const uint64_t* d_cand_base, const uint32_t* d_cand_cnt,
+                  const uint32_t* d_seg_begin, uint32_t total_keys, uint32_t max_seg_len, double alpha, uint32_t R,
+                  uint32_t* d_rows, uint32_t* d_rcnt, uint32_t* d_dc);
+
+// vamana_delete.hip: one batch of deletions consolidated on the device (DESIGN.md "Deleting points").  d_del: m ids on the
+// device (checked there); ws / rows_ws: the call's own arrays and the new rows, prune_ws: the prune's key scratch.
+// range_keys: most keys pruned at once (0 = what the 32-bit key index allows); synchronises st.
+int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& prune_ws, Workspace& rows_ws, hipStream_t st,
+                            const uint32_t* d_del, uint64_t m, uint32_t R, double alpha, uint64_t range_keys,
+                            pann_delete_stats* stats);
 
 // dense.hip
 int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_a_ext, uint64_t a_stride,

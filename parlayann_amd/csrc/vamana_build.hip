@@ -860,6 +860,37 @@ int insert_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, Works
   return vamana_apply_rows_dev(ix, ws, ws2, st, d_batch, m, d_rows, R, alpha, stats);
 }
 
+// robustPrune in the id-only form (cand_dists = null, add_out_nbrs = 0) of m owners whose candidate ids already sit in a device
+// CSR slab -- the seam of the delete consolidation (vamana_delete.hip).  Owner i prunes cand_ids[cand_base[i] .. + cand_cnt[i]);
+// seg_begin[i] is its first key slot, total_keys the slots of all m.  Reads the graph not at all and writes only d_rows
+// (m x R, SENTINEL padded), d_rcnt and d_dc (accumulated): the caller decides when rows reach the graph.
+int prune_csr_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint32_t* d_owners, uint32_t m,
+                  const uint32_t* d_cand_ids, const uint64_t* d_cand_base, const uint32_t* d_cand_cnt,
+                  const uint32_t* d_seg_begin, uint32_t total_keys, uint32_t max_seg_len, double alpha, uint32_t R,
+                  uint32_t* d_rows, uint32_t* d_rcnt, uint32_t* d_dc) {
+  if (m == 0) return PANN_OK;
+  const size_t stmp = seg_sort_temp_bytes(total_keys, m);
+  uint32_t* d_send; uint64_t *ka, *kb; void* d_tmp;
+  auto layout = [&](Bump& b) {
+    d_send = b.take<uint32_t>(m);
+    ka = b.take<uint64_t>((size_t)total_keys + 1); kb = b.take<uint64_t>((size_t)total_keys + 1);
+    d_tmp = b.take<uint8_t>(stmp + 16);
+  };
+  Bump dry(nullptr, 0); layout(dry);
+  if (int rc = ws.ensure(dry.off + 4096)) return rc;
+  Bump b(ws.buf, ws.bytes); layout(b);
+  PruneArgs pa{};
+  pa.pv = PointsView{ix.points, ix.pstride, ix.nch, ix.exact}; pa.dbytes = ix.dbytes;
+  pa.graph = ix.graph; pa.gstride = ix.gstride; pa.max_deg = ix.max_deg;
+  pa.owners = d_owners; pa.cand_ids = d_cand_ids; pa.cand_dists = nullptr; pa.cand_base = d_cand_base; pa.cand_cnt = d_cand_cnt;
+  pa.seg_begin = d_seg_begin; pa.seg_end = d_send; pa.dcmps = d_dc; pa.add_out_nbrs = 0; pa.m = m;
+  GreedyArgs ga{};
+  ga.pv = pa.pv; ga.dbytes = ix.dbytes; ga.owners = d_owners; ga.alpha = alpha; ga.R = R;
+  ga.rows_out = d_rows; ga.rows_stride = R; ga.cnt_out = d_rcnt; ga.graph = nullptr; ga.gstride = ix.gstride;
+  ga.dcmps = d_dc; ga.m = m;
+  return run_prune(ix, pa, ga, ka, kb, total_keys, d_tmp, stmp, st, max_seg_len);
+}
+
 int sort_neighbors_dev(const DeviceIndex& ix, hipStream_t st) {
   if (ix.max_deg > 4096) { set_error("sort_neighbors: max_deg > 4096"); return PANN_ERR_UNSUPPORTED; }
   const PointsView pv{ix.points, ix.pstride, ix.nch, ix.exact};

@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _capi
 from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I4, PANN_I8, PANN_L2, PANN_MIPS, PANN_QUANT_EUCLID_U4, PANN_QUANT_EUCLID_U8,
-                    PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats, QuantParams, QueryParams, RerankOut, SearchOut,
+                    PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats, DeleteStats, QuantParams, QueryParams, RerankOut, SearchOut,
                     check)
 from .bf16 import bfloat16
 
@@ -239,6 +239,14 @@ class DeviceIndex:
         """empty graph again (Graph(maxDeg, n), graph.h:145-147), on the device"""
         check(self._lib.pann_index_clear_graph(self._h))
 
+    def upload_points(self, first_row, rows):
+        """pann_index_upload_points: replace the vectors of rows first_row .. first_row + len(rows) (the graph is not touched):
+        new vectors for slots freed by vamana_delete_batch, to be inserted with vamana_insert_batch"""
+        rows = np.ascontiguousarray(rows)
+        if rows.ndim != 2 or rows.dtype != self.dtype or rows.shape[1] * rows.itemsize != self.row_bytes:
+            raise ValueError("rows must be a 2-D array of the index's dtype and width")
+        check(self._lib.pann_index_upload_points(self._h, int(first_row), _ptr(rows), len(rows), _row_stride(rows)))
+
     def set_stream(self, stream_ptr, private=False):
         """pann_index_set_stream: run the handle's calls on the caller's stream (a hipStream_t as an integer; 0 = the device's
         default stream, torch's usual current stream); private=True: back to the handle's own stream"""
@@ -455,6 +463,35 @@ class DeviceIndex:
         check(self._lib.pann_vamana_apply_rows_dev(self._h, C.c_void_p(d_batch_ptr), m, C.c_void_p(d_rows_ptr), R, float(alpha),
                                                    C.byref(st)))
         return st
+
+    # ---- deleting points: batched consolidation (DESIGN.md "Deleting points") ----
+    def _delete_stats(self, point_stats):
+        st = DeleteStats()
+        if point_stats is not None:
+            if not (point_stats.dtype == np.uint32 and point_stats.flags.c_contiguous and point_stats.shape == (self.n,)):
+                raise ValueError("point_stats must be a C-contiguous uint32 array of n entries")
+            st.per_point_dist_cmps = point_stats.ctypes.data_as(C.c_void_p)
+        return st
+
+    @staticmethod
+    def _delete_dict(st):
+        return {f: getattr(st, f) for f in ("t_expand_s", "t_prune_s", "deleted", "affected", "candidates", "prune_dist_cmps")}
+
+    def vamana_delete_batch(self, ids, R, alpha, point_stats=None):
+        """pann_vamana_delete_batch: delete the ids given (any order, repeats allowed) in one call -- every vertex with a deleted
+        out-neighbour is re-pruned over its surviving neighbours and those of its deleted neighbours, then the deleted rows are
+        emptied.  Search from a vertex that is still live afterwards.  point_stats: uint32[n], the prune comparisons of every
+        re-pruned vertex are added to it.  Returns the call's pann_delete_stats as a dict."""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        st = self._delete_stats(point_stats)
+        check(self._lib.pann_vamana_delete_batch(self._h, _ptr(ids), len(ids), R, float(alpha), C.byref(st)))
+        return self._delete_dict(st)
+
+    def vamana_delete_batch_dev(self, d_ids_ptr, m, R, alpha, point_stats=None):
+        """the same for m ids at device address d_ids_ptr, on the handle's stream"""
+        st = self._delete_stats(point_stats)
+        check(self._lib.pann_vamana_delete_batch_dev(self._h, C.c_void_p(d_ids_ptr or None), m, R, float(alpha), C.byref(st)))
+        return self._delete_dict(st)
 
     def vamana_sort_neighbors(self):
         check(self._lib.pann_vamana_sort_neighbors(self._h))
