@@ -264,7 +264,13 @@ int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, doub
  * and equal to the single-GPU build.  Both calls run on the handle's stream and return after it has drained.
  *   A: beam search from `start` + robustPrune of the visited list (vamana/index.h:247-266) for the m ids given; reads the
  *      graph only.  d_rows_out: m x R uint32, unused slots 0xFFFFFFFF.
- *   B: write the rows (:268-270), reverse edges grouped by target, append-or-re-prune (:278-300). */
+ *   B: write the rows (:268-270), reverse edges grouped by target, append-or-re-prune (:278-300).
+ * Ids held in device memory are NOT validated (unlike pann_vamana_insert_batch, which checks its host ids, and unlike
+ * pann_vamana_delete_batch_dev, which checks its ids on the device): every d_batch_ids[i], and every word of d_rows other than
+ * 0xFFFFFFFF, must be < n -- the caller guarantees it; anything else indexes the points and the graph out of bounds.  The
+ * scalar arguments are checked (PANN_ERR_BAD_ARG, nothing written): null pointers with m > 0, L outside [1, 65536], start >= n,
+ * R outside [1, min(max_deg, 1024)].  m == 0 returns PANN_OK and touches nothing.  stats, when given, is accumulated into
+ * (per-point arrays included): the calls of a split batch add up to what pann_vamana_insert_batch reports for the batch. */
 int pann_vamana_search_prune_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, uint32_t start, uint32_t R, uint32_t L,
                                  double alpha, uint32_t* d_rows_out, pann_build_stats* stats);
 int pann_vamana_apply_rows_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, const uint32_t* d_rows, uint32_t R,
@@ -386,7 +392,12 @@ int pann_merge_topk_dev(const uint32_t* d_ids, const float* d_dists, uint32_t nl
  *     (at most mst_deg, hcnng_index.h:213) into slots [j*mst_deg, (j+1)*mst_deg) of row v of d_slab (device, n rows of
  *     slab_stride uint32, 0xFFFFFFFF = empty; filled here).  The handle's own graph is not touched.
  *   assemble: d_slabs = nslabs slabs one after the other (the all-gather's output); slab w holds trees w, w + nslabs, ...;
- *     row v of the handle's graph gets, after its current neighbours, the edges of trees 0 .. ntrees-1 in tree order. */
+ *     row v of the handle's graph gets, after its current neighbours, the edges of trees 0 .. ntrees-1 in tree order; a row
+ *     takes edges while it has room and stops at max_deg (process_edges, hcnng_index.h:121-124).
+ * The words of d_slabs are not validated either: every one other than 0xFFFFFFFF must be an id < n (what build_trees wrote).
+ * Checked, PANN_ERR_BAD_ARG and nothing written: a null slab, mst_deg == 0, tree_step == 0; for assemble also nslabs == 0, slab
+ * rows shorter than ceil(ntrees / nslabs) * mst_deg, and ntrees * mst_deg > max_deg.  build_trees refuses slab rows shorter
+ * than ntrees * mst_deg and a cluster_size outside [2, 65535] too, but only after it has filled the slab with 0xFFFFFFFF. */
 int pann_hcnng_build_trees_dev(pann_index* idx, uint32_t first_tree, uint32_t tree_step, uint32_t ntrees, uint32_t cluster_size,
                                uint32_t mst_deg, uint64_t seed, uint32_t* d_slab, uint32_t slab_stride, double* times3);
 int pann_hcnng_assemble_dev(pann_index* idx, const uint32_t* d_slabs, uint32_t nslabs, uint32_t slab_stride, uint32_t ntrees,

@@ -366,6 +366,11 @@ def test_refusals(oracle):
             un("pann_vamana_build_single_batch", lambda: lib.pann_vamana_build_single_batch(h, 8, 16, 1.2, 1, 4, 1, 1, None))
             un("pann_hcnng_build", lambda: lib.pann_hcnng_build(h, 2, 16, 3, 1, None))
             un("pann_vamana_insert_batch", lambda: lib.pann_vamana_insert_batch(h, _vp(ids), 16, 0, 8, 16, 1.2, None))
+            # the two-phase build seams take device pointers; a four-bit handle is refused before any pointer is used
+            un("pann_vamana_search_prune_dev", lambda: lib.pann_vamana_search_prune_dev(h, _vp(ids), 16, 0, 8, 16, 1.2, _vp(o_rows), None), (o_rows,))
+            un("pann_vamana_apply_rows_dev", lambda: lib.pann_vamana_apply_rows_dev(h, _vp(ids), 16, _vp(o_rows), 8, 1.2, None), (o_rows,))
+            un("pann_hcnng_build_trees_dev", lambda: lib.pann_hcnng_build_trees_dev(h, 0, 1, 2, 16, 3, 1, _vp(o_rows), 6, None), (o_rows,))
+            un("pann_hcnng_assemble_dev", lambda: lib.pann_hcnng_assemble_dev(h, _vp(o_rows), 1, 6, 2, 3), (o_rows,))
             un("pann_robust_prune_batch", lambda: lib.pann_robust_prune_batch(h, _vp(ids[:1]), 1, _vp(ids), None, _vp(off2), 1.2, 8, 1,
                                                                                _vp(o_rows), _vp(o_dc)), (o_rows, o_dc))
             un("pann_leaf_knn", lambda: lib.pann_leaf_knn(h, _vp(ids), 16, 4, _vp(o_ids), _vp(o_d)), (o_ids, o_d))
