@@ -604,6 +604,30 @@ int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_qua
                              const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                              const pann_rerank_out* out);
 
+/* ---- masked beam search: results restricted by an allow bitmap, traversal unchanged (DESIGN.md "Masked search") ----
+ * allow: ceil(n / 32) uint32 words per row; point i is allowed iff bit (i & 31) of word (i >> 5) is set; bits at positions
+ * >= n are ignored.  allow_stride_words == 0: one bitmap for the whole batch; >= ceil(n / 32): query q reads row q.
+ * The search is pann_batch_search's, step for step: out->frontier_size, visited_count, dist_cmps, degree_sum and
+ * visited_ids/dists are what pann_batch_search returns for the same arguments, whatever the bitmap holds.
+ * out->ids/dists do NOT hold the head of the frontier: they hold, sorted by (dist, id), the min(out_k, count) best ALLOWED
+ * points among all points whose full distance the search computed -- start points, neighbours at or beyond the cutoff and
+ * candidates still unmerged at the end included, a point that was compared twice listed once.  Unused slots 0xFFFFFFFF / +inf.
+ * out_result_count (optional, nq): entries of the query's list (<= out_k).  out_allowed_cmps (optional, nq): full distances
+ * computed for allowed points, repeats counted -- a small value says that the mask starved the query.
+ * Status: NULL bitmap, a stride between 1 and ceil(n / 32) - 1, out_k > beam -> PANN_ERR_BAD_ARG; out_k > 64 ->
+ * PANN_ERR_UNSUPPORTED; everything else as pann_batch_search (a dropped-list overflow grows the list and repeats the batch).
+ * Per-query rows are staged in one piece with the queries: nq * ceil(n / 32) * 4 bytes of pinned and of device memory (1.25 GB
+ * for 10 000 queries at 1M points).  Callers with many per-query masks keep them on the device and use the _dev entry. */
+int pann_batch_search_masked(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                             uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                             const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
+                             uint32_t* out_result_count, uint32_t* out_allowed_cmps);
+/* Device pointers throughout, launched on `stream`; no sync, no alloc beyond the workspace growth of pann_batch_search_dev. */
+int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                 uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                 const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
+                                 uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,11 @@ SIGNATURES = {
     "pann_batch_search_filtered_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64,
                                                  C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.POINTER(SearchOut), C.c_void_p,
                                                  C.c_void_p]),
+    "pann_batch_search_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                           C.POINTER(QueryParams), C.c_void_p, C.c_uint64, C.POINTER(SearchOut), C.c_void_p, C.c_void_p]),
+    "pann_batch_search_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                               C.POINTER(QueryParams), C.c_void_p, C.c_uint64, C.POINTER(SearchOut), C.c_void_p,
+                                               C.c_void_p, C.c_void_p]),
     "pann_batch_search_rerank": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
                                            C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.POINTER(RerankOut)]),
     "pann_batch_search_rerank_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,

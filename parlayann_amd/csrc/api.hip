@@ -494,6 +494,20 @@ int pann_index_get_graph(pann_index* idx, uint32_t* graph_out) {
 // batched beam search
 // ---------------------------------------------------------------------------------------------
 
+// the extra arguments of pann_batch_search_masked*: bitmap rows (host or device, as the entry point's other pointers) and outputs
+struct MaskArgs { const uint32_t* allow; uint64_t stride; uint32_t* result_count; uint32_t* allowed_cmps; };
+static int mask_checks(const pann_index* idx, const MaskArgs& m, const pann_query_params* qp, const pann_search_out* out) {
+  const uint64_t words = (idx->ix.n + 31) / 32;
+  if ((int64_t)out->out_k > qp->beam) { set_error("pann_batch_search_masked: out_k larger than the beam"); return PANN_ERR_BAD_ARG; }
+  if (!m.allow) { set_error("pann_batch_search_masked: null allow bitmap"); return PANN_ERR_BAD_ARG; }
+  if (m.stride != 0 && m.stride < words) {
+    set_error("pann_batch_search_masked: allow_stride_words must be 0 (one shared bitmap) or at least ceil(n / 32) = " + std::to_string(words));
+    return PANN_ERR_BAD_ARG;
+  }
+  if (out->out_k > 64) { set_error("pann_batch_search_masked: out_k > 64 is not supported"); return PANN_ERR_UNSUPPORTED; }
+  return PANN_OK;
+}
+
 static int search_common_checks(pann_index* idx, uint64_t nq, const pann_query_params* qp, const pann_search_out* out) {
   if (int rc = check_idx(idx, "pann_batch_search")) return rc;
   if (!qp || !out) { set_error("pann_batch_search: null params/out"); return PANN_ERR_BAD_ARG; }
@@ -509,8 +523,9 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
                                  uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
                                  uint32_t nstarts, const pann_query_params* qp,
                                  const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
-                                 uint64_t sq_stride, uint32_t* d_pruned) {
+                                 uint64_t sq_stride, uint32_t* d_pruned, const MaskArgs* mask = nullptr) {
   if (int rc = search_common_checks(idx, nq, qp, d_out)) return rc;
+  if (mask) { if (int rc = mask_checks(idx, *mask, qp, d_out)) return rc; }
   if (filter) { if (int rc = refuse_4bit(idx, "pann_batch_search_filtered_dev")) return rc; }
   if (!d_starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if (d_queries && q_stride_bytes < idx->ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
@@ -522,6 +537,9 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
   a.dcap = idx->dcap;
   a.out = *d_out;
   a.filter = filter; a.sketch_queries = (const uint8_t*)d_sketch_queries; a.sq_stride = sq_stride; a.pruned_cmps = d_pruned;
+  if (mask) {
+    a.masked = 1; a.allow = mask->allow; a.allow_stride = mask->stride; a.result_count = mask->result_count; a.allowed_cmps = mask->allowed_cmps;
+  }
   if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
   return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, (hipStream_t)stream);
 }
@@ -539,6 +557,14 @@ int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const
                                    const pann_search_out* d_out, uint32_t* d_out_pruned_cmps, void* stream) {
   return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 1, d_sketch_queries,
                                sq_stride_bytes, d_out_pruned_cmps);
+}
+
+int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                 uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                 const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
+                                 uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
+  const MaskArgs m{d_allow, allow_stride_words, d_out_result_count, d_out_allowed_cmps};
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &m);
 }
 
 }  // extern "C"
@@ -577,8 +603,10 @@ static int run_with_dropped_growth(pann_index* idx, uint64_t nq, const pann_quer
 static int batch_search_host(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int per_query,
                              const pann_query_params* qp, const pann_search_out* out, int filter = 0,
-                             const void* sketch_queries = nullptr, uint64_t sq_stride = 0, uint32_t* out_pruned = nullptr) {
+                             const void* sketch_queries = nullptr, uint64_t sq_stride = 0, uint32_t* out_pruned = nullptr,
+                             const MaskArgs* mask = nullptr) {
   if (int rc = search_common_checks(idx, nq, qp, out)) return rc;
+  if (mask) { if (int rc = mask_checks(idx, *mask, qp, out)) return rc; }
   uint32_t sk_row = 0;
   if (filter) {
     if (int rc = refuse_4bit(idx, "pann_batch_search_filtered")) return rc;
@@ -605,11 +633,16 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   if (queries && q_stride_bytes < ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   const size_t qbytes = queries ? (nq - 1) * q_stride_bytes + ix.dbytes : nq * 4;
-  const size_t off_st = al(qbytes + 16), in_bytes = off_st + al((size_t)nst_total * 4);
+  // masked: the bitmap rows travel with them, packed to ceil(n / 32) words per row
+  const size_t mwords = (size_t)((ix.n + 31) / 32), mrows = mask ? (mask->stride ? (size_t)nq : 1) : 0;
+  const size_t off_st = al(qbytes + 16), off_mask = off_st + al((size_t)nst_total * 4), in_bytes = off_mask + al(mrows * mwords * 4);
   if (int rc = idx->pin_in.ensure(in_bytes)) return rc;
   if (int rc = idx->stage[2].ensure(in_bytes)) return rc;
   std::memcpy(idx->pin_in.p, queries ? queries : (const void*)query_ids, qbytes);
   std::memcpy((uint8_t*)idx->pin_in.p + off_st, starts, (size_t)nst_total * 4);
+  for (size_t r = 0; r < mrows; r++)
+    std::memcpy((uint8_t*)idx->pin_in.p + off_mask + r * mwords * 4, mask->allow + r * mask->stride, mwords * 4);
+  const uint32_t* d_allow = (const uint32_t*)((uint8_t*)idx->stage[2].p + off_mask);
   PANN_HIP(hipMemcpyAsync(idx->stage[2].p, idx->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
   const void* d_q = queries ? idx->stage[2].p : nullptr;
   const uint32_t* d_qid = queries ? nullptr : idx->stage[2].as<uint32_t>();
@@ -622,10 +655,11 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
   const size_t ok = out->out_k, vc = out->visited_cap;
   struct Piece { void* host; size_t bytes; size_t off; };
-  Piece pc[9] = {{out->ids, nq * ok * 4, 0}, {out->dists, nq * ok * 4, 0}, {out->frontier_size, nq * 4, 0},
-                 {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {out->degree_sum, nq * 4, 0},
-                 {out->visited_ids, nq * vc * 4, 0}, {out->visited_dists, nq * vc * 4, 0},
-                 {filter ? out_pruned : nullptr, nq * 4, 0}};
+  Piece pc[11] = {{out->ids, nq * ok * 4, 0}, {out->dists, nq * ok * 4, 0}, {out->frontier_size, nq * 4, 0},
+                  {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {out->degree_sum, nq * 4, 0},
+                  {out->visited_ids, nq * vc * 4, 0}, {out->visited_dists, nq * vc * 4, 0},
+                  {filter ? out_pruned : nullptr, nq * 4, 0},
+                  {mask ? mask->result_count : nullptr, nq * 4, 0}, {mask ? mask->allowed_cmps : nullptr, nq * 4, 0}};
   size_t out_bytes = 0;
   for (auto& x : pc) { if (!x.host) x.bytes = 0; x.off = out_bytes; out_bytes += al(x.bytes); }
   if (int rc = idx->stage[4].ensure(out_bytes + 256)) return rc;
@@ -661,6 +695,11 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
       if (filter) {
         a.sketch_queries = sketch_queries ? (const uint8_t*)idx->stage[5].p + q0 * sk_row : nullptr; a.sq_stride = sk_row;
         a.pruned_cmps = dptr(8) ? (uint32_t*)dptr(8) + q0 : nullptr;
+      }
+      if (mask) {
+        a.masked = 1; a.allow = mask->stride ? d_allow + q0 * mwords : d_allow; a.allow_stride = mask->stride ? mwords : 0;
+        a.result_count = dptr(9) ? (uint32_t*)dptr(9) + q0 : nullptr;
+        a.allowed_cmps = dptr(10) ? (uint32_t*)dptr(10) + q0 : nullptr;
       }
       if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
       if (int rc = launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
@@ -700,6 +739,14 @@ int pann_batch_search_filtered(pann_index* idx, const void* queries, const uint3
                                const pann_search_out* out, uint32_t* out_pruned_cmps) {
   return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 1, sketch_queries, sq_stride_bytes,
                            out_pruned_cmps);
+}
+
+int pann_batch_search_masked(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                             uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                             const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
+                             uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
+  const MaskArgs m{allow, allow_stride_words, out_result_count, out_allowed_cmps};
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &m);
 }
 
 int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,

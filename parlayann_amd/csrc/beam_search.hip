@@ -118,6 +118,10 @@ struct BSParams {
   const uint8_t* sketch_queries; uint64_t sq_stride; uint32_t sk_row_bytes;   // external queries: nq host-layout rows
   uint32_t sk_lds_off;                            // byte offset of the query sketch in LDS
   uint32_t* pruned_cmps;                          // [nq] optional: starts + neighbours that passed the hash filter
+  // masked search (MASKED variants only): allow bitmap, see DESIGN.md "Masked search"
+  const uint32_t* allow; uint64_t allow_stride;   // point i is allowed iff bit i & 31 of word i >> 5; query q reads row q (stride in words, 0: shared)
+  uint32_t* result_count; uint32_t* allowed_cmps; // [nq] optional: entries of the result list; full distances of allowed points
+  uint32_t rl_off;                                // byte offset of the result list in LDS (64 keys), then the keys of one gather (64)
 };
 
 template <bool HASH_LDS>
@@ -371,6 +375,67 @@ __device__ __forceinline__ uint32_t gather_distances_split(const BSParams& P, co
 }
 
 
+// ---- masked search: the result list (DESIGN.md "Masked search") ----
+// The min(out_k, count) smallest keys among the ALLOWED points whose full distance the search computed, kept beside the
+// traversal, which never looks at it: one key per lane, ascending, KEY_INF beyond the fill.  `thr` (wave-uniform) is its
+// out_k-th entry: a key at or above it cannot enter the result.  The list itself keeps up to 64 entries, so a point that is
+// compared again (the hash filter is lossy) and would enter is always still there to be recognised.
+// The keys live in LDS (L[lane], touched by their own lane only) and are in registers only while a key is being inserted: the
+// beam-64 kernel has no VGPRs to spare while the rows of a gather are in flight.
+struct MaskedList { uint64_t* L; uint64_t thr; uint32_t cmps; };
+__device__ __forceinline__ void masked_offer(MaskedList& R, uint64_t key, bool allowed, uint32_t thr_lane, int lane) {
+  R.cmps += __popcll(__ballot(allowed));
+  uint64_t bm = __ballot(allowed && key < R.thr);
+  if (bm == 0ull) return;                                 // the common case once the list is full
+  uint64_t lk = R.L[lane];
+  while (bm) {                                            // uniform: one trip per key that may enter
+    const int l = __ffsll((unsigned long long)bm) - 1;
+    bm &= bm - 1;
+    const uint64_t kk = readlane64(key, l);
+    if (kk >= R.thr) continue;                            // an earlier trip tightened the threshold
+    if (__ballot((uint32_t)lk == (uint32_t)kk) != 0ull) continue;   // compared before: equal ids <=> equal keys
+    const uint32_t r = __popcll(__ballot(lk < kk));       // rank of the new key
+    const uint64_t up = __shfl_up(lk, 1);
+    if (lane > (int)r) lk = up; else if (lane == (int)r) lk = kk;
+    R.thr = readlane64(lk, (int)thr_lane);
+  }
+  R.L[lane] = lk;
+}
+
+// What the lane that owns a filter survivor keeps across the gather: position in Pl and bit number of its id (0: owns none).
+__device__ __forceinline__ uint32_t masked_note(bool mine, uint32_t mypos, uint32_t a) {
+  return mine ? (0x80000000u | (mypos << 5) | (a & 31u)) : 0u;
+}
+
+// gather_distances (batched emit) for the MASKED kernels.  The callback does what gather_distances' does and also leaves every
+// candidate's key -- at or beyond the cutoff too -- in LDS at its index in Pl (MK, 64 keys behind the result list).  After the
+// gather the lane that owns candidate Pl[mypos] (`note`, masked_note) reads that key back and tests its own bit: the bitmap word
+// `aword` was requested before the row loads of the gather and is first used here, after all of them, so it adds no dependent
+// round trip, and the callback holds nothing but a ballot and LDS stores.  One offer of up to 64 keys per call.
+template <int DT, int METRIC, int LPC, bool NCH1, int U>
+__device__ __forceinline__ uint32_t gather_distances_masked(const BSParams& P, const QReg<DT>& qreg, const uint4* qlds,
+                                                            const uint32_t* Pl, uint32_t m, uint32_t cutoff_ord, uint64_t* C,
+                                                            uint32_t c, int lane, uint32_t note, uint32_t aword, MaskedList& R,
+                                                            uint32_t thr_lane) {
+  const PointsView PV{P.points, P.pstride, P.nch, P.exact};
+  uint64_t* MK = R.L + PANN_WAVE;
+  gather_tile<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, lane,
+    [&](bool has, uint32_t ci, uint32_t id, float dist, uint64_t before) {
+      const uint32_t ord = f2ord(dist);
+      const uint64_t key = ((uint64_t)ord << 32) | id;
+      const bool pass = has && (ord < cutoff_ord);
+      const uint64_t pm = __ballot(pass);
+      if (pass) C[c + (uint32_t)__popcll(pm & before)] = key;
+      c += __popcll(pm);
+      if (has) MK[ci] = key;
+    });
+  PANN_WSYNC();
+  const bool mine = (note >> 31) != 0u;
+  const uint64_t key = mine ? MK[(note >> 5) & 63u] : KEY_INF;
+  masked_offer(R, key, mine && ((aword >> (note & 31u)) & 1u) != 0u, thr_lane, lane);
+  return c;
+}
+
 // Sketch distance of base point `a` to the query sketch SQ (LDS, wave-uniform), as the float the reference's distance()
 // returns: Hamming distance (Euclidean_Bit_Point / Mips_Bit_Point; as_written: the reference's loop, which counts block 0
 // num_blocks times, euclidian_point.h:360-361, mips_point.h:652-653) or sum of 2 pop(ne & nz) - pop(nz) over the blocks
@@ -407,8 +472,10 @@ __device__ __forceinline__ float sketch_distance(const BSParams& P, const uint4*
 // neighbour that passed the hash filter gets a full distance only if its sketch distance to the query is below the running
 // mean of the sketch distance to the worst frontier entry.  After the hash-filter replay lane i still owns neighbour i: it
 // reads its own candidate's sketch, and the ballot compaction that follows hands the gather a dense list in row order.
-template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = false>
+// MASKED: the traversal of the plain search; out->ids/dists hold the result list over the allowed points (see MaskedList).
+template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = false, bool MASKED = false>
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(BSParams P) {
+  static_assert(!(FILTER && MASKED), "the masked search has no sketch-filtered form");
   const int lane = threadIdx.x;
   extern __shared__ __align__(16) uint8_t smem[];
   // ---- LDS carve (all regions 16 B aligned): 6.4 KB at beam 64 / degree 64 -> 24 queries per CU ----
@@ -468,6 +535,10 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
 #endif
     uint64_t* DL = P.dropped + (size_t)qi * P.dcap;
+    [[maybe_unused]] MaskedList R{reinterpret_cast<uint64_t*>(smem + P.rl_off), P.out.out_k ? KEY_INF : 0ull, 0u};
+    [[maybe_unused]] const uint32_t thr_lane = P.out.out_k ? P.out.out_k - 1u : 0u;
+    [[maybe_unused]] const uint32_t* AW = nullptr;
+    if constexpr (MASKED) { AW = P.allow + (size_t)qi * P.allow_stride; R.L[lane] = KEY_INF; }
 
     // ---- start points (:66-70): distance for each, filter insert in order, then "merge" into
     // the empty frontier (which sorts them) ----
@@ -476,10 +547,16 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
       const bool act = i < P.nstarts;
       const uint32_t a = act ? P.starts[(size_t)qi * P.starts_stride + i] : 0u;
       (void)filter_update<HASH_LDS>(H, hmask, act, a, lane, reinterpret_cast<uint8_t*>(Hl));
+      [[maybe_unused]] uint32_t aword = 0u;
+      if constexpr (MASKED) if (act) aword = AW[a >> 5];
       if (act) PANN_PL[lane] = a;
       PANN_WSYNC();
       const uint32_t m = min(P.nstarts - s0, (uint32_t)PANN_WAVE);
       // every start enters the frontier: cutoff above any finite distance
+      if constexpr (MASKED)
+        c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane,
+                                                              masked_note(act, (uint32_t)lane, a), aword, R, thr_lane);
+      else
       c = gather_distances<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane);
       PANN_WSYNC();
     }
@@ -547,11 +624,19 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
           }
           const uint64_t km = __ballot(keep);
           const uint32_t m = __popcll(km);
-          if (keep) PANN_PL[lanes_below(km, lane)] = a;
+          [[maybe_unused]] uint32_t aword = 0u;
+          if constexpr (MASKED) if (keep) aword = AW[a >> 5];         // in flight with the rows of the gather
+          const uint32_t mypos = lanes_below(km, lane);
+          if (keep) PANN_PL[mypos] = a;
           dcmps += m;                                                 // :137,155
           PANN_WSYNC();
           PANN_STAMP(2);   // filter + compaction
+          if constexpr (MASKED) {
+            if (m) c = gather_distances_masked<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, PANN_PL, m, cutoff_ord, C, c, lane,
+                                                                               masked_note(keep, mypos, a), aword, R, thr_lane);
+          } else {
           if (m) c = gather_distances<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, PANN_PL, m, cutoff_ord, C, c, lane);
+          }
           PANN_WSYNC();
           PANN_STAMP(3);   // gather + distances
         }
@@ -664,12 +749,26 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
 
     // ---- outputs (:211-213; searchAll takes the first k ids :378-380) ----
     const size_t qo = (size_t)qi * P.out.out_k;
+    if constexpr (MASKED) {                                        // out_k <= 64: the result list, not the head of the frontier
+      const uint64_t rkey = R.L[lane];
+      const uint64_t fill = __ballot(rkey != KEY_INF);
+      if (lane < (int)P.out.out_k) {
+        const bool ok = rkey != KEY_INF;
+        if (P.out.ids) P.out.ids[qo + lane] = ok ? key_id(rkey) : SENTINEL;
+        if (P.out.dists) P.out.dists[qo + lane] = ok ? key_dist(rkey) : __builtin_inff();
+      }
+      if (lane == 0) {
+        if (P.result_count) P.result_count[qi] = min((uint32_t)__popcll(fill), P.out.out_k);
+        if (P.allowed_cmps) P.allowed_cmps[qi] = R.cmps;
+      }
+    } else {
     for (uint32_t j = lane; j < P.out.out_k; j += PANN_WAVE) {
       const bool ok = j < f;
       uint64_t key = 0ull;
       if (ok) key = F[j];
       if (P.out.ids) P.out.ids[qo + j] = ok ? key_id(key) : SENTINEL;
       if (P.out.dists) P.out.dists[qo + j] = ok ? key_dist(key) : __builtin_inff();
+    }
     }
 #ifdef PANN_STAMPS
     if (lane == 0 && P.stamps) for (int i = 0; i < 8; i++) P.stamps[(size_t)qi * 8 + i] = stamp_sum[i];
@@ -698,7 +797,8 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
 // are merged one after the other; cut-prune runs once at the end).  LDS per query shrinks to the
 // filter (4 KB) + a 64-entry scatter scratch + the candidate list: 5.2 KB -> 31 queries per CU.
 // =============================================================================================
-template <int DT, int METRIC, int LPC, bool NCH1>
+// MASKED: as in the generic kernel.
+template <int DT, int METRIC, int LPC, bool NCH1, bool MASKED = false>
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_kernel(BSParams P) {
   const int lane = threadIdx.x;
   extern __shared__ __align__(16) uint8_t smem[];
@@ -729,6 +829,10 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
   uint64_t fkey = KEY_INF;
   uint32_t fflag = 0;
   uint64_t* DL = P.dropped + (size_t)qi * P.dcap;
+  [[maybe_unused]] MaskedList R{reinterpret_cast<uint64_t*>(smem + P.rl_off), P.out.out_k ? KEY_INF : 0ull, 0u};
+  [[maybe_unused]] const uint32_t thr_lane = P.out.out_k ? P.out.out_k - 1u : 0u;
+  [[maybe_unused]] const uint32_t* AW = nullptr;
+  if constexpr (MASKED) { AW = P.allow + (size_t)qi * P.allow_stride; R.L[lane] = KEY_INF; }
 #ifdef PANN_STAMPS
   unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
@@ -739,8 +843,14 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
     const bool act = lane < (int)P.nstarts;
     const uint32_t a = act ? P.starts[(size_t)qi * P.starts_stride + lane] : 0u;
     (void)filter_update<true>(H, hmask, act, a, lane);
+    [[maybe_unused]] uint32_t aword = 0u;
+    if constexpr (MASKED) if (act) aword = AW[a >> 5];
     if (act) Pl[lane] = a;
     PANN_WSYNC();
+    if constexpr (MASKED)
+      c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane,
+                                                            masked_note(act, (uint32_t)lane, a), aword, R, thr_lane);
+    else
     c = gather_distances<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane);
     PANN_WSYNC();
   }
@@ -782,8 +892,9 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
       const uint32_t pref_val = pref_row;
       pref_id = SENTINEL;
       const uint64_t rest1 = um & (um - 1);
-      // two vertices this iteration? (nvis already counts `cur`: a second visit needs nvis < limit)
-      const bool pair_try = PANN_B64_PAIR && P.skip_enabled && rest1 != 0ull && P.gstride <= PANN_WAVE && nvis < P.limit;
+      // two vertices this iteration? (nvis already counts `cur`: a second visit needs nvis < limit).  The pair path (off in the
+      // shipped build) has no masked form: a MASKED instantiation always takes the single-vertex path
+      const bool pair_try = PANN_B64_PAIR && !MASKED && P.skip_enabled && rest1 != 0ull && P.gstride <= PANN_WAVE && nvis < P.limit;
       if (PANN_B64_PREFETCH) {
         const uint64_t rest = pair_try ? (rest1 & (rest1 - 1)) : rest1;      // the entry after the one(s) visited now
         if (rest) {
@@ -867,11 +978,19 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
         const bool keep = act && !seen && ((int64_t)a != self);   // :133
         const uint64_t km = __ballot(keep);
         const uint32_t m = __popcll(km);
-        if (keep) Pl[lanes_below(km, lane)] = a;
+        [[maybe_unused]] uint32_t aword = 0u;
+        if constexpr (MASKED) if (keep) aword = AW[a >> 5];         // in flight with the rows of the gather
+        const uint32_t mypos = lanes_below(km, lane);
+        if (keep) Pl[mypos] = a;
         dcmps += m;
         PANN_WSYNC();
         PANN_STAMP(2);
+        if constexpr (MASKED) {
+          if (m) c = gather_distances_masked<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane,
+                                                                             masked_note(keep, mypos, a), aword, R, thr_lane);
+        } else {
         if (m) c = gather_distances<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane);
+        }
         PANN_WSYNC();
         PANN_STAMP(3);
       }
@@ -965,6 +1084,19 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
   asm volatile("s_waitcnt vmcnt(0)" : "+v"(pref_row));          // no speculative load may outlive its register
 
   const size_t qo = (size_t)qi * P.out.out_k;
+  if constexpr (MASKED) {                                        // the result list, not the head of the frontier
+    const uint64_t rkey = R.L[lane];
+    const uint64_t fill = __ballot(rkey != KEY_INF);
+    if (lane < (int)P.out.out_k) {
+      const bool ok = rkey != KEY_INF;
+      if (P.out.ids) P.out.ids[qo + lane] = ok ? key_id(rkey) : SENTINEL;
+      if (P.out.dists) P.out.dists[qo + lane] = ok ? key_dist(rkey) : __builtin_inff();
+    }
+    if (lane == 0) {
+      if (P.result_count) P.result_count[qi] = min((uint32_t)__popcll(fill), P.out.out_k);
+      if (P.allowed_cmps) P.allowed_cmps[qi] = R.cmps;
+    }
+  } else
   if (lane < (int)P.out.out_k) {                                 // out_k <= beam <= 64
     const bool ok = lane < (int)f;
     if (P.out.ids) P.out.ids[qo + lane] = ok ? key_id(fkey) : SENTINEL;
@@ -1373,7 +1505,12 @@ struct Plan {
   uint32_t hsplit; // ... of which the part with an LDS share (filter_update split mode)
   uint32_t p24;    // ... stored as planar 24-bit entries
   bool filter; uint32_t sk_lds_off;   // sketch-filtered search: the generic kernel's FILTER variant, query sketch after its LDS state
+  uint32_t rl_off; // ... masked: byte offset of the result list (64 keys) in LDS
+  bool masked;     // allow-bitmap search: the MASKED variant of the b64 kernel (bcap 64) or of the generic kernel (every other beam)
 };
+
+// which layouts have a MASKED instantiation of the b64 kernel (the others spill under its launch bound: make_plan)
+constexpr bool masked_b64_fits(int dtype, uint32_t lpc, bool nch1) { return !(lpc == 8 && nch1) && !(dtype == PANN_BF16 && !nch1); }
 
 static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
   Plan p;
@@ -1393,6 +1530,17 @@ static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
   p.lds_bytes = (uint32_t)(fixed + (p.hash_lds ? hbytes : 1024));      // HBM filter: 1 KB replay scratch (filter_update)
   p.slots = 256 * 8;
   p.filter = a.filter != 0; p.sk_lds_off = 0;
+  p.masked = a.masked != 0; p.rl_off = 0;
+  // Two families of the b64 kernel have no room for the masked state under its 72-VGPR bound: 128-byte rows (8 lanes per
+  // candidate, 32 candidates per gather iteration) and bf16 rows of several chunks per lane.  Their masked forms would spill next
+  // to the hand-issued row prefetch, so they are not instantiated and take the generic kernel
+  const bool masked_b64 = p.hash_lds && p.bcap == 64 && masked_b64_fits(ix.dtype, ix.lpc, nch1);
+  if (p.masked && !masked_b64) {   // no masked b128 kernel either: the generic one, as the sketch filter does
+    p.b64 = p.b128 = p.b128_codes = p.b128_hbm = false; p.hsplit = 0; p.p24 = 0;
+    p.rl_off = (p.lds_bytes + 15u) & ~15u;             // its LDS state, then the result list and the keys of one gather (64 + 64 keys)
+    p.lds_bytes = p.rl_off + 1024;
+    return p;
+  }
   if (p.filter) {     // every beam width takes the generic kernel; its LDS state, then the query sketch
     p.b64 = p.b128 = p.b128_codes = p.b128_hbm = false; p.hsplit = 0; p.p24 = 0;
     p.sk_lds_off = (p.lds_bytes + 15u) & ~15u;
@@ -1403,6 +1551,7 @@ static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
   if (p.b64) {   // register-frontier kernel: scratch[64] + candidates (exact, 8-entry granules) + flags + query + filter
     p.ccap = (std::max<uint32_t>(beam / 8 + p.deg_eff, a.nstarts) + 7) / 8 * 8;
     p.lds_bytes = (uint32_t)(64 * 8 + (size_t)p.ccap * 8 + 64 + (nch1 ? 0 : (size_t)ix.nch * ix.lpc * 16) + hbytes);
+    if (p.masked) { p.rl_off = (p.lds_bytes + 15u) & ~15u; p.lds_bytes = p.rl_off + 1024; }
   }
   p.b128 = p.hash_lds && p.bcap == 128 && a.nstarts <= 64;
   p.b128_hbm = false;
@@ -1455,6 +1604,25 @@ static hipError_t launch_variant(const BSParams& P, const Plan& p, hipStream_t s
       hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
     } else {
       auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, true>;
+      if (p.lds_bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+      const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
+      hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    }
+  } else if (p.masked) {   // allow bitmap: register frontier at bcap 64, else the generic kernel
+    if (p.b64) {
+      if constexpr (!masked_b64_fits(DT, LPC, NCH1)) return hipErrorInvalidValue;   // make_plan never asks for it
+      else {
+        auto kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1, true>;
+        hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+      }
+    } else if (p.hash_lds) {
+      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, true>;
+      if (p.lds_bytes > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+      hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    } else {
+      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, true>;
       if (p.lds_bytes > 48 * 1024)
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
       const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
@@ -1527,6 +1695,9 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
       set_error("pann_batch_search_filtered: sketch query stride smaller than a sketch row, or rows not 8-byte aligned"); return PANN_ERR_BAD_ARG;
     }
   }
+  // the bitmap, its stride and out_k <= 64 are checked by the entry points (api.hip: mask_checks); no entry point combines a mask
+  // with the sketch filter, and there is no kernel for it
+  if (a.masked && a.filter) { set_error("pann_batch_search_masked: the sketch filter has no masked form"); return PANN_ERR_UNSUPPORTED; }
   Plan p = make_plan(ix, a);
   if (p.lds_bytes > 160 * 1024) { set_error("pann_batch_search: beam/degree too large for LDS state"); return PANN_ERR_UNSUPPORTED; }
   if (search_workspace_bytes(ix, a) > ws_bytes) { set_error("pann_batch_search: workspace too small"); return PANN_ERR_BAD_ARG; }
@@ -1562,6 +1733,9 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   P.sketch_queries = a.sketch_queries; P.sq_stride = a.sq_stride;
   P.sk_row_bytes = a.filter ? sketch_row_bytes(ix.sk_kind, ix.d) : 0u;
   P.sk_lds_off = p.sk_lds_off; P.pruned_cmps = a.filter ? a.pruned_cmps : nullptr;
+  P.allow = a.masked ? a.allow : nullptr; P.allow_stride = a.masked ? a.allow_stride : 0;
+  P.result_count = a.masked ? a.result_count : nullptr; P.allowed_cmps = a.masked ? a.allowed_cmps : nullptr;
+  P.rl_off = p.rl_off;
 #ifdef PANN_STAMPS
   static unsigned long long* d_stamps = nullptr; static size_t stamps_cap = 0;
   if (stamps_cap < a.nq) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void**)&d_stamps, a.nq * 64); stamps_cap = a.nq; }

@@ -94,6 +94,12 @@ struct SearchArgs {  // one batched beam search, everything device resident
   const uint8_t* sketch_queries = nullptr;   // nq host-layout sketch rows (external queries); base-point queries use their own row
   uint64_t sq_stride = 0;
   uint32_t* pruned_cmps = nullptr;           // nq, optional: the reference's local dist_cmps (starts + sum of pruned.size())
+  // masked search (DESIGN.md "Masked search"): same traversal, out.ids/dists = the best allowed points that were compared
+  int masked = 0;
+  const uint32_t* allow = nullptr;           // ceil(n / 32) words per row: point i allowed iff bit i & 31 of word i >> 5
+  uint64_t allow_stride = 0;                 // words between the rows of two queries; 0: one bitmap for the batch
+  uint32_t* result_count = nullptr;          // nq, optional: entries of the query's result list (<= out.out_k)
+  uint32_t* allowed_cmps = nullptr;          // nq, optional: full distances computed for allowed points
 };
 
 // per-handle scratch that the search kernels need (grown on demand, never shrunk)

@@ -2,7 +2,7 @@
 classes python/module.cpp registers (:50-57,150-155), over the C-ABI.
 
     Index(data_path, index_path)                       (positional order of graph_index.cpp:82)
-    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1) -> (uint32[nq,knn], float32[nq,knn])
+    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None) -> (uint32[nq,knn], float32[nq,knn])
     .single_search(q, knn, beam_width, quant, visit_limit)               -> uint32[knn]
     .batch_search_from_string(queries_path, knn, beam_width, quant=False, visit_limit=-1)
     .check_recall(queries_file, gt_file, neighbors, k)   prints "Recall: x"
@@ -77,9 +77,17 @@ class GraphIndex:
         return dict(k=knn, beam=beam_width, cut=1.35, limit=visit_limit,
                     degree_limit=min(self.index.max_degree, 3 * visit_limit))
 
-    def _search(self, queries, knn, beam_width, quant, visit_limit):           # search_dispatch :120-190
+    def _search(self, queries, knn, beam_width, quant, visit_limit, allow=None):   # search_dispatch :120-190
         queries = np.ascontiguousarray(queries, dtype=self.T)
         qp = self._qp(knn, beam_width, visit_limit)
+        if allow is not None:
+            # masked search (this project's own, DESIGN.md "Masked search"): the plain search's walk over the full-precision
+            # points, results = the best allowed points it compared.  Rows may be short (padding 0xFFFFFFFF / +inf), so the
+            # k-results check of the plain path does not apply.  Not in the quantised or rerank paths.
+            if quant and self.use_quantization:
+                raise ValueError("allow= goes with quant=False: the quantised and rerank paths have no masked form")
+            r = self.index.batch_search_masked(queries, allow=allow, out_k=knn, **qp)
+            return r["ids"], r["dists"]
         if not (quant and self.use_quantization):
             r = self.index.batch_search(queries, out_k=knn, **qp)                # :188
             self._need(r["frontier_size"], knn)
@@ -102,15 +110,16 @@ class GraphIndex:
         if len(frontier_size) and int(frontier_size.min()) < knn:               # beamSearch.h:416-419
             raise RuntimeError(f"Error: beam search returned {int(frontier_size.min())} elements, which is less than k = {knn}")
 
-    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1):
-        return self._search(queries, knn, beam_width, quant, visit_limit)
+    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None):
+        """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned"""
+        return self._search(queries, knn, beam_width, quant, visit_limit, allow)
 
     def single_search(self, q, knn, beam_width, quant, visit_limit):
         ids, _ = self._search(np.asarray(q)[None, :], knn, beam_width, quant, visit_limit)
         return ids[0]
 
-    def batch_search_from_string(self, queries, knn, beam_width, quant=False, visit_limit=-1):
-        return self._search(io.read_bin(queries, self.T), knn, beam_width, quant, visit_limit)
+    def batch_search_from_string(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None):
+        return self._search(io.read_bin(queries, self.T), knn, beam_width, quant, visit_limit, allow)
 
     def check_recall(self, queries_file, graph_file, neighbors, k):             # :259-305
         gt_ids, _ = io.read_ibin(graph_file)

@@ -64,6 +64,35 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def allow_bitmap(n, allowed_ids=None, deleted_ids=None):
+    """The allow bitmap of batch_search_masked: ceil(n / 32) uint32 words, point i allowed iff bit i & 31 of word i >> 5.
+    allowed_ids: only these are allowed (default: all n points); deleted_ids: these are then disallowed (lazy tombstones)."""
+    n = int(n)
+    bits = np.zeros(n, dtype=bool) if allowed_ids is not None else np.ones(n, dtype=bool)
+    if allowed_ids is not None:
+        bits[np.asarray(allowed_ids, dtype=np.int64)] = True
+    if deleted_ids is not None:
+        bits[np.asarray(deleted_ids, dtype=np.int64)] = False
+    return pack_allow(bits, n)
+
+
+def pack_allow(allow, n):
+    """boolean (n,) / (nq, n) -> packed uint32 (W,) / (nq, W), W = ceil(n / 32); packed uint32 arrays pass through"""
+    a = np.asarray(allow)
+    w = (int(n) + 31) // 32
+    if a.dtype == np.bool_:
+        if a.ndim not in (1, 2) or a.shape[-1] != n:
+            raise ValueError(f"a boolean allow mask must be ({n},) or (nq, {n}), got {a.shape}")
+        by = np.packbits(a, axis=-1, bitorder="little")
+        pad = w * 4 - by.shape[-1]
+        if pad:
+            by = np.concatenate([by, np.zeros(by.shape[:-1] + (pad,), np.uint8)], axis=-1)
+        return np.ascontiguousarray(by).view("<u4").astype(np.uint32, copy=False)
+    if a.dtype != np.uint32 or a.ndim not in (1, 2) or a.shape[-1] < w:
+        raise ValueError(f"allow must be boolean or packed uint32 with at least {w} words per row, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
 def host_graph(n, max_deg):
     """An empty graph slab in the reference layout (graph.h:134-141): n x (max_deg+1), slot 0 = degree."""
     return np.zeros((n, max_deg + 1), dtype=np.uint32)
@@ -312,8 +341,20 @@ class DeviceIndex:
         return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
                                   filtered=True, sketch_queries=sketch_queries)
 
+    def batch_search_masked(self, queries=None, allow=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
+                            query_ids=None, out_k=None, visited_cap=0, want_dists=True):
+        """pann_batch_search_masked: the traversal of batch_search, results restricted to the points `allow` allows
+        (DESIGN.md "Masked search").  allow: packed uint32 (W,) or (nq, W), W = ceil(n / 32) (allow_bitmap), or boolean (n,)
+        or (nq, n); one row serves the whole batch.  ids/dists: per query the best allowed points among ALL points the search
+        computed a full distance for, padded with 0xFFFFFFFF / +inf; the other fields are batch_search's.  Adds
+        "result_count" (entries per row) and "allowed_cmps" (full distances of allowed points)."""
+        if allow is not None:
+            allow = pack_allow(allow, self.n)
+        return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
+                                  masked=True, allow=allow)
+
     def _batch_search(self, queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                      filtered=False, sketch_queries=None):
+                      filtered=False, sketch_queries=None, masked=False, allow=None):
         nq = len(queries) if queries is not None else len(query_ids)
         qp = QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
                          degree_limit=self.max_degree if degree_limit is None else degree_limit,
@@ -358,6 +399,18 @@ class DeviceIndex:
             check(self._lib.pann_batch_search_filtered(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(sq), 0 if sq is None else sq.shape[1],
                                                        _ptr(starts), starts.shape[-1], C.byref(qp), C.byref(out),
                                                        _ptr(res["pruned_cmps"])))
+            return res
+        if masked:
+            if per_query:
+                raise ValueError("masked searches take shared starts")
+            if allow is not None and allow.ndim == 2 and allow.shape[0] != nq:
+                raise ValueError("per-query allow rows must be nq x W")
+            astride = allow.shape[1] if allow is not None and allow.ndim == 2 else 0
+            res["result_count"] = np.empty(nq, dtype=np.uint32)
+            res["allowed_cmps"] = np.empty(nq, dtype=np.uint32)
+            check(self._lib.pann_batch_search_masked(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1], C.byref(qp),
+                                                     _ptr(allow), astride, C.byref(out), _ptr(res["result_count"]),
+                                                     _ptr(res["allowed_cmps"])))
             return res
         fn = self._lib.pann_batch_search_per_query_starts if per_query else self._lib.pann_batch_search
         check(fn(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1], C.byref(qp), C.byref(out)))
