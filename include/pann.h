@@ -628,6 +628,44 @@ int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const u
                                  const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream);
 
+/* ---- masked search on the fused path: pann_batch_search_rerank with an allow bitmap (DESIGN.md "Masked search on the fused
+ * path") ----  This project's own rule; the reference has no masks.  full: the f32 handle; quant: its one-byte or four-bit
+ * copy; allow / allow_stride_words: the bitmap of pann_batch_search_masked (shared, or one row per query; bits at positions
+ * >= n are ignored).
+ *   1. The queries are quantised as by pann_batch_search_rerank (normalize_first: normalised first, and the normalised row is
+ *      the one the rerank scores against).
+ *   2. The masked search of pann_batch_search_masked_dev on quant with a result list of
+ *      pool = min(qp->k * qp->rerank_factor, qp->beam, 64) entries (a rerank_factor below 1 counts as 1): per query the best
+ *      min(pool, count) ALLOWED points by (quantised dist, id) among all points whose quantised distance the walk computed.  The
+ *      walk is pann_batch_search's: out->frontier_size, visited_count and dist_cmps are what the plain quantised search (and
+ *      pann_batch_search_rerank) returns for the same arguments, whatever the bitmap holds.
+ *   3. num_check = result_count (<= pool): every list entry gets its exact distance on `full` (the arithmetic of pann_rerank,
+ *      exact-float-order flag included), the entries are sorted by (exact dist, id), the first min(k, num_check) are written,
+ *      the remaining slots hold 0xFFFFFFFF / +inf.
+ * A short row is a legitimate answer under a mask: PANN_STATUS_SHORT_FRONTIER is NOT raised; read out_result_count.
+ * out_result_count (optional, nq): length of the quantised list (<= pool).  out_allowed_cmps (optional, nq): as the masked search.
+ * out->pruned_cmps is not written.  The result equals pann_quantize_rows, pann_batch_search_masked on quant with out_k = pool,
+ * and pann_rerank on full with counts = result_count and resort = 1 run one after the other, bit for bit.
+ * Device pointers throughout, launched on `stream`; no synchronisation, and no allocation once quant's scratch has reached
+ * its size.
+ * Status: k == 0, k > beam, a NULL bitmap, a stride between 1 and ceil(n / 32) - 1, and everything
+ * pann_batch_search_rerank_dev rejects -> PANN_ERR_BAD_ARG; k > 64 (the list holds at most 64 keys), use_filter != 0 (there
+ * is no sketch-filter x mask kernel), a `full` handle that is not f32 -> PANN_ERR_UNSUPPORTED; nq == 0 -> PANN_OK.  Nothing is
+ * written on an error. */
+int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams,
+                                        const float* d_queries, uint64_t nq, uint64_t q_stride_bytes, int normalize_first,
+                                        int use_filter, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                        const uint32_t* d_allow, uint64_t allow_stride_words, const pann_rerank_out* d_out,
+                                        uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream);
+/* The same rule with host pointers: queries, starts and the bitmap rows (packed to ceil(n / 32) words each, as
+ * pann_batch_search_masked stages them) go up in one transfer, all outputs come back in one.  A launch that reports
+ * PANN_STATUS_DROPPED_OVERFLOW is grown and run again as by pann_batch_search.  Runs on quant's stream. */
+int pann_batch_search_masked_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                                    uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter,
+                                    const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp, const uint32_t* allow,
+                                    uint64_t allow_stride_words, const pann_rerank_out* out, uint32_t* out_result_count,
+                                    uint32_t* out_allowed_cmps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -198,6 +198,13 @@ SIGNATURES = {
     "pann_batch_search_rerank_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
                                                C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams),
                                                C.POINTER(RerankOut), C.c_void_p]),
+    "pann_batch_search_masked_rerank": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
+                                                  C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.c_void_p,
+                                                  C.c_uint64, C.POINTER(RerankOut), C.c_void_p, C.c_void_p]),
+    "pann_batch_search_masked_rerank_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64,
+                                                      C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams),
+                                                      C.c_void_p, C.c_uint64, C.POINTER(RerankOut), C.c_void_p, C.c_void_p,
+                                                      C.c_void_p]),
 }
 
 _lib = None

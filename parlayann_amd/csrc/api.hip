@@ -1793,16 +1793,34 @@ int search_rerank_checks(const pann_index* full, const pann_index* quant, const 
 // one launch sequence for nq queries with a dropped list of dcap entries; grows quant's workspaces on first use
 int search_rerank_launch(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
                          uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
-                         const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st) {
+                         const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
+                         const MaskedRerank* mask = nullptr) {
   SearchArgs a{};                                  // the fields search_workspace_bytes reads
   a.queries = reinterpret_cast<const uint8_t*>(d_queries); a.nq = nq; a.nstarts = nstarts;
   a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
   a.dcap = dcap; a.filter = use_filter ? 1 : 0;
-  a.out = pann_search_out{}; a.out.out_k = (uint32_t)qp->beam;
+  const uint32_t list = mask ? masked_rerank_pool(qp) : (uint32_t)qp->beam;     // ids kept per query between search and rerank
+  a.out = pann_search_out{}; a.out.out_k = list;
+  a.masked = mask ? 1 : 0;
   if (int rc = quant->ws.ensure(search_workspace_bytes(quant->ix, a))) return rc;
-  if (int rc = quant->ws_rr.ensure(search_rerank_scratch_bytes(quant->ix, nq, (uint32_t)qp->beam, normalize_first, use_filter))) return rc;
+  if (int rc = quant->ws_rr.ensure(search_rerank_scratch_bytes(quant->ix, nq, list, normalize_first, use_filter))) return rc;
   return search_rerank_dev(full->ix, quant->ix, quant->ws.buf, quant->ws.bytes, quant->ws_rr.buf, qparams, &quant->sk_params, d_queries,
-                           nq, q_stride, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d_out, st);
+                           nq, q_stride, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d_out, st, mask);
+}
+
+// pann_batch_search_masked_rerank*: the rerank checks, then the bitmap's through mask_checks (out_k = the list length)
+int masked_rerank_checks(const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                         uint64_t nq, uint64_t q_stride, int use_filter, const uint32_t* starts, uint32_t nstarts,
+                         const pann_query_params* qp, const uint32_t* allow, uint64_t allow_stride_words, const pann_rerank_out* out,
+                         const char* fn) {
+  if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride, 0, starts, nstarts, qp, out, fn)) return rc;
+  const std::string f = fn;
+  if (use_filter) { set_error(f + ": a mask together with the sketch filter is not supported (use_filter must be 0)"); return PANN_ERR_UNSUPPORTED; }
+  pann_search_out so{};
+  so.out_k = masked_rerank_pool(qp);
+  if (int rc = mask_checks(quant, MaskArgs{allow, allow_stride_words, nullptr, nullptr}, qp, &so)) return rc;
+  if (qp->k > 64) { set_error(f + ": k > 64 is not supported (the result list holds at most 64 keys)"); return PANN_ERR_UNSUPPORTED; }
+  return PANN_OK;
 }
 
 }  // namespace
@@ -1866,6 +1884,93 @@ int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_qua
       d.status = (uint32_t*)((uint8_t*)quant->stage[4].p + out_bytes);
       if (int rc = search_rerank_launch(full, quant, qparams, (const float*)((const uint8_t*)d_q + q0 * q_stride_bytes), cnt,
                                         q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d, st)) return rc;
+      if (cnt == nq) {             // the normal case: the word travels with the results
+        PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes + 4, hipMemcpyDeviceToHost, st));
+        PANN_HIP(hipStreamSynchronize(st));
+        std::memcpy(st_word, (uint8_t*)quant->pin_out.p + out_bytes, 4);
+      } else {
+        PANN_HIP(hipMemcpyAsync(st_word, d.status, 4, hipMemcpyDeviceToHost, st));
+        PANN_HIP(hipStreamSynchronize(st));
+      }
+      return PANN_OK;
+    })) return rc;
+  if (!results_home) {
+    PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes, hipMemcpyDeviceToHost, st));
+    PANN_HIP(hipStreamSynchronize(st));
+  }
+  if (quant->ws.bytes > (2ull << 30)) quant->ws.release();          // a one-off worst-case scratch is not kept on the handle
+  for (auto& x : pc) if (x.bytes) std::memcpy(x.host, (uint8_t*)quant->pin_out.p + x.off, x.bytes);
+  if (out->status) *out->status = status;
+  return PANN_OK;
+}
+
+int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
+                                        uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter,
+                                        const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp, const uint32_t* d_allow,
+                                        uint64_t allow_stride_words, const pann_rerank_out* d_out, uint32_t* d_out_result_count,
+                                        uint32_t* d_out_allowed_cmps, void* stream) {
+  if (int rc = masked_rerank_checks(full, quant, qparams, d_queries, nq, q_stride_bytes, use_filter, d_starts, nstarts, qp, d_allow,
+                                    allow_stride_words, d_out, "pann_batch_search_masked_rerank_dev")) return rc;
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)d_queries % 4 != 0) { set_error("pann_batch_search_masked_rerank_dev: query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  const MaskedRerank m{d_allow, allow_stride_words, d_out_result_count, d_out_allowed_cmps};
+  return search_rerank_launch(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, 0, d_starts, nstarts, qp,
+                              quant->dcap, *d_out, (hipStream_t)stream, &m);
+}
+
+int pann_batch_search_masked_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                                    uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts,
+                                    uint32_t nstarts, const pann_query_params* qp, const uint32_t* allow, uint64_t allow_stride_words,
+                                    const pann_rerank_out* out, uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
+  if (int rc = masked_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, allow,
+                                    allow_stride_words, out, "pann_batch_search_masked_rerank")) return rc;
+  for (uint32_t i = 0; i < nstarts; i++)
+    if (starts[i] >= quant->ix.n) { set_error("pann_batch_search_masked_rerank: start point out of range"); return PANN_ERR_BAD_ARG; }
+  if (nq == 0) return PANN_OK;
+  DeviceGuard g(quant->device);
+  hipStream_t st = quant->stream;
+  const DeviceIndex& qx = quant->ix;
+  const uint32_t k = (uint32_t)qp->k;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // ---- inputs: the float rows, the starts and the bitmap rows (packed to ceil(n / 32) words each), one transfer up ----
+  const size_t qbytes = (nq - 1) * q_stride_bytes + 4ull * qx.d;
+  const size_t mwords = (size_t)((qx.n + 31) / 32), mrows = allow_stride_words ? (size_t)nq : 1;
+  const size_t off_st = al(qbytes), off_mask = off_st + al((size_t)nstarts * 4), in_bytes = off_mask + al(mrows * mwords * 4);
+  if (int rc = quant->pin_in.ensure(in_bytes)) return rc;
+  if (int rc = quant->stage[2].ensure(in_bytes)) return rc;
+  std::memcpy(quant->pin_in.p, queries, qbytes);
+  std::memcpy((uint8_t*)quant->pin_in.p + off_st, starts, (size_t)nstarts * 4);
+  for (size_t r = 0; r < mrows; r++)
+    std::memcpy((uint8_t*)quant->pin_in.p + off_mask + r * mwords * 4, allow + r * allow_stride_words, mwords * 4);
+  PANN_HIP(hipMemcpyAsync(quant->stage[2].p, quant->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
+  const float* d_q = quant->stage[2].as<float>();
+  const uint32_t* d_starts = (const uint32_t*)((uint8_t*)quant->stage[2].p + off_st);
+  const uint32_t* d_allow = (const uint32_t*)((uint8_t*)quant->stage[2].p + off_mask);
+  // ---- outputs: one packed device region (the status word last), one transfer down ----
+  struct Piece { void* host; size_t bytes; size_t off; };
+  Piece pc[7] = {{out->ids, nq * k * 4, 0}, {out->dists, nq * k * 4, 0}, {out->frontier_size, nq * 4, 0},
+                 {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {out_result_count, nq * 4, 0},
+                 {out_allowed_cmps, nq * 4, 0}};
+  size_t out_bytes = 0;
+  for (auto& x : pc) { if (!x.host) x.bytes = 0; x.off = out_bytes; out_bytes += al(x.bytes); }
+  if (int rc = quant->stage[4].ensure(out_bytes + 256)) return rc;
+  if (int rc = quant->pin_out.ensure(out_bytes + 256)) return rc;
+  auto dptr = [&](int i) -> uint8_t* { return pc[i].bytes ? (uint8_t*)quant->stage[4].p + pc[i].off : nullptr; };
+  uint32_t status = 0;
+  bool results_home = false;
+  if (int rc = run_with_dropped_growth(quant, nq, qp, "pann_batch_search_masked_rerank", &status, &results_home,
+      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
+      pann_rerank_out d{};
+      d.ids = (uint32_t*)dptr(0) + q0 * k; d.dists = (float*)dptr(1) + q0 * k;
+      if (dptr(2)) d.frontier_size = (uint32_t*)dptr(2) + q0;
+      if (dptr(3)) d.visited_count = (uint32_t*)dptr(3) + q0;
+      if (dptr(4)) d.dist_cmps = (uint32_t*)dptr(4) + q0;
+      d.status = (uint32_t*)((uint8_t*)quant->stage[4].p + out_bytes);
+      const MaskedRerank m{allow_stride_words ? d_allow + q0 * mwords : d_allow, allow_stride_words ? mwords : 0,
+                           dptr(5) ? (uint32_t*)dptr(5) + q0 : nullptr, dptr(6) ? (uint32_t*)dptr(6) + q0 : nullptr};
+      if (int rc = search_rerank_launch(full, quant, qparams, (const float*)((const uint8_t*)d_q + q0 * q_stride_bytes), cnt,
+                                        q_stride_bytes, normalize_first, 0, d_starts, nstarts, qp, dcap, d, st, &m)) return rc;
       if (cnt == nq) {             // the normal case: the word travels with the results
         PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes + 4, hipMemcpyDeviceToHost, st));
         PANN_HIP(hipStreamSynchronize(st));

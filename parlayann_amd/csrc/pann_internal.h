@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
+#include <algorithm>
 #include <string>
 
 #include "../../include/pann.h"
@@ -222,11 +223,23 @@ float sketch_threshold(const pann_sketch_params* p);               // the value 
 // search_rerank.hip: beam_search_rerank on the device -- prepare the float queries (one-byte rows, sketch rows, normalised
 // rows), beam search on the one-byte index, exact rerank of the frontier on the f32 index.  `scratch`: search_rerank_scratch_bytes
 // bytes, 256-byte aligned; search_ws: the one-byte handle's search workspace (its status word gets the SHORT_FRONTIER bit).
+// Masked form (mask != null, DESIGN.md "Masked search on the fused path"): the search is the masked one with a result list of
+// masked_rerank_pool(qp) ids per query, the rerank reads that list (result_count entries) instead of the frontier, raises no
+// SHORT_FRONTIER, and the scratch is sized with the pool in place of the beam.
+struct MaskedRerank {
+  const uint32_t* allow; uint64_t stride;          // device bitmap rows, as SearchArgs::allow / allow_stride
+  uint32_t* result_count; uint32_t* allowed_cmps;  // nq each, optional (device)
+};
+inline uint32_t masked_rerank_pool(const pann_query_params* qp) {   // min(k * rerank_factor, beam, 64), at least 1
+  const int64_t want = std::max<int64_t>((int64_t)qp->k * qp->rerank_factor, 1);
+  return (uint32_t)std::min<int64_t>(std::min<int64_t>(want, std::max<int64_t>(qp->beam, 1)), 64);
+}
 size_t search_rerank_scratch_bytes(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int normalize_first, int use_filter);
 int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* search_ws, size_t search_ws_bytes, void* scratch,
                       const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
                       uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
-                      const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st);
+                      const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
+                      const MaskedRerank* mask = nullptr);
 
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,

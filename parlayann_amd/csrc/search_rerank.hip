@@ -16,6 +16,10 @@
 // bitonic network of lane exchanges sorts them, lane r writes result r.  Nothing but the candidate ids (and a query that
 // does not fit registers) is in LDS, so four queries share a 256-thread workgroup.  More candidates (up to the 4 096 of
 // pann_rerank) keep their keys in LDS and are ranked by counting, one wave per query, as rerank_kernel does.
+//
+// Masked form (pann_batch_search_masked_rerank*, DESIGN.md "Masked search on the fused path"): step 2 is the masked search with
+// a result list of pool = min(k * rerank_factor, beam, 64) ids, step 3 is rerank_list_kernel, which reads result_count entries of
+// that list instead of the head of the frontier.  At most 64 candidates, so it has the register form only.
 #include <algorithm>
 
 #include "pann_device.h"
@@ -198,6 +202,48 @@ __global__ void __launch_bounds__(REG ? RR_WAVES * PANN_WAVE : PANN_WAVE) rerank
   }
 }
 
+// The masked form: the candidates are the result list of the masked search.  RerankArgs as above with fids = the nq x pool
+// lists, beam = pool (<= 64), fsize = the lists' lengths (result_count); want, kcap, out_fsize and status are not read -- the
+// search itself writes frontier_size, and a short row is an answer, not a SHORT_FRONTIER.  Slots past a list's length hold
+// 0xFFFFFFFF: only lanes below the length load an id, and an empty list pads its row without entering the gather.
+template <int METRIC, int LPC, bool NCH1>
+__global__ void __launch_bounds__(RR_WAVES * PANN_WAVE) rerank_list_kernel(RerankArgs P) {
+  constexpr int DT = PANN_F32;
+  const int lane = threadIdx.x & (PANN_WAVE - 1);
+  const uint32_t w = threadIdx.x / PANN_WAVE;
+  const uint64_t qi = (uint64_t)blockIdx.x * (blockDim.x / PANN_WAVE) + w;
+  if (qi >= P.nq) return;                          // a whole wave leaves; the waves of a block share no data and no barrier
+  extern __shared__ __align__(16) uint8_t smem[];
+  uint8_t* base = smem + (size_t)w * (P.qbytes + PANN_WAVE * 4);       // per wave: [query, qbytes] [64 candidate ids]
+  uint4* qlds = reinterpret_cast<uint4*>(base);
+  uint32_t* Pl = reinterpret_cast<uint32_t*>(base + P.qbytes);
+  const uint32_t cn = min(min(P.fsize[qi], P.beam), (uint32_t)PANN_WAVE);      // num_check = result_count
+  const size_t ro = (size_t)qi * P.k;
+  uint64_t key = KEY_INF;
+  if (cn) {                                        // wave-uniform
+    QReg<DT> qreg{};
+    load_query<DT, LPC, NCH1>(P.q + qi * P.q_stride, P.dbytes, P.pv.nch, qreg, qlds, lane);
+    if (lane < (int)cn) Pl[lane] = P.fids[qi * P.beam + lane];
+    wave_lds_sync();
+    const bool per_lane = !NCH1 && P.pv.exact;     // exact float order: lane j already holds candidate j
+    gather_tile<DT, METRIC, LPC, NCH1, 4>(P.pv, qreg, qlds, Pl, cn, lane,
+      [&](bool has, uint32_t ci, uint32_t id, float dist) {
+        const uint64_t mine = make_key(dist, id);
+        if (per_lane) { if (has) key = mine; return; }
+        constexpr int G = PANN_WAVE / LPC;           // as rerank_frontier_kernel: lane j takes candidate j from group j - first
+        const int first = (int)ci - lane / LPC, g = lane - first;
+        const uint64_t got = __shfl(mine, (g & (G - 1)) * LPC);
+        if (g >= 0 && g < G && lane < (int)cn) key = got;
+      });
+    key = wave_sort64(key, lane);                   // lanes >= cn hold KEY_INF: they sort behind every candidate
+  }
+  if (lane < (int)P.k) {                           // k <= 64
+    const bool ok = lane < (int)cn;
+    P.out_ids[ro + lane] = ok ? key_id(key) : SENTINEL;
+    P.out_dists[ro + lane] = ok ? key_dist(key) : __builtin_inff();
+  }
+}
+
 struct Scratch { uint8_t* qb; uint64_t qb_stride; uint8_t* sk; uint64_t sk_stride; uint8_t* nr; uint64_t nr_stride; uint32_t* fids; uint32_t* fsize; size_t bytes; };
 
 Scratch cut_scratch(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int normalize_first, int use_filter, void* base) {
@@ -223,11 +269,14 @@ size_t search_rerank_scratch_bytes(const DeviceIndex& quant, uint64_t nq, uint32
 int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* search_ws, size_t search_ws_bytes, void* scratch,
                       const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
                       uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
-                      const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st) {
+                      const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
+                      const MaskedRerank* mask) {
   if (nq == 0) return PANN_OK;
   const uint32_t d = full.d, beam = (uint32_t)qp->beam, k = (uint32_t)qp->k;
   if (beam == 0 || beam > 4096) { set_error("pann_rerank: candidates per query must be in [1,4096]"); return PANN_ERR_BAD_ARG; }
-  const Scratch s = cut_scratch(quant, nq, beam, normalize_first, use_filter, scratch);
+  const uint32_t pool = mask ? masked_rerank_pool(qp) : 0u;        // masked: ids per result list
+  if (mask && (use_filter || k > PANN_WAVE)) { set_error("pann_batch_search_masked_rerank: no sketch filter, k <= 64"); return PANN_ERR_UNSUPPORTED; }
+  const Scratch s = cut_scratch(quant, nq, mask ? pool : beam, normalize_first, use_filter, scratch);
 
   // ---- 1. the queries ----
   const size_t prep_lds = normalize_first ? (size_t)d * 4 : 0;
@@ -247,6 +296,12 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
   a.dcap = dcap;
   a.out = pann_search_out{};
   a.out.ids = s.fids; a.out.out_k = beam; a.out.frontier_size = s.fsize;
+  uint32_t* rcount = s.fsize;                      // masked: the lists' lengths, in the caller's array when there is one
+  if (mask) {
+    if (mask->result_count) rcount = mask->result_count;
+    a.out.out_k = pool; a.out.frontier_size = d_out.frontier_size;
+    a.masked = 1; a.allow = mask->allow; a.allow_stride = mask->stride; a.result_count = rcount; a.allowed_cmps = mask->allowed_cmps;
+  }
   a.out.visited_count = d_out.visited_count; a.out.dist_cmps = d_out.dist_cmps;
   a.filter = use_filter ? 1 : 0;
   if (use_filter) { a.sketch_queries = s.sk; a.sq_stride = s.sk_stride; a.pruned_cmps = d_out.pruned_cmps; }
@@ -263,7 +318,9 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
   R.kcap = R.want;
   R.qbytes = (uint32_t)query_lds_bytes(full);
   R.out_ids = d_out.ids; R.out_dists = d_out.dists; R.out_fsize = d_out.frontier_size; R.status = status;
-  const bool reg = std::max(R.want, k) <= PANN_WAVE;
+  // masked: the lists (pool <= 64 ids each) and their lengths; the search has written frontier_size itself
+  if (mask) { R.beam = pool; R.fsize = rcount; R.want = R.kcap = pool; R.out_fsize = nullptr; }
+  const bool reg = std::max(R.want, k) <= PANN_WAVE;       // always true for the masked form
   const size_t wave_lds = (size_t)R.qbytes + PANN_WAVE * 4;
   uint32_t waves = RR_WAVES;                       // rows of a thousand floats and more: fewer queries per workgroup, as rerank_kernel
   while (waves > 1 && waves * wave_lds > 64 * 1024) waves >>= 1;
@@ -275,8 +332,14 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
                                 dim3(waves * PANN_WAVE), lds, st, R);                                                              \
     else hipLaunchKernelGGL((rerank_frontier_kernel<MT, L, N1, false>), dim3((uint32_t)nq), dim3(PANN_WAVE), lds, st, R);          \
   } while (0)
-  if (full.metric == PANN_L2) PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_L2, CALL_RF);
+#define CALL_RL(DT, MT, L, N1)                                                                                                    \
+  hipLaunchKernelGGL((rerank_list_kernel<MT, L, N1>), dim3((uint32_t)((nq + waves - 1) / waves)), dim3(waves * PANN_WAVE), lds, st, R)
+  if (mask) {
+    if (full.metric == PANN_L2) PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_L2, CALL_RL);
+    else PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_MIPS, CALL_RL);
+  } else if (full.metric == PANN_L2) PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_L2, CALL_RF);
   else PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_MIPS, CALL_RF);
+#undef CALL_RL
 #undef CALL_RF
   PANN_HIP(hipGetLastError());
   if (d_out.status) PANN_HIP(hipMemcpyAsync(d_out.status, status, 4, hipMemcpyDeviceToDevice, st));

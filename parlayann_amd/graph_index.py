@@ -5,6 +5,7 @@ classes python/module.cpp registers (:50-57,150-155), over the C-ABI.
     .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None) -> (uint32[nq,knn], float32[nq,knn])
     .single_search(q, knn, beam_width, quant, visit_limit)               -> uint32[knn]
     .batch_search_from_string(queries_path, knn, beam_width, quant=False, visit_limit=-1)
+    .batch_search_masked(queries, knn, beam_width, allow, quant=False, visit_limit=-1)   this project's own: masked results
     .check_recall(queries_file, gt_file, neighbors, k)   prints "Recall: x"
 """
 import numpy as np
@@ -85,7 +86,8 @@ class GraphIndex:
             # points, results = the best allowed points it compared.  Rows may be short (padding 0xFFFFFFFF / +inf), so the
             # k-results check of the plain path does not apply.  Not in the quantised or rerank paths.
             if quant and self.use_quantization:
-                raise ValueError("allow= goes with quant=False: the quantised and rerank paths have no masked form")
+                raise ValueError("allow= goes with quant=False: the quantised and rerank paths have no masked form here "
+                                 "(batch_search_masked(..., quant=True) is the fused masked search)")
             r = self.index.batch_search_masked(queries, allow=allow, out_k=knn, **qp)
             return r["ids"], r["dists"]
         if not (quant and self.use_quantization):
@@ -113,6 +115,37 @@ class GraphIndex:
     def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None):
         """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned"""
         return self._search(queries, knn, beam_width, quant, visit_limit, allow)
+
+    def _search_masked(self, queries, knn, beam_width, allow, quant, visit_limit):
+        """Masked searches (this project's own, DESIGN.md "Masked search").  Rows may be short (padding 0xFFFFFFFF / +inf):
+        a short row is an answer under a mask, so the k-results check of the plain paths does not apply."""
+        if allow is None:
+            raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
+        if not (quant and self.use_quantization):        # one-byte points, or the float table: the plain masked search
+            return self._search(queries, knn, beam_width, False, visit_limit, allow)
+        if self.second_level is not None:
+            raise ValueError("quant=True masked searches have no second level: a mask together with the sketch filter is not "
+                             "supported (build the index without second_level=)")
+        queries = np.ascontiguousarray(queries, dtype=self.T)
+        qp = self._qp(knn, beam_width, visit_limit)
+        if self.metric == "Euclidian" and self.quant_bits == 8 and self.eparams.identity:   # slope == 1: the u8 copy, as _search
+            qq = quantize.device_quantize_rows(queries, self.qparams, device=self.device)
+            r = self.q_index.batch_search_masked(qq, allow=allow, out_k=knn, **qp)
+            return r["ids"], r["dists"]
+        # the fused masked call: masked search of the quantised copy, exact rerank of its result list on the float handle
+        r = self.index.search_rerank(self.q_index, self.qparams, queries, normalize_first=self.metric != "Euclidian",
+                                     rerank_factor=100, allow=allow, **qp)
+        return r["ids"], r["dists"]
+
+    def batch_search_masked(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1):
+        """Only allowed points are returned (allow: an allow bitmap or boolean mask, DeviceIndex.batch_search_masked).
+        quant=False, or one-byte points: batch_search(..., allow=).  quant=True on float points: the masked search of the
+        quantised copy (quant_bits 8 or 4) with an exact rerank of its result list, in one call on the device
+        (DeviceIndex.search_rerank(allow=)); not with second_level=."""
+        return self._search_masked(queries, knn, beam_width, allow, quant, visit_limit)
+
+    def batch_search_masked_from_string(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1):
+        return self._search_masked(io.read_bin(queries, self.T), knn, beam_width, allow, quant, visit_limit)
 
     def single_search(self, q, knn, beam_width, quant, visit_limit):
         ids, _ = self._search(np.asarray(q)[None, :], knn, beam_width, quant, visit_limit)

@@ -423,13 +423,17 @@ class DeviceIndex:
                            rerank_factor=rerank_factor, pad=1.0)
 
     def search_rerank(self, quant, qparams, queries, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
-                      normalize_first=False, use_filter=False, rerank_factor=100):
+                      normalize_first=False, use_filter=False, rerank_factor=100, allow=None):
         """pann_batch_search_rerank on this (float32) index: `queries` (float32 rows) are quantised with `qparams` on the
         device, searched on `quant` (the one-byte DeviceIndex of quantized(); use_filter: through the sketch attached to it),
         and the first min(k * rerank_factor, frontier size) frontier ids are re-scored here and sorted.  normalize_first:
         every query goes through Point::normalize first, and the rerank scores against the normalised row.  Returns a dict
         of numpy arrays: ids, dists (nq x k), frontier_size, visited_count, dist_cmps, status (PANN_STATUS_* bits; a query
-        with fewer than k frontier entries sets PANN_STATUS_SHORT_FRONTIER and pads its row), pruned_cmps with use_filter."""
+        with fewer than k frontier entries sets PANN_STATUS_SHORT_FRONTIER and pads its row), pruned_cmps with use_filter.
+        allow (an allow bitmap or boolean mask, as batch_search_masked): pann_batch_search_masked_rerank -- the masked search
+        of quant with a result list of min(k * rerank_factor, beam, 64) allowed points, all of them re-scored here, k kept
+        (DESIGN.md "Masked search on the fused path").  The dict gains result_count (length of the quantised list) and
+        allowed_cmps; a short row is padded and raises no status bit."""
         q = self._queries(queries)
         nq = len(q)
         qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
@@ -442,6 +446,18 @@ class DeviceIndex:
                         visited_count=_ptr(res["visited_count"]), dist_cmps=_ptr(res["dist_cmps"]),
                         pruned_cmps=_ptr(res.get("pruned_cmps")), status=_ptr(res["status"]))
         starts = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
+        if allow is not None:
+            allow = pack_allow(allow, self.n)
+            if allow.ndim == 2 and allow.shape[0] != nq:
+                raise ValueError("per-query allow rows must be nq x W")
+            res["result_count"] = np.empty(nq, np.uint32)
+            res["allowed_cmps"] = np.empty(nq, np.uint32)
+            check(self._lib.pann_batch_search_masked_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q),
+                                                            1 if normalize_first else 0, 1 if use_filter else 0, _ptr(starts),
+                                                            len(starts), C.byref(qp), _ptr(allow),
+                                                            allow.shape[1] if allow.ndim == 2 else 0, C.byref(out),
+                                                            _ptr(res["result_count"]), _ptr(res["allowed_cmps"])))
+            return res
         check(self._lib.pann_batch_search_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q),
                                                  1 if normalize_first else 0, 1 if use_filter else 0, _ptr(starts), len(starts),
                                                  C.byref(qp), C.byref(out)))
@@ -450,15 +466,24 @@ class DeviceIndex:
     def search_rerank_dev(self, quant, qparams, d_queries_ptr, nq, q_stride_bytes, d_starts_ptr, nstarts, d_ids_ptr, d_dists_ptr,
                           k=10, beam=64, cut=1.35, limit=None, degree_limit=None, normalize_first=False, use_filter=False,
                           rerank_factor=100, d_frontier_size_ptr=None, d_visited_count_ptr=None, d_dist_cmps_ptr=None,
-                          d_pruned_cmps_ptr=None, d_status_ptr=None, stream_ptr=None):
+                          d_pruned_cmps_ptr=None, d_status_ptr=None, stream_ptr=None, d_allow_ptr=None, allow_stride_words=0,
+                          d_result_count_ptr=None, d_allowed_cmps_ptr=None):
         """pann_batch_search_rerank_dev: the same on raw device addresses (integers), enqueued on `stream_ptr` (a hipStream_t as
         an integer; None / 0 = the device's default stream).  Nothing is synchronised: read the outputs after the stream has
-        been.  The first call grows quant's scratch."""
+        been.  The first call grows quant's scratch.  d_allow_ptr (packed bitmap rows on the device, allow_stride_words 0 =
+        one shared row): pann_batch_search_masked_rerank_dev, with the two optional per-query outputs."""
         qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
         vp = lambda a: C.c_void_p(a or None)
         out = RerankOut(ids=vp(d_ids_ptr), dists=vp(d_dists_ptr), frontier_size=vp(d_frontier_size_ptr),
                         visited_count=vp(d_visited_count_ptr), dist_cmps=vp(d_dist_cmps_ptr), pruned_cmps=vp(d_pruned_cmps_ptr),
                         status=vp(d_status_ptr))
+        if d_allow_ptr is not None:
+            check(self._lib.pann_batch_search_masked_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq,
+                                                                q_stride_bytes, 1 if normalize_first else 0, 1 if use_filter else 0,
+                                                                vp(d_starts_ptr), nstarts, C.byref(qp), vp(d_allow_ptr),
+                                                                allow_stride_words, C.byref(out), vp(d_result_count_ptr),
+                                                                vp(d_allowed_cmps_ptr), vp(stream_ptr)))
+            return
         check(self._lib.pann_batch_search_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
                                                      1 if normalize_first else 0, 1 if use_filter else 0, vp(d_starts_ptr), nstarts,
                                                      C.byref(qp), C.byref(out), vp(stream_ptr)))

@@ -14,6 +14,16 @@ Every step has a time limit, but it is a Python alarm: it ends a step that is sl
 Run the tool under `timeout -k 10 <seconds>` so that a hang ends the process too.
 
     python tools/masked_time.py [--n 1000000] [--nq 10000] [--steps 20] [--fractions 1.0,0.9,0.5,0.1] [--json out.json]
+
+--rerank: the same question for the fused quantised search with exact rerank (DESIGN.md "Masked search on the fused path").  The
+tools/rerank_time.py setup -- 1M x 128 f32 (datasets.deep_like x 2), Vamana R = 64 L = 128, 10 000 resident queries, beam 64,
+k = 10, rerank_factor 100 -- with pann_batch_search_rerank_dev and pann_batch_search_masked_rerank_dev timed beside each other
+at 100 %, 50 % and 10 % allowed; recall@10 of the masked call against the exact allowed neighbours, and of the post-filter
+baseline (the plain fused call at k = 64, disallowed ids thrown away on the host, the first 10 kept).  The fused masked ids must
+equal those of the composition (pann_quantize_rows, pann_batch_search_masked with out_k = 64, pann_rerank); the tool stops
+otherwise.
+
+    python tools/masked_time.py --rerank [--bits 8|4|8,4] [--fractions 1.0,0.5,0.1] [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -26,11 +36,12 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from parlayann_amd import DeviceIndex, _capi, datasets  # noqa: E402
+from parlayann_amd import DeviceIndex, _capi, datasets, quantize  # noqa: E402
 from parlayann_amd.index import pack_allow  # noqa: E402
 from parlayann_amd.recall import recall_at_k  # noqa: E402
 
 K, BEAM, R, L, ALPHA = 10, 64, 64, 128, 1.15
+RF = 100          # --rerank: rerank_factor
 
 
 class step:
@@ -60,9 +71,15 @@ def main():
     ap.add_argument("--nq", type=int, default=10000)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--fractions", default="1.0,0.9,0.5,0.1")
+    ap.add_argument("--fractions", default=None, help="default 1.0,0.9,0.5,0.1 (--rerank: 1.0,0.5,0.1)")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--rerank", action="store_true", help="the fused quantised search + rerank instead of the plain search")
+    ap.add_argument("--bits", default="8", help="--rerank: bits per coordinate of the quantised copy: 8, 4 or 8,4 (one build for both)")
     a = ap.parse_args()
+    if a.fractions is None:
+        a.fractions = "1.0,0.5,0.1" if a.rerank else "1.0,0.9,0.5,0.1"
+    if a.rerank:
+        return main_rerank(a)
     import torch
     n, d, nq = a.n, a.d, a.nq
     with step("data", 300):
@@ -153,6 +170,111 @@ def main():
         with open(a.json, "w") as f:
             json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, steps=a.steps, rows=rows), f, indent=1)
     ix.close()
+
+
+def main_rerank(a):
+    import torch
+    n, d, nq = a.n, a.d, a.nq
+    bits_list = [int(b) for b in a.bits.split(",")]
+    assert all(b in (8, 4) for b in bits_list)
+    with step("data", 300):                       # real-valued, so that the quantiser is not the identity
+        X = (datasets.deep_like(n, d, seed=1) * 2.0).astype(np.float32)
+        Q = (datasets.deep_like(nq, d, seed=2) * 2.0).astype(np.float32)
+    with step(f"upload + build R={R} L={L}", 900):
+        full = DeviceIndex(X, max_degree=R, metric="Euclidian")
+        full.vamana_build(R, L, 1.2, num_passes=1, seed=3)
+    t_q = torch.from_numpy(Q).cuda()
+    t_st = torch.zeros(1, dtype=torch.int32, device="cuda")
+    t_ids = {k: torch.zeros((nq, k), dtype=torch.int32, device="cuda") for k in (K, BEAM)}
+    t_d = {k: torch.zeros((nq, k), dtype=torch.float32, device="cuda") for k in (K, BEAM)}
+    t_rc, t_ac, t_dc = (torch.zeros(nq, dtype=torch.int32, device="cuda") for _ in range(3))
+    t_status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        stream.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+        with torch.cuda.stream(stream):
+            for e0, e1 in ev:
+                e0.record(stream); fn(); e1.record(stream)
+        stream.synchronize()
+        ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+        assert int(t_status.cpu()[0]) == 0
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    truth = {}          # fraction -> (allow, gt ids, gt dists): shared by the bit widths
+    out = []
+    for bits in bits_list:
+        with step(f"quantise to {bits} bits", 120):
+            quant, qparams = full.quantized("euclid_u8" if bits == 8 else "euclid_u4")
+            assert not qparams.identity
+
+        def fused_step(k=K, t_allow=None):
+            kw = {} if t_allow is None else dict(d_allow_ptr=t_allow.data_ptr(), allow_stride_words=0, d_result_count_ptr=t_rc.data_ptr(),
+                                                 d_allowed_cmps_ptr=t_ac.data_ptr())
+            full.search_rerank_dev(quant, qparams, t_q.data_ptr(), nq, 4 * d, t_st.data_ptr(), 1, t_ids[k].data_ptr(), t_d[k].data_ptr(),
+                                   k=k, beam=BEAM, limit=n, degree_limit=R, rerank_factor=RF, d_dist_cmps_ptr=t_dc.data_ptr(),
+                                   d_status_ptr=t_status.data_ptr(), stream_ptr=stream.cuda_stream, **kw)
+
+        rows = []
+        for frac in [float(f) for f in a.fractions.split(",")]:
+            if frac not in truth:
+                allow = np.ones(n, bool) if frac >= 1.0 else np.random.default_rng(int(frac * 1000)).random(n) < frac
+                live = np.flatnonzero(allow).astype(np.uint32)
+                with step(f"allow {frac:.0%}: ground truth over {len(live)} allowed points", 600):
+                    sub = DeviceIndex(X[live], max_degree=4)
+                    gt_local, gd = sub.bruteforce_knn(Q, K)
+                    sub.close()
+                truth[frac] = (allow, live[gt_local], gd)
+            allow, gt, gd = truth[frac]
+            packed = pack_allow(allow, n)
+            t_allow = torch.from_numpy(packed.view(np.int32)).cuda()
+            torch.cuda.synchronize()
+            with step(f"{bits} bits, allow {frac:.0%}: timing", 300):
+                p_ms = timed(fused_step)
+                m_ms = timed(lambda: fused_step(K, t_allow))
+                ids_m = t_ids[K].cpu().numpy().view(np.uint32).copy()
+                rc, ac, dc = (t.cpu().numpy().view(np.uint32).copy() for t in (t_rc, t_ac, t_dc))
+                if not allow[ids_m[ids_m != 0xFFFFFFFF]].all():
+                    print("ERROR: the fused masked search returned a disallowed id", flush=True)
+                    sys.exit(1)
+            with step(f"{bits} bits, allow {frac:.0%}: composition", 300):
+                qq = quantize.device_quantize_rows(Q, qparams)
+                r = quant.batch_search_masked(qq, allow=packed, k=K, beam=BEAM, out_k=BEAM, limit=n, degree_limit=R)
+                ids_c, _ = full.rerank(Q, r["ids"], r["result_count"], K, resort=True)
+                ids_c[np.arange(K)[None, :] >= r["result_count"][:, None]] = 0xFFFFFFFF
+                if not np.array_equal(ids_c, ids_m):
+                    print("ERROR: the fused masked ids differ from the composition's", flush=True)
+                    sys.exit(1)
+            with step(f"{bits} bits, allow {frac:.0%}: post-filter baseline", 300):
+                fused_step(BEAM); stream.synchronize()
+                front = t_ids[BEAM].cpu().numpy().view(np.uint32)
+                ids_p = np.full((nq, K), 0xFFFFFFFF, np.uint32)
+                for q in range(nq):
+                    row = front[q][front[q] != 0xFFFFFFFF]
+                    kept = row[allow[row]][:K]
+                    ids_p[q, :len(kept)] = kept
+            row = dict(bits=bits, allow=frac, plain_ms=p_ms[0], plain_ms_min=p_ms[1], plain_ms_max=p_ms[2], masked_ms=m_ms[0],
+                       masked_ms_min=m_ms[1], masked_ms_max=m_ms[2], plain_qps=nq / p_ms[0] * 1e3, masked_qps=nq / m_ms[0] * 1e3,
+                       recall10_masked=recall_at_k(ids_m, gt, gd, K), recall10_post_filter=recall_at_k(ids_p, gt, gd, K),
+                       short_rows=int((rc < K).sum()), result_count=float(rc.mean()), allowed_cmps=float(ac.mean()),
+                       dist_cmps=float(dc.mean()))
+            rows.append(row)
+            print(f"  {bits} bits  allow {frac:5.0%}  fused plain {p_ms[0]:8.3f} ms (min {p_ms[1]:.3f}, max {p_ms[2]:.3f}) QPS "
+                  f"{row['plain_qps']:9.0f}   fused masked {m_ms[0]:8.3f} ms (min {m_ms[1]:.3f}, max {m_ms[2]:.3f}) QPS "
+                  f"{row['masked_qps']:9.0f}  ratio {row['masked_qps'] / row['plain_qps']:.3f}   recall@10 masked "
+                  f"{row['recall10_masked']:.4f} post-filter {row['recall10_post_filter']:.4f}   rows shorter than k "
+                  f"{row['short_rows']}  list {row['result_count']:.1f}  allowed cmps/q {row['allowed_cmps']:.1f} of "
+                  f"{row['dist_cmps']:.1f}   fused masked ids == composition", flush=True)
+        out.extend(rows)
+        quant.close()
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, rerank_factor=RF, steps=a.steps, rows=out), f, indent=1)
+    full.close()
 
 
 if __name__ == "__main__":
