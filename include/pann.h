@@ -666,6 +666,41 @@ int pann_batch_search_masked_rerank(pann_index* full, pann_index* quant, const p
                                     uint64_t allow_stride_words, const pann_rerank_out* out, uint32_t* out_result_count,
                                     uint32_t* out_allowed_cmps);
 
+/* ---- exact kNN under an allow bitmap (DESIGN.md "Exact masked kNN") ----  This project's own; what a caller turns to when a mask
+ * is so selective that the masked searches above see too few allowed points (out_allowed_cmps says so).  No graph is walked: the
+ * allowed points are scored one by one.  allow / allow_stride_words: the bitmap of pann_batch_search_masked -- stride 0: one
+ * bitmap for the whole batch; >= ceil(n / 32): query q reads row q; bits at positions >= n are ignored.
+ * Row q of out_ids / out_dists holds the min(k, c_q) allowed points nearest to query q, sorted by (dist, id), c_q = the number of
+ * allowed points; unused slots 0xFFFFFFFF / +inf.  out_counts (optional, nq): min(k, c_q).  A row with no allowed point is an
+ * answer, not an error: all padding, count 0; an all-empty shared bitmap launches no distance kernel.
+ * Exact wherever pann_bruteforce_knn is: the one-byte types, integer-valued floats, exact-float-order mode; in default float mode
+ * the rounding caveat of DESIGN.md "Float summation order" applies.
+ *   shared bitmap (stride 0), k <= 128: the bitmap is compacted on the device into the ascending list of allowed ids, and the
+ *     dense kernels of pann_bruteforce_knn run over that list ("gt_pieces" is honoured).  The result equals pann_bruteforce_knn
+ *     on an index made of the allowed rows in ascending id order, ids mapped back, bit for bit.
+ *   per-query bitmaps, k <= 64: one wavefront per query walks its row.  Every returned distance equals, bit for bit and on any
+ *     data, what pann_query_distances returns for the same (query, id) pair (the same arithmetic, exact-float-order flag included).
+ * Status: NULL bitmap, queries or outputs, a stride between 1 and ceil(n / 32) - 1, a query stride shorter than a row, k == 0 ->
+ * PANN_ERR_BAD_ARG; k > 64 with per-query bitmaps, k > 128 with a shared one, a four-bit handle -> PANN_ERR_UNSUPPORTED;
+ * nq == 0 -> PANN_OK.  Nothing is written on an error.
+ * Host pointers: the queries and the bitmap rows (packed to ceil(n / 32) words each) go up in one transfer, as
+ * pann_batch_search_masked stages them -- the same memory note applies to per-query rows --, the outputs come back in one. */
+int pann_bruteforce_knn_masked(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                               const uint32_t* allow, uint64_t allow_stride_words, uint32_t* out_ids, float* out_dists,
+                               uint32_t* out_counts);
+/* Device pointers throughout, launched on `stream`.  Per-query bitmaps: no synchronisation and no allocation.  Shared bitmap:
+ * SYNCHRONISES the stream once -- the number of allowed points has to come back before the list can be allocated and the
+ * distance launch sized -- and grows the handle's scratch to 4 bytes per allowed point on first use. */
+int pann_bruteforce_knn_masked_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                   const uint32_t* d_allow, uint64_t allow_stride_words, uint32_t* d_out_ids, float* d_out_dists,
+                                   uint32_t* d_out_counts, void* stream);
+/* d_counts[r] = number of allowed points of bitmap row r, r < rows: rows x ceil(n / 32) words, allow_stride_words apart; bits at
+ * positions >= n are ignored.  allow_stride_words == 0: one row (`rows` is not read).  Device pointers, on `stream` of the
+ * current device; no synchronisation, no allocation.  n < 2^32.  NULL pointers, a stride between 1 and ceil(n / 32) - 1 ->
+ * PANN_ERR_BAD_ARG. */
+int pann_allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t allow_stride_words, uint32_t* d_counts,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -205,6 +205,11 @@ SIGNATURES = {
                                                       C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams),
                                                       C.c_void_p, C.c_uint64, C.POINTER(RerankOut), C.c_void_p, C.c_void_p,
                                                       C.c_void_p]),
+    "pann_bruteforce_knn_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_bruteforce_knn_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_allow_count_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

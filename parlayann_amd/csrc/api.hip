@@ -1102,6 +1102,25 @@ int pann_leaf_knn(pann_index* idx, const uint32_t* ids, uint32_t N, uint32_t m, 
   return pann_leaf_knn_batch(idx, ids, off, 1, m, out_ids, out_dists);
 }
 
+// B is cut into nsplit pieces per A tile.  Every piece warms up its own top-k lists (about k * ln(piece / k) + k list inserts per
+// query: 10K x 1M, k = 100 spent 7.5 G instructions there at 14 pieces), and at k = 100 the lists leave room for ONE workgroup
+// per CU, so what matters is how evenly ntiles * nsplit workgroups fill whole rounds of the 256 CUs: the smallest count (<= 8,
+// or enough to reach every CU when there are few queries) with the best fill wins (10K queries: 157 tiles x 3 = 1.84 rounds,
+// 43 ms; x 1: 53 ms; x 14: 68 ms).  slots: 256 x the workgroups a CU holds (1 for the LDS-list kernels); nb: B rows.
+static uint32_t choose_gt_pieces(const pann_index* idx, uint32_t ntiles, double slots, uint64_t nb) {
+  uint32_t want = 1;
+  double best = -1.0;
+  const uint32_t smax = std::max<uint32_t>(8, ((uint32_t)slots + ntiles - 1) / ntiles);
+  for (uint32_t sp = 1; sp <= smax; sp++) {
+    const double wgs = (double)ntiles * sp;
+    const double fill = wgs / (slots * std::ceil(wgs / slots)) - 0.02 * std::min<uint32_t>(sp, 8);
+    if (fill > best + 1e-9) { best = fill; want = sp; }
+  }
+  const uint32_t env_split = idx->gt_pieces;      // pann_index_set_option("gt_pieces")
+  const uint32_t nsplit = std::max<uint32_t>(1, std::min<uint32_t>(env_split ? env_split : want, (uint32_t)((nb + 4095) / 4096)));
+  return std::min<uint32_t>(nsplit, 64);
+}
+
 int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                         uint32_t* out_ids, float* out_dists) {
   if (int rc = check_idx_no4(idx, "pann_bruteforce_knn")) return rc;
@@ -1115,25 +1134,7 @@ int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint6
   if (int rc = idx->stage[7].ensure(nq * k * 4)) return rc;
   PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, hipMemcpyHostToDevice, st));
   const uint32_t ntiles = (uint32_t)((nq + 63) / 64);
-  // B is cut into nsplit pieces per A tile.  Every piece warms up its own top-k lists (about k * ln(piece / k) + k list inserts per
-  // query: 10K x 1M, k = 100 spent 7.5 G instructions there at 14 pieces), and at k = 100 the lists leave room for ONE workgroup
-  // per CU, so what matters is how evenly ntiles * nsplit workgroups fill whole rounds of the 256 CUs: the smallest count (<= 8,
-  // or enough to reach every CU when there are few queries) with the best fill wins (10K queries: 157 tiles x 3 = 1.84 rounds,
-  // 43 ms; x 1: 53 ms; x 14: 68 ms)
-  uint32_t want = 1;
-  {
-    double best = -1.0;
-    const double slots = (double)dense_gt_slots(idx->ix, k);       // 256 x the workgroups a CU holds (1 for the LDS-list kernels)
-    const uint32_t smax = std::max<uint32_t>(8, ((uint32_t)slots + ntiles - 1) / ntiles);
-    for (uint32_t sp = 1; sp <= smax; sp++) {
-      const double wgs = (double)ntiles * sp;
-      const double fill = wgs / (slots * std::ceil(wgs / slots)) - 0.02 * std::min<uint32_t>(sp, 8);
-      if (fill > best + 1e-9) { best = fill; want = sp; }
-    }
-  }
-  const uint32_t env_split = idx->gt_pieces;      // pann_index_set_option("gt_pieces")
-  uint32_t nsplit = std::max<uint32_t>(1, std::min<uint32_t>(env_split ? env_split : want, (uint32_t)((idx->ix.n + 4095) / 4096)));
-  nsplit = std::min<uint32_t>(nsplit, 64);
+  const uint32_t nsplit = choose_gt_pieces(idx, ntiles, (double)dense_gt_slots(idx->ix, k), idx->ix.n);
   if (int rc = dense_topk_dev(idx->ix, idx->ws2, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nullptr, nullptr, nullptr,
                               nullptr, nullptr, nullptr, ntiles, nq, idx->ix.n, nsplit, k, 0, idx->stage[6].as<uint32_t>(),
                               idx->stage[7].as<float>())) return rc;
@@ -1143,6 +1144,114 @@ int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint6
   return PANN_OK;
 }
 
+// ---- exact kNN under an allow bitmap (masked_knn.hip, DESIGN.md "Exact masked kNN") ----
+
+int pann_allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t allow_stride_words, uint32_t* d_counts,
+                         void* stream) {
+  const uint64_t words = (n + 31) / 32;
+  if (!d_allow || !d_counts) { set_error("pann_allow_count_dev: null argument"); return PANN_ERR_BAD_ARG; }
+  if (n > 0xFFFFFFFFull) { set_error("pann_allow_count_dev: n must be < 2^32"); return PANN_ERR_BAD_ARG; }
+  if (allow_stride_words != 0 && allow_stride_words < words) {
+    set_error("pann_allow_count_dev: allow_stride_words must be 0 (one row) or at least ceil(n / 32) = " + std::to_string(words));
+    return PANN_ERR_BAD_ARG;
+  }
+  return allow_count_dev(d_allow, n, allow_stride_words ? rows : 1, allow_stride_words, d_counts, (hipStream_t)stream);
+}
+
+// everything that is refused before anything is launched, allocated or written (host and device entry alike)
+static int masked_knn_checks(const pann_index* idx, const char* fn, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                             const uint32_t* allow, uint64_t stride, const uint32_t* out_ids, const float* out_dists, bool* done) {
+  *done = false;
+  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (nq == 0) { *done = true; return PANN_OK; }
+  const uint64_t words = (idx->ix.n + 31) / 32;
+  if (!queries || !out_ids || !out_dists) { set_error(std::string(fn) + ": null argument"); return PANN_ERR_BAD_ARG; }
+  if (!allow) { set_error(std::string(fn) + ": null allow bitmap"); return PANN_ERR_BAD_ARG; }
+  if (stride != 0 && stride < words) {
+    set_error(std::string(fn) + ": allow_stride_words must be 0 (one shared bitmap) or at least ceil(n / 32) = " + std::to_string(words));
+    return PANN_ERR_BAD_ARG;
+  }
+  if (q_stride_bytes < idx->ix.dbytes) { set_error(std::string(fn) + ": query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  if (k == 0) { set_error(std::string(fn) + ": k == 0"); return PANN_ERR_BAD_ARG; }
+  if (k > (stride ? 64u : 128u)) {
+    set_error(std::string(fn) + (stride ? ": k > 64 with per-query bitmaps is not supported" : ": k > 128 is not supported"));
+    return PANN_ERR_UNSUPPORTED;
+  }
+  return PANN_OK;
+}
+
+// both routes on device pointers, after the checks.  Shared bitmap: SYNCHRONISES st (the allowed count sizes the launch).
+static int masked_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, const uint32_t* d_allow,
+                          uint64_t stride, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+  const DeviceIndex& ix = idx->ix;
+  if (stride) return masked_scan_dev(ix, st, d_q, q_stride_bytes, nq, d_allow, stride, k, d_ids, d_dists, d_counts);
+  if (int rc = idx->ws3.ensure(allow_compact_scratch_bytes(ix.n))) return rc;
+  const uint32_t* d_total = nullptr;
+  if (int rc = allow_compact_count_dev(d_allow, ix.n, (uint32_t*)idx->ws3.buf, &d_total, st)) return rc;
+  uint32_t count = 0;
+  PANN_HIP(hipMemcpyAsync(&count, d_total, 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  if (count == 0) return knn_pad_dev(d_ids, d_dists, d_counts, nq, k, 0, 1, st);       // an empty mask: no distance kernel
+  if (int rc = idx->ws4.ensure((size_t)count * 4)) return rc;
+  uint32_t* d_list = (uint32_t*)idx->ws4.buf;
+  if (int rc = allow_compact_scatter_dev(d_allow, ix.n, (const uint32_t*)idx->ws3.buf, d_list, count, st)) return rc;
+  // the list as B rows makes the launch one of the LDS-list kernels: one workgroup per CU
+  const uint32_t ntiles = (uint32_t)((nq + 63) / 64);
+  const uint32_t nsplit = choose_gt_pieces(idx, ntiles, 256.0, count);
+  if (int rc = dense_topk_dev(ix, idx->ws2, st, d_q, q_stride_bytes, nullptr, d_list, nullptr, nullptr, nullptr, nullptr, ntiles, nq,
+                              count, nsplit, k, 0, d_ids, d_dists)) return rc;
+  return knn_pad_dev(nullptr, nullptr, d_counts, nq, k, std::min(count, k), 0, st);
+}
+
+int pann_bruteforce_knn_masked_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                   const uint32_t* d_allow, uint64_t allow_stride_words, uint32_t* d_out_ids, float* d_out_dists,
+                                   uint32_t* d_out_counts, void* stream) {
+  bool done;
+  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_masked_dev", d_queries, nq, q_stride_bytes, k, d_allow, allow_stride_words,
+                                 d_out_ids, d_out_dists, &done)) return rc;
+  if (done) return PANN_OK;
+  DeviceGuard g(idx->device);
+  return masked_knn_run(idx, (const uint8_t*)d_queries, nq, q_stride_bytes, k, d_allow, allow_stride_words, d_out_ids, d_out_dists,
+                        d_out_counts, (hipStream_t)stream);
+}
+
+int pann_bruteforce_knn_masked(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                               const uint32_t* allow, uint64_t allow_stride_words, uint32_t* out_ids, float* out_dists,
+                               uint32_t* out_counts) {
+  bool done;
+  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_masked", queries, nq, q_stride_bytes, k, allow, allow_stride_words, out_ids,
+                                 out_dists, &done)) return rc;
+  if (done) return PANN_OK;
+  DeviceGuard g(idx->device);
+  hipStream_t st = idx->stream;
+  const DeviceIndex& ix = idx->ix;
+  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // in: the queries and the bitmap rows, packed to ceil(n / 32) words each, in one transfer (as pann_batch_search_masked)
+  const size_t qbytes = (nq - 1) * q_stride_bytes + ix.dbytes;
+  const size_t mwords = (size_t)((ix.n + 31) / 32), mrows = allow_stride_words ? (size_t)nq : 1;
+  const size_t off_mask = al(qbytes + 16), in_bytes = off_mask + al(mrows * mwords * 4);
+  if (int rc = idx->pin_in.ensure(in_bytes)) return rc;
+  if (int rc = idx->stage[2].ensure(in_bytes)) return rc;
+  std::memcpy(idx->pin_in.p, queries, qbytes);
+  for (size_t r = 0; r < mrows; r++)
+    std::memcpy((uint8_t*)idx->pin_in.p + off_mask + r * mwords * 4, allow + r * allow_stride_words, mwords * 4);
+  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, idx->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
+  // out: ids, dists and counts in one region, one transfer back
+  const size_t row_bytes = (size_t)nq * k * 4;
+  const size_t off_d = al(row_bytes), off_c = off_d + al(row_bytes), out_bytes = off_c + al(nq * 4);
+  if (int rc = idx->stage[4].ensure(out_bytes)) return rc;
+  if (int rc = idx->pin_out.ensure(out_bytes)) return rc;
+  uint8_t* d_out = idx->stage[4].as<uint8_t>();
+  if (int rc = masked_knn_run(idx, idx->stage[2].as<uint8_t>(), nq, q_stride_bytes, k, (const uint32_t*)(idx->stage[2].as<uint8_t>() + off_mask),
+                              allow_stride_words ? mwords : 0, (uint32_t*)d_out, (float*)(d_out + off_d), (uint32_t*)(d_out + off_c), st)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->pin_out.p, d_out, out_bytes, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  const uint8_t* h = (const uint8_t*)idx->pin_out.p;
+  std::memcpy(out_ids, h, row_bytes);
+  std::memcpy(out_dists, h + off_d, row_bytes);
+  if (out_counts) std::memcpy(out_counts, h + off_c, nq * 4);
+  return PANN_OK;
+}
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,
                      const uint32_t* pivot_a, const uint32_t* pivot_b, uint8_t* out_side) {

@@ -1,0 +1,264 @@
+// masked_knn.hip -- exact kNN under an allow bitmap (DESIGN.md "Exact masked kNN"): what a caller falls back to when a mask is
+// so selective that the masked beam search sees too few allowed points.  Two routes, both on the bitmap format of
+// pann_batch_search_masked (ceil(n / 32) words per row, bits at positions >= n ignored):
+//
+//   shared bitmap      allow_block_count_kernel   popcount of every block of 256 words
+//                      allow_block_scan_kernel    exclusive scan over the blocks (one workgroup), total = allowed points
+//                      allow_scatter_kernel       every word's set bits to their ranks: the ascending list of allowed ids
+//                      the list then is the b_ids of dense_topk_dev (dense.hip), the queries its external A rows.
+//   per-query bitmaps  masked_scan_kernel         one wave per query walks its row 64 words (2 048 positions) at a time, ranks
+//                                                 the set bits, scores the allowed ids with gather_tile -- the arithmetic of
+//                                                 query_distances_kernel, exact-float-order mode included -- and keeps the best
+//                                                 k <= 64 keys as one sorted (dist, id) key per lane.
+//
+// allow_count_kernel (pann_allow_count_dev) is the count half alone, per row.
+#include "pann_device.h"
+
+namespace pann {
+namespace {
+
+constexpr uint32_t MK_BLOCK = 256;                 // words (= threads) of one compaction block: 8 192 positions
+constexpr uint32_t MK_CHUNK = PANN_WAVE * 32;      // positions one step of the per-query scan covers
+
+// word w of a bitmap row of `words` words over n points: bits at positions >= n cleared, 0 past the row
+__device__ __forceinline__ uint32_t allow_word(const uint32_t* __restrict__ row, uint64_t w, uint64_t words, uint64_t n) {
+  if (w >= words) return 0u;
+  uint32_t v = row[w];
+  if (w == words - 1 && (n & 31)) v &= (1u << (n & 31)) - 1u;
+  return v;
+}
+
+// exclusive prefix sum over the lanes of the wave; *total: the sum of all 64
+__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v, int lane, uint32_t* total) {
+  uint32_t s = v;
+#pragma unroll
+  for (int o = 1; o < PANN_WAVE; o <<= 1) {
+    const uint32_t t = __shfl_up(s, o);
+    if (lane >= o) s += t;
+  }
+  *total = __shfl(s, PANN_WAVE - 1);
+  return s - v;
+}
+
+// the thread's exclusive rank among the 256 threads of its block, *total: the block's sum (every thread must call)
+__device__ __forceinline__ uint32_t block_excl_scan(uint32_t v, uint32_t* wsum, uint32_t* total) {
+  const int lane = threadIdx.x & (PANN_WAVE - 1), wave = threadIdx.x / PANN_WAVE;
+  uint32_t wt;
+  const uint32_t excl = wave_excl_scan(v, lane, &wt);
+  __syncthreads();                                 // the previous use of wsum has been read
+  if (lane == 0) wsum[wave] = wt;
+  __syncthreads();
+  uint32_t before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < (int)(MK_BLOCK / PANN_WAVE); w++) { before += w < wave ? wsum[w] : 0u; all += wsum[w]; }
+  *total = all;
+  return before + excl;
+}
+
+// counts[row] += allowed points of row (counts zeroed by the caller); grid.x: blocks per row, grid.y strides over the rows
+__global__ void __launch_bounds__(MK_BLOCK) allow_count_kernel(const uint32_t* __restrict__ allow, uint64_t n, uint64_t rows,
+                                                               uint64_t stride, uint32_t* __restrict__ counts) {
+  const uint64_t words = (n + 31) / 32;
+  for (uint64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    const uint32_t* row = allow + r * stride;
+    uint32_t c = 0;
+    for (uint64_t w = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x; w < words; w += (uint64_t)gridDim.x * MK_BLOCK)
+      c += __popc(allow_word(row, w, words, n));
+#pragma unroll
+    for (int o = PANN_WAVE / 2; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    if ((threadIdx.x & (PANN_WAVE - 1)) == 0 && c) atomicAdd(&counts[r], c);
+  }
+}
+
+__global__ void __launch_bounds__(MK_BLOCK) allow_block_count_kernel(const uint32_t* __restrict__ allow, uint64_t n,
+                                                                     uint32_t* __restrict__ block_counts) {
+  __shared__ uint32_t wsum[MK_BLOCK / PANN_WAVE];
+  const uint64_t words = (n + 31) / 32;
+  uint32_t total;
+  (void)block_excl_scan(__popc(allow_word(allow, (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x, words, n)), wsum, &total);
+  if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+}
+
+// block_counts[0 .. nblk) -> their exclusive prefix sums, in place; block_counts[nblk] = the total.  One workgroup.
+__global__ void __launch_bounds__(MK_BLOCK) allow_block_scan_kernel(uint32_t* __restrict__ block_counts, uint32_t nblk) {
+  __shared__ uint32_t wsum[MK_BLOCK / PANN_WAVE];
+  uint32_t carry = 0;
+  for (uint32_t base = 0; base < nblk; base += MK_BLOCK) {
+    const uint32_t i = base + threadIdx.x;
+    uint32_t total;
+    const uint32_t excl = block_excl_scan(i < nblk ? block_counts[i] : 0u, wsum, &total);
+    if (i < nblk) block_counts[i] = carry + excl;
+    carry += total;
+  }
+  if (threadIdx.x == 0) block_counts[nblk] = carry;
+}
+
+// ids[rank of bit] = position of the bit, for every set bit below n: ascending.  cap: entries of ids (the total of the scan)
+__global__ void __launch_bounds__(MK_BLOCK) allow_scatter_kernel(const uint32_t* __restrict__ allow, uint64_t n,
+                                                                 const uint32_t* __restrict__ block_off, uint32_t* __restrict__ ids,
+                                                                 uint32_t cap) {
+  __shared__ uint32_t wsum[MK_BLOCK / PANN_WAVE];
+  const uint64_t words = (n + 31) / 32;
+  const uint64_t w = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+  uint32_t v = allow_word(allow, w, words, n);
+  uint32_t total;
+  uint32_t pos = block_off[blockIdx.x] + block_excl_scan(__popc(v), wsum, &total);
+  const uint32_t first = (uint32_t)(w * 32);
+  while (v) {
+    const uint32_t j = __ffs(v) - 1;
+    v &= v - 1;
+    if (pos < cap) ids[pos] = first + j;
+    pos++;
+  }
+}
+
+// rows of an answer that no kernel computed: pad != 0 fills ids / dists with 0xFFFFFFFF / +inf; counts (optional) = cnt
+__global__ void __launch_bounds__(MK_BLOCK) knn_pad_kernel(uint32_t* __restrict__ ids, float* __restrict__ dists,
+                                                           uint32_t* __restrict__ counts, uint64_t nq, uint32_t k, uint32_t cnt, int pad) {
+  const uint64_t step = (uint64_t)gridDim.x * blockDim.x, i0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pad) for (uint64_t i = i0; i < nq * k; i += step) { ids[i] = SENTINEL; dists[i] = __builtin_inff(); }
+  if (counts) for (uint64_t i = i0; i < nq; i += step) counts[i] = cnt;
+}
+
+struct MaskedScanArgs {
+  PointsView pv; uint32_t dbytes;
+  const uint8_t* q; uint64_t q_stride;
+  const uint32_t* allow; uint64_t allow_stride; uint64_t n;
+  uint32_t k;                                      // <= 64
+  uint32_t* out_ids; float* out_dists; uint32_t* out_counts;
+};
+
+template <int DT, int METRIC, int LPC, bool NCH1>
+__global__ void __launch_bounds__(PANN_WAVE) masked_scan_kernel(MaskedScanArgs P) {
+  const int lane = threadIdx.x;
+  __shared__ uint32_t Lst[MK_CHUNK + PANN_WAVE];   // allowed ids waiting for their distance: < 64 left over + one step's
+  __shared__ uint64_t K[PANN_WAVE];                // keys of the tile just scored
+  extern __shared__ __align__(16) uint8_t smem[];
+  uint4* qlds = reinterpret_cast<uint4*>(smem);
+  const uint64_t qi = blockIdx.x;
+  QReg<DT> qreg{};
+  load_query<DT, LPC, NCH1>(P.q + qi * P.q_stride, P.dbytes, P.pv.nch, qreg, qlds, lane);
+  __syncthreads();
+  const uint32_t* row = P.allow + qi * P.allow_stride;
+  const uint64_t words = (P.n + 31) / 32;
+  uint64_t best = KEY_INF;                         // lane i: the i-th smallest key seen so far
+  uint64_t tau = KEY_INF;                          // the k-th smallest: what a candidate has to beat
+  uint32_t fill = 0, total = 0;
+  uint32_t wnext = allow_word(row, lane, words, P.n);
+  for (uint64_t w0 = 0; w0 < words; w0 += PANN_WAVE) {
+    uint32_t v = wnext;
+    wnext = allow_word(row, w0 + PANN_WAVE + lane, words, P.n);       // in flight while this step is scored
+    const bool last = w0 + PANN_WAVE >= words;
+    uint32_t step_total;
+    uint32_t pos = fill + wave_excl_scan(__popc(v), lane, &step_total);
+    if (step_total == 0 && !last) continue;        // wave-uniform
+    const uint32_t first = (uint32_t)((w0 + lane) * 32);
+    while (v) {
+      const uint32_t j = __ffs(v) - 1;
+      v &= v - 1;
+      Lst[pos++] = first + j;
+    }
+    fill += step_total; total += step_total;
+    wave_lds_sync();
+    // whole tiles of 64 now; what is left waits for the next step, and the last step scores it as a partial tile
+    uint32_t t0 = 0;
+    while (t0 + PANN_WAVE <= fill || (last && t0 < fill)) {
+      const uint32_t mm = min(fill - t0, (uint32_t)PANN_WAVE);
+      gather_tile<DT, METRIC, LPC, NCH1, 4>(P.pv, qreg, qlds, Lst + t0, mm, lane,
+        [&](bool has, uint32_t ci, uint32_t id, float dist) { if (has) K[ci] = make_key(dist, id); });
+      wave_lds_sync();
+      const uint64_t key = lane < (int)mm ? K[lane] : KEY_INF;
+      wave_lds_sync();                             // K is free for the next tile
+      uint64_t mask = __ballot(key < tau);
+      while (mask) {
+        const int src = __ffsll((unsigned long long)mask) - 1;
+        mask &= mask - 1;
+        const uint64_t x = readlane64(key, src);
+        if (x < tau) {                             // sorted insert, one key per lane; ids are unique, so no key repeats
+          const uint64_t prev = __shfl_up(best, 1);
+          best = best < x ? best : ((lane == 0 || prev < x) ? x : prev);
+          tau = readlane64(best, (int)P.k - 1);
+        }
+      }
+      t0 += mm;
+    }
+    const uint32_t rem = fill - t0;                // < 64
+    if (t0 && rem) {
+      const uint32_t keep = lane < (int)rem ? Lst[t0 + lane] : 0u;
+      wave_lds_sync();
+      if (lane < (int)rem) Lst[lane] = keep;
+      wave_lds_sync();
+    }
+    fill = rem;
+  }
+  const uint32_t cnt = min(total, P.k);
+  if (lane < (int)P.k) {
+    const bool ok = lane < (int)cnt;
+    P.out_ids[qi * P.k + lane] = ok ? key_id(best) : SENTINEL;
+    P.out_dists[qi * P.k + lane] = ok ? key_dist(best) : __builtin_inff();
+  }
+  if (lane == 0 && P.out_counts) P.out_counts[qi] = cnt;
+}
+
+inline uint32_t compaction_blocks(uint64_t n) { return (uint32_t)(((n + 31) / 32 + MK_BLOCK - 1) / MK_BLOCK); }
+
+}  // namespace
+
+int allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t stride, uint32_t* d_counts, hipStream_t st) {
+  if (rows == 0) return PANN_OK;
+  PANN_HIP(hipMemsetAsync(d_counts, 0, rows * 4, st));
+  if (n == 0) return PANN_OK;
+  const uint64_t words = (n + 31) / 32;
+  const uint32_t per_row = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((words + 8 * MK_BLOCK - 1) / (8 * MK_BLOCK), 1), 256);
+  hipLaunchKernelGGL(allow_count_kernel, dim3(per_row, (uint32_t)std::min<uint64_t>(rows, 65535)), dim3(MK_BLOCK), 0, st, d_allow, n,
+                     rows, stride, d_counts);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+size_t allow_compact_scratch_bytes(uint64_t n) { return ((size_t)compaction_blocks(n) + 1) * 4; }
+
+int allow_compact_count_dev(const uint32_t* d_allow, uint64_t n, uint32_t* d_scratch, const uint32_t** d_total, hipStream_t st) {
+  const uint32_t nblk = compaction_blocks(n);
+  hipLaunchKernelGGL(allow_block_count_kernel, dim3(nblk), dim3(MK_BLOCK), 0, st, d_allow, n, d_scratch);
+  PANN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(allow_block_scan_kernel, dim3(1), dim3(MK_BLOCK), 0, st, d_scratch, nblk);
+  PANN_HIP(hipGetLastError());
+  *d_total = d_scratch + nblk;
+  return PANN_OK;
+}
+
+int allow_compact_scatter_dev(const uint32_t* d_allow, uint64_t n, const uint32_t* d_scratch, uint32_t* d_ids, uint32_t count,
+                              hipStream_t st) {
+  hipLaunchKernelGGL(allow_scatter_kernel, dim3(compaction_blocks(n)), dim3(MK_BLOCK), 0, st, d_allow, n, d_scratch, d_ids, count);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+int knn_pad_dev(uint32_t* d_ids, float* d_dists, uint32_t* d_counts, uint64_t nq, uint32_t k, uint32_t cnt, int pad, hipStream_t st) {
+  if (nq == 0 || (!pad && !d_counts)) return PANN_OK;
+  const uint64_t work = pad ? nq * k : nq;
+  hipLaunchKernelGGL(knn_pad_kernel, dim3((uint32_t)std::min<uint64_t>((work + MK_BLOCK - 1) / MK_BLOCK, 4096)), dim3(MK_BLOCK), 0, st,
+                     d_ids, d_dists, d_counts, nq, k, cnt, pad);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
+                    uint64_t allow_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
+  if (nq == 0) return PANN_OK;
+  if (k == 0 || k > PANN_WAVE) { set_error("masked scan: k must be in [1,64]"); return PANN_ERR_UNSUPPORTED; }
+  const size_t qb = query_lds_bytes(ix);
+  if (qb > 48 * 1024) { set_error("masked scan: rows too long for the scan's LDS state"); return PANN_ERR_UNSUPPORTED; }
+  MaskedScanArgs P{};
+  P.pv = PointsView{ix.points, ix.pstride, ix.nch, ix.exact}; P.dbytes = ix.dbytes;
+  P.q = d_q; P.q_stride = q_stride; P.allow = d_allow; P.allow_stride = allow_stride; P.n = ix.n; P.k = k;
+  P.out_ids = d_out_ids; P.out_dists = d_out_dists; P.out_counts = d_out_counts;
+#define CALL_MS(DT, MT, L, N1) hipLaunchKernelGGL((masked_scan_kernel<DT, MT, L, N1>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, P)
+  PANN_TYPE_SWITCH(ix, CALL_MS);
+#undef CALL_MS
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+}  // namespace pann

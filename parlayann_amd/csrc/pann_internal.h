@@ -167,6 +167,22 @@ int rerank_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64
                const uint32_t* d_cand, uint32_t c, const uint32_t* d_cnt, uint32_t k, int resort, uint32_t* d_out_ids,
                float* d_out_dists);
 
+// masked_knn.hip: exact kNN under an allow bitmap (DESIGN.md "Exact masked kNN").  Bitmap rows as SearchArgs::allow.
+// allow_count_dev: d_counts[r] = allowed points of row r (rows x stride words; bits at positions >= n ignored).
+int allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t stride, uint32_t* d_counts, hipStream_t st);
+// Compaction of ONE bitmap in two calls that share d_scratch (allow_compact_scratch_bytes(n) bytes): count leaves the number of
+// allowed points at *d_total (a word of the scratch; the caller reads it back), scatter writes their ids, ascending, to
+// d_ids[0 .. count).
+size_t allow_compact_scratch_bytes(uint64_t n);
+int allow_compact_count_dev(const uint32_t* d_allow, uint64_t n, uint32_t* d_scratch, const uint32_t** d_total, hipStream_t st);
+int allow_compact_scatter_dev(const uint32_t* d_allow, uint64_t n, const uint32_t* d_scratch, uint32_t* d_ids, uint32_t count,
+                              hipStream_t st);
+// pad != 0: nq x k ids / dists <- 0xFFFFFFFF / +inf; d_counts (optional): nq entries <- cnt
+int knn_pad_dev(uint32_t* d_ids, float* d_dists, uint32_t* d_counts, uint64_t nq, uint32_t k, uint32_t cnt, int pad, hipStream_t st);
+// one bitmap row per query (allow_stride words apart), k <= 64: rows sorted by (dist, id), padded; d_out_counts optional
+int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
+                    uint64_t allow_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts);
+
 // leaf_knn.hip: lane-owns-row all-pairs top-m for one-byte element types (HCNNG leaves)
 bool dense_gt_eligible(const DeviceIndex& ix, uint32_t m, bool b_ids, bool segmented, int exclude_same);
 uint32_t dense_gt_slots(const DeviceIndex& ix, uint32_t m);

@@ -2,16 +2,18 @@
 classes python/module.cpp registers (:50-57,150-155), over the C-ABI.
 
     Index(data_path, index_path)                       (positional order of graph_index.cpp:82)
-    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None) -> (uint32[nq,knn], float32[nq,knn])
+    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None)
+                                                                         -> (uint32[nq,knn], float32[nq,knn])
     .single_search(q, knn, beam_width, quant, visit_limit)               -> uint32[knn]
     .batch_search_from_string(queries_path, knn, beam_width, quant=False, visit_limit=-1)
-    .batch_search_masked(queries, knn, beam_width, allow, quant=False, visit_limit=-1)   this project's own: masked results
+    .batch_search_masked(queries, knn, beam_width, allow, quant=False, visit_limit=-1, exact_below=None)
+                                                                         this project's own: masked results
     .check_recall(queries_file, gt_file, neighbors, k)   prints "Recall: x"
 """
 import numpy as np
 
 from . import io, quantize, sketch
-from .index import DeviceIndex
+from .index import DeviceIndex, allow_count, pack_allow
 from .recall import recall_at_k
 
 
@@ -112,9 +114,38 @@ class GraphIndex:
         if len(frontier_size) and int(frontier_size.min()) < knn:               # beamSearch.h:416-419
             raise RuntimeError(f"Error: beam search returned {int(frontier_size.min())} elements, which is less than k = {knn}")
 
-    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None):
-        """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned"""
-        return self._search(queries, knn, beam_width, quant, visit_limit, allow)
+    def _exact_or_walk(self, queries, knn, allow, exact_below, walk):
+        """The rule of DESIGN.md "Exact masked kNN": a mask with at most exact_below allowed points is answered exactly
+        (DeviceIndex.bruteforce_knn_masked on the full-precision handle), any other by walk(queries, allow) -> (ids, dists).
+        Per-query rows are split by their own counts, each part takes its route, and the rows come back in the given order."""
+        if exact_below is None:
+            return walk(queries, allow)
+        queries = np.ascontiguousarray(queries, dtype=self.T)
+        allow = pack_allow(allow, self.index.n)
+        cnt = allow_count(allow, self.index.n)
+        if allow.ndim == 1:
+            if cnt > exact_below:
+                return walk(queries, allow)
+            ids, dists, _ = self.index.bruteforce_knn_masked(queries, knn, allow)
+            return ids, dists
+        if allow.shape[0] != len(queries):
+            raise ValueError("per-query allow rows must be nq x W")
+        exact = cnt <= exact_below
+        ids = np.full((len(queries), knn), 0xFFFFFFFF, np.uint32)
+        dists = np.full((len(queries), knn), np.inf, np.float32)
+        if exact.any():
+            ids[exact], dists[exact], _ = self.index.bruteforce_knn_masked(queries[exact], knn, allow[exact])
+        if not exact.all():
+            ids[~exact], dists[~exact] = walk(queries[~exact], allow[~exact])
+        return ids, dists
+
+    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None):
+        """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned.
+        exact_below (with allow): as batch_search_masked"""
+        if allow is None:
+            return self._search(queries, knn, beam_width, quant, visit_limit)
+        return self._exact_or_walk(queries, knn, allow, exact_below,
+                                   lambda q, a: self._search(q, knn, beam_width, quant, visit_limit, a))
 
     def _search_masked(self, queries, knn, beam_width, allow, quant, visit_limit):
         """Masked searches (this project's own, DESIGN.md "Masked search").  Rows may be short (padding 0xFFFFFFFF / +inf):
@@ -137,12 +168,19 @@ class GraphIndex:
                                      rerank_factor=100, allow=allow, **qp)
         return r["ids"], r["dists"]
 
-    def batch_search_masked(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1):
+    def batch_search_masked(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1, exact_below=None):
         """Only allowed points are returned (allow: an allow bitmap or boolean mask, DeviceIndex.batch_search_masked).
         quant=False, or one-byte points: batch_search(..., allow=).  quant=True on float points: the masked search of the
         quantised copy (quant_bits 8 or 4) with an exact rerank of its result list, in one call on the device
-        (DeviceIndex.search_rerank(allow=)); not with second_level=."""
-        return self._search_masked(queries, knn, beam_width, allow, quant, visit_limit)
+        (DeviceIndex.search_rerank(allow=)); not with second_level=.
+        exact_below: None (the default) -- every mask is walked, as above.  An integer: a mask that allows at most that many
+        points is answered EXACTLY instead, by scoring its allowed points on the full-precision table (DESIGN.md "Exact masked
+        kNN"; quant makes no difference there); per-query rows are split by their own counts.  There is no built-in
+        threshold: the count at which the two routes cost the same depends on the data (tools/masked_time.py --exact)."""
+        if allow is None:
+            raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
+        return self._exact_or_walk(queries, knn, allow, exact_below,
+                                   lambda q, a: self._search_masked(q, knn, beam_width, a, quant, visit_limit))
 
     def batch_search_masked_from_string(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1):
         return self._search_masked(io.read_bin(queries, self.T), knn, beam_width, allow, quant, visit_limit)

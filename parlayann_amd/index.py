@@ -93,6 +93,19 @@ def pack_allow(allow, n):
     return np.ascontiguousarray(a)
 
 
+def allow_count(allow, n):
+    """number of allowed points below n per bitmap row: packed uint32 (W,) / (nq, W) or boolean (n,) / (nq, n) -> int /
+    int64 (nq,).  Bits at positions >= n (the tail of the last word, words past ceil(n / 32)) do not count, as on the device."""
+    a = pack_allow(allow, n)
+    n = int(n)
+    w = (n + 31) // 32
+    a = a[..., :w].copy()
+    if n & 31 and w:
+        a[..., w - 1] &= np.uint32((1 << (n & 31)) - 1)
+    c = np.unpackbits(np.ascontiguousarray(a).view(np.uint8), axis=-1).sum(axis=-1, dtype=np.int64)
+    return int(c) if a.ndim == 1 else c
+
+
 def host_graph(n, max_deg):
     """An empty graph slab in the reference layout (graph.h:134-141): n x (max_deg+1), slot 0 = degree."""
     return np.zeros((n, max_deg + 1), dtype=np.uint32)
@@ -664,6 +677,29 @@ class DeviceIndex:
         oi = np.empty((len(q), k), np.uint32); od = np.empty((len(q), k), np.float32)
         check(self._lib.pann_bruteforce_knn(self._h, _ptr(q), len(q), _row_stride(q), k, _ptr(oi), _ptr(od)))
         return oi, od
+
+    def bruteforce_knn_masked(self, queries, k, allow):
+        """pann_bruteforce_knn_masked: the exact k nearest ALLOWED points of every query (DESIGN.md "Exact masked kNN") ->
+        (ids uint32[nq, k], dists float32[nq, k], counts uint32[nq]).  allow: as batch_search_masked -- packed uint32 (W,) or
+        (nq, W), or boolean (n,) or (nq, n); one row serves the whole batch (k <= 128), rows are per query (k <= 64).  Row q
+        holds counts[q] = min(k, allowed points) entries sorted by (dist, id), then 0xFFFFFFFF / +inf."""
+        q = self._queries(queries)
+        allow = pack_allow(allow, self.n)
+        if allow.ndim == 2 and allow.shape[0] != len(q):
+            raise ValueError("per-query allow rows must be nq x W")
+        oi = np.empty((len(q), k), np.uint32); od = np.empty((len(q), k), np.float32); oc = np.empty(len(q), np.uint32)
+        check(self._lib.pann_bruteforce_knn_masked(self._h, _ptr(q), len(q), _row_stride(q), k, _ptr(allow),
+                                                   allow.shape[1] if allow.ndim == 2 else 0, _ptr(oi), _ptr(od), _ptr(oc)))
+        return oi, od, oc
+
+    def bruteforce_knn_masked_dev(self, d_queries_ptr, nq, q_stride_bytes, k, d_allow_ptr, allow_stride_words, d_ids_ptr,
+                                  d_dists_ptr, d_counts_ptr=None, stream_ptr=None):
+        """pann_bruteforce_knn_masked_dev: the same on raw device addresses (integers), enqueued on `stream_ptr`.  Per-query rows
+        (allow_stride_words != 0): nothing is synchronised; a shared bitmap synchronises the stream once."""
+        vp = lambda a: C.c_void_p(a or None)
+        check(self._lib.pann_bruteforce_knn_masked_dev(self._h, vp(d_queries_ptr), nq, q_stride_bytes, k, vp(d_allow_ptr),
+                                                       allow_stride_words, vp(d_ids_ptr), vp(d_dists_ptr), vp(d_counts_ptr),
+                                                       vp(stream_ptr)))
 
     def bruteforce_range(self, queries, radius):
         """data_tools/compute_range_groundtruth.cpp:13-29: every base point within `radius` of every query, as CSR ->

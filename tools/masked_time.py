@@ -24,6 +24,16 @@ equal those of the composition (pann_quantize_rows, pann_batch_search_masked wit
 otherwise.
 
     python tools/masked_time.py --rerank [--bits 8|4|8,4] [--fractions 1.0,0.5,0.1] [--json out.json]
+
+--exact: the exact masked kNN beside the masked search on selective masks (DESIGN.md "Exact masked kNN").  The first setup above
+with masks that allow 0.1 %, 1 % and 10 % of the points.  Per mask: pann_bruteforce_knn_masked_dev with the shared bitmap, the
+same call with the same content as one row per query (nq x ceil(n / 32) words on the device: 1.25 GB at the defaults), and
+pann_batch_search_masked_dev at beam 64 -- time (HIP events) and recall@10 of each against the sub-index ground truth above,
+whose wall time (upload of the allowed rows + pann_bruteforce_knn) is printed as the yardstick it is.  The shared exact ids
+must equal that ground truth; the tool stops otherwise.  Last line: the allowed count at which the shared exact route and the
+masked search cost the same, interpolated between the measured masks in log(count).
+
+    python tools/masked_time.py --exact [--fractions 0.001,0.01,0.1] [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -75,11 +85,14 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--rerank", action="store_true", help="the fused quantised search + rerank instead of the plain search")
     ap.add_argument("--bits", default="8", help="--rerank: bits per coordinate of the quantised copy: 8, 4 or 8,4 (one build for both)")
+    ap.add_argument("--exact", action="store_true", help="the exact masked kNN beside the masked search on selective masks")
     a = ap.parse_args()
     if a.fractions is None:
-        a.fractions = "1.0,0.5,0.1" if a.rerank else "1.0,0.9,0.5,0.1"
+        a.fractions = "0.001,0.01,0.1" if a.exact else "1.0,0.5,0.1" if a.rerank else "1.0,0.9,0.5,0.1"
     if a.rerank:
         return main_rerank(a)
+    if a.exact:
+        return main_exact(a)
     import torch
     n, d, nq = a.n, a.d, a.nq
     with step("data", 300):
@@ -169,6 +182,111 @@ def main():
     if a.json:
         with open(a.json, "w") as f:
             json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, steps=a.steps, rows=rows), f, indent=1)
+    ix.close()
+
+
+def main_exact(a):
+    import torch
+    n, d, nq = a.n, a.d, a.nq
+    with step("data", 300):
+        X = datasets.sift1m_like(n, d, seed=1234, dtype=np.float32).astype(np.float16)
+        Q = datasets.sift1m_like(nq, d, seed=4321, dtype=np.float16)
+    with step(f"upload + build R={R} L={L}", 900):
+        ix = DeviceIndex(X, max_degree=R)
+        ix.vamana_build(R, L, ALPHA, num_passes=2, seed=1, sort_neighbors=True)
+    lib = _capi.load()
+    qp = _capi.QueryParams(k=K, beam=BEAM, cut=1.35, limit=n, degree_limit=R, rerank_factor=100, pad=1.0)
+    t_q = torch.from_numpy(Q.view(np.uint8).reshape(nq, -1)).cuda()
+    t_st = torch.zeros(1, dtype=torch.int32, device="cuda")
+    t_ids = torch.zeros((nq, K), dtype=torch.int32, device="cuda")
+    t_d = torch.zeros((nq, K), dtype=torch.float32, device="cuda")
+    t_cnt = torch.zeros(nq, dtype=torch.int32, device="cuda")
+    t_status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    words = (n + 31) // 32
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        stream.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+        with torch.cuda.stream(stream):
+            for e0, e1 in ev:
+                e0.record(stream); fn(); e1.record(stream)
+        stream.synchronize()
+        ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def ids_now():
+        return t_ids.cpu().numpy().view(np.uint32).copy()
+
+    rows = []
+    for frac in [float(f) for f in a.fractions.split(",")]:
+        allow = np.random.default_rng(int(frac * 100000)).random(n) < frac
+        live = np.flatnonzero(allow).astype(np.uint32)
+        t_allow = torch.from_numpy(pack_allow(allow, n).view(np.int32)).cuda()
+        torch.cuda.synchronize()
+        with step(f"allow {frac:.1%}: ground truth over {len(live)} allowed points", 600):
+            t0 = time.perf_counter()
+            sub = DeviceIndex(X[live], max_degree=4)
+            gt_local, gd = sub.bruteforce_knn(Q, K)
+            sub.close()
+            sub_ms = (time.perf_counter() - t0) * 1e3
+            gt = np.where(gt_local != 0xFFFFFFFF, live[np.minimum(gt_local, len(live) - 1)], 0xFFFFFFFF).astype(np.uint32)
+
+        def exact_step(t_bits, stride):
+            ix.bruteforce_knn_masked_dev(t_q.data_ptr(), nq, 2 * d, K, t_bits.data_ptr(), stride, t_ids.data_ptr(), t_d.data_ptr(),
+                                         t_cnt.data_ptr(), stream.cuda_stream)
+
+        def masked_step():
+            out = _capi.SearchOut(ids=t_ids.data_ptr(), dists=t_d.data_ptr(), out_k=K, status=t_status.data_ptr())
+            _capi.check(lib.pann_batch_search_masked_dev(ix.handle, C.c_void_p(t_q.data_ptr()), None, nq, 2 * d, C.c_void_p(t_st.data_ptr()), 1,
+                                                         C.byref(qp), C.c_void_p(t_allow.data_ptr()), 0, C.byref(out), None, None,
+                                                         C.c_void_p(stream.cuda_stream)))
+
+        with step(f"allow {frac:.1%}: shared exact route", 300):
+            s_ms = timed(lambda: exact_step(t_allow, 0))
+            ids_s = ids_now()
+            if not np.array_equal(ids_s, gt):
+                print("ERROR: the shared exact ids differ from the sub-index ground truth", flush=True)
+                sys.exit(1)
+        with step(f"allow {frac:.1%}: per-query exact route", 300):
+            t_rows = t_allow.repeat(nq, 1)
+            torch.cuda.synchronize()
+            r_ms = timed(lambda: exact_step(t_rows, words))
+            ids_r = ids_now()
+            del t_rows
+        with step(f"allow {frac:.1%}: masked search, beam {BEAM}", 300):
+            m_ms = timed(masked_step)
+            assert int(t_status.cpu()[0]) == 0
+            ids_m = ids_now()
+        row = dict(allow=frac, allowed=int(len(live)), sub_index_wall_ms=sub_ms, shared_ms=s_ms[0], shared_ms_min=s_ms[1],
+                   shared_ms_max=s_ms[2], rows_ms=r_ms[0], rows_ms_min=r_ms[1], rows_ms_max=r_ms[2], masked_ms=m_ms[0],
+                   masked_ms_min=m_ms[1], masked_ms_max=m_ms[2], recall10_shared=recall_at_k(ids_s, gt, gd, K),
+                   recall10_rows=recall_at_k(ids_r, gt, gd, K), recall10_masked=recall_at_k(ids_m, gt, gd, K))
+        rows.append(row)
+        print(f"  allow {frac:6.1%} ({len(live):7d} points)  sub-index ground truth {sub_ms:9.1f} ms wall   exact shared {s_ms[0]:9.3f} ms "
+              f"(min {s_ms[1]:.3f}, max {s_ms[2]:.3f}) recall@10 {row['recall10_shared']:.4f}   exact per-query {r_ms[0]:9.3f} ms "
+              f"(min {r_ms[1]:.3f}, max {r_ms[2]:.3f}) recall@10 {row['recall10_rows']:.4f}   masked beam {BEAM} {m_ms[0]:9.3f} ms "
+              f"(min {m_ms[1]:.3f}, max {m_ms[2]:.3f}) recall@10 {row['recall10_masked']:.4f}   shared exact ids == ground truth", flush=True)
+    # where the shared exact route and the masked search cost the same: log-linear between the two masks around the sign change
+    rows_sorted = sorted(rows, key=lambda r: r["allowed"])
+    diff = [r["shared_ms"] - r["masked_ms"] for r in rows_sorted]
+    cross = None
+    for lo, hi, d0, d1 in zip(rows_sorted, rows_sorted[1:], diff, diff[1:]):
+        if d0 <= 0 < d1:
+            t = d0 / (d0 - d1)
+            cross = float(np.exp(np.log(lo["allowed"]) + t * (np.log(hi["allowed"]) - np.log(lo["allowed"]))))
+    if cross is not None:
+        print(f"  equal cost at about {cross:.0f} allowed points ({cross / n:.2%} of {n}): below it the shared exact route is faster", flush=True)
+    elif all(x <= 0 for x in diff):
+        print(f"  the shared exact route was faster at every mask measured (up to {rows_sorted[-1]['allowed']} allowed points)", flush=True)
+    else:
+        print(f"  the masked search was faster at every mask measured (down to {rows_sorted[0]['allowed']} allowed points)", flush=True)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, steps=a.steps, equal_cost_allowed=cross, rows=rows), f, indent=1)
     ix.close()
 
 
