@@ -8,6 +8,7 @@
 #include <mutex>
 #include <vector>
 
+#include "host_staging.h"
 #include "pann_internal.h"
 #include "quant_device.h"
 
@@ -157,6 +158,24 @@ int refuse_4bit(const pann_index* idx, const char* fn) {
 int check_idx_no4(const pann_index* idx, const char* fn) {
   if (int rc = check_idx(idx, fn)) return rc;
   return refuse_4bit(idx, fn);
+}
+
+int k_beam_check(const pann_query_params* qp) {  // beamSearch.h:368-372, :549-553
+  if (qp->k <= qp->beam) return PANN_OK;
+  set_error("Error: beam search parameter Q = " + std::to_string(qp->beam) + " same size or smaller than k = " + std::to_string(qp->k));
+  return PANN_ERR_BAD_ARG;
+}
+
+// a bitmap of n bits per row: rows lie allow_stride_words apart, 0 = `zero_means` in the caller's words
+int allow_stride_check(const char* fn, const char* zero_means, uint64_t stride, uint64_t n) {
+  const uint64_t words = (n + 31) / 32;
+  if (stride == 0 || stride >= words) return PANN_OK;
+  set_error(std::string(fn) + ": allow_stride_words must be 0 (" + zero_means + ") or at least ceil(n / 32) = " + std::to_string(words));
+  return PANN_ERR_BAD_ARG;
+}
+
+void fill_search_params(SearchArgs& a, const pann_query_params* qp) {
+  a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
 }
 
 int upload_graph_rows(pann_index* idx, const uint32_t* h_rows, uint64_t m, const uint32_t* h_row_ids) {
@@ -494,16 +513,10 @@ int pann_index_get_graph(pann_index* idx, uint32_t* graph_out) {
 // batched beam search
 // ---------------------------------------------------------------------------------------------
 
-// the extra arguments of pann_batch_search_masked*: bitmap rows (host or device, as the entry point's other pointers) and outputs
-struct MaskArgs { const uint32_t* allow; uint64_t stride; uint32_t* result_count; uint32_t* allowed_cmps; };
 static int mask_checks(const pann_index* idx, const MaskArgs& m, const pann_query_params* qp, const pann_search_out* out) {
-  const uint64_t words = (idx->ix.n + 31) / 32;
   if ((int64_t)out->out_k > qp->beam) { set_error("pann_batch_search_masked: out_k larger than the beam"); return PANN_ERR_BAD_ARG; }
   if (!m.allow) { set_error("pann_batch_search_masked: null allow bitmap"); return PANN_ERR_BAD_ARG; }
-  if (m.stride != 0 && m.stride < words) {
-    set_error("pann_batch_search_masked: allow_stride_words must be 0 (one shared bitmap) or at least ceil(n / 32) = " + std::to_string(words));
-    return PANN_ERR_BAD_ARG;
-  }
+  if (int rc = allow_stride_check("pann_batch_search_masked", "one shared bitmap", m.stride, idx->ix.n)) return rc;
   if (out->out_k > 64) { set_error("pann_batch_search_masked: out_k > 64 is not supported"); return PANN_ERR_UNSUPPORTED; }
   return PANN_OK;
 }
@@ -511,10 +524,7 @@ static int mask_checks(const pann_index* idx, const MaskArgs& m, const pann_quer
 static int search_common_checks(pann_index* idx, uint64_t nq, const pann_query_params* qp, const pann_search_out* out) {
   if (int rc = check_idx(idx, "pann_batch_search")) return rc;
   if (!qp || !out) { set_error("pann_batch_search: null params/out"); return PANN_ERR_BAD_ARG; }
-  if (qp->k > qp->beam) {  // beamSearch.h:368-372, :549-553
-    set_error("Error: beam search parameter Q = " + std::to_string(qp->beam) + " same size or smaller than k = " + std::to_string(qp->k));
-    return PANN_ERR_BAD_ARG;
-  }
+  if (int rc = k_beam_check(qp)) return rc;
   (void)nq;
   return PANN_OK;
 }
@@ -533,7 +543,7 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
   SearchArgs a;
   a.queries = (const uint8_t*)d_queries; a.qstride = q_stride_bytes; a.query_ids = d_query_ids;
   a.nq = nq; a.starts = d_starts; a.nstarts = nstarts;
-  a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
+  fill_search_params(a, qp);
   a.dcap = idx->dcap;
   a.out = *d_out;
   a.filter = filter; a.sketch_queries = (const uint8_t*)d_sketch_queries; a.sq_stride = sq_stride; a.pruned_cmps = d_pruned;
@@ -569,36 +579,64 @@ int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const u
 
 }  // extern "C"
 
-// The "dropped" scratch of a search is nq * dcap * 8 bytes.  When a launch reports that it was too small the list is grown (x8,
-// up to min(limit, n): a query drops at most one entry per visited vertex) and the batch runs again; a grown list that would
-// take more than kDropBudget for the whole batch makes the batch run in ranges of queries instead, and the handle keeps at most
-// kDropKeep entries per query for later calls (10K queries x 2048 x 8 B = 160 MB), not the worst case of one odd batch.
-// launch(q0, cnt, dcap, &word): queries [q0, q0 + cnt) with a list of dcap entries, synchronised, word = the launch's status
-// word.  *status: the bits of the last pass over the batch; *whole: that pass was one launch of all nq queries.
-template <class Launch>
-static int run_with_dropped_growth(pann_index* idx, uint64_t nq, const pann_query_params* qp, const char* fn, uint32_t* status,
-                                   bool* whole, Launch&& launch) {
-  constexpr uint64_t kDropBudget = 1ull << 30;
-  constexpr uint32_t kDropKeep = 2048;
-  const uint64_t dneed = (uint64_t)std::min<int64_t>(std::max<int64_t>(qp->limit, 1), (int64_t)idx->ix.n);
-  uint32_t dcap = idx->dcap;
-  for (;;) {
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, kDropBudget / ((uint64_t)std::max<uint32_t>(dcap, 64) * 8)));
-    *status = 0; *whole = chunk >= nq;
-    for (uint64_t q0 = 0; q0 < nq; q0 += chunk) {
-      uint32_t st_word = 0;      // the launch's status word (the next launch clears it)
-      if (int rc = launch(q0, std::min(chunk, nq - q0), dcap, &st_word)) return rc;
-      *status |= st_word;
-      if (*status & PANN_STATUS_DROPPED_OVERFLOW) break;
-    }
-    if (!(*status & PANN_STATUS_DROPPED_OVERFLOW)) break;
-    // The reference has no such list (its `visited` vector grows as needed, beamSearch.h:80,113): grow ours and run the batch again.
-    if ((uint64_t)dcap >= dneed) { set_error(std::string(fn) + ": internal dropped-list overflow"); return PANN_ERR_OVERFLOW; }
-    dcap = (uint32_t)std::min<uint64_t>((uint64_t)dcap * 8, (dneed + 63) / 64 * 64);
+// The host round trip of a host-pointer search call.  The caller adds its arrays to `in` and `out`, then: begin() packs the inputs
+// into pin_in and sends them up into stage[2] in ONE transfer, and makes room for the outputs in stage[4] / pin_out (with room
+// for a status word behind them); after the launches the outputs come down into pin_out in ONE transfer and go to their arrays.
+struct HostTrip {
+  pann_index* h;
+  hipStream_t st;
+  PackedLayout in, out;
+  explicit HostTrip(pann_index* handle) : h(handle), st(handle->stream) {}
+
+  int begin() {
+    if (int rc = h->pin_in.ensure(in.total)) return rc;
+    if (int rc = h->stage[2].ensure(in.total)) return rc;
+    if (int rc = h->stage[4].ensure(out.total + 256)) return rc;
+    if (int rc = h->pin_out.ensure(out.total + 256)) return rc;
+    in.copy(h->pin_in.p, true);
+    PANN_HIP(hipMemcpyAsync(h->stage[2].p, h->pin_in.p, in.total, hipMemcpyHostToDevice, st));
+    return PANN_OK;
   }
-  idx->dcap = std::max(idx->dcap, std::min(dcap, kDropKeep));
-  return PANN_OK;
-}
+  template <typename T> const T* din(int piece) const { return (const T*)in.at(h->stage[2].p, piece); }
+  template <typename T> T* dout(int piece, size_t first = 0) const {      // element `first` of an output (null if not asked for)
+    T* p = (T*)out.at(h->stage[4].p, piece);
+    return p ? p + first : nullptr;
+  }
+  uint32_t* status_slot() const { return (uint32_t*)((uint8_t*)h->stage[4].p + out.total); }
+
+  int finish(bool results_home = false) {          // results_home: the packed outputs already sit in pin_out
+    if (!results_home) {
+      PANN_HIP(hipMemcpyAsync(h->pin_out.p, h->stage[4].p, out.total, hipMemcpyDeviceToHost, st));
+      PANN_HIP(hipStreamSynchronize(st));
+    }
+    out.copy(h->pin_out.p, false);
+    return PANN_OK;
+  }
+
+  // The launches under the dropped-list growth policy of host_staging.h, then finish().  launch(q0, cnt, dcap, &d_word): enqueue queries
+  // [q0, q0 + cnt) and say where on the device the launch's status word lies.
+  template <class Launch>
+  int run_grown(uint64_t nq, const pann_query_params* qp, const char* fn, uint32_t* status, Launch&& launch) {
+    bool results_home = false;
+    if (int rc = run_with_dropped_growth(h->dcap, h->ix.n, nq, qp->limit, fn, status, &results_home, &g_err,
+        [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
+        const uint32_t* d_word = nullptr;
+        if (int rc = launch(q0, cnt, dcap, &d_word)) return rc;
+        if (cnt == nq) {           // the whole batch in one launch (the normal case): the word travels with the results, ONE transfer
+          if (d_word != status_slot()) PANN_HIP(hipMemcpyAsync(status_slot(), d_word, 4, hipMemcpyDeviceToDevice, st));
+          PANN_HIP(hipMemcpyAsync(h->pin_out.p, h->stage[4].p, out.total + 4, hipMemcpyDeviceToHost, st));
+          PANN_HIP(hipStreamSynchronize(st));
+          std::memcpy(st_word, (uint8_t*)h->pin_out.p + out.total, 4);
+        } else {
+          PANN_HIP(hipMemcpyAsync(st_word, d_word, 4, hipMemcpyDeviceToHost, st));
+          PANN_HIP(hipStreamSynchronize(st));
+        }
+        return PANN_OK;
+      })) return rc;
+    if (h->ws.bytes > (2ull << 30)) h->ws.release();          // a one-off worst-case scratch is not kept on the handle
+    return finish(results_home);
+  }
+};
 
 static int batch_search_host(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int per_query,
@@ -631,95 +669,57 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   const DeviceIndex& ix = idx->ix;
   // ---- inputs: packed into pinned memory, one H2D transfer ----
   if (queries && q_stride_bytes < ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  const size_t qbytes = queries ? (nq - 1) * q_stride_bytes + ix.dbytes : nq * 4;
+  HostTrip t(idx);
+  const int i_q = t.in.add(queries ? queries : (const void*)query_ids, queries ? (nq - 1) * q_stride_bytes + ix.dbytes : nq * 4, 16);
+  const int i_st = t.in.add(starts, (size_t)nst_total * 4);
   // masked: the bitmap rows travel with them, packed to ceil(n / 32) words per row
-  const size_t mwords = (size_t)((ix.n + 31) / 32), mrows = mask ? (mask->stride ? (size_t)nq : 1) : 0;
-  const size_t off_st = al(qbytes + 16), off_mask = off_st + al((size_t)nst_total * 4), in_bytes = off_mask + al(mrows * mwords * 4);
-  if (int rc = idx->pin_in.ensure(in_bytes)) return rc;
-  if (int rc = idx->stage[2].ensure(in_bytes)) return rc;
-  std::memcpy(idx->pin_in.p, queries ? queries : (const void*)query_ids, qbytes);
-  std::memcpy((uint8_t*)idx->pin_in.p + off_st, starts, (size_t)nst_total * 4);
-  for (size_t r = 0; r < mrows; r++)
-    std::memcpy((uint8_t*)idx->pin_in.p + off_mask + r * mwords * 4, mask->allow + r * mask->stride, mwords * 4);
-  const uint32_t* d_allow = (const uint32_t*)((uint8_t*)idx->stage[2].p + off_mask);
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, idx->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
-  const void* d_q = queries ? idx->stage[2].p : nullptr;
-  const uint32_t* d_qid = queries ? nullptr : idx->stage[2].as<uint32_t>();
-  const uint32_t* d_starts = (const uint32_t*)((uint8_t*)idx->stage[2].p + off_st);
+  const size_t mwords = (size_t)((ix.n + 31) / 32);
+  const int i_mask = mask ? t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4) : -1;
+  // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
+  const size_t ok = out->out_k, vc = out->visited_cap;
+  const int o_ids = t.out.add(out->ids, nq * ok * 4), o_dists = t.out.add(out->dists, nq * ok * 4);
+  const int o_fs = t.out.add(out->frontier_size, nq * 4), o_vcnt = t.out.add(out->visited_count, nq * 4);
+  const int o_cmps = t.out.add(out->dist_cmps, nq * 4), o_deg = t.out.add(out->degree_sum, nq * 4);
+  const int o_vids = t.out.add(out->visited_ids, nq * vc * 4), o_vdists = t.out.add(out->visited_dists, nq * vc * 4);
+  const int o_pruned = t.out.add(filter ? out_pruned : nullptr, nq * 4);
+  const int o_rcnt = t.out.add(mask ? mask->result_count : nullptr, nq * 4), o_acmps = t.out.add(mask ? mask->allowed_cmps : nullptr, nq * 4);
+  if (int rc = t.begin()) return rc;
+  const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
+  const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
+  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask ? t.din<uint32_t>(i_mask) : nullptr;
   if (filter && sketch_queries) {      // dense rows of sk_row bytes
     if (int rc = idx->stage[5].ensure((size_t)nq * sk_row)) return rc;
     PANN_HIP(hipMemcpy2D(idx->stage[5].p, sk_row, sketch_queries, sq_stride, sk_row, nq, hipMemcpyHostToDevice));
   }
-
-  // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
-  const size_t ok = out->out_k, vc = out->visited_cap;
-  struct Piece { void* host; size_t bytes; size_t off; };
-  Piece pc[11] = {{out->ids, nq * ok * 4, 0}, {out->dists, nq * ok * 4, 0}, {out->frontier_size, nq * 4, 0},
-                  {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {out->degree_sum, nq * 4, 0},
-                  {out->visited_ids, nq * vc * 4, 0}, {out->visited_dists, nq * vc * 4, 0},
-                  {filter ? out_pruned : nullptr, nq * 4, 0},
-                  {mask ? mask->result_count : nullptr, nq * 4, 0}, {mask ? mask->allowed_cmps : nullptr, nq * 4, 0}};
-  size_t out_bytes = 0;
-  for (auto& x : pc) { if (!x.host) x.bytes = 0; x.off = out_bytes; out_bytes += al(x.bytes); }
-  if (int rc = idx->stage[4].ensure(out_bytes + 256)) return rc;
-  if (int rc = idx->pin_out.ensure(out_bytes + 256)) return rc;
-  auto dptr = [&](int i) -> void* { return pc[i].bytes ? (void*)((uint8_t*)idx->stage[4].p + pc[i].off) : nullptr; };
-  pann_search_out d = *out;
-  d.ids = (uint32_t*)dptr(0); d.dists = (float*)dptr(1); d.frontier_size = (uint32_t*)dptr(2);
-  d.visited_count = (uint32_t*)dptr(3); d.dist_cmps = (uint32_t*)dptr(4); d.degree_sum = (uint32_t*)dptr(5);
-  d.visited_ids = (uint32_t*)dptr(6); d.visited_dists = (float*)dptr(7);
-  if (!d.visited_ids && !d.visited_dists) d.visited_cap = 0;
-
-  d.status = nullptr;   // read from the workspace below
   uint32_t status = 0;
-  bool results_home = false;        // the packed outputs already sit in pin_out
-  if (int rc = run_with_dropped_growth(idx, nq, qp, "pann_batch_search", &status, &results_home,
-      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
+  if (int rc = t.run_grown(nq, qp, "pann_batch_search", &status,
+      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, const uint32_t** d_word) -> int {
       SearchArgs a;
-      a.queries = d_q ? (const uint8_t*)d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
+      a.queries = d_q ? d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
       a.query_ids = d_qid ? d_qid + q0 : nullptr;
       a.nq = cnt; a.starts = per_query ? d_starts + q0 * nstarts : d_starts; a.nstarts = nstarts; a.starts_per_query = per_query;
-      a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
+      fill_search_params(a, qp);
       a.dcap = dcap;
-      a.out = d;
-      if (a.out.ids) a.out.ids += q0 * ok;
-      if (a.out.dists) a.out.dists += q0 * ok;
-      if (a.out.frontier_size) a.out.frontier_size += q0;
-      if (a.out.visited_count) a.out.visited_count += q0;
-      if (a.out.dist_cmps) a.out.dist_cmps += q0;
-      if (a.out.degree_sum) a.out.degree_sum += q0;
-      if (a.out.visited_ids) a.out.visited_ids += q0 * vc;
-      if (a.out.visited_dists) a.out.visited_dists += q0 * vc;
+      a.out = *out;
+      a.out.ids = t.dout<uint32_t>(o_ids, q0 * ok); a.out.dists = t.dout<float>(o_dists, q0 * ok);
+      a.out.frontier_size = t.dout<uint32_t>(o_fs, q0); a.out.visited_count = t.dout<uint32_t>(o_vcnt, q0);
+      a.out.dist_cmps = t.dout<uint32_t>(o_cmps, q0); a.out.degree_sum = t.dout<uint32_t>(o_deg, q0);
+      a.out.visited_ids = t.dout<uint32_t>(o_vids, q0 * vc); a.out.visited_dists = t.dout<float>(o_vdists, q0 * vc);
+      if (!a.out.visited_ids && !a.out.visited_dists) a.out.visited_cap = 0;
+      a.out.status = nullptr;   // read from the workspace
       a.filter = filter;
       if (filter) {
         a.sketch_queries = sketch_queries ? (const uint8_t*)idx->stage[5].p + q0 * sk_row : nullptr; a.sq_stride = sk_row;
-        a.pruned_cmps = dptr(8) ? (uint32_t*)dptr(8) + q0 : nullptr;
+        a.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
       }
       if (mask) {
         a.masked = 1; a.allow = mask->stride ? d_allow + q0 * mwords : d_allow; a.allow_stride = mask->stride ? mwords : 0;
-        a.result_count = dptr(9) ? (uint32_t*)dptr(9) + q0 : nullptr;
-        a.allowed_cmps = dptr(10) ? (uint32_t*)dptr(10) + q0 : nullptr;
+        a.result_count = t.dout<uint32_t>(o_rcnt, q0); a.allowed_cmps = t.dout<uint32_t>(o_acmps, q0);
       }
       if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
-      if (int rc = launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
-      if (cnt == nq) {           // the whole batch in one launch (the normal case): the word travels with the results, ONE transfer
-        PANN_HIP(hipMemcpyAsync((uint8_t*)idx->stage[4].p + out_bytes, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToDevice, st));
-        PANN_HIP(hipMemcpyAsync(idx->pin_out.p, idx->stage[4].p, out_bytes + 4, hipMemcpyDeviceToHost, st));
-        PANN_HIP(hipStreamSynchronize(st));
-        std::memcpy(st_word, (uint8_t*)idx->pin_out.p + out_bytes, 4);
-      } else {
-        PANN_HIP(hipMemcpyAsync(st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
-        PANN_HIP(hipStreamSynchronize(st));
-      }
-      return PANN_OK;
+      *d_word = (const uint32_t*)((uint8_t*)idx->ws.buf + 64);
+      return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st);
     })) return rc;
-  if (!results_home) {
-    PANN_HIP(hipMemcpyAsync(idx->pin_out.p, idx->stage[4].p, out_bytes, hipMemcpyDeviceToHost, st));
-    PANN_HIP(hipStreamSynchronize(st));
-  }
-  if (idx->ws.bytes > (2ull << 30)) idx->ws.release();          // a one-off worst-case scratch is not kept on the handle
-  for (auto& x : pc) if (x.bytes) std::memcpy(x.host, (uint8_t*)idx->pin_out.p + x.off, x.bytes);
   if (out->status) *out->status = status;
   if (status & PANN_STATUS_VISITED_OVERFLOW) { set_error("pann_batch_search: visited list longer than visited_cap"); return PANN_ERR_OVERFLOW; }
   return PANN_OK;
@@ -1148,13 +1148,9 @@ int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint6
 
 int pann_allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t allow_stride_words, uint32_t* d_counts,
                          void* stream) {
-  const uint64_t words = (n + 31) / 32;
   if (!d_allow || !d_counts) { set_error("pann_allow_count_dev: null argument"); return PANN_ERR_BAD_ARG; }
   if (n > 0xFFFFFFFFull) { set_error("pann_allow_count_dev: n must be < 2^32"); return PANN_ERR_BAD_ARG; }
-  if (allow_stride_words != 0 && allow_stride_words < words) {
-    set_error("pann_allow_count_dev: allow_stride_words must be 0 (one row) or at least ceil(n / 32) = " + std::to_string(words));
-    return PANN_ERR_BAD_ARG;
-  }
+  if (int rc = allow_stride_check("pann_allow_count_dev", "one row", allow_stride_words, n)) return rc;
   return allow_count_dev(d_allow, n, allow_stride_words ? rows : 1, allow_stride_words, d_counts, (hipStream_t)stream);
 }
 
@@ -1164,13 +1160,9 @@ static int masked_knn_checks(const pann_index* idx, const char* fn, const void* 
   *done = false;
   if (int rc = check_idx_no4(idx, fn)) return rc;
   if (nq == 0) { *done = true; return PANN_OK; }
-  const uint64_t words = (idx->ix.n + 31) / 32;
   if (!queries || !out_ids || !out_dists) { set_error(std::string(fn) + ": null argument"); return PANN_ERR_BAD_ARG; }
   if (!allow) { set_error(std::string(fn) + ": null allow bitmap"); return PANN_ERR_BAD_ARG; }
-  if (stride != 0 && stride < words) {
-    set_error(std::string(fn) + ": allow_stride_words must be 0 (one shared bitmap) or at least ceil(n / 32) = " + std::to_string(words));
-    return PANN_ERR_BAD_ARG;
-  }
+  if (int rc = allow_stride_check(fn, "one shared bitmap", stride, idx->ix.n)) return rc;
   if (q_stride_bytes < idx->ix.dbytes) { set_error(std::string(fn) + ": query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   if (k == 0) { set_error(std::string(fn) + ": k == 0"); return PANN_ERR_BAD_ARG; }
   if (k > (stride ? 64u : 128u)) {
@@ -1223,34 +1215,20 @@ int pann_bruteforce_knn_masked(pann_index* idx, const void* queries, uint64_t nq
                                  out_dists, &done)) return rc;
   if (done) return PANN_OK;
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
   const DeviceIndex& ix = idx->ix;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   // in: the queries and the bitmap rows, packed to ceil(n / 32) words each, in one transfer (as pann_batch_search_masked)
-  const size_t qbytes = (nq - 1) * q_stride_bytes + ix.dbytes;
-  const size_t mwords = (size_t)((ix.n + 31) / 32), mrows = allow_stride_words ? (size_t)nq : 1;
-  const size_t off_mask = al(qbytes + 16), in_bytes = off_mask + al(mrows * mwords * 4);
-  if (int rc = idx->pin_in.ensure(in_bytes)) return rc;
-  if (int rc = idx->stage[2].ensure(in_bytes)) return rc;
-  std::memcpy(idx->pin_in.p, queries, qbytes);
-  for (size_t r = 0; r < mrows; r++)
-    std::memcpy((uint8_t*)idx->pin_in.p + off_mask + r * mwords * 4, allow + r * allow_stride_words, mwords * 4);
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, idx->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
+  HostTrip t(idx);
+  const size_t mwords = (size_t)((ix.n + 31) / 32);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, 16);
+  const int i_mask = t.in.add_rows(allow, allow_stride_words ? (size_t)nq : 1, mwords * 4, (size_t)allow_stride_words * 4);
   // out: ids, dists and counts in one region, one transfer back
   const size_t row_bytes = (size_t)nq * k * 4;
-  const size_t off_d = al(row_bytes), off_c = off_d + al(row_bytes), out_bytes = off_c + al(nq * 4);
-  if (int rc = idx->stage[4].ensure(out_bytes)) return rc;
-  if (int rc = idx->pin_out.ensure(out_bytes)) return rc;
-  uint8_t* d_out = idx->stage[4].as<uint8_t>();
-  if (int rc = masked_knn_run(idx, idx->stage[2].as<uint8_t>(), nq, q_stride_bytes, k, (const uint32_t*)(idx->stage[2].as<uint8_t>() + off_mask),
-                              allow_stride_words ? mwords : 0, (uint32_t*)d_out, (float*)(d_out + off_d), (uint32_t*)(d_out + off_c), st)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->pin_out.p, d_out, out_bytes, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  const uint8_t* h = (const uint8_t*)idx->pin_out.p;
-  std::memcpy(out_ids, h, row_bytes);
-  std::memcpy(out_dists, h + off_d, row_bytes);
-  if (out_counts) std::memcpy(out_counts, h + off_c, nq * 4);
-  return PANN_OK;
+  const int o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes), o_counts = t.out.add(out_counts, nq * 4);
+  if (int rc = t.begin()) return rc;
+  if (int rc = masked_knn_run(idx, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, t.din<uint32_t>(i_mask),
+                              allow_stride_words ? mwords : 0, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists), t.dout<uint32_t>(o_counts),
+                              t.st)) return rc;
+  return t.finish();
 }
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,
@@ -1325,6 +1303,25 @@ int pann_rerank(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_st
 }
 
 
+// The tail of a range call.  The counts (stage[5]) come down and are waited for; of the id rows (stage[4]) only the columns any
+// query filled come back (entries past a row's count are unspecified: include/pann.h); then the two optional counters.
+static int download_range_results(pann_index* idx, uint64_t nq, uint32_t max_results, uint32_t* out_ids, uint32_t* out_counts,
+                                  uint32_t* out_cmps, uint32_t* out_truncated) {
+  hipStream_t st = idx->stream;
+  PANN_HIP(hipMemcpyAsync(out_counts, idx->stage[5].p, nq * 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  uint32_t widest = 0;
+  for (uint64_t i = 0; i < nq; i++) widest = std::max(widest, out_counts[i]);
+  widest = std::min(widest, max_results);
+  if (widest)
+    PANN_HIP(hipMemcpy2DAsync(out_ids, (size_t)max_results * 4, idx->stage[4].p, (size_t)max_results * 4, (size_t)widest * 4, nq,
+                              hipMemcpyDeviceToHost, st));
+  if (out_cmps) PANN_HIP(hipMemcpyAsync(out_cmps, idx->stage[6].p, nq * 4, hipMemcpyDeviceToHost, st));
+  if (out_truncated) PANN_HIP(hipMemcpyAsync(out_truncated, idx->stage[7].p, nq * 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  return PANN_OK;
+}
+
 int pann_range_search(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                       uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int starts_per_query,
                       float radius_2, uint32_t max_results, uint32_t* out_ids, uint32_t* out_counts,
@@ -1357,19 +1354,7 @@ int pann_range_search(pann_index* idx, const void* queries, const uint32_t* quer
                                 queries ? nullptr : idx->stage[2].as<uint32_t>(), nq, idx->stage[3].as<uint32_t>(), nstarts,
                                 starts_per_query, radius_2, max_results, idx->stage[4].as<uint32_t>(),
                                 idx->stage[5].as<uint32_t>(), idx->stage[6].as<uint32_t>(), idx->stage[7].as<uint32_t>())) return rc;
-  // only the columns any query filled come back (entries past a row's count are unspecified: include/pann.h)
-  PANN_HIP(hipMemcpyAsync(out_counts, idx->stage[5].p, nq * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  uint32_t widest = 0;
-  for (uint64_t i = 0; i < nq; i++) widest = std::max(widest, out_counts[i]);
-  widest = std::min(widest, max_results);
-  if (widest)
-    PANN_HIP(hipMemcpy2DAsync(out_ids, (size_t)max_results * 4, idx->stage[4].p, (size_t)max_results * 4, (size_t)widest * 4, nq,
-                              hipMemcpyDeviceToHost, st));
-  if (out_dist_cmps) PANN_HIP(hipMemcpyAsync(out_dist_cmps, idx->stage[6].p, nq * 4, hipMemcpyDeviceToHost, st));
-  if (out_truncated) PANN_HIP(hipMemcpyAsync(out_truncated, idx->stage[7].p, nq * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+  return download_range_results(idx, nq, max_results, out_ids, out_counts, out_dist_cmps, out_truncated);
 }
 
 
@@ -1423,10 +1408,7 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
   if (int rc = refuse_4bit(idx, "pann_range_query")) return rc;
   const DeviceIndex& ix = idx->ix;
   if (!qp) { set_error("pann_range_query: null params"); return PANN_ERR_BAD_ARG; }
-  if (qp->k > qp->beam) {  // beamSearch.h:368-372, :549-553
-    set_error("Error: beam search parameter Q = " + std::to_string(qp->beam) + " same size or smaller than k = " + std::to_string(qp->k));
-    return PANN_ERR_BAD_ARG;
-  }
+  if (int rc = k_beam_check(qp)) return rc;
   if (qp->beam < 1 || qp->beam > 0x7FFFFFFF) { set_error("pann_range_query: beam out of range"); return PANN_ERR_BAD_ARG; }
   if ((queries == nullptr) == (query_ids == nullptr)) { set_error("pann_range_query: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
   if (!starts || nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
@@ -1458,20 +1440,15 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
   const uint8_t* d_q = queries ? idx->stage[2].as<uint8_t>() : nullptr;
   const uint32_t* d_qid = queries ? nullptr : idx->stage[2].as<uint32_t>();
   // ---- round 1: the beam search; a launch that reports a full dropped list is grown and repeated (as batch_search_host) ----
-  constexpr uint64_t kDropBudget = 1ull << 30;
-  constexpr uint32_t kDropKeep = 2048;
-  const uint64_t dneed = (uint64_t)std::min<int64_t>(std::max<int64_t>(qp->limit, 1), (int64_t)ix.n);
-  uint32_t dcap = idx->dcap;
-  for (;;) {
-    const uint64_t chunk = std::max<uint64_t>(1, std::min<uint64_t>(nq, kDropBudget / ((uint64_t)std::max<uint32_t>(dcap, 64) * 8)));
-    uint32_t status = 0;
-    for (uint64_t q0 = 0; q0 < nq && !(status & PANN_STATUS_DROPPED_OVERFLOW); q0 += chunk) {
-      const uint64_t cnt = std::min(chunk, nq - q0);
+  uint32_t status = 0;
+  bool whole = false;
+  if (int rc = run_with_dropped_growth(idx->dcap, ix.n, nq, qp->limit, "pann_range_query", &status, &whole, &g_err,
+      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
       SearchArgs a;
       a.queries = d_q ? d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
       a.query_ids = d_qid ? d_qid + q0 : nullptr;
       a.nq = cnt; a.starts = idx->stage[3].as<uint32_t>(); a.nstarts = nstarts;
-      a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
+      fill_search_params(a, qp);
       a.dcap = dcap;
       a.out = pann_search_out{};
       a.out.ids = idx->stage[8].as<uint32_t>() + q0 * beam; a.out.out_k = beam;
@@ -1479,33 +1456,17 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
       a.out.visited_count = idx->stage[10].as<uint32_t>() + q0;
       if (int rc = idx->ws.ensure(search_workspace_bytes(ix, a))) return rc;
       if (int rc = launch_beam_search(ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
-      uint32_t st_word = 0;      // the launch's status word (the next launch clears it)
-      PANN_HIP(hipMemcpyAsync(&st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
+      PANN_HIP(hipMemcpyAsync(st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
       PANN_HIP(hipStreamSynchronize(st));
-      status |= st_word;
-    }
-    if (!(status & PANN_STATUS_DROPPED_OVERFLOW)) break;
-    if ((uint64_t)dcap >= dneed) { set_error("pann_range_query: internal dropped-list overflow"); return PANN_ERR_OVERFLOW; }
-    dcap = (uint32_t)std::min<uint64_t>((uint64_t)dcap * 8, (dneed + 63) / 64 * 64);
-  }
-  idx->dcap = std::max(idx->dcap, std::min(dcap, kDropKeep));
+      return PANN_OK;
+    })) return rc;
   // ---- round 2: the BFS, seeded per query with its frontier as it lies on the device (SENTINEL padding is skipped) ----
   if (int rc = range_search_dev(ix, idx->ws, st, d_q, q_stride_bytes, d_qid, nq, idx->stage[8].as<uint32_t>(), beam, 1, radius,
                                 max_results, idx->stage[4].as<uint32_t>(), idx->stage[5].as<uint32_t>(), idx->stage[6].as<uint32_t>(),
                                 idx->stage[7].as<uint32_t>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out_counts, idx->stage[5].p, nq * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  uint32_t widest = 0;
-  for (uint64_t i = 0; i < nq; i++) widest = std::max(widest, out_counts[i]);
-  widest = std::min(widest, max_results);
-  if (widest)         // only the columns any query filled come back (entries past a row's count are unspecified)
-    PANN_HIP(hipMemcpy2DAsync(out_ids, (size_t)max_results * 4, idx->stage[4].p, (size_t)max_results * 4, (size_t)widest * 4, nq,
-                              hipMemcpyDeviceToHost, st));
   if (out_search_cmps) PANN_HIP(hipMemcpyAsync(out_search_cmps, idx->stage[9].p, nq * 4, hipMemcpyDeviceToHost, st));
   if (out_visited) PANN_HIP(hipMemcpyAsync(out_visited, idx->stage[10].p, nq * 4, hipMemcpyDeviceToHost, st));
-  if (out_range_cmps) PANN_HIP(hipMemcpyAsync(out_range_cmps, idx->stage[6].p, nq * 4, hipMemcpyDeviceToHost, st));
-  if (out_truncated) PANN_HIP(hipMemcpyAsync(out_truncated, idx->stage[7].p, nq * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
+  if (int rc = download_range_results(idx, nq, max_results, out_ids, out_counts, out_range_cmps, out_truncated)) return rc;
   if (idx->ws.bytes > (2ull << 30)) idx->ws.release();          // a one-off worst-case scratch is not kept on the handle
   return PANN_OK;
 }
@@ -1871,10 +1832,7 @@ int search_rerank_checks(const pann_index* full, const pann_index* quant, const 
   if (!full || !quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
   if (!qparams || !qp || !out || !out->ids || !out->dists) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
   if (qp->k <= 0) { set_error(f + ": k must be at least 1"); return PANN_ERR_BAD_ARG; }
-  if (qp->k > qp->beam) {  // beamSearch.h:368-372, :549-553
-    set_error("Error: beam search parameter Q = " + std::to_string(qp->beam) + " same size or smaller than k = " + std::to_string(qp->k));
-    return PANN_ERR_BAD_ARG;
-  }
+  if (int rc = k_beam_check(qp)) return rc;
   const DeviceIndex& fx = full->ix;
   const DeviceIndex& qx = quant->ix;
   if (fx.dtype != PANN_F32) { set_error(f + ": the full-precision index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
@@ -1903,10 +1861,10 @@ int search_rerank_checks(const pann_index* full, const pann_index* quant, const 
 int search_rerank_launch(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
                          uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
                          const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                         const MaskedRerank* mask = nullptr) {
+                         const MaskArgs* mask = nullptr) {
   SearchArgs a{};                                  // the fields search_workspace_bytes reads
   a.queries = reinterpret_cast<const uint8_t*>(d_queries); a.nq = nq; a.nstarts = nstarts;
-  a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
+  fill_search_params(a, qp);
   a.dcap = dcap; a.filter = use_filter ? 1 : 0;
   const uint32_t list = mask ? masked_rerank_pool(qp) : (uint32_t)qp->beam;     // ids kept per query between search and rerank
   a.out = pann_search_out{}; a.out.out_k = list;
@@ -1932,6 +1890,50 @@ int masked_rerank_checks(const pann_index* full, const pann_index* quant, const 
   return PANN_OK;
 }
 
+// pann_batch_search_rerank / pann_batch_search_masked_rerank after their checks: one host round trip, with the bitmap rows and
+// the two masked outputs when `mask` (host pointers) is given; `fn` names the entry point in the messages
+int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                       uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts, uint32_t nstarts,
+                       const pann_query_params* qp, const pann_rerank_out* out, const MaskArgs* mask, const char* fn) {
+  for (uint32_t i = 0; i < nstarts; i++)
+    if (starts[i] >= quant->ix.n) { set_error(std::string(fn) + ": start point out of range"); return PANN_ERR_BAD_ARG; }
+  if (nq == 0) return PANN_OK;
+  DeviceGuard g(quant->device);
+  const DeviceIndex& qx = quant->ix;
+  const uint32_t k = (uint32_t)qp->k;
+  HostTrip t(quant);
+  // ---- inputs: the float rows, the starts and the bitmap rows (packed to ceil(n / 32) words each), one transfer up ----
+  const size_t mwords = (size_t)((qx.n + 31) / 32);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * qx.d);
+  const int i_st = t.in.add(starts, (size_t)nstarts * 4);
+  const int i_mask = mask ? t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4) : -1;
+  // ---- outputs: one packed device region (the status word last), one transfer down ----
+  const int o_ids = t.out.add(out->ids, nq * k * 4), o_dists = t.out.add(out->dists, nq * k * 4);
+  const int o_fs = t.out.add(out->frontier_size, nq * 4), o_vcnt = t.out.add(out->visited_count, nq * 4);
+  const int o_cmps = t.out.add(out->dist_cmps, nq * 4);
+  const int o_pruned = t.out.add(use_filter ? out->pruned_cmps : nullptr, nq * 4);       // (no room where it is not asked for)
+  const int o_rcnt = t.out.add(mask ? mask->result_count : nullptr, nq * 4), o_acmps = t.out.add(mask ? mask->allowed_cmps : nullptr, nq * 4);
+  if (int rc = t.begin()) return rc;
+  const uint8_t* d_q = t.din<uint8_t>(i_q);
+  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask ? t.din<uint32_t>(i_mask) : nullptr;
+  uint32_t status = 0;
+  if (int rc = t.run_grown(nq, qp, fn, &status,
+      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, const uint32_t** d_word) -> int {
+      pann_rerank_out d{};
+      d.ids = t.dout<uint32_t>(o_ids, q0 * k); d.dists = t.dout<float>(o_dists, q0 * k);
+      d.frontier_size = t.dout<uint32_t>(o_fs, q0); d.visited_count = t.dout<uint32_t>(o_vcnt, q0);
+      d.dist_cmps = t.dout<uint32_t>(o_cmps, q0);
+      d.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
+      *d_word = d.status = t.status_slot();
+      const MaskArgs m{mask && mask->stride ? d_allow + q0 * mwords : d_allow, mask && mask->stride ? mwords : 0,
+                       t.dout<uint32_t>(o_rcnt, q0), t.dout<uint32_t>(o_acmps, q0)};
+      return search_rerank_launch(full, quant, qparams, (const float*)(d_q + q0 * q_stride_bytes), cnt, q_stride_bytes, normalize_first,
+                                  use_filter, d_starts, nstarts, qp, dcap, d, t.st, mask ? &m : nullptr);
+    })) return rc;
+  if (out->status) *out->status = status;
+  return PANN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1953,64 +1955,8 @@ int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_qua
                              uint32_t nstarts, const pann_query_params* qp, const pann_rerank_out* out) {
   if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, out,
                                     "pann_batch_search_rerank")) return rc;
-  for (uint32_t i = 0; i < nstarts; i++)
-    if (starts[i] >= quant->ix.n) { set_error("pann_batch_search_rerank: start point out of range"); return PANN_ERR_BAD_ARG; }
-  if (nq == 0) return PANN_OK;
-  DeviceGuard g(quant->device);
-  hipStream_t st = quant->stream;
-  const DeviceIndex& qx = quant->ix;
-  const uint32_t k = (uint32_t)qp->k;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  // ---- inputs: the float rows and the starts, packed in pinned memory, one transfer up ----
-  const size_t qbytes = (nq - 1) * q_stride_bytes + 4ull * qx.d;
-  const size_t off_st = al(qbytes), in_bytes = off_st + al((size_t)nstarts * 4);
-  if (int rc = quant->pin_in.ensure(in_bytes)) return rc;
-  if (int rc = quant->stage[2].ensure(in_bytes)) return rc;
-  std::memcpy(quant->pin_in.p, queries, qbytes);
-  std::memcpy((uint8_t*)quant->pin_in.p + off_st, starts, (size_t)nstarts * 4);
-  PANN_HIP(hipMemcpyAsync(quant->stage[2].p, quant->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
-  const float* d_q = quant->stage[2].as<float>();
-  const uint32_t* d_starts = (const uint32_t*)((uint8_t*)quant->stage[2].p + off_st);
-  // ---- outputs: one packed device region (the status word last), one transfer down ----
-  struct Piece { void* host; size_t bytes; size_t off; };
-  Piece pc[6] = {{out->ids, nq * k * 4, 0}, {out->dists, nq * k * 4, 0}, {out->frontier_size, nq * 4, 0},
-                 {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {use_filter ? out->pruned_cmps : nullptr, nq * 4, 0}};
-  size_t out_bytes = 0;
-  for (auto& x : pc) { if (!x.host) x.bytes = 0; x.off = out_bytes; out_bytes += al(x.bytes); }
-  if (int rc = quant->stage[4].ensure(out_bytes + 256)) return rc;
-  if (int rc = quant->pin_out.ensure(out_bytes + 256)) return rc;
-  auto dptr = [&](int i) -> uint8_t* { return pc[i].bytes ? (uint8_t*)quant->stage[4].p + pc[i].off : nullptr; };
-  uint32_t status = 0;
-  bool results_home = false;
-  if (int rc = run_with_dropped_growth(quant, nq, qp, "pann_batch_search_rerank", &status, &results_home,
-      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
-      pann_rerank_out d{};
-      d.ids = (uint32_t*)dptr(0) + q0 * k; d.dists = (float*)dptr(1) + q0 * k;
-      if (dptr(2)) d.frontier_size = (uint32_t*)dptr(2) + q0;
-      if (dptr(3)) d.visited_count = (uint32_t*)dptr(3) + q0;
-      if (dptr(4)) d.dist_cmps = (uint32_t*)dptr(4) + q0;
-      if (dptr(5)) d.pruned_cmps = (uint32_t*)dptr(5) + q0;
-      d.status = (uint32_t*)((uint8_t*)quant->stage[4].p + out_bytes);
-      if (int rc = search_rerank_launch(full, quant, qparams, (const float*)((const uint8_t*)d_q + q0 * q_stride_bytes), cnt,
-                                        q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d, st)) return rc;
-      if (cnt == nq) {             // the normal case: the word travels with the results
-        PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes + 4, hipMemcpyDeviceToHost, st));
-        PANN_HIP(hipStreamSynchronize(st));
-        std::memcpy(st_word, (uint8_t*)quant->pin_out.p + out_bytes, 4);
-      } else {
-        PANN_HIP(hipMemcpyAsync(st_word, d.status, 4, hipMemcpyDeviceToHost, st));
-        PANN_HIP(hipStreamSynchronize(st));
-      }
-      return PANN_OK;
-    })) return rc;
-  if (!results_home) {
-    PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes, hipMemcpyDeviceToHost, st));
-    PANN_HIP(hipStreamSynchronize(st));
-  }
-  if (quant->ws.bytes > (2ull << 30)) quant->ws.release();          // a one-off worst-case scratch is not kept on the handle
-  for (auto& x : pc) if (x.bytes) std::memcpy(x.host, (uint8_t*)quant->pin_out.p + x.off, x.bytes);
-  if (out->status) *out->status = status;
-  return PANN_OK;
+  return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, use_filter, starts, nstarts, qp, out,
+                            nullptr, "pann_batch_search_rerank");
 }
 
 int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
@@ -2023,7 +1969,7 @@ int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, con
   if (nq == 0) return PANN_OK;
   if ((uintptr_t)d_queries % 4 != 0) { set_error("pann_batch_search_masked_rerank_dev: query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(quant->device);
-  const MaskedRerank m{d_allow, allow_stride_words, d_out_result_count, d_out_allowed_cmps};
+  const MaskArgs m{d_allow, allow_stride_words, d_out_result_count, d_out_allowed_cmps};
   return search_rerank_launch(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, 0, d_starts, nstarts, qp,
                               quant->dcap, *d_out, (hipStream_t)stream, &m);
 }
@@ -2034,70 +1980,9 @@ int pann_batch_search_masked_rerank(pann_index* full, pann_index* quant, const p
                                     const pann_rerank_out* out, uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
   if (int rc = masked_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, allow,
                                     allow_stride_words, out, "pann_batch_search_masked_rerank")) return rc;
-  for (uint32_t i = 0; i < nstarts; i++)
-    if (starts[i] >= quant->ix.n) { set_error("pann_batch_search_masked_rerank: start point out of range"); return PANN_ERR_BAD_ARG; }
-  if (nq == 0) return PANN_OK;
-  DeviceGuard g(quant->device);
-  hipStream_t st = quant->stream;
-  const DeviceIndex& qx = quant->ix;
-  const uint32_t k = (uint32_t)qp->k;
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-  // ---- inputs: the float rows, the starts and the bitmap rows (packed to ceil(n / 32) words each), one transfer up ----
-  const size_t qbytes = (nq - 1) * q_stride_bytes + 4ull * qx.d;
-  const size_t mwords = (size_t)((qx.n + 31) / 32), mrows = allow_stride_words ? (size_t)nq : 1;
-  const size_t off_st = al(qbytes), off_mask = off_st + al((size_t)nstarts * 4), in_bytes = off_mask + al(mrows * mwords * 4);
-  if (int rc = quant->pin_in.ensure(in_bytes)) return rc;
-  if (int rc = quant->stage[2].ensure(in_bytes)) return rc;
-  std::memcpy(quant->pin_in.p, queries, qbytes);
-  std::memcpy((uint8_t*)quant->pin_in.p + off_st, starts, (size_t)nstarts * 4);
-  for (size_t r = 0; r < mrows; r++)
-    std::memcpy((uint8_t*)quant->pin_in.p + off_mask + r * mwords * 4, allow + r * allow_stride_words, mwords * 4);
-  PANN_HIP(hipMemcpyAsync(quant->stage[2].p, quant->pin_in.p, in_bytes, hipMemcpyHostToDevice, st));
-  const float* d_q = quant->stage[2].as<float>();
-  const uint32_t* d_starts = (const uint32_t*)((uint8_t*)quant->stage[2].p + off_st);
-  const uint32_t* d_allow = (const uint32_t*)((uint8_t*)quant->stage[2].p + off_mask);
-  // ---- outputs: one packed device region (the status word last), one transfer down ----
-  struct Piece { void* host; size_t bytes; size_t off; };
-  Piece pc[7] = {{out->ids, nq * k * 4, 0}, {out->dists, nq * k * 4, 0}, {out->frontier_size, nq * 4, 0},
-                 {out->visited_count, nq * 4, 0}, {out->dist_cmps, nq * 4, 0}, {out_result_count, nq * 4, 0},
-                 {out_allowed_cmps, nq * 4, 0}};
-  size_t out_bytes = 0;
-  for (auto& x : pc) { if (!x.host) x.bytes = 0; x.off = out_bytes; out_bytes += al(x.bytes); }
-  if (int rc = quant->stage[4].ensure(out_bytes + 256)) return rc;
-  if (int rc = quant->pin_out.ensure(out_bytes + 256)) return rc;
-  auto dptr = [&](int i) -> uint8_t* { return pc[i].bytes ? (uint8_t*)quant->stage[4].p + pc[i].off : nullptr; };
-  uint32_t status = 0;
-  bool results_home = false;
-  if (int rc = run_with_dropped_growth(quant, nq, qp, "pann_batch_search_masked_rerank", &status, &results_home,
-      [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
-      pann_rerank_out d{};
-      d.ids = (uint32_t*)dptr(0) + q0 * k; d.dists = (float*)dptr(1) + q0 * k;
-      if (dptr(2)) d.frontier_size = (uint32_t*)dptr(2) + q0;
-      if (dptr(3)) d.visited_count = (uint32_t*)dptr(3) + q0;
-      if (dptr(4)) d.dist_cmps = (uint32_t*)dptr(4) + q0;
-      d.status = (uint32_t*)((uint8_t*)quant->stage[4].p + out_bytes);
-      const MaskedRerank m{allow_stride_words ? d_allow + q0 * mwords : d_allow, allow_stride_words ? mwords : 0,
-                           dptr(5) ? (uint32_t*)dptr(5) + q0 : nullptr, dptr(6) ? (uint32_t*)dptr(6) + q0 : nullptr};
-      if (int rc = search_rerank_launch(full, quant, qparams, (const float*)((const uint8_t*)d_q + q0 * q_stride_bytes), cnt,
-                                        q_stride_bytes, normalize_first, 0, d_starts, nstarts, qp, dcap, d, st, &m)) return rc;
-      if (cnt == nq) {             // the normal case: the word travels with the results
-        PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes + 4, hipMemcpyDeviceToHost, st));
-        PANN_HIP(hipStreamSynchronize(st));
-        std::memcpy(st_word, (uint8_t*)quant->pin_out.p + out_bytes, 4);
-      } else {
-        PANN_HIP(hipMemcpyAsync(st_word, d.status, 4, hipMemcpyDeviceToHost, st));
-        PANN_HIP(hipStreamSynchronize(st));
-      }
-      return PANN_OK;
-    })) return rc;
-  if (!results_home) {
-    PANN_HIP(hipMemcpyAsync(quant->pin_out.p, quant->stage[4].p, out_bytes, hipMemcpyDeviceToHost, st));
-    PANN_HIP(hipStreamSynchronize(st));
-  }
-  if (quant->ws.bytes > (2ull << 30)) quant->ws.release();          // a one-off worst-case scratch is not kept on the handle
-  for (auto& x : pc) if (x.bytes) std::memcpy(x.host, (uint8_t*)quant->pin_out.p + x.off, x.bytes);
-  if (out->status) *out->status = status;
-  return PANN_OK;
+  const MaskArgs m{allow, allow_stride_words, out_result_count, out_allowed_cmps};
+  return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, out, &m,
+                            "pann_batch_search_masked_rerank");
 }
 
 }  // extern "C"

@@ -103,6 +103,13 @@ struct SearchArgs {  // one batched beam search, everything device resident
   uint32_t* allowed_cmps = nullptr;          // nq, optional: full distances computed for allowed points
 };
 
+// the extra arguments of the masked entry points (pann_batch_search_masked*, pann_batch_search_masked_rerank*): host or device
+// pointers, as the entry point's other pointers
+struct MaskArgs {
+  const uint32_t* allow; uint64_t stride;          // bitmap rows, as SearchArgs::allow / allow_stride
+  uint32_t* result_count; uint32_t* allowed_cmps;  // nq each, optional
+};
+
 // per-handle scratch that the search kernels need (grown on demand, never shrunk)
 struct Workspace {
   void* buf = nullptr; size_t bytes = 0;
@@ -242,10 +249,6 @@ float sketch_threshold(const pann_sketch_params* p);               // the value 
 // Masked form (mask != null, DESIGN.md "Masked search on the fused path"): the search is the masked one with a result list of
 // masked_rerank_pool(qp) ids per query, the rerank reads that list (result_count entries) instead of the frontier, raises no
 // SHORT_FRONTIER, and the scratch is sized with the pool in place of the beam.
-struct MaskedRerank {
-  const uint32_t* allow; uint64_t stride;          // device bitmap rows, as SearchArgs::allow / allow_stride
-  uint32_t* result_count; uint32_t* allowed_cmps;  // nq each, optional (device)
-};
 inline uint32_t masked_rerank_pool(const pann_query_params* qp) {   // min(k * rerank_factor, beam, 64), at least 1
   const int64_t want = std::max<int64_t>((int64_t)qp->k * qp->rerank_factor, 1);
   return (uint32_t)std::min<int64_t>(std::min<int64_t>(want, std::max<int64_t>(qp->beam, 1)), 64);
@@ -255,7 +258,7 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
                       const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
                       uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
                       const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                      const MaskedRerank* mask = nullptr);
+                      const MaskArgs* mask = nullptr);
 
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,

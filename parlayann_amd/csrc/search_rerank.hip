@@ -270,7 +270,7 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
                       const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
                       uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
                       const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                      const MaskedRerank* mask) {
+                      const MaskArgs* mask) {
   if (nq == 0) return PANN_OK;
   const uint32_t d = full.d, beam = (uint32_t)qp->beam, k = (uint32_t)qp->k;
   if (beam == 0 || beam > 4096) { set_error("pann_rerank: candidates per query must be in [1,4096]"); return PANN_ERR_BAD_ARG; }

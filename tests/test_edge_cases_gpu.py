@@ -215,6 +215,26 @@ def test_dropped_list_grows_instead_of_failing(oracle, beam):
     ix.close()
 
 
+def test_range_query_grows_the_dropped_list_too(oracle):
+    """pann_range_query runs its beam search under the same growth policy as pann_batch_search: a first round that drops more
+    than 256 vertices is run again with a longer list, and the call equals search + range_search composed by hand"""
+    X, G = _line_graph(1500)
+    Q = np.zeros((3, 8), np.float32); Q[:, 0] = [1499.0, 1400.5, 700.0]
+    so = oracle.batch_search(X, G, queries=Q, k=1, beam=16, cut=1.0, out_k=16)
+    assert so["visited_count"].max() > 600
+    o = oracle.range_search(X, G, so["ids"], 6.5, 16, queries=Q)
+    ix = DeviceIndex(X, G)
+    assert ix.dropped_capacity == 256
+    g = ix.range_query(Q, radius=6.5, beam=16, k=1, cut=1.0, max_results=16)
+    assert ix.dropped_capacity > 256
+    c = ix.range_search(ix.batch_search(Q, k=1, beam=16, cut=1.0, out_k=16)["ids"], 6.5, 16, queries=Q)
+    for ref in (c, o):
+        for f in ("ids", "counts", "truncated"):
+            np.testing.assert_array_equal(ref[f], g[f], err_msg=f)
+    np.testing.assert_array_equal(g["search_cmps"], so["dist_cmps"]); np.testing.assert_array_equal(g["visited"], so["visited_count"])
+    ix.close()
+
+
 def test_dropped_list_growth_is_bounded_by_running_the_batch_in_ranges(oracle):
     """growing the dropped list for a whole large batch could ask for tens of GB (nq x min(limit, n) x 8 bytes).
     Above a 1 GiB budget the batch runs in ranges of queries instead; the handle keeps a modest capacity afterwards.
