@@ -21,30 +21,17 @@ int hip_fail(hipError_t e, const char* what) {
   return PANN_ERR_HIP;
 }
 
+constexpr size_t kAllocSlack = 4096;      // a grown buffer gets a quarter more than was asked for, and this
+
 int Workspace::ensure(size_t need) {
   if (need <= bytes) return PANN_OK;
   if (buf) { PANN_HIP(hipFree(buf)); buf = nullptr; bytes = 0; }
-  size_t cap = need + need / 4 + 4096;
+  size_t cap = need + need / 4 + kAllocSlack;
   PANN_HIP(hipMalloc(&buf, cap));
   bytes = cap;
   return PANN_OK;
 }
 void Workspace::release() { if (buf) (void)hipFree(buf); buf = nullptr; bytes = 0; }
-
-// a growable device buffer used for host-pointer entry points
-struct DevBuf {
-  void* p = nullptr; size_t bytes = 0;
-  int ensure(size_t need) {
-    if (need <= bytes) return PANN_OK;
-    if (p) { PANN_HIP(hipFree(p)); p = nullptr; bytes = 0; }
-    size_t cap = need + need / 4 + 256;
-    PANN_HIP(hipMalloc(&p, cap));
-    bytes = cap;
-    return PANN_OK;
-  }
-  void release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-  template <typename T> T* as() { return (T*)p; }
-};
 
 // growable pinned host buffer: host-pointer calls pack their inputs / outputs here so that each direction is ONE
 // DMA transfer (copies from or to pageable memory are staged and synchronised one by one by the runtime)
@@ -53,7 +40,7 @@ struct PinnedBuf {
   int ensure(size_t need) {
     if (need <= bytes) return PANN_OK;
     if (p) { PANN_HIP(hipHostFree(p)); p = nullptr; bytes = 0; }
-    size_t cap = need + need / 4 + 4096;
+    size_t cap = need + need / 4 + kAllocSlack;
     PANN_HIP(hipHostMalloc(&p, cap, hipHostMallocDefault));
     bytes = cap;
     return PANN_OK;
@@ -76,15 +63,19 @@ struct pann_index {
   uint32_t dcap = 256;      // dropped-list capacity of the searches (pann_index_reserve_dropped; grows on overflow)
   uint32_t delete_range_keys = 0;   // pann_index_set_option("delete_range_keys"): most keys one prune of a delete consolidation takes (0 = what the key index allows)
   uint32_t gt_pieces = 0;   // pann_index_set_option("gt_pieces"): pieces of the base per query tile in pann_bruteforce_knn (0 = auto)
-  DevBuf cell_buf;          // locality cell of every point (ensure_locality_cells)
+  Workspace cell_buf;       // locality cell of every point (ensure_locality_cells)
   uint32_t locality_groups = 32;    // ... whose pivots are grouped by their nearest of this many top pivots (0 / 1: no grouping)
   uint32_t locality_pivots = 1024;   // cells of the locality order (pann_index_set_option("locality_pivots"): measurement knob)
   int cells_state = 0;      // 0 not tried, 1 computed, -1 not worth it (table small enough to be cache resident) or switched off
-  DevBuf code_rank, code_rows;   // filter-code table (filter_codes.hip): rank16[n], gcode[n][gstride]
+  Workspace code_rank, code_rows;   // filter-code table (filter_codes.hip): rank16[n], gcode[n][gstride]
   int codes_state = 0;      // 0 not tried, 1 available (rank16 built), -1 unavailable (a slot class has 4 095 or more members) or switched off
-  DevBuf stage[12];      // staging for host-pointer calls
-  PinnedBuf pin_in, pin_out;   // packed pinned staging of pann_batch_search
-  DevBuf sketch_buf;           // attached bit sketch (pann_index_attach_sketch): ix.sketch points into it
+  PinnedBuf pin_in, pin_out;   // HostTrip: the packed inputs / outputs of a host-pointer call in pinned memory ...
+  Workspace trip_in, trip_out; // ... and their device regions
+  Workspace graph_slab, graph_row_ids, graph_bad;   // graph upload / download: a slice of host-layout rows, their row ids, the bad-neighbour flag
+  Workspace batch_ids;         // the ids of a Vamana insert / delete batch, or the permutation of a whole build
+  Workspace pivot_rows, pivot_dists;   // ensure_locality_cells: the pivots as a table; the top-1 distances (released after use)
+  Workspace params_scratch;    // pann_quantize_params / pann_sketch_params_generate: each call is synchronised before it returns, so they share it
+  Workspace sketch_buf;         // attached bit sketch (pann_index_attach_sketch): ix.sketch points into it
   pann_sketch_params sk_params{};   // ... and the parameters it was made with (the fused rerank sketches its queries with them)
 };
 
@@ -185,26 +176,26 @@ int upload_graph_rows(pann_index* idx, const uint32_t* h_rows, uint64_t m, const
   const size_t row_bytes = (size_t)(ix.max_deg + 1) * 4;
   // stream in slices so the staging buffer stays bounded (288 GB HBM, but host slabs can be huge)
   const uint64_t slice = std::max<uint64_t>(1, (256ull << 20) / row_bytes);
-  if (int rc = idx->stage[9].ensure(4)) return rc;
-  PANN_HIP(hipMemsetAsync(idx->stage[9].p, 0, 4, idx->stream));
+  if (int rc = idx->graph_bad.ensure(4)) return rc;
+  PANN_HIP(hipMemsetAsync(idx->graph_bad.buf, 0, 4, idx->stream));
   for (uint64_t r0 = 0; r0 < m; r0 += slice) {
     const uint64_t cnt = std::min(slice, m - r0);
-    int rc = idx->stage[0].ensure(cnt * row_bytes); if (rc) return rc;
-    PANN_HIP(hipMemcpyAsync(idx->stage[0].p, h_rows + r0 * (ix.max_deg + 1), cnt * row_bytes, hipMemcpyHostToDevice, idx->stream));
+    int rc = idx->graph_slab.ensure(cnt * row_bytes); if (rc) return rc;
+    PANN_HIP(hipMemcpyAsync(idx->graph_slab.buf, h_rows + r0 * (ix.max_deg + 1), cnt * row_bytes, hipMemcpyHostToDevice, idx->stream));
     const uint32_t* d_ids = nullptr;
     if (h_row_ids) {
-      rc = idx->stage[1].ensure(cnt * 4); if (rc) return rc;
-      PANN_HIP(hipMemcpyAsync(idx->stage[1].p, h_row_ids + r0, cnt * 4, hipMemcpyHostToDevice, idx->stream));
-      d_ids = idx->stage[1].as<uint32_t>();
+      rc = idx->graph_row_ids.ensure(cnt * 4); if (rc) return rc;
+      PANN_HIP(hipMemcpyAsync(idx->graph_row_ids.buf, h_row_ids + r0, cnt * 4, hipMemcpyHostToDevice, idx->stream));
+      d_ids = idx->graph_row_ids.as<uint32_t>();
     }
     uint32_t* dst = h_row_ids ? ix.graph : ix.graph + r0 * (uint64_t)ix.gstride;
     hipLaunchKernelGGL(graph_to_device_kernel, dim3((uint32_t)cnt), dim3(64), 0, idx->stream,
-                       idx->stage[0].as<uint32_t>(), dst, cnt, ix.max_deg, ix.gstride, d_ids, ix.n, idx->stage[9].as<uint32_t>());
+                       idx->graph_slab.as<uint32_t>(), dst, cnt, ix.max_deg, ix.gstride, d_ids, ix.n, idx->graph_bad.as<uint32_t>());
     PANN_HIP(hipGetLastError());
     PANN_HIP(hipStreamSynchronize(idx->stream));
   }
   uint32_t bad = 0;
-  PANN_HIP(hipMemcpy(&bad, idx->stage[9].p, 4, hipMemcpyDeviceToHost));
+  PANN_HIP(hipMemcpy(&bad, idx->graph_bad.buf, 4, hipMemcpyDeviceToHost));
   if (bad) { set_error("graph upload: neighbour id out of range (>= number of points); those rows were left empty"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
 }
@@ -234,28 +225,28 @@ int ensure_locality_cells(pann_index* idx) {
     idx->cells_state = -1; return PANN_OK;
   }
   hipStream_t st = idx->stream;
-  if (int rc = idx->stage[10].ensure((size_t)NPIV * ix.pstride)) return rc;
-  if (int rc = idx->stage[11].ensure((size_t)ix.n * 4)) return rc;                      // the distances (not kept)
+  if (int rc = idx->pivot_rows.ensure((size_t)NPIV * ix.pstride)) return rc;
+  if (int rc = idx->pivot_dists.ensure((size_t)ix.n * 4)) return rc;                      // the distances (not kept)
   if (int rc = idx->cell_buf.ensure((size_t)ix.n * 4 + 256)) return rc;
   hipLaunchKernelGGL(gather_rows_kernel, dim3(NPIV), dim3(64), 0, st, ix.points, ix.pstride, ix.n, NPIV,
-                     idx->stage[10].as<uint8_t>());
+                     idx->pivot_rows.as<uint8_t>());
   PANN_HIP(hipGetLastError());
   DeviceIndex pix = ix;                       // the pivots as a 256-point table; A rows = all base points, as external rows
-  pix.points = idx->stage[10].as<uint8_t>(); pix.n = NPIV; pix.graph = nullptr; pix.gcode = nullptr; pix.rank16 = nullptr; pix.cell = nullptr;
+  pix.points = idx->pivot_rows.as<uint8_t>(); pix.n = NPIV; pix.graph = nullptr; pix.gcode = nullptr; pix.rank16 = nullptr; pix.cell = nullptr;
   if (int rc = dense_topk_dev(pix, idx->ws2, st, ix.points, ix.pstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                               (uint32_t)((ix.n + 63) / 64), ix.n, NPIV, 1, 1, 0, idx->cell_buf.as<uint32_t>(),
-                              idx->stage[11].as<float>())) return rc;
+                              idx->pivot_dists.as<float>())) return rc;
   if (idx->locality_groups > 1 && NPIV >= 4 * idx->locality_groups && NPIV <= 65536) {
     // the pivots themselves by their nearest of the first `groups` pivots (a prefix of the pivot slab is a table too)
     DeviceIndex gix = pix; gix.n = idx->locality_groups;
-    uint32_t* d_pg = idx->stage[11].as<uint32_t>();                       // [NPIV] group of every pivot, then [NPIV] distances
+    uint32_t* d_pg = idx->pivot_dists.as<uint32_t>();                       // [NPIV] group of every pivot, then [NPIV] distances
     if (int rc = dense_topk_dev(gix, idx->ws2, st, pix.points, ix.pstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                                 (NPIV + 63) / 64, NPIV, gix.n, 1, 1, 0, d_pg, reinterpret_cast<float*>(d_pg + NPIV))) return rc;
     hipLaunchKernelGGL(group_cells_kernel, dim3((uint32_t)((ix.n + 255) / 256)), dim3(256), 0, st, idx->cell_buf.as<uint32_t>(), ix.n, d_pg);
     PANN_HIP(hipGetLastError());
   }
   PANN_HIP(hipStreamSynchronize(st));
-  idx->stage[11].release();
+  idx->pivot_dists.release();
   ix.cell = idx->cell_buf.as<uint32_t>();
   idx->cells_state = 1;
   return PANN_OK;
@@ -393,8 +384,9 @@ void pann_index_destroy(pann_index* idx) {
   if (idx->ix.points) (void)hipFree(idx->ix.points);
   if (idx->ix.graph) (void)hipFree(idx->ix.graph);
   idx->ws.release(); idx->ws2.release(); idx->ws3.release(); idx->ws4.release(); idx->ws_rr.release();
-  for (auto& s : idx->stage) s.release();
-  idx->pin_in.release(); idx->pin_out.release();
+  idx->pin_in.release(); idx->pin_out.release(); idx->trip_in.release(); idx->trip_out.release();
+  idx->graph_slab.release(); idx->graph_row_ids.release(); idx->graph_bad.release(); idx->batch_ids.release();
+  idx->pivot_rows.release(); idx->pivot_dists.release(); idx->params_scratch.release();
   idx->code_rank.release(); idx->code_rows.release(); idx->cell_buf.release();
   idx->sketch_buf.release();
   if (idx->own_stream) (void)hipStreamDestroy(idx->own_stream);
@@ -456,6 +448,7 @@ int64_t pann_index_get_option(const pann_index* idx, const char* name) {
   if (nm == "delete_range_keys") return idx->delete_range_keys;
   if (nm == "locality_order") return idx->ix.cell ? 1 : 0;
   if (nm == "filter_codes") return idx->ix.codes_valid ? 1 : 0;         // are the class codes in step with the graph right now?
+  if (nm == "pinned_bytes") return (int64_t)(idx->pin_in.bytes + idx->pin_out.bytes);   // pinned host memory the handle holds (HostTrip)
   return -1;
 }
 
@@ -479,7 +472,7 @@ int pann_index_set_option(pann_index* idx, const char* name, int64_t value) {
   else if (nm == "locality_order") {        // 0: the builder launches a batch's searches in batch order
     idx->ix.cell = nullptr;
     idx->ix.cell_min_batch = value == 2 ? 64u : 4096u;       // 2: also on small tables and small batches (tests)
-    idx->cells_state = value ? ((idx->cell_buf.p && idx->cells_state == 1) ? 1 : 0) : -2;
+    idx->cells_state = value ? ((idx->cell_buf.buf && idx->cells_state == 1) ? 1 : 0) : -2;
     if (idx->cells_state == 1) idx->ix.cell = idx->cell_buf.as<uint32_t>();
   }
   else if (nm == "filter_codes") {          // 0: the beam-91..128 searches use the id table even where the class codes are available
@@ -499,11 +492,11 @@ int pann_index_get_graph(pann_index* idx, uint32_t* graph_out) {
   const uint64_t slice = std::max<uint64_t>(1, (256ull << 20) / row_bytes);
   for (uint64_t r0 = 0; r0 < ix.n; r0 += slice) {
     const uint64_t cnt = std::min(slice, ix.n - r0);
-    if (int rc = idx->stage[0].ensure(cnt * row_bytes)) return rc;
+    if (int rc = idx->graph_slab.ensure(cnt * row_bytes)) return rc;
     hipLaunchKernelGGL(graph_to_host_layout_kernel, dim3((uint32_t)cnt), dim3(64), 0, idx->stream,
-                       ix.graph + r0 * (uint64_t)ix.gstride, idx->stage[0].as<uint32_t>(), cnt, ix.max_deg, ix.gstride);
+                       ix.graph + r0 * (uint64_t)ix.gstride, idx->graph_slab.as<uint32_t>(), cnt, ix.max_deg, ix.gstride);
     PANN_HIP(hipGetLastError());
-    PANN_HIP(hipMemcpyAsync(graph_out + r0 * (ix.max_deg + 1), idx->stage[0].p, cnt * row_bytes, hipMemcpyDeviceToHost, idx->stream));
+    PANN_HIP(hipMemcpyAsync(graph_out + r0 * (ix.max_deg + 1), idx->graph_slab.buf, cnt * row_bytes, hipMemcpyDeviceToHost, idx->stream));
     PANN_HIP(hipStreamSynchronize(idx->stream));
   }
   return PANN_OK;
@@ -579,37 +572,75 @@ int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const u
 
 }  // extern "C"
 
-// The host round trip of a host-pointer search call.  The caller adds its arrays to `in` and `out`, then: begin() packs the inputs
-// into pin_in and sends them up into stage[2] in ONE transfer, and makes room for the outputs in stage[4] / pin_out (with room
-// for a status word behind them); after the launches the outputs come down into pin_out in ONE transfer and go to their arrays.
+constexpr size_t kQuerySlack = 16;      // kept free behind external query rows: the kernels read a row in 16-byte chunks
+
+// The host round trip of a host-pointer call.  The caller adds its arrays to `in` and `out`, then: begin() packs the inputs into
+// pin_in and sends them up into trip_in in ONE transfer, and makes room for the outputs in trip_out / pin_out (with room for a
+// status word behind them); after the launches finish() brings the outputs down into pin_out in ONE transfer, waits, and hands
+// them to their arrays.  Scratch pieces (PackedLayout::add_scratch) lie in the same regions and are never copied; added last,
+// they take no pinned room either.  Outside the search family an array of kDirectBytes or more is a direct piece: it goes
+// between the caller's memory and its place in the region in a transfer of its own, as every array did before there was a trip.
+// Every array added behind it is direct too (PackedLayout), so the packed pieces are a prefix of the region and only that prefix
+// has pinned room and a packed transfer: the callers add their small arrays first.
+// Unpacking runs at about 15 GB/s on the host (80 MB of pann_leaf_knn_batch results: +5.5 ms; 8 MB of pann_bruteforce_knn: +0.48 ms;
+// the two 400 KB outputs of a 10K-query pann_rerank: +0.06 ms over the 0.51 ms of their own two transfers), so a transfer of its
+// own is the cheaper way from somewhere below 400 KB on; at the bound the copy costs 17 us.  (tools/host_trip_time.py)
+constexpr size_t kDirectBytes = 256u << 10;
+
 struct HostTrip {
   pann_index* h;
   hipStream_t st;
   PackedLayout in, out;
-  explicit HostTrip(pann_index* handle) : h(handle), st(handle->stream) {}
-
-  int begin() {
-    if (int rc = h->pin_in.ensure(in.total)) return rc;
-    if (int rc = h->stage[2].ensure(in.total)) return rc;
-    if (int rc = h->stage[4].ensure(out.total + 256)) return rc;
-    if (int rc = h->pin_out.ensure(out.total + 256)) return rc;
-    in.copy(h->pin_in.p, true);
-    PANN_HIP(hipMemcpyAsync(h->stage[2].p, h->pin_in.p, in.total, hipMemcpyHostToDevice, st));
+  int home = 0;          // leading output pieces that fetch_head() has brought down already
+  // packed_only: the search family, whose results are a few hundred KB and come down with the status word in one transfer
+  explicit HostTrip(pann_index* handle, bool packed_only = false) : h(handle), st(handle->stream) {
+    if (!packed_only) in.direct_from = out.direct_from = kDirectBytes;
+  }
+  int move_direct(const PackedLayout& l, void* region, bool up, int first, int last) {
+    for (int i = first; i < std::min(last, l.count); i++) {
+      if (!l.pc[i].direct) continue;
+      if (up) PANN_HIP(hipMemcpyAsync(l.at(region, i), l.pc[i].host, l.pc[i].bytes, hipMemcpyHostToDevice, st));
+      else PANN_HIP(hipMemcpyAsync(l.pc[i].host, l.at(region, i), l.pc[i].bytes, hipMemcpyDeviceToHost, st));
+    }
     return PANN_OK;
   }
-  template <typename T> const T* din(int piece) const { return (const T*)in.at(h->stage[2].p, piece); }
+
+  int begin() {
+    if (int rc = h->pin_in.ensure(in.host_end)) return rc;
+    if (int rc = h->trip_in.ensure(in.total)) return rc;
+    if (int rc = h->trip_out.ensure(out.total + 256)) return rc;
+    if (int rc = h->pin_out.ensure(out.host_end + 256)) return rc;
+    in.copy(h->pin_in.p, true);
+    if (in.host_end) PANN_HIP(hipMemcpyAsync(h->trip_in.buf, h->pin_in.p, in.host_end, hipMemcpyHostToDevice, st));
+    return move_direct(in, h->trip_in.buf, true, 0, in.count);
+  }
+  template <typename T> const T* din(int piece) const { return (const T*)in.at(h->trip_in.buf, piece); }
   template <typename T> T* dout(int piece, size_t first = 0) const {      // element `first` of an output (null if not asked for)
-    T* p = (T*)out.at(h->stage[4].p, piece);
+    T* p = (T*)out.at(h->trip_out.buf, piece);
     return p ? p + first : nullptr;
   }
-  uint32_t* status_slot() const { return (uint32_t*)((uint8_t*)h->stage[4].p + out.total); }
+  uint32_t* status_slot() const { return (uint32_t*)((uint8_t*)h->trip_out.buf + out.total); }
+
+  // the first npieces outputs ahead of the rest, waited for: the host decides something by them (how many ids to fetch)
+  int fetch_head(int npieces) {
+    const size_t head = std::min(out.end_of(npieces), out.host_end);
+    if (head) PANN_HIP(hipMemcpyAsync(h->pin_out.p, h->trip_out.buf, head, hipMemcpyDeviceToHost, st));
+    if (int rc = move_direct(out, h->trip_out.buf, false, 0, npieces)) return rc;
+    PANN_HIP(hipStreamSynchronize(st));
+    out.copy(h->pin_out.p, false, 0, npieces);
+    home = npieces;
+    return PANN_OK;
+  }
 
   int finish(bool results_home = false) {          // results_home: the packed outputs already sit in pin_out
     if (!results_home) {
-      PANN_HIP(hipMemcpyAsync(h->pin_out.p, h->stage[4].p, out.total, hipMemcpyDeviceToHost, st));
+      const size_t from = out.end_of(home);
+      if (out.host_end > from)
+        PANN_HIP(hipMemcpyAsync((uint8_t*)h->pin_out.p + from, (uint8_t*)h->trip_out.buf + from, out.host_end - from, hipMemcpyDeviceToHost, st));
+      if (int rc = move_direct(out, h->trip_out.buf, false, home, out.count)) return rc;
       PANN_HIP(hipStreamSynchronize(st));
     }
-    out.copy(h->pin_out.p, false);
+    out.copy(h->pin_out.p, false, home);
     return PANN_OK;
   }
 
@@ -617,6 +648,7 @@ struct HostTrip {
   // [q0, q0 + cnt) and say where on the device the launch's status word lies.
   template <class Launch>
   int run_grown(uint64_t nq, const pann_query_params* qp, const char* fn, uint32_t* status, Launch&& launch) {
+    assert(out.host_end == out.total);      // the status word lies behind the outputs and comes down with them: no scratch, no direct piece
     bool results_home = false;
     if (int rc = run_with_dropped_growth(h->dcap, h->ix.n, nq, qp->limit, fn, status, &results_home, &g_err,
         [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
@@ -624,7 +656,7 @@ struct HostTrip {
         if (int rc = launch(q0, cnt, dcap, &d_word)) return rc;
         if (cnt == nq) {           // the whole batch in one launch (the normal case): the word travels with the results, ONE transfer
           if (d_word != status_slot()) PANN_HIP(hipMemcpyAsync(status_slot(), d_word, 4, hipMemcpyDeviceToDevice, st));
-          PANN_HIP(hipMemcpyAsync(h->pin_out.p, h->stage[4].p, out.total + 4, hipMemcpyDeviceToHost, st));
+          PANN_HIP(hipMemcpyAsync(h->pin_out.p, h->trip_out.buf, out.total + 4, hipMemcpyDeviceToHost, st));
           PANN_HIP(hipStreamSynchronize(st));
           std::memcpy(st_word, (uint8_t*)h->pin_out.p + out.total, 4);
         } else {
@@ -669,12 +701,13 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   const DeviceIndex& ix = idx->ix;
   // ---- inputs: packed into pinned memory, one H2D transfer ----
   if (queries && q_stride_bytes < ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
-  HostTrip t(idx);
-  const int i_q = t.in.add(queries ? queries : (const void*)query_ids, queries ? (nq - 1) * q_stride_bytes + ix.dbytes : nq * 4, 16);
+  HostTrip t(idx, true);
+  const int i_q = queries ? t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack) : t.in.add(query_ids, nq * 4);
   const int i_st = t.in.add(starts, (size_t)nst_total * 4);
   // masked: the bitmap rows travel with them, packed to ceil(n / 32) words per row
   const size_t mwords = (size_t)((ix.n + 31) / 32);
   const int i_mask = mask ? t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4) : -1;
+  const int i_sk = filter ? t.in.add_rows(sketch_queries, nq, sk_row, sq_stride) : -1;      // filtered: the sketch rows, dense
   // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
   const size_t ok = out->out_k, vc = out->visited_cap;
   const int o_ids = t.out.add(out->ids, nq * ok * 4), o_dists = t.out.add(out->dists, nq * ok * 4);
@@ -687,10 +720,7 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
   const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
   const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask ? t.din<uint32_t>(i_mask) : nullptr;
-  if (filter && sketch_queries) {      // dense rows of sk_row bytes
-    if (int rc = idx->stage[5].ensure((size_t)nq * sk_row)) return rc;
-    PANN_HIP(hipMemcpy2D(idx->stage[5].p, sk_row, sketch_queries, sq_stride, sk_row, nq, hipMemcpyHostToDevice));
-  }
+  const uint8_t* d_sk = filter ? t.din<uint8_t>(i_sk) : nullptr;
   uint32_t status = 0;
   if (int rc = t.run_grown(nq, qp, "pann_batch_search", &status,
       [&](uint64_t q0, uint64_t cnt, uint32_t dcap, const uint32_t** d_word) -> int {
@@ -709,7 +739,7 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
       a.out.status = nullptr;   // read from the workspace
       a.filter = filter;
       if (filter) {
-        a.sketch_queries = sketch_queries ? (const uint8_t*)idx->stage[5].p + q0 * sk_row : nullptr; a.sq_stride = sk_row;
+        a.sketch_queries = d_sk ? d_sk + q0 * sk_row : nullptr; a.sq_stride = sk_row;
         a.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
       }
       if (mask) {
@@ -786,10 +816,10 @@ int pann_vamana_insert_batch(pann_index* idx, const uint32_t* batch_ids, uint64_
     }
   DeviceGuard g(idx->device);
   if (int rc = ensure_filter_codes(idx, L)) return rc;
-  if (int rc = idx->stage[2].ensure(m * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, batch_ids, m * 4, hipMemcpyHostToDevice, idx->stream));
+  if (int rc = idx->batch_ids.ensure(m * 4)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->batch_ids.buf, batch_ids, m * 4, hipMemcpyHostToDevice, idx->stream));
   if (idx->vcap < default_vcap(L)) idx->vcap = default_vcap(L);
-  return insert_batch_dev(idx->ix, idx->ws2, idx->ws3, idx->ws, idx->ws4, idx->stream, idx->stage[2].as<uint32_t>(), (uint32_t)m,
+  return insert_batch_dev(idx->ix, idx->ws2, idx->ws3, idx->ws, idx->ws4, idx->stream, idx->batch_ids.as<uint32_t>(), (uint32_t)m,
                           start, R, L, alpha, &idx->vcap, stats);
 }
 
@@ -839,9 +869,9 @@ int pann_vamana_delete_batch(pann_index* idx, const uint32_t* del_ids, uint64_t 
       set_error("pann_vamana_delete_batch: id " + std::to_string(del_ids[i]) + " out of range; nothing was changed"); return PANN_ERR_BAD_ARG;
     }
   DeviceGuard g(idx->device);
-  if (int rc = idx->stage[2].ensure(m * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, del_ids, m * 4, hipMemcpyHostToDevice, idx->stream));
-  return vamana_delete_batch_dev(idx->ix, idx->ws3, idx->ws2, idx->ws4, idx->stream, idx->stage[2].as<uint32_t>(), m, R, alpha,
+  if (int rc = idx->batch_ids.ensure(m * 4)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->batch_ids.buf, del_ids, m * 4, hipMemcpyHostToDevice, idx->stream));
+  return vamana_delete_batch_dev(idx->ix, idx->ws3, idx->ws2, idx->ws4, idx->stream, idx->batch_ids.as<uint32_t>(), m, R, alpha,
                                  idx->delete_range_keys, stats);
 }
 
@@ -943,8 +973,8 @@ int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, doub
   if (int rc = idx->pin_in.ensure(n * 4)) return rc;
   uint32_t* perm = static_cast<uint32_t*>(idx->pin_in.p);
   build_permutation(n, seed, perm);
-  if (int rc = idx->stage[2].ensure(n * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, perm, n * 4, hipMemcpyHostToDevice, idx->stream));
+  if (int rc = idx->batch_ids.ensure(n * 4)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->batch_ids.buf, perm, n * 4, hipMemcpyHostToDevice, idx->stream));
   {
     const uint64_t tot = n * idx->ix.gstride;
     hipLaunchKernelGGL(random_edges_kernel, dim3((uint32_t)((tot + 255) / 256)), dim3(256), 0, idx->stream, idx->ix.graph,
@@ -957,7 +987,7 @@ int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, doub
   if (idx->vcap < default_vcap(L)) idx->vcap = default_vcap(L);
   for (int pass = 0; pass < num_passes; pass++) {
     const double a = (pass == num_passes - 1) ? alpha : 1.0;   // :173-178
-    if (int rc = insert_batch_dev(idx->ix, idx->ws2, idx->ws3, idx->ws, idx->ws4, idx->stream, idx->stage[2].as<uint32_t>(),
+    if (int rc = insert_batch_dev(idx->ix, idx->ws2, idx->ws3, idx->ws, idx->ws4, idx->stream, idx->batch_ids.as<uint32_t>(),
                                   (uint32_t)n, 0u, R, L, a, &idx->vcap, stats))      // floor = 0, ceiling = m (:236-240)
       return rc;
   }
@@ -976,10 +1006,10 @@ int pann_vamana_build(pann_index* idx, uint32_t R, uint32_t L, double alpha, int
   if (int rc = idx->pin_in.ensure(n * 4)) return rc;
   uint32_t* perm = static_cast<uint32_t*>(idx->pin_in.p);
   build_permutation(n, seed, perm);
-  if (int rc = idx->stage[2].ensure(n * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, perm, n * 4, hipMemcpyHostToDevice, idx->stream));
+  if (int rc = idx->batch_ids.ensure(n * 4)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->batch_ids.buf, perm, n * 4, hipMemcpyHostToDevice, idx->stream));
   PANN_HIP(hipStreamSynchronize(idx->stream));
-  const uint32_t* d_perm = idx->stage[2].as<uint32_t>();
+  const uint32_t* d_perm = idx->batch_ids.as<uint32_t>();
   if (int rc = ensure_filter_codes(idx, L)) return rc;
   if (idx->vcap < default_vcap(L)) idx->vcap = default_vcap(L);
   // vamana/index.h:206-209
@@ -1022,17 +1052,11 @@ int pann_pair_distances(pann_index* idx, const uint32_t* a_ids, const uint32_t* 
   for (uint64_t i = 0; i < m; i++)
     if (a_ids[i] >= idx->ix.n || b_ids[i] >= idx->ix.n) { set_error("pann_pair_distances: id out of range"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
-  if (int rc = idx->stage[2].ensure(m * 4)) return rc;
-  if (int rc = idx->stage[3].ensure(m * 4)) return rc;
-  if (int rc = idx->stage[4].ensure(m * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, a_ids, m * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, b_ids, m * 4, hipMemcpyHostToDevice, st));
-  if (int rc = query_distances_dev(idx->ix, st, nullptr, 0, idx->stage[2].as<uint32_t>(), m, idx->stage[3].as<uint32_t>(), m, 1,
-                                   idx->stage[4].as<float>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out, idx->stage[4].p, m * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+  HostTrip t(idx);
+  const int i_a = t.in.add(a_ids, m * 4), i_b = t.in.add(b_ids, m * 4), o_d = t.out.add(out, m * 4);
+  if (int rc = t.begin()) return rc;
+  if (int rc = query_distances_dev(idx->ix, t.st, nullptr, 0, t.din<uint32_t>(i_a), m, t.din<uint32_t>(i_b), m, 1, t.dout<float>(o_d))) return rc;
+  return t.finish();
 }
 
 int pann_query_distances(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes,
@@ -1044,17 +1068,13 @@ int pann_query_distances(pann_index* idx, const void* queries, uint64_t nq, uint
   for (uint64_t i = 0; i < m; i++)
     if (ids[i] >= idx->ix.n) { set_error("pann_query_distances: id out of range"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
-  if (int rc = idx->stage[2].ensure(nq * q_stride_bytes + 16)) return rc;
-  if (int rc = idx->stage[3].ensure(m * 4)) return rc;
-  if (int rc = idx->stage[4].ensure(nq * m * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, ids, m * 4, hipMemcpyHostToDevice, st));
-  if (int rc = query_distances_dev(idx->ix, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nullptr, nq,
-                                   idx->stage[3].as<uint32_t>(), m, 0, idx->stage[4].as<float>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out, idx->stage[4].p, nq * m * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+  HostTrip t(idx);
+  const int i_ids = t.in.add(ids, m * 4), i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
+  const int o_d = t.out.add(out, nq * m * 4);
+  if (int rc = t.begin()) return rc;
+  if (int rc = query_distances_dev(idx->ix, t.st, t.din<uint8_t>(i_q), q_stride_bytes, nullptr, nq, t.din<uint32_t>(i_ids), m, 0,
+                                   t.dout<float>(o_d))) return rc;
+  return t.finish();
 }
 
 int pann_leaf_knn_batch(pann_index* idx, const uint32_t* ids, const uint64_t* leaf_offsets, uint64_t nleaves,
@@ -1072,29 +1092,21 @@ int pann_leaf_knn_batch(pann_index* idx, const uint32_t* ids, const uint64_t* le
     for (uint64_t a = leaf_offsets[s]; a < leaf_offsets[s + 1]; a += 64) { tseg.push_back((uint32_t)s); ta0.push_back((uint32_t)a); }
   }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
   const size_t nt = tseg.size();
-  if (int rc = idx->stage[2].ensure(total * 4)) return rc;
-  if (int rc = idx->stage[3].ensure((nleaves + 1) * 8)) return rc;
-  if (int rc = idx->stage[4].ensure(nt * 4)) return rc;
-  if (int rc = idx->stage[5].ensure(nt * 4)) return rc;
-  if (int rc = idx->stage[6].ensure(total * m * 4)) return rc;
-  if (int rc = idx->stage[7].ensure(total * m * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, ids, total * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, leaf_offsets, (nleaves + 1) * 8, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[4].p, tseg.data(), nt * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[5].p, ta0.data(), nt * 4, hipMemcpyHostToDevice, st));
+  HostTrip t(idx);
+  const int i_off = t.in.add(leaf_offsets, (nleaves + 1) * 8), i_tseg = t.in.add(tseg.data(), nt * 4), i_ta0 = t.in.add(ta0.data(), nt * 4);
+  const int i_ids = t.in.add(ids, total * 4);
+  const int o_ids = t.out.add(out_ids, total * m * 4), o_dists = t.out.add(out_dists, total * m * 4);
+  if (int rc = t.begin()) return rc;
+  const uint32_t* d_ids = t.din<uint32_t>(i_ids);
+  const uint64_t* d_off = t.din<uint64_t>(i_off);
   if (leaf_knn_rows_eligible(idx->ix, m)) {     // one-byte element types: lane-owns-row kernel (leaf_knn.hip)
-    if (int rc = leaf_knn_rows_dev(idx->ix, idx->ws2, st, idx->stage[2].as<uint32_t>(), idx->stage[3].as<uint64_t>(), leaf_offsets, nleaves, m, 1,
-                                   idx->stage[6].as<uint32_t>(), idx->stage[7].as<float>())) return rc;
-  } else if (int rc = dense_topk_dev(idx->ix, idx->ws2, st, nullptr, 0, idx->stage[2].as<uint32_t>(), idx->stage[2].as<uint32_t>(),
-                              idx->stage[3].as<uint64_t>(), idx->stage[3].as<uint64_t>(), idx->stage[4].as<uint32_t>(),
-                              idx->stage[5].as<uint32_t>(), (uint32_t)nt, total, total, 1, m, 1,
-                              idx->stage[6].as<uint32_t>(), idx->stage[7].as<float>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out_ids, idx->stage[6].p, total * m * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipMemcpyAsync(out_dists, idx->stage[7].p, total * m * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+    if (int rc = leaf_knn_rows_dev(idx->ix, idx->ws2, t.st, d_ids, d_off, leaf_offsets, nleaves, m, 1, t.dout<uint32_t>(o_ids),
+                                   t.dout<float>(o_dists))) return rc;
+  } else if (int rc = dense_topk_dev(idx->ix, idx->ws2, t.st, nullptr, 0, d_ids, d_ids, d_off, d_off, t.din<uint32_t>(i_tseg),
+                                     t.din<uint32_t>(i_ta0), (uint32_t)nt, total, total, 1, m, 1, t.dout<uint32_t>(o_ids),
+                                     t.dout<float>(o_dists))) return rc;
+  return t.finish();
 }
 
 int pann_leaf_knn(pann_index* idx, const uint32_t* ids, uint32_t N, uint32_t m, uint32_t* out_ids, float* out_dists) {
@@ -1128,20 +1140,15 @@ int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint6
   if (!queries || !out_ids || !out_dists) { set_error("pann_bruteforce_knn: null argument"); return PANN_ERR_BAD_ARG; }
   if (q_stride_bytes < idx->ix.dbytes) { set_error("pann_bruteforce_knn: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
-  if (int rc = idx->stage[2].ensure(nq * q_stride_bytes + 16)) return rc;
-  if (int rc = idx->stage[6].ensure(nq * k * 4)) return rc;
-  if (int rc = idx->stage[7].ensure(nq * k * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, hipMemcpyHostToDevice, st));
+  HostTrip t(idx);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
+  const int o_ids = t.out.add(out_ids, nq * k * 4), o_dists = t.out.add(out_dists, nq * k * 4);
+  if (int rc = t.begin()) return rc;
   const uint32_t ntiles = (uint32_t)((nq + 63) / 64);
   const uint32_t nsplit = choose_gt_pieces(idx, ntiles, (double)dense_gt_slots(idx->ix, k), idx->ix.n);
-  if (int rc = dense_topk_dev(idx->ix, idx->ws2, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nullptr, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, ntiles, nq, idx->ix.n, nsplit, k, 0, idx->stage[6].as<uint32_t>(),
-                              idx->stage[7].as<float>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out_ids, idx->stage[6].p, nq * k * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipMemcpyAsync(out_dists, idx->stage[7].p, nq * k * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+  if (int rc = dense_topk_dev(idx->ix, idx->ws2, t.st, t.din<uint8_t>(i_q), q_stride_bytes, nullptr, nullptr, nullptr, nullptr, nullptr,
+                              nullptr, ntiles, nq, idx->ix.n, nsplit, k, 0, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists))) return rc;
+  return t.finish();
 }
 
 // ---- exact kNN under an allow bitmap (masked_knn.hip, DESIGN.md "Exact masked kNN") ----
@@ -1219,11 +1226,11 @@ int pann_bruteforce_knn_masked(pann_index* idx, const void* queries, uint64_t nq
   // in: the queries and the bitmap rows, packed to ceil(n / 32) words each, in one transfer (as pann_batch_search_masked)
   HostTrip t(idx);
   const size_t mwords = (size_t)((ix.n + 31) / 32);
-  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, 16);
   const int i_mask = t.in.add_rows(allow, allow_stride_words ? (size_t)nq : 1, mwords * 4, (size_t)allow_stride_words * 4);
-  // out: ids, dists and counts in one region, one transfer back
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack);
+  // out: counts, ids and dists in one region (the small one first: ids and dists can be large enough to travel on their own)
   const size_t row_bytes = (size_t)nq * k * 4;
-  const int o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes), o_counts = t.out.add(out_counts, nq * 4);
+  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
   if (int rc = t.begin()) return rc;
   if (int rc = masked_knn_run(idx, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, t.din<uint32_t>(i_mask),
                               allow_stride_words ? mwords : 0, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists), t.dout<uint32_t>(o_counts),
@@ -1248,27 +1255,17 @@ int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_o
     }
   }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
   const size_t nt = tseg.size();
-  if (int rc = idx->stage[2].ensure(total * 4)) return rc;
-  if (int rc = idx->stage[3].ensure(nt * 8)) return rc;
-  if (int rc = idx->stage[4].ensure(nt * 4)) return rc;
-  if (int rc = idx->stage[5].ensure(nt * 4)) return rc;
-  if (int rc = idx->stage[6].ensure(nseg * 4)) return rc;
-  if (int rc = idx->stage[7].ensure(nseg * 4)) return rc;
-  if (int rc = idx->stage[8].ensure(total)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, ids, total * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, tlo.data(), nt * 8, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[4].p, tseg.data(), nt * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[5].p, tcnt.data(), nt * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[6].p, pivot_a, nseg * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[7].p, pivot_b, nseg * 4, hipMemcpyHostToDevice, st));
-  if (int rc = pivot_split_dev(idx->ix, st, idx->stage[2].as<uint32_t>(), idx->stage[4].as<uint32_t>(), idx->stage[3].as<uint64_t>(),
-                               idx->stage[5].as<uint32_t>(), (uint32_t)nt, idx->stage[6].as<uint32_t>(), idx->stage[7].as<uint32_t>(),
-                               idx->stage[8].as<uint8_t>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out_side, idx->stage[8].p, total, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+  HostTrip t(idx);
+  const int i_pa = t.in.add(pivot_a, nseg * 4), i_pb = t.in.add(pivot_b, nseg * 4);
+  const int i_tseg = t.in.add(tseg.data(), nt * 4), i_tcnt = t.in.add(tcnt.data(), nt * 4), i_tlo = t.in.add(tlo.data(), nt * 8);
+  const int i_ids = t.in.add(ids, total * 4);
+  const int o_side = t.out.add(out_side, total);
+  if (int rc = t.begin()) return rc;
+  if (int rc = pivot_split_dev(idx->ix, t.st, t.din<uint32_t>(i_ids), t.din<uint32_t>(i_tseg), t.din<uint64_t>(i_tlo),
+                               t.din<uint32_t>(i_tcnt), (uint32_t)nt, t.din<uint32_t>(i_pa), t.din<uint32_t>(i_pb),
+                               t.dout<uint8_t>(o_side))) return rc;
+  return t.finish();
 }
 
 
@@ -1284,42 +1281,30 @@ int pann_rerank(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_st
       if (cand_ids[i * c + j] >= idx->ix.n) { set_error("pann_rerank: candidate id out of range"); return PANN_ERR_BAD_ARG; }
   }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
-  if (int rc = idx->stage[2].ensure(nq * q_stride_bytes + 16)) return rc;
-  if (int rc = idx->stage[3].ensure(nq * c * 4)) return rc;
-  if (int rc = idx->stage[4].ensure(nq * 4)) return rc;
-  if (int rc = idx->stage[6].ensure(nq * k * 4)) return rc;
-  if (int rc = idx->stage[7].ensure(nq * k * 4)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, cand_ids, nq * c * 4, hipMemcpyHostToDevice, st));
-  if (cand_counts) PANN_HIP(hipMemcpyAsync(idx->stage[4].p, cand_counts, nq * 4, hipMemcpyHostToDevice, st));
-  if (int rc = rerank_dev(idx->ix, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nq, idx->stage[3].as<uint32_t>(), c,
-                          cand_counts ? idx->stage[4].as<uint32_t>() : nullptr, k, resort, idx->stage[6].as<uint32_t>(),
-                          idx->stage[7].as<float>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out_ids, idx->stage[6].p, nq * k * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipMemcpyAsync(out_dists, idx->stage[7].p, nq * k * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+  HostTrip t(idx);
+  const int i_cnt = t.in.add(cand_counts, nq * 4), i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
+  const int i_cand = t.in.add(cand_ids, nq * c * 4);
+  const int o_ids = t.out.add(out_ids, nq * k * 4), o_dists = t.out.add(out_dists, nq * k * 4);
+  if (int rc = t.begin()) return rc;
+  if (int rc = rerank_dev(idx->ix, t.st, t.din<uint8_t>(i_q), q_stride_bytes, nq, t.din<uint32_t>(i_cand), c, t.din<uint32_t>(i_cnt), k,
+                          resort, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists))) return rc;
+  return t.finish();
 }
 
 
-// The tail of a range call.  The counts (stage[5]) come down and are waited for; of the id rows (stage[4]) only the columns any
-// query filled come back (entries past a row's count are unspecified: include/pann.h); then the two optional counters.
-static int download_range_results(pann_index* idx, uint64_t nq, uint32_t max_results, uint32_t* out_ids, uint32_t* out_counts,
-                                  uint32_t* out_cmps, uint32_t* out_truncated) {
-  hipStream_t st = idx->stream;
-  PANN_HIP(hipMemcpyAsync(out_counts, idx->stage[5].p, nq * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
+// The tail of a range call, whose first output piece is the counts and whose id rows are the scratch piece o_ids.  The counts
+// come down and are waited for; of the id rows only the columns any query filled come back, straight into the caller's rows
+// (max_results is a cap, the rows are mostly empty; entries past a row's count are unspecified: include/pann.h); then the
+// other outputs in one transfer.
+static int download_range_results(HostTrip& t, int o_ids, uint64_t nq, uint32_t max_results, uint32_t* out_ids, const uint32_t* out_counts) {
+  if (int rc = t.fetch_head(1)) return rc;
   uint32_t widest = 0;
   for (uint64_t i = 0; i < nq; i++) widest = std::max(widest, out_counts[i]);
   widest = std::min(widest, max_results);
   if (widest)
-    PANN_HIP(hipMemcpy2DAsync(out_ids, (size_t)max_results * 4, idx->stage[4].p, (size_t)max_results * 4, (size_t)widest * 4, nq,
-                              hipMemcpyDeviceToHost, st));
-  if (out_cmps) PANN_HIP(hipMemcpyAsync(out_cmps, idx->stage[6].p, nq * 4, hipMemcpyDeviceToHost, st));
-  if (out_truncated) PANN_HIP(hipMemcpyAsync(out_truncated, idx->stage[7].p, nq * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+    PANN_HIP(hipMemcpy2DAsync(out_ids, (size_t)max_results * 4, t.dout<uint32_t>(o_ids), (size_t)max_results * 4, (size_t)widest * 4, nq,
+                              hipMemcpyDeviceToHost, t.st));
+  return t.finish();
 }
 
 int pann_range_search(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
@@ -1339,22 +1324,18 @@ int pann_range_search(pann_index* idx, const void* queries, const uint32_t* quer
   for (uint64_t i = 0; i < ns_total; i++)
     if (starts[i] != SENTINEL && starts[i] >= ix.n) { set_error("pann_range_search: start id out of range"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
-  const size_t qbytes = queries ? nq * q_stride_bytes + 16 : nq * 4;
-  if (int rc = idx->stage[2].ensure(qbytes)) return rc;
-  if (int rc = idx->stage[3].ensure(ns_total * 4)) return rc;
-  if (int rc = idx->stage[4].ensure(nq * (uint64_t)max_results * 4)) return rc;
-  if (int rc = idx->stage[5].ensure(nq * 4)) return rc;
-  if (int rc = idx->stage[6].ensure(nq * 4)) return rc;
-  if (int rc = idx->stage[7].ensure(nq * 4)) return rc;
-  if (queries) PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + ix.dbytes, hipMemcpyHostToDevice, st));
-  else PANN_HIP(hipMemcpyAsync(idx->stage[2].p, query_ids, nq * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, starts, ns_total * 4, hipMemcpyHostToDevice, st));
-  if (int rc = range_search_dev(ix, idx->ws, st, queries ? idx->stage[2].as<uint8_t>() : nullptr, q_stride_bytes,
-                                queries ? nullptr : idx->stage[2].as<uint32_t>(), nq, idx->stage[3].as<uint32_t>(), nstarts,
-                                starts_per_query, radius_2, max_results, idx->stage[4].as<uint32_t>(),
-                                idx->stage[5].as<uint32_t>(), idx->stage[6].as<uint32_t>(), idx->stage[7].as<uint32_t>())) return rc;
-  return download_range_results(idx, nq, max_results, out_ids, out_counts, out_dist_cmps, out_truncated);
+  HostTrip t(idx);
+  const int i_st = t.in.add(starts, ns_total * 4);
+  const int i_q = queries ? t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack) : t.in.add(query_ids, nq * 4);
+  const int o_counts = t.out.add(out_counts, nq * 4);
+  const int o_cmps = t.out.add_or_scratch(out_dist_cmps, nq * 4), o_trunc = t.out.add_or_scratch(out_truncated, nq * 4);
+  const int o_ids = t.out.add_scratch(nq * (size_t)max_results * 4);
+  if (int rc = t.begin()) return rc;
+  if (int rc = range_search_dev(ix, idx->ws, t.st, queries ? t.din<uint8_t>(i_q) : nullptr, q_stride_bytes,
+                                queries ? nullptr : t.din<uint32_t>(i_q), nq, t.din<uint32_t>(i_st), nstarts, starts_per_query, radius_2,
+                                max_results, t.dout<uint32_t>(o_ids), t.dout<uint32_t>(o_counts), t.dout<uint32_t>(o_cmps),
+                                t.dout<uint32_t>(o_trunc))) return rc;
+  return download_range_results(t, o_ids, nq, max_results, out_ids, out_counts);
 }
 
 
@@ -1374,16 +1355,15 @@ int pann_bruteforce_range(pann_index* idx, const void* queries, uint64_t nq, uin
   if (!queries) { set_error("pann_bruteforce_range: null queries"); return PANN_ERR_BAD_ARG; }
   if (q_stride_bytes < idx->ix.dbytes) { set_error("pann_bruteforce_range: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
   const DeviceIndex& ix = idx->ix;
-  if (int rc = idx->stage[2].ensure(nq * q_stride_bytes + 16)) return rc;
-  if (int rc = idx->stage[7].ensure((nq + 1) * 8)) return rc;
-  PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + ix.dbytes, hipMemcpyHostToDevice, st));
+  HostTrip t(idx);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack);
+  const int o_off = t.out.add(out_offsets, (nq + 1) * 8);
+  if (int rc = t.begin()) return rc;
+  const uint8_t* d_q = t.din<uint8_t>(i_q);
   const uint32_t nsplit = range_join_pieces(ix, nq, idx->gt_pieces);       // pann_index_set_option("gt_pieces")
-  if (int rc = range_join_count_dev(ix, idx->ws2, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nq, radius, nsplit,
-                                    idx->stage[7].as<uint64_t>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out_offsets, idx->stage[7].p, (nq + 1) * 8, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
+  if (int rc = range_join_count_dev(ix, idx->ws2, t.st, d_q, q_stride_bytes, nq, radius, nsplit, t.dout<uint64_t>(o_off))) return rc;
+  if (int rc = t.finish()) return rc;
   const uint64_t total = out_offsets[nq];
   if (!out_ids) return PANN_OK;                                            // count only
   if (ids_capacity < total) {
@@ -1391,12 +1371,11 @@ int pann_bruteforce_range(pann_index* idx, const void* queries, uint64_t nq, uin
     return PANN_ERR_OVERFLOW;
   }
   if (total == 0) return PANN_OK;
-  if (int rc = idx->stage[6].ensure(total * 4)) return rc;
-  if (int rc = range_join_fill_dev(ix, idx->ws2, st, idx->stage[2].as<uint8_t>(), q_stride_bytes, nq, radius, nsplit,
-                                   idx->stage[6].as<uint32_t>())) return rc;
-  PANN_HIP(hipMemcpyAsync(out_ids, idx->stage[6].p, total * 4, hipMemcpyDeviceToHost, st));
-  PANN_HIP(hipStreamSynchronize(st));
-  return PANN_OK;
+  HostTrip fill(idx);       // a second trip for the ids, now that their number is known: no inputs, so the queries stay where they are
+  const int o_ids = fill.out.add(out_ids, total * 4);
+  if (int rc = fill.begin()) return rc;
+  if (int rc = range_join_fill_dev(ix, idx->ws2, fill.st, d_q, q_stride_bytes, nq, radius, nsplit, fill.dout<uint32_t>(o_ids))) return rc;
+  return fill.finish();
 }
 
 int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
@@ -1421,24 +1400,20 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
       if (query_ids[i] >= ix.n) { set_error("pann_range_query: query id out of range"); return PANN_ERR_BAD_ARG; }
   if (nq == 0) return PANN_OK;
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
   const uint32_t beam = (uint32_t)qp->beam;
+  HostTrip t(idx);
+  hipStream_t st = t.st;
   // ---- inputs go up once: the queries (or their ids) and the shared starts ----
-  const size_t qbytes = queries ? nq * q_stride_bytes + 16 : nq * 4;
-  if (int rc = idx->stage[2].ensure(qbytes)) return rc;
-  if (int rc = idx->stage[3].ensure((size_t)nstarts * 4)) return rc;
-  if (int rc = idx->stage[8].ensure(nq * (uint64_t)beam * 4)) return rc;      // the frontiers: never leave the device
-  if (int rc = idx->stage[9].ensure(nq * 4)) return rc;                       // dist_cmps of the beam search
-  if (int rc = idx->stage[10].ensure(nq * 4)) return rc;                      // visited_count
-  if (int rc = idx->stage[4].ensure(nq * (uint64_t)max_results * 4)) return rc;
-  if (int rc = idx->stage[5].ensure(nq * 4)) return rc;
-  if (int rc = idx->stage[6].ensure(nq * 4)) return rc;
-  if (int rc = idx->stage[7].ensure(nq * 4)) return rc;
-  if (queries) PANN_HIP(hipMemcpyAsync(idx->stage[2].p, queries, (nq - 1) * q_stride_bytes + ix.dbytes, hipMemcpyHostToDevice, st));
-  else PANN_HIP(hipMemcpyAsync(idx->stage[2].p, query_ids, nq * 4, hipMemcpyHostToDevice, st));
-  PANN_HIP(hipMemcpyAsync(idx->stage[3].p, starts, (size_t)nstarts * 4, hipMemcpyHostToDevice, st));
-  const uint8_t* d_q = queries ? idx->stage[2].as<uint8_t>() : nullptr;
-  const uint32_t* d_qid = queries ? nullptr : idx->stage[2].as<uint32_t>();
+  const int i_st = t.in.add(starts, (size_t)nstarts * 4);
+  const int i_q = queries ? t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack) : t.in.add(query_ids, nq * 4);
+  // ---- outputs: the counts first (download_range_results); the frontiers never leave the device ----
+  const int o_counts = t.out.add(out_counts, nq * 4);
+  const int o_rcmps = t.out.add_or_scratch(out_range_cmps, nq * 4), o_trunc = t.out.add_or_scratch(out_truncated, nq * 4);
+  const int o_scmps = t.out.add_or_scratch(out_search_cmps, nq * 4), o_vis = t.out.add_or_scratch(out_visited, nq * 4);
+  const int o_ids = t.out.add_scratch(nq * (size_t)max_results * 4), o_front = t.out.add_scratch(nq * (size_t)beam * 4);
+  if (int rc = t.begin()) return rc;
+  const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
+  const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
   // ---- round 1: the beam search; a launch that reports a full dropped list is grown and repeated (as batch_search_host) ----
   uint32_t status = 0;
   bool whole = false;
@@ -1447,13 +1422,13 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
       SearchArgs a;
       a.queries = d_q ? d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
       a.query_ids = d_qid ? d_qid + q0 : nullptr;
-      a.nq = cnt; a.starts = idx->stage[3].as<uint32_t>(); a.nstarts = nstarts;
+      a.nq = cnt; a.starts = t.din<uint32_t>(i_st); a.nstarts = nstarts;
       fill_search_params(a, qp);
       a.dcap = dcap;
       a.out = pann_search_out{};
-      a.out.ids = idx->stage[8].as<uint32_t>() + q0 * beam; a.out.out_k = beam;
-      a.out.dist_cmps = idx->stage[9].as<uint32_t>() + q0;
-      a.out.visited_count = idx->stage[10].as<uint32_t>() + q0;
+      a.out.ids = t.dout<uint32_t>(o_front, q0 * beam); a.out.out_k = beam;
+      a.out.dist_cmps = t.dout<uint32_t>(o_scmps, q0);
+      a.out.visited_count = t.dout<uint32_t>(o_vis, q0);
       if (int rc = idx->ws.ensure(search_workspace_bytes(ix, a))) return rc;
       if (int rc = launch_beam_search(ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
       PANN_HIP(hipMemcpyAsync(st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
@@ -1461,12 +1436,10 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
       return PANN_OK;
     })) return rc;
   // ---- round 2: the BFS, seeded per query with its frontier as it lies on the device (SENTINEL padding is skipped) ----
-  if (int rc = range_search_dev(ix, idx->ws, st, d_q, q_stride_bytes, d_qid, nq, idx->stage[8].as<uint32_t>(), beam, 1, radius,
-                                max_results, idx->stage[4].as<uint32_t>(), idx->stage[5].as<uint32_t>(), idx->stage[6].as<uint32_t>(),
-                                idx->stage[7].as<uint32_t>())) return rc;
-  if (out_search_cmps) PANN_HIP(hipMemcpyAsync(out_search_cmps, idx->stage[9].p, nq * 4, hipMemcpyDeviceToHost, st));
-  if (out_visited) PANN_HIP(hipMemcpyAsync(out_visited, idx->stage[10].p, nq * 4, hipMemcpyDeviceToHost, st));
-  if (int rc = download_range_results(idx, nq, max_results, out_ids, out_counts, out_range_cmps, out_truncated)) return rc;
+  if (int rc = range_search_dev(ix, idx->ws, st, d_q, q_stride_bytes, d_qid, nq, t.dout<uint32_t>(o_front), beam, 1, radius, max_results,
+                                t.dout<uint32_t>(o_ids), t.dout<uint32_t>(o_counts), t.dout<uint32_t>(o_rcmps),
+                                t.dout<uint32_t>(o_trunc))) return rc;
+  if (int rc = download_range_results(t, o_ids, nq, max_results, out_ids, out_counts)) return rc;
   if (idx->ws.bytes > (2ull << 30)) idx->ws.release();          // a one-off worst-case scratch is not kept on the handle
   return PANN_OK;
 }
@@ -1537,7 +1510,31 @@ int check_quant_source(const pann_index* src, int kind, const char* fn) {
 // scratch of the handle-less _dev form: one small buffer per device, allocated on first use; the lock is held for the call
 // (pann_quantize_params_dev synchronises anyway)
 std::mutex g_qscratch_mu;
-DevBuf g_qscratch[64];
+Workspace g_qscratch[64];
+
+// The handle-free host forms (pann_quantize_rows, pann_sketch_rows): n host rows of floats go through the current device a slice of
+// 256 MiB at a time (query sets are small; a base that is not resident streams through here) -- dense copy up, per_slice(d_in, cnt,
+// d_out) on the null stream, dense copy of the out_row_bytes results down.  The two slice buffers are freed on every way out.
+template <class PerSlice>
+int rows_through_device(const float* rows, uint64_t n, uint64_t stride_bytes, size_t in_row_bytes, void* out, uint64_t out_stride_bytes,
+                        size_t out_row_bytes, PerSlice&& per_slice) {
+  const uint64_t slice = std::max<uint64_t>(1, (256ull << 20) / in_row_bytes);
+  Workspace in, ob;
+  auto done = [&](int rc) { in.release(); ob.release(); return rc; };
+  const uint64_t cap = std::min(slice, n);
+  if (int rc = in.ensure(cap * in_row_bytes)) return done(rc);
+  if (int rc = ob.ensure(cap * out_row_bytes)) return done(rc);
+  for (uint64_t r0 = 0; r0 < n; r0 += slice) {
+    const uint64_t cnt = std::min(slice, n - r0);
+    hipError_t e = hipMemcpy2D(in.buf, in_row_bytes, (const uint8_t*)rows + r0 * stride_bytes, stride_bytes, in_row_bytes, cnt, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(rows)"));
+    if (int rc = per_slice(in.as<float>(), cnt, ob.buf)) return done(rc);
+    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
+    e = hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ob.buf, out_row_bytes, out_row_bytes, cnt, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(out)"));
+  }
+  return done(PANN_OK);
+}
 
 }  // namespace
 
@@ -1562,9 +1559,9 @@ int pann_quantize_params(pann_index* src, int kind, int trim, pann_quant_params*
   if (int rc = check_quant_source(src, kind, "pann_quantize_params")) return rc;
   if (!out) { set_error("pann_quantize_params: null output"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(src->device);
-  if (int rc = src->stage[8].ensure(quant_scratch_bytes())) return rc;
+  if (int rc = src->params_scratch.ensure(quant_scratch_bytes())) return rc;
   const DeviceIndex& ix = src->ix;
-  return quant_params_dev(reinterpret_cast<const float*>(ix.points), ix.n, ix.d, ix.pstride, kind, trim, out, src->stage[8].p, src->stream);
+  return quant_params_dev(reinterpret_cast<const float*>(ix.points), ix.n, ix.d, ix.pstride, kind, trim, out, src->params_scratch.buf, src->stream);
 }
 
 int pann_quantize_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t stride_bytes, int kind, int trim,
@@ -1577,7 +1574,7 @@ int pann_quantize_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64
   if (dev < 0 || dev >= 64) { set_error("pann_quantize_params_dev: device ordinal out of range"); return PANN_ERR_BAD_ARG; }
   std::lock_guard<std::mutex> lk(g_qscratch_mu);
   if (int rc = g_qscratch[dev].ensure(quant_scratch_bytes())) return rc;
-  return quant_params_dev(d_rows, n, d, stride_bytes, kind, trim, out, g_qscratch[dev].p, (hipStream_t)stream);
+  return quant_params_dev(d_rows, n, d, stride_bytes, kind, trim, out, g_qscratch[dev].buf, (hipStream_t)stream);
 }
 
 int pann_index_create_quantized(pann_index** out, pann_index* src, const pann_quant_params* p, int copy_graph) {
@@ -1625,23 +1622,8 @@ int pann_quantize_rows(const pann_quant_params* p, const float* rows, uint64_t n
   if (device < 0 || device >= ndev) { set_error("pann_quantize_rows: device ordinal out of range"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(device);
   if (!g.ok) { set_error("pann_quantize_rows: hipSetDevice failed"); return PANN_ERR_HIP; }
-  // dense device copies of a slice of rows at a time (query sets are small; a base that is not resident streams through here)
-  const uint64_t slice = std::max<uint64_t>(1, (256ull << 20) / (4ull * d));
-  DevBuf in, ob;
-  auto done = [&](int rc) { in.release(); ob.release(); return rc; };
-  const uint64_t cap = std::min(slice, n);
-  if (int rc = in.ensure(cap * d * 4)) return done(rc);
-  if (int rc = ob.ensure(cap * ob_row)) return done(rc);
-  for (uint64_t r0 = 0; r0 < n; r0 += slice) {
-    const uint64_t cnt = std::min(slice, n - r0);
-    hipError_t e = hipMemcpy2D(in.p, (size_t)d * 4, (const uint8_t*)rows + r0 * stride_bytes, stride_bytes, (size_t)d * 4, cnt, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(rows)"));
-    if (int rc = pann_quantize_rows_dev(p, in.as<float>(), cnt, (uint64_t)d * 4, normalize_first, ob.p, ob_row, nullptr)) return done(rc);
-    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
-    e = hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ob.p, ob_row, ob_row, cnt, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(out)"));
-  }
-  return done(PANN_OK);
+  return rows_through_device(rows, n, stride_bytes, (size_t)d * 4, out, out_stride_bytes, ob_row,
+      [&](const float* d_in, uint64_t cnt, void* d_ob) { return pann_quantize_rows_dev(p, d_in, cnt, (uint64_t)d * 4, normalize_first, d_ob, ob_row, nullptr); });
 }
 
 int pann_index_download_points(pann_index* idx, uint64_t first_row, uint64_t nrows, void* out, uint64_t out_stride_bytes) {
@@ -1707,8 +1689,8 @@ int pann_sketch_params_generate(pann_index* src, int kind, pann_sketch_params* o
   const DeviceIndex& ix = src->ix;
   if (ix.n == 0 || ix.d == 0) { set_error("pann_sketch_params_generate: empty index"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(src->device);
-  if (int rc = src->stage[8].ensure(quant_scratch_bytes())) return rc;
-  return sketch_params_dev(reinterpret_cast<const float*>(ix.points), ix.n, ix.d, ix.pstride, kind, out, src->stage[8].p, src->stream);
+  if (int rc = src->params_scratch.ensure(quant_scratch_bytes())) return rc;
+  return sketch_params_dev(reinterpret_cast<const float*>(ix.points), ix.n, ix.d, ix.pstride, kind, out, src->params_scratch.buf, src->stream);
 }
 
 int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch_params* p) {
@@ -1725,7 +1707,7 @@ int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch
   const uint32_t stride = sketch_dev_stride(p->kind, sx.d);
   idx->ix.sketch = nullptr; idx->ix.sk_kind = -1;
   if (int rc = idx->sketch_buf.ensure((size_t)sx.n * stride)) return rc;
-  if (int rc = sketch_translate_dev(p, reinterpret_cast<const float*>(sx.points), sx.n, sx.pstride, idx->sketch_buf.p, stride, stride, src->stream)) return rc;
+  if (int rc = sketch_translate_dev(p, reinterpret_cast<const float*>(sx.points), sx.n, sx.pstride, idx->sketch_buf.buf, stride, stride, src->stream)) return rc;
   PANN_HIP(hipStreamSynchronize(src->stream));
   idx->ix.sketch = idx->sketch_buf.as<uint8_t>(); idx->ix.sk_stride = stride; idx->ix.sk_kind = p->kind;
   idx->sk_params = *p;
@@ -1746,8 +1728,8 @@ int pann_index_upload_sketch(pann_index* idx, const pann_sketch_params* p, const
   idx->ix.sketch = nullptr; idx->ix.sk_kind = -1;
   if (ix.n == 0) { set_error("pann_index_upload_sketch: empty index"); return PANN_ERR_BAD_ARG; }
   if (int rc = idx->sketch_buf.ensure((size_t)ix.n * stride)) return rc;
-  if (stride != row) PANN_HIP(hipMemset(idx->sketch_buf.p, 0, (size_t)ix.n * stride));      // the pad bytes of a device row are zero
-  PANN_HIP(hipMemcpy2D(idx->sketch_buf.p, stride, rows, stride_bytes, row, ix.n, hipMemcpyHostToDevice));
+  if (stride != row) PANN_HIP(hipMemset(idx->sketch_buf.buf, 0, (size_t)ix.n * stride));      // the pad bytes of a device row are zero
+  PANN_HIP(hipMemcpy2D(idx->sketch_buf.buf, stride, rows, stride_bytes, row, ix.n, hipMemcpyHostToDevice));
   idx->ix.sketch = idx->sketch_buf.as<uint8_t>(); idx->ix.sk_stride = stride; idx->ix.sk_kind = p->kind;
   idx->sk_params = *p;
   idx->ix.sk_as_written = (p->kind != PANN_SKETCH_MIPS_2BIT && p->hamming_as_written) ? 1u : 0u;
@@ -1798,22 +1780,8 @@ int pann_sketch_rows(const pann_sketch_params* p, const float* rows, uint64_t n,
   DeviceGuard g(device);
   if (!g.ok) { set_error("pann_sketch_rows: hipSetDevice failed"); return PANN_ERR_HIP; }
   const uint32_t d = (uint32_t)p->dims, row = sketch_row_bytes(p->kind, d);
-  const uint64_t slice = std::max<uint64_t>(1, (256ull << 20) / (4ull * d));
-  DevBuf in, ob;
-  auto done = [&](int rc) { in.release(); ob.release(); return rc; };
-  const uint64_t cap = std::min(slice, n);
-  if (int rc = in.ensure(cap * d * 4)) return done(rc);
-  if (int rc = ob.ensure(cap * row)) return done(rc);
-  for (uint64_t r0 = 0; r0 < n; r0 += slice) {
-    const uint64_t cnt = std::min(slice, n - r0);
-    hipError_t e = hipMemcpy2D(in.p, (size_t)d * 4, (const uint8_t*)rows + r0 * stride_bytes, stride_bytes, (size_t)d * 4, cnt, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(rows)"));
-    if (int rc = pann_sketch_rows_dev(p, in.as<float>(), cnt, (uint64_t)d * 4, ob.p, row, nullptr)) return done(rc);
-    if ((e = hipStreamSynchronize(nullptr)) != hipSuccess) return done(hip_fail(e, "hipStreamSynchronize"));
-    e = hipMemcpy2D((uint8_t*)out + r0 * out_stride_bytes, out_stride_bytes, ob.p, row, row, cnt, hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return done(hip_fail(e, "hipMemcpy2D(out)"));
-  }
-  return done(PANN_OK);
+  return rows_through_device(rows, n, stride_bytes, (size_t)d * 4, out, out_stride_bytes, row,
+      [&](const float* d_in, uint64_t cnt, void* d_ob) { return pann_sketch_rows_dev(p, d_in, cnt, (uint64_t)d * 4, d_ob, row, nullptr); });
 }
 
 }  // extern "C"
@@ -1901,7 +1869,7 @@ int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_par
   DeviceGuard g(quant->device);
   const DeviceIndex& qx = quant->ix;
   const uint32_t k = (uint32_t)qp->k;
-  HostTrip t(quant);
+  HostTrip t(quant, true);
   // ---- inputs: the float rows, the starts and the bitmap rows (packed to ceil(n / 32) words each), one transfer up ----
   const size_t mwords = (size_t)((qx.n + 31) / 32);
   const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * qx.d);

@@ -15,13 +15,22 @@ namespace pann {
 
 // One packed region: host arrays laid out one after the other, each on a 256-byte boundary, so that a call moves them in ONE
 // transfer (inputs: copy() into pinned memory and send up; outputs: bring down into pinned memory and copy() out).  A piece whose
-// host pointer is null takes no room and has no device address: optional arrays are simply added.
+// host pointer is null takes no room and has no device address: optional arrays are simply added.  A scratch piece has room and
+// a device address but no host array: copy() passes it by (what never leaves the device, or leaves it by a transfer of its own).
+// A direct piece is a contiguous host array of direct_from bytes or more: it has its place in the region too, but copy() passes
+// it by and the caller moves it between the host array and that place in a transfer of its own (a large array gains nothing
+// from the pinned copy and would keep as much pinned memory on the handle).  Behind a direct piece every later one-row piece is
+// direct too, whatever its size, so the packed pieces end at host_end and nothing behind it needs pinned room or is carried by
+// the packed transfer; small arrays are therefore added first.
 struct PackedLayout {
   static constexpr int kMaxPieces = 12;
-  struct Piece { void* host; size_t bytes, off, rows, host_stride; };
+  struct Piece { void* host; size_t bytes, off, rows, host_stride; bool direct; };
   Piece pc[kMaxPieces];
   int count = 0;
   size_t total = 0;      // bytes of the region: the sum of the aligned piece sizes
+  size_t host_end = 0;   // where the last packed piece ends: scratch and direct pieces behind it need no pinned room and no packed transfer
+  size_t direct_from = SIZE_MAX;      // one-row pieces of this many bytes or more are direct (set before the first add)
+  bool any_direct = false;
 
   static size_t align(size_t x) { return (x + 255) & ~(size_t)255; }
 
@@ -29,20 +38,35 @@ struct PackedLayout {
   int add_rows(const void* host, size_t rows, size_t row_bytes, size_t host_stride, size_t slack = 0) {
     assert(count < kMaxPieces);
     const size_t bytes = host ? rows * row_bytes : 0;
-    pc[count] = Piece{const_cast<void*>(host), bytes, total, rows, host_stride};
+    const bool direct = rows == 1 && bytes && (bytes >= direct_from || any_direct);
+    any_direct = any_direct || direct;
+    pc[count] = Piece{const_cast<void*>(host), bytes, total, rows, host_stride, direct};
     total += align(bytes ? bytes + slack : 0);
+    if (bytes && !direct) host_end = total;
     return count++;
   }
   // `slack`: bytes kept free behind the piece before the next one is aligned (kernels that read a query row in 16-byte chunks)
   int add(const void* host, size_t bytes, size_t slack = 0) { return add_rows(host, 1, bytes, bytes, slack); }
+  int add_scratch(size_t bytes) {
+    assert(count < kMaxPieces);
+    pc[count] = Piece{nullptr, bytes, total, 1, bytes, false};
+    total += align(bytes);
+    return count++;
+  }
+  // an output that the kernel writes whether or not the caller asked for it
+  int add_or_scratch(const void* host, size_t bytes) { return host ? add(host, bytes) : add_scratch(bytes); }
 
   // the piece's address in a region that starts at `base` (null for an empty piece)
   void* at(void* base, int i) const { return pc[i].bytes ? (void*)((uint8_t*)base + pc[i].off) : nullptr; }
 
-  void copy(void* region, bool to_region) const {      // host arrays -> region (pack the inputs) or back (unpack the outputs)
-    for (int i = 0; i < count; i++) {
+  // where the region ends that holds the first npieces pieces
+  size_t end_of(int npieces) const { return npieces < count ? pc[npieces].off : total; }
+
+  // host arrays -> region (pack the inputs) or back (unpack the outputs), pieces [first, last)
+  void copy(void* region, bool to_region, int first = 0, int last = kMaxPieces) const {
+    for (int i = first; i < std::min(last, count); i++) {
       const size_t rb = pc[i].bytes / std::max<size_t>(pc[i].rows, 1);
-      for (size_t r = 0; r < pc[i].rows && pc[i].bytes; r++) {
+      for (size_t r = 0; r < pc[i].rows && pc[i].bytes && pc[i].host && !pc[i].direct; r++) {
         uint8_t* in_region = (uint8_t*)region + pc[i].off + r * rb, *on_host = (uint8_t*)pc[i].host + r * pc[i].host_stride;
         memcpy(to_region ? in_region : on_host, to_region ? on_host : in_region, rb);
       }

@@ -110,11 +110,12 @@ struct MaskArgs {
   uint32_t* result_count; uint32_t* allowed_cmps;  // nq each, optional
 };
 
-// per-handle scratch that the search kernels need (grown on demand, never shrunk)
+// the one growable device buffer: kernel scratch, staging regions, tables kept on a handle (grown on demand, never shrunk)
 struct Workspace {
   void* buf = nullptr; size_t bytes = 0;
   int ensure(size_t need);
   void release();
+  template <typename T> T* as() const { return (T*)buf; }
 };
 
 void set_error(const std::string& s);

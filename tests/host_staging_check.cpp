@@ -71,6 +71,86 @@ static void layout_checks() {
     for (int r = 0; r < 3; r++) CHECK(memcmp(region + 256 + r * 8, host + 10 + r * 20, 8) == 0);
     CHECK(l.add_rows(nullptr, 3, 8, 20) == 2 && l.at(region, 2) == nullptr && l.total == 512);
   }
+  {   // input, scratch and output pieces mixed: the scratch has room and an address, and no copy touches it or the gaps
+    PackedLayout l;
+    const int a = l.add(host, 10), s1 = l.add_scratch(300), e = l.add(nullptr, 64), b = l.add(host + 10, 257), s2 = l.add_scratch(1);
+    CHECK(l.pc[a].off == 0 && l.pc[s1].off == 256 && l.pc[e].off == 768 && l.pc[b].off == 768 && l.pc[s2].off == 1280);
+    for (int i = 0; i < l.count; i++) CHECK(l.pc[i].off % 256 == 0);
+    CHECK(l.total == 1536 && l.host_end == 1280);      // the scratch counts; what a transfer must cover ends with the last host piece
+    CHECK(l.end_of(1) == 256 && l.end_of(2) == 768 && l.end_of(l.count) == l.total);
+    CHECK(l.at(region, s1) == region + 256 && l.at(region, s2) == region + 1280 && l.at(region, e) == nullptr);
+    memset(region, 0xA5, sizeof region);
+    l.copy(region, true);
+    CHECK(memcmp(region, host, 10) == 0 && memcmp(region + 768, host + 10, 257) == 0);
+    for (int i = 0; i < 2048; i++)
+      if (!(i < 10 || (i >= 768 && i < 768 + 257))) CHECK(region[i] == 0xA5);
+    // the way back, over host arrays of the same sizes: only the two host pieces arrive, the region is only read
+    uint8_t was[2048];
+    memcpy(was, region, sizeof was);
+    PackedLayout o;
+    o.add(back, 10); o.add_scratch(300); o.add(nullptr, 64); o.add(back + 10, 257); o.add_scratch(1);
+    memset(back, 0x5A, sizeof back);
+    o.copy(region, false);
+    CHECK(memcmp(back, host, 267) == 0 && memcmp(region, was, sizeof was) == 0);
+    for (int i = 267; i < 600; i++) CHECK(back[i] == 0x5A);
+    // a range of pieces: the head alone, then the rest
+    memset(back, 0x5A, sizeof back);
+    o.copy(region, false, 0, 1);
+    CHECK(memcmp(back, host, 10) == 0 && back[10] == 0x5A);
+    o.copy(region, false, 1);
+    CHECK(memcmp(back, host, 267) == 0);
+    // an optional counter: a piece where the caller has an array, scratch where not -- room and an address either way
+    PackedLayout c;
+    CHECK(c.add_or_scratch(back, 40) == 0 && c.add_or_scratch(nullptr, 40) == 1);
+    CHECK(c.total == 512 && c.host_end == 256 && c.at(region, 0) == region && c.at(region, 1) == region + 256);
+  }
+  {   // query rows as every upload takes them: host_stride > row_bytes, in an allocation that ends with the last row
+    const size_t nq = 5, row = 24, stride = 64, extent = (nq - 1) * stride + row;
+    uint8_t* q = (uint8_t*)malloc(extent);
+    for (size_t i = 0; i < extent; i++) q[i] = (uint8_t)(i * 13 + 5);
+    PackedLayout l;
+    const int whole = l.add(q, extent, 16), rows = l.add_rows(q, nq, row, stride);
+    CHECK(l.pc[whole].off == 0 && l.pc[rows].off == 512 && l.pc[rows].bytes == nq * row && l.total == 768);
+    memset(region, 0xA5, sizeof region);
+    l.copy(region, true);
+    CHECK(memcmp(region, q, extent) == 0 && region[extent] == 0xA5);
+    for (size_t r = 0; r < nq; r++) CHECK(memcmp(region + 512 + r * row, q + r * stride, row) == 0);
+    CHECK(region[512 + nq * row] == 0xA5);
+    free(q);
+  }
+  {   // direct pieces: a place in the region, no copy, no pinned room when they come last; rows of a table are never direct
+    PackedLayout l;
+    l.direct_from = 256;
+    const int a = l.add(host, 100), rows = l.add_rows(host, 3, 100, 200), big = l.add(host + 300, 256, 16), e = l.add(nullptr, 4096);
+    CHECK(!l.pc[a].direct && !l.pc[rows].direct && l.pc[big].direct && !l.pc[e].direct);
+    CHECK(l.pc[big].off == 768 && l.total == 1280 && l.host_end == 768 && l.at(region, big) == region + 768);
+    memset(region, 0xA5, sizeof region);
+    l.copy(region, true);
+    CHECK(memcmp(region, host, 100) == 0 && memcmp(region + 256, host, 100) == 0 && memcmp(region + 456, host + 400, 100) == 0);
+    for (int i = 768; i < 2048; i++) CHECK(region[i] == 0xA5);
+    uint8_t keep[600];
+    memcpy(keep, host, sizeof keep);
+    l.copy(region, false);                                   // the direct piece's host array is not written either
+    CHECK(memcmp(keep + 300, host + 300, 256) == 0);
+    // behind a direct piece a small one-row piece is direct too: the packed pieces stay a prefix that ends at host_end
+    const int small = l.add(host, 8), tab = l.add_rows(host, 2, 8, 16), sc = l.add_scratch(8);
+    CHECK(l.pc[small].direct && !l.pc[tab].direct && !l.pc[sc].direct && l.pc[small].off == 1280);
+    PackedLayout f;                                          // small pieces first, as the callers add them: nothing pinned behind host_end
+    f.direct_from = 256;
+    f.add(host, 8); f.add(host, 300); f.add(host, 8);
+    CHECK(f.host_end == 256 && f.total == 1024 && !f.pc[0].direct && f.pc[1].direct && f.pc[2].direct);
+    PackedLayout packed;                                     // the default packs whatever the size
+    CHECK(!packed.pc[packed.add(host, 600)].direct && packed.host_end == 768);
+  }
+  {   // a trip with nothing in it
+    PackedLayout l;
+    CHECK(l.total == 0 && l.host_end == 0 && l.end_of(0) == 0);
+    l.add(nullptr, 100); l.add_rows(nullptr, 3, 8, 20); l.add(host, 0);
+    CHECK(l.total == 0 && l.host_end == 0);
+    memset(region, 0xA5, sizeof region);
+    l.copy(region, true); l.copy(region, false);
+    for (int i = 0; i < 2048; i++) CHECK(region[i] == 0xA5);
+  }
 }
 
 static void growth_checks() {

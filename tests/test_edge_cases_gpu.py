@@ -328,3 +328,164 @@ def test_query_dtype_and_width_are_checked_everywhere():
             call(X[:4, :8])
         call(X[:4])
     ix.close()
+
+
+# ---- the host round trip (HostTrip, csrc/api.hip): every host-pointer call shares the handle's staging regions ----
+
+def _trip_data(dtype):
+    """a 300 x 24 table (24-byte or 48-byte rows in a 64-byte device stride), 70 queries, a radius that finds about 12 points per
+    query, and every query's two nearest points (the starts of its BFS)"""
+    X = datasets.sift_like(300, 24, seed=11, dtype=dtype)
+    Q = datasets.sift_like(70, 24, seed=12, dtype=dtype)
+    d2 = ((X.astype(np.float32)[None] - Q.astype(np.float32)[:, None]) ** 2).sum(-1)
+    return X, Q, float(np.percentile(d2, 4)), np.argsort(d2, axis=1, kind="stable")[:, :2].astype(np.uint32)
+
+
+def _filtered_strided(ix, Q, sq, k, beam):
+    """pann_batch_search_filtered with the sketch rows as they lie in a wider host table (sq: a strided 2-D view)"""
+    import ctypes as C
+    from parlayann_amd import _capi
+    from parlayann_amd._capi import QueryParams, SearchOut, check
+    nq = len(Q)
+    assert sq.strides[0] > sq.shape[1] and sq.strides[1] == 1
+    ids = np.empty((nq, k), np.uint32); dists = np.empty((nq, k), np.float32)
+    vis = np.empty(nq, np.uint32); cmps = np.empty(nq, np.uint32); pruned = np.empty(nq, np.uint32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)
+    qp = QueryParams(k=k, beam=beam, cut=1.35, limit=ix.n, degree_limit=ix.max_degree, rerank_factor=100, pad=1.0)
+    out = SearchOut(ids=vp(ids), dists=vp(dists), out_k=k, visited_count=vp(vis), dist_cmps=vp(cmps))
+    starts = np.zeros(1, np.uint32)
+    check(_capi.load().pann_batch_search_filtered(ix.handle, vp(Q), None, nq, Q.shape[1] * Q.itemsize, vp(sq), sq.strides[0], vp(starts), 1,
+                                                  C.byref(qp), C.byref(out), vp(pruned)))
+    return ids, dists, vis, cmps, pruned
+
+
+def _trip_calls(Q, near, sq_wide, radius, nq, rng):
+    """the ported calls in the order the test runs them: (name, fn(index) -> arrays)"""
+    Q70, Q = np.ascontiguousarray(Q[:70]), np.ascontiguousarray(Q[:nq])
+    cand = rng.integers(0, 300, (nq, 8)).astype(np.uint32)
+    counts = rng.integers(0, 9, nq).astype(np.uint32)
+    pa, pb = rng.integers(0, 300, nq * 3).astype(np.uint32), rng.integers(0, 300, nq * 3).astype(np.uint32)
+    members = rng.permutation(300)[:75].astype(np.uint32)
+    near = np.ascontiguousarray(near[:nq])
+    sq = sq_wide[:nq, :8]                                        # 8-byte sketch rows, 24 bytes apart
+    big_a, big_b = rng.integers(0, 300, 70_000).astype(np.uint32), rng.integers(0, 300, 70_000).astype(np.uint32)
+
+    def as_list(r):
+        if isinstance(r, dict):
+            return [r[f] for f in sorted(r)]
+        return list(r) if isinstance(r, (tuple, list)) else [r]
+    calls = [
+        ("bruteforce_knn", lambda ix: ix.bruteforce_knn(Q, 5)),
+        ("rerank with counts", lambda ix: ix.rerank(Q, cand, counts, 4)),
+        ("rerank without counts", lambda ix: ix.rerank(Q, cand, None, 4)),
+        ("query_distances", lambda ix: ix.query_distances(Q, np.arange(0, 300, 7))),
+        ("pair_distances", lambda ix: ix.pair_distances(pa, pb)),
+        ("leaf_knn_batch", lambda ix: ix.leaf_knn_batch(members, [0, 70, 75], 3)),
+        ("pivot_split", lambda ix: ix.pivot_split(members, [0, 70, 75], [1, 2], [3, 4])),
+        ("range_search", lambda ix: ix.range_search(near, radius, 16, queries=Q)),
+        ("range_query", lambda ix: ix.range_query(Q, radius=radius, beam=8, max_results=16)),
+        ("bruteforce_range", lambda ix: ix.bruteforce_range(Q, radius)),       # the count-only call, then the one with ids
+        ("batch_search_filtered", lambda ix: _filtered_strided(ix, Q, sq, 5, 16)),
+        # arrays of 256 KiB and more travel on their own, beside the packed ones (kDirectBytes, csrc/api.hip)
+        ("pair_distances, 280 KB arrays", lambda ix: ix.pair_distances(big_a, big_b)),
+        ("query_distances, 280 KB result", lambda ix: ix.query_distances(Q70, big_a[:1000])),
+    ]
+    return [(name, lambda ix, fn=fn: as_list(fn(ix))) for name, fn in calls]
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.float16])
+def test_one_handle_serves_every_host_pointer_call_like_a_fresh_one(dtype):
+    """Every ported call on ONE handle, interleaved, at nq = 3 and then nq = 70 (the shared regions are used small, regrown and
+    used again; 70 crosses a 64-row tile), equals the same call on a handle created for that call alone, bit for bit.  The
+    reference is this library: the test is about isolation between calls, the oracle tests are about correctness."""
+    from parlayann_amd import sketch
+    X, Q, radius, near = _trip_data(dtype)
+    src = DeviceIndex(X.astype(np.float32), max_degree=8)
+    sp = sketch.sketch_params(src, "euclid_bit")
+    sq_wide = np.zeros((70, 24), np.uint8)
+    sq_wide[:, :8] = sketch.sketch_rows(Q.astype(np.float32), sp)
+    sq_wide[:, 8:] = 0xEE                                        # what lies between the rows must not matter
+    one = DeviceIndex(X, max_degree=8)
+    one.vamana_build(8, 16, 1.2)
+    G = one.get_graph()
+    sketch.attach_sketch(one, src, sp)
+    found = {}
+    for nq in (3, 70):
+        for name, fn in _trip_calls(Q, near, sq_wide, radius, nq, np.random.default_rng(nq)):
+            got = fn(one)
+            fresh = DeviceIndex(X, G)
+            if name == "batch_search_filtered":
+                sketch.attach_sketch(fresh, src, sp)
+            want = fn(fresh)
+            fresh.close()
+            assert len(got) == len(want)
+            for i, (g, w) in enumerate(zip(got, want)):
+                np.testing.assert_array_equal(g, w, err_msg=f"{name} nq={nq} output {i}")
+            if name in ("range_search", "range_query"):
+                found[name] = found.get(name, 0) + int(want[0].sum())           # "counts" sorts first
+            if name == "bruteforce_range":
+                found[name] = found.get(name, 0) + len(want[1])
+    assert len(found) == 3 and all(found.values()), found      # the range calls were not compared on empty results only
+    one.close(); src.close()
+
+
+def test_optional_range_counters_do_not_change_the_required_outputs():
+    """pann_range_search / pann_range_query with each optional counter absent and present: ids (up to each row's count) and
+    counts are the same in every combination, and a counter that is asked for is the same whatever else is"""
+    import ctypes as C
+    import itertools
+    from parlayann_amd import _capi
+    from parlayann_amd._capi import QueryParams, check
+    X, Q, radius, near = _trip_data(np.uint8)
+    ix = DeviceIndex(X, max_degree=8)
+    ix.vamana_build(8, 16, 1.2)
+    lib = _capi.load()
+    nq, cap = len(Q), 16
+    vp = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+    starts = np.zeros(1, np.uint32)
+    qp = QueryParams(k=8, beam=8, cut=0.0, limit=ix.n, degree_limit=ix.max_degree, rerank_factor=100, pad=1.0)
+
+    def run(entry, present):
+        ids = np.full((nq, cap), 0xFFFFFFFF, np.uint32); cnt = np.zeros(nq, np.uint32)
+        opt = [np.full(nq, 0xABCD, np.uint32) if p else None for p in present]
+        if entry == "range_search":
+            check(lib.pann_range_search(ix.handle, vp(Q), None, nq, Q.shape[1], vp(near), near.shape[1], 1, radius, cap, vp(ids), vp(cnt),
+                                        vp(opt[0]), vp(opt[1])))      # per-query starts: each query's two nearest points
+        else:
+            check(lib.pann_range_query(ix.handle, vp(Q), None, nq, Q.shape[1], vp(starts), 1, C.byref(qp), radius, cap, vp(ids), vp(cnt),
+                                       vp(opt[0]), vp(opt[1]), vp(opt[2]), vp(opt[3])))
+        ids[np.arange(cap)[None, :] >= cnt[:, None]] = 0xFFFFFFFF
+        return ids, cnt, opt
+    for entry, nopt in (("range_search", 2), ("range_query", 4)):
+        ids0, cnt0, opt0 = run(entry, (True,) * nopt)
+        assert cnt0.max() > 0, entry      # nothing is compared on empty rows only
+        for present in itertools.product((False, True), repeat=nopt):
+            ids, cnt, opt = run(entry, present)
+            np.testing.assert_array_equal(ids, ids0, err_msg=f"{entry} {present}")
+            np.testing.assert_array_equal(cnt, cnt0, err_msg=f"{entry} {present}")
+            for o, o0 in zip(opt, opt0):
+                if o is not None:
+                    np.testing.assert_array_equal(o, o0, err_msg=f"{entry} {present}")
+    ix.close()
+
+
+def test_large_arrays_travel_on_their_own_with_the_same_results():
+    """Arrays of 256 KiB and more are not packed (kDirectBytes, csrc/api.hip).  A range call of 65 536 queries has its counts and
+    counters that large, so its tail fetches the head and the rest as direct pieces; a masked kNN of 2048 queries, k = 32, has
+    packed counts ahead of direct ids and dists.  Each row must equal the row of the same query in a small, packed call."""
+    X, Q, radius, near = _trip_data(np.uint8)
+    ix = DeviceIndex(X, max_degree=8)
+    ix.vamana_build(8, 16, 1.2)
+    small_ids = np.arange(300, dtype=np.uint32)
+    big_ids = np.arange(65536, dtype=np.uint32) % 300
+    r2 = float(np.percentile(((X.astype(np.float32)[None] - X.astype(np.float32)[:, None]) ** 2).sum(-1), 4))
+    for call in (lambda q: ix.range_search([0, 150], r2, 4, query_ids=q), lambda q: ix.range_query(query_ids=q, radius=r2, beam=8, max_results=4)):
+        want, got = call(small_ids), call(big_ids)
+        assert want["counts"].max() > 0
+        for f in want:
+            np.testing.assert_array_equal(got[f], want[f][big_ids], err_msg=f)
+    rows = np.arange(2048) % 70
+    want, got = ix.bruteforce_knn_masked(Q, 32, np.ones(300, bool)), ix.bruteforce_knn_masked(np.ascontiguousarray(Q[rows]), 32, np.ones(300, bool))
+    for w, g in zip(want, got):
+        np.testing.assert_array_equal(g, w[rows])
+    ix.close()
