@@ -617,7 +617,8 @@ int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_qua
  * Status: NULL bitmap, a stride between 1 and ceil(n / 32) - 1, out_k > beam -> PANN_ERR_BAD_ARG; out_k > 64 ->
  * PANN_ERR_UNSUPPORTED; everything else as pann_batch_search (a dropped-list overflow grows the list and repeats the batch).
  * Per-query rows are staged in one piece with the queries: nq * ceil(n / 32) * 4 bytes of pinned and of device memory (1.25 GB
- * for 10 000 queries at 1M points).  Callers with many per-query masks keep them on the device and use the _dev entry. */
+ * for 10 000 queries at 1M points).  Callers with many per-query masks keep them on the device and use the _dev entry, or give
+ * the points labels and send a predicate per query instead: 8 bytes each (pann_batch_search_labeled, below). */
 int pann_batch_search_masked(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                              const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
@@ -699,6 +700,87 @@ int pann_bruteforce_knn_masked_dev(pann_index* idx, const void* d_queries, uint6
  * current device; no synchronisation, no allocation.  n < 2^32.  NULL pointers, a stride between 1 and ceil(n / 32) - 1 ->
  * PANN_ERR_BAD_ARG. */
 int pann_allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t allow_stride_words, uint32_t* d_counts,
+                         void* stream);
+
+/* ---- label predicates: per-point labels in place of per-query bitmaps (DESIGN.md "Label predicates") ----  This project's own;
+ * the reference has no filters.  A handle can own one uint32 label per point (n words on the device); a query's filter then is a
+ * two-word predicate over the labels instead of a bitmap row of ceil(n / 32) words: 8 bytes per query, whatever n is.
+ *   PANN_PRED_ANY    point i is allowed iff (label[i] & a) != 0          (b is ignored)   any of a category set
+ *   PANN_PRED_MATCH  point i is allowed iff (label[i] & a) == b          all of a set (b == a), none of it (b == 0), equality of a
+ *                                                                         bit field (a tenant id), a tombstone bit with any of these
+ *   PANN_PRED_RANGE  point i is allowed iff a <= label[i] <= b, UNSIGNED, both ends inclusive (a > b allows nothing)
+ * kind is one per call; npreds is 1 (preds[0] for the whole batch) or nq (query q uses preds[q]).
+ * THE RULE: every labeled entry point returns, field for field and bit for bit, what its bitmap twin returns when query q's
+ * bitmap row is { i < n : pred_q(label[i]) } -- pann_batch_search_labeled* <-> pann_batch_search_masked*,
+ * pann_batch_search_labeled_rerank* <-> pann_batch_search_masked_rerank*, pann_bruteforce_knn_labeled* <->
+ * pann_bruteforce_knn_masked* (one predicate <-> the shared bitmap, nq predicates <-> per-query rows).  Everything said at the
+ * twins holds: the walk is not steered by the predicate and its counters do not depend on it, the result list holds at most 64
+ * keys, empty rows are answers, no PANN_STATUS_SHORT_FRONTIER under a filter.
+ * Status, beyond what the twin rejects with the twin's code (out_k > 64, k > 64, use_filter != 0, a four-bit handle on the exact
+ * route -> PANN_ERR_UNSUPPORTED): a handle without labels, an unknown kind, NULL preds, a device preds pointer that is not 8-byte
+ * aligned, npreds not in {1, nq} -> PANN_ERR_BAD_ARG; nq == 0 -> PANN_OK.  Nothing is written on an error. */
+enum { PANN_PRED_ANY = 0, PANN_PRED_MATCH = 1, PANN_PRED_RANGE = 2 };
+typedef struct pann_label_pred { uint32_t a, b; } pann_label_pred;
+
+/* Labels on the handle.  A handle has none until the first set call, which allocates n words, zero filled.  set_labels: host
+ * pointer; rows [first_row, first_row + nrows) get labels[0 .. nrows) -- the range form of pann_index_upload_points, so a refilled
+ * slot of a dynamic index gets its label; waits for the handle's stream first and returns when the labels are in place.
+ * set_labels_dev: device pointer, enqueued on the handle's stream, no synchronisation; allocates on the first call only.
+ * get_labels: rows [first_row, first_row + nrows) to out (host).  drop_labels: frees them (waits for the stream).
+ * has_labels: 1 / 0.  A range outside [0, n), a NULL pointer, get_labels on a handle without labels -> PANN_ERR_BAD_ARG, and
+ * nothing is written (nor allocated).  pann_index_create_quantized copies no labels. */
+int pann_index_set_labels(pann_index* idx, uint64_t first_row, const uint32_t* labels, uint64_t nrows);
+int pann_index_set_labels_dev(pann_index* idx, uint64_t first_row, const uint32_t* d_labels, uint64_t nrows);
+int pann_index_get_labels(pann_index* idx, uint64_t first_row, uint64_t nrows, uint32_t* out);
+int pann_index_drop_labels(pann_index* idx);
+int pann_index_has_labels(const pann_index* idx);
+
+/* pann_batch_search_masked with (kind, preds, npreds) in place of the bitmap.  Host pointers: the predicates travel in the packed
+ * transfer of the queries, 8 bytes per query. */
+int pann_batch_search_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                              int kind, const pann_label_pred* preds, uint64_t npreds, const pann_search_out* out,
+                              uint32_t* out_result_count, uint32_t* out_allowed_cmps);
+/* Device pointers throughout, launched on `stream`; no sync, no alloc beyond the workspace growth of pann_batch_search_dev. */
+int pann_batch_search_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                  uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                  int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_search_out* d_out,
+                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream);
+
+/* pann_batch_search_masked_rerank* with predicates.  The labels are read from `full`, the caller's primary handle; quant needs
+ * none, and its own labels are not consulted. */
+int pann_batch_search_labeled_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams,
+                                         const float* d_queries, uint64_t nq, uint64_t q_stride_bytes, int normalize_first,
+                                         int use_filter, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                         int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_rerank_out* d_out,
+                                         uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream);
+int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                                     uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter,
+                                     const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp, int kind,
+                                     const pann_label_pred* preds, uint64_t npreds, const pann_rerank_out* out,
+                                     uint32_t* out_result_count, uint32_t* out_allowed_cmps);
+
+/* pann_bruteforce_knn_masked* with predicates.
+ *   npreds == 1, k <= 128: the predicate is expanded on the device into one bitmap in the handle's scratch, and the shared-bitmap
+ *     route of pann_bruteforce_knn_masked runs on it -- its one stream synchronisation included.
+ *   npreds == nq, k <= 64: one wavefront per query scans the label array, 2 048 labels a step, no bitmap is materialised; no
+ *     synchronisation and no allocation on the _dev entry. */
+int pann_bruteforce_knn_labeled(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int kind,
+                                const pann_label_pred* preds, uint64_t npreds, uint32_t* out_ids, float* out_dists,
+                                uint32_t* out_counts);
+int pann_bruteforce_knn_labeled_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                    int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_out_ids,
+                                    float* d_out_dists, uint32_t* d_out_counts, void* stream);
+
+/* The bridge to every bitmap API: row r of d_allow (rows allow_stride_words >= ceil(n / 32) apart, npreds >= 1 rows) gets the
+ * bitmap of d_preds[r] over the handle's labels, in the format of pann_batch_search_masked; bits at positions >= n of the last
+ * word are written 0, words past ceil(n / 32) are not touched.  Device pointers, on `stream`; no synchronisation, no allocation.
+ * A handle without labels, an unknown kind, NULL or misaligned pointers, a stride below ceil(n / 32) -> PANN_ERR_BAD_ARG. */
+int pann_labels_to_allow_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_allow,
+                             uint64_t allow_stride_words, void* stream);
+/* d_counts[r] = number of points d_preds[r] allows, r < npreds, without materialising rows: what a caller decides exact-or-walk
+ * by.  Device pointers, on `stream`; no synchronisation, no allocation.  Status as pann_labels_to_allow_dev. */
+int pann_label_count_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_counts,
                          void* stream);
 
 #ifdef __cplusplus

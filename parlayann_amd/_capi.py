@@ -79,6 +79,8 @@ class QuantParams(C.Structure):
         return self.kind != PANN_QUANT_EUCLID_U4 and self.slope == 1.0 and self.offset == 0      # the 4-bit translate never casts
 
 
+PANN_PRED_ANY, PANN_PRED_MATCH, PANN_PRED_RANGE = 0, 1, 2      # pann_label_pred kinds: two uint32 words (a, b) per predicate
+
 PANN_SKETCH_EUCLID_BIT, PANN_SKETCH_MIPS_BIT, PANN_SKETCH_MIPS_2BIT = 0, 1, 2
 PANN_SKETCH_MAX_DIMS = 2048
 
@@ -210,6 +212,30 @@ SIGNATURES = {
     "pann_bruteforce_knn_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pann_allow_count_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pann_index_set_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "pann_index_set_labels_dev": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]),
+    "pann_index_get_labels": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
+    "pann_index_drop_labels": (C.c_int, [C.c_void_p]),
+    "pann_index_has_labels": (C.c_int, [C.c_void_p]),
+    "pann_batch_search_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                            C.POINTER(QueryParams), C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SearchOut), C.c_void_p,
+                                            C.c_void_p]),
+    "pann_batch_search_labeled_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                C.POINTER(QueryParams), C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SearchOut),
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_batch_search_labeled_rerank": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
+                                                   C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.c_int,
+                                                   C.c_void_p, C.c_uint64, C.POINTER(RerankOut), C.c_void_p, C.c_void_p]),
+    "pann_batch_search_labeled_rerank_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64,
+                                                       C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams),
+                                                       C.c_int, C.c_void_p, C.c_uint64, C.POINTER(RerankOut), C.c_void_p, C.c_void_p,
+                                                       C.c_void_p]),
+    "pann_bruteforce_knn_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
+                                              C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_bruteforce_knn_labeled_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
+                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_labels_to_allow_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "pann_label_count_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -77,6 +77,8 @@ struct pann_index {
   Workspace params_scratch;    // pann_quantize_params / pann_sketch_params_generate: each call is synchronised before it returns, so they share it
   Workspace sketch_buf;         // attached bit sketch (pann_index_attach_sketch): ix.sketch points into it
   pann_sketch_params sk_params{};   // ... and the parameters it was made with (the fused rerank sketches its queries with them)
+  Workspace labels_buf;         // one label word per point (pann_index_set_labels): ix.labels points into it
+  Workspace label_row;          // pann_bruteforce_knn_labeled*, one predicate: its bitmap row, expanded on the device
 };
 
 namespace {
@@ -163,6 +165,25 @@ int allow_stride_check(const char* fn, const char* zero_means, uint64_t stride, 
   if (stride == 0 || stride >= words) return PANN_OK;
   set_error(std::string(fn) + ": allow_stride_words must be 0 (" + zero_means + ") or at least ceil(n / 32) = " + std::to_string(words));
   return PANN_ERR_BAD_ARG;
+}
+
+// the label-predicate arguments of a labeled entry point, as the caller gave them (host or device `preds`, as the entry's pointers)
+struct LabelArgs { int kind; const pann_label_pred* preds; uint64_t npreds; };
+// `owner`: the handle whose labels are read (not null).  dev: `preds` is a device pointer
+int label_checks(const pann_index* owner, const char* fn, const LabelArgs& l, uint64_t nq, bool dev) {
+  const std::string f = fn;
+  if (!owner->ix.labels) { set_error(f + ": the handle has no labels (pann_index_set_labels)"); return PANN_ERR_BAD_ARG; }
+  if (!pred_kind_known(l.kind)) { set_error(f + ": unknown predicate kind " + std::to_string(l.kind)); return PANN_ERR_BAD_ARG; }
+  if (!l.preds) { set_error(f + ": null predicates"); return PANN_ERR_BAD_ARG; }
+  if (dev && (uintptr_t)l.preds % 8 != 0) { set_error(f + ": device predicates must be 8-byte aligned"); return PANN_ERR_BAD_ARG; }
+  if (l.npreds != 1 && l.npreds != nq) { set_error(f + ": npreds must be 1 (one predicate for the batch) or nq"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+// the MaskArgs of a labeled call after label_checks; preds: where the predicates lie for the launch (device)
+MaskArgs label_mask(const pann_index* owner, const LabelArgs& l, const pann_label_pred* d_preds, uint32_t* result_count, uint32_t* allowed_cmps) {
+  MaskArgs m{nullptr, 0, result_count, allowed_cmps};
+  m.labels = owner->ix.labels; m.preds = d_preds; m.pred_stride = l.npreds == 1 ? 0u : 1u; m.pred_kind = l.kind;
+  return m;
 }
 
 void fill_search_params(SearchArgs& a, const pann_query_params* qp) {
@@ -322,6 +343,62 @@ int pann_index_upload_points(pann_index* idx, uint64_t first_row, const void* ro
   return PANN_OK;
 }
 
+// ---- labels (DESIGN.md "Label predicates"): one uint32 per point, owned by the handle ----
+
+// the checks of the three range calls; nothing is allocated or written when one fails
+static int label_range_checks(const pann_index* idx, const char* fn, uint64_t first_row, const void* p, uint64_t nrows) {
+  if (int rc = check_idx(idx, fn)) return rc;
+  if (!p) { set_error(std::string(fn) + ": null argument"); return PANN_ERR_BAD_ARG; }
+  if (first_row > idx->ix.n || nrows > idx->ix.n - first_row) { set_error(std::string(fn) + ": row range outside the index"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+// the first set call: n words, zero filled on the handle's stream
+static int ensure_labels(pann_index* idx) {
+  if (idx->ix.labels) return PANN_OK;
+  if (int rc = idx->labels_buf.ensure((size_t)idx->ix.n * 4)) return rc;
+  PANN_HIP(hipMemsetAsync(idx->labels_buf.buf, 0, (size_t)idx->ix.n * 4, idx->stream));
+  idx->ix.labels = idx->labels_buf.as<uint32_t>();
+  return PANN_OK;
+}
+
+int pann_index_set_labels(pann_index* idx, uint64_t first_row, const uint32_t* labels, uint64_t nrows) {
+  if (int rc = label_range_checks(idx, "pann_index_set_labels", first_row, labels, nrows)) return rc;
+  DeviceGuard g(idx->device);
+  if (int rc = ensure_labels(idx)) return rc;
+  PANN_HIP(hipStreamSynchronize(idx->stream));                  // no search may be reading the labels being replaced
+  if (nrows) PANN_HIP(hipMemcpy(idx->labels_buf.as<uint32_t>() + first_row, labels, (size_t)nrows * 4, hipMemcpyHostToDevice));
+  return PANN_OK;
+}
+
+int pann_index_set_labels_dev(pann_index* idx, uint64_t first_row, const uint32_t* d_labels, uint64_t nrows) {
+  if (int rc = label_range_checks(idx, "pann_index_set_labels_dev", first_row, d_labels, nrows)) return rc;
+  DeviceGuard g(idx->device);
+  if (int rc = ensure_labels(idx)) return rc;
+  if (nrows) PANN_HIP(hipMemcpyAsync(idx->labels_buf.as<uint32_t>() + first_row, d_labels, (size_t)nrows * 4, hipMemcpyDeviceToDevice, idx->stream));
+  return PANN_OK;
+}
+
+int pann_index_get_labels(pann_index* idx, uint64_t first_row, uint64_t nrows, uint32_t* out) {
+  if (int rc = label_range_checks(idx, "pann_index_get_labels", first_row, out, nrows)) return rc;
+  if (!idx->ix.labels) { set_error("pann_index_get_labels: the handle has no labels (pann_index_set_labels)"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  PANN_HIP(hipStreamSynchronize(idx->stream));
+  if (nrows) PANN_HIP(hipMemcpy(out, idx->ix.labels + first_row, (size_t)nrows * 4, hipMemcpyDeviceToHost));
+  return PANN_OK;
+}
+
+int pann_index_drop_labels(pann_index* idx) {
+  if (int rc = check_idx(idx, "pann_index_drop_labels")) return rc;
+  DeviceGuard g(idx->device);
+  PANN_HIP(hipStreamSynchronize(idx->stream));
+  idx->ix.labels = nullptr;
+  idx->labels_buf.release();
+  return PANN_OK;
+}
+
+int pann_index_has_labels(const pann_index* idx) { return (idx && idx->ix.labels) ? 1 : 0; }
+
 static int index_create_impl(pann_index** out, const void* points, uint64_t n, uint32_t d, int dtype,
                              uint64_t row_stride_bytes, int metric, const uint32_t* graph,
                              uint32_t max_deg, int device) {
@@ -388,7 +465,7 @@ void pann_index_destroy(pann_index* idx) {
   idx->graph_slab.release(); idx->graph_row_ids.release(); idx->graph_bad.release(); idx->batch_ids.release();
   idx->pivot_rows.release(); idx->pivot_dists.release(); idx->params_scratch.release();
   idx->code_rank.release(); idx->code_rows.release(); idx->cell_buf.release();
-  idx->sketch_buf.release();
+  idx->sketch_buf.release(); idx->labels_buf.release(); idx->label_row.release();
   if (idx->own_stream) (void)hipStreamDestroy(idx->own_stream);
   delete idx;
 }
@@ -508,8 +585,10 @@ int pann_index_get_graph(pann_index* idx, uint32_t* graph_out) {
 
 static int mask_checks(const pann_index* idx, const MaskArgs& m, const pann_query_params* qp, const pann_search_out* out) {
   if ((int64_t)out->out_k > qp->beam) { set_error("pann_batch_search_masked: out_k larger than the beam"); return PANN_ERR_BAD_ARG; }
-  if (!m.allow) { set_error("pann_batch_search_masked: null allow bitmap"); return PANN_ERR_BAD_ARG; }
-  if (int rc = allow_stride_check("pann_batch_search_masked", "one shared bitmap", m.stride, idx->ix.n)) return rc;
+  if (!m.by_labels()) {       // (a labeled call has been through label_checks)
+    if (!m.allow) { set_error("pann_batch_search_masked: null allow bitmap"); return PANN_ERR_BAD_ARG; }
+    if (int rc = allow_stride_check("pann_batch_search_masked", "one shared bitmap", m.stride, idx->ix.n)) return rc;
+  }
   if (out->out_k > 64) { set_error("pann_batch_search_masked: out_k > 64 is not supported"); return PANN_ERR_UNSUPPORTED; }
   return PANN_OK;
 }
@@ -540,9 +619,7 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
   a.dcap = idx->dcap;
   a.out = *d_out;
   a.filter = filter; a.sketch_queries = (const uint8_t*)d_sketch_queries; a.sq_stride = sq_stride; a.pruned_cmps = d_pruned;
-  if (mask) {
-    a.masked = 1; a.allow = mask->allow; a.allow_stride = mask->stride; a.result_count = mask->result_count; a.allowed_cmps = mask->allowed_cmps;
-  }
+  if (mask) { mask->apply(a); a.result_count = mask->result_count; a.allowed_cmps = mask->allowed_cmps; }
   if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
   return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, (hipStream_t)stream);
 }
@@ -567,6 +644,17 @@ int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const u
                                  const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
   const MaskArgs m{d_allow, allow_stride_words, d_out_result_count, d_out_allowed_cmps};
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &m);
+}
+
+int pann_batch_search_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                  uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                  int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_search_out* d_out,
+                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
+  if (int rc = check_idx(idx, "pann_batch_search_labeled_dev")) return rc;
+  const LabelArgs l{kind, d_preds, npreds};
+  if (int rc = label_checks(idx, "pann_batch_search_labeled_dev", l, nq, true)) return rc;
+  const MaskArgs m = label_mask(idx, l, d_preds, d_out_result_count, d_out_allowed_cmps);
   return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &m);
 }
 
@@ -704,9 +792,11 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   HostTrip t(idx, true);
   const int i_q = queries ? t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack) : t.in.add(query_ids, nq * 4);
   const int i_st = t.in.add(starts, (size_t)nst_total * 4);
-  // masked: the bitmap rows travel with them, packed to ceil(n / 32) words per row
+  // masked: the bitmap rows travel with them, packed to ceil(n / 32) words per row; labeled: the predicates, 8 bytes per query
   const size_t mwords = (size_t)((ix.n + 31) / 32);
-  const int i_mask = mask ? t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4) : -1;
+  const bool lab = mask && mask->by_labels();
+  const int i_mask = !mask ? -1 : lab ? t.in.add(mask->preds, (mask->pred_stride ? (size_t)nq : 1) * sizeof(pann_label_pred))
+                                      : t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4);
   const int i_sk = filter ? t.in.add_rows(sketch_queries, nq, sk_row, sq_stride) : -1;      // filtered: the sketch rows, dense
   // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
   const size_t ok = out->out_k, vc = out->visited_cap;
@@ -719,7 +809,8 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   if (int rc = t.begin()) return rc;
   const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
   const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
-  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask ? t.din<uint32_t>(i_mask) : nullptr;
+  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask && !lab ? t.din<uint32_t>(i_mask) : nullptr;
+  const pann_label_pred* d_preds = lab ? t.din<pann_label_pred>(i_mask) : nullptr;
   const uint8_t* d_sk = filter ? t.din<uint8_t>(i_sk) : nullptr;
   uint32_t status = 0;
   if (int rc = t.run_grown(nq, qp, "pann_batch_search", &status,
@@ -743,7 +834,9 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
         a.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
       }
       if (mask) {
-        a.masked = 1; a.allow = mask->stride ? d_allow + q0 * mwords : d_allow; a.allow_stride = mask->stride ? mwords : 0;
+        mask->apply(a);
+        if (lab) a.preds = d_preds + q0 * mask->pred_stride;
+        else { a.allow = mask->stride ? d_allow + q0 * mwords : d_allow; a.allow_stride = mask->stride ? mwords : 0; }
         a.result_count = t.dout<uint32_t>(o_rcnt, q0); a.allowed_cmps = t.dout<uint32_t>(o_acmps, q0);
       }
       if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
@@ -776,6 +869,17 @@ int pann_batch_search_masked(pann_index* idx, const void* queries, const uint32_
                              const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
                              uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
   const MaskArgs m{allow, allow_stride_words, out_result_count, out_allowed_cmps};
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &m);
+}
+
+int pann_batch_search_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                              int kind, const pann_label_pred* preds, uint64_t npreds, const pann_search_out* out,
+                              uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
+  if (int rc = check_idx(idx, "pann_batch_search_labeled")) return rc;
+  const LabelArgs l{kind, preds, npreds};
+  if (int rc = label_checks(idx, "pann_batch_search_labeled", l, nq, false)) return rc;
+  const MaskArgs m = label_mask(idx, l, preds, out_result_count, out_allowed_cmps);      // preds: host, staged by batch_search_host
   return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &m);
 }
 
@@ -1162,18 +1266,25 @@ int pann_allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uin
 }
 
 // everything that is refused before anything is launched, allocated or written (host and device entry alike)
+// lab (pann_bruteforce_knn_labeled*): predicates in place of the bitmap -- one for the batch is the shared route, nq the per-query one
 static int masked_knn_checks(const pann_index* idx, const char* fn, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
-                             const uint32_t* allow, uint64_t stride, const uint32_t* out_ids, const float* out_dists, bool* done) {
+                             const uint32_t* allow, uint64_t stride, const uint32_t* out_ids, const float* out_dists, bool* done,
+                             const LabelArgs* lab = nullptr, bool dev = false) {
   *done = false;
   if (int rc = check_idx_no4(idx, fn)) return rc;
   if (nq == 0) { *done = true; return PANN_OK; }
   if (!queries || !out_ids || !out_dists) { set_error(std::string(fn) + ": null argument"); return PANN_ERR_BAD_ARG; }
-  if (!allow) { set_error(std::string(fn) + ": null allow bitmap"); return PANN_ERR_BAD_ARG; }
-  if (int rc = allow_stride_check(fn, "one shared bitmap", stride, idx->ix.n)) return rc;
+  if (lab) {
+    if (int rc = label_checks(idx, fn, *lab, nq, dev)) return rc;
+  } else {
+    if (!allow) { set_error(std::string(fn) + ": null allow bitmap"); return PANN_ERR_BAD_ARG; }
+    if (int rc = allow_stride_check(fn, "one shared bitmap", stride, idx->ix.n)) return rc;
+  }
+  const bool per_query = lab ? lab->npreds != 1 : stride != 0;
   if (q_stride_bytes < idx->ix.dbytes) { set_error(std::string(fn) + ": query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   if (k == 0) { set_error(std::string(fn) + ": k == 0"); return PANN_ERR_BAD_ARG; }
-  if (k > (stride ? 64u : 128u)) {
-    set_error(std::string(fn) + (stride ? ": k > 64 with per-query bitmaps is not supported" : ": k > 128 is not supported"));
+  if (k > (per_query ? 64u : 128u)) {
+    set_error(std::string(fn) + (per_query ? ": k > 64 with per-query bitmaps or predicates is not supported" : ": k > 128 is not supported"));
     return PANN_ERR_UNSUPPORTED;
   }
   return PANN_OK;
@@ -1236,6 +1347,80 @@ int pann_bruteforce_knn_masked(pann_index* idx, const void* queries, uint64_t nq
                               allow_stride_words ? mwords : 0, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists), t.dout<uint32_t>(o_counts),
                               t.st)) return rc;
   return t.finish();
+}
+
+// ---- label predicates on the exact route and the two helpers (masked_knn.hip, DESIGN.md "Label predicates") ----
+
+// both routes on device pointers, after the checks.  One predicate: its bitmap row is expanded into the handle's scratch and the
+// shared-bitmap route runs on it (SYNCHRONISES st, as masked_knn_run says); nq predicates: the label scan, nothing materialised
+static int labeled_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, const LabelArgs& l,
+                           const pann_label_pred* d_preds, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+  const DeviceIndex& ix = idx->ix;
+  if (l.npreds != 1) return label_scan_dev(ix, st, d_q, q_stride_bytes, nq, ix.labels, l.kind, d_preds, k, d_ids, d_dists, d_counts);
+  const uint64_t words = (ix.n + 31) / 32;
+  if (int rc = idx->label_row.ensure((size_t)words * 4)) return rc;
+  if (int rc = labels_to_allow_dev(ix.labels, ix.n, l.kind, d_preds, 1, idx->label_row.as<uint32_t>(), words, st)) return rc;
+  return masked_knn_run(idx, d_q, nq, q_stride_bytes, k, idx->label_row.as<uint32_t>(), 0, d_ids, d_dists, d_counts, st);
+}
+
+int pann_bruteforce_knn_labeled_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                    int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_out_ids,
+                                    float* d_out_dists, uint32_t* d_out_counts, void* stream) {
+  bool done;
+  const LabelArgs l{kind, d_preds, npreds};
+  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_labeled_dev", d_queries, nq, q_stride_bytes, k, nullptr, 0, d_out_ids,
+                                 d_out_dists, &done, &l, true)) return rc;
+  if (done) return PANN_OK;
+  DeviceGuard g(idx->device);
+  return labeled_knn_run(idx, (const uint8_t*)d_queries, nq, q_stride_bytes, k, l, d_preds, d_out_ids, d_out_dists, d_out_counts,
+                         (hipStream_t)stream);
+}
+
+int pann_bruteforce_knn_labeled(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int kind,
+                                const pann_label_pred* preds, uint64_t npreds, uint32_t* out_ids, float* out_dists,
+                                uint32_t* out_counts) {
+  bool done;
+  const LabelArgs l{kind, preds, npreds};
+  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_labeled", queries, nq, q_stride_bytes, k, nullptr, 0, out_ids, out_dists,
+                                 &done, &l, false)) return rc;
+  if (done) return PANN_OK;
+  DeviceGuard g(idx->device);
+  // in: the predicates (8 bytes each) and the queries in one transfer; out: as pann_bruteforce_knn_masked
+  HostTrip t(idx);
+  const int i_pred = t.in.add(preds, (size_t)npreds * sizeof(pann_label_pred));
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
+  const size_t row_bytes = (size_t)nq * k * 4;
+  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
+  if (int rc = t.begin()) return rc;
+  if (int rc = labeled_knn_run(idx, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, l, t.din<pann_label_pred>(i_pred), t.dout<uint32_t>(o_ids),
+                               t.dout<float>(o_dists), t.dout<uint32_t>(o_counts), t.st)) return rc;
+  return t.finish();
+}
+
+// the checks of the two helpers: a handle with labels, a known kind, device pointers that are there and aligned
+static int label_helper_checks(const pann_index* idx, const char* fn, int kind, const pann_label_pred* d_preds, const uint32_t* d_out) {
+  if (int rc = check_idx(idx, fn)) return rc;
+  if (!d_out) { set_error(std::string(fn) + ": null output"); return PANN_ERR_BAD_ARG; }
+  if ((uintptr_t)d_out % 4 != 0) { set_error(std::string(fn) + ": the output must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  return label_checks(idx, fn, LabelArgs{kind, d_preds, 1}, 1, true);      // (any number of predicates: nothing to match it with)
+}
+
+int pann_labels_to_allow_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_allow,
+                             uint64_t allow_stride_words, void* stream) {
+  if (int rc = label_helper_checks(idx, "pann_labels_to_allow_dev", kind, d_preds, d_allow)) return rc;
+  if (allow_stride_words < (idx->ix.n + 31) / 32) {
+    set_error("pann_labels_to_allow_dev: allow_stride_words must be at least ceil(n / 32) = " + std::to_string((idx->ix.n + 31) / 32));
+    return PANN_ERR_BAD_ARG;
+  }
+  DeviceGuard g(idx->device);
+  return labels_to_allow_dev(idx->ix.labels, idx->ix.n, kind, d_preds, npreds, d_allow, allow_stride_words, (hipStream_t)stream);
+}
+
+int pann_label_count_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_counts,
+                         void* stream) {
+  if (int rc = label_helper_checks(idx, "pann_label_count_dev", kind, d_preds, d_counts)) return rc;
+  DeviceGuard g(idx->device);
+  return label_count_dev(idx->ix.labels, idx->ix.n, kind, d_preds, npreds, d_counts, (hipStream_t)stream);
 }
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,
@@ -1836,7 +2021,7 @@ int search_rerank_launch(pann_index* full, pann_index* quant, const pann_quant_p
   a.dcap = dcap; a.filter = use_filter ? 1 : 0;
   const uint32_t list = mask ? masked_rerank_pool(qp) : (uint32_t)qp->beam;     // ids kept per query between search and rerank
   a.out = pann_search_out{}; a.out.out_k = list;
-  a.masked = mask ? 1 : 0;
+  a.masked = !mask ? MASK_NONE : mask->by_labels() ? MASK_LABELS : MASK_BITMAP;
   if (int rc = quant->ws.ensure(search_workspace_bytes(quant->ix, a))) return rc;
   if (int rc = quant->ws_rr.ensure(search_rerank_scratch_bytes(quant->ix, nq, list, normalize_first, use_filter))) return rc;
   return search_rerank_dev(full->ix, quant->ix, quant->ws.buf, quant->ws.bytes, quant->ws_rr.buf, qparams, &quant->sk_params, d_queries,
@@ -1847,19 +2032,25 @@ int search_rerank_launch(pann_index* full, pann_index* quant, const pann_quant_p
 int masked_rerank_checks(const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
                          uint64_t nq, uint64_t q_stride, int use_filter, const uint32_t* starts, uint32_t nstarts,
                          const pann_query_params* qp, const uint32_t* allow, uint64_t allow_stride_words, const pann_rerank_out* out,
-                         const char* fn) {
+                         const char* fn, const LabelArgs* lab = nullptr, bool dev = false) {
   if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride, 0, starts, nstarts, qp, out, fn)) return rc;
   const std::string f = fn;
   if (use_filter) { set_error(f + ": a mask together with the sketch filter is not supported (use_filter must be 0)"); return PANN_ERR_UNSUPPORTED; }
   pann_search_out so{};
   so.out_k = masked_rerank_pool(qp);
-  if (int rc = mask_checks(quant, MaskArgs{allow, allow_stride_words, nullptr, nullptr}, qp, &so)) return rc;
+  MaskArgs m{allow, allow_stride_words, nullptr, nullptr};
+  if (lab) {      // pann_batch_search_labeled_rerank*: the labels are `full`'s
+    if (int rc = label_checks(full, fn, *lab, nq, dev)) return rc;
+    m = label_mask(full, *lab, lab->preds, nullptr, nullptr);
+  }
+  if (int rc = mask_checks(quant, m, qp, &so)) return rc;
   if (qp->k > 64) { set_error(f + ": k > 64 is not supported (the result list holds at most 64 keys)"); return PANN_ERR_UNSUPPORTED; }
   return PANN_OK;
 }
 
-// pann_batch_search_rerank / pann_batch_search_masked_rerank after their checks: one host round trip, with the bitmap rows and
-// the two masked outputs when `mask` (host pointers) is given; `fn` names the entry point in the messages
+// pann_batch_search_rerank / pann_batch_search_masked_rerank / pann_batch_search_labeled_rerank after their checks: one host round
+// trip, with the bitmap rows -- or the predicates -- and the two masked outputs when `mask` (host pointers) is given; `fn` names
+// the entry point in the messages
 int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
                        uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts, uint32_t nstarts,
                        const pann_query_params* qp, const pann_rerank_out* out, const MaskArgs* mask, const char* fn) {
@@ -1874,7 +2065,9 @@ int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_par
   const size_t mwords = (size_t)((qx.n + 31) / 32);
   const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * qx.d);
   const int i_st = t.in.add(starts, (size_t)nstarts * 4);
-  const int i_mask = mask ? t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4) : -1;
+  const bool lab = mask && mask->by_labels();
+  const int i_mask = !mask ? -1 : lab ? t.in.add(mask->preds, (mask->pred_stride ? (size_t)nq : 1) * sizeof(pann_label_pred))
+                                      : t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4);
   // ---- outputs: one packed device region (the status word last), one transfer down ----
   const int o_ids = t.out.add(out->ids, nq * k * 4), o_dists = t.out.add(out->dists, nq * k * 4);
   const int o_fs = t.out.add(out->frontier_size, nq * 4), o_vcnt = t.out.add(out->visited_count, nq * 4);
@@ -1883,7 +2076,8 @@ int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_par
   const int o_rcnt = t.out.add(mask ? mask->result_count : nullptr, nq * 4), o_acmps = t.out.add(mask ? mask->allowed_cmps : nullptr, nq * 4);
   if (int rc = t.begin()) return rc;
   const uint8_t* d_q = t.din<uint8_t>(i_q);
-  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask ? t.din<uint32_t>(i_mask) : nullptr;
+  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask && !lab ? t.din<uint32_t>(i_mask) : nullptr;
+  const pann_label_pred* d_preds = lab ? t.din<pann_label_pred>(i_mask) : nullptr;
   uint32_t status = 0;
   if (int rc = t.run_grown(nq, qp, fn, &status,
       [&](uint64_t q0, uint64_t cnt, uint32_t dcap, const uint32_t** d_word) -> int {
@@ -1893,8 +2087,9 @@ int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_par
       d.dist_cmps = t.dout<uint32_t>(o_cmps, q0);
       d.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
       *d_word = d.status = t.status_slot();
-      const MaskArgs m{mask && mask->stride ? d_allow + q0 * mwords : d_allow, mask && mask->stride ? mwords : 0,
-                       t.dout<uint32_t>(o_rcnt, q0), t.dout<uint32_t>(o_acmps, q0)};
+      MaskArgs m{mask && mask->stride ? d_allow + q0 * mwords : d_allow, mask && mask->stride ? mwords : 0,
+                 t.dout<uint32_t>(o_rcnt, q0), t.dout<uint32_t>(o_acmps, q0)};
+      if (lab) { m.labels = mask->labels; m.preds = d_preds + q0 * mask->pred_stride; m.pred_stride = mask->pred_stride; m.pred_kind = mask->pred_kind; }
       return search_rerank_launch(full, quant, qparams, (const float*)(d_q + q0 * q_stride_bytes), cnt, q_stride_bytes, normalize_first,
                                   use_filter, d_starts, nstarts, qp, dcap, d, t.st, mask ? &m : nullptr);
     })) return rc;
@@ -1951,6 +2146,35 @@ int pann_batch_search_masked_rerank(pann_index* full, pann_index* quant, const p
   const MaskArgs m{allow, allow_stride_words, out_result_count, out_allowed_cmps};
   return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, out, &m,
                             "pann_batch_search_masked_rerank");
+}
+
+int pann_batch_search_labeled_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams,
+                                         const float* d_queries, uint64_t nq, uint64_t q_stride_bytes, int normalize_first,
+                                         int use_filter, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                         int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_rerank_out* d_out,
+                                         uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
+  const LabelArgs l{kind, d_preds, npreds};
+  if (int rc = masked_rerank_checks(full, quant, qparams, d_queries, nq, q_stride_bytes, use_filter, d_starts, nstarts, qp, nullptr, 0,
+                                    d_out, "pann_batch_search_labeled_rerank_dev", &l, true)) return rc;
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)d_queries % 4 != 0) { set_error("pann_batch_search_labeled_rerank_dev: query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  const MaskArgs m = label_mask(full, l, d_preds, d_out_result_count, d_out_allowed_cmps);
+  return search_rerank_launch(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, 0, d_starts, nstarts, qp,
+                              quant->dcap, *d_out, (hipStream_t)stream, &m);
+}
+
+int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                                     uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter,
+                                     const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp, int kind,
+                                     const pann_label_pred* preds, uint64_t npreds, const pann_rerank_out* out,
+                                     uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
+  const LabelArgs l{kind, preds, npreds};
+  if (int rc = masked_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, nullptr, 0, out,
+                                    "pann_batch_search_labeled_rerank", &l, false)) return rc;
+  const MaskArgs m = label_mask(full, l, preds, out_result_count, out_allowed_cmps);      // preds: host, staged by search_rerank_host
+  return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, out, &m,
+                            "pann_batch_search_labeled_rerank");
 }
 
 }  // extern "C"

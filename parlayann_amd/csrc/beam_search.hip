@@ -122,6 +122,9 @@ struct BSParams {
   const uint32_t* allow; uint64_t allow_stride;   // point i is allowed iff bit i & 31 of word i >> 5; query q reads row q (stride in words, 0: shared)
   uint32_t* result_count; uint32_t* allowed_cmps; // [nq] optional: entries of the result list; full distances of allowed points
   uint32_t rl_off;                                // byte offset of the result list in LDS (64 keys), then the keys of one gather (64)
+  // ... by label predicates (MASK_LABELS variants only), see DESIGN.md "Label predicates"
+  const uint32_t* labels;                         // [n] one word per point
+  const pann_label_pred* preds; uint32_t pred_stride, pred_kind;   // query q reads preds[q * pred_stride] (0: shared); PANN_PRED_*
 };
 
 template <bool HASH_LDS>
@@ -402,6 +405,32 @@ __device__ __forceinline__ void masked_offer(MaskedList& R, uint64_t key, bool a
   R.L[lane] = lk;
 }
 
+// Where a MASKED kernel's verdict on a compared point comes from.  MASK_BITMAP: W is the query's bitmap row, the word of point a
+// is W[a >> 5] and the verdict its bit a & 31.  MASK_LABELS: W is the label array, the word of point a is W[a] and the verdict the
+// query's predicate on it; kind, pa and pb are wave-uniform and are forced into scalar registers once per query, so the label
+// form holds no vector register the bitmap form does not.  Either way ONE 4-byte load per compared point, issued at the same place.
+struct MaskSrc { const uint32_t* W; uint32_t kind, pa, pb; };
+template <int MODE>
+__device__ __forceinline__ MaskSrc mask_src(const BSParams& P, uint32_t qi) {
+  if constexpr (MODE == MASK_LABELS) {
+    const pann_label_pred* pp = P.preds + (size_t)qi * P.pred_stride;
+    return MaskSrc{P.labels, P.pred_kind, (uint32_t)__builtin_amdgcn_readfirstlane((int)pp->a),
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)pp->b)};
+  } else {
+    return MaskSrc{P.allow + (size_t)qi * P.allow_stride, 0u, 0u, 0u};
+  }
+}
+template <int MODE>
+__device__ __forceinline__ uint32_t mask_word(const MaskSrc& M, uint32_t a) {
+  if constexpr (MODE == MASK_LABELS) return M.W[a];
+  else return M.W[a >> 5];
+}
+template <int MODE>
+__device__ __forceinline__ bool mask_verdict(const MaskSrc& M, uint32_t aword, uint32_t note) {
+  if constexpr (MODE == MASK_LABELS) return label_pred(M.kind, M.pa, M.pb, aword);
+  else return ((aword >> (note & 31u)) & 1u) != 0u;
+}
+
 // What the lane that owns a filter survivor keeps across the gather: position in Pl and bit number of its id (0: owns none).
 __device__ __forceinline__ uint32_t masked_note(bool mine, uint32_t mypos, uint32_t a) {
   return mine ? (0x80000000u | (mypos << 5) | (a & 31u)) : 0u;
@@ -409,14 +438,15 @@ __device__ __forceinline__ uint32_t masked_note(bool mine, uint32_t mypos, uint3
 
 // gather_distances (batched emit) for the MASKED kernels.  The callback does what gather_distances' does and also leaves every
 // candidate's key -- at or beyond the cutoff too -- in LDS at its index in Pl (MK, 64 keys behind the result list).  After the
-// gather the lane that owns candidate Pl[mypos] (`note`, masked_note) reads that key back and tests its own bit: the bitmap word
-// `aword` was requested before the row loads of the gather and is first used here, after all of them, so it adds no dependent
-// round trip, and the callback holds nothing but a ballot and LDS stores.  One offer of up to 64 keys per call.
-template <int DT, int METRIC, int LPC, bool NCH1, int U>
+// gather the lane that owns candidate Pl[mypos] (`note`, masked_note) reads that key back and tests its own bit (MASK_LABELS: its
+// label against the query's predicate): the word `aword` was requested before the row loads of the gather and is first used here,
+// after all of them, so it adds no dependent round trip, and the callback holds nothing but a ballot and LDS stores.  One offer of
+// up to 64 keys per call.
+template <int DT, int METRIC, int LPC, bool NCH1, int U, int MODE>
 __device__ __forceinline__ uint32_t gather_distances_masked(const BSParams& P, const QReg<DT>& qreg, const uint4* qlds,
                                                             const uint32_t* Pl, uint32_t m, uint32_t cutoff_ord, uint64_t* C,
-                                                            uint32_t c, int lane, uint32_t note, uint32_t aword, MaskedList& R,
-                                                            uint32_t thr_lane) {
+                                                            uint32_t c, int lane, uint32_t note, uint32_t aword, const MaskSrc& M,
+                                                            MaskedList& R, uint32_t thr_lane) {
   const PointsView PV{P.points, P.pstride, P.nch, P.exact};
   uint64_t* MK = R.L + PANN_WAVE;
   gather_tile<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, lane,
@@ -432,7 +462,7 @@ __device__ __forceinline__ uint32_t gather_distances_masked(const BSParams& P, c
   PANN_WSYNC();
   const bool mine = (note >> 31) != 0u;
   const uint64_t key = mine ? MK[(note >> 5) & 63u] : KEY_INF;
-  masked_offer(R, key, mine && ((aword >> (note & 31u)) & 1u) != 0u, thr_lane, lane);
+  masked_offer(R, key, mine && mask_verdict<MODE>(M, aword, note), thr_lane, lane);
   return c;
 }
 
@@ -472,8 +502,9 @@ __device__ __forceinline__ float sketch_distance(const BSParams& P, const uint4*
 // neighbour that passed the hash filter gets a full distance only if its sketch distance to the query is below the running
 // mean of the sketch distance to the worst frontier entry.  After the hash-filter replay lane i still owns neighbour i: it
 // reads its own candidate's sketch, and the ballot compaction that follows hands the gather a dense list in row order.
-// MASKED: the traversal of the plain search; out->ids/dists hold the result list over the allowed points (see MaskedList).
-template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = false, bool MASKED = false>
+// MASKED (MASK_BITMAP / MASK_LABELS): the traversal of the plain search; out->ids/dists hold the result list over the allowed
+// points (see MaskedList, MaskSrc).
+template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = false, int MASKED = MASK_NONE>
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(BSParams P) {
   static_assert(!(FILTER && MASKED), "the masked search has no sketch-filtered form");
   const int lane = threadIdx.x;
@@ -537,8 +568,8 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
     uint64_t* DL = P.dropped + (size_t)qi * P.dcap;
     [[maybe_unused]] MaskedList R{reinterpret_cast<uint64_t*>(smem + P.rl_off), P.out.out_k ? KEY_INF : 0ull, 0u};
     [[maybe_unused]] const uint32_t thr_lane = P.out.out_k ? P.out.out_k - 1u : 0u;
-    [[maybe_unused]] const uint32_t* AW = nullptr;
-    if constexpr (MASKED) { AW = P.allow + (size_t)qi * P.allow_stride; R.L[lane] = KEY_INF; }
+    [[maybe_unused]] MaskSrc M{};
+    if constexpr (MASKED) { M = mask_src<MASKED>(P, qi); R.L[lane] = KEY_INF; }
 
     // ---- start points (:66-70): distance for each, filter insert in order, then "merge" into
     // the empty frontier (which sorts them) ----
@@ -548,14 +579,14 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
       const uint32_t a = act ? P.starts[(size_t)qi * P.starts_stride + i] : 0u;
       (void)filter_update<HASH_LDS>(H, hmask, act, a, lane, reinterpret_cast<uint8_t*>(Hl));
       [[maybe_unused]] uint32_t aword = 0u;
-      if constexpr (MASKED) if (act) aword = AW[a >> 5];
+      if constexpr (MASKED) if (act) aword = mask_word<MASKED>(M, a);
       if (act) PANN_PL[lane] = a;
       PANN_WSYNC();
       const uint32_t m = min(P.nstarts - s0, (uint32_t)PANN_WAVE);
       // every start enters the frontier: cutoff above any finite distance
       if constexpr (MASKED)
-        c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane,
-                                                              masked_note(act, (uint32_t)lane, a), aword, R, thr_lane);
+        c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4, MASKED>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane,
+                                                              masked_note(act, (uint32_t)lane, a), aword, M, R, thr_lane);
       else
       c = gather_distances<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane);
       PANN_WSYNC();
@@ -625,15 +656,15 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
           const uint64_t km = __ballot(keep);
           const uint32_t m = __popcll(km);
           [[maybe_unused]] uint32_t aword = 0u;
-          if constexpr (MASKED) if (keep) aword = AW[a >> 5];         // in flight with the rows of the gather
+          if constexpr (MASKED) if (keep) aword = mask_word<MASKED>(M, a);         // in flight with the rows of the gather
           const uint32_t mypos = lanes_below(km, lane);
           if (keep) PANN_PL[mypos] = a;
           dcmps += m;                                                 // :137,155
           PANN_WSYNC();
           PANN_STAMP(2);   // filter + compaction
           if constexpr (MASKED) {
-            if (m) c = gather_distances_masked<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, PANN_PL, m, cutoff_ord, C, c, lane,
-                                                                               masked_note(keep, mypos, a), aword, R, thr_lane);
+            if (m) c = gather_distances_masked<DT, METRIC, LPC, NCH1, PANN_GU, MASKED>(P, qreg, qlds, PANN_PL, m, cutoff_ord, C, c, lane,
+                                                                               masked_note(keep, mypos, a), aword, M, R, thr_lane);
           } else {
           if (m) c = gather_distances<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, PANN_PL, m, cutoff_ord, C, c, lane);
           }
@@ -798,7 +829,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
 // filter (4 KB) + a 64-entry scatter scratch + the candidate list: 5.2 KB -> 31 queries per CU.
 // =============================================================================================
 // MASKED: as in the generic kernel.
-template <int DT, int METRIC, int LPC, bool NCH1, bool MASKED = false>
+template <int DT, int METRIC, int LPC, bool NCH1, int MASKED = MASK_NONE>
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_kernel(BSParams P) {
   const int lane = threadIdx.x;
   extern __shared__ __align__(16) uint8_t smem[];
@@ -831,8 +862,8 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
   uint64_t* DL = P.dropped + (size_t)qi * P.dcap;
   [[maybe_unused]] MaskedList R{reinterpret_cast<uint64_t*>(smem + P.rl_off), P.out.out_k ? KEY_INF : 0ull, 0u};
   [[maybe_unused]] const uint32_t thr_lane = P.out.out_k ? P.out.out_k - 1u : 0u;
-  [[maybe_unused]] const uint32_t* AW = nullptr;
-  if constexpr (MASKED) { AW = P.allow + (size_t)qi * P.allow_stride; R.L[lane] = KEY_INF; }
+  [[maybe_unused]] MaskSrc M{};
+  if constexpr (MASKED) { M = mask_src<MASKED>(P, qi); R.L[lane] = KEY_INF; }
 #ifdef PANN_STAMPS
   unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
@@ -844,12 +875,12 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
     const uint32_t a = act ? P.starts[(size_t)qi * P.starts_stride + lane] : 0u;
     (void)filter_update<true>(H, hmask, act, a, lane);
     [[maybe_unused]] uint32_t aword = 0u;
-    if constexpr (MASKED) if (act) aword = AW[a >> 5];
+    if constexpr (MASKED) if (act) aword = mask_word<MASKED>(M, a);
     if (act) Pl[lane] = a;
     PANN_WSYNC();
     if constexpr (MASKED)
-      c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane,
-                                                            masked_note(act, (uint32_t)lane, a), aword, R, thr_lane);
+      c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4, MASKED>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane,
+                                                            masked_note(act, (uint32_t)lane, a), aword, M, R, thr_lane);
     else
     c = gather_distances<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane);
     PANN_WSYNC();
@@ -979,15 +1010,15 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
         const uint64_t km = __ballot(keep);
         const uint32_t m = __popcll(km);
         [[maybe_unused]] uint32_t aword = 0u;
-        if constexpr (MASKED) if (keep) aword = AW[a >> 5];         // in flight with the rows of the gather
+        if constexpr (MASKED) if (keep) aword = mask_word<MASKED>(M, a);         // in flight with the rows of the gather
         const uint32_t mypos = lanes_below(km, lane);
         if (keep) Pl[mypos] = a;
         dcmps += m;
         PANN_WSYNC();
         PANN_STAMP(2);
         if constexpr (MASKED) {
-          if (m) c = gather_distances_masked<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane,
-                                                                             masked_note(keep, mypos, a), aword, R, thr_lane);
+          if (m) c = gather_distances_masked<DT, METRIC, LPC, NCH1, PANN_GU, MASKED>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane,
+                                                                             masked_note(keep, mypos, a), aword, M, R, thr_lane);
         } else {
         if (m) c = gather_distances<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane);
         }
@@ -1507,9 +1538,11 @@ struct Plan {
   bool filter; uint32_t sk_lds_off;   // sketch-filtered search: the generic kernel's FILTER variant, query sketch after its LDS state
   uint32_t rl_off; // ... masked: byte offset of the result list (64 keys) in LDS
   bool masked;     // allow-bitmap search: the MASKED variant of the b64 kernel (bcap 64) or of the generic kernel (every other beam)
+  bool by_labels;  // ... with label predicates in place of the bitmap: the MASK_LABELS instantiation of the same kernel
 };
 
-// which layouts have a MASKED instantiation of the b64 kernel (the others spill under its launch bound: make_plan)
+// which layouts have a MASKED instantiation of the b64 kernel (the others spill under its launch bound: make_plan); the label form
+// needs no vector register beyond the bitmap form (MaskSrc), so one predicate serves both
 constexpr bool masked_b64_fits(int dtype, uint32_t lpc, bool nch1) { return !(lpc == 8 && nch1) && !(dtype == PANN_BF16 && !nch1); }
 
 static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
@@ -1530,7 +1563,7 @@ static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
   p.lds_bytes = (uint32_t)(fixed + (p.hash_lds ? hbytes : 1024));      // HBM filter: 1 KB replay scratch (filter_update)
   p.slots = 256 * 8;
   p.filter = a.filter != 0; p.sk_lds_off = 0;
-  p.masked = a.masked != 0; p.rl_off = 0;
+  p.masked = a.masked != MASK_NONE; p.by_labels = a.masked == MASK_LABELS; p.rl_off = 0;
   // Two families of the b64 kernel have no room for the masked state under its 72-VGPR bound: 128-byte rows (8 lanes per
   // candidate, 32 candidates per gather iteration) and bf16 rows of several chunks per lane.  Their masked forms would spill next
   // to the hand-issued row prefetch, so they are not instantiated and take the generic kernel
@@ -1594,6 +1627,30 @@ size_t search_workspace_bytes(const DeviceIndex& ix, const SearchArgs& a) {
   return need;
 }
 
+// masked search, MODE = MASK_BITMAP / MASK_LABELS: register frontier at bcap 64, else the generic kernel
+template <int DT, int METRIC, int LPC, bool NCH1, int MODE>
+static hipError_t launch_masked(const BSParams& P, const Plan& p, hipStream_t stream) {
+  if (p.b64) {
+    if constexpr (!masked_b64_fits(DT, LPC, NCH1)) return hipErrorInvalidValue;   // make_plan never asks for it
+    else {
+      auto kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MODE>;
+      hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    }
+  } else if (p.hash_lds) {
+    auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MODE>;
+    if (p.lds_bytes > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+  } else {
+    auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MODE>;
+    if (p.lds_bytes > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+  }
+  return hipGetLastError();
+}
+
 template <int DT, int METRIC, int LPC, bool NCH1>
 static hipError_t launch_variant(const BSParams& P, const Plan& p, hipStream_t stream) {
   if (p.filter) {   // generic kernel with the sketch filter
@@ -1609,25 +1666,9 @@ static hipError_t launch_variant(const BSParams& P, const Plan& p, hipStream_t s
       const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
       hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
     }
-  } else if (p.masked) {   // allow bitmap: register frontier at bcap 64, else the generic kernel
-    if (p.b64) {
-      if constexpr (!masked_b64_fits(DT, LPC, NCH1)) return hipErrorInvalidValue;   // make_plan never asks for it
-      else {
-        auto kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1, true>;
-        hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-      }
-    } else if (p.hash_lds) {
-      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, true>;
-      if (p.lds_bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-      hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-    } else {
-      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, true>;
-      if (p.lds_bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-    }
+  } else if (p.masked) {   // allow bitmap or label predicates
+    return p.by_labels ? launch_masked<DT, METRIC, LPC, NCH1, MASK_LABELS>(P, p, stream)
+                       : launch_masked<DT, METRIC, LPC, NCH1, MASK_BITMAP>(P, p, stream);
   } else if (p.b64) {   // frontier in registers
     auto kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
     hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
@@ -1698,6 +1739,10 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   // the bitmap, its stride and out_k <= 64 are checked by the entry points (api.hip: mask_checks); no entry point combines a mask
   // with the sketch filter, and there is no kernel for it
   if (a.masked && a.filter) { set_error("pann_batch_search_masked: the sketch filter has no masked form"); return PANN_ERR_UNSUPPORTED; }
+  // label mode: the entry points have checked the handle's labels, the kind and npreds (api.hip: label_checks)
+  if (a.masked == MASK_LABELS && (!a.labels || !a.preds || a.pred_stride > 1 || !pred_kind_known(a.pred_kind))) {
+    set_error("pann_batch_search_labeled: labels, predicates of a known kind and a predicate stride of 0 or 1 are needed"); return PANN_ERR_BAD_ARG;
+  }
   Plan p = make_plan(ix, a);
   if (p.lds_bytes > 160 * 1024) { set_error("pann_batch_search: beam/degree too large for LDS state"); return PANN_ERR_UNSUPPORTED; }
   if (search_workspace_bytes(ix, a) > ws_bytes) { set_error("pann_batch_search: workspace too small"); return PANN_ERR_BAD_ARG; }
@@ -1733,7 +1778,10 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   P.sketch_queries = a.sketch_queries; P.sq_stride = a.sq_stride;
   P.sk_row_bytes = a.filter ? sketch_row_bytes(ix.sk_kind, ix.d) : 0u;
   P.sk_lds_off = p.sk_lds_off; P.pruned_cmps = a.filter ? a.pruned_cmps : nullptr;
-  P.allow = a.masked ? a.allow : nullptr; P.allow_stride = a.masked ? a.allow_stride : 0;
+  P.allow = a.masked == MASK_BITMAP ? a.allow : nullptr; P.allow_stride = a.masked == MASK_BITMAP ? a.allow_stride : 0;
+  const bool lab = a.masked == MASK_LABELS;
+  P.labels = lab ? a.labels : nullptr; P.preds = lab ? a.preds : nullptr;
+  P.pred_stride = lab ? a.pred_stride : 0u; P.pred_kind = lab ? (uint32_t)a.pred_kind : 0u;
   P.result_count = a.masked ? a.result_count : nullptr; P.allowed_cmps = a.masked ? a.allowed_cmps : nullptr;
   P.rl_off = p.rl_off;
 #ifdef PANN_STAMPS

@@ -12,6 +12,12 @@
 //                                                 k <= 64 keys as one sorted (dist, id) key per lane.
 //
 // allow_count_kernel (pann_allow_count_dev) is the count half alone, per row.
+//
+// Label predicates (DESIGN.md "Label predicates"): one uint32 label per point and a two-word predicate per query stand for the
+// bitmap row { i : pred(label[i]) }.
+//   labels_to_allow_kernel   materialises such rows in the bitmap format (the bridge to everything above)
+//   label_count_kernel       counts them without materialising anything
+//   masked_scan_kernel<.., LABELS = true>   the per-query scan with its 64 words per step built from 2 048 labels
 #include "pann_device.h"
 
 namespace pann {
@@ -120,15 +126,95 @@ __global__ void __launch_bounds__(MK_BLOCK) knn_pad_kernel(uint32_t* __restrict_
   if (counts) for (uint64_t i = i0; i < nq; i += step) counts[i] = cnt;
 }
 
+// ---- label predicates ----
+constexpr uint32_t LA_WAVE_LABELS = PANN_WAVE * PANN_WAVE;               // labels one wave turns into 128 words: 64 ballots
+constexpr uint32_t LA_BLOCK_LABELS = LA_WAVE_LABELS * (MK_BLOCK / PANN_WAVE);
+constexpr uint32_t LC_TILE = 4096;                                       // labels of one tile of label_count_kernel (16 KB of LDS)
+
+__device__ __forceinline__ uint32_t uniform_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+
+// the verdicts of 64 consecutive labels from `first` on (lane i: label first + i), as a ballot; positions >= n: 0
+__device__ __forceinline__ uint64_t label_ballot(const uint32_t* __restrict__ labels, uint64_t first, uint64_t n, uint32_t kind,
+                                                 uint32_t pa, uint32_t pb, int lane) {
+  const uint64_t i = first + (uint64_t)lane;
+  const bool in = i < n;
+  const uint32_t l = in ? labels[i] : 0u;
+  return __ballot(in && label_pred(kind, pa, pb, l));
+}
+
+// Row r = blockIdx.y (+ gridDim.y ...) of `allow` <- the bitmap of preds[r].  A wave covers 4 096 labels: 64 coalesced loads of 64
+// labels and one ballot each; lane j keeps ballot j and writes it as the two whole words 2j, 2j + 1 of the wave's 128.  Bits at
+// positions >= n are 0 (label_ballot), words at or past ceil(n / 32) are not written.
+__global__ void __launch_bounds__(MK_BLOCK) labels_to_allow_kernel(const uint32_t* __restrict__ labels, uint64_t n, uint32_t kind,
+                                                                   const pann_label_pred* __restrict__ preds, uint64_t npreds,
+                                                                   uint32_t* __restrict__ allow, uint64_t stride) {
+  const int lane = threadIdx.x & (PANN_WAVE - 1), wave = threadIdx.x / PANN_WAVE;
+  const uint64_t words = (n + 31) / 32;
+  const uint64_t base = (uint64_t)blockIdx.x * LA_BLOCK_LABELS + (uint64_t)wave * LA_WAVE_LABELS;   // first label of the wave
+  if (base >= n) return;
+  for (uint64_t r = blockIdx.y; r < npreds; r += gridDim.y) {
+    const uint32_t pa = uniform_u32(preds[r].a), pb = uniform_u32(preds[r].b);
+    uint64_t mine = 0ull;
+#pragma unroll 8
+    for (int j = 0; j < PANN_WAVE; j++) {
+      const uint64_t bal = label_ballot(labels, base + (uint64_t)j * PANN_WAVE, n, kind, pa, pb, lane);
+      if (lane == j) mine = bal;
+    }
+    const uint64_t w = base / 32 + 2u * (uint32_t)lane;
+    uint32_t* row = allow + r * stride;
+    if (w < words) row[w] = (uint32_t)mine;
+    if (w + 1 < words) row[w + 1] = (uint32_t)(mine >> 32);
+  }
+}
+
+// counts[p] += points of the tile that preds[p] allows (counts zeroed by the caller).  blockIdx.x: the tile of LC_TILE labels,
+// staged in LDS once; blockIdx.y: a group of 256 predicates, one per thread, which reads the tile by broadcast (every lane the
+// same address) and keeps its count in a register: one atomic per thread and tile.
+__global__ void __launch_bounds__(MK_BLOCK) label_count_kernel(const uint32_t* __restrict__ labels, uint64_t n, uint32_t kind,
+                                                               const pann_label_pred* __restrict__ preds, uint64_t npreds,
+                                                               uint32_t* __restrict__ counts) {
+  __shared__ uint32_t T[LC_TILE];
+  const uint64_t first = (uint64_t)blockIdx.x * LC_TILE;
+  const uint32_t m = (uint32_t)min((uint64_t)LC_TILE, n - first);        // the launch has no tile at or past n
+  for (uint32_t i = threadIdx.x; i < m; i += MK_BLOCK) T[i] = labels[first + i];
+  __syncthreads();
+  for (uint64_t p = (uint64_t)blockIdx.y * MK_BLOCK + threadIdx.x; p < npreds; p += (uint64_t)gridDim.y * MK_BLOCK) {
+    const uint32_t pa = preds[p].a, pb = preds[p].b;
+    uint32_t c = 0;
+    for (uint32_t i = 0; i < m; i++) c += label_pred(kind, pa, pb, T[i]) ? 1u : 0u;
+    if (c) atomicAdd(&counts[p], c);
+  }
+}
+
 struct MaskedScanArgs {
   PointsView pv; uint32_t dbytes;
   const uint8_t* q; uint64_t q_stride;
   const uint32_t* allow; uint64_t allow_stride; uint64_t n;
+  const uint32_t* labels; const pann_label_pred* preds; uint32_t kind;   // LABELS form: the words come from these instead of `allow`
   uint32_t k;                                      // <= 64
   uint32_t* out_ids; float* out_dists; uint32_t* out_counts;
 };
 
-template <int DT, int METRIC, int LPC, bool NCH1>
+// Where the scan's words come from: word w0 + lane of the query's bitmap row (allow_word), or -- LABELS -- the same word built from
+// the 32 labels it stands for.  The step's 2 048 labels are read as 32 coalesced loads of 64 with one ballot each: ballot j holds
+// the step's words 2j and 2j + 1, which lanes 2j and 2j + 1 keep.  Positions >= n are cleared either way.
+struct ScanSrc { const uint32_t* row; uint32_t kind, pa, pb; };
+template <bool LABELS>
+__device__ __forceinline__ uint32_t scan_word(const ScanSrc& S, uint64_t w0, int lane, uint64_t words, uint64_t n) {
+  if constexpr (!LABELS) return allow_word(S.row, w0 + lane, words, n);
+  else {
+    uint32_t v = 0u;
+    if (w0 >= words) return v;                      // wave-uniform: the prefetch past the last step
+#pragma unroll 8
+    for (int j = 0; j < PANN_WAVE / 2; j++) {
+      const uint64_t bal = label_ballot(S.row, (w0 + 2u * (uint32_t)j) * 32, n, S.kind, S.pa, S.pb, lane);
+      if ((lane >> 1) == j) v = (lane & 1) ? (uint32_t)(bal >> 32) : (uint32_t)bal;
+    }
+    return v;
+  }
+}
+
+template <int DT, int METRIC, int LPC, bool NCH1, bool LABELS>
 __global__ void __launch_bounds__(PANN_WAVE) masked_scan_kernel(MaskedScanArgs P) {
   const int lane = threadIdx.x;
   __shared__ uint32_t Lst[MK_CHUNK + PANN_WAVE];   // allowed ids waiting for their distance: < 64 left over + one step's
@@ -139,15 +225,16 @@ __global__ void __launch_bounds__(PANN_WAVE) masked_scan_kernel(MaskedScanArgs P
   QReg<DT> qreg{};
   load_query<DT, LPC, NCH1>(P.q + qi * P.q_stride, P.dbytes, P.pv.nch, qreg, qlds, lane);
   __syncthreads();
-  const uint32_t* row = P.allow + qi * P.allow_stride;
+  ScanSrc S{P.allow + qi * P.allow_stride, 0u, 0u, 0u};
+  if constexpr (LABELS) S = ScanSrc{P.labels, P.kind, uniform_u32(P.preds[qi].a), uniform_u32(P.preds[qi].b)};
   const uint64_t words = (P.n + 31) / 32;
   uint64_t best = KEY_INF;                         // lane i: the i-th smallest key seen so far
   uint64_t tau = KEY_INF;                          // the k-th smallest: what a candidate has to beat
   uint32_t fill = 0, total = 0;
-  uint32_t wnext = allow_word(row, lane, words, P.n);
+  uint32_t wnext = scan_word<LABELS>(S, 0, lane, words, P.n);
   for (uint64_t w0 = 0; w0 < words; w0 += PANN_WAVE) {
     uint32_t v = wnext;
-    wnext = allow_word(row, w0 + PANN_WAVE + lane, words, P.n);       // in flight while this step is scored
+    wnext = scan_word<LABELS>(S, w0 + PANN_WAVE, lane, words, P.n);   // bitmap: in flight while this step is scored
     const bool last = w0 + PANN_WAVE >= words;
     uint32_t step_total;
     uint32_t pos = fill + wave_excl_scan(__popc(v), lane, &step_total);
@@ -244,8 +331,10 @@ int knn_pad_dev(uint32_t* d_ids, float* d_dists, uint32_t* d_counts, uint64_t nq
   return PANN_OK;
 }
 
-int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
-                    uint64_t allow_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
+// the per-query scan on bitmap rows (d_labels == null) or on the labels with one predicate per query
+static int scan_launch(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
+                       uint64_t allow_stride, const uint32_t* d_labels, int kind, const pann_label_pred* d_preds, uint32_t k,
+                       uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
   if (nq == 0) return PANN_OK;
   if (k == 0 || k > PANN_WAVE) { set_error("masked scan: k must be in [1,64]"); return PANN_ERR_UNSUPPORTED; }
   const size_t qb = query_lds_bytes(ix);
@@ -253,10 +342,48 @@ int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, u
   MaskedScanArgs P{};
   P.pv = PointsView{ix.points, ix.pstride, ix.nch, ix.exact}; P.dbytes = ix.dbytes;
   P.q = d_q; P.q_stride = q_stride; P.allow = d_allow; P.allow_stride = allow_stride; P.n = ix.n; P.k = k;
+  P.labels = d_labels; P.preds = d_preds; P.kind = (uint32_t)kind;
   P.out_ids = d_out_ids; P.out_dists = d_out_dists; P.out_counts = d_out_counts;
-#define CALL_MS(DT, MT, L, N1) hipLaunchKernelGGL((masked_scan_kernel<DT, MT, L, N1>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, P)
+#define CALL_MS(DT, MT, L, N1)                                                                                              \
+  do {                                                                                                                      \
+    if (d_labels) hipLaunchKernelGGL((masked_scan_kernel<DT, MT, L, N1, true>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, P);   \
+    else hipLaunchKernelGGL((masked_scan_kernel<DT, MT, L, N1, false>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, P);    \
+  } while (0)
   PANN_TYPE_SWITCH(ix, CALL_MS);
 #undef CALL_MS
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
+                    uint64_t allow_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
+  return scan_launch(ix, st, d_q, q_stride, nq, d_allow, allow_stride, nullptr, 0, nullptr, k, d_out_ids, d_out_dists, d_out_counts);
+}
+
+int label_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_labels,
+                   int kind, const pann_label_pred* d_preds, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
+                   uint32_t* d_out_counts) {
+  return scan_launch(ix, st, d_q, q_stride, nq, nullptr, 0, d_labels, kind, d_preds, k, d_out_ids, d_out_dists, d_out_counts);
+}
+
+int labels_to_allow_dev(const uint32_t* d_labels, uint64_t n, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                        uint32_t* d_allow, uint64_t stride, hipStream_t st) {
+  if (npreds == 0 || n == 0) return PANN_OK;
+  const uint32_t gx = (uint32_t)((n + LA_BLOCK_LABELS - 1) / LA_BLOCK_LABELS);
+  hipLaunchKernelGGL(labels_to_allow_kernel, dim3(gx, (uint32_t)std::min<uint64_t>(npreds, 65535)), dim3(MK_BLOCK), 0, st, d_labels, n,
+                     (uint32_t)kind, d_preds, npreds, d_allow, stride);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+int label_count_dev(const uint32_t* d_labels, uint64_t n, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                    uint32_t* d_counts, hipStream_t st) {
+  if (npreds == 0) return PANN_OK;
+  PANN_HIP(hipMemsetAsync(d_counts, 0, npreds * 4, st));
+  if (n == 0) return PANN_OK;
+  const uint32_t gx = (uint32_t)((n + LC_TILE - 1) / LC_TILE);
+  const uint32_t gy = (uint32_t)std::min<uint64_t>((npreds + MK_BLOCK - 1) / MK_BLOCK, 65535);
+  hipLaunchKernelGGL(label_count_kernel, dim3(gx, gy), dim3(MK_BLOCK), 0, st, d_labels, n, (uint32_t)kind, d_preds, npreds, d_counts);
   PANN_HIP(hipGetLastError());
   return PANN_OK;
 }

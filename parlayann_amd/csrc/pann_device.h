@@ -36,6 +36,13 @@ __device__ __forceinline__ uint32_t key_id(uint64_t k) { return (uint32_t)k; }
 __device__ __forceinline__ float key_dist(uint64_t k) { return ord2f((uint32_t)(k >> 32)); }
 constexpr uint64_t KEY_INF = 0xFFFFFFFFFFFFFFFFull;
 
+// label predicate (include/pann.h, pann_label_pred): kind, a and b are wave-uniform, l is the lane's label word
+__device__ __forceinline__ bool label_pred(uint32_t kind, uint32_t a, uint32_t b, uint32_t l) {
+  if (kind == PANN_PRED_ANY) return (l & a) != 0u;
+  if (kind == PANN_PRED_MATCH) return (l & a) == b;
+  return l >= a && l <= b;                                  // PANN_PRED_RANGE: unsigned, both ends inclusive
+}
+
 // ---- DPP butterfly sum over aligned groups of LPC consecutive lanes; every lane of the group
 // ends with the group total (fp adds are commutative, so all lanes hold the same bits) ----
 template <int CTRL>

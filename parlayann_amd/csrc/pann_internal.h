@@ -72,6 +72,8 @@ struct DeviceIndex {
   uint32_t sk_stride = 0;
   int sk_kind = -1;
   uint32_t sk_as_written = 0;         // one-bit kinds: the reference's distance loop as written (block 0 counted num_blocks times)
+  // one label word per point (pann_index_set_labels), what the label predicates are evaluated on; null = none set
+  const uint32_t* labels = nullptr;   // [n]
 };
 
 // The kernels come in two families (PANN_LAYOUT_SWITCH): rows that are ONE 16-byte chunk per lane with 8 / 16 / 32
@@ -79,6 +81,10 @@ struct DeviceIndex {
 // runs the generic variants, which keep the query in LDS.  All LDS sizes on the host must use THIS predicate.
 inline bool layout_query_in_registers(const DeviceIndex& ix) { return ix.nch == 1 && ix.lpc != 4; }
 inline size_t query_lds_bytes(const DeviceIndex& ix) { return layout_query_in_registers(ix) ? 0 : (size_t)ix.nch * ix.lpc * 16; }
+
+// how a masked search decides whether a compared point is allowed (SearchArgs::masked; template parameter of the kernels)
+enum { MASK_NONE = 0, MASK_BITMAP = 1, MASK_LABELS = 2 };
+inline bool pred_kind_known(int kind) { return kind == PANN_PRED_ANY || kind == PANN_PRED_MATCH || kind == PANN_PRED_RANGE; }
 
 struct SearchArgs {  // one batched beam search, everything device resident
   const uint8_t* queries; uint64_t qstride;  // external queries (or null)
@@ -96,11 +102,16 @@ struct SearchArgs {  // one batched beam search, everything device resident
   uint64_t sq_stride = 0;
   uint32_t* pruned_cmps = nullptr;           // nq, optional: the reference's local dist_cmps (starts + sum of pruned.size())
   // masked search (DESIGN.md "Masked search"): same traversal, out.ids/dists = the best allowed points that were compared
-  int masked = 0;
+  int masked = 0;                            // MASK_NONE / MASK_BITMAP / MASK_LABELS
   const uint32_t* allow = nullptr;           // ceil(n / 32) words per row: point i allowed iff bit i & 31 of word i >> 5
   uint64_t allow_stride = 0;                 // words between the rows of two queries; 0: one bitmap for the batch
   uint32_t* result_count = nullptr;          // nq, optional: entries of the query's result list (<= out.out_k)
   uint32_t* allowed_cmps = nullptr;          // nq, optional: full distances computed for allowed points
+  // MASK_LABELS (DESIGN.md "Label predicates"): point i allowed iff the query's predicate holds on labels[i]
+  const uint32_t* labels = nullptr;          // n words; not necessarily the searched handle's own (the fused path reads `full`'s)
+  const pann_label_pred* preds = nullptr;    // query q reads preds[q * pred_stride]
+  uint32_t pred_stride = 0;                  // 0: one predicate for the batch, 1: one per query
+  int pred_kind = 0;                         // PANN_PRED_*
 };
 
 // the extra arguments of the masked entry points (pann_batch_search_masked*, pann_batch_search_masked_rerank*): host or device
@@ -108,6 +119,14 @@ struct SearchArgs {  // one batched beam search, everything device resident
 struct MaskArgs {
   const uint32_t* allow; uint64_t stride;          // bitmap rows, as SearchArgs::allow / allow_stride
   uint32_t* result_count; uint32_t* allowed_cmps;  // nq each, optional
+  // label mode (allow == null): as SearchArgs::labels / preds / pred_stride / pred_kind; labels is always a device pointer
+  const uint32_t* labels = nullptr; const pann_label_pred* preds = nullptr; uint32_t pred_stride = 0; int pred_kind = 0;
+  bool by_labels() const { return labels != nullptr; }
+  void apply(SearchArgs& a) const {                // everything but the two outputs, which the callers place themselves
+    a.masked = by_labels() ? MASK_LABELS : MASK_BITMAP;
+    a.allow = allow; a.allow_stride = stride;
+    a.labels = labels; a.preds = preds; a.pred_stride = pred_stride; a.pred_kind = pred_kind;
+  }
 };
 
 // the one growable device buffer: kernel scratch, staging regions, tables kept on a handle (grown on demand, never shrunk)
@@ -190,6 +209,17 @@ int knn_pad_dev(uint32_t* d_ids, float* d_dists, uint32_t* d_counts, uint64_t nq
 // one bitmap row per query (allow_stride words apart), k <= 64: rows sorted by (dist, id), padded; d_out_counts optional
 int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
                     uint64_t allow_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts);
+// label predicates (DESIGN.md "Label predicates"): d_labels n words, d_preds npreds predicates of one kind
+// row r of d_allow (stride words apart, >= ceil(n / 32)) <- the bitmap of d_preds[r]; dead bits of the last word 0
+int labels_to_allow_dev(const uint32_t* d_labels, uint64_t n, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                        uint32_t* d_allow, uint64_t stride, hipStream_t st);
+// d_counts[r] = points d_preds[r] allows
+int label_count_dev(const uint32_t* d_labels, uint64_t n, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                    uint32_t* d_counts, hipStream_t st);
+// masked_scan_dev with the bitmap words of query q built from the labels and d_preds[q] as the scan goes
+int label_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_labels,
+                   int kind, const pann_label_pred* d_preds, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
+                   uint32_t* d_out_counts);
 
 // leaf_knn.hip: lane-owns-row all-pairs top-m for one-byte element types (HCNNG leaves)
 bool dense_gt_eligible(const DeviceIndex& ix, uint32_t m, bool b_ids, bool segmented, int exclude_same);

@@ -300,7 +300,8 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
   if (mask) {
     if (mask->result_count) rcount = mask->result_count;
     a.out.out_k = pool; a.out.frontier_size = d_out.frontier_size;
-    a.masked = 1; a.allow = mask->allow; a.allow_stride = mask->stride; a.result_count = rcount; a.allowed_cmps = mask->allowed_cmps;
+    mask->apply(a);                                // bitmap rows, or the labels of `full` with the queries' predicates
+    a.result_count = rcount; a.allowed_cmps = mask->allowed_cmps;
   }
   a.out.visited_count = d_out.visited_count; a.out.dist_cmps = d_out.dist_cmps;
   a.filter = use_filter ? 1 : 0;

@@ -2,12 +2,13 @@
 classes python/module.cpp registers (:50-57,150-155), over the C-ABI.
 
     Index(data_path, index_path)                       (positional order of graph_index.cpp:82)
-    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None)
+    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None)
                                                                          -> (uint32[nq,knn], float32[nq,knn])
     .single_search(q, knn, beam_width, quant, visit_limit)               -> uint32[knn]
     .batch_search_from_string(queries_path, knn, beam_width, quant=False, visit_limit=-1)
-    .batch_search_masked(queries, knn, beam_width, allow, quant=False, visit_limit=-1, exact_below=None)
+    .batch_search_masked(queries, knn, beam_width, allow, quant=False, visit_limit=-1, exact_below=None, where=None)
                                                                          this project's own: masked results
+    .set_labels(labels, first_row=0)                                     ... by label predicates: where=(kind, preds)
     .check_recall(queries_file, gt_file, neighbors, k)   prints "Recall: x"
 """
 import numpy as np
@@ -21,8 +22,9 @@ class GraphIndex:
     T = None
     metric = None
 
-    def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None, quant_bits=8):
-        """quant_bits: 8 | 4 -- bits per coordinate of the quantised copy that quant=True searches (float points only).  4: the
+    def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None, quant_bits=8, labels=None):
+        """labels: one uint32 per point (set_labels), what where= predicates are evaluated on (DESIGN.md "Label predicates").
+        quant_bits: 8 | 4 -- bits per coordinate of the quantised copy that quant=True searches (float points only).  4: the
         four-bit quantisers ("euclid_u4" / "mips_i4", packed rows of ceil(d / 2) bytes) for the copy and for the fused rerank
         call; it has no second level, and its Euclidian translate is never a plain cast.  The default changes nothing.
         second_level: None | "bit" | "2bit" -- the three-range beam_search_rerank of graph_index.cpp:156-185: quantised
@@ -74,15 +76,29 @@ class GraphIndex:
                 kind = "mips_2bit" if second_level == "2bit" else ("euclid_bit" if self.metric == "Euclidian" else "mips_bit")
                 self.sparams = sketch.sketch_params(self.index, kind)
                 sketch.attach_sketch(self.q_index, self.index, self.sparams)
+        if labels is not None:
+            self.set_labels(labels)
+
+    def set_labels(self, labels, first_row=0):
+        """Labels of rows first_row .. first_row + len(labels) (DeviceIndex.set_labels).  The quantised copy gets them too: the
+        fused call reads the float handle's, the plain search of a copy that is a cast (slope 1) its own."""
+        self.index.set_labels(labels, first_row)
+        if self.q_index is not None:
+            self.q_index.set_labels(labels, first_row)
 
     # QueryParams(knn, beam, 1.35, visit_limit, min(maxDeg, 3*visit_limit))   (:198,:222,:242)
     def _qp(self, knn, beam_width, visit_limit):
         return dict(k=knn, beam=beam_width, cut=1.35, limit=visit_limit,
                     degree_limit=min(self.index.max_degree, 3 * visit_limit))
 
-    def _search(self, queries, knn, beam_width, quant, visit_limit, allow=None):   # search_dispatch :120-190
+    def _search(self, queries, knn, beam_width, quant, visit_limit, allow=None, where=None):   # search_dispatch :120-190
         queries = np.ascontiguousarray(queries, dtype=self.T)
         qp = self._qp(knn, beam_width, visit_limit)
+        if where is not None:      # label predicates: the masked search below with the labels standing for the bitmap
+            if quant and self.use_quantization:
+                raise ValueError("where= goes with quant=False here (batch_search_masked(..., quant=True, where=) is the fused form)")
+            r = self.index.batch_search_labeled(queries, where=where, out_k=knn, **qp)
+            return r["ids"], r["dists"]
         if allow is not None:
             # masked search (this project's own, DESIGN.md "Masked search"): the plain search's walk over the full-precision
             # points, results = the best allowed points it compared.  Rows may be short (padding 0xFFFFFFFF / +inf), so the
@@ -139,21 +155,57 @@ class GraphIndex:
             ids[~exact], dists[~exact] = walk(queries[~exact], allow[~exact])
         return ids, dists
 
-    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None):
+    @staticmethod
+    def _where_rows(where, rows):
+        """the predicates of the queries `rows` selects (a boolean mask): an (a, b) pair serves any of them"""
+        preds = np.asarray(where[1])
+        return where if preds.ndim == 1 else (where[0], preds[rows])
+
+    def _exact_or_walk_labeled(self, queries, knn, where, exact_below, walk):
+        """_exact_or_walk for label predicates: the counts come from DeviceIndex.label_count (nothing is materialised), the exact
+        route is DeviceIndex.bruteforce_knn_labeled, walk(queries, where) -> (ids, dists) every other."""
+        if exact_below is None:
+            return walk(queries, where)
+        queries = np.ascontiguousarray(queries, dtype=self.T)
+        cnt = self.index.label_count(where)
+        if np.ndim(cnt) == 0:
+            if cnt > exact_below:
+                return walk(queries, where)
+            ids, dists, _ = self.index.bruteforce_knn_labeled(queries, knn, where)
+            return ids, dists
+        if len(cnt) != len(queries):
+            raise ValueError("per-query predicates must be an (nq, 2) array")
+        exact = cnt <= exact_below
+        ids = np.full((len(queries), knn), 0xFFFFFFFF, np.uint32)
+        dists = np.full((len(queries), knn), np.inf, np.float32)
+        if exact.any():
+            ids[exact], dists[exact], _ = self.index.bruteforce_knn_labeled(queries[exact], knn, self._where_rows(where, exact))
+        if not exact.all():
+            ids[~exact], dists[~exact] = walk(queries[~exact], self._where_rows(where, ~exact))
+        return ids, dists
+
+    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None):
         """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned.
-        exact_below (with allow): as batch_search_masked"""
+        where = (kind, preds): the same by a label predicate (DeviceIndex.batch_search_labeled); not together with allow.
+        exact_below (with allow or where): as batch_search_masked"""
+        if where is not None:
+            if allow is not None:
+                raise ValueError("where and allow exclude each other")
+            return self._exact_or_walk_labeled(queries, knn, where, exact_below,
+                                               lambda q, w: self._search(q, knn, beam_width, quant, visit_limit, where=w))
         if allow is None:
             return self._search(queries, knn, beam_width, quant, visit_limit)
         return self._exact_or_walk(queries, knn, allow, exact_below,
                                    lambda q, a: self._search(q, knn, beam_width, quant, visit_limit, a))
 
-    def _search_masked(self, queries, knn, beam_width, allow, quant, visit_limit):
+    def _search_masked(self, queries, knn, beam_width, allow, quant, visit_limit, where=None):
         """Masked searches (this project's own, DESIGN.md "Masked search").  Rows may be short (padding 0xFFFFFFFF / +inf):
-        a short row is an answer under a mask, so the k-results check of the plain paths does not apply."""
-        if allow is None:
-            raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
+        a short row is an answer under a mask, so the k-results check of the plain paths does not apply.
+        where: a label predicate in place of allow (DESIGN.md "Label predicates")."""
+        if allow is None and where is None:
+            raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask) or where (a label predicate)")
         if not (quant and self.use_quantization):        # one-byte points, or the float table: the plain masked search
-            return self._search(queries, knn, beam_width, False, visit_limit, allow)
+            return self._search(queries, knn, beam_width, False, visit_limit, allow, where)
         if self.second_level is not None:
             raise ValueError("quant=True masked searches have no second level: a mask together with the sketch filter is not "
                              "supported (build the index without second_level=)")
@@ -161,15 +213,18 @@ class GraphIndex:
         qp = self._qp(knn, beam_width, visit_limit)
         if self.metric == "Euclidian" and self.quant_bits == 8 and self.eparams.identity:   # slope == 1: the u8 copy, as _search
             qq = quantize.device_quantize_rows(queries, self.qparams, device=self.device)
-            r = self.q_index.batch_search_masked(qq, allow=allow, out_k=knn, **qp)
+            r = (self.q_index.batch_search_masked(qq, allow=allow, out_k=knn, **qp) if where is None else
+                 self.q_index.batch_search_labeled(qq, where=where, out_k=knn, **qp))
             return r["ids"], r["dists"]
         # the fused masked call: masked search of the quantised copy, exact rerank of its result list on the float handle
         r = self.index.search_rerank(self.q_index, self.qparams, queries, normalize_first=self.metric != "Euclidian",
-                                     rerank_factor=100, allow=allow, **qp)
+                                     rerank_factor=100, allow=allow, where=where, **qp)
         return r["ids"], r["dists"]
 
-    def batch_search_masked(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1, exact_below=None):
-        """Only allowed points are returned (allow: an allow bitmap or boolean mask, DeviceIndex.batch_search_masked).
+    def batch_search_masked(self, queries, knn, beam_width, allow=None, quant=False, visit_limit=-1, exact_below=None, where=None):
+        """Only allowed points are returned (allow: an allow bitmap or boolean mask, DeviceIndex.batch_search_masked; or
+        where = (kind, preds): a label predicate over the labels of set_labels, 8 bytes per query in place of a bitmap row --
+        every route below has the same form under it, and exact_below is decided by DeviceIndex.label_count).
         quant=False, or one-byte points: batch_search(..., allow=).  quant=True on float points: the masked search of the
         quantised copy (quant_bits 8 or 4) with an exact rerank of its result list, in one call on the device
         (DeviceIndex.search_rerank(allow=)); not with second_level=.
@@ -177,6 +232,11 @@ class GraphIndex:
         points is answered EXACTLY instead, by scoring its allowed points on the full-precision table (DESIGN.md "Exact masked
         kNN"; quant makes no difference there); per-query rows are split by their own counts.  There is no built-in
         threshold: the count at which the two routes cost the same depends on the data (tools/masked_time.py --exact)."""
+        if where is not None:
+            if allow is not None:
+                raise ValueError("where and allow exclude each other")
+            return self._exact_or_walk_labeled(queries, knn, where, exact_below,
+                                               lambda q, w: self._search_masked(q, knn, beam_width, None, quant, visit_limit, w))
         if allow is None:
             raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
         return self._exact_or_walk(queries, knn, allow, exact_below,

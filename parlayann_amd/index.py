@@ -8,9 +8,9 @@ import ctypes as C
 import numpy as np
 
 from . import _capi
-from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I4, PANN_I8, PANN_L2, PANN_MIPS, PANN_QUANT_EUCLID_U4, PANN_QUANT_EUCLID_U8,
-                    PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats, DeleteStats, QuantParams, QueryParams, RerankOut, SearchOut,
-                    check)
+from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I4, PANN_I8, PANN_L2, PANN_MIPS, PANN_PRED_ANY, PANN_PRED_MATCH, PANN_PRED_RANGE,
+                    PANN_QUANT_EUCLID_U4, PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats,
+                    DeleteStats, QuantParams, QueryParams, RerankOut, SearchOut, check)
 from .bf16 import bfloat16
 
 _DT = {np.dtype(np.uint8): PANN_U8, np.dtype(np.int8): PANN_I8, np.dtype(np.float32): PANN_F32,
@@ -104,6 +104,50 @@ def allow_count(allow, n):
         a[..., w - 1] &= np.uint32((1 << (n & 31)) - 1)
     c = np.unpackbits(np.ascontiguousarray(a).view(np.uint8), axis=-1).sum(axis=-1, dtype=np.int64)
     return int(c) if a.ndim == 1 else c
+
+
+_PRED = {"any": PANN_PRED_ANY, "match": PANN_PRED_MATCH, "range": PANN_PRED_RANGE}
+
+
+def pred_kind(kind):
+    """"any" | "match" | "range" (or the PANN_PRED_* code) -> PANN_PRED_* code"""
+    if isinstance(kind, str):
+        if kind.lower() not in _PRED:
+            raise ValueError(f'unknown predicate kind {kind!r}: "any", "match" or "range"')
+        return _PRED[kind.lower()]
+    return int(kind)
+
+
+_pred_kind = pred_kind      # (methods that take an argument called pred_kind)
+
+
+def label_preds(preds):
+    """(a, b) or an (m, 2) array -> C-contiguous uint32 (m, 2) (pann_label_pred[m]) and whether it was the single (a, b) form"""
+    p = np.asarray(preds)
+    if p.ndim not in (1, 2) or p.shape[-1] != 2:
+        raise ValueError(f"preds must be (a, b) or an (nq, 2) array, got shape {p.shape}")
+    if p.size and (p.min() < 0 or p.max() > 0xFFFFFFFF):
+        raise ValueError("predicate words must fit 32 unsigned bits")
+    return np.ascontiguousarray(p.reshape(-1, 2).astype(np.uint32)), p.ndim == 1
+
+
+def label_allow(labels, kind, preds):
+    """What a label predicate allows, on the host (DESIGN.md "Label predicates"): labels uint32 (n,); kind "any" | "match" |
+    "range"; preds (a, b) -> boolean (n,), or an (nq, 2) array -> boolean (nq, n).
+    any: (label & a) != 0; match: (label & a) == b; range: a <= label <= b, unsigned, both ends inclusive."""
+    lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+    k = pred_kind(kind)
+    p, single = label_preds(preds)
+    a, b = p[:, :1], p[:, 1:]
+    if k == PANN_PRED_ANY:
+        out = (lab[None, :] & a) != 0
+    elif k == PANN_PRED_MATCH:
+        out = (lab[None, :] & a) == b
+    elif k == PANN_PRED_RANGE:
+        out = (lab[None, :] >= a) & (lab[None, :] <= b)
+    else:
+        raise ValueError(f"unknown predicate kind {kind!r}")
+    return out[0] if single else out
 
 
 def host_graph(n, max_deg):
@@ -289,6 +333,71 @@ class DeviceIndex:
             raise ValueError("rows must be a 2-D array of the index's dtype and width")
         check(self._lib.pann_index_upload_points(self._h, int(first_row), _ptr(rows), len(rows), _row_stride(rows)))
 
+    # ---- labels: one uint32 per point, what the label predicates are evaluated on (DESIGN.md "Label predicates") ----
+    def set_labels(self, labels, first_row=0):
+        """pann_index_set_labels: rows first_row .. first_row + len(labels) get these labels (uint32).  The first call gives the
+        handle its label array, zero filled."""
+        lab = np.ascontiguousarray(labels, dtype=np.uint32).reshape(-1)
+        check(self._lib.pann_index_set_labels(self._h, int(first_row), _ptr(lab), len(lab)))
+
+    def labels(self, first_row=0, nrows=None):
+        """pann_index_get_labels: the labels of rows [first_row, first_row + nrows) as uint32"""
+        nrows = self.n - first_row if nrows is None else nrows
+        out = np.empty(nrows, np.uint32)
+        check(self._lib.pann_index_get_labels(self._h, int(first_row), int(nrows), _ptr(out)))
+        return out
+
+    def drop_labels(self):
+        check(self._lib.pann_index_drop_labels(self._h))
+
+    @property
+    def has_labels(self):
+        return bool(self._lib.pann_index_has_labels(self._h))
+
+    def _where(self, where, nq=None):
+        """where = (kind, preds) -> (PANN_PRED_* code, uint32 (m, 2) array); m is 1 or nq"""
+        if where is None or len(where) != 2:
+            raise ValueError('where must be (kind, preds): kind "any" | "match" | "range", preds (a, b) or an (nq, 2) array')
+        kind = pred_kind(where[0])
+        p, single = label_preds(where[1])
+        if nq is not None and not single and len(p) != nq:
+            raise ValueError("per-query predicates must be an (nq, 2) array")
+        return kind, p
+
+    def _device_preds(self, where):
+        """the predicates of `where` as a torch tensor on the handle's device (the two helpers take device pointers)"""
+        import torch
+        kind, p = self._where(where)
+        dev = torch.device("cuda", int(self._lib.pann_index_device(self._h)))
+        return kind, p, torch.from_numpy(p.view(np.int32)).to(dev), dev
+
+    def label_count(self, where):
+        """pann_label_count_dev: the number of points each predicate of `where` allows, nothing materialised -> int for the
+        (a, b) form, int64 (m,) for an (m, 2) array"""
+        import torch
+        kind, p, d_p, dev = self._device_preds(where)
+        d_c = torch.empty(len(p), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev)
+        check(self._lib.pann_label_count_dev(self._h, kind, C.c_void_p(d_p.data_ptr()), len(p), C.c_void_p(d_c.data_ptr()),
+                                             C.c_void_p(st.cuda_stream or None)))
+        st.synchronize()
+        c = d_c.cpu().numpy().view(np.uint32).astype(np.int64)
+        return int(c[0]) if np.asarray(where[1]).ndim == 1 else c
+
+    def labels_to_allow(self, where):
+        """pann_labels_to_allow_dev: the bitmap rows of the predicates of `where`, in the format of batch_search_masked ->
+        packed uint32 (W,) for the (a, b) form, (m, W) for an (m, 2) array, W = ceil(n / 32); bits at positions >= n are 0"""
+        import torch
+        kind, p, d_p, dev = self._device_preds(where)
+        w = (self.n + 31) // 32
+        d_a = torch.empty((len(p), w), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev)
+        check(self._lib.pann_labels_to_allow_dev(self._h, kind, C.c_void_p(d_p.data_ptr()), len(p), C.c_void_p(d_a.data_ptr()), w,
+                                                 C.c_void_p(st.cuda_stream or None)))
+        st.synchronize()
+        a = d_a.cpu().numpy().view(np.uint32)
+        return a[0] if np.asarray(where[1]).ndim == 1 else a
+
     def set_stream(self, stream_ptr, private=False):
         """pann_index_set_stream: run the handle's calls on the caller's stream (a hipStream_t as an integer; 0 = the device's
         default stream, torch's usual current stream); private=True: back to the handle's own stream"""
@@ -366,8 +475,18 @@ class DeviceIndex:
         return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
                                   masked=True, allow=allow)
 
+    def batch_search_labeled(self, queries=None, where=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
+                             query_ids=None, out_k=None, visited_cap=0, want_dists=True):
+        """pann_batch_search_labeled: batch_search_masked with a label predicate in place of the bitmap (DESIGN.md "Label
+        predicates").  where = (kind, preds): kind "any" | "match" | "range"; preds (a, b) for the whole batch or an (nq, 2)
+        uint32 array, one predicate per query.  Returns, field for field, what batch_search_masked returns for
+        allow = label_allow(self.labels(), kind, preds)."""
+        nq = len(queries) if queries is not None else len(query_ids)
+        return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
+                                  masked=True, where=self._where(where, nq))
+
     def _batch_search(self, queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                      filtered=False, sketch_queries=None, masked=False, allow=None):
+                      filtered=False, sketch_queries=None, masked=False, allow=None, where=None):
         nq = len(queries) if queries is not None else len(query_ids)
         qp = QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
                          degree_limit=self.max_degree if degree_limit is None else degree_limit,
@@ -416,6 +535,14 @@ class DeviceIndex:
         if masked:
             if per_query:
                 raise ValueError("masked searches take shared starts")
+            if where is not None:
+                kind, preds = where
+                res["result_count"] = np.empty(nq, dtype=np.uint32)
+                res["allowed_cmps"] = np.empty(nq, dtype=np.uint32)
+                check(self._lib.pann_batch_search_labeled(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1],
+                                                          C.byref(qp), kind, _ptr(preds), len(preds), C.byref(out),
+                                                          _ptr(res["result_count"]), _ptr(res["allowed_cmps"])))
+                return res
             if allow is not None and allow.ndim == 2 and allow.shape[0] != nq:
                 raise ValueError("per-query allow rows must be nq x W")
             astride = allow.shape[1] if allow is not None and allow.ndim == 2 else 0
@@ -436,7 +563,7 @@ class DeviceIndex:
                            rerank_factor=rerank_factor, pad=1.0)
 
     def search_rerank(self, quant, qparams, queries, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
-                      normalize_first=False, use_filter=False, rerank_factor=100, allow=None):
+                      normalize_first=False, use_filter=False, rerank_factor=100, allow=None, where=None):
         """pann_batch_search_rerank on this (float32) index: `queries` (float32 rows) are quantised with `qparams` on the
         device, searched on `quant` (the one-byte DeviceIndex of quantized(); use_filter: through the sketch attached to it),
         and the first min(k * rerank_factor, frontier size) frontier ids are re-scored here and sorted.  normalize_first:
@@ -446,7 +573,9 @@ class DeviceIndex:
         allow (an allow bitmap or boolean mask, as batch_search_masked): pann_batch_search_masked_rerank -- the masked search
         of quant with a result list of min(k * rerank_factor, beam, 64) allowed points, all of them re-scored here, k kept
         (DESIGN.md "Masked search on the fused path").  The dict gains result_count (length of the quantised list) and
-        allowed_cmps; a short row is padded and raises no status bit."""
+        allowed_cmps; a short row is padded and raises no status bit.
+        where = (kind, preds), as batch_search_labeled: pann_batch_search_labeled_rerank -- the same with label predicates in
+        place of the bitmap, evaluated on THIS handle's labels (quant needs none).  Not together with allow."""
         q = self._queries(queries)
         nq = len(q)
         qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
@@ -459,6 +588,17 @@ class DeviceIndex:
                         visited_count=_ptr(res["visited_count"]), dist_cmps=_ptr(res["dist_cmps"]),
                         pruned_cmps=_ptr(res.get("pruned_cmps")), status=_ptr(res["status"]))
         starts = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
+        if where is not None:
+            if allow is not None:
+                raise ValueError("where and allow exclude each other")
+            kind, preds = self._where(where, nq)
+            res["result_count"] = np.empty(nq, np.uint32)
+            res["allowed_cmps"] = np.empty(nq, np.uint32)
+            check(self._lib.pann_batch_search_labeled_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q),
+                                                             1 if normalize_first else 0, 1 if use_filter else 0, _ptr(starts),
+                                                             len(starts), C.byref(qp), kind, _ptr(preds), len(preds), C.byref(out),
+                                                             _ptr(res["result_count"]), _ptr(res["allowed_cmps"])))
+            return res
         if allow is not None:
             allow = pack_allow(allow, self.n)
             if allow.ndim == 2 and allow.shape[0] != nq:
@@ -480,16 +620,24 @@ class DeviceIndex:
                           k=10, beam=64, cut=1.35, limit=None, degree_limit=None, normalize_first=False, use_filter=False,
                           rerank_factor=100, d_frontier_size_ptr=None, d_visited_count_ptr=None, d_dist_cmps_ptr=None,
                           d_pruned_cmps_ptr=None, d_status_ptr=None, stream_ptr=None, d_allow_ptr=None, allow_stride_words=0,
-                          d_result_count_ptr=None, d_allowed_cmps_ptr=None):
+                          d_result_count_ptr=None, d_allowed_cmps_ptr=None, d_preds_ptr=None, pred_kind=None, npreds=1):
         """pann_batch_search_rerank_dev: the same on raw device addresses (integers), enqueued on `stream_ptr` (a hipStream_t as
         an integer; None / 0 = the device's default stream).  Nothing is synchronised: read the outputs after the stream has
         been.  The first call grows quant's scratch.  d_allow_ptr (packed bitmap rows on the device, allow_stride_words 0 =
-        one shared row): pann_batch_search_masked_rerank_dev, with the two optional per-query outputs."""
+        one shared row): pann_batch_search_masked_rerank_dev, with the two optional per-query outputs.  d_preds_ptr (npreds = 1 or nq
+        predicates of kind pred_kind on the device, 8-byte aligned): pann_batch_search_labeled_rerank_dev, on this handle's labels."""
         qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
         vp = lambda a: C.c_void_p(a or None)
         out = RerankOut(ids=vp(d_ids_ptr), dists=vp(d_dists_ptr), frontier_size=vp(d_frontier_size_ptr),
                         visited_count=vp(d_visited_count_ptr), dist_cmps=vp(d_dist_cmps_ptr), pruned_cmps=vp(d_pruned_cmps_ptr),
                         status=vp(d_status_ptr))
+        if d_preds_ptr is not None:
+            check(self._lib.pann_batch_search_labeled_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq,
+                                                                 q_stride_bytes, 1 if normalize_first else 0, 1 if use_filter else 0,
+                                                                 vp(d_starts_ptr), nstarts, C.byref(qp), _pred_kind(pred_kind),
+                                                                 vp(d_preds_ptr), npreds, C.byref(out), vp(d_result_count_ptr),
+                                                                 vp(d_allowed_cmps_ptr), vp(stream_ptr)))
+            return
         if d_allow_ptr is not None:
             check(self._lib.pann_batch_search_masked_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq,
                                                                 q_stride_bytes, 1 if normalize_first else 0, 1 if use_filter else 0,
@@ -690,6 +838,17 @@ class DeviceIndex:
         oi = np.empty((len(q), k), np.uint32); od = np.empty((len(q), k), np.float32); oc = np.empty(len(q), np.uint32)
         check(self._lib.pann_bruteforce_knn_masked(self._h, _ptr(q), len(q), _row_stride(q), k, _ptr(allow),
                                                    allow.shape[1] if allow.ndim == 2 else 0, _ptr(oi), _ptr(od), _ptr(oc)))
+        return oi, od, oc
+
+    def bruteforce_knn_labeled(self, queries, k, where):
+        """pann_bruteforce_knn_labeled: bruteforce_knn_masked with a label predicate in place of the bitmap.  where = (kind,
+        preds), as batch_search_labeled: (a, b) is the shared route (k <= 128), an (nq, 2) array the per-query one (k <= 64).
+        -> (ids uint32[nq, k], dists float32[nq, k], counts uint32[nq])"""
+        q = self._queries(queries)
+        kind, preds = self._where(where, len(q))
+        oi = np.empty((len(q), k), np.uint32); od = np.empty((len(q), k), np.float32); oc = np.empty(len(q), np.uint32)
+        check(self._lib.pann_bruteforce_knn_labeled(self._h, _ptr(q), len(q), _row_stride(q), k, kind, _ptr(preds), len(preds),
+                                                    _ptr(oi), _ptr(od), _ptr(oc)))
         return oi, od, oc
 
     def bruteforce_knn_masked_dev(self, d_queries_ptr, nq, q_stride_bytes, k, d_allow_ptr, allow_stride_words, d_ids_ptr,

@@ -34,6 +34,17 @@ must equal that ground truth; the tool stops otherwise.  Last line: the allowed 
 masked search cost the same, interpolated between the measured masks in log(count).
 
     python tools/masked_time.py --exact [--fractions 0.001,0.01,0.1] [--json out.json]
+
+--labels: label predicates beside per-query bitmaps (DESIGN.md "Label predicates").  The first setup above; every point gets a
+label whose low byte is a tenant in 0..9 and whose second byte is a sub-tenant in 0..9 (the upper half is random), and every
+query its own MATCH predicate: one tenant (about 10 % of the points) or one (tenant, sub-tenant) pair (about 1 %).  Per
+selectivity, in one process and from one binary: QPS of pann_batch_search_labeled_dev with 10 000 predicates, of
+pann_batch_search_masked_dev on the same content as 10 000 bitmap rows (expanded on the device by pann_labels_to_allow_dev: 1.25 GB
+at the defaults), and of the plain search; the bytes each form stages per batch; the two id arrays must be equal, the tool stops
+otherwise.  With --exact also pann_bruteforce_knn_labeled_dev (one predicate per query: the label scan) beside
+pann_bruteforce_knn_masked_dev on the rows, and the time of pann_label_count_dev for the 10 000 predicates.
+
+    python tools/masked_time.py --labels [--exact] [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -86,7 +97,10 @@ def main():
     ap.add_argument("--rerank", action="store_true", help="the fused quantised search + rerank instead of the plain search")
     ap.add_argument("--bits", default="8", help="--rerank: bits per coordinate of the quantised copy: 8, 4 or 8,4 (one build for both)")
     ap.add_argument("--exact", action="store_true", help="the exact masked kNN beside the masked search on selective masks")
+    ap.add_argument("--labels", action="store_true", help="per-query label predicates beside per-query bitmaps (with --exact: on the exact route too)")
     a = ap.parse_args()
+    if a.labels:
+        return main_labels(a)
     if a.fractions is None:
         a.fractions = "0.001,0.01,0.1" if a.exact else "1.0,0.5,0.1" if a.rerank else "1.0,0.9,0.5,0.1"
     if a.rerank:
@@ -287,6 +301,135 @@ def main_exact(a):
     if a.json:
         with open(a.json, "w") as f:
             json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, steps=a.steps, equal_cost_allowed=cross, rows=rows), f, indent=1)
+    ix.close()
+
+
+def main_labels(a):
+    import torch
+    n, d, nq = a.n, a.d, a.nq
+    with step("data", 300):
+        X = datasets.sift1m_like(n, d, seed=1234, dtype=np.float32).astype(np.float16)
+        Q = datasets.sift1m_like(nq, d, seed=4321, dtype=np.float16)
+        rng = np.random.default_rng(77)
+        labels = (rng.integers(0, 10, n).astype(np.uint32) | (rng.integers(0, 10, n).astype(np.uint32) << np.uint32(8))
+                  | (rng.integers(0, 1 << 16, n).astype(np.uint32) << np.uint32(16)))
+    with step(f"upload + build R={R} L={L}", 900):
+        ix = DeviceIndex(X, max_degree=R)
+        ix.vamana_build(R, L, ALPHA, num_passes=2, seed=1, sort_neighbors=True)
+        ix.set_labels(labels)
+    lib = _capi.load()
+    qp = _capi.QueryParams(k=K, beam=BEAM, cut=1.35, limit=n, degree_limit=R, rerank_factor=100, pad=1.0)
+    words = (n + 31) // 32
+    t_q = torch.from_numpy(Q.view(np.uint8).reshape(nq, -1)).cuda()
+    t_st = torch.zeros(1, dtype=torch.int32, device="cuda")
+    t_ids = torch.zeros((nq, K), dtype=torch.int32, device="cuda")
+    t_d = torch.zeros((nq, K), dtype=torch.float32, device="cuda")
+    t_rc, t_ac, t_dc, t_cnt = (torch.zeros(nq, dtype=torch.int32, device="cuda") for _ in range(4))
+    t_status = torch.zeros(1, dtype=torch.int32, device="cuda")
+    t_rows = torch.zeros((nq, words), dtype=torch.int32, device="cuda")          # the per-query bitmaps: nq * ceil(n / 32) words
+    torch.cuda.synchronize()
+    stream = torch.cuda.Stream()
+    sp = C.c_void_p(stream.cuda_stream)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+
+    def search_out():
+        return _capi.SearchOut(ids=t_ids.data_ptr(), dists=t_d.data_ptr(), out_k=K, dist_cmps=t_dc.data_ptr(), status=t_status.data_ptr())
+
+    def timed(fn):
+        for _ in range(a.warmup):
+            fn()
+        stream.synchronize()
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps)]
+        with torch.cuda.stream(stream):
+            for e0, e1 in ev:
+                e0.record(stream); fn(); e1.record(stream)
+        stream.synchronize()
+        ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+        assert int(t_status.cpu()[0]) == 0
+        return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def ids_now():
+        return t_ids.cpu().numpy().view(np.uint32).copy()
+
+    qn = np.arange(nq, dtype=np.uint32)
+    sets = [("tenant (about 10 %)", np.stack([np.full(nq, 0xFF, np.uint32), qn % 10], axis=1)),
+            ("tenant and sub-tenant (about 1 %)", np.stack([np.full(nq, 0xFFFF, np.uint32), (qn % 10) | ((qn // 10 % 10) << 8)], axis=1))]
+    rows = []
+    for name, preds in sets:
+        preds = np.ascontiguousarray(preds.astype(np.uint32))
+        t_p = torch.from_numpy(preds.view(np.int32)).cuda()
+        torch.cuda.synchronize()
+
+        def plain_step():
+            out = search_out()
+            _capi.check(lib.pann_batch_search_dev(ix.handle, vp(t_q), None, nq, 2 * d, vp(t_st), 1, C.byref(qp), C.byref(out), sp))
+
+        def labeled_step():
+            out = search_out()
+            _capi.check(lib.pann_batch_search_labeled_dev(ix.handle, vp(t_q), None, nq, 2 * d, vp(t_st), 1, C.byref(qp), _capi.PANN_PRED_MATCH,
+                                                          vp(t_p), nq, C.byref(out), vp(t_rc), vp(t_ac), sp))
+
+        def bitmap_step():
+            out = search_out()
+            _capi.check(lib.pann_batch_search_masked_dev(ix.handle, vp(t_q), None, nq, 2 * d, vp(t_st), 1, C.byref(qp), vp(t_rows), words,
+                                                         C.byref(out), vp(t_rc), vp(t_ac), sp))
+
+        def expand_step():
+            _capi.check(lib.pann_labels_to_allow_dev(ix.handle, _capi.PANN_PRED_MATCH, vp(t_p), nq, vp(t_rows), words, sp))
+
+        def count_step():
+            _capi.check(lib.pann_label_count_dev(ix.handle, _capi.PANN_PRED_MATCH, vp(t_p), nq, vp(t_cnt), sp))
+
+        with step(f"{name}: expand to {nq} bitmap rows on the device, count", 300):
+            x_ms = timed(expand_step)
+            c_ms = timed(count_step)
+            cnt = t_cnt.cpu().numpy().view(np.uint32)
+            want = np.bincount((labels & np.uint32(preds[0, 0])).astype(np.int64), minlength=1 << 16)[preds[:, 1]]
+            if not np.array_equal(cnt, want):
+                print("ERROR: pann_label_count_dev differs from the host count", flush=True)
+                sys.exit(1)
+        with step(f"{name}: timing", 300):
+            p_ms = timed(plain_step)
+            l_ms = timed(labeled_step)
+            ids_l = ids_now()
+            rc, ac, dc = (t.cpu().numpy().view(np.uint32).copy() for t in (t_rc, t_ac, t_dc))
+            b_ms = timed(bitmap_step)
+            if not np.array_equal(ids_now(), ids_l):
+                print("ERROR: the labeled ids differ from the bitmap entry's", flush=True)
+                sys.exit(1)
+            real = ids_l != 0xFFFFFFFF
+            if not ((labels[ids_l[real]] & preds[np.nonzero(real)[0], 0]) == preds[np.nonzero(real)[0], 1]).all():
+                print("ERROR: the labeled search returned a point its predicate does not allow", flush=True)
+                sys.exit(1)
+        row = dict(predicates=name, allowed_mean=float(cnt.mean()), plain_ms=p_ms[0], labeled_ms=l_ms[0], labeled_ms_min=l_ms[1],
+                   labeled_ms_max=l_ms[2], bitmap_ms=b_ms[0], bitmap_ms_min=b_ms[1], bitmap_ms_max=b_ms[2], plain_qps=nq / p_ms[0] * 1e3,
+                   labeled_qps=nq / l_ms[0] * 1e3, bitmap_qps=nq / b_ms[0] * 1e3, labeled_bytes_per_batch=8 * nq,
+                   bitmap_bytes_per_batch=4 * words * nq, expand_ms=x_ms[0], count_ms=c_ms[0], short_rows=int((rc < K).sum()),
+                   allowed_cmps=float(ac.mean()), dist_cmps=float(dc.mean()))
+        print(f"  {name}: {row['allowed_mean']:.0f} allowed points per query   plain {p_ms[0]:.3f} ms QPS {row['plain_qps']:.0f}   labeled "
+              f"{l_ms[0]:.3f} ms (min {l_ms[1]:.3f}, max {l_ms[2]:.3f}) QPS {row['labeled_qps']:.0f}   per-query bitmaps {b_ms[0]:.3f} ms (min "
+              f"{b_ms[1]:.3f}, max {b_ms[2]:.3f}) QPS {row['bitmap_qps']:.0f}   labeled / bitmap {row['labeled_qps'] / row['bitmap_qps']:.3f}   "
+              f"staged per batch: {row['labeled_bytes_per_batch']} B of predicates against {row['bitmap_bytes_per_batch']} B of bitmap rows   "
+              f"expanding the rows {x_ms[0]:.3f} ms, counting {c_ms[0]:.3f} ms   rows shorter than k {row['short_rows']}  allowed cmps/q "
+              f"{row['allowed_cmps']:.1f} of {row['dist_cmps']:.1f}   labeled ids == bitmap ids", flush=True)
+        if a.exact:
+            with step(f"{name}: exact routes", 600):
+                e_l = timed(lambda: _capi.check(lib.pann_bruteforce_knn_labeled_dev(ix.handle, vp(t_q), nq, 2 * d, K, _capi.PANN_PRED_MATCH,
+                                                                                  vp(t_p), nq, vp(t_ids), vp(t_d), vp(t_cnt), sp)))
+                ids_el = ids_now()
+                e_b = timed(lambda: ix.bruteforce_knn_masked_dev(t_q.data_ptr(), nq, 2 * d, K, t_rows.data_ptr(), words, t_ids.data_ptr(),
+                                                                 t_d.data_ptr(), t_cnt.data_ptr(), stream.cuda_stream))
+                if not np.array_equal(ids_now(), ids_el):
+                    print("ERROR: the labeled exact ids differ from the per-query bitmap route's", flush=True)
+                    sys.exit(1)
+            row.update(exact_labeled_ms=e_l[0], exact_labeled_ms_min=e_l[1], exact_labeled_ms_max=e_l[2], exact_bitmap_ms=e_b[0],
+                       exact_bitmap_ms_min=e_b[1], exact_bitmap_ms_max=e_b[2])
+            print(f"  {name}: exact, one predicate per query {e_l[0]:.3f} ms (min {e_l[1]:.3f}, max {e_l[2]:.3f})   exact, per-query bitmaps "
+                  f"{e_b[0]:.3f} ms (min {e_b[1]:.3f}, max {e_b[2]:.3f})   ids equal", flush=True)
+        rows.append(row)
+    if a.json:
+        with open(a.json, "w") as f:
+            json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, steps=a.steps, rows=rows), f, indent=1)
     ix.close()
 
 
