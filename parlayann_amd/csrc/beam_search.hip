@@ -43,27 +43,16 @@ namespace pann {
 #ifndef PANN_MINWAVES
 #define PANN_MINWAVES 1
 #endif
-#ifndef PANN_B128_PAIR
-/* beam 65..128: two vertices per memory round trip while merges are skipped.  Exact (the whole GPU suite and the fuzz soak pass
-   with it on) but OFF: measured on the C3-shaped 2M build, search phase 0.864 s without vs 0.91..0.93 s with it -- the kernel
-   already moves 5.1 TB/s on the HBM side (81 % of the 6.3 TB/s random-row ceiling), so more bytes in flight buy nothing and the
-   rows fetched for nothing when row 1 ends the skipping cost bandwidth.  It does pay when the table sits wholly in LDS and
-   occupancy is low (PANN_B128_SPLIT=3: 1.03 -> 0.98 s), which is slower than the default split anyway.
-   Round 3: with the filter-code table (CODES: the whole filter in 6 KB of LDS, no table traffic) it is ON for that variant:
-   C3 2M search phase 0.743 -> 0.712 s (PANN_B128_PAIR_CODES). */
-#define PANN_B128_PAIR 0
-#endif
 #ifndef PANN_B128_PAIR_CODES
+/* beam 65..128: two vertices per memory round trip while merges are skipped.  Only the CODES variant has the path (the whole
+   filter in 6 KB of LDS, no table traffic): C3 2M search phase 0.743 -> 0.712 s.  With the id table it was exact but slower
+   (C3-shaped 2M build, search phase 0.864 s without vs 0.91..0.93 s with it: the kernel already moves 5.1 TB/s on the HBM side,
+   81 % of the 6.3 TB/s random-row ceiling, so more bytes in flight buy nothing and the rows fetched for nothing when row 1 ends
+   the skipping cost bandwidth), and that form has been removed. */
 #define PANN_B128_PAIR_CODES 1
 #endif
 #ifndef PANN_B64_PREFETCH
 #define PANN_B64_PREFETCH 1   /* speculative adjacency-row fetch in the beam-64 kernel (0: A/B library builds) */
-#endif
-#ifndef PANN_B64_PAIR
-/* beam <= 64: two vertices per memory round trip while merges are skipped (the b128 form above, on the register frontier of
-   the beam-64 kernel): one query's chain of dependent round trips gets a third shorter, which is what the tail of a 10K-query
-   launch consists of.  A/B in profiles/r03_b64_pair.txt. */
-#define PANN_B64_PAIR 0
 #endif
 #ifndef PANN_MINWAVES_B64
 #define PANN_MINWAVES_B64 7   /* at least 7 waves per SIMD (<= 72 VGPRs); the kernel uses 61 -> 8 waves, LDS caps a CU at 30 queries */
@@ -78,8 +67,18 @@ namespace pann {
     stamp_sum[slot] += t_ - stamp_prev;                                                         \
     stamp_prev = t_;                                                                            \
   } while (0)
+/* once per query: before its first PANN_STAMP / after its last (the kernel's `lane` and `P` are in scope) */
+#define PANN_STAMP_BEGIN()                                                                      \
+  unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;                       \
+  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory")
+#define PANN_STAMP_FLUSH(qi)                                                                    \
+  do {                                                                                          \
+    if (lane == 0 && P.stamps) for (int i_ = 0; i_ < 8; i_++) P.stamps[(size_t)(qi) * 8 + i_] = stamp_sum[i_]; \
+  } while (0)
 #else
 #define PANN_STAMP(slot) do { } while (0)
+#define PANN_STAMP_BEGIN() ((void)0)
+#define PANN_STAMP_FLUSH(qi) ((void)0)
 #endif
 
 // every kernel of this file runs ONE wavefront per workgroup
@@ -198,24 +197,9 @@ __device__ __forceinline__ void lds_part_clear(const LdsPart& L, int lane) {
   }
 }
 
-// What one filter_update call changed, per lane: enough to put the table back (a row that was scanned speculatively and
-// turns out not to be the next vertex must leave no trace in the lossy table, whose state decides later hits and misses).
-struct FilterUndo { uint32_t s, old; bool wrote; };
-template <bool HASH_LDS>
-__device__ __forceinline__ void filter_undo(uint32_t* H, const FilterUndo& u, uint32_t hb, const LdsPart& Lp) {
-  if (u.wrote) {
-    const uint32_t hm = (1u << hb) - 1u;
-    if constexpr (HASH_LDS) H[u.s] = u.old;
-    else if (hb != 3 && (u.s & hm) == hm) __hip_atomic_store(H + (u.s >> hb), u.old, __ATOMIC_RELAXED, PANN_PRIVATE_SCOPE);
-    else lds_part_store(Lp, split_lds_index(u.s, hb), u.old);
-  }
-  PANN_WSYNC();
-}
-
 template <bool HASH_LDS>
 __device__ __forceinline__ bool filter_update(uint32_t* H, uint32_t hmask, bool active, uint32_t a, int lane,
-                                              uint8_t* T = nullptr, uint32_t hb = 0, LdsPart Lp = LdsPart{nullptr, 0, 0},
-                                              FilterUndo* undo = nullptr) {
+                                              uint8_t* T = nullptr, uint32_t hb = 0, LdsPart Lp = LdsPart{nullptr, 0, 0}) {
   const uint32_t s = (uint32_t)hash64_2((uint64_t)a) & hmask;
   uint32_t old, w;
   const uint32_t hm = (1u << hb) - 1u;
@@ -251,7 +235,6 @@ __device__ __forceinline__ bool filter_update(uint32_t* H, uint32_t hmask, bool 
   }
   const uint32_t a_prev = __shfl(a, prev < 0 ? lane : prev);
   const bool seen = active && (prev >= 0 ? (a_prev == a) : (old == a));
-  if (undo) { undo->s = s; undo->old = old; undo->wrote = active && last; }   // `old` of a slot group: the value on entry
   if constexpr (HASH_LDS) {
     PANN_WSYNC();
     if (active && last) H[s] = a;
@@ -271,6 +254,9 @@ __device__ __forceinline__ bool filter_update(uint32_t* H, uint32_t hmask, bool 
 // plane P8[s] and a 4-bit plane, eight slots per dword of P4.  Two lanes of one instruction may own different nibbles of one
 // dword, so the nibble is written with ds_mskor_b32 (D = (D & ~mask) | data, atomic per lane).  Empty slot = 0xFFF (no code is).
 // Lanes that share a slot are found through the 1 KB byte scratch T as in the HBM-table form above.
+// What one filter_update_codes call changed, per lane: enough to put the table back (a row that was scanned speculatively and
+// turns out not to be the next vertex must leave no trace in the lossy table, whose state decides later hits and misses).
+struct FilterUndo { uint32_t s, old; bool wrote; };
 __device__ __forceinline__ void code_store(uint8_t* P8, uint32_t* P4, uint32_t s, uint32_t code) {
   const uint32_t sh = (s & 7u) * 4u;
   P8[s] = (uint8_t)code;
@@ -346,33 +332,21 @@ __device__ __forceinline__ uint32_t gather_distances(const BSParams& P, const QR
 
 // The same for the survivors of TWO rows listed one after the other in Pl (row 1: Pl[0..split), row 2: the rest):
 // *c_split = size of C after the candidates of row 1 alone (the appends keep Pl order).
-template <int DT, int METRIC, int LPC, bool NCH1, int U, bool BATCH_EMIT = false>
+template <int DT, int METRIC, int LPC, bool NCH1, int U>
 __device__ __forceinline__ uint32_t gather_distances_split(const BSParams& P, const QReg<DT>& qreg, const uint4* qlds,
                                                            const uint32_t* Pl, uint32_t m, uint32_t split, uint32_t cutoff_ord,
                                                            uint64_t* C, uint32_t c, int lane, uint32_t* c_split) {
   const PointsView PV{P.points, P.pstride, P.nch, P.exact};
   uint32_t c1 = c;
-  if constexpr (BATCH_EMIT) {
-    gather_tile<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, lane,
-      [&](bool has, uint32_t ci, uint32_t id, float dist, uint64_t before) {
-        const uint32_t ord = f2ord(dist);
-        const bool pass = has && (ord < cutoff_ord);
-        const uint64_t pm = __ballot(pass);
-        if (pass) C[c + (uint32_t)__popcll(pm & before)] = ((uint64_t)ord << 32) | id;
-        c += __popcll(pm);
-        c1 += __popcll(__ballot(pass && ci < split));
-      });
-  } else {
-    gather_tile<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, lane,
-      [&](bool has, uint32_t ci, uint32_t id, float dist) {
-        const uint32_t ord = f2ord(dist);
-        const bool pass = has && (ord < cutoff_ord);
-        const uint64_t pm = __ballot(pass);
-        if (pass) C[c + lanes_below(pm, lane)] = ((uint64_t)ord << 32) | id;
-        c += __popcll(pm);
-        c1 += __popcll(__ballot(pass && ci < split));
-      });
-  }
+  gather_tile<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, lane,
+    [&](bool has, uint32_t ci, uint32_t id, float dist) {
+      const uint32_t ord = f2ord(dist);
+      const bool pass = has && (ord < cutoff_ord);
+      const uint64_t pm = __ballot(pass);
+      if (pass) C[c + lanes_below(pm, lane)] = ((uint64_t)ord << 32) | id;
+      c += __popcll(pm);
+      c1 += __popcll(__ballot(pass && ci < split));
+    });
   *c_split = c1;
   return c;
 }
@@ -497,6 +471,36 @@ __device__ __forceinline__ float sketch_distance(const BSParams& P, const uint4*
   return (float)tot;
 }
 
+// ---- per-query bookkeeping that does not depend on the frontier layout: shared by the three kernels ----
+// The callers keep the `lane == 0` tests: with the test inside the helper hipcc schedules the register-frontier kernels
+// differently ("Shared per-query helpers").
+
+// Persistent blocks (filter table in HBM, one table per block): the next launch slot from the counter, wave-uniform.  Only
+// lane 0's value is read back; `slot` is what the other lanes carry meanwhile.
+__device__ __forceinline__ uint32_t next_slot(const BSParams& P, int lane, uint32_t slot = 0) {
+  if (lane == 0) slot = atomicAdd(P.work_counter, 1u);
+  return __builtin_amdgcn_readfirstlane(slot);
+}
+
+// visited.insert(current) (:112-114) as far as the caller sees it: entry nvis of the query's visited list (lane 0, and only when
+// a list was asked for: visited_cap != 0).  A full list sets status bit 1.  The frontier's own flag is the kernel's business.
+__device__ __forceinline__ void record_visit(const BSParams& P, uint32_t qi, uint32_t nvis, uint64_t cur_key) {
+  if (nvis < P.out.visited_cap) {
+    if (P.out.visited_ids) P.out.visited_ids[(size_t)qi * P.out.visited_cap + nvis] = key_id(cur_key);
+    if (P.out.visited_dists) P.out.visited_dists[(size_t)qi * P.out.visited_cap + nvis] = key_dist(cur_key);
+  } else {
+    atomicOr(P.status, 1u);
+  }
+}
+
+// The per-query counters (:211-213), each optional (lane 0).
+__device__ __forceinline__ void write_counters(const BSParams& P, uint32_t qi, uint32_t f, uint32_t nvis, uint32_t dcmps, uint32_t degsum) {
+  if (P.out.frontier_size) P.out.frontier_size[qi] = f;
+  if (P.out.visited_count) P.out.visited_count[qi] = nvis;
+  if (P.out.dist_cmps) P.out.dist_cmps[qi] = dcmps;
+  if (P.out.degree_sum) P.out.degree_sum[qi] = degsum;
+}
+
 // Generic kernel: any beam (frontier in LDS), filter in LDS or in HBM scratch.
 // FILTER: filtered_beam_search with use_filtering (beamSearch.h:98-100,117-123,139-146) -- while the frontier is full, a
 // neighbour that passed the hash filter gets a full distance only if its sketch distance to the query is below the running
@@ -526,11 +530,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
   const uint32_t BIG_ORD = f2ord(2147483648.0f);  // (distanceType) numeric_limits<int>::max()  (:152)
 
   uint32_t slot = blockIdx.x;
-  if constexpr (!HASH_LDS) {  // persistent: one filter slot per block, queries pulled from a counter
-    slot = 0;
-    if (lane == 0) slot = atomicAdd(P.work_counter, 1u);
-    slot = __builtin_amdgcn_readfirstlane(slot);
-  }
+  if constexpr (!HASH_LDS) slot = next_slot(P, lane);
   while (slot < P.nq) {
     const uint32_t qi = P.order ? P.order[slot] : slot;
     uint32_t* H = HASH_LDS ? Hl : P.hash_global + ((size_t)blockIdx.x << P.bits);
@@ -561,10 +561,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
     [[maybe_unused]] uint32_t pcmps = P.nstarts;   // FILTER: the reference's local dist_cmps (:83,137); dcmps is full_dist_cmps
     [[maybe_unused]] float fsum = 0.0f, fthr = 0.0f;   // FILTER: filter_threshold_sum / filter_threshold (:98-100)
     [[maybe_unused]] uint32_t fcount = 0;
-#ifdef PANN_STAMPS
-    unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
-#endif
+    PANN_STAMP_BEGIN();
     uint64_t* DL = P.dropped + (size_t)qi * P.dcap;
     [[maybe_unused]] MaskedList R{reinterpret_cast<uint64_t*>(smem + P.rl_off), P.out.out_k ? KEY_INF : 0ull, 0u};
     [[maybe_unused]] const uint32_t thr_lane = P.out.out_k ? P.out.out_k - 1u : 0u;
@@ -612,14 +609,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
         // ---- visited.insert(current) (:112-114) ----
         if (lane == 0) {
           Fv[cur_idx] = 1;
-          if (P.out.visited_cap) {
-            if (nvis < P.out.visited_cap) {
-              if (P.out.visited_ids) P.out.visited_ids[(size_t)qi * P.out.visited_cap + nvis] = cur;
-              if (P.out.visited_dists) P.out.visited_dists[(size_t)qi * P.out.visited_cap + nvis] = key_dist(cur_key);
-            } else {
-              atomicOr(P.status, 1u);
-            }
-          }
+          if (P.out.visited_cap) record_visit(P, qi, nvis, cur_key);
         }
         nvis++;
         const bool more_unvisited = unv_total > 1;         // offset + 1 < remain (:165)
@@ -801,23 +791,14 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
       if (P.out.dists) P.out.dists[qo + j] = ok ? key_dist(key) : __builtin_inff();
     }
     }
-#ifdef PANN_STAMPS
-    if (lane == 0 && P.stamps) for (int i = 0; i < 8; i++) P.stamps[(size_t)qi * 8 + i] = stamp_sum[i];
-#endif
+    PANN_STAMP_FLUSH(qi);
     if (lane == 0) {
-      if (P.out.frontier_size) P.out.frontier_size[qi] = f;
-      if (P.out.visited_count) P.out.visited_count[qi] = nvis;
-      if (P.out.dist_cmps) P.out.dist_cmps[qi] = dcmps;
-      if (P.out.degree_sum) P.out.degree_sum[qi] = degsum;
+      write_counters(P, qi, f, nvis, dcmps, degsum);
       if constexpr (FILTER) if (P.pruned_cmps) P.pruned_cmps[qi] = pcmps;
     }
     PANN_WSYNC();
     if constexpr (HASH_LDS) break;
-    else {
-      slot = 0;
-      if (lane == 0) slot = atomicAdd(P.work_counter, 1u);
-      slot = __builtin_amdgcn_readfirstlane(slot);
-    }
+    else slot = next_slot(P, lane);
   }
 }
 
@@ -864,10 +845,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
   [[maybe_unused]] const uint32_t thr_lane = P.out.out_k ? P.out.out_k - 1u : 0u;
   [[maybe_unused]] MaskSrc M{};
   if constexpr (MASKED) { M = mask_src<MASKED>(P, qi); R.L[lane] = KEY_INF; }
-#ifdef PANN_STAMPS
-  unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
-#endif
+  PANN_STAMP_BEGIN();
 
   // ---- start points (:66-70); nstarts <= 64 here ----
   {
@@ -900,14 +878,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
       const uint64_t cur_key = readlane64(fkey, cur_idx);
       const uint32_t cur = key_id(cur_key);
       if (lane == cur_idx) fflag = 1;                            // visited.insert(current) (:112-114)
-      if (lane == 0 && P.out.visited_cap) {
-        if (nvis < P.out.visited_cap) {
-          if (P.out.visited_ids) P.out.visited_ids[(size_t)qi * P.out.visited_cap + nvis] = cur;
-          if (P.out.visited_dists) P.out.visited_dists[(size_t)qi * P.out.visited_cap + nvis] = key_dist(cur_key);
-        } else {
-          atomicOr(P.status, 1u);
-        }
-      }
+      if (lane == 0 && P.out.visited_cap) record_visit(P, qi, nvis, cur_key);
       nvis++;
       uint32_t cutoff_ord = BIG_ORD;                             // :150-152
       if (f == beam) cutoff_ord = (uint32_t)(readlane64(fkey, (int)f - 1) >> 32);
@@ -922,12 +893,8 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
       const bool pref_hit = PANN_B64_PREFETCH && (pref_id == cur);
       const uint32_t pref_val = pref_row;
       pref_id = SENTINEL;
-      const uint64_t rest1 = um & (um - 1);
-      // two vertices this iteration? (nvis already counts `cur`: a second visit needs nvis < limit).  The pair path (off in the
-      // shipped build) has no masked form: a MASKED instantiation always takes the single-vertex path
-      const bool pair_try = PANN_B64_PAIR && !MASKED && P.skip_enabled && rest1 != 0ull && P.gstride <= PANN_WAVE && nvis < P.limit;
       if (PANN_B64_PREFETCH) {
-        const uint64_t rest = pair_try ? (rest1 & (rest1 - 1)) : rest1;      // the entry after the one(s) visited now
+        const uint64_t rest = um & (um - 1);                       // the entry after the one visited now
         if (rest) {
           pref_id = key_id(readlane64(fkey, __ffsll((unsigned long long)rest) - 1));
           const uint32_t* np = P.graph + (size_t)pref_id * P.gstride + min((uint32_t)lane, P.gstride - 1);
@@ -936,65 +903,6 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
       }
 
       const uint32_t* row = P.graph + (size_t)cur * P.gstride;
-      if (pair_try) {
-        // While merges are skipped (:162-168) the frontier and the cutoff do not change, so the vertex after `cur` is known:
-        // the second unvisited entry.  Both adjacency rows are fetched together, the filter is replayed row after row and ONE
-        // gather fetches the survivors of both.  If the candidates of row 1 alone end the skipping (or row 2 does not fit the
-        // candidate list), row 2 never happened: its candidates are cut off and its table writes are put back.
-        const int idx2 = __ffsll((unsigned long long)rest1) - 1;
-        const bool more_after2 = (rest1 & (rest1 - 1)) != 0ull;
-        const uint64_t key2 = readlane64(fkey, idx2);
-        const uint32_t cur2 = key_id(key2);
-        uint32_t a1 = SENTINEL, a2 = SENTINEL;
-        if (lane < (int)P.gstride) {
-          a1 = pref_hit ? pref_val : row[lane];
-          a2 = P.graph[(size_t)cur2 * P.gstride + lane];
-        }
-        const bool act1 = (a1 != SENTINEL) && ((uint32_t)lane < P.degree_limit);
-        const bool act2 = (a2 != SENTINEL) && ((uint32_t)lane < P.degree_limit);
-        PANN_STAMP(1);
-        const bool seen1 = filter_update<true>(H, hmask, act1, a1, lane);
-        FilterUndo u2;
-        const bool seen2 = filter_update<true>(H, hmask, act2, a2, lane, nullptr, 0, LdsPart{nullptr, 0, 0}, &u2);
-        const bool keep1 = act1 && !seen1 && ((int64_t)a1 != self);
-        const bool keep2 = act2 && !seen2 && ((int64_t)a2 != self);
-        const uint64_t km1 = __ballot(keep1), km2 = __ballot(keep2);
-        const uint32_t m1 = __popcll(km1), m2 = __popcll(km2);
-        const bool both = (c + m1 + m2 <= P.ccap);                   // the candidate list is sized for beam/8 - 1 + ONE row
-        if (keep1) Pl[lanes_below(km1, lane)] = a1;
-        if (both && keep2) Pl[m1 + lanes_below(km2, lane)] = a2;
-        PANN_WSYNC();
-        PANN_STAMP(2);
-        uint32_t c_after1 = c;
-        if (both) {
-          if (m1 + m2) c = gather_distances_split<DT, METRIC, LPC, NCH1, PANN_GU, true>(P, qreg, qlds, Pl, m1 + m2, m1, cutoff_ord, C, c, lane, &c_after1);
-        } else {
-          if (m1) c = gather_distances<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, Pl, m1, cutoff_ord, C, c, lane);
-          c_after1 = c;
-        }
-        PANN_WSYNC();
-        PANN_STAMP(3);
-        // the reference's decision after vertex 1 (another unvisited entry exists): skip iff its list is still short
-        const bool two = both && (c_after1 == 0 || c_after1 < beam / 8);
-        if (!two) { c = c_after1; filter_undo<true>(H, u2, 0, LdsPart{nullptr, 0, 0}); }
-        if (two) {
-          if (lane == idx2) fflag = 1;
-          if (lane == 0 && P.out.visited_cap) {
-            if (nvis < P.out.visited_cap) {
-              if (P.out.visited_ids) P.out.visited_ids[(size_t)qi * P.out.visited_cap + nvis] = cur2;
-              if (P.out.visited_dists) P.out.visited_dists[(size_t)qi * P.out.visited_cap + nvis] = key_dist(key2);
-            } else {
-              atomicOr(P.status, 1u);
-            }
-          }
-          nvis++;
-        }
-        degsum += __popcll(__ballot(act1)) + (two ? __popcll(__ballot(act2)) : 0u);
-        dcmps += m1 + (two ? m2 : 0u);
-        const bool more_left = two ? more_after2 : true;
-        const bool skip = (c == 0) || (c < beam / 8 && more_left);
-        do_merge = !skip;
-      } else {
       for (uint32_t i0 = 0; i0 < P.gstride; i0 += PANN_WAVE) {
         const uint32_t i = i0 + lane;
         uint32_t a = SENTINEL;
@@ -1027,7 +935,6 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
       }
       const bool skip = (c == 0) || (P.skip_enabled && c < beam / 8 && more_unvisited);   // :162-168
       do_merge = !skip;
-      }   // single-vertex path
     }
     if (do_merge) {
       const uint32_t f_old = f;
@@ -1133,15 +1040,8 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
     if (P.out.ids) P.out.ids[qo + lane] = ok ? key_id(fkey) : SENTINEL;
     if (P.out.dists) P.out.dists[qo + lane] = ok ? key_dist(fkey) : __builtin_inff();
   }
-#ifdef PANN_STAMPS
-  if (lane == 0 && P.stamps) for (int i = 0; i < 8; i++) P.stamps[(size_t)qi * 8 + i] = stamp_sum[i];
-#endif
-  if (lane == 0) {
-    if (P.out.frontier_size) P.out.frontier_size[qi] = f;
-    if (P.out.visited_count) P.out.visited_count[qi] = nvis;
-    if (P.out.dist_cmps) P.out.dist_cmps[qi] = dcmps;
-    if (P.out.degree_sum) P.out.degree_sum[qi] = degsum;
-  }
+  PANN_STAMP_FLUSH(qi);
+  if (lane == 0) write_counters(P, qi, f, nvis, dcmps, degsum);
 }
 
 // =============================================================================================
@@ -1172,11 +1072,7 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
   // filter in LDS: one query per block.  Filter in HBM (16 KB of LDS would cap a CU at 8 queries): persistent
   // blocks, one table per block, queries pulled from a counter.
   uint32_t slot = blockIdx.x;
-  if constexpr (!HASH_LDS) {
-    slot = 0;
-    if (lane == 0) slot = atomicAdd(P.work_counter, 1u);
-    slot = __builtin_amdgcn_readfirstlane(slot);
-  }
+  if constexpr (!HASH_LDS) slot = next_slot(P, lane);
   while (slot < P.nq) {
   const uint32_t qi = P.order ? P.order[slot] : slot;
   uint32_t* H = HASH_LDS ? Hl : P.hash_global + ((size_t)blockIdx.x << P.bits);
@@ -1199,10 +1095,7 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
   uint64_t fkey[RB] = {KEY_INF, KEY_INF};
   uint32_t fflag[RB] = {0, 0};
   uint64_t* DL = P.dropped + (size_t)qi * P.dcap;
-#ifdef PANN_STAMPS
-  unsigned long long stamp_sum[8] = {0, 0, 0, 0, 0, 0, 0, 0}, stamp_prev;
-  asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(stamp_prev)::"memory");
-#endif
+  PANN_STAMP_BEGIN();
   auto entry_key = [&](uint32_t e) -> uint64_t {            // uniform e
     return (e < 64) ? readlane64(fkey[0], (int)e) : readlane64(fkey[1], (int)e - 64);
   };
@@ -1240,7 +1133,10 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
       // sequential loop) and ONE gather fetches the survivors of both -- twice the bytes in flight per wave in the phase
       // that is 52 % of this kernel's time.  If the candidates of row 1 alone end the skipping (or row 2 does not fit),
       // row 2 never happened: its candidates are cut off the list and its table writes are put back (FilterUndo).
-      if ((CODES ? PANN_B128_PAIR_CODES : PANN_B128_PAIR) && P.skip_enabled && more_unvisited && P.gstride <= PANN_WAVE && nvis + 1 < P.limit) {
+      // Only with the filter of class codes (PANN_B128_PAIR_CODES): the id table, in LDS or HBM, measured slower with it.
+      bool pair = false;
+      if constexpr (CODES) pair = PANN_B128_PAIR_CODES && P.skip_enabled && more_unvisited && P.gstride <= PANN_WAVE && nvis + 1 < P.limit;
+      if (pair) {
         uint64_t r0 = um0, r1 = um1;
         if (r0) r0 &= r0 - 1; else r1 &= r1 - 1;
         const int idx2 = r0 ? __ffsll((unsigned long long)r0) - 1 : 64 + __ffsll((unsigned long long)r1) - 1;
@@ -1254,23 +1150,15 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
         if (lane < (int)P.gstride) {
           a1 = (pref_id == cur) ? pref_row : P.graph[(size_t)cur * P.gstride + lane];
           a2 = P.graph[(size_t)cur2 * P.gstride + lane];
-          if constexpr (CODES) {
-            code1 = (pref_id == cur) ? pref_code : (uint32_t)P.gcode[(size_t)cur * P.gstride + lane];
-            code2 = P.gcode[(size_t)cur2 * P.gstride + lane];
-          }
+          code1 = (pref_id == cur) ? pref_code : (uint32_t)P.gcode[(size_t)cur * P.gstride + lane];
+          code2 = P.gcode[(size_t)cur2 * P.gstride + lane];
         }
         pref_id = SENTINEL;
         const bool act1 = (a1 != SENTINEL) && ((uint32_t)lane < P.degree_limit);
         const bool act2 = (a2 != SENTINEL) && ((uint32_t)lane < P.degree_limit);
         FilterUndo u2;
-        bool seen1, seen2;
-        if constexpr (CODES) {
-          seen1 = filter_update_codes(P8, P4, hmask, act1, a1, code1, lane, T);
-          seen2 = filter_update_codes(P8, P4, hmask, act2, a2, code2, lane, T, &u2);
-        } else {
-          seen1 = filter_update<HASH_LDS>(H, hmask, act1, a1, lane, T, hb, Lp);
-          seen2 = filter_update<HASH_LDS>(H, hmask, act2, a2, lane, T, hb, Lp, &u2);
-        }
+        const bool seen1 = filter_update_codes(P8, P4, hmask, act1, a1, code1, lane, T);
+        const bool seen2 = filter_update_codes(P8, P4, hmask, act2, a2, code2, lane, T, &u2);
         const bool keep1 = act1 && !seen1 && ((int64_t)a1 != self);
         const bool keep2 = act2 && !seen2 && ((int64_t)a2 != self);
         const uint64_t km1 = __ballot(keep1), km2 = __ballot(keep2);
@@ -1289,11 +1177,7 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
         PANN_WSYNC();
         // the reference's decision after vertex 1 (another unvisited entry exists): skip iff its list is still short
         const bool two = both && (c_after1 == 0 || c_after1 < beam / 8);
-        if (!two) {
-          c = c_after1;
-          if constexpr (CODES) filter_undo_codes(P8, P4, u2);
-          else filter_undo<HASH_LDS>(H, u2, hb, Lp);
-        }
+        if (!two) { c = c_after1; filter_undo_codes(P8, P4, u2); }
         // commit: visited.insert(current) (:112-114), counters
         if (cur_idx < 64) { if (lane == cur_idx) fflag[0] = 1; } else { if (lane == cur_idx - 64) fflag[1] = 1; }
         if (two) { if (idx2 < 64) { if (lane == idx2) fflag[0] = 1; } else { if (lane == idx2 - 64) fflag[1] = 1; } }
@@ -1315,14 +1199,7 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
         do_merge = !skip;
       } else {
       if (cur_idx < 64) { if (lane == cur_idx) fflag[0] = 1; } else { if (lane == cur_idx - 64) fflag[1] = 1; }
-      if (lane == 0 && P.out.visited_cap) {
-        if (nvis < P.out.visited_cap) {
-          if (P.out.visited_ids) P.out.visited_ids[(size_t)qi * P.out.visited_cap + nvis] = cur;
-          if (P.out.visited_dists) P.out.visited_dists[(size_t)qi * P.out.visited_cap + nvis] = key_dist(cur_key);
-        } else {
-          atomicOr(P.status, 1u);
-        }
-      }
+      if (lane == 0 && P.out.visited_cap) record_visit(P, qi, nvis, cur_key);
       nvis++;
       uint32_t cutoff_ord = BIG_ORD;
       if (f == beam) cutoff_ord = (uint32_t)(entry_key(f - 1) >> 32);
@@ -1472,9 +1349,7 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
     PANN_STAMP(4);
     first = false;
   }
-#ifdef PANN_STAMPS
-  if (lane == 0 && P.stamps) for (int i = 0; i < 8; i++) P.stamps[(size_t)qi * 8 + i] = stamp_sum[i];
-#endif
+  PANN_STAMP_FLUSH(qi);
 
   const size_t qo = (size_t)qi * P.out.out_k;
 #pragma unroll
@@ -1486,18 +1361,12 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
       if (P.out.dists) P.out.dists[qo + j] = ok ? key_dist(fkey[r]) : __builtin_inff();
     }
   }
-  if (lane == 0) {
-    if (P.out.frontier_size) P.out.frontier_size[qi] = f;
-    if (P.out.visited_count) P.out.visited_count[qi] = nvis;
-    if (P.out.dist_cmps) P.out.dist_cmps[qi] = dcmps;
-    if (P.out.degree_sum) P.out.degree_sum[qi] = degsum;
-  }
+  if (lane == 0) write_counters(P, qi, f, nvis, dcmps, degsum);
   if constexpr (HASH_LDS) {
     break;
   } else {
     PANN_WSYNC();
-    if (lane == 0) slot = atomicAdd(P.work_counter, 1u);
-    slot = __builtin_amdgcn_readfirstlane(slot);
+    slot = next_slot(P, lane, slot);
   }
   }   // while (slot < P.nq)
 }
@@ -1627,76 +1496,51 @@ size_t search_workspace_bytes(const DeviceIndex& ix, const SearchArgs& a) {
   return need;
 }
 
-// masked search, MODE = MASK_BITMAP / MASK_LABELS: register frontier at bcap 64, else the generic kernel
-template <int DT, int METRIC, int LPC, bool NCH1, int MODE>
-static hipError_t launch_masked(const BSParams& P, const Plan& p, hipStream_t stream) {
-  if (p.b64) {
-    if constexpr (!masked_b64_fits(DT, LPC, NCH1)) return hipErrorInvalidValue;   // make_plan never asks for it
-    else {
-      auto kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MODE>;
-      hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-    }
-  } else if (p.hash_lds) {
-    auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MODE>;
-    if (p.lds_bytes > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-  } else {
-    auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MODE>;
-    if (p.lds_bytes > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-  }
+// One launch: LDS above the 48 KB default is asked for by attribute; one block per query, or -- persistent kernels, whose blocks
+// pull queries from the counter -- one block per filter table of the workspace (search_workspace_bytes).
+using SearchKernel = void (*)(BSParams);
+static hipError_t launch_search(SearchKernel kern, const BSParams& P, const Plan& p, bool persistent, hipStream_t stream) {
+  if (p.lds_bytes > 48 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+  const uint32_t grid = persistent ? (uint32_t)std::min<uint64_t>(P.nq, p.slots) : P.nq;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
   return hipGetLastError();
 }
 
+// masked search, MODE = MASK_BITMAP / MASK_LABELS: register frontier at bcap 64, else the generic kernel
+template <int DT, int METRIC, int LPC, bool NCH1, int MODE>
+static SearchKernel masked_kernel(const Plan& p) {
+  if (p.b64) {
+    if constexpr (masked_b64_fits(DT, LPC, NCH1)) return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MODE>;
+    else return nullptr;                                                             // make_plan never asks for it
+  }
+  if (p.hash_lds) return beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MODE>;
+  return beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MODE>;
+}
+
+// Every kernel whose filter table is in HBM (!hash_lds) is persistent, and no other.
 template <int DT, int METRIC, int LPC, bool NCH1>
 static hipError_t launch_variant(const BSParams& P, const Plan& p, hipStream_t stream) {
-  if (p.filter) {   // generic kernel with the sketch filter
-    if (p.hash_lds) {
-      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, true>;
-      if (p.lds_bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-      hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-    } else {
-      auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, true>;
-      if (p.lds_bytes > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-    }
-  } else if (p.masked) {   // allow bitmap or label predicates
-    return p.by_labels ? launch_masked<DT, METRIC, LPC, NCH1, MASK_LABELS>(P, p, stream)
-                       : launch_masked<DT, METRIC, LPC, NCH1, MASK_BITMAP>(P, p, stream);
-  } else if (p.b64) {   // frontier in registers
-    auto kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
-    hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-  } else if (p.b128_codes) {   // two frontier entries per lane, filter of class codes
-    auto kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true, true>;
-    hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-  } else if (p.b128) {   // two frontier entries per lane
-    if (p.b128_hbm) {
-      auto kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, false>;
-      const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-    } else {
-      auto kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true>;
-      hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-    }
+  SearchKernel kern;
+  if (p.filter) {            // generic kernel with the sketch filter
+    if (p.hash_lds) kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, true>;
+    else kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, true>;
+  } else if (p.masked) {     // allow bitmap or label predicates
+    kern = p.by_labels ? masked_kernel<DT, METRIC, LPC, NCH1, MASK_LABELS>(p) : masked_kernel<DT, METRIC, LPC, NCH1, MASK_BITMAP>(p);
+    if (!kern) return hipErrorInvalidValue;
+  } else if (p.b64) {        // frontier in registers
+    kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
+  } else if (p.b128_codes) { // two frontier entries per lane, filter of class codes
+    kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true, true>;
+  } else if (p.b128) {       // two frontier entries per lane
+    if (p.b128_hbm) kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, false>;
+    else kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true>;
   } else if (p.hash_lds) {
-    auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true>;
-    if (p.lds_bytes > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    hipLaunchKernelGGL(kern, dim3(P.nq), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true>;
   } else {
-    auto kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false>;
-    if (p.lds_bytes > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-    const uint32_t grid = (uint32_t)std::min<uint64_t>(P.nq, p.slots);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false>;
   }
-  return hipGetLastError();
+  return launch_search(kern, P, p, !p.hash_lds, stream);
 }
 
 template <int DT, int METRIC>

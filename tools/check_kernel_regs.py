@@ -19,12 +19,18 @@ RULES = {   # object -> [(kernel name pattern, max vgprs or None)]
 }
 
 
+def unbundle(obj, td):
+    """The gfx950 code object inside a host object, written into directory td; returns its path."""
+    fat, co = os.path.join(td, "fat.bin"), os.path.join(td, "dev.co")
+    subprocess.check_call([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj])
+    subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
+                           f"--input={fat}", f"--output={co}", "--unbundle"])
+    return co
+
+
 def kernels_of(obj):
     with tempfile.TemporaryDirectory() as td:
-        fat, co = os.path.join(td, "fat.bin"), os.path.join(td, "dev.co")
-        subprocess.check_call([f"{LLVM}/llvm-objcopy", f"--dump-section=.hip_fatbin={fat}", obj])
-        subprocess.check_call([f"{LLVM}/clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950",
-                               f"--input={fat}", f"--output={co}", "--unbundle"])
+        co = unbundle(obj, td)
         notes = subprocess.run([f"{LLVM}/llvm-readelf", "--notes", co], capture_output=True, text=True, check=True).stdout
     out = []
     for blk in re.split(r"\n\s+- \.agpr_count:", notes)[1:]:
