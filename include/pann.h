@@ -783,6 +783,44 @@ int pann_labels_to_allow_dev(pann_index* idx, int kind, const pann_label_pred* d
 int pann_label_count_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_counts,
                          void* stream);
 
+/* ---- subset index: carve out, compact or grow a handle on the device (DESIGN.md "Subset index") ----  This project's own.
+ * A new handle over the rows of src that a bitmap keeps, in ascending id order, with room for n_out rows; the graph is
+ * renumbered, labels and sketch are carried over, nothing leaves the device.  Compaction after pann_vamana_delete_batch (the
+ * bitmap without the deleted ids), a dedicated index over one tenant's or label's points (the bitmap of
+ * pann_labels_to_allow_dev), growth (allow == NULL, n_out > n).
+ * THE RULE.
+ *   Bitmap: `allow` is ONE bitmap in the format of pann_batch_search_masked: ceil(n / 32) words, point i kept iff bit i & 31 of
+ *     word i >> 5 is set; bits at positions >= n are ignored.  allow == NULL keeps every point: a clone, or a grown copy when
+ *     n_out > n.
+ *   Sizes: K = the kept ids in ascending order, m = |K|.  The new handle has n' = n_out ? n_out : m rows.
+ *     new_to_old[r] = K[r] for r < m (entries past m are not written); old_to_new[i] = the rank of i in K, or 0xFFFFFFFF if i
+ *     is dropped (n words); *kept_out = m.  All three outputs are optional (NULL).
+ *   Fixed: the new handle has src's d, dtype, metric, max_deg and device.  Every element type is allowed, PANN_U4 / PANN_I4
+ *     included: rows are moved as bytes.
+ *   Points: row r < m is row K[r] of src, byte for byte, over the whole device row including its zero padding; rows [m, n')
+ *     are zero.
+ *   Graph: copy_graph != 0: row r < m holds the neighbours of src's row K[r] IN ROW ORDER, without those that are not in K, each
+ *     mapped through old_to_new, packed at the front, the remaining slots empty; rows [m, n') are empty.  copy_graph == 0: every
+ *     row is empty.
+ *   Labels: if src has labels, row r < m gets label[K[r]] and rows [m, n') get 0; otherwise the new handle has none.
+ *   Sketch: if src has a sketch attached its rows are gathered the same way, zero rows past m, and the new handle gets src's
+ *     pann_sketch_params: pann_index_sketch_kind and the query sketching of the fused rerank behave as on src.
+ *   Other state: the exact-float-order flag is carried.  NOT carried, left as on a fresh handle: filter-code tables, locality
+ *     cells, options, dropped-list capacity, the stream -- the new handle has its own private stream.  src is not modified
+ *     (its scratch is used).
+ * Execution: the work runs on src's stream.  With a bitmap that stream is synchronised once for m, which must be known before
+ * anything is allocated, and in every case once more before the call returns, as pann_index_create_quantized does.  The host form
+ * moves the bitmap up and the maps down in packed transfers like every host-pointer entry point; the _dev form takes device
+ * pointers (4-byte aligned) for the bitmap and the two maps -- out and kept_out are host pointers in both.
+ * Status: NULL out or src, n_out != 0 && n_out < m, n' == 0, n' >= 2^31 - 1, a misaligned device pointer -> PANN_ERR_BAD_ARG;
+ * new_to_old != NULL && new_to_old_cap < m -> PANN_ERR_OVERFLOW.  *kept_out is written whenever m was counted -- under
+ * PANN_ERR_OVERFLOW and the n_out / n' errors it is valid, the ids_capacity convention of pann_bruteforce_range.  On every error
+ * nothing is created, *out is left as it was and no output array is written. */
+int pann_index_create_subset_dev(pann_index** out, pann_index* src, const uint32_t* d_allow, uint64_t n_out, int copy_graph,
+                                 uint32_t* d_new_to_old, uint64_t new_to_old_cap, uint32_t* d_old_to_new, uint64_t* kept_out);
+int pann_index_create_subset(pann_index** out, pann_index* src, const uint32_t* allow, uint64_t n_out, int copy_graph,
+                             uint32_t* new_to_old, uint64_t new_to_old_cap, uint32_t* old_to_new, uint64_t* kept_out);
+
 #ifdef __cplusplus
 }
 #endif

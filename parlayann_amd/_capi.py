@@ -236,6 +236,10 @@ SIGNATURES = {
                                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pann_labels_to_allow_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pann_label_count_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pann_index_create_subset_dev": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
+                                               C.c_uint64, C.c_void_p, u64p]),
+    "pann_index_create_subset": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
+                                           C.c_uint64, C.c_void_p, u64p]),
 }
 
 _lib = None

@@ -1784,6 +1784,144 @@ int pann_index_create_quantized(pann_index** out, pann_index* src, const pann_qu
   return PANN_OK;
 }
 
+// ---- subset index (subset.hip, DESIGN.md "Subset index"): a new handle over the rows of src that a bitmap keeps ----
+
+static int subset_checks(pann_index* const* out, const pann_index* src, const char* fn) {
+  if (!out) { set_error(std::string(fn) + ": null output"); return PANN_ERR_BAD_ARG; }
+  return check_idx(src, fn);
+}
+
+// The first half: m = the points d_allow keeps (null: all of them), counted on st and waited for -- the ONE synchronisation
+// before anything is allocated -- and every check that needs m.  The block offsets of the count stay in src->ws3 for the
+// scatter of subset_build.  *kept_out is written as soon as m is known, whatever the checks behind it say.
+static int subset_count(pann_index* src, const char* fn, const uint32_t* d_allow, uint64_t n_out, bool want_new_to_old,
+                        uint64_t new_to_old_cap, uint64_t* kept_out, uint64_t* m_out, uint64_t* rows_out, hipStream_t st) {
+  const std::string f = fn;
+  const uint64_t n = src->ix.n;
+  if (n_out >= 0x7FFFFFFFull) { set_error(f + ": n_out must be < 2^31 - 1 (as n of pann_index_create)"); return PANN_ERR_BAD_ARG; }
+  uint64_t m = n;
+  if (d_allow) {
+    if (int rc = src->ws3.ensure(allow_compact_scratch_bytes(n))) return rc;
+    const uint32_t* d_total = nullptr;
+    if (int rc = allow_compact_count_dev(d_allow, n, src->ws3.as<uint32_t>(), &d_total, st)) return rc;
+    uint32_t count = 0;
+    PANN_HIP(hipMemcpyAsync(&count, d_total, 4, hipMemcpyDeviceToHost, st));
+    PANN_HIP(hipStreamSynchronize(st));
+    m = count;
+  }
+  if (kept_out) *kept_out = m;
+  if (n_out && n_out < m) {
+    set_error(f + ": the bitmap keeps " + std::to_string(m) + " points, n_out has room for " + std::to_string(n_out)); return PANN_ERR_BAD_ARG;
+  }
+  if (m == 0 && n_out == 0) { set_error(f + ": the bitmap keeps no point and n_out is 0: the new handle would have no rows"); return PANN_ERR_BAD_ARG; }
+  if (want_new_to_old && new_to_old_cap < m) {
+    set_error(f + ": " + std::to_string(m) + " kept points, new_to_old has room for " + std::to_string(new_to_old_cap)); return PANN_ERR_OVERFLOW;
+  }
+  *m_out = m; *rows_out = n_out ? n_out : m;
+  return PANN_OK;
+}
+
+// everything that is enqueued on st once the new handle q exists (zero rows, empty graph, idle stream: index_create_impl)
+static int subset_fill(pann_index* q, pann_index* src, const uint32_t* d_allow, uint64_t m, int copy_graph, uint32_t* d_new_to_old,
+                       uint32_t* d_old_to_new, hipStream_t st) {
+  const DeviceIndex& sx = src->ix;
+  DeviceIndex& qx = q->ix;
+  const uint64_t n = sx.n, rows = qx.n;
+  qx.exact = sx.exact; qx.lpc = sx.lpc; qx.nch = sx.nch;        // the exact-float-order flag (same dbytes: same pstride)
+  if (sx.labels) {
+    if (int rc = q->labels_buf.ensure((size_t)rows * 4)) return rc;
+    if (rows > m) PANN_HIP(hipMemsetAsync(q->labels_buf.as<uint32_t>() + m, 0, (size_t)(rows - m) * 4, st));
+    qx.labels = q->labels_buf.as<uint32_t>();
+  }
+  if (sx.sketch) {
+    if (int rc = q->sketch_buf.ensure((size_t)rows * sx.sk_stride)) return rc;
+    if (rows > m) PANN_HIP(hipMemsetAsync(q->sketch_buf.as<uint8_t>() + (size_t)m * sx.sk_stride, 0, (size_t)(rows - m) * sx.sk_stride, st));
+    qx.sketch = q->sketch_buf.as<uint8_t>(); qx.sk_stride = sx.sk_stride; qx.sk_kind = sx.sk_kind; qx.sk_as_written = sx.sk_as_written;
+    q->sk_params = src->sk_params;
+  }
+  if (!d_allow) {      // everything is kept (m == n): the rows as they are, and the identity for the maps
+    PANN_HIP(hipMemcpyAsync(qx.points, sx.points, (size_t)n * sx.pstride, hipMemcpyDeviceToDevice, st));
+    if (copy_graph) PANN_HIP(hipMemcpyAsync(qx.graph, sx.graph, (size_t)n * sx.gstride * 4, hipMemcpyDeviceToDevice, st));
+    if (sx.labels) PANN_HIP(hipMemcpyAsync(q->labels_buf.buf, sx.labels, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    if (sx.sketch) PANN_HIP(hipMemcpyAsync(q->sketch_buf.buf, sx.sketch, (size_t)n * sx.sk_stride, hipMemcpyDeviceToDevice, st));
+    return subset_iota_dev(d_new_to_old, d_old_to_new, n, st);
+  }
+  if (m) { if (int rc = allow_compact_scatter_dev(d_allow, n, src->ws3.as<uint32_t>(), d_new_to_old, (uint32_t)m, st)) return rc; }
+  if (d_old_to_new) { if (int rc = subset_invert_dev(d_new_to_old, m, d_old_to_new, n, st)) return rc; }
+  if (int rc = subset_gather_rows_dev(sx.points, qx.points, sx.pstride, d_new_to_old, m, st)) return rc;
+  if (sx.labels) { if (int rc = subset_gather_rows_dev(sx.labels, q->labels_buf.buf, 4, d_new_to_old, m, st)) return rc; }
+  if (sx.sketch) { if (int rc = subset_gather_rows_dev(sx.sketch, q->sketch_buf.buf, sx.sk_stride, d_new_to_old, m, st)) return rc; }
+  if (copy_graph) return subset_renumber_graph_dev(sx.graph, qx.graph, sx.gstride, d_new_to_old, d_old_to_new, n, m, st);
+  return PANN_OK;
+}
+
+// The second half, on device pointers: allocate (scratch on src for a map the caller did not ask for, then the new handle), enqueue
+// on st.  NOT synchronised: the caller waits for st before it hands *q_out on.  Nothing is enqueued before everything is allocated
+// but the labels and the sketch of the new handle itself.
+static int subset_build(pann_index** q_out, pann_index* src, const uint32_t* d_allow, uint64_t m, uint64_t rows, int copy_graph,
+                        uint32_t* d_new_to_old, uint32_t* d_old_to_new, hipStream_t st) {
+  const DeviceIndex& sx = src->ix;
+  if (d_allow && m && !d_new_to_old) {
+    if (int rc = src->ws4.ensure((size_t)m * 4)) return rc;
+    d_new_to_old = src->ws4.as<uint32_t>();
+  }
+  if (d_allow && m && copy_graph && !d_old_to_new) {
+    if (int rc = src->ws2.ensure((size_t)sx.n * 4)) return rc;
+    d_old_to_new = src->ws2.as<uint32_t>();
+  }
+  pann_index* q = nullptr;
+  if (int rc = index_create_impl(&q, nullptr, rows, sx.d, sx.dtype, row_bytes_of(sx.dtype, sx.d), sx.metric, nullptr, sx.max_deg, src->device)) return rc;
+  if (int rc = subset_fill(q, src, d_allow, m, copy_graph, d_new_to_old, d_old_to_new, st)) {
+    (void)hipStreamSynchronize(st);      // nothing of q may still be written when it goes
+    pann_index_destroy(q);
+    return rc;
+  }
+  *q_out = q;
+  return PANN_OK;
+}
+
+int pann_index_create_subset_dev(pann_index** out, pann_index* src, const uint32_t* d_allow, uint64_t n_out, int copy_graph,
+                                 uint32_t* d_new_to_old, uint64_t new_to_old_cap, uint32_t* d_old_to_new, uint64_t* kept_out) {
+  const char* fn = "pann_index_create_subset_dev";
+  if (int rc = subset_checks(out, src, fn)) return rc;
+  if ((uintptr_t)d_allow % 4 != 0 || (uintptr_t)d_new_to_old % 4 != 0 || (uintptr_t)d_old_to_new % 4 != 0) {
+    set_error(std::string(fn) + ": device pointers must be 4-byte aligned"); return PANN_ERR_BAD_ARG;
+  }
+  DeviceGuard g(src->device);
+  hipStream_t st = src->stream;
+  uint64_t m = 0, rows = 0;
+  if (int rc = subset_count(src, fn, d_allow, n_out, d_new_to_old != nullptr, new_to_old_cap, kept_out, &m, &rows, st)) return rc;
+  pann_index* q = nullptr;
+  if (int rc = subset_build(&q, src, d_allow, m, rows, copy_graph, d_new_to_old, d_old_to_new, st)) return rc;
+  const hipError_t e = hipStreamSynchronize(st);
+  if (e != hipSuccess) { pann_index_destroy(q); return hip_fail(e, "hipStreamSynchronize"); }
+  *out = q;
+  return PANN_OK;
+}
+
+int pann_index_create_subset(pann_index** out, pann_index* src, const uint32_t* allow, uint64_t n_out, int copy_graph,
+                             uint32_t* new_to_old, uint64_t new_to_old_cap, uint32_t* old_to_new, uint64_t* kept_out) {
+  const char* fn = "pann_index_create_subset";
+  if (int rc = subset_checks(out, src, fn)) return rc;
+  DeviceGuard g(src->device);
+  const uint64_t n = src->ix.n;
+  // up: the bitmap, ceil(n / 32) words; the count decides what comes down, so the maps travel in a trip of their own
+  HostTrip up(src);
+  const int i_allow = up.in.add(allow, (size_t)((n + 31) / 32) * 4);
+  if (allow) { if (int rc = up.begin()) return rc; }
+  const uint32_t* d_allow = allow ? up.din<uint32_t>(i_allow) : nullptr;
+  uint64_t m = 0, rows = 0;
+  if (int rc = subset_count(src, fn, d_allow, n_out, new_to_old != nullptr, new_to_old_cap, kept_out, &m, &rows, up.st)) return rc;
+  HostTrip down(src);       // no inputs: the bitmap stays where it is
+  const int o_n2o = down.out.add(new_to_old, (size_t)m * 4), o_o2n = down.out.add(old_to_new, (size_t)n * 4);
+  if (int rc = down.begin()) return rc;
+  pann_index* q = nullptr;
+  if (int rc = subset_build(&q, src, d_allow, m, rows, copy_graph, down.dout<uint32_t>(o_n2o), down.dout<uint32_t>(o_o2n), down.st)) return rc;
+  if (int rc = down.finish()) { pann_index_destroy(q); return rc; }      // waits for the stream: the new handle is complete
+  *out = q;
+  return PANN_OK;
+}
+
 int pann_quantize_rows_dev(const pann_quant_params* p, const float* d_rows, uint64_t n, uint64_t stride_bytes,
                            int normalize_first, void* d_out, uint64_t out_stride_bytes, void* stream) {
   if (int rc = check_quant_params(p, "pann_quantize_rows_dev")) return rc;

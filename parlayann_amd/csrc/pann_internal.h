@@ -221,6 +221,19 @@ int label_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, ui
                    int kind, const pann_label_pred* d_preds, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
                    uint32_t* d_out_counts);
 
+// subset.hip: the kernels of pann_index_create_subset* (DESIGN.md "Subset index").  d_new_to_old: the m kept ids, ascending
+// (allow_compact_scatter_dev); every call is a no-op for m == 0 apart from the fill of subset_invert_dev.
+// d_a[r] = d_b[r] = r, r < m (either may be null): the two maps when everything is kept
+int subset_iota_dev(uint32_t* d_a, uint32_t* d_b, uint64_t m, hipStream_t st);
+// d_old_to_new (n words) <- 0xFFFFFFFF, then d_old_to_new[d_new_to_old[r]] = r
+int subset_invert_dev(const uint32_t* d_new_to_old, uint64_t m, uint32_t* d_old_to_new, uint64_t n, hipStream_t st);
+// row r of d_dst <- row d_new_to_old[r] of d_src, r < m; rows of row_bytes bytes, dense: 4, or a multiple of 16 (16-byte aligned)
+int subset_gather_rows_dev(const void* d_src, void* d_dst, uint32_t row_bytes, const uint32_t* d_new_to_old, uint64_t m, hipStream_t st);
+// graph row r of d_dst_graph <- row d_new_to_old[r] of d_src_graph (n rows of gstride words) without the neighbours that
+// d_old_to_new drops, the others mapped through it, in row order, packed at the front, SENTINEL behind them
+int subset_renumber_graph_dev(const uint32_t* d_src_graph, uint32_t* d_dst_graph, uint32_t gstride, const uint32_t* d_new_to_old,
+                              const uint32_t* d_old_to_new, uint64_t n, uint64_t m, hipStream_t st);
+
 // leaf_knn.hip: lane-owns-row all-pairs top-m for one-byte element types (HCNNG leaves)
 bool dense_gt_eligible(const DeviceIndex& ix, uint32_t m, bool b_ids, bool segmented, int exclude_same);
 uint32_t dense_gt_slots(const DeviceIndex& ix, uint32_t m);

@@ -447,6 +447,59 @@ class DeviceIndex:
         q._h, q._lib = h, self._lib
         return q, p
 
+    # ---- subset index: carve out, compact or grow a handle on the device (DESIGN.md "Subset index") ----
+    def subset(self, allow=None, *, where=None, capacity=None, copy_graph=True, maps=True):
+        """pann_index_create_subset*: a new DeviceIndex over the points a bitmap keeps, in ascending id order, renumbered graph,
+        labels and sketch carried over; nothing but the bitmap and the maps crosses the bus.
+        allow: boolean (n,) or one packed row (allow_bitmap); None keeps every point (a clone; with capacity > n a grown copy).
+        where=(kind, (a, b)): a single label predicate instead, expanded on the device (pann_labels_to_allow_dev) -- no bitmap
+        crosses the bus; the index needs labels.  capacity: rows of the new index (default: the kept points; the rows behind
+        them are zero with empty graph rows).  copy_graph=False: an empty graph (a dedicated index to be built).
+        maps=True -> (index, new_to_old uint32 (m,), old_to_new uint32 (n,), 0xFFFFFFFF for a dropped id); else the index alone.
+        Compaction after deletions: ix.subset(allow_bitmap(ix.n, deleted_ids=D))."""
+        if allow is not None and where is not None:
+            raise ValueError("give allow or where, not both")
+        n, cap = self.n, 0 if capacity is None else int(capacity)
+        if cap < 0:
+            raise ValueError("capacity must not be negative")
+        h, kept = C.c_void_p(), C.c_uint64(0)
+        if where is not None:
+            import torch
+            if np.asarray(where[1]).ndim != 1:
+                raise ValueError("subset takes a single predicate (a, b)")
+            kind, p, d_p, dev = self._device_preds(where)
+            w = (n + 31) // 32
+            d_a = torch.empty(w, dtype=torch.int32, device=dev)
+            st = torch.cuda.current_stream(dev)
+            check(self._lib.pann_labels_to_allow_dev(self._h, kind, C.c_void_p(d_p.data_ptr()), 1, C.c_void_p(d_a.data_ptr()), w,
+                                                     C.c_void_p(st.cuda_stream or None)))
+            st.synchronize()               # the subset runs on the handle's stream: the bitmap has to be complete before it
+            d_n2o = torch.empty(n, dtype=torch.int32, device=dev) if maps else None
+            d_o2n = torch.empty(n, dtype=torch.int32, device=dev) if maps else None
+            check(self._lib.pann_index_create_subset_dev(C.byref(h), self._h, C.c_void_p(d_a.data_ptr()), cap, 1 if copy_graph else 0,
+                                                         C.c_void_p(d_n2o.data_ptr()) if maps else None, n,
+                                                         C.c_void_p(d_o2n.data_ptr()) if maps else None, C.byref(kept)))
+            if maps:
+                n2o = d_n2o[:kept.value].cpu().numpy().view(np.uint32)
+                o2n = d_o2n.cpu().numpy().view(np.uint32)
+        else:
+            a = None
+            if allow is not None:
+                a = pack_allow(allow, n)
+                if a.ndim != 1:
+                    raise ValueError("subset takes one bitmap: boolean (n,) or one packed row")
+            n2o = np.empty(n, np.uint32) if maps else None
+            o2n = np.empty(n, np.uint32) if maps else None
+            check(self._lib.pann_index_create_subset(C.byref(h), self._h, _ptr(a), cap, 1 if copy_graph else 0, _ptr(n2o), n, _ptr(o2n),
+                                                     C.byref(kept)))
+            if maps:
+                n2o = n2o[:kept.value].copy()
+        s = DeviceIndex.__new__(DeviceIndex)
+        s._h, s._lib = h, self._lib
+        s.n, s.d, s.max_degree = int(self._lib.pann_index_size(h)), self.d, self.max_degree
+        s.dtype, s.metric, s.dtype4 = self.dtype, self.metric, self.dtype4
+        return (s, n2o, o2n) if maps else s
+
     # ---- batched beam search: the searchAll / qsearchAll seam (beamSearch.h:374,556) ----
     def batch_search(self, queries=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
                      query_ids=None, out_k=None, visited_cap=0, want_dists=True):
