@@ -821,6 +821,56 @@ int pann_index_create_subset_dev(pann_index** out, pann_index* src, const uint32
 int pann_index_create_subset(pann_index** out, pann_index* src, const uint32_t* allow, uint64_t n_out, int copy_graph,
                              uint32_t* new_to_old, uint64_t new_to_old_cap, uint32_t* old_to_new, uint64_t* kept_out);
 
+/* ---- graph reachability: BFS levels and degrees on the device (DESIGN.md "Graph reachability") ----  This project's own.
+ * Which vertices can a search that starts at `starts` reach at all?  A level-synchronous breadth-first walk over the handle's
+ * current rows.  Only the graph is read, never a point, so every element type is accepted, PANN_U4 / PANN_I4 included.  A
+ * neighbour word >= n (the empty marker) is skipped.
+ * THE RULE.
+ *   level: level[v] = the length of a shortest directed path from any start to v; starts have level 0, duplicate starts mean
+ *     nothing; 0xFFFFFFFF = no path.  n words, every one of them written.
+ *   reached: the bitmap {v : level[v] != 0xFFFFFFFF} in the format of pann_batch_search_masked, ceil(n / 32) words, bits at
+ *     positions >= n written 0: it goes as it is into pann_index_create_subset*, pann_allow_count_dev and every masked entry.
+ *   consider: ONE bitmap in the same format, NULL = every vertex; bits at positions >= n are ignored.  It does NOT steer the walk
+ *     (a masked search walks through disallowed points too); it only selects which vertices are counted and listed as unreached.
+ *     The typical value is the live set after pann_vamana_delete_batch.
+ *   unreached_ids: the considered vertices without a level, ascending, each once; entries past stats->unreached are not written.
+ *     unreached_ids != NULL && unreached_cap < stats->unreached -> PANN_ERR_OVERFLOW: the list is untouched, stats, level and
+ *     reached are valid (the ids_capacity convention of pann_bruteforce_range).
+ *   max_rounds: 0 = expand until the frontier is empty.  r > 0 = at most r expansion rounds: levels 0 .. r are written, vertices
+ *     beyond them are 0xFFFFFFFF and count as unreached, and stats->truncated = 1 iff the level-r frontier is not empty.
+ *   stats (optional) is OVERWRITTEN, not added to.  Every output pointer is optional (NULL); without level no level array exists
+ *     anywhere, the visited bitmap suffices.
+ * Execution: as pann_vamana_delete_batch_dev -- the work runs on the handle's stream, scratch comes from the handle, and both
+ * forms return after the stream has drained: the frontier lengths are read back once per group of rounds (not once per level),
+ * and the unreached count before the list is written.  The host form moves starts and consider up and level, reached and the
+ * ids down in packed transfers like every host-pointer entry point; the _dev form takes device pointers (4-byte aligned) for
+ * them -- stats is a host pointer in both.
+ * Status: NULL idx or starts, nstarts == 0, a start >= n, a misaligned device pointer -> PANN_ERR_BAD_ARG, nothing written (the
+ * host form checks the starts on the host, the _dev form on the device before any output is written). */
+typedef struct pann_reach_stats {
+  uint64_t reached;       /* vertices that got a level, starts included */
+  uint64_t unreached;     /* considered vertices without a level (no consider bitmap: n - reached) */
+  uint64_t max_frontier;  /* population of the largest level */
+  uint32_t levels;        /* 1 + the largest level written */
+  uint32_t truncated;     /* 1: max_rounds stopped the walk with a non-empty frontier left unexpanded */
+  double   t_s;           /* seconds on the device, events around the call's work */
+} pann_reach_stats;
+
+int pann_graph_reach_dev(pann_index* idx, const uint32_t* d_starts, uint32_t nstarts, const uint32_t* d_consider,
+                         uint32_t max_rounds, uint32_t* d_level, uint32_t* d_reached, uint32_t* d_unreached_ids,
+                         uint64_t unreached_cap, pann_reach_stats* stats);
+int pann_graph_reach(pann_index* idx, const uint32_t* starts, uint32_t nstarts, const uint32_t* consider,
+                     uint32_t max_rounds, uint32_t* level, uint32_t* reached, uint32_t* unreached_ids,
+                     uint64_t unreached_cap, pann_reach_stats* stats);
+
+/* out_deg[v] = the neighbour slots of row v that hold an id < n; in_deg[w] = the (row, slot) pairs that name w: a duplicate
+ * in a row counts twice, a self loop counts.  n words each, either may be NULL.  The _dev form takes device pointers (4-byte
+ * aligned) and runs on `stream` with no synchronisation and no allocation (it zero-fills d_in_deg itself, on that stream); the
+ * host form goes through the handle's stream and returns when the arrays are home.  NULL idx, both outputs NULL, a misaligned
+ * device pointer -> PANN_ERR_BAD_ARG. */
+int pann_graph_degrees_dev(pann_index* idx, uint32_t* d_out_deg, uint32_t* d_in_deg, void* stream);
+int pann_graph_degrees(pann_index* idx, uint32_t* out_deg, uint32_t* in_deg);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,12 @@ class DeleteStats(C.Structure):
                 ("candidates", C.c_uint64), ("prune_dist_cmps", C.c_uint64), ("per_point_dist_cmps", C.c_void_p)]
 
 
+class ReachStats(C.Structure):
+    """pann_reach_stats: overwritten by pann_graph_reach*"""
+    _fields_ = [("reached", C.c_uint64), ("unreached", C.c_uint64), ("max_frontier", C.c_uint64), ("levels", C.c_uint32),
+                ("truncated", C.c_uint32), ("t_s", C.c_double)]
+
+
 PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4 = 0, 1, 2, 3
 
 
@@ -240,6 +246,12 @@ SIGNATURES = {
                                                C.c_uint64, C.c_void_p, u64p]),
     "pann_index_create_subset": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                            C.c_uint64, C.c_void_p, u64p]),
+    "pann_graph_reach_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_uint64, C.POINTER(ReachStats)]),
+    "pann_graph_reach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                   C.c_void_p, C.c_uint64, C.POINTER(ReachStats)]),
+    "pann_graph_degrees_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_graph_degrees": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

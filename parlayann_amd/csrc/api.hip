@@ -1922,6 +1922,195 @@ int pann_index_create_subset(pann_index** out, pann_index* src, const uint32_t* 
   return PANN_OK;
 }
 
+// ---- graph reachability (graph_reach.hip, DESIGN.md "Graph reachability"): BFS levels from a set of starts, degrees ----
+
+namespace {
+
+// the scratch of one walk, all of it in idx->ws3: the counter block (the bad-start flag, then the frontier lengths of one group
+// of rounds), the visited and the unreached bitmap, the block offsets of the compaction, the two frontier queues
+struct ReachScratch {
+  uint32_t *flag, *lens, *visited, *unreached, *compact, *queue[2];
+  int place(pann_index* idx) {
+    const uint64_t n = idx->ix.n;
+    const size_t bm = PackedLayout::align((size_t)((n + 31) / 32) * 4), qb = PackedLayout::align((size_t)n * 4);
+    const size_t cb = PackedLayout::align(allow_compact_scratch_bytes(n));
+    if (int rc = idx->ws3.ensure(256 + 2 * bm + cb + 2 * qb)) return rc;
+    uint8_t* p = idx->ws3.as<uint8_t>();
+    flag = (uint32_t*)p; lens = flag + 1; p += 256;
+    visited = (uint32_t*)p; p += bm;
+    unreached = (uint32_t*)p; p += bm;
+    compact = (uint32_t*)p; p += cb;
+    queue[0] = (uint32_t*)p; queue[1] = (uint32_t*)(p + qb);
+    return PANN_OK;
+  }
+};
+static_assert((2 + REACH_GROUP) * 4 <= 256, "the counter block holds the flag and REACH_GROUP + 1 frontier lengths");
+
+struct EventPair {      // t_s of pann_reach_stats: two events around the call's work on the stream
+  hipEvent_t a = nullptr, b = nullptr;
+  ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  int start(hipStream_t st) { PANN_HIP(hipEventCreate(&a)); PANN_HIP(hipEventCreate(&b)); PANN_HIP(hipEventRecord(a, st)); return PANN_OK; }
+  int stop(hipStream_t st) { PANN_HIP(hipEventRecord(b, st)); return PANN_OK; }
+  int seconds(double* out) { float ms = 0; PANN_HIP(hipEventElapsedTime(&ms, a, b)); *out = (double)ms * 1e-3; return PANN_OK; }      // after b has completed
+};
+
+int reach_checks(const pann_index* idx, const char* fn, const uint32_t* starts, uint32_t nstarts) {
+  if (int rc = check_idx(idx, fn)) return rc;
+  if (!starts || nstarts == 0) { set_error(std::string(fn) + ": no start vertex"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+// The walk and the count, on device pointers.  The seeds go into the scratch alone; d_level (optional, n words) is first written
+// once the flag has come back clear.  Rounds are enqueued in groups of REACH_GROUP with one read-back of their frontier lengths
+// per group.  Everything of *rs but t_s; st has drained when it returns.
+int reach_walk(pann_index* idx, const char* fn, const uint32_t* d_starts, uint32_t nstarts, const uint32_t* d_consider,
+               uint32_t max_rounds, uint32_t* d_level, ReachScratch& s, pann_reach_stats* rs, hipStream_t st) {
+  const DeviceIndex& ix = idx->ix;
+  const uint64_t n = ix.n, words = (n + 31) / 32;
+  if (int rc = s.place(idx)) return rc;
+  PANN_HIP(hipMemsetAsync(s.flag, 0, 256, st));
+  PANN_HIP(hipMemsetAsync(s.visited, 0, (size_t)words * 4, st));
+  if (int rc = reach_seed_dev(d_starts, nstarts, n, s.visited, s.queue[0], s.lens, s.flag, st)) return rc;
+  uint32_t h[2 + REACH_GROUP] = {0};
+  PANN_HIP(hipMemcpyAsync(h, s.flag, 8, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  if (h[0]) { set_error(std::string(fn) + ": a start vertex is out of range (>= number of points); nothing was written"); return PANN_ERR_BAD_ARG; }
+  if (d_level) {
+    PANN_HIP(hipMemsetAsync(d_level, 0xFF, (size_t)n * 4, st));
+    if (int rc = reach_level0_dev(s.queue[0], s.lens, n, d_level, st)) return rc;
+  }
+  uint64_t frontier = h[1], reached = h[1], max_frontier = h[1];
+  uint32_t levels = 1, rounds = 0, cur = 0, truncated = 0;
+  while (frontier) {
+    if (max_rounds && rounds == max_rounds) { truncated = 1; break; }
+    const uint32_t g = max_rounds ? std::min(REACH_GROUP, max_rounds - rounds) : REACH_GROUP;
+    PANN_HIP(hipMemsetAsync(s.lens + 1, 0, (size_t)g * 4, st));
+    for (uint32_t j = 0; j < g; j++)
+      if (int rc = reach_expand_dev(ix, s.queue[(cur + j) & 1], s.lens + j, s.queue[(cur + j + 1) & 1], s.lens + j + 1, s.visited,
+                                    d_level, rounds + j + 1, st)) return rc;
+    PANN_HIP(hipMemcpyAsync(h + 1, s.lens + 1, (size_t)g * 4, hipMemcpyDeviceToHost, st));
+    PANN_HIP(hipMemcpyAsync(s.lens, s.lens + g, 4, hipMemcpyDeviceToDevice, st));      // the last frontier opens the next group
+    PANN_HIP(hipStreamSynchronize(st));
+    for (uint32_t j = 1; j <= g && frontier; j++) {
+      frontier = h[j];
+      if (!frontier) break;
+      reached += frontier; max_frontier = std::max(max_frontier, frontier); levels++;
+    }
+    rounds += g; cur = (cur + g) & 1;
+  }
+  if (int rc = reach_finish_dev(s.visited, d_consider, n, s.unreached, st)) return rc;
+  const uint32_t* d_total = nullptr;
+  if (int rc = allow_compact_count_dev(s.unreached, n, s.compact, &d_total, st)) return rc;
+  uint32_t count = 0;
+  PANN_HIP(hipMemcpyAsync(&count, d_total, 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  rs->reached = reached; rs->unreached = count; rs->max_frontier = max_frontier; rs->levels = levels; rs->truncated = truncated;
+  rs->t_s = 0;
+  return PANN_OK;
+}
+
+// what leaves the scratch after the walk: the reached bitmap (the visited bitmap as it is: no bit at or past n was ever set) and
+// the ascending list of the rs.unreached ids; either may be null
+int reach_emit(pann_index* idx, const ReachScratch& s, const pann_reach_stats& rs, uint32_t* d_reached, uint32_t* d_ids, hipStream_t st) {
+  const uint64_t n = idx->ix.n;
+  if (d_reached) PANN_HIP(hipMemcpyAsync(d_reached, s.visited, (size_t)((n + 31) / 32) * 4, hipMemcpyDeviceToDevice, st));
+  if (d_ids && rs.unreached) return allow_compact_scatter_dev(s.unreached, n, s.compact, d_ids, (uint32_t)rs.unreached, st);
+  return PANN_OK;
+}
+
+int reach_overflow(const char* fn, const pann_reach_stats& rs, uint64_t cap) {
+  set_error(std::string(fn) + ": " + std::to_string(rs.unreached) + " unreached vertices, unreached_ids has room for " + std::to_string(cap));
+  return PANN_ERR_OVERFLOW;
+}
+
+}  // namespace
+
+int pann_graph_reach_dev(pann_index* idx, const uint32_t* d_starts, uint32_t nstarts, const uint32_t* d_consider,
+                         uint32_t max_rounds, uint32_t* d_level, uint32_t* d_reached, uint32_t* d_unreached_ids,
+                         uint64_t unreached_cap, pann_reach_stats* stats) {
+  const char* fn = "pann_graph_reach_dev";
+  if (int rc = reach_checks(idx, fn, d_starts, nstarts)) return rc;
+  if ((uintptr_t)d_starts % 4 != 0 || (uintptr_t)d_consider % 4 != 0 || (uintptr_t)d_level % 4 != 0 || (uintptr_t)d_reached % 4 != 0 ||
+      (uintptr_t)d_unreached_ids % 4 != 0) {
+    set_error(std::string(fn) + ": device pointers must be 4-byte aligned"); return PANN_ERR_BAD_ARG;
+  }
+  DeviceGuard g(idx->device);
+  hipStream_t st = idx->stream;
+  EventPair ev;
+  if (int rc = ev.start(st)) return rc;
+  ReachScratch s;
+  pann_reach_stats rs{};
+  if (int rc = reach_walk(idx, fn, d_starts, nstarts, d_consider, max_rounds, d_level, s, &rs, st)) return rc;
+  const bool overflow = d_unreached_ids && unreached_cap < rs.unreached;
+  if (int rc = reach_emit(idx, s, rs, d_reached, overflow ? nullptr : d_unreached_ids, st)) return rc;
+  if (int rc = ev.stop(st)) return rc;
+  PANN_HIP(hipStreamSynchronize(st));
+  if (int rc = ev.seconds(&rs.t_s)) return rc;
+  if (stats) *stats = rs;
+  return overflow ? reach_overflow(fn, rs, unreached_cap) : PANN_OK;
+}
+
+int pann_graph_reach(pann_index* idx, const uint32_t* starts, uint32_t nstarts, const uint32_t* consider,
+                     uint32_t max_rounds, uint32_t* level, uint32_t* reached, uint32_t* unreached_ids,
+                     uint64_t unreached_cap, pann_reach_stats* stats) {
+  const char* fn = "pann_graph_reach";
+  if (int rc = reach_checks(idx, fn, starts, nstarts)) return rc;
+  const uint64_t n = idx->ix.n, words = (n + 31) / 32;
+  for (uint32_t i = 0; i < nstarts; i++)
+    if (starts[i] >= n) { set_error(std::string(fn) + ": start " + std::to_string(starts[i]) + " out of range; nothing was written"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  // up: the starts and the bitmap; the unreached count decides what comes down, so the outputs travel in a trip of their own
+  // (as pann_index_create_subset) and the levels are walked in the handle's scratch
+  HostTrip up(idx);
+  const int i_starts = up.in.add(starts, (size_t)nstarts * 4), i_consider = up.in.add(consider, (size_t)words * 4);
+  if (int rc = up.begin()) return rc;
+  EventPair ev;
+  if (int rc = ev.start(up.st)) return rc;
+  uint32_t* d_level = nullptr;
+  if (level) { if (int rc = idx->ws4.ensure((size_t)n * 4)) return rc; d_level = idx->ws4.as<uint32_t>(); }
+  ReachScratch s;
+  pann_reach_stats rs{};
+  if (int rc = reach_walk(idx, fn, up.din<uint32_t>(i_starts), nstarts, up.din<uint32_t>(i_consider), max_rounds, d_level, s, &rs, up.st)) return rc;
+  const bool overflow = unreached_ids && unreached_cap < rs.unreached;
+  HostTrip down(idx);       // no inputs; the small pieces first
+  const int o_reached = down.out.add(reached, (size_t)words * 4);
+  const int o_ids = down.out.add(overflow ? nullptr : unreached_ids, (size_t)rs.unreached * 4);
+  const int o_level = down.out.add(level, (size_t)n * 4);
+  if (int rc = down.begin()) return rc;
+  if (int rc = reach_emit(idx, s, rs, down.dout<uint32_t>(o_reached), down.dout<uint32_t>(o_ids), down.st)) return rc;
+  if (level) PANN_HIP(hipMemcpyAsync(down.dout<uint32_t>(o_level), d_level, (size_t)n * 4, hipMemcpyDeviceToDevice, down.st));
+  if (int rc = ev.stop(down.st)) return rc;
+  if (int rc = down.finish()) return rc;
+  if (int rc = ev.seconds(&rs.t_s)) return rc;
+  if (stats) *stats = rs;
+  return overflow ? reach_overflow(fn, rs, unreached_cap) : PANN_OK;
+}
+
+static int degrees_checks(const pann_index* idx, const char* fn, const uint32_t* out_deg, const uint32_t* in_deg) {
+  if (int rc = check_idx(idx, fn)) return rc;
+  if (!out_deg && !in_deg) { set_error(std::string(fn) + ": both outputs are null"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+int pann_graph_degrees_dev(pann_index* idx, uint32_t* d_out_deg, uint32_t* d_in_deg, void* stream) {
+  const char* fn = "pann_graph_degrees_dev";
+  if (int rc = degrees_checks(idx, fn, d_out_deg, d_in_deg)) return rc;
+  if ((uintptr_t)d_out_deg % 4 != 0 || (uintptr_t)d_in_deg % 4 != 0) { set_error(std::string(fn) + ": device pointers must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  return graph_degrees_dev(idx->ix, d_out_deg, d_in_deg, (hipStream_t)stream);
+}
+
+int pann_graph_degrees(pann_index* idx, uint32_t* out_deg, uint32_t* in_deg) {
+  if (int rc = degrees_checks(idx, "pann_graph_degrees", out_deg, in_deg)) return rc;
+  DeviceGuard g(idx->device);
+  HostTrip t(idx);
+  const size_t bytes = (size_t)idx->ix.n * 4;
+  const int o_out = t.out.add(out_deg, bytes), o_in = t.out.add(in_deg, bytes);
+  if (int rc = t.begin()) return rc;
+  if (int rc = graph_degrees_dev(idx->ix, t.dout<uint32_t>(o_out), t.dout<uint32_t>(o_in), t.st)) return rc;
+  return t.finish();
+}
+
 int pann_quantize_rows_dev(const pann_quant_params* p, const float* d_rows, uint64_t n, uint64_t stride_bytes,
                            int normalize_first, void* d_out, uint64_t out_stride_bytes, void* stream) {
   if (int rc = check_quant_params(p, "pann_quantize_rows_dev")) return rc;

@@ -234,6 +234,23 @@ int subset_gather_rows_dev(const void* d_src, void* d_dst, uint32_t row_bytes, c
 int subset_renumber_graph_dev(const uint32_t* d_src_graph, uint32_t* d_dst_graph, uint32_t gstride, const uint32_t* d_new_to_old,
                               const uint32_t* d_old_to_new, uint64_t n, uint64_t m, hipStream_t st);
 
+// graph_reach.hip: the kernels of pann_graph_reach* / pann_graph_degrees* (DESIGN.md "Graph reachability").  Only ix.graph,
+// ix.gstride and ix.n are read.  d_visited: ceil(n / 32) words, zeroed by the caller; d_queue: n words; a counter is one word.
+constexpr uint32_t REACH_GROUP = 8;      // rounds enqueued back to back between two read-backs of the frontier lengths
+// every start below n that is not yet in d_visited enters it and d_queue (tail *d_qlen); a start >= n raises *d_flag instead
+int reach_seed_dev(const uint32_t* d_starts, uint32_t nstarts, uint64_t n, uint32_t* d_visited, uint32_t* d_queue, uint32_t* d_qlen,
+                   uint32_t* d_flag, hipStream_t st);
+// d_level[d_queue[i]] = 0, i < *d_qlen: the level of the seeds, once the flag has come back clear
+int reach_level0_dev(const uint32_t* d_queue, const uint32_t* d_qlen, uint64_t n, uint32_t* d_level, hipStream_t st);
+// one round: every undiscovered neighbour of d_queue_in[0 .. *d_len_in) enters d_visited and d_queue_out (tail *d_len_out,
+// zeroed by the caller) exactly once and, with d_level != null, gets level `next_level`.  *d_len_in == 0: a no-op.
+int reach_expand_dev(const DeviceIndex& ix, const uint32_t* d_queue_in, const uint32_t* d_len_in, uint32_t* d_queue_out,
+                     uint32_t* d_len_out, uint32_t* d_visited, uint32_t* d_level, uint32_t next_level, hipStream_t st);
+// d_unreached[w] = ~d_visited[w] & d_consider[w] (null: all ones), bits at positions >= n cleared
+int reach_finish_dev(const uint32_t* d_visited, const uint32_t* d_consider, uint64_t n, uint32_t* d_unreached, hipStream_t st);
+// d_out_deg / d_in_deg (n words each, either may be null); d_in_deg is zero-filled here, on st
+int graph_degrees_dev(const DeviceIndex& ix, uint32_t* d_out_deg, uint32_t* d_in_deg, hipStream_t st);
+
 // leaf_knn.hip: lane-owns-row all-pairs top-m for one-byte element types (HCNNG leaves)
 bool dense_gt_eligible(const DeviceIndex& ix, uint32_t m, bool b_ids, bool segmented, int exclude_same);
 uint32_t dense_gt_slots(const DeviceIndex& ix, uint32_t m);

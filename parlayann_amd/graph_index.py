@@ -86,6 +86,19 @@ class GraphIndex:
         if self.q_index is not None:
             self.q_index.set_labels(labels, first_row)
 
+    # ---- graph reachability (DESIGN.md "Graph reachability"): from vertex 0, the start of every search of this class ----
+    def reachability(self, consider=None, max_rounds=0, levels=True, ids=True):
+        """DeviceIndex.reachability from vertex 0 on the searched graph (a quantised copy holds the same rows)."""
+        return self.index.reachability((0,), consider, max_rounds, levels, ids)
+
+    def reconnect(self, R, L, alpha, consider=None, max_rounds=3):
+        """DeviceIndex.reconnect from vertex 0.  It rewrites graph rows, so an index with a quantised copy refuses: the copy's
+        graph would go stale, and rebuilding the copy (quantized(copy_graph=True)) is the caller's decision."""
+        if self.q_index is not None:
+            raise ValueError("reconnect would leave the graph of the quantised copy stale: reconnect the DeviceIndex and make "
+                             "the copy again with quantized(copy_graph=True)")
+        return self.index.reconnect(R, L, alpha, 0, consider, max_rounds)
+
     # QueryParams(knn, beam, 1.35, visit_limit, min(maxDeg, 3*visit_limit))   (:198,:222,:242)
     def _qp(self, knn, beam_width, visit_limit):
         return dict(k=knn, beam=beam_width, cut=1.35, limit=visit_limit,

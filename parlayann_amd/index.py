@@ -10,7 +10,7 @@ import numpy as np
 from . import _capi
 from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I4, PANN_I8, PANN_L2, PANN_MIPS, PANN_PRED_ANY, PANN_PRED_MATCH, PANN_PRED_RANGE,
                     PANN_QUANT_EUCLID_U4, PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats,
-                    DeleteStats, QuantParams, QueryParams, RerankOut, SearchOut, check)
+                    DeleteStats, QuantParams, QueryParams, ReachStats, RerankOut, SearchOut, check)
 from .bf16 import bfloat16
 
 _DT = {np.dtype(np.uint8): PANN_U8, np.dtype(np.int8): PANN_I8, np.dtype(np.float32): PANN_F32,
@@ -787,6 +787,75 @@ class DeviceIndex:
 
     def vamana_sort_neighbors(self):
         check(self._lib.pann_vamana_sort_neighbors(self._h))
+
+    # ---- graph reachability: BFS levels, degrees, reconnect (DESIGN.md "Graph reachability") ----
+    def _consider(self, consider):
+        if consider is None:
+            return None
+        a = pack_allow(consider, self.n)
+        if a.ndim != 1:
+            raise ValueError("consider is one bitmap: boolean (n,) or one packed row")
+        return a
+
+    def reachability(self, starts=(0,), consider=None, max_rounds=0, levels=True, ids=True):
+        """pann_graph_reach: which vertices can a search from `starts` reach at all?  A breadth-first walk over the graph rows
+        on the device; points are not read, so it works on every element type.
+        consider: what allow= accepts elsewhere (boolean (n,) or one packed row, allow_bitmap): it does not steer the walk, it
+        selects which vertices count and are listed as unreached -- typically the live set, allow_bitmap(n, deleted_ids=D).
+        max_rounds: 0 = until the frontier is empty; r = at most r rounds (levels 0 .. r).
+        Returns a dict: level uint32 (n,) with 0xFFFFFFFF for no path (None with levels=False); reached, the packed bitmap (it
+        goes as it is into subset(allow=) and every masked search); unreached_ids uint32, ascending (None with ids=False);
+        reached_count, unreached_count, levels, max_frontier, truncated, seconds (on the device).
+        ids=True makes room for n ids and calls ONCE (the list that comes back is cut to unreached_count); only the ids found
+        cross the bus."""
+        n = self.n
+        s = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
+        c = self._consider(consider)
+        level = np.empty(n, np.uint32) if levels else None
+        reached = np.empty((n + 31) // 32, np.uint32)
+        uid = np.empty(n, np.uint32) if ids else None
+        st = ReachStats()
+        check(self._lib.pann_graph_reach(self._h, _ptr(s), len(s), _ptr(c), int(max_rounds), _ptr(level), _ptr(reached), _ptr(uid), n,
+                                         C.byref(st)))
+        return {"level": level, "reached": reached, "unreached_ids": uid[:st.unreached].copy() if ids else None,
+                "reached_count": int(st.reached), "unreached_count": int(st.unreached), "levels": int(st.levels),
+                "max_frontier": int(st.max_frontier), "truncated": bool(st.truncated), "seconds": float(st.t_s)}
+
+    def degrees(self):
+        """pann_graph_degrees -> (out_deg, in_deg), uint32 (n,) each: the neighbour slots of a row that hold an id, and the
+        (row, slot) pairs that name a vertex (a repeated neighbour counts every time, a self loop counts)"""
+        out_deg, in_deg = np.empty(self.n, np.uint32), np.empty(self.n, np.uint32)
+        check(self._lib.pann_graph_degrees(self._h, _ptr(out_deg), _ptr(in_deg)))
+        return out_deg, in_deg
+
+    def reconnect(self, R, L, alpha, start=0, consider=None, max_rounds=3):
+        """Re-insert what a search from `start` cannot reach.  A composition, nothing more.  One round:
+          U = reachability((start,), consider)["unreached_ids"]; stop if U is empty;
+          vamana_insert_batch(U[i : i + b], R, L, alpha, start) over U in ascending order, b = max(1, n // 50) -- the batch bound
+          of the reference's batch_insert (max_fraction .02).  A vertex that has a row is inserted as a second build pass inserts
+          it: its row is overwritten.
+        It stops after max_rounds rounds, or as soon as a round does not strictly reduce |U| (re-insertion stalls on some graphs).
+        consider: as in reachability, typically the live set -- a deleted id must not be considered, it would be inserted again.
+        Raises ValueError if `start` is not in consider.
+        Returns {"unreached": [|U| before round 1, after round 1, ...], "remaining_ids": the last U}.  The filter-code state of
+        the index is whatever vamana_insert_batch leaves."""
+        n, start = self.n, int(start)
+        c = self._consider(consider)
+        if not 0 <= start < n or (c is not None and not (int(c[start >> 5]) >> (start & 31)) & 1):
+            raise ValueError(f"start {start} is not a considered vertex")
+        b = max(1, n // 50)
+        U = self.reachability((start,), c, levels=False)["unreached_ids"]
+        counts = [len(U)]
+        for _ in range(int(max_rounds)):
+            if len(U) == 0:
+                break
+            for i in range(0, len(U), b):
+                self.vamana_insert_batch(U[i:i + b], R, L, alpha, start)
+            U = self.reachability((start,), c, levels=False)["unreached_ids"]
+            counts.append(len(U))
+            if counts[-1] >= counts[-2]:
+                break
+        return {"unreached": counts, "remaining_ids": U}
 
     # ---- distances / dense all-pairs ----
     def hcnng_build(self, num_clusters, cluster_size, mst_deg, seed=1):
