@@ -15,16 +15,11 @@
 // types one lane sums a whole row left to right in 16-byte chunks).
 #include <vector>
 
-#include "pann_device.h"
+#include "dense_tile.h"
 
 namespace pann {
 
-constexpr int DT_A = 64;        // A rows per workgroup
-constexpr int DT_AW = 16;       // A rows per wave
-constexpr int DT_B = 64;        // B rows per lane group (one per lane)
 constexpr int DT_RB = 2;        // VALU kernel: B rows per lane (tile = 128 rows); halves the LDS broadcasts per FMA
-constexpr int DT_SEG = 256;     // bytes of the dimension staged per step
-constexpr int DT_BSTRIDE = DT_SEG + 16;
 
 struct DenseArgs {
   const uint8_t* points; uint32_t pstride; uint32_t dbytes;
@@ -44,6 +39,20 @@ struct DenseArgs {
   const uint32_t* tile_a0;    // [grid.x] first A row (global index) of each tile
 };
 
+// this workgroup's tile: segmented (leaves, tile arrays) or the contiguous default; TB = B rows per tile
+__device__ __forceinline__ TileGeom dense_geom(const DenseArgs& A, uint32_t TB) {
+  const uint32_t seg = A.tile_seg ? A.tile_seg[blockIdx.x] : 0u;
+  const uint64_t a_hi = A.a_off ? A.a_off[seg + 1] : A.na;
+  const uint64_t b_lo = A.b_off ? A.b_off[seg] : 0ull, b_hi = A.b_off ? A.b_off[seg + 1] : A.nb;
+  const uint64_t a0 = A.tile_a0 ? (uint64_t)A.tile_a0[blockIdx.x] : (uint64_t)blockIdx.x * DT_A;
+  return tile_geom(a0, a_hi, b_lo, b_hi, piece_rows(b_hi - b_lo, A.nsplit, TB));
+}
+// 16 bytes at `off` of row r of the A tile -- a point id or an external vector; zeros beyond the tile and beyond the row
+__device__ __forceinline__ uint4 dense_a_load(const DenseArgs& A, const TileGeom& g, uint32_t r, uint32_t off) {
+  if (r >= g.na_tile) return make_uint4(0, 0, 0, 0);
+  const uint8_t* rp = A.a_ids ? A.points + (uint64_t)A.a_ids[g.a0 + r] * A.pstride : A.a_ext + (g.a0 + r) * A.a_stride;
+  return load16_unaligned(rp, off, A.a_ids ? A.pstride : A.dbytes);
+}
 
 // sorted insert of key x into list[0..mcap) (ascending, KEY_INF padded), dropping the last entry
 __device__ __forceinline__ void list_insert(uint64_t* list, uint32_t mcap, uint64_t x, int lane) {
@@ -65,6 +74,23 @@ __device__ __forceinline__ void list_insert(uint64_t* list, uint32_t mcap, uint6
     if (i < mcap) list[i] = nv[r];
   }
   wave_lds_sync();
+}
+// the survivors of a ballot (`mask`: lanes whose `key` beat tau, the m-th best of `list`), one at a time into that LDS list;
+// a key that the inserts before it have pushed out of reach is dropped
+__device__ __forceinline__ void list_insert_survivors(uint64_t* list, uint64_t tau, uint64_t mask, uint64_t key, uint32_t m, uint32_t mcap, int lane) {
+  while (mask) {
+    const int L = __ffsll((unsigned long long)mask) - 1;
+    const uint64_t x = readlane64(key, L);
+    mask &= mask - 1;
+    if (x < tau) { list_insert(list, mcap, x, lane); tau = list[m - 1]; }
+  }
+}
+// this block's partial lists -> partial[row][piece][0..m)
+__device__ __forceinline__ void emit_partial(const DenseArgs& A, uint64_t a0, uint32_t na_tile, const uint64_t* lists, int tid) {
+  for (uint32_t i = tid; i < na_tile * A.m; i += 256) {
+    const uint32_t ar = i / A.m, j = i % A.m;
+    A.partial[((a0 + ar) * A.nsplit + blockIdx.y) * A.m + j] = lists[(size_t)ar * A.mcap + j];
+  }
 }
 
 // ---- lane-parallel top-m for m <= 16 (the HCNNG leaf case, m = 10) ----
@@ -95,6 +121,38 @@ __device__ __forceinline__ uint32_t tm_lower_bound16(const uint64_t* list, uint6
   lo += (list[lo] < x) ? 1 : 0;      // lo <= 15 here
   return lo;
 }
+// After the last tile: merge the four quarter lists of every row by rank -- position in the own list + entries of the other
+// three that are smaller (keys are unique: a column belongs to one quarter) -- and write this piece's partial list of the row.
+// Lw: this wave's [16 rows][4][16] keys of LDS that nobody reads any more.
+// (The per-tile walk over the marked entries stays written out in both kernels: as a function shared by them it changed the
+//  SGPR spill count of every dense_topk_kernel instance, 94 -> 96.)
+__device__ __forceinline__ void tm_merge_write(const DenseArgs& A, const uint64_t (&TL)[16], uint64_t* Lw, uint64_t a0, uint32_t na_tile, int wave, int lane) {
+  const int row = lane & 15, qd = lane >> 4;
+#pragma unroll
+  for (int i = 0; i < 16; i++) Lw[(row * 4 + qd) * 16 + i] = TL[i];
+  const uint32_t ar = wave * DT_AW + row;
+  uint64_t* out = A.partial + ((a0 + ar) * A.nsplit + blockIdx.y) * A.m;
+  __syncthreads();                                      // lists visible
+  const int lead = 16 - (int)A.m;                       // leading key-0 entries of every list
+  if (ar < na_tile && qd == 0) {                        // slots beyond the number of real keys stay empty
+    int real = 0;
+#pragma unroll
+    for (int o = 0; o < 4; o++) real += (int)tm_lower_bound16(Lw + (row * 4 + o) * 16, KEY_INF) - lead;
+    for (int j = real; j < (int)A.m; j++) out[j] = KEY_INF;
+  }
+  if (ar < na_tile) {
+#pragma unroll
+    for (int e = 0; e < 16; e++) {
+      const uint64_t x = TL[e];
+      if (e >= lead && x != KEY_INF) {
+        int rank = e - lead;
+#pragma unroll
+        for (int o = 1; o < 4; o++) rank += (int)tm_lower_bound16(Lw + (row * 4 + ((qd + o) & 3)) * 16, x) - lead;
+        if (rank < (int)A.m) out[rank] = x;
+      }
+    }
+  }
+}
 
 template <int DT, int METRIC>
 __global__ void __launch_bounds__(256) dense_topk_kernel(DenseArgs A) {
@@ -106,17 +164,8 @@ __global__ void __launch_bounds__(256) dense_topk_kernel(DenseArgs A) {
   uint32_t* Aid = Bid + TB;                             // [64] ids of the A tile (SENTINEL: none)
   uint64_t* lists = reinterpret_cast<uint64_t*>(Aid + DT_A);            // [64][mcap]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t seg = A.tile_seg ? A.tile_seg[blockIdx.x] : 0u;
-  const uint64_t a_lo = A.a_off ? A.a_off[seg] : 0ull, a_hi = A.a_off ? A.a_off[seg + 1] : A.na;
-  const uint64_t b_lo = A.b_off ? A.b_off[seg] : 0ull, b_hi = A.b_off ? A.b_off[seg + 1] : A.nb;
-  const uint64_t a0 = A.tile_a0 ? (uint64_t)A.tile_a0[blockIdx.x] : (uint64_t)blockIdx.x * DT_A;
-  const uint32_t na_tile = (uint32_t)min((uint64_t)DT_A, a_hi - a0);
-  (void)a_lo;
-  // this block's share of the B range
-  const uint64_t nb_seg = b_hi - b_lo;
-  const uint64_t per = ((nb_seg + A.nsplit - 1) / A.nsplit + TB - 1) / TB * TB;
-  const uint64_t bs = b_lo + min(nb_seg, (uint64_t)blockIdx.y * per);
-  const uint64_t be = b_lo + min(nb_seg, (uint64_t)(blockIdx.y + 1) * per);
+  const TileGeom g = dense_geom(A, TB);
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
 
   for (uint32_t i = tid; i < DT_A * A.mcap; i += 256) lists[i] = KEY_INF;
   if (tid < DT_A) Aid[tid] = (tid < (int)na_tile && A.a_ids) ? A.a_ids[a0 + tid] : SENTINEL;
@@ -134,17 +183,7 @@ __global__ void __launch_bounds__(256) dense_topk_kernel(DenseArgs A) {
     for (int r = r0; r < rows_total; r += 16) {
       uint4 v = make_uint4(0, 0, 0, 0);
       const uint32_t off = sg * DT_SEG + c * 16;
-      if (r < (int)nrows) {
-        const uint8_t* rp = rowptr(r);
-        const uint32_t valid = rowvalid();
-        if ((reinterpret_cast<uintptr_t>(rp) & 15) == 0) v = load16_guarded(rp, off, valid);
-        else {
-          uint8_t tmp[16];
-#pragma unroll
-          for (int i = 0; i < 16; i++) tmp[i] = (off + i < valid) ? rp[off + i] : (uint8_t)0;
-          __builtin_memcpy(&v, tmp, 16);
-        }
-      }
+      if (r < (int)nrows) v = load16_unaligned(rowptr(r), off, rowvalid());
       *reinterpret_cast<uint4*>(dst + (size_t)r * dstride + c * 16) = v;
     }
   };
@@ -253,59 +292,17 @@ __global__ void __launch_bounds__(256) dense_topk_kernel(DenseArgs A) {
         const uint64_t key = make_key(dist, bid);
         bool ok = (brow < nb_tile);
         if (A.exclude_same_id) ok = ok && (bid != Aid[ar]);
-        uint64_t tau = list[A.m - 1];
-        uint64_t mask = __ballot(ok && key < tau);
-        while (mask) {
-          const int L = __ffsll((unsigned long long)mask) - 1;
-          const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, L);
-          const uint32_t khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), L);
-          const uint64_t x = ((uint64_t)khi << 32) | klo;
-          mask &= mask - 1;
-          if (x < tau) {
-            list_insert(list, A.mcap, x, lane);
-            tau = list[A.m - 1];
-          }
-        }
+        const uint64_t tau = list[A.m - 1];
+        list_insert_survivors(list, tau, __ballot(ok && key < tau), key, A.m, A.mcap, lane);
       }
     }
   }
   __syncthreads();
-  if (lane_lists) {
-    // merge the four quarter lists of every row by rank: position in the own list + entries of the other three
-    // that are smaller (keys are unique: a column belongs to one quarter)
-    uint64_t* Lw = reinterpret_cast<uint64_t*>(Bt) + (size_t)wave * (DT_AW * 4 * 16);       // [16 rows][4][16]
-    const int row = lane & 15, qd = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < 16; i++) Lw[(row * 4 + qd) * 16 + i] = TL[i];
-    const uint32_t ar = wave * DT_AW + row;
-    uint64_t* out = A.partial + ((a0 + ar) * A.nsplit + blockIdx.y) * A.m;
-    __syncthreads();                                      // lists visible
-    const int lead = 16 - (int)A.m;                       // leading key-0 entries of every list
-    if (ar < na_tile && qd == 0) {                        // slots beyond the number of real keys stay empty
-      int real = 0;
-#pragma unroll
-      for (int o = 0; o < 4; o++) real += (int)tm_lower_bound16(Lw + (row * 4 + o) * 16, KEY_INF) - lead;
-      for (int j = real; j < (int)A.m; j++) out[j] = KEY_INF;
-    }
-    if (ar < na_tile) {
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const uint64_t x = TL[e];
-        if (e >= lead && x != KEY_INF) {
-          int rank = e - lead;
-#pragma unroll
-          for (int o = 1; o < 4; o++) rank += (int)tm_lower_bound16(Lw + (row * 4 + ((qd + o) & 3)) * 16, x) - lead;
-          if (rank < (int)A.m) out[rank] = x;
-        }
-      }
-    }
+  if (lane_lists) {                                       // the B tile holds the quarter lists for the merge
+    tm_merge_write(A, TL, reinterpret_cast<uint64_t*>(Bt) + (size_t)wave * (DT_AW * 4 * 16), a0, na_tile, wave, lane);
     return;
   }
-  // ---- emit this block's partial lists ----
-  for (uint32_t i = tid; i < na_tile * A.m; i += 256) {
-    const uint32_t ar = i / A.m, j = i % A.m;
-    A.partial[((a0 + ar) * A.nsplit + blockIdx.y) * A.m + j] = lists[(size_t)ar * A.mcap + j];
-  }
+  emit_partial(A, a0, na_tile, lists, tid);
 }
 
 // ---- fp16 variant on the matrix cores (north_star: MFMA only for the dense fp16 contraction) ----
@@ -317,31 +314,19 @@ __global__ void __launch_bounds__(256) dense_topk_kernel(DenseArgs A) {
 // product and partial sum is exact, so the result is bit-identical to the VALU path; on real-valued
 // data the norm form differs from sum((a-b)^2) by cancellation error (bound: DESIGN.md "Float summation order") and is
 // clamped at 0: its three sums round in different orders, so equal rows would come out a few ulp of |a|^2 + |b|^2 below zero.
-typedef _Float16 mf_half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 mf_bf8 __attribute__((ext_vector_type(8)));
-typedef float mf_float4 __attribute__((ext_vector_type(4)));
-
+// (Operand types, mfma_step, sumsq16 and the LDS-only barrier: dense_tile.h.)
+// The wave's 16 x 64 block of dot products over one staged segment: acc[t] += a(row wave*16 + (lane & 15)) . b(row t*16 + (lane & 15))
 template <bool BF>
-__device__ __forceinline__ float sumsq16(uint4 v) {
-  float ss = 0.f;
-  if constexpr (BF) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+__device__ __forceinline__ void mf_segment(mf_float4 (&acc)[4], const uint8_t* At, const uint8_t* Bt, uint32_t ksteps, int wave, int lane) {
+  for (uint32_t ks = 0; ks < ksteps; ks++) {
+    const uint32_t koff = ks * 64 + (lane >> 4) * 16;                              // k = 8*(lane>>4) + j, 32 halves per MFMA
+    uint4 braw[4];
 #pragma unroll
-    for (int i = 0; i < 4; i++) { const float lo = bf16_lo(w[i]), hi = bf16_hi(w[i]); ss = fmaf(lo, lo, ss); ss = fmaf(hi, hi, ss); }
-  } else {
-    mf_half8 h; __builtin_memcpy(&h, &v, 16);
-#pragma unroll
-    for (int i = 0; i < 8; i++) { const float f = (float)h[i]; ss = fmaf(f, f, ss); }
+    for (int t = 0; t < 4; t++) braw[t] = *reinterpret_cast<const uint4*>(Bt + (size_t)(t * 16 + (lane & 15)) * DT_BSTRIDE + koff);
+    mfma_step<BF>(*reinterpret_cast<const uint4*>(At + (size_t)(wave * DT_AW + (lane & 15)) * DT_BSTRIDE + koff), braw, acc);
   }
-  return ss;
 }
 
-// workgroup barrier that orders LDS traffic only: __syncthreads() also drains the vector memory counter, which would wait
-// for the tile requested two iterations ahead at every tile (measured: 2.6 us per tile, the loaded HBM latency)
-__device__ __forceinline__ void gt_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// BF == false: IEEE binary16 operands (v_mfma_f32_16x16x32_f16); BF == true: bfloat16 (v_mfma_f32_16x16x32_bf16).
-// Both accumulate in f32; products of two-byte values are exact in f32, so integer-valued data gives exact sums.
 template <int METRIC, bool BF>
 __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
   extern __shared__ __align__(16) uint8_t smem[];
@@ -353,15 +338,8 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
   float* Bn = An + DT_A;                                // [64] |b|^2
   uint64_t* lists = reinterpret_cast<uint64_t*>(Bn + DT_B);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint32_t seg = A.tile_seg ? A.tile_seg[blockIdx.x] : 0u;
-  const uint64_t a_hi = A.a_off ? A.a_off[seg + 1] : A.na;
-  const uint64_t b_lo = A.b_off ? A.b_off[seg] : 0ull, b_hi = A.b_off ? A.b_off[seg + 1] : A.nb;
-  const uint64_t a0 = A.tile_a0 ? (uint64_t)A.tile_a0[blockIdx.x] : (uint64_t)blockIdx.x * DT_A;
-  const uint32_t na_tile = (uint32_t)min((uint64_t)DT_A, a_hi - a0);
-  const uint64_t nb_seg = b_hi - b_lo;
-  const uint64_t per = ((nb_seg + A.nsplit - 1) / A.nsplit + DT_B - 1) / DT_B * DT_B;
-  const uint64_t bs = b_lo + min(nb_seg, (uint64_t)blockIdx.y * per);
-  const uint64_t be = b_lo + min(nb_seg, (uint64_t)(blockIdx.y + 1) * per);
+  const TileGeom g = dense_geom(A, DT_B);
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
 
   for (uint32_t i = tid; i < DT_A * A.mcap; i += 256) lists[i] = KEY_INF;
   if (tid < DT_A) { Aid[tid] = (tid < (int)na_tile && A.a_ids) ? A.a_ids[a0 + tid] : SENTINEL; An[tid] = 0.f; }
@@ -382,28 +360,9 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
     for (int r = r0; r < 64; r += 16) {
       uint4 v = make_uint4(0, 0, 0, 0);
       const uint32_t off = sg * DT_SEG + c * 16;
-      if (r < (int)nrows) {
-        const uint8_t* rp = rowptr(r);
-        if ((reinterpret_cast<uintptr_t>(rp) & 15) == 0) v = load16_guarded(rp, off, valid);
-        else {
-          uint8_t tmp[16];
-#pragma unroll
-          for (int i = 0; i < 16; i++) tmp[i] = (off + i < valid) ? rp[off + i] : (uint8_t)0;
-          __builtin_memcpy(&v, tmp, 16);
-        }
-      }
+      if (r < (int)nrows) v = load16_unaligned(rowptr(r), off, valid);
       *reinterpret_cast<uint4*>(dst + (size_t)r * DT_BSTRIDE + c * 16) = v;
-      float ss = 0.f;
-      if constexpr (BF) {
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int i = 0; i < 4; i++) { const float lo = bf16_lo(w[i]), hi = bf16_hi(w[i]); ss = fmaf(lo, lo, ss); ss = fmaf(hi, hi, ss); }
-      } else {
-        mf_half8 h; __builtin_memcpy(&h, &v, 16);
-#pragma unroll
-        for (int i = 0; i < 8; i++) { const float f = (float)h[i]; ss = fmaf(f, f, ss); }
-      }
-      ss = group_sum<16>(ss);                       // the 16 threads of a row are 16 consecutive lanes
+      const float ss = group_sum<16>(sumsq16<BF>(v));     // the 16 threads of a row are 16 consecutive lanes
       if (c == 0) norms[r] += ss;
     }
   };
@@ -450,7 +409,7 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
         if (x < tau) { tm_chain_insert(TL, x); tau = TL[15]; }
       }
     }
-    return;                                               // (K aliasing Bt: the next tile's barrier protects it)
+    return;                                              // (K aliasing Bt: the next tile's barrier protects it)
   }
   // m > 16 (ground truth): the 16 distances of a lane (4 rows x 4 columns) are tested against register copies of their rows'
   // m-th best FIRST -- after the lists have warmed up nearly every tile ends here with one ballot; only a tile with a
@@ -486,9 +445,7 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
           uint64_t mask = __ballot(pass[r][t]);
           while (mask) {
             const int L = __ffsll((unsigned long long)mask) - 1;
-            const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key[r][t], L);
-            const uint32_t khi = __builtin_amdgcn_readlane((uint32_t)(key[r][t] >> 32), L);
-            const uint64_t x = ((uint64_t)khi << 32) | klo;
+            const uint64_t x = readlane64(key[r][t], L);
             mask &= mask - 1;
             uint64_t* list = lists + (size_t)(wave * DT_AW + (L >> 4) * 4 + r) * A.mcap;
             if (x < list[A.m - 1]) list_insert(list, A.mcap, x, lane);
@@ -540,35 +497,17 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
     }
     for (uint64_t bt = bs; bt < be; bt += DT_B) {
       const uint32_t nb_tile = (uint32_t)min((uint64_t)DT_B, be - bt);
-      gt_lds_barrier();                                                 // the previous tile's multiply has read Bt
+      lds_barrier();                                                    // the previous tile's multiply has read Bt
       store_rows(id_cur, bt);
       load_rows(id_nxt);                                                // tile bt + 64 (its ids arrived a tile ago)
 #pragma unroll
       for (int k = 0; k < 4; k++) id_cur[k] = id_nxt[k];
       load_ids(bt + 2 * DT_B, id_nxt);                                  // ids of tile bt + 128
-      gt_lds_barrier();
+      lds_barrier();
       mf_float4 acc[4];
 #pragma unroll
       for (int t = 0; t < 4; t++) acc[t] = mf_float4{0.f, 0.f, 0.f, 0.f};
-      const uint32_t ksteps = A.pstride / 64;
-      for (uint32_t ks = 0; ks < ksteps; ks++) {
-        const uint32_t koff = ks * 64 + (lane >> 4) * 16;
-        if constexpr (BF) {
-          const mf_bf8 af = *reinterpret_cast<const mf_bf8*>(At + (size_t)(wave * DT_AW + (lane & 15)) * DT_BSTRIDE + koff);
-#pragma unroll
-          for (int t = 0; t < 4; t++) {
-            const mf_bf8 bf = *reinterpret_cast<const mf_bf8*>(Bt + (size_t)(t * 16 + (lane & 15)) * DT_BSTRIDE + koff);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[t], 0, 0, 0);
-          }
-        } else {
-          const mf_half8 af = *reinterpret_cast<const mf_half8*>(At + (size_t)(wave * DT_AW + (lane & 15)) * DT_BSTRIDE + koff);
-#pragma unroll
-          for (int t = 0; t < 4; t++) {
-            const mf_half8 bf = *reinterpret_cast<const mf_half8*>(Bt + (size_t)(t * 16 + (lane & 15)) * DT_BSTRIDE + koff);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc[t], 0, 0, 0);
-          }
-        }
-      }
+      mf_segment<BF>(acc, At, Bt, A.pstride / 64, wave, lane);
       epilogue(acc, nb_tile, Ks, false);
     }
   } else
@@ -590,62 +529,16 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
       stage_rows(Bt, Bn, sg, b_rowptr, A.pstride, nb_tile);
       stage_rows(At, An, sg, a_rowptr, a_valid, na_tile);
       __syncthreads();
-      const uint32_t ksteps = min((uint32_t)DT_SEG, A.pstride - sg * DT_SEG) / 64;   // 32 halves per MFMA
-      for (uint32_t ks = 0; ks < ksteps; ks++) {
-        const uint32_t koff = ks * 64 + (lane >> 4) * 16;                              // k = 8*(lane>>4) + j
-        if constexpr (BF) {
-          const mf_bf8 af = *reinterpret_cast<const mf_bf8*>(At + (size_t)(wave * DT_AW + (lane & 15)) * DT_BSTRIDE + koff);
-#pragma unroll
-          for (int t = 0; t < 4; t++) {
-            const mf_bf8 bf = *reinterpret_cast<const mf_bf8*>(Bt + (size_t)(t * 16 + (lane & 15)) * DT_BSTRIDE + koff);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[t], 0, 0, 0);
-          }
-        } else {
-          const mf_half8 af = *reinterpret_cast<const mf_half8*>(At + (size_t)(wave * DT_AW + (lane & 15)) * DT_BSTRIDE + koff);
-#pragma unroll
-          for (int t = 0; t < 4; t++) {
-            const mf_half8 bf = *reinterpret_cast<const mf_half8*>(Bt + (size_t)(t * 16 + (lane & 15)) * DT_BSTRIDE + koff);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc[t], 0, 0, 0);
-          }
-        }
-      }
+      mf_segment<BF>(acc, At, Bt, min((uint32_t)DT_SEG, A.pstride - sg * DT_SEG) / 64, wave, lane);
     }
     epilogue(acc, nb_tile, Kw, true);
   }
   __syncthreads();
   if (lane_lists) {   // rank merge of the four quarter lists of every row (as in dense_topk_kernel); At + Bt hold the lists
-    uint64_t* Lw = reinterpret_cast<uint64_t*>(At) + (size_t)wave * (DT_AW * 4 * 16);
-    const int row = lane & 15, qd = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < 16; i++) Lw[(row * 4 + qd) * 16 + i] = TL[i];
-    const uint32_t ar = wave * DT_AW + row;
-    uint64_t* out = A.partial + ((a0 + ar) * A.nsplit + blockIdx.y) * A.m;
-    __syncthreads();
-    const int lead = 16 - (int)A.m;
-    if (ar < na_tile && qd == 0) {
-      int real = 0;
-#pragma unroll
-      for (int o = 0; o < 4; o++) real += (int)tm_lower_bound16(Lw + (row * 4 + o) * 16, KEY_INF) - lead;
-      for (int j = real; j < (int)A.m; j++) out[j] = KEY_INF;
-    }
-    if (ar < na_tile) {
-#pragma unroll
-      for (int e = 0; e < 16; e++) {
-        const uint64_t x = TL[e];
-        if (e >= lead && x != KEY_INF) {
-          int rank = e - lead;
-#pragma unroll
-          for (int o = 1; o < 4; o++) rank += (int)tm_lower_bound16(Lw + (row * 4 + ((qd + o) & 3)) * 16, x) - lead;
-          if (rank < (int)A.m) out[rank] = x;
-        }
-      }
-    }
+    tm_merge_write(A, TL, reinterpret_cast<uint64_t*>(At) + (size_t)wave * (DT_AW * 4 * 16), a0, na_tile, wave, lane);
     return;
   }
-  for (uint32_t i = tid; i < na_tile * A.m; i += 256) {
-    const uint32_t ar = i / A.m, j = i % A.m;
-    A.partial[((a0 + ar) * A.nsplit + blockIdx.y) * A.m + j] = lists[(size_t)ar * A.mcap + j];
-  }
+  emit_partial(A, a0, na_tile, lists, tid);
 }
 
 // ---- ground-truth variant (m in 17..128, two-byte floats, rows of at most 256 bytes, B = all points) ----
@@ -671,6 +564,20 @@ __global__ void __launch_bounds__(256) dense_topk_mfma_f16_kernel(DenseArgs A) {
 constexpr int GT_BSTRIDE = DT_SEG;
 constexpr int GT_BT_BYTES = DT_B * GT_BSTRIDE;
 __device__ __forceinline__ uint32_t gt_swz(uint32_t row, uint32_t off) { return row * GT_BSTRIDE + (off ^ ((row & 15u) << 4)); }
+// One staged tile, registers -> LDS buffer Bt: thread (r0 = tid >> 4, c = tid & 15) holds chunk c of rows r0 + 16 k in v0..v3
+// (cvalid: the chunk lies inside the row; the others were zeroed once), threads 0..63 the norm bits of row bt + tid.
+// Bm[row] = (norm bits, id bits); a row at or beyond `be` is labelled SENTINEL.
+__device__ __forceinline__ void gt_store_tile(uint8_t* Bt, float2* Bm, bool cvalid, const uint4& v0, const uint4& v1, const uint4& v2,
+                                              const uint4& v3, float normbits, uint64_t bt, uint64_t be, int tid) {
+  if (cvalid) {
+    uint8_t* dst = Bt + gt_swz((uint32_t)(tid >> 4), (uint32_t)(tid & 15) * 16u);      // rows r0 + 16 k share r0's swizzle
+    *reinterpret_cast<uint4*>(dst) = v0;
+    *reinterpret_cast<uint4*>(dst + 16 * GT_BSTRIDE) = v1;
+    *reinterpret_cast<uint4*>(dst + 32 * GT_BSTRIDE) = v2;
+    *reinterpret_cast<uint4*>(dst + 48 * GT_BSTRIDE) = v3;
+  }
+  if (tid < DT_B) Bm[tid] = make_float2(normbits, __uint_as_float(bt + tid < be ? (uint32_t)(bt + tid) : SENTINEL));
+}
 #ifndef PANN_GT_TAU_PERIOD
 #define PANN_GT_TAU_PERIOD 16
 #endif
@@ -1006,33 +913,20 @@ __global__ void __launch_bounds__(256, PANN_GT_WGS) dense_gt_mfma_kernel(DenseAr
   float* An = reinterpret_cast<float*>(Bm + 2 * DT_B);                    // [64]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4;
   uint64_t* Qw = reinterpret_cast<uint64_t*>(An + DT_A) + (size_t)wave * DT_AW * GT_QCAP;   // this wave's survivor queues [16][GT_QCAP]
-  const uint64_t a0 = (uint64_t)blockIdx.x * DT_A;
-  const uint32_t na_tile = (uint32_t)min((uint64_t)DT_A, A.na - a0);
-  const uint64_t per = ((A.nb + A.nsplit - 1) / A.nsplit + DT_B - 1) / DT_B * DT_B;
-  const uint64_t bs = min(A.nb, (uint64_t)blockIdx.y * per), be = min(A.nb, (uint64_t)(blockIdx.y + 1) * per);
+  const TileGeom g = tile_geom(A.na, A.nb, piece_rows(A.nb, A.nsplit, DT_B));
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
   const uint32_t ntile = (uint32_t)((be - bs + DT_B - 1) / DT_B);
-  const uint32_t a_valid = A.a_ids ? A.pstride : A.dbytes;
-  auto a_load = [&](uint32_t r, uint32_t off) -> uint4 {
-    if (r >= na_tile) return make_uint4(0, 0, 0, 0);
-    const uint8_t* rp = A.a_ids ? A.points + (uint64_t)A.a_ids[a0 + r] * A.pstride : A.a_ext + (a0 + r) * A.a_stride;
-    if ((reinterpret_cast<uintptr_t>(rp) & 15) == 0) return load16_guarded(rp, off, a_valid);
-    uint8_t tmp[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) tmp[i] = (off + i < a_valid) ? rp[off + i] : (uint8_t)0;
-    uint4 v; __builtin_memcpy(&v, tmp, 16);
-    return v;
-  };
   const int r0 = tid >> 4, c = tid & 15;
   // |a|^2 of the 64 A rows (same summation as the staging code above)
 #pragma unroll
   for (int k = 0; k < 4; k++) {
-    const float ss = group_sum<16>(sumsq16<BF>(a_load(r0 + 16 * k, c * 16)));
+    const float ss = group_sum<16>(sumsq16<BF>(dense_a_load(A, g, r0 + 16 * k, c * 16)));
     if (c == 0) An[r0 + 16 * k] = ss;
   }
   // A fragments of this wave: row wave*16 + (lane & 15), bytes ks*64 + q*16 .. +16 of it, for the 4 k-steps of a 256-byte row
   uint4 af[4];
 #pragma unroll
-  for (int ks = 0; ks < 4; ks++) af[ks] = a_load(wave * DT_AW + (lane & 15), ks * 64 + q * 16);
+  for (int ks = 0; ks < 4; ks++) af[ks] = dense_a_load(A, g, wave * DT_AW + (lane & 15), ks * 64 + q * 16);
 
   // The queue pays where an insert is long: k > 16 (NR = 8, an 80-instruction shift chain: 12.9 -> 11.0 ms at k = 100).  At
   // k <= 16 (NR = 1) an insert is one shift + max step, cheaper than a trip through the queue (6.8 vs 7.5 ms at k = 10).
@@ -1081,15 +975,7 @@ __global__ void __launch_bounds__(256, PANN_GT_WGS) dense_gt_mfma_kernel(DenseAr
     if (METRIC == PANN_L2) vn = bnorm[min((uint32_t)(bt_) + (uint32_t)lane, last_row)];    /* every wave: no branch around a load */ \
   } while (0)
   auto store_tile = [&](const uint4& v0, const uint4& v1, const uint4& v2, const uint4& v3, float vn, int buf, uint64_t bt) {
-    if (cvalid) {
-      uint8_t* dst = Bt0 + buf * GT_BT_BYTES + gt_swz((uint32_t)r0, (uint32_t)c * 16u);      // rows r0 + 16 k share r0's swizzle
-      *reinterpret_cast<uint4*>(dst) = v0;
-      *reinterpret_cast<uint4*>(dst + 16 * GT_BSTRIDE) = v1;
-      *reinterpret_cast<uint4*>(dst + 32 * GT_BSTRIDE) = v2;
-      *reinterpret_cast<uint4*>(dst + 48 * GT_BSTRIDE) = v3;
-    }
-    if (tid < DT_B)
-      Bm[buf * DT_B + tid] = make_float2(vn, __uint_as_float(bt + tid < be ? (uint32_t)(bt + tid) : SENTINEL));
+    gt_store_tile(Bt0 + buf * GT_BT_BYTES, Bm + buf * DT_B, cvalid, v0, v1, v2, v3, vn, bt, be, tid);
   };
   // tile bt -> LDS buffer buf from its register set, then the set is refilled with tile bt + 2 tiles
   auto stage_a = [&](int buf, uint64_t bt) { store_tile(pa0, pa1, pa2, pa3, pan, buf, bt); GT_LOAD_PRE(pa0, pa1, pa2, pa3, pan, bt + 2 * DT_B); };
@@ -1104,7 +990,7 @@ __global__ void __launch_bounds__(256, PANN_GT_WGS) dense_gt_mfma_kernel(DenseAr
     GT_LOAD_PRE(pa0, pa1, pa2, pa3, pan, bs + DT_B);
     GT_LOAD_PRE(pb0, pb1, pb2, pb3, pbn, bs + 2 * DT_B);
   }
-  gt_lds_barrier();
+  lds_barrier();
 
   // one tile: `buf` holds it, `stage` writes tile i+1 (requested two iterations ago) and requests tile i+3 into the same registers
   auto tile_step = [&](uint32_t i, const int buf, auto&& stage) {
@@ -1123,22 +1009,10 @@ __global__ void __launch_bounds__(256, PANN_GT_WGS) dense_gt_mfma_kernel(DenseAr
     const uint8_t* Bt = Bt0 + buf * GT_BT_BYTES;
 #pragma unroll
     for (int ks = 0; ks < 4; ks++) {      // always the 4 k-steps of a 256-byte row: bytes beyond the row are zero in both tiles
-      const uint32_t koff = ks * 64 + q * 16;
-      if constexpr (BF) {
-        mf_bf8 a8; __builtin_memcpy(&a8, &af[ks], 16);
+      uint4 braw[4];
 #pragma unroll
-        for (int t = 0; t < 4; t++) {
-          const mf_bf8 b8 = *reinterpret_cast<const mf_bf8*>(Bt + gt_swz((uint32_t)(t * 16 + (lane & 15)), koff));
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a8, b8, acc[t], 0, 0, 0);
-        }
-      } else {
-        mf_half8 a8; __builtin_memcpy(&a8, &af[ks], 16);
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-          const mf_half8 b8 = *reinterpret_cast<const mf_half8*>(Bt + gt_swz((uint32_t)(t * 16 + (lane & 15)), koff));
-          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a8, b8, acc[t], 0, 0, 0);
-        }
-      }
+      for (int t = 0; t < 4; t++) braw[t] = *reinterpret_cast<const uint4*>(Bt + gt_swz((uint32_t)(t * 16 + (lane & 15)), ks * 64 + q * 16));
+      mfma_step<BF>(af[ks], braw, acc);
     }
     // ---- epilogue: acc[t][r] = a(row wave*16 + 4q + r) . b(column t*16 + (lane & 15)) ----
     float bn[4]; uint32_t bid[4];
@@ -1185,7 +1059,7 @@ __global__ void __launch_bounds__(256, PANN_GT_WGS) dense_gt_mfma_kernel(DenseAr
 #ifdef PANN_GT_DIAG_NOBARRIER     /* timing diagnostic: the waves of a workgroup run free (results are wrong) */
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #else
-    gt_lds_barrier();
+    lds_barrier();
 #endif
   };
   // (an odd tile count runs one more step on a tile of SENTINEL labels: no branch around the second half's loads)
@@ -1233,19 +1107,6 @@ __device__ __forceinline__ void gt_chunk_accum(typename AccT<DT>::type (&acc)[4]
     }
   }
 }
-// sum of squares of 16 bytes of a one-byte type
-template <int DT>
-__device__ __forceinline__ int sumsq16_i8(uint4 v) {
-  if constexpr (DT == PANN_U8) {
-    uint32_t x = __builtin_amdgcn_udot4(v.x, v.x, 0u, false); x = __builtin_amdgcn_udot4(v.y, v.y, x, false);
-    x = __builtin_amdgcn_udot4(v.z, v.z, x, false); x = __builtin_amdgcn_udot4(v.w, v.w, x, false);
-    return (int)x;
-  } else {
-    int x = __builtin_amdgcn_sdot4((int)v.x, (int)v.x, 0, false); x = __builtin_amdgcn_sdot4((int)v.y, (int)v.y, x, false);
-    x = __builtin_amdgcn_sdot4((int)v.z, (int)v.z, x, false); x = __builtin_amdgcn_sdot4((int)v.w, (int)v.w, x, false);
-    return x;
-  }
-}
 // |row|^2 of every point of a one-byte type as an int32 (exact), stored through the float pointer
 template <int DT>
 __global__ void __launch_bounds__(256) row_norms_i8_kernel(const uint8_t* points, uint32_t pstride, uint64_t n, int* out) {
@@ -1269,29 +1130,16 @@ __global__ void __launch_bounds__(256, 2) dense_gt_valu_kernel(DenseArgs A, cons
   int* An = reinterpret_cast<int*>(Bm + 2 * DT_B);                        // [64] |a|^2 (one-byte types, L2)
   uint8_t* At = reinterpret_cast<uint8_t*>(An + DT_A);                    // [64][astride]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4;
-  const uint64_t a0 = (uint64_t)blockIdx.x * DT_A;
-  const uint32_t na_tile = (uint32_t)min((uint64_t)DT_A, A.na - a0);
-  const uint64_t per = ((A.nb + A.nsplit - 1) / A.nsplit + DT_B - 1) / DT_B * DT_B;
-  const uint64_t bs = min(A.nb, (uint64_t)blockIdx.y * per), be = min(A.nb, (uint64_t)(blockIdx.y + 1) * per);
+  const TileGeom g = tile_geom(A.na, A.nb, piece_rows(A.nb, A.nsplit, DT_B));
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
   const uint32_t ntile = (uint32_t)((be - bs + DT_B - 1) / DT_B);
-  const uint32_t a_valid = A.a_ids ? A.pstride : A.dbytes;
-  auto a_load = [&](uint32_t r, uint32_t off) -> uint4 {
-    if (r >= na_tile) return make_uint4(0, 0, 0, 0);
-    const uint8_t* rp = A.a_ids ? A.points + (uint64_t)A.a_ids[a0 + r] * A.pstride : A.a_ext + (a0 + r) * A.a_stride;
-    if ((reinterpret_cast<uintptr_t>(rp) & 15) == 0) return load16_guarded(rp, off, a_valid);
-    uint8_t tmp[16];
-#pragma unroll
-    for (int i = 0; i < 16; i++) tmp[i] = (off + i < a_valid) ? rp[off + i] : (uint8_t)0;
-    uint4 v; __builtin_memcpy(&v, tmp, 16);
-    return v;
-  };
   const int r0 = tid >> 4, c = tid & 15;
   // the A tile -> LDS, with |a|^2 for the one-byte L2 form |a|^2 + |b|^2 - 2 a.b (all int32, exact)
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     int ss = 0;
     for (uint32_t sg = 0; sg < nseg; sg++) {
-      const uint4 v = a_load(r0 + 16 * k, sg * DT_SEG + c * 16);
+      const uint4 v = dense_a_load(A, g, r0 + 16 * k, sg * DT_SEG + c * 16);
       *reinterpret_cast<uint4*>(At + (size_t)(r0 + 16 * k) * astride + sg * DT_SEG + c * 16) = v;
       if constexpr (INTS) ss += sumsq16_i8<DT>(v);
     }
@@ -1333,23 +1181,15 @@ __global__ void __launch_bounds__(256, 2) dense_gt_valu_kernel(DenseArgs A, cons
     if (INTS && METRIC == PANN_L2) pn = bnorm[min(bt + (uint32_t)lane, last_row)];
   };
   auto store_pre = [&](uint32_t u) {
-    const uint32_t bt = unit_bt(u);
     const int buf = (int)(u & 1);
-    if ((nseg == 2 && (u & 1)) ? cv1 : cv0) {
-      uint8_t* dst = Bt0 + buf * GT_BT_BYTES + gt_swz((uint32_t)r0, (uint32_t)c * 16u);      // rows r0 + 16 k share r0's swizzle
-      *reinterpret_cast<uint4*>(dst) = pre0;
-      *reinterpret_cast<uint4*>(dst + 16 * GT_BSTRIDE) = pre1;
-      *reinterpret_cast<uint4*>(dst + 32 * GT_BSTRIDE) = pre2;
-      *reinterpret_cast<uint4*>(dst + 48 * GT_BSTRIDE) = pre3;
-    }
-    if (tid < DT_B)
-      Bm[buf * DT_B + tid] = make_float2(__int_as_float(pn), __uint_as_float((uint64_t)bt + tid < be ? bt + (uint32_t)tid : SENTINEL));
+    gt_store_tile(Bt0 + buf * GT_BT_BYTES, Bm + buf * DT_B, (nseg == 2 && (u & 1)) ? cv1 : cv0, pre0, pre1, pre2, pre3, __int_as_float(pn),
+                  unit_bt(u), be, tid);
   };
   if (nunits > 0) {
     load_pre(0); store_pre(0);
     load_pre(1);
   }
-  gt_lds_barrier();
+  lds_barrier();
 
   acc_t acc[4][4];
   for (uint32_t u = 0; u < nunits; u++) {
@@ -1399,7 +1239,7 @@ __global__ void __launch_bounds__(256, 2) dense_gt_valu_kernel(DenseArgs A, cons
       // queues would take the LDS of the second workgroup per CU)
       gt_select<NR>(S, dist, bid, skip, pplace, gtau_mine, A.nsplit, lane);
     }
-    gt_lds_barrier();
+    lds_barrier();
   }
   gt_sel_write<NR>(S, A.partial + ((a0 + wave * DT_AW + q * 4) * A.nsplit + blockIdx.y) * A.m, A.m, A.nsplit, lane);
 }
@@ -1418,16 +1258,8 @@ __global__ void __launch_bounds__(64) dense_merge_kernel(const uint64_t* partial
   for (uint32_t i0 = 0; i0 < total; i0 += 64) {
     const uint32_t i = i0 + lane;
     const uint64_t key = i < total ? src[i] : KEY_INF;
-    uint64_t tau = list[m - 1];
-    uint64_t mask = __ballot(key < tau);
-    while (mask) {
-      const int L = __ffsll((unsigned long long)mask) - 1;
-      const uint32_t klo = __builtin_amdgcn_readlane((uint32_t)key, L);
-      const uint32_t khi = __builtin_amdgcn_readlane((uint32_t)(key >> 32), L);
-      const uint64_t x = ((uint64_t)khi << 32) | klo;
-      mask &= mask - 1;
-      if (x < tau) { list_insert(list, mcap, x, lane); tau = list[m - 1]; }
-    }
+    const uint64_t tau = list[m - 1];
+    list_insert_survivors(list, tau, __ballot(key < tau), key, m, mcap, lane);
   }
   for (uint32_t j = lane; j < m; j += 64) {
     const uint64_t k = list[j];
@@ -1460,23 +1292,15 @@ template <typename F>
 static int dense_gt_pick(const DeviceIndex& ix, uint32_t m, F&& f) {
   // list registers per row: 1 (k <= 16), 7 (k <= 112: the usual ground truth, k = 100 -- an insert step is one register shorter
   // than with 8 and the kernel holds 8 registers less) or 8
-  const bool l2 = ix.metric == PANN_L2, small = m <= 16, mid = m <= 112;
-#define GT_MF(BF)                                                                                                                   \
-  (small ? (l2 ? f(dense_gt_mfma_kernel<PANN_L2, BF, 1>) : f(dense_gt_mfma_kernel<PANN_MIPS, BF, 1>))                                \
-   : mid ? (l2 ? f(dense_gt_mfma_kernel<PANN_L2, BF, 7>) : f(dense_gt_mfma_kernel<PANN_MIPS, BF, 7>))                                \
-         : (l2 ? f(dense_gt_mfma_kernel<PANN_L2, BF, 8>) : f(dense_gt_mfma_kernel<PANN_MIPS, BF, 8>)))
-#define GT_VA(DT)                                                                                                                   \
-  (small ? (l2 ? f(dense_gt_valu_kernel<DT, PANN_L2, 1>) : f(dense_gt_valu_kernel<DT, PANN_MIPS, 1>))                                \
-         : (l2 ? f(dense_gt_valu_kernel<DT, PANN_L2, 8>) : f(dense_gt_valu_kernel<DT, PANN_MIPS, 8>)))
-  switch (ix.dtype) {
-    case PANN_F16: return GT_MF(false);
-    case PANN_BF16: return GT_MF(true);
-    case PANN_U8: return GT_VA(PANN_U8);
-    case PANN_I8: return GT_VA(PANN_I8);
-    default: return GT_VA(PANN_F32);
-  }
-#undef GT_MF
-#undef GT_VA
+  return dispatch_type_metric(ix.dtype, ix.metric, [&](auto dt, auto mt) -> int {
+    constexpr int DT = decltype(dt)::value, MT = decltype(mt)::value;
+    if constexpr (is_two_byte(DT)) {
+      constexpr bool BF = DT == PANN_BF16;
+      return m <= 16 ? f(dense_gt_mfma_kernel<MT, BF, 1>) : m <= 112 ? f(dense_gt_mfma_kernel<MT, BF, 7>) : f(dense_gt_mfma_kernel<MT, BF, 8>);
+    } else {
+      return m <= 16 ? f(dense_gt_valu_kernel<DT, MT, 1>) : f(dense_gt_valu_kernel<DT, MT, 8>);
+    }
+  });
 }
 
 // workgroups of the ground-truth launch that are resident at once (for the caller's choice of nsplit)
@@ -1511,7 +1335,6 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const u
   A.a_ext = d_a_ext; A.a_stride = a_stride; A.a_ids = d_a_ids; A.b_ids = d_b_ids;
   A.a_off = d_a_off; A.b_off = d_b_off; A.na = na; A.nb = nb; A.nsplit = nsplit; A.m = m; A.mcap = mcap;
   A.exclude_same_id = exclude_same; A.exact = ix.exact; A.partial = (uint64_t*)ws.buf; A.tile_seg = d_tile_seg; A.tile_a0 = d_tile_a0;
-  const size_t lds = dense_lds_bytes(mcap);
   const dim3 grid(ntiles, nsplit);
   if (dense_gt_eligible(ix, m, d_b_ids != nullptr, d_a_off || d_b_off || d_tile_seg || d_tile_a0, exclude_same)) {
     // register-list ground-truth kernel; |b|^2 of every point first (after the partial lists in the workspace)
@@ -1524,55 +1347,30 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const u
     uint32_t* d_gtau = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws.buf) + noff);      // [A row][piece]: the piece's ceil(m/nsplit)-th best so far
     PANN_HIP(hipMemsetAsync(d_gtau, 0xFF, (size_t)na * nsplit * 4, st));
     const dim3 ng((uint32_t)((nnorm + 15) / 16));
-    if (ix.metric == PANN_L2) {       // |b|^2 of every point: f32 bits for the two-byte floats, exact int32 for the one-byte types
-      if (ix.dtype == PANN_BF16) hipLaunchKernelGGL(row_norms_kernel<true>, ng, dim3(256), 0, st, ix.points, ix.pstride, nnorm, d_norm);
-      else if (ix.dtype == PANN_F16) hipLaunchKernelGGL(row_norms_kernel<false>, ng, dim3(256), 0, st, ix.points, ix.pstride, nnorm, d_norm);
-      else if (ix.dtype == PANN_U8) hipLaunchKernelGGL(row_norms_i8_kernel<PANN_U8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nnorm, (int*)d_norm);
-      else if (ix.dtype == PANN_I8) hipLaunchKernelGGL(row_norms_i8_kernel<PANN_I8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nnorm, (int*)d_norm);
-    }
-    const size_t glds = dense_gt_lds(ix, m);
+    // |b|^2 of every point: f32 bits for the two-byte floats, exact int32 for the one-byte types (f32: difference form, no norms)
+    if (ix.metric == PANN_L2) dispatch_type_metric(ix.dtype, ix.metric, [&](auto dt, auto) {
+      constexpr int DT = decltype(dt)::value;
+      if constexpr (is_two_byte(DT)) { hipLaunchKernelGGL((row_norms_kernel<DT == PANN_BF16>), ng, dim3(256), 0, st, ix.points, ix.pstride, nnorm, d_norm); }
+      else if constexpr (DT != PANN_F32) { hipLaunchKernelGGL(row_norms_i8_kernel<DT>, ng, dim3(256), 0, st, ix.points, ix.pstride, nnorm, (int*)d_norm); }
+    });
     dense_gt_pick(ix, m, [&](auto kern) -> int {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)glds);
       using norm_t = std::conditional_t<std::is_invocable_v<decltype(kern), DenseArgs, const float*, uint32_t*>, const float*, const int*>;
-      hipLaunchKernelGGL(kern, grid, dim3(256), glds, st, A, (norm_t)d_norm, d_gtau);
+      launch_lds(kern, grid, dim3(256), dense_gt_lds(ix, m), st, A, (norm_t)d_norm, d_gtau);
       return 0;
     });
-    PANN_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dense_merge_kernel, dim3((uint32_t)na), dim3(64), (size_t)mcap * 8, st,
-                       (const uint64_t*)ws.buf, na, nsplit, m, mcap, d_out_ids, d_out_dists);
-    PANN_HIP(hipGetLastError());
-    return PANN_OK;
+  } else {
+    dispatch_type_metric(ix.dtype, ix.metric, [&](auto dt, auto mt) {
+      constexpr int DT = decltype(dt)::value, MT = decltype(mt)::value;
+      if constexpr (is_two_byte(DT)) {
+        if (!ix.exact) {                // (exact order: VALU path, not MFMA)
+          const size_t lds2 = (size_t)(DT_A + DT_B) * DT_BSTRIDE + (DT_A + DT_B) * 8 + (size_t)DT_A * mcap * 8 +
+                              4 * (size_t)DT_AW * 68 * 4;       // + the epilogue's transposition scratch K (single-segment rows keep it apart from the B tile)
+          return launch_lds(dense_topk_mfma_f16_kernel<MT, DT == PANN_BF16>, grid, dim3(256), lds2, st, A);
+        }
+      }
+      launch_lds(dense_topk_kernel<DT, MT>, grid, dim3(256), dense_lds_bytes(mcap), st, A);
+    });
   }
-#define CALL_DENSE(DT, MT)                                                                              \
-  do {                                                                                                   \
-    auto kern = dense_topk_kernel<DT, MT>;                                                               \
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A);                                               \
-  } while (0)
-  if (ix.dtype == PANN_U8 && ix.metric == PANN_L2) CALL_DENSE(PANN_U8, PANN_L2);
-  else if (ix.dtype == PANN_U8) CALL_DENSE(PANN_U8, PANN_MIPS);
-  else if (ix.dtype == PANN_I8 && ix.metric == PANN_L2) CALL_DENSE(PANN_I8, PANN_L2);
-  else if (ix.dtype == PANN_I8) CALL_DENSE(PANN_I8, PANN_MIPS);
-  else if (ix.dtype == PANN_F32 && ix.metric == PANN_L2) CALL_DENSE(PANN_F32, PANN_L2);
-  else if (ix.dtype == PANN_F32) CALL_DENSE(PANN_F32, PANN_MIPS);
-  else if (ix.dtype == PANN_F16 && ix.exact && ix.metric == PANN_L2) CALL_DENSE(PANN_F16, PANN_L2);      // exact order: VALU path, not MFMA
-  else if (ix.dtype == PANN_F16 && ix.exact) CALL_DENSE(PANN_F16, PANN_MIPS);
-  else if (ix.dtype == PANN_BF16 && ix.exact && ix.metric == PANN_L2) CALL_DENSE(PANN_BF16, PANN_L2);
-  else if (ix.dtype == PANN_BF16 && ix.exact) CALL_DENSE(PANN_BF16, PANN_MIPS);
-  else {
-    const size_t lds2 = (size_t)(DT_A + DT_B) * DT_BSTRIDE + (DT_A + DT_B) * 8 + (size_t)DT_A * mcap * 8 +
-                        4 * (size_t)DT_AW * 68 * 4;       // + the epilogue's transposition scratch K (single-segment rows keep it apart from the B tile)
-#define CALL_MFMA(MT, BF)                                                                               \
-  do {                                                                                                   \
-    auto kern = dense_topk_mfma_f16_kernel<MT, BF>;                                                      \
-    if (lds2 > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2); \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds2, st, A);                                              \
-  } while (0)
-    if (ix.dtype == PANN_BF16) { if (ix.metric == PANN_L2) CALL_MFMA(PANN_L2, true); else CALL_MFMA(PANN_MIPS, true); }
-    else { if (ix.metric == PANN_L2) CALL_MFMA(PANN_L2, false); else CALL_MFMA(PANN_MIPS, false); }
-#undef CALL_MFMA
-  }
-#undef CALL_DENSE
   PANN_HIP(hipGetLastError());
   hipLaunchKernelGGL(dense_merge_kernel, dim3((uint32_t)na), dim3(64), (size_t)mcap * 8, st,
                      (const uint64_t*)ws.buf, na, nsplit, m, mcap, d_out_ids, d_out_dists);

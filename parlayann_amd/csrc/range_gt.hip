@@ -25,16 +25,12 @@
 // Exact float order (all three float types): dist_accum_exact, one sequential f32 sum per pair, strictly left to right.
 #include <algorithm>
 
-#include "pann_device.h"
+#include "dense_tile.h"
 
 namespace pann {
 
-constexpr int RJ_A = 64;          // query rows per workgroup
-constexpr int RJ_AW = 16;         // query rows per wave
-constexpr int RJ_SEG = 256;       // bytes of the dimension staged per step
-constexpr int RJ_BSTRIDE = RJ_SEG + 16;     // padded LDS row: the lane-per-row ds_read_b128 is conflict free
+// (DT_A = 64 query rows per workgroup, DT_AW = 16 per wave, DT_SEG, DT_BSTRIDE, DT_B = 64 base rows per matrix-core tile: dense_tile.h)
 constexpr int RJ_VB = 128;        // VALU kernel: base rows per tile (two per lane)
-constexpr int RJ_MB = 64;         // matrix-core kernel: base rows per tile
 constexpr uint64_t RJ_PIECE_ALIGN = 128;    // a piece is a whole number of tiles of either kernel
 
 struct RangeJoinArgs {
@@ -48,38 +44,6 @@ struct RangeJoinArgs {
   uint32_t* out_ids;
 };
 
-// workgroup barrier that orders LDS traffic only (as gt_lds_barrier of dense.hip): __syncthreads() would also wait for the
-// rows requested one step ahead
-__device__ __forceinline__ void rj_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// 16 bytes of a query row that may be unaligned and ends after `valid` bytes
-__device__ __forceinline__ uint4 rj_load_query16(const uint8_t* rp, uint32_t off, uint32_t valid) {
-  if ((reinterpret_cast<uintptr_t>(rp) & 15) == 0) return load16_guarded(rp, off, valid);
-  uint8_t tmp[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) tmp[i] = (off + i < valid) ? rp[off + i] : (uint8_t)0;
-  uint4 v;
-  __builtin_memcpy(&v, tmp, 16);
-  return v;
-}
-
-template <int DT>
-__device__ __forceinline__ int rj_dot16_self(const uint4& v) {
-  if constexpr (DT == PANN_U8) {
-    uint32_t s = __builtin_amdgcn_udot4(v.x, v.x, 0u, false);
-    s = __builtin_amdgcn_udot4(v.y, v.y, s, false);
-    s = __builtin_amdgcn_udot4(v.z, v.z, s, false);
-    s = __builtin_amdgcn_udot4(v.w, v.w, s, false);
-    return (int)s;
-  } else {
-    int s = __builtin_amdgcn_sdot4((int)v.x, (int)v.x, 0, false);
-    s = __builtin_amdgcn_sdot4((int)v.y, (int)v.y, s, false);
-    s = __builtin_amdgcn_sdot4((int)v.z, (int)v.z, s, false);
-    s = __builtin_amdgcn_sdot4((int)v.w, (int)v.w, s, false);
-    return s;
-  }
-}
-
 // ---- VALU tiles: one-byte types (dot4), f32 (fma), and every float type in exact-float-order mode ----
 template <int DT, int METRIC, bool FILL>
 __global__ void __launch_bounds__(256) range_join_valu_kernel(RangeJoinArgs A) {
@@ -87,33 +51,32 @@ __global__ void __launch_bounds__(256) range_join_valu_kernel(RangeJoinArgs A) {
   constexpr bool INTEGER = !is_float_dt<DT>();
   constexpr int ACC_METRIC = INTEGER ? PANN_MIPS : METRIC;      // one-byte types accumulate a.b only; L2 adds the norms
   constexpr bool EXACT_ONLY = DT == PANN_F16 || DT == PANN_BF16;   // two-byte types come here in exact-float-order mode only
-  uint8_t* At = smem;                                           // [64][RJ_SEG]
-  uint8_t* Bt = At + RJ_A * RJ_SEG;                             // [128][RJ_BSTRIDE]
-  int* An = reinterpret_cast<int*>(Bt + RJ_VB * RJ_BSTRIDE);    // [64]  |a|^2 (one-byte types, L2)
-  int* Bn = An + RJ_A;                                          // [128] |b|^2
+  uint8_t* At = smem;                                           // [64][DT_SEG]
+  uint8_t* Bt = At + DT_A * DT_SEG;                             // [128][DT_BSTRIDE]
+  int* An = reinterpret_cast<int*>(Bt + RJ_VB * DT_BSTRIDE);    // [64]  |a|^2 (one-byte types, L2)
+  int* Bn = An + DT_A;                                          // [128] |b|^2
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);    // uniform: the per-row counters and positions below stay scalar
-  const uint64_t a0 = (uint64_t)blockIdx.x * RJ_A;
-  const uint32_t na_tile = (uint32_t)min((uint64_t)RJ_A, A.nq - a0);
-  const uint64_t bs = min(A.n, (uint64_t)blockIdx.y * A.per), be = min(A.n, ((uint64_t)blockIdx.y + 1) * A.per);
-  const uint32_t nseg = (A.pstride + RJ_SEG - 1) / RJ_SEG;
+  const TileGeom g = tile_geom(A.nq, A.n, A.per);
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
+  const uint32_t nseg = (A.pstride + DT_SEG - 1) / DT_SEG;
   const int r0 = tid >> 4, c = tid & 15;                        // staging: 16 threads x 16 B per row, 16 rows per sweep
 
-  uint32_t cnt[RJ_AW];                                          // matches of the wave's rows in this piece so far (both passes)
+  uint32_t cnt[DT_AW];                                          // matches of the wave's rows in this piece so far (both passes)
   uint64_t total = 0;                                           // no write lands at or beyond it, whatever happens
   if constexpr (FILL) total = A.pos[A.nq * A.nsplit];
 #pragma unroll
-  for (int a = 0; a < RJ_AW; a++) cnt[a] = 0;
+  for (int a = 0; a < DT_AW; a++) cnt[a] = 0;
 
   auto stage_a = [&](uint32_t sg) {
 #pragma unroll
-    for (int k = 0; k < RJ_A / 16; k++) {
+    for (int k = 0; k < DT_A / 16; k++) {
       const int r = r0 + 16 * k;
       uint4 v = make_uint4(0, 0, 0, 0);
-      if (r < (int)na_tile) v = rj_load_query16(A.q + (a0 + r) * A.q_stride, sg * RJ_SEG + c * 16, A.dbytes);
-      *reinterpret_cast<uint4*>(At + (size_t)r * RJ_SEG + c * 16) = v;
+      if (r < (int)na_tile) v = load16_unaligned(A.q + (a0 + r) * A.q_stride, sg * DT_SEG + c * 16, A.dbytes);
+      *reinterpret_cast<uint4*>(At + (size_t)r * DT_SEG + c * 16) = v;
       if constexpr (INTEGER && METRIC == PANN_L2) {
-        const int ss = group_sum<16>(rj_dot16_self<DT>(v));
+        const int ss = group_sum<16>(sumsq16_i8<DT>(v));
         if (c == 0) An[r] = sg == 0 ? ss : An[r] + ss;
       }
     }
@@ -123,10 +86,10 @@ __global__ void __launch_bounds__(256) range_join_valu_kernel(RangeJoinArgs A) {
     for (int k = 0; k < RJ_VB / 16; k++) {
       const int r = r0 + 16 * k;
       uint4 v = make_uint4(0, 0, 0, 0);
-      if (r < (int)nb_tile) v = load16_guarded(A.points + (bt + r) * A.pstride, sg * RJ_SEG + c * 16, A.pstride);
-      *reinterpret_cast<uint4*>(Bt + (size_t)r * RJ_BSTRIDE + c * 16) = v;
+      if (r < (int)nb_tile) v = load16_guarded(A.points + (bt + r) * A.pstride, sg * DT_SEG + c * 16, A.pstride);
+      *reinterpret_cast<uint4*>(Bt + (size_t)r * DT_BSTRIDE + c * 16) = v;
       if constexpr (INTEGER && METRIC == PANN_L2) {
-        const int ss = group_sum<16>(rj_dot16_self<DT>(v));
+        const int ss = group_sum<16>(sumsq16_i8<DT>(v));
         if (c == 0) Bn[r] = sg == 0 ? ss : Bn[r] + ss;
       }
     }
@@ -136,26 +99,26 @@ __global__ void __launch_bounds__(256) range_join_valu_kernel(RangeJoinArgs A) {
 
   for (uint64_t bt = bs; bt < be; bt += RJ_VB) {
     const uint32_t nb_tile = (uint32_t)min((uint64_t)RJ_VB, be - bt);
-    Acc<DT> acc[RJ_AW][2];
+    Acc<DT> acc[DT_AW][2];
 #pragma unroll
-    for (int a = 0; a < RJ_AW; a++) { acc[a][0].clear(); acc[a][1].clear(); }
+    for (int a = 0; a < DT_AW; a++) { acc[a][0].clear(); acc[a][1].clear(); }
     for (uint32_t sg = 0; sg < nseg; sg++) {
       __syncthreads();                                          // the previous step's readers are done with the tiles
       stage_b(bt, nb_tile, sg);
       if (nseg > 1) stage_a(sg);
       __syncthreads();
       // chunks that hold only the rows' zero padding add nothing: skip them
-      const uint32_t seg_bytes = min((uint32_t)RJ_SEG, A.pstride - sg * RJ_SEG);
-      const uint32_t seg_valid = A.dbytes > sg * RJ_SEG ? min(seg_bytes, A.dbytes - sg * RJ_SEG) : 0u;
+      const uint32_t seg_bytes = min((uint32_t)DT_SEG, A.pstride - sg * DT_SEG);
+      const uint32_t seg_valid = A.dbytes > sg * DT_SEG ? min(seg_bytes, A.dbytes - sg * DT_SEG) : 0u;
       const uint32_t nchunk = (seg_valid + 15) / 16;
       for (uint32_t ch = 0; ch < nchunk; ch++) {
-        const uint4 braw0 = *reinterpret_cast<const uint4*>(Bt + (size_t)lane * RJ_BSTRIDE + ch * 16);
-        const uint4 braw1 = *reinterpret_cast<const uint4*>(Bt + (size_t)(lane + 64) * RJ_BSTRIDE + ch * 16);
+        const uint4 braw0 = *reinterpret_cast<const uint4*>(Bt + (size_t)lane * DT_BSTRIDE + ch * 16);
+        const uint4 braw1 = *reinterpret_cast<const uint4*>(Bt + (size_t)(lane + 64) * DT_BSTRIDE + ch * 16);
         if constexpr (!INTEGER) {
           if (EXACT_ONLY || A.exact) {      // strictly left to right, unfused, one accumulator per pair (s.y stays 0)
 #pragma unroll
-            for (int a = 0; a < RJ_AW; a++) {
-              const uint4 q = *reinterpret_cast<const uint4*>(At + (size_t)(wave * RJ_AW + a) * RJ_SEG + ch * 16);
+            for (int a = 0; a < DT_AW; a++) {
+              const uint4 q = *reinterpret_cast<const uint4*>(At + (size_t)(wave * DT_AW + a) * DT_SEG + ch * 16);
               float t0 = acc[a][0].s.x, t1 = acc[a][1].s.x;
               dist_accum_exact<DT, METRIC>(t0, q, braw0);
               dist_accum_exact<DT, METRIC>(t1, q, braw1);
@@ -168,8 +131,8 @@ __global__ void __launch_bounds__(256) range_join_valu_kernel(RangeJoinArgs A) {
         if constexpr (!EXACT_ONLY) {
           const QReg<DT> b0 = make_qreg<DT>(braw0), b1 = make_qreg<DT>(braw1);
 #pragma unroll
-          for (int a = 0; a < RJ_AW; a++) {
-            const uint4 q = *reinterpret_cast<const uint4*>(At + (size_t)(wave * RJ_AW + a) * RJ_SEG + ch * 16);
+          for (int a = 0; a < DT_AW; a++) {
+            const uint4 q = *reinterpret_cast<const uint4*>(At + (size_t)(wave * DT_AW + a) * DT_SEG + ch * 16);
             dist_accum<DT, ACC_METRIC>(acc[a][0], q, b0);
             dist_accum<DT, ACC_METRIC>(acc[a][1], q, b1);
           }
@@ -178,8 +141,8 @@ __global__ void __launch_bounds__(256) range_join_valu_kernel(RangeJoinArgs A) {
     }
     // ---- epilogue: compare with the radius; ballot order is id order ----
 #pragma unroll
-    for (int a = 0; a < RJ_AW; a++) {
-      const uint32_t ar = wave * RJ_AW + a;
+    for (int a = 0; a < DT_AW; a++) {
+      const uint32_t ar = wave * DT_AW + a;
 #pragma unroll
       for (int rb = 0; rb < 2; rb++) {
         const uint32_t brow = lane + 64 * rb;
@@ -204,33 +167,14 @@ __global__ void __launch_bounds__(256) range_join_valu_kernel(RangeJoinArgs A) {
   }
   if constexpr (!FILL) {
 #pragma unroll
-    for (int a = 0; a < RJ_AW; a++) {
-      const uint32_t ar = wave * RJ_AW + a;
+    for (int a = 0; a < DT_AW; a++) {
+      const uint32_t ar = wave * DT_AW + a;
       if (lane == 0 && ar < na_tile) A.counts[(a0 + ar) * A.nsplit + blockIdx.y] = cnt[a];
     }
   }
 }
 
 // ---- matrix-core tiles: f16 / bf16 in default mode ----
-typedef _Float16 rj_half8 __attribute__((ext_vector_type(8)));
-typedef __bf16 rj_bf8 __attribute__((ext_vector_type(8)));
-typedef float rj_float4 __attribute__((ext_vector_type(4)));
-
-template <bool BF>
-__device__ __forceinline__ float rj_sumsq16(uint4 v) {
-  float ss = 0.f;
-  if constexpr (BF) {
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const float lo = bf16_lo(w[i]), hi = bf16_hi(w[i]); ss = fmaf(lo, lo, ss); ss = fmaf(hi, hi, ss); }
-  } else {
-    rj_half8 h; __builtin_memcpy(&h, &v, 16);
-#pragma unroll
-    for (int i = 0; i < 8; i++) { const float f = (float)h[i]; ss = fmaf(f, f, ss); }
-  }
-  return ss;
-}
-
 // Each wave owns 16 query rows and computes the 16 x 64 block of dot products against the tile with four MFMAs per 32
 // elements of the dimension (fragments are plain ds_read_b128 from the padded LDS rows, as in dense_topk_mfma_f16_kernel);
 // acc[t][r] = a(row wave*16 + 4*(lane>>4) + r) . b(column t*16 + (lane & 15)).  The base rows of step i+1 (a step = one
@@ -239,15 +183,14 @@ __device__ __forceinline__ float rj_sumsq16(uint4 v) {
 template <int METRIC, bool BF, bool FILL>
 __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
   extern __shared__ __align__(16) uint8_t smem[];
-  uint8_t* At = smem;                                           // [64][RJ_BSTRIDE]
-  uint8_t* Bt = At + RJ_A * RJ_BSTRIDE;                         // [64][RJ_BSTRIDE]
-  float* An = reinterpret_cast<float*>(Bt + RJ_MB * RJ_BSTRIDE);   // [64] |a|^2
-  float* Bn = An + RJ_A;                                        // [64] |b|^2
+  uint8_t* At = smem;                                           // [64][DT_BSTRIDE]
+  uint8_t* Bt = At + DT_A * DT_BSTRIDE;                         // [64][DT_BSTRIDE]
+  float* An = reinterpret_cast<float*>(Bt + DT_B * DT_BSTRIDE);   // [64] |a|^2
+  float* Bn = An + DT_A;                                        // [64] |b|^2
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const uint64_t a0 = (uint64_t)blockIdx.x * RJ_A;
-  const uint32_t na_tile = (uint32_t)min((uint64_t)RJ_A, A.nq - a0);
-  const uint64_t bs = min(A.n, (uint64_t)blockIdx.y * A.per), be = min(A.n, ((uint64_t)blockIdx.y + 1) * A.per);
-  const uint32_t nseg = (A.pstride + RJ_SEG - 1) / RJ_SEG;
+  const TileGeom g = tile_geom(A.nq, A.n, A.per);
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
+  const uint32_t nseg = (A.pstride + DT_SEG - 1) / DT_SEG;
   const int r0 = tid >> 4, c = tid & 15;
   const int q = lane >> 4, col = lane & 15;
 
@@ -259,7 +202,7 @@ __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
   for (int r = 0; r < 4; r++) {
     cnt[r] = 0; wpos[r] = 0;
     if constexpr (FILL) {
-      const uint32_t ar = wave * RJ_AW + q * 4 + r;
+      const uint32_t ar = wave * DT_AW + q * 4 + r;
       if (ar < na_tile) wpos[r] = A.pos[(a0 + ar) * A.nsplit + blockIdx.y];
     }
   }
@@ -267,7 +210,7 @@ __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
     if constexpr (!FILL) {
 #pragma unroll
       for (int r = 0; r < 4; r++) {
-        const uint32_t ar = wave * RJ_AW + q * 4 + r;
+        const uint32_t ar = wave * DT_AW + q * 4 + r;
         if (col == 0 && ar < na_tile) A.counts[(a0 + ar) * A.nsplit + blockIdx.y] = 0;
       }
     }
@@ -281,10 +224,10 @@ __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
     for (int k = 0; k < 4; k++) {
       const int r = r0 + 16 * k;
       uint4 v = make_uint4(0, 0, 0, 0);
-      if (r < (int)na_tile) v = rj_load_query16(A.q + (a0 + r) * A.q_stride, sg * RJ_SEG + c * 16, A.dbytes);
-      *reinterpret_cast<uint4*>(At + (size_t)r * RJ_BSTRIDE + c * 16) = v;
+      if (r < (int)na_tile) v = load16_unaligned(A.q + (a0 + r) * A.q_stride, sg * DT_SEG + c * 16, A.dbytes);
+      *reinterpret_cast<uint4*>(At + (size_t)r * DT_BSTRIDE + c * 16) = v;
       if (norms) {
-        anorm[k] += group_sum<16>(rj_sumsq16<BF>(v));
+        anorm[k] += group_sum<16>(sumsq16<BF>(v));
         if (c == 0) An[r] = anorm[k];
       }
     }
@@ -299,7 +242,7 @@ __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
   const uint64_t last = be - 1;
   uint4 pre[4];
   auto load_b = [&](uint64_t bt, uint32_t sg) {
-    const uint32_t off = sg * RJ_SEG + c * 16;
+    const uint32_t off = sg * DT_SEG + c * 16;
     const uint32_t offc = min(off, A.pstride - 16u);            // a chunk beyond the row re-reads its last one and is zeroed
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -309,14 +252,14 @@ __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
   };
   float bnorm[4] = {0.f, 0.f, 0.f, 0.f};
   auto store_b = [&](uint32_t sg) {
-    const bool cvalid = sg * RJ_SEG + c * 16 < A.pstride;
+    const bool cvalid = sg * DT_SEG + c * 16 < A.pstride;
 #pragma unroll
     for (int k = 0; k < 4; k++) {
       const int r = r0 + 16 * k;
       const uint4 v = cvalid ? pre[k] : make_uint4(0, 0, 0, 0);
-      *reinterpret_cast<uint4*>(Bt + (size_t)r * RJ_BSTRIDE + c * 16) = v;
+      *reinterpret_cast<uint4*>(Bt + (size_t)r * DT_BSTRIDE + c * 16) = v;
       if constexpr (METRIC == PANN_L2) {
-        const float ss = group_sum<16>(rj_sumsq16<BF>(v));
+        const float ss = group_sum<16>(sumsq16<BF>(v));
         bnorm[k] = sg == 0 ? ss : bnorm[k] + ss;
         if (c == 0) Bn[r] = bnorm[k];
       }
@@ -329,49 +272,41 @@ __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
     __syncthreads();
 #pragma unroll
     for (int ks = 0; ks < 4; ks++)
-      afrag[ks] = *reinterpret_cast<const uint4*>(At + (size_t)(wave * RJ_AW + col) * RJ_BSTRIDE + ks * 64 + q * 16);
+      afrag[ks] = *reinterpret_cast<const uint4*>(At + (size_t)(wave * DT_AW + col) * DT_BSTRIDE + ks * 64 + q * 16);
   }
 
   load_b(bs, 0);
-  for (uint64_t bt = bs; bt < be; bt += RJ_MB) {
-    const uint32_t nb_tile = (uint32_t)min((uint64_t)RJ_MB, be - bt);
-    rj_float4 acc[4];
+  for (uint64_t bt = bs; bt < be; bt += DT_B) {
+    const uint32_t nb_tile = (uint32_t)min((uint64_t)DT_B, be - bt);
+    mf_float4 acc[4];
 #pragma unroll
-    for (int t = 0; t < 4; t++) acc[t] = rj_float4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 4; t++) acc[t] = mf_float4{0.f, 0.f, 0.f, 0.f};
     for (uint32_t sg = 0; sg < nseg; sg++) {
-      rj_lds_barrier();                                         // the previous step's multiply and epilogue have read the tiles
+      lds_barrier();                                         // the previous step's multiply and epilogue have read the tiles
       store_b(sg);
       if (nseg > 1) stage_a(sg, false);
       {                                                         // next step: the next segment of this tile, or the next tile
         const bool wrap = sg + 1 == nseg;
-        load_b(wrap ? bt + RJ_MB : bt, wrap ? 0u : sg + 1);
+        load_b(wrap ? bt + DT_B : bt, wrap ? 0u : sg + 1);
       }
-      rj_lds_barrier();
-      const uint32_t ksteps = min((uint32_t)RJ_SEG, A.pstride - sg * RJ_SEG) / 64;      // 32 two-byte elements per MFMA
+      lds_barrier();
+      const uint32_t ksteps = min((uint32_t)DT_SEG, A.pstride - sg * DT_SEG) / 64;      // 32 two-byte elements per MFMA
 #pragma unroll
       for (uint32_t ks = 0; ks < 4; ks++) {                     // (unrolled: afrag stays in registers)
         if (ks >= ksteps) break;
         const uint32_t koff = ks * 64 + q * 16;
         uint4 araw;
         if (nseg == 1) araw = afrag[ks];
-        else araw = *reinterpret_cast<const uint4*>(At + (size_t)(wave * RJ_AW + col) * RJ_BSTRIDE + koff);
+        else araw = *reinterpret_cast<const uint4*>(At + (size_t)(wave * DT_AW + col) * DT_BSTRIDE + koff);
 #pragma unroll
-        for (int t = 0; t < 4; t++) {
-          const uint4 braw = *reinterpret_cast<const uint4*>(Bt + (size_t)(t * 16 + col) * RJ_BSTRIDE + koff);
-          if constexpr (BF) {
-            rj_bf8 af, bf; __builtin_memcpy(&af, &araw, 16); __builtin_memcpy(&bf, &braw, 16);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, acc[t], 0, 0, 0);
-          } else {
-            rj_half8 af, bf; __builtin_memcpy(&af, &araw, 16); __builtin_memcpy(&bf, &braw, 16);
-            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(af, bf, acc[t], 0, 0, 0);
-          }
-        }
+        for (int t = 0; t < 4; t++)
+          acc[t] = mfma_step<BF>(araw, *reinterpret_cast<const uint4*>(Bt + (size_t)(t * 16 + col) * DT_BSTRIDE + koff), acc[t]);
       }
     }
     // ---- epilogue: the ballot of (r, t) holds row 4 q' + r in its bits 16 q' .. 16 q' + 15, columns t*16 .. t*16 + 15 in order ----
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const uint32_t ar = wave * RJ_AW + q * 4 + r;
+      const uint32_t ar = wave * DT_AW + q * 4 + r;
       const float an = An[ar];
 #pragma unroll
       for (int t = 0; t < 4; t++) {
@@ -395,7 +330,7 @@ __global__ void __launch_bounds__(256) range_join_mfma_kernel(RangeJoinArgs A) {
   if constexpr (!FILL) {
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-      const uint32_t ar = wave * RJ_AW + q * 4 + r;
+      const uint32_t ar = wave * DT_AW + q * 4 + r;
       if (col == 0 && ar < na_tile) A.counts[(a0 + ar) * A.nsplit + blockIdx.y] = cnt[r];
     }
   }
@@ -444,31 +379,16 @@ static size_t rj_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 template <bool FILL>
 static int range_join_launch(const DeviceIndex& ix, hipStream_t st, const RangeJoinArgs& A, dim3 grid) {
-  const bool twobyte = ix.dtype == PANN_F16 || ix.dtype == PANN_BF16;
-  if (twobyte && !ix.exact) {
-    const size_t lds = (size_t)(RJ_A + RJ_MB) * RJ_BSTRIDE + (RJ_A + RJ_MB) * sizeof(float);
-#define CALL_RJ_MFMA(MT, BF) hipLaunchKernelGGL((range_join_mfma_kernel<MT, BF, FILL>), grid, dim3(256), lds, st, A)
-    if (ix.dtype == PANN_BF16) { if (ix.metric == PANN_L2) CALL_RJ_MFMA(PANN_L2, true); else CALL_RJ_MFMA(PANN_MIPS, true); }
-    else { if (ix.metric == PANN_L2) CALL_RJ_MFMA(PANN_L2, false); else CALL_RJ_MFMA(PANN_MIPS, false); }
-#undef CALL_RJ_MFMA
-  } else {
-    const size_t lds = (size_t)RJ_A * RJ_SEG + (size_t)RJ_VB * RJ_BSTRIDE + (RJ_A + RJ_VB) * sizeof(int);
-#define CALL_RJ_VALU(DT, MT)                                                                                                        \
-  do {                                                                                                                               \
-    auto kern = range_join_valu_kernel<DT, MT, FILL>;                                                                                \
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);           \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, A);                                                                           \
-  } while (0)
-    const bool l2 = ix.metric == PANN_L2;
-    switch (ix.dtype) {
-      case PANN_U8: if (l2) CALL_RJ_VALU(PANN_U8, PANN_L2); else CALL_RJ_VALU(PANN_U8, PANN_MIPS); break;
-      case PANN_I8: if (l2) CALL_RJ_VALU(PANN_I8, PANN_L2); else CALL_RJ_VALU(PANN_I8, PANN_MIPS); break;
-      case PANN_F16: if (l2) CALL_RJ_VALU(PANN_F16, PANN_L2); else CALL_RJ_VALU(PANN_F16, PANN_MIPS); break;
-      case PANN_BF16: if (l2) CALL_RJ_VALU(PANN_BF16, PANN_L2); else CALL_RJ_VALU(PANN_BF16, PANN_MIPS); break;
-      default: if (l2) CALL_RJ_VALU(PANN_F32, PANN_L2); else CALL_RJ_VALU(PANN_F32, PANN_MIPS); break;
+  dispatch_type_metric(ix.dtype, ix.metric, [&](auto dt, auto mt) {
+    constexpr int DT = decltype(dt)::value, MT = decltype(mt)::value;
+    if constexpr (is_two_byte(DT)) {
+      if (!ix.exact)
+        return launch_lds(range_join_mfma_kernel<MT, DT == PANN_BF16, FILL>, grid, dim3(256),
+                          (size_t)(DT_A + DT_B) * DT_BSTRIDE + (DT_A + DT_B) * sizeof(float), st, A);
     }
-#undef CALL_RJ_VALU
-  }
+    launch_lds(range_join_valu_kernel<DT, MT, FILL>, grid, dim3(256),
+               (size_t)DT_A * DT_SEG + (size_t)RJ_VB * DT_BSTRIDE + (DT_A + RJ_VB) * sizeof(int), st, A);
+  });
   PANN_HIP(hipGetLastError());
   return PANN_OK;
 }
@@ -490,7 +410,7 @@ static RangeJoinArgs range_join_args(const DeviceIndex& ix, Workspace& ws, const
 // pieces of the base per query tile: enough workgroups to fill the 256 CUs several times over (a workgroup keeps no state
 // between tiles, so small pieces cost nothing but their share of the scan), never less than one tile per piece
 uint32_t range_join_pieces(const DeviceIndex& ix, uint64_t nq, uint32_t wanted) {
-  const uint64_t ntiles = (nq + RJ_A - 1) / RJ_A;
+  const uint64_t ntiles = (nq + DT_A - 1) / DT_A;
   uint64_t p = wanted ? wanted : (2048 + ntiles - 1) / ntiles;
   p = std::min<uint64_t>(p, (ix.n + 255) / 256);
   return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(p, 64));
@@ -504,7 +424,7 @@ int range_join_count_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, c
   const size_t slots = (size_t)nq * nsplit;
   if (int rc = ws.ensure(rj_align(slots * 4) + rj_align((slots + 1) * 8))) return rc;
   const RangeJoinArgs A = range_join_args(ix, ws, d_q, q_stride, nq, radius, nsplit);
-  const dim3 grid((uint32_t)((nq + RJ_A - 1) / RJ_A), nsplit);
+  const dim3 grid((uint32_t)((nq + DT_A - 1) / DT_A), nsplit);
   if (int rc = range_join_launch<false>(ix, st, A, grid)) return rc;
   hipLaunchKernelGGL(range_join_scan_kernel, dim3(1), dim3(1024), 0, st, A.counts, (uint64_t)slots, const_cast<uint64_t*>(A.pos));
   PANN_HIP(hipGetLastError());
@@ -519,7 +439,7 @@ int range_join_fill_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, co
   if (nq == 0) return PANN_OK;
   RangeJoinArgs A = range_join_args(ix, ws, d_q, q_stride, nq, radius, nsplit);
   A.out_ids = d_out_ids;
-  const dim3 grid((uint32_t)((nq + RJ_A - 1) / RJ_A), nsplit);
+  const dim3 grid((uint32_t)((nq + DT_A - 1) / DT_A), nsplit);
   return range_join_launch<true>(ix, st, A, grid);
 }
 

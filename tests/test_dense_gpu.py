@@ -3,13 +3,15 @@ distances) against the CPU oracle; integer-valued data, so results are bit-exact
 import numpy as np
 import pytest
 
-from parlayann_amd import DeviceIndex, datasets
+from parlayann_amd import DeviceIndex, bfloat16, datasets, to_bf16
 
 pytestmark = pytest.mark.gpu
 
 
 def _mk(n, d, dtype, seed=1234):
     X = datasets.sift_like(n, d, seed=seed, dtype=np.float32)
+    if np.dtype(dtype) == bfloat16:
+        return to_bf16(X)                      # integers up to 255: exact in bfloat16
     return (X - 128).clip(-127, 127).astype(np.int8) if dtype == np.int8 else X.astype(dtype)
 
 
@@ -108,6 +110,25 @@ def test_bruteforce_register_list_kernel_valu_types(oracle, dtype, metric, d, k,
     oi, od = oracle.bruteforce_knn(X, Q, k, metric=metric)
     np.testing.assert_array_equal(oi, gi)
     np.testing.assert_array_equal(od, gd)
+    ix.close()
+
+
+@pytest.mark.parametrize("dtype,metric,d,k", [(np.float16, "l2", 132, 10), (np.float16, "mips", 132, 40), (np.float32, "l2", 130, 10),
+                                              (np.float32, "l2", 130, 40), (bfloat16, "l2", 100, 40)])
+def test_bruteforce_unaligned_query_rows(oracle, dtype, metric, d, k):
+    """The query rows are packed at d x esize bytes -- 264, 520 and 200 here -- so every odd row starts 8 bytes off a 16-byte
+    boundary: the unaligned path of the tile kernels' row loader.  f16 d = 132: dense_topk_mfma_f16_kernel, two segments, lane
+    lists (k = 10) and LDS lists (k = 40); f32 d = 130: dense_topk_kernel, three segments; bf16 d = 100: dense_gt_mfma_kernel.
+    Two query tiles, the second partial; n a multiple of neither 64 nor 128."""
+    n, nq = 700, 70
+    X = _mk(n, d, dtype)
+    Q = _mk(nq, d, dtype, seed=4321)
+    assert Q.flags.c_contiguous and (Q.strides[0] % 16) == 8
+    ix = DeviceIndex(X, max_degree=8, metric=metric)
+    gi, gd = ix.bruteforce_knn(Q, k)
+    oi, od = oracle.bruteforce_knn(X, Q, k, metric=metric)
+    np.testing.assert_array_equal(oi, gi)
+    np.testing.assert_array_equal(od.view(np.uint32), gd.view(np.uint32))
     ix.close()
 
 

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import float_cases as fc
-from parlayann_amd import DeviceIndex, PannError, _capi, datasets, io
+from parlayann_amd import DeviceIndex, PannError, _capi, bfloat16, datasets, io, to_bf16
 from parlayann_amd.recall import range_recall
 
 pytestmark = pytest.mark.gpu
@@ -74,6 +74,31 @@ def test_integer_types_equal_int64_brute_force(dtype, metric, d):
     off, ids = ix.bruteforce_range(Q, float(Df.max()) + 1.0)                    # above every distance
     np.testing.assert_array_equal(off, np.arange(nq + 1, dtype=np.uint64) * n)
     np.testing.assert_array_equal(ids.reshape(nq, n), np.broadcast_to(np.arange(n, dtype=np.uint32), (nq, n)))
+    ix.close()
+
+
+# ---- 1b. two-byte floats on the matrix cores, unaligned query rows -----------------------------------------------------------
+@pytest.mark.parametrize("d", [100, 132])
+@pytest.mark.parametrize("metric", ["l2", "mips"])
+@pytest.mark.parametrize("dtype", [np.float16, bfloat16], ids=["f16", "bf16"])
+def test_two_byte_floats_unaligned_query_rows(dtype, metric, d):
+    """range_join_mfma_kernel, one (d = 100) and two (d = 132) segments; the query rows are packed at 200 / 264 bytes, so every
+    odd row starts 8 bytes off a 16-byte boundary.  Values are integers in 0..15: every product and every sum is an integer far
+    below 2^24, so the norm form |a|^2 + |b|^2 - 2 a.b is exact in f32 and equals the int64 brute force."""
+    n, nq = 1003, 70
+    rng = np.random.default_rng(1000 + d)
+    Xi, Qi = rng.integers(0, 16, (n, d)), rng.integers(0, 16, (nq, d))
+    cast = (lambda a: to_bf16(a.astype(np.float32))) if np.dtype(dtype) == bfloat16 else (lambda a: a.astype(dtype))
+    X, Q = cast(Xi), cast(Qi)
+    assert Q.flags.c_contiguous and (Q.strides[0] % 16) == 8
+    dot = Qi.astype(np.int64) @ Xi.astype(np.int64).T
+    D = -dot if metric == "mips" else (Qi * Qi).sum(1)[:, None] + (Xi * Xi).sum(1)[None, :] - 2 * dot
+    assert np.abs(D).max() < 2 ** 24
+    r = float(np.median(D))
+    inside = D <= r
+    assert inside.any() and not inside.all()
+    ix = DeviceIndex(X, max_degree=4, metric=metric)
+    _check_csr(ix.bruteforce_range(Q, r), inside, f"{metric} d={d} r={r}")
     ix.close()
 
 

@@ -3,7 +3,9 @@
 (default beam_search.o) the code objects are unbundled (check_kernel_regs.unbundle), disassembled, and compared kernel by
 kernel: the instruction text with the addresses stripped, and the metadata note (registers, scratch, spills, LDS, kernarg size).
 It only compares two listings; it knows nothing about particular instructions.
-usage: tools/compare_kernels.py BUILD_DIR_A BUILD_DIR_B [object ...]; exit status 1 on any difference"""
+usage: tools/compare_kernels.py [--diff N] BUILD_DIR_A BUILD_DIR_B [object ...]; exit status 1 on any difference
+--diff N also prints the first N lines of a unified diff of every kernel whose code differs"""
+import difflib
 import os
 import re
 import subprocess
@@ -41,7 +43,7 @@ def listing(obj):
     return names, code, meta
 
 
-def compare(a, b):
+def compare(a, b, ndiff=0):
     sa, ca, ma = listing(a)
     sb, cb, mb = listing(b)
     print(f"{os.path.basename(a)}: {len(sa)} symbols / {len(ma)} kernels in A, {len(sb)} symbols / {len(mb)} kernels in B")
@@ -58,6 +60,9 @@ def compare(a, b):
         if what:
             diff += 1
             print(f"DIFFERENT   {k}: " + "; ".join(what))
+            if ndiff and ca.get(k) != cb.get(k):
+                for line in list(difflib.unified_diff(ca.get(k, []), cb.get(k, []), "A", "B", n=2, lineterm=""))[:ndiff]:
+                    print("    " + line)
         else:
             same += 1
     print(f"compare_kernels: {same} identical, {diff} different, {len(only_a)} only in A, {len(only_b)} only in B")
@@ -65,11 +70,15 @@ def compare(a, b):
 
 
 def main():
-    if len(sys.argv) < 3:
+    args = sys.argv[1:]
+    ndiff = 0
+    if args[:1] == ["--diff"] and len(args) >= 2:
+        ndiff, args = int(args[1]), args[2:]
+    if len(args) < 2:
         print(__doc__)
         return 2
-    objs = sys.argv[3:] or ["beam_search.o"]
-    bad = sum(compare(os.path.join(sys.argv[1], o), os.path.join(sys.argv[2], o)) for o in objs)
+    objs = args[2:] or ["beam_search.o"]
+    bad = sum(compare(os.path.join(args[0], o), os.path.join(args[1], o), ndiff) for o in objs)
     return 1 if bad else 0
 
 
