@@ -783,6 +783,52 @@ int pann_labels_to_allow_dev(pann_index* idx, int kind, const pann_label_pred* d
 int pann_label_count_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_counts,
                          void* stream);
 
+/* ---- exact kNN by predicate group: many queries, few distinct filters (DESIGN.md "Exact kNN by predicate group") ----
+ * This project's own.  The call gives a TABLE of G >= 1 filters -- `npreds` predicates of one kind over the handle's labels, or
+ * `nrows` bitmap rows allow_stride_words >= ceil(n / 32) apart (0 is allowed for one row) -- and one table index per query
+ * (group_of_query / row_of_query, nq x uint32, each < G).
+ * THE RULE: row q of the result is, field for field and bit for bit, what pann_bruteforce_knn_labeled with the ONE predicate
+ * preds[group_of_query[q]] (pann_bruteforce_knn_masked with the ONE shared bitmap row row_of_query[q]) returns for query q: the
+ * min(k, c) nearest allowed points sorted by (dist, id), c = the points the filter allows, then 0xFFFFFFFF / +inf;
+ * out_counts[q] (optional) = min(k, c); a filter that allows nothing is an answer, not an error.  k <= 128 for any G.  Table
+ * entries that no query names and entries that repeat a filter are allowed.  G == nq with all filters different is correct but
+ * does the work of the per-query scan with more steps: the grouped call pays off when many queries share few filters.
+ * How: the queries are sorted by table index on the device, every used entry is compacted into its ascending id list, the lists
+ * of a chunk of entries lie one after the other, and ONE segmented launch of the dense kernels of pann_bruteforce_knn scores
+ * every entry's queries against that entry's list ("gt_pieces" is honoured); the rows then go back to the caller's order.
+ * max_list_ids bounds the ids materialised at once: table entries are processed in chunks of consecutive used entries whose
+ * lists together hold at most max_list_ids ids (with predicates also: whose bitmap rows, expanded into scratch, hold at most
+ * max_list_ids words); an entry whose own list is longer (<= n ids) is a chunk alone.  0 = the default, 16 Mi ids: 64 MB of ids
+ * and, with predicates, as much of rows.  Results never depend on it.
+ * Status: everything the twins refuse keeps its code (a four-bit handle, k > 128 -> PANN_ERR_UNSUPPORTED; k == 0, no labels, an
+ * unknown kind, NULL or misaligned preds, NULL queries / outputs / bitmap, a short query stride -> PANN_ERR_BAD_ARG); an empty
+ * table, a NULL index array, a bitmap stride below ceil(n / 32), a table index >= G -> PANN_ERR_BAD_ARG; nq == 0 -> PANN_OK.
+ * Nothing is written on an error.
+ * Host pointers: the table indices are checked on the host; index array, table and queries go up in one transfer, the outputs
+ * come back in one (HostTrip, as the twins). */
+int pann_bruteforce_knn_labeled_grouped(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                        int kind, const pann_label_pred* preds, uint64_t npreds, const uint32_t* group_of_query,
+                                        uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts);
+int pann_bruteforce_knn_masked_grouped(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                       const uint32_t* allow, uint64_t nrows, uint64_t allow_stride_words,
+                                       const uint32_t* row_of_query, uint64_t max_list_ids, uint32_t* out_ids, float* out_dists,
+                                       uint32_t* out_counts);
+/* Device pointers throughout, launched on `stream`.  SYNCHRONISES the stream ONCE, as the shared route of
+ * pann_bruteforce_knn_masked_dev does: the flag of the range check, the number of queries per table entry and the number of
+ * allowed points per table entry come back in that one read, and the host plans the chunks, segments and tiles from them; the
+ * plan goes up and everything after it is enqueued without another wait.  A table index >= G is detected by the grouping pass on
+ * the device and reported as PANN_ERR_BAD_ARG after that synchronisation, with no output written.  Grows the handle's scratch
+ * on first use (the sorted queries, a chunk's lists and rows, a chunk's queries and staged results); one call per handle at a
+ * time. */
+int pann_bruteforce_knn_labeled_grouped_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                            int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                                            const uint32_t* d_group_of_query, uint64_t max_list_ids, uint32_t* d_out_ids,
+                                            float* d_out_dists, uint32_t* d_out_counts, void* stream);
+int pann_bruteforce_knn_masked_grouped_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                           const uint32_t* d_allow, uint64_t nrows, uint64_t allow_stride_words,
+                                           const uint32_t* d_row_of_query, uint64_t max_list_ids, uint32_t* d_out_ids,
+                                           float* d_out_dists, uint32_t* d_out_counts, void* stream);
+
 /* ---- subset index: carve out, compact or grow a handle on the device (DESIGN.md "Subset index") ----  This project's own.
  * A new handle over the rows of src that a bitmap keeps, in ascending id order, with room for n_out rows; the graph is
  * renumbered, labels and sketch are carried over, nothing leaves the device.  Compaction after pann_vamana_delete_batch (the

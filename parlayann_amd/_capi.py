@@ -242,6 +242,16 @@ SIGNATURES = {
                                                   C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pann_labels_to_allow_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pann_label_count_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pann_bruteforce_knn_labeled_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p,
+                                                      C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_bruteforce_knn_labeled_grouped_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int,
+                                                          C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                          C.c_void_p, C.c_void_p]),
+    "pann_bruteforce_knn_masked_grouped": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                     C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_bruteforce_knn_masked_grouped_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
+                                                         C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p]),
     "pann_index_create_subset_dev": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                                C.c_uint64, C.c_void_p, u64p]),
     "pann_index_create_subset": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,

@@ -79,6 +79,10 @@ struct pann_index {
   pann_sketch_params sk_params{};   // ... and the parameters it was made with (the fused rerank sketches its queries with them)
   Workspace labels_buf;         // one label word per point (pann_index_set_labels): ix.labels points into it
   Workspace label_row;          // pann_bruteforce_knn_labeled*, one predicate: its bitmap row, expanded on the device
+  // pann_bruteforce_knn_*_grouped* (grouped_knn_run): the sorted queries and counts; the plan; a chunk's bitmap rows and block
+  // counts; a chunk's query slab and staged results; the read-back and the plan on the host
+  Workspace grp_sort, grp_plan, grp_rows, grp_io;
+  PinnedBuf grp_pin;
 };
 
 namespace {
@@ -466,6 +470,7 @@ void pann_index_destroy(pann_index* idx) {
   idx->pivot_rows.release(); idx->pivot_dists.release(); idx->params_scratch.release();
   idx->code_rank.release(); idx->code_rows.release(); idx->cell_buf.release();
   idx->sketch_buf.release(); idx->labels_buf.release(); idx->label_row.release();
+  idx->grp_sort.release(); idx->grp_plan.release(); idx->grp_rows.release(); idx->grp_io.release(); idx->grp_pin.release();
   if (idx->own_stream) (void)hipStreamDestroy(idx->own_stream);
   delete idx;
 }
@@ -1421,6 +1426,227 @@ int pann_label_count_dev(pann_index* idx, int kind, const pann_label_pred* d_pre
   if (int rc = label_helper_checks(idx, "pann_label_count_dev", kind, d_preds, d_counts)) return rc;
   DeviceGuard g(idx->device);
   return label_count_dev(idx->ix.labels, idx->ix.n, kind, d_preds, npreds, d_counts, (hipStream_t)stream);
+}
+
+// ---- exact kNN by predicate group (masked_knn.hip, DESIGN.md "Exact kNN by predicate group") ----
+
+constexpr uint64_t kGroupedListIds = 16ull << 20;      // max_list_ids == 0 (include/pann.h): 64 MB of ids, as much again of bitmap rows
+
+// the filter table of a grouped call on the device: predicates over the handle's labels (d_preds) or bitmap rows (d_allow)
+struct GroupedTable {
+  int kind; const pann_label_pred* d_preds;
+  const uint32_t* d_allow; uint64_t stride;
+  uint64_t G; const uint32_t* d_group; uint64_t max_list_ids;
+};
+
+// what is refused before anything is launched, beyond the twin's own checks (masked_knn_checks, called with one filter: k <= 128)
+static int grouped_checks(const pann_index* idx, const char* fn, uint64_t G, const uint32_t* group, const uint32_t* allow, uint64_t stride) {
+  const std::string f = fn;
+  if (G == 0) { set_error(f + ": an empty filter table"); return PANN_ERR_BAD_ARG; }
+  if (G > 0xFFFFFFFFull) { set_error(f + ": more than 2^32 - 1 table entries"); return PANN_ERR_BAD_ARG; }
+  if (!group) { set_error(f + ": null index array"); return PANN_ERR_BAD_ARG; }
+  if (allow && stride < (idx->ix.n + 31) / 32 && !(stride == 0 && G == 1)) {
+    set_error(f + ": allow_stride_words must be at least ceil(n / 32) = " + std::to_string((idx->ix.n + 31) / 32));
+    return PANN_ERR_BAD_ARG;
+  }
+  return PANN_OK;
+}
+
+// One chunk of the plan: the used table entries [u0, u1) as the segments of one dense launch.
+struct GroupedChunk { size_t u0, u1; uint64_t a_base, na, ids, max_ids; uint32_t ntiles; size_t o_aoff, o_boff, o_tseg, o_ta0; };
+
+// Everything on device pointers, after the checks.  SYNCHRONISES st once: the flag of the range check, the queries per table entry
+// and the allowed points per table entry come back in one read, and the chunks, segments and tiles are planned from them.
+static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                           const GroupedTable& T, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+  const DeviceIndex& ix = idx->ix;
+  const uint64_t G = T.G, words = (ix.n + 31) / 32, stride = T.stride ? T.stride : words;
+  const bool lab = T.d_preds != nullptr;
+  // ---- before the read-back: sort the queries by table index, count what every entry allows ----
+  uint32_t nblocks; uint64_t per_block;
+  group_sort_shape(nq, G, &nblocks, &per_block);
+  const size_t head_words = 1 + 2 * (size_t)G;       // flag | queries per entry | allowed points per entry
+  if (int rc = idx->grp_sort.ensure((head_words + (size_t)G + 1 + (size_t)nblocks * G + (size_t)nq) * 4)) return rc;
+  uint32_t* d_head = idx->grp_sort.as<uint32_t>();
+  uint32_t* d_hist = d_head + 1, *d_allowed = d_hist + G, *d_off = d_allowed + G, *d_part = d_off + G + 1, *d_perm = d_part + (size_t)nblocks * G;
+  if (int rc = group_queries_dev(T.d_group, nq, G, d_head, d_hist, d_off, d_part, d_perm, st)) return rc;
+  if (lab) { if (int rc = label_count_dev(ix.labels, ix.n, T.kind, T.d_preds, G, d_allowed, st)) return rc; }
+  else if (int rc = allow_count_dev(T.d_allow, ix.n, G, stride, d_allowed, st)) return rc;
+  if (int rc = idx->grp_pin.ensure(head_words * 4)) return rc;
+  PANN_HIP(hipMemcpyAsync(idx->grp_pin.p, d_head, head_words * 4, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  const std::vector<uint32_t> head((const uint32_t*)idx->grp_pin.p, (const uint32_t*)idx->grp_pin.p + head_words);
+  if (head[0]) { set_error(std::string(fn) + ": a query's table index is out of range (>= " + std::to_string(G) + ")"); return PANN_ERR_BAD_ARG; }
+  const uint32_t* hist = head.data() + 1, *allowed = hist + G;
+
+  // ---- the plan: chunks of consecutive used entries whose lists fit the budget; an entry larger than it is a chunk alone ----
+  const uint64_t budget = std::min<uint64_t>(T.max_list_ids ? T.max_list_ids : kGroupedListIds, 0x7FFFFFFFull);
+  const uint64_t row_cap = lab ? std::max<uint64_t>(1, budget / std::max<uint64_t>(words, 1)) : UINT64_MAX;   // label form: the rows' words fit it too
+  std::vector<uint32_t> used;
+  std::vector<uint64_t> first;                        // first slot of every used entry (the scan of hist), and nq behind them
+  { uint64_t run = 0; for (uint64_t g = 0; g < G; g++) if (hist[g]) { used.push_back((uint32_t)g); first.push_back(run); run += hist[g]; } first.push_back(run); }
+  const size_t U = used.size();
+  auto al8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
+  size_t plan_bytes = al8(U * 4);
+  std::vector<GroupedChunk> chunks;
+  for (size_t u = 0; u < U;) {
+    GroupedChunk c{u, u, first[u], 0, 0, 0, 0, 0, 0, 0, 0};
+    while (c.u1 < U && (c.u1 == c.u0 || (c.ids + allowed[used[c.u1]] <= budget && c.u1 - c.u0 < row_cap))) {
+      const uint64_t cg = allowed[used[c.u1]];
+      c.ids += cg; c.max_ids = std::max(c.max_ids, cg);
+      c.ntiles += (uint32_t)((hist[used[c.u1]] + 63) / 64);
+      c.u1++;
+    }
+    c.na = first[c.u1] - c.a_base;
+    const size_t S = c.u1 - c.u0;
+    c.o_aoff = plan_bytes; c.o_boff = c.o_aoff + (S + 1) * 8; c.o_tseg = c.o_boff + (S + 1) * 8; c.o_ta0 = c.o_tseg + al8((size_t)c.ntiles * 4);
+    plan_bytes = c.o_ta0 + al8((size_t)c.ntiles * 4);
+    chunks.push_back(c);
+    u = c.u1;
+  }
+  if (int rc = idx->grp_pin.ensure(plan_bytes)) return rc;      // (the read-back has been copied out of it)
+  uint8_t* hp = (uint8_t*)idx->grp_pin.p;
+  memcpy(hp, used.data(), U * 4);
+  size_t max_rows = 0, max_na = 0; uint64_t max_ids = 0;
+  for (const GroupedChunk& c : chunks) {
+    uint64_t* a_off = (uint64_t*)(hp + c.o_aoff), *b_off = (uint64_t*)(hp + c.o_boff);
+    uint32_t* tseg = (uint32_t*)(hp + c.o_tseg), *ta0 = (uint32_t*)(hp + c.o_ta0);
+    uint64_t b = 0; uint32_t t = 0;
+    for (size_t u = c.u0; u < c.u1; u++) {
+      const size_t s = u - c.u0;
+      a_off[s] = first[u] - c.a_base; b_off[s] = b;
+      b += allowed[used[u]];
+      for (uint64_t a = a_off[s]; a < first[u + 1] - c.a_base; a += 64) { tseg[t] = (uint32_t)s; ta0[t] = (uint32_t)a; t++; }
+    }
+    a_off[c.u1 - c.u0] = c.na; b_off[c.u1 - c.u0] = b;
+    max_rows = std::max(max_rows, c.u1 - c.u0); max_na = std::max<size_t>(max_na, c.na); max_ids = std::max(max_ids, c.ids);
+  }
+  // ---- device room for the largest chunk, then the plan goes up in one transfer ----
+  const uint32_t a_stride = (ix.dbytes + 15) / 16 * 16;
+  const size_t o_upreds = (plan_bytes + 255) & ~(size_t)255;
+  if (int rc = idx->grp_plan.ensure(o_upreds + (lab ? U * sizeof(pann_label_pred) : 0))) return rc;
+  const size_t o_bc = lab ? (max_rows * words * 4 + 255) & ~(size_t)255 : 0;
+  if (int rc = idx->grp_rows.ensure(o_bc + allow_rows_compact_scratch_bytes(ix.n, max_rows))) return rc;
+  if (int rc = idx->ws4.ensure(std::max<size_t>(max_ids, 1) * 4)) return rc;
+  const size_t o_sids = (max_na * a_stride + kQuerySlack + 255) & ~(size_t)255, o_sdists = o_sids + ((max_na * k * 4 + 255) & ~(size_t)255);
+  if (int rc = idx->grp_io.ensure(o_sdists + max_na * k * 4)) return rc;
+  uint8_t* dp = idx->grp_plan.as<uint8_t>();
+  PANN_HIP(hipMemcpyAsync(dp, hp, plan_bytes, hipMemcpyHostToDevice, st));
+  const uint32_t* d_used = (const uint32_t*)dp;
+  pann_label_pred* d_upreds = (pann_label_pred*)(dp + o_upreds);
+  if (lab) { if (int rc = gather_preds_dev(T.d_preds, d_used, U, d_upreds, st)) return rc; }
+  uint32_t* d_rows = idx->grp_rows.as<uint32_t>();
+  uint32_t* d_bc = (uint32_t*)(idx->grp_rows.as<uint8_t>() + o_bc);
+  uint32_t* d_list = idx->ws4.as<uint32_t>();
+  uint8_t* d_slab = idx->grp_io.as<uint8_t>();
+  uint32_t* d_sids = (uint32_t*)(d_slab + o_sids);
+  float* d_sdists = (float*)(d_slab + o_sdists);
+  // ---- per chunk: id lists (CSR), query slab, ONE segmented dense launch, rows back to the caller's order ----
+  for (const GroupedChunk& c : chunks) {
+    const uint32_t S = (uint32_t)(c.u1 - c.u0);
+    if (c.ids) {
+      if (lab) {
+        if (int rc = labels_to_allow_dev(ix.labels, ix.n, T.kind, d_upreds + c.u0, S, d_rows, words, st)) return rc;
+        if (int rc = allow_rows_compact_dev(d_rows, ix.n, nullptr, words, S, d_bc, d_list, (uint32_t)c.ids, st)) return rc;
+      } else if (int rc = allow_rows_compact_dev(T.d_allow, ix.n, d_used + c.u0, stride, S, d_bc, d_list, (uint32_t)c.ids, st)) return rc;
+    }
+    if (int rc = gather_query_rows_dev(d_q, q_stride_bytes, ix.dbytes, d_perm + c.a_base, c.na, d_slab, a_stride, st)) return rc;
+    // the lists as B rows: the LDS-list kernels, one workgroup per CU (as masked_knn_run); the pieces cut every segment's list
+    const uint32_t nsplit = choose_gt_pieces(idx, c.ntiles, 256.0, c.max_ids);
+    if (int rc = dense_topk_dev(ix, idx->ws2, st, d_slab, a_stride, nullptr, d_list, (const uint64_t*)(dp + c.o_aoff),
+                                (const uint64_t*)(dp + c.o_boff), (const uint32_t*)(dp + c.o_tseg), (const uint32_t*)(dp + c.o_ta0),
+                                c.ntiles, c.na, c.ids, nsplit, k, 0, d_sids, d_sdists)) return rc;
+    if (int rc = scatter_knn_rows_dev(d_sids, d_sdists, d_perm + c.a_base, c.na, k, d_ids, d_dists, d_counts, st)) return rc;
+  }
+  return PANN_OK;
+}
+
+int pann_bruteforce_knn_labeled_grouped_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                            int kind, const pann_label_pred* d_preds, uint64_t npreds, const uint32_t* d_group_of_query,
+                                            uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                            void* stream) {
+  const char* fn = "pann_bruteforce_knn_labeled_grouped_dev";
+  bool done;
+  const LabelArgs l{kind, d_preds, 1};           // (the twin's checks with one filter: k <= 128)
+  if (int rc = masked_knn_checks(idx, fn, d_queries, nq, q_stride_bytes, k, nullptr, 0, d_out_ids, d_out_dists, &done, &l, true)) return rc;
+  if (done) return PANN_OK;
+  if (int rc = grouped_checks(idx, fn, npreds, d_group_of_query, nullptr, 0)) return rc;
+  DeviceGuard g(idx->device);
+  const GroupedTable T{kind, d_preds, nullptr, 0, npreds, d_group_of_query, max_list_ids};
+  return grouped_knn_run(idx, fn, (const uint8_t*)d_queries, nq, q_stride_bytes, k, T, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream);
+}
+
+int pann_bruteforce_knn_masked_grouped_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                           const uint32_t* d_allow, uint64_t nrows, uint64_t allow_stride_words,
+                                           const uint32_t* d_row_of_query, uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists,
+                                           uint32_t* d_out_counts, void* stream) {
+  const char* fn = "pann_bruteforce_knn_masked_grouped_dev";
+  bool done;
+  if (int rc = masked_knn_checks(idx, fn, d_queries, nq, q_stride_bytes, k, d_allow, 0, d_out_ids, d_out_dists, &done)) return rc;
+  if (done) return PANN_OK;
+  if (int rc = grouped_checks(idx, fn, nrows, d_row_of_query, d_allow, allow_stride_words)) return rc;
+  DeviceGuard g(idx->device);
+  const GroupedTable T{0, nullptr, d_allow, allow_stride_words, nrows, d_row_of_query, max_list_ids};
+  return grouped_knn_run(idx, fn, (const uint8_t*)d_queries, nq, q_stride_bytes, k, T, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream);
+}
+
+// the host entries check the index array on the host: nothing is staged for a call that will be refused
+static int grouped_index_check(const char* fn, const uint32_t* group, uint64_t nq, uint64_t G) {
+  for (uint64_t q = 0; q < nq; q++)
+    if (group[q] >= G) {
+      set_error(std::string(fn) + ": table index " + std::to_string(group[q]) + " of query " + std::to_string(q) + " is out of range (>= " + std::to_string(G) + ")");
+      return PANN_ERR_BAD_ARG;
+    }
+  return PANN_OK;
+}
+
+int pann_bruteforce_knn_labeled_grouped(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int kind,
+                                        const pann_label_pred* preds, uint64_t npreds, const uint32_t* group_of_query,
+                                        uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts) {
+  const char* fn = "pann_bruteforce_knn_labeled_grouped";
+  bool done;
+  const LabelArgs l{kind, preds, 1};
+  if (int rc = masked_knn_checks(idx, fn, queries, nq, q_stride_bytes, k, nullptr, 0, out_ids, out_dists, &done, &l, false)) return rc;
+  if (done) return PANN_OK;
+  if (int rc = grouped_checks(idx, fn, npreds, group_of_query, nullptr, 0)) return rc;
+  if (int rc = grouped_index_check(fn, group_of_query, nq, npreds)) return rc;
+  DeviceGuard g(idx->device);
+  // in: the index array, the table and the queries in one transfer; out: as pann_bruteforce_knn_masked
+  HostTrip t(idx);
+  const int i_grp = t.in.add(group_of_query, (size_t)nq * 4), i_pred = t.in.add(preds, (size_t)npreds * sizeof(pann_label_pred));
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
+  const size_t row_bytes = (size_t)nq * k * 4;
+  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
+  if (int rc = t.begin()) return rc;
+  const GroupedTable T{kind, t.din<pann_label_pred>(i_pred), nullptr, 0, npreds, t.din<uint32_t>(i_grp), max_list_ids};
+  if (int rc = grouped_knn_run(idx, fn, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, T, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists),
+                               t.dout<uint32_t>(o_counts), t.st)) return rc;
+  return t.finish();
+}
+
+int pann_bruteforce_knn_masked_grouped(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                       const uint32_t* allow, uint64_t nrows, uint64_t allow_stride_words, const uint32_t* row_of_query,
+                                       uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts) {
+  const char* fn = "pann_bruteforce_knn_masked_grouped";
+  bool done;
+  if (int rc = masked_knn_checks(idx, fn, queries, nq, q_stride_bytes, k, allow, 0, out_ids, out_dists, &done)) return rc;
+  if (done) return PANN_OK;
+  if (int rc = grouped_checks(idx, fn, nrows, row_of_query, allow, allow_stride_words)) return rc;
+  if (int rc = grouped_index_check(fn, row_of_query, nq, nrows)) return rc;
+  DeviceGuard g(idx->device);
+  // in: the index array, the rows packed to ceil(n / 32) words each and the queries in one transfer
+  HostTrip t(idx);
+  const size_t mwords = (size_t)((idx->ix.n + 31) / 32);
+  const int i_grp = t.in.add(row_of_query, (size_t)nq * 4);
+  const int i_mask = t.in.add_rows(allow, (size_t)nrows, mwords * 4, (size_t)(allow_stride_words ? allow_stride_words : mwords) * 4);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
+  const size_t row_bytes = (size_t)nq * k * 4;
+  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
+  if (int rc = t.begin()) return rc;
+  const GroupedTable T{0, nullptr, t.din<uint32_t>(i_mask), mwords, nrows, t.din<uint32_t>(i_grp), max_list_ids};
+  if (int rc = grouped_knn_run(idx, fn, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, T, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists),
+                               t.dout<uint32_t>(o_counts), t.st)) return rc;
+  return t.finish();
 }
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,

@@ -13,12 +13,20 @@
 //
 // allow_count_kernel (pann_allow_count_dev) is the count half alone, per row.
 //
+// Grouped route (DESIGN.md "Exact kNN by predicate group"): a table of G filters and one table index per query.
+//   group_hist_kernel / group_colscan_kernel / group_place_kernel   stable counting sort of the queries by table index: the
+//                                                 queries of a table entry one after the other, ascending inside an entry
+//   the compaction kernels above with rows on grid.y      the ascending id list of every used entry of a chunk, one after the
+//                                                 other (CSR): the b_ids / b_off of ONE segmented dense_topk_dev launch
+//   gather_query_rows_kernel / scatter_knn_rows_kernel    the queries into a slab in group order (its external A rows), the
+//                                                 result rows back into the caller's order
+//
 // Label predicates (DESIGN.md "Label predicates"): one uint32 label per point and a two-word predicate per query stand for the
 // bitmap row { i : pred(label[i]) }.
 //   labels_to_allow_kernel   materialises such rows in the bitmap format (the bridge to everything above)
 //   label_count_kernel       counts them without materialising anything
 //   masked_scan_kernel<.., LABELS = true>   the per-query scan with its 64 words per step built from 2 048 labels
-#include "pann_device.h"
+#include "dense_tile.h"
 
 namespace pann {
 namespace {
@@ -76,13 +84,23 @@ __global__ void __launch_bounds__(MK_BLOCK) allow_count_kernel(const uint32_t* _
   }
 }
 
+// Row r (blockIdx.y, striding over `rows`) is row rowidx[r] (null: r) of `allow`, rows `stride` words apart; its block b writes
+// block_counts[r * gridDim.x + b].  One bitmap: rows = 1, rowidx = null.
+__device__ __forceinline__ const uint32_t* compact_row(const uint32_t* __restrict__ allow, const uint32_t* __restrict__ rowidx,
+                                                       uint64_t stride, uint32_t r) {
+  return allow + (uint64_t)(rowidx ? rowidx[r] : r) * stride;
+}
 __global__ void __launch_bounds__(MK_BLOCK) allow_block_count_kernel(const uint32_t* __restrict__ allow, uint64_t n,
+                                                                     const uint32_t* __restrict__ rowidx, uint64_t stride, uint32_t rows,
                                                                      uint32_t* __restrict__ block_counts) {
   __shared__ uint32_t wsum[MK_BLOCK / PANN_WAVE];
   const uint64_t words = (n + 31) / 32;
-  uint32_t total;
-  (void)block_excl_scan(__popc(allow_word(allow, (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x, words, n)), wsum, &total);
-  if (threadIdx.x == 0) block_counts[blockIdx.x] = total;
+  for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    uint32_t total;
+    (void)block_excl_scan(__popc(allow_word(compact_row(allow, rowidx, stride, r), (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x, words, n)),
+                          wsum, &total);
+    if (threadIdx.x == 0) block_counts[(uint64_t)r * gridDim.x + blockIdx.x] = total;
+  }
 }
 
 // block_counts[0 .. nblk) -> their exclusive prefix sums, in place; block_counts[nblk] = the total.  One workgroup.
@@ -99,22 +117,26 @@ __global__ void __launch_bounds__(MK_BLOCK) allow_block_scan_kernel(uint32_t* __
   if (threadIdx.x == 0) block_counts[nblk] = carry;
 }
 
-// ids[rank of bit] = position of the bit, for every set bit below n: ascending.  cap: entries of ids (the total of the scan)
+// ids[rank of bit] = position of the bit, for every set bit below n: ascending.  cap: entries of ids (the total of the scan).
+// Rows as allow_block_count_kernel: block_off is the scan over all rows' blocks, so the lists lie one after the other.
 __global__ void __launch_bounds__(MK_BLOCK) allow_scatter_kernel(const uint32_t* __restrict__ allow, uint64_t n,
+                                                                 const uint32_t* __restrict__ rowidx, uint64_t stride, uint32_t rows,
                                                                  const uint32_t* __restrict__ block_off, uint32_t* __restrict__ ids,
                                                                  uint32_t cap) {
   __shared__ uint32_t wsum[MK_BLOCK / PANN_WAVE];
   const uint64_t words = (n + 31) / 32;
   const uint64_t w = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
-  uint32_t v = allow_word(allow, w, words, n);
-  uint32_t total;
-  uint32_t pos = block_off[blockIdx.x] + block_excl_scan(__popc(v), wsum, &total);
-  const uint32_t first = (uint32_t)(w * 32);
-  while (v) {
-    const uint32_t j = __ffs(v) - 1;
-    v &= v - 1;
-    if (pos < cap) ids[pos] = first + j;
-    pos++;
+  for (uint32_t r = blockIdx.y; r < rows; r += gridDim.y) {
+    uint32_t v = allow_word(compact_row(allow, rowidx, stride, r), w, words, n);
+    uint32_t total;
+    uint32_t pos = block_off[(uint64_t)r * gridDim.x + blockIdx.x] + block_excl_scan(__popc(v), wsum, &total);
+    const uint32_t first = (uint32_t)(w * 32);
+    while (v) {
+      const uint32_t j = __ffs(v) - 1;
+      v &= v - 1;
+      if (pos < cap) ids[pos] = first + j;
+      pos++;
+    }
   }
 }
 
@@ -289,7 +311,177 @@ __global__ void __launch_bounds__(PANN_WAVE) masked_scan_kernel(MaskedScanArgs P
 
 inline uint32_t compaction_blocks(uint64_t n) { return (uint32_t)(((n + 31) / 32 + MK_BLOCK - 1) / MK_BLOCK); }
 
+// ---- grouped route: the queries sorted by table index, stably ----
+// A counting sort in three kernels.  Workgroup b owns the queries [b * per_block, (b + 1) * per_block), per_block a multiple of
+// GQ_TILE, and row b of `part` (G words, zeroed by the caller):
+//   group_hist_kernel     part[b][g] = queries of entry g in b's range; an index >= G raises *flag and is left out
+//   group_colscan_kernel  part[b][g] <- the queries of g in the ranges before b; hist[g] = off[g] = all of them
+//   (allow_block_scan_kernel turns off[0 .. G] into the first slot of every entry)
+//   group_place_kernel    b walks its range a tile at a time: a query's slot is off[g] + part[b][g] + the queries of g before it
+//                         in the tile; the last query of g in the tile adds the tile's share to part[b][g] for the next tile
+constexpr uint32_t GQ_TILE = MK_BLOCK;
+
+__global__ void __launch_bounds__(MK_BLOCK) group_hist_kernel(const uint32_t* __restrict__ group, uint64_t nq, uint64_t G,
+                                                              uint64_t per_block, uint32_t* __restrict__ part, uint32_t* __restrict__ flag) {
+  const uint64_t lo = (uint64_t)blockIdx.x * per_block, hi = min(nq, lo + per_block);
+  uint32_t* row = part + (uint64_t)blockIdx.x * G;
+  for (uint64_t q = lo + threadIdx.x; q < hi; q += MK_BLOCK) {
+    const uint32_t g = group[q];
+    if (g >= G) atomicOr(flag, 1u);
+    else atomicAdd(&row[g], 1u);
+  }
+}
+
+__global__ void __launch_bounds__(MK_BLOCK) group_colscan_kernel(uint32_t* __restrict__ part, uint64_t G, uint32_t nblocks,
+                                                                 uint32_t* __restrict__ hist, uint32_t* __restrict__ off) {
+  const uint64_t g = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+  if (g >= G) return;
+  uint32_t run = 0;
+  for (uint32_t b = 0; b < nblocks; b++) {
+    const uint32_t c = part[(uint64_t)b * G + g];
+    part[(uint64_t)b * G + g] = run;
+    run += c;
+  }
+  hist[g] = run;
+  off[g] = run;
+}
+
+__global__ void __launch_bounds__(MK_BLOCK) group_place_kernel(const uint32_t* __restrict__ group, uint64_t nq, uint64_t G,
+                                                               uint64_t per_block, uint32_t* __restrict__ part,
+                                                               const uint32_t* __restrict__ off, uint32_t* __restrict__ perm) {
+  __shared__ uint32_t Gs[GQ_TILE];
+  const uint64_t lo = (uint64_t)blockIdx.x * per_block, hi = min(nq, lo + per_block);
+  uint32_t* row = part + (uint64_t)blockIdx.x * G;
+  for (uint64_t t0 = lo; t0 < hi; t0 += GQ_TILE) {
+    const uint64_t q = t0 + threadIdx.x;
+    uint32_t g = q < hi ? group[q] : SENTINEL;
+    if (g >= G) g = SENTINEL;                      // past the range, or refused by group_hist_kernel: no slot
+    __syncthreads();                               // the previous tile has been read, and its shares have been added
+    Gs[threadIdx.x] = g;
+    __syncthreads();
+    uint32_t before = 0, after = 0;
+    if (g != SENTINEL) {
+      for (uint32_t s = 0; s < GQ_TILE; s++) {
+        const bool same = Gs[s] == g;
+        before += (same && s < threadIdx.x) ? 1u : 0u;
+        after += (same && s > threadIdx.x) ? 1u : 0u;
+      }
+      const uint32_t base = __hip_atomic_load(&row[g], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint64_t slot = (uint64_t)off[g] + base + before;
+      if (slot < nq) perm[slot] = (uint32_t)q;
+    }
+    __syncthreads();                               // every query of the tile has read its base
+    if (g != SENTINEL && after == 0) atomicAdd(&row[g], before + 1u);
+  }
+}
+
+// out[u] = preds[used[u]]
+__global__ void __launch_bounds__(MK_BLOCK) gather_preds_kernel(const pann_label_pred* __restrict__ preds, const uint32_t* __restrict__ used,
+                                                                uint64_t m, pann_label_pred* __restrict__ out) {
+  const uint64_t u = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+  if (u < m) out[u] = preds[used[u]];
+}
+
+// slab row r <- the row of query perm[r], as bytes: dbytes of them, zeros up to slab_stride (a multiple of 16).  A thread moves
+// 16 bytes; the query rows may start anywhere.
+__global__ void __launch_bounds__(MK_BLOCK) gather_query_rows_kernel(const uint8_t* __restrict__ q, uint64_t q_stride, uint32_t dbytes,
+                                                                     const uint32_t* __restrict__ perm, uint64_t rows,
+                                                                     uint8_t* __restrict__ slab, uint32_t slab_stride) {
+  const uint32_t cpr = slab_stride / 16;
+  const uint64_t i = (uint64_t)blockIdx.x * MK_BLOCK + threadIdx.x;
+  const uint64_t r = i / cpr;
+  const uint32_t c = (uint32_t)(i % cpr);
+  if (r >= rows) return;
+  const uint4 v = load16_unaligned(q + (uint64_t)perm[r] * q_stride, c * 16, dbytes);
+  *reinterpret_cast<uint4*>(slab + r * slab_stride + (size_t)c * 16) = v;
+}
+
+// row perm[r] of the outputs <- staged row r; counts[perm[r]] = its entries that are not padding.  One wave per row, k <= 128.
+__global__ void __launch_bounds__(PANN_WAVE) scatter_knn_rows_kernel(const uint32_t* __restrict__ sids, const float* __restrict__ sdists,
+                                                                     const uint32_t* __restrict__ perm, uint32_t k,
+                                                                     uint32_t* __restrict__ out_ids, float* __restrict__ out_dists,
+                                                                     uint32_t* __restrict__ out_counts) {
+  const uint64_t r = blockIdx.x, q = perm[r];
+  uint32_t cnt = 0;
+  for (uint32_t j0 = 0; j0 < k; j0 += PANN_WAVE) {
+    const uint32_t j = j0 + threadIdx.x;
+    const uint32_t id = j < k ? sids[r * k + j] : SENTINEL;
+    if (j < k) { out_ids[q * k + j] = id; out_dists[q * k + j] = sdists[r * k + j]; }
+    cnt += (uint32_t)__popcll(__ballot(id != SENTINEL));
+  }
+  if (threadIdx.x == 0 && out_counts) out_counts[q] = cnt;
+}
+
 }  // namespace
+
+void group_sort_shape(uint64_t nq, uint64_t G, uint32_t* nblocks, uint64_t* per_block) {
+  const uint64_t tiles = (nq + GQ_TILE - 1) / GQ_TILE;
+  const uint64_t want = std::max<uint64_t>(1, std::min<uint64_t>(tiles, (1ull << 20) / std::max<uint64_t>(G, 1)));   // `part` stays at 4 MB
+  *per_block = (tiles + want - 1) / want * GQ_TILE;
+  *nblocks = (uint32_t)((nq + *per_block - 1) / *per_block);
+}
+
+int group_queries_dev(const uint32_t* d_group, uint64_t nq, uint64_t G, uint32_t* d_flag, uint32_t* d_hist, uint32_t* d_off,
+                      uint32_t* d_part, uint32_t* d_perm, hipStream_t st) {
+  uint32_t nblocks; uint64_t per_block;
+  group_sort_shape(nq, G, &nblocks, &per_block);
+  PANN_HIP(hipMemsetAsync(d_flag, 0, 4, st));
+  PANN_HIP(hipMemsetAsync(d_part, 0, (size_t)nblocks * G * 4, st));
+  hipLaunchKernelGGL(group_hist_kernel, dim3(nblocks), dim3(MK_BLOCK), 0, st, d_group, nq, G, per_block, d_part, d_flag);
+  PANN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(group_colscan_kernel, dim3((uint32_t)((G + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0, st, d_part, G, nblocks,
+                     d_hist, d_off);
+  PANN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(allow_block_scan_kernel, dim3(1), dim3(MK_BLOCK), 0, st, d_off, (uint32_t)G);
+  PANN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(group_place_kernel, dim3(nblocks), dim3(MK_BLOCK), 0, st, d_group, nq, G, per_block, d_part, d_off, d_perm);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+int gather_preds_dev(const pann_label_pred* d_preds, const uint32_t* d_used, uint64_t m, pann_label_pred* d_out, hipStream_t st) {
+  if (m == 0) return PANN_OK;
+  hipLaunchKernelGGL(gather_preds_kernel, dim3((uint32_t)((m + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0, st, d_preds, d_used, m, d_out);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+size_t allow_rows_compact_scratch_bytes(uint64_t n, uint64_t rows) { return ((size_t)compaction_blocks(n) * rows + 1) * 4; }
+
+int allow_rows_compact_dev(const uint32_t* d_allow, uint64_t n, const uint32_t* d_rowidx, uint64_t stride, uint32_t rows,
+                           uint32_t* d_scratch, uint32_t* d_ids, uint32_t cap, hipStream_t st) {
+  if (rows == 0 || n == 0) return PANN_OK;
+  const uint32_t nblk = compaction_blocks(n);
+  const dim3 grid(nblk, std::min<uint32_t>(rows, 65535));
+  hipLaunchKernelGGL(allow_block_count_kernel, grid, dim3(MK_BLOCK), 0, st, d_allow, n, d_rowidx, stride, rows, d_scratch);
+  PANN_HIP(hipGetLastError());
+  // (grid.y strides over the rows, so the counts of row r lie at r * nblk whatever grid.y is)
+  hipLaunchKernelGGL(allow_block_scan_kernel, dim3(1), dim3(MK_BLOCK), 0, st, d_scratch, nblk * rows);
+  PANN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(allow_scatter_kernel, grid, dim3(MK_BLOCK), 0, st, d_allow, n, d_rowidx, stride, rows, (const uint32_t*)d_scratch, d_ids, cap);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+int gather_query_rows_dev(const uint8_t* d_q, uint64_t q_stride, uint32_t dbytes, const uint32_t* d_perm, uint64_t rows, uint8_t* d_slab,
+                          uint32_t slab_stride, hipStream_t st) {
+  if (rows == 0) return PANN_OK;
+  const uint64_t work = rows * (slab_stride / 16);
+  hipLaunchKernelGGL(gather_query_rows_kernel, dim3((uint32_t)((work + MK_BLOCK - 1) / MK_BLOCK)), dim3(MK_BLOCK), 0, st, d_q, q_stride,
+                     dbytes, d_perm, rows, d_slab, slab_stride);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+int scatter_knn_rows_dev(const uint32_t* d_sids, const float* d_sdists, const uint32_t* d_perm, uint64_t rows, uint32_t k,
+                         uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, hipStream_t st) {
+  if (rows == 0) return PANN_OK;
+  hipLaunchKernelGGL(scatter_knn_rows_kernel, dim3((uint32_t)rows), dim3(PANN_WAVE), 0, st, d_sids, d_sdists, d_perm, k, d_out_ids,
+                     d_out_dists, d_out_counts);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
 
 int allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t stride, uint32_t* d_counts, hipStream_t st) {
   if (rows == 0) return PANN_OK;
@@ -307,7 +499,8 @@ size_t allow_compact_scratch_bytes(uint64_t n) { return ((size_t)compaction_bloc
 
 int allow_compact_count_dev(const uint32_t* d_allow, uint64_t n, uint32_t* d_scratch, const uint32_t** d_total, hipStream_t st) {
   const uint32_t nblk = compaction_blocks(n);
-  hipLaunchKernelGGL(allow_block_count_kernel, dim3(nblk), dim3(MK_BLOCK), 0, st, d_allow, n, d_scratch);
+  hipLaunchKernelGGL(allow_block_count_kernel, dim3(nblk), dim3(MK_BLOCK), 0, st, d_allow, n, (const uint32_t*)nullptr, (uint64_t)0, 1u,
+                     d_scratch);
   PANN_HIP(hipGetLastError());
   hipLaunchKernelGGL(allow_block_scan_kernel, dim3(1), dim3(MK_BLOCK), 0, st, d_scratch, nblk);
   PANN_HIP(hipGetLastError());
@@ -317,7 +510,8 @@ int allow_compact_count_dev(const uint32_t* d_allow, uint64_t n, uint32_t* d_scr
 
 int allow_compact_scatter_dev(const uint32_t* d_allow, uint64_t n, const uint32_t* d_scratch, uint32_t* d_ids, uint32_t count,
                               hipStream_t st) {
-  hipLaunchKernelGGL(allow_scatter_kernel, dim3(compaction_blocks(n)), dim3(MK_BLOCK), 0, st, d_allow, n, d_scratch, d_ids, count);
+  hipLaunchKernelGGL(allow_scatter_kernel, dim3(compaction_blocks(n)), dim3(MK_BLOCK), 0, st, d_allow, n, (const uint32_t*)nullptr,
+                     (uint64_t)0, 1u, d_scratch, d_ids, count);
   PANN_HIP(hipGetLastError());
   return PANN_OK;
 }

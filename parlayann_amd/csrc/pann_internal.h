@@ -221,6 +221,28 @@ int label_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, ui
                    int kind, const pann_label_pred* d_preds, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
                    uint32_t* d_out_counts);
 
+// grouped route (DESIGN.md "Exact kNN by predicate group"): a table of G filters, d_group[q] < G names the filter of query q.
+// The queries sorted by table index, stably: d_hist[g] = queries of entry g, d_off[0 .. G] = the first slot of every entry (G + 1
+// words), d_perm[slot] = query (nq words); an index >= G raises *d_flag, and that query gets no slot.  d_part: scratch of
+// nblocks x G words, nblocks from group_sort_shape.  Nothing is synchronised.
+void group_sort_shape(uint64_t nq, uint64_t G, uint32_t* nblocks, uint64_t* per_block);
+int group_queries_dev(const uint32_t* d_group, uint64_t nq, uint64_t G, uint32_t* d_flag, uint32_t* d_hist, uint32_t* d_off,
+                      uint32_t* d_part, uint32_t* d_perm, hipStream_t st);
+// d_out[u] = d_preds[d_used[u]], u < m
+int gather_preds_dev(const pann_label_pred* d_preds, const uint32_t* d_used, uint64_t m, pann_label_pred* d_out, hipStream_t st);
+// Compaction of `rows` bitmaps in one go: row r is row d_rowidx[r] (null: r) of d_allow, rows `stride` words apart; the ascending id
+// lists are written one after the other to d_ids[0 .. cap), cap = the sum of the rows' counts (< 2^32).  d_scratch:
+// allow_rows_compact_scratch_bytes(n, rows) bytes.
+size_t allow_rows_compact_scratch_bytes(uint64_t n, uint64_t rows);
+int allow_rows_compact_dev(const uint32_t* d_allow, uint64_t n, const uint32_t* d_rowidx, uint64_t stride, uint32_t rows,
+                           uint32_t* d_scratch, uint32_t* d_ids, uint32_t cap, hipStream_t st);
+// row r of d_slab (slab_stride bytes apart, a multiple of 16, 16-byte aligned) <- the dbytes bytes of query d_perm[r], zero padded
+int gather_query_rows_dev(const uint8_t* d_q, uint64_t q_stride, uint32_t dbytes, const uint32_t* d_perm, uint64_t rows, uint8_t* d_slab,
+                          uint32_t slab_stride, hipStream_t st);
+// row d_perm[r] of the outputs <- row r of the staged k-wide result; d_out_counts (optional): its entries that are not padding
+int scatter_knn_rows_dev(const uint32_t* d_sids, const float* d_sdists, const uint32_t* d_perm, uint64_t rows, uint32_t k,
+                         uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, hipStream_t st);
+
 // subset.hip: the kernels of pann_index_create_subset* (DESIGN.md "Subset index").  d_new_to_old: the m kept ids, ascending
 // (allow_compact_scatter_dev); every call is a no-op for m == 0 apart from the fill of subset_invert_dev.
 // d_a[r] = d_b[r] = r, r < m (either may be null): the two maps when everything is kept

@@ -2,11 +2,13 @@
 classes python/module.cpp registers (:50-57,150-155), over the C-ABI.
 
     Index(data_path, index_path)                       (positional order of graph_index.cpp:82)
-    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None)
+    .batch_search(queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None,
+                  exact_grouped=False)
                                                                          -> (uint32[nq,knn], float32[nq,knn])
     .single_search(q, knn, beam_width, quant, visit_limit)               -> uint32[knn]
     .batch_search_from_string(queries_path, knn, beam_width, quant=False, visit_limit=-1)
-    .batch_search_masked(queries, knn, beam_width, allow, quant=False, visit_limit=-1, exact_below=None, where=None)
+    .batch_search_masked(queries, knn, beam_width, allow, quant=False, visit_limit=-1, exact_below=None, where=None,
+                         exact_grouped=False)
                                                                          this project's own: masked results
     .set_labels(labels, first_row=0)                                     ... by label predicates: where=(kind, preds)
     .check_recall(queries_file, gt_file, neighbors, k)   prints "Recall: x"
@@ -143,10 +145,11 @@ class GraphIndex:
         if len(frontier_size) and int(frontier_size.min()) < knn:               # beamSearch.h:416-419
             raise RuntimeError(f"Error: beam search returned {int(frontier_size.min())} elements, which is less than k = {knn}")
 
-    def _exact_or_walk(self, queries, knn, allow, exact_below, walk):
+    def _exact_or_walk(self, queries, knn, allow, exact_below, walk, grouped=False):
         """The rule of DESIGN.md "Exact masked kNN": a mask with at most exact_below allowed points is answered exactly
         (DeviceIndex.bruteforce_knn_masked on the full-precision handle), any other by walk(queries, allow) -> (ids, dists).
-        Per-query rows are split by their own counts, each part takes its route, and the rows come back in the given order."""
+        Per-query rows are split by their own counts, each part takes its route, and the rows come back in the given order.
+        grouped: the exact part of per-query rows goes through DeviceIndex.bruteforce_knn_grouped (equal rows share one list)."""
         if exact_below is None:
             return walk(queries, allow)
         queries = np.ascontiguousarray(queries, dtype=self.T)
@@ -163,7 +166,8 @@ class GraphIndex:
         ids = np.full((len(queries), knn), 0xFFFFFFFF, np.uint32)
         dists = np.full((len(queries), knn), np.inf, np.float32)
         if exact.any():
-            ids[exact], dists[exact], _ = self.index.bruteforce_knn_masked(queries[exact], knn, allow[exact])
+            knn_exact = self.index.bruteforce_knn_grouped if grouped else self.index.bruteforce_knn_masked
+            ids[exact], dists[exact], _ = knn_exact(queries[exact], knn, allow=allow[exact])
         if not exact.all():
             ids[~exact], dists[~exact] = walk(queries[~exact], allow[~exact])
         return ids, dists
@@ -174,9 +178,10 @@ class GraphIndex:
         preds = np.asarray(where[1])
         return where if preds.ndim == 1 else (where[0], preds[rows])
 
-    def _exact_or_walk_labeled(self, queries, knn, where, exact_below, walk):
+    def _exact_or_walk_labeled(self, queries, knn, where, exact_below, walk, grouped=False):
         """_exact_or_walk for label predicates: the counts come from DeviceIndex.label_count (nothing is materialised), the exact
-        route is DeviceIndex.bruteforce_knn_labeled, walk(queries, where) -> (ids, dists) every other."""
+        route is DeviceIndex.bruteforce_knn_labeled (grouped: bruteforce_knn_grouped for per-query predicates),
+        walk(queries, where) -> (ids, dists) every other."""
         if exact_below is None:
             return walk(queries, where)
         queries = np.ascontiguousarray(queries, dtype=self.T)
@@ -192,24 +197,26 @@ class GraphIndex:
         ids = np.full((len(queries), knn), 0xFFFFFFFF, np.uint32)
         dists = np.full((len(queries), knn), np.inf, np.float32)
         if exact.any():
-            ids[exact], dists[exact], _ = self.index.bruteforce_knn_labeled(queries[exact], knn, self._where_rows(where, exact))
+            knn_exact = self.index.bruteforce_knn_grouped if grouped else self.index.bruteforce_knn_labeled
+            ids[exact], dists[exact], _ = knn_exact(queries[exact], knn, where=self._where_rows(where, exact))
         if not exact.all():
             ids[~exact], dists[~exact] = walk(queries[~exact], self._where_rows(where, ~exact))
         return ids, dists
 
-    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None):
+    def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None,
+                     exact_grouped=False):
         """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned.
         where = (kind, preds): the same by a label predicate (DeviceIndex.batch_search_labeled); not together with allow.
-        exact_below (with allow or where): as batch_search_masked"""
+        exact_below, exact_grouped (with allow or where): as batch_search_masked"""
         if where is not None:
             if allow is not None:
                 raise ValueError("where and allow exclude each other")
             return self._exact_or_walk_labeled(queries, knn, where, exact_below,
-                                               lambda q, w: self._search(q, knn, beam_width, quant, visit_limit, where=w))
+                                               lambda q, w: self._search(q, knn, beam_width, quant, visit_limit, where=w), exact_grouped)
         if allow is None:
             return self._search(queries, knn, beam_width, quant, visit_limit)
         return self._exact_or_walk(queries, knn, allow, exact_below,
-                                   lambda q, a: self._search(q, knn, beam_width, quant, visit_limit, a))
+                                   lambda q, a: self._search(q, knn, beam_width, quant, visit_limit, a), exact_grouped)
 
     def _search_masked(self, queries, knn, beam_width, allow, quant, visit_limit, where=None):
         """Masked searches (this project's own, DESIGN.md "Masked search").  Rows may be short (padding 0xFFFFFFFF / +inf):
@@ -234,7 +241,8 @@ class GraphIndex:
                                      rerank_factor=100, allow=allow, where=where, **qp)
         return r["ids"], r["dists"]
 
-    def batch_search_masked(self, queries, knn, beam_width, allow=None, quant=False, visit_limit=-1, exact_below=None, where=None):
+    def batch_search_masked(self, queries, knn, beam_width, allow=None, quant=False, visit_limit=-1, exact_below=None, where=None,
+                            exact_grouped=False):
         """Only allowed points are returned (allow: an allow bitmap or boolean mask, DeviceIndex.batch_search_masked; or
         where = (kind, preds): a label predicate over the labels of set_labels, 8 bytes per query in place of a bitmap row --
         every route below has the same form under it, and exact_below is decided by DeviceIndex.label_count).
@@ -244,16 +252,20 @@ class GraphIndex:
         exact_below: None (the default) -- every mask is walked, as above.  An integer: a mask that allows at most that many
         points is answered EXACTLY instead, by scoring its allowed points on the full-precision table (DESIGN.md "Exact masked
         kNN"; quant makes no difference there); per-query rows are split by their own counts.  There is no built-in
-        threshold: the count at which the two routes cost the same depends on the data (tools/masked_time.py --exact)."""
+        threshold: the count at which the two routes cost the same depends on the data (tools/masked_time.py --exact).
+        exact_grouped: the exact part of per-query rows or predicates is answered by DeviceIndex.bruteforce_knn_grouped, which
+        scores the queries of equal filters together (DESIGN.md "Exact kNN by predicate group"): the same rows, faster when many
+        queries share few filters.  The default changes nothing."""
         if where is not None:
             if allow is not None:
                 raise ValueError("where and allow exclude each other")
             return self._exact_or_walk_labeled(queries, knn, where, exact_below,
-                                               lambda q, w: self._search_masked(q, knn, beam_width, None, quant, visit_limit, w))
+                                               lambda q, w: self._search_masked(q, knn, beam_width, None, quant, visit_limit, w),
+                                               exact_grouped)
         if allow is None:
             raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
         return self._exact_or_walk(queries, knn, allow, exact_below,
-                                   lambda q, a: self._search_masked(q, knn, beam_width, a, quant, visit_limit))
+                                   lambda q, a: self._search_masked(q, knn, beam_width, a, quant, visit_limit), exact_grouped)
 
     def batch_search_masked_from_string(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1):
         return self._search_masked(io.read_bin(queries, self.T), knn, beam_width, allow, quant, visit_limit)

@@ -973,6 +973,46 @@ class DeviceIndex:
                                                     _ptr(oi), _ptr(od), _ptr(oc)))
         return oi, od, oc
 
+    def bruteforce_knn_grouped(self, queries, k, *, where=None, allow=None, group_of_query=None, max_list_ids=0):
+        """pann_bruteforce_knn_labeled_grouped / _masked_grouped: exact kNN for many queries that share few filters (DESIGN.md
+        "Exact kNN by predicate group") -> (ids uint32[nq, k], dists float32[nq, k], counts uint32[nq]), k <= 128.
+        The filters are a table: where = (kind, preds[G, 2]), or allow rows (G, W) packed / (G, n) boolean; group_of_query
+        (nq, each < G) names the table entry of every query, and row q is what bruteforce_knn_labeled / bruteforce_knn_masked
+        returns for query q under that ONE filter.  group_of_query=None: the table holds one filter per query (nq of them) and is
+        deduplicated here (np.unique over the rows).  max_list_ids: the ids materialised at once (0: the library's default);
+        results do not depend on it."""
+        q = self._queries(queries)
+        nq = len(q)
+        if (where is None) == (allow is None):
+            raise ValueError("bruteforce_knn_grouped needs where (label predicates) or allow (bitmap rows), not both")
+        if where is not None:
+            kind, table = self._where(where)
+        else:
+            table = pack_allow(allow, self.n)
+            if table.ndim == 1:
+                table = table[None, :]
+        if group_of_query is None:
+            if len(table) != nq:
+                raise ValueError("without group_of_query the table holds one filter per query")
+            table, group = np.unique(table, axis=0, return_inverse=True)
+        else:
+            group = np.asarray(group_of_query)
+            if group.shape != (nq,):
+                raise ValueError("group_of_query must hold one table index per query")
+            if nq and (group.min() < 0 or group.max() >= len(table)):
+                raise ValueError("group_of_query: a table index is out of range")
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        group = np.ascontiguousarray(np.asarray(group).reshape(-1), dtype=np.uint32)
+        oi = np.empty((nq, k), np.uint32); od = np.empty((nq, k), np.float32); oc = np.empty(nq, np.uint32)
+        if where is not None:
+            check(self._lib.pann_bruteforce_knn_labeled_grouped(self._h, _ptr(q), nq, _row_stride(q), k, kind, _ptr(table), len(table),
+                                                                _ptr(group), int(max_list_ids), _ptr(oi), _ptr(od), _ptr(oc)))
+        else:
+            check(self._lib.pann_bruteforce_knn_masked_grouped(self._h, _ptr(q), nq, _row_stride(q), k, _ptr(table), len(table),
+                                                               table.shape[1], _ptr(group), int(max_list_ids), _ptr(oi), _ptr(od),
+                                                               _ptr(oc)))
+        return oi, od, oc
+
     def bruteforce_knn_masked_dev(self, d_queries_ptr, nq, q_stride_bytes, k, d_allow_ptr, allow_stride_words, d_ids_ptr,
                                   d_dists_ptr, d_counts_ptr=None, stream_ptr=None):
         """pann_bruteforce_knn_masked_dev: the same on raw device addresses (integers), enqueued on `stream_ptr`.  Per-query rows

@@ -45,6 +45,16 @@ otherwise.  With --exact also pann_bruteforce_knn_labeled_dev (one predicate per
 pann_bruteforce_knn_masked_dev on the rows, and the time of pann_label_count_dev for the 10 000 predicates.
 
     python tools/masked_time.py --labels [--exact] [--json out.json]
+
+--labels --exact --grouped: the exact kNN by predicate group (DESIGN.md "Exact kNN by predicate group") on the same data and
+predicates -- 10 000 queries that name 10 tenants, or 100 (tenant, sub-tenant) pairs.  No graph is built and nothing is walked.
+Per selectivity, in one process: pann_bruteforce_knn_labeled_grouped_dev with the deduplicated table (10 or 100 predicates) and
+one table index per query; the per-query label scan and the per-query bitmap scan of --exact; and G sequential calls of the shared
+route (pann_bruteforce_knn_labeled_dev with one predicate) over the queries of one table entry each.  HIP events on the stream,
+and for the two forms that synchronise also the host's wall time per batch.  The grouped ids must equal the scan's ids; the tool
+stops otherwise.
+
+    python tools/masked_time.py --labels --exact --grouped [--json out.json]
 """
 import argparse
 import ctypes as C
@@ -98,7 +108,10 @@ def main():
     ap.add_argument("--bits", default="8", help="--rerank: bits per coordinate of the quantised copy: 8, 4 or 8,4 (one build for both)")
     ap.add_argument("--exact", action="store_true", help="the exact masked kNN beside the masked search on selective masks")
     ap.add_argument("--labels", action="store_true", help="per-query label predicates beside per-query bitmaps (with --exact: on the exact route too)")
+    ap.add_argument("--grouped", action="store_true", help="with --labels --exact: the grouped exact route beside the scans; no graph, no walk")
     a = ap.parse_args()
+    if a.grouped and not (a.labels and a.exact):
+        ap.error("--grouped goes with --labels --exact")
     if a.labels:
         return main_labels(a)
     if a.fractions is None:
@@ -314,8 +327,9 @@ def main_labels(a):
         labels = (rng.integers(0, 10, n).astype(np.uint32) | (rng.integers(0, 10, n).astype(np.uint32) << np.uint32(8))
                   | (rng.integers(0, 1 << 16, n).astype(np.uint32) << np.uint32(16)))
     with step(f"upload + build R={R} L={L}", 900):
-        ix = DeviceIndex(X, max_degree=R)
-        ix.vamana_build(R, L, ALPHA, num_passes=2, seed=1, sort_neighbors=True)
+        ix = DeviceIndex(X, max_degree=4 if a.grouped else R)
+        if not a.grouped:
+            ix.vamana_build(R, L, ALPHA, num_passes=2, seed=1, sort_neighbors=True)
         ix.set_labels(labels)
     lib = _capi.load()
     qp = _capi.QueryParams(k=K, beam=BEAM, cut=1.35, limit=n, degree_limit=R, rerank_factor=100, pad=1.0)
@@ -347,6 +361,17 @@ def main_labels(a):
         ms = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
         assert int(t_status.cpu()[0]) == 0
         return ms[len(ms) // 2], ms[0], ms[-1]
+
+    def wall(fn):
+        """median host time of a call that synchronises: from a drained stream to a drained stream"""
+        out = []
+        for _ in range(a.steps):
+            stream.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            stream.synchronize()
+            out.append((time.perf_counter() - t0) * 1e3)
+        return sorted(out)[len(out) // 2]
 
     def ids_now():
         return t_ids.cpu().numpy().view(np.uint32).copy()
@@ -380,6 +405,9 @@ def main_labels(a):
         def count_step():
             _capi.check(lib.pann_label_count_dev(ix.handle, _capi.PANN_PRED_MATCH, vp(t_p), nq, vp(t_cnt), sp))
 
+        if a.grouped:
+            rows.append(grouped_rows(a, name, preds, lib, ix, labels, t_q, t_p, t_rows, t_ids, t_d, t_cnt, stream, timed, wall, ids_now))
+            continue
         with step(f"{name}: expand to {nq} bitmap rows on the device, count", 300):
             x_ms = timed(expand_step)
             c_ms = timed(count_step)
@@ -431,6 +459,74 @@ def main_labels(a):
         with open(a.json, "w") as f:
             json.dump(dict(n=n, d=d, nq=nq, k=K, beam=BEAM, steps=a.steps, rows=rows), f, indent=1)
     ix.close()
+
+
+def grouped_rows(a, name, preds, lib, ix, labels, t_q, t_p, t_rows, t_ids, t_d, t_cnt, stream, timed, wall, ids_now):
+    """--labels --exact --grouped, one selectivity: the grouped call, the two scans, G sequential shared-route calls"""
+    import torch
+    n, d, nq = a.n, a.d, a.nq
+    words = (n + 31) // 32
+    sp = C.c_void_p(stream.cuda_stream)
+    vp = lambda t: C.c_void_p(t.data_ptr())
+    table, group = np.unique(preds, axis=0, return_inverse=True)
+    table = np.ascontiguousarray(table.astype(np.uint32))
+    group = np.ascontiguousarray(group.reshape(-1).astype(np.uint32))
+    G = len(table)
+    t_tab, t_grp = torch.from_numpy(table.view(np.int32)).cuda(), torch.from_numpy(group.view(np.int32)).cuda()
+    # the sequential form: the queries of a table entry side by side, one shared-route call per entry
+    order = np.argsort(group, kind="stable")
+    first = np.concatenate([[0], np.cumsum(np.bincount(group, minlength=G))])
+    t_qs = t_q[torch.from_numpy(order).cuda()].contiguous()
+    t_ids_s, t_d_s, t_cnt_s = torch.zeros_like(t_ids), torch.zeros_like(t_d), torch.zeros_like(t_cnt)
+    torch.cuda.synchronize()
+    qb = 2 * d
+
+    def grouped_step():
+        _capi.check(lib.pann_bruteforce_knn_labeled_grouped_dev(ix.handle, vp(t_q), nq, qb, K, _capi.PANN_PRED_MATCH, vp(t_tab), G, vp(t_grp), 0,
+                                                                vp(t_ids), vp(t_d), vp(t_cnt), sp))
+
+    def sequential_step():
+        for g in range(G):
+            lo, m = int(first[g]), int(first[g + 1] - first[g])
+            if m:
+                _capi.check(lib.pann_bruteforce_knn_labeled_dev(ix.handle, C.c_void_p(t_qs.data_ptr() + lo * qb), m, qb, K, _capi.PANN_PRED_MATCH,
+                                                                C.c_void_p(t_tab.data_ptr() + 8 * g), 1, C.c_void_p(t_ids_s.data_ptr() + lo * K * 4),
+                                                                C.c_void_p(t_d_s.data_ptr() + lo * K * 4), C.c_void_p(t_cnt_s.data_ptr() + lo * 4), sp))
+
+    with step(f"{name}: grouped, scans, {G} sequential shared calls", 900):
+        _capi.check(lib.pann_labels_to_allow_dev(ix.handle, _capi.PANN_PRED_MATCH, vp(t_p), nq, vp(t_rows), words, sp))
+        g_ms = timed(grouped_step)
+        g_wall = wall(grouped_step)
+        ids_g = ids_now()
+        cnt_g = t_cnt.cpu().numpy().view(np.uint32).copy()
+        s_ms = timed(sequential_step)
+        s_wall = wall(sequential_step)
+        ids_s = t_ids_s.cpu().numpy().view(np.uint32)
+        e_l = timed(lambda: _capi.check(lib.pann_bruteforce_knn_labeled_dev(ix.handle, vp(t_q), nq, qb, K, _capi.PANN_PRED_MATCH, vp(t_p), nq,
+                                                                          vp(t_ids), vp(t_d), vp(t_cnt), sp)))
+        ids_el = ids_now()
+        e_b = timed(lambda: ix.bruteforce_knn_masked_dev(t_q.data_ptr(), nq, qb, K, t_rows.data_ptr(), words, t_ids.data_ptr(), t_d.data_ptr(),
+                                                         t_cnt.data_ptr(), stream.cuda_stream))
+        if not np.array_equal(ids_g, ids_el) or not np.array_equal(ids_now(), ids_el):
+            print("ERROR: the grouped ids differ from the per-query scan's", flush=True)
+            sys.exit(1)
+        if not np.array_equal(ids_s, ids_g[order]):
+            print("ERROR: the sequential shared-route ids differ from the grouped ids", flush=True)
+            sys.exit(1)
+    allowed = np.array([int(((labels & t[0]) == t[1]).sum()) for t in table])
+    if not np.array_equal(cnt_g, np.minimum(allowed[group], K)):
+        print("ERROR: the grouped counts differ from the host count", flush=True)
+        sys.exit(1)
+    row = dict(predicates=name, distinct=G, allowed_mean=float(allowed[group].mean()),
+               grouped_ms=g_ms[0], grouped_ms_min=g_ms[1], grouped_ms_max=g_ms[2], grouped_wall_ms=g_wall, sequential_ms=s_ms[0],
+               sequential_ms_min=s_ms[1], sequential_ms_max=s_ms[2], sequential_wall_ms=s_wall, exact_labeled_ms=e_l[0],
+               exact_labeled_ms_min=e_l[1], exact_labeled_ms_max=e_l[2], exact_bitmap_ms=e_b[0], exact_bitmap_ms_min=e_b[1],
+               exact_bitmap_ms_max=e_b[2])
+    print(f"  {name}: {G} distinct predicates, {row['allowed_mean']:.0f} allowed points per query   grouped {g_ms[0]:.3f} ms (min {g_ms[1]:.3f}, "
+          f"max {g_ms[2]:.3f}; host wall {g_wall:.3f})   {G} sequential shared calls {s_ms[0]:.3f} ms (min {s_ms[1]:.3f}, max {s_ms[2]:.3f}; host "
+          f"wall {s_wall:.3f})   label scan {e_l[0]:.3f} ms (min {e_l[1]:.3f}, max {e_l[2]:.3f})   bitmap scan {e_b[0]:.3f} ms (min "
+          f"{e_b[1]:.3f}, max {e_b[2]:.3f})   grouped ids == scan ids == sequential ids", flush=True)
+    return row
 
 
 def main_rerank(a):
