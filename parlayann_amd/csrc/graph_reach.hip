@@ -93,10 +93,10 @@ __global__ void __launch_bounds__(GR_BLOCK) reach_finish_kernel(const uint32_t* 
 }
 
 // one wave per row (GR_WAVES rows per block); either output may be null, in_deg zeroed by the caller
-__global__ void __launch_bounds__(GR_BLOCK) degrees_kernel(const uint32_t* __restrict__ graph, uint32_t gstride, uint64_t n,
-                                                           uint32_t* __restrict__ out_deg, uint32_t* in_deg) {
+__global__ void __launch_bounds__(GR_BLOCK) degrees_kernel(const uint32_t* __restrict__ graph, uint32_t gstride, uint64_t first_row,
+                                                           uint64_t n, uint32_t* __restrict__ out_deg, uint32_t* in_deg) {
   const uint32_t lane = threadIdx.x & (PANN_WAVE - 1);
-  const uint64_t r = (uint64_t)blockIdx.x * GR_WAVES + threadIdx.x / PANN_WAVE;
+  const uint64_t r = first_row + (uint64_t)blockIdx.x * GR_WAVES + threadIdx.x / PANN_WAVE;
   if (r >= n) return;                                       // wave uniform
   const uint32_t* row = graph + r * gstride;
   uint32_t deg = 0;
@@ -152,9 +152,13 @@ int reach_finish_dev(const uint32_t* d_visited, const uint32_t* d_consider, uint
 int graph_degrees_dev(const DeviceIndex& ix, uint32_t* d_out_deg, uint32_t* d_in_deg, hipStream_t st) {
   if (ix.n == 0) return PANN_OK;
   if (d_in_deg) PANN_HIP(hipMemsetAsync(d_in_deg, 0, (size_t)ix.n * 4, st));
-  hipLaunchKernelGGL(degrees_kernel, dim3((uint32_t)((ix.n + GR_WAVES - 1) / GR_WAVES)), dim3(GR_BLOCK), 0, st, ix.graph, ix.gstride,
-                     ix.n, d_out_deg, d_in_deg);
-  PANN_HIP(hipGetLastError());
+  const uint64_t slice = (uint64_t)launch_slice_blocks(GR_BLOCK) * GR_WAVES;        // rows of one launch (pann_internal.h)
+  for (uint64_t r0 = 0; r0 < ix.n; r0 += slice) {
+    const uint64_t rows = std::min<uint64_t>(slice, ix.n - r0);
+    hipLaunchKernelGGL(degrees_kernel, dim3((uint32_t)((rows + GR_WAVES - 1) / GR_WAVES)), dim3(GR_BLOCK), 0, st, ix.graph, ix.gstride,
+                       r0, ix.n, d_out_deg, d_in_deg);
+    PANN_HIP(hipGetLastError());
+  }
   return PANN_OK;
 }
 

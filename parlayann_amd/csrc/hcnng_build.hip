@@ -126,8 +126,8 @@ __global__ void invert_perm(const uint32_t* ids, uint32_t* pos, uint64_t n) {
   uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i < n) pos[ids[i]] = (uint32_t)i;
 }
-__global__ void degree_init_kernel(const uint32_t* graph, uint32_t gstride, uint32_t* deg, uint64_t n) {
-  const uint64_t v = blockIdx.x;
+__global__ void degree_init_kernel(const uint32_t* graph, uint32_t gstride, uint32_t* deg, uint64_t first, uint64_t n) {
+  const uint64_t v = first + blockIdx.x;
   if (v >= n) return;
   const uint32_t* row = graph + v * gstride;
   uint32_t d = 0;
@@ -300,9 +300,9 @@ __global__ void fill_u32_hc(uint32_t* p, uint64_t n, uint32_t v) {
 // [j*mst_deg, (j+1)*mst_deg) of every row.  Row v of the graph = the edges of trees 0, 1, 2, ... in that order (the append order
 // of the single-process build, hcnng_index.h:117-131), continuing after the row's current neighbours.  One wave per vertex.
 __global__ void __launch_bounds__(PANN_WAVE) hcnng_assemble_kernel(uint32_t* graph, uint32_t gstride, uint32_t max_deg, const uint32_t* slabs,
-                                                                   uint64_t n, uint32_t W, uint32_t slab_stride, uint32_t ntrees,
-                                                                   uint32_t mst_deg) {
-  const uint64_t v = blockIdx.x;
+                                                                   uint64_t first, uint64_t n, uint32_t W, uint32_t slab_stride,
+                                                                   uint32_t ntrees, uint32_t mst_deg) {
+  const uint64_t v = first + blockIdx.x;
   const int lane = threadIdx.x;
   uint32_t* row = graph + v * gstride;
   uint32_t deg = 0;
@@ -326,9 +326,11 @@ __global__ void __launch_bounds__(PANN_WAVE) hcnng_assemble_kernel(uint32_t* gra
 int hcnng_assemble_dev(const DeviceIndex& ix, hipStream_t st, const uint32_t* d_slabs, uint32_t W, uint32_t slab_stride,
                        uint32_t ntrees, uint32_t mst_deg) {
   if (W == 0 || (uint64_t)((ntrees + W - 1) / W) * mst_deg > slab_stride) { set_error("pann_hcnng_assemble_dev: slab rows too short"); return PANN_ERR_BAD_ARG; }
-  hipLaunchKernelGGL(hcnng_assemble_kernel, dim3((uint32_t)ix.n), dim3(PANN_WAVE), 0, st, ix.graph, ix.gstride, ix.max_deg, d_slabs,
-                     ix.n, W, slab_stride, ntrees, mst_deg);
-  PANN_HIP(hipGetLastError());
+  for (uint64_t v0 = 0; v0 < ix.n; v0 += launch_slice_blocks(PANN_WAVE)) {          // one wave per vertex, in slices (pann_internal.h)
+    hipLaunchKernelGGL(hcnng_assemble_kernel, dim3((uint32_t)std::min<uint64_t>(launch_slice_blocks(PANN_WAVE), ix.n - v0)), dim3(PANN_WAVE), 0, st,
+                       ix.graph, ix.gstride, ix.max_deg, d_slabs, v0, ix.n, W, slab_stride, ntrees, mst_deg);
+    PANN_HIP(hipGetLastError());
+  }
   PANN_HIP(hipStreamSynchronize(st));
   return PANN_OK;
 }
@@ -404,8 +406,11 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
   arena.add(d_scat, ncl_cap * sizeof(ScatterCluster)); arena.add(d_n0, ncl_cap * 4);
   arena.add(d_loff, (n + 2) * 8); arena.add(d_seg_b, (n + 1) * 4); arena.add(d_seg_e, (n + 1) * 4);
   if (arena.commit()) { set_error("pann_hcnng_build: hipMalloc failed"); return PANN_ERR_HIP; }
-  hipLaunchKernelGGL(degree_init_kernel, dim3((uint32_t)n), dim3(64), 0, st, ix.graph, ix.gstride, b_deg.as<uint32_t>(), n);
-  PANN_HIP(hipGetLastError());
+  for (uint64_t v0 = 0; v0 < n; v0 += launch_slice_blocks(64)) {
+    hipLaunchKernelGGL(degree_init_kernel, dim3((uint32_t)std::min<uint64_t>(launch_slice_blocks(64), n - v0)), dim3(64), 0, st, ix.graph,
+                       ix.gstride, b_deg.as<uint32_t>(), v0, n);
+    PANN_HIP(hipGetLastError());
+  }
 
   struct Cl { uint32_t lo, len; uint64_t rnd; };
   double t_tree = 0, t_leaf = 0, t_mst = 0;

@@ -147,6 +147,11 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
                        hipStream_t stream);
 void choose_point_layout(uint32_t dbytes, uint32_t* lpc, uint32_t* nch);
 
+// A launch carries its work-item count (blocks x threads) in 32 bits, and the runtime takes a larger count modulo 2^32 without
+// an error: 2^26 + 4096 blocks of one wave run 4096 blocks.  A launch with a block or a wave per vertex therefore goes in slices
+// of at most this many blocks, and its kernel adds the slice's first block to blockIdx.x.
+inline uint32_t launch_slice_blocks(uint32_t threads) { return (1u << 31) / threads; }
+
 // vamana_build.hip
 int robust_prune_batch_host(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint32_t* owners,
                             uint64_t m, const uint32_t* cand_ids, const float* cand_dists,

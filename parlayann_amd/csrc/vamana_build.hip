@@ -472,9 +472,9 @@ __global__ void __launch_bounds__(PANN_WAVE) reverse_light_kernel(ReverseArgs A)
 // G[i].sort by distance to i (:180-185); ties by id
 template <int DT, int METRIC, int LPC, bool NCH1>
 __global__ void __launch_bounds__(PANN_WAVE) sort_rows_kernel(PointsView pv, uint32_t dbytes, uint32_t* graph,
-                                                              uint32_t gstride, uint32_t n) {
+                                                              uint32_t gstride, uint32_t first, uint32_t n) {
   const int lane = threadIdx.x;
-  const uint32_t v = blockIdx.x;
+  const uint32_t v = first + blockIdx.x;
   __shared__ uint32_t Pl[PANN_WAVE];
   __shared__ uint64_t Kk[4096 + 64];
   extern __shared__ __align__(16) uint8_t smem[];
@@ -895,10 +895,13 @@ int sort_neighbors_dev(const DeviceIndex& ix, hipStream_t st) {
   if (ix.max_deg > 4096) { set_error("sort_neighbors: max_deg > 4096"); return PANN_ERR_UNSUPPORTED; }
   const PointsView pv{ix.points, ix.pstride, ix.nch, ix.exact};
   const size_t qb = query_lds_bytes(ix);
-#define CALL_SORT(DT, MT, L, N1) hipLaunchKernelGGL((sort_rows_kernel<DT, MT, L, N1>), dim3((uint32_t)ix.n), dim3(PANN_WAVE), qb, st, pv, ix.dbytes, ix.graph, ix.gstride, (uint32_t)ix.n)
-  PANN_TYPE_SWITCH(ix, CALL_SORT);
+#define CALL_SORT(DT, MT, L, N1) hipLaunchKernelGGL((sort_rows_kernel<DT, MT, L, N1>), dim3(rows), dim3(PANN_WAVE), qb, st, pv, ix.dbytes, ix.graph, ix.gstride, v0, (uint32_t)ix.n)
+  for (uint64_t r0 = 0; r0 < ix.n; r0 += launch_slice_blocks(PANN_WAVE)) {          // one wave per row, in slices (pann_internal.h)
+    const uint32_t v0 = (uint32_t)r0, rows = (uint32_t)std::min<uint64_t>(launch_slice_blocks(PANN_WAVE), ix.n - r0);
+    PANN_TYPE_SWITCH(ix, CALL_SORT);
+    PANN_HIP(hipGetLastError());
+  }
 #undef CALL_SORT
-  PANN_HIP(hipGetLastError());
   PANN_HIP(hipStreamSynchronize(st));
   return PANN_OK;
 }

@@ -49,7 +49,7 @@ __global__ void delete_mark_kernel(const uint32_t* __restrict__ del, uint64_t m,
 struct ExpandArgs {
   const uint32_t* graph; uint32_t gstride;
   const uint32_t* bitmap;
-  uint64_t count;              // waves with work: n (count) or |A| (fill)
+  uint64_t first, count;       // this launch starts at wave `first`; waves with work: n (count) or |A| (fill)
   uint32_t* cnt; uint32_t* flag; uint32_t* sc;                            // count: [n] list length, [n] p is an affected owner
   const uint32_t* owners; const uint64_t* offs; uint32_t* cand;           // fill: [|A|], [|A|] first slot of the owner's list
 };
@@ -59,7 +59,7 @@ struct ExpandArgs {
 template <bool FILL>
 __global__ void __launch_bounds__(WAVE * EXPAND_WAVES) delete_expand_kernel(ExpandArgs A) {
   const int lane = threadIdx.x & (WAVE - 1);
-  const uint64_t wv = blockIdx.x * (uint64_t)EXPAND_WAVES + (threadIdx.x >> 6);
+  const uint64_t wv = A.first + blockIdx.x * (uint64_t)EXPAND_WAVES + (threadIdx.x >> 6);
   if (wv >= A.count) return;
   const uint32_t p = FILL ? A.owners[wv] : (uint32_t)wv;
   uint32_t* out = FILL ? A.cand + A.offs[wv] : nullptr;
@@ -104,6 +104,18 @@ __global__ void __launch_bounds__(WAVE * EXPAND_WAVES) delete_expand_kernel(Expa
     }
   }
   if (!FILL && lane == 0) { A.cnt[p] = w; A.flag[p] = 1; atomicMax(&A.sc[SC_MAXLEN], w); }
+}
+
+// A.count waves, in launches of at most launch_slice_blocks blocks (pann_internal.h)
+template <bool FILL>
+int launch_expand(ExpandArgs A, hipStream_t st) {
+  const uint64_t slice = (uint64_t)launch_slice_blocks(WAVE * EXPAND_WAVES) * EXPAND_WAVES;
+  for (A.first = 0; A.first < A.count; A.first += slice) {
+    const uint64_t waves = std::min(slice, A.count - A.first);
+    hipLaunchKernelGGL(delete_expand_kernel<FILL>, dim3((uint32_t)((waves + EXPAND_WAVES - 1) / EXPAND_WAVES)), dim3(WAVE * EXPAND_WAVES), 0, st, A);
+    PANN_HIP(hipGetLastError());
+  }
+  return PANN_OK;
 }
 
 // A in increasing id: pos is the exclusive scan of flag
@@ -213,8 +225,7 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
   ExpandArgs ea{};
   ea.graph = ix.graph; ea.gstride = ix.gstride; ea.bitmap = bitmap;
   ea.count = n; ea.cnt = cnt; ea.flag = flag; ea.sc = sc;
-  hipLaunchKernelGGL(delete_expand_kernel<false>, dim3((uint32_t)((n + EXPAND_WAVES - 1) / EXPAND_WAVES)), dim3(WAVE * EXPAND_WAVES), 0, st, ea);
-  PANN_HIP(hipGetLastError());
+  if (int rc = launch_expand<false>(ea, st)) return rc;
   size_t tb = stmp;
   PANN_HIP(rocprim::exclusive_scan(d_tmp, tb, flag, pos, 0u, (size_t)n, rocprim::plus<uint32_t>(), st));
   uint32_t h_last[3] = {0, 0, 0};
@@ -239,8 +250,7 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
     total = h_off + h_cnt;
     PANN_HIP(hipMalloc(&cand.p, (total + 1) * 4));
     ea.count = na; ea.owners = owners; ea.offs = offs; ea.cand = (uint32_t*)cand.p;
-    hipLaunchKernelGGL(delete_expand_kernel<true>, dim3((na + EXPAND_WAVES - 1) / EXPAND_WAVES), dim3(WAVE * EXPAND_WAVES), 0, st, ea);
-    PANN_HIP(hipGetLastError());
+    if (int rc = launch_expand<true>(ea, st)) return rc;
   }
   PANN_HIP(hipStreamSynchronize(st));
   const auto t1 = now_();
@@ -274,11 +284,14 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
       PANN_HIP(hipStreamSynchronize(st));        // the next range reuses the key scratch (and may regrow it)
     }
     // ---- 5. write: every prune is done ----
-    hipLaunchKernelGGL(delete_write_rows_kernel, dim3(na), dim3(WAVE), 0, st, ix.graph, ix.gstride, owners, d_rows, R, gcode, ix.rank16);
-    PANN_HIP(hipGetLastError());
+    for (uint32_t i0 = 0; i0 < na; i0 += launch_slice_blocks(WAVE)) {
+      hipLaunchKernelGGL(delete_write_rows_kernel, dim3(std::min(na - i0, launch_slice_blocks(WAVE))), dim3(WAVE), 0, st, ix.graph, ix.gstride,
+                         owners + i0, d_rows + (size_t)i0 * R, R, gcode, ix.rank16);
+      PANN_HIP(hipGetLastError());
+    }
   }
-  for (uint64_t i0 = 0; i0 < m; i0 += (1u << 30)) {
-    const uint32_t c = (uint32_t)std::min<uint64_t>(m - i0, 1u << 30);
+  for (uint64_t i0 = 0; i0 < m; i0 += launch_slice_blocks(WAVE)) {
+    const uint32_t c = (uint32_t)std::min<uint64_t>(m - i0, launch_slice_blocks(WAVE));
     hipLaunchKernelGGL(delete_empty_rows_kernel, dim3(c), dim3(WAVE), 0, st, ix.graph, ix.gstride, d_del + i0, gcode);
     PANN_HIP(hipGetLastError());
   }

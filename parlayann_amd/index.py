@@ -217,6 +217,22 @@ class DeviceIndex:
         return (self.d + 1) // 2 if self.dtype4 is not None else self.d * np.dtype(self.dtype).itemsize
 
     @classmethod
+    def empty(cls, n, d, dtype, max_degree, metric="Euclidian", device=0):
+        """pann_index_create_empty: n zero vectors of d coordinates and an empty graph, both filled on the device -- nothing
+        crosses the bus.  Rows come later (upload_points, update_rows, vamana_insert_batch)."""
+        lib = _capi.load()
+        dt = np.dtype(dtype)
+        if dt not in _DT:
+            raise ValueError("dtype must be uint8/int8/float32/float16/bfloat16 (parlayann_amd.bfloat16)")
+        self = cls.__new__(cls)
+        self.n, self.d, self.max_degree = int(n), int(d), int(max_degree)
+        self.dtype, self.metric = dt, _metric_code(metric)
+        h = C.c_void_p()
+        check(lib.pann_index_create_empty(C.byref(h), self.n, self.d, _DT[dt], self.metric, self.max_degree, device))
+        self._h, self._lib = h, lib
+        return self
+
+    @classmethod
     def from_files(cls, points_path, dtype, graph_path=None, max_degree=None, metric="Euclidian", device=0, rows=None,
                    chunk_bytes=256 << 20, exact_float_order=False):
         """Stream a reference-format vector file (point_range.h:74-117: [n:u32][d:u32][rows]) -- and, optionally, a graph file
@@ -243,12 +259,8 @@ class DeviceIndex:
             max_degree = gmax
         if max_degree is None:
             raise ValueError("give a graph file or max_degree")
-        self = cls.__new__(cls)
-        self.n, self.d, self.max_degree = n, d, int(max_degree)
-        self.dtype, self.metric = dt, _metric_code(metric)
-        h = C.c_void_p()
-        check(lib.pann_index_create_empty(C.byref(h), n, d, _DT[dt], self.metric, self.max_degree, device))
-        self._h, self._lib = h, lib
+        self = cls.empty(n, d, dt, max_degree, metric=metric, device=device)
+        h = self._h
         try:
             row_bytes = d * dt.itemsize
             step = max(1, int(chunk_bytes) // row_bytes)

@@ -16,6 +16,7 @@ import math
 
 import numpy as np
 
+import masked_ref
 import oracle_api
 from parlayann_amd import sketch as sk
 
@@ -47,7 +48,7 @@ def filtered_batch_search(points, graph, queries=None, query_ids=None, k=10, bea
 
     bits = max(10, int(math.ceil(math.log2(float(beam) * float(beam)))) - 2)           # :52
     hmask = (1 << bits) - 1
-    slot_of = np.array([o.hash64_2(a) & hmask for a in range(n)], dtype=np.int64)       # hash64_2(a) & ((1 << bits) - 1)
+    slot_of = masked_ref.FilterSlots(o, bits)                                           # hash64_2(a) & ((1 << bits) - 1)
     pbase, pstride = points.ctypes.data, points.strides[0]
     dist_fn = o.lib.pann_oracle_distance
     c_dt, c_m, c_d = C.c_int(dt), C.c_int(mcode), C.c_uint32(d)

@@ -30,7 +30,20 @@ import oracle_api
 
 F = np.float32
 BIG = F(2147483648.0)          # (distanceType) numeric_limits<int>::max()  (:152)
-_slots = {}                    # (n, bits) -> filter slot of every id
+_slots = {}                    # bits -> FilterSlots
+
+
+class FilterSlots(dict):
+    """id -> its slot in the visited filter, hash64_2(id) & ((1 << bits) - 1) (:52,:150), worked out when first asked for: a
+    search touches a few thousand ids, whatever the size of the table"""
+
+    def __init__(self, oracle, bits):
+        super().__init__()
+        self.hash, self.mask = oracle.hash64_2, (1 << bits) - 1
+
+    def __missing__(self, a):
+        v = self[a] = self.hash(int(a)) & self.mask
+        return v
 
 
 def unpack_allow(allow, n, nq):
@@ -63,9 +76,9 @@ def masked_batch_search(points, graph, allow, queries=None, query_ids=None, k=10
 
     bits = max(10, int(math.ceil(math.log2(float(beam) * float(beam)))) - 2)           # :52
     hmask = (1 << bits) - 1
-    if (n, bits) not in _slots:
-        _slots[(n, bits)] = np.array([o.hash64_2(a) & hmask for a in range(n)], dtype=np.int64)
-    slot_of = _slots[(n, bits)]
+    if bits not in _slots:
+        _slots[bits] = FilterSlots(o, bits)
+    slot_of = _slots[bits]
     pbase, pstride = points.ctypes.data, points.strides[0]
     dist_fn = o.lib.pann_oracle_distance
     c_dt, c_m, c_d = C.c_int(dt), C.c_int(mcode), C.c_uint32(d)
