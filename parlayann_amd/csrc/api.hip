@@ -8,6 +8,7 @@
 #include <mutex>
 #include <vector>
 
+#include "grouped_plan.h"
 #include "host_staging.h"
 #include "pann_internal.h"
 #include "quant_device.h"
@@ -57,7 +58,7 @@ struct pann_index {
   int device = 0;
   hipStream_t stream = nullptr;      // the stream every call of this handle runs on: own_stream, or the caller's (pann_index_set_stream)
   hipStream_t own_stream = nullptr;
-  Workspace ws, ws2, ws3, ws4;   // kernel scratch (search / prune / re-prune / rows of a batch)
+  Workspace ws, ws2, ws3, ws4;   // kernel scratch (builder: search / prune / re-prune / rows of a batch; exact kNN: ws2 partial lists, ws3 block counts, ws4 id lists)
   Workspace ws_rr;               // pann_batch_search_rerank*: prepared queries and frontiers (search_rerank.hip)
   uint32_t vcap = 0;        // visited-list capacity used by the builder (grows on overflow)
   uint32_t dcap = 256;      // dropped-list capacity of the searches (pann_index_reserve_dropped; grows on overflow)
@@ -171,23 +172,40 @@ int allow_stride_check(const char* fn, const char* zero_means, uint64_t stride, 
   return PANN_ERR_BAD_ARG;
 }
 
-// the label-predicate arguments of a labeled entry point, as the caller gave them (host or device `preds`, as the entry's pointers)
-struct LabelArgs { int kind; const pann_label_pred* preds; uint64_t npreds; };
-// `owner`: the handle whose labels are read (not null).  dev: `preds` is a device pointer
-int label_checks(const pann_index* owner, const char* fn, const LabelArgs& l, uint64_t nq, bool dev) {
+// npreds predicates over the labels of `owner` (which the entry point's checks may yet find to be null)
+PointFilter label_filter(const pann_index* owner, int kind, const pann_label_pred* preds, uint64_t npreds, bool dev) {
+  PointFilter f;
+  f.mode = MASK_LABELS; f.labels = owner ? owner->ix.labels : nullptr; f.kind = kind; f.preds = preds; f.count = npreds; f.dev = dev;
+  if (npreds != 1) f.layout = PointFilter::PER_QUERY;
+  return f;
+}
+
+// Every refusal that concerns the filter itself.  `owner`: the handle whose labels are read and whose size the bitmap rows have (not
+// null); nq: what a per-query filter must count.  A table's rules are table_checks': the grouped entries test queries and k in between.
+int filter_checks(const pann_index* owner, const char* fn, const PointFilter& F, uint64_t nq) {
   const std::string f = fn;
+  if (F.mode == MASK_BITMAP) {
+    if (!F.allow) { set_error(f + ": null allow bitmap"); return PANN_ERR_BAD_ARG; }
+    return F.is_table() ? PANN_OK : allow_stride_check(fn, "one shared bitmap", F.stride, owner->ix.n);
+  }
   if (!owner->ix.labels) { set_error(f + ": the handle has no labels (pann_index_set_labels)"); return PANN_ERR_BAD_ARG; }
-  if (!pred_kind_known(l.kind)) { set_error(f + ": unknown predicate kind " + std::to_string(l.kind)); return PANN_ERR_BAD_ARG; }
-  if (!l.preds) { set_error(f + ": null predicates"); return PANN_ERR_BAD_ARG; }
-  if (dev && (uintptr_t)l.preds % 8 != 0) { set_error(f + ": device predicates must be 8-byte aligned"); return PANN_ERR_BAD_ARG; }
-  if (l.npreds != 1 && l.npreds != nq) { set_error(f + ": npreds must be 1 (one predicate for the batch) or nq"); return PANN_ERR_BAD_ARG; }
+  if (!pred_kind_known(F.kind)) { set_error(f + ": unknown predicate kind " + std::to_string(F.kind)); return PANN_ERR_BAD_ARG; }
+  if (!F.preds) { set_error(f + ": null predicates"); return PANN_ERR_BAD_ARG; }
+  if (F.dev && (uintptr_t)F.preds % 8 != 0) { set_error(f + ": device predicates must be 8-byte aligned"); return PANN_ERR_BAD_ARG; }
+  if (!F.is_table() && F.count != 1 && F.count != nq) { set_error(f + ": npreds must be 1 (one predicate for the batch) or nq"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
 }
-// the MaskArgs of a labeled call after label_checks; preds: where the predicates lie for the launch (device)
-MaskArgs label_mask(const pann_index* owner, const LabelArgs& l, const pann_label_pred* d_preds, uint32_t* result_count, uint32_t* allowed_cmps) {
-  MaskArgs m{nullptr, 0, result_count, allowed_cmps};
-  m.labels = owner->ix.labels; m.preds = d_preds; m.pred_stride = l.npreds == 1 ? 0u : 1u; m.pred_kind = l.kind;
-  return m;
+int table_checks(const pann_index* owner, const char* fn, const PointFilter& F) {
+  const std::string f = fn;
+  const uint64_t words = PointFilter::row_words(owner->ix.n);
+  if (F.count == 0) { set_error(f + ": an empty filter table"); return PANN_ERR_BAD_ARG; }
+  if (F.count > 0xFFFFFFFFull) { set_error(f + ": more than 2^32 - 1 table entries"); return PANN_ERR_BAD_ARG; }
+  if (!F.group) { set_error(f + ": null index array"); return PANN_ERR_BAD_ARG; }
+  if (F.mode == MASK_BITMAP && F.stride < words && !(F.stride == 0 && F.count == 1)) {
+    set_error(f + ": allow_stride_words must be at least ceil(n / 32) = " + std::to_string(words));
+    return PANN_ERR_BAD_ARG;
+  }
+  return PANN_OK;
 }
 
 void fill_search_params(SearchArgs& a, const pann_query_params* qp) {
@@ -258,15 +276,17 @@ int ensure_locality_cells(pann_index* idx) {
   PANN_HIP(hipGetLastError());
   DeviceIndex pix = ix;                       // the pivots as a 256-point table; A rows = all base points, as external rows
   pix.points = idx->pivot_rows.as<uint8_t>(); pix.n = NPIV; pix.graph = nullptr; pix.gcode = nullptr; pix.rank16 = nullptr; pix.cell = nullptr;
-  if (int rc = dense_topk_dev(pix, idx->ws2, st, ix.points, ix.pstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              (uint32_t)((ix.n + 63) / 64), ix.n, NPIV, 1, 1, 0, idx->cell_buf.as<uint32_t>(),
-                              idx->pivot_dists.as<float>())) return rc;
+  DenseTopkCall nearest;
+  nearest.a_ext = ix.points; nearest.a_stride = ix.pstride; nearest.ntiles = (uint32_t)((ix.n + 63) / 64); nearest.na = ix.n; nearest.nb = NPIV;
+  nearest.m = 1; nearest.out_ids = idx->cell_buf.as<uint32_t>(); nearest.out_dists = idx->pivot_dists.as<float>();
+  if (int rc = dense_topk_dev(pix, idx->ws2, st, nearest)) return rc;
   if (idx->locality_groups > 1 && NPIV >= 4 * idx->locality_groups && NPIV <= 65536) {
     // the pivots themselves by their nearest of the first `groups` pivots (a prefix of the pivot slab is a table too)
     DeviceIndex gix = pix; gix.n = idx->locality_groups;
     uint32_t* d_pg = idx->pivot_dists.as<uint32_t>();                       // [NPIV] group of every pivot, then [NPIV] distances
-    if (int rc = dense_topk_dev(gix, idx->ws2, st, pix.points, ix.pstride, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                                (NPIV + 63) / 64, NPIV, gix.n, 1, 1, 0, d_pg, reinterpret_cast<float*>(d_pg + NPIV))) return rc;
+    nearest.a_ext = pix.points; nearest.ntiles = (NPIV + 63) / 64; nearest.na = NPIV; nearest.nb = gix.n;
+    nearest.out_ids = d_pg; nearest.out_dists = reinterpret_cast<float*>(d_pg + NPIV);
+    if (int rc = dense_topk_dev(gix, idx->ws2, st, nearest)) return rc;
     hipLaunchKernelGGL(group_cells_kernel, dim3((uint32_t)((ix.n + 255) / 256)), dim3(256), 0, st, idx->cell_buf.as<uint32_t>(), ix.n, d_pg);
     PANN_HIP(hipGetLastError());
   }
@@ -588,12 +608,11 @@ int pann_index_get_graph(pann_index* idx, uint32_t* graph_out) {
 // batched beam search
 // ---------------------------------------------------------------------------------------------
 
-static int mask_checks(const pann_index* idx, const MaskArgs& m, const pann_query_params* qp, const pann_search_out* out) {
+// the limits of the masked searches (the fused path comes through here too, out_k = its list length).  The bitmap's own checks lie
+// between them; a labeled call has been through filter_checks at its entry, ahead of the search's checks
+static int masked_search_checks(const pann_index* idx, const PointFilter& F, uint64_t nq, const pann_query_params* qp, const pann_search_out* out) {
   if ((int64_t)out->out_k > qp->beam) { set_error("pann_batch_search_masked: out_k larger than the beam"); return PANN_ERR_BAD_ARG; }
-  if (!m.by_labels()) {       // (a labeled call has been through label_checks)
-    if (!m.allow) { set_error("pann_batch_search_masked: null allow bitmap"); return PANN_ERR_BAD_ARG; }
-    if (int rc = allow_stride_check("pann_batch_search_masked", "one shared bitmap", m.stride, idx->ix.n)) return rc;
-  }
+  if (F.mode == MASK_BITMAP) { if (int rc = filter_checks(idx, "pann_batch_search_masked", F, nq)) return rc; }
   if (out->out_k > 64) { set_error("pann_batch_search_masked: out_k > 64 is not supported"); return PANN_ERR_UNSUPPORTED; }
   return PANN_OK;
 }
@@ -610,9 +629,10 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
                                  uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
                                  uint32_t nstarts, const pann_query_params* qp,
                                  const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
-                                 uint64_t sq_stride, uint32_t* d_pruned, const MaskArgs* mask = nullptr) {
+                                 uint64_t sq_stride, uint32_t* d_pruned, const PointFilter* points = nullptr,
+                                 uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr) {
   if (int rc = search_common_checks(idx, nq, qp, d_out)) return rc;
-  if (mask) { if (int rc = mask_checks(idx, *mask, qp, d_out)) return rc; }
+  if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, d_out)) return rc; }
   if (filter) { if (int rc = refuse_4bit(idx, "pann_batch_search_filtered_dev")) return rc; }
   if (!d_starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if (d_queries && q_stride_bytes < idx->ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
@@ -624,7 +644,7 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
   a.dcap = idx->dcap;
   a.out = *d_out;
   a.filter = filter; a.sketch_queries = (const uint8_t*)d_sketch_queries; a.sq_stride = sq_stride; a.pruned_cmps = d_pruned;
-  if (mask) { mask->apply(a); a.result_count = mask->result_count; a.allowed_cmps = mask->allowed_cmps; }
+  if (points) { points->apply(a); a.result_count = d_result_count; a.allowed_cmps = d_allowed_cmps; }
   if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
   return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, (hipStream_t)stream);
 }
@@ -648,8 +668,9 @@ int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const u
                                  uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
                                  const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
-  const MaskArgs m{d_allow, allow_stride_words, d_out_result_count, d_out_allowed_cmps};
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &m);
+  const PointFilter F = PointFilter::bitmap(d_allow, allow_stride_words, nq, true);
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
+                               d_out_result_count, d_out_allowed_cmps);
 }
 
 int pann_batch_search_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
@@ -657,10 +678,10 @@ int pann_batch_search_labeled_dev(pann_index* idx, const void* d_queries, const 
                                   int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_search_out* d_out,
                                   uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
   if (int rc = check_idx(idx, "pann_batch_search_labeled_dev")) return rc;
-  const LabelArgs l{kind, d_preds, npreds};
-  if (int rc = label_checks(idx, "pann_batch_search_labeled_dev", l, nq, true)) return rc;
-  const MaskArgs m = label_mask(idx, l, d_preds, d_out_result_count, d_out_allowed_cmps);
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &m);
+  const PointFilter F = label_filter(idx, kind, d_preds, npreds, true);
+  if (int rc = filter_checks(idx, "pann_batch_search_labeled_dev", F, nq)) return rc;
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
+                               d_out_result_count, d_out_allowed_cmps);
 }
 
 }  // extern "C"
@@ -763,13 +784,36 @@ struct HostTrip {
   }
 };
 
+// A point filter on a host trip.  The constructor adds the filter's host arrays to t.in where it is called (the packed layout and the
+// small-before-large rule of direct pieces depend on the place): the table index of every query, then the predicates or the bitmap rows
+// packed to ceil(n / 32) words each.  After t.begin(), on_device() is the same filter on the staged copies.  `host` null: no filter.
+struct StagedFilter {
+  PointFilter f;
+  int i_group = -1, i_rows = -1; uint64_t words;
+  StagedFilter(HostTrip& t, const PointFilter* host, uint64_t n, uint64_t nq) : words(PointFilter::row_words(n)) {
+    if (!host) return;
+    f = *host;
+    if (f.is_table()) i_group = t.in.add(f.group, (size_t)nq * 4);
+    // (a stride of 0 goes with one row -- the shared bitmap, or a table with G == 1 -- where the stride is never applied)
+    i_rows = f.mode == MASK_LABELS ? t.in.add(f.preds, (size_t)f.count * sizeof(pann_label_pred))
+                                   : t.in.add_rows(f.allow, (size_t)f.count, words * 4, (size_t)(f.stride ? f.stride : words) * 4);
+  }
+  PointFilter on_device(const HostTrip& t) const {
+    PointFilter d = f; d.dev = true;
+    if (i_group >= 0) d.group = t.din<uint32_t>(i_group);
+    if (f.mode == MASK_LABELS) d.preds = t.din<pann_label_pred>(i_rows);
+    else if (f.mode == MASK_BITMAP) { d.allow = t.din<uint32_t>(i_rows); d.stride = f.shared() ? 0 : words; }
+    return d;
+  }
+};
+
 static int batch_search_host(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int per_query,
                              const pann_query_params* qp, const pann_search_out* out, int filter = 0,
                              const void* sketch_queries = nullptr, uint64_t sq_stride = 0, uint32_t* out_pruned = nullptr,
-                             const MaskArgs* mask = nullptr) {
+                             const PointFilter* points = nullptr, uint32_t* result_count = nullptr, uint32_t* allowed_cmps = nullptr) {
   if (int rc = search_common_checks(idx, nq, qp, out)) return rc;
-  if (mask) { if (int rc = mask_checks(idx, *mask, qp, out)) return rc; }
+  if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, out)) return rc; }
   uint32_t sk_row = 0;
   if (filter) {
     if (int rc = refuse_4bit(idx, "pann_batch_search_filtered")) return rc;
@@ -797,11 +841,7 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   HostTrip t(idx, true);
   const int i_q = queries ? t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack) : t.in.add(query_ids, nq * 4);
   const int i_st = t.in.add(starts, (size_t)nst_total * 4);
-  // masked: the bitmap rows travel with them, packed to ceil(n / 32) words per row; labeled: the predicates, 8 bytes per query
-  const size_t mwords = (size_t)((ix.n + 31) / 32);
-  const bool lab = mask && mask->by_labels();
-  const int i_mask = !mask ? -1 : lab ? t.in.add(mask->preds, (mask->pred_stride ? (size_t)nq : 1) * sizeof(pann_label_pred))
-                                      : t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4);
+  const StagedFilter staged(t, points, ix.n, nq);      // masked / labeled: the bitmap rows or the predicates travel with them
   const int i_sk = filter ? t.in.add_rows(sketch_queries, nq, sk_row, sq_stride) : -1;      // filtered: the sketch rows, dense
   // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
   const size_t ok = out->out_k, vc = out->visited_cap;
@@ -810,12 +850,12 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   const int o_cmps = t.out.add(out->dist_cmps, nq * 4), o_deg = t.out.add(out->degree_sum, nq * 4);
   const int o_vids = t.out.add(out->visited_ids, nq * vc * 4), o_vdists = t.out.add(out->visited_dists, nq * vc * 4);
   const int o_pruned = t.out.add(filter ? out_pruned : nullptr, nq * 4);
-  const int o_rcnt = t.out.add(mask ? mask->result_count : nullptr, nq * 4), o_acmps = t.out.add(mask ? mask->allowed_cmps : nullptr, nq * 4);
+  const int o_rcnt = t.out.add(points ? result_count : nullptr, nq * 4), o_acmps = t.out.add(points ? allowed_cmps : nullptr, nq * 4);
   if (int rc = t.begin()) return rc;
   const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
   const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
-  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask && !lab ? t.din<uint32_t>(i_mask) : nullptr;
-  const pann_label_pred* d_preds = lab ? t.din<pann_label_pred>(i_mask) : nullptr;
+  const uint32_t* d_starts = t.din<uint32_t>(i_st);
+  const PointFilter d_filter = staged.on_device(t);
   const uint8_t* d_sk = filter ? t.din<uint8_t>(i_sk) : nullptr;
   uint32_t status = 0;
   if (int rc = t.run_grown(nq, qp, "pann_batch_search", &status,
@@ -838,10 +878,8 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
         a.sketch_queries = d_sk ? d_sk + q0 * sk_row : nullptr; a.sq_stride = sk_row;
         a.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
       }
-      if (mask) {
-        mask->apply(a);
-        if (lab) a.preds = d_preds + q0 * mask->pred_stride;
-        else { a.allow = mask->stride ? d_allow + q0 * mwords : d_allow; a.allow_stride = mask->stride ? mwords : 0; }
+      if (points) {
+        d_filter.slice(q0, cnt).apply(a);
         a.result_count = t.dout<uint32_t>(o_rcnt, q0); a.allowed_cmps = t.dout<uint32_t>(o_acmps, q0);
       }
       if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
@@ -873,8 +911,9 @@ int pann_batch_search_masked(pann_index* idx, const void* queries, const uint32_
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                              const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
                              uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
-  const MaskArgs m{allow, allow_stride_words, out_result_count, out_allowed_cmps};
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &m);
+  const PointFilter F = PointFilter::bitmap(allow, allow_stride_words, nq, false);
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
+                           out_allowed_cmps);
 }
 
 int pann_batch_search_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
@@ -882,10 +921,10 @@ int pann_batch_search_labeled(pann_index* idx, const void* queries, const uint32
                               int kind, const pann_label_pred* preds, uint64_t npreds, const pann_search_out* out,
                               uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
   if (int rc = check_idx(idx, "pann_batch_search_labeled")) return rc;
-  const LabelArgs l{kind, preds, npreds};
-  if (int rc = label_checks(idx, "pann_batch_search_labeled", l, nq, false)) return rc;
-  const MaskArgs m = label_mask(idx, l, preds, out_result_count, out_allowed_cmps);      // preds: host, staged by batch_search_host
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &m);
+  const PointFilter F = label_filter(idx, kind, preds, npreds, false);
+  if (int rc = filter_checks(idx, "pann_batch_search_labeled", F, nq)) return rc;
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
+                           out_allowed_cmps);
 }
 
 int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
@@ -1195,11 +1234,10 @@ int pann_leaf_knn_batch(pann_index* idx, const uint32_t* ids, const uint64_t* le
   if (total == 0) return PANN_OK;
   for (uint64_t i = 0; i < total; i++)
     if (ids[i] >= idx->ix.n) { set_error("pann_leaf_knn: id out of range"); return PANN_ERR_BAD_ARG; }
-  std::vector<uint32_t> tseg, ta0;
-  for (uint64_t s = 0; s < nleaves; s++) {
+  for (uint64_t s = 0; s < nleaves; s++)
     if (leaf_offsets[s + 1] < leaf_offsets[s]) { set_error("pann_leaf_knn: offsets not monotone"); return PANN_ERR_BAD_ARG; }
-    for (uint64_t a = leaf_offsets[s]; a < leaf_offsets[s + 1]; a += 64) { tseg.push_back((uint32_t)s); ta0.push_back((uint32_t)a); }
-  }
+  std::vector<uint32_t> tseg, ta0;
+  append_tiles(leaf_offsets, nleaves, std::back_inserter(tseg), std::back_inserter(ta0));
   DeviceGuard g(idx->device);
   const size_t nt = tseg.size();
   HostTrip t(idx);
@@ -1212,9 +1250,13 @@ int pann_leaf_knn_batch(pann_index* idx, const uint32_t* ids, const uint64_t* le
   if (leaf_knn_rows_eligible(idx->ix, m)) {     // one-byte element types: lane-owns-row kernel (leaf_knn.hip)
     if (int rc = leaf_knn_rows_dev(idx->ix, idx->ws2, t.st, d_ids, d_off, leaf_offsets, nleaves, m, 1, t.dout<uint32_t>(o_ids),
                                    t.dout<float>(o_dists))) return rc;
-  } else if (int rc = dense_topk_dev(idx->ix, idx->ws2, t.st, nullptr, 0, d_ids, d_ids, d_off, d_off, t.din<uint32_t>(i_tseg),
-                                     t.din<uint32_t>(i_ta0), (uint32_t)nt, total, total, 1, m, 1, t.dout<uint32_t>(o_ids),
-                                     t.dout<float>(o_dists))) return rc;
+  } else {
+    DenseTopkCall c;
+    c.a_ids = c.b_ids = d_ids; c.a_off = c.b_off = d_off; c.tile_seg = t.din<uint32_t>(i_tseg); c.tile_a0 = t.din<uint32_t>(i_ta0);
+    c.ntiles = (uint32_t)nt; c.na = c.nb = total; c.m = m; c.exclude_same = 1;
+    c.out_ids = t.dout<uint32_t>(o_ids); c.out_dists = t.dout<float>(o_dists);
+    if (int rc = dense_topk_dev(idx->ix, idx->ws2, t.st, c)) return rc;
+  }
   return t.finish();
 }
 
@@ -1253,14 +1295,15 @@ int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint6
   const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
   const int o_ids = t.out.add(out_ids, nq * k * 4), o_dists = t.out.add(out_dists, nq * k * 4);
   if (int rc = t.begin()) return rc;
-  const uint32_t ntiles = (uint32_t)((nq + 63) / 64);
-  const uint32_t nsplit = choose_gt_pieces(idx, ntiles, (double)dense_gt_slots(idx->ix, k), idx->ix.n);
-  if (int rc = dense_topk_dev(idx->ix, idx->ws2, t.st, t.din<uint8_t>(i_q), q_stride_bytes, nullptr, nullptr, nullptr, nullptr, nullptr,
-                              nullptr, ntiles, nq, idx->ix.n, nsplit, k, 0, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists))) return rc;
+  DenseTopkCall c;
+  c.a_ext = t.din<uint8_t>(i_q); c.a_stride = q_stride_bytes; c.ntiles = (uint32_t)((nq + 63) / 64); c.na = nq; c.nb = idx->ix.n;
+  c.nsplit = choose_gt_pieces(idx, c.ntiles, (double)dense_gt_slots(idx->ix, k), idx->ix.n); c.m = k;
+  c.out_ids = t.dout<uint32_t>(o_ids); c.out_dists = t.dout<float>(o_dists);
+  if (int rc = dense_topk_dev(idx->ix, idx->ws2, t.st, c)) return rc;
   return t.finish();
 }
 
-// ---- exact kNN under an allow bitmap (masked_knn.hip, DESIGN.md "Exact masked kNN") ----
+// ---- exact kNN under a point filter (masked_knn.hip; DESIGN.md "Exact masked kNN", "Label predicates") ----
 
 int pann_allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uint64_t allow_stride_words, uint32_t* d_counts,
                          void* stream) {
@@ -1270,36 +1313,25 @@ int pann_allow_count_dev(const uint32_t* d_allow, uint64_t n, uint64_t rows, uin
   return allow_count_dev(d_allow, n, allow_stride_words ? rows : 1, allow_stride_words, d_counts, (hipStream_t)stream);
 }
 
-// everything that is refused before anything is launched, allocated or written (host and device entry alike)
-// lab (pann_bruteforce_knn_labeled*): predicates in place of the bitmap -- one for the batch is the shared route, nq the per-query one
-static int masked_knn_checks(const pann_index* idx, const char* fn, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
-                             const uint32_t* allow, uint64_t stride, const uint32_t* out_ids, const float* out_dists, bool* done,
-                             const LabelArgs* lab = nullptr, bool dev = false) {
-  *done = false;
-  if (int rc = check_idx_no4(idx, fn)) return rc;
-  if (nq == 0) { *done = true; return PANN_OK; }
+// everything that is refused, behind the handle's own checks, before anything is launched, allocated or written: the arguments, the filter,
+// the queries and k -- one filter or a table is the dense route, k <= 128; one per query the scan, k <= 64 -- and, behind those, a table's rules
+static int filtered_knn_checks(const pann_index* idx, const char* fn, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                               const PointFilter& F, const uint32_t* out_ids, const float* out_dists) {
   if (!queries || !out_ids || !out_dists) { set_error(std::string(fn) + ": null argument"); return PANN_ERR_BAD_ARG; }
-  if (lab) {
-    if (int rc = label_checks(idx, fn, *lab, nq, dev)) return rc;
-  } else {
-    if (!allow) { set_error(std::string(fn) + ": null allow bitmap"); return PANN_ERR_BAD_ARG; }
-    if (int rc = allow_stride_check(fn, "one shared bitmap", stride, idx->ix.n)) return rc;
-  }
-  const bool per_query = lab ? lab->npreds != 1 : stride != 0;
+  if (int rc = filter_checks(idx, fn, F, nq)) return rc;
   if (q_stride_bytes < idx->ix.dbytes) { set_error(std::string(fn) + ": query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
   if (k == 0) { set_error(std::string(fn) + ": k == 0"); return PANN_ERR_BAD_ARG; }
-  if (k > (per_query ? 64u : 128u)) {
-    set_error(std::string(fn) + (per_query ? ": k > 64 with per-query bitmaps or predicates is not supported" : ": k > 128 is not supported"));
+  if (k > (F.per_query() ? 64u : 128u)) {
+    set_error(std::string(fn) + (F.per_query() ? ": k > 64 with per-query bitmaps or predicates is not supported" : ": k > 128 is not supported"));
     return PANN_ERR_UNSUPPORTED;
   }
-  return PANN_OK;
+  return F.is_table() ? table_checks(idx, fn, F) : PANN_OK;
 }
 
-// both routes on device pointers, after the checks.  Shared bitmap: SYNCHRONISES st (the allowed count sizes the launch).
+// The routes, on device pointers.  One bitmap: its id list, then the dense kernels on the list.  SYNCHRONISES st (the count sizes the launch).
 static int masked_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, const uint32_t* d_allow,
-                          uint64_t stride, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+                          uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
   const DeviceIndex& ix = idx->ix;
-  if (stride) return masked_scan_dev(ix, st, d_q, q_stride_bytes, nq, d_allow, stride, k, d_ids, d_dists, d_counts);
   if (int rc = idx->ws3.ensure(allow_compact_scratch_bytes(ix.n))) return rc;
   const uint32_t* d_total = nullptr;
   if (int rc = allow_compact_count_dev(d_allow, ix.n, (uint32_t*)idx->ws3.buf, &d_total, st)) return rc;
@@ -1311,157 +1343,32 @@ static int masked_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint
   uint32_t* d_list = (uint32_t*)idx->ws4.buf;
   if (int rc = allow_compact_scatter_dev(d_allow, ix.n, (const uint32_t*)idx->ws3.buf, d_list, count, st)) return rc;
   // the list as B rows makes the launch one of the LDS-list kernels: one workgroup per CU
-  const uint32_t ntiles = (uint32_t)((nq + 63) / 64);
-  const uint32_t nsplit = choose_gt_pieces(idx, ntiles, 256.0, count);
-  if (int rc = dense_topk_dev(ix, idx->ws2, st, d_q, q_stride_bytes, nullptr, d_list, nullptr, nullptr, nullptr, nullptr, ntiles, nq,
-                              count, nsplit, k, 0, d_ids, d_dists)) return rc;
+  DenseTopkCall c;
+  c.a_ext = d_q; c.a_stride = q_stride_bytes; c.b_ids = d_list; c.ntiles = (uint32_t)((nq + 63) / 64); c.na = nq; c.nb = count;
+  c.nsplit = choose_gt_pieces(idx, c.ntiles, 256.0, count); c.m = k; c.out_ids = d_ids; c.out_dists = d_dists;
+  if (int rc = dense_topk_dev(ix, idx->ws2, st, c)) return rc;
   return knn_pad_dev(nullptr, nullptr, d_counts, nq, k, std::min(count, k), 0, st);
 }
 
-int pann_bruteforce_knn_masked_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
-                                   const uint32_t* d_allow, uint64_t allow_stride_words, uint32_t* d_out_ids, float* d_out_dists,
-                                   uint32_t* d_out_counts, void* stream) {
-  bool done;
-  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_masked_dev", d_queries, nq, q_stride_bytes, k, d_allow, allow_stride_words,
-                                 d_out_ids, d_out_dists, &done)) return rc;
-  if (done) return PANN_OK;
-  DeviceGuard g(idx->device);
-  return masked_knn_run(idx, (const uint8_t*)d_queries, nq, q_stride_bytes, k, d_allow, allow_stride_words, d_out_ids, d_out_dists,
-                        d_out_counts, (hipStream_t)stream);
-}
-
-int pann_bruteforce_knn_masked(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
-                               const uint32_t* allow, uint64_t allow_stride_words, uint32_t* out_ids, float* out_dists,
-                               uint32_t* out_counts) {
-  bool done;
-  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_masked", queries, nq, q_stride_bytes, k, allow, allow_stride_words, out_ids,
-                                 out_dists, &done)) return rc;
-  if (done) return PANN_OK;
-  DeviceGuard g(idx->device);
+// One predicate for the batch: its bitmap row is expanded into the handle's scratch and the route above runs on it
+static int labeled_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, const PointFilter& F,
+                           uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
   const DeviceIndex& ix = idx->ix;
-  // in: the queries and the bitmap rows, packed to ceil(n / 32) words each, in one transfer (as pann_batch_search_masked)
-  HostTrip t(idx);
-  const size_t mwords = (size_t)((ix.n + 31) / 32);
-  const int i_mask = t.in.add_rows(allow, allow_stride_words ? (size_t)nq : 1, mwords * 4, (size_t)allow_stride_words * 4);
-  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack);
-  // out: counts, ids and dists in one region (the small one first: ids and dists can be large enough to travel on their own)
-  const size_t row_bytes = (size_t)nq * k * 4;
-  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
-  if (int rc = t.begin()) return rc;
-  if (int rc = masked_knn_run(idx, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, t.din<uint32_t>(i_mask),
-                              allow_stride_words ? mwords : 0, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists), t.dout<uint32_t>(o_counts),
-                              t.st)) return rc;
-  return t.finish();
-}
-
-// ---- label predicates on the exact route and the two helpers (masked_knn.hip, DESIGN.md "Label predicates") ----
-
-// both routes on device pointers, after the checks.  One predicate: its bitmap row is expanded into the handle's scratch and the
-// shared-bitmap route runs on it (SYNCHRONISES st, as masked_knn_run says); nq predicates: the label scan, nothing materialised
-static int labeled_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, const LabelArgs& l,
-                           const pann_label_pred* d_preds, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
-  const DeviceIndex& ix = idx->ix;
-  if (l.npreds != 1) return label_scan_dev(ix, st, d_q, q_stride_bytes, nq, ix.labels, l.kind, d_preds, k, d_ids, d_dists, d_counts);
-  const uint64_t words = (ix.n + 31) / 32;
+  const uint64_t words = PointFilter::row_words(ix.n);
   if (int rc = idx->label_row.ensure((size_t)words * 4)) return rc;
-  if (int rc = labels_to_allow_dev(ix.labels, ix.n, l.kind, d_preds, 1, idx->label_row.as<uint32_t>(), words, st)) return rc;
-  return masked_knn_run(idx, d_q, nq, q_stride_bytes, k, idx->label_row.as<uint32_t>(), 0, d_ids, d_dists, d_counts, st);
-}
-
-int pann_bruteforce_knn_labeled_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
-                                    int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_out_ids,
-                                    float* d_out_dists, uint32_t* d_out_counts, void* stream) {
-  bool done;
-  const LabelArgs l{kind, d_preds, npreds};
-  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_labeled_dev", d_queries, nq, q_stride_bytes, k, nullptr, 0, d_out_ids,
-                                 d_out_dists, &done, &l, true)) return rc;
-  if (done) return PANN_OK;
-  DeviceGuard g(idx->device);
-  return labeled_knn_run(idx, (const uint8_t*)d_queries, nq, q_stride_bytes, k, l, d_preds, d_out_ids, d_out_dists, d_out_counts,
-                         (hipStream_t)stream);
-}
-
-int pann_bruteforce_knn_labeled(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int kind,
-                                const pann_label_pred* preds, uint64_t npreds, uint32_t* out_ids, float* out_dists,
-                                uint32_t* out_counts) {
-  bool done;
-  const LabelArgs l{kind, preds, npreds};
-  if (int rc = masked_knn_checks(idx, "pann_bruteforce_knn_labeled", queries, nq, q_stride_bytes, k, nullptr, 0, out_ids, out_dists,
-                                 &done, &l, false)) return rc;
-  if (done) return PANN_OK;
-  DeviceGuard g(idx->device);
-  // in: the predicates (8 bytes each) and the queries in one transfer; out: as pann_bruteforce_knn_masked
-  HostTrip t(idx);
-  const int i_pred = t.in.add(preds, (size_t)npreds * sizeof(pann_label_pred));
-  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
-  const size_t row_bytes = (size_t)nq * k * 4;
-  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
-  if (int rc = t.begin()) return rc;
-  if (int rc = labeled_knn_run(idx, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, l, t.din<pann_label_pred>(i_pred), t.dout<uint32_t>(o_ids),
-                               t.dout<float>(o_dists), t.dout<uint32_t>(o_counts), t.st)) return rc;
-  return t.finish();
-}
-
-// the checks of the two helpers: a handle with labels, a known kind, device pointers that are there and aligned
-static int label_helper_checks(const pann_index* idx, const char* fn, int kind, const pann_label_pred* d_preds, const uint32_t* d_out) {
-  if (int rc = check_idx(idx, fn)) return rc;
-  if (!d_out) { set_error(std::string(fn) + ": null output"); return PANN_ERR_BAD_ARG; }
-  if ((uintptr_t)d_out % 4 != 0) { set_error(std::string(fn) + ": the output must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
-  return label_checks(idx, fn, LabelArgs{kind, d_preds, 1}, 1, true);      // (any number of predicates: nothing to match it with)
-}
-
-int pann_labels_to_allow_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_allow,
-                             uint64_t allow_stride_words, void* stream) {
-  if (int rc = label_helper_checks(idx, "pann_labels_to_allow_dev", kind, d_preds, d_allow)) return rc;
-  if (allow_stride_words < (idx->ix.n + 31) / 32) {
-    set_error("pann_labels_to_allow_dev: allow_stride_words must be at least ceil(n / 32) = " + std::to_string((idx->ix.n + 31) / 32));
-    return PANN_ERR_BAD_ARG;
-  }
-  DeviceGuard g(idx->device);
-  return labels_to_allow_dev(idx->ix.labels, idx->ix.n, kind, d_preds, npreds, d_allow, allow_stride_words, (hipStream_t)stream);
-}
-
-int pann_label_count_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_counts,
-                         void* stream) {
-  if (int rc = label_helper_checks(idx, "pann_label_count_dev", kind, d_preds, d_counts)) return rc;
-  DeviceGuard g(idx->device);
-  return label_count_dev(idx->ix.labels, idx->ix.n, kind, d_preds, npreds, d_counts, (hipStream_t)stream);
+  if (int rc = labels_to_allow_dev(F.labels, ix.n, F.kind, F.preds, 1, idx->label_row.as<uint32_t>(), words, st)) return rc;
+  return masked_knn_run(idx, d_q, nq, q_stride_bytes, k, idx->label_row.as<uint32_t>(), d_ids, d_dists, d_counts, st);
 }
 
 // ---- exact kNN by predicate group (masked_knn.hip, DESIGN.md "Exact kNN by predicate group") ----
 
-constexpr uint64_t kGroupedListIds = 16ull << 20;      // max_list_ids == 0 (include/pann.h): 64 MB of ids, as much again of bitmap rows
-
-// the filter table of a grouped call on the device: predicates over the handle's labels (d_preds) or bitmap rows (d_allow)
-struct GroupedTable {
-  int kind; const pann_label_pred* d_preds;
-  const uint32_t* d_allow; uint64_t stride;
-  uint64_t G; const uint32_t* d_group; uint64_t max_list_ids;
-};
-
-// what is refused before anything is launched, beyond the twin's own checks (masked_knn_checks, called with one filter: k <= 128)
-static int grouped_checks(const pann_index* idx, const char* fn, uint64_t G, const uint32_t* group, const uint32_t* allow, uint64_t stride) {
-  const std::string f = fn;
-  if (G == 0) { set_error(f + ": an empty filter table"); return PANN_ERR_BAD_ARG; }
-  if (G > 0xFFFFFFFFull) { set_error(f + ": more than 2^32 - 1 table entries"); return PANN_ERR_BAD_ARG; }
-  if (!group) { set_error(f + ": null index array"); return PANN_ERR_BAD_ARG; }
-  if (allow && stride < (idx->ix.n + 31) / 32 && !(stride == 0 && G == 1)) {
-    set_error(f + ": allow_stride_words must be at least ceil(n / 32) = " + std::to_string((idx->ix.n + 31) / 32));
-    return PANN_ERR_BAD_ARG;
-  }
-  return PANN_OK;
-}
-
-// One chunk of the plan: the used table entries [u0, u1) as the segments of one dense launch.
-struct GroupedChunk { size_t u0, u1; uint64_t a_base, na, ids, max_ids; uint32_t ntiles; size_t o_aoff, o_boff, o_tseg, o_ta0; };
-
-// Everything on device pointers, after the checks.  SYNCHRONISES st once: the flag of the range check, the queries per table entry
-// and the allowed points per table entry come back in one read, and the chunks, segments and tiles are planned from them.
+// A table of filters.  SYNCHRONISES st once: the flag of the range check, the queries per table entry and the allowed points per
+// table entry come back in one read, and the chunks, segments and tiles are planned from them (grouped_plan.h).
 static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
-                           const GroupedTable& T, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+                           const PointFilter& T, uint64_t max_list_ids, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
   const DeviceIndex& ix = idx->ix;
-  const uint64_t G = T.G, words = (ix.n + 31) / 32, stride = T.stride ? T.stride : words;
-  const bool lab = T.d_preds != nullptr;
+  const uint64_t G = T.count, words = PointFilter::row_words(ix.n), stride = T.stride ? T.stride : words;
+  const bool lab = T.mode == MASK_LABELS;
   // ---- before the read-back: sort the queries by table index, count what every entry allows ----
   uint32_t nblocks; uint64_t per_block;
   group_sort_shape(nq, G, &nblocks, &per_block);
@@ -1469,184 +1376,193 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
   if (int rc = idx->grp_sort.ensure((head_words + (size_t)G + 1 + (size_t)nblocks * G + (size_t)nq) * 4)) return rc;
   uint32_t* d_head = idx->grp_sort.as<uint32_t>();
   uint32_t* d_hist = d_head + 1, *d_allowed = d_hist + G, *d_off = d_allowed + G, *d_part = d_off + G + 1, *d_perm = d_part + (size_t)nblocks * G;
-  if (int rc = group_queries_dev(T.d_group, nq, G, d_head, d_hist, d_off, d_part, d_perm, st)) return rc;
-  if (lab) { if (int rc = label_count_dev(ix.labels, ix.n, T.kind, T.d_preds, G, d_allowed, st)) return rc; }
-  else if (int rc = allow_count_dev(T.d_allow, ix.n, G, stride, d_allowed, st)) return rc;
+  if (int rc = group_queries_dev(T.group, nq, G, d_head, d_hist, d_off, d_part, d_perm, st)) return rc;
+  if (lab) { if (int rc = label_count_dev(T.labels, ix.n, T.kind, T.preds, G, d_allowed, st)) return rc; }
+  else if (int rc = allow_count_dev(T.allow, ix.n, G, stride, d_allowed, st)) return rc;
   if (int rc = idx->grp_pin.ensure(head_words * 4)) return rc;
   PANN_HIP(hipMemcpyAsync(idx->grp_pin.p, d_head, head_words * 4, hipMemcpyDeviceToHost, st));
   PANN_HIP(hipStreamSynchronize(st));
   const std::vector<uint32_t> head((const uint32_t*)idx->grp_pin.p, (const uint32_t*)idx->grp_pin.p + head_words);
   if (head[0]) { set_error(std::string(fn) + ": a query's table index is out of range (>= " + std::to_string(G) + ")"); return PANN_ERR_BAD_ARG; }
   const uint32_t* hist = head.data() + 1, *allowed = hist + G;
-
-  // ---- the plan: chunks of consecutive used entries whose lists fit the budget; an entry larger than it is a chunk alone ----
-  const uint64_t budget = std::min<uint64_t>(T.max_list_ids ? T.max_list_ids : kGroupedListIds, 0x7FFFFFFFull);
-  const uint64_t row_cap = lab ? std::max<uint64_t>(1, budget / std::max<uint64_t>(words, 1)) : UINT64_MAX;   // label form: the rows' words fit it too
-  std::vector<uint32_t> used;
-  std::vector<uint64_t> first;                        // first slot of every used entry (the scan of hist), and nq behind them
-  { uint64_t run = 0; for (uint64_t g = 0; g < G; g++) if (hist[g]) { used.push_back((uint32_t)g); first.push_back(run); run += hist[g]; } first.push_back(run); }
-  const size_t U = used.size();
-  auto al8 = [](size_t x) { return (x + 7) & ~(size_t)7; };
-  size_t plan_bytes = al8(U * 4);
-  std::vector<GroupedChunk> chunks;
-  for (size_t u = 0; u < U;) {
-    GroupedChunk c{u, u, first[u], 0, 0, 0, 0, 0, 0, 0, 0};
-    while (c.u1 < U && (c.u1 == c.u0 || (c.ids + allowed[used[c.u1]] <= budget && c.u1 - c.u0 < row_cap))) {
-      const uint64_t cg = allowed[used[c.u1]];
-      c.ids += cg; c.max_ids = std::max(c.max_ids, cg);
-      c.ntiles += (uint32_t)((hist[used[c.u1]] + 63) / 64);
-      c.u1++;
-    }
-    c.na = first[c.u1] - c.a_base;
-    const size_t S = c.u1 - c.u0;
-    c.o_aoff = plan_bytes; c.o_boff = c.o_aoff + (S + 1) * 8; c.o_tseg = c.o_boff + (S + 1) * 8; c.o_ta0 = c.o_tseg + al8((size_t)c.ntiles * 4);
-    plan_bytes = c.o_ta0 + al8((size_t)c.ntiles * 4);
-    chunks.push_back(c);
-    u = c.u1;
-  }
-  if (int rc = idx->grp_pin.ensure(plan_bytes)) return rc;      // (the read-back has been copied out of it)
+  // ---- the plan, written into pinned memory (the read-back has been copied out of it) ----
+  const uint64_t budget = grouped_budget(max_list_ids);
+  const GroupedPlan plan(hist, allowed, G, budget, grouped_row_cap(budget, words, lab));
+  const size_t U = plan.used.size();
+  if (int rc = idx->grp_pin.ensure(plan.plan_bytes)) return rc;
   uint8_t* hp = (uint8_t*)idx->grp_pin.p;
-  memcpy(hp, used.data(), U * 4);
-  size_t max_rows = 0, max_na = 0; uint64_t max_ids = 0;
-  for (const GroupedChunk& c : chunks) {
-    uint64_t* a_off = (uint64_t*)(hp + c.o_aoff), *b_off = (uint64_t*)(hp + c.o_boff);
-    uint32_t* tseg = (uint32_t*)(hp + c.o_tseg), *ta0 = (uint32_t*)(hp + c.o_ta0);
-    uint64_t b = 0; uint32_t t = 0;
-    for (size_t u = c.u0; u < c.u1; u++) {
-      const size_t s = u - c.u0;
-      a_off[s] = first[u] - c.a_base; b_off[s] = b;
-      b += allowed[used[u]];
-      for (uint64_t a = a_off[s]; a < first[u + 1] - c.a_base; a += 64) { tseg[t] = (uint32_t)s; ta0[t] = (uint32_t)a; t++; }
-    }
-    a_off[c.u1 - c.u0] = c.na; b_off[c.u1 - c.u0] = b;
-    max_rows = std::max(max_rows, c.u1 - c.u0); max_na = std::max<size_t>(max_na, c.na); max_ids = std::max(max_ids, c.ids);
-  }
+  plan.write(allowed, hp);
   // ---- device room for the largest chunk, then the plan goes up in one transfer ----
   const uint32_t a_stride = (ix.dbytes + 15) / 16 * 16;
-  const size_t o_upreds = (plan_bytes + 255) & ~(size_t)255;
+  const size_t o_upreds = (plan.plan_bytes + 255) & ~(size_t)255;
   if (int rc = idx->grp_plan.ensure(o_upreds + (lab ? U * sizeof(pann_label_pred) : 0))) return rc;
-  const size_t o_bc = lab ? (max_rows * words * 4 + 255) & ~(size_t)255 : 0;
-  if (int rc = idx->grp_rows.ensure(o_bc + allow_rows_compact_scratch_bytes(ix.n, max_rows))) return rc;
-  if (int rc = idx->ws4.ensure(std::max<size_t>(max_ids, 1) * 4)) return rc;
-  const size_t o_sids = (max_na * a_stride + kQuerySlack + 255) & ~(size_t)255, o_sdists = o_sids + ((max_na * k * 4 + 255) & ~(size_t)255);
-  if (int rc = idx->grp_io.ensure(o_sdists + max_na * k * 4)) return rc;
+  const size_t o_bc = lab ? (plan.max_rows * words * 4 + 255) & ~(size_t)255 : 0;
+  if (int rc = idx->grp_rows.ensure(o_bc + allow_rows_compact_scratch_bytes(ix.n, plan.max_rows))) return rc;
+  if (int rc = idx->ws4.ensure(std::max<size_t>(plan.max_ids, 1) * 4)) return rc;
+  const size_t o_sids = (plan.max_na * a_stride + kQuerySlack + 255) & ~(size_t)255, o_sdists = o_sids + ((plan.max_na * k * 4 + 255) & ~(size_t)255);
+  if (int rc = idx->grp_io.ensure(o_sdists + plan.max_na * k * 4)) return rc;
   uint8_t* dp = idx->grp_plan.as<uint8_t>();
-  PANN_HIP(hipMemcpyAsync(dp, hp, plan_bytes, hipMemcpyHostToDevice, st));
+  PANN_HIP(hipMemcpyAsync(dp, hp, plan.plan_bytes, hipMemcpyHostToDevice, st));
   const uint32_t* d_used = (const uint32_t*)dp;
   pann_label_pred* d_upreds = (pann_label_pred*)(dp + o_upreds);
-  if (lab) { if (int rc = gather_preds_dev(T.d_preds, d_used, U, d_upreds, st)) return rc; }
-  uint32_t* d_rows = idx->grp_rows.as<uint32_t>();
-  uint32_t* d_bc = (uint32_t*)(idx->grp_rows.as<uint8_t>() + o_bc);
-  uint32_t* d_list = idx->ws4.as<uint32_t>();
+  if (lab) { if (int rc = gather_preds_dev(T.preds, d_used, U, d_upreds, st)) return rc; }
+  uint32_t* d_rows = idx->grp_rows.as<uint32_t>(), *d_bc = (uint32_t*)(idx->grp_rows.as<uint8_t>() + o_bc), *d_list = idx->ws4.as<uint32_t>();
   uint8_t* d_slab = idx->grp_io.as<uint8_t>();
   uint32_t* d_sids = (uint32_t*)(d_slab + o_sids);
   float* d_sdists = (float*)(d_slab + o_sdists);
   // ---- per chunk: id lists (CSR), query slab, ONE segmented dense launch, rows back to the caller's order ----
-  for (const GroupedChunk& c : chunks) {
+  for (const GroupedChunk& c : plan.chunks) {
     const uint32_t S = (uint32_t)(c.u1 - c.u0);
     if (c.ids) {
       if (lab) {
-        if (int rc = labels_to_allow_dev(ix.labels, ix.n, T.kind, d_upreds + c.u0, S, d_rows, words, st)) return rc;
+        if (int rc = labels_to_allow_dev(T.labels, ix.n, T.kind, d_upreds + c.u0, S, d_rows, words, st)) return rc;
         if (int rc = allow_rows_compact_dev(d_rows, ix.n, nullptr, words, S, d_bc, d_list, (uint32_t)c.ids, st)) return rc;
-      } else if (int rc = allow_rows_compact_dev(T.d_allow, ix.n, d_used + c.u0, stride, S, d_bc, d_list, (uint32_t)c.ids, st)) return rc;
+      } else if (int rc = allow_rows_compact_dev(T.allow, ix.n, d_used + c.u0, stride, S, d_bc, d_list, (uint32_t)c.ids, st)) return rc;
     }
     if (int rc = gather_query_rows_dev(d_q, q_stride_bytes, ix.dbytes, d_perm + c.a_base, c.na, d_slab, a_stride, st)) return rc;
     // the lists as B rows: the LDS-list kernels, one workgroup per CU (as masked_knn_run); the pieces cut every segment's list
-    const uint32_t nsplit = choose_gt_pieces(idx, c.ntiles, 256.0, c.max_ids);
-    if (int rc = dense_topk_dev(ix, idx->ws2, st, d_slab, a_stride, nullptr, d_list, (const uint64_t*)(dp + c.o_aoff),
-                                (const uint64_t*)(dp + c.o_boff), (const uint32_t*)(dp + c.o_tseg), (const uint32_t*)(dp + c.o_ta0),
-                                c.ntiles, c.na, c.ids, nsplit, k, 0, d_sids, d_sdists)) return rc;
+    DenseTopkCall call;
+    call.a_ext = d_slab; call.a_stride = a_stride; call.b_ids = d_list;
+    call.a_off = (const uint64_t*)(dp + c.o_aoff); call.b_off = (const uint64_t*)(dp + c.o_boff);
+    call.tile_seg = (const uint32_t*)(dp + c.o_tseg); call.tile_a0 = (const uint32_t*)(dp + c.o_ta0);
+    call.ntiles = c.ntiles; call.na = c.na; call.nb = c.ids; call.nsplit = choose_gt_pieces(idx, c.ntiles, 256.0, c.max_ids); call.m = k;
+    call.out_ids = d_sids; call.out_dists = d_sdists;
+    if (int rc = dense_topk_dev(ix, idx->ws2, st, call)) return rc;
     if (int rc = scatter_knn_rows_dev(d_sids, d_sdists, d_perm + c.a_base, c.na, k, d_ids, d_dists, d_counts, st)) return rc;
   }
   return PANN_OK;
+}
+
+// the route of a filter: a table -> grouped; one per query -> the scan, which synchronises nothing; one predicate -> its row, then
+// as one bitmap; one bitmap -> compaction and the dense kernels
+static int filtered_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                            const PointFilter& F, uint64_t max_list_ids, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+  if (F.is_table()) return grouped_knn_run(idx, fn, d_q, nq, q_stride_bytes, k, F, max_list_ids, d_ids, d_dists, d_counts, st);
+  if (F.per_query()) return filter_scan_dev(idx->ix, st, d_q, q_stride_bytes, nq, F, k, d_ids, d_dists, d_counts);
+  if (F.mode == MASK_LABELS) return labeled_knn_run(idx, d_q, nq, q_stride_bytes, k, F, d_ids, d_dists, d_counts, st);
+  return masked_knn_run(idx, d_q, nq, q_stride_bytes, k, F.allow, d_ids, d_dists, d_counts, st);
+}
+
+static int filtered_knn_dev(pann_index* idx, const char* fn, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                            const PointFilter& F, uint64_t max_list_ids, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, void* stream) {
+  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (nq == 0) return PANN_OK;
+  if (int rc = filtered_knn_checks(idx, fn, d_queries, nq, q_stride_bytes, k, F, d_ids, d_dists)) return rc;
+  DeviceGuard g(idx->device);
+  return filtered_knn_run(idx, fn, (const uint8_t*)d_queries, nq, q_stride_bytes, k, F, max_list_ids, d_ids, d_dists, d_counts, (hipStream_t)stream);
+}
+
+static int filtered_knn_host(pann_index* idx, const char* fn, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                             const PointFilter& F, uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts) {
+  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (nq == 0) return PANN_OK;
+  if (int rc = filtered_knn_checks(idx, fn, queries, nq, q_stride_bytes, k, F, out_ids, out_dists)) return rc;
+  for (uint64_t q = 0; F.is_table() && q < nq; q++)      // the index array is checked on the host: nothing is staged for a call that will be refused
+    if (F.group[q] >= F.count) {
+      set_error(std::string(fn) + ": table index " + std::to_string(F.group[q]) + " of query " + std::to_string(q) + " is out of range (>= " + std::to_string(F.count) + ")");
+      return PANN_ERR_BAD_ARG;
+    }
+  DeviceGuard g(idx->device);
+  // in: the filter and the queries; out: counts, ids and dists (the small one first: ids and dists can be large enough to travel on their own)
+  HostTrip t(idx);
+  const StagedFilter staged(t, &F, idx->ix.n, nq);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
+  const size_t row_bytes = (size_t)nq * k * 4;
+  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
+  if (int rc = t.begin()) return rc;
+  if (int rc = filtered_knn_run(idx, fn, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, staged.on_device(t), max_list_ids, t.dout<uint32_t>(o_ids),
+                                t.dout<float>(o_dists), t.dout<uint32_t>(o_counts), t.st)) return rc;
+  return t.finish();
+}
+
+int pann_bruteforce_knn_masked_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                   const uint32_t* d_allow, uint64_t allow_stride_words, uint32_t* d_out_ids, float* d_out_dists,
+                                   uint32_t* d_out_counts, void* stream) {
+  return filtered_knn_dev(idx, "pann_bruteforce_knn_masked_dev", d_queries, nq, q_stride_bytes, k,
+                          PointFilter::bitmap(d_allow, allow_stride_words, nq, true), 0, d_out_ids, d_out_dists, d_out_counts, stream);
+}
+
+int pann_bruteforce_knn_masked(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                               const uint32_t* allow, uint64_t allow_stride_words, uint32_t* out_ids, float* out_dists,
+                               uint32_t* out_counts) {
+  return filtered_knn_host(idx, "pann_bruteforce_knn_masked", queries, nq, q_stride_bytes, k,
+                           PointFilter::bitmap(allow, allow_stride_words, nq, false), 0, out_ids, out_dists, out_counts);
+}
+
+int pann_bruteforce_knn_labeled_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
+                                    int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_out_ids,
+                                    float* d_out_dists, uint32_t* d_out_counts, void* stream) {
+  return filtered_knn_dev(idx, "pann_bruteforce_knn_labeled_dev", d_queries, nq, q_stride_bytes, k, label_filter(idx, kind, d_preds, npreds, true), 0,
+                          d_out_ids, d_out_dists, d_out_counts, stream);
+}
+
+int pann_bruteforce_knn_labeled(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int kind,
+                                const pann_label_pred* preds, uint64_t npreds, uint32_t* out_ids, float* out_dists,
+                                uint32_t* out_counts) {
+  return filtered_knn_host(idx, "pann_bruteforce_knn_labeled", queries, nq, q_stride_bytes, k, label_filter(idx, kind, preds, npreds, false), 0,
+                           out_ids, out_dists, out_counts);
+}
+
+// the two helpers: a device output that is there and aligned, then the predicates' checks -- one row or count each, so any number is "one per query"
+static int label_helper_checks(const pann_index* idx, const char* fn, const PointFilter& F, const uint32_t* d_out) {
+  if (int rc = check_idx(idx, fn)) return rc;
+  if (!d_out) { set_error(std::string(fn) + ": null output"); return PANN_ERR_BAD_ARG; }
+  if ((uintptr_t)d_out % 4 != 0) { set_error(std::string(fn) + ": the output must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  return filter_checks(idx, fn, F, F.count);
+}
+
+int pann_labels_to_allow_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_allow,
+                             uint64_t allow_stride_words, void* stream) {
+  const PointFilter F = label_filter(idx, kind, d_preds, npreds, true);
+  if (int rc = label_helper_checks(idx, "pann_labels_to_allow_dev", F, d_allow)) return rc;
+  if (allow_stride_words < PointFilter::row_words(idx->ix.n)) {
+    set_error("pann_labels_to_allow_dev: allow_stride_words must be at least ceil(n / 32) = " + std::to_string(PointFilter::row_words(idx->ix.n)));
+    return PANN_ERR_BAD_ARG;
+  }
+  DeviceGuard g(idx->device);
+  return labels_to_allow_dev(F.labels, idx->ix.n, kind, d_preds, npreds, d_allow, allow_stride_words, (hipStream_t)stream);
+}
+
+int pann_label_count_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t* d_counts,
+                         void* stream) {
+  const PointFilter F = label_filter(idx, kind, d_preds, npreds, true);
+  if (int rc = label_helper_checks(idx, "pann_label_count_dev", F, d_counts)) return rc;
+  DeviceGuard g(idx->device);
+  return label_count_dev(F.labels, idx->ix.n, kind, d_preds, npreds, d_counts, (hipStream_t)stream);
 }
 
 int pann_bruteforce_knn_labeled_grouped_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                                             int kind, const pann_label_pred* d_preds, uint64_t npreds, const uint32_t* d_group_of_query,
                                             uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
                                             void* stream) {
-  const char* fn = "pann_bruteforce_knn_labeled_grouped_dev";
-  bool done;
-  const LabelArgs l{kind, d_preds, 1};           // (the twin's checks with one filter: k <= 128)
-  if (int rc = masked_knn_checks(idx, fn, d_queries, nq, q_stride_bytes, k, nullptr, 0, d_out_ids, d_out_dists, &done, &l, true)) return rc;
-  if (done) return PANN_OK;
-  if (int rc = grouped_checks(idx, fn, npreds, d_group_of_query, nullptr, 0)) return rc;
-  DeviceGuard g(idx->device);
-  const GroupedTable T{kind, d_preds, nullptr, 0, npreds, d_group_of_query, max_list_ids};
-  return grouped_knn_run(idx, fn, (const uint8_t*)d_queries, nq, q_stride_bytes, k, T, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream);
+  return filtered_knn_dev(idx, "pann_bruteforce_knn_labeled_grouped_dev", d_queries, nq, q_stride_bytes, k,
+                          label_filter(idx, kind, d_preds, npreds, true).as_table(d_group_of_query, npreds), max_list_ids, d_out_ids, d_out_dists,
+                          d_out_counts, stream);
 }
 
 int pann_bruteforce_knn_masked_grouped_dev(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                                            const uint32_t* d_allow, uint64_t nrows, uint64_t allow_stride_words,
                                            const uint32_t* d_row_of_query, uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists,
                                            uint32_t* d_out_counts, void* stream) {
-  const char* fn = "pann_bruteforce_knn_masked_grouped_dev";
-  bool done;
-  if (int rc = masked_knn_checks(idx, fn, d_queries, nq, q_stride_bytes, k, d_allow, 0, d_out_ids, d_out_dists, &done)) return rc;
-  if (done) return PANN_OK;
-  if (int rc = grouped_checks(idx, fn, nrows, d_row_of_query, d_allow, allow_stride_words)) return rc;
-  DeviceGuard g(idx->device);
-  const GroupedTable T{0, nullptr, d_allow, allow_stride_words, nrows, d_row_of_query, max_list_ids};
-  return grouped_knn_run(idx, fn, (const uint8_t*)d_queries, nq, q_stride_bytes, k, T, d_out_ids, d_out_dists, d_out_counts, (hipStream_t)stream);
-}
-
-// the host entries check the index array on the host: nothing is staged for a call that will be refused
-static int grouped_index_check(const char* fn, const uint32_t* group, uint64_t nq, uint64_t G) {
-  for (uint64_t q = 0; q < nq; q++)
-    if (group[q] >= G) {
-      set_error(std::string(fn) + ": table index " + std::to_string(group[q]) + " of query " + std::to_string(q) + " is out of range (>= " + std::to_string(G) + ")");
-      return PANN_ERR_BAD_ARG;
-    }
-  return PANN_OK;
+  return filtered_knn_dev(idx, "pann_bruteforce_knn_masked_grouped_dev", d_queries, nq, q_stride_bytes, k,
+                          PointFilter::bitmap(d_allow, allow_stride_words, nq, true).as_table(d_row_of_query, nrows), max_list_ids, d_out_ids,
+                          d_out_dists, d_out_counts, stream);
 }
 
 int pann_bruteforce_knn_labeled_grouped(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int kind,
                                         const pann_label_pred* preds, uint64_t npreds, const uint32_t* group_of_query,
                                         uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts) {
-  const char* fn = "pann_bruteforce_knn_labeled_grouped";
-  bool done;
-  const LabelArgs l{kind, preds, 1};
-  if (int rc = masked_knn_checks(idx, fn, queries, nq, q_stride_bytes, k, nullptr, 0, out_ids, out_dists, &done, &l, false)) return rc;
-  if (done) return PANN_OK;
-  if (int rc = grouped_checks(idx, fn, npreds, group_of_query, nullptr, 0)) return rc;
-  if (int rc = grouped_index_check(fn, group_of_query, nq, npreds)) return rc;
-  DeviceGuard g(idx->device);
-  // in: the index array, the table and the queries in one transfer; out: as pann_bruteforce_knn_masked
-  HostTrip t(idx);
-  const int i_grp = t.in.add(group_of_query, (size_t)nq * 4), i_pred = t.in.add(preds, (size_t)npreds * sizeof(pann_label_pred));
-  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
-  const size_t row_bytes = (size_t)nq * k * 4;
-  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
-  if (int rc = t.begin()) return rc;
-  const GroupedTable T{kind, t.din<pann_label_pred>(i_pred), nullptr, 0, npreds, t.din<uint32_t>(i_grp), max_list_ids};
-  if (int rc = grouped_knn_run(idx, fn, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, T, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists),
-                               t.dout<uint32_t>(o_counts), t.st)) return rc;
-  return t.finish();
+  return filtered_knn_host(idx, "pann_bruteforce_knn_labeled_grouped", queries, nq, q_stride_bytes, k,
+                           label_filter(idx, kind, preds, npreds, false).as_table(group_of_query, npreds), max_list_ids, out_ids, out_dists,
+                           out_counts);
 }
 
 int pann_bruteforce_knn_masked_grouped(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                                        const uint32_t* allow, uint64_t nrows, uint64_t allow_stride_words, const uint32_t* row_of_query,
                                        uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts) {
-  const char* fn = "pann_bruteforce_knn_masked_grouped";
-  bool done;
-  if (int rc = masked_knn_checks(idx, fn, queries, nq, q_stride_bytes, k, allow, 0, out_ids, out_dists, &done)) return rc;
-  if (done) return PANN_OK;
-  if (int rc = grouped_checks(idx, fn, nrows, row_of_query, allow, allow_stride_words)) return rc;
-  if (int rc = grouped_index_check(fn, row_of_query, nq, nrows)) return rc;
-  DeviceGuard g(idx->device);
-  // in: the index array, the rows packed to ceil(n / 32) words each and the queries in one transfer
-  HostTrip t(idx);
-  const size_t mwords = (size_t)((idx->ix.n + 31) / 32);
-  const int i_grp = t.in.add(row_of_query, (size_t)nq * 4);
-  const int i_mask = t.in.add_rows(allow, (size_t)nrows, mwords * 4, (size_t)(allow_stride_words ? allow_stride_words : mwords) * 4);
-  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + idx->ix.dbytes, kQuerySlack);
-  const size_t row_bytes = (size_t)nq * k * 4;
-  const int o_counts = t.out.add(out_counts, nq * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
-  if (int rc = t.begin()) return rc;
-  const GroupedTable T{0, nullptr, t.din<uint32_t>(i_mask), mwords, nrows, t.din<uint32_t>(i_grp), max_list_ids};
-  if (int rc = grouped_knn_run(idx, fn, t.din<uint8_t>(i_q), nq, q_stride_bytes, k, T, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists),
-                               t.dout<uint32_t>(o_counts), t.st)) return rc;
-  return t.finish();
+  return filtered_knn_host(idx, "pann_bruteforce_knn_masked_grouped", queries, nq, q_stride_bytes, k,
+                           PointFilter::bitmap(allow, allow_stride_words, nq, false).as_table(row_of_query, nrows), max_list_ids, out_ids, out_dists,
+                           out_counts);
 }
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,
@@ -2563,50 +2479,47 @@ int search_rerank_checks(const pann_index* full, const pann_index* quant, const 
   return PANN_OK;
 }
 
-// one launch sequence for nq queries with a dropped list of dcap entries; grows quant's workspaces on first use
+// one launch sequence for nq queries with a dropped list of dcap entries; grows quant's workspaces on first use (points: a masked call's filter)
 int search_rerank_launch(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
                          uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
                          const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                         const MaskArgs* mask = nullptr) {
+                         const PointFilter* points = nullptr, uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr) {
   SearchArgs a{};                                  // the fields search_workspace_bytes reads
   a.queries = reinterpret_cast<const uint8_t*>(d_queries); a.nq = nq; a.nstarts = nstarts;
   fill_search_params(a, qp);
   a.dcap = dcap; a.filter = use_filter ? 1 : 0;
-  const uint32_t list = mask ? masked_rerank_pool(qp) : (uint32_t)qp->beam;     // ids kept per query between search and rerank
+  const uint32_t list = points ? masked_rerank_pool(qp) : (uint32_t)qp->beam;     // ids kept per query between search and rerank
   a.out = pann_search_out{}; a.out.out_k = list;
-  a.masked = !mask ? MASK_NONE : mask->by_labels() ? MASK_LABELS : MASK_BITMAP;
+  a.masked = points ? points->mode : MASK_NONE;
   if (int rc = quant->ws.ensure(search_workspace_bytes(quant->ix, a))) return rc;
   if (int rc = quant->ws_rr.ensure(search_rerank_scratch_bytes(quant->ix, nq, list, normalize_first, use_filter))) return rc;
   return search_rerank_dev(full->ix, quant->ix, quant->ws.buf, quant->ws.bytes, quant->ws_rr.buf, qparams, &quant->sk_params, d_queries,
-                           nq, q_stride, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d_out, st, mask);
+                           nq, q_stride, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d_out, st, points, d_result_count, d_allowed_cmps);
 }
 
-// pann_batch_search_masked_rerank*: the rerank checks, then the bitmap's through mask_checks (out_k = the list length)
+// pann_batch_search_{masked,labeled}_rerank*: the rerank checks, then the filter's -- predicates over the labels of `full`, ahead
+// of the masked search's own checks on `quant` (out_k = the list length), which hold the bitmap's
 int masked_rerank_checks(const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
                          uint64_t nq, uint64_t q_stride, int use_filter, const uint32_t* starts, uint32_t nstarts,
-                         const pann_query_params* qp, const uint32_t* allow, uint64_t allow_stride_words, const pann_rerank_out* out,
-                         const char* fn, const LabelArgs* lab = nullptr, bool dev = false) {
+                         const pann_query_params* qp, const PointFilter& F, const pann_rerank_out* out, const char* fn) {
   if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride, 0, starts, nstarts, qp, out, fn)) return rc;
   const std::string f = fn;
   if (use_filter) { set_error(f + ": a mask together with the sketch filter is not supported (use_filter must be 0)"); return PANN_ERR_UNSUPPORTED; }
   pann_search_out so{};
   so.out_k = masked_rerank_pool(qp);
-  MaskArgs m{allow, allow_stride_words, nullptr, nullptr};
-  if (lab) {      // pann_batch_search_labeled_rerank*: the labels are `full`'s
-    if (int rc = label_checks(full, fn, *lab, nq, dev)) return rc;
-    m = label_mask(full, *lab, lab->preds, nullptr, nullptr);
-  }
-  if (int rc = mask_checks(quant, m, qp, &so)) return rc;
+  if (F.mode == MASK_LABELS) { if (int rc = filter_checks(full, fn, F, nq)) return rc; }
+  if (int rc = masked_search_checks(quant, F, nq, qp, &so)) return rc;
   if (qp->k > 64) { set_error(f + ": k > 64 is not supported (the result list holds at most 64 keys)"); return PANN_ERR_UNSUPPORTED; }
   return PANN_OK;
 }
 
 // pann_batch_search_rerank / pann_batch_search_masked_rerank / pann_batch_search_labeled_rerank after their checks: one host round
-// trip, with the bitmap rows -- or the predicates -- and the two masked outputs when `mask` (host pointers) is given; `fn` names
+// trip, with the bitmap rows -- or the predicates -- and the two masked outputs when `points` (host pointers) is given; `fn` names
 // the entry point in the messages
 int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
                        uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts, uint32_t nstarts,
-                       const pann_query_params* qp, const pann_rerank_out* out, const MaskArgs* mask, const char* fn) {
+                       const pann_query_params* qp, const pann_rerank_out* out, const char* fn, const PointFilter* points = nullptr,
+                       uint32_t* result_count = nullptr, uint32_t* allowed_cmps = nullptr) {
   for (uint32_t i = 0; i < nstarts; i++)
     if (starts[i] >= quant->ix.n) { set_error(std::string(fn) + ": start point out of range"); return PANN_ERR_BAD_ARG; }
   if (nq == 0) return PANN_OK;
@@ -2614,23 +2527,20 @@ int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_par
   const DeviceIndex& qx = quant->ix;
   const uint32_t k = (uint32_t)qp->k;
   HostTrip t(quant, true);
-  // ---- inputs: the float rows, the starts and the bitmap rows (packed to ceil(n / 32) words each), one transfer up ----
-  const size_t mwords = (size_t)((qx.n + 31) / 32);
+  // ---- inputs: the float rows, the starts and the filter's arrays, one transfer up ----
   const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * qx.d);
   const int i_st = t.in.add(starts, (size_t)nstarts * 4);
-  const bool lab = mask && mask->by_labels();
-  const int i_mask = !mask ? -1 : lab ? t.in.add(mask->preds, (mask->pred_stride ? (size_t)nq : 1) * sizeof(pann_label_pred))
-                                      : t.in.add_rows(mask->allow, mask->stride ? (size_t)nq : 1, mwords * 4, (size_t)mask->stride * 4);
+  const StagedFilter staged(t, points, qx.n, nq);
   // ---- outputs: one packed device region (the status word last), one transfer down ----
   const int o_ids = t.out.add(out->ids, nq * k * 4), o_dists = t.out.add(out->dists, nq * k * 4);
   const int o_fs = t.out.add(out->frontier_size, nq * 4), o_vcnt = t.out.add(out->visited_count, nq * 4);
   const int o_cmps = t.out.add(out->dist_cmps, nq * 4);
   const int o_pruned = t.out.add(use_filter ? out->pruned_cmps : nullptr, nq * 4);       // (no room where it is not asked for)
-  const int o_rcnt = t.out.add(mask ? mask->result_count : nullptr, nq * 4), o_acmps = t.out.add(mask ? mask->allowed_cmps : nullptr, nq * 4);
+  const int o_rcnt = t.out.add(result_count, nq * 4), o_acmps = t.out.add(allowed_cmps, nq * 4);
   if (int rc = t.begin()) return rc;
   const uint8_t* d_q = t.din<uint8_t>(i_q);
-  const uint32_t* d_starts = t.din<uint32_t>(i_st), *d_allow = mask && !lab ? t.din<uint32_t>(i_mask) : nullptr;
-  const pann_label_pred* d_preds = lab ? t.din<pann_label_pred>(i_mask) : nullptr;
+  const uint32_t* d_starts = t.din<uint32_t>(i_st);
+  const PointFilter d_filter = staged.on_device(t);
   uint32_t status = 0;
   if (int rc = t.run_grown(nq, qp, fn, &status,
       [&](uint64_t q0, uint64_t cnt, uint32_t dcap, const uint32_t** d_word) -> int {
@@ -2640,14 +2550,28 @@ int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_par
       d.dist_cmps = t.dout<uint32_t>(o_cmps, q0);
       d.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
       *d_word = d.status = t.status_slot();
-      MaskArgs m{mask && mask->stride ? d_allow + q0 * mwords : d_allow, mask && mask->stride ? mwords : 0,
-                 t.dout<uint32_t>(o_rcnt, q0), t.dout<uint32_t>(o_acmps, q0)};
-      if (lab) { m.labels = mask->labels; m.preds = d_preds + q0 * mask->pred_stride; m.pred_stride = mask->pred_stride; m.pred_kind = mask->pred_kind; }
+      const PointFilter range = d_filter.slice(q0, cnt);
       return search_rerank_launch(full, quant, qparams, (const float*)(d_q + q0 * q_stride_bytes), cnt, q_stride_bytes, normalize_first,
-                                  use_filter, d_starts, nstarts, qp, dcap, d, t.st, mask ? &m : nullptr);
+                                  use_filter, d_starts, nstarts, qp, dcap, d, t.st, points ? &range : nullptr, t.dout<uint32_t>(o_rcnt, q0),
+                                  t.dout<uint32_t>(o_acmps, q0));
     })) return rc;
   if (out->status) *out->status = status;
   return PANN_OK;
+}
+
+// the masked / labeled fused entries behind their descriptor: the checks, then the host round trip or (F.dev) the launch on the caller's stream
+int masked_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                  uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts, uint32_t nstarts,
+                  const pann_query_params* qp, const PointFilter& F, const pann_rerank_out* out, uint32_t* result_count,
+                  uint32_t* allowed_cmps, void* stream, const char* fn) {
+  if (int rc = masked_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, F, out, fn)) return rc;
+  if (!F.dev) return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, out, fn,
+                                        &F, result_count, allowed_cmps);      // F.dev is also the entry's kind: a host entry (no stream) ends here
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)queries % 4 != 0) { set_error(std::string(fn) + ": query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  return search_rerank_launch(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, quant->dcap, *out,
+                              (hipStream_t)stream, &F, result_count, allowed_cmps);
 }
 
 }  // namespace
@@ -2672,7 +2596,7 @@ int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_qua
   if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, out,
                                     "pann_batch_search_rerank")) return rc;
   return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, use_filter, starts, nstarts, qp, out,
-                            nullptr, "pann_batch_search_rerank");
+                            "pann_batch_search_rerank");
 }
 
 int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
@@ -2680,25 +2604,18 @@ int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, con
                                         const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp, const uint32_t* d_allow,
                                         uint64_t allow_stride_words, const pann_rerank_out* d_out, uint32_t* d_out_result_count,
                                         uint32_t* d_out_allowed_cmps, void* stream) {
-  if (int rc = masked_rerank_checks(full, quant, qparams, d_queries, nq, q_stride_bytes, use_filter, d_starts, nstarts, qp, d_allow,
-                                    allow_stride_words, d_out, "pann_batch_search_masked_rerank_dev")) return rc;
-  if (nq == 0) return PANN_OK;
-  if ((uintptr_t)d_queries % 4 != 0) { set_error("pann_batch_search_masked_rerank_dev: query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
-  DeviceGuard g(quant->device);
-  const MaskArgs m{d_allow, allow_stride_words, d_out_result_count, d_out_allowed_cmps};
-  return search_rerank_launch(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, 0, d_starts, nstarts, qp,
-                              quant->dcap, *d_out, (hipStream_t)stream, &m);
+  return masked_rerank(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp,
+                       PointFilter::bitmap(d_allow, allow_stride_words, nq, true), d_out, d_out_result_count, d_out_allowed_cmps, stream,
+                       "pann_batch_search_masked_rerank_dev");
 }
 
 int pann_batch_search_masked_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
                                     uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts,
                                     uint32_t nstarts, const pann_query_params* qp, const uint32_t* allow, uint64_t allow_stride_words,
                                     const pann_rerank_out* out, uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
-  if (int rc = masked_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, allow,
-                                    allow_stride_words, out, "pann_batch_search_masked_rerank")) return rc;
-  const MaskArgs m{allow, allow_stride_words, out_result_count, out_allowed_cmps};
-  return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, out, &m,
-                            "pann_batch_search_masked_rerank");
+  return masked_rerank(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, use_filter, starts, nstarts, qp,
+                       PointFilter::bitmap(allow, allow_stride_words, nq, false), out, out_result_count, out_allowed_cmps, nullptr,
+                       "pann_batch_search_masked_rerank");
 }
 
 int pann_batch_search_labeled_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams,
@@ -2706,15 +2623,9 @@ int pann_batch_search_labeled_rerank_dev(pann_index* full, pann_index* quant, co
                                          int use_filter, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
                                          int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_rerank_out* d_out,
                                          uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
-  const LabelArgs l{kind, d_preds, npreds};
-  if (int rc = masked_rerank_checks(full, quant, qparams, d_queries, nq, q_stride_bytes, use_filter, d_starts, nstarts, qp, nullptr, 0,
-                                    d_out, "pann_batch_search_labeled_rerank_dev", &l, true)) return rc;
-  if (nq == 0) return PANN_OK;
-  if ((uintptr_t)d_queries % 4 != 0) { set_error("pann_batch_search_labeled_rerank_dev: query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
-  DeviceGuard g(quant->device);
-  const MaskArgs m = label_mask(full, l, d_preds, d_out_result_count, d_out_allowed_cmps);
-  return search_rerank_launch(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, 0, d_starts, nstarts, qp,
-                              quant->dcap, *d_out, (hipStream_t)stream, &m);
+  return masked_rerank(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp,
+                       label_filter(full, kind, d_preds, npreds, true), d_out, d_out_result_count, d_out_allowed_cmps, stream,
+                       "pann_batch_search_labeled_rerank_dev");
 }
 
 int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
@@ -2722,12 +2633,9 @@ int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const 
                                      const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp, int kind,
                                      const pann_label_pred* preds, uint64_t npreds, const pann_rerank_out* out,
                                      uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
-  const LabelArgs l{kind, preds, npreds};
-  if (int rc = masked_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, nullptr, 0, out,
-                                    "pann_batch_search_labeled_rerank", &l, false)) return rc;
-  const MaskArgs m = label_mask(full, l, preds, out_result_count, out_allowed_cmps);      // preds: host, staged by search_rerank_host
-  return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, out, &m,
-                            "pann_batch_search_labeled_rerank");
+  return masked_rerank(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, use_filter, starts, nstarts, qp,
+                       label_filter(full, kind, preds, npreds, false), out, out_result_count, out_allowed_cmps, nullptr,
+                       "pann_batch_search_labeled_rerank");
 }
 
 }  // extern "C"

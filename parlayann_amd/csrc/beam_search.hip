@@ -1580,10 +1580,10 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
       set_error("pann_batch_search_filtered: sketch query stride smaller than a sketch row, or rows not 8-byte aligned"); return PANN_ERR_BAD_ARG;
     }
   }
-  // the bitmap, its stride and out_k <= 64 are checked by the entry points (api.hip: mask_checks); no entry point combines a mask
+  // the bitmap, its stride and out_k <= 64 are checked by the entry points (api.hip: masked_search_checks); no entry point combines a mask
   // with the sketch filter, and there is no kernel for it
   if (a.masked && a.filter) { set_error("pann_batch_search_masked: the sketch filter has no masked form"); return PANN_ERR_UNSUPPORTED; }
-  // label mode: the entry points have checked the handle's labels, the kind and npreds (api.hip: label_checks)
+  // label mode: the entry points have checked the handle's labels, the kind and npreds (api.hip: filter_checks)
   if (a.masked == MASK_LABELS && (!a.labels || !a.preds || a.pred_stride > 1 || !pred_kind_known(a.pred_kind))) {
     set_error("pann_batch_search_labeled: labels, predicates of a known kind and a predicate stride of 0 or 1 are needed"); return PANN_ERR_BAD_ARG;
   }

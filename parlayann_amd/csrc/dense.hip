@@ -1321,10 +1321,9 @@ static size_t dense_lds_bytes(uint32_t mcap) {
 }
 
 // Runs the dense top-m.  All pointers device.  tile arrays may be null for a single segment.
-int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_a_ext, uint64_t a_stride,
-                   const uint32_t* d_a_ids, const uint32_t* d_b_ids, const uint64_t* d_a_off, const uint64_t* d_b_off,
-                   const uint32_t* d_tile_seg, const uint32_t* d_tile_a0, uint32_t ntiles, uint64_t na, uint64_t nb,
-                   uint32_t nsplit, uint32_t m, int exclude_same, uint32_t* d_out_ids, float* d_out_dists) {
+int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c) {
+  const uint32_t ntiles = c.ntiles, nsplit = c.nsplit, m = c.m;
+  const uint64_t na = c.na, nb = c.nb; const int exclude_same = c.exclude_same;
   if (m == 0 || m > 128) { set_error("dense top-m: m must be in [1,128]"); return PANN_ERR_BAD_ARG; }
   if (na == 0) return PANN_OK;
   const uint32_t mcap = (m + 15) / 16 * 16;
@@ -1332,11 +1331,11 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const u
   if (int rc = ws.ensure(pbytes + 256)) return rc;
   DenseArgs A{};
   A.points = ix.points; A.pstride = ix.pstride; A.dbytes = ix.dbytes;
-  A.a_ext = d_a_ext; A.a_stride = a_stride; A.a_ids = d_a_ids; A.b_ids = d_b_ids;
-  A.a_off = d_a_off; A.b_off = d_b_off; A.na = na; A.nb = nb; A.nsplit = nsplit; A.m = m; A.mcap = mcap;
-  A.exclude_same_id = exclude_same; A.exact = ix.exact; A.partial = (uint64_t*)ws.buf; A.tile_seg = d_tile_seg; A.tile_a0 = d_tile_a0;
+  A.a_ext = c.a_ext; A.a_stride = c.a_stride; A.a_ids = c.a_ids; A.b_ids = c.b_ids;
+  A.a_off = c.a_off; A.b_off = c.b_off; A.na = na; A.nb = nb; A.nsplit = nsplit; A.m = m; A.mcap = mcap;
+  A.exclude_same_id = exclude_same; A.exact = ix.exact; A.partial = (uint64_t*)ws.buf; A.tile_seg = c.tile_seg; A.tile_a0 = c.tile_a0;
   const dim3 grid(ntiles, nsplit);
-  if (dense_gt_eligible(ix, m, d_b_ids != nullptr, d_a_off || d_b_off || d_tile_seg || d_tile_a0, exclude_same)) {
+  if (dense_gt_eligible(ix, m, c.b_ids != nullptr, c.a_off || c.b_off || c.tile_seg || c.tile_a0, exclude_same)) {
     // register-list ground-truth kernel; |b|^2 of every point first (after the partial lists in the workspace)
     const size_t poff = (pbytes + 255) / 256 * 256;
     const uint64_t nnorm = nb;
@@ -1373,7 +1372,7 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const u
   }
   PANN_HIP(hipGetLastError());
   hipLaunchKernelGGL(dense_merge_kernel, dim3((uint32_t)na), dim3(64), (size_t)mcap * 8, st,
-                     (const uint64_t*)ws.buf, na, nsplit, m, mcap, d_out_ids, d_out_dists);
+                     (const uint64_t*)ws.buf, na, nsplit, m, mcap, c.out_ids, c.out_dists);
   PANN_HIP(hipGetLastError());
   return PANN_OK;
 }

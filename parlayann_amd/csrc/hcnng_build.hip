@@ -16,6 +16,7 @@
 #include <rocprim/device/device_scan.hpp>
 #include <rocprim/device/device_segmented_radix_sort.hpp>
 
+#include "grouped_plan.h"
 #include "pann_device.h"
 
 namespace pann {
@@ -286,11 +287,6 @@ __global__ void __launch_bounds__(PANN_WAVE) leaf_mst_kernel(MstArgs A) {
 
 // ---------------------------------------------------------------------------------------------
 
-int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_a_ext, uint64_t a_stride,
-                   const uint32_t* d_a_ids, const uint32_t* d_b_ids, const uint64_t* d_a_off, const uint64_t* d_b_off,
-                   const uint32_t* d_tile_seg, const uint32_t* d_tile_a0, uint32_t ntiles, uint64_t na, uint64_t nb,
-                   uint32_t nsplit, uint32_t m, int exclude_same, uint32_t* d_out_ids, float* d_out_dists);
-
 __global__ void fill_u32_hc(uint32_t* p, uint64_t n, uint32_t v) {
   const uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -499,13 +495,14 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
       if (int rc = leaf_knn_rows_dev(ix, ws, st, ids, d_loff.as<uint64_t>(), leaf_off.data(), nleaves, m, 1, b_nnids.as<uint32_t>(), b_nnd.as<float>())) return rc;
     } else {
       std::vector<uint32_t> tseg, ta0;
-      for (uint32_t l = 0; l < nleaves; l++)
-        for (uint64_t a = leaf_off[l]; a < leaf_off[l + 1]; a += 64) { tseg.push_back(l); ta0.push_back((uint32_t)a); }
+      append_tiles(leaf_off.data(), nleaves, std::back_inserter(tseg), std::back_inserter(ta0));
       if (d_tseg.alloc(tseg.size() * 4) || d_ta0.alloc(ta0.size() * 4)) { set_error("pann_hcnng_build: hipMalloc failed"); return PANN_ERR_HIP; }
       PANN_HIP(hipMemcpyAsync(d_tseg.p, tseg.data(), tseg.size() * 4, hipMemcpyHostToDevice, st));
       PANN_HIP(hipMemcpyAsync(d_ta0.p, ta0.data(), ta0.size() * 4, hipMemcpyHostToDevice, st));
-      if (int rc = dense_topk_dev(ix, ws, st, nullptr, 0, ids, ids, d_loff.as<uint64_t>(), d_loff.as<uint64_t>(), d_tseg.as<uint32_t>(),
-                                  d_ta0.as<uint32_t>(), (uint32_t)tseg.size(), n, n, 1, m, 1, b_nnids.as<uint32_t>(), b_nnd.as<float>())) return rc;
+      DenseTopkCall c;
+      c.a_ids = c.b_ids = ids; c.a_off = c.b_off = d_loff.as<uint64_t>(); c.tile_seg = d_tseg.as<uint32_t>(); c.tile_a0 = d_ta0.as<uint32_t>();
+      c.ntiles = (uint32_t)tseg.size(); c.na = c.nb = n; c.m = m; c.exclude_same = 1; c.out_ids = b_nnids.as<uint32_t>(); c.out_dists = b_nnd.as<float>();
+      if (int rc = dense_topk_dev(ix, ws, st, c)) return rc;
       PANN_HIP(hipStreamSynchronize(st));        // the host tile vectors go out of scope
     }
     PANN_HIP(hipStreamSynchronize(st));

@@ -525,39 +525,28 @@ int knn_pad_dev(uint32_t* d_ids, float* d_dists, uint32_t* d_counts, uint64_t nq
   return PANN_OK;
 }
 
-// the per-query scan on bitmap rows (d_labels == null) or on the labels with one predicate per query
-static int scan_launch(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
-                       uint64_t allow_stride, const uint32_t* d_labels, int kind, const pann_label_pred* d_preds, uint32_t k,
-                       uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
+// the per-query scan on bitmap rows or on the labels with one predicate per query
+int filter_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const PointFilter& F,
+                    uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
   if (nq == 0) return PANN_OK;
   if (k == 0 || k > PANN_WAVE) { set_error("masked scan: k must be in [1,64]"); return PANN_ERR_UNSUPPORTED; }
   const size_t qb = query_lds_bytes(ix);
   if (qb > 48 * 1024) { set_error("masked scan: rows too long for the scan's LDS state"); return PANN_ERR_UNSUPPORTED; }
+  const bool by_labels = F.mode == MASK_LABELS;
   MaskedScanArgs P{};
   P.pv = PointsView{ix.points, ix.pstride, ix.nch, ix.exact}; P.dbytes = ix.dbytes;
-  P.q = d_q; P.q_stride = q_stride; P.allow = d_allow; P.allow_stride = allow_stride; P.n = ix.n; P.k = k;
-  P.labels = d_labels; P.preds = d_preds; P.kind = (uint32_t)kind;
+  P.q = d_q; P.q_stride = q_stride; P.allow = F.allow; P.allow_stride = F.stride; P.n = ix.n; P.k = k;
+  P.labels = F.labels; P.preds = F.preds; P.kind = (uint32_t)F.kind;      // (a bitmap filter has no labels, a label filter no rows)
   P.out_ids = d_out_ids; P.out_dists = d_out_dists; P.out_counts = d_out_counts;
 #define CALL_MS(DT, MT, L, N1)                                                                                              \
   do {                                                                                                                      \
-    if (d_labels) hipLaunchKernelGGL((masked_scan_kernel<DT, MT, L, N1, true>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, P);   \
+    if (by_labels) hipLaunchKernelGGL((masked_scan_kernel<DT, MT, L, N1, true>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, P);  \
     else hipLaunchKernelGGL((masked_scan_kernel<DT, MT, L, N1, false>), dim3((uint32_t)nq), dim3(PANN_WAVE), qb, st, P);    \
   } while (0)
   PANN_TYPE_SWITCH(ix, CALL_MS);
 #undef CALL_MS
   PANN_HIP(hipGetLastError());
   return PANN_OK;
-}
-
-int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
-                    uint64_t allow_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts) {
-  return scan_launch(ix, st, d_q, q_stride, nq, d_allow, allow_stride, nullptr, 0, nullptr, k, d_out_ids, d_out_dists, d_out_counts);
-}
-
-int label_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_labels,
-                   int kind, const pann_label_pred* d_preds, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
-                   uint32_t* d_out_counts) {
-  return scan_launch(ix, st, d_q, q_stride, nq, nullptr, 0, d_labels, kind, d_preds, k, d_out_ids, d_out_dists, d_out_counts);
 }
 
 int labels_to_allow_dev(const uint32_t* d_labels, uint64_t n, int kind, const pann_label_pred* d_preds, uint64_t npreds,

@@ -114,19 +114,49 @@ struct SearchArgs {  // one batched beam search, everything device resident
   int pred_kind = 0;                         // PANN_PRED_*
 };
 
-// the extra arguments of the masked entry points (pann_batch_search_masked*, pann_batch_search_masked_rerank*): host or device
-// pointers, as the entry point's other pointers
-struct MaskArgs {
-  const uint32_t* allow; uint64_t stride;          // bitmap rows, as SearchArgs::allow / allow_stride
-  uint32_t* result_count; uint32_t* allowed_cmps;  // nq each, optional
-  // label mode (allow == null): as SearchArgs::labels / preds / pred_stride / pred_kind; labels is always a device pointer
-  const uint32_t* labels = nullptr; const pann_label_pred* preds = nullptr; uint32_t pred_stride = 0; int pred_kind = 0;
-  bool by_labels() const { return labels != nullptr; }
-  void apply(SearchArgs& a) const {                // everything but the two outputs, which the callers place themselves
-    a.masked = by_labels() ? MASK_LABELS : MASK_BITMAP;
-    a.allow = allow; a.allow_stride = stride;
-    a.labels = labels; a.preds = preds; a.pred_stride = pred_stride; a.pred_kind = pred_kind;
+// Which points a query may return: what every masked / labeled / grouped entry point builds once from its C arguments and
+// everything behind it takes.  allow / preds / group are host or device pointers, as the entry point's other pointers (`dev`);
+// labels is the device array of the handle whose labels are read.  Only the filter: the optional outputs of the masked
+// searches (result_count, allowed_cmps) travel beside it.
+struct PointFilter {
+  enum { SHARED, PER_QUERY, TABLE };    // one filter for the batch | one per query | `count` table entries, query q uses entry group[q]
+  int mode = MASK_NONE, layout = SHARED;      // MASK_BITMAP: rows of `allow`; MASK_LABELS: `preds` of one `kind` over `labels`
+  uint64_t count = 1;                   // filters given, as the caller said it (the checks hold it against nq): 1, nq, or the table's entries
+  const uint32_t* allow = nullptr; uint64_t stride = 0;      // bitmap rows, as SearchArgs::allow; words between two rows (0: one row)
+  const uint32_t* labels = nullptr; int kind = 0; const pann_label_pred* preds = nullptr;
+  const uint32_t* group = nullptr; bool dev = false;      // group: nq entries of a TABLE
+  static PointFilter bitmap(const uint32_t* allow, uint64_t stride, uint64_t nq, bool dev) {      // a stride makes one row per query, even at nq == 1
+    PointFilter f; f.mode = MASK_BITMAP; f.allow = allow; f.stride = stride; f.dev = dev;
+    if (stride) { f.layout = PER_QUERY; f.count = nq; }
+    return f;
   }
+  PointFilter as_table(const uint32_t* group_of_query, uint64_t entries) const {
+    PointFilter f = *this; f.layout = TABLE; f.count = entries; f.group = group_of_query; return f;
+  }
+  bool shared() const { return layout == SHARED; }
+  bool per_query() const { return layout == PER_QUERY; }
+  bool is_table() const { return layout == TABLE; }
+  static uint64_t row_words(uint64_t n) { return (n + 31) / 32; }
+  PointFilter slice(uint64_t q0, uint64_t cnt) const {      // the filter of the queries [q0, q0 + cnt) (a shared one is its own slice)
+    PointFilter f = *this;
+    if (per_query()) { f.count = cnt; if (allow) f.allow += q0 * stride; if (preds) f.preds += q0; }
+    return f;
+  }
+  void apply(SearchArgs& a) const {     // (a.result_count / a.allowed_cmps: the callers place them themselves)
+    a.masked = mode; a.allow = allow; a.allow_stride = stride;
+    a.labels = labels; a.preds = preds; a.pred_stride = mode == MASK_LABELS && per_query() ? 1u : 0u; a.pred_kind = kind;
+  }
+};
+
+// dense_topk_dev (dense.hip): for every A row the m nearest B rows.  A rows: external rows (a_ext, a_stride bytes apart) or the table's rows
+// a_ids; B rows: the table's rows b_ids (null: 0 .. nb).  Segmented form: segment s pairs the A rows [a_off[s], a_off[s + 1]) with the B rows
+// [b_off[s], b_off[s + 1]), tile t the 64 A rows from tile_a0[t] of segment tile_seg[t] (grouped_plan.h); all four null: one segment.  Device pointers.
+struct DenseTopkCall {
+  const uint8_t* a_ext = nullptr; uint64_t a_stride = 0;
+  const uint32_t* a_ids = nullptr, *b_ids = nullptr, *tile_seg = nullptr, *tile_a0 = nullptr;
+  const uint64_t* a_off = nullptr, *b_off = nullptr;
+  uint32_t ntiles = 0, nsplit = 1, m = 0; uint64_t na = 0, nb = 0; int exclude_same = 0;      // nsplit: pieces B is cut into per tile
+  uint32_t* out_ids = nullptr; float* out_dists = nullptr;      // na x m each
 };
 
 // the one growable device buffer: kernel scratch, staging regions, tables kept on a handle (grown on demand, never shrunk)
@@ -183,10 +213,7 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
                             pann_delete_stats* stats);
 
 // dense.hip
-int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_a_ext, uint64_t a_stride,
-                   const uint32_t* d_a_ids, const uint32_t* d_b_ids, const uint64_t* d_a_off, const uint64_t* d_b_off,
-                   const uint32_t* d_tile_seg, const uint32_t* d_tile_a0, uint32_t ntiles, uint64_t na, uint64_t nb,
-                   uint32_t nsplit, uint32_t m, int exclude_same, uint32_t* d_out_ids, float* d_out_dists);
+int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c);
 int query_distances_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q_ext, uint64_t q_stride,
                         const uint32_t* d_q_ids, uint64_t nq, const uint32_t* d_ids, uint64_t m, int paired,
                         float* d_out);
@@ -211,9 +238,10 @@ int allow_compact_scatter_dev(const uint32_t* d_allow, uint64_t n, const uint32_
                               hipStream_t st);
 // pad != 0: nq x k ids / dists <- 0xFFFFFFFF / +inf; d_counts (optional): nq entries <- cnt
 int knn_pad_dev(uint32_t* d_ids, float* d_dists, uint32_t* d_counts, uint64_t nq, uint32_t k, uint32_t cnt, int pad, hipStream_t st);
-// one bitmap row per query (allow_stride words apart), k <= 64: rows sorted by (dist, id), padded; d_out_counts optional
-int masked_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_allow,
-                    uint64_t allow_stride, uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts);
+// one filter per query (device pointers), k <= 64: a bitmap row per query, F.stride words apart, or the bitmap words of query q
+// built from F.labels and F.preds[q] as the scan goes.  nq x k ids and dists, rows sorted by (dist, id) and padded; counts (nq) optional
+int filter_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const PointFilter& F,
+                    uint32_t k, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts);
 // label predicates (DESIGN.md "Label predicates"): d_labels n words, d_preds npreds predicates of one kind
 // row r of d_allow (stride words apart, >= ceil(n / 32)) <- the bitmap of d_preds[r]; dead bits of the last word 0
 int labels_to_allow_dev(const uint32_t* d_labels, uint64_t n, int kind, const pann_label_pred* d_preds, uint64_t npreds,
@@ -221,10 +249,6 @@ int labels_to_allow_dev(const uint32_t* d_labels, uint64_t n, int kind, const pa
 // d_counts[r] = points d_preds[r] allows
 int label_count_dev(const uint32_t* d_labels, uint64_t n, int kind, const pann_label_pred* d_preds, uint64_t npreds,
                     uint32_t* d_counts, hipStream_t st);
-// masked_scan_dev with the bitmap words of query q built from the labels and d_preds[q] as the scan goes
-int label_scan_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq, const uint32_t* d_labels,
-                   int kind, const pann_label_pred* d_preds, uint32_t k, uint32_t* d_out_ids, float* d_out_dists,
-                   uint32_t* d_out_counts);
 
 // grouped route (DESIGN.md "Exact kNN by predicate group"): a table of G filters, d_group[q] < G names the filter of query q.
 // The queries sorted by table index, stably: d_hist[g] = queries of entry g, d_off[0 .. G] = the first slot of every entry (G + 1
@@ -334,9 +358,9 @@ float sketch_threshold(const pann_sketch_params* p);               // the value 
 // search_rerank.hip: beam_search_rerank on the device -- prepare the float queries (one-byte rows, sketch rows, normalised
 // rows), beam search on the one-byte index, exact rerank of the frontier on the f32 index.  `scratch`: search_rerank_scratch_bytes
 // bytes, 256-byte aligned; search_ws: the one-byte handle's search workspace (its status word gets the SHORT_FRONTIER bit).
-// Masked form (mask != null, DESIGN.md "Masked search on the fused path"): the search is the masked one with a result list of
-// masked_rerank_pool(qp) ids per query, the rerank reads that list (result_count entries) instead of the frontier, raises no
-// SHORT_FRONTIER, and the scratch is sized with the pool in place of the beam.
+// Masked form (points != null, device pointers, with its two optional outputs of nq entries; DESIGN.md "Masked search on the fused path"):
+// the search is the masked one with a result list of masked_rerank_pool(qp) ids per query, the rerank reads that list (result_count
+// entries) instead of the frontier, raises no SHORT_FRONTIER, and the scratch is sized with the pool in place of the beam.
 inline uint32_t masked_rerank_pool(const pann_query_params* qp) {   // min(k * rerank_factor, beam, 64), at least 1
   const int64_t want = std::max<int64_t>((int64_t)qp->k * qp->rerank_factor, 1);
   return (uint32_t)std::min<int64_t>(std::min<int64_t>(want, std::max<int64_t>(qp->beam, 1)), 64);
@@ -346,7 +370,7 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
                       const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
                       uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
                       const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                      const MaskArgs* mask = nullptr);
+                      const PointFilter* points = nullptr, uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr);
 
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,

@@ -270,7 +270,7 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
                       const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
                       uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
                       const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                      const MaskArgs* mask) {
+                      const PointFilter* mask, uint32_t* d_result_count, uint32_t* d_allowed_cmps) {
   if (nq == 0) return PANN_OK;
   const uint32_t d = full.d, beam = (uint32_t)qp->beam, k = (uint32_t)qp->k;
   if (beam == 0 || beam > 4096) { set_error("pann_rerank: candidates per query must be in [1,4096]"); return PANN_ERR_BAD_ARG; }
@@ -298,10 +298,10 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
   a.out.ids = s.fids; a.out.out_k = beam; a.out.frontier_size = s.fsize;
   uint32_t* rcount = s.fsize;                      // masked: the lists' lengths, in the caller's array when there is one
   if (mask) {
-    if (mask->result_count) rcount = mask->result_count;
+    if (d_result_count) rcount = d_result_count;
     a.out.out_k = pool; a.out.frontier_size = d_out.frontier_size;
     mask->apply(a);                                // bitmap rows, or the labels of `full` with the queries' predicates
-    a.result_count = rcount; a.allowed_cmps = mask->allowed_cmps;
+    a.result_count = rcount; a.allowed_cmps = d_allowed_cmps;
   }
   a.out.visited_count = d_out.visited_count; a.out.dist_cmps = d_out.dist_cmps;
   a.filter = use_filter ? 1 : 0;
