@@ -548,6 +548,7 @@ int64_t pann_index_get_option(const pann_index* idx, const char* name) {
   if (nm == "forest_group") return idx->ix.forest_group;
   if (nm == "gt_pieces") return idx->gt_pieces;
   if (nm == "delete_range_keys") return idx->delete_range_keys;
+  if (nm == "b64_seen") return idx->ix.b64_seen;
   if (nm == "locality_order") return idx->ix.cell ? 1 : 0;
   if (nm == "filter_codes") return idx->ix.codes_valid ? 1 : 0;         // are the class codes in step with the graph right now?
   if (nm == "pinned_bytes") return (int64_t)(idx->pin_in.bytes + idx->pin_out.bytes);   // pinned host memory the handle holds (HostTrip)
@@ -569,6 +570,7 @@ int pann_index_set_option(pann_index* idx, const char* name, int64_t value) {
   if (nm == "forest_group") idx->ix.forest_group = (uint32_t)value;
   else if (nm == "gt_pieces") idx->gt_pieces = (uint32_t)value;
   else if (nm == "delete_range_keys") idx->delete_range_keys = (uint32_t)value;
+  else if (nm == "b64_seen") idx->ix.b64_seen = value ? 1u : 0u;      // 0: the beam-64 search without the second-sighting table (tests, A/B)
   else if (nm == "locality_pivots") { idx->locality_pivots = std::max<uint32_t>(2, std::min<uint32_t>((uint32_t)value, 65536)); idx->ix.cell = nullptr; idx->cells_state = idx->cells_state < 0 ? idx->cells_state : 0; }
   else if (nm == "locality_groups") { idx->locality_groups = (uint32_t)std::min<int64_t>(value, 4096); idx->ix.cell = nullptr; idx->cells_state = idx->cells_state < 0 ? idx->cells_state : 0; }
   else if (nm == "locality_order") {        // 0: the builder launches a batch's searches in batch order

@@ -197,9 +197,12 @@ __device__ __forceinline__ void lds_part_clear(const LdsPart& L, int lane) {
   }
 }
 
+// victim (optional, table in LDS): per lane, the id this call evicted from the table -- the value the lane's slot held on entry,
+// reported by the lane that writes the slot, when it was another id than the one written -- or SENTINEL.
 template <bool HASH_LDS>
 __device__ __forceinline__ bool filter_update(uint32_t* H, uint32_t hmask, bool active, uint32_t a, int lane,
-                                              uint8_t* T = nullptr, uint32_t hb = 0, LdsPart Lp = LdsPart{nullptr, 0, 0}) {
+                                              uint8_t* T = nullptr, uint32_t hb = 0, LdsPart Lp = LdsPart{nullptr, 0, 0},
+                                              uint32_t* victim = nullptr) {
   const uint32_t s = (uint32_t)hash64_2((uint64_t)a) & hmask;
   uint32_t old, w;
   const uint32_t hm = (1u << hb) - 1u;
@@ -236,6 +239,7 @@ __device__ __forceinline__ bool filter_update(uint32_t* H, uint32_t hmask, bool 
   const uint32_t a_prev = __shfl(a, prev < 0 ? lane : prev);
   const bool seen = active && (prev >= 0 ? (a_prev == a) : (old == a));
   if constexpr (HASH_LDS) {
+    if (victim) *victim = (active && last && old != SENTINEL && old != a) ? old : SENTINEL;
     PANN_WSYNC();
     if (active && last) H[s] = a;
     PANN_WSYNC();
@@ -810,8 +814,14 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
 // filter (4 KB) + a 64-entry scatter scratch + the candidate list: 5.2 KB -> 31 queries per CU.
 // =============================================================================================
 // MASKED: as in the generic kernel.
-template <int DT, int METRIC, int LPC, bool NCH1, int MASKED = MASK_NONE>
+// MODE: MASK_NONE, a masked form, or B64_SEEN: the plain search with the second-sighting table V ("Second
+// sightings"), whose size is the compile-time constant VN (0: no table, the kernel as it was before V).
+enum { B64_SEEN = 3 };
+template <int DT, int METRIC, int LPC, bool NCH1, int MODE = MASK_NONE>
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_kernel(BSParams P) {
+  constexpr int MASKED = (MODE == MASK_BITMAP || MODE == MASK_LABELS) ? MODE : MASK_NONE;
+  constexpr int VN = MODE == B64_SEEN ? (int)B64_SEEN_N : 0;
+  static_assert((B64_SEEN_N & (B64_SEEN_N - 1)) == 0 && B64_SEEN_N >= 128, "V: a power of two of whole words per lane");
   const int lane = threadIdx.x;
   extern __shared__ __align__(16) uint8_t smem[];
   uint64_t* S = reinterpret_cast<uint64_t*>(smem);          // [64] merge scatter scratch; first 256 B double as Pl
@@ -824,6 +834,12 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
   const uint32_t hsize = 1u << P.bits, hmask = hsize - 1u;
   const uint32_t beam = P.beam;
   const uint32_t BIG_ORD = f2ord(2147483648.0f);            // (:152)
+  // V[VN]: entry id & (VN - 1) holds the tag id >> log2(VN) of an id that H has forgotten (0xFFFF: empty; make_plan keeps every
+  // tag below it).  An id found here was compared by this query before; an id not found may have been, too.
+  constexpr uint32_t VSHIFT = VN ? (uint32_t)__builtin_ctz((unsigned)(VN ? VN : 1)) : 0u;
+  [[maybe_unused]] uint16_t* V = reinterpret_cast<uint16_t*>(H + hsize);
+  [[maybe_unused]] bool v_ok = true;                        // no cut-prune has left the frontier at or below k entries
+  if constexpr (VN != 0) for (uint32_t i = lane; i < VN / 2; i += PANN_WAVE) reinterpret_cast<uint32_t*>(V)[i] = 0xFFFFFFFFu;
   const uint32_t qi = P.order ? P.order[blockIdx.x] : blockIdx.x;
   // Blocks are dispatched in index order, so the highest indices start last and form the tail of the launch: they
   // get instruction-issue priority over the queries that are already under way (measured +1..3 % at 10K queries,
@@ -913,15 +929,48 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
         PANN_STAMP(1);
         if (am == 0ull) break;
         degsum += __popcll(am);
-        const bool seen = filter_update<true>(H, hmask, act, a, lane);
-        const bool keep = act && !seen && ((int64_t)a != self);   // :133
+        [[maybe_unused]] uint32_t victim = SENTINEL;
+        bool seen;
+        if constexpr (VN != 0) seen = filter_update<true>(H, hmask, act, a, lane, nullptr, 0, LdsPart{nullptr, 0, 0}, &victim);
+        else seen = filter_update<true>(H, hmask, act, a, lane);
+        bool keep = act && !seen && ((int64_t)a != self);         // :133
+        if constexpr (VN != 0) {
+          dcmps += __popcll(__ballot(keep));                      // :137,155 -- a comparison, whether or not its row is fetched
+          // Second sightings.  The frontier is full and no cut-prune ever left it at or below k entries, so a vertex this query
+          // compared before and that is neither in the frontier nor pending in C lies at or beyond the cutoff:
+          // its row is not fetched.  One in the frontier or in C gets the key it has there -- the key the fetch would produce.
+          // Pending candidates are looked at through one register per lane, hence c <= 64 (always, for rows of <= 64 slots).
+          if (f == beam && v_ok && cutoff_ord <= BIG_ORD && c <= PANN_WAVE) {
+            const bool hit = keep && V[a & (VN - 1)] == (uint16_t)(a >> VSHIFT);
+            uint64_t hm = __ballot(hit);
+            if (hm) {
+              const uint64_t pkey = lane < (int)c ? C[lane] : KEY_INF;      // the id of KEY_INF (free lanes, too) is no vertex
+              const uint32_t fid = (uint32_t)fkey, pid = (uint32_t)pkey;
+              while (hm) {                                        // uniform: one trip per second sighting
+                const int l = __ffsll((unsigned long long)hm) - 1;
+                hm &= hm - 1;
+                const uint32_t al = __builtin_amdgcn_readlane(a, l);
+                const uint64_t inf = __ballot(fid == al), inc = __ballot(pid == al);
+                uint64_t key = KEY_INF;
+                if (inf) key = readlane64(fkey, __ffsll((unsigned long long)inf) - 1);
+                else if (inc) key = readlane64(pkey, __ffsll((unsigned long long)inc) - 1);
+                if ((uint32_t)(key >> 32) < cutoff_ord) {          // :157
+                  if (lane == 0) C[c] = key;
+                  c++;
+                }
+              }
+              keep = keep && !hit;
+            }
+          }
+          if (victim != SENTINEL) V[victim & (VN - 1)] = (uint16_t)(victim >> VSHIFT);
+        }
         const uint64_t km = __ballot(keep);
         const uint32_t m = __popcll(km);
         [[maybe_unused]] uint32_t aword = 0u;
         if constexpr (MASKED) if (keep) aword = mask_word<MASKED>(M, a);         // in flight with the rows of the gather
         const uint32_t mypos = lanes_below(km, lane);
         if (keep) Pl[mypos] = a;
-        dcmps += m;
+        if constexpr (VN == 0) dcmps += m;
         PANN_WSYNC();
         PANN_STAMP(2);
         if constexpr (MASKED) {
@@ -998,6 +1047,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
         const uint64_t thr_key = (uint64_t)f2ord(thr) << 32;     // pair{0, thr}: kept iff key <= thr_key
         const uint32_t ub = __popcll(__ballot(lane < (int)f_new && fkey <= thr_key));
         f_new = max(ub, f_old);
+        if constexpr (VN != 0) if (f_new <= P.k) v_ok = false;    // entry k is gone: the next threshold may be a higher one
       }
       if (f_new == beam) {
         ndrop = 0;                                               // a full frontier never re-admits anything
@@ -1408,6 +1458,7 @@ struct Plan {
   uint32_t rl_off; // ... masked: byte offset of the result list (64 keys) in LDS
   bool masked;     // allow-bitmap search: the MASKED variant of the b64 kernel (bcap 64) or of the generic kernel (every other beam)
   bool by_labels;  // ... with label predicates in place of the bitmap: the MASK_LABELS instantiation of the same kernel
+  uint32_t seen_n; // plain b64 kernel: entries of the second-sighting table V behind the filter (0: the kernel without it)
 };
 
 // which layouts have a MASKED instantiation of the b64 kernel (the others spill under its launch bound: make_plan); the label form
@@ -1433,6 +1484,7 @@ static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
   p.slots = 256 * 8;
   p.filter = a.filter != 0; p.sk_lds_off = 0;
   p.masked = a.masked != MASK_NONE; p.by_labels = a.masked == MASK_LABELS; p.rl_off = 0;
+  p.seen_n = 0;
   // Two families of the b64 kernel have no room for the masked state under its 72-VGPR bound: 128-byte rows (8 lanes per
   // candidate, 32 candidates per gather iteration) and bf16 rows of several chunks per lane.  Their masked forms would spill next
   // to the hand-issued row prefetch, so they are not instantiated and take the generic kernel
@@ -1454,6 +1506,17 @@ static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
     p.ccap = (std::max<uint32_t>(beam / 8 + p.deg_eff, a.nstarts) + 7) / 8 * 8;
     p.lds_bytes = (uint32_t)(64 * 8 + (size_t)p.ccap * 8 + 64 + (nch1 ? 0 : (size_t)ix.nch * ix.lpc * 16) + hbytes);
     if (p.masked) { p.rl_off = (p.lds_bytes + 15u) & ~15u; p.lds_bytes = p.rl_off + 1024; }
+    // Second-sighting table (plain search): B64_SEEN_N 16-bit tags id >> log2(B64_SEEN_N), every one below the empty value
+    // 0xFFFF, so the table is exact up to n = 0xFFFF * B64_SEEN_N points (33.5M); a larger table, or a cut-prune whose threshold
+    // is not monotone in the distance (a negative or NaN `cut`), takes the kernel without it.  1 KB more LDS per query: 26
+    // queries per CU instead of 30.
+    bool seen = ix.b64_seen != 0;
+    if (const char* sv = ab_env("PANN_B64_SEEN")) seen = atoi(sv) != 0;      // A/B switch: PANN_B64_SEEN=0 is the kernel without V
+    const bool cut_monotone = !(a.k > 0 && ix.metric == PANN_L2) || a.cut >= 0.0;
+    if (!p.masked && seen && cut_monotone && ix.n <= (uint64_t)0xFFFF * B64_SEEN_N) {
+      p.seen_n = B64_SEEN_N;
+      p.lds_bytes += B64_SEEN_N * 2;
+    }
   }
   p.b128 = p.hash_lds && p.bcap == 128 && a.nstarts <= 64;
   p.b128_hbm = false;
@@ -1529,7 +1592,7 @@ static hipError_t launch_variant(const BSParams& P, const Plan& p, hipStream_t s
     kern = p.by_labels ? masked_kernel<DT, METRIC, LPC, NCH1, MASK_LABELS>(p) : masked_kernel<DT, METRIC, LPC, NCH1, MASK_BITMAP>(p);
     if (!kern) return hipErrorInvalidValue;
   } else if (p.b64) {        // frontier in registers
-    kern = beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
+    kern = p.seen_n ? beam_search_b64_kernel<DT, METRIC, LPC, NCH1, B64_SEEN> : beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
   } else if (p.b128_codes) { // two frontier entries per lane, filter of class codes
     kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true, true>;
   } else if (p.b128) {       // two frontier entries per lane

@@ -12,6 +12,7 @@
 namespace pann {
 
 constexpr uint32_t SENTINEL = 0xFFFFFFFFu;  // empty adjacency slot on the device / empty filter slot
+constexpr uint32_t B64_SEEN_N = 512;        // entries of the beam-64 search's second-sighting table ("Second sightings")
 
 // Diagnostic A/B switches (environment variables that select kernel variants for same-box comparisons, tools/ab_*.sh) exist
 // only in `make alt` builds (-DPANN_AB, lib/libpann_alt.so); the shipped libpann.so reads no environment variable.
@@ -58,6 +59,7 @@ struct DeviceIndex {
   uint32_t max_deg = 0;
   uint32_t gstride = 0;  // uint32 per graph row on the device
   uint32_t forest_group = 0;  // HCNNG: trees split level by level together (0 = as many as 2^31 positions allow)
+  uint32_t b64_seen = 1;      // beam <= 64: search with the second-sighting table (0: without; beam_search.hip make_plan)
   // filter-code table of the beam-91..128 searches (filter_codes.hip): the code of every id and, slot-aligned with the graph rows,
   // of every neighbour.  gcode is only read while codes_valid: every writer of graph rows either maintains it or clears the flag.
   const uint16_t* rank16 = nullptr;   // [n]
