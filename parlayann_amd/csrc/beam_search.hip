@@ -127,11 +127,6 @@ struct BSParams {
 };
 
 template <bool HASH_LDS>
-__device__ __forceinline__ uint32_t hload(const uint32_t* H, uint32_t s) {
-  if constexpr (HASH_LDS) return H[s];
-  else return __hip_atomic_load(H + s, __ATOMIC_RELAXED, PANN_PRIVATE_SCOPE);
-}
-template <bool HASH_LDS>
 __device__ __forceinline__ void hstore(uint32_t* H, uint32_t s, uint32_t v) {
   if constexpr (HASH_LDS) H[s] = v;
   else __hip_atomic_store(H + s, v, __ATOMIC_RELAXED, PANN_PRIVATE_SCOPE);
@@ -516,7 +511,7 @@ template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = f
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(BSParams P) {
   static_assert(!(FILTER && MASKED), "the masked search has no sketch-filtered form");
   const int lane = threadIdx.x;
-  extern __shared__ __align__(16) uint8_t smem[];
+  extern __shared__ __align__(16) uint8_t smem[];   // carved as generic_lds (search_plan.h) lays it out, by typed pointer steps
   // ---- LDS carve (all regions 16 B aligned): 6.4 KB at beam 64 / degree 64 -> 24 queries per CU ----
   uint64_t* F = reinterpret_cast<uint64_t*>(smem);       // [bcap] frontier keys
   uint64_t* NF = F + P.bcap;                             // [bcap] merge output (swapped with F); between
@@ -823,7 +818,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
   constexpr int VN = MODE == B64_SEEN ? (int)B64_SEEN_N : 0;
   static_assert((B64_SEEN_N & (B64_SEEN_N - 1)) == 0 && B64_SEEN_N >= 128, "V: a power of two of whole words per lane");
   const int lane = threadIdx.x;
-  extern __shared__ __align__(16) uint8_t smem[];
+  extern __shared__ __align__(16) uint8_t smem[];   // carved as b64_lds (search_plan.h) lays it out, by typed pointer steps
   uint64_t* S = reinterpret_cast<uint64_t*>(smem);          // [64] merge scatter scratch; first 256 B double as Pl
   uint64_t* C = S + 64;                                     // [ccap] candidates (unsorted)
   uint8_t* Sv = reinterpret_cast<uint8_t*>(C + P.ccap);     // [64] flags of the scatter scratch
@@ -1106,7 +1101,7 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
   static_assert(!CODES || HASH_LDS, "the code table lives in LDS");
   constexpr int RB = 2;
   const int lane = threadIdx.x;
-  extern __shared__ __align__(16) uint8_t smem[];
+  extern __shared__ __align__(16) uint8_t smem[];   // carved as b128_lds (search_plan.h) lays it out, by typed pointer steps
   uint64_t* S = reinterpret_cast<uint64_t*>(smem);          // [128] merge scatter scratch; first 256 B double as Pl
   uint64_t* C = S + 64 * RB;                                // [ccap] candidates (unsorted)
   uint8_t* Sv = reinterpret_cast<uint8_t*>(C + P.ccap);     // [128] flags of the scatter scratch
@@ -1128,7 +1123,7 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
   uint32_t* H = HASH_LDS ? Hl : P.hash_global + ((size_t)blockIdx.x << P.bits);
   const uint32_t hb = HASH_LDS ? 0u : P.hsplit;
   uint8_t* const P8 = reinterpret_cast<uint8_t*>(Hl);                    // CODES: 8-bit plane [hsize], then
-  uint32_t* const P4 = Hl + (hsize >> 2);                                 // ... the 4-bit plane, 8 slots per dword [hsize / 8]
+  uint32_t* const P4 = Hl + (hsize >> 2);                            // ... the 4-bit plane, 8 slots per dword [hsize / 8]
   if constexpr (CODES) {
     for (uint32_t i = lane; i < (hsize >> 2) + (hsize >> 3); i += PANN_WAVE) Hl[i] = 0xFFFFFFFFu;
   } else {
@@ -1421,219 +1416,81 @@ __global__ void __launch_bounds__(PANN_WAVE) beam_search_b128_kernel(BSParams P)
   }   // while (slot < P.nq)
 }
 
-// ---------------------------------------------------------------------------------------------
-// host side: layout choice, LDS budget, dispatch
-// ---------------------------------------------------------------------------------------------
-
-// Lanes-per-candidate and chunks-per-lane for a row of dbytes.  One chunk (query in registers)
-// whenever the row is 128/256/512 B after padding to 16*LPC; otherwise LPC=4 (64-B granules,
-// the reference's own row alignment, point_range.h:94) or LPC=16 for long rows.
-void choose_point_layout(uint32_t dbytes, uint32_t* lpc, uint32_t* nch) {
-  const uint32_t r64 = (dbytes + 63) / 64 * 64;
-  if (const char* f = ab_env("PANN_FORCE_LPC")) {          // diagnostic A/B switch: lanes per candidate 4 / 8 / 16
-    const uint32_t l = (uint32_t)atoi(f);
-    if ((l == 4 || l == 8 || l == 16) && r64 % (l * 16) == 0 && r64 / (l * 16) > 1) { *lpc = l; *nch = r64 / (l * 16); return; }
-  }
-  if (r64 == 128) { *lpc = 8; *nch = 1; return; }
-  if (r64 == 256) { *lpc = 16; *nch = 1; return; }
-  if (r64 == 512) { *lpc = 32; *nch = 1; return; }
-  if (r64 % 256 == 0) { *lpc = 16; *nch = r64 / 256; return; }
-  if (r64 % 128 == 0) { *lpc = 8; *nch = r64 / 128; return; }      // e.g. f32 d=96: 384 B = 3 chunks of 8 lanes x 16 B
-  *lpc = 4; *nch = r64 / 64;
+// ---- host side: the plan (search_plan.h) and the dispatch ----
+// The plan's A/B switches, read here and nowhere else (`make alt` builds; in the shipped library ab_env answers null).  As before,
+// the three b128 switches are read once per process, PANN_B64_SEEN and PANN_FORCE_LPC at every call.
+static PlanSwitches plan_switches() {
+  static const bool b128_lds = ab_env("PANN_B128_LDS") != nullptr, b128_no24 = ab_env("PANN_B128_NO24") != nullptr;
+  static const char* split = ab_env("PANN_B128_SPLIT");
+  PlanSwitches s{b128_lds, b128_no24};
+  if (split) s.b128_split = (uint32_t)atoi(split);
+  if (const char* v = ab_env("PANN_B64_SEEN")) s.b64_seen = atoi(v) != 0;      // PANN_B64_SEEN=0 is the kernel without V
+  if (const char* v = ab_env("PANN_FORCE_LPC")) s.force_lpc = (uint32_t)atoi(v);
+  return s;
 }
-
-static uint32_t filter_bits(int64_t beam) {  // :52
-  double l = std::ceil(std::log2((double)beam * (double)beam)) - 2.0;
-  int b = (int)l;
-  return (uint32_t)(b < 10 ? 10 : b);
+void choose_point_layout(uint32_t dbytes, uint32_t* lpc, uint32_t* nch) { choose_point_layout(dbytes, plan_switches().force_lpc, lpc, nch); }
+static SearchPlan plan_of(const DeviceIndex& ix, const SearchArgs& a) {
+  const PlanIndex pi{ix.dtype, ix.metric, ix.lpc, ix.nch, ix.max_deg, ix.gstride, ix.n, ix.sk_stride, ix.b64_seen,
+                     ix.codes_valid && ix.gcode && ix.rank16};
+  const PlanCall pc{a.nq, a.nstarts, a.k, a.beam, a.degree_limit, a.cut, a.dcap, a.filter != 0, a.masked};
+  return make_plan(pi, pc, plan_switches());
 }
+size_t search_workspace_bytes(const DeviceIndex& ix, const SearchArgs& a) { return (size_t)plan_of(ix, a).ws_bytes; }
 
-struct Plan {
-  uint32_t bits, bcap, ccap, deg_eff, dcap, lds_bytes; bool hash_lds; uint32_t slots; bool b64; bool b128;
-  bool b128_codes; // beam 91..128 with the filter as 12-bit class codes in LDS (the index keeps the codes: filter_codes.hip)
-  bool b128_hbm;   // beam 65..128 with the filter in HBM (persistent blocks)
-  uint32_t hsplit; // ... of which the part with an LDS share (filter_update split mode)
-  uint32_t p24;    // ... stored as planar 24-bit entries
-  bool filter; uint32_t sk_lds_off;   // sketch-filtered search: the generic kernel's FILTER variant, query sketch after its LDS state
-  uint32_t rl_off; // ... masked: byte offset of the result list (64 keys) in LDS
-  bool masked;     // allow-bitmap search: the MASKED variant of the b64 kernel (bcap 64) or of the generic kernel (every other beam)
-  bool by_labels;  // ... with label predicates in place of the bitmap: the MASK_LABELS instantiation of the same kernel
-  uint32_t seen_n; // plain b64 kernel: entries of the second-sighting table V behind the filter (0: the kernel without it)
-};
-
-// which layouts have a MASKED instantiation of the b64 kernel (the others spill under its launch bound: make_plan); the label form
-// needs no vector register beyond the bitmap form (MaskSrc), so one predicate serves both
-constexpr bool masked_b64_fits(int dtype, uint32_t lpc, bool nch1) { return !(lpc == 8 && nch1) && !(dtype == PANN_BF16 && !nch1); }
-
-static Plan make_plan(const DeviceIndex& ix, const SearchArgs& a) {
-  Plan p;
-  p.bits = filter_bits(a.beam);
-  const uint32_t beam = (uint32_t)a.beam;
-  p.bcap = (std::max<uint32_t>(beam, a.nstarts) + 63) / 64 * 64;
-  int64_t dl = std::min<int64_t>(std::max<int64_t>(a.degree_limit, 0), (int64_t)ix.max_deg);
-  p.deg_eff = (uint32_t)dl;
-  // at merge time |C| <= (beam/8 - 1) + deg_eff (accumulation stops at beam/8); starts first
-  p.ccap = (std::max<uint32_t>(beam / 8 + p.deg_eff, a.nstarts) + 63) / 64 * 64;
-  p.dcap = std::max<uint32_t>(a.dcap, 64);
-  const bool nch1 = layout_query_in_registers(ix);
-  size_t fixed = (size_t)p.bcap * 8 * 2 + (size_t)p.ccap * 8 + (size_t)p.bcap * 2 +
-                 (size_t)p.ccap * 2 + (nch1 ? 0 : (size_t)ix.nch * ix.lpc * 16);
-  size_t hbytes = (size_t)4 << p.bits;
-  p.hash_lds = (hbytes <= 16384) && (fixed + hbytes <= 64 * 1024);
-  p.lds_bytes = (uint32_t)(fixed + (p.hash_lds ? hbytes : 1024));      // HBM filter: 1 KB replay scratch (filter_update)
-  p.slots = 256 * 8;
-  p.filter = a.filter != 0; p.sk_lds_off = 0;
-  p.masked = a.masked != MASK_NONE; p.by_labels = a.masked == MASK_LABELS; p.rl_off = 0;
-  p.seen_n = 0;
-  // Two families of the b64 kernel have no room for the masked state under its 72-VGPR bound: 128-byte rows (8 lanes per
-  // candidate, 32 candidates per gather iteration) and bf16 rows of several chunks per lane.  Their masked forms would spill next
-  // to the hand-issued row prefetch, so they are not instantiated and take the generic kernel
-  const bool masked_b64 = p.hash_lds && p.bcap == 64 && masked_b64_fits(ix.dtype, ix.lpc, nch1);
-  if (p.masked && !masked_b64) {   // no masked b128 kernel either: the generic one, as the sketch filter does
-    p.b64 = p.b128 = p.b128_codes = p.b128_hbm = false; p.hsplit = 0; p.p24 = 0;
-    p.rl_off = (p.lds_bytes + 15u) & ~15u;             // its LDS state, then the result list and the keys of one gather (64 + 64 keys)
-    p.lds_bytes = p.rl_off + 1024;
-    return p;
-  }
-  if (p.filter) {     // every beam width takes the generic kernel; its LDS state, then the query sketch
-    p.b64 = p.b128 = p.b128_codes = p.b128_hbm = false; p.hsplit = 0; p.p24 = 0;
-    p.sk_lds_off = (p.lds_bytes + 15u) & ~15u;
-    p.lds_bytes = p.sk_lds_off + ix.sk_stride;
-    return p;
-  }
-  p.b64 = p.hash_lds && p.bcap == 64;
-  if (p.b64) {   // register-frontier kernel: scratch[64] + candidates (exact, 8-entry granules) + flags + query + filter
-    p.ccap = (std::max<uint32_t>(beam / 8 + p.deg_eff, a.nstarts) + 7) / 8 * 8;
-    p.lds_bytes = (uint32_t)(64 * 8 + (size_t)p.ccap * 8 + 64 + (nch1 ? 0 : (size_t)ix.nch * ix.lpc * 16) + hbytes);
-    if (p.masked) { p.rl_off = (p.lds_bytes + 15u) & ~15u; p.lds_bytes = p.rl_off + 1024; }
-    // Second-sighting table (plain search): B64_SEEN_N 16-bit tags id >> log2(B64_SEEN_N), every one below the empty value
-    // 0xFFFF, so the table is exact up to n = 0xFFFF * B64_SEEN_N points (33.5M); a larger table, or a cut-prune whose threshold
-    // is not monotone in the distance (a negative or NaN `cut`), takes the kernel without it.  1 KB more LDS per query: 26
-    // queries per CU instead of 30.
-    bool seen = ix.b64_seen != 0;
-    if (const char* sv = ab_env("PANN_B64_SEEN")) seen = atoi(sv) != 0;      // A/B switch: PANN_B64_SEEN=0 is the kernel without V
-    const bool cut_monotone = !(a.k > 0 && ix.metric == PANN_L2) || a.cut >= 0.0;
-    if (!p.masked && seen && cut_monotone && ix.n <= (uint64_t)0xFFFF * B64_SEEN_N) {
-      p.seen_n = B64_SEEN_N;
-      p.lds_bytes += B64_SEEN_N * 2;
-    }
-  }
-  p.b128 = p.hash_lds && p.bcap == 128 && a.nstarts <= 64;
-  p.b128_hbm = false;
-  p.b128_codes = p.b128 && p.bits == FILTER_CODE_BITS && ix.codes_valid && ix.gcode && ix.rank16 && ix.gstride <= PANN_WAVE;
-  if (p.b128_codes) {        // 6 KB of table + the merge scratch (which doubles as the replay scratch T) + candidates + flags + query
-    p.ccap = (std::max<uint32_t>(beam / 8 + p.deg_eff, a.nstarts) + 7) / 8 * 8;
-    p.hsplit = 0; p.p24 = 0;
-    p.lds_bytes = (uint32_t)(128 * 8 + (size_t)p.ccap * 8 + 128 + (nch1 ? 0 : (size_t)ix.nch * ix.lpc * 16) + ((size_t)1 << p.bits) * 3 / 2);
-  } else if (p.b128) {
-    p.ccap = (std::max<uint32_t>(beam / 8 + p.deg_eff, a.nstarts) + 7) / 8 * 8;
-    // 16 KB of filter per query leaves 8 queries per CU (2 048 on the chip).  Larger batches put the table in HBM
-    // (Infinity-Cache resident): one dependent load per adjacency row, 3x the queries per CU; measured +17 % on the
-    // C3 build's search phase and +10 % on beam-128 queries -- the 64 single-word table requests per row make the
-    // L2 request rate the new limit (in-kernel stamps: every phase 2-3x longer at 3x the occupancy).
-    static const bool force_lds = ab_env("PANN_B128_LDS") != nullptr;       // diagnostic A/B switch
-    p.b128_hbm = (hbytes > 8192) && a.nq > 2048 && !force_lds;
-    p.hsplit = 0;
-    if (p.b128_hbm) {   // one table per block, >= the resident waves
-      static const char* sp = ab_env("PANN_B128_SPLIT");
-      p.hsplit = sp ? (uint32_t)atoi(sp) : 1u;     // measured: half in LDS 2.99 M q/s, none 2.46, three quarters 2.67, whole table in LDS 2.28
-      if (p.hsplit > 3) p.hsplit = 0;
-      static const bool no24 = ab_env("PANN_B128_NO24") != nullptr;              // diagnostic A/B switch
-      if (p.hsplit == 3 && (no24 || !(ix.n < 0xFFFFFFull))) p.hsplit = 1;     // the all-LDS mode exists for 24-bit planes only
-      p.hash_lds = false; p.slots = 256 * 32;
-      p.p24 = (p.hsplit && ix.n < 0xFFFFFFull && !no24) ? 1u : 0u;
-      // the 1 KB replay scratch of filter_update aliases the merge scratch S; the LDS share of the table follows the query
-      hbytes = p.hsplit == 3 ? ((size_t)3 << p.bits)
-             : p.hsplit ? (((size_t)1 << p.bits) - ((size_t)1 << (p.bits - p.hsplit))) * (p.p24 ? 3 : 4) : 0;
-    }
-    p.lds_bytes = (uint32_t)(128 * 8 + (size_t)p.ccap * 8 + 128 + (nch1 ? 0 : (size_t)ix.nch * ix.lpc * 16) + hbytes);
-  }
-  return p;
-}
-
-size_t search_workspace_bytes(const DeviceIndex& ix, const SearchArgs& a) {
-  Plan p = make_plan(ix, a);
-  size_t need = 256;                                   // counter + status
-  need += (size_t)a.nq * p.dcap * 8;                   // dropped lists
-  if (!p.hash_lds) need += ((size_t)std::min<uint64_t>(a.nq, p.slots) << p.bits) * 4;
-  return need;
-}
-
-// One launch: LDS above the 48 KB default is asked for by attribute; one block per query, or -- persistent kernels, whose blocks
-// pull queries from the counter -- one block per filter table of the workspace (search_workspace_bytes).
+// The kernel of a plan's (kernel, table, mode) for one point layout.  make_plan plans no other combination: no masked or sketch
+// b128, no sketch b64, no masked b64 of a layout that masked_b64_fits rules out.  The second form picks the handle's element type,
+// metric and point layout; a handle with none of the known ones (a corrupt one) gets no kernel, as before.
 using SearchKernel = void (*)(BSParams);
-static hipError_t launch_search(SearchKernel kern, const BSParams& P, const Plan& p, bool persistent, hipStream_t stream) {
-  if (p.lds_bytes > 48 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
-  const uint32_t grid = persistent ? (uint32_t)std::min<uint64_t>(P.nq, p.slots) : P.nq;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
-  return hipGetLastError();
-}
-
-// masked search, MODE = MASK_BITMAP / MASK_LABELS: register frontier at bcap 64, else the generic kernel
-template <int DT, int METRIC, int LPC, bool NCH1, int MODE>
-static SearchKernel masked_kernel(const Plan& p) {
-  if (p.b64) {
-    if constexpr (masked_b64_fits(DT, LPC, NCH1)) return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MODE>;
-    else return nullptr;                                                             // make_plan never asks for it
-  }
-  if (p.hash_lds) return beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MODE>;
-  return beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MODE>;
-}
-
-// Every kernel whose filter table is in HBM (!hash_lds) is persistent, and no other.
 template <int DT, int METRIC, int LPC, bool NCH1>
-static hipError_t launch_variant(const BSParams& P, const Plan& p, hipStream_t stream) {
-  SearchKernel kern;
-  if (p.filter) {            // generic kernel with the sketch filter
-    if (p.hash_lds) kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true, true>;
-    else kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false, true>;
-  } else if (p.masked) {     // allow bitmap or label predicates
-    kern = p.by_labels ? masked_kernel<DT, METRIC, LPC, NCH1, MASK_LABELS>(p) : masked_kernel<DT, METRIC, LPC, NCH1, MASK_BITMAP>(p);
-    if (!kern) return hipErrorInvalidValue;
-  } else if (p.b64) {        // frontier in registers
-    kern = p.seen_n ? beam_search_b64_kernel<DT, METRIC, LPC, NCH1, B64_SEEN> : beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
-  } else if (p.b128_codes) { // two frontier entries per lane, filter of class codes
-    kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true, true>;
-  } else if (p.b128) {       // two frontier entries per lane
-    if (p.b128_hbm) kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, false>;
-    else kern = beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true>;
-  } else if (p.hash_lds) {
-    kern = beam_search_kernel<DT, METRIC, LPC, NCH1, true>;
-  } else {
-    kern = beam_search_kernel<DT, METRIC, LPC, NCH1, false>;
+static SearchKernel plan_kernel(const SearchPlan& p) {
+  const bool lds = p.table == TABLE_LDS;
+  switch (p.kernel * 8 + p.mode) {
+    case KERNEL_GENERIC * 8 + MODE_SKETCH:  // frontier in LDS
+      return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true, true> : beam_search_kernel<DT, METRIC, LPC, NCH1, false, true>;
+    case KERNEL_B64 * 8 + MODE_LABELS:      // frontier in registers
+      if constexpr (masked_b64_fits(DT, LPC, NCH1)) return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MASK_LABELS>;
+      break;
+    case KERNEL_GENERIC * 8 + MODE_LABELS:
+      return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MASK_LABELS> : beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MASK_LABELS>;
+    case KERNEL_B64 * 8 + MODE_BITMAP:
+      if constexpr (masked_b64_fits(DT, LPC, NCH1)) return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MASK_BITMAP>;
+      break;
+    case KERNEL_GENERIC * 8 + MODE_BITMAP:
+      return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MASK_BITMAP> : beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MASK_BITMAP>;
+    case KERNEL_B64 * 8 + MODE_PLAIN_V: return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, B64_SEEN>;
+    case KERNEL_B64 * 8 + MODE_PLAIN: return beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
+    case KERNEL_B128 * 8 + MODE_PLAIN:      // two frontier entries per lane
+      if (p.table == TABLE_CODES) return beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true, true>;
+      return !lds ? beam_search_b128_kernel<DT, METRIC, LPC, NCH1, false> : beam_search_b128_kernel<DT, METRIC, LPC, NCH1, true>;
+    case KERNEL_GENERIC * 8 + MODE_PLAIN:
+      return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true> : beam_search_kernel<DT, METRIC, LPC, NCH1, false>;
   }
-  return launch_search(kern, P, p, !p.hash_lds, stream);
+  return nullptr;      // not a plan of make_plan: the launch fails with hipErrorInvalidValue
+}
+static SearchKernel plan_kernel(const DeviceIndex& ix, const SearchPlan& p) {
+  const bool type_ok = ix.dtype == PANN_U4 ? ix.metric == PANN_L2 : ix.dtype == PANN_I4 ? ix.metric == PANN_MIPS      // a four-bit handle's only pairings
+                       : esize_of(ix.dtype) != 0 && (ix.metric == PANN_L2 || ix.metric == PANN_MIPS);
+  const bool lpc_ok = ix.lpc == 8 || ix.lpc == 16 || (layout_query_in_registers(ix) ? ix.lpc == 32 : ix.lpc == 4);
+  SearchKernel kern = nullptr;
+#define CALL_BS(DT, MT, LPC, NCH1) kern = plan_kernel<DT, MT, LPC, NCH1>(p)
+  if (!type_ok || !lpc_ok) return nullptr;
+  if (!is_4bit_dtype(ix.dtype)) PANN_TYPE_SWITCH(ix, CALL_BS);
+  else if (ix.dtype == PANN_U4) PANN_LAYOUT_SWITCH(ix, PANN_U4, PANN_L2, CALL_BS);
+  else PANN_LAYOUT_SWITCH(ix, PANN_I4, PANN_MIPS, CALL_BS);
+#undef CALL_BS
+  return kern;
 }
 
-template <int DT, int METRIC>
-static hipError_t launch_layout(const DeviceIndex& ix, const BSParams& P, const Plan& p, hipStream_t s) {
-  if (layout_query_in_registers(ix)) {
-    if (ix.lpc == 8) return launch_variant<DT, METRIC, 8, true>(P, p, s);
-    if (ix.lpc == 16) return launch_variant<DT, METRIC, 16, true>(P, p, s);
-    if (ix.lpc == 32) return launch_variant<DT, METRIC, 32, true>(P, p, s);
-  }
-  if (ix.lpc == 4) return launch_variant<DT, METRIC, 4, false>(P, p, s);
-  if (ix.lpc == 8) return launch_variant<DT, METRIC, 8, false>(P, p, s);
-  if (ix.lpc == 16) return launch_variant<DT, METRIC, 16, false>(P, p, s);
-  return hipErrorInvalidValue;
-}
-
-int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, size_t ws_bytes,
-                       hipStream_t stream) {
+int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, size_t ws_bytes, hipStream_t stream) {
   if (a.nq == 0) return PANN_OK;
   if (a.nq > 0xFFFFFFF0ull) { set_error("pann_batch_search: nq too large"); return PANN_ERR_BAD_ARG; }
   if (a.beam <= 0 || a.beam > 65536) { set_error("pann_batch_search: beam out of range [1,65536]"); return PANN_ERR_BAD_ARG; }
-  if (a.nstarts == 0) {  // beamSearch.h:38-41
-    set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG;
-  }
+  if (a.nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }  // beamSearch.h:38-41
   if ((int64_t)a.nstarts > a.beam) { set_error("pann_batch_search: more start points than beam"); return PANN_ERR_BAD_ARG; }
   if (a.out.out_k > (uint64_t)a.beam) {  // beamSearch.h:368-372
     set_error("Error: beam search parameter Q same size or smaller than k"); return PANN_ERR_BAD_ARG;
   }
-  if ((a.queries == nullptr) == (a.query_ids == nullptr)) {
-    set_error("pann_batch_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG;
-  }
+  if ((a.queries == nullptr) == (a.query_ids == nullptr)) { set_error("pann_batch_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
   if (a.filter) {
     if (!ix.sketch || !sketch_kind_ok(ix.sk_kind)) { set_error("pann_batch_search_filtered: no sketch attached to the index"); return PANN_ERR_BAD_ARG; }
     if ((a.queries != nullptr) != (a.sketch_queries != nullptr)) {
@@ -1650,10 +1507,9 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   if (a.masked == MASK_LABELS && (!a.labels || !a.preds || a.pred_stride > 1 || !pred_kind_known(a.pred_kind))) {
     set_error("pann_batch_search_labeled: labels, predicates of a known kind and a predicate stride of 0 or 1 are needed"); return PANN_ERR_BAD_ARG;
   }
-  Plan p = make_plan(ix, a);
+  const SearchPlan p = plan_of(ix, a);
   if (p.lds_bytes > 160 * 1024) { set_error("pann_batch_search: beam/degree too large for LDS state"); return PANN_ERR_UNSUPPORTED; }
-  if (search_workspace_bytes(ix, a) > ws_bytes) { set_error("pann_batch_search: workspace too small"); return PANN_ERR_BAD_ARG; }
-
+  if (p.ws_bytes > ws_bytes) { set_error("pann_batch_search: workspace too small"); return PANN_ERR_BAD_ARG; }
   BSParams P;
   P.points = ix.points; P.pstride = ix.pstride; P.dbytes = ix.dbytes; P.nch = ix.nch; P.exact = ix.exact;
   P.graph = ix.graph; P.gstride = ix.gstride; P.max_deg = ix.max_deg;
@@ -1662,35 +1518,27 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   P.k = (uint32_t)std::max<int64_t>(a.k, 0); P.beam = (uint32_t)a.beam;
   P.limit = (uint32_t)std::min<int64_t>(std::max<int64_t>(a.limit, 0), 0xFFFFFFFFll);
   P.degree_limit = p.deg_eff; P.cut = a.cut;
-  P.skip_enabled = (a.limit >= 2 * a.beam) ? 1u : 0u;
-  P.cut_enabled = (a.k > 0 && ix.metric == PANN_L2) ? 1u : 0u;
-  P.bits = p.bits; P.bcap = p.bcap; P.ccap = p.ccap;
-  uint8_t* w = (uint8_t*)ws;
+  P.skip_enabled = (a.limit >= 2 * a.beam) ? 1u : 0u; P.cut_enabled = (a.k > 0 && ix.metric == PANN_L2) ? 1u : 0u;
+  P.bits = p.bits; P.bcap = p.bcap; P.ccap = p.ccap; P.hsplit = p.hsplit; P.p24 = p.p24; P.sk_lds_off = p.sk_lds_off; P.rl_off = p.rl_off;   // the plan's
+  uint8_t* w = (uint8_t*)ws;      // 256 bytes (counter, status) | dropped lists | filter tables of a persistent launch
   P.work_counter = (uint32_t*)w; P.status = (uint32_t*)(w + 64);
   P.dropped = (uint64_t*)(w + 256); P.dcap = p.dcap;
-  {
-    static const char* pf = ab_env("PANN_PRIO_FROM");              // A/B switch: tenths of the grid without priority (default 8; 10 = off)
-    const uint32_t tenths = pf ? (uint32_t)atoi(pf) : 8u;
-    P.prio_start = tenths >= 10 ? 0xFFFFFFFFu : (uint32_t)((uint64_t)a.nq * tenths / 10);
-  }
-  P.hsplit = p.b128_hbm ? p.hsplit : 0u;
-  P.p24 = p.b128_hbm ? p.p24 : 0u;
-  P.gcode = ix.gcode; P.rank16 = ix.rank16;
-  P.order = a.order;
-  P.hash_global = p.hash_lds ? nullptr : (uint32_t*)(w + 256 + (size_t)a.nq * p.dcap * 8);
-  P.out = a.out;
-  P.stamps = nullptr;
+  static const char* pf = ab_env("PANN_PRIO_FROM");              // A/B switch: tenths of the grid without priority (default 8; 10 = off)
+  const uint32_t tenths = pf ? (uint32_t)atoi(pf) : 8u;
+  P.prio_start = tenths >= 10 ? 0xFFFFFFFFu : (uint32_t)((uint64_t)a.nq * tenths / 10);
+  P.gcode = ix.gcode; P.rank16 = ix.rank16; P.order = a.order;
+  P.hash_global = p.persistent() ? (uint32_t*)(w + 256 + p.dropped_bytes(a.nq)) : nullptr;
+  P.out = a.out; P.stamps = nullptr;
   P.sketch = a.filter ? ix.sketch : nullptr; P.sk_stride = a.filter ? ix.sk_stride : 0u;
   P.sk_kind = (uint32_t)ix.sk_kind; P.sk_as_written = ix.sk_as_written; P.sk_nblk = (ix.d + 63) / 64;
   P.sketch_queries = a.sketch_queries; P.sq_stride = a.sq_stride;
   P.sk_row_bytes = a.filter ? sketch_row_bytes(ix.sk_kind, ix.d) : 0u;
-  P.sk_lds_off = p.sk_lds_off; P.pruned_cmps = a.filter ? a.pruned_cmps : nullptr;
+  P.pruned_cmps = a.filter ? a.pruned_cmps : nullptr;
   P.allow = a.masked == MASK_BITMAP ? a.allow : nullptr; P.allow_stride = a.masked == MASK_BITMAP ? a.allow_stride : 0;
   const bool lab = a.masked == MASK_LABELS;
   P.labels = lab ? a.labels : nullptr; P.preds = lab ? a.preds : nullptr;
   P.pred_stride = lab ? a.pred_stride : 0u; P.pred_kind = lab ? (uint32_t)a.pred_kind : 0u;
   P.result_count = a.masked ? a.result_count : nullptr; P.allowed_cmps = a.masked ? a.allowed_cmps : nullptr;
-  P.rl_off = p.rl_off;
 #ifdef PANN_STAMPS
   static unsigned long long* d_stamps = nullptr; static size_t stamps_cap = 0;
   if (stamps_cap < a.nq) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void**)&d_stamps, a.nq * 64); stamps_cap = a.nq; }
@@ -1698,15 +1546,16 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
 #endif
   PANN_HIP(hipMemsetAsync(w, 0, 256, stream));
 
+  // One launch: LDS above the 48 KB default is asked for by attribute; one block per query, or -- persistent kernels, whose blocks
+  // pull queries from the counter -- one block per filter table of the workspace.
   hipError_t e = hipErrorInvalidValue;
-#define PANN_DISPATCH(DT, MT) if (ix.dtype == DT && ix.metric == MT) e = launch_layout<DT, MT>(ix, P, p, stream);
-  PANN_DISPATCH(PANN_U8, PANN_L2) PANN_DISPATCH(PANN_U8, PANN_MIPS)
-  PANN_DISPATCH(PANN_I8, PANN_L2) PANN_DISPATCH(PANN_I8, PANN_MIPS)
-  PANN_DISPATCH(PANN_F32, PANN_L2) PANN_DISPATCH(PANN_F32, PANN_MIPS)
-  PANN_DISPATCH(PANN_F16, PANN_L2) PANN_DISPATCH(PANN_F16, PANN_MIPS)
-  PANN_DISPATCH(PANN_BF16, PANN_L2) PANN_DISPATCH(PANN_BF16, PANN_MIPS)
-  PANN_DISPATCH(PANN_U4, PANN_L2) PANN_DISPATCH(PANN_I4, PANN_MIPS)      // the only pairings a four-bit handle can have
-#undef PANN_DISPATCH
+  if (const SearchKernel kern = plan_kernel(ix, p)) {
+    if (p.lds_bytes > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
+    const uint32_t grid = p.persistent() ? (uint32_t)std::min<uint64_t>(P.nq, p.slots) : P.nq;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(PANN_WAVE), p.lds_bytes, stream, P);
+    e = hipGetLastError();
+  }
   if (e != hipSuccess) return hip_fail(e, "beam_search_kernel launch");
   // the status word follows the results on the launch stream (pann_search_out::status, device pointer here)
   if (a.out.status) PANN_HIP(hipMemcpyAsync(a.out.status, P.status, 4, hipMemcpyDeviceToDevice, stream));

@@ -8,11 +8,11 @@
 #include <string>
 
 #include "../../include/pann.h"
+#include "search_plan.h"
 
 namespace pann {
 
 constexpr uint32_t SENTINEL = 0xFFFFFFFFu;  // empty adjacency slot on the device / empty filter slot
-constexpr uint32_t B64_SEEN_N = 512;        // entries of the beam-64 search's second-sighting table ("Second sightings")
 
 // Diagnostic A/B switches (environment variables that select kernel variants for same-box comparisons, tools/ab_*.sh) exist
 // only in `make alt` builds (-DPANN_AB, lib/libpann_alt.so); the shipped libpann.so reads no environment variable.
@@ -59,7 +59,7 @@ struct DeviceIndex {
   uint32_t max_deg = 0;
   uint32_t gstride = 0;  // uint32 per graph row on the device
   uint32_t forest_group = 0;  // HCNNG: trees split level by level together (0 = as many as 2^31 positions allow)
-  uint32_t b64_seen = 1;      // beam <= 64: search with the second-sighting table (0: without; beam_search.hip make_plan)
+  uint32_t b64_seen = 1;      // beam <= 64: search with the second-sighting table (0: without; search_plan.h make_plan)
   // filter-code table of the beam-91..128 searches (filter_codes.hip): the code of every id and, slot-aligned with the graph rows,
   // of every neighbour.  gcode is only read while codes_valid: every writer of graph rows either maintains it or clears the flag.
   const uint16_t* rank16 = nullptr;   // [n]
@@ -78,14 +78,10 @@ struct DeviceIndex {
   const uint32_t* labels = nullptr;   // [n]
 };
 
-// The kernels come in two families (PANN_LAYOUT_SWITCH): rows that are ONE 16-byte chunk per lane with 8 / 16 / 32
-// lanes per candidate keep the query in registers; every other layout -- including 64-byte rows, lpc 4 / nch 1 --
-// runs the generic variants, which keep the query in LDS.  All LDS sizes on the host must use THIS predicate.
-inline bool layout_query_in_registers(const DeviceIndex& ix) { return ix.nch == 1 && ix.lpc != 4; }
-inline size_t query_lds_bytes(const DeviceIndex& ix) { return layout_query_in_registers(ix) ? 0 : (size_t)ix.nch * ix.lpc * 16; }
+// query in registers or in LDS: the one definition is search_plan.h's
+inline bool layout_query_in_registers(const DeviceIndex& ix) { return layout_query_in_registers(ix.lpc, ix.nch); }
+inline size_t query_lds_bytes(const DeviceIndex& ix) { return query_lds_bytes(ix.lpc, ix.nch); }
 
-// how a masked search decides whether a compared point is allowed (SearchArgs::masked; template parameter of the kernels)
-enum { MASK_NONE = 0, MASK_BITMAP = 1, MASK_LABELS = 2 };
 inline bool pred_kind_known(int kind) { return kind == PANN_PRED_ANY || kind == PANN_PRED_MATCH || kind == PANN_PRED_RANGE; }
 
 struct SearchArgs {  // one batched beam search, everything device resident
@@ -312,7 +308,6 @@ int leaf_knn_rows_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, cons
                       const uint64_t* h_off, uint64_t nseg, uint32_t m, int exclude_same, uint32_t* d_out_ids, float* d_out_dists);
 
 // filter_codes.hip
-constexpr uint32_t FILTER_CODE_BITS = 12;      // the table size the codes are made for: beam 91..128 (beamSearch.h:52)
 int filter_codes_build_ranks(uint64_t n, uint32_t bits, Workspace& ws, hipStream_t st, uint16_t* rank16, uint32_t* max_rank_out);
 int filter_codes_rebuild_rows(const DeviceIndex& ix, hipStream_t st);
 

@@ -180,7 +180,7 @@ def test_per_query_starts_like_beamSearchRandom(oracle):
 @pytest.mark.parametrize("dtype,d,beam", [(np.uint8, 128, 128), (np.float32, 96, 100), (np.float16, 128, 90)])
 def test_search_large_batches_beam_65_to_128(oracle, dtype, d, beam):
     """more than 2048 queries at beam 65..128 take the persistent kernel whose filter table is split between LDS
-    and HBM (beam_search.hip make_plan): results and counters must not depend on where the table lives"""
+    and HBM (search_plan.h make_plan): results and counters must not depend on where the table lives"""
     n, nq = 6000, 2600
     X, _, G = _setup(oracle, n, d, dtype, "l2", R=32, L=64, nq=10)
     Q = _data(nq, d, dtype, 777)

@@ -1,4 +1,4 @@
-"""Launch shapes of the beam search that no other test pins (beam_search.hip: launch_search): persistent grids with more
+"""Launch shapes of the beam search that no other test pins (beam_search.hip: launch_beam_search): persistent grids with more
 queries than filter tables, and more than 48 KB of dynamic LDS.  u8 L2, n = 4096, d = 32, a random graph of degree 16,
 base-point queries; ids, dists, visited_count and dist_cmps bit for bit against the CPU oracle (tests/oracle_api.py), the
 masked case against the restatement tests/masked_ref.py."""
