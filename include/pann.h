@@ -747,6 +747,39 @@ int pann_batch_search_labeled_dev(pann_index* idx, const void* d_queries, const 
                                   int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_search_out* d_out,
                                   uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream);
 
+/* ---- steered masked search: the walk spends its distances on allowed points only (DESIGN.md "Steered masked search") ----
+ * This project's own rule.  pann_batch_search_masked / _labeled with ONE change: the neighbours of a visited vertex that passed
+ * the hash filter and are NOT allowed get no distance; they are bridges.  After the vertex's own row, the bridges' rows are read in
+ * order, each whole or not at all, until `fill` points wait for a distance; of a bridge's neighbours only the allowed ones are
+ * looked at (and only they enter the hash filter), so there is no third hop.  fill: 1 .. deg_eff = min(degree_limit, max_degree);
+ * 0 means deg_eff, a larger value is clamped.  Start points get a distance whether allowed or not; they are the only disallowed
+ * points that do, so apart from them out->dist_cmps == out_allowed_cmps.  degree_sum counts the visited vertices' rows only.
+ * The result rule, out_result_count and out_allowed_cmps are pann_batch_search_masked's.  With a bitmap that allows every point
+ * every output equals pann_batch_search_masked's, whatever fill is.
+ * out_steer (optional, nq x 2): per query the bridge rows expanded, and the entries the two-hop pass added.
+ * Status: as the masked twin (out_k > 64 -> PANN_ERR_UNSUPPORTED, out_k > beam or k > beam -> PANN_ERR_BAD_ARG, ...).  There is no
+ * form with the sketch filter, on the fused rerank path or for a sharded index. */
+int pann_batch_search_steered(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                              const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
+                              uint32_t* out_result_count, uint32_t* out_allowed_cmps, uint32_t fill, uint32_t* out_steer);
+/* Device pointers throughout, launched on `stream`; no sync, no alloc beyond the workspace growth of pann_batch_search_dev. */
+int pann_batch_search_steered_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                  uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                  const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
+                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, uint32_t fill, uint32_t* d_out_steer,
+                                  void* stream);
+/* The same with (kind, preds, npreds) in place of the bitmap, as pann_batch_search_labeled. */
+int pann_batch_search_steered_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                                      uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                                      int kind, const pann_label_pred* preds, uint64_t npreds, const pann_search_out* out,
+                                      uint32_t* out_result_count, uint32_t* out_allowed_cmps, uint32_t fill, uint32_t* out_steer);
+int pann_batch_search_steered_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                          uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts,
+                                          const pann_query_params* qp, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                                          const pann_search_out* d_out, uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps,
+                                          uint32_t fill, uint32_t* d_out_steer, void* stream);
+
 /* pann_batch_search_masked_rerank* with predicates.  The labels are read from `full`, the caller's primary handle; quant needs
  * none, and its own labels are not consulted. */
 int pann_batch_search_labeled_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams,

@@ -229,6 +229,19 @@ SIGNATURES = {
     "pann_batch_search_labeled_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
                                                 C.POINTER(QueryParams), C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SearchOut),
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_batch_search_steered": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                            C.POINTER(QueryParams), C.c_void_p, C.c_uint64, C.POINTER(SearchOut), C.c_void_p, C.c_void_p,
+                                            C.c_uint32, C.c_void_p]),
+    "pann_batch_search_steered_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                C.POINTER(QueryParams), C.c_void_p, C.c_uint64, C.POINTER(SearchOut), C.c_void_p,
+                                                C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "pann_batch_search_steered_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                    C.POINTER(QueryParams), C.c_int, C.c_void_p, C.c_uint64, C.POINTER(SearchOut),
+                                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "pann_batch_search_steered_labeled_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                        C.c_uint32, C.POINTER(QueryParams), C.c_int, C.c_void_p, C.c_uint64,
+                                                        C.POINTER(SearchOut), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                                        C.c_void_p]),
     "pann_batch_search_labeled_rerank": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
                                                    C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.c_int,
                                                    C.c_void_p, C.c_uint64, C.POINTER(RerankOut), C.c_void_p, C.c_void_p]),

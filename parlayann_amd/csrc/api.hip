@@ -619,6 +619,9 @@ static int masked_search_checks(const pann_index* idx, const PointFilter& F, uin
   return PANN_OK;
 }
 
+// the steered form of a masked call (DESIGN.md "Steered masked search"): fill, and the optional nq x 2 counters (host or device, as the call)
+struct SteerReq { uint32_t fill; uint32_t* out; };
+
 static int search_common_checks(pann_index* idx, uint64_t nq, const pann_query_params* qp, const pann_search_out* out) {
   if (int rc = check_idx(idx, "pann_batch_search")) return rc;
   if (!qp || !out) { set_error("pann_batch_search: null params/out"); return PANN_ERR_BAD_ARG; }
@@ -632,7 +635,7 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
                                  uint32_t nstarts, const pann_query_params* qp,
                                  const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
                                  uint64_t sq_stride, uint32_t* d_pruned, const PointFilter* points = nullptr,
-                                 uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr) {
+                                 uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr, const SteerReq* steer = nullptr) {
   if (int rc = search_common_checks(idx, nq, qp, d_out)) return rc;
   if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, d_out)) return rc; }
   if (filter) { if (int rc = refuse_4bit(idx, "pann_batch_search_filtered_dev")) return rc; }
@@ -647,6 +650,7 @@ static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const u
   a.out = *d_out;
   a.filter = filter; a.sketch_queries = (const uint8_t*)d_sketch_queries; a.sq_stride = sq_stride; a.pruned_cmps = d_pruned;
   if (points) { points->apply(a); a.result_count = d_result_count; a.allowed_cmps = d_allowed_cmps; }
+  if (steer) { a.steer = 1; a.fill = steer->fill; a.steer_out = steer->out; }
   if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
   return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, (hipStream_t)stream);
 }
@@ -684,6 +688,30 @@ int pann_batch_search_labeled_dev(pann_index* idx, const void* d_queries, const 
   if (int rc = filter_checks(idx, "pann_batch_search_labeled_dev", F, nq)) return rc;
   return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
                                d_out_result_count, d_out_allowed_cmps);
+}
+
+int pann_batch_search_steered_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                  uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
+                                  const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
+                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, uint32_t fill, uint32_t* d_out_steer,
+                                  void* stream) {
+  const PointFilter F = PointFilter::bitmap(d_allow, allow_stride_words, nq, true);
+  const SteerReq S{fill, d_out_steer};
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
+                               d_out_result_count, d_out_allowed_cmps, &S);
+}
+
+int pann_batch_search_steered_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                          uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts,
+                                          const pann_query_params* qp, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                                          const pann_search_out* d_out, uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps,
+                                          uint32_t fill, uint32_t* d_out_steer, void* stream) {
+  if (int rc = check_idx(idx, "pann_batch_search_steered_labeled_dev")) return rc;
+  const PointFilter F = label_filter(idx, kind, d_preds, npreds, true);
+  if (int rc = filter_checks(idx, "pann_batch_search_steered_labeled_dev", F, nq)) return rc;
+  const SteerReq S{fill, d_out_steer};
+  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
+                               d_out_result_count, d_out_allowed_cmps, &S);
 }
 
 }  // extern "C"
@@ -813,7 +841,8 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int per_query,
                              const pann_query_params* qp, const pann_search_out* out, int filter = 0,
                              const void* sketch_queries = nullptr, uint64_t sq_stride = 0, uint32_t* out_pruned = nullptr,
-                             const PointFilter* points = nullptr, uint32_t* result_count = nullptr, uint32_t* allowed_cmps = nullptr) {
+                             const PointFilter* points = nullptr, uint32_t* result_count = nullptr, uint32_t* allowed_cmps = nullptr,
+                             const SteerReq* steer = nullptr) {
   if (int rc = search_common_checks(idx, nq, qp, out)) return rc;
   if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, out)) return rc; }
   uint32_t sk_row = 0;
@@ -853,6 +882,7 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   const int o_vids = t.out.add(out->visited_ids, nq * vc * 4), o_vdists = t.out.add(out->visited_dists, nq * vc * 4);
   const int o_pruned = t.out.add(filter ? out_pruned : nullptr, nq * 4);
   const int o_rcnt = t.out.add(points ? result_count : nullptr, nq * 4), o_acmps = t.out.add(points ? allowed_cmps : nullptr, nq * 4);
+  const int o_steer = t.out.add(steer ? steer->out : nullptr, nq * 8);
   if (int rc = t.begin()) return rc;
   const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
   const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
@@ -884,6 +914,7 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
         d_filter.slice(q0, cnt).apply(a);
         a.result_count = t.dout<uint32_t>(o_rcnt, q0); a.allowed_cmps = t.dout<uint32_t>(o_acmps, q0);
       }
+      if (steer) { a.steer = 1; a.fill = steer->fill; a.steer_out = t.dout<uint32_t>(o_steer, q0 * 2); }
       if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
       *d_word = (const uint32_t*)((uint8_t*)idx->ws.buf + 64);
       return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st);
@@ -927,6 +958,28 @@ int pann_batch_search_labeled(pann_index* idx, const void* queries, const uint32
   if (int rc = filter_checks(idx, "pann_batch_search_labeled", F, nq)) return rc;
   return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
                            out_allowed_cmps);
+}
+
+int pann_batch_search_steered(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                              const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
+                              uint32_t* out_result_count, uint32_t* out_allowed_cmps, uint32_t fill, uint32_t* out_steer) {
+  const PointFilter F = PointFilter::bitmap(allow, allow_stride_words, nq, false);
+  const SteerReq S{fill, out_steer};
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
+                           out_allowed_cmps, &S);
+}
+
+int pann_batch_search_steered_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                                      uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
+                                      int kind, const pann_label_pred* preds, uint64_t npreds, const pann_search_out* out,
+                                      uint32_t* out_result_count, uint32_t* out_allowed_cmps, uint32_t fill, uint32_t* out_steer) {
+  if (int rc = check_idx(idx, "pann_batch_search_steered_labeled")) return rc;
+  const PointFilter F = label_filter(idx, kind, preds, npreds, false);
+  if (int rc = filter_checks(idx, "pann_batch_search_steered_labeled", F, nq)) return rc;
+  const SteerReq S{fill, out_steer};
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
+                           out_allowed_cmps, &S);
 }
 
 int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,

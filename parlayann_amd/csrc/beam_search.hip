@@ -113,10 +113,12 @@ struct BSParams {
   unsigned long long* stamps;   // diagnostic build: [nq][8] cycle sums
   // second level (FILTER variants of the generic kernel only): bit sketches, see sketch.hip
   const uint8_t* sketch; uint32_t sk_stride;      // [n] rows of sk_stride bytes (a multiple of 16, zero padded)
-  uint32_t sk_kind, sk_as_written, sk_nblk;       // PANN_SKETCH_*; Hamming loop as written; 64-bit blocks per sketch
+  union { uint32_t sk_kind; uint32_t fill; };     // PANN_SKETCH_* | STEER (no sketch there): the two-hop pass stops at `fill` entries of pruned (1..deg_eff)
+  uint32_t sk_as_written, sk_nblk;                // Hamming loop as written; 64-bit blocks per sketch
   const uint8_t* sketch_queries; uint64_t sq_stride; uint32_t sk_row_bytes;   // external queries: nq host-layout rows
-  uint32_t sk_lds_off;                            // byte offset of the query sketch in LDS
-  uint32_t* pruned_cmps;                          // [nq] optional: starts + neighbours that passed the hash filter
+  union { uint32_t sk_lds_off; uint32_t br_off; };        // byte offset of the query sketch in LDS | STEER: of the bridge list
+  union { uint32_t* pruned_cmps; uint32_t* steer_out; };  // [nq] optional: starts + neighbours that passed the hash filter | STEER: [nq][2]
+                                                  // optional: bridge rows expanded, entries appended by the two-hop pass
   // masked search (MASKED variants only): allow bitmap, see DESIGN.md "Masked search"
   const uint32_t* allow; uint64_t allow_stride;   // point i is allowed iff bit i & 31 of word i >> 5; query q reads row q (stride in words, 0: shared)
   uint32_t* result_count; uint32_t* allowed_cmps; // [nq] optional: entries of the result list; full distances of allowed points
@@ -124,6 +126,9 @@ struct BSParams {
   // ... by label predicates (MASK_LABELS variants only), see DESIGN.md "Label predicates"
   const uint32_t* labels;                         // [n] one word per point
   const pann_label_pred* preds; uint32_t pred_stride, pred_kind;   // query q reads preds[q * pred_stride] (0: shared); PANN_PRED_*
+  // The steered masked search (STEER variants, DESIGN.md "Steered masked search") keeps its three parameters in the storage of sketch
+  // fields (the unions above): it has no sketch form, and the kernel argument block of every other instantiation stays byte for byte
+  // what it was.
 };
 
 template <bool HASH_LDS>
@@ -358,7 +363,11 @@ __device__ __forceinline__ uint32_t gather_distances_split(const BSParams& P, co
 // compared again (the hash filter is lossy) and would enter is always still there to be recognised.
 // The keys live in LDS (L[lane], touched by their own lane only) and are in registers only while a key is being inserted: the
 // beam-64 kernel has no VGPRs to spare while the rows of a gather are in flight.
+// (The masked helpers below carry a trailing template flag S that changes nothing in them: the STEER kernels instantiate their own
+// copies, S = true.  hipcc's code for a kernel depends on which other kernels share its inlined helpers -- with shared copies 41 MASKED
+// instantiations of the generic kernel came out with one or two more VGPRs; DESIGN.md "Steered masked search".)
 struct MaskedList { uint64_t* L; uint64_t thr; uint32_t cmps; };
+template <bool S = false>
 __device__ __forceinline__ void masked_offer(MaskedList& R, uint64_t key, bool allowed, uint32_t thr_lane, int lane) {
   R.cmps += __popcll(__ballot(allowed));
   uint64_t bm = __ballot(allowed && key < R.thr);
@@ -383,7 +392,7 @@ __device__ __forceinline__ void masked_offer(MaskedList& R, uint64_t key, bool a
 // query's predicate on it; kind, pa and pb are wave-uniform and are forced into scalar registers once per query, so the label
 // form holds no vector register the bitmap form does not.  Either way ONE 4-byte load per compared point, issued at the same place.
 struct MaskSrc { const uint32_t* W; uint32_t kind, pa, pb; };
-template <int MODE>
+template <int MODE, bool S = false>
 __device__ __forceinline__ MaskSrc mask_src(const BSParams& P, uint32_t qi) {
   if constexpr (MODE == MASK_LABELS) {
     const pann_label_pred* pp = P.preds + (size_t)qi * P.pred_stride;
@@ -393,18 +402,19 @@ __device__ __forceinline__ MaskSrc mask_src(const BSParams& P, uint32_t qi) {
     return MaskSrc{P.allow + (size_t)qi * P.allow_stride, 0u, 0u, 0u};
   }
 }
-template <int MODE>
+template <int MODE, bool S = false>
 __device__ __forceinline__ uint32_t mask_word(const MaskSrc& M, uint32_t a) {
   if constexpr (MODE == MASK_LABELS) return M.W[a];
   else return M.W[a >> 5];
 }
-template <int MODE>
+template <int MODE, bool S = false>
 __device__ __forceinline__ bool mask_verdict(const MaskSrc& M, uint32_t aword, uint32_t note) {
   if constexpr (MODE == MASK_LABELS) return label_pred(M.kind, M.pa, M.pb, aword);
   else return ((aword >> (note & 31u)) & 1u) != 0u;
 }
 
 // What the lane that owns a filter survivor keeps across the gather: position in Pl and bit number of its id (0: owns none).
+template <bool S = false>
 __device__ __forceinline__ uint32_t masked_note(bool mine, uint32_t mypos, uint32_t a) {
   return mine ? (0x80000000u | (mypos << 5) | (a & 31u)) : 0u;
 }
@@ -415,7 +425,7 @@ __device__ __forceinline__ uint32_t masked_note(bool mine, uint32_t mypos, uint3
 // label against the query's predicate): the word `aword` was requested before the row loads of the gather and is first used here,
 // after all of them, so it adds no dependent round trip, and the callback holds nothing but a ballot and LDS stores.  One offer of
 // up to 64 keys per call.
-template <int DT, int METRIC, int LPC, bool NCH1, int U, int MODE>
+template <int DT, int METRIC, int LPC, bool NCH1, int U, int MODE, bool S = false>
 __device__ __forceinline__ uint32_t gather_distances_masked(const BSParams& P, const QReg<DT>& qreg, const uint4* qlds,
                                                             const uint32_t* Pl, uint32_t m, uint32_t cutoff_ord, uint64_t* C,
                                                             uint32_t c, int lane, uint32_t note, uint32_t aword, const MaskSrc& M,
@@ -435,7 +445,31 @@ __device__ __forceinline__ uint32_t gather_distances_masked(const BSParams& P, c
   PANN_WSYNC();
   const bool mine = (note >> 31) != 0u;
   const uint64_t key = mine ? MK[(note >> 5) & 63u] : KEY_INF;
-  masked_offer(R, key, mine && mask_verdict<MODE>(M, aword, note), thr_lane, lane);
+  masked_offer<S>(R, key, mine && mask_verdict<MODE, S>(M, aword, note), thr_lane, lane);
+  return c;
+}
+
+// The same for the STEER variants, whose gathers hold allowed points only: the m ids of Pl were chosen by their verdict, so every
+// key is offered, by the lane of its index in Pl.  masked_offer does the duplicate handling as for any other offer.
+template <int DT, int METRIC, int LPC, bool NCH1, int U>
+__device__ __forceinline__ uint32_t gather_distances_steered(const BSParams& P, const QReg<DT>& qreg, const uint4* qlds,
+                                                             const uint32_t* Pl, uint32_t m, uint32_t cutoff_ord, uint64_t* C,
+                                                             uint32_t c, int lane, MaskedList& R, uint32_t thr_lane) {
+  const PointsView PV{P.points, P.pstride, P.nch, P.exact};
+  uint64_t* MK = R.L + PANN_WAVE;
+  gather_tile<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, lane,
+    [&](bool has, uint32_t ci, uint32_t id, float dist, uint64_t before) {
+      const uint32_t ord = f2ord(dist);
+      const uint64_t key = ((uint64_t)ord << 32) | id;
+      const bool pass = has && (ord < cutoff_ord);
+      const uint64_t pm = __ballot(pass);
+      if (pass) C[c + (uint32_t)__popcll(pm & before)] = key;
+      c += __popcll(pm);
+      if (has) MK[ci] = key;
+    });
+  PANN_WSYNC();
+  const bool mine = (uint32_t)lane < m;
+  masked_offer<true>(R, mine ? MK[lane] : KEY_INF, mine, thr_lane, lane);
   return c;
 }
 
@@ -507,9 +541,15 @@ __device__ __forceinline__ void write_counters(const BSParams& P, uint32_t qi, u
 // reads its own candidate's sketch, and the ballot compaction that follows hands the gather a dense list in row order.
 // MASKED (MASK_BITMAP / MASK_LABELS): the traversal of the plain search; out->ids/dists hold the result list over the allowed
 // points (see MaskedList, MaskSrc).
-template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = false, int MASKED = MASK_NONE>
+// STEER (masked forms only; DESIGN.md "Steered masked search"): `pruned` of a visit holds allowed points only -- the allowed
+// neighbours that passed the hash filter, then the allowed neighbours of the disallowed ones (the bridges, BR in LDS) until `fill`
+// entries are there.  The verdict is taken BEFORE the gather, survivors wait in the whole of NF (128 ids) and are gathered 64 at a
+// time or when the visit ends; bridge rows are loaded four row chunks at a time, their mask words requested together, and only then
+// does the filter replay run, chunk by chunk in order, on the allowed lanes: a row loaded past the `fill` stop is dropped unseen.
+template <int DT, int METRIC, int LPC, bool NCH1, bool HASH_LDS, bool FILTER = false, int MASKED = MASK_NONE, bool STEER = false>
 __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(BSParams P) {
   static_assert(!(FILTER && MASKED), "the masked search has no sketch-filtered form");
+  static_assert(!STEER || MASKED != MASK_NONE, "steering needs a verdict: masked forms only");
   const int lane = threadIdx.x;
   extern __shared__ __align__(16) uint8_t smem[];   // carved as generic_lds (search_plan.h) lays it out, by typed pointer steps
   // ---- LDS carve (all regions 16 B aligned): 6.4 KB at beam 64 / degree 64 -> 24 queries per CU ----
@@ -560,12 +600,13 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
     [[maybe_unused]] uint32_t pcmps = P.nstarts;   // FILTER: the reference's local dist_cmps (:83,137); dcmps is full_dist_cmps
     [[maybe_unused]] float fsum = 0.0f, fthr = 0.0f;   // FILTER: filter_threshold_sum / filter_threshold (:98-100)
     [[maybe_unused]] uint32_t fcount = 0;
+    [[maybe_unused]] uint32_t sbr = 0, shop = 0;       // STEER: bridge rows expanded; entries the two-hop pass appended
     PANN_STAMP_BEGIN();
     uint64_t* DL = P.dropped + (size_t)qi * P.dcap;
     [[maybe_unused]] MaskedList R{reinterpret_cast<uint64_t*>(smem + P.rl_off), P.out.out_k ? KEY_INF : 0ull, 0u};
     [[maybe_unused]] const uint32_t thr_lane = P.out.out_k ? P.out.out_k - 1u : 0u;
     [[maybe_unused]] MaskSrc M{};
-    if constexpr (MASKED) { M = mask_src<MASKED>(P, qi); R.L[lane] = KEY_INF; }
+    if constexpr (MASKED) { M = mask_src<MASKED, STEER>(P, qi); R.L[lane] = KEY_INF; }
 
     // ---- start points (:66-70): distance for each, filter insert in order, then "merge" into
     // the empty frontier (which sorts them) ----
@@ -575,14 +616,14 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
       const uint32_t a = act ? P.starts[(size_t)qi * P.starts_stride + i] : 0u;
       (void)filter_update<HASH_LDS>(H, hmask, act, a, lane, reinterpret_cast<uint8_t*>(Hl));
       [[maybe_unused]] uint32_t aword = 0u;
-      if constexpr (MASKED) if (act) aword = mask_word<MASKED>(M, a);
+      if constexpr (MASKED) if (act) aword = mask_word<MASKED, STEER>(M, a);
       if (act) PANN_PL[lane] = a;
       PANN_WSYNC();
       const uint32_t m = min(P.nstarts - s0, (uint32_t)PANN_WAVE);
       // every start enters the frontier: cutoff above any finite distance
       if constexpr (MASKED)
-        c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4, MASKED>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane,
-                                                              masked_note(act, (uint32_t)lane, a), aword, M, R, thr_lane);
+        c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4, MASKED, STEER>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane,
+                                                              masked_note<STEER>(act, (uint32_t)lane, a), aword, M, R, thr_lane);
       else
       c = gather_distances<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, PANN_PL, m, 0xFFFFFFFFu, C, c, lane);
       PANN_WSYNC();
@@ -627,6 +668,88 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
 
         // ---- adjacency row: lane i <- slot i; degree = number of non-sentinel slots ----
         const uint32_t* row = P.graph + (size_t)cur * P.gstride;
+        if constexpr (STEER) {
+          uint32_t* BR = reinterpret_cast<uint32_t*>(smem + P.br_off);   // [deg_eff] bridges of this visit, in row order
+          uint32_t* PQ = PANN_PL;                  // [128] pruned entries waiting for their gather (NF is idle between merges)
+          uint32_t npend = 0, npr = 0, nbr = 0;    // waiting in PQ; len(pruned) so far; bridges
+          // gather 64 at a time while at least `least` entries wait; what stays moves to the head of PQ
+          auto drain = [&](uint32_t least) {
+            while (npend != 0u && npend >= least) {
+              const uint32_t m = min(npend, (uint32_t)PANN_WAVE), rest = npend - m;      // rest < 64
+              c = gather_distances_steered<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, PQ, m, cutoff_ord, C, c, lane, R, thr_lane);
+              PANN_WSYNC();
+              uint32_t mv = 0u;
+              if ((uint32_t)lane < rest) mv = PQ[PANN_WAVE + lane];
+              PANN_WSYNC();
+              if ((uint32_t)lane < rest) PQ[lane] = mv;
+              PANN_WSYNC();
+              npend = rest;
+            }
+          };
+          // ---- direct pass: filter replay in row order; allowed survivors -> pruned, the others -> bridges ----
+          for (uint32_t i0 = 0; i0 < P.gstride; i0 += PANN_WAVE) {
+            const uint32_t i = i0 + lane;
+            uint32_t a = SENTINEL;
+            if (i < P.gstride) a = row[i];
+            const bool act = (a != SENTINEL) && (i < P.degree_limit);   // min(size, degree_limit) (:130)
+            const uint64_t am = __ballot(act);
+            if (am == 0ull) break;
+            degsum += __popcll(am);
+            const bool seen = filter_update<HASH_LDS>(H, hmask, act, a, lane, reinterpret_cast<uint8_t*>(Hl));
+            const bool keep = act && !seen && ((int64_t)a != self);     // :133
+            uint32_t aword = 0u;
+            if (keep) aword = mask_word<MASKED, true>(M, a);
+            const bool ok = keep && mask_verdict<MASKED, true>(M, aword, a);
+            const uint64_t okm = __ballot(ok), brm = __ballot(keep && !ok);
+            if (ok) PQ[npend + lanes_below(okm, lane)] = a;
+            if (keep && !ok) BR[nbr + lanes_below(brm, lane)] = a;     // nbr <= deg_eff: act holds for the first degree_limit slots only
+            npend += __popcll(okm); npr += __popcll(okm); nbr += __popcll(brm);
+            PANN_WSYNC();
+            drain(PANN_WAVE);
+          }
+          // ---- two-hop pass: unit t = row chunk t % nchunk of bridge t / nchunk; four units per round trip ----
+          const uint32_t nchunk = (P.gstride + PANN_WAVE - 1) / PANN_WAVE, nunits = nbr * nchunk;
+          bool stop = false;
+          for (uint32_t t0 = 0; t0 < nunits && !stop; t0 += 4) {
+            if (t0 % nchunk == 0u && npr >= P.fill) break;             // nothing to speculate on
+            uint32_t rc[4], rw[4];
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+              const uint32_t t = t0 + u;
+              rc[u] = SENTINEL;
+              if (t < nunits) {
+                const uint32_t b = BR[t / nchunk], i = (t % nchunk) * PANN_WAVE + lane;
+                if (i < P.gstride && i < P.degree_limit) rc[u] = P.graph[(size_t)b * P.gstride + i];
+              }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+              rw[u] = 0u;
+              if (rc[u] != SENTINEL) rw[u] = mask_word<MASKED, true>(M, rc[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+              const uint32_t t = t0 + u;
+              if (t >= nunits) break;
+              if (t % nchunk == 0u) {                                  // before touching a bridge: taken whole or not at all
+                if (npr >= P.fill) { stop = true; break; }
+                sbr++;
+              }
+              const bool al = rc[u] != SENTINEL && mask_verdict<MASKED, true>(M, rw[u], rc[u]);   // disallowed: the filter is not touched
+              if (__ballot(al) == 0ull) continue;
+              const bool seen = filter_update<HASH_LDS>(H, hmask, al, rc[u], lane, reinterpret_cast<uint8_t*>(Hl));
+              const bool keep = al && !seen && ((int64_t)rc[u] != self);
+              const uint64_t km = __ballot(keep);
+              if (keep) PQ[npend + lanes_below(km, lane)] = rc[u];
+              const uint32_t m = __popcll(km);
+              npend += m; npr += m; shop += m;
+              PANN_WSYNC();
+              drain(PANN_WAVE);
+            }
+          }
+          drain(1u);
+          dcmps += npr;                                                // :137,155
+        } else
         for (uint32_t i0 = 0; i0 < P.gstride; i0 += PANN_WAVE) {
           const uint32_t i = i0 + lane;
           uint32_t a = SENTINEL;
@@ -794,6 +917,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES) beam_search_kernel(B
     if (lane == 0) {
       write_counters(P, qi, f, nvis, dcmps, degsum);
       if constexpr (FILTER) if (P.pruned_cmps) P.pruned_cmps[qi] = pcmps;
+      if constexpr (STEER) if (P.steer_out) { P.steer_out[(size_t)qi * 2] = sbr; P.steer_out[(size_t)qi * 2 + 1] = shop; }
     }
     PANN_WSYNC();
     if constexpr (HASH_LDS) break;
@@ -1432,7 +1556,7 @@ void choose_point_layout(uint32_t dbytes, uint32_t* lpc, uint32_t* nch) { choose
 static SearchPlan plan_of(const DeviceIndex& ix, const SearchArgs& a) {
   const PlanIndex pi{ix.dtype, ix.metric, ix.lpc, ix.nch, ix.max_deg, ix.gstride, ix.n, ix.sk_stride, ix.b64_seen,
                      ix.codes_valid && ix.gcode && ix.rank16};
-  const PlanCall pc{a.nq, a.nstarts, a.k, a.beam, a.degree_limit, a.cut, a.dcap, a.filter != 0, a.masked};
+  const PlanCall pc{a.nq, a.nstarts, a.k, a.beam, a.degree_limit, a.cut, a.dcap, a.filter != 0, a.masked, a.steer != 0};
   return make_plan(pi, pc, plan_switches());
 }
 size_t search_workspace_bytes(const DeviceIndex& ix, const SearchArgs& a) { return (size_t)plan_of(ix, a).ws_bytes; }
@@ -1451,11 +1575,13 @@ static SearchKernel plan_kernel(const SearchPlan& p) {
       if constexpr (masked_b64_fits(DT, LPC, NCH1)) return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MASK_LABELS>;
       break;
     case KERNEL_GENERIC * 8 + MODE_LABELS:
+      if (p.steer) return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MASK_LABELS, true> : beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MASK_LABELS, true>;
       return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MASK_LABELS> : beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MASK_LABELS>;
     case KERNEL_B64 * 8 + MODE_BITMAP:
       if constexpr (masked_b64_fits(DT, LPC, NCH1)) return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, MASK_BITMAP>;
       break;
     case KERNEL_GENERIC * 8 + MODE_BITMAP:
+      if (p.steer) return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MASK_BITMAP, true> : beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MASK_BITMAP, true>;
       return lds ? beam_search_kernel<DT, METRIC, LPC, NCH1, true, false, MASK_BITMAP> : beam_search_kernel<DT, METRIC, LPC, NCH1, false, false, MASK_BITMAP>;
     case KERNEL_B64 * 8 + MODE_PLAIN_V: return beam_search_b64_kernel<DT, METRIC, LPC, NCH1, B64_SEEN>;
     case KERNEL_B64 * 8 + MODE_PLAIN: return beam_search_b64_kernel<DT, METRIC, LPC, NCH1>;
@@ -1507,6 +1633,7 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   if (a.masked == MASK_LABELS && (!a.labels || !a.preds || a.pred_stride > 1 || !pred_kind_known(a.pred_kind))) {
     set_error("pann_batch_search_labeled: labels, predicates of a known kind and a predicate stride of 0 or 1 are needed"); return PANN_ERR_BAD_ARG;
   }
+  if (a.steer && (!a.masked || a.filter)) { set_error("pann_batch_search_steered: steering goes with a bitmap or label predicates, and not with the sketch filter"); return PANN_ERR_UNSUPPORTED; }
   const SearchPlan p = plan_of(ix, a);
   if (p.lds_bytes > 160 * 1024) { set_error("pann_batch_search: beam/degree too large for LDS state"); return PANN_ERR_UNSUPPORTED; }
   if (p.ws_bytes > ws_bytes) { set_error("pann_batch_search: workspace too small"); return PANN_ERR_BAD_ARG; }
@@ -1539,6 +1666,10 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
   P.labels = lab ? a.labels : nullptr; P.preds = lab ? a.preds : nullptr;
   P.pred_stride = lab ? a.pred_stride : 0u; P.pred_kind = lab ? (uint32_t)a.pred_kind : 0u;
   P.result_count = a.masked ? a.result_count : nullptr; P.allowed_cmps = a.masked ? a.allowed_cmps : nullptr;
+  if (p.steer) {      // in the storage of sk_kind, sk_lds_off and pruned_cmps: a steered launch has no sketch
+    P.fill = a.fill == 0 || a.fill > p.deg_eff ? p.deg_eff : a.fill;      // 0: deg_eff; clamped
+    P.br_off = p.br_off; P.steer_out = a.steer_out;
+  }
 #ifdef PANN_STAMPS
   static unsigned long long* d_stamps = nullptr; static size_t stamps_cap = 0;
   if (stamps_cap < a.nq) { if (d_stamps) (void)hipFree(d_stamps); (void)hipMalloc((void**)&d_stamps, a.nq * 64); stamps_cap = a.nq; }

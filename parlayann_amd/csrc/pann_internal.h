@@ -110,6 +110,9 @@ struct SearchArgs {  // one batched beam search, everything device resident
   const pann_label_pred* preds = nullptr;    // query q reads preds[q * pred_stride]
   uint32_t pred_stride = 0;                  // 0: one predicate for the batch, 1: one per query
   int pred_kind = 0;                         // PANN_PRED_*
+  // steered form of a masked search (DESIGN.md "Steered masked search"): pruned = allowed neighbours + allowed neighbours of bridges
+  int steer = 0; uint32_t fill = 0;          // fill: the two-hop pass stops at this many entries; 0 or above deg_eff: deg_eff
+  uint32_t* steer_out = nullptr;             // nq x 2, optional: bridge_rows, hop2_cmps
 };
 
 // Which points a query may return: what every masked / labeled / grouped entry point builds once from its C arguments and

@@ -65,6 +65,14 @@ constexpr RegLds reg_lds(uint32_t nf, uint32_t ccap, uint32_t qbytes, uint32_t t
   L.rl = align16(end); L.total = masked ? L.rl + RESULT_LIST_BYTES : end; L.Pl = L.T = L.S;
   return L;
 }
+// steered generic kernel (masked modes only; DESIGN.md "Steered masked search"): the masked layout, then BR, the bridge list of one
+// visit: deg_eff ids behind the result list.  Between merges the whole of NF (>= 512 B) holds the pending survivors, 128 ids.
+struct SteerLds { GenericLds g; uint32_t br, total; };
+constexpr SteerLds steered_lds(uint32_t bcap, uint32_t ccap, uint32_t qbytes, uint32_t bits, bool table_in_lds, uint32_t deg_eff) {
+  SteerLds L{generic_lds(bcap, ccap, qbytes, bits, table_in_lds, true, 0), 0, 0};
+  L.br = L.g.total; L.total = L.br + align16(deg_eff * 4);
+  return L;
+}
 constexpr RegLds b64_lds(uint32_t ccap, uint32_t qbytes, uint32_t bits, uint32_t seen_n, bool masked) { return reg_lds(64, ccap, qbytes, 4u << bits, seen_n, masked); }
 constexpr RegLds b128_lds(uint32_t ccap, uint32_t qbytes, uint32_t bits, int table, uint32_t hsplit, uint32_t p24) {
   static_assert(REPLAY_BYTES <= 128 * 8, "T fits S");
@@ -79,6 +87,7 @@ struct SearchPlan {
   uint32_t bits, bcap, ccap, deg_eff;      // log2 of the filter size (:52); LDS capacities of frontier and candidates; min(degree_limit, max_deg)
   uint32_t dcap, slots, hsplit, p24, seen_n;      // dropped-list entries per query; blocks of a persistent launch; HBM_SPLIT: LDS share, 24-bit planes; entries of V
   uint32_t lds_bytes, sk_lds_off, rl_off;      // of the kernel's layout: total, and the tail of the sketch / masked modes
+  uint32_t br_off = 0; bool steer = false;     // steered masked search: the bridge list's offset (always KERNEL_GENERIC)
   uint64_t ws_bytes;             // 256 (counter, status) | dropped_bytes | the tables of a persistent launch
   bool table_in_lds() const { return table == TABLE_LDS || table == TABLE_CODES; }
   bool persistent() const { return !table_in_lds(); }      // every kernel whose table is in HBM is persistent, and no other
@@ -86,7 +95,8 @@ struct SearchPlan {
   uint64_t dropped_bytes(uint64_t nq) const { return nq * dcap * 8; }
 };
 struct PlanIndex { int dtype, metric; uint32_t lpc, nch, max_deg, gstride; uint64_t n; uint32_t sk_stride, b64_seen; bool codes; };
-struct PlanCall { uint64_t nq; uint32_t nstarts; int64_t k, beam, degree_limit; double cut; uint32_t dcap; bool filter; int masked; };
+struct PlanCall { uint64_t nq; uint32_t nstarts; int64_t k, beam, degree_limit; double cut; uint32_t dcap; bool filter; int masked;
+                  bool steer = false; };      // steer: the steered form of a masked call (no sketch filter)
 // Diagnostic A/B switches of `make alt` builds (beam_search.hip reads them from the environment); the shipped library runs on these defaults
 struct PlanSwitches {
   bool b128_lds = false, b128_no24 = false;      // PANN_B128_LDS: never the HBM table; PANN_B128_NO24: no 24-bit planes
@@ -112,6 +122,18 @@ inline SearchPlan make_plan(const PlanIndex& ix, const PlanCall& a, const PlanSw
   p.ccap = (cmax + 63) / 64 * 64;
   p.dcap = std::max<uint32_t>(a.dcap, 64); p.slots = 256 * 8;
   p.mode = a.filter ? MODE_SKETCH : a.masked == MASK_BITMAP ? MODE_BITMAP : a.masked == MASK_LABELS ? MODE_LABELS : MODE_PLAIN;
+  if (a.steer) {
+    // steered: |pruned| <= fill - 1 + deg_eff <= 2 deg_eff - 1 per visit, so |C| <= (beam/8 - 1) + 2 deg_eff - 1 at merge time; the
+    // table's place is decided with the steered layout's bytes
+    p.steer = true; p.kernel = KERNEL_GENERIC;
+    p.ccap = (std::max<uint32_t>(beam / 8 + 2 * p.deg_eff, a.nstarts) + 63) / 64 * 64;
+    const bool sfits = p.bits <= 12 && steered_lds(p.bcap, p.ccap, qb, p.bits, true, p.deg_eff).total <= 64 * 1024;
+    p.table = sfits ? TABLE_LDS : TABLE_HBM;
+    const SteerLds L = steered_lds(p.bcap, p.ccap, qb, p.bits, sfits, p.deg_eff);
+    p.lds_bytes = L.total; p.rl_off = L.g.tail; p.br_off = L.br;
+    p.ws_bytes = 256 + p.dropped_bytes(a.nq) + (p.persistent() ? (std::min<uint64_t>(a.nq, p.slots) << p.bits) * 4 : 0);
+    return p;
+  }
   // the table goes to LDS up to 16 KB, if the generic kernel's state with it stays within 64 KB
   const bool fits = p.bits <= 12 && generic_lds(p.bcap, p.ccap, qb, p.bits, true, false, 0).total <= 64 * 1024;
   // the register-frontier kernels: no sketch form; masked forms of b64 only, and not for every layout

@@ -106,9 +106,15 @@ class GraphIndex:
         return dict(k=knn, beam=beam_width, cut=1.35, limit=visit_limit,
                     degree_limit=min(self.index.max_degree, 3 * visit_limit))
 
-    def _search(self, queries, knn, beam_width, quant, visit_limit, allow=None, where=None):   # search_dispatch :120-190
+    def _search(self, queries, knn, beam_width, quant, visit_limit, allow=None, where=None, steer=None):   # search_dispatch :120-190
         queries = np.ascontiguousarray(queries, dtype=self.T)
         qp = self._qp(knn, beam_width, visit_limit)
+        if steer is not None:      # the steered walk (DESIGN.md "Steered masked search"): plain masked / labeled searches only
+            if allow is None and where is None:
+                raise ValueError("steer= goes with allow= or where=")
+            if quant and self.use_quantization:
+                raise ValueError("steer= goes with quant=False: the quantised and rerank paths have no steered form")
+            qp = dict(qp, steer=steer)
         if where is not None:      # label predicates: the masked search below with the labels standing for the bitmap
             if quant and self.use_quantization:
                 raise ValueError("where= goes with quant=False here (batch_search_masked(..., quant=True, where=) is the fused form)")
@@ -204,19 +210,21 @@ class GraphIndex:
         return ids, dists
 
     def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None,
-                     exact_grouped=False):
+                     exact_grouped=False, steer=None):
         """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned.
         where = (kind, preds): the same by a label predicate (DeviceIndex.batch_search_labeled); not together with allow.
-        exact_below, exact_grouped (with allow or where): as batch_search_masked"""
+        exact_below, exact_grouped (with allow or where): as batch_search_masked
+        steer (with allow or where, quant=False): the steered walk, DeviceIndex.batch_search_masked(steer=); None changes nothing"""
         if where is not None:
             if allow is not None:
                 raise ValueError("where and allow exclude each other")
             return self._exact_or_walk_labeled(queries, knn, where, exact_below,
-                                               lambda q, w: self._search(q, knn, beam_width, quant, visit_limit, where=w), exact_grouped)
+                                               lambda q, w: self._search(q, knn, beam_width, quant, visit_limit, where=w, steer=steer),
+                                               exact_grouped)
         if allow is None:
-            return self._search(queries, knn, beam_width, quant, visit_limit)
+            return self._search(queries, knn, beam_width, quant, visit_limit, steer=steer)
         return self._exact_or_walk(queries, knn, allow, exact_below,
-                                   lambda q, a: self._search(q, knn, beam_width, quant, visit_limit, a), exact_grouped)
+                                   lambda q, a: self._search(q, knn, beam_width, quant, visit_limit, a, steer=steer), exact_grouped)
 
     def _search_masked(self, queries, knn, beam_width, allow, quant, visit_limit, where=None):
         """Masked searches (this project's own, DESIGN.md "Masked search").  Rows may be short (padding 0xFFFFFFFF / +inf):

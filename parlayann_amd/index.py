@@ -529,29 +529,33 @@ class DeviceIndex:
                                   filtered=True, sketch_queries=sketch_queries)
 
     def batch_search_masked(self, queries=None, allow=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
-                            query_ids=None, out_k=None, visited_cap=0, want_dists=True):
+                            query_ids=None, out_k=None, visited_cap=0, want_dists=True, steer=None):
         """pann_batch_search_masked: the traversal of batch_search, results restricted to the points `allow` allows
         (DESIGN.md "Masked search").  allow: packed uint32 (W,) or (nq, W), W = ceil(n / 32) (allow_bitmap), or boolean (n,)
         or (nq, n); one row serves the whole batch.  ids/dists: per query the best allowed points among ALL points the search
         computed a full distance for, padded with 0xFFFFFFFF / +inf; the other fields are batch_search's.  Adds
-        "result_count" (entries per row) and "allowed_cmps" (full distances of allowed points)."""
+        "result_count" (entries per row) and "allowed_cmps" (full distances of allowed points).
+        steer (None: the call above, untouched): an integer makes it pann_batch_search_steered, the walk that spends its
+        distances on allowed points only -- disallowed neighbours are bridges to their own allowed neighbours (DESIGN.md
+        "Steered masked search").  The integer is `fill`, the number of waiting points at which a visit stops expanding
+        bridges: 1 .. min(degree_limit, max_degree), 0 means that bound.  Adds "bridge_rows" and "hop2_cmps" per query."""
         if allow is not None:
             allow = pack_allow(allow, self.n)
         return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                                  masked=True, allow=allow)
+                                  masked=True, allow=allow, steer=steer)
 
     def batch_search_labeled(self, queries=None, where=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
-                             query_ids=None, out_k=None, visited_cap=0, want_dists=True):
+                             query_ids=None, out_k=None, visited_cap=0, want_dists=True, steer=None):
         """pann_batch_search_labeled: batch_search_masked with a label predicate in place of the bitmap (DESIGN.md "Label
         predicates").  where = (kind, preds): kind "any" | "match" | "range"; preds (a, b) for the whole batch or an (nq, 2)
         uint32 array, one predicate per query.  Returns, field for field, what batch_search_masked returns for
-        allow = label_allow(self.labels(), kind, preds)."""
+        allow = label_allow(self.labels(), kind, preds).  steer: as batch_search_masked (pann_batch_search_steered_labeled)."""
         nq = len(queries) if queries is not None else len(query_ids)
         return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                                  masked=True, where=self._where(where, nq))
+                                  masked=True, where=self._where(where, nq), steer=steer)
 
     def _batch_search(self, queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                      filtered=False, sketch_queries=None, masked=False, allow=None, where=None):
+                      filtered=False, sketch_queries=None, masked=False, allow=None, where=None, steer=None):
         nq = len(queries) if queries is not None else len(query_ids)
         qp = QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
                          degree_limit=self.max_degree if degree_limit is None else degree_limit,
@@ -600,10 +604,22 @@ class DeviceIndex:
         if masked:
             if per_query:
                 raise ValueError("masked searches take shared starts")
+            if steer is not None:
+                fill = int(steer)
+                if fill < 0 or fill > 0xFFFFFFFF:
+                    raise ValueError("steer is the fill count: 0 (the degree bound) or a positive integer")
+                counters = np.empty((nq, 2), dtype=np.uint32)
             if where is not None:
                 kind, preds = where
                 res["result_count"] = np.empty(nq, dtype=np.uint32)
                 res["allowed_cmps"] = np.empty(nq, dtype=np.uint32)
+                if steer is not None:
+                    check(self._lib.pann_batch_search_steered_labeled(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts),
+                                                                      starts.shape[-1], C.byref(qp), kind, _ptr(preds), len(preds),
+                                                                      C.byref(out), _ptr(res["result_count"]), _ptr(res["allowed_cmps"]),
+                                                                      fill, _ptr(counters)))
+                    res["bridge_rows"], res["hop2_cmps"] = counters[:, 0].copy(), counters[:, 1].copy()
+                    return res
                 check(self._lib.pann_batch_search_labeled(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1],
                                                           C.byref(qp), kind, _ptr(preds), len(preds), C.byref(out),
                                                           _ptr(res["result_count"]), _ptr(res["allowed_cmps"])))
@@ -613,6 +629,12 @@ class DeviceIndex:
             astride = allow.shape[1] if allow is not None and allow.ndim == 2 else 0
             res["result_count"] = np.empty(nq, dtype=np.uint32)
             res["allowed_cmps"] = np.empty(nq, dtype=np.uint32)
+            if steer is not None:
+                check(self._lib.pann_batch_search_steered(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1],
+                                                          C.byref(qp), _ptr(allow), astride, C.byref(out), _ptr(res["result_count"]),
+                                                          _ptr(res["allowed_cmps"]), fill, _ptr(counters)))
+                res["bridge_rows"], res["hop2_cmps"] = counters[:, 0].copy(), counters[:, 1].copy()
+                return res
             check(self._lib.pann_batch_search_masked(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1], C.byref(qp),
                                                      _ptr(allow), astride, C.byref(out), _ptr(res["result_count"]),
                                                      _ptr(res["allowed_cmps"])))
