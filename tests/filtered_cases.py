@@ -77,6 +77,16 @@ def random_graph(n, maxdeg, seed):
     return g
 
 
+def random_rows(dtype, n, d, seed):
+    """seeded rows of the small pin cases in the test_*_ref_cpu.py files: u8 / i8 over their whole range, standard normal f32"""
+    rng = np.random.default_rng(seed)
+    if dtype == np.uint8:
+        return rng.integers(0, 256, size=(n, d), dtype=np.uint8)
+    if dtype == np.int8:
+        return rng.integers(-127, 128, size=(n, d)).astype(np.int8)
+    return rng.standard_normal((n, d)).astype(np.float32)
+
+
 def float_data(kind, metric, n, d, seed):
     """the float rows the sketch is made from (and, for the f32 cases, the rows that are searched)"""
     rng = np.random.default_rng(seed)

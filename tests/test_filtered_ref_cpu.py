@@ -13,18 +13,12 @@ import numpy as np
 import pytest
 
 import filtered_cases as fc
+from filtered_cases import random_rows as _data
 import filtered_ref
 import oracle_api
 from parlayann_amd import sketch as sk
 
 FIELDS = ("ids", "dists", "frontier_size", "visited_count", "dist_cmps", "degree_sum")
-
-
-def _data(dtype, n, d, seed):
-    rng = np.random.default_rng(seed)
-    if dtype == np.uint8:
-        return rng.integers(0, 256, size=(n, d), dtype=np.uint8)
-    return rng.standard_normal((n, d)).astype(np.float32)
 
 
 PIN_CASES = [

@@ -17,20 +17,12 @@ import pytest
 
 import delete_ref as dr
 import filtered_cases as fc
+from filtered_cases import random_rows as _data
 import masked_cases as mc
 import masked_ref
 from parlayann_amd import datasets
 
 TRAVERSAL = ("frontier_size", "visited_count", "dist_cmps", "degree_sum")
-
-
-def _data(dtype, n, d, seed):
-    rng = np.random.default_rng(seed)
-    if dtype == np.uint8:
-        return rng.integers(0, 256, size=(n, d), dtype=np.uint8)
-    if dtype == np.int8:
-        return rng.integers(-127, 128, size=(n, d)).astype(np.int8)
-    return rng.standard_normal((n, d)).astype(np.float32)
 
 
 PIN = [(dt, m, beam) for dt, m in ((np.uint8, "l2"), (np.int8, "mips"), (np.float32, "l2")) for beam in (8, 64, 200)]

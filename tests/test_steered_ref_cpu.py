@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import filtered_cases as fc
+from filtered_cases import random_rows as _data
 import masked_ref
 import steered_ref
 from parlayann_amd import datasets
@@ -18,15 +19,6 @@ from parlayann_amd import datasets
 FIELDS = ("ids", "dists", "frontier_ids", "frontier_dists", "frontier_size", "visited_count", "dist_cmps", "degree_sum",
           "visited_ids", "visited_dists", "result_count", "allowed_cmps", "from_beyond_cutoff", "from_unmerged", "recompared_in_result")
 N, NQ, DEG = 1200, 8, 16
-
-
-def _data(dtype, n, d, seed):
-    rng = np.random.default_rng(seed)
-    if dtype == np.uint8:
-        return rng.integers(0, 256, size=(n, d), dtype=np.uint8)
-    if dtype == np.int8:
-        return rng.integers(-127, 128, size=(n, d)).astype(np.int8)
-    return rng.standard_normal((n, d)).astype(np.float32)
 
 
 PIN = [(dt, m, beam) for dt, m in ((np.uint8, "l2"), (np.int8, "mips"), (np.float32, "l2")) for beam in (8, 64, 200)]
