@@ -16,7 +16,7 @@ classes python/module.cpp registers (:50-57,150-155), over the C-ABI.
 import numpy as np
 
 from . import io, quantize, sketch
-from .index import DeviceIndex, allow_count, pack_allow
+from .index import DeviceIndex, PointFilter
 from .recall import recall_at_k
 
 
@@ -115,20 +115,16 @@ class GraphIndex:
             if quant and self.use_quantization:
                 raise ValueError("steer= goes with quant=False: the quantised and rerank paths have no steered form")
             qp = dict(qp, steer=steer)
-        if where is not None:      # label predicates: the masked search below with the labels standing for the bitmap
+        if where is not None or allow is not None:
+            # masked search (this project's own, DESIGN.md "Masked search"; where=: "Label predicates"): the plain search's walk
+            # over the full-precision points, results = the best allowed points it compared.  Rows may be short (padding
+            # 0xFFFFFFFF / +inf), so the k-results check of the plain path does not apply.  Not in the quantised or rerank paths.
             if quant and self.use_quantization:
-                raise ValueError("where= goes with quant=False here (batch_search_masked(..., quant=True, where=) is the fused form)")
-            r = self.index.batch_search_labeled(queries, where=where, out_k=knn, **qp)
-            return r["ids"], r["dists"]
-        if allow is not None:
-            # masked search (this project's own, DESIGN.md "Masked search"): the plain search's walk over the full-precision
-            # points, results = the best allowed points it compared.  Rows may be short (padding 0xFFFFFFFF / +inf), so the
-            # k-results check of the plain path does not apply.  Not in the quantised or rerank paths.
-            if quant and self.use_quantization:
-                raise ValueError("allow= goes with quant=False: the quantised and rerank paths have no masked form here "
+                raise ValueError("where= goes with quant=False here (batch_search_masked(..., quant=True, where=) is the fused form)"
+                                 if where is not None else
+                                 "allow= goes with quant=False: the quantised and rerank paths have no masked form here "
                                  "(batch_search_masked(..., quant=True) is the fused masked search)")
-            r = self.index.batch_search_masked(queries, allow=allow, out_k=knn, **qp)
-            return r["ids"], r["dists"]
+            return self._masked_walk(self.index, queries, knn, qp, allow, where)
         if not (quant and self.use_quantization):
             r = self.index.batch_search(queries, out_k=knn, **qp)                # :188
             self._need(r["frontier_size"], knn)
@@ -151,62 +147,41 @@ class GraphIndex:
         if len(frontier_size) and int(frontier_size.min()) < knn:               # beamSearch.h:416-419
             raise RuntimeError(f"Error: beam search returned {int(frontier_size.min())} elements, which is less than k = {knn}")
 
-    def _exact_or_walk(self, queries, knn, allow, exact_below, walk, grouped=False):
-        """The rule of DESIGN.md "Exact masked kNN": a mask with at most exact_below allowed points is answered exactly
-        (DeviceIndex.bruteforce_knn_masked on the full-precision handle), any other by walk(queries, allow) -> (ids, dists).
-        Per-query rows are split by their own counts, each part takes its route, and the rows come back in the given order.
-        grouped: the exact part of per-query rows goes through DeviceIndex.bruteforce_knn_grouped (equal rows share one list)."""
-        if exact_below is None:
-            return walk(queries, allow)
-        queries = np.ascontiguousarray(queries, dtype=self.T)
-        allow = pack_allow(allow, self.index.n)
-        cnt = allow_count(allow, self.index.n)
-        if allow.ndim == 1:
-            if cnt > exact_below:
-                return walk(queries, allow)
-            ids, dists, _ = self.index.bruteforce_knn_masked(queries, knn, allow)
-            return ids, dists
-        if allow.shape[0] != len(queries):
-            raise ValueError("per-query allow rows must be nq x W")
-        exact = cnt <= exact_below
-        ids = np.full((len(queries), knn), 0xFFFFFFFF, np.uint32)
-        dists = np.full((len(queries), knn), np.inf, np.float32)
-        if exact.any():
-            knn_exact = self.index.bruteforce_knn_grouped if grouped else self.index.bruteforce_knn_masked
-            ids[exact], dists[exact], _ = knn_exact(queries[exact], knn, allow=allow[exact])
-        if not exact.all():
-            ids[~exact], dists[~exact] = walk(queries[~exact], allow[~exact])
-        return ids, dists
-
     @staticmethod
-    def _where_rows(where, rows):
-        """the predicates of the queries `rows` selects (a boolean mask): an (a, b) pair serves any of them"""
-        preds = np.asarray(where[1])
-        return where if preds.ndim == 1 else (where[0], preds[rows])
+    def _masked_walk(index, queries, knn, qp, allow, where):
+        """the masked walk of `index`: a label predicate, if given, stands for the bitmap"""
+        r = (index.batch_search_labeled(queries, where=where, out_k=knn, **qp) if where is not None else
+             index.batch_search_masked(queries, allow=allow, out_k=knn, **qp))
+        return r["ids"], r["dists"]
 
-    def _exact_or_walk_labeled(self, queries, knn, where, exact_below, walk, grouped=False):
-        """_exact_or_walk for label predicates: the counts come from DeviceIndex.label_count (nothing is materialised), the exact
-        route is DeviceIndex.bruteforce_knn_labeled (grouped: bruteforce_knn_grouped for per-query predicates),
-        walk(queries, where) -> (ids, dists) every other."""
+    def _exact_or_walk(self, queries, knn, allow, where, exact_below, walk, grouped=False):
+        """The rule of DESIGN.md "Exact masked kNN": a filter (allow= or where=, not both) with at most exact_below allowed
+        points is answered exactly on the full-precision handle (DeviceIndex.bruteforce_knn_masked / _labeled), any other by
+        walk(queries, allow=) or walk(queries, where=) -> (ids, dists).  The counts come from PointFilter.count: bitmaps on the
+        host, predicates by DeviceIndex.label_count (nothing is materialised).  Per-query rows are split by their own counts,
+        each part takes its route, and the rows come back in the given order.
+        grouped: the exact part of per-query rows goes through DeviceIndex.bruteforce_knn_grouped (equal rows share one list)."""
+        if where is not None and allow is not None:
+            raise ValueError("where and allow exclude each other")
         if exact_below is None:
-            return walk(queries, where)
+            return walk(queries, allow=allow, where=where)
         queries = np.ascontiguousarray(queries, dtype=self.T)
-        cnt = self.index.label_count(where)
-        if np.ndim(cnt) == 0:
+        flt = PointFilter.of(self.index.n, allow, where)
+        cnt = flt.count(self.index)
+        if flt.shared:
             if cnt > exact_below:
-                return walk(queries, where)
-            ids, dists, _ = self.index.bruteforce_knn_labeled(queries, knn, where)
+                return walk(queries, **flt.kw)
+            ids, dists, _ = getattr(self.index, "bruteforce_knn_" + flt.infix)(queries, knn, **flt.kw)
             return ids, dists
-        if len(cnt) != len(queries):
-            raise ValueError("per-query predicates must be an (nq, 2) array")
+        flt.check(len(queries))
         exact = cnt <= exact_below
         ids = np.full((len(queries), knn), 0xFFFFFFFF, np.uint32)
         dists = np.full((len(queries), knn), np.inf, np.float32)
         if exact.any():
-            knn_exact = self.index.bruteforce_knn_grouped if grouped else self.index.bruteforce_knn_labeled
-            ids[exact], dists[exact], _ = knn_exact(queries[exact], knn, where=self._where_rows(where, exact))
+            knn_exact = getattr(self.index, "bruteforce_knn_" + ("grouped" if grouped else flt.infix))
+            ids[exact], dists[exact], _ = knn_exact(queries[exact], knn, **flt.select(exact).kw)
         if not exact.all():
-            ids[~exact], dists[~exact] = walk(queries[~exact], self._where_rows(where, ~exact))
+            ids[~exact], dists[~exact] = walk(queries[~exact], **flt.select(~exact).kw)
         return ids, dists
 
     def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None,
@@ -215,16 +190,11 @@ class GraphIndex:
         where = (kind, preds): the same by a label predicate (DeviceIndex.batch_search_labeled); not together with allow.
         exact_below, exact_grouped (with allow or where): as batch_search_masked
         steer (with allow or where, quant=False): the steered walk, DeviceIndex.batch_search_masked(steer=); None changes nothing"""
-        if where is not None:
-            if allow is not None:
-                raise ValueError("where and allow exclude each other")
-            return self._exact_or_walk_labeled(queries, knn, where, exact_below,
-                                               lambda q, w: self._search(q, knn, beam_width, quant, visit_limit, where=w, steer=steer),
-                                               exact_grouped)
-        if allow is None:
+        if where is None and allow is None:
             return self._search(queries, knn, beam_width, quant, visit_limit, steer=steer)
-        return self._exact_or_walk(queries, knn, allow, exact_below,
-                                   lambda q, a: self._search(q, knn, beam_width, quant, visit_limit, a, steer=steer), exact_grouped)
+        return self._exact_or_walk(queries, knn, allow, where, exact_below,
+                                   lambda q, allow=None, where=None: self._search(q, knn, beam_width, quant, visit_limit, allow, where, steer),
+                                   exact_grouped)
 
     def _search_masked(self, queries, knn, beam_width, allow, quant, visit_limit, where=None):
         """Masked searches (this project's own, DESIGN.md "Masked search").  Rows may be short (padding 0xFFFFFFFF / +inf):
@@ -241,9 +211,7 @@ class GraphIndex:
         qp = self._qp(knn, beam_width, visit_limit)
         if self.metric == "Euclidian" and self.quant_bits == 8 and self.eparams.identity:   # slope == 1: the u8 copy, as _search
             qq = quantize.device_quantize_rows(queries, self.qparams, device=self.device)
-            r = (self.q_index.batch_search_masked(qq, allow=allow, out_k=knn, **qp) if where is None else
-                 self.q_index.batch_search_labeled(qq, where=where, out_k=knn, **qp))
-            return r["ids"], r["dists"]
+            return self._masked_walk(self.q_index, qq, knn, qp, allow, where)
         # the fused masked call: masked search of the quantised copy, exact rerank of its result list on the float handle
         r = self.index.search_rerank(self.q_index, self.qparams, queries, normalize_first=self.metric != "Euclidian",
                                      rerank_factor=100, allow=allow, where=where, **qp)
@@ -264,16 +232,11 @@ class GraphIndex:
         exact_grouped: the exact part of per-query rows or predicates is answered by DeviceIndex.bruteforce_knn_grouped, which
         scores the queries of equal filters together (DESIGN.md "Exact kNN by predicate group"): the same rows, faster when many
         queries share few filters.  The default changes nothing."""
-        if where is not None:
-            if allow is not None:
-                raise ValueError("where and allow exclude each other")
-            return self._exact_or_walk_labeled(queries, knn, where, exact_below,
-                                               lambda q, w: self._search_masked(q, knn, beam_width, None, quant, visit_limit, w),
-                                               exact_grouped)
-        if allow is None:
+        if where is None and allow is None:
             raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
-        return self._exact_or_walk(queries, knn, allow, exact_below,
-                                   lambda q, a: self._search_masked(q, knn, beam_width, a, quant, visit_limit), exact_grouped)
+        return self._exact_or_walk(queries, knn, allow, where, exact_below,
+                                   lambda q, allow=None, where=None: self._search_masked(q, knn, beam_width, allow, quant, visit_limit, where),
+                                   exact_grouped)
 
     def batch_search_masked_from_string(self, queries, knn, beam_width, allow, quant=False, visit_limit=-1):
         return self._search_masked(io.read_bin(queries, self.T), knn, beam_width, allow, quant, visit_limit)

@@ -150,6 +150,86 @@ def label_allow(labels, kind, preds):
     return out[0] if single else out
 
 
+class PointFilter:
+    """Which points a query may return, in one place (the C side: PointFilter, pann_internal.h; DESIGN.md "The point filter on
+    the host"): bitmap rows (allow=) or label predicates (where=).  rows: packed uint32 (W,) / (m, W), W >= ceil(n / 32), with
+    kind None; or uint32 (m, 2) predicates with their PANN_PRED_* kind.  shared: one row serves every query."""
+
+    def __init__(self, rows, kind=None, shared=True):
+        self.rows, self.kind, self.shared = rows, kind, shared
+
+    @classmethod
+    def masked(cls, allow, n):
+        """allow: boolean or packed, (n,) / (W,) shared or one row per query"""
+        rows = pack_allow(allow, n)
+        return cls(rows, None, rows.ndim == 1)
+
+    @classmethod
+    def labeled(cls, where):
+        """where = (kind, preds): preds (a, b) shared, or an (m, 2) array"""
+        if where is None or len(where) != 2:
+            raise ValueError('where must be (kind, preds): kind "any" | "match" | "range", preds (a, b) or an (nq, 2) array')
+        kind = pred_kind(where[0])
+        preds, single = label_preds(where[1])
+        return cls(preds, kind, single)
+
+    @classmethod
+    def of(cls, n, allow=None, where=None):
+        """the filter of an allow= / where= pair of keywords; None for neither"""
+        if where is not None:
+            if allow is not None:
+                raise ValueError("where and allow exclude each other")
+            return cls.labeled(where)
+        return None if allow is None else cls.masked(allow, n)
+
+    infix = property(lambda self: "masked" if self.kind is None else "labeled", doc="what names the C symbols of this mode")
+
+    def check(self, nq):
+        """per-query rows have to be nq; -> self"""
+        if not self.shared and len(self.rows) != nq:
+            raise ValueError("per-query allow rows must be nq x W" if self.kind is None else "per-query predicates must be an (nq, 2) array")
+        return self
+
+    def select(self, rows):
+        """the filter of the queries a boolean mask selects: a shared one serves any of them"""
+        return self if self.shared else PointFilter(self.rows[rows], self.kind, False)
+
+    def count(self, index):
+        """allowed points per row -> int (shared) or int64 (m,): bitmaps on the host, predicates on the device (index.label_count)"""
+        return allow_count(self.rows, index.n) if self.kind is None else index.label_count(self.kw["where"])
+
+    @property
+    def kw(self):
+        """the allow= / where= keyword that gives this filter again"""
+        return {"allow": self.rows} if self.kind is None else {"where": (self.kind, self.rows[0] if self.shared else self.rows)}
+
+    def table(self):
+        """the rows as the filter table of the grouped calls: (G, W) or (G, 2)"""
+        return self.rows[None, :] if self.rows.ndim == 1 else self.rows
+
+    def args(self, table=False):
+        """the C arguments: (kind, preds, count) for predicates; (rows, stride in words, 0 = one shared row) for a bitmap, or
+        (rows, count, words per row) as a table.  A None bitmap goes through as a null pointer: the library refuses it."""
+        if self.kind is not None:
+            return self.kind, _ptr(self.rows), len(self.rows)
+        if table:
+            return _ptr(self.rows), len(self.rows), self.rows.shape[1]
+        return _ptr(self.rows), 0 if self.shared else self.rows.shape[1]
+
+
+def _knn_out(nq, k):
+    return np.empty((nq, k), np.uint32), np.empty((nq, k), np.float32), np.empty(nq, np.uint32)
+
+
+def _pad_past_counts(ids, cnt):
+    """entries past a row's count are unspecified after a range call: pad them"""
+    w = int(cnt.max()) if len(cnt) else 0
+    ids[:, w:] = 0xFFFFFFFF
+    if w:
+        sub = ids[:, :w]
+        sub[np.arange(w, dtype=np.uint32)[None, :] >= cnt[:, None]] = 0xFFFFFFFF
+
+
 def host_graph(n, max_deg):
     """An empty graph slab in the reference layout (graph.h:134-141): n x (max_deg+1), slot 0 = degree."""
     return np.zeros((n, max_deg + 1), dtype=np.uint32)
@@ -161,22 +241,9 @@ class DeviceIndex:
         points = np.ascontiguousarray(points)
         if points.ndim != 2 or points.dtype not in _DT:
             raise ValueError("points must be a 2-D uint8/int8/float32/float16/bfloat16 (parlayann_amd.bfloat16) array")
-        n, d = points.shape
-        if graph is not None:
-            graph = np.ascontiguousarray(graph, dtype=np.uint32)
-            if graph.ndim != 2 or graph.shape[0] != n:
-                raise ValueError("graph must be n x (max_deg+1) uint32 (reference layout)")
-            max_degree = graph.shape[1] - 1
-        if max_degree is None:
-            raise ValueError("give a graph or max_degree")
-        self.n, self.d, self.max_degree = n, d, int(max_degree)
-        self.dtype, self.metric = points.dtype, _metric_code(metric)
-        h = C.c_void_p()
-        check(lib.pann_index_create(C.byref(h), _ptr(points), n, d, _DT[points.dtype], _row_stride(points),
-                                    self.metric, _ptr(graph), self.max_degree, device))
-        self._h, self._lib = h, lib
+        self._create(lib, points, points.shape[1], points.dtype, None, graph, max_degree, metric, device)
         if exact_float_order:      # validation mode: bit-identical float results on real-valued data
-            check(lib.pann_index_set_exact_float_order(h, 1))
+            check(self._lib.pann_index_set_exact_float_order(self._h, 1))
 
     @classmethod
     def from_packed(cls, rows, dims, dtype, graph=None, max_degree=None, metric=None, device=0):
@@ -191,6 +258,12 @@ class DeviceIndex:
         dims = int(dims)
         if rows.ndim != 2 or rows.shape[1] != (dims + 1) // 2:
             raise ValueError(f"rows must be n x {(dims + 1) // 2} uint8 (two coordinates per byte)")
+        if metric is None:
+            metric = PANN_L2 if code == PANN_U4 else PANN_MIPS
+        return cls.__new__(cls)._create(lib, rows, dims, rows.dtype, code, graph, max_degree, metric, device)
+
+    def _create(self, lib, rows, dims, dtype, dtype4, graph, max_degree, metric, device):
+        """pann_index_create over host rows, with the one check of the graph argument -> self"""
         if graph is not None:
             graph = np.ascontiguousarray(graph, dtype=np.uint32)
             if graph.ndim != 2 or graph.shape[0] != len(rows):
@@ -198,15 +271,16 @@ class DeviceIndex:
             max_degree = graph.shape[1] - 1
         if max_degree is None:
             raise ValueError("give a graph or max_degree")
-        if metric is None:
-            metric = PANN_L2 if code == PANN_U4 else PANN_MIPS
-        self = cls.__new__(cls)
-        self.n, self.d, self.max_degree = len(rows), dims, int(max_degree)
-        self.dtype, self.metric, self.dtype4 = np.dtype(np.uint8), _metric_code(metric), code
-        h = C.c_void_p()
-        check(lib.pann_index_create(C.byref(h), _ptr(rows), self.n, dims, code, _row_stride(rows), self.metric, _ptr(graph),
-                                    self.max_degree, device))
-        self._h, self._lib = h, lib
+        max_degree, metric, h = int(max_degree), _metric_code(metric), C.c_void_p()
+        check(lib.pann_index_create(C.byref(h), _ptr(rows), len(rows), dims, _DT[dtype] if dtype4 is None else dtype4, _row_stride(rows),
+                                    metric, _ptr(graph), max_degree, device))
+        return self._adopt(lib, h, len(rows), dims, max_degree, dtype, metric, dtype4)
+
+    def _adopt(self, lib, h, n, d, max_degree, dtype, metric, dtype4=None):
+        """the one place that makes an object the owner of a handle -> self"""
+        self._lib, self._h = lib, h
+        self.n, self.d, self.max_degree = n, d, max_degree
+        self.dtype, self.metric, self.dtype4 = dtype, metric, dtype4
         return self
 
     dtype4 = None          # PANN_U4 / PANN_I4 for a four-bit index: rows are packed uint8, row_bytes of them per row
@@ -224,13 +298,9 @@ class DeviceIndex:
         dt = np.dtype(dtype)
         if dt not in _DT:
             raise ValueError("dtype must be uint8/int8/float32/float16/bfloat16 (parlayann_amd.bfloat16)")
-        self = cls.__new__(cls)
-        self.n, self.d, self.max_degree = int(n), int(d), int(max_degree)
-        self.dtype, self.metric = dt, _metric_code(metric)
-        h = C.c_void_p()
-        check(lib.pann_index_create_empty(C.byref(h), self.n, self.d, _DT[dt], self.metric, self.max_degree, device))
-        self._h, self._lib = h, lib
-        return self
+        n, d, max_degree, metric, h = int(n), int(d), int(max_degree), _metric_code(metric), C.c_void_p()
+        check(lib.pann_index_create_empty(C.byref(h), n, d, _DT[dt], metric, max_degree, device))
+        return cls.__new__(cls)._adopt(lib, h, n, d, max_degree, dt, metric)
 
     @classmethod
     def from_files(cls, points_path, dtype, graph_path=None, max_degree=None, metric="Euclidian", device=0, rows=None,
@@ -366,49 +436,38 @@ class DeviceIndex:
     def has_labels(self):
         return bool(self._lib.pann_index_has_labels(self._h))
 
-    def _where(self, where, nq=None):
-        """where = (kind, preds) -> (PANN_PRED_* code, uint32 (m, 2) array); m is 1 or nq"""
-        if where is None or len(where) != 2:
-            raise ValueError('where must be (kind, preds): kind "any" | "match" | "range", preds (a, b) or an (nq, 2) array')
-        kind = pred_kind(where[0])
-        p, single = label_preds(where[1])
-        if nq is not None and not single and len(p) != nq:
-            raise ValueError("per-query predicates must be an (nq, 2) array")
-        return kind, p
-
-    def _device_preds(self, where):
-        """the predicates of `where` as a torch tensor on the handle's device (the two helpers take device pointers)"""
+    def _label_rows_dev(self, where, words=None):
+        """The one device-side evaluation of the predicates of `where` -> (int32 tensor on the handle's device, complete; the
+        filter).  words=None: pann_label_count_dev, one count per predicate; else pann_labels_to_allow_dev, `words` bitmap words
+        per predicate.  Both take device pointers and run on torch's current stream, which is synchronised here."""
         import torch
-        kind, p = self._where(where)
+        flt = PointFilter.labeled(where)
+        m = len(flt.rows)
         dev = torch.device("cuda", int(self._lib.pann_index_device(self._h)))
-        return kind, p, torch.from_numpy(p.view(np.int32)).to(dev), dev
+        d_p = torch.from_numpy(flt.rows.view(np.int32)).to(dev)
+        d_out = torch.empty(m if words is None else (m, words), dtype=torch.int32, device=dev)
+        st = torch.cuda.current_stream(dev)
+        p, out, stream = C.c_void_p(d_p.data_ptr()), C.c_void_p(d_out.data_ptr()), C.c_void_p(st.cuda_stream or None)
+        if words is None:
+            check(self._lib.pann_label_count_dev(self._h, flt.kind, p, m, out, stream))
+        else:
+            check(self._lib.pann_labels_to_allow_dev(self._h, flt.kind, p, m, out, words, stream))
+        st.synchronize()
+        return d_out, flt
 
     def label_count(self, where):
         """pann_label_count_dev: the number of points each predicate of `where` allows, nothing materialised -> int for the
         (a, b) form, int64 (m,) for an (m, 2) array"""
-        import torch
-        kind, p, d_p, dev = self._device_preds(where)
-        d_c = torch.empty(len(p), dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev)
-        check(self._lib.pann_label_count_dev(self._h, kind, C.c_void_p(d_p.data_ptr()), len(p), C.c_void_p(d_c.data_ptr()),
-                                             C.c_void_p(st.cuda_stream or None)))
-        st.synchronize()
+        d_c, flt = self._label_rows_dev(where)
         c = d_c.cpu().numpy().view(np.uint32).astype(np.int64)
-        return int(c[0]) if np.asarray(where[1]).ndim == 1 else c
+        return int(c[0]) if flt.shared else c
 
     def labels_to_allow(self, where):
         """pann_labels_to_allow_dev: the bitmap rows of the predicates of `where`, in the format of batch_search_masked ->
         packed uint32 (W,) for the (a, b) form, (m, W) for an (m, 2) array, W = ceil(n / 32); bits at positions >= n are 0"""
-        import torch
-        kind, p, d_p, dev = self._device_preds(where)
-        w = (self.n + 31) // 32
-        d_a = torch.empty((len(p), w), dtype=torch.int32, device=dev)
-        st = torch.cuda.current_stream(dev)
-        check(self._lib.pann_labels_to_allow_dev(self._h, kind, C.c_void_p(d_p.data_ptr()), len(p), C.c_void_p(d_a.data_ptr()), w,
-                                                 C.c_void_p(st.cuda_stream or None)))
-        st.synchronize()
+        d_a, flt = self._label_rows_dev(where, (self.n + 31) // 32)
         a = d_a.cpu().numpy().view(np.uint32)
-        return a[0] if np.asarray(where[1]).ndim == 1 else a
+        return a[0] if flt.shared else a
 
     def set_stream(self, stream_ptr, private=False):
         """pann_index_set_stream: run the handle's calls on the caller's stream (a hipStream_t as an integer; 0 = the device's
@@ -453,11 +512,7 @@ class DeviceIndex:
         p = self.quantize_params(kind, trim) if params is None else params
         h = C.c_void_p()
         check(self._lib.pann_index_create_quantized(C.byref(h), self._h, C.byref(p), 1 if copy_graph else 0))
-        q = DeviceIndex.__new__(DeviceIndex)
-        q.n, q.d, q.max_degree = self.n, self.d, self.max_degree
-        q.dtype, q.metric, q.dtype4 = _QUANT_DT[p.kind]
-        q._h, q._lib = h, self._lib
-        return q, p
+        return DeviceIndex.__new__(DeviceIndex)._adopt(self._lib, h, self.n, self.d, self.max_degree, *_QUANT_DT[p.kind]), p
 
     # ---- subset index: carve out, compact or grow a handle on the device (DESIGN.md "Subset index") ----
     def subset(self, allow=None, *, where=None, capacity=None, copy_graph=True, maps=True):
@@ -479,15 +534,9 @@ class DeviceIndex:
             import torch
             if np.asarray(where[1]).ndim != 1:
                 raise ValueError("subset takes a single predicate (a, b)")
-            kind, p, d_p, dev = self._device_preds(where)
-            w = (n + 31) // 32
-            d_a = torch.empty(w, dtype=torch.int32, device=dev)
-            st = torch.cuda.current_stream(dev)
-            check(self._lib.pann_labels_to_allow_dev(self._h, kind, C.c_void_p(d_p.data_ptr()), 1, C.c_void_p(d_a.data_ptr()), w,
-                                                     C.c_void_p(st.cuda_stream or None)))
-            st.synchronize()               # the subset runs on the handle's stream: the bitmap has to be complete before it
-            d_n2o = torch.empty(n, dtype=torch.int32, device=dev) if maps else None
-            d_o2n = torch.empty(n, dtype=torch.int32, device=dev) if maps else None
+            d_a, _ = self._label_rows_dev(where, (n + 31) // 32)     # complete on return: the subset runs on the handle's stream
+            d_n2o = torch.empty(n, dtype=torch.int32, device=d_a.device) if maps else None
+            d_o2n = torch.empty(n, dtype=torch.int32, device=d_a.device) if maps else None
             check(self._lib.pann_index_create_subset_dev(C.byref(h), self._h, C.c_void_p(d_a.data_ptr()), cap, 1 if copy_graph else 0,
                                                          C.c_void_p(d_n2o.data_ptr()) if maps else None, n,
                                                          C.c_void_p(d_o2n.data_ptr()) if maps else None, C.byref(kept)))
@@ -506,10 +555,8 @@ class DeviceIndex:
                                                      C.byref(kept)))
             if maps:
                 n2o = n2o[:kept.value].copy()
-        s = DeviceIndex.__new__(DeviceIndex)
-        s._h, s._lib = h, self._lib
-        s.n, s.d, s.max_degree = int(self._lib.pann_index_size(h)), self.d, self.max_degree
-        s.dtype, s.metric, s.dtype4 = self.dtype, self.metric, self.dtype4
+        s = DeviceIndex.__new__(DeviceIndex)._adopt(self._lib, h, int(self._lib.pann_index_size(h)), self.d, self.max_degree, self.dtype,
+                                                    self.metric, self.dtype4)
         return (s, n2o, o2n) if maps else s
 
     # ---- batched beam search: the searchAll / qsearchAll seam (beamSearch.h:374,556) ----
@@ -539,10 +586,9 @@ class DeviceIndex:
         distances on allowed points only -- disallowed neighbours are bridges to their own allowed neighbours (DESIGN.md
         "Steered masked search").  The integer is `fill`, the number of waiting points at which a visit stops expanding
         bridges: 1 .. min(degree_limit, max_degree), 0 means that bound.  Adds "bridge_rows" and "hop2_cmps" per query."""
-        if allow is not None:
-            allow = pack_allow(allow, self.n)
+        flt = PointFilter(None) if allow is None else PointFilter.masked(allow, self.n)      # no bitmap: the library's refusal
         return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                                  masked=True, allow=allow, steer=steer)
+                                  flt=flt, steer=steer)
 
     def batch_search_labeled(self, queries=None, where=None, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
                              query_ids=None, out_k=None, visited_cap=0, want_dists=True, steer=None):
@@ -552,14 +598,33 @@ class DeviceIndex:
         allow = label_allow(self.labels(), kind, preds).  steer: as batch_search_masked (pann_batch_search_steered_labeled)."""
         nq = len(queries) if queries is not None else len(query_ids)
         return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                                  masked=True, where=self._where(where, nq), steer=steer)
+                                  flt=PointFilter.labeled(where).check(nq), steer=steer)
+
+    def _query_rows(self, queries, query_ids):
+        """queries or query_ids -> (query rows or None, uint32 ids or None, nq, row stride in bytes)"""
+        if queries is not None:
+            q = self._queries(queries)
+            return q, None, len(q), _row_stride(q)
+        qid = np.ascontiguousarray(query_ids, dtype=np.uint32)
+        return None, qid, len(qid), 0
+
+    def _qp(self, k, beam, cut, limit, degree_limit, rerank_factor=100):
+        return QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
+                           degree_limit=self.max_degree if degree_limit is None else degree_limit,
+                           rerank_factor=rerank_factor, pad=1.0)
+
+    @staticmethod
+    def _filter_counters(res, nq):
+        """the two per-query outputs every filtered search adds -> their pointers, the tail of the C call"""
+        res["result_count"], res["allowed_cmps"] = np.empty(nq, np.uint32), np.empty(nq, np.uint32)
+        return _ptr(res["result_count"]), _ptr(res["allowed_cmps"])
 
     def _batch_search(self, queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                      filtered=False, sketch_queries=None, masked=False, allow=None, where=None, steer=None):
+                      filtered=False, sketch_queries=None, flt=None, steer=None):
+        """One body for pann_batch_search{, _per_query_starts, _filtered, _masked, _labeled, _steered, _steered_labeled}: they
+        share (handle, queries, ids, nq, stride, [sketch rows, bytes,] starts, nstarts, params, [filter,] out, [extra outputs])."""
         nq = len(queries) if queries is not None else len(query_ids)
-        qp = QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
-                         degree_limit=self.max_degree if degree_limit is None else degree_limit,
-                         rerank_factor=100, pad=1.0)
+        qp = self._qp(k, beam, cut, limit, degree_limit)
         out_k = k if out_k is None else out_k
         res = {
             "ids": np.empty((nq, out_k), dtype=np.uint32),
@@ -581,74 +646,38 @@ class DeviceIndex:
         per_query = starts.ndim == 2          # nq x nstarts: beamSearchRandom-style, one start set per query
         if per_query and starts.shape[0] != nq:
             raise ValueError("per-query starts must be nq x nstarts")
-        q = qid = None
-        stride = 0
-        if queries is not None:
-            q = self._queries(queries)
-            stride = _row_stride(q)
-        else:
-            qid = np.ascontiguousarray(query_ids, dtype=np.uint32)
+        q, qid, _, stride = self._query_rows(queries, query_ids)
+        if per_query and (filtered or flt is not None):
+            raise ValueError(f"{'filtered' if filtered else 'masked'} searches take shared starts")
+        name, sketch, mid, tail, counters = "pann_batch_search", (), (), (), None
         if filtered:
-            if per_query:
-                raise ValueError("filtered searches take shared starts")
             sq = None
             if sketch_queries is not None:
                 sq = np.ascontiguousarray(sketch_queries, dtype=np.uint8)
                 if sq.ndim != 2 or sq.shape[0] != nq:
                     raise ValueError("sketch_queries must be nq rows of uint8")
             res["pruned_cmps"] = np.empty(nq, dtype=np.uint32)
-            check(self._lib.pann_batch_search_filtered(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(sq), 0 if sq is None else sq.shape[1],
-                                                       _ptr(starts), starts.shape[-1], C.byref(qp), C.byref(out),
-                                                       _ptr(res["pruned_cmps"])))
-            return res
-        if masked:
-            if per_query:
-                raise ValueError("masked searches take shared starts")
+            name, sketch, tail = name + "_filtered", (_ptr(sq), 0 if sq is None else sq.shape[1]), (_ptr(res["pruned_cmps"]),)
+        elif flt is not None:
             if steer is not None:
                 fill = int(steer)
                 if fill < 0 or fill > 0xFFFFFFFF:
                     raise ValueError("steer is the fill count: 0 (the degree bound) or a positive integer")
+            mid, tail = flt.check(nq).args(), self._filter_counters(res, nq)
+            if steer is None:
+                name += "_" + flt.infix
+            else:
                 counters = np.empty((nq, 2), dtype=np.uint32)
-            if where is not None:
-                kind, preds = where
-                res["result_count"] = np.empty(nq, dtype=np.uint32)
-                res["allowed_cmps"] = np.empty(nq, dtype=np.uint32)
-                if steer is not None:
-                    check(self._lib.pann_batch_search_steered_labeled(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts),
-                                                                      starts.shape[-1], C.byref(qp), kind, _ptr(preds), len(preds),
-                                                                      C.byref(out), _ptr(res["result_count"]), _ptr(res["allowed_cmps"]),
-                                                                      fill, _ptr(counters)))
-                    res["bridge_rows"], res["hop2_cmps"] = counters[:, 0].copy(), counters[:, 1].copy()
-                    return res
-                check(self._lib.pann_batch_search_labeled(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1],
-                                                          C.byref(qp), kind, _ptr(preds), len(preds), C.byref(out),
-                                                          _ptr(res["result_count"]), _ptr(res["allowed_cmps"])))
-                return res
-            if allow is not None and allow.ndim == 2 and allow.shape[0] != nq:
-                raise ValueError("per-query allow rows must be nq x W")
-            astride = allow.shape[1] if allow is not None and allow.ndim == 2 else 0
-            res["result_count"] = np.empty(nq, dtype=np.uint32)
-            res["allowed_cmps"] = np.empty(nq, dtype=np.uint32)
-            if steer is not None:
-                check(self._lib.pann_batch_search_steered(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1],
-                                                          C.byref(qp), _ptr(allow), astride, C.byref(out), _ptr(res["result_count"]),
-                                                          _ptr(res["allowed_cmps"]), fill, _ptr(counters)))
-                res["bridge_rows"], res["hop2_cmps"] = counters[:, 0].copy(), counters[:, 1].copy()
-                return res
-            check(self._lib.pann_batch_search_masked(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1], C.byref(qp),
-                                                     _ptr(allow), astride, C.byref(out), _ptr(res["result_count"]),
-                                                     _ptr(res["allowed_cmps"])))
-            return res
-        fn = self._lib.pann_batch_search_per_query_starts if per_query else self._lib.pann_batch_search
-        check(fn(self._h, _ptr(q), _ptr(qid), nq, stride, _ptr(starts), starts.shape[-1], C.byref(qp), C.byref(out)))
+                name, tail = name + "_steered" + ("" if flt.kind is None else "_labeled"), tail + (fill, _ptr(counters))
+        elif per_query:
+            name += "_per_query_starts"
+        check(getattr(self._lib, name)(self._h, _ptr(q), _ptr(qid), nq, stride, *sketch, _ptr(starts), starts.shape[-1], C.byref(qp), *mid,
+                                       C.byref(out), *tail))
+        if counters is not None:
+            res["bridge_rows"], res["hop2_cmps"] = counters[:, 0].copy(), counters[:, 1].copy()
         return res
 
     # ---- quantised search + exact rerank in one call: beam_search_rerank (beamSearch.h:390-454) ----
-    def _rerank_qp(self, k, beam, cut, limit, degree_limit, rerank_factor):
-        return QueryParams(k=k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
-                           degree_limit=self.max_degree if degree_limit is None else degree_limit,
-                           rerank_factor=rerank_factor, pad=1.0)
-
     def search_rerank(self, quant, qparams, queries, k=10, beam=64, cut=1.35, limit=None, degree_limit=None, starts=(0,),
                       normalize_first=False, use_filter=False, rerank_factor=100, allow=None, where=None):
         """pann_batch_search_rerank on this (float32) index: `queries` (float32 rows) are quantised with `qparams` on the
@@ -665,7 +694,7 @@ class DeviceIndex:
         place of the bitmap, evaluated on THIS handle's labels (quant needs none).  Not together with allow."""
         q = self._queries(queries)
         nq = len(q)
-        qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
+        qp = self._qp(k, beam, cut, limit, degree_limit, rerank_factor)
         res = {"ids": np.empty((nq, k), np.uint32), "dists": np.empty((nq, k), np.float32),
                "frontier_size": np.empty(nq, np.uint32), "visited_count": np.empty(nq, np.uint32),
                "dist_cmps": np.empty(nq, np.uint32), "status": np.zeros(1, np.uint32)}
@@ -675,32 +704,12 @@ class DeviceIndex:
                         visited_count=_ptr(res["visited_count"]), dist_cmps=_ptr(res["dist_cmps"]),
                         pruned_cmps=_ptr(res.get("pruned_cmps")), status=_ptr(res["status"]))
         starts = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
-        if where is not None:
-            if allow is not None:
-                raise ValueError("where and allow exclude each other")
-            kind, preds = self._where(where, nq)
-            res["result_count"] = np.empty(nq, np.uint32)
-            res["allowed_cmps"] = np.empty(nq, np.uint32)
-            check(self._lib.pann_batch_search_labeled_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q),
-                                                             1 if normalize_first else 0, 1 if use_filter else 0, _ptr(starts),
-                                                             len(starts), C.byref(qp), kind, _ptr(preds), len(preds), C.byref(out),
-                                                             _ptr(res["result_count"]), _ptr(res["allowed_cmps"])))
-            return res
-        if allow is not None:
-            allow = pack_allow(allow, self.n)
-            if allow.ndim == 2 and allow.shape[0] != nq:
-                raise ValueError("per-query allow rows must be nq x W")
-            res["result_count"] = np.empty(nq, np.uint32)
-            res["allowed_cmps"] = np.empty(nq, np.uint32)
-            check(self._lib.pann_batch_search_masked_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q),
-                                                            1 if normalize_first else 0, 1 if use_filter else 0, _ptr(starts),
-                                                            len(starts), C.byref(qp), _ptr(allow),
-                                                            allow.shape[1] if allow.ndim == 2 else 0, C.byref(out),
-                                                            _ptr(res["result_count"]), _ptr(res["allowed_cmps"])))
-            return res
-        check(self._lib.pann_batch_search_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q),
-                                                 1 if normalize_first else 0, 1 if use_filter else 0, _ptr(starts), len(starts),
-                                                 C.byref(qp), C.byref(out)))
+        flt = PointFilter.of(self.n, allow, where)
+        name, mid, tail = "pann_batch_search_rerank", (), ()
+        if flt is not None:
+            name, mid, tail = f"pann_batch_search_{flt.infix}_rerank", flt.check(nq).args(), self._filter_counters(res, nq)
+        check(getattr(self._lib, name)(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q), 1 if normalize_first else 0,
+                                       1 if use_filter else 0, _ptr(starts), len(starts), C.byref(qp), *mid, C.byref(out), *tail))
         return res
 
     def search_rerank_dev(self, quant, qparams, d_queries_ptr, nq, q_stride_bytes, d_starts_ptr, nstarts, d_ids_ptr, d_dists_ptr,
@@ -713,28 +722,21 @@ class DeviceIndex:
         been.  The first call grows quant's scratch.  d_allow_ptr (packed bitmap rows on the device, allow_stride_words 0 =
         one shared row): pann_batch_search_masked_rerank_dev, with the two optional per-query outputs.  d_preds_ptr (npreds = 1 or nq
         predicates of kind pred_kind on the device, 8-byte aligned): pann_batch_search_labeled_rerank_dev, on this handle's labels."""
-        qp = self._rerank_qp(k, beam, cut, limit, degree_limit, rerank_factor)
+        qp = self._qp(k, beam, cut, limit, degree_limit, rerank_factor)
         vp = lambda a: C.c_void_p(a or None)
         out = RerankOut(ids=vp(d_ids_ptr), dists=vp(d_dists_ptr), frontier_size=vp(d_frontier_size_ptr),
                         visited_count=vp(d_visited_count_ptr), dist_cmps=vp(d_dist_cmps_ptr), pruned_cmps=vp(d_pruned_cmps_ptr),
                         status=vp(d_status_ptr))
+        name, mid, tail = "pann_batch_search_rerank_dev", (), ()
         if d_preds_ptr is not None:
-            check(self._lib.pann_batch_search_labeled_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq,
-                                                                 q_stride_bytes, 1 if normalize_first else 0, 1 if use_filter else 0,
-                                                                 vp(d_starts_ptr), nstarts, C.byref(qp), _pred_kind(pred_kind),
-                                                                 vp(d_preds_ptr), npreds, C.byref(out), vp(d_result_count_ptr),
-                                                                 vp(d_allowed_cmps_ptr), vp(stream_ptr)))
-            return
-        if d_allow_ptr is not None:
-            check(self._lib.pann_batch_search_masked_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq,
-                                                                q_stride_bytes, 1 if normalize_first else 0, 1 if use_filter else 0,
-                                                                vp(d_starts_ptr), nstarts, C.byref(qp), vp(d_allow_ptr),
-                                                                allow_stride_words, C.byref(out), vp(d_result_count_ptr),
-                                                                vp(d_allowed_cmps_ptr), vp(stream_ptr)))
-            return
-        check(self._lib.pann_batch_search_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
-                                                     1 if normalize_first else 0, 1 if use_filter else 0, vp(d_starts_ptr), nstarts,
-                                                     C.byref(qp), C.byref(out), vp(stream_ptr)))
+            name, mid = "pann_batch_search_labeled_rerank_dev", (_pred_kind(pred_kind), vp(d_preds_ptr), npreds)
+        elif d_allow_ptr is not None:
+            name, mid = "pann_batch_search_masked_rerank_dev", (vp(d_allow_ptr), allow_stride_words)
+        if mid:
+            tail = (vp(d_result_count_ptr), vp(d_allowed_cmps_ptr))
+        check(getattr(self._lib, name)(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
+                                       1 if normalize_first else 0, 1 if use_filter else 0, vp(d_starts_ptr), nstarts, C.byref(qp), *mid,
+                                       C.byref(out), *tail, vp(stream_ptr)))
 
     # ---- robustPrune (vamana/index.h:63-137), batched ----
     def robust_prune_batch(self, owners, cand_ids, cand_offsets, alpha, R, cand_dists=None, add_out_nbrs=True):
@@ -905,21 +907,14 @@ class DeviceIndex:
         per_query = starts.ndim == 2
         if (queries is None) == (query_ids is None):
             raise ValueError("exactly one of queries / query_ids must be given")
-        if queries is not None:
-            q = self._queries(queries); nq = len(q); qp, qs, qi = _ptr(q), _row_stride(q), None
-        else:
-            qid = np.ascontiguousarray(query_ids, dtype=np.uint32); nq = len(qid); qp, qs, qi = None, 0, _ptr(qid)
+        q, qid, nq, qs = self._query_rows(queries, query_ids)
         if per_query and len(starts) != nq:
             raise ValueError("per-query starts must have one row per query")
         ids = np.empty((nq, max_results), np.uint32)
         cnt = np.zeros(nq, np.uint32); cmps = np.zeros(nq, np.uint32); trunc = np.zeros(nq, np.uint32)
-        check(self._lib.pann_range_search(self._h, qp, qi, nq, qs, _ptr(starts), starts.shape[-1], 1 if per_query else 0,
+        check(self._lib.pann_range_search(self._h, _ptr(q), _ptr(qid), nq, qs, _ptr(starts), starts.shape[-1], 1 if per_query else 0,
                                           float(radius_2), max_results, _ptr(ids), _ptr(cnt), _ptr(cmps), _ptr(trunc)))
-        w = int(cnt.max()) if nq else 0                      # entries past a row's count are unspecified: pad them
-        ids[:, w:] = 0xFFFFFFFF
-        if w:
-            sub = ids[:, :w]
-            sub[np.arange(w, dtype=np.uint32)[None, :] >= cnt[:, None]] = 0xFFFFFFFF
+        _pad_past_counts(ids, cnt)
         return {"ids": ids, "counts": cnt, "dist_cmps": cmps, "truncated": trunc}
 
     def range_query(self, queries=None, radius=None, beam=10, max_results=1024, query_ids=None, starts=(0,), k=None, cut=0.0,
@@ -932,23 +927,15 @@ class DeviceIndex:
             raise ValueError("radius must be given")
         if (queries is None) == (query_ids is None):
             raise ValueError("exactly one of queries / query_ids must be given")
-        if queries is not None:
-            q = self._queries(queries); nq = len(q); qptr, qs, qi = _ptr(q), _row_stride(q), None
-        else:
-            qid = np.ascontiguousarray(query_ids, dtype=np.uint32); nq = len(qid); qptr, qs, qi = None, 0, _ptr(qid)
+        q, qid, nq, qs = self._query_rows(queries, query_ids)
         starts = np.ascontiguousarray(starts, dtype=np.uint32).reshape(-1)
-        qp = QueryParams(k=beam if k is None else k, beam=beam, cut=cut, limit=self.n if limit is None else limit,
-                         degree_limit=self.max_degree if degree_limit is None else degree_limit, rerank_factor=100, pad=1.0)
+        qp = self._qp(beam if k is None else k, beam, cut, limit, degree_limit)
         ids = np.empty((nq, max_results), np.uint32)
         cnt = np.zeros(nq, np.uint32); trunc = np.zeros(nq, np.uint32)
         scmps = np.zeros(nq, np.uint32); vis = np.zeros(nq, np.uint32); rcmps = np.zeros(nq, np.uint32)
-        check(self._lib.pann_range_query(self._h, qptr, qi, nq, qs, _ptr(starts), len(starts), C.byref(qp), float(radius),
+        check(self._lib.pann_range_query(self._h, _ptr(q), _ptr(qid), nq, qs, _ptr(starts), len(starts), C.byref(qp), float(radius),
                                          max_results, _ptr(ids), _ptr(cnt), _ptr(scmps), _ptr(vis), _ptr(rcmps), _ptr(trunc)))
-        w = int(cnt.max()) if nq else 0                      # entries past a row's count are unspecified: pad them
-        ids[:, w:] = 0xFFFFFFFF
-        if w:
-            sub = ids[:, :w]
-            sub[np.arange(w, dtype=np.uint32)[None, :] >= cnt[:, None]] = 0xFFFFFFFF
+        _pad_past_counts(ids, cnt)
         return {"ids": ids, "counts": cnt, "dist_cmps": rcmps, "truncated": trunc, "search_cmps": scmps, "visited": vis,
                 "range_cmps": rcmps}
 
@@ -988,24 +975,20 @@ class DeviceIndex:
         (nq, W), or boolean (n,) or (nq, n); one row serves the whole batch (k <= 128), rows are per query (k <= 64).  Row q
         holds counts[q] = min(k, allowed points) entries sorted by (dist, id), then 0xFFFFFFFF / +inf."""
         q = self._queries(queries)
-        allow = pack_allow(allow, self.n)
-        if allow.ndim == 2 and allow.shape[0] != len(q):
-            raise ValueError("per-query allow rows must be nq x W")
-        oi = np.empty((len(q), k), np.uint32); od = np.empty((len(q), k), np.float32); oc = np.empty(len(q), np.uint32)
-        check(self._lib.pann_bruteforce_knn_masked(self._h, _ptr(q), len(q), _row_stride(q), k, _ptr(allow),
-                                                   allow.shape[1] if allow.ndim == 2 else 0, _ptr(oi), _ptr(od), _ptr(oc)))
-        return oi, od, oc
+        return self._knn_filtered(q, k, PointFilter.masked(allow, self.n))
 
     def bruteforce_knn_labeled(self, queries, k, where):
         """pann_bruteforce_knn_labeled: bruteforce_knn_masked with a label predicate in place of the bitmap.  where = (kind,
         preds), as batch_search_labeled: (a, b) is the shared route (k <= 128), an (nq, 2) array the per-query one (k <= 64).
         -> (ids uint32[nq, k], dists float32[nq, k], counts uint32[nq])"""
         q = self._queries(queries)
-        kind, preds = self._where(where, len(q))
-        oi = np.empty((len(q), k), np.uint32); od = np.empty((len(q), k), np.float32); oc = np.empty(len(q), np.uint32)
-        check(self._lib.pann_bruteforce_knn_labeled(self._h, _ptr(q), len(q), _row_stride(q), k, kind, _ptr(preds), len(preds),
-                                                    _ptr(oi), _ptr(od), _ptr(oc)))
-        return oi, od, oc
+        return self._knn_filtered(q, k, PointFilter.labeled(where))
+
+    def _knn_filtered(self, q, k, flt):
+        """pann_bruteforce_knn_masked / _labeled: (handle, queries, nq, stride, k, filter, ids, dists, counts)"""
+        fn, outs = getattr(self._lib, "pann_bruteforce_knn_" + flt.check(len(q)).infix), _knn_out(len(q), k)
+        check(fn(self._h, _ptr(q), len(q), _row_stride(q), k, *flt.args(), *map(_ptr, outs)))
+        return outs
 
     def bruteforce_knn_grouped(self, queries, k, *, where=None, allow=None, group_of_query=None, max_list_ids=0):
         """pann_bruteforce_knn_labeled_grouped / _masked_grouped: exact kNN for many queries that share few filters (DESIGN.md
@@ -1019,12 +1002,8 @@ class DeviceIndex:
         nq = len(q)
         if (where is None) == (allow is None):
             raise ValueError("bruteforce_knn_grouped needs where (label predicates) or allow (bitmap rows), not both")
-        if where is not None:
-            kind, table = self._where(where)
-        else:
-            table = pack_allow(allow, self.n)
-            if table.ndim == 1:
-                table = table[None, :]
+        flt = PointFilter.of(self.n, allow, where)
+        table = flt.table()
         if group_of_query is None:
             if len(table) != nq:
                 raise ValueError("without group_of_query the table holds one filter per query")
@@ -1035,17 +1014,11 @@ class DeviceIndex:
                 raise ValueError("group_of_query must hold one table index per query")
             if nq and (group.min() < 0 or group.max() >= len(table)):
                 raise ValueError("group_of_query: a table index is out of range")
-        table = np.ascontiguousarray(table, dtype=np.uint32)
+        table = PointFilter(np.ascontiguousarray(table, dtype=np.uint32), flt.kind, False)
         group = np.ascontiguousarray(np.asarray(group).reshape(-1), dtype=np.uint32)
-        oi = np.empty((nq, k), np.uint32); od = np.empty((nq, k), np.float32); oc = np.empty(nq, np.uint32)
-        if where is not None:
-            check(self._lib.pann_bruteforce_knn_labeled_grouped(self._h, _ptr(q), nq, _row_stride(q), k, kind, _ptr(table), len(table),
-                                                                _ptr(group), int(max_list_ids), _ptr(oi), _ptr(od), _ptr(oc)))
-        else:
-            check(self._lib.pann_bruteforce_knn_masked_grouped(self._h, _ptr(q), nq, _row_stride(q), k, _ptr(table), len(table),
-                                                               table.shape[1], _ptr(group), int(max_list_ids), _ptr(oi), _ptr(od),
-                                                               _ptr(oc)))
-        return oi, od, oc
+        fn, outs = getattr(self._lib, f"pann_bruteforce_knn_{flt.infix}_grouped"), _knn_out(nq, k)
+        check(fn(self._h, _ptr(q), nq, _row_stride(q), k, *table.args(table=True), _ptr(group), int(max_list_ids), *map(_ptr, outs)))
+        return outs
 
     def bruteforce_knn_masked_dev(self, d_queries_ptr, nq, q_stride_bytes, k, d_allow_ptr, allow_stride_words, d_ids_ptr,
                                   d_dists_ptr, d_counts_ptr=None, stream_ptr=None):
