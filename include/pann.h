@@ -117,6 +117,8 @@ typedef struct pann_search_out {
                                            call pann_index_reserve_dropped() with a larger capacity and launch again. */
 #define PANN_STATUS_SHORT_FRONTIER 4u   /* pann_batch_search_rerank*: some query's frontier held fewer than k entries
                                            (beamSearch.h:416-419); its row is padded with 0xFFFFFFFF / +inf */
+#define PANN_STATUS_BAD_GROUP 8u        /* pann_batch_search_grouped_labeled_dev: some query's table index was >= npreds; its row
+                                           is padding and its result_count 0, the other queries' rows are valid */
 
 typedef struct pann_index pann_index;
 
@@ -861,6 +863,77 @@ int pann_bruteforce_knn_masked_grouped_dev(pann_index* idx, const void* d_querie
                                            const uint32_t* d_allow, uint64_t nrows, uint64_t allow_stride_words,
                                            const uint32_t* d_row_of_query, uint64_t max_list_ids, uint32_t* d_out_ids,
                                            float* d_out_dists, uint32_t* d_out_counts, void* stream);
+
+/* ---- entry points: the medoids of a table of filters, on the device (DESIGN.md "Entry points") ----  This project's own.
+ * Where a filtered search starts: for every filter of a table the points nearest to the centroid of what it allows, so that a
+ * tenant's queries begin in the tenant's region (the per-label entry points of FilteredDiskANN), and a dynamic index gets a live
+ * start after pann_vamana_delete_batch without a host round trip.  The table formats are exactly those of
+ * pann_bruteforce_knn_{labeled,masked}_grouped: G = npreds predicates of one kind over the handle's labels, or G = nrows bitmap
+ * rows allow_stride_words >= ceil(n / 32) apart (0 is allowed for one row); there is no index array.  allow == NULL with
+ * nrows == 1: every point -- the medoid of the index.
+ * THE RULE, for table entry g with allowed set A_g, c_g = |A_g|:
+ *   centroid[g][j] = (float)(S / (double)c_g), S = the sum over A_g of coordinate j widened exactly -- accumulated in 64-bit
+ *     integers for PANN_U8 / PANN_I8, in double for the three float types -- ONE double division, ONE rounding to f32; c_g == 0:
+ *     the row is all zeros.  out_centroids (optional): G x d floats.
+ *   the query row = the centroid converted to the handle's element type: f32 as it is; f16 and bf16 round to nearest even (NaN
+ *     -> 0x7FC0 in bf16); u8 / i8 rint (ties to even), clamped to the type's range.
+ *   row g of out_ids / out_dists (G x per_filter) is, bit for bit, what pann_bruteforce_knn_*_grouped returns for that query row
+ *     under filter g with k = per_filter: the min(per_filter, c_g) allowed points nearest to the centroid under the handle's
+ *     distance, sorted by (dist, id); out_counts[g] (optional) = min(per_filter, c_g); unused slots hold fill_id / +inf.  A caller
+ *     passes its ordinary start as fill_id and can use every row as a row of starts as it stands; 0xFFFFFFFF is plain padding.
+ *   The sums are exact for the one-byte types and for float data whose double sums are exact (integer-valued data, dyadic
+ *     grids).  On other float data the summation order is the implementation's -- a fixed one, without floating-point atomics:
+ *     the same call on the same handle gives the same bits ("centroid_piece_ids" of pann_index_get_option, a compile-time
+ *     constant that pann_index_set_option refuses, is the number of consecutive list ids one workgroup sums).
+ * max_list_ids chunks the work as in the grouped route and never changes a result on exactly-summable data.
+ * Status: per_filter in 1 .. 128 (0 -> PANN_ERR_BAD_ARG, above -> PANN_ERR_UNSUPPORTED); a four-bit handle ->
+ * PANN_ERR_UNSUPPORTED; everything else the grouped twins refuse keeps its code (no labels, an unknown kind, NULL or misaligned
+ * preds, a NULL bitmap with nrows != 1, NULL out_ids / out_dists, an empty table, a bitmap stride below ceil(n / 32) ->
+ * PANN_ERR_BAD_ARG).  Nothing is written on an error.
+ * Host pointers: the table goes up in one transfer, the outputs come back in one (HostTrip, as the twins). */
+int pann_filter_medoids_labeled(pann_index* idx, int kind, const pann_label_pred* preds, uint64_t npreds, uint32_t per_filter,
+                                uint32_t fill_id, uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts,
+                                float* out_centroids);
+int pann_filter_medoids_masked(pann_index* idx, const uint32_t* allow, uint64_t nrows, uint64_t allow_stride_words, uint32_t per_filter,
+                               uint32_t fill_id, uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts,
+                               float* out_centroids);
+/* Device pointers throughout, launched on `stream`.  SYNCHRONISES the stream ONCE, as the grouped route does (the allowed points
+ * per table entry come back and the host plans the chunks); scratch comes from the handle; one call per handle at a time. */
+int pann_filter_medoids_labeled_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t per_filter,
+                                    uint32_t fill_id, uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists,
+                                    uint32_t* d_out_counts, float* d_out_centroids, void* stream);
+int pann_filter_medoids_masked_dev(pann_index* idx, const uint32_t* d_allow, uint64_t nrows, uint64_t allow_stride_words,
+                                   uint32_t per_filter, uint32_t fill_id, uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists,
+                                   uint32_t* d_out_counts, float* d_out_centroids, void* stream);
+
+/* Grouped labeled search: many queries, few distinct predicates, and a row of starts per predicate -- the rows that
+ * pann_filter_medoids_labeled returns.  The table is `npreds` = G predicates of one kind, group_of_query (nq x uint32, each < G)
+ * names every query's entry; starts holds start_rows x nstarts ids, start_rows == 1 (one row for the batch) or G.
+ * THE RULE: row q of every output is what pann_batch_search_labeled returns for query q alone, with the ONE predicate
+ * preds[group_of_query[q]] and the shared starts row starts[(start_rows == 1 ? 0 : group_of_query[q]) * nstarts ..]; with
+ * steer != 0 the twin is pann_batch_search_steered_labeled with this `fill`, and out_steer (optional, nq x 2) its counters.  A
+ * start that the filter disallows is treated as both twins treat it: it gets a distance and is no result.
+ * How: one kernel gathers every query's predicate and start row into the handle's scratch; the search kernels then run with one
+ * predicate and one start row per query.
+ * Status: everything the twin refuses keeps its code; start_rows not in {1, G}, a NULL index array, an empty table ->
+ * PANN_ERR_BAD_ARG.  Nothing is written on an error.  Host pointers: the table indices (each < G) and the starts (each < n) are
+ * checked on the host. */
+int pann_batch_search_grouped_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
+                                      uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, uint64_t start_rows,
+                                      const pann_query_params* qp, int kind, const pann_label_pred* preds, uint64_t npreds,
+                                      const uint32_t* group_of_query, const pann_search_out* out, uint32_t* out_result_count,
+                                      uint32_t* out_allowed_cmps, int steer, uint32_t fill, uint32_t* out_steer);
+/* Device pointers throughout, launched on `stream`; no sync, no alloc beyond the growth of the workspace and of the gather's
+ * scratch.  Nothing is read back, so a bad table index cannot be refused: a query whose index is >= G reads no table entry -- it
+ * gets a predicate that allows nothing and start row 0, its ids row is padding, its result_count 0, and PANN_STATUS_BAD_GROUP is
+ * raised in d_out->status (when given); the other queries' rows are what they would have been.  The start ids are NOT validated
+ * (the _dev convention): a start >= n is gathered unchecked. */
+int pann_batch_search_grouped_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                          uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, uint64_t start_rows,
+                                          const pann_query_params* qp, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                                          const uint32_t* d_group_of_query, const pann_search_out* d_out,
+                                          uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, int steer, uint32_t fill,
+                                          uint32_t* d_out_steer, void* stream);
 
 /* ---- subset index: carve out, compact or grow a handle on the device (DESIGN.md "Subset index") ----  This project's own.
  * A new handle over the rows of src that a bitmap keeps, in ascending id order, with room for n_out rows; the graph is

@@ -25,7 +25,7 @@ PANN_OK = 0
 PANN_ERR_BAD_ARG, PANN_ERR_UNSUPPORTED = 1, 4
 PANN_ERR_OVERFLOW = 5
 PANN_ABI_VERSION = 3
-PANN_STATUS_VISITED_OVERFLOW, PANN_STATUS_DROPPED_OVERFLOW, PANN_STATUS_SHORT_FRONTIER = 1, 2, 4
+PANN_STATUS_VISITED_OVERFLOW, PANN_STATUS_DROPPED_OVERFLOW, PANN_STATUS_SHORT_FRONTIER, PANN_STATUS_BAD_GROUP = 1, 2, 4, 8
 
 u32p = C.POINTER(C.c_uint32)
 u64p = C.POINTER(C.c_uint64)
@@ -265,6 +265,21 @@ SIGNATURES = {
     "pann_bruteforce_knn_masked_grouped_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
                                                          C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                                          C.c_void_p, C.c_void_p]),
+    "pann_batch_search_grouped_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                    C.c_uint64, C.POINTER(QueryParams), C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                    C.POINTER(SearchOut), C.c_void_p, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]),
+    "pann_batch_search_grouped_labeled_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p,
+                                                        C.c_uint32, C.c_uint64, C.POINTER(QueryParams), C.c_int, C.c_void_p, C.c_uint64,
+                                                        C.c_void_p, C.POINTER(SearchOut), C.c_void_p, C.c_void_p, C.c_int, C.c_uint32,
+                                                        C.c_void_p, C.c_void_p]),
+    "pann_filter_medoids_labeled": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_filter_medoids_labeled_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_filter_medoids_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_filter_medoids_masked_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pann_index_create_subset_dev": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,
                                                C.c_uint64, C.c_void_p, u64p]),
     "pann_index_create_subset": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p,

@@ -84,6 +84,8 @@ struct pann_index {
   // counts; a chunk's query slab and staged results; the read-back and the plan on the host
   Workspace grp_sort, grp_plan, grp_rows, grp_io;
   PinnedBuf grp_pin;
+  Workspace grp_cen;            // pann_filter_medoids_*: a chunk's piece offsets and per-piece sums (entry_points.hip)
+  Workspace grp_search;         // pann_batch_search_grouped_labeled*: every query's predicate and start row, gathered (entry_points.hip)
 };
 
 namespace {
@@ -195,12 +197,12 @@ int filter_checks(const pann_index* owner, const char* fn, const PointFilter& F,
   if (!F.is_table() && F.count != 1 && F.count != nq) { set_error(f + ": npreds must be 1 (one predicate for the batch) or nq"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
 }
-int table_checks(const pann_index* owner, const char* fn, const PointFilter& F) {
+int table_checks(const pann_index* owner, const char* fn, const PointFilter& F, bool indexed = true) {      // indexed: by an array of the caller's
   const std::string f = fn;
   const uint64_t words = PointFilter::row_words(owner->ix.n);
   if (F.count == 0) { set_error(f + ": an empty filter table"); return PANN_ERR_BAD_ARG; }
   if (F.count > 0xFFFFFFFFull) { set_error(f + ": more than 2^32 - 1 table entries"); return PANN_ERR_BAD_ARG; }
-  if (!F.group) { set_error(f + ": null index array"); return PANN_ERR_BAD_ARG; }
+  if (indexed && !F.group) { set_error(f + ": null index array"); return PANN_ERR_BAD_ARG; }
   if (F.mode == MASK_BITMAP && F.stride < words && !(F.stride == 0 && F.count == 1)) {
     set_error(f + ": allow_stride_words must be at least ceil(n / 32) = " + std::to_string(words));
     return PANN_ERR_BAD_ARG;
@@ -491,6 +493,7 @@ void pann_index_destroy(pann_index* idx) {
   idx->code_rank.release(); idx->code_rows.release(); idx->cell_buf.release();
   idx->sketch_buf.release(); idx->labels_buf.release(); idx->label_row.release();
   idx->grp_sort.release(); idx->grp_plan.release(); idx->grp_rows.release(); idx->grp_io.release(); idx->grp_pin.release();
+  idx->grp_cen.release(); idx->grp_search.release();
   if (idx->own_stream) (void)hipStreamDestroy(idx->own_stream);
   delete idx;
 }
@@ -551,6 +554,7 @@ int64_t pann_index_get_option(const pann_index* idx, const char* name) {
   if (nm == "b64_seen") return idx->ix.b64_seen;
   if (nm == "locality_order") return idx->ix.cell ? 1 : 0;
   if (nm == "filter_codes") return idx->ix.codes_valid ? 1 : 0;         // are the class codes in step with the graph right now?
+  if (nm == "centroid_piece_ids") return CENTROID_PIECE_IDS;            // compile-time, not settable: list ids one workgroup of pann_filter_medoids_* sums
   if (nm == "pinned_bytes") return (int64_t)(idx->pin_in.bytes + idx->pin_out.bytes);   // pinned host memory the handle holds (HostTrip)
   return -1;
 }
@@ -622,6 +626,33 @@ static int masked_search_checks(const pann_index* idx, const PointFilter& F, uin
 // the steered form of a masked call (DESIGN.md "Steered masked search"): fill, and the optional nq x 2 counters (host or device, as the call)
 struct SteerReq { uint32_t fill; uint32_t* out; };
 
+// The grouped labeled search (DESIGN.md "Entry points"): a table of G predicates, one table index per query and 1 or G rows of
+// starts.  The refusals of its own, behind the filter's; then every query's predicate and start row are gathered into the handle's
+// scratch and the search runs as one with a predicate and a start row per query.
+struct GroupedSearch { uint32_t start_rows; };
+struct GatheredRows { const pann_label_pred* preds; const uint32_t* starts; const uint32_t* flag; };      // flag: a table index was >= G
+
+static int grouped_search_checks(const pann_index* idx, const char* fn, const PointFilter& T, uint64_t start_rows) {
+  if (int rc = table_checks(idx, fn, T)) return rc;
+  if (start_rows != 1 && start_rows != T.count) {
+    set_error(std::string(fn) + ": start_rows must be 1 (one row of starts for the batch) or npreds (one per table entry)");
+    return PANN_ERR_BAD_ARG;
+  }
+  return PANN_OK;
+}
+
+// T: the table on the device (preds, kind, group, count); d_starts: start_rows x nstarts
+static int gather_group_rows(pann_index* idx, const PointFilter& T, uint64_t nq, const uint32_t* d_starts, uint32_t nstarts, uint32_t start_rows,
+                             GatheredRows* out, hipStream_t st) {
+  const size_t o_starts = (size_t)nq * sizeof(pann_label_pred), o_flag = (o_starts + (size_t)nq * nstarts * 4 + 7) & ~(size_t)7;
+  if (int rc = idx->grp_search.ensure(o_flag + 8)) return rc;
+  uint8_t* w = idx->grp_search.as<uint8_t>();
+  pann_label_pred* d_preds = (pann_label_pred*)w;
+  uint32_t* d_rows = (uint32_t*)(w + o_starts), *d_flag = (uint32_t*)(w + o_flag);
+  *out = GatheredRows{d_preds, d_rows, d_flag};
+  return group_rows_dev(T.preds, (uint32_t)T.count, T.kind, T.group, nq, d_starts, nstarts, start_rows, d_preds, d_rows, d_flag, st);
+}
+
 static int search_common_checks(pann_index* idx, uint64_t nq, const pann_query_params* qp, const pann_search_out* out) {
   if (int rc = check_idx(idx, "pann_batch_search")) return rc;
   if (!qp || !out) { set_error("pann_batch_search: null params/out"); return PANN_ERR_BAD_ARG; }
@@ -630,21 +661,29 @@ static int search_common_checks(pann_index* idx, uint64_t nq, const pann_query_p
   return PANN_OK;
 }
 
-static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids,
-                                 uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
-                                 uint32_t nstarts, const pann_query_params* qp,
-                                 const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
-                                 uint64_t sq_stride, uint32_t* d_pruned, const PointFilter* points = nullptr,
-                                 uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr, const SteerReq* steer = nullptr) {
+// what a device-pointer search refuses before anything is enqueued
+static int batch_search_dev_checks(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
+                                   const pann_query_params* qp, const pann_search_out* d_out, int filter, const PointFilter* points) {
   if (int rc = search_common_checks(idx, nq, qp, d_out)) return rc;
   if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, d_out)) return rc; }
   if (filter) { if (int rc = refuse_4bit(idx, "pann_batch_search_filtered_dev")) return rc; }
   if (!d_starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if (d_queries && q_stride_bytes < idx->ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids,
+                                 uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
+                                 uint32_t nstarts, const pann_query_params* qp,
+                                 const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
+                                 uint64_t sq_stride, uint32_t* d_pruned, const PointFilter* points = nullptr,
+                                 uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr, const SteerReq* steer = nullptr,
+                                 int per_query = 0, bool checked = false) {      // checked: the caller has been through batch_search_dev_checks
+  if (!checked) { if (int rc = batch_search_dev_checks(idx, d_queries, nq, q_stride_bytes, d_starts, qp, d_out, filter, points)) return rc; }
   DeviceGuard g(idx->device);
   SearchArgs a;
   a.queries = (const uint8_t*)d_queries; a.qstride = q_stride_bytes; a.query_ids = d_query_ids;
-  a.nq = nq; a.starts = d_starts; a.nstarts = nstarts;
+  a.nq = nq; a.starts = d_starts; a.nstarts = nstarts; a.starts_per_query = per_query;
   fill_search_params(a, qp);
   a.dcap = idx->dcap;
   a.out = *d_out;
@@ -712,6 +751,28 @@ int pann_batch_search_steered_labeled_dev(pann_index* idx, const void* d_queries
   const SteerReq S{fill, d_out_steer};
   return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
                                d_out_result_count, d_out_allowed_cmps, &S);
+}
+
+int pann_batch_search_grouped_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
+                                          uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, uint64_t start_rows,
+                                          const pann_query_params* qp, int kind, const pann_label_pred* d_preds, uint64_t npreds,
+                                          const uint32_t* d_group_of_query, const pann_search_out* d_out, uint32_t* d_out_result_count,
+                                          uint32_t* d_out_allowed_cmps, int steer, uint32_t fill, uint32_t* d_out_steer, void* stream) {
+  const char* fn = "pann_batch_search_grouped_labeled_dev";
+  if (int rc = check_idx(idx, fn)) return rc;
+  const PointFilter T = label_filter(idx, kind, d_preds, npreds, true).as_table(d_group_of_query, npreds);
+  if (int rc = filter_checks(idx, fn, T, nq)) return rc;
+  if (int rc = grouped_search_checks(idx, fn, T, start_rows)) return rc;
+  // what the twin refuses before it launches, once, before the gather reads the starts
+  if (int rc = batch_search_dev_checks(idx, d_queries, nq, q_stride_bytes, d_starts, qp, d_out, 0, &T)) return rc;
+  DeviceGuard g(idx->device);
+  GatheredRows rows;
+  if (int rc = gather_group_rows(idx, T, nq, d_starts, nstarts, (uint32_t)start_rows, &rows, (hipStream_t)stream)) return rc;
+  const PointFilter F = label_filter(idx, kind, rows.preds, nq, true);
+  const SteerReq S{fill, d_out_steer};
+  if (int rc = batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, rows.starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr,
+                                     &F, d_out_result_count, d_out_allowed_cmps, steer ? &S : nullptr, 1, true)) return rc;
+  return d_out->status ? raise_status_dev(rows.flag, PANN_STATUS_BAD_GROUP, d_out->status, (hipStream_t)stream) : PANN_OK;
 }
 
 }  // extern "C"
@@ -842,7 +903,9 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
                              const pann_query_params* qp, const pann_search_out* out, int filter = 0,
                              const void* sketch_queries = nullptr, uint64_t sq_stride = 0, uint32_t* out_pruned = nullptr,
                              const PointFilter* points = nullptr, uint32_t* result_count = nullptr, uint32_t* allowed_cmps = nullptr,
-                             const SteerReq* steer = nullptr) {
+                             const SteerReq* steer = nullptr, const GroupedSearch* grouped = nullptr) {
+  // grouped (points: the table of predicates, its index array one entry per query; starts: start_rows x nstarts): the predicates and
+  // start rows are gathered per query on the device, and from there on the call is one with per-query predicates and starts
   if (int rc = search_common_checks(idx, nq, qp, out)) return rc;
   if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, out)) return rc; }
   uint32_t sk_row = 0;
@@ -857,9 +920,15 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   }
   if (!starts || nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if ((queries == nullptr) == (query_ids == nullptr)) { set_error("pann_batch_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
-  const uint64_t nst_total = per_query ? nq * nstarts : nstarts;
+  const uint64_t nst_total = grouped ? (uint64_t)grouped->start_rows * nstarts : per_query ? nq * nstarts : nstarts;
   for (uint64_t i = 0; i < nst_total; i++)
     if (starts[i] >= idx->ix.n) { set_error("pann_batch_search: start point out of range"); return PANN_ERR_BAD_ARG; }
+  for (uint64_t q = 0; grouped && q < nq; q++)
+    if (points->group[q] >= points->count) {
+      set_error("pann_batch_search_grouped_labeled: table index " + std::to_string(points->group[q]) + " of query " + std::to_string(q) +
+                " is out of range (>= " + std::to_string(points->count) + ")");
+      return PANN_ERR_BAD_ARG;
+    }
   if (query_ids)
     for (uint64_t i = 0; i < nq; i++)
       if (query_ids[i] >= idx->ix.n) { set_error("pann_batch_search: query id out of range"); return PANN_ERR_BAD_ARG; }
@@ -887,7 +956,13 @@ static int batch_search_host(pann_index* idx, const void* queries, const uint32_
   const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
   const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
   const uint32_t* d_starts = t.din<uint32_t>(i_st);
-  const PointFilter d_filter = staged.on_device(t);
+  PointFilter d_filter = staged.on_device(t);
+  if (grouped) {
+    GatheredRows rows;
+    if (int rc = gather_group_rows(idx, d_filter, nq, d_starts, nstarts, grouped->start_rows, &rows, st)) return rc;
+    d_starts = rows.starts; per_query = 1;
+    d_filter = label_filter(idx, d_filter.kind, rows.preds, nq, true);
+  }
   const uint8_t* d_sk = filter ? t.din<uint8_t>(i_sk) : nullptr;
   uint32_t status = 0;
   if (int rc = t.run_grown(nq, qp, "pann_batch_search", &status,
@@ -980,6 +1055,21 @@ int pann_batch_search_steered_labeled(pann_index* idx, const void* queries, cons
   const SteerReq S{fill, out_steer};
   return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
                            out_allowed_cmps, &S);
+}
+
+int pann_batch_search_grouped_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq, uint64_t q_stride_bytes,
+                                      const uint32_t* starts, uint32_t nstarts, uint64_t start_rows, const pann_query_params* qp, int kind,
+                                      const pann_label_pred* preds, uint64_t npreds, const uint32_t* group_of_query, const pann_search_out* out,
+                                      uint32_t* out_result_count, uint32_t* out_allowed_cmps, int steer, uint32_t fill, uint32_t* out_steer) {
+  const char* fn = "pann_batch_search_grouped_labeled";
+  if (int rc = check_idx(idx, fn)) return rc;
+  const PointFilter T = label_filter(idx, kind, preds, npreds, false).as_table(group_of_query, npreds);
+  if (int rc = filter_checks(idx, fn, T, nq)) return rc;
+  if (int rc = grouped_search_checks(idx, fn, T, start_rows)) return rc;
+  const SteerReq S{fill, out_steer};
+  const GroupedSearch grouped{(uint32_t)start_rows};
+  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &T, out_result_count,
+                           out_allowed_cmps, steer ? &S : nullptr, &grouped);
 }
 
 int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
@@ -1417,10 +1507,16 @@ static int labeled_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uin
 
 // ---- exact kNN by predicate group (masked_knn.hip, DESIGN.md "Exact kNN by predicate group") ----
 
+// the medoid form of the grouped route (pann_filter_medoids_*): ONE query per table entry, the entry's centroid, made on the device from
+// the entry's id list instead of gathered from the caller's queries; d_centroids (optional): G x d floats
+struct CentroidReq { float* d_centroids; };
+
 // A table of filters.  SYNCHRONISES st once: the flag of the range check, the queries per table entry and the allowed points per
 // table entry come back in one read, and the chunks, segments and tiles are planned from them (grouped_plan.h).
+// cen != null: nq == T.count, d_q and T.group are not read -- query g belongs to entry g and is that entry's centroid.
 static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
-                           const PointFilter& T, uint64_t max_list_ids, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+                           const PointFilter& T, uint64_t max_list_ids, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st,
+                           const CentroidReq* cen = nullptr) {
   const DeviceIndex& ix = idx->ix;
   const uint64_t G = T.count, words = PointFilter::row_words(ix.n), stride = T.stride ? T.stride : words;
   const bool lab = T.mode == MASK_LABELS;
@@ -1428,10 +1524,12 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
   uint32_t nblocks; uint64_t per_block;
   group_sort_shape(nq, G, &nblocks, &per_block);
   const size_t head_words = 1 + 2 * (size_t)G;       // flag | queries per entry | allowed points per entry
-  if (int rc = idx->grp_sort.ensure((head_words + (size_t)G + 1 + (size_t)nblocks * G + (size_t)nq) * 4)) return rc;
+  if (int rc = idx->grp_sort.ensure((head_words + (size_t)G + 1 + (size_t)nblocks * G + (size_t)nq + (cen ? (size_t)nq : 0)) * 4)) return rc;
   uint32_t* d_head = idx->grp_sort.as<uint32_t>();
   uint32_t* d_hist = d_head + 1, *d_allowed = d_hist + G, *d_off = d_allowed + G, *d_part = d_off + G + 1, *d_perm = d_part + (size_t)nblocks * G;
-  if (int rc = group_queries_dev(T.group, nq, G, d_head, d_hist, d_off, d_part, d_perm, st)) return rc;
+  const uint32_t* d_group = T.group;
+  if (cen) { if (int rc = subset_iota_dev(d_perm + nq, nullptr, nq, st)) return rc; d_group = d_perm + nq; }
+  if (int rc = group_queries_dev(d_group, nq, G, d_head, d_hist, d_off, d_part, d_perm, st)) return rc;
   if (lab) { if (int rc = label_count_dev(T.labels, ix.n, T.kind, T.preds, G, d_allowed, st)) return rc; }
   else if (int rc = allow_count_dev(T.allow, ix.n, G, stride, d_allowed, st)) return rc;
   if (int rc = idx->grp_pin.ensure(head_words * 4)) return rc;
@@ -1454,6 +1552,12 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
   const size_t o_bc = lab ? (plan.max_rows * words * 4 + 255) & ~(size_t)255 : 0;
   if (int rc = idx->grp_rows.ensure(o_bc + allow_rows_compact_scratch_bytes(ix.n, plan.max_rows))) return rc;
   if (int rc = idx->ws4.ensure(std::max<size_t>(plan.max_ids, 1) * 4)) return rc;
+  if (cen) {      // the pieces of every chunk's lists and the room for their sums (grouped_plan.h)
+    size_t need = 0;
+    for (const GroupedChunk& c : plan.chunks)
+      need = std::max(need, CentroidScratch(c.u1 - c.u0, centroid_chunk_pieces(plan, c, allowed), centroid_row_sums(ix.dbytes, ix.esize)).bytes);
+    if (int rc = idx->grp_cen.ensure(need)) return rc;
+  }
   const size_t o_sids = (plan.max_na * a_stride + kQuerySlack + 255) & ~(size_t)255, o_sdists = o_sids + ((plan.max_na * k * 4 + 255) & ~(size_t)255);
   if (int rc = idx->grp_io.ensure(o_sdists + plan.max_na * k * 4)) return rc;
   uint8_t* dp = idx->grp_plan.as<uint8_t>();
@@ -1474,7 +1578,10 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
         if (int rc = allow_rows_compact_dev(d_rows, ix.n, nullptr, words, S, d_bc, d_list, (uint32_t)c.ids, st)) return rc;
       } else if (int rc = allow_rows_compact_dev(T.allow, ix.n, d_used + c.u0, stride, S, d_bc, d_list, (uint32_t)c.ids, st)) return rc;
     }
-    if (int rc = gather_query_rows_dev(d_q, q_stride_bytes, ix.dbytes, d_perm + c.a_base, c.na, d_slab, a_stride, st)) return rc;
+    if (cen) {      // one query per entry: slab row s is the centroid of list s
+      if (int rc = centroid_rows_dev(ix, st, d_list, (const uint64_t*)(dp + c.o_boff), S, centroid_chunk_pieces(plan, c, allowed), idx->grp_cen.buf, d_perm + c.a_base, d_slab,
+                                     a_stride, cen->d_centroids)) return rc;
+    } else if (int rc = gather_query_rows_dev(d_q, q_stride_bytes, ix.dbytes, d_perm + c.a_base, c.na, d_slab, a_stride, st)) return rc;
     // the lists as B rows: the LDS-list kernels, one workgroup per CU (as masked_knn_run); the pieces cut every segment's list
     DenseTopkCall call;
     call.a_ext = d_slab; call.a_stride = a_stride; call.b_ids = d_list;
@@ -1618,6 +1725,103 @@ int pann_bruteforce_knn_masked_grouped(pann_index* idx, const void* queries, uin
   return filtered_knn_host(idx, "pann_bruteforce_knn_masked_grouped", queries, nq, q_stride_bytes, k,
                            PointFilter::bitmap(allow, allow_stride_words, nq, false).as_table(row_of_query, nrows), max_list_ids, out_ids, out_dists,
                            out_counts);
+}
+
+}  // extern "C"
+
+// ---- entry points: the medoids of a table of filters (entry_points.hip, DESIGN.md "Entry points") ----
+
+// the table of a medoid call: the G filters themselves, no index array; a NULL bitmap with one row is "every point"
+static bool medoid_all_points(const PointFilter& F) { return F.mode == MASK_BITMAP && !F.allow && F.count == 1; }
+static PointFilter medoid_bitmap_table(const uint32_t* allow, uint64_t nrows, uint64_t stride, bool dev) {
+  PointFilter f = PointFilter::bitmap(allow, stride, nrows, dev);
+  f.count = nrows;
+  return f;
+}
+
+// what the grouped twins refuse, in their order: the handle, the outputs, the filter, per_filter as their k, the table
+static int filter_medoids_checks(const pann_index* idx, const char* fn, const PointFilter& F, uint32_t per_filter, const uint32_t* out_ids,
+                                 const float* out_dists) {
+  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (!out_ids || !out_dists) { set_error(std::string(fn) + ": null argument"); return PANN_ERR_BAD_ARG; }
+  if (!medoid_all_points(F)) { if (int rc = filter_checks(idx, fn, F, F.count)) return rc; }
+  if (per_filter == 0) { set_error(std::string(fn) + ": per_filter == 0"); return PANN_ERR_BAD_ARG; }
+  if (per_filter > 128) { set_error(std::string(fn) + ": per_filter > 128 is not supported"); return PANN_ERR_UNSUPPORTED; }
+  return table_checks(idx, fn, F, false);
+}
+
+// T: the table on the device.  The grouped route with one query per entry, made there; then the padding takes the caller's id.
+static int filter_medoids_run(pann_index* idx, const char* fn, PointFilter T, uint32_t per_filter, uint32_t fill_id, uint64_t max_list_ids,
+                              uint32_t* d_ids, float* d_dists, uint32_t* d_counts, float* d_centroids, hipStream_t st) {
+  if (medoid_all_points(T)) {      // one row of all ones (bits at positions >= n are ignored)
+    const size_t row = (size_t)PointFilter::row_words(idx->ix.n) * 4;
+    if (int rc = idx->label_row.ensure(row)) return rc;
+    PANN_HIP(hipMemsetAsync(idx->label_row.buf, 0xFF, row, st));
+    T.allow = idx->label_row.as<uint32_t>(); T.stride = 0;
+  }
+  const CentroidReq cen{d_centroids};
+  if (int rc = grouped_knn_run(idx, fn, nullptr, T.count, 0, per_filter, T.as_table(nullptr, T.count), max_list_ids, d_ids, d_dists, d_counts, st,
+                               &cen)) return rc;
+  return pad_fill_dev(d_ids, T.count * per_filter, fill_id, st);
+}
+
+static int filter_medoids_dev(pann_index* idx, const char* fn, const PointFilter& F, uint32_t per_filter, uint32_t fill_id, uint64_t max_list_ids,
+                              uint32_t* d_ids, float* d_dists, uint32_t* d_counts, float* d_centroids, void* stream) {
+  if (int rc = filter_medoids_checks(idx, fn, F, per_filter, d_ids, d_dists)) return rc;
+  DeviceGuard g(idx->device);
+  return filter_medoids_run(idx, fn, F, per_filter, fill_id, max_list_ids, d_ids, d_dists, d_counts, d_centroids, (hipStream_t)stream);
+}
+
+static int filter_medoids_host(pann_index* idx, const char* fn, const PointFilter& F, uint32_t per_filter, uint32_t fill_id, uint64_t max_list_ids,
+                               uint32_t* out_ids, float* out_dists, uint32_t* out_counts, float* out_centroids) {
+  if (int rc = filter_medoids_checks(idx, fn, F, per_filter, out_ids, out_dists)) return rc;
+  DeviceGuard g(idx->device);
+  const uint64_t G = F.count;
+  HostTrip t(idx);
+  const bool all = medoid_all_points(F);
+  const StagedFilter staged(t, all ? nullptr : &F, idx->ix.n, G);
+  const size_t row_bytes = (size_t)G * per_filter * 4;
+  const int o_counts = t.out.add(out_counts, G * 4), o_ids = t.out.add(out_ids, row_bytes), o_dists = t.out.add(out_dists, row_bytes);
+  const int o_cen = t.out.add(out_centroids, (size_t)G * idx->ix.d * 4);
+  if (int rc = t.begin()) return rc;
+  PointFilter T = all ? F : staged.on_device(t);
+  T.dev = true; T.count = G;
+  if (int rc = filter_medoids_run(idx, fn, T, per_filter, fill_id, max_list_ids, t.dout<uint32_t>(o_ids), t.dout<float>(o_dists),
+                                  t.dout<uint32_t>(o_counts), t.dout<float>(o_cen), t.st)) return rc;
+  return t.finish();
+}
+
+extern "C" {
+
+int pann_filter_medoids_labeled_dev(pann_index* idx, int kind, const pann_label_pred* d_preds, uint64_t npreds, uint32_t per_filter,
+                                    uint32_t fill_id, uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                    float* d_out_centroids, void* stream) {
+  PointFilter F = label_filter(idx, kind, d_preds, npreds, true);
+  F.count = npreds;
+  return filter_medoids_dev(idx, "pann_filter_medoids_labeled_dev", F, per_filter, fill_id, max_list_ids, d_out_ids, d_out_dists, d_out_counts,
+                            d_out_centroids, stream);
+}
+
+int pann_filter_medoids_masked_dev(pann_index* idx, const uint32_t* d_allow, uint64_t nrows, uint64_t allow_stride_words, uint32_t per_filter,
+                                   uint32_t fill_id, uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts,
+                                   float* d_out_centroids, void* stream) {
+  return filter_medoids_dev(idx, "pann_filter_medoids_masked_dev", medoid_bitmap_table(d_allow, nrows, allow_stride_words, true), per_filter,
+                            fill_id, max_list_ids, d_out_ids, d_out_dists, d_out_counts, d_out_centroids, stream);
+}
+
+int pann_filter_medoids_labeled(pann_index* idx, int kind, const pann_label_pred* preds, uint64_t npreds, uint32_t per_filter, uint32_t fill_id,
+                                uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts, float* out_centroids) {
+  PointFilter F = label_filter(idx, kind, preds, npreds, false);
+  F.count = npreds;
+  return filter_medoids_host(idx, "pann_filter_medoids_labeled", F, per_filter, fill_id, max_list_ids, out_ids, out_dists, out_counts,
+                             out_centroids);
+}
+
+int pann_filter_medoids_masked(pann_index* idx, const uint32_t* allow, uint64_t nrows, uint64_t allow_stride_words, uint32_t per_filter,
+                               uint32_t fill_id, uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts,
+                               float* out_centroids) {
+  return filter_medoids_host(idx, "pann_filter_medoids_masked", medoid_bitmap_table(allow, nrows, allow_stride_words, false), per_filter, fill_id,
+                             max_list_ids, out_ids, out_dists, out_counts, out_centroids);
 }
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,

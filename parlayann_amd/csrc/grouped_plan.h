@@ -78,4 +78,25 @@ struct GroupedPlan {
   }
 };
 
+// ---- the medoid form of the grouped route (DESIGN.md "Entry points"): the lists of a chunk are cut into pieces of
+// CENTROID_PIECE_IDS consecutive ids, one workgroup sums one piece, and the sums wait in scratch for the finish pass.  The kernels
+// (entry_points.hip) count a list's pieces with the same function, so host and device agree on every offset.
+constexpr uint32_t CENTROID_PIECE_IDS = 512;      // pann_index_get_option("centroid_piece_ids")
+constexpr uint64_t centroid_pieces_of(uint64_t ids) { return (ids + CENTROID_PIECE_IDS - 1) / CENTROID_PIECE_IDS; }
+// the pieces of chunk c's lists
+inline uint64_t centroid_chunk_pieces(const GroupedPlan& p, const GroupedChunk& c, const uint32_t* allowed) {
+  uint64_t pieces = 0;
+  for (size_t u = c.u0; u < c.u1; u++) pieces += centroid_pieces_of(allowed[p.used[u]]);
+  return pieces;
+}
+// sums one piece leaves: the coordinates of the 16-byte chunks of a row that hold data (esize: bytes per element, 1, 2 or 4)
+constexpr uint32_t centroid_row_sums(uint32_t dbytes, uint32_t esize) { return (dbytes + 15) / 16 * (16 / esize); }
+// The scratch of a chunk of S lists: piece_off (S + 1 words: the pieces before every list, and their total) | 64-bit sums,
+// row_sums per piece, 256-byte aligned.
+struct CentroidScratch {
+  size_t o_partial, bytes;
+  CentroidScratch(uint64_t S, uint64_t pieces, uint32_t row_sums)
+      : o_partial((((size_t)S + 1) * 4 + 255) & ~(size_t)255), bytes(o_partial + (size_t)pieces * row_sums * 8) {}
+};
+
 }  // namespace pann

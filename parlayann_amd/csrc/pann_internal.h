@@ -273,6 +273,22 @@ int gather_query_rows_dev(const uint8_t* d_q, uint64_t q_stride, uint32_t dbytes
 int scatter_knn_rows_dev(const uint32_t* d_sids, const float* d_sdists, const uint32_t* d_perm, uint64_t rows, uint32_t k,
                          uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_counts, hipStream_t st);
 
+// entry_points.hip (DESIGN.md "Entry points"): the centroids of the S lists of a CSR (d_list, d_b_off: S + 1 offsets, as the grouped
+// route makes them) as query rows.  Row s of d_slab (slab_stride bytes apart, a multiple of 16) <- the centroid of list s converted to
+// the handle's element type, zero padded; d_centroids (optional): row d_entry[s] of d floats <- the centroid itself.  An empty list
+// gives zeros.  `pieces`: centroid_chunk_pieces of the lists; d_scratch: CentroidScratch(S, pieces, centroid_row_sums(ix.dbytes, ix.esize)).bytes
+// bytes, 256-byte aligned (grouped_plan.h).
+int centroid_rows_dev(const DeviceIndex& ix, hipStream_t st, const uint32_t* d_list, const uint64_t* d_b_off, uint32_t S, uint64_t pieces,
+                      void* d_scratch, const uint32_t* d_entry, uint8_t* d_slab, uint32_t slab_stride, float* d_centroids);
+// grouped labeled search: d_out_preds[q] = d_table[d_group[q]] and d_out_starts[q * nstarts ..] = row d_group[q] (row 0 with
+// start_rows == 1) of d_starts, q < nq.  A table index >= G reads no table: a predicate that allows nothing, start row 0, and
+// *d_flag (zeroed here) is raised.  raise_status_dev: *d_status |= bit if *d_flag.
+int group_rows_dev(const pann_label_pred* d_table, uint32_t G, int kind, const uint32_t* d_group, uint64_t nq, const uint32_t* d_starts,
+                   uint32_t nstarts, uint32_t start_rows, pann_label_pred* d_out_preds, uint32_t* d_out_starts, uint32_t* d_flag, hipStream_t st);
+int raise_status_dev(const uint32_t* d_flag, uint32_t bit, uint32_t* d_status, hipStream_t st);
+// every id of d_ids[0 .. count) that is padding (0xFFFFFFFF) <- fill_id
+int pad_fill_dev(uint32_t* d_ids, uint64_t count, uint32_t fill_id, hipStream_t st);
+
 // subset.hip: the kernels of pann_index_create_subset* (DESIGN.md "Subset index").  d_new_to_old: the m kept ids, ascending
 // (allow_compact_scatter_dev); every call is a no-op for m == 0 apart from the fill of subset_invert_dev.
 // d_a[r] = d_b[r] = r, r < m (either may be null): the two maps when everything is kept

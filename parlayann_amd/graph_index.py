@@ -154,6 +154,20 @@ class GraphIndex:
              index.batch_search_masked(queries, allow=allow, out_k=knn, **qp))
         return r["ids"], r["dists"]
 
+    def _medoid_walk(self, queries, knn, beam_width, visit_limit, where, steer):
+        """batch_search(where=, entry="medoid"): a composition, nothing more"""
+        queries = np.ascontiguousarray(queries, dtype=self.T)
+        flt = PointFilter.labeled(where)
+        if flt.shared:
+            table, group = flt.table(), np.zeros(len(queries), np.uint32)
+        else:
+            table, group = np.unique(flt.check(len(queries)).rows, axis=0, return_inverse=True)
+        table = (flt.kind, table)
+        starts = self.index.filter_medoids(where=table, per_filter=1, fill_id=0)["ids"]
+        r = self.index.batch_search_grouped(queries, where=table, group_of_query=np.asarray(group).reshape(-1), starts=starts, out_k=knn,
+                                            steer=steer, **self._qp(knn, beam_width, visit_limit))
+        return r["ids"], r["dists"]
+
     def _exact_or_walk(self, queries, knn, allow, where, exact_below, walk, grouped=False):
         """The rule of DESIGN.md "Exact masked kNN": a filter (allow= or where=, not both) with at most exact_below allowed
         points is answered exactly on the full-precision handle (DeviceIndex.bruteforce_knn_masked / _labeled), any other by
@@ -185,11 +199,20 @@ class GraphIndex:
         return ids, dists
 
     def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None,
-                     exact_grouped=False, steer=None):
+                     exact_grouped=False, steer=None, entry=None):
         """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned.
         where = (kind, preds): the same by a label predicate (DeviceIndex.batch_search_labeled); not together with allow.
         exact_below, exact_grouped (with allow or where): as batch_search_masked
-        steer (with allow or where, quant=False): the steered walk, DeviceIndex.batch_search_masked(steer=); None changes nothing"""
+        steer (with allow or where, quant=False): the steered walk, DeviceIndex.batch_search_masked(steer=); None changes nothing
+        entry (with where, quant=False, no exact_below): "medoid" starts every query at the medoid of what its predicate allows
+        (DESIGN.md "Entry points") -- the distinct predicates (np.unique), DeviceIndex.filter_medoids(per_filter=1, fill_id=0),
+        DeviceIndex.batch_search_grouped with those start rows, steer forwarded; None changes nothing"""
+        if entry is not None:
+            if entry != "medoid":
+                raise ValueError('entry is None or "medoid"')
+            if where is None or allow is not None or exact_below is not None or (quant and self.use_quantization):
+                raise ValueError('entry="medoid" goes with where=, quant=False and no exact_below')
+            return self._medoid_walk(queries, knn, beam_width, visit_limit, where, steer)
         if where is None and allow is None:
             return self._search(queries, knn, beam_width, quant, visit_limit, steer=steer)
         return self._exact_or_walk(queries, knn, allow, where, exact_below,

@@ -600,6 +600,26 @@ class DeviceIndex:
         return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
                                   flt=PointFilter.labeled(where).check(nq), steer=steer)
 
+    def batch_search_grouped(self, queries=None, where=None, group_of_query=None, k=10, beam=64, cut=1.35, limit=None,
+                             degree_limit=None, starts=(0,), query_ids=None, out_k=None, visited_cap=0, want_dists=True, steer=None):
+        """pann_batch_search_grouped_labeled: batch_search_labeled for many queries that share few predicates, with a row of
+        starts per predicate (DESIGN.md "Entry points").  where = (kind, preds[G, 2]) is a table, group_of_query (nq, each < G)
+        names every query's entry; starts: one row (nstarts,) for the batch or an array (G, nstarts), one row per table entry --
+        filter_medoids(where=..., fill_id=...)["ids"] as it stands.  Row q of every field is what batch_search_labeled returns
+        for query q alone under the ONE predicate preds[group_of_query[q]] from its entry's start row; steer as there."""
+        nq = len(queries) if queries is not None else len(query_ids)
+        flt = PointFilter.labeled(where)
+        table = PointFilter(np.ascontiguousarray(flt.table(), dtype=np.uint32), flt.kind, False)
+        if group_of_query is None:
+            raise ValueError("batch_search_grouped needs group_of_query, one table index per query")
+        group = np.asarray(group_of_query)
+        if group.shape != (nq,):
+            raise ValueError("group_of_query must hold one table index per query")
+        if nq and (group.min() < 0 or group.max() >= len(table.rows)):
+            raise ValueError("group_of_query: a table index is out of range")
+        return self._batch_search(queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
+                                  flt=table, steer=steer, group=np.ascontiguousarray(group.reshape(-1), dtype=np.uint32))
+
     def _query_rows(self, queries, query_ids):
         """queries or query_ids -> (query rows or None, uint32 ids or None, nq, row stride in bytes)"""
         if queries is not None:
@@ -620,9 +640,11 @@ class DeviceIndex:
         return _ptr(res["result_count"]), _ptr(res["allowed_cmps"])
 
     def _batch_search(self, queries, k, beam, cut, limit, degree_limit, starts, query_ids, out_k, visited_cap, want_dists,
-                      filtered=False, sketch_queries=None, flt=None, steer=None):
-        """One body for pann_batch_search{, _per_query_starts, _filtered, _masked, _labeled, _steered, _steered_labeled}: they
-        share (handle, queries, ids, nq, stride, [sketch rows, bytes,] starts, nstarts, params, [filter,] out, [extra outputs])."""
+                      filtered=False, sketch_queries=None, flt=None, steer=None, group=None):
+        """One body for pann_batch_search{, _per_query_starts, _filtered, _masked, _labeled, _steered, _steered_labeled,
+        _grouped_labeled}: they share (handle, queries, ids, nq, stride, [sketch rows, bytes,] starts, nstarts, [start rows,]
+        params, [filter, [table indices,]] out, [extra outputs]).  group: the table indices of a grouped call, whose flt is the
+        table and whose starts are one row or one row per table entry."""
         nq = len(queries) if queries is not None else len(query_ids)
         qp = self._qp(k, beam, cut, limit, degree_limit)
         out_k = k if out_k is None else out_k
@@ -643,13 +665,13 @@ class DeviceIndex:
                         visited_ids=_ptr(res["visited_ids"]), visited_dists=_ptr(res["visited_dists"]),
                         visited_cap=visited_cap, status=_ptr(res["status"]))
         starts = np.ascontiguousarray(starts, dtype=np.uint32)
-        per_query = starts.ndim == 2          # nq x nstarts: beamSearchRandom-style, one start set per query
+        per_query = starts.ndim == 2 and group is None          # nq x nstarts: beamSearchRandom-style, one start set per query
         if per_query and starts.shape[0] != nq:
             raise ValueError("per-query starts must be nq x nstarts")
         q, qid, _, stride = self._query_rows(queries, query_ids)
         if per_query and (filtered or flt is not None):
             raise ValueError(f"{'filtered' if filtered else 'masked'} searches take shared starts")
-        name, sketch, mid, tail, counters = "pann_batch_search", (), (), (), None
+        name, sketch, mid, tail, counters, start_rows = "pann_batch_search", (), (), (), None, ()
         if filtered:
             sq = None
             if sketch_queries is not None:
@@ -663,16 +685,24 @@ class DeviceIndex:
                 fill = int(steer)
                 if fill < 0 or fill > 0xFFFFFFFF:
                     raise ValueError("steer is the fill count: 0 (the degree bound) or a positive integer")
-            mid, tail = flt.check(nq).args(), self._filter_counters(res, nq)
-            if steer is None:
-                name += "_" + flt.infix
-            else:
+            if steer is not None:
                 counters = np.empty((nq, 2), dtype=np.uint32)
-                name, tail = name + "_steered" + ("" if flt.kind is None else "_labeled"), tail + (fill, _ptr(counters))
+            if group is not None:      # flt is the table: steer is a flag of the one symbol
+                if starts.ndim == 2 and starts.shape[0] != len(flt.rows):
+                    raise ValueError("starts must be one row, or one row per table entry")
+                start_rows, mid = (1 if starts.ndim == 1 else len(starts),), flt.args() + (_ptr(group),)
+                tail = self._filter_counters(res, nq) + ((0, 0, None) if steer is None else (1, fill, _ptr(counters)))
+                name += "_grouped_labeled"
+            else:
+                mid, tail = flt.check(nq).args(), self._filter_counters(res, nq)
+                if steer is None:
+                    name += "_" + flt.infix
+                else:
+                    name, tail = name + "_steered" + ("" if flt.kind is None else "_labeled"), tail + (fill, _ptr(counters))
         elif per_query:
             name += "_per_query_starts"
-        check(getattr(self._lib, name)(self._h, _ptr(q), _ptr(qid), nq, stride, *sketch, _ptr(starts), starts.shape[-1], C.byref(qp), *mid,
-                                       C.byref(out), *tail))
+        check(getattr(self._lib, name)(self._h, _ptr(q), _ptr(qid), nq, stride, *sketch, _ptr(starts), starts.shape[-1], *start_rows,
+                                       C.byref(qp), *mid, C.byref(out), *tail))
         if counters is not None:
             res["bridge_rows"], res["hop2_cmps"] = counters[:, 0].copy(), counters[:, 1].copy()
         return res
@@ -1019,6 +1049,37 @@ class DeviceIndex:
         fn, outs = getattr(self._lib, f"pann_bruteforce_knn_{flt.infix}_grouped"), _knn_out(nq, k)
         check(fn(self._h, _ptr(q), nq, _row_stride(q), k, *table.args(table=True), _ptr(group), int(max_list_ids), *map(_ptr, outs)))
         return outs
+
+    # ---- entry points: where a filtered search starts (DESIGN.md "Entry points") ----
+    def filter_medoids(self, where=None, allow=None, per_filter=1, fill_id=0xFFFFFFFF, max_list_ids=0, centroids=False):
+        """pann_filter_medoids_labeled / _masked: for every filter of a table the per_filter (<= 128) allowed points nearest to
+        the centroid of what it allows, on the device.  where = (kind, preds[G, 2]) or allow rows (G, W) packed / (G, n) boolean
+        (one predicate or one row is a table of one); neither: every point, the medoid of the index.
+        Returns {"ids" uint32 (G, per_filter), "dists" float32 (G, per_filter), "counts" uint32 (G,)} and, with centroids=True,
+        "centroids" float32 (G, d).  Row g: min(per_filter, c_g) ids sorted by (dist, id), then fill_id / +inf -- with the
+        ordinary start as fill_id every row is a row of starts as it stands (batch_search_grouped)."""
+        flt = PointFilter.of(self.n, allow, where)
+        if flt is None:
+            infix, G, args = "masked", 1, (None, 1, 0)
+        else:
+            table = PointFilter(np.ascontiguousarray(flt.table(), dtype=np.uint32), flt.kind, False)
+            infix, G, args = flt.infix, len(table.rows), table.args(table=True)
+        E = int(per_filter)
+        res = {"ids": np.empty((G, E), np.uint32), "dists": np.empty((G, E), np.float32), "counts": np.empty(G, np.uint32)}
+        if centroids:
+            res["centroids"] = np.empty((G, self.d), np.float32)
+        check(getattr(self._lib, "pann_filter_medoids_" + infix)(self._h, *args, E, int(fill_id), int(max_list_ids), _ptr(res["ids"]),
+                                                                 _ptr(res["dists"]), _ptr(res["counts"]), _ptr(res.get("centroids"))))
+        return res
+
+    def medoid(self, consider=None):
+        """The point nearest to the centroid of the considered points -> int.  consider: what reachability takes (boolean (n,)
+        or one packed row), typically the live set after vamana_delete_batch; None: every point.  ValueError if nothing is
+        allowed."""
+        r = self.filter_medoids(allow=self._consider(consider))
+        if r["counts"][0] == 0:
+            raise ValueError("medoid: no point is considered")
+        return int(r["ids"][0, 0])
 
     def bruteforce_knn_masked_dev(self, d_queries_ptr, nq, q_stride_bytes, k, d_allow_ptr, allow_stride_words, d_ids_ptr,
                                   d_dists_ptr, d_counts_ptr=None, stream_ptr=None):
