@@ -210,10 +210,6 @@ int table_checks(const pann_index* owner, const char* fn, const PointFilter& F, 
   return PANN_OK;
 }
 
-void fill_search_params(SearchArgs& a, const pann_query_params* qp) {
-  a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
-}
-
 int upload_graph_rows(pann_index* idx, const uint32_t* h_rows, uint64_t m, const uint32_t* h_row_ids) {
   DeviceIndex& ix = idx->ix;
   if (m == 0) return PANN_OK;
@@ -614,119 +610,144 @@ int pann_index_get_graph(pann_index* idx, uint32_t* graph_out) {
 // batched beam search
 // ---------------------------------------------------------------------------------------------
 
-// the limits of the masked searches (the fused path comes through here too, out_k = its list length).  The bitmap's own checks lie
-// between them; a labeled call has been through filter_checks at its entry, ahead of the search's checks
-static int masked_search_checks(const pann_index* idx, const PointFilter& F, uint64_t nq, const pann_query_params* qp, const pann_search_out* out) {
-  if ((int64_t)out->out_k > qp->beam) { set_error("pann_batch_search_masked: out_k larger than the beam"); return PANN_ERR_BAD_ARG; }
+// Every search entry point fills a SearchCall (search_call.h) by field name and goes through batch_search_host or batch_search_dev.
+
+// the limits of a masked search with a result list of out_k entries (the fused path comes through here too, out_k = its list length).
+// The bitmap's own checks lie between them; a labeled call has been through filter_checks ahead of the search's checks
+static int masked_limits(const pann_index* idx, const PointFilter& F, uint64_t nq, const pann_query_params* qp, uint32_t out_k) {
+  if ((int64_t)out_k > qp->beam) { set_error("pann_batch_search_masked: out_k larger than the beam"); return PANN_ERR_BAD_ARG; }
   if (F.mode == MASK_BITMAP) { if (int rc = filter_checks(idx, "pann_batch_search_masked", F, nq)) return rc; }
-  if (out->out_k > 64) { set_error("pann_batch_search_masked: out_k > 64 is not supported"); return PANN_ERR_UNSUPPORTED; }
+  if (out_k > 64) { set_error("pann_batch_search_masked: out_k > 64 is not supported"); return PANN_ERR_UNSUPPORTED; }
   return PANN_OK;
 }
 
-// the steered form of a masked call (DESIGN.md "Steered masked search"): fill, and the optional nq x 2 counters (host or device, as the call)
-struct SteerReq { uint32_t fill; uint32_t* out; };
-
-// The grouped labeled search (DESIGN.md "Entry points"): a table of G predicates, one table index per query and 1 or G rows of
-// starts.  The refusals of its own, behind the filter's; then every query's predicate and start row are gathered into the handle's
-// scratch and the search runs as one with a predicate and a start row per query.
-struct GroupedSearch { uint32_t start_rows; };
-struct GatheredRows { const pann_label_pred* preds; const uint32_t* starts; const uint32_t* flag; };      // flag: a table index was >= G
-
-static int grouped_search_checks(const pann_index* idx, const char* fn, const PointFilter& T, uint64_t start_rows) {
-  if (int rc = table_checks(idx, fn, T)) return rc;
-  if (start_rows != 1 && start_rows != T.count) {
-    set_error(std::string(fn) + ": start_rows must be 1 (one row of starts for the batch) or npreds (one per table entry)");
-    return PANN_ERR_BAD_ARG;
+// What a search refuses before anything is staged or enqueued, in the order in which it is tested (tests/search_refusal_cases.py and
+// tests/filter_refusal_cases.py pin the order and the texts).  `fn`: the entry point; only the label filter's and the four-bit refusals
+// name it, everything else says pann_batch_search, pann_batch_search_masked or pann_batch_search_filtered (DESIGN.md lists these).
+// The head is one chain; the tails of the host and the device path differ: a host call can read its arrays, and tests the queries'
+// stride behind nq == 0 (batch_search_host); a device call leaves what it does not test here to the launcher (beam_search.hip).
+static int search_refusals(const pann_index* idx, const SearchCall& c, const char* fn) {
+  const PointFilter& F = c.filter;
+  if (F.mode == MASK_LABELS) {      // the predicates, and a grouped call's table and start rows
+    if (int rc = check_idx(idx, fn)) return rc;
+    if (int rc = filter_checks(idx, fn, F, c.nq)) return rc;
+    if (F.is_table()) {
+      if (int rc = table_checks(idx, fn, F)) return rc;
+      if (c.start_rows != 1 && c.start_rows != F.count) {
+        set_error(std::string(fn) + ": start_rows must be 1 (one row of starts for the batch) or npreds (one per table entry)");
+        return PANN_ERR_BAD_ARG;
+      }
+    }
   }
+  if (int rc = check_idx(idx, "pann_batch_search")) return rc;
+  if (!c.qp || !c.has_out) { set_error("pann_batch_search: null params/out"); return PANN_ERR_BAD_ARG; }
+  if (int rc = k_beam_check(c.qp)) return rc;
+  if (F.given()) { if (int rc = masked_limits(idx, F, c.nq, c.qp, c.out.out_k)) return rc; }
+  if (c.sketch) { if (int rc = refuse_4bit(idx, fn)) return rc; }
+  const uint64_t n = idx->ix.n;
+  if (c.dev) {
+    if (!c.starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
+    if (c.queries && c.qstride < idx->ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+    return PANN_OK;
+  }
+  if (c.sketch) {
+    if (!idx->ix.sketch) { set_error("pann_batch_search_filtered: no sketch attached to the index"); return PANN_ERR_BAD_ARG; }
+    if ((c.queries != nullptr) != (c.sketch_queries != nullptr)) {
+      set_error("pann_batch_search_filtered: sketch_queries go with queries, and only with them"); return PANN_ERR_BAD_ARG;
+    }
+    if (c.sketch_queries && c.sq_stride < sketch_row_bytes(idx->ix.sk_kind, idx->ix.d)) {
+      set_error("pann_batch_search_filtered: sketch query stride smaller than a sketch row"); return PANN_ERR_BAD_ARG;
+    }
+  }
+  if (!c.starts || c.nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
+  if ((c.queries == nullptr) == (c.query_ids == nullptr)) { set_error("pann_batch_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
+  for (uint64_t i = 0, m = c.start_count(); i < m; i++)
+    if (c.starts[i] >= n) { set_error("pann_batch_search: start point out of range"); return PANN_ERR_BAD_ARG; }
+  for (uint64_t q = 0; F.is_table() && q < c.nq; q++)
+    if (F.group[q] >= F.count) {
+      set_error("pann_batch_search_grouped_labeled: table index " + std::to_string(F.group[q]) + " of query " + std::to_string(q) +
+                " is out of range (>= " + std::to_string(F.count) + ")");
+      return PANN_ERR_BAD_ARG;
+    }
+  for (uint64_t i = 0; c.query_ids && i < c.nq; i++)
+    if (c.query_ids[i] >= n) { set_error("pann_batch_search: query id out of range"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
 }
 
-// T: the table on the device (preds, kind, group, count); d_starts: start_rows x nstarts
-static int gather_group_rows(pann_index* idx, const PointFilter& T, uint64_t nq, const uint32_t* d_starts, uint32_t nstarts, uint32_t start_rows,
-                             GatheredRows* out, hipStream_t st) {
-  const size_t o_starts = (size_t)nq * sizeof(pann_label_pred), o_flag = (o_starts + (size_t)nq * nstarts * 4 + 7) & ~(size_t)7;
+// The grouped labeled search (DESIGN.md "Entry points"): a table of G predicates, one table index per query and 1 or G rows of starts.
+// d: the request on the device, its filter the table.  Every query's predicate and start row are gathered into the handle's scratch
+// and d becomes a request with a predicate and a start row per query.  *flag (optional): the device word that is raised when a table
+// index was >= G.
+static int gather_group_rows(pann_index* idx, SearchCall& d, hipStream_t st, const uint32_t** flag) {
+  const PointFilter T = d.filter;
+  const size_t o_starts = (size_t)d.nq * sizeof(pann_label_pred), o_flag = (o_starts + (size_t)d.nq * d.nstarts * 4 + 7) & ~(size_t)7;
   if (int rc = idx->grp_search.ensure(o_flag + 8)) return rc;
   uint8_t* w = idx->grp_search.as<uint8_t>();
   pann_label_pred* d_preds = (pann_label_pred*)w;
   uint32_t* d_rows = (uint32_t*)(w + o_starts), *d_flag = (uint32_t*)(w + o_flag);
-  *out = GatheredRows{d_preds, d_rows, d_flag};
-  return group_rows_dev(T.preds, (uint32_t)T.count, T.kind, T.group, nq, d_starts, nstarts, start_rows, d_preds, d_rows, d_flag, st);
-}
-
-static int search_common_checks(pann_index* idx, uint64_t nq, const pann_query_params* qp, const pann_search_out* out) {
-  if (int rc = check_idx(idx, "pann_batch_search")) return rc;
-  if (!qp || !out) { set_error("pann_batch_search: null params/out"); return PANN_ERR_BAD_ARG; }
-  if (int rc = k_beam_check(qp)) return rc;
-  (void)nq;
+  if (int rc = group_rows_dev(T.preds, (uint32_t)T.count, T.kind, T.group, d.nq, d.starts, d.nstarts, (uint32_t)d.start_rows, d_preds, d_rows,
+                              d_flag, st)) return rc;
+  d.starts = d_rows; d.starts_layout = SearchCall::STARTS_PER_QUERY;
+  d.filter = label_filter(idx, T.kind, d_preds, d.nq, true);
+  if (flag) *flag = d_flag;
   return PANN_OK;
 }
 
-// what a device-pointer search refuses before anything is enqueued
-static int batch_search_dev_checks(pann_index* idx, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
-                                   const pann_query_params* qp, const pann_search_out* d_out, int filter, const PointFilter* points) {
-  if (int rc = search_common_checks(idx, nq, qp, d_out)) return rc;
-  if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, d_out)) return rc; }
-  if (filter) { if (int rc = refuse_4bit(idx, "pann_batch_search_filtered_dev")) return rc; }
-  if (!d_starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
-  if (d_queries && q_stride_bytes < idx->ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
-  return PANN_OK;
-}
-
-static int batch_search_dev_impl(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids,
-                                 uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
-                                 uint32_t nstarts, const pann_query_params* qp,
-                                 const pann_search_out* d_out, void* stream, int filter, const void* d_sketch_queries,
-                                 uint64_t sq_stride, uint32_t* d_pruned, const PointFilter* points = nullptr,
-                                 uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr, const SteerReq* steer = nullptr,
-                                 int per_query = 0, bool checked = false) {      // checked: the caller has been through batch_search_dev_checks
-  if (!checked) { if (int rc = batch_search_dev_checks(idx, d_queries, nq, q_stride_bytes, d_starts, qp, d_out, filter, points)) return rc; }
+// a device-pointer search: the whole batch in one launch on the caller's stream, with the handle's dropped-list capacity
+static int batch_search_dev(pann_index* idx, const SearchCall& c, const char* fn) {
+  if (int rc = search_refusals(idx, c, fn)) return rc;
   DeviceGuard g(idx->device);
-  SearchArgs a;
-  a.queries = (const uint8_t*)d_queries; a.qstride = q_stride_bytes; a.query_ids = d_query_ids;
-  a.nq = nq; a.starts = d_starts; a.nstarts = nstarts; a.starts_per_query = per_query;
-  fill_search_params(a, qp);
-  a.dcap = idx->dcap;
-  a.out = *d_out;
-  a.filter = filter; a.sketch_queries = (const uint8_t*)d_sketch_queries; a.sq_stride = sq_stride; a.pruned_cmps = d_pruned;
-  if (points) { points->apply(a); a.result_count = d_result_count; a.allowed_cmps = d_allowed_cmps; }
-  if (steer) { a.steer = 1; a.fill = steer->fill; a.steer_out = steer->out; }
+  hipStream_t st = (hipStream_t)c.stream;
+  SearchCall d = c;
+  const uint32_t* bad_group = nullptr;
+  if (c.filter.is_table()) { if (int rc = gather_group_rows(idx, d, st, &bad_group)) return rc; }
+  const SearchArgs a = slice(d, 0, d.nq, idx->dcap);
   if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
-  return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, (hipStream_t)stream);
+  if (int rc = launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
+  return bad_group && d.out.status ? raise_status_dev(bad_group, PANN_STATUS_BAD_GROUP, d.out.status, st) : PANN_OK;
 }
 
 int pann_batch_search_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids,
                           uint64_t nq, uint64_t q_stride_bytes, const uint32_t* d_starts,
                           uint32_t nstarts, const pann_query_params* qp,
                           const pann_search_out* d_out, void* stream) {
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr);
+  SearchCall c;
+  c.queries = d_queries; c.qstride = q_stride_bytes; c.query_ids = d_query_ids; c.nq = nq; c.starts = d_starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(d_out); c.dev = true; c.stream = stream;
+  return batch_search_dev(idx, c, "pann_batch_search_dev");
 }
 
 int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
                                    uint64_t q_stride_bytes, const void* d_sketch_queries, uint64_t sq_stride_bytes,
                                    const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
                                    const pann_search_out* d_out, uint32_t* d_out_pruned_cmps, void* stream) {
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 1, d_sketch_queries,
-                               sq_stride_bytes, d_out_pruned_cmps);
+  SearchCall c;
+  c.queries = d_queries; c.qstride = q_stride_bytes; c.query_ids = d_query_ids; c.nq = nq; c.starts = d_starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(d_out); c.dev = true; c.stream = stream;
+  c.sketch = true; c.sketch_queries = d_sketch_queries; c.sq_stride = sq_stride_bytes; c.pruned_cmps = d_out_pruned_cmps;
+  return batch_search_dev(idx, c, "pann_batch_search_filtered_dev");
 }
 
 int pann_batch_search_masked_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
                                  uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
                                  const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
                                  uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
-  const PointFilter F = PointFilter::bitmap(d_allow, allow_stride_words, nq, true);
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
-                               d_out_result_count, d_out_allowed_cmps);
+  SearchCall c;
+  c.queries = d_queries; c.qstride = q_stride_bytes; c.query_ids = d_query_ids; c.nq = nq; c.starts = d_starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(d_out); c.dev = true; c.stream = stream;
+  c.filter = PointFilter::bitmap(d_allow, allow_stride_words, nq, true); c.result_count = d_out_result_count; c.allowed_cmps = d_out_allowed_cmps;
+  return batch_search_dev(idx, c, "pann_batch_search_masked_dev");
 }
 
 int pann_batch_search_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
                                   uint64_t q_stride_bytes, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
                                   int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_search_out* d_out,
                                   uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
-  if (int rc = check_idx(idx, "pann_batch_search_labeled_dev")) return rc;
-  const PointFilter F = label_filter(idx, kind, d_preds, npreds, true);
-  if (int rc = filter_checks(idx, "pann_batch_search_labeled_dev", F, nq)) return rc;
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
-                               d_out_result_count, d_out_allowed_cmps);
+  SearchCall c;
+  c.queries = d_queries; c.qstride = q_stride_bytes; c.query_ids = d_query_ids; c.nq = nq; c.starts = d_starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(d_out); c.dev = true; c.stream = stream;
+  c.filter = label_filter(idx, kind, d_preds, npreds, true); c.result_count = d_out_result_count; c.allowed_cmps = d_out_allowed_cmps;
+  return batch_search_dev(idx, c, "pann_batch_search_labeled_dev");
 }
 
 int pann_batch_search_steered_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
@@ -734,10 +755,12 @@ int pann_batch_search_steered_dev(pann_index* idx, const void* d_queries, const 
                                   const uint32_t* d_allow, uint64_t allow_stride_words, const pann_search_out* d_out,
                                   uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, uint32_t fill, uint32_t* d_out_steer,
                                   void* stream) {
-  const PointFilter F = PointFilter::bitmap(d_allow, allow_stride_words, nq, true);
-  const SteerReq S{fill, d_out_steer};
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
-                               d_out_result_count, d_out_allowed_cmps, &S);
+  SearchCall c;
+  c.queries = d_queries; c.qstride = q_stride_bytes; c.query_ids = d_query_ids; c.nq = nq; c.starts = d_starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(d_out); c.dev = true; c.stream = stream;
+  c.filter = PointFilter::bitmap(d_allow, allow_stride_words, nq, true); c.result_count = d_out_result_count; c.allowed_cmps = d_out_allowed_cmps;
+  c.steer = true; c.fill = fill; c.steer_out = d_out_steer;
+  return batch_search_dev(idx, c, "pann_batch_search_steered_dev");
 }
 
 int pann_batch_search_steered_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
@@ -745,12 +768,12 @@ int pann_batch_search_steered_labeled_dev(pann_index* idx, const void* d_queries
                                           const pann_query_params* qp, int kind, const pann_label_pred* d_preds, uint64_t npreds,
                                           const pann_search_out* d_out, uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps,
                                           uint32_t fill, uint32_t* d_out_steer, void* stream) {
-  if (int rc = check_idx(idx, "pann_batch_search_steered_labeled_dev")) return rc;
-  const PointFilter F = label_filter(idx, kind, d_preds, npreds, true);
-  if (int rc = filter_checks(idx, "pann_batch_search_steered_labeled_dev", F, nq)) return rc;
-  const SteerReq S{fill, d_out_steer};
-  return batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, d_starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr, &F,
-                               d_out_result_count, d_out_allowed_cmps, &S);
+  SearchCall c;
+  c.queries = d_queries; c.qstride = q_stride_bytes; c.query_ids = d_query_ids; c.nq = nq; c.starts = d_starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(d_out); c.dev = true; c.stream = stream;
+  c.filter = label_filter(idx, kind, d_preds, npreds, true); c.result_count = d_out_result_count; c.allowed_cmps = d_out_allowed_cmps;
+  c.steer = true; c.fill = fill; c.steer_out = d_out_steer;
+  return batch_search_dev(idx, c, "pann_batch_search_steered_labeled_dev");
 }
 
 int pann_batch_search_grouped_labeled_dev(pann_index* idx, const void* d_queries, const uint32_t* d_query_ids, uint64_t nq,
@@ -758,21 +781,14 @@ int pann_batch_search_grouped_labeled_dev(pann_index* idx, const void* d_queries
                                           const pann_query_params* qp, int kind, const pann_label_pred* d_preds, uint64_t npreds,
                                           const uint32_t* d_group_of_query, const pann_search_out* d_out, uint32_t* d_out_result_count,
                                           uint32_t* d_out_allowed_cmps, int steer, uint32_t fill, uint32_t* d_out_steer, void* stream) {
-  const char* fn = "pann_batch_search_grouped_labeled_dev";
-  if (int rc = check_idx(idx, fn)) return rc;
-  const PointFilter T = label_filter(idx, kind, d_preds, npreds, true).as_table(d_group_of_query, npreds);
-  if (int rc = filter_checks(idx, fn, T, nq)) return rc;
-  if (int rc = grouped_search_checks(idx, fn, T, start_rows)) return rc;
-  // what the twin refuses before it launches, once, before the gather reads the starts
-  if (int rc = batch_search_dev_checks(idx, d_queries, nq, q_stride_bytes, d_starts, qp, d_out, 0, &T)) return rc;
-  DeviceGuard g(idx->device);
-  GatheredRows rows;
-  if (int rc = gather_group_rows(idx, T, nq, d_starts, nstarts, (uint32_t)start_rows, &rows, (hipStream_t)stream)) return rc;
-  const PointFilter F = label_filter(idx, kind, rows.preds, nq, true);
-  const SteerReq S{fill, d_out_steer};
-  if (int rc = batch_search_dev_impl(idx, d_queries, d_query_ids, nq, q_stride_bytes, rows.starts, nstarts, qp, d_out, stream, 0, nullptr, 0, nullptr,
-                                     &F, d_out_result_count, d_out_allowed_cmps, steer ? &S : nullptr, 1, true)) return rc;
-  return d_out->status ? raise_status_dev(rows.flag, PANN_STATUS_BAD_GROUP, d_out->status, (hipStream_t)stream) : PANN_OK;
+  SearchCall c;
+  c.queries = d_queries; c.qstride = q_stride_bytes; c.query_ids = d_query_ids; c.nq = nq;
+  c.starts = d_starts; c.nstarts = nstarts; c.starts_layout = SearchCall::STARTS_TABLE; c.start_rows = start_rows;
+  c.qp = qp; c.set_out(d_out); c.dev = true; c.stream = stream;
+  c.filter = label_filter(idx, kind, d_preds, npreds, true).as_table(d_group_of_query, npreds);
+  c.result_count = d_out_result_count; c.allowed_cmps = d_out_allowed_cmps;
+  if (steer) { c.steer = true; c.fill = fill; c.steer_out = d_out_steer; }
+  return batch_search_dev(idx, c, "pann_batch_search_grouped_labeled_dev");
 }
 
 }  // extern "C"
@@ -820,10 +836,7 @@ struct HostTrip {
     return move_direct(in, h->trip_in.buf, true, 0, in.count);
   }
   template <typename T> const T* din(int piece) const { return (const T*)in.at(h->trip_in.buf, piece); }
-  template <typename T> T* dout(int piece, size_t first = 0) const {      // element `first` of an output (null if not asked for)
-    T* p = (T*)out.at(h->trip_out.buf, piece);
-    return p ? p + first : nullptr;
-  }
+  template <typename T> T* dout(int piece) const { return (T*)out.at(h->trip_out.buf, piece); }      // an output (null if not asked for)
   uint32_t* status_slot() const { return (uint32_t*)((uint8_t*)h->trip_out.buf + out.total); }
 
   // the first npieces outputs ahead of the rest, waited for: the host decides something by them (how many ids to fetch)
@@ -898,103 +911,58 @@ struct StagedFilter {
   }
 };
 
-static int batch_search_host(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
-                             uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int per_query,
-                             const pann_query_params* qp, const pann_search_out* out, int filter = 0,
-                             const void* sketch_queries = nullptr, uint64_t sq_stride = 0, uint32_t* out_pruned = nullptr,
-                             const PointFilter* points = nullptr, uint32_t* result_count = nullptr, uint32_t* allowed_cmps = nullptr,
-                             const SteerReq* steer = nullptr, const GroupedSearch* grouped = nullptr) {
-  // grouped (points: the table of predicates, its index array one entry per query; starts: start_rows x nstarts): the predicates and
-  // start rows are gathered per query on the device, and from there on the call is one with per-query predicates and starts
-  if (int rc = search_common_checks(idx, nq, qp, out)) return rc;
-  if (points) { if (int rc = masked_search_checks(idx, *points, nq, qp, out)) return rc; }
-  uint32_t sk_row = 0;
-  if (filter) {
-    if (int rc = refuse_4bit(idx, "pann_batch_search_filtered")) return rc;
-    if (!idx->ix.sketch) { set_error("pann_batch_search_filtered: no sketch attached to the index"); return PANN_ERR_BAD_ARG; }
-    if ((queries != nullptr) != (sketch_queries != nullptr)) {
-      set_error("pann_batch_search_filtered: sketch_queries go with queries, and only with them"); return PANN_ERR_BAD_ARG;
-    }
-    sk_row = sketch_row_bytes(idx->ix.sk_kind, idx->ix.d);
-    if (sketch_queries && sq_stride < sk_row) { set_error("pann_batch_search_filtered: sketch query stride smaller than a sketch row"); return PANN_ERR_BAD_ARG; }
-  }
-  if (!starts || nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
-  if ((queries == nullptr) == (query_ids == nullptr)) { set_error("pann_batch_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
-  const uint64_t nst_total = grouped ? (uint64_t)grouped->start_rows * nstarts : per_query ? nq * nstarts : nstarts;
-  for (uint64_t i = 0; i < nst_total; i++)
-    if (starts[i] >= idx->ix.n) { set_error("pann_batch_search: start point out of range"); return PANN_ERR_BAD_ARG; }
-  for (uint64_t q = 0; grouped && q < nq; q++)
-    if (points->group[q] >= points->count) {
-      set_error("pann_batch_search_grouped_labeled: table index " + std::to_string(points->group[q]) + " of query " + std::to_string(q) +
-                " is out of range (>= " + std::to_string(points->count) + ")");
-      return PANN_ERR_BAD_ARG;
-    }
-  if (query_ids)
-    for (uint64_t i = 0; i < nq; i++)
-      if (query_ids[i] >= idx->ix.n) { set_error("pann_batch_search: query id out of range"); return PANN_ERR_BAD_ARG; }
+// A host-pointer search: one round trip.  The request is restated once on the staged copies (t.din / t.dout) and sliced per launch.
+static int batch_search_host(pann_index* idx, const SearchCall& c, const char* fn) {
+  if (int rc = search_refusals(idx, c, fn)) return rc;
+  const uint64_t nq = c.nq;
   if (nq == 0) return PANN_OK;
   DeviceGuard g(idx->device);
-  hipStream_t st = idx->stream;
   const DeviceIndex& ix = idx->ix;
   // ---- inputs: packed into pinned memory, one H2D transfer ----
-  if (queries && q_stride_bytes < ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  if (c.queries && c.qstride < ix.dbytes) { set_error("pann_batch_search: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
+  const uint32_t sk_row = c.sketch ? sketch_row_bytes(ix.sk_kind, ix.d) : 0;
   HostTrip t(idx, true);
-  const int i_q = queries ? t.in.add(queries, (nq - 1) * q_stride_bytes + ix.dbytes, kQuerySlack) : t.in.add(query_ids, nq * 4);
-  const int i_st = t.in.add(starts, (size_t)nst_total * 4);
-  const StagedFilter staged(t, points, ix.n, nq);      // masked / labeled: the bitmap rows or the predicates travel with them
-  const int i_sk = filter ? t.in.add_rows(sketch_queries, nq, sk_row, sq_stride) : -1;      // filtered: the sketch rows, dense
+  const int i_q = c.queries ? t.in.add(c.queries, (nq - 1) * c.qstride + ix.dbytes, kQuerySlack) : t.in.add(c.query_ids, nq * 4);
+  const int i_st = t.in.add(c.starts, (size_t)c.start_count() * 4);
+  const StagedFilter staged(t, c.filter.given() ? &c.filter : nullptr, ix.n, nq);      // masked / labeled: the bitmap rows or the predicates travel with them
+  const int i_sk = c.sketch ? t.in.add_rows(c.sketch_queries, nq, sk_row, c.sq_stride) : -1;      // filtered: the sketch rows, dense
   // ---- outputs: one packed device region, one D2H transfer into pinned memory, then host copies ----
-  const size_t ok = out->out_k, vc = out->visited_cap;
-  const int o_ids = t.out.add(out->ids, nq * ok * 4), o_dists = t.out.add(out->dists, nq * ok * 4);
-  const int o_fs = t.out.add(out->frontier_size, nq * 4), o_vcnt = t.out.add(out->visited_count, nq * 4);
-  const int o_cmps = t.out.add(out->dist_cmps, nq * 4), o_deg = t.out.add(out->degree_sum, nq * 4);
-  const int o_vids = t.out.add(out->visited_ids, nq * vc * 4), o_vdists = t.out.add(out->visited_dists, nq * vc * 4);
-  const int o_pruned = t.out.add(filter ? out_pruned : nullptr, nq * 4);
-  const int o_rcnt = t.out.add(points ? result_count : nullptr, nq * 4), o_acmps = t.out.add(points ? allowed_cmps : nullptr, nq * 4);
-  const int o_steer = t.out.add(steer ? steer->out : nullptr, nq * 8);
+  const pann_search_out& out = c.out;
+  const size_t ok = out.out_k, vc = out.visited_cap;
+  const int o_ids = t.out.add(out.ids, nq * ok * 4), o_dists = t.out.add(out.dists, nq * ok * 4);
+  const int o_fs = t.out.add(out.frontier_size, nq * 4), o_vcnt = t.out.add(out.visited_count, nq * 4);
+  const int o_cmps = t.out.add(out.dist_cmps, nq * 4), o_deg = t.out.add(out.degree_sum, nq * 4);
+  const int o_vids = t.out.add(out.visited_ids, nq * vc * 4), o_vdists = t.out.add(out.visited_dists, nq * vc * 4);
+  const int o_pruned = t.out.add(c.pruned_cmps, nq * 4);
+  const int o_rcnt = t.out.add(c.result_count, nq * 4), o_acmps = t.out.add(c.allowed_cmps, nq * 4);
+  const int o_steer = t.out.add(c.steer_out, nq * 8);
   if (int rc = t.begin()) return rc;
-  const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
-  const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
-  const uint32_t* d_starts = t.din<uint32_t>(i_st);
-  PointFilter d_filter = staged.on_device(t);
-  if (grouped) {
-    GatheredRows rows;
-    if (int rc = gather_group_rows(idx, d_filter, nq, d_starts, nstarts, grouped->start_rows, &rows, st)) return rc;
-    d_starts = rows.starts; per_query = 1;
-    d_filter = label_filter(idx, d_filter.kind, rows.preds, nq, true);
-  }
-  const uint8_t* d_sk = filter ? t.din<uint8_t>(i_sk) : nullptr;
+  // ---- the request on the device.  Where it differs from what a _dev caller would have passed, it says so ----
+  SearchCall d = c;
+  d.dev = true; d.stream = t.st;
+  d.queries = c.queries ? t.din<uint8_t>(i_q) : nullptr; d.query_ids = c.queries ? nullptr : t.din<uint32_t>(i_q);
+  d.starts = t.din<uint32_t>(i_st);
+  d.filter = staged.on_device(t);
+  d.sketch_queries = c.sketch ? t.din<uint8_t>(i_sk) : nullptr; d.sq_stride = sk_row;      // the staged sketch rows are dense
+  d.out.ids = t.dout<uint32_t>(o_ids); d.out.dists = t.dout<float>(o_dists);
+  d.out.frontier_size = t.dout<uint32_t>(o_fs); d.out.visited_count = t.dout<uint32_t>(o_vcnt);
+  d.out.dist_cmps = t.dout<uint32_t>(o_cmps); d.out.degree_sum = t.dout<uint32_t>(o_deg);
+  d.out.visited_ids = t.dout<uint32_t>(o_vids); d.out.visited_dists = t.dout<float>(o_vdists);
+  if (!d.out.visited_ids && !d.out.visited_dists) d.out.visited_cap = 0;      // HOST ONLY: no visited array, no visited list (a _dev call keeps its visited_cap)
+  d.out.status = nullptr;      // HOST ONLY: the status word is read from the workspace (a _dev call gets it copied to its own word)
+  d.pruned_cmps = t.dout<uint32_t>(o_pruned);
+  d.result_count = t.dout<uint32_t>(o_rcnt); d.allowed_cmps = t.dout<uint32_t>(o_acmps);
+  d.steer_out = t.dout<uint32_t>(o_steer);
+  if (d.filter.is_table()) { if (int rc = gather_group_rows(idx, d, t.st, nullptr)) return rc; }      // (the indices were checked above: no flag to read)
   uint32_t status = 0;
-  if (int rc = t.run_grown(nq, qp, "pann_batch_search", &status,
+  if (int rc = t.run_grown(nq, c.qp, "pann_batch_search", &status,
       [&](uint64_t q0, uint64_t cnt, uint32_t dcap, const uint32_t** d_word) -> int {
-      SearchArgs a;
-      a.queries = d_q ? d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
-      a.query_ids = d_qid ? d_qid + q0 : nullptr;
-      a.nq = cnt; a.starts = per_query ? d_starts + q0 * nstarts : d_starts; a.nstarts = nstarts; a.starts_per_query = per_query;
-      fill_search_params(a, qp);
-      a.dcap = dcap;
-      a.out = *out;
-      a.out.ids = t.dout<uint32_t>(o_ids, q0 * ok); a.out.dists = t.dout<float>(o_dists, q0 * ok);
-      a.out.frontier_size = t.dout<uint32_t>(o_fs, q0); a.out.visited_count = t.dout<uint32_t>(o_vcnt, q0);
-      a.out.dist_cmps = t.dout<uint32_t>(o_cmps, q0); a.out.degree_sum = t.dout<uint32_t>(o_deg, q0);
-      a.out.visited_ids = t.dout<uint32_t>(o_vids, q0 * vc); a.out.visited_dists = t.dout<float>(o_vdists, q0 * vc);
-      if (!a.out.visited_ids && !a.out.visited_dists) a.out.visited_cap = 0;
-      a.out.status = nullptr;   // read from the workspace
-      a.filter = filter;
-      if (filter) {
-        a.sketch_queries = d_sk ? d_sk + q0 * sk_row : nullptr; a.sq_stride = sk_row;
-        a.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
-      }
-      if (points) {
-        d_filter.slice(q0, cnt).apply(a);
-        a.result_count = t.dout<uint32_t>(o_rcnt, q0); a.allowed_cmps = t.dout<uint32_t>(o_acmps, q0);
-      }
-      if (steer) { a.steer = 1; a.fill = steer->fill; a.steer_out = t.dout<uint32_t>(o_steer, q0 * 2); }
-      if (int rc = idx->ws.ensure(search_workspace_bytes(idx->ix, a))) return rc;
+      const SearchArgs a = slice(d, q0, cnt, dcap);
+      if (int rc = idx->ws.ensure(search_workspace_bytes(ix, a))) return rc;
       *d_word = (const uint32_t*)((uint8_t*)idx->ws.buf + 64);
-      return launch_beam_search(idx->ix, a, idx->ws.buf, idx->ws.bytes, st);
+      return launch_beam_search(ix, a, idx->ws.buf, idx->ws.bytes, t.st);
     })) return rc;
-  if (out->status) *out->status = status;
+  if (out.status) *out.status = status;
   if (status & PANN_STATUS_VISITED_OVERFLOW) { set_error("pann_batch_search: visited list longer than visited_cap"); return PANN_ERR_OVERFLOW; }
   return PANN_OK;
 }
@@ -1004,78 +972,91 @@ extern "C" {
 int pann_batch_search(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                       uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts,
                       const pann_query_params* qp, const pann_search_out* out) {
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq; c.starts = starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(out);
+  return batch_search_host(idx, c, "pann_batch_search");
 }
 
 int pann_batch_search_filtered(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                                uint64_t q_stride_bytes, const void* sketch_queries, uint64_t sq_stride_bytes,
                                const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                                const pann_search_out* out, uint32_t* out_pruned_cmps) {
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 1, sketch_queries, sq_stride_bytes,
-                           out_pruned_cmps);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq; c.starts = starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(out);
+  c.sketch = true; c.sketch_queries = sketch_queries; c.sq_stride = sq_stride_bytes; c.pruned_cmps = out_pruned_cmps;
+  return batch_search_host(idx, c, "pann_batch_search_filtered");
 }
 
 int pann_batch_search_masked(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                              uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                              const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
                              uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
-  const PointFilter F = PointFilter::bitmap(allow, allow_stride_words, nq, false);
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
-                           out_allowed_cmps);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq; c.starts = starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(out);
+  c.filter = PointFilter::bitmap(allow, allow_stride_words, nq, false); c.result_count = out_result_count; c.allowed_cmps = out_allowed_cmps;
+  return batch_search_host(idx, c, "pann_batch_search_masked");
 }
 
 int pann_batch_search_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                               uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                               int kind, const pann_label_pred* preds, uint64_t npreds, const pann_search_out* out,
                               uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
-  if (int rc = check_idx(idx, "pann_batch_search_labeled")) return rc;
-  const PointFilter F = label_filter(idx, kind, preds, npreds, false);
-  if (int rc = filter_checks(idx, "pann_batch_search_labeled", F, nq)) return rc;
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
-                           out_allowed_cmps);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq; c.starts = starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(out);
+  c.filter = label_filter(idx, kind, preds, npreds, false); c.result_count = out_result_count; c.allowed_cmps = out_allowed_cmps;
+  return batch_search_host(idx, c, "pann_batch_search_labeled");
 }
 
 int pann_batch_search_steered(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                               uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                               const uint32_t* allow, uint64_t allow_stride_words, const pann_search_out* out,
                               uint32_t* out_result_count, uint32_t* out_allowed_cmps, uint32_t fill, uint32_t* out_steer) {
-  const PointFilter F = PointFilter::bitmap(allow, allow_stride_words, nq, false);
-  const SteerReq S{fill, out_steer};
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
-                           out_allowed_cmps, &S);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq; c.starts = starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(out);
+  c.filter = PointFilter::bitmap(allow, allow_stride_words, nq, false); c.result_count = out_result_count; c.allowed_cmps = out_allowed_cmps;
+  c.steer = true; c.fill = fill; c.steer_out = out_steer;
+  return batch_search_host(idx, c, "pann_batch_search_steered");
 }
 
 int pann_batch_search_steered_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                                       uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                                       int kind, const pann_label_pred* preds, uint64_t npreds, const pann_search_out* out,
                                       uint32_t* out_result_count, uint32_t* out_allowed_cmps, uint32_t fill, uint32_t* out_steer) {
-  if (int rc = check_idx(idx, "pann_batch_search_steered_labeled")) return rc;
-  const PointFilter F = label_filter(idx, kind, preds, npreds, false);
-  if (int rc = filter_checks(idx, "pann_batch_search_steered_labeled", F, nq)) return rc;
-  const SteerReq S{fill, out_steer};
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &F, out_result_count,
-                           out_allowed_cmps, &S);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq; c.starts = starts; c.nstarts = nstarts;
+  c.qp = qp; c.set_out(out);
+  c.filter = label_filter(idx, kind, preds, npreds, false); c.result_count = out_result_count; c.allowed_cmps = out_allowed_cmps;
+  c.steer = true; c.fill = fill; c.steer_out = out_steer;
+  return batch_search_host(idx, c, "pann_batch_search_steered_labeled");
 }
 
 int pann_batch_search_grouped_labeled(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq, uint64_t q_stride_bytes,
                                       const uint32_t* starts, uint32_t nstarts, uint64_t start_rows, const pann_query_params* qp, int kind,
                                       const pann_label_pred* preds, uint64_t npreds, const uint32_t* group_of_query, const pann_search_out* out,
                                       uint32_t* out_result_count, uint32_t* out_allowed_cmps, int steer, uint32_t fill, uint32_t* out_steer) {
-  const char* fn = "pann_batch_search_grouped_labeled";
-  if (int rc = check_idx(idx, fn)) return rc;
-  const PointFilter T = label_filter(idx, kind, preds, npreds, false).as_table(group_of_query, npreds);
-  if (int rc = filter_checks(idx, fn, T, nq)) return rc;
-  if (int rc = grouped_search_checks(idx, fn, T, start_rows)) return rc;
-  const SteerReq S{fill, out_steer};
-  const GroupedSearch grouped{(uint32_t)start_rows};
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 0, qp, out, 0, nullptr, 0, nullptr, &T, out_result_count,
-                           out_allowed_cmps, steer ? &S : nullptr, &grouped);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq;
+  c.starts = starts; c.nstarts = nstarts; c.starts_layout = SearchCall::STARTS_TABLE; c.start_rows = start_rows;
+  c.qp = qp; c.set_out(out);
+  c.filter = label_filter(idx, kind, preds, npreds, false).as_table(group_of_query, npreds);
+  c.result_count = out_result_count; c.allowed_cmps = out_allowed_cmps;
+  if (steer) { c.steer = true; c.fill = fill; c.steer_out = out_steer; }
+  return batch_search_host(idx, c, "pann_batch_search_grouped_labeled");
 }
 
 int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, const uint32_t* query_ids, uint64_t nq,
                                        uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts,
                                        const pann_query_params* qp, const pann_search_out* out) {
-  return batch_search_host(idx, queries, query_ids, nq, q_stride_bytes, starts, nstarts, 1, qp, out);
+  SearchCall c;
+  c.queries = queries; c.qstride = q_stride_bytes; c.query_ids = query_ids; c.nq = nq;
+  c.starts = starts; c.nstarts = nstarts; c.starts_layout = SearchCall::STARTS_PER_QUERY;
+  c.qp = qp; c.set_out(out);
+  return batch_search_host(idx, c, "pann_batch_search_per_query_starts");
 }
 
 
@@ -2001,20 +1982,16 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
   const uint8_t* d_q = queries ? t.din<uint8_t>(i_q) : nullptr;
   const uint32_t* d_qid = queries ? nullptr : t.din<uint32_t>(i_q);
   // ---- round 1: the beam search; a launch that reports a full dropped list is grown and repeated (as batch_search_host) ----
+  SearchCall round1;      // on the staged copies: the frontiers (beam ids per query) and the two counters
+  round1.queries = d_q; round1.qstride = q_stride_bytes; round1.query_ids = d_qid; round1.nq = nq;
+  round1.starts = t.din<uint32_t>(i_st); round1.nstarts = nstarts; round1.qp = qp; round1.dev = true; round1.stream = st;
+  round1.out.ids = t.dout<uint32_t>(o_front); round1.out.out_k = beam;
+  round1.out.dist_cmps = t.dout<uint32_t>(o_scmps); round1.out.visited_count = t.dout<uint32_t>(o_vis);
   uint32_t status = 0;
   bool whole = false;
   if (int rc = run_with_dropped_growth(idx->dcap, ix.n, nq, qp->limit, "pann_range_query", &status, &whole, &g_err,
       [&](uint64_t q0, uint64_t cnt, uint32_t dcap, uint32_t* st_word) -> int {
-      SearchArgs a;
-      a.queries = d_q ? d_q + q0 * q_stride_bytes : nullptr; a.qstride = q_stride_bytes;
-      a.query_ids = d_qid ? d_qid + q0 : nullptr;
-      a.nq = cnt; a.starts = t.din<uint32_t>(i_st); a.nstarts = nstarts;
-      fill_search_params(a, qp);
-      a.dcap = dcap;
-      a.out = pann_search_out{};
-      a.out.ids = t.dout<uint32_t>(o_front, q0 * beam); a.out.out_k = beam;
-      a.out.dist_cmps = t.dout<uint32_t>(o_scmps, q0);
-      a.out.visited_count = t.dout<uint32_t>(o_vis, q0);
+      const SearchArgs a = slice(round1, q0, cnt, dcap);
       if (int rc = idx->ws.ensure(search_workspace_bytes(ix, a))) return rc;
       if (int rc = launch_beam_search(ix, a, idx->ws.buf, idx->ws.bytes, st)) return rc;
       PANN_HIP(hipMemcpyAsync(st_word, (uint8_t*)idx->ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
@@ -2705,24 +2682,26 @@ int pann_sketch_rows(const pann_sketch_params* p, const float* rows, uint64_t n,
 
 namespace {
 
-// everything that can be refused before anything is enqueued; `fn` names the entry point in the messages
-int search_rerank_checks(const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
-                         uint64_t nq, uint64_t q_stride, int use_filter, const uint32_t* starts, uint32_t nstarts,
-                         const pann_query_params* qp, const pann_rerank_out* out, const char* fn) {
-  const std::string f = fn;
-  if (!full || !quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
-  if (!qparams || !qp || !out || !out->ids || !out->dists) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
+// Every fused entry point fills a RerankCall (search_call.h) by field name and goes through search_rerank.
+
+// everything that can be refused before anything is enqueued; r.fn names the entry point in the messages.  use_filter: the
+// caller's, or 0 where a masked call tests it itself
+int search_rerank_checks(const RerankCall& r, int use_filter) {
+  const std::string f = r.fn;
+  const pann_query_params* qp = r.qp;
+  if (!r.full || !r.quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
+  if (!r.qparams || !qp || !r.has_out || !r.out.ids || !r.out.dists) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
   if (qp->k <= 0) { set_error(f + ": k must be at least 1"); return PANN_ERR_BAD_ARG; }
   if (int rc = k_beam_check(qp)) return rc;
-  const DeviceIndex& fx = full->ix;
-  const DeviceIndex& qx = quant->ix;
+  const DeviceIndex& fx = r.full->ix;
+  const DeviceIndex& qx = r.quant->ix;
   if (fx.dtype != PANN_F32) { set_error(f + ": the full-precision index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
-  if (fx.n != qx.n || fx.d != qx.d || full->device != quant->device || fx.metric != qx.metric) {
+  if (fx.n != qx.n || fx.d != qx.d || r.full->device != r.quant->device || fx.metric != qx.metric) {
     set_error(f + ": the two indices must agree in size, dimension, device and metric"); return PANN_ERR_BAD_ARG;
   }
-  if (int rc = check_quant_kind(qparams->kind, fn)) return rc;
-  const bool eu = quant_kind_is_euclid(qparams->kind);
-  if (qx.dtype != quant_kind_dtype(qparams->kind) || qx.metric != (eu ? PANN_L2 : PANN_MIPS) || (uint32_t)qparams->dims != qx.d) {
+  if (int rc = check_quant_kind(r.qparams->kind, r.fn)) return rc;
+  const bool eu = quant_kind_is_euclid(r.qparams->kind);
+  if (qx.dtype != quant_kind_dtype(r.qparams->kind) || qx.metric != (eu ? PANN_L2 : PANN_MIPS) || (uint32_t)r.qparams->dims != qx.d) {
     set_error(f + ": the quantisation parameters do not fit the one-byte index (EUCLID_U8 <-> u8 / L2, MIPS_I8 <-> i8 / MIPS, EUCLID_U4 <-> "
                   "u4 / L2, MIPS_I4 <-> i4 / MIPS, same dimension)");
     return PANN_ERR_BAD_ARG;
@@ -2731,106 +2710,84 @@ int search_rerank_checks(const pann_index* full, const pann_index* quant, const 
     set_error(f + ": use_filter is not supported with a four-bit (" + dtype_name(qx.dtype) + ") quantised index"); return PANN_ERR_UNSUPPORTED;
   }
   if (use_filter && !qx.sketch) { set_error(f + ": use_filter needs a sketch attached to the one-byte index"); return PANN_ERR_BAD_ARG; }
-  if (q_stride < 4ull * fx.d || q_stride % 4 != 0) { set_error(f + ": query stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }
-  if (!starts || nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
+  if (r.qstride < 4ull * fx.d || r.qstride % 4 != 0) { set_error(f + ": query stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }
+  if (!r.starts || r.nstarts == 0) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
   if (qp->beam > 4096) { set_error("pann_rerank: candidates per query must be in [1,4096]"); return PANN_ERR_BAD_ARG; }
-  if (nq && !queries) { set_error(f + ": null queries"); return PANN_ERR_BAD_ARG; }
+  if (r.nq && !r.queries) { set_error(f + ": null queries"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
-}
-
-// one launch sequence for nq queries with a dropped list of dcap entries; grows quant's workspaces on first use (points: a masked call's filter)
-int search_rerank_launch(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
-                         uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
-                         const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                         const PointFilter* points = nullptr, uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr) {
-  SearchArgs a{};                                  // the fields search_workspace_bytes reads
-  a.queries = reinterpret_cast<const uint8_t*>(d_queries); a.nq = nq; a.nstarts = nstarts;
-  fill_search_params(a, qp);
-  a.dcap = dcap; a.filter = use_filter ? 1 : 0;
-  const uint32_t list = points ? masked_rerank_pool(qp) : (uint32_t)qp->beam;     // ids kept per query between search and rerank
-  a.out = pann_search_out{}; a.out.out_k = list;
-  a.masked = points ? points->mode : MASK_NONE;
-  if (int rc = quant->ws.ensure(search_workspace_bytes(quant->ix, a))) return rc;
-  if (int rc = quant->ws_rr.ensure(search_rerank_scratch_bytes(quant->ix, nq, list, normalize_first, use_filter))) return rc;
-  return search_rerank_dev(full->ix, quant->ix, quant->ws.buf, quant->ws.bytes, quant->ws_rr.buf, qparams, &quant->sk_params, d_queries,
-                           nq, q_stride, normalize_first, use_filter, d_starts, nstarts, qp, dcap, d_out, st, points, d_result_count, d_allowed_cmps);
 }
 
 // pann_batch_search_{masked,labeled}_rerank*: the rerank checks, then the filter's -- predicates over the labels of `full`, ahead
-// of the masked search's own checks on `quant` (out_k = the list length), which hold the bitmap's
-int masked_rerank_checks(const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
-                         uint64_t nq, uint64_t q_stride, int use_filter, const uint32_t* starts, uint32_t nstarts,
-                         const pann_query_params* qp, const PointFilter& F, const pann_rerank_out* out, const char* fn) {
-  if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride, 0, starts, nstarts, qp, out, fn)) return rc;
-  const std::string f = fn;
-  if (use_filter) { set_error(f + ": a mask together with the sketch filter is not supported (use_filter must be 0)"); return PANN_ERR_UNSUPPORTED; }
-  pann_search_out so{};
-  so.out_k = masked_rerank_pool(qp);
-  if (F.mode == MASK_LABELS) { if (int rc = filter_checks(full, fn, F, nq)) return rc; }
-  if (int rc = masked_search_checks(quant, F, nq, qp, &so)) return rc;
-  if (qp->k > 64) { set_error(f + ": k > 64 is not supported (the result list holds at most 64 keys)"); return PANN_ERR_UNSUPPORTED; }
+// of the masked search's own limits on `quant` (out_k = the list length), which hold the bitmap's
+int masked_rerank_checks(const RerankCall& r) {
+  if (int rc = search_rerank_checks(r, 0)) return rc;
+  const std::string f = r.fn;
+  if (r.use_filter) { set_error(f + ": a mask together with the sketch filter is not supported (use_filter must be 0)"); return PANN_ERR_UNSUPPORTED; }
+  if (r.filter.mode == MASK_LABELS) { if (int rc = filter_checks(r.full, r.fn, r.filter, r.nq)) return rc; }
+  if (int rc = masked_limits(r.quant, r.filter, r.nq, r.qp, masked_rerank_pool(r.qp))) return rc;
+  if (r.qp->k > 64) { set_error(f + ": k > 64 is not supported (the result list holds at most 64 keys)"); return PANN_ERR_UNSUPPORTED; }
   return PANN_OK;
 }
 
-// pann_batch_search_rerank / pann_batch_search_masked_rerank / pann_batch_search_labeled_rerank after their checks: one host round
-// trip, with the bitmap rows -- or the predicates -- and the two masked outputs when `points` (host pointers) is given; `fn` names
-// the entry point in the messages
-int search_rerank_host(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
-                       uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts, uint32_t nstarts,
-                       const pann_query_params* qp, const pann_rerank_out* out, const char* fn, const PointFilter* points = nullptr,
-                       uint32_t* result_count = nullptr, uint32_t* allowed_cmps = nullptr) {
-  for (uint32_t i = 0; i < nstarts; i++)
-    if (starts[i] >= quant->ix.n) { set_error(std::string(fn) + ": start point out of range"); return PANN_ERR_BAD_ARG; }
+// one launch sequence for the queries of r (device pointers, r.dcap set); grows quant's workspaces on first use
+int search_rerank_launch(const RerankCall& r) {
+  pann_index* quant = r.quant;
+  const uint32_t list = r.filter.given() ? masked_rerank_pool(r.qp) : (uint32_t)r.qp->beam;     // ids kept per query between search and rerank
+  if (int rc = quant->ws.ensure(search_rerank_ws_bytes(quant->ix, r))) return rc;
+  if (int rc = quant->ws_rr.ensure(search_rerank_scratch_bytes(quant->ix, r.nq, list, r.normalize_first, r.use_filter))) return rc;
+  return search_rerank_dev(r.full->ix, quant->ix, quant->ws, quant->ws_rr.buf, &quant->sk_params, r);
+}
+
+// a host-pointer fused call after its checks: one host round trip, with the bitmap rows -- or the predicates -- and the two masked
+// outputs when there is a filter.  The request is restated once on the staged copies and sliced per launch.
+int search_rerank_host(const RerankCall& c) {
+  pann_index* quant = c.quant;
+  const uint64_t nq = c.nq;
+  for (uint32_t i = 0; i < c.nstarts; i++)
+    if (c.starts[i] >= quant->ix.n) { set_error(std::string(c.fn) + ": start point out of range"); return PANN_ERR_BAD_ARG; }
   if (nq == 0) return PANN_OK;
   DeviceGuard g(quant->device);
   const DeviceIndex& qx = quant->ix;
-  const uint32_t k = (uint32_t)qp->k;
+  const uint32_t k = (uint32_t)c.qp->k;
   HostTrip t(quant, true);
   // ---- inputs: the float rows, the starts and the filter's arrays, one transfer up ----
-  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * qx.d);
-  const int i_st = t.in.add(starts, (size_t)nstarts * 4);
-  const StagedFilter staged(t, points, qx.n, nq);
+  const int i_q = t.in.add(c.queries, (nq - 1) * c.qstride + 4ull * qx.d);
+  const int i_st = t.in.add(c.starts, (size_t)c.nstarts * 4);
+  const StagedFilter staged(t, c.filter.given() ? &c.filter : nullptr, qx.n, nq);
   // ---- outputs: one packed device region (the status word last), one transfer down ----
-  const int o_ids = t.out.add(out->ids, nq * k * 4), o_dists = t.out.add(out->dists, nq * k * 4);
-  const int o_fs = t.out.add(out->frontier_size, nq * 4), o_vcnt = t.out.add(out->visited_count, nq * 4);
-  const int o_cmps = t.out.add(out->dist_cmps, nq * 4);
-  const int o_pruned = t.out.add(use_filter ? out->pruned_cmps : nullptr, nq * 4);       // (no room where it is not asked for)
-  const int o_rcnt = t.out.add(result_count, nq * 4), o_acmps = t.out.add(allowed_cmps, nq * 4);
+  const pann_rerank_out& out = c.out;
+  const int o_ids = t.out.add(out.ids, nq * k * 4), o_dists = t.out.add(out.dists, nq * k * 4);
+  const int o_fs = t.out.add(out.frontier_size, nq * 4), o_vcnt = t.out.add(out.visited_count, nq * 4);
+  const int o_cmps = t.out.add(out.dist_cmps, nq * 4);
+  const int o_pruned = t.out.add(c.use_filter ? out.pruned_cmps : nullptr, nq * 4);       // (no room where it is not asked for)
+  const int o_rcnt = t.out.add(c.result_count, nq * 4), o_acmps = t.out.add(c.allowed_cmps, nq * 4);
   if (int rc = t.begin()) return rc;
-  const uint8_t* d_q = t.din<uint8_t>(i_q);
-  const uint32_t* d_starts = t.din<uint32_t>(i_st);
-  const PointFilter d_filter = staged.on_device(t);
+  RerankCall d = c;
+  d.dev = true; d.stream = t.st;
+  d.queries = (const float*)t.din<uint8_t>(i_q); d.starts = t.din<uint32_t>(i_st); d.filter = staged.on_device(t);
+  d.out.ids = t.dout<uint32_t>(o_ids); d.out.dists = t.dout<float>(o_dists);
+  d.out.frontier_size = t.dout<uint32_t>(o_fs); d.out.visited_count = t.dout<uint32_t>(o_vcnt);
+  d.out.dist_cmps = t.dout<uint32_t>(o_cmps); d.out.pruned_cmps = t.dout<uint32_t>(o_pruned);
+  d.out.status = t.status_slot();      // the status word comes down with the results
+  d.result_count = t.dout<uint32_t>(o_rcnt); d.allowed_cmps = t.dout<uint32_t>(o_acmps);
   uint32_t status = 0;
-  if (int rc = t.run_grown(nq, qp, fn, &status,
+  if (int rc = t.run_grown(nq, c.qp, c.fn, &status,
       [&](uint64_t q0, uint64_t cnt, uint32_t dcap, const uint32_t** d_word) -> int {
-      pann_rerank_out d{};
-      d.ids = t.dout<uint32_t>(o_ids, q0 * k); d.dists = t.dout<float>(o_dists, q0 * k);
-      d.frontier_size = t.dout<uint32_t>(o_fs, q0); d.visited_count = t.dout<uint32_t>(o_vcnt, q0);
-      d.dist_cmps = t.dout<uint32_t>(o_cmps, q0);
-      d.pruned_cmps = t.dout<uint32_t>(o_pruned, q0);
-      *d_word = d.status = t.status_slot();
-      const PointFilter range = d_filter.slice(q0, cnt);
-      return search_rerank_launch(full, quant, qparams, (const float*)(d_q + q0 * q_stride_bytes), cnt, q_stride_bytes, normalize_first,
-                                  use_filter, d_starts, nstarts, qp, dcap, d, t.st, points ? &range : nullptr, t.dout<uint32_t>(o_rcnt, q0),
-                                  t.dout<uint32_t>(o_acmps, q0));
+      *d_word = t.status_slot();
+      return search_rerank_launch(d.slice(q0, cnt, dcap));
     })) return rc;
-  if (out->status) *out->status = status;
+  if (out.status) *out.status = status;
   return PANN_OK;
 }
 
-// the masked / labeled fused entries behind their descriptor: the checks, then the host round trip or (F.dev) the launch on the caller's stream
-int masked_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
-                  uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts, uint32_t nstarts,
-                  const pann_query_params* qp, const PointFilter& F, const pann_rerank_out* out, uint32_t* result_count,
-                  uint32_t* allowed_cmps, void* stream, const char* fn) {
-  if (int rc = masked_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, F, out, fn)) return rc;
-  if (!F.dev) return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, out, fn,
-                                        &F, result_count, allowed_cmps);      // F.dev is also the entry's kind: a host entry (no stream) ends here
-  if (nq == 0) return PANN_OK;
-  if ((uintptr_t)queries % 4 != 0) { set_error(std::string(fn) + ": query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
-  DeviceGuard g(quant->device);
-  return search_rerank_launch(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, 0, starts, nstarts, qp, quant->dcap, *out,
-                              (hipStream_t)stream, &F, result_count, allowed_cmps);
+// every fused entry behind its request: the checks, then the host round trip or (r.dev) the launch on the caller's stream
+int search_rerank(const RerankCall& r) {
+  if (int rc = r.filter.given() ? masked_rerank_checks(r) : search_rerank_checks(r, r.use_filter)) return rc;
+  if (!r.dev) return search_rerank_host(r);
+  if (r.nq == 0) return PANN_OK;
+  if ((uintptr_t)r.queries % 4 != 0) { set_error(std::string(r.fn) + ": query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(r.quant->device);
+  return search_rerank_launch(r.slice(0, r.nq, r.quant->dcap));
 }
 
 }  // namespace
@@ -2840,22 +2797,21 @@ extern "C" {
 int pann_batch_search_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
                                  uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* d_starts,
                                  uint32_t nstarts, const pann_query_params* qp, const pann_rerank_out* d_out, void* stream) {
-  if (int rc = search_rerank_checks(full, quant, qparams, d_queries, nq, q_stride_bytes, use_filter, d_starts, nstarts, qp, d_out,
-                                    "pann_batch_search_rerank_dev")) return rc;
-  if (nq == 0) return PANN_OK;
-  if ((uintptr_t)d_queries % 4 != 0) { set_error("pann_batch_search_rerank_dev: query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
-  DeviceGuard g(quant->device);
-  return search_rerank_launch(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp,
-                              quant->dcap, *d_out, (hipStream_t)stream);
+  RerankCall r;
+  r.full = full; r.quant = quant; r.qparams = qparams; r.queries = d_queries; r.nq = nq; r.qstride = q_stride_bytes;
+  r.normalize_first = normalize_first; r.use_filter = use_filter; r.starts = d_starts; r.nstarts = nstarts; r.qp = qp; r.set_out(d_out);
+  r.dev = true; r.stream = stream; r.fn = "pann_batch_search_rerank_dev";
+  return search_rerank(r);
 }
 
 int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
                              uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts,
                              uint32_t nstarts, const pann_query_params* qp, const pann_rerank_out* out) {
-  if (int rc = search_rerank_checks(full, quant, qparams, queries, nq, q_stride_bytes, use_filter, starts, nstarts, qp, out,
-                                    "pann_batch_search_rerank")) return rc;
-  return search_rerank_host(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, use_filter, starts, nstarts, qp, out,
-                            "pann_batch_search_rerank");
+  RerankCall r;
+  r.full = full; r.quant = quant; r.qparams = qparams; r.queries = queries; r.nq = nq; r.qstride = q_stride_bytes;
+  r.normalize_first = normalize_first; r.use_filter = use_filter; r.starts = starts; r.nstarts = nstarts; r.qp = qp; r.set_out(out);
+  r.fn = "pann_batch_search_rerank";
+  return search_rerank(r);
 }
 
 int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
@@ -2863,18 +2819,24 @@ int pann_batch_search_masked_rerank_dev(pann_index* full, pann_index* quant, con
                                         const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp, const uint32_t* d_allow,
                                         uint64_t allow_stride_words, const pann_rerank_out* d_out, uint32_t* d_out_result_count,
                                         uint32_t* d_out_allowed_cmps, void* stream) {
-  return masked_rerank(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp,
-                       PointFilter::bitmap(d_allow, allow_stride_words, nq, true), d_out, d_out_result_count, d_out_allowed_cmps, stream,
-                       "pann_batch_search_masked_rerank_dev");
+  RerankCall r;
+  r.full = full; r.quant = quant; r.qparams = qparams; r.queries = d_queries; r.nq = nq; r.qstride = q_stride_bytes;
+  r.normalize_first = normalize_first; r.use_filter = use_filter; r.starts = d_starts; r.nstarts = nstarts; r.qp = qp; r.set_out(d_out);
+  r.filter = PointFilter::bitmap(d_allow, allow_stride_words, nq, true); r.result_count = d_out_result_count; r.allowed_cmps = d_out_allowed_cmps;
+  r.dev = true; r.stream = stream; r.fn = "pann_batch_search_masked_rerank_dev";
+  return search_rerank(r);
 }
 
 int pann_batch_search_masked_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
                                     uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter, const uint32_t* starts,
                                     uint32_t nstarts, const pann_query_params* qp, const uint32_t* allow, uint64_t allow_stride_words,
                                     const pann_rerank_out* out, uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
-  return masked_rerank(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, use_filter, starts, nstarts, qp,
-                       PointFilter::bitmap(allow, allow_stride_words, nq, false), out, out_result_count, out_allowed_cmps, nullptr,
-                       "pann_batch_search_masked_rerank");
+  RerankCall r;
+  r.full = full; r.quant = quant; r.qparams = qparams; r.queries = queries; r.nq = nq; r.qstride = q_stride_bytes;
+  r.normalize_first = normalize_first; r.use_filter = use_filter; r.starts = starts; r.nstarts = nstarts; r.qp = qp; r.set_out(out);
+  r.filter = PointFilter::bitmap(allow, allow_stride_words, nq, false); r.result_count = out_result_count; r.allowed_cmps = out_allowed_cmps;
+  r.fn = "pann_batch_search_masked_rerank";
+  return search_rerank(r);
 }
 
 int pann_batch_search_labeled_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams,
@@ -2882,9 +2844,12 @@ int pann_batch_search_labeled_rerank_dev(pann_index* full, pann_index* quant, co
                                          int use_filter, const uint32_t* d_starts, uint32_t nstarts, const pann_query_params* qp,
                                          int kind, const pann_label_pred* d_preds, uint64_t npreds, const pann_rerank_out* d_out,
                                          uint32_t* d_out_result_count, uint32_t* d_out_allowed_cmps, void* stream) {
-  return masked_rerank(full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, use_filter, d_starts, nstarts, qp,
-                       label_filter(full, kind, d_preds, npreds, true), d_out, d_out_result_count, d_out_allowed_cmps, stream,
-                       "pann_batch_search_labeled_rerank_dev");
+  RerankCall r;
+  r.full = full; r.quant = quant; r.qparams = qparams; r.queries = d_queries; r.nq = nq; r.qstride = q_stride_bytes;
+  r.normalize_first = normalize_first; r.use_filter = use_filter; r.starts = d_starts; r.nstarts = nstarts; r.qp = qp; r.set_out(d_out);
+  r.filter = label_filter(full, kind, d_preds, npreds, true); r.result_count = d_out_result_count; r.allowed_cmps = d_out_allowed_cmps;
+  r.dev = true; r.stream = stream; r.fn = "pann_batch_search_labeled_rerank_dev";
+  return search_rerank(r);
 }
 
 int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
@@ -2892,9 +2857,12 @@ int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const 
                                      const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp, int kind,
                                      const pann_label_pred* preds, uint64_t npreds, const pann_rerank_out* out,
                                      uint32_t* out_result_count, uint32_t* out_allowed_cmps) {
-  return masked_rerank(full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, use_filter, starts, nstarts, qp,
-                       label_filter(full, kind, preds, npreds, false), out, out_result_count, out_allowed_cmps, nullptr,
-                       "pann_batch_search_labeled_rerank");
+  RerankCall r;
+  r.full = full; r.quant = quant; r.qparams = qparams; r.queries = queries; r.nq = nq; r.qstride = q_stride_bytes;
+  r.normalize_first = normalize_first; r.use_filter = use_filter; r.starts = starts; r.nstarts = nstarts; r.qp = qp; r.set_out(out);
+  r.filter = label_filter(full, kind, preds, npreds, false); r.result_count = out_result_count; r.allowed_cmps = out_allowed_cmps;
+  r.fn = "pann_batch_search_labeled_rerank";
+  return search_rerank(r);
 }
 
 }  // extern "C"

@@ -1626,7 +1626,7 @@ int launch_beam_search(const DeviceIndex& ix, const SearchArgs& a, void* ws, siz
       set_error("pann_batch_search_filtered: sketch query stride smaller than a sketch row, or rows not 8-byte aligned"); return PANN_ERR_BAD_ARG;
     }
   }
-  // the bitmap, its stride and out_k <= 64 are checked by the entry points (api.hip: masked_search_checks); no entry point combines a mask
+  // the bitmap, its stride and out_k <= 64 are checked by the entry points (api.hip: masked_limits in search_refusals); no entry point combines a mask
   // with the sketch filter, and there is no kernel for it
   if (a.masked && a.filter) { set_error("pann_batch_search_masked: the sketch filter has no masked form"); return PANN_ERR_UNSUPPORTED; }
   // label mode: the entry points have checked the handle's labels, the kind and npreds (api.hip: filter_checks)

@@ -9,6 +9,7 @@
 
 #include "../../include/pann.h"
 #include "search_plan.h"
+#include "search_call.h"
 
 namespace pann {
 
@@ -84,70 +85,7 @@ inline size_t query_lds_bytes(const DeviceIndex& ix) { return query_lds_bytes(ix
 
 inline bool pred_kind_known(int kind) { return kind == PANN_PRED_ANY || kind == PANN_PRED_MATCH || kind == PANN_PRED_RANGE; }
 
-struct SearchArgs {  // one batched beam search, everything device resident
-  const uint8_t* queries; uint64_t qstride;  // external queries (or null)
-  const uint32_t* query_ids;                 // base-point queries (or null)
-  uint64_t nq;
-  const uint32_t* starts; uint32_t nstarts;
-  int starts_per_query = 0;                  // starts is nq x nstarts (beamSearchRandom)
-  int64_t k, beam, limit, degree_limit; double cut;
-  uint32_t dcap = 256;                       // dropped-list entries per query (pann_index_reserve_dropped)
-  const uint32_t* order = nullptr;           // device, nq entries: launch slot -> query index (a permutation); null = identity
-  pann_search_out out;
-  // second level (filtered_beam_search with use_filtering): the handle's sketch decides which neighbours get a full distance
-  int filter = 0;
-  const uint8_t* sketch_queries = nullptr;   // nq host-layout sketch rows (external queries); base-point queries use their own row
-  uint64_t sq_stride = 0;
-  uint32_t* pruned_cmps = nullptr;           // nq, optional: the reference's local dist_cmps (starts + sum of pruned.size())
-  // masked search (DESIGN.md "Masked search"): same traversal, out.ids/dists = the best allowed points that were compared
-  int masked = 0;                            // MASK_NONE / MASK_BITMAP / MASK_LABELS
-  const uint32_t* allow = nullptr;           // ceil(n / 32) words per row: point i allowed iff bit i & 31 of word i >> 5
-  uint64_t allow_stride = 0;                 // words between the rows of two queries; 0: one bitmap for the batch
-  uint32_t* result_count = nullptr;          // nq, optional: entries of the query's result list (<= out.out_k)
-  uint32_t* allowed_cmps = nullptr;          // nq, optional: full distances computed for allowed points
-  // MASK_LABELS (DESIGN.md "Label predicates"): point i allowed iff the query's predicate holds on labels[i]
-  const uint32_t* labels = nullptr;          // n words; not necessarily the searched handle's own (the fused path reads `full`'s)
-  const pann_label_pred* preds = nullptr;    // query q reads preds[q * pred_stride]
-  uint32_t pred_stride = 0;                  // 0: one predicate for the batch, 1: one per query
-  int pred_kind = 0;                         // PANN_PRED_*
-  // steered form of a masked search (DESIGN.md "Steered masked search"): pruned = allowed neighbours + allowed neighbours of bridges
-  int steer = 0; uint32_t fill = 0;          // fill: the two-hop pass stops at this many entries; 0 or above deg_eff: deg_eff
-  uint32_t* steer_out = nullptr;             // nq x 2, optional: bridge_rows, hop2_cmps
-};
-
-// Which points a query may return: what every masked / labeled / grouped entry point builds once from its C arguments and
-// everything behind it takes.  allow / preds / group are host or device pointers, as the entry point's other pointers (`dev`);
-// labels is the device array of the handle whose labels are read.  Only the filter: the optional outputs of the masked
-// searches (result_count, allowed_cmps) travel beside it.
-struct PointFilter {
-  enum { SHARED, PER_QUERY, TABLE };    // one filter for the batch | one per query | `count` table entries, query q uses entry group[q]
-  int mode = MASK_NONE, layout = SHARED;      // MASK_BITMAP: rows of `allow`; MASK_LABELS: `preds` of one `kind` over `labels`
-  uint64_t count = 1;                   // filters given, as the caller said it (the checks hold it against nq): 1, nq, or the table's entries
-  const uint32_t* allow = nullptr; uint64_t stride = 0;      // bitmap rows, as SearchArgs::allow; words between two rows (0: one row)
-  const uint32_t* labels = nullptr; int kind = 0; const pann_label_pred* preds = nullptr;
-  const uint32_t* group = nullptr; bool dev = false;      // group: nq entries of a TABLE
-  static PointFilter bitmap(const uint32_t* allow, uint64_t stride, uint64_t nq, bool dev) {      // a stride makes one row per query, even at nq == 1
-    PointFilter f; f.mode = MASK_BITMAP; f.allow = allow; f.stride = stride; f.dev = dev;
-    if (stride) { f.layout = PER_QUERY; f.count = nq; }
-    return f;
-  }
-  PointFilter as_table(const uint32_t* group_of_query, uint64_t entries) const {
-    PointFilter f = *this; f.layout = TABLE; f.count = entries; f.group = group_of_query; return f;
-  }
-  bool shared() const { return layout == SHARED; }
-  bool per_query() const { return layout == PER_QUERY; }
-  bool is_table() const { return layout == TABLE; }
-  static uint64_t row_words(uint64_t n) { return (n + 31) / 32; }
-  PointFilter slice(uint64_t q0, uint64_t cnt) const {      // the filter of the queries [q0, q0 + cnt) (a shared one is its own slice)
-    PointFilter f = *this;
-    if (per_query()) { f.count = cnt; if (allow) f.allow += q0 * stride; if (preds) f.preds += q0; }
-    return f;
-  }
-  void apply(SearchArgs& a) const {     // (a.result_count / a.allowed_cmps: the callers place them themselves)
-    a.masked = mode; a.allow = allow; a.allow_stride = stride;
-    a.labels = labels; a.preds = preds; a.pred_stride = mode == MASK_LABELS && per_query() ? 1u : 0u; a.pred_kind = kind;
-  }
-};
+// SearchArgs (the launch arguments of one beam search), PointFilter and the request descriptors of the search family: search_call.h
 
 // dense_topk_dev (dense.hip): for every A row the m nearest B rows.  A rows: external rows (a_ext, a_stride bytes apart) or the table's rows
 // a_ids; B rows: the table's rows b_ids (null: 0 .. nb).  Segmented form: segment s pairs the A rows [a_off[s], a_off[s + 1]) with the B rows
@@ -374,7 +312,7 @@ float sketch_threshold(const pann_sketch_params* p);               // the value 
 // search_rerank.hip: beam_search_rerank on the device -- prepare the float queries (one-byte rows, sketch rows, normalised
 // rows), beam search on the one-byte index, exact rerank of the frontier on the f32 index.  `scratch`: search_rerank_scratch_bytes
 // bytes, 256-byte aligned; search_ws: the one-byte handle's search workspace (its status word gets the SHORT_FRONTIER bit).
-// Masked form (points != null, device pointers, with its two optional outputs of nq entries; DESIGN.md "Masked search on the fused path"):
+// Masked form (r.filter given, with its two optional outputs of nq entries; DESIGN.md "Masked search on the fused path"):
 // the search is the masked one with a result list of masked_rerank_pool(qp) ids per query, the rerank reads that list (result_count
 // entries) instead of the frontier, raises no SHORT_FRONTIER, and the scratch is sized with the pool in place of the beam.
 inline uint32_t masked_rerank_pool(const pann_query_params* qp) {   // min(k * rerank_factor, beam, 64), at least 1
@@ -382,11 +320,10 @@ inline uint32_t masked_rerank_pool(const pann_query_params* qp) {   // min(k * r
   return (uint32_t)std::min<int64_t>(std::min<int64_t>(want, std::max<int64_t>(qp->beam, 1)), 64);
 }
 size_t search_rerank_scratch_bytes(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int normalize_first, int use_filter);
-int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* search_ws, size_t search_ws_bytes, void* scratch,
-                      const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
-                      uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
-                      const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                      const PointFilter* points = nullptr, uint32_t* d_result_count = nullptr, uint32_t* d_allowed_cmps = nullptr);
+// r: the request of the queries to launch (device pointers, r.dcap set); sparams: the parameters of quant's sketch (use_filter)
+size_t search_rerank_ws_bytes(const DeviceIndex& quant, const RerankCall& r);      // of the search workspace, by the same request
+int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, const Workspace& search_ws, void* scratch,
+                      const pann_sketch_params* sparams, const RerankCall& r);
 
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,

@@ -266,17 +266,48 @@ size_t search_rerank_scratch_bytes(const DeviceIndex& quant, uint64_t nq, uint32
   return cut_scratch(quant, nq, beam, normalize_first, use_filter, nullptr).bytes;
 }
 
-int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* search_ws, size_t search_ws_bytes, void* scratch,
-                      const pann_quant_params* qparams, const pann_sketch_params* sparams, const float* d_queries, uint64_t nq,
-                      uint64_t q_stride, int normalize_first, int use_filter, const uint32_t* d_starts, uint32_t nstarts,
-                      const pann_query_params* qp, uint32_t dcap, const pann_rerank_out& d_out, hipStream_t st,
-                      const PointFilter* mask, uint32_t* d_result_count, uint32_t* d_allowed_cmps) {
+// ids kept per query between search and rerank: the frontier, or the masked search's result list
+static uint32_t list_length(const RerankCall& r) { return r.filter.given() ? masked_rerank_pool(r.qp) : (uint32_t)r.qp->beam; }
+
+// step 2 as a request: the search on the one-byte index, over the prepared rows of the scratch
+static SearchCall quant_search(const RerankCall& r, const Scratch& s) {
+  SearchCall c;
+  c.queries = s.qb; c.qstride = s.qb_stride; c.nq = r.nq;
+  c.starts = r.starts; c.nstarts = r.nstarts; c.qp = r.qp; c.dev = true;
+  c.out.ids = s.fids; c.out.out_k = list_length(r); c.out.frontier_size = s.fsize;
+  c.out.visited_count = r.out.visited_count; c.out.dist_cmps = r.out.dist_cmps;
+  if (r.filter.given()) {                          // bitmap rows, or the labels of `full` with the queries' predicates
+    c.out.frontier_size = r.out.frontier_size;
+    c.filter = r.filter; c.result_count = r.result_count ? r.result_count : s.fsize; c.allowed_cmps = r.allowed_cmps;
+  }
+  if (r.use_filter) { c.sketch = true; c.sketch_queries = s.sk; c.sq_stride = s.sk_stride; c.pruned_cmps = r.out.pruned_cmps; }
+  return c;
+}
+
+// The workspace is sized by the plan of the same request that search_rerank_dev launches, so the two cannot disagree.  The scratch
+// is cut from a null base here: the plan reads counts, parameters and modes of the launch arguments (plan_of, beam_search.hip), never a
+// pointer, and nothing is dereferenced.
+size_t search_rerank_ws_bytes(const DeviceIndex& quant, const RerankCall& r) {
+  const Scratch s = cut_scratch(quant, r.nq, list_length(r), r.normalize_first, r.use_filter, nullptr);
+  return search_workspace_bytes(quant, slice(quant_search(r, s), 0, r.nq, r.dcap));
+}
+
+int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, const Workspace& search_ws, void* scratch,
+                      const pann_sketch_params* sparams, const RerankCall& r) {
+  const uint64_t nq = r.nq, q_stride = r.qstride;
+  const pann_query_params* qp = r.qp;
+  const pann_quant_params* qparams = r.qparams;
+  const float* d_queries = r.queries;
+  const int normalize_first = r.normalize_first, use_filter = r.use_filter;
+  const pann_rerank_out& d_out = r.out;
+  const bool mask = r.filter.given();
+  hipStream_t st = (hipStream_t)r.stream;
   if (nq == 0) return PANN_OK;
   const uint32_t d = full.d, beam = (uint32_t)qp->beam, k = (uint32_t)qp->k;
   if (beam == 0 || beam > 4096) { set_error("pann_rerank: candidates per query must be in [1,4096]"); return PANN_ERR_BAD_ARG; }
   const uint32_t pool = mask ? masked_rerank_pool(qp) : 0u;        // masked: ids per result list
   if (mask && (use_filter || k > PANN_WAVE)) { set_error("pann_batch_search_masked_rerank: no sketch filter, k <= 64"); return PANN_ERR_UNSUPPORTED; }
-  const Scratch s = cut_scratch(quant, nq, mask ? pool : beam, normalize_first, use_filter, scratch);
+  const Scratch s = cut_scratch(quant, nq, list_length(r), normalize_first, use_filter, scratch);
 
   // ---- 1. the queries ----
   const size_t prep_lds = normalize_first ? (size_t)d * 4 : 0;
@@ -289,25 +320,10 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, void* s
   PANN_HIP(hipGetLastError());
 
   // ---- 2. the search on the one-byte index ----
-  SearchArgs a;
-  a.queries = s.qb; a.qstride = s.qb_stride; a.query_ids = nullptr;
-  a.nq = nq; a.starts = d_starts; a.nstarts = nstarts;
-  a.k = qp->k; a.beam = qp->beam; a.limit = qp->limit; a.degree_limit = qp->degree_limit; a.cut = qp->cut;
-  a.dcap = dcap;
-  a.out = pann_search_out{};
-  a.out.ids = s.fids; a.out.out_k = beam; a.out.frontier_size = s.fsize;
-  uint32_t* rcount = s.fsize;                      // masked: the lists' lengths, in the caller's array when there is one
-  if (mask) {
-    if (d_result_count) rcount = d_result_count;
-    a.out.out_k = pool; a.out.frontier_size = d_out.frontier_size;
-    mask->apply(a);                                // bitmap rows, or the labels of `full` with the queries' predicates
-    a.result_count = rcount; a.allowed_cmps = d_allowed_cmps;
-  }
-  a.out.visited_count = d_out.visited_count; a.out.dist_cmps = d_out.dist_cmps;
-  a.filter = use_filter ? 1 : 0;
-  if (use_filter) { a.sketch_queries = s.sk; a.sq_stride = s.sk_stride; a.pruned_cmps = d_out.pruned_cmps; }
-  if (int rc = launch_beam_search(quant, a, search_ws, search_ws_bytes, st)) return rc;
-  uint32_t* status = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(search_ws) + 64);      // the search's status word
+  const SearchArgs a = slice(quant_search(r, s), 0, nq, r.dcap);
+  uint32_t* rcount = mask ? a.result_count : s.fsize;      // masked: the lists' lengths, in the caller's array when there is one
+  if (int rc = launch_beam_search(quant, a, search_ws.buf, search_ws.bytes, st)) return rc;
+  uint32_t* status = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(search_ws.buf) + 64);      // the search's status word
 
   // ---- 3. rerank from the frontier ----
   RerankArgs R{};
