@@ -388,7 +388,8 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
   Arena arena;
   size_t scan_tmp = 0, sort_tmp = 0;
   (void)rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)gn + 1, rocprim::plus<uint32_t>(), st);
-  (void)rocprim::segmented_radix_sort_keys(nullptr, sort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned)(n * m), (unsigned)(n / 2 + 2),
+  // the sort's scratch grows with the segment count; a tree has up to n leaves (leaves of one member, when cluster_size is 2 or 3)
+  (void)rocprim::segmented_radix_sort_keys(nullptr, sort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned)(n * m), (unsigned)(n + 1),
                                            (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0, 64, st);
   if (n * m >= 0xFFFFFFF0ull) { set_error("pann_hcnng_build: n too large for 32-bit edge offsets"); return PANN_ERR_BAD_ARG; }
   // per-level buffers, sized once for the worst level: clusters that still split are longer than cluster_size; a tree has at
