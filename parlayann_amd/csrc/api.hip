@@ -1505,9 +1505,12 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
   uint32_t nblocks; uint64_t per_block;
   group_sort_shape(nq, G, &nblocks, &per_block);
   const size_t head_words = 1 + 2 * (size_t)G;       // flag | queries per entry | allowed points per entry
-  if (int rc = idx->grp_sort.ensure((head_words + (size_t)G + 1 + (size_t)nblocks * G + (size_t)nq + (cen ? (size_t)nq : 0)) * 4)) return rc;
-  uint32_t* d_head = idx->grp_sort.as<uint32_t>();
-  uint32_t* d_hist = d_head + 1, *d_allowed = d_hist + G, *d_off = d_allowed + G, *d_part = d_off + G + 1, *d_perm = d_part + (size_t)nblocks * G;
+  uint32_t *d_head, *d_off, *d_part, *d_perm;      // the head is read back as one block; d_perm: the slots, then (cen) the iota table indices
+  if (int rc = carve_into(idx->grp_sort, 0, [&](Carve& c) {
+    d_head = c.take<uint32_t>(head_words); d_off = c.take<uint32_t>(G + 1); d_part = c.take<uint32_t>((size_t)nblocks * G);
+    d_perm = c.take<uint32_t>((size_t)nq + (cen ? (size_t)nq : 0));
+  })) return rc;
+  uint32_t* d_hist = d_head + 1, *d_allowed = d_hist + G;
   const uint32_t* d_group = T.group;
   if (cen) { if (int rc = subset_iota_dev(d_perm + nq, nullptr, nq, st)) return rc; d_group = d_perm + nq; }
   if (int rc = group_queries_dev(d_group, nq, G, d_head, d_hist, d_off, d_part, d_perm, st)) return rc;
@@ -1528,10 +1531,15 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
   plan.write(allowed, hp);
   // ---- device room for the largest chunk, then the plan goes up in one transfer ----
   const uint32_t a_stride = (ix.dbytes + 15) / 16 * 16;
-  const size_t o_upreds = (plan.plan_bytes + 255) & ~(size_t)255;
-  if (int rc = idx->grp_plan.ensure(o_upreds + (lab ? U * sizeof(pann_label_pred) : 0))) return rc;
-  const size_t o_bc = lab ? (plan.max_rows * words * 4 + 255) & ~(size_t)255 : 0;
-  if (int rc = idx->grp_rows.ensure(o_bc + allow_rows_compact_scratch_bytes(ix.n, plan.max_rows))) return rc;
+  uint8_t* dp; pann_label_pred* d_upreds;      // the plan goes up as one block; the predicates of the used entries (label form)
+  if (int rc = carve_into(idx->grp_plan, 0, [&](Carve& c) {
+    dp = c.take<uint8_t>(plan.plan_bytes); d_upreds = c.take<pann_label_pred>(lab ? U : 0);
+  })) return rc;
+  uint32_t *d_rows, *d_bc;      // a chunk's bitmap rows (label form) and the block counts of their compaction
+  if (int rc = carve_into(idx->grp_rows, 0, [&](Carve& c) {
+    d_rows = c.take<uint32_t>(lab ? plan.max_rows * words : 0);
+    d_bc = (uint32_t*)c.take<uint8_t>(allow_rows_compact_scratch_bytes(ix.n, plan.max_rows));
+  })) return rc;
   if (int rc = idx->ws4.ensure(std::max<size_t>(plan.max_ids, 1) * 4)) return rc;
   if (cen) {      // the pieces of every chunk's lists and the room for their sums (grouped_plan.h)
     size_t need = 0;
@@ -1539,17 +1547,15 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
       need = std::max(need, CentroidScratch(c.u1 - c.u0, centroid_chunk_pieces(plan, c, allowed), centroid_row_sums(ix.dbytes, ix.esize)).bytes);
     if (int rc = idx->grp_cen.ensure(need)) return rc;
   }
-  const size_t o_sids = (plan.max_na * a_stride + kQuerySlack + 255) & ~(size_t)255, o_sdists = o_sids + ((plan.max_na * k * 4 + 255) & ~(size_t)255);
-  if (int rc = idx->grp_io.ensure(o_sdists + plan.max_na * k * 4)) return rc;
-  uint8_t* dp = idx->grp_plan.as<uint8_t>();
+  uint8_t* d_slab; uint32_t* d_sids; float* d_sdists;      // a chunk's query rows and its staged results
+  if (int rc = carve_into(idx->grp_io, 0, [&](Carve& c) {
+    d_slab = c.take<uint8_t>(plan.max_na * a_stride, kQuerySlack);
+    d_sids = c.take<uint32_t>(plan.max_na * k); d_sdists = c.take<float>(plan.max_na * k);
+  })) return rc;
   PANN_HIP(hipMemcpyAsync(dp, hp, plan.plan_bytes, hipMemcpyHostToDevice, st));
   const uint32_t* d_used = (const uint32_t*)dp;
-  pann_label_pred* d_upreds = (pann_label_pred*)(dp + o_upreds);
   if (lab) { if (int rc = gather_preds_dev(T.preds, d_used, U, d_upreds, st)) return rc; }
-  uint32_t* d_rows = idx->grp_rows.as<uint32_t>(), *d_bc = (uint32_t*)(idx->grp_rows.as<uint8_t>() + o_bc), *d_list = idx->ws4.as<uint32_t>();
-  uint8_t* d_slab = idx->grp_io.as<uint8_t>();
-  uint32_t* d_sids = (uint32_t*)(d_slab + o_sids);
-  float* d_sdists = (float*)(d_slab + o_sdists);
+  uint32_t* d_list = idx->ws4.as<uint32_t>();
   // ---- per chunk: id lists (CSR), query slab, ONE segmented dense launch, rows back to the caller's order ----
   for (const GroupedChunk& c : plan.chunks) {
     const uint32_t S = (uint32_t)(c.u1 - c.u0);
@@ -2310,15 +2316,14 @@ struct ReachScratch {
   uint32_t *flag, *lens, *visited, *unreached, *compact, *queue[2];
   int place(pann_index* idx) {
     const uint64_t n = idx->ix.n;
-    const size_t bm = PackedLayout::align((size_t)((n + 31) / 32) * 4), qb = PackedLayout::align((size_t)n * 4);
-    const size_t cb = PackedLayout::align(allow_compact_scratch_bytes(n));
-    if (int rc = idx->ws3.ensure(256 + 2 * bm + cb + 2 * qb)) return rc;
-    uint8_t* p = idx->ws3.as<uint8_t>();
-    flag = (uint32_t*)p; lens = flag + 1; p += 256;
-    visited = (uint32_t*)p; p += bm;
-    unreached = (uint32_t*)p; p += bm;
-    compact = (uint32_t*)p; p += cb;
-    queue[0] = (uint32_t*)p; queue[1] = (uint32_t*)(p + qb);
+    const size_t words = (size_t)((n + 31) / 32);
+    if (int rc = carve_into(idx->ws3, 0, [&](Carve& c) {
+      flag = c.take<uint32_t>(64);      // the counter block: 256 bytes cleared as one, the lengths behind the flag
+      visited = c.take<uint32_t>(words); unreached = c.take<uint32_t>(words);
+      compact = (uint32_t*)c.take<uint8_t>(allow_compact_scratch_bytes(n));
+      queue[0] = c.take<uint32_t>(n); queue[1] = c.take<uint32_t>(n);
+    })) return rc;
+    lens = flag + 1;
     return PANN_OK;
   }
 };

@@ -1327,23 +1327,22 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
   if (m == 0 || m > 128) { set_error("dense top-m: m must be in [1,128]"); return PANN_ERR_BAD_ARG; }
   if (na == 0) return PANN_OK;
   const uint32_t mcap = (m + 15) / 16 * 16;
-  const size_t pbytes = (size_t)na * nsplit * m * 8;
-  if (int rc = ws.ensure(pbytes + 256)) return rc;
+  // the partial lists; for the register-list ground-truth kernel also |b|^2 of every point and, per [A row][piece], the piece's
+  // ceil(m/nsplit)-th best so far
+  const bool gt = dense_gt_eligible(ix, m, c.b_ids != nullptr, c.a_off || c.b_off || c.tile_seg || c.tile_a0, exclude_same);
+  const uint64_t nnorm = nb;
+  uint64_t* partial; float* d_norm = nullptr; uint32_t* d_gtau = nullptr;
+  if (int rc = carve_into(ws, 256, [&](Carve& cv) {
+    partial = cv.take<uint64_t>((size_t)na * nsplit * m);
+    if (gt) { d_norm = cv.take<float>(nnorm); d_gtau = cv.take<uint32_t>((size_t)na * nsplit); }
+  })) return rc;
   DenseArgs A{};
   A.points = ix.points; A.pstride = ix.pstride; A.dbytes = ix.dbytes;
   A.a_ext = c.a_ext; A.a_stride = c.a_stride; A.a_ids = c.a_ids; A.b_ids = c.b_ids;
   A.a_off = c.a_off; A.b_off = c.b_off; A.na = na; A.nb = nb; A.nsplit = nsplit; A.m = m; A.mcap = mcap;
-  A.exclude_same_id = exclude_same; A.exact = ix.exact; A.partial = (uint64_t*)ws.buf; A.tile_seg = c.tile_seg; A.tile_a0 = c.tile_a0;
+  A.exclude_same_id = exclude_same; A.exact = ix.exact; A.partial = partial; A.tile_seg = c.tile_seg; A.tile_a0 = c.tile_a0;
   const dim3 grid(ntiles, nsplit);
-  if (dense_gt_eligible(ix, m, c.b_ids != nullptr, c.a_off || c.b_off || c.tile_seg || c.tile_a0, exclude_same)) {
-    // register-list ground-truth kernel; |b|^2 of every point first (after the partial lists in the workspace)
-    const size_t poff = (pbytes + 255) / 256 * 256;
-    const uint64_t nnorm = nb;
-    const size_t noff = poff + ((size_t)nnorm * 4 + 255) / 256 * 256;
-    if (int rc = ws.ensure(noff + (size_t)na * nsplit * 4 + 256)) return rc;
-    A.partial = (uint64_t*)ws.buf;
-    float* d_norm = reinterpret_cast<float*>(static_cast<uint8_t*>(ws.buf) + poff);
-    uint32_t* d_gtau = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(ws.buf) + noff);      // [A row][piece]: the piece's ceil(m/nsplit)-th best so far
+  if (gt) {
     PANN_HIP(hipMemsetAsync(d_gtau, 0xFF, (size_t)na * nsplit * 4, st));
     const dim3 ng((uint32_t)((nnorm + 15) / 16));
     // |b|^2 of every point: f32 bits for the two-byte floats, exact int32 for the one-byte types (f32: difference form, no norms)
@@ -1372,7 +1371,7 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
   }
   PANN_HIP(hipGetLastError());
   hipLaunchKernelGGL(dense_merge_kernel, dim3((uint32_t)na), dim3(64), (size_t)mcap * 8, st,
-                     (const uint64_t*)ws.buf, na, nsplit, m, mcap, c.out_ids, c.out_dists);
+                     (const uint64_t*)partial, na, nsplit, m, mcap, c.out_ids, c.out_dists);
   PANN_HIP(hipGetLastError());
   return PANN_OK;
 }

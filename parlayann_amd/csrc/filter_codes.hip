@@ -12,9 +12,8 @@
 // gcode[n][gstride] of uint16, slot-aligned with the adjacency rows, read with the row (128 coalesced bytes per visited vertex).
 // It is maintained by the builder's row writers (vamana_build.hip) from rank16[id]; anything else that changes the graph marks it
 // stale and the searches fall back to the id table.
-#include <rocprim/device/device_radix_sort.hpp>
-
 #include "pann_device.h"
+#include "rocprim_temp.h"
 
 namespace pann {
 
@@ -56,15 +55,13 @@ __global__ void code_rows_kernel(const uint32_t* graph, uint32_t gstride, uint64
 // rank16[a] for all a < n at 1 << bits slots; *max_rank_out = the largest code of a class with 4 095 or more members (0: none)
 int filter_codes_build_ranks(uint64_t n, uint32_t bits, Workspace& ws, hipStream_t st, uint16_t* rank16, uint32_t* max_rank_out) {
   if (n == 0 || n >= 0xFFFFFFF0ull) { set_error("filter codes: n out of range"); return PANN_ERR_BAD_ARG; }
-  size_t sort_tmp = 0;
-  (void)rocprim::radix_sort_keys(nullptr, sort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (size_t)n, 0, 64, st);
-  const size_t kbytes = ((size_t)n * 8 + 255) / 256 * 256;
-  const size_t cbytes = (((size_t)1 << bits) * 4 + 255) / 256 * 256;
-  if (int rc = ws.ensure(2 * kbytes + cbytes + 256 + sort_tmp + 256)) return rc;
-  uint8_t* w = (uint8_t*)ws.buf;
-  uint64_t* ka = (uint64_t*)w; uint64_t* kb = (uint64_t*)(w + kbytes);
-  uint32_t* cstart = (uint32_t*)(w + 2 * kbytes); uint32_t* d_max = (uint32_t*)(w + 2 * kbytes + cbytes);
-  void* tmp = w + 2 * kbytes + cbytes + 256;
+  size_t sort_tmp = sort_temp_bytes((size_t)n);
+  uint64_t *ka, *kb; uint32_t *cstart, *d_max; void* tmp;
+  if (int rc = carve_into(ws, 256, [&](Carve& c) {
+    ka = c.take<uint64_t>(n); kb = c.take<uint64_t>(n);
+    cstart = c.take<uint32_t>((size_t)1 << bits); d_max = c.take<uint32_t>(64);
+    tmp = c.take<uint8_t>(sort_tmp);
+  })) return rc;
   const uint32_t nb = (uint32_t)((n + 255) / 256);
   hipLaunchKernelGGL(code_keys_kernel, dim3(nb), dim3(256), 0, st, n, (1u << bits) - 1u, ka);
   PANN_HIP(rocprim::radix_sort_keys(tmp, sort_tmp, ka, kb, (size_t)n, 0, 32 + bits, st));

@@ -9,6 +9,8 @@
 #include <iterator>
 #include <vector>
 
+#include "scratch_carve.h"
+
 namespace pann {
 
 // One tile of 64 A rows per (segment, a0): segment s holds the rows [off[s], off[s + 1]), an empty one has no tile.  The tiles are
@@ -96,7 +98,7 @@ constexpr uint32_t centroid_row_sums(uint32_t dbytes, uint32_t esize) { return (
 struct CentroidScratch {
   size_t o_partial, bytes;
   CentroidScratch(uint64_t S, uint64_t pieces, uint32_t row_sums)
-      : o_partial((((size_t)S + 1) * 4 + 255) & ~(size_t)255), bytes(o_partial + (size_t)pieces * row_sums * 8) {}
+      : o_partial(Carve::align(((size_t)S + 1) * 4)), bytes(o_partial + (size_t)pieces * row_sums * 8) {}
 };
 
 }  // namespace pann

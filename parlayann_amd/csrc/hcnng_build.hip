@@ -9,15 +9,12 @@
 //
 // The sequential part of Kruskal runs on lane 0 of one wave per leaf (union-find arrays in LDS for
 // leaves up to 4096 members, in HBM scratch beyond); thousands of leaves run concurrently.
-#include <chrono>
 #include <cstring>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-
 #include "grouped_plan.h"
 #include "pann_device.h"
+#include "rocprim_temp.h"
 
 namespace pann {
 
@@ -331,32 +328,6 @@ int hcnng_assemble_dev(const DeviceIndex& ix, hipStream_t st, const uint32_t* d_
   return PANN_OK;
 }
 
-struct HBuf {   // small RAII device buffer
-  void* p = nullptr;
-  ~HBuf() { if (p) (void)hipFree(p); }
-  int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 16) == hipSuccess ? 0 : 1; }
-  template <typename T> T* as() { return (T*)p; }
-};
-// The builder's scratch arrays are carved out of ONE allocation: at 10M points the forest needs ~6 GB in twenty arrays, and
-// twenty hipMalloc / hipFree pairs of that size cost more than the tree phase itself.
-struct ABuf {
-  void* p = nullptr;
-  template <typename T> T* as() { return (T*)p; }
-};
-struct Arena {
-  HBuf mem;
-  std::vector<std::pair<ABuf*, size_t>> want;
-  void add(ABuf& b, size_t bytes) { want.emplace_back(&b, (std::max<size_t>(bytes, 16) + 255) / 256 * 256); }
-  int commit() {
-    size_t tot = 0;
-    for (auto& w : want) tot += w.second;
-    if (mem.alloc(tot)) return 1;
-    size_t off = 0;
-    for (auto& w : want) { w.first->p = static_cast<uint8_t*>(mem.p) + off; off += w.second; }
-    return 0;
-  }
-};
-
 // Trees first_tree, first_tree + tree_step, ... (num_clusters of them) of the forest seeded by `seed` (tree t: mix(mix(seed + t))).
 // slab == nullptr: the edges are appended to the index's graph rows (pann_hcnng_build).  slab != nullptr (tree-parallel build over
 // ranks): tree j of THIS call writes vertex v's edges into slots [j*mst_deg, (j+1)*mst_deg) of row v of the slab (n rows of
@@ -371,8 +342,6 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
   if (!slab && (uint64_t)num_clusters * mst_deg > ix.max_deg) { set_error("pann_hcnng_build: max_deg < num_clusters * mst_deg"); return PANN_ERR_BAD_ARG; }
   if (slab && (uint64_t)num_clusters * mst_deg > slab_stride) { set_error("pann_hcnng_build_trees: slab rows shorter than ntrees * mst_deg"); return PANN_ERR_BAD_ARG; }
   if (mst_deg > 255) { set_error("pann_hcnng_build: mst_deg > 255"); return PANN_ERR_BAD_ARG; }
-  auto now = [] { return std::chrono::steady_clock::now(); };
-  auto secs = [](auto a, auto b) { return std::chrono::duration<double>(b - a).count(); };
   const PointsView pv{ix.points, ix.pstride, ix.nch, ix.exact};
   const size_t qb = query_lds_bytes(ix);
   const uint32_t nb256 = (uint32_t)((n + 255) / 256);
@@ -383,29 +352,35 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
   uint32_t group = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(num_clusters, (1ull << 31) / std::max<uint64_t>(n, 1)));
   if (ix.forest_group) group = std::min<uint32_t>(group, ix.forest_group);   // pann_index_set_forest_group: bounds the forest's scratch
   const uint64_t gn = (uint64_t)group * n;
-  ABuf b_ids, b_new, b_first, b_scan, b_pos, b_deg, b_leaflo, b_nnids, b_nnd, b_ka, b_kb, b_par, b_rnk, b_dgr, b_tmp;
-  ABuf d_sc, d_tbase, d_same, d_scat, d_n0, d_loff, d_seg_b, d_seg_e;
-  Arena arena;
-  size_t scan_tmp = 0, sort_tmp = 0;
-  (void)rocprim::exclusive_scan(nullptr, scan_tmp, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)gn + 1, rocprim::plus<uint32_t>(), st);
+  const size_t scan_tmp = scan_temp_bytes<uint32_t>((size_t)gn + 1);
   // the sort's scratch grows with the segment count; a tree has up to n leaves (leaves of one member, when cluster_size is 2 or 3)
-  (void)rocprim::segmented_radix_sort_keys(nullptr, sort_tmp, (uint64_t*)nullptr, (uint64_t*)nullptr, (unsigned)(n * m), (unsigned)(n + 1),
-                                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0, 64, st);
+  const size_t sort_tmp = seg_sort_temp_bytes((unsigned)(n * m), (unsigned)(n + 1));
   if (n * m >= 0xFFFFFFF0ull) { set_error("pann_hcnng_build: n too large for 32-bit edge offsets"); return PANN_ERR_BAD_ARG; }
   // per-level buffers, sized once for the worst level: clusters that still split are longer than cluster_size; a tree has at
   // most n / (cluster_size / 2) + 1 leaves only when every split is even, so the leaf arrays take the safe bound n + 1
   const size_t ncl_cap = (size_t)(gn / cluster_size) + 2 * group + 2;
-  arena.add(b_ids, gn * 4); arena.add(b_new, gn * 4); arena.add(b_first, (gn + 1) * 4); arena.add(b_scan, (gn + 1) * 4);
-  arena.add(b_pos, n * 4); arena.add(b_deg, n * 4); arena.add(b_leaflo, n * 4); arena.add(b_nnids, n * m * 4); arena.add(b_nnd, n * m * 4);
-  arena.add(b_ka, n * m * 8); arena.add(b_kb, n * m * 8); arena.add(b_par, n * 4); arena.add(b_rnk, n); arena.add(b_dgr, n);
-  arena.add(b_tmp, std::max(scan_tmp, sort_tmp) + 256);
-  arena.add(d_sc, ncl_cap * sizeof(SplitCluster)); arena.add(d_tbase, (ncl_cap + 1) * 4); arena.add(d_same, ncl_cap * 4);
-  arena.add(d_scat, ncl_cap * sizeof(ScatterCluster)); arena.add(d_n0, ncl_cap * 4);
-  arena.add(d_loff, (n + 2) * 8); arena.add(d_seg_b, (n + 1) * 4); arena.add(d_seg_e, (n + 1) * 4);
-  if (arena.commit()) { set_error("pann_hcnng_build: hipMalloc failed"); return PANN_ERR_HIP; }
+  // The builder's scratch arrays are carved out of ONE allocation: at 10M points the forest needs ~6 GB in twenty arrays, and
+  // twenty hipMalloc / hipFree pairs of that size cost more than the tree phase itself.  It is owned by this call, not kept on
+  // the handle; every array has 16 bytes at least, so none is empty.
+  uint32_t *b_ids, *b_new, *b_first, *b_scan, *b_pos, *b_deg, *b_leaflo, *b_nnids, *d_tbase, *d_same, *d_n0, *d_seg_b, *d_seg_e;
+  float* b_nnd; uint64_t *b_ka, *b_kb, *d_loff; int32_t* b_par; uint8_t *b_rnk, *b_dgr; void* b_tmp;
+  SplitCluster* d_sc; ScatterCluster* d_scat;
+  HBuf arena;
+  if (int rc = carve_into(arena, 0, [&](Carve& c) {
+    auto arr = [&](auto*& p, size_t count) {
+      using T = std::remove_reference_t<decltype(*p)>;
+      p = c.take<T>(std::max<size_t>(count, (16 + sizeof(T) - 1) / sizeof(T)));
+    };
+    arr(b_ids, gn); arr(b_new, gn); arr(b_first, gn + 1); arr(b_scan, gn + 1);
+    arr(b_pos, n); arr(b_deg, n); arr(b_leaflo, n); arr(b_nnids, n * m); arr(b_nnd, n * m);
+    arr(b_ka, n * m); arr(b_kb, n * m); arr(b_par, n); arr(b_rnk, n); arr(b_dgr, n);
+    b_tmp = c.take<uint8_t>(std::max(scan_tmp, sort_tmp), 256);
+    arr(d_sc, ncl_cap); arr(d_tbase, ncl_cap + 1); arr(d_same, ncl_cap); arr(d_scat, ncl_cap); arr(d_n0, ncl_cap);
+    arr(d_loff, n + 2); arr(d_seg_b, n + 1); arr(d_seg_e, n + 1);
+  })) return rc;
   for (uint64_t v0 = 0; v0 < n; v0 += launch_slice_blocks(64)) {
     hipLaunchKernelGGL(degree_init_kernel, dim3((uint32_t)std::min<uint64_t>(launch_slice_blocks(64), n - v0)), dim3(64), 0, st, ix.graph,
-                       ix.gstride, b_deg.as<uint32_t>(), v0, n);
+                       ix.gstride, b_deg, v0, n);
     PANN_HIP(hipGetLastError());
   }
 
@@ -414,8 +389,8 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
   for (uint32_t tg = 0; tg < num_clusters; tg += group) {
    const uint32_t ng = std::min(group, num_clusters - tg);            // trees tg .. tg+ng-1 in this forest
    const auto tf0 = now();
-   uint32_t* fids = b_ids.as<uint32_t>();
-   uint32_t* fnew = b_new.as<uint32_t>();
+   uint32_t* fids = b_ids;
+   uint32_t* fnew = b_new;
    std::vector<std::vector<uint64_t>> forest_leaves(ng);              // leaf start positions per tree (local to the tree)
    {
     const uint64_t tot = (uint64_t)ng * n;
@@ -441,21 +416,21 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
       for (size_t ci = 0; ci < ncl; ci++) { tile_base[ci] = (uint32_t)ntiles; ntiles += (sc[ci].len + 63) / 64; }
       tile_base[ncl] = (uint32_t)ntiles;
       const size_t nt = (size_t)ntiles;
-      PANN_HIP(hipMemcpyAsync(d_sc.p, sc.data(), ncl * sizeof(SplitCluster), hipMemcpyHostToDevice, st));
-      PANN_HIP(hipMemcpyAsync(d_tbase.p, tile_base.data(), (ncl + 1) * 4, hipMemcpyHostToDevice, st));
-      PANN_HIP(hipMemsetAsync(b_first.p, 0, (tot + 1) * 4, st));
-#define CALL_TS(DT, MT, L, N1) hipLaunchKernelGGL((tree_split_kernel<DT, MT, L, N1>), dim3((uint32_t)nt), dim3(PANN_WAVE), qb, st, pv, ix.dbytes, fids, d_sc.as<SplitCluster>(), d_tbase.as<uint32_t>(), (uint32_t)ncl, b_first.as<uint32_t>(), d_same.as<uint32_t>())
+      PANN_HIP(hipMemcpyAsync(d_sc, sc.data(), ncl * sizeof(SplitCluster), hipMemcpyHostToDevice, st));
+      PANN_HIP(hipMemcpyAsync(d_tbase, tile_base.data(), (ncl + 1) * 4, hipMemcpyHostToDevice, st));
+      PANN_HIP(hipMemsetAsync(b_first, 0, (tot + 1) * 4, st));
+#define CALL_TS(DT, MT, L, N1) hipLaunchKernelGGL((tree_split_kernel<DT, MT, L, N1>), dim3((uint32_t)nt), dim3(PANN_WAVE), qb, st, pv, ix.dbytes, fids, d_sc, d_tbase, (uint32_t)ncl, b_first, d_same)
       PANN_TYPE_SWITCH(ix, CALL_TS);
 #undef CALL_TS
       PANN_HIP(hipGetLastError());
       size_t tb = scan_tmp;
-      PANN_HIP(rocprim::exclusive_scan(b_tmp.p, tb, b_first.as<uint32_t>(), b_scan.as<uint32_t>(), 0u, (size_t)tot + 1, rocprim::plus<uint32_t>(), st));
+      PANN_HIP(rocprim::exclusive_scan(b_tmp, tb, b_first, b_scan, 0u, (size_t)tot + 1, rocprim::plus<uint32_t>(), st));
       // per-cluster first-side counts and identical-pivot flags back to the host (a few KB)
       std::vector<uint32_t> h_same(ncl), h_n0(ncl);
-      hipLaunchKernelGGL(cluster_counts_kernel, dim3((uint32_t)((ncl + 255) / 256)), dim3(256), 0, st, b_scan.as<uint32_t>(),
-                         d_sc.as<SplitCluster>(), (uint32_t)ncl, d_n0.as<uint32_t>());
-      PANN_HIP(hipMemcpyAsync(h_same.data(), d_same.p, ncl * 4, hipMemcpyDeviceToHost, st));
-      PANN_HIP(hipMemcpyAsync(h_n0.data(), d_n0.p, ncl * 4, hipMemcpyDeviceToHost, st));
+      hipLaunchKernelGGL(cluster_counts_kernel, dim3((uint32_t)((ncl + 255) / 256)), dim3(256), 0, st, b_scan,
+                         d_sc, (uint32_t)ncl, d_n0);
+      PANN_HIP(hipMemcpyAsync(h_same.data(), d_same, ncl * 4, hipMemcpyDeviceToHost, st));
+      PANN_HIP(hipMemcpyAsync(h_n0.data(), d_n0, ncl * 4, hipMemcpyDeviceToHost, st));
       PANN_HIP(hipStreamSynchronize(st));
       std::vector<ScatterCluster> scat(ncl);
       std::vector<Cl> next;
@@ -469,10 +444,10 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
         next.push_back(Cl{sc[ci].lo, n0, hc_mix_host(hc_mix_host(r) + 0 + 17)});     // rnd.fork(0) :85
         next.push_back(Cl{sc[ci].lo + n0, sc[ci].len - n0, hc_mix_host(hc_mix_host(r) + 1 + 17)});
       }
-      PANN_HIP(hipMemcpyAsync(d_scat.p, scat.data(), ncl * sizeof(ScatterCluster), hipMemcpyHostToDevice, st));
+      PANN_HIP(hipMemcpyAsync(d_scat, scat.data(), ncl * sizeof(ScatterCluster), hipMemcpyHostToDevice, st));
       PANN_HIP(hipMemcpyAsync(fnew, fids, tot * 4, hipMemcpyDeviceToDevice, st));     // finished clusters keep their place
-      hipLaunchKernelGGL(tree_scatter_kernel, dim3((uint32_t)nt), dim3(64), 0, st, fids, fnew, b_first.as<uint32_t>(),
-                         b_scan.as<uint32_t>(), d_scat.as<ScatterCluster>(), d_tbase.as<uint32_t>(), (uint32_t)ncl);
+      hipLaunchKernelGGL(tree_scatter_kernel, dim3((uint32_t)nt), dim3(64), 0, st, fids, fnew, b_first,
+                         b_scan, d_scat, d_tbase, (uint32_t)ncl);
       PANN_HIP(hipGetLastError());
       PANN_HIP(hipStreamSynchronize(st));   // the host vectors of this level go out of scope
       std::swap(fids, fnew);
@@ -491,18 +466,19 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
 
     // ---- all-pairs 10-NN of every leaf (device ids, no host copy) ----
     HBuf d_tseg, d_ta0;
-    PANN_HIP(hipMemcpyAsync(d_loff.p, leaf_off.data(), (nleaves + 1) * 8, hipMemcpyHostToDevice, st));
+    PANN_HIP(hipMemcpyAsync(d_loff, leaf_off.data(), (nleaves + 1) * 8, hipMemcpyHostToDevice, st));
     if (leaf_knn_rows_eligible(ix, m)) {     // one-byte element types: lane-owns-row kernel (leaf_knn.hip)
-      if (int rc = leaf_knn_rows_dev(ix, ws, st, ids, d_loff.as<uint64_t>(), leaf_off.data(), nleaves, m, 1, b_nnids.as<uint32_t>(), b_nnd.as<float>())) return rc;
+      if (int rc = leaf_knn_rows_dev(ix, ws, st, ids, d_loff, leaf_off.data(), nleaves, m, 1, b_nnids, b_nnd)) return rc;
     } else {
       std::vector<uint32_t> tseg, ta0;
       append_tiles(leaf_off.data(), nleaves, std::back_inserter(tseg), std::back_inserter(ta0));
-      if (d_tseg.alloc(tseg.size() * 4) || d_ta0.alloc(ta0.size() * 4)) { set_error("pann_hcnng_build: hipMalloc failed"); return PANN_ERR_HIP; }
-      PANN_HIP(hipMemcpyAsync(d_tseg.p, tseg.data(), tseg.size() * 4, hipMemcpyHostToDevice, st));
-      PANN_HIP(hipMemcpyAsync(d_ta0.p, ta0.data(), ta0.size() * 4, hipMemcpyHostToDevice, st));
+      if (int rc = d_tseg.ensure(tseg.size() * 4)) return rc;
+      if (int rc = d_ta0.ensure(ta0.size() * 4)) return rc;
+      PANN_HIP(hipMemcpyAsync(d_tseg.buf, tseg.data(), tseg.size() * 4, hipMemcpyHostToDevice, st));
+      PANN_HIP(hipMemcpyAsync(d_ta0.buf, ta0.data(), ta0.size() * 4, hipMemcpyHostToDevice, st));
       DenseTopkCall c;
-      c.a_ids = c.b_ids = ids; c.a_off = c.b_off = d_loff.as<uint64_t>(); c.tile_seg = d_tseg.as<uint32_t>(); c.tile_a0 = d_ta0.as<uint32_t>();
-      c.ntiles = (uint32_t)tseg.size(); c.na = c.nb = n; c.m = m; c.exclude_same = 1; c.out_ids = b_nnids.as<uint32_t>(); c.out_dists = b_nnd.as<float>();
+      c.a_ids = c.b_ids = ids; c.a_off = c.b_off = d_loff; c.tile_seg = d_tseg.as<uint32_t>(); c.tile_a0 = d_ta0.as<uint32_t>();
+      c.ntiles = (uint32_t)tseg.size(); c.na = c.nb = n; c.m = m; c.exclude_same = 1; c.out_ids = b_nnids; c.out_dists = b_nnd;
       if (int rc = dense_topk_dev(ix, ws, st, c)) return rc;
       PANN_HIP(hipStreamSynchronize(st));        // the host tile vectors go out of scope
     }
@@ -510,27 +486,27 @@ int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32
     const auto t2 = now();
 
     // ---- edges, per-leaf sort (less_dup order), Kruskal, process_edges ----
-    hipLaunchKernelGGL(invert_perm, dim3(nb256), dim3(256), 0, st, ids, b_pos.as<uint32_t>(), n);
-    hipLaunchKernelGGL(leaf_lo_kernel, dim3(nleaves), dim3(64), 0, st, d_loff.as<uint64_t>(), nleaves, b_leaflo.as<uint32_t>());
+    hipLaunchKernelGGL(invert_perm, dim3(nb256), dim3(256), 0, st, ids, b_pos, n);
+    hipLaunchKernelGGL(leaf_lo_kernel, dim3(nleaves), dim3(64), 0, st, d_loff, nleaves, b_leaflo);
     const uint64_t ne = n * m;
-    hipLaunchKernelGGL(leaf_edges_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, st, b_nnids.as<uint32_t>(), b_nnd.as<float>(),
-                       b_pos.as<uint32_t>(), b_leaflo.as<uint32_t>(), m, n, b_ka.as<uint64_t>());
+    hipLaunchKernelGGL(leaf_edges_kernel, dim3((uint32_t)((ne + 255) / 256)), dim3(256), 0, st, b_nnids, b_nnd,
+                       b_pos, b_leaflo, m, n, b_ka);
     PANN_HIP(hipGetLastError());
     std::vector<uint32_t> seg_b(nleaves), seg_e(nleaves);
     for (uint32_t l = 0; l < nleaves; l++) { seg_b[l] = (uint32_t)(leaf_off[l] * m); seg_e[l] = (uint32_t)(leaf_off[l + 1] * m); }
-    PANN_HIP(hipMemcpyAsync(d_seg_b.p, seg_b.data(), nleaves * 4, hipMemcpyHostToDevice, st));
-    PANN_HIP(hipMemcpyAsync(d_seg_e.p, seg_e.data(), nleaves * 4, hipMemcpyHostToDevice, st));
+    PANN_HIP(hipMemcpyAsync(d_seg_b, seg_b.data(), nleaves * 4, hipMemcpyHostToDevice, st));
+    PANN_HIP(hipMemcpyAsync(d_seg_e, seg_e.data(), nleaves * 4, hipMemcpyHostToDevice, st));
     size_t tb = sort_tmp;
-    PANN_HIP(rocprim::segmented_radix_sort_keys(b_tmp.p, tb, b_ka.as<uint64_t>(), b_kb.as<uint64_t>(), (unsigned)ne, nleaves,
-                                                (const uint32_t*)d_seg_b.as<uint32_t>(), (const uint32_t*)d_seg_e.as<uint32_t>(), 0, 64, st));
+    PANN_HIP(rocprim::segmented_radix_sort_keys(b_tmp, tb, b_ka, b_kb, (unsigned)ne, nleaves,
+                                                (const uint32_t*)d_seg_b, (const uint32_t*)d_seg_e, 0, 64, st));
     MstArgs ma{};
-    ma.keys = b_kb.as<uint64_t>(); ma.leaf_off = d_loff.as<uint64_t>(); ma.nleaves = nleaves; ma.m = m; ma.ids = ids;
-    ma.graph = ix.graph; ma.gstride = ix.gstride; ma.max_deg = ix.max_deg; ma.deg = b_deg.as<uint32_t>(); ma.mst_deg = mst_deg;
+    ma.keys = b_kb; ma.leaf_off = d_loff; ma.nleaves = nleaves; ma.m = m; ma.ids = ids;
+    ma.graph = ix.graph; ma.gstride = ix.gstride; ma.max_deg = ix.max_deg; ma.deg = b_deg; ma.mst_deg = mst_deg;
     if (slab) {   // slotted rows: local tree tg + j owns slots [(tg+j)*mst_deg, (tg+j+1)*mst_deg)
-      hipLaunchKernelGGL(fill_u32_hc, dim3(nb256), dim3(256), 0, st, b_deg.as<uint32_t>(), n, (tg + j) * mst_deg);
+      hipLaunchKernelGGL(fill_u32_hc, dim3(nb256), dim3(256), 0, st, b_deg, n, (tg + j) * mst_deg);
       ma.graph = slab; ma.gstride = slab_stride; ma.max_deg = (tg + j + 1) * mst_deg;
     }
-    ma.g_parent = b_par.as<int32_t>(); ma.g_rank = b_rnk.as<uint8_t>(); ma.g_degree = b_dgr.as<uint8_t>();
+    ma.g_parent = b_par; ma.g_rank = b_rnk; ma.g_degree = b_dgr;
     uint64_t max_leaf = 2;
     for (uint32_t l = 0; l < nleaves; l++) max_leaf = std::max<uint64_t>(max_leaf, leaf_off[l + 1] - leaf_off[l]);
     ma.lds_cap = (uint32_t)std::min<uint64_t>((max_leaf + 63) / 64 * 64, 4096);     // 12 bytes of LDS per member

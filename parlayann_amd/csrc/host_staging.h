@@ -10,6 +10,7 @@
 #include <string>
 
 #include "../../include/pann.h"
+#include "scratch_carve.h"
 
 namespace pann {
 
@@ -32,7 +33,7 @@ struct PackedLayout {
   size_t direct_from = SIZE_MAX;      // one-row pieces of this many bytes or more are direct (set before the first add)
   bool any_direct = false;
 
-  static size_t align(size_t x) { return (x + 255) & ~(size_t)255; }
+  static size_t align(size_t x) { return Carve::align(x); }
 
   // `rows` rows of row_bytes each, host_stride bytes apart on the host and dense in the region (bitmap rows of a wider table)
   int add_rows(const void* host, size_t rows, size_t row_bytes, size_t host_stride, size_t slack = 0) {

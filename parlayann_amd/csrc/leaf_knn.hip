@@ -211,8 +211,8 @@ int leaf_knn_rows_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, cons
     for (uint64_t a = h_off[s]; a < h_off[s + 1]; a += LK_ROWS) { tseg.push_back((uint32_t)s); ta0.push_back((uint32_t)a); }
   if (tseg.empty()) return PANN_OK;
   const size_t nt = tseg.size();
-  if (int rc = ws.ensure(nt * 8 + 256)) return rc;
-  uint32_t* d_tseg = (uint32_t*)ws.buf; uint32_t* d_ta0 = d_tseg + nt;
+  uint32_t *d_tseg, *d_ta0;
+  if (int rc = carve_into(ws, 256, [&](Carve& c) { d_tseg = c.take<uint32_t>(nt); d_ta0 = c.take<uint32_t>(nt); })) return rc;
   PANN_HIP(hipMemcpyAsync(d_tseg, tseg.data(), nt * 4, hipMemcpyHostToDevice, st));
   PANN_HIP(hipMemcpyAsync(d_ta0, ta0.data(), nt * 4, hipMemcpyHostToDevice, st));
   PANN_HIP(hipStreamSynchronize(st));                                          // the host vectors go out of scope

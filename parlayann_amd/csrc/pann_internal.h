@@ -5,9 +5,11 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include <algorithm>
+#include <chrono>
 #include <string>
 
 #include "../../include/pann.h"
+#include "scratch_carve.h"
 #include "search_plan.h"
 #include "search_call.h"
 
@@ -98,7 +100,9 @@ struct DenseTopkCall {
   uint32_t* out_ids = nullptr; float* out_dists = nullptr;      // na x m each
 };
 
-// the one growable device buffer: kernel scratch, staging regions, tables kept on a handle (grown on demand, never shrunk)
+// the one growable device buffer: kernel scratch, staging regions, tables kept on a handle (grown on demand, never shrunk).
+// A buffer of several arrays is laid out by ONE function that takes them from a Carve; carve_into(ws, tail_slack, layout) runs it
+// dry to size the buffer, then on the buffer to set the pointers (scratch_carve.h).
 struct Workspace {
   void* buf = nullptr; size_t bytes = 0;
   int ensure(size_t need);
@@ -109,6 +113,30 @@ struct Workspace {
 void set_error(const std::string& s);
 int hip_fail(hipError_t e, const char* what);
 #define PANN_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return pann::hip_fail(e_, #call); } while (0)
+
+// a device buffer owned by ONE call and freed on every return path: what is too large to stay on the handle, or as large as a
+// count the device has just produced.  ensure() allocates exactly what is asked (16 bytes at least), carve_into() accepts it.
+struct HBuf {
+  void* buf = nullptr; size_t bytes = 0;
+  HBuf() = default;
+  HBuf(const HBuf&) = delete;
+  HBuf& operator=(const HBuf&) = delete;
+  ~HBuf() { if (buf) (void)hipFree(buf); }
+  int ensure(size_t need) {
+    if (buf && need <= bytes) return PANN_OK;
+    if (buf) { PANN_HIP(hipFree(buf)); buf = nullptr; bytes = 0; }
+    need = std::max<size_t>(need, 16);
+    PANN_HIP(hipMalloc(&buf, need));
+    bytes = need;
+    return PANN_OK;
+  }
+  template <typename T> T* as() const { return (T*)buf; }
+};
+
+// the phase timers of the builders' statistics
+using TimePoint = std::chrono::steady_clock::time_point;
+inline TimePoint now() { return std::chrono::steady_clock::now(); }
+inline double secs(TimePoint a, TimePoint b) { return std::chrono::duration<double>(b - a).count(); }
 
 // beam_search.hip
 size_t search_workspace_bytes(const DeviceIndex& ix, const SearchArgs& a);

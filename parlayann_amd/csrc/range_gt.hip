@@ -375,8 +375,6 @@ __global__ void __launch_bounds__(256) range_join_offsets_kernel(const uint64_t*
   if (i <= nq) offsets[i] = pos[i * nsplit];
 }
 
-static size_t rj_align(size_t x) { return (x + 255) & ~(size_t)255; }
-
 template <bool FILL>
 static int range_join_launch(const DeviceIndex& ix, hipStream_t st, const RangeJoinArgs& A, dim3 grid) {
   dispatch_type_metric(ix.dtype, ix.metric, [&](auto dt, auto mt) {
@@ -393,18 +391,18 @@ static int range_join_launch(const DeviceIndex& ix, hipStream_t st, const RangeJ
   return PANN_OK;
 }
 
-static RangeJoinArgs range_join_args(const DeviceIndex& ix, Workspace& ws, const uint8_t* d_q, uint64_t q_stride, uint64_t nq,
-                                     float radius, uint32_t nsplit) {
-  RangeJoinArgs A{};
+// The arguments of both passes, with the two arrays of `ws`: a count per (query, piece) and their scan.  The count call grows ws
+// here; the fill call, with the same arguments, finds it large enough, so the buffer stays where it was.
+static int range_join_args(const DeviceIndex& ix, Workspace& ws, const uint8_t* d_q, uint64_t q_stride, uint64_t nq,
+                           float radius, uint32_t nsplit, RangeJoinArgs& A) {
+  A = RangeJoinArgs{};
   A.points = ix.points; A.pstride = ix.pstride; A.dbytes = ix.dbytes;
   A.q = d_q; A.q_stride = q_stride; A.nq = nq; A.n = ix.n;
   A.nsplit = nsplit;
   A.per = ((ix.n + nsplit - 1) / nsplit + RJ_PIECE_ALIGN - 1) / RJ_PIECE_ALIGN * RJ_PIECE_ALIGN;
   A.radius = radius; A.exact = ix.exact;
   const size_t slots = (size_t)nq * nsplit;
-  A.counts = static_cast<uint32_t*>(ws.buf);
-  A.pos = reinterpret_cast<const uint64_t*>(static_cast<uint8_t*>(ws.buf) + rj_align(slots * 4));
-  return A;
+  return carve_into(ws, 0, [&](Carve& c) { A.counts = c.take<uint32_t>(slots); A.pos = c.take<uint64_t>(slots + 1); });
 }
 
 // pieces of the base per query tile: enough workgroups to fill the 256 CUs several times over (a workgroup keeps no state
@@ -422,8 +420,8 @@ int range_join_count_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, c
                          float radius, uint32_t nsplit, uint64_t* d_offsets) {
   if (nq == 0) return PANN_OK;
   const size_t slots = (size_t)nq * nsplit;
-  if (int rc = ws.ensure(rj_align(slots * 4) + rj_align((slots + 1) * 8))) return rc;
-  const RangeJoinArgs A = range_join_args(ix, ws, d_q, q_stride, nq, radius, nsplit);
+  RangeJoinArgs A;
+  if (int rc = range_join_args(ix, ws, d_q, q_stride, nq, radius, nsplit, A)) return rc;
   const dim3 grid((uint32_t)((nq + DT_A - 1) / DT_A), nsplit);
   if (int rc = range_join_launch<false>(ix, st, A, grid)) return rc;
   hipLaunchKernelGGL(range_join_scan_kernel, dim3(1), dim3(1024), 0, st, A.counts, (uint64_t)slots, const_cast<uint64_t*>(A.pos));
@@ -437,7 +435,8 @@ int range_join_count_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, c
 int range_join_fill_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq,
                         float radius, uint32_t nsplit, uint32_t* d_out_ids) {
   if (nq == 0) return PANN_OK;
-  RangeJoinArgs A = range_join_args(ix, ws, d_q, q_stride, nq, radius, nsplit);
+  RangeJoinArgs A;
+  if (int rc = range_join_args(ix, ws, d_q, q_stride, nq, radius, nsplit, A)) return rc;
   A.out_ids = d_out_ids;
   const dim3 grid((uint32_t)((nq + DT_A - 1) / DT_A), nsplit);
   return range_join_launch<true>(ix, st, A, grid);

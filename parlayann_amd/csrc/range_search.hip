@@ -291,8 +291,15 @@ int range_search_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const
   uint64_t hs_small = 1024;                                             // the largest table that lets all of them run (>= 16384 entries)
   while (hs_small < hs_worst && (hs_small * 2) * 8 * waves1 <= budget) hs_small <<= 1;
   hs_small = std::min(hs_worst, std::max<uint64_t>(hs_small, 16384));
-  const size_t head = 256 + ((size_t)nq * 4 + 255) / 256 * 256;         // counters + overflow list
-  if (int rc = ws.ensure(head + waves1 * hs_small * 8)) return rc;
+  // the workspace: a 256-byte counter block cleared as one (work_counter at +0, ovf_count at +64: the 4-byte read-back below),
+  // the overflow list, the seen-set tables of one pass
+  uint32_t *counters, *ovf; unsigned long long* table;
+  auto place = [&](uint64_t table_entries) {
+    return carve_into(ws, 0, [&](Carve& c) {
+      counters = c.take<uint32_t>(64); ovf = c.take<uint32_t>(nq); table = c.take<unsigned long long>(table_entries);
+    });
+  };
+  if (int rc = place(waves1 * hs_small)) return rc;
   RSArgs A{};
   A.pv = PointsView{ix.points, ix.pstride, ix.nch, ix.exact}; A.dbytes = ix.dbytes;
   A.graph = ix.graph; A.gstride = ix.gstride; A.n = ix.n;
@@ -302,13 +309,12 @@ int range_search_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const
   A.out_ids = d_out_ids; A.out_counts = d_out_counts; A.out_cmps = d_out_cmps; A.out_trunc = d_out_trunc;
   const size_t lds = query_lds_bytes(ix);
   auto launch = [&](uint64_t waves, uint64_t hsize, const uint32_t* qlist, uint64_t nlist, bool may_overflow) -> int {
-    uint8_t* w = static_cast<uint8_t*>(ws.buf);
-    A.work_counter = reinterpret_cast<uint32_t*>(w); A.ovf_count = reinterpret_cast<uint32_t*>(w + 64);
-    A.ovf_list = may_overflow ? reinterpret_cast<uint32_t*>(w + 256) : nullptr;
+    A.work_counter = counters; A.ovf_count = counters + 16;
+    A.ovf_list = may_overflow ? ovf : nullptr;
     A.qlist = qlist; A.nlist = nlist;
-    A.table = reinterpret_cast<unsigned long long*>(w + head); A.hsize = hsize;
-    PANN_HIP(hipMemsetAsync(w, 0, 256, st));
-    PANN_HIP(hipMemsetAsync(w + head, 0, waves * hsize * 8, st));       // tag 0 = never used
+    A.table = table; A.hsize = hsize;
+    PANN_HIP(hipMemsetAsync(counters, 0, 256, st));
+    PANN_HIP(hipMemsetAsync(table, 0, waves * hsize * 8, st));          // tag 0 = never used
 #define CALL_RS(DT, MT, L, N1) hipLaunchKernelGGL((range_search_kernel<DT, MT, L, N1>), dim3((uint32_t)waves), dim3(PANN_WAVE), lds, st, A)
     PANN_TYPE_SWITCH(ix, CALL_RS);
 #undef CALL_RS
@@ -318,17 +324,17 @@ int range_search_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const
   if (int rc = launch(waves1, hs_small, nullptr, nq, hs_small < hs_worst)) return rc;
   if (hs_small < hs_worst) {
     uint32_t novf = 0;
-    PANN_HIP(hipMemcpyAsync(&novf, static_cast<uint8_t*>(ws.buf) + 64, 4, hipMemcpyDeviceToHost, st));
+    PANN_HIP(hipMemcpyAsync(&novf, counters + 16, 4, hipMemcpyDeviceToHost, st));
     PANN_HIP(hipStreamSynchronize(st));
     if (novf) {
       const uint64_t waves2 = std::min<uint64_t>(novf, std::max<uint64_t>(1, budget / (hs_worst * 8)));
-      // the overflow list sits in the head of the workspace: growing the workspace would move it, so copy it out first
+      // the overflow list sits in the workspace: growing the workspace would move it, so copy it out first
       std::vector<uint32_t> h_ovf(novf);
-      PANN_HIP(hipMemcpy(h_ovf.data(), static_cast<uint8_t*>(ws.buf) + 256, (size_t)novf * 4, hipMemcpyDeviceToHost));
-      if (int rc = ws.ensure(head + waves2 * hs_worst * 8)) return rc;
-      PANN_HIP(hipMemcpyAsync(static_cast<uint8_t*>(ws.buf) + 256, h_ovf.data(), (size_t)novf * 4, hipMemcpyHostToDevice, st));
+      PANN_HIP(hipMemcpy(h_ovf.data(), ovf, (size_t)novf * 4, hipMemcpyDeviceToHost));
+      if (int rc = place(waves2 * hs_worst)) return rc;
+      PANN_HIP(hipMemcpyAsync(ovf, h_ovf.data(), (size_t)novf * 4, hipMemcpyHostToDevice, st));
       PANN_HIP(hipStreamSynchronize(st));                                 // h_ovf goes out of scope
-      if (int rc = launch(waves2, hs_worst, reinterpret_cast<const uint32_t*>(static_cast<uint8_t*>(ws.buf) + 256), novf, false)) return rc;
+      if (int rc = launch(waves2, hs_worst, ovf, novf, false)) return rc;
     }
   }
   return PANN_OK;

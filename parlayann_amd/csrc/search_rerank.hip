@@ -31,8 +31,6 @@ namespace {
 constexpr uint32_t RR_WAVES = 4;           // queries per workgroup of the register form (fewer when four long queries do not fit LDS)
 constexpr uint32_t PREP_MAX_BLOCKS = 4096; // 256 CUs x 16 one-wave blocks
 
-inline size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // ---- step 1: the queries ------------------------------------------------------------------------------------------------
 // One wave per row.  Without normalize the row is read straight from memory, 64 coordinates (256 B) at a time.  With it the
 // row is staged in LDS, lane 0 sums the squares in index order -- float product, double sum: the order is part of the
@@ -248,15 +246,14 @@ struct Scratch { uint8_t* qb; uint64_t qb_stride; uint8_t* sk; uint64_t sk_strid
 
 Scratch cut_scratch(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int normalize_first, int use_filter, void* base) {
   Scratch s{};
-  uint8_t* p = static_cast<uint8_t*>(base);
-  size_t off = 0;
+  Carve c(base);
   s.qb_stride = (quant.dbytes + 15) / 16 * 16;
-  s.qb = p + off; off += al256(nq * s.qb_stride);
-  if (use_filter) { s.sk_stride = sketch_row_bytes(quant.sk_kind, quant.d); s.sk = p + off; off += al256(nq * s.sk_stride); }
-  if (normalize_first) { s.nr_stride = ((uint64_t)quant.d * 4 + 15) / 16 * 16; s.nr = p + off; off += al256(nq * s.nr_stride); }
-  s.fids = reinterpret_cast<uint32_t*>(p + off); off += al256(nq * (size_t)beam * 4);
-  s.fsize = reinterpret_cast<uint32_t*>(p + off); off += al256(nq * 4);
-  s.bytes = off;
+  s.qb = c.take<uint8_t>(nq * s.qb_stride);
+  if (use_filter) { s.sk_stride = sketch_row_bytes(quant.sk_kind, quant.d); s.sk = c.take<uint8_t>(nq * s.sk_stride); }
+  if (normalize_first) { s.nr_stride = ((uint64_t)quant.d * 4 + 15) / 16 * 16; s.nr = c.take<uint8_t>(nq * s.nr_stride); }
+  s.fids = c.take<uint32_t>(nq * (size_t)beam);
+  s.fsize = c.take<uint32_t>(nq);
+  s.bytes = c.bytes();
   return s;
 }
 

@@ -11,14 +11,10 @@
 // The alpha test `alpha * d(p*,p') <= d(p,p')` is evaluated in double exactly as the reference
 // does (:111).
 #include <cstring>
-#include <chrono>
 #include <vector>
 
-#include <rocprim/device/device_radix_sort.hpp>
-#include <rocprim/device/device_scan.hpp>
-#include <rocprim/device/device_segmented_radix_sort.hpp>
-
 #include "pann_device.h"
+#include "rocprim_temp.h"
 
 #ifndef PANN_PRUNE_MINWAVES
 #define PANN_PRUNE_MINWAVES 6   /* the greedy prune is latency-bound: the f16 / bf16 variants take 104 VGPRs (4 waves per SIMD) unless told otherwise, 77 with this */
@@ -512,36 +508,6 @@ __global__ void __launch_bounds__(PANN_WAVE) sort_rows_kernel(PointsView pv, uin
 // host orchestration
 // ---------------------------------------------------------------------------------------------
 
-struct Bump {
-  uint8_t* base; size_t cap; size_t off = 0; bool dry;
-  Bump(void* b, size_t c) : base((uint8_t*)b), cap(c), dry(b == nullptr) {}
-  template <typename T> T* take(size_t count) {
-    off = (off + 255) / 256 * 256;
-    T* p = dry ? nullptr : reinterpret_cast<T*>(base + off);
-    off += count * sizeof(T);
-    return p;
-  }
-};
-
-static size_t seg_sort_temp_bytes(uint32_t size, uint32_t segs) {
-  size_t t = 0;
-  (void)rocprim::segmented_radix_sort_keys(nullptr, t, (uint64_t*)nullptr, (uint64_t*)nullptr, size, segs,
-                                           (const uint32_t*)nullptr, (const uint32_t*)nullptr, 0, 64, (hipStream_t)0);
-  return t;
-}
-static size_t sort_temp_bytes(uint32_t size) {
-  size_t t = 0;
-  (void)rocprim::radix_sort_keys(nullptr, t, (uint64_t*)nullptr, (uint64_t*)nullptr, size, 0, 64, (hipStream_t)0);
-  return t;
-}
-static size_t scan_temp_bytes(uint32_t size) {
-  size_t t = 0;
-  (void)rocprim::exclusive_scan(nullptr, t, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, size,
-                                rocprim::plus<uint32_t>(), (hipStream_t)0);
-  return t;
-}
-
-
 // keys -> segmented sort -> greedy.  keys_a holds the unsorted keys, keys_b receives the sorted ones.
 static int run_prune(const DeviceIndex& ix, PruneArgs pa, GreedyArgs ga, uint64_t* keys_a, uint64_t* keys_b,
                      uint32_t total_keys, void* sort_tmp, size_t sort_tmp_bytes, hipStream_t st, uint32_t max_seg_len) {
@@ -591,21 +557,14 @@ int robust_prune_batch_host(const DeviceIndex& ix, Workspace& ws, hipStream_t st
     if (cand_ids[j] >= ix.n) { set_error("pann_robust_prune_batch: candidate id out of range"); return PANN_ERR_BAD_ARG; }
   if (total >= 0xFFFFFFF0ull) { set_error("pann_robust_prune_batch: too many candidates in one call"); return PANN_ERR_BAD_ARG; }
   const size_t stmp = seg_sort_temp_bytes((uint32_t)total, (uint32_t)m);
-  auto layout = [&](Bump& b, uint32_t*& d_own, uint32_t*& d_cid, float*& d_cd, uint64_t*& d_base, uint32_t*& d_cnt,
-                    uint32_t*& d_seg, uint32_t*& d_send, uint64_t*& ka, uint64_t*& kb, uint32_t*& d_rows,
-                    uint32_t*& d_rcnt, uint32_t*& d_dc, void*& d_tmp) {
+  uint32_t *d_own, *d_cid, *d_cnt, *d_seg, *d_send, *d_rows, *d_rcnt, *d_dc; float* d_cd; uint64_t *d_base, *ka, *kb; void* d_tmp;
+  if (int rc = carve_into(ws, 4096, [&](Carve& b) {
     d_own = b.take<uint32_t>(m); d_cid = b.take<uint32_t>(ncand + 1); d_cd = b.take<float>(ncand + 1);
     d_base = b.take<uint64_t>(m); d_cnt = b.take<uint32_t>(m); d_seg = b.take<uint32_t>(m); d_send = b.take<uint32_t>(m);
     ka = b.take<uint64_t>(total + 1); kb = b.take<uint64_t>(total + 1);
     d_rows = b.take<uint32_t>(m * R); d_rcnt = b.take<uint32_t>(m); d_dc = b.take<uint32_t>(m);
-    d_tmp = b.take<uint8_t>(stmp + 16);
-  };
-  uint32_t *d_own, *d_cid, *d_cnt, *d_seg, *d_send, *d_rows, *d_rcnt, *d_dc; float* d_cd; uint64_t *d_base, *ka, *kb; void* d_tmp;
-  Bump dry(nullptr, 0);
-  layout(dry, d_own, d_cid, d_cd, d_base, d_cnt, d_seg, d_send, ka, kb, d_rows, d_rcnt, d_dc, d_tmp);
-  if (int rc = ws.ensure(dry.off + 4096)) return rc;
-  Bump b(ws.buf, ws.bytes);
-  layout(b, d_own, d_cid, d_cd, d_base, d_cnt, d_seg, d_send, ka, kb, d_rows, d_rcnt, d_dc, d_tmp);
+    d_tmp = b.take<uint8_t>(stmp, 16);
+  })) return rc;
   PANN_HIP(hipMemcpyAsync(d_own, owners, m * 4, hipMemcpyHostToDevice, st));
   if (ncand) PANN_HIP(hipMemcpyAsync(d_cid, cand_ids, ncand * 4, hipMemcpyHostToDevice, st));
   if (cand_dists && ncand) PANN_HIP(hipMemcpyAsync(d_cd, cand_dists, ncand * 4, hipMemcpyHostToDevice, st));
@@ -645,17 +604,12 @@ int robust_prune_batch_host(const DeviceIndex& ix, Workspace& ws, hipStream_t st
 //   phase B  vamana_apply_rows_dev   : write the rows of the WHOLE batch (:268-270), then the reverse edges grouped by
 //            target, append-or-re-prune (:278-300) -- a deterministic function of (graph, batch ids, rows)
 // insert_batch_dev = A then B on one device.
-namespace {
-auto now_ = [] { return std::chrono::steady_clock::now(); };
-template <class A, class B> double secs_(A a, B b) { return std::chrono::duration<double>(b - a).count(); }
-}  // namespace
-
 int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& search_ws, hipStream_t st, const uint32_t* d_batch,
                             uint32_t m, uint32_t start, uint32_t R, uint32_t L, double alpha, uint32_t* vcap_io,
                             uint32_t* d_rows, pann_build_stats* stats) {
   if (m == 0) return PANN_OK;
   if (R == 0 || R > ix.max_deg || R > 1024) { set_error("vamana insert: R must be in [1, min(max_deg,1024)]"); return PANN_ERR_BAD_ARG; }
-  const auto t0 = now_();
+  const auto t0 = now();
   uint32_t vcap = *vcap_io;
   for (int attempt = 0;; attempt++) {
     const uint32_t seg_stride = vcap + ix.gstride;
@@ -665,7 +619,7 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
     const size_t stmp = std::max(seg_sort_temp_bytes((uint32_t)total_keys, m), ordered ? sort_temp_bytes(m) : (size_t)0);
     uint32_t *d_start, *d_vis_ids, *d_vis_cnt, *d_dcs, *d_seg, *d_send, *d_rcnt, *d_dc, *d_order;
     float* d_vis_d; uint64_t *d_base, *ka, *kb; void* d_tmp;
-    auto layout = [&](Bump& b) {
+    if (int rc = carve_into(ws, 4096, [&](Carve& b) {
       d_start = b.take<uint32_t>(4);
       d_order = b.take<uint32_t>(ordered ? m : 1);
       d_vis_ids = b.take<uint32_t>((size_t)m * vcap); d_vis_d = b.take<float>((size_t)m * vcap);
@@ -673,11 +627,8 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
       d_base = b.take<uint64_t>(m); d_seg = b.take<uint32_t>(m); d_send = b.take<uint32_t>(m);
       ka = b.take<uint64_t>(total_keys + 1); kb = b.take<uint64_t>(total_keys + 1);
       d_rcnt = b.take<uint32_t>(m); d_dc = b.take<uint32_t>(m);
-      d_tmp = b.take<uint8_t>(stmp + 16);
-    };
-    Bump dry(nullptr, 0); layout(dry);
-    if (int rc = ws.ensure(dry.off + 4096)) return rc;
-    Bump b(ws.buf, ws.bytes); layout(b);
+      d_tmp = b.take<uint8_t>(stmp, 16);
+    })) return rc;
 
     // ---- 1. beam search from `start` for every batch point (:247-259) ----
     PANN_HIP(hipMemcpyAsync(d_start, &start, 4, hipMemcpyHostToDevice, st));
@@ -704,7 +655,7 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
       if (attempt >= 6) { set_error("vamana insert: visited lists keep overflowing"); return PANN_ERR_OVERFLOW; }
       vcap *= 2; *vcap_io = vcap; continue;
     }
-    const auto t1 = now_();
+    const auto t1 = now();
 
     // ---- 2. robustPrune(index, visited) for every batch point (:264) ----
     hipLaunchKernelGGL(fixed_stride_setup_kernel, dim3((m + 255) / 256), dim3(256), 0, st, d_base, d_seg, m, vcap, seg_stride);
@@ -721,7 +672,7 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
     ga.dcmps = d_dc; ga.m = m; ga.order = pa.order;
     if (int rc = run_prune(ix, pa, ga, ka, kb, (uint32_t)total_keys, d_tmp, stmp, st, seg_stride)) return rc;
     PANN_HIP(hipStreamSynchronize(st));
-    const auto t2 = now_();
+    const auto t2 = now();
     if (stats) {
       std::vector<uint32_t> hs(m), hp(m), hv(m);
       PANN_HIP(hipMemcpy(hs.data(), d_dcs, (size_t)m * 4, hipMemcpyDeviceToHost));
@@ -736,7 +687,7 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
           if (stats->per_point_dist_cmps) stats->per_point_dist_cmps[hb[i]] += hs[i] + hp[i];
         }
       }
-      stats->t_search_s += secs_(t0, t1); stats->t_prune_s += secs_(t1, t2);
+      stats->t_search_s += secs(t0, t1); stats->t_prune_s += secs(t1, t2);
     }
     return PANN_OK;
   }
@@ -746,24 +697,21 @@ int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, 
                           const uint32_t* d_rows, uint32_t R, double alpha, pann_build_stats* stats) {
   if (m == 0) return PANN_OK;
   if (R == 0 || R > ix.max_deg || R > 1024) { set_error("vamana insert: R must be in [1, min(max_deg,1024)]"); return PANN_ERR_BAD_ARG; }
-  const auto t2 = now_();
+  const auto t2 = now();
   const uint64_t total_edges = (uint64_t)m * R;
   if (total_edges >= 0xFFFFFFF0ull) { set_error("vamana insert: batch too large"); return PANN_ERR_BAD_ARG; }
-  const size_t stmp = std::max(sort_temp_bytes((uint32_t)total_edges), scan_temp_bytes((uint32_t)total_edges));
+  const size_t stmp = std::max(sort_temp_bytes((uint32_t)total_edges), scan_temp_bytes<uint32_t>((uint32_t)total_edges));
   uint32_t *d_heads, *d_gidx, *d_gstart, *d_src, *d_hown, *d_hcnt, *d_hlen, *d_scalars;
   uint64_t *ek_a, *ek_b, *d_hbase; void* d_tmp;
-  auto layout = [&](Bump& b) {
+  if (int rc = carve_into(ws, 4096, [&](Carve& b) {
     d_scalars = b.take<uint32_t>(64);   // [1] nvalid, [2] ngroups, [3] nheavy
     ek_a = b.take<uint64_t>(total_edges + 1); ek_b = b.take<uint64_t>(total_edges + 1);
     d_heads = b.take<uint32_t>(total_edges + 1); d_gidx = b.take<uint32_t>(total_edges + 1);
     d_gstart = b.take<uint32_t>(total_edges + 1); d_src = b.take<uint32_t>(total_edges + 1);
     d_hown = b.take<uint32_t>(total_edges + 1); d_hbase = b.take<uint64_t>(total_edges + 1);
     d_hcnt = b.take<uint32_t>(total_edges + 1); d_hlen = b.take<uint32_t>(total_edges + 1);
-    d_tmp = b.take<uint8_t>(stmp + 16);
-  };
-  Bump dry(nullptr, 0); layout(dry);
-  if (int rc = ws.ensure(dry.off + 4096)) return rc;
-  Bump b(ws.buf, ws.bytes); layout(b);
+    d_tmp = b.take<uint8_t>(stmp, 16);
+  })) return rc;
 
   // ---- :268-270 write the new out-neighbourhoods (only now: every search and prune of the batch saw the old graph)
   uint16_t* const gcode = ix.codes_valid ? ix.gcode : nullptr;      // filter codes maintained with the rows (filter_codes.hip)
@@ -786,7 +734,7 @@ int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, 
   PANN_HIP(hipStreamSynchronize(st));
   const uint32_t ngroups = h_last[0] + h_last[1];
   PANN_HIP(hipMemcpyAsync(d_scalars + 2, &ngroups, 4, hipMemcpyHostToDevice, st));
-  const auto t3 = now_();
+  const auto t3 = now();
 
   // ---- 4. append or re-prune per target (:289-300) ----
   uint32_t nheavy = 0;
@@ -813,13 +761,10 @@ int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, 
     if (tk >= 0xFFFFFFF0ull) { set_error("vamana insert: re-prune too large"); return PANN_ERR_BAD_ARG; }
     const size_t stmp2 = seg_sort_temp_bytes((uint32_t)tk, nheavy);
     uint32_t *h_dseg, *h_dsend, *h_ddc; uint64_t *hk_a, *hk_b; void* h_tmp;
-    auto layout2 = [&](Bump& bb) {
+    if (int rc = carve_into(ws2, 4096, [&](Carve& bb) {
       h_dseg = bb.take<uint32_t>(nheavy); h_dsend = bb.take<uint32_t>(nheavy); h_ddc = bb.take<uint32_t>(nheavy);
-      hk_a = bb.take<uint64_t>(tk + 1); hk_b = bb.take<uint64_t>(tk + 1); h_tmp = bb.take<uint8_t>(stmp2 + 16);
-    };
-    Bump dry2(nullptr, 0); layout2(dry2);
-    if (int rc = ws2.ensure(dry2.off + 4096)) return rc;
-    Bump b2(ws2.buf, ws2.bytes); layout2(b2);
+      hk_a = bb.take<uint64_t>(tk + 1); hk_b = bb.take<uint64_t>(tk + 1); h_tmp = bb.take<uint8_t>(stmp2, 16);
+    })) return rc;
     PANN_HIP(hipMemcpyAsync(h_dseg, h_seg.data(), (size_t)nheavy * 4, hipMemcpyHostToDevice, st));
     PANN_HIP(hipMemsetAsync(h_ddc, 0, (size_t)nheavy * 4, st));
     PruneArgs pb{};
@@ -842,10 +787,10 @@ int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, 
     }
   }
   PANN_HIP(hipStreamSynchronize(st));
-  const auto t4 = now_();
+  const auto t4 = now();
   if (stats) {
     stats->prune_dist_cmps += reprune_dc;
-    stats->t_bidirect_s += secs_(t2, t3); stats->t_reprune_s += secs_(t3, t4);
+    stats->t_bidirect_s += secs(t2, t3); stats->t_reprune_s += secs(t3, t4);
   }
   return PANN_OK;
 }
@@ -871,14 +816,11 @@ int prune_csr_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const ui
   if (m == 0) return PANN_OK;
   const size_t stmp = seg_sort_temp_bytes(total_keys, m);
   uint32_t* d_send; uint64_t *ka, *kb; void* d_tmp;
-  auto layout = [&](Bump& b) {
+  if (int rc = carve_into(ws, 4096, [&](Carve& b) {
     d_send = b.take<uint32_t>(m);
     ka = b.take<uint64_t>((size_t)total_keys + 1); kb = b.take<uint64_t>((size_t)total_keys + 1);
-    d_tmp = b.take<uint8_t>(stmp + 16);
-  };
-  Bump dry(nullptr, 0); layout(dry);
-  if (int rc = ws.ensure(dry.off + 4096)) return rc;
-  Bump b(ws.buf, ws.bytes); layout(b);
+    d_tmp = b.take<uint8_t>(stmp, 16);
+  })) return rc;
   PruneArgs pa{};
   pa.pv = PointsView{ix.points, ix.pstride, ix.nch, ix.exact}; pa.dbytes = ix.dbytes;
   pa.graph = ix.graph; pa.gstride = ix.gstride; pa.max_deg = ix.max_deg;

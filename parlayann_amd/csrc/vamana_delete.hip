@@ -12,12 +12,10 @@
 //
 // count and fill are ONE kernel template, so the two walks cannot disagree about a list's length.
 #include <algorithm>
-#include <chrono>
 #include <vector>
 
-#include <rocprim/device/device_scan.hpp>
-
 #include "pann_internal.h"
+#include "rocprim_temp.h"
 
 namespace pann {
 
@@ -162,55 +160,30 @@ __global__ void __launch_bounds__(WAVE) delete_empty_rows_kernel(uint32_t* graph
   }
 }
 
-struct DevMem {      // owned by one call: freed on every return path
-  void* p = nullptr;
-  ~DevMem() { if (p) (void)hipFree(p); }
-};
-
-struct Bump {
-  uint8_t* base; size_t off = 0;
-  explicit Bump(void* b) : base((uint8_t*)b) {}
-  template <typename T> T* take(size_t count) {
-    off = (off + 255) / 256 * 256;
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += count * sizeof(T);
-    return p;
-  }
-};
-
-auto now_ = [] { return std::chrono::steady_clock::now(); };
-template <class A, class B> double secs_(A a, B b) { return std::chrono::duration<double>(b - a).count(); }
-
 }  // namespace
 
 int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& prune_ws, Workspace& rows_ws, hipStream_t st,
                             const uint32_t* d_del, uint64_t m, uint32_t R, double alpha, uint64_t range_keys,
                             pann_delete_stats* stats) {
   if (m == 0) return PANN_OK;
-  const auto t0 = now_();
+  const auto t0 = now();
   const uint64_t n = ix.n;
   const size_t words = (size_t)((n + 31) / 32);
 
-  size_t tmp_a = 0, tmp_b = 0;
-  (void)rocprim::exclusive_scan(nullptr, tmp_a, (uint32_t*)nullptr, (uint32_t*)nullptr, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
-  (void)rocprim::exclusive_scan(nullptr, tmp_b, (uint32_t*)nullptr, (uint64_t*)nullptr, (uint64_t)0, (size_t)n, rocprim::plus<uint64_t>(), st);
-  const size_t stmp = std::max(tmp_a, tmp_b);
+  const size_t stmp = std::max(scan_temp_bytes<uint32_t>((size_t)n), scan_temp_bytes<uint64_t>((size_t)n));
   uint32_t *sc, *cnt, *flag, *pos, *owners, *ocnt, *seg, *rcnt, *dc; uint64_t* offs; void* d_tmp;
-  auto layout = [&](Bump& b) {       // everything but the bitmap, the candidate slab and the rows; |A| <= n
+  if (int rc = carve_into(ws, 4096, [&](Carve& b) {       // everything but the bitmap, the candidate slab and the rows; |A| <= n
     sc = b.take<uint32_t>(SC_WORDS);
     cnt = b.take<uint32_t>(n); flag = b.take<uint32_t>(n); pos = b.take<uint32_t>(n);
     owners = b.take<uint32_t>(n); ocnt = b.take<uint32_t>(n); offs = b.take<uint64_t>(n + 1);
     seg = b.take<uint32_t>(n); rcnt = b.take<uint32_t>(n); dc = b.take<uint32_t>(n);
-    d_tmp = b.take<uint8_t>(stmp + 16);
-  };
-  Bump dry(nullptr); layout(dry);
-  if (int rc = ws.ensure(dry.off + 4096)) return rc;
-  Bump bump(ws.buf); layout(bump);
+    d_tmp = b.take<uint8_t>(stmp, 16);
+  })) return rc;
 
   // ---- 1. mark ----
-  DevMem bm;
-  PANN_HIP(hipMalloc(&bm.p, words * 4));
-  uint32_t* bitmap = (uint32_t*)bm.p;
+  HBuf bm;
+  if (int rc = bm.ensure(words * 4)) return rc;
+  uint32_t* bitmap = bm.as<uint32_t>();
   PANN_HIP(hipMemsetAsync(bitmap, 0, words * 4, st));
   PANN_HIP(hipMemsetAsync(sc, 0, SC_WORDS * 4, st));
   hipLaunchKernelGGL(delete_mark_kernel, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, st, d_del, m, n, bitmap, sc);
@@ -237,7 +210,7 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
 
   // ---- 3. fill ----
   uint64_t total = 0;
-  DevMem cand;
+  HBuf cand;
   if (na) {
     hipLaunchKernelGGL(delete_compact_kernel, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, st, flag, pos, cnt, n, owners, ocnt);
     PANN_HIP(hipGetLastError());
@@ -248,12 +221,12 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
     PANN_HIP(hipMemcpyAsync(&h_cnt, ocnt + (na - 1), 4, hipMemcpyDeviceToHost, st));
     PANN_HIP(hipStreamSynchronize(st));
     total = h_off + h_cnt;
-    PANN_HIP(hipMalloc(&cand.p, (total + 1) * 4));
-    ea.count = na; ea.owners = owners; ea.offs = offs; ea.cand = (uint32_t*)cand.p;
+    if (int rc = cand.ensure((total + 1) * 4)) return rc;
+    ea.count = na; ea.owners = owners; ea.offs = offs; ea.cand = cand.as<uint32_t>();
     if (int rc = launch_expand<true>(ea, st)) return rc;
   }
   PANN_HIP(hipStreamSynchronize(st));
-  const auto t1 = now_();
+  const auto t1 = now();
 
   // ---- 4. prune, in ranges of owners whose keys fit the prune's 32-bit key index; all against the same snapshot ----
   uint16_t* const gcode = ix.codes_valid ? ix.gcode : nullptr;      // filter codes maintained with the rows (filter_codes.hip)
@@ -279,7 +252,7 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
       if (keys >= 0xFFFFFFF0ull) { set_error("vamana delete: one candidate list exceeds the key index"); return PANN_ERR_OVERFLOW; }
       hipLaunchKernelGGL(delete_seg_kernel, dim3((cntr + 255) / 256), dim3(256), 0, st, offs + lo, cntr, seg + lo);
       PANN_HIP(hipGetLastError());
-      if (int rc = prune_csr_dev(ix, prune_ws, st, owners + lo, cntr, (const uint32_t*)cand.p, offs + lo, ocnt + lo, seg + lo,
+      if (int rc = prune_csr_dev(ix, prune_ws, st, owners + lo, cntr, cand.as<uint32_t>(), offs + lo, ocnt + lo, seg + lo,
                                  (uint32_t)keys, max_len, alpha, R, d_rows + (size_t)lo * R, rcnt + lo, dc + lo)) return rc;
       PANN_HIP(hipStreamSynchronize(st));        // the next range reuses the key scratch (and may regrow it)
     }
@@ -302,7 +275,7 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
     PANN_HIP(hipMemcpyAsync(&h_sum, sc + SC_SUM64, 8, hipMemcpyDeviceToHost, st));
   }
   PANN_HIP(hipStreamSynchronize(st));
-  const auto t2 = now_();
+  const auto t2 = now();
   if (stats) {
     if (stats->per_point_dist_cmps && na) {
       std::vector<uint32_t> ho(na), hd(na);
@@ -310,7 +283,7 @@ int vamana_delete_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& pru
       PANN_HIP(hipMemcpy(hd.data(), dc, (size_t)na * 4, hipMemcpyDeviceToHost));
       for (uint32_t i = 0; i < na; i++) stats->per_point_dist_cmps[ho[i]] += hd[i];
     }
-    stats->t_expand_s += secs_(t0, t1); stats->t_prune_s += secs_(t1, t2);
+    stats->t_expand_s += secs(t0, t1); stats->t_prune_s += secs(t1, t2);
     stats->deleted += ndel; stats->affected += na; stats->candidates += total; stats->prune_dist_cmps += h_sum;
   }
   return PANN_OK;
