@@ -70,8 +70,17 @@ extern "C" {
  * its points and graph moved (upload / download / set_graph / update_rows / get_graph); it gets its graph from
  * pann_index_create_quantized(copy_graph) or pann_index_set_graph.  Every entry point that builds, prunes, ranges, reranks ON
  * it, filters through a sketch or runs a dense all-pairs pass returns PANN_ERR_UNSUPPORTED before anything is launched,
- * allocated or written. */
-typedef enum { PANN_U8 = 0, PANN_I8 = 1, PANN_F32 = 2, PANN_F16 = 3, PANN_BF16 = 4, PANN_U4 = 5, PANN_I4 = 6 } pann_dtype;
+ * allocated or written.
+ *
+ * PANN_F8 (DESIGN.md "FP8 rows"): one byte per coordinate, OCP FP8 E4M3FN -- 1 sign bit, 4 exponent bits (bias 7), 3 mantissa
+ * bits, subnormals, no infinities, largest magnitude 448.  Both metrics; values are widened exactly to f32 and all arithmetic is
+ * f32, as for PANN_F16 / PANN_BF16.  The byte codes 0x7F and 0xFF are NaN: rows and queries that are uploaded must not hold them,
+ * distances of rows that do are unspecified.  A row is d bytes, laid out like the other one-byte types.  An FP8 handle is accepted
+ * exactly where a four-bit handle is (the list above, the masked / labeled / steered / grouped forms of pann_batch_search* and of
+ * pann_batch_search_rerank* included) and, beyond that, by pann_index_set_exact_float_order.  Everything else -- builds, prune, leaf
+ * kNN, pivot split, pann_bruteforce_knn and the masked / labeled / grouped / medoid dense routes, range searches, pann_rerank ON it,
+ * sketches, normalize -- returns PANN_ERR_UNSUPPORTED right after the null check. */
+typedef enum { PANN_U8 = 0, PANN_I8 = 1, PANN_F32 = 2, PANN_F16 = 3, PANN_BF16 = 4, PANN_U4 = 5, PANN_I4 = 6, PANN_F8 = 7 } pann_dtype;
 
 /* distance functor: euclidian_point.h:54-90 / mips_point.h:43-65 */
 typedef enum { PANN_L2 = 0, PANN_MIPS = 1 } pann_metric;
@@ -455,8 +464,17 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
  *                         special-cased; every translated value is then unspecified.
  *   PANN_QUANT_MIPS_I4    Quantized_Mips_Point<4, trim>: parameters exactly those of MIPS_I8 (mips_point.h:433-486, same trim
  *                         ranks); translate :416-430 with range = 15: scale = 7.0f / max_val, values below -max_val become -7,
- *                         above max_val +7, otherwise (int32) round(x * scale). */
-enum { PANN_QUANT_EUCLID_U8 = 0, PANN_QUANT_MIPS_I8 = 1, PANN_QUANT_EUCLID_U4 = 2, PANN_QUANT_MIPS_I4 = 3 };
+ *                         above max_val +7, otherwise (int32) round(x * scale).
+ *
+ * And a float form, valid for BOTH metrics (the copy keeps the source's), which gives a PANN_F8 handle and rows of d bytes:
+ *   PANN_QUANT_F8         M = the largest |x| over all coordinates (the min / max scan of EUCLID_U8; trim is ignored); slope = the
+ *                         largest power of two s with M * s <= 448, so x * slope is exact unless it underflows; offset = 0,
+ *                         max_val = M.  M == 0 is degenerate and unspecified, as the all-zero case of EUCLID_U8 is.  Translate:
+ *                         y = x * slope, clamped to [-448, 448] in f32, then rounded to nearest even on the E4M3 grid; finite
+ *                         inputs only.  Distances of a search on the copy are in scaled units -- x slope^2 for L2, x slope^2 for
+ *                         MIPS with queries translated by the same parameters --; the cut-prune is scale-invariant, and the fused
+ *                         rerank returns exact float distances as it does for the other kinds. */
+enum { PANN_QUANT_EUCLID_U8 = 0, PANN_QUANT_MIPS_I8 = 1, PANN_QUANT_EUCLID_U4 = 2, PANN_QUANT_MIPS_I4 = 3, PANN_QUANT_F8 = 4 };
 typedef struct pann_quant_params {
   int32_t kind;
   int32_t dims;
@@ -578,7 +596,8 @@ int pann_batch_search_filtered_dev(pann_index* idx, const void* d_queries, const
  * and raises PANN_STATUS_SHORT_FRONTIER (the reference aborts there, :416-419; callers reproduce that).
  * Scratch (one-byte / sketch / normalised queries, frontiers) belongs to quant and grows on first use.
  * quant may also be a four-bit copy (PANN_U4 / PANN_I4, qparams of kind EUCLID_U4 / MIPS_I4): step 1 then writes packed nibble
- * rows, the contract is the same.  use_filter != 0 with a four-bit quant -> PANN_ERR_UNSUPPORTED. */
+ * rows, the contract is the same; or an FP8 copy (PANN_F8, qparams of kind PANN_QUANT_F8, either metric): step 1 writes E4M3
+ * bytes.  use_filter != 0 with a four-bit or FP8 quant -> PANN_ERR_UNSUPPORTED. */
 typedef struct pann_rerank_out {
   uint32_t* ids;            /* nq x k, sorted by (exact dist, id); unused slots 0xFFFFFFFF */
   float*    dists;          /* nq x k, exact distances on the full-precision handle; unused slots +inf */

@@ -19,7 +19,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libpann.so")
 if os.environ.get("PANN_LIBRARY"):      # A/B runs of diagnostic builds (tools/): same ABI, another file
     LIB_PATH = os.environ["PANN_LIBRARY"]
 
-PANN_U8, PANN_I8, PANN_F32, PANN_F16, PANN_BF16, PANN_U4, PANN_I4 = 0, 1, 2, 3, 4, 5, 6
+PANN_U8, PANN_I8, PANN_F32, PANN_F16, PANN_BF16, PANN_U4, PANN_I4, PANN_F8 = 0, 1, 2, 3, 4, 5, 6, 7
 PANN_L2, PANN_MIPS = 0, 1
 PANN_OK = 0
 PANN_ERR_BAD_ARG, PANN_ERR_UNSUPPORTED = 1, 4
@@ -71,7 +71,7 @@ class ReachStats(C.Structure):
                 ("truncated", C.c_uint32), ("t_s", C.c_double)]
 
 
-PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4 = 0, 1, 2, 3
+PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4, PANN_QUANT_F8 = 0, 1, 2, 3, 4
 
 
 class QuantParams(C.Structure):
@@ -82,7 +82,7 @@ class QuantParams(C.Structure):
 
     @property
     def identity(self):
-        return self.kind != PANN_QUANT_EUCLID_U4 and self.slope == 1.0 and self.offset == 0      # the 4-bit translate never casts
+        return self.kind not in (PANN_QUANT_EUCLID_U4, PANN_QUANT_F8) and self.slope == 1.0 and self.offset == 0      # the 4-bit and FP8 translates never cast
 
 
 PANN_PRED_ANY, PANN_PRED_MATCH, PANN_PRED_RANGE = 0, 1, 2      # pann_label_pred kinds: two uint32 words (a, b) per predicate

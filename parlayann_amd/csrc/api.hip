@@ -148,16 +148,18 @@ int check_idx(const pann_index* idx, const char* fn) {
   return PANN_OK;
 }
 
-// A four-bit handle is searched and measured; everything else refuses it (include/pann.h, pann_dtype) -- first thing after the
-// null check, before anything is launched, allocated or written.  (PANN_TYPE_SWITCH has no four-bit branch.)
-int refuse_4bit(const pann_index* idx, const char* fn) {
-  if (!is_4bit_dtype(idx->ix.dtype)) return PANN_OK;
-  set_error(std::string(fn) + ": not supported on a four-bit (" + dtype_name(idx->ix.dtype) + ") handle");
+// A handle of a compact search-only type (four-bit, FP8) is searched and measured; everything else refuses it (include/pann.h,
+// pann_dtype) -- first thing after the null check, before anything is launched, allocated or written.  (PANN_TYPE_SWITCH has no
+// branch for these types.)
+int refuse_compact(const pann_index* idx, const char* fn) {
+  const int dt = idx->ix.dtype;
+  if (!is_compact_dtype(dt)) return PANN_OK;
+  set_error(std::string(fn) + ": not supported on a " + (dt == PANN_F8 ? "FP8" : "four-bit") + " (" + dtype_name(dt) + ") handle");
   return PANN_ERR_UNSUPPORTED;
 }
-int check_idx_no4(const pann_index* idx, const char* fn) {
+int check_idx_full(const pann_index* idx, const char* fn) {
   if (int rc = check_idx(idx, fn)) return rc;
-  return refuse_4bit(idx, fn);
+  return refuse_compact(idx, fn);
 }
 
 int k_beam_check(const pann_query_params* qp) {  // beamSearch.h:368-372, :549-553
@@ -502,7 +504,7 @@ int pann_index_device(const pann_index* idx) { return idx ? idx->device : -1; }
 int pann_index_set_exact_float_order(pann_index* idx, int on) {
   if (int rc = check_idx(idx, "pann_index_set_exact_float_order")) return rc;
   DeviceIndex& ix = idx->ix;
-  const bool is_float = ix.dtype == PANN_F32 || ix.dtype == PANN_F16 || ix.dtype == PANN_BF16;
+  const bool is_float = ix.dtype == PANN_F32 || ix.dtype == PANN_F16 || ix.dtype == PANN_BF16 || ix.dtype == PANN_F8;
   if (on && is_float) { ix.exact = 1; ix.lpc = 4; ix.nch = ix.pstride / 64; }   // whole query in LDS, lane-per-candidate sums
   else { ix.exact = 0; choose_point_layout(ix.dbytes, &ix.lpc, &ix.nch); }
   return PANN_OK;
@@ -643,7 +645,7 @@ static int search_refusals(const pann_index* idx, const SearchCall& c, const cha
   if (!c.qp || !c.has_out) { set_error("pann_batch_search: null params/out"); return PANN_ERR_BAD_ARG; }
   if (int rc = k_beam_check(c.qp)) return rc;
   if (F.given()) { if (int rc = masked_limits(idx, F, c.nq, c.qp, c.out.out_k)) return rc; }
-  if (c.sketch) { if (int rc = refuse_4bit(idx, fn)) return rc; }
+  if (c.sketch) { if (int rc = refuse_compact(idx, fn)) return rc; }
   const uint64_t n = idx->ix.n;
   if (c.dev) {
     if (!c.starts) { set_error("beam search expects at least one start point"); return PANN_ERR_BAD_ARG; }
@@ -1067,7 +1069,7 @@ int pann_batch_search_per_query_starts(pann_index* idx, const void* queries, con
 int pann_robust_prune_batch(pann_index* idx, const uint32_t* owners, uint64_t m, const uint32_t* cand_ids,
                             const float* cand_dists, const uint64_t* cand_offsets, double alpha, uint32_t R,
                             int add_out_nbrs, uint32_t* out_rows, uint32_t* out_dist_cmps) {
-  if (int rc = check_idx_no4(idx, "pann_robust_prune_batch")) return rc;
+  if (int rc = check_idx_full(idx, "pann_robust_prune_batch")) return rc;
   if (m && (!owners || !cand_offsets || !out_rows)) { set_error("pann_robust_prune_batch: null argument"); return PANN_ERR_BAD_ARG; }
   if (m && cand_offsets[m] && !cand_ids) { set_error("pann_robust_prune_batch: null candidate ids"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
@@ -1079,7 +1081,7 @@ static uint32_t default_vcap(uint32_t L) { return std::max<uint32_t>(2 * L, 128)
 
 int pann_vamana_insert_batch(pann_index* idx, const uint32_t* batch_ids, uint64_t m, uint32_t start, uint32_t R,
                              uint32_t L, double alpha, pann_build_stats* stats) {
-  if (int rc = check_idx_no4(idx, "pann_vamana_insert_batch")) return rc;
+  if (int rc = check_idx_full(idx, "pann_vamana_insert_batch")) return rc;
   if (m == 0) return PANN_OK;
   if (!batch_ids) { set_error("pann_vamana_insert_batch: null batch"); return PANN_ERR_BAD_ARG; }
   if (L == 0 || L > 65536) { set_error("pann_vamana_insert_batch: L out of range"); return PANN_ERR_BAD_ARG; }
@@ -1101,7 +1103,7 @@ int pann_vamana_insert_batch(pann_index* idx, const uint32_t* batch_ids, uint64_
 
 int pann_vamana_search_prune_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, uint32_t start, uint32_t R, uint32_t L,
                                  double alpha, uint32_t* d_rows_out, pann_build_stats* stats) {
-  if (int rc = check_idx_no4(idx, "pann_vamana_search_prune_dev")) return rc;
+  if (int rc = check_idx_full(idx, "pann_vamana_search_prune_dev")) return rc;
   if (m == 0) return PANN_OK;
   if (!d_batch_ids || !d_rows_out) { set_error("pann_vamana_search_prune_dev: null argument"); return PANN_ERR_BAD_ARG; }
   if (L == 0 || L > 65536) { set_error("pann_vamana_search_prune_dev: L out of range"); return PANN_ERR_BAD_ARG; }
@@ -1115,7 +1117,7 @@ int pann_vamana_search_prune_dev(pann_index* idx, const uint32_t* d_batch_ids, u
 
 int pann_vamana_apply_rows_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, const uint32_t* d_rows, uint32_t R,
                                double alpha, pann_build_stats* stats) {
-  if (int rc = check_idx_no4(idx, "pann_vamana_apply_rows_dev")) return rc;
+  if (int rc = check_idx_full(idx, "pann_vamana_apply_rows_dev")) return rc;
   if (m == 0) return PANN_OK;
   if (!d_batch_ids || !d_rows) { set_error("pann_vamana_apply_rows_dev: null argument"); return PANN_ERR_BAD_ARG; }
   if (m > 0xFFFFFFF0ull) { set_error("pann_vamana_apply_rows_dev: batch too large"); return PANN_ERR_BAD_ARG; }
@@ -1127,7 +1129,7 @@ int pann_vamana_apply_rows_dev(pann_index* idx, const uint32_t* d_batch_ids, uin
 
 static int delete_batch_checks(const pann_index* idx, const char* fn, const uint32_t* ids, uint64_t m, uint32_t R) {
   if (!idx && pann_device_count() <= 0) { set_error(std::string(fn) + ": no HIP device visible (this library has no CPU path)"); return PANN_ERR_NO_DEVICE; }
-  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (int rc = check_idx_full(idx, fn)) return rc;
   if (R == 0 || R > idx->ix.max_deg || R > 1024) { set_error(std::string(fn) + ": R must be in [1, min(max_deg,1024)]"); return PANN_ERR_BAD_ARG; }
   if (m > 0xFFFFFFF0ull) { set_error(std::string(fn) + ": batch too large"); return PANN_ERR_BAD_ARG; }
   if (m && !ids) { set_error(std::string(fn) + ": null ids"); return PANN_ERR_BAD_ARG; }
@@ -1158,7 +1160,7 @@ int pann_vamana_delete_batch_dev(pann_index* idx, const uint32_t* d_del_ids, uin
 }
 
 int pann_vamana_sort_neighbors(pann_index* idx) {
-  if (int rc = check_idx_no4(idx, "pann_vamana_sort_neighbors")) return rc;
+  if (int rc = check_idx_full(idx, "pann_vamana_sort_neighbors")) return rc;
   DeviceGuard g(idx->device);
   idx->ix.codes_valid = 0;                              // the rows are permuted without their filter codes
   return sort_neighbors_dev(idx->ix, idx->stream);
@@ -1236,7 +1238,7 @@ __global__ void random_edges_kernel(uint32_t* graph, uint32_t gstride, uint64_t 
 
 int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint32_t degree,
                                    uint64_t seed, int sort_neighbors, pann_build_stats* stats) {
-  if (int rc = check_idx_no4(idx, "pann_vamana_build_single_batch")) return rc;
+  if (int rc = check_idx_full(idx, "pann_vamana_build_single_batch")) return rc;
   if (L == 0 || L > 65536 || num_passes < 1) { set_error("pann_vamana_build_single_batch: bad L / num_passes"); return PANN_ERR_BAD_ARG; }
   if (degree == 0 || degree > idx->ix.max_deg) { set_error("pann_vamana_build_single_batch: degree must be in [1, max_deg]"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
@@ -1271,7 +1273,7 @@ int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, doub
 
 int pann_vamana_build(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint64_t seed,
                       int sort_neighbors, pann_build_stats* stats) {
-  if (int rc = check_idx_no4(idx, "pann_vamana_build")) return rc;
+  if (int rc = check_idx_full(idx, "pann_vamana_build")) return rc;
   if (L == 0 || L > 65536 || num_passes < 1) { set_error("pann_vamana_build: bad L / num_passes"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
   const uint64_t n = idx->ix.n;
@@ -1353,7 +1355,7 @@ int pann_query_distances(pann_index* idx, const void* queries, uint64_t nq, uint
 
 int pann_leaf_knn_batch(pann_index* idx, const uint32_t* ids, const uint64_t* leaf_offsets, uint64_t nleaves,
                         uint32_t m, uint32_t* out_ids, float* out_dists) {
-  if (int rc = check_idx_no4(idx, "pann_leaf_knn_batch")) return rc;
+  if (int rc = check_idx_full(idx, "pann_leaf_knn_batch")) return rc;
   if (nleaves == 0) return PANN_OK;
   if (!ids || !leaf_offsets || !out_ids || !out_dists) { set_error("pann_leaf_knn: null argument"); return PANN_ERR_BAD_ARG; }
   const uint64_t total = leaf_offsets[nleaves];
@@ -1412,7 +1414,7 @@ static uint32_t choose_gt_pieces(const pann_index* idx, uint32_t ntiles, double 
 
 int pann_bruteforce_knn(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                         uint32_t* out_ids, float* out_dists) {
-  if (int rc = check_idx_no4(idx, "pann_bruteforce_knn")) return rc;
+  if (int rc = check_idx_full(idx, "pann_bruteforce_knn")) return rc;
   if (nq == 0) return PANN_OK;
   if (!queries || !out_ids || !out_dists) { set_error("pann_bruteforce_knn: null argument"); return PANN_ERR_BAD_ARG; }
   if (q_stride_bytes < idx->ix.dbytes) { set_error("pann_bruteforce_knn: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
@@ -1594,7 +1596,7 @@ static int filtered_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q,
 
 static int filtered_knn_dev(pann_index* idx, const char* fn, const void* d_queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                             const PointFilter& F, uint64_t max_list_ids, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, void* stream) {
-  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (int rc = check_idx_full(idx, fn)) return rc;
   if (nq == 0) return PANN_OK;
   if (int rc = filtered_knn_checks(idx, fn, d_queries, nq, q_stride_bytes, k, F, d_ids, d_dists)) return rc;
   DeviceGuard g(idx->device);
@@ -1603,7 +1605,7 @@ static int filtered_knn_dev(pann_index* idx, const char* fn, const void* d_queri
 
 static int filtered_knn_host(pann_index* idx, const char* fn, const void* queries, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                              const PointFilter& F, uint64_t max_list_ids, uint32_t* out_ids, float* out_dists, uint32_t* out_counts) {
-  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (int rc = check_idx_full(idx, fn)) return rc;
   if (nq == 0) return PANN_OK;
   if (int rc = filtered_knn_checks(idx, fn, queries, nq, q_stride_bytes, k, F, out_ids, out_dists)) return rc;
   for (uint64_t q = 0; F.is_table() && q < nq; q++)      // the index array is checked on the host: nothing is staged for a call that will be refused
@@ -1729,7 +1731,7 @@ static PointFilter medoid_bitmap_table(const uint32_t* allow, uint64_t nrows, ui
 // what the grouped twins refuse, in their order: the handle, the outputs, the filter, per_filter as their k, the table
 static int filter_medoids_checks(const pann_index* idx, const char* fn, const PointFilter& F, uint32_t per_filter, const uint32_t* out_ids,
                                  const float* out_dists) {
-  if (int rc = check_idx_no4(idx, fn)) return rc;
+  if (int rc = check_idx_full(idx, fn)) return rc;
   if (!out_ids || !out_dists) { set_error(std::string(fn) + ": null argument"); return PANN_ERR_BAD_ARG; }
   if (!medoid_all_points(F)) { if (int rc = filter_checks(idx, fn, F, F.count)) return rc; }
   if (per_filter == 0) { set_error(std::string(fn) + ": per_filter == 0"); return PANN_ERR_BAD_ARG; }
@@ -1813,7 +1815,7 @@ int pann_filter_medoids_masked(pann_index* idx, const uint32_t* allow, uint64_t 
 
 int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_offsets, uint64_t nseg,
                      const uint32_t* pivot_a, const uint32_t* pivot_b, uint8_t* out_side) {
-  if (int rc = check_idx_no4(idx, "pann_pivot_split")) return rc;
+  if (int rc = check_idx_full(idx, "pann_pivot_split")) return rc;
   if (nseg == 0) return PANN_OK;
   if (!ids || !seg_offsets || !pivot_a || !pivot_b || !out_side) { set_error("pann_pivot_split: null argument"); return PANN_ERR_BAD_ARG; }
   const uint64_t total = seg_offsets[nseg];
@@ -1844,7 +1846,7 @@ int pann_pivot_split(pann_index* idx, const uint32_t* ids, const uint64_t* seg_o
 
 int pann_rerank(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, const uint32_t* cand_ids,
                 uint32_t c, const uint32_t* cand_counts, uint32_t k, int resort, uint32_t* out_ids, float* out_dists) {
-  if (int rc = check_idx_no4(idx, "pann_rerank")) return rc;
+  if (int rc = check_idx_full(idx, "pann_rerank")) return rc;
   if (nq == 0) return PANN_OK;
   if (!queries || !cand_ids || !out_ids || !out_dists || k == 0) { set_error("pann_rerank: null argument"); return PANN_ERR_BAD_ARG; }
   if (q_stride_bytes < idx->ix.dbytes) { set_error("pann_rerank: query stride smaller than a row"); return PANN_ERR_BAD_ARG; }
@@ -1884,7 +1886,7 @@ int pann_range_search(pann_index* idx, const void* queries, const uint32_t* quer
                       uint64_t q_stride_bytes, const uint32_t* starts, uint32_t nstarts, int starts_per_query,
                       float radius_2, uint32_t max_results, uint32_t* out_ids, uint32_t* out_counts,
                       uint32_t* out_dist_cmps, uint32_t* out_truncated) {
-  if (int rc = check_idx_no4(idx, "pann_range_search")) return rc;
+  if (int rc = check_idx_full(idx, "pann_range_search")) return rc;
   if (nq == 0) return PANN_OK;
   const DeviceIndex& ix = idx->ix;
   if ((queries == nullptr) == (query_ids == nullptr)) { set_error("pann_range_search: exactly one of queries / query_ids must be given"); return PANN_ERR_BAD_ARG; }
@@ -1921,7 +1923,7 @@ static int check_idx_or_device(const pann_index* idx, const char* fn) {
 int pann_bruteforce_range(pann_index* idx, const void* queries, uint64_t nq, uint64_t q_stride_bytes, float radius,
                           uint64_t* out_offsets, uint32_t* out_ids, uint64_t ids_capacity) {
   if (int rc = check_idx_or_device(idx, "pann_bruteforce_range")) return rc;
-  if (int rc = refuse_4bit(idx, "pann_bruteforce_range")) return rc;
+  if (int rc = refuse_compact(idx, "pann_bruteforce_range")) return rc;
   if (std::isnan(radius)) { set_error("pann_bruteforce_range: radius is NaN"); return PANN_ERR_BAD_ARG; }
   if (!out_offsets) { set_error("pann_bruteforce_range: null out_offsets"); return PANN_ERR_BAD_ARG; }
   if (nq == 0) { out_offsets[0] = 0; return PANN_OK; }
@@ -1957,7 +1959,7 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
                      uint32_t* out_search_cmps, uint32_t* out_visited, uint32_t* out_range_cmps,
                      uint32_t* out_truncated) {
   if (int rc = check_idx_or_device(idx, "pann_range_query")) return rc;
-  if (int rc = refuse_4bit(idx, "pann_range_query")) return rc;
+  if (int rc = refuse_compact(idx, "pann_range_query")) return rc;
   const DeviceIndex& ix = idx->ix;
   if (!qp) { set_error("pann_range_query: null params"); return PANN_ERR_BAD_ARG; }
   if (int rc = k_beam_check(qp)) return rc;
@@ -2015,7 +2017,7 @@ int pann_range_query(pann_index* idx, const void* queries, const uint32_t* query
 
 int pann_hcnng_build_trees_dev(pann_index* idx, uint32_t first_tree, uint32_t tree_step, uint32_t ntrees, uint32_t cluster_size,
                                uint32_t mst_deg, uint64_t seed, uint32_t* d_slab, uint32_t slab_stride, double* times3) {
-  if (int rc = check_idx_no4(idx, "pann_hcnng_build_trees_dev")) return rc;
+  if (int rc = check_idx_full(idx, "pann_hcnng_build_trees_dev")) return rc;
   if (mst_deg == 0 || tree_step == 0 || !d_slab) { set_error("pann_hcnng_build_trees_dev: null / zero argument"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
   hipLaunchKernelGGL(fill_u32_kernel, dim3(2048), dim3(256), 0, idx->stream, d_slab, idx->ix.n * (uint64_t)slab_stride, SENTINEL);
@@ -2026,7 +2028,7 @@ int pann_hcnng_build_trees_dev(pann_index* idx, uint32_t first_tree, uint32_t tr
 
 int pann_hcnng_assemble_dev(pann_index* idx, const uint32_t* d_slabs, uint32_t nslabs, uint32_t slab_stride, uint32_t ntrees,
                             uint32_t mst_deg) {
-  if (int rc = check_idx_no4(idx, "pann_hcnng_assemble_dev")) return rc;
+  if (int rc = check_idx_full(idx, "pann_hcnng_assemble_dev")) return rc;
   if (!d_slabs || mst_deg == 0) { set_error("pann_hcnng_assemble_dev: null / zero argument"); return PANN_ERR_BAD_ARG; }
   if ((uint64_t)ntrees * mst_deg > idx->ix.max_deg) { set_error("pann_hcnng_assemble_dev: max_deg < ntrees * mst_deg"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
@@ -2036,7 +2038,7 @@ int pann_hcnng_assemble_dev(pann_index* idx, const uint32_t* d_slabs, uint32_t n
 
 int pann_hcnng_build(pann_index* idx, uint32_t num_clusters, uint32_t cluster_size, uint32_t mst_deg, uint64_t seed,
                      double* times3) {
-  if (int rc = check_idx_no4(idx, "pann_hcnng_build")) return rc;
+  if (int rc = check_idx_full(idx, "pann_hcnng_build")) return rc;
   if (num_clusters == 0 || mst_deg == 0) { set_error("pann_hcnng_build: num_clusters and mst_deg must be positive"); return PANN_ERR_BAD_ARG; }
   DeviceGuard g(idx->device);
   idx->ix.codes_valid = 0;
@@ -2052,7 +2054,7 @@ int pann_hcnng_build(pann_index* idx, uint32_t num_clusters, uint32_t cluster_si
 namespace {
 
 int check_quant_kind(int kind, const char* fn) {
-  if (kind != PANN_QUANT_EUCLID_U8 && kind != PANN_QUANT_MIPS_I8 && kind != PANN_QUANT_EUCLID_U4 && kind != PANN_QUANT_MIPS_I4) { set_error(std::string(fn) + ": unknown quantisation kind"); return PANN_ERR_BAD_ARG; }
+  if (kind != PANN_QUANT_EUCLID_U8 && kind != PANN_QUANT_MIPS_I8 && kind != PANN_QUANT_EUCLID_U4 && kind != PANN_QUANT_MIPS_I4 && kind != PANN_QUANT_F8) { set_error(std::string(fn) + ": unknown quantisation kind"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
 }
 int check_quant_rows(const float* rows, uint64_t n, uint32_t d, uint64_t stride, const char* fn) {
@@ -2070,7 +2072,7 @@ int check_quant_source(const pann_index* src, int kind, const char* fn) {
   if (int rc = check_idx(src, fn)) return rc;
   if (src->ix.dtype != PANN_F32) { set_error(std::string(fn) + ": the source index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
   if (int rc = check_quant_kind(kind, fn)) return rc;
-  if (quant_kind_is_euclid(kind) != (src->ix.metric == PANN_L2)) {
+  if (!quant_kind_fits_metric(kind, src->ix.metric)) {      // (PANN_QUANT_F8 fits both metrics and never comes here)
     set_error(std::string(fn) + ": kind does not fit the index's metric (EUCLID_U8 / EUCLID_U4 <-> L2, MIPS_I8 / MIPS_I4 <-> MIPS)"); return PANN_ERR_BAD_ARG;
   }
   return PANN_OK;
@@ -2115,7 +2117,7 @@ void pann_quantize_select_ranks(uint64_t len, int trim, uint64_t* a, uint64_t* b
 }
 
 int pann_index_normalize(pann_index* idx) {
-  if (int rc = check_idx_no4(idx, "pann_index_normalize")) return rc;
+  if (int rc = check_idx_full(idx, "pann_index_normalize")) return rc;
   DeviceIndex& ix = idx->ix;
   if (ix.dtype != PANN_F32) { set_error("pann_index_normalize: float (PANN_F32) handles only"); return PANN_ERR_UNSUPPORTED; }
   DeviceGuard g(idx->device);
@@ -2154,7 +2156,7 @@ int pann_index_create_quantized(pann_index** out, pann_index* src, const pann_qu
   if ((uint32_t)p->dims != sx.d) { set_error("pann_index_create_quantized: parameters made for another dimension"); return PANN_ERR_BAD_ARG; }
   const int qdt = quant_kind_dtype(p->kind);
   pann_index* q = nullptr;
-  if (int rc = index_create_impl(&q, nullptr, sx.n, sx.d, qdt, row_bytes_of(qdt, sx.d), quant_kind_is_euclid(p->kind) ? PANN_L2 : PANN_MIPS, nullptr,
+  if (int rc = index_create_impl(&q, nullptr, sx.n, sx.d, qdt, row_bytes_of(qdt, sx.d), sx.metric /* check_quant_source: the kind fits it */, nullptr,
                                  sx.max_deg, src->device)) return rc;
   DeviceGuard g(src->device);
   auto fail = [&](int rc) { pann_index_destroy(q); return rc; };
@@ -2589,7 +2591,7 @@ int pann_sketch_params_generate(pann_index* src, int kind, pann_sketch_params* o
 }
 
 int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch_params* p) {
-  if (int rc = check_idx_no4(idx, "pann_index_attach_sketch")) return rc;
+  if (int rc = check_idx_full(idx, "pann_index_attach_sketch")) return rc;
   if (int rc = check_idx(src, "pann_index_attach_sketch")) return rc;
   if (int rc = check_sketch_params(p, "pann_index_attach_sketch")) return rc;
   if (int rc = check_sketch_source(src, "pann_index_attach_sketch")) return rc;
@@ -2611,7 +2613,7 @@ int pann_index_attach_sketch(pann_index* idx, pann_index* src, const pann_sketch
 }
 
 int pann_index_upload_sketch(pann_index* idx, const pann_sketch_params* p, const void* rows, uint64_t stride_bytes) {
-  if (int rc = check_idx_no4(idx, "pann_index_upload_sketch")) return rc;
+  if (int rc = check_idx_full(idx, "pann_index_upload_sketch")) return rc;
   if (int rc = check_sketch_params(p, "pann_index_upload_sketch")) return rc;
   const DeviceIndex& ix = idx->ix;
   if (!rows) { set_error("pann_index_upload_sketch: null rows"); return PANN_ERR_BAD_ARG; }
@@ -2705,14 +2707,18 @@ int search_rerank_checks(const RerankCall& r, int use_filter) {
     set_error(f + ": the two indices must agree in size, dimension, device and metric"); return PANN_ERR_BAD_ARG;
   }
   if (int rc = check_quant_kind(r.qparams->kind, r.fn)) return rc;
-  const bool eu = quant_kind_is_euclid(r.qparams->kind);
-  if (qx.dtype != quant_kind_dtype(r.qparams->kind) || qx.metric != (eu ? PANN_L2 : PANN_MIPS) || (uint32_t)r.qparams->dims != qx.d) {
+  if ((r.qparams->kind == PANN_QUANT_F8 || qx.dtype == PANN_F8) && (qx.dtype != quant_kind_dtype(r.qparams->kind) || (uint32_t)r.qparams->dims != qx.d)) {
+    set_error(f + ": the quantisation parameters do not fit the quantised index (PANN_QUANT_F8 <-> a PANN_F8 index of either metric, same dimension; " +
+                  dtype_name(qx.dtype) + " here)");
+    return PANN_ERR_BAD_ARG;
+  }
+  if (qx.dtype != quant_kind_dtype(r.qparams->kind) || !quant_kind_fits_metric(r.qparams->kind, qx.metric) || (uint32_t)r.qparams->dims != qx.d) {
     set_error(f + ": the quantisation parameters do not fit the one-byte index (EUCLID_U8 <-> u8 / L2, MIPS_I8 <-> i8 / MIPS, EUCLID_U4 <-> "
                   "u4 / L2, MIPS_I4 <-> i4 / MIPS, same dimension)");
     return PANN_ERR_BAD_ARG;
   }
-  if (use_filter && is_4bit_dtype(qx.dtype)) {
-    set_error(f + ": use_filter is not supported with a four-bit (" + dtype_name(qx.dtype) + ") quantised index"); return PANN_ERR_UNSUPPORTED;
+  if (use_filter && is_compact_dtype(qx.dtype)) {
+    set_error(f + ": use_filter is not supported with a " + (qx.dtype == PANN_F8 ? "FP8" : "four-bit") + " (" + dtype_name(qx.dtype) + ") quantised index"); return PANN_ERR_UNSUPPORTED;
   }
   if (use_filter && !qx.sketch) { set_error(f + ": use_filter needs a sketch attached to the one-byte index"); return PANN_ERR_BAD_ARG; }
   if (r.qstride < 4ull * fx.d || r.qstride % 4 != 0) { set_error(f + ": query stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }

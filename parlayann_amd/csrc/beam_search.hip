@@ -305,14 +305,14 @@ __device__ __forceinline__ bool filter_update_codes(uint8_t* P8, uint32_t* P4, u
 
 // Distances from the query to the m ids in Pl[0..m); survivors of `dist < cutoff` (:157) are
 // appended to C in row order.
-template <int DT, int METRIC, int LPC, bool NCH1, int U, bool BATCH_EMIT = true>
+template <int DT, int METRIC, int LPC, bool NCH1, int U, bool BATCH_EMIT = true, bool EXACT_OK = true>
 __device__ __forceinline__ uint32_t gather_distances(const BSParams& P, const QReg<DT>& qreg,
                                                      const uint4* qlds, const uint32_t* Pl, uint32_t m,
                                                      uint32_t cutoff_ord, uint64_t* C, uint32_t c, int lane) {
   const PointsView PV{P.points, P.pstride, P.nch, P.exact};
   if constexpr (BATCH_EMIT) {
     // one append per gather iteration (G*U candidates): +4 % on the beam-64 kernel at 10K queries
-    gather_tile<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, lane,
+    gather_tile<DT, METRIC, LPC, NCH1, U, EXACT_OK>(PV, qreg, qlds, Pl, m, lane,
       [&](bool has, uint32_t, uint32_t id, float dist, uint64_t before) {
         const uint32_t ord = f2ord(dist);
         const bool pass = has && (ord < cutoff_ord);
@@ -995,7 +995,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
       c = gather_distances_masked<DT, METRIC, LPC, NCH1, 4, MASKED>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane,
                                                             masked_note(act, (uint32_t)lane, a), aword, M, R, thr_lane);
     else
-    c = gather_distances<DT, METRIC, LPC, NCH1, 4>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane);
+    c = gather_distances<DT, METRIC, LPC, NCH1, 4, true, DT != PANN_F8>(P, qreg, qlds, Pl, P.nstarts, 0xFFFFFFFFu, C, c, lane);      // (FP8: no exact-order branch here)
     PANN_WSYNC();
   }
 
@@ -1096,7 +1096,7 @@ __global__ void __launch_bounds__(PANN_WAVE, PANN_MINWAVES_B64) beam_search_b64_
           if (m) c = gather_distances_masked<DT, METRIC, LPC, NCH1, PANN_GU, MASKED>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane,
                                                                              masked_note(keep, mypos, a), aword, M, R, thr_lane);
         } else {
-        if (m) c = gather_distances<DT, METRIC, LPC, NCH1, PANN_GU>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane);
+        if (m) c = gather_distances<DT, METRIC, LPC, NCH1, PANN_GU, true, DT != PANN_F8>(P, qreg, qlds, Pl, m, cutoff_ord, C, c, lane);
         }
         PANN_WSYNC();
         PANN_STAMP(3);
@@ -1555,7 +1555,7 @@ static PlanSwitches plan_switches() {
 void choose_point_layout(uint32_t dbytes, uint32_t* lpc, uint32_t* nch) { choose_point_layout(dbytes, plan_switches().force_lpc, lpc, nch); }
 static SearchPlan plan_of(const DeviceIndex& ix, const SearchArgs& a) {
   const PlanIndex pi{ix.dtype, ix.metric, ix.lpc, ix.nch, ix.max_deg, ix.gstride, ix.n, ix.sk_stride, ix.b64_seen,
-                     ix.codes_valid && ix.gcode && ix.rank16};
+                     ix.codes_valid && ix.gcode && ix.rank16, ix.dtype == PANN_F8 && ix.exact != 0};
   const PlanCall pc{a.nq, a.nstarts, a.k, a.beam, a.degree_limit, a.cut, a.dcap, a.filter != 0, a.masked, a.steer != 0};
   return make_plan(pi, pc, plan_switches());
 }
@@ -1600,9 +1600,11 @@ static SearchKernel plan_kernel(const DeviceIndex& ix, const SearchPlan& p) {
   SearchKernel kern = nullptr;
 #define CALL_BS(DT, MT, LPC, NCH1) kern = plan_kernel<DT, MT, LPC, NCH1>(p)
   if (!type_ok || !lpc_ok) return nullptr;
-  if (!is_4bit_dtype(ix.dtype)) PANN_TYPE_SWITCH(ix, CALL_BS);
+  if (!is_compact_dtype(ix.dtype)) PANN_TYPE_SWITCH(ix, CALL_BS);
   else if (ix.dtype == PANN_U4) PANN_LAYOUT_SWITCH(ix, PANN_U4, PANN_L2, CALL_BS);
-  else PANN_LAYOUT_SWITCH(ix, PANN_I4, PANN_MIPS, CALL_BS);
+  else if (ix.dtype == PANN_I4) PANN_LAYOUT_SWITCH(ix, PANN_I4, PANN_MIPS, CALL_BS);
+  else if (ix.metric == PANN_L2) PANN_LAYOUT_SWITCH(ix, PANN_F8, PANN_L2, CALL_BS);      // FP8 rows: both metrics
+  else PANN_LAYOUT_SWITCH(ix, PANN_F8, PANN_MIPS, CALL_BS);
 #undef CALL_BS
   return kern;
 }

@@ -104,6 +104,7 @@ template <> struct QReg<PANN_F16> { uint4 raw; };        // halves stay packed; 
 template <> struct QReg<PANN_BF16> { float f[8]; };      // widened once per query (a shift / a mask per element)
 template <> struct QReg<PANN_U4>  { uint4 raw; uint32_t qq; };   // 32 nibbles; qq = sum of their squares
 template <> struct QReg<PANN_I4>  { uint4 raw; };                // MIPS only: no norm term
+template <> struct QReg<PANN_F8>  { uint4 raw; };                // 16 E4M3 bytes stay packed; widened per step (v_cvt_pk_f32_fp8)
 
 template <int DT> struct Acc;           // per-lane partial state
 template <> struct Acc<PANN_U8>  { uint32_t aa, aq; __device__ __forceinline__ void clear() { aa = 0; aq = 0; } };
@@ -113,11 +114,13 @@ template <> struct Acc<PANN_F16> { float2v s;       __device__ __forceinline__ v
 template <> struct Acc<PANN_BF16> { float2v s;      __device__ __forceinline__ void clear() { s = float2v{0.f, 0.f}; } };
 template <> struct Acc<PANN_U4>  { uint32_t aa, aq; __device__ __forceinline__ void clear() { aa = 0; aq = 0; } };
 template <> struct Acc<PANN_I4>  { int aq;          __device__ __forceinline__ void clear() { aq = 0; } };
+template <> struct Acc<PANN_F8>  { float2v s;       __device__ __forceinline__ void clear() { s = float2v{0.f, 0.f}; } };
 
 template <int DT> struct AccT { using type = int; };             // type that crosses lanes
 template <> struct AccT<PANN_F32> { using type = float; };
 template <> struct AccT<PANN_F16> { using type = float; };
 template <> struct AccT<PANN_BF16> { using type = float; };
+template <> struct AccT<PANN_F8> { using type = float; };
 
 // bfloat16 pair in a dword -> the two floats (exact: the 16 bits are the float's upper half)
 __device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
@@ -181,6 +184,28 @@ __device__ __forceinline__ float fma_widen_f16(uint32_t a_pair, uint32_t q_pair,
   return t;
 }
 
+// FP8 (OCP E4M3) terms.  A dword of four bytes is widened exactly by two v_cvt_pk_f32_fp8 (low word, high word); L2 is t = q - a,
+// acc = fma(t, t, acc), MIPS acc = fma(q, a, acc).  The operations are written out as scalar instructions ON PURPOSE: the FP8
+// kernels are to hold no packed f32 arithmetic (v_pk_add / v_pk_mul / v_pk_fma_f32) -- this code was written to be built with the
+// packed f32 operations switched off, and as plain C++ on two partial sums the vectoriser pairs them again under the library's
+// flags.  It costs issue slots (40 / 24 VALU instructions per 16-byte step, DESIGN.md "FP8 rows"), not correctness or registers.
+__device__ __forceinline__ float f8_sub(float q, float a) { float t; asm("v_sub_f32 %0, %1, %2" : "=v"(t) : "v"(q), "v"(a)); return t; }
+__device__ __forceinline__ float f8_mul(float x, float y) { float t; asm("v_mul_f32 %0, %1, %2" : "=v"(t) : "v"(x), "v"(y)); return t; }
+__device__ __forceinline__ float f8_add(float x, float y) { float t; asm("v_add_f32 %0, %1, %2" : "=v"(t) : "v"(x), "v"(y)); return t; }
+__device__ __forceinline__ float f8_fma(float x, float y, float acc) { float t; asm("v_fma_f32 %0, %1, %2, %3" : "=v"(t) : "v"(x), "v"(y), "v"(acc)); return t; }
+template <int METRIC>
+__device__ __forceinline__ void f8_pair_accum(float2v& s, float2v qv, float2v av) {
+  if constexpr (METRIC == PANN_L2) { const float t0 = f8_sub(qv.x, av.x), t1 = f8_sub(qv.y, av.y); s.x = f8_fma(t0, t0, s.x); s.y = f8_fma(t1, t1, s.y); }
+  else { s.x = f8_fma(qv.x, av.x, s.x); s.y = f8_fma(qv.y, av.y, s.y); }
+}
+
+// exact float order: elements x then y of the pair, one rounding per subtract, multiply and add
+template <int METRIC>
+__device__ __forceinline__ void f8_pair_exact(float& acc, float2v qv, float2v av) {
+  if constexpr (METRIC == PANN_L2) { const float t0 = f8_sub(qv.x, av.x); acc = f8_add(acc, f8_mul(t0, t0)); const float t1 = f8_sub(qv.y, av.y); acc = f8_add(acc, f8_mul(t1, t1)); }
+  else { acc = f8_add(acc, f8_mul(qv.x, av.x)); acc = f8_add(acc, f8_mul(qv.y, av.y)); }
+}
+
 template <int DT, int METRIC>
 __device__ __forceinline__ void dist_accum(Acc<DT>& acc, const uint4& a, const QReg<DT>& q) {
   if constexpr (DT == PANN_U8) {
@@ -227,6 +252,13 @@ __device__ __forceinline__ void dist_accum(Acc<DT>& acc, const uint4& a, const Q
     acc.aq = __builtin_amdgcn_sdot8((int)a.y, (int)q.raw.y, acc.aq, false);
     acc.aq = __builtin_amdgcn_sdot8((int)a.z, (int)q.raw.z, acc.aq, false);
     acc.aq = __builtin_amdgcn_sdot8((int)a.w, (int)q.raw.w, acc.aq, false);
+  } else if constexpr (DT == PANN_F8) {     // 16 coordinates per step; bytes 0 / 2 of every dword go to s.x, bytes 1 / 3 to s.y
+    const uint32_t w[4] = {a.x, a.y, a.z, a.w}, qw[4] = {q.raw.x, q.raw.y, q.raw.z, q.raw.w};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      f8_pair_accum<METRIC>(acc.s, __builtin_amdgcn_cvt_pk_f32_fp8((int)qw[i], false), __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], false));
+      f8_pair_accum<METRIC>(acc.s, __builtin_amdgcn_cvt_pk_f32_fp8((int)qw[i], true), __builtin_amdgcn_cvt_pk_f32_fp8((int)w[i], true));
+    }
   } else if constexpr (DT == PANN_F32) {
     const float2v a01{__uint_as_float(a.x), __uint_as_float(a.y)}, a23{__uint_as_float(a.z), __uint_as_float(a.w)};
     const float2v q01{q.f[0], q.f[1]}, q23{q.f[2], q.f[3]};
@@ -342,9 +374,16 @@ __device__ __forceinline__ void dist_accum_exact(float& acc, const uint4& a, con
       if constexpr (METRIC == PANN_L2) { const float t = qf - af; const float p = t * t; acc = acc + p; }
       else { const float p = qf * af; acc = acc + p; }
     }
+  } else if constexpr (DT == PANN_F8) {
+    const uint32_t aw[4] = {a.x, a.y, a.z, a.w}, qw[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+    for (int i = 0; i < 4; i++) {      // one pair at a time: the widened values of a pair are dead before the next is made
+      f8_pair_exact<METRIC>(acc, __builtin_amdgcn_cvt_pk_f32_fp8((int)qw[i], false), __builtin_amdgcn_cvt_pk_f32_fp8((int)aw[i], false));
+      f8_pair_exact<METRIC>(acc, __builtin_amdgcn_cvt_pk_f32_fp8((int)qw[i], true), __builtin_amdgcn_cvt_pk_f32_fp8((int)aw[i], true));
+    }
   }
 }
-template <int DT> constexpr bool is_float_dt() { return DT == PANN_F32 || DT == PANN_F16 || DT == PANN_BF16; }
+template <int DT> constexpr bool is_float_dt() { return DT == PANN_F32 || DT == PANN_F16 || DT == PANN_BF16 || DT == PANN_F8; }
 
 
 // 16 bytes of a gathered base-point row.  -DPANN_NT_ROWS (A/B builds): non-temporal, so the streamed rows do not displace
@@ -381,7 +420,7 @@ __device__ __forceinline__ void gather_iter(const PointsView& PV, const QReg<DT>
     // rows of several chunks per lane: CB chunks of every group are requested before the first is used, so a
     // row costs ceil(nch/CB) memory round trips instead of nch; a batch running past the row re-reads its last
     // chunk (a cache hit) and skips the arithmetic (wave-uniform branch)
-    constexpr int CB = 3;
+    constexpr int CB = DT == PANN_F8 ? 2 : 3;      // FP8: the widened operands of a step need the registers of the third chunk
 #pragma unroll
     for (int u = 0; u < U; u++) acc[u].clear();
     const uint8_t* rp[U];
@@ -450,10 +489,12 @@ __device__ __forceinline__ void gather_span(const PointsView& PV, const QReg<DT>
   gather_iter<DT, METRIC, LPC, NCH1, U>(PV, qreg, qlds, Pl, m, s0, lane, emit);
 }
 
-template <int DT, int METRIC, int LPC, bool NCH1, int U_, typename Emit>
+template <int DT, int METRIC, int LPC, bool NCH1, int U_, bool EXACT_OK = true, typename Emit>
 __device__ __forceinline__ void gather_tile(const PointsView& PV, const QReg<DT>& qreg, const uint4* qlds,
                                             const uint32_t* Pl, uint32_t m, int lane, Emit&& emit) {
-  if constexpr (is_float_dt<DT>() && !NCH1) {
+  // (EXACT_OK false: the FP8 beam-64 kernel, whose MIPS instances spilled two registers with this branch in them; make_plan gives
+  // an FP8 handle in this mode the generic kernel)
+  if constexpr (is_float_dt<DT>() && !NCH1 && EXACT_OK) {
     if (PV.exact) {      // lane-per-candidate, sequential sum (the whole query sits in qlds in this mode)
       const uint32_t nchunks = PV.pstride / 16;
       for (uint32_t s0 = 0; s0 < m; s0 += PANN_WAVE) {

@@ -28,15 +28,17 @@ inline const char* ab_env(const char*) { return nullptr; }
 // ---- element types: bytes of one element (0 for the four-bit types: half a byte) and of one host-layout row of d elements.
 // A four-bit row is the reference's num_bytes() = (dims * bits - 1) / 8 + 1 (mips_point.h:297), two coordinates per byte.
 inline bool is_4bit_dtype(int dtype) { return dtype == PANN_U4 || dtype == PANN_I4; }
+// the compact types a handle is searched, measured and reranked from, and nothing else (include/pann.h, pann_dtype): four-bit and FP8 rows
+inline bool is_compact_dtype(int dtype) { return is_4bit_dtype(dtype) || dtype == PANN_F8; }
 inline const char* dtype_name(int dtype) {
   switch (dtype) {
     case PANN_U8: return "PANN_U8"; case PANN_I8: return "PANN_I8"; case PANN_F32: return "PANN_F32"; case PANN_F16: return "PANN_F16";
-    case PANN_BF16: return "PANN_BF16"; case PANN_U4: return "PANN_U4"; case PANN_I4: return "PANN_I4";
+    case PANN_BF16: return "PANN_BF16"; case PANN_U4: return "PANN_U4"; case PANN_I4: return "PANN_I4"; case PANN_F8: return "PANN_F8";
   }
   return "unknown dtype";
 }
 inline uint32_t esize_of(int dtype) {
-  switch (dtype) { case PANN_U8: case PANN_I8: return 1; case PANN_F16: case PANN_BF16: return 2; case PANN_F32: return 4; }
+  switch (dtype) { case PANN_U8: case PANN_I8: case PANN_F8: return 1; case PANN_F16: case PANN_BF16: return 2; case PANN_F32: return 4; }
   return 0;
 }
 inline bool dtype_known(int dtype) { return esize_of(dtype) != 0 || is_4bit_dtype(dtype); }

@@ -1,6 +1,7 @@
 // quant_device.h -- translate_point of the two one-byte quantisers (euclidian_point.h:182-209, mips_point.h:416-430) and of their
 // four-bit forms (range = 15, two values per byte) as device functions, shared by quantize.hip and the query preparation of
-// search_rerank.hip: both must give the same bytes.
+// search_rerank.hip: both must give the same bytes.  PANN_QUANT_F8 (include/pann.h): scale by a power of two, clamp, round to nearest
+// even on the E4M3 grid with v_cvt_pk_fp8_f32 -- a one-byte kind, so it runs through the one-byte paths of every caller.
 #pragma once
 #include <math.h>
 
@@ -17,8 +18,21 @@ struct QParams {
 
 __host__ __device__ inline bool quant_kind_is_4bit(int kind) { return kind == PANN_QUANT_EUCLID_U4 || kind == PANN_QUANT_MIPS_I4; }
 __host__ __device__ inline bool quant_kind_is_euclid(int kind) { return kind == PANN_QUANT_EUCLID_U8 || kind == PANN_QUANT_EUCLID_U4; }
+// PANN_QUANT_F8 goes with both metrics; every other kind with the one it was made for
+inline bool quant_kind_fits_metric(int kind, int metric) { return kind == PANN_QUANT_F8 || quant_kind_is_euclid(kind) == (metric == PANN_L2); }
 inline int quant_kind_dtype(int kind) {
+  if (kind == PANN_QUANT_F8) return PANN_F8;
   return kind == PANN_QUANT_EUCLID_U8 ? PANN_U8 : kind == PANN_QUANT_MIPS_I8 ? PANN_I8 : kind == PANN_QUANT_EUCLID_U4 ? PANN_U4 : PANN_I4;
+}
+
+// PANN_QUANT_F8: two coordinates per v_cvt_pk_fp8_f32 (round to nearest even), bytes lo | hi << 8.  The clamp is done in f32 BEFORE
+// the conversion, so the result never depends on what the hardware conversion does on overflow; -0.0f stays -0.0f (code 0x80).
+__device__ __forceinline__ float f8_scaled(float x, float slope) {
+#pragma clang fp contract(off)
+  return fminf(fmaxf(x * slope, -448.0f), 448.0f);
+}
+__device__ __forceinline__ uint32_t quantize_pair_f8(float lo, float hi, const QParams& q) {
+  return (uint32_t)__builtin_amdgcn_cvt_pk_fp8_f32(f8_scaled(lo, q.slope), f8_scaled(hi, q.slope), 0, false) & 0xFFFFu;
 }
 
 // products are rounded before anything else happens to them; rounding is roundf (halves away from zero)
@@ -30,6 +44,7 @@ __device__ __forceinline__ uint32_t quantize_one(float x, const QParams& q) {
     r = r < 0 ? 0 : (r > 255 ? 255 : r);
     return (uint32_t)r;
   }
+  if (q.kind == PANN_QUANT_F8) return quantize_pair_f8(x, x, q) & 0xFFu;
   if (q.kind == PANN_QUANT_EUCLID_U4) {                                         // :193-207 with range = 15, never the cast
     long long r = (long long)roundf(x * q.slope) - (long long)q.offset;
     r = r < 0 ? 0 : (r > 15 ? 15 : r);
@@ -45,6 +60,7 @@ __device__ __forceinline__ uint32_t quantize_one(float x, const QParams& q) {
   return (uint32_t)(int32_t)roundf(x * q.scale) & 0xFFu;                        // :426-427
 }
 __device__ __forceinline__ uint32_t quantize_four(float4 x, const QParams& q) {
+  if (q.kind == PANN_QUANT_F8) return quantize_pair_f8(x.x, x.y, q) | (quantize_pair_f8(x.z, x.w, q) << 16);      // one dword store
   return quantize_one(x.x, q) | (quantize_one(x.y, q) << 8) | (quantize_one(x.z, q) << 16) | (quantize_one(x.w, q) << 24);
 }
 

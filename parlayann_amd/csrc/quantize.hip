@@ -108,7 +108,7 @@ __global__ void quant_init_kernel(uint8_t* scratch, int kind, unsigned long long
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(scratch + SCRATCH_HIST_OFF);
   for (uint32_t i = threadIdx.x; i < 2 * QBINS; i += blockDim.x) hist[i] = 0;
   if (threadIdx.x == 0) {
-    if (quant_kind_is_euclid(kind)) {
+    if (quant_kind_is_euclid(kind) || kind == PANN_QUANT_F8) {      // the kinds whose parameters come from the running min / max
       uint32_t* w = reinterpret_cast<uint32_t*>(scratch);
       w[0] = 0x80000000u; w[1] = 0x80000000u; w[2] = 0;
     } else {
@@ -396,7 +396,7 @@ int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t strid
   const int nv = make_views(d_rows, n, d, stride, nullptr, 0, v);
   pann_quant_params p{};
   p.kind = kind; p.dims = (int32_t)d; p.slope = 1.0f; p.offset = 0; p.max_val = 0.0f;
-  if (quant_kind_is_euclid(kind)) {
+  if (quant_kind_is_euclid(kind) || kind == PANN_QUANT_F8) {      // the running min / max scan (F8: for M = the largest |x|)
     hipLaunchKernelGGL(quant_init_kernel, dim3(1), dim3(256), 0, st, sc, kind, 0ull, 0ull);
     PANN_HIP(hipGetLastError());
     for (int i = 0; i < nv; i++) {
@@ -415,6 +415,16 @@ int quant_params_dev(const float* d_rows, uint64_t n, uint32_t d, uint64_t strid
     PANN_HIP(hipMemcpyAsync(w, sc, sizeof(w), hipMemcpyDeviceToHost, st));
     PANN_HIP(hipStreamSynchronize(st));
     float min_val = key_to_float(w[0]) + 0.0f, max_val = key_to_float(w[1]);     // (-0.0f + 0.0f == +0.0f: std::min(0.0f, -0.0f) keeps +0)
+    if (kind == PANN_QUANT_F8) {
+      // slope: the largest power of two s with M * s <= 448 = 0.875 * 2^9.  M = m * 2^e, m in [0.5, 1): s = 2^(9 - e), one less if m > 0.875
+      const float M = std::max(max_val, -min_val);
+      int e = 0;
+      const float m = std::frexp(M, &e);
+      p.slope = std::ldexp(1.0f, std::min(std::max((m > 0.875f ? 8 : 9) - e, -126), 127));
+      p.max_val = M; p.min_seen = min_val; p.max_seen = max_val;
+      *out = p;
+      return PANN_OK;
+    }
     const bool u4 = kind == PANN_QUANT_EUCLID_U4;
     if (!w[2] && !u4) { if (max_val < 256) max_val = 255; min_val = 0; }       // euclidian_point.h:228-231 (a cast cannot fit 4 bits)
     const long range = u4 ? 15 : 255;

@@ -94,7 +94,8 @@ struct SearchPlan {
   bool masked() const { return mode == MODE_BITMAP || mode == MODE_LABELS; }
   uint64_t dropped_bytes(uint64_t nq) const { return nq * dcap * 8; }
 };
-struct PlanIndex { int dtype, metric; uint32_t lpc, nch, max_deg, gstride; uint64_t n; uint32_t sk_stride, b64_seen; bool codes; };
+struct PlanIndex { int dtype, metric; uint32_t lpc, nch, max_deg, gstride; uint64_t n; uint32_t sk_stride, b64_seen; bool codes;
+                   bool f8_exact = false; };      // an FP8 handle in exact float order: the beam-64 kernel has no such form
 struct PlanCall { uint64_t nq; uint32_t nstarts; int64_t k, beam, degree_limit; double cut; uint32_t dcap; bool filter; int masked;
                   bool steer = false; };      // steer: the steered form of a masked call (no sketch filter)
 // Diagnostic A/B switches of `make alt` builds (beam_search.hip reads them from the environment); the shipped library runs on these defaults
@@ -110,7 +111,8 @@ inline uint32_t filter_bits(int64_t beam) {  // :52
 // Which layouts have a MASKED instantiation of the b64 kernel: 128-byte rows (8 lanes per candidate) and bf16 rows of several chunks
 // per lane would spill under its 72-VGPR bound (DESIGN.md "Masked search") and take the generic kernel.  The label form needs no
 // vector register beyond the bitmap form (MaskSrc), so one predicate serves both.
-constexpr bool masked_b64_fits(int dtype, uint32_t lpc, bool nch1) { return !(lpc == 8 && nch1) && !(dtype == PANN_BF16 && !nch1); }
+// FP8 rows widen both operands of every step into registers: no masked b64 instantiation of theirs fits either (DESIGN.md "FP8 rows").
+constexpr bool masked_b64_fits(int dtype, uint32_t lpc, bool nch1) { return !(lpc == 8 && nch1) && !(dtype == PANN_BF16 && !nch1) && dtype != PANN_F8; }
 inline SearchPlan make_plan(const PlanIndex& ix, const PlanCall& a, const PlanSwitches& sw = PlanSwitches()) {
   SearchPlan p{};
   const uint32_t beam = (uint32_t)a.beam, qb = query_lds_bytes(ix.lpc, ix.nch);
@@ -137,7 +139,7 @@ inline SearchPlan make_plan(const PlanIndex& ix, const PlanCall& a, const PlanSw
   // the table goes to LDS up to 16 KB, if the generic kernel's state with it stays within 64 KB
   const bool fits = p.bits <= 12 && generic_lds(p.bcap, p.ccap, qb, p.bits, true, false, 0).total <= 64 * 1024;
   // the register-frontier kernels: no sketch form; masked forms of b64 only, and not for every layout
-  const bool regs = fits && (p.mode == MODE_PLAIN || (p.masked() && masked_b64_fits(ix.dtype, ix.lpc, layout_query_in_registers(ix.lpc, ix.nch))));
+  const bool regs = fits && !(ix.f8_exact && p.bcap == 64) && (p.mode == MODE_PLAIN || (p.masked() && masked_b64_fits(ix.dtype, ix.lpc, layout_query_in_registers(ix.lpc, ix.nch))));
   p.kernel = regs && p.bcap == 64 ? KERNEL_B64 : regs && p.bcap == 128 && a.nstarts <= 64 && !p.masked() ? KERNEL_B128 : KERNEL_GENERIC;
   p.table = fits ? TABLE_LDS : TABLE_HBM;
   if (p.kernel != KERNEL_GENERIC) p.ccap = (cmax + 7) / 8 * 8;      // exact, 8-entry granules

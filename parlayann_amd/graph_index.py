@@ -26,9 +26,10 @@ class GraphIndex:
 
     def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None, quant_bits=8, labels=None):
         """labels: one uint32 per point (set_labels), what where= predicates are evaluated on (DESIGN.md "Label predicates").
-        quant_bits: 8 | 4 -- bits per coordinate of the quantised copy that quant=True searches (float points only).  4: the
+        quant_bits: 8 | 4 | "f8" -- bits per coordinate of the quantised copy that quant=True searches (float points only).  4: the
         four-bit quantisers ("euclid_u4" / "mips_i4", packed rows of ceil(d / 2) bytes) for the copy and for the fused rerank
-        call; it has no second level, and its Euclidian translate is never a plain cast.  The default changes nothing.
+        call; it has no second level, and its Euclidian translate is never a plain cast.  "f8": the FP8 (E4M3) quantiser, one byte
+        per coordinate for either metric, no second level either (DESIGN.md "FP8 rows").  The default changes nothing.
         second_level: None | "bit" | "2bit" -- the three-range beam_search_rerank of graph_index.cpp:156-185: quantised
         searches (quant=True) of the one-byte copy run with a bit-sketch pre-filter (filtered_beam_search, use_filtering) before
         the exact rerank.  "bit": Euclidean_Bit_Point / Mips_Bit_Point by the metric; "2bit": Mips_2Bit_Point (mips only).
@@ -42,10 +43,10 @@ class GraphIndex:
             raise ValueError('second_level must be None, "bit" or "2bit"')
         if second_level == "2bit" and self.metric == "Euclidian":
             raise ValueError('second_level="2bit" (Mips_2Bit_Point) is a mips sketch')
-        if quant_bits not in (8, 4):
-            raise ValueError("quant_bits must be 8 or 4")
-        if quant_bits == 4 and second_level is not None:
-            raise ValueError("quant_bits=4 has no second level: sketches are not attached to four-bit indices")
+        if quant_bits not in (8, 4, "f8"):
+            raise ValueError('quant_bits must be 8, 4 or "f8"')
+        if quant_bits != 8 and second_level is not None:
+            raise ValueError(f"quant_bits={quant_bits!r} has no second level: sketches are not attached to four-bit or FP8 indices")
         self.quant_bits = quant_bits
         if second_level is not None and np.dtype(self.T).itemsize == 1:
             raise ValueError("second_level needs float points: one-byte indices are searched directly (no quantised copy to filter)")
@@ -62,14 +63,16 @@ class GraphIndex:
         self.index = DeviceIndex(self.points, self.graph, metric=self.metric, device=device)
         if self.use_quantization:
             if self.metric == "Euclidian":
-                self.q_index, self.qparams = self.index.quantized("euclid_u8" if quant_bits == 8 else "euclid_u4")   # EQuantRange(Points) :90
-                self.eparams = quantize.EuclidParams.__new__(quantize.EuclidParams)
-                self.eparams.range, self.eparams.dims = (255 if quant_bits == 8 else 15), self.qparams.dims
-                self.eparams.slope, self.eparams.offset = np.float32(self.qparams.slope), np.int32(self.qparams.offset)
+                self.q_index, self.qparams = self.index.quantized({8: "euclid_u8", 4: "euclid_u4", "f8": "f8"}[quant_bits])   # EQuantRange(Points) :90
+                self.eparams = None                                                  # "f8": no integer range / offset (qparams has the slope)
+                if quant_bits != "f8":
+                    self.eparams = quantize.EuclidParams.__new__(quantize.EuclidParams)
+                    self.eparams.range, self.eparams.dims = (255 if quant_bits == 8 else 15), self.qparams.dims
+                    self.eparams.slope, self.eparams.offset = np.float32(self.qparams.slope), np.int32(self.qparams.offset)
             else:
                 self.index.normalize()                                               # :94-95
                 self.points = self.index.points()
-                self.q_index, self.qparams = self.index.quantized("mips_i8" if quant_bits == 8 else "mips_i4", trim=True)   # Quantized_Mips_Point<8,true> :69
+                self.q_index, self.qparams = self.index.quantized({8: "mips_i8", 4: "mips_i4", "f8": "f8"}[quant_bits], trim=True)   # Quantized_Mips_Point<8,true> :69
                 self.mmax = np.float32(self.qparams.max_val)
             if second_level is not None and self.metric == "Euclidian" and self.eparams.identity:
                 raise ValueError("second_level: these points quantise to themselves (slope 1), so quantised searches are plain "

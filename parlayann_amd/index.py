@@ -9,18 +9,20 @@ import numpy as np
 
 from . import _capi
 from ._capi import (PANN_BF16, PANN_F16, PANN_F32, PANN_I4, PANN_I8, PANN_L2, PANN_MIPS, PANN_PRED_ANY, PANN_PRED_MATCH, PANN_PRED_RANGE,
-                    PANN_QUANT_EUCLID_U4, PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats,
+                    PANN_F8, PANN_QUANT_EUCLID_U4, PANN_QUANT_EUCLID_U8, PANN_QUANT_F8, PANN_QUANT_MIPS_I4, PANN_QUANT_MIPS_I8, PANN_U4, PANN_U8, BuildStats,
                     DeleteStats, QuantParams, QueryParams, ReachStats, RerankOut, SearchOut, check)
 from .bf16 import bfloat16
+from .fp8 import float8_e4m3
 
 _DT = {np.dtype(np.uint8): PANN_U8, np.dtype(np.int8): PANN_I8, np.dtype(np.float32): PANN_F32,
-       np.dtype(np.float16): PANN_F16, bfloat16: PANN_BF16}
+       np.dtype(np.float16): PANN_F16, bfloat16: PANN_BF16, float8_e4m3: PANN_F8}
 
 
 # four-bit element types have no numpy dtype: they go by name, their rows are packed uint8 (quantize.pack_nibbles)
 _DT4 = {"u4": PANN_U4, "uint4": PANN_U4, "i4": PANN_I4, "int4": PANN_I4}
 _QUANT_DT = {PANN_QUANT_EUCLID_U8: (np.dtype(np.uint8), PANN_L2, None), PANN_QUANT_MIPS_I8: (np.dtype(np.int8), PANN_MIPS, None),
-             PANN_QUANT_EUCLID_U4: (np.dtype(np.uint8), PANN_L2, PANN_U4), PANN_QUANT_MIPS_I4: (np.dtype(np.uint8), PANN_MIPS, PANN_I4)}
+             PANN_QUANT_EUCLID_U4: (np.dtype(np.uint8), PANN_L2, PANN_U4), PANN_QUANT_MIPS_I4: (np.dtype(np.uint8), PANN_MIPS, PANN_I4),
+             PANN_QUANT_F8: (float8_e4m3, None, None)}      # metric None: the source's
 
 
 def dtype_code(dt):
@@ -41,7 +43,7 @@ def _metric_code(metric):
 
 
 def quant_kind(kind):
-    if kind in (PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4):
+    if kind in (PANN_QUANT_EUCLID_U8, PANN_QUANT_MIPS_I8, PANN_QUANT_EUCLID_U4, PANN_QUANT_MIPS_I4, PANN_QUANT_F8):
         return kind
     k = str(kind).lower()
     if k in ("euclid_u8", "euclidian_u8", "u8"):
@@ -52,6 +54,8 @@ def quant_kind(kind):
         return PANN_QUANT_EUCLID_U4
     if k in ("mips_i4", "i4"):
         return PANN_QUANT_MIPS_I4
+    if k in ("f8", "fp8", "e4m3"):
+        return PANN_QUANT_F8
     raise ValueError(f"unknown quantisation kind {kind!r}")
 
 
@@ -507,12 +511,13 @@ class DeviceIndex:
 
     def quantized(self, kind, trim=True, params=None, copy_graph=True):
         """QPR Q_Points(Points): -> (DeviceIndex of uint8 / int8 rows translated on the device, QuantParams).  kind:
-        "euclid_u8" | "mips_i8" | "euclid_u4" | "mips_i4" (packed four-bit rows); params: translate with these instead of
-        generating them from this index's rows."""
+        "euclid_u8" | "mips_i8" | "euclid_u4" | "mips_i4" (packed four-bit rows) | "f8" (FP8 E4M3 rows, either metric: the copy
+        keeps this index's); params: translate with these instead of generating them from this index's rows."""
         p = self.quantize_params(kind, trim) if params is None else params
         h = C.c_void_p()
         check(self._lib.pann_index_create_quantized(C.byref(h), self._h, C.byref(p), 1 if copy_graph else 0))
-        return DeviceIndex.__new__(DeviceIndex)._adopt(self._lib, h, self.n, self.d, self.max_degree, *_QUANT_DT[p.kind]), p
+        dt, metric, dt4 = _QUANT_DT[p.kind]
+        return DeviceIndex.__new__(DeviceIndex)._adopt(self._lib, h, self.n, self.d, self.max_degree, dt, self.metric if metric is None else metric, dt4), p
 
     # ---- subset index: carve out, compact or grow a handle on the device (DESIGN.md "Subset index") ----
     def subset(self, allow=None, *, where=None, capacity=None, copy_graph=True, maps=True):

@@ -14,6 +14,8 @@ and the four-bit forms (range 15, two coordinates per byte; include/pann.h, PANN
 """
 import numpy as np
 
+from .fp8 import F8_MAX, float8_e4m3, to_f8
+
 F = np.float32
 
 
@@ -89,6 +91,20 @@ def mips_i8_translate(x, max_val, rng=255):
     return v.astype(np.int8)
 
 
+# ---- FP8 (E4M3) rows: include/pann.h, PANN_QUANT_F8 ----
+
+def f8_params(x):
+    """(slope, max_val): M = the largest |x|, slope = the largest power of two s with M * s <= 448 (offset is 0)"""
+    M = F(np.abs(np.asarray(x, dtype=F)).max())
+    m, e = np.frexp(M)                                      # M = m * 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
+    return F(np.ldexp(F(1.0), int(np.clip((8 if m > 0.875 else 9) - e, -126, 127)))), M
+
+
+def f8_translate(x, slope):
+    """y = x * slope in f32, clamped to [-448, 448], rounded to nearest even on the E4M3 grid (fp8.to_f8) -> float8_e4m3 rows"""
+    return to_f8(np.clip(np.asarray(x, dtype=F) * F(slope), -F8_MAX, F8_MAX))
+
+
 # ---- four-bit rows ----
 
 def pack_nibbles(values):
@@ -160,7 +176,7 @@ def device_quantize_rows(x, params, normalize_first=False, device=0):
     if x.ndim != 2 or x.shape[1] != params.dims:
         raise ValueError(f"rows must be n x {params.dims} float32")
     rb = quant_row_bytes(params.kind, params.dims)
-    out = np.empty((len(x), rb), np.int8 if params.kind == _capi.PANN_QUANT_MIPS_I8 else np.uint8)
+    out = np.empty((len(x), rb), {_capi.PANN_QUANT_MIPS_I8: np.int8, _capi.PANN_QUANT_F8: float8_e4m3}.get(params.kind, np.uint8))
     if len(x):
         _capi.check(_capi.load().pann_quantize_rows(C.byref(params), x.ctypes.data_as(C.c_void_p), len(x), x.shape[1] * 4,
                                                     1 if normalize_first else 0, out.ctypes.data_as(C.c_void_p), rb, device))

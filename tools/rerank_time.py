@@ -16,6 +16,7 @@ call.  Run the tool under `timeout -k 10 <seconds>` so that a hang ends the proc
 
     python tools/rerank_time.py [--n 1000000] [--d 128] [--nq 10000] [--steps 20] [--json out.json]
     python tools/rerank_time.py --bits 4 [--beam 128] # the quantised copy holds four-bit rows (DESIGN.md "Four-bit rows")
+    python tools/rerank_time.py --bits f8 [--metric mips]   # ... FP8 (E4M3) rows (DESIGN.md "FP8 rows"); --metric goes with every --bits
     python tools/rerank_time.py --profile-steps 5     # only fused steps, for a kernel trace taken in a run of its own
 """
 import argparse
@@ -64,20 +65,27 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--profile-steps", type=int, default=0)
     ap.add_argument("--json", default=None)
-    ap.add_argument("--bits", type=int, choices=(8, 4), default=8, help="bits per coordinate of the quantised copy")
+    ap.add_argument("--bits", type=lambda v: v if v == "f8" else int(v), choices=(8, 4, "f8"), default=8,
+                    help="bits per coordinate of the quantised copy; f8: one byte of FP8 E4M3")
     ap.add_argument("--beam", type=int, default=BEAM)
+    ap.add_argument("--metric", choices=("Euclidian", "mips"), default="Euclidian", help="mips: normalised rows and queries, the MIPS quantisers")
     a = ap.parse_args()
     import torch
-    n, d, nq, beam = a.n, a.d, a.nq, a.beam
-    qrow = d if a.bits == 8 else (d + 1) // 2          # bytes of one row of the quantised copy
+    n, d, nq, beam, mips = a.n, a.d, a.nq, a.beam, a.metric == "mips"
+    qrow = (d + 1) // 2 if a.bits == 4 else d          # bytes of one row of the quantised copy
     with step("data", 300):                       # real-valued, so that the quantiser is not the identity
-        X = (datasets.deep_like(n, d, seed=1) * 2.0).astype(np.float32)
-        Q = (datasets.deep_like(nq, d, seed=2) * 2.0).astype(np.float32)
+        if mips:                                   # queries normalised here, the rows on the device: every step sees the same floats
+            X, Q = datasets.t2i_like(n, d, seed=1), quantize.normalize_rows(datasets.t2i_like(nq, d, seed=2))
+        else:
+            X = (datasets.deep_like(n, d, seed=1) * 2.0).astype(np.float32)
+            Q = (datasets.deep_like(nq, d, seed=2) * 2.0).astype(np.float32)
     with step("upload + build R=64 L=128", 900):
-        full = DeviceIndex(X, max_degree=64, metric="Euclidian")
+        full = DeviceIndex(X, max_degree=64, metric=a.metric)
+        if mips:
+            full.normalize()
         full.vamana_build(64, 128, 1.2, num_passes=1, seed=3)
     with step("quantise", 120):
-        quant, qparams = full.quantized("euclid_u8" if a.bits == 8 else "euclid_u4")
+        quant, qparams = full.quantized({8: "mips_i8" if mips else "euclid_u8", 4: "mips_i4" if mips else "euclid_u4", "f8": "f8"}[a.bits])
         assert not qparams.identity
     lib = _capi.load()
     qp = _capi.QueryParams(k=K, beam=beam, cut=1.35, limit=n, degree_limit=64, rerank_factor=RF, pad=1.0)
@@ -158,7 +166,7 @@ def main():
         print("ERROR: the fused ids differ from the composed ids", flush=True)
         sys.exit(1)
     print(f"  fused ids == composed ids; table {n * d * 4 / 2**20:.0f} MiB float / {n * qrow / 2**20:.0f} MiB "
-          f"{'one-byte' if a.bits == 8 else 'four-bit'} (Infinity Cache: 256 MiB)", flush=True)
+          f"{'four-bit' if a.bits == 4 else 'one-byte'} (Infinity Cache: 256 MiB)", flush=True)
     if a.json:
         with open(a.json, "w") as f:
             json.dump(dict(n=n, d=d, nq=nq, k=K, beam=beam, bits=a.bits, rerank_factor=RF, steps=a.steps, rows=rows), f, indent=1)
