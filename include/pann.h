@@ -16,6 +16,7 @@
  *   data_tools/compute_range_groundtruth.cpp:13-29 brute-force radius join -> pann_bruteforce_range
  *   algorithms/utils/beamSearch.h:567-614  RangeSearch (beam search + BFS)  -> pann_range_query
  *   algorithms/utils/beamSearch.h:390-454  beam_search_rerank (quantised)   -> pann_batch_search_rerank*
+ *   (none: the exhaustive twin of beam_search_rerank, this build's own)    -> pann_scan_rerank*
  *
  * The reference has no FFI of its own for this path (it is a header-only template library); these
  * entry points are what a cgo/ctypes/pybind binding placed at the parallel_for seams above would
@@ -66,7 +67,8 @@ extern "C" {
  *            -256 * sum a * q, over ALL d coordinates (the reference's loops stop at dims / 2 bytes and so drop the last
  *            coordinate of an odd d)
  * Any other pairing is refused by pann_index_create* with PANN_ERR_UNSUPPORTED.  A 4-bit handle is searched
- * (pann_batch_search*, as `quant` of pann_batch_search_rerank*), measured (pann_pair_distances, pann_query_distances), and has
+ * (pann_batch_search*, as `quant` of pann_batch_search_rerank*), scanned exhaustively (as `quant` of pann_scan_rerank*),
+ * measured (pann_pair_distances, pann_query_distances), and has
  * its points and graph moved (upload / download / set_graph / update_rows / get_graph); it gets its graph from
  * pann_index_create_quantized(copy_graph) or pann_index_set_graph.  Every entry point that builds, prunes, ranges, reranks ON
  * it, filters through a sketch or runs a dense all-pairs pass returns PANN_ERR_UNSUPPORTED before anything is launched,
@@ -624,6 +626,33 @@ int pann_batch_search_rerank(pann_index* full, pann_index* quant, const pann_qua
                              uint64_t nq, uint64_t q_stride_bytes, int normalize_first, int use_filter,
                              const uint32_t* starts, uint32_t nstarts, const pann_query_params* qp,
                              const pann_rerank_out* out);
+
+/* ---- exhaustive quantised scan + exact rerank in one call (DESIGN.md "Exhaustive quantised scan") ----  The exhaustive twin of
+ * pann_batch_search_rerank: no graph is read.  full: the f32 handle; quant: its PANN_U8 / PANN_I8 / PANN_U4 / PANN_I4 copy (same
+ * n, d, device and metric; device rows of at most 512 bytes: d <= 512, four-bit d <= 1024).  Per batch of nq float query rows, on
+ * one stream:
+ *   1. the queries are quantised as by pann_batch_search_rerank (normalize_first: normalised first, and the normalised row is
+ *      the one the rerank scores against); there is no sketch;
+ *   2. EVERY row of quant is scored against every quantised query on the int8 matrix cores, in exact int32 arithmetic -- the
+ *      distance of pann_query_distances on quant, cast to float once -- and the c = min(k * rerank_factor, 64, n) rows with the
+ *      smallest (float distance, id) are kept, in that order: d_out_cand_ids (optional, nq x c), d_out_cand_count (optional, nq:
+ *      always c);
+ *   3. those c ids get their exact distance on `full` (the arithmetic of pann_rerank, resort = 1), are sorted by (dist, id), and
+ *      k are kept; k > c writes the c results there are and fills the rest of the row with 0xFFFFFFFF / +inf.
+ * d_out_ids / d_out_dists (nq x k) equal pann_rerank on full with the returned candidates, bit for bit.
+ * Status: NULL handles / qparams / ids / dists / queries, k == 0, rerank_factor < 1, handles that differ in n, d, device or
+ * metric, a kind that does not fit quant's element type, a row stride shorter than a row or not a multiple of 4 ->
+ * PANN_ERR_BAD_ARG; a `full` handle that is not f32, a quant of PANN_F8 (no exact integer form) or of any type but the four, rows
+ * of more than 512 bytes -> PANN_ERR_UNSUPPORTED; nq == 0 -> PANN_OK.  Nothing is written on an error.
+ * Device pointers throughout, launched on `stream`; no synchronisation, and no allocation once quant's scratch has reached its
+ * size (call once to warm up). */
+int pann_scan_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                         uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, uint32_t* d_out_ids,
+                         float* d_out_dists, uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream);
+/* Host pointers: the queries go up in one transfer, the outputs come back in one.  Runs on quant's stream. */
+int pann_scan_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                     uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, uint32_t* out_ids, float* out_dists,
+                     uint32_t* out_cand_ids, uint32_t* out_cand_count);
 
 /* ---- masked beam search: results restricted by an allow bitmap, traversal unchanged (DESIGN.md "Masked search") ----
  * allow: ceil(n / 32) uint32 words per row; point i is allowed iff bit (i & 31) of word (i >> 5) is set; bits at positions

@@ -2877,3 +2877,92 @@ int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const 
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// exhaustive quantised scan + exact rerank in one call (dense.hip, search_rerank.hip)
+// ---------------------------------------------------------------------------------------------
+
+namespace {
+
+// everything pann_scan_rerank* refuses, before anything is enqueued -- the rules of search_rerank_checks where they apply
+int scan_rerank_checks(const char* fn, const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                       uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int rerank_factor, const uint32_t* out_ids, const float* out_dists) {
+  const std::string f = fn;
+  if (!full || !quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
+  if (!qparams || !out_ids || !out_dists) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
+  if (k == 0) { set_error(f + ": k must be at least 1"); return PANN_ERR_BAD_ARG; }
+  if (rerank_factor < 1) { set_error(f + ": rerank_factor must be at least 1"); return PANN_ERR_BAD_ARG; }
+  const DeviceIndex& fx = full->ix;
+  const DeviceIndex& qx = quant->ix;
+  if (fx.dtype != PANN_F32) { set_error(f + ": the full-precision index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
+  if (fx.n != qx.n || fx.d != qx.d || full->device != quant->device || fx.metric != qx.metric) {
+    set_error(f + ": the two indices must agree in size, dimension, device and metric"); return PANN_ERR_BAD_ARG;
+  }
+  if (qx.dtype != PANN_U8 && qx.dtype != PANN_I8 && !is_4bit_dtype(qx.dtype)) {
+    set_error(f + ": not supported on a " + dtype_name(qx.dtype) + " quantised index (the scan is exact integer arithmetic: PANN_U8, PANN_I8, PANN_U4, PANN_I4)");
+    return PANN_ERR_UNSUPPORTED;
+  }
+  if (int rc = check_quant_kind(qparams->kind, fn)) return rc;
+  if (qx.dtype != quant_kind_dtype(qparams->kind) || !quant_kind_fits_metric(qparams->kind, qx.metric) || (uint32_t)qparams->dims != qx.d) {
+    set_error(f + ": the quantisation parameters do not fit the quantised index (EUCLID_U8 <-> u8 / L2, MIPS_I8 <-> i8 / MIPS, EUCLID_U4 <-> "
+                  "u4 / L2, MIPS_I4 <-> i4 / MIPS, same dimension)");
+    return PANN_ERR_BAD_ARG;
+  }
+  if (!dense_scan_eligible(qx)) { set_error(f + ": quantised rows of more than 512 bytes are not supported"); return PANN_ERR_UNSUPPORTED; }
+  if (q_stride_bytes < 4ull * fx.d || q_stride_bytes % 4 != 0) { set_error(f + ": query stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }
+  if (nq && !queries) { set_error(f + ": null queries"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+uint32_t scan_list_length(const pann_index* quant, uint32_t k, int rerank_factor) {      // c = min(k * rerank_factor, 64, n)
+  return (uint32_t)std::min<uint64_t>(std::min<uint64_t>((uint64_t)k * (uint64_t)rerank_factor, 64), quant->ix.n);
+}
+
+// the launches for device pointers; nsplit as pann_bruteforce_knn chooses it.  The scratch belongs to quant.
+int scan_rerank_launch(pann_index* full, pann_index* quant, ScanRerankCall r, int rerank_factor) {
+  r.c = scan_list_length(quant, r.k, rerank_factor);
+  const uint32_t ntiles = (uint32_t)((r.nq + 63) / 64);
+  r.nsplit = choose_gt_pieces(quant, ntiles, (double)dense_scan_slots(quant->ix, r.c), quant->ix.n);
+  return scan_rerank_dev(full->ix, quant->ix, quant->ws_rr, quant->ws2, r);
+}
+
+}  // namespace
+
+extern "C" {
+
+int pann_scan_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                         uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, uint32_t* d_out_ids, float* d_out_dists,
+                         uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream) {
+  const char* fn = "pann_scan_rerank_dev";
+  if (int rc = scan_rerank_checks(fn, full, quant, qparams, d_queries, nq, q_stride_bytes, k, rerank_factor, d_out_ids, d_out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)d_queries % 4 != 0) { set_error(std::string(fn) + ": query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  ScanRerankCall r;
+  r.qparams = qparams; r.queries = d_queries; r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first; r.k = k;
+  r.out_ids = d_out_ids; r.out_dists = d_out_dists; r.out_cand_ids = d_out_cand_ids; r.out_cand_count = d_out_cand_count; r.stream = stream;
+  return scan_rerank_launch(full, quant, r, rerank_factor);
+}
+
+int pann_scan_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                     uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, uint32_t* out_ids, float* out_dists,
+                     uint32_t* out_cand_ids, uint32_t* out_cand_count) {
+  if (int rc = scan_rerank_checks("pann_scan_rerank", full, quant, qparams, queries, nq, q_stride_bytes, k, rerank_factor, out_ids, out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  DeviceGuard g(quant->device);
+  const uint32_t c = scan_list_length(quant, k, rerank_factor);
+  HostTrip t(quant);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * quant->ix.d);
+  const int o_cnt = t.out.add(out_cand_count, nq * 4);      // (the small pieces first: HostTrip)
+  const int o_ids = t.out.add(out_ids, nq * k * 4), o_dists = t.out.add(out_dists, nq * k * 4);
+  const int o_cand = t.out.add(out_cand_ids, nq * c * 4);
+  if (int rc = t.begin()) return rc;
+  ScanRerankCall r;
+  r.qparams = qparams; r.queries = (const float*)t.din<uint8_t>(i_q); r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first; r.k = k;
+  r.out_ids = t.dout<uint32_t>(o_ids); r.out_dists = t.dout<float>(o_dists);
+  r.out_cand_ids = t.dout<uint32_t>(o_cand); r.out_cand_count = t.dout<uint32_t>(o_cnt); r.stream = t.st;
+  if (int rc = scan_rerank_launch(full, quant, r, rerank_factor)) return rc;
+  return t.finish();
+}
+
+}  // extern "C"

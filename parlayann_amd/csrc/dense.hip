@@ -1244,6 +1244,209 @@ __global__ void __launch_bounds__(256, 2) dense_gt_valu_kernel(DenseArgs A, cons
   gt_sel_write<NR>(S, A.partial + ((a0 + wave * DT_AW + q * 4) * A.nsplit + blockIdx.y) * A.m, A.m, A.nsplit, lane);
 }
 
+// ---- exhaustive scan of a quantised copy on the int8 matrix cores (DESIGN.md "Exhaustive quantised scan") ----
+// External quantised query rows against ALL rows of a PANN_U8 / PANN_U4 (L2) or PANN_I8 / PANN_I4 (MIPS) handle, top-m per query,
+// m <= 64, on v_mfma_i32_16x16x64_i8.  The frame is dense_gt_valu_kernel's: 64 x 64 tile, B through the swizzled double buffer one
+// 256-byte segment per pipeline step, the register lists of GtSel in the MFMA's output layout.  What differs:
+//   * A sits in LDS for the whole piece in the SAME swizzled layout as B ([segment][64][256]): per 64 row bytes a lane reads one
+//     16-byte A fragment (row wave*16 + (lane & 15), bytes ks*64 + 16 q ..) and the four B fragments at the same offset.  A dot
+//     product does not care in which order k is walked, so the instruction's own k order is never reproduced: both operands come
+//     through the one lane-to-byte mapping.
+//   * one-byte rows: the 16 bytes are the operand (4 MFMAs per 64 row bytes).  The instruction is signed, so PANN_U8 is moved by
+//     -128 -- bit 7 of EVERY byte of A, of B and of the chunks behind the row that a k step still covers is flipped, and both norms
+//     are taken of exactly those bytes, so the padding's terms cancel in |a|^2 + |b|^2 - 2 a.b (L2 does not see a translation).
+//   * four-bit rows stay packed in HBM and in LDS; a lane's 16 bytes are 32 coordinates and feed TWO MFMAs, the low nibbles of all
+//     16 bytes and the high nibbles (one mask, one shift-and-mask per dword): 8 MFMAs per 64 row bytes = 128 coordinates.
+//     PANN_U4: the nibble values 0..15 as int8.  PANN_I4: the nibble in the HIGH half of the byte, i.e. the signed nibble times
+//     16 in each factor -- the accumulator is 256 x the nibble dot product, the very value dist_finish<PANN_I4> defines.
+// Everything is int32 and exact; the distance is cast to float once (dist_finish's cast), ties break by id in the 64-bit key.
+typedef int mf_int4 __attribute__((ext_vector_type(4)));
+constexpr bool scan_is_l2(int dt) { return dt == PANN_U8 || dt == PANN_U4; }
+constexpr bool scan_is_4bit(int dt) { return dt == PANN_U4 || dt == PANN_I4; }
+constexpr int SCAN_PAD_SQ = 16 * 128 * 128;      // |.|^2 of a 16-byte chunk of zero bytes once bit 7 is flipped (PANN_U8)
+
+__device__ __forceinline__ uint4 scan_flip7(const uint4& v) {
+  return make_uint4(v.x ^ 0x80808080u, v.y ^ 0x80808080u, v.z ^ 0x80808080u, v.w ^ 0x80808080u);
+}
+// |chunk|^2 of 16 row bytes as the scan multiplies them: PANN_U8 moved by -128, PANN_U4 on the nibble values
+template <int DT>
+__device__ __forceinline__ int scan_chunk_sq(const uint4& v) {
+  if constexpr (DT == PANN_U8) return sumsq16_i8<PANN_I8>(scan_flip7(v));
+  else {
+    uint32_t x = __builtin_amdgcn_udot8(v.x, v.x, 0u, false); x = __builtin_amdgcn_udot8(v.y, v.y, x, false);
+    x = __builtin_amdgcn_udot8(v.z, v.z, x, false); x = __builtin_amdgcn_udot8(v.w, v.w, x, false);
+    return (int)x;
+  }
+}
+// the zero chunks between the end of a row's data and the end of its last k step (4 chunks per step), as |.|^2 of the moved bytes
+template <int DT>
+__device__ __forceinline__ int scan_pad_sq(uint32_t nch) { return DT == PANN_U8 ? (int)((nch + 3u) / 4u * 4u - nch) * SCAN_PAD_SQ : 0; }
+// the int8 operand of the low (HI = false) or high nibbles of 16 packed bytes
+template <int DT, bool HI>
+__device__ __forceinline__ mf_int4 scan_nibbles(const uint4& v) {
+  const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+  mf_int4 o;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    if constexpr (DT == PANN_U4) o[i] = (int)((HI ? w[i] >> 4 : w[i]) & 0x0F0F0F0Fu);
+    else o[i] = (int)((HI ? w[i] : w[i] << 4) & 0xF0F0F0F0u);
+  }
+  return o;
+}
+// 64 row bytes: acc[t] += a(row lane & 15) . b(row t*16 + (lane & 15)) over the lane group's 16 bytes (A of PANN_U8 is stored moved)
+template <int DT>
+__device__ __forceinline__ void scan_mfma_step(const uint4& a, const uint4 (&b)[4], mf_int4 (&acc)[4]) {
+  if constexpr (scan_is_4bit(DT)) {
+    const mf_int4 alo = scan_nibbles<DT, false>(a), ahi = scan_nibbles<DT, true>(a);
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(alo, scan_nibbles<DT, false>(b[t]), acc[t], 0, 0, 0);
+      acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(ahi, scan_nibbles<DT, true>(b[t]), acc[t], 0, 0, 0);
+    }
+  } else {
+    mf_int4 a4; __builtin_memcpy(&a4, &a, 16);
+#pragma unroll
+    for (int t = 0; t < 4; t++) {
+      const uint4 bv = DT == PANN_U8 ? scan_flip7(b[t]) : b[t];
+      mf_int4 b4; __builtin_memcpy(&b4, &bv, 16);
+      acc[t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a4, b4, acc[t], 0, 0, 0);
+    }
+  }
+}
+// |row|^2 of every point as the scan multiplies it (scan_chunk_sq over the nch data chunks + the moved padding), exact int32
+template <int DT>
+__global__ void __launch_bounds__(256) scan_norms_kernel(const uint8_t* points, uint32_t pstride, uint32_t nch, uint64_t n, int* out) {
+  const uint64_t row = (uint64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const uint32_t c = threadIdx.x & 15;
+  int ss = 0;
+  if (row < n) for (uint32_t j = c; j < nch; j += 16) ss += scan_chunk_sq<DT>(*reinterpret_cast<const uint4*>(points + row * pstride + j * 16));
+  ss = group_sum<16>(ss) + scan_pad_sq<DT>(nch);
+  if (row < n && c == 0) out[row] = ss;
+}
+// (the shared thresholds start at "none"; a kernel, so that the scan can be recorded into a graph)
+__global__ void __launch_bounds__(256) scan_fill_kernel(uint32_t* p, uint64_t n, uint32_t v) {
+  for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) p[i] = v;
+}
+
+template <int DT, int NR>
+__global__ void __launch_bounds__(256, 2) dense_scan_mfma_kernel(DenseArgs A, const int* __restrict__ bnorm, uint32_t* gtau) {
+  constexpr bool L2 = scan_is_l2(DT);
+  extern __shared__ __align__(16) uint8_t smem[];
+  const uint32_t nch = (A.dbytes + 15) / 16;                              // 16-byte chunks that hold data: 1 .. 32 (the launcher checks)
+  const uint32_t nseg = (nch + 15) / 16;
+  uint8_t* Bt0 = smem;                                                    // [2][64][GT_BSTRIDE], slots swizzled (gt_swz)
+  float2* Bm = reinterpret_cast<float2*>(smem + 2 * GT_BT_BYTES);         // [2][64] (|b|^2 bits, id bits)
+  int* An = reinterpret_cast<int*>(Bm + 2 * DT_B);                        // [64] |a|^2 (L2)
+  uint8_t* At = reinterpret_cast<uint8_t*>(An + DT_A);                    // [nseg][64][GT_BSTRIDE], swizzled like B
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4;
+  const TileGeom g = tile_geom(A.na, A.nb, piece_rows(A.nb, A.nsplit, DT_B));
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
+  const uint32_t ntile = (uint32_t)((be - bs + DT_B - 1) / DT_B);
+  const int r0 = tid >> 4, c = tid & 15;
+  // the A tile -> LDS (rows beyond the tile and bytes beyond the row: zeros), PANN_U8 moved; |a|^2 of the bytes the k steps cover
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    int ss = 0;
+    for (uint32_t sg = 0; sg < nseg; sg++) {
+      uint4 v = dense_a_load(A, g, r0 + 16 * k, sg * DT_SEG + c * 16);
+      if (L2 && sg * 16u + (uint32_t)c < nch) ss += scan_chunk_sq<DT>(v);
+      if constexpr (DT == PANN_U8) v = scan_flip7(v);
+      *reinterpret_cast<uint4*>(At + sg * GT_BT_BYTES + gt_swz((uint32_t)(r0 + 16 * k), (uint32_t)c * 16u)) = v;
+    }
+    if constexpr (L2) { ss = group_sum<16>(ss) + scan_pad_sq<DT>(nch); if (c == 0) An[r0 + 16 * k] = ss; }
+  }
+  GtSel<NR> S;
+  gt_sel_init<NR>(S, A.m, (uint32_t)(wave * DT_AW + q * 4), na_tile, lane);
+  // pipeline step u = (tile u / nseg, segment u % nseg), buffer u & 1 (dense_gt_valu_kernel): with two segments buffer b always
+  // holds segment b.  A chunk column that holds no data is never staged: it is zeroed here, once, in both buffers.
+  const bool cv0 = (uint32_t)c < nch, cv1 = nseg == 2 && 16u + (uint32_t)c < nch;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    if (!((nseg == 2 && (k >> 2)) ? cv1 : cv0))
+      *reinterpret_cast<uint4*>(Bt0 + (k >> 2) * GT_BT_BYTES + gt_swz((uint32_t)(r0 + 16 * (k & 3)), (uint32_t)c * 16u)) = make_uint4(0, 0, 0, 0);
+  }
+  __syncthreads();
+  int an[4] = {0, 0, 0, 0};
+  if constexpr (L2) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) an[r] = An[wave * DT_AW + q * 4 + r];
+  }
+  const uint32_t pplace = 16u * NR - A.m + (A.m + A.nsplit - 1) / A.nsplit - 1;
+  const uint32_t skip[4] = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
+  const uint32_t tau_period = GT_TAU_PERIOD * ((A.nsplit + 7) / 8);
+  uint32_t tau_wait = tau_period;
+  uint32_t* gtau_mine = gtau + (a0 + wave * DT_AW + q * 4) * A.nsplit + blockIdx.y;
+
+  const uint32_t nunits = ntile * nseg;
+  const uint32_t last_row = (uint32_t)(be - 1);                           // (read only where a load is issued: be > bs there)
+  const uint8_t* cb0 = A.points + min((uint32_t)c, nch - 1u) * 16u;
+  const uint8_t* cb1 = A.points + min(16u + (uint32_t)c, nch - 1u) * 16u;
+  uint4 pre0, pre1, pre2, pre3;
+  int pn = 0;
+  auto unit_bt = [&](uint32_t u) -> uint32_t { return (uint32_t)bs + (nseg == 2 ? (u >> 1) : u) * DT_B; };
+  auto load_pre = [&](uint32_t u) {          // requests only: clamped rows, no branch around a load
+    const uint32_t bt = unit_bt(u);
+    const uint8_t* cb = (nseg == 2 && (u & 1)) ? cb1 : cb0;
+    pre0 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0, last_row) * A.pstride);
+    pre1 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 16u, last_row) * A.pstride);
+    pre2 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 32u, last_row) * A.pstride);
+    pre3 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 48u, last_row) * A.pstride);
+    if (L2) pn = bnorm[min(bt + (uint32_t)lane, last_row)];
+  };
+  auto store_pre = [&](uint32_t u) {
+    const int buf = (int)(u & 1);
+    gt_store_tile(Bt0 + buf * GT_BT_BYTES, Bm + buf * DT_B, (nseg == 2 && (u & 1)) ? cv1 : cv0, pre0, pre1, pre2, pre3, __int_as_float(pn),
+                  unit_bt(u), be, tid);
+  };
+  if (nunits > 0) {
+    load_pre(0); store_pre(0);
+    load_pre(1);
+  }
+  lds_barrier();
+
+  mf_int4 acc[4];
+  const uint32_t arow = (uint32_t)(wave * DT_AW + (lane & 15));
+  for (uint32_t u = 0; u < nunits; u++) {
+    const int buf = (int)(u & 1);
+    const uint32_t sg = nseg == 2 ? (u & 1) : 0u;
+    if (sg == 0 && A.nsplit > 1 && --tau_wait == 0) { tau_wait = tau_period; gt_sel_refresh<NR>(S, gtau + a0 * A.nsplit, (uint32_t)(wave * DT_AW + q * 4), na_tile, A.nsplit, lane); }
+    store_pre(u + 1);                                          // (beyond the last step: the piece's last row again, into a dead buffer)
+    load_pre(u + 2);
+    if (sg == 0) {
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[t] = mf_int4{0, 0, 0, 0};
+    }
+    const uint8_t* Bt = Bt0 + buf * GT_BT_BYTES;
+    const uint8_t* Ap = At + sg * GT_BT_BYTES;
+    const uint32_t nks = (min(16u, nch - sg * 16u) + 3u) / 4u;              // k steps of 64 row bytes that reach data in this segment
+    for (uint32_t ks = 0; ks < nks; ks++) {
+      const uint32_t off = ks * 64u + (uint32_t)q * 16u;
+      uint4 braw[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) braw[t] = *reinterpret_cast<const uint4*>(Bt + gt_swz((uint32_t)(t * 16 + (lane & 15)), off));
+      scan_mfma_step<DT>(*reinterpret_cast<const uint4*>(Ap + gt_swz(arow, off)), braw, acc);
+    }
+    if (sg == nseg - 1) {
+      // ---- epilogue: acc[t][r] = a(row wave*16 + 4q + r) . b(column t*16 + (lane & 15)) ----
+      int bn[4]; uint32_t bid[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) { const float2 m2 = Bm[buf * DT_B + t * 16 + (lane & 15)]; bn[t] = __float_as_int(m2.x); bid[t] = __float_as_uint(m2.y); }
+      float dist[4][4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          if constexpr (L2) dist[r][t] = (float)(an[r] + bn[t] - 2 * acc[t][r]);
+          else dist[r][t] = -(float)acc[t][r];
+        }
+      }
+      gt_select<NR>(S, dist, bid, skip, pplace, gtau_mine, A.nsplit, lane);
+    }
+    lds_barrier();
+  }
+  gt_sel_write<NR>(S, A.partial + ((a0 + wave * DT_AW + q * 4) * A.nsplit + blockIdx.y) * A.m, A.m, A.nsplit, lane);
+}
+
 // merge the nsplit partial lists of each A row (one wave per row) and write ids / dists
 __global__ void __launch_bounds__(64) dense_merge_kernel(const uint64_t* partial, uint64_t na, uint32_t nsplit,
                                                          uint32_t m, uint32_t mcap, uint32_t* out_ids, float* out_dists) {
@@ -1372,6 +1575,57 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
   PANN_HIP(hipGetLastError());
   hipLaunchKernelGGL(dense_merge_kernel, dim3((uint32_t)na), dim3(64), (size_t)mcap * 8, st,
                      (const uint64_t*)partial, na, nsplit, m, mcap, c.out_ids, c.out_dists);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
+// ---- the exhaustive quantised scan (dense_scan_mfma_kernel): external quantised rows against all points, m <= 64 ----
+using ScanKernel = void (*)(DenseArgs, const int*, uint32_t*);
+// list registers per row: 1 (m <= 16) or 4 (m <= 64); the four pairings the quantiser produces, or null
+static ScanKernel dense_scan_kernel_of(const DeviceIndex& ix, uint32_t m) {
+  const bool one = m <= 16;
+  if (ix.dtype == PANN_U8 && ix.metric == PANN_L2) return one ? dense_scan_mfma_kernel<PANN_U8, 1> : dense_scan_mfma_kernel<PANN_U8, 4>;
+  if (ix.dtype == PANN_I8 && ix.metric == PANN_MIPS) return one ? dense_scan_mfma_kernel<PANN_I8, 1> : dense_scan_mfma_kernel<PANN_I8, 4>;
+  if (ix.dtype == PANN_U4 && ix.metric == PANN_L2) return one ? dense_scan_mfma_kernel<PANN_U4, 1> : dense_scan_mfma_kernel<PANN_U4, 4>;
+  if (ix.dtype == PANN_I4 && ix.metric == PANN_MIPS) return one ? dense_scan_mfma_kernel<PANN_I4, 1> : dense_scan_mfma_kernel<PANN_I4, 4>;
+  return nullptr;
+}
+bool dense_scan_eligible(const DeviceIndex& ix) { return dense_scan_kernel_of(ix, 1) != nullptr && ix.pstride <= 2 * DT_SEG; }
+static size_t dense_scan_lds(const DeviceIndex& ix) { return GT_LDS_BYTES + (size_t)((ix.dbytes + DT_SEG - 1) / DT_SEG) * GT_BT_BYTES; }
+// workgroups of the scan that are resident at once (for the caller's choice of nsplit)
+uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m) {
+  const void* kern = reinterpret_cast<const void*>(dense_scan_kernel_of(ix, m));
+  const size_t lds = dense_scan_lds(ix);
+  int v = 0;
+  (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, lds) != hipSuccess || v < 1) v = 1;
+  return 256u * (uint32_t)v;
+}
+// c.a_ext: na rows in ix's own row format, 16-byte aligned, c.a_stride a multiple of 16; c.m <= 64; B = all c.nb points
+int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c) {
+  const ScanKernel kern = dense_scan_kernel_of(ix, c.m);
+  if (!kern || ix.pstride > 2 * DT_SEG || c.m == 0 || c.m > 64) { set_error("quantised scan: unsupported element type, row length or list length"); return PANN_ERR_UNSUPPORTED; }
+  if (c.na == 0) return PANN_OK;
+  const uint32_t mcap = (c.m + 15) / 16 * 16, nch = (ix.dbytes + 15) / 16;
+  uint64_t* partial; int* d_norm = nullptr; uint32_t* d_gtau;
+  if (int rc = carve_into(ws, 256, [&](Carve& cv) {
+    partial = cv.take<uint64_t>((size_t)c.na * c.nsplit * c.m);
+    if (ix.metric == PANN_L2) d_norm = cv.take<int>(c.nb);
+    d_gtau = cv.take<uint32_t>((size_t)c.na * c.nsplit);
+  })) return rc;
+  DenseArgs A{};
+  A.points = ix.points; A.pstride = ix.pstride; A.dbytes = ix.dbytes;
+  A.a_ext = c.a_ext; A.a_stride = c.a_stride; A.na = c.na; A.nb = c.nb; A.nsplit = c.nsplit; A.m = c.m; A.mcap = mcap; A.partial = partial;
+  const uint64_t ngtau = c.na * c.nsplit;
+  hipLaunchKernelGGL(scan_fill_kernel, dim3((uint32_t)std::min<uint64_t>((ngtau + 255) / 256, 4096)), dim3(256), 0, st, d_gtau, ngtau, 0xFFFFFFFFu);
+  const dim3 ng((uint32_t)((c.nb + 15) / 16));
+  if (ix.dtype == PANN_U8) hipLaunchKernelGGL(scan_norms_kernel<PANN_U8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.nb, d_norm);
+  else if (ix.dtype == PANN_U4) hipLaunchKernelGGL(scan_norms_kernel<PANN_U4>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.nb, d_norm);
+  PANN_HIP(hipGetLastError());
+  launch_lds(kern, dim3(c.ntiles, c.nsplit), dim3(256), dense_scan_lds(ix), st, A, (const int*)d_norm, d_gtau);
+  PANN_HIP(hipGetLastError());
+  hipLaunchKernelGGL(dense_merge_kernel, dim3((uint32_t)c.na), dim3(64), (size_t)mcap * 8, st,
+                     (const uint64_t*)partial, c.na, c.nsplit, c.m, mcap, c.out_ids, c.out_dists);
   PANN_HIP(hipGetLastError());
   return PANN_OK;
 }

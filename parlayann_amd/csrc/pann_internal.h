@@ -186,6 +186,12 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
 int query_distances_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_q_ext, uint64_t q_stride,
                         const uint32_t* d_q_ids, uint64_t nq, const uint32_t* d_ids, uint64_t m, int paired,
                         float* d_out);
+// the exhaustive scan of a quantised copy on the int8 matrix cores (DESIGN.md "Exhaustive quantised scan"): the c.m <= 64 nearest
+// of ALL c.nb points for c.na external rows in the handle's own row format (c.a_ext 16-byte aligned, c.a_stride a multiple of 16),
+// sorted by (float32 of the exact integer distance, id).  PANN_U8 / PANN_U4 with L2, PANN_I8 / PANN_I4 with MIPS, pstride <= 512.
+bool dense_scan_eligible(const DeviceIndex& ix);
+uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m);      // workgroups resident at once, for the choice of c.nsplit
+int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c);
 
 int pivot_split_dev(const DeviceIndex& ix, hipStream_t st, const uint32_t* d_ids, const uint32_t* d_tile_seg,
                     const uint64_t* d_tile_lo, const uint32_t* d_tile_cnt, uint32_t ntiles, const uint32_t* d_pa,
@@ -354,6 +360,17 @@ size_t search_rerank_scratch_bytes(const DeviceIndex& quant, uint64_t nq, uint32
 size_t search_rerank_ws_bytes(const DeviceIndex& quant, const RerankCall& r);      // of the search workspace, by the same request
 int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, const Workspace& search_ws, void* scratch,
                       const pann_sketch_params* sparams, const RerankCall& r);
+// pann_scan_rerank* (search_rerank.hip): prepare the queries as above (no sketch), dense_scan_dev over all rows of quant with lists of
+// c = min(k * rerank_factor, 64, n) ids, rerank of the lists on full.  Device pointers; the prepared rows and what the caller does not
+// take of the lists are carved from rr_ws, the scan's partial lists from scan_ws.  k > c: the rest of a row is 0xFFFFFFFF / +inf.
+struct ScanRerankCall {
+  const pann_quant_params* qparams = nullptr; const float* queries = nullptr; uint64_t nq = 0, qstride = 0; int normalize_first = 0;
+  uint32_t k = 0, c = 0, nsplit = 1;
+  uint32_t* out_ids = nullptr; float* out_dists = nullptr;                 // nq x k
+  uint32_t* out_cand_ids = nullptr, *out_cand_count = nullptr;            // nq x c, nq (optional)
+  void* stream = nullptr;
+};
+int scan_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace& rr_ws, Workspace& scan_ws, const ScanRerankCall& r);
 
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,

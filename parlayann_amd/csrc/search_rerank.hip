@@ -360,4 +360,59 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, const W
   return PANN_OK;
 }
 
+// ---- the exhaustive twin (pann_scan_rerank*, DESIGN.md "Exhaustive quantised scan"): step 2 is dense_scan_dev over ALL rows of
+// quant -- the r.c best by the quantised (dist, id) --, step 3 rerank_list_kernel on that list.  No graph, no starts, no status.
+int scan_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace& rr_ws, Workspace& scan_ws, const ScanRerankCall& r) {
+  const uint64_t nq = r.nq;
+  hipStream_t st = (hipStream_t)r.stream;
+  if (nq == 0) return PANN_OK;
+  const uint32_t d = full.d, c = r.c;
+  // the scratch: quantised rows, normalised rows, and whatever of the candidate list the caller does not take
+  uint8_t* qb; uint8_t* nr = nullptr; uint32_t* cand = r.out_cand_ids; float* cdist; uint32_t* count = r.out_cand_count;
+  const uint64_t qb_stride = (quant.dbytes + 15) / 16 * 16, nr_stride = ((uint64_t)d * 4 + 15) / 16 * 16;
+  if (int rc = carve_into(rr_ws, 256, [&](Carve& cv) {
+    qb = cv.take<uint8_t>(nq * qb_stride);
+    if (r.normalize_first) nr = cv.take<uint8_t>(nq * nr_stride);
+    cdist = cv.take<float>(nq * (size_t)c);
+    if (!r.out_cand_ids) cand = cv.take<uint32_t>(nq * (size_t)c);
+    if (!r.out_cand_count) count = cv.take<uint32_t>(nq);
+  })) return rc;
+
+  // ---- 1. the queries ----
+  const size_t prep_lds = r.normalize_first ? (size_t)d * 4 : 0;
+  hipLaunchKernelGGL(prepare_queries_kernel, dim3((uint32_t)std::min<uint64_t>(nq, PREP_MAX_BLOCKS)), dim3(PANN_WAVE), prep_lds, st,
+                     reinterpret_cast<const uint8_t*>(r.queries), r.qstride, nq, d, r.normalize_first ? 1 : 0, make_qparams(r.qparams), qb,
+                     qb_stride, nr, nr_stride, -1, 0.0f, (uint8_t*)nullptr, (uint64_t)0, 0u);
+  PANN_HIP(hipGetLastError());
+
+  // ---- 2. the scan: every list holds exactly c = min(k * rerank_factor, 64, n) ids ----
+  DenseTopkCall s;
+  s.a_ext = qb; s.a_stride = qb_stride; s.ntiles = (uint32_t)((nq + 63) / 64); s.na = nq; s.nb = quant.n; s.nsplit = r.nsplit; s.m = c;
+  s.out_ids = cand; s.out_dists = cdist;
+  if (int rc = dense_scan_dev(quant, scan_ws, st, s)) return rc;
+  if (int rc = knn_pad_dev(nullptr, nullptr, count, nq, c, c, 0, st)) return rc;
+
+  // ---- 3. rerank of the list on the float rows ----
+  if (r.k > PANN_WAVE) { if (int rc = knn_pad_dev(r.out_ids, r.out_dists, nullptr, nq, r.k, 0, 1, st)) return rc; }   // (a wave writes 64 slots of a row)
+  RerankArgs R{};
+  R.pv = PointsView{full.points, full.pstride, full.nch, full.exact}; R.dbytes = full.dbytes;
+  R.q = r.normalize_first ? nr : reinterpret_cast<const uint8_t*>(r.queries);
+  R.q_stride = r.normalize_first ? nr_stride : r.qstride;
+  R.fids = cand; R.beam = c; R.fsize = count; R.nq = nq; R.k = r.k; R.want = R.kcap = c;
+  R.qbytes = (uint32_t)query_lds_bytes(full);
+  R.out_ids = r.out_ids; R.out_dists = r.out_dists;
+  const size_t wave_lds = (size_t)R.qbytes + PANN_WAVE * 4;
+  uint32_t waves = RR_WAVES;
+  while (waves > 1 && waves * wave_lds > 64 * 1024) waves >>= 1;
+  const size_t lds = waves * wave_lds;
+  if (lds > 64 * 1024) { set_error("pann_scan_rerank: rows too long for the rerank's LDS state"); return PANN_ERR_UNSUPPORTED; }
+#define CALL_RL(DT, MT, L, N1)                                                                                                    \
+  hipLaunchKernelGGL((rerank_list_kernel<MT, L, N1>), dim3((uint32_t)((nq + waves - 1) / waves)), dim3(waves * PANN_WAVE), lds, st, R)
+  if (full.metric == PANN_L2) PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_L2, CALL_RL);
+  else PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_MIPS, CALL_RL);
+#undef CALL_RL
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
 }  // namespace pann

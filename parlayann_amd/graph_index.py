@@ -202,14 +202,26 @@ class GraphIndex:
         return ids, dists
 
     def batch_search(self, queries, knn, beam_width, quant=False, visit_limit=-1, allow=None, exact_below=None, where=None,
-                     exact_grouped=False, steer=None, entry=None):
+                     exact_grouped=False, steer=None, entry=None, exhaustive=False):
         """allow: an allow bitmap or boolean mask (DeviceIndex.batch_search_masked): only allowed points are returned.
         where = (kind, preds): the same by a label predicate (DeviceIndex.batch_search_labeled); not together with allow.
         exact_below, exact_grouped (with allow or where): as batch_search_masked
         steer (with allow or where, quant=False): the steered walk, DeviceIndex.batch_search_masked(steer=); None changes nothing
         entry (with where, quant=False, no exact_below): "medoid" starts every query at the medoid of what its predicate allows
         (DESIGN.md "Entry points") -- the distinct predicates (np.unique), DeviceIndex.filter_medoids(per_filter=1, fill_id=0),
-        DeviceIndex.batch_search_grouped with those start rows, steer forwarded; None changes nothing"""
+        DeviceIndex.batch_search_grouped with those start rows, steer forwarded; None changes nothing
+        exhaustive (with quant=True on float points, quant_bits 8 or 4; not with allow= / where=): the batch goes through the
+        exhaustive scan of the quantised copy instead of the walk (DeviceIndex.scan_rerank, DESIGN.md "Exhaustive quantised
+        scan"): the min(knn * 100, 64) nearest rows of the copy, re-scored on the float rows.  beam_width and visit_limit are
+        not read.  The default changes nothing."""
+        if exhaustive:
+            if allow is not None or where is not None or steer is not None or entry is not None:
+                raise ValueError("exhaustive=True has no filtered form: not with allow=, where=, steer= or entry=")
+            if not (quant and self.use_quantization) or self.quant_bits not in (8, 4):
+                raise ValueError("exhaustive=True scans the quantised copy: quant=True on float points, quant_bits 8 or 4")
+            r = self.index.scan_rerank(self.q_index, self.qparams, np.ascontiguousarray(queries, dtype=self.T), k=knn, rerank_factor=100,
+                                       normalize_first=self.metric != "Euclidian")
+            return r["ids"], r["dists"]
         if entry is not None:
             if entry != "medoid":
                 raise ValueError('entry is None or "medoid"')

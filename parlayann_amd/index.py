@@ -773,6 +773,32 @@ class DeviceIndex:
                                        1 if normalize_first else 0, 1 if use_filter else 0, vp(d_starts_ptr), nstarts, C.byref(qp), *mid,
                                        C.byref(out), *tail, vp(stream_ptr)))
 
+    # ---- exhaustive quantised scan + exact rerank in one call (DESIGN.md "Exhaustive quantised scan") ----
+    def scan_rerank(self, quant, qparams, queries, k=10, rerank_factor=100, normalize_first=False, candidates=False):
+        """pann_scan_rerank on this (float32) index, the exhaustive twin of search_rerank: `queries` (float32 rows) are quantised
+        with `qparams` on the device, EVERY row of `quant` (a u8 / i8 / u4 / i4 DeviceIndex of quantized()) is scored on the int8
+        matrix cores, the c = min(k * rerank_factor, 64, n) nearest by the quantised (dist, id) are re-scored here, sorted, and k
+        kept (k > c: the rest of a row is 0xFFFFFFFF / +inf).  No graph is read.  Returns a dict of numpy arrays: ids, dists
+        (nq x k); with candidates=True also cand_ids (nq x c, the exact c nearest rows of the copy, in order) and cand_count."""
+        q = self._queries(queries)
+        nq = len(q)
+        c = max(min(k * rerank_factor, 64, quant.n), 0)
+        res = {"ids": np.empty((nq, k), np.uint32), "dists": np.empty((nq, k), np.float32)}
+        if candidates:
+            res["cand_ids"], res["cand_count"] = np.empty((nq, c), np.uint32), np.empty(nq, np.uint32)
+        check(self._lib.pann_scan_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q), 1 if normalize_first else 0,
+                                         k, rerank_factor, _ptr(res["ids"]), _ptr(res["dists"]), _ptr(res.get("cand_ids")),
+                                         _ptr(res.get("cand_count"))))
+        return res
+
+    def scan_rerank_dev(self, quant, qparams, d_queries_ptr, nq, q_stride_bytes, d_ids_ptr, d_dists_ptr, k=10, rerank_factor=100,
+                        normalize_first=False, d_cand_ids_ptr=None, d_cand_count_ptr=None, stream_ptr=None):
+        """pann_scan_rerank_dev: the same on raw device addresses (integers), enqueued on `stream_ptr`; nothing is synchronised."""
+        vp = lambda a: C.c_void_p(a or None)
+        check(self._lib.pann_scan_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
+                                             1 if normalize_first else 0, k, rerank_factor, vp(d_ids_ptr), vp(d_dists_ptr),
+                                             vp(d_cand_ids_ptr), vp(d_cand_count_ptr), vp(stream_ptr)))
+
     # ---- robustPrune (vamana/index.h:63-137), batched ----
     def robust_prune_batch(self, owners, cand_ids, cand_offsets, alpha, R, cand_dists=None, add_out_nbrs=True):
         owners = np.ascontiguousarray(owners, dtype=np.uint32)

@@ -18,6 +18,10 @@ call.  Run the tool under `timeout -k 10 <seconds>` so that a hang ends the proc
     python tools/rerank_time.py --bits 4 [--beam 128] # the quantised copy holds four-bit rows (DESIGN.md "Four-bit rows")
     python tools/rerank_time.py --bits f8 [--metric mips]   # ... FP8 (E4M3) rows (DESIGN.md "FP8 rows"); --metric goes with every --bits
     python tools/rerank_time.py --profile-steps 5     # only fused steps, for a kernel trace taken in a run of its own
+    python tools/rerank_time.py --scan [--bits 4] [--no-graph]   # (d) the exhaustive scan, pann_scan_rerank_dev (DESIGN.md "Exhaustive
+                                                      # quantised scan"), beside (c); then three alternating wall-clock runs of the host
+                                                      # entries pann_scan_rerank / pann_bruteforce_knn on the float handle / (--bits 8)
+                                                      # pann_bruteforce_knn(k = 64) on the copy.  --no-graph: no build, (d) and those only
 """
 import argparse
 import ctypes as C
@@ -69,6 +73,8 @@ def main():
                     help="bits per coordinate of the quantised copy; f8: one byte of FP8 E4M3")
     ap.add_argument("--beam", type=int, default=BEAM)
     ap.add_argument("--metric", choices=("Euclidian", "mips"), default="Euclidian", help="mips: normalised rows and queries, the MIPS quantisers")
+    ap.add_argument("--scan", action="store_true", help="also time the exhaustive scan + rerank (pann_scan_rerank*)")
+    ap.add_argument("--no-graph", action="store_true", help="with --scan: build no graph, time the scan and the exact routes only")
     a = ap.parse_args()
     import torch
     n, d, nq, beam, mips = a.n, a.d, a.nq, a.beam, a.metric == "mips"
@@ -83,7 +89,8 @@ def main():
         full = DeviceIndex(X, max_degree=64, metric=a.metric)
         if mips:
             full.normalize()
-        full.vamana_build(64, 128, 1.2, num_passes=1, seed=3)
+        if not (a.scan and a.no_graph):
+            full.vamana_build(64, 128, 1.2, num_passes=1, seed=3)
     with step("quantise", 120):
         quant, qparams = full.quantized({8: "mips_i8" if mips else "euclid_u8", 4: "mips_i4" if mips else "euclid_u4", "f8": "f8"}[a.bits])
         assert not qparams.identity
@@ -147,6 +154,39 @@ def main():
         print(f"  {name:9s} {ms:9.3f} ms (min {lo:.3f}, max {hi:.3f})  QPS {rows[-1]['qps']:10.0f}  recall@10 {rows[-1]['recall10']:.4f}  "
               f"full dists/q {cmps.mean():8.1f}  rerank rows/q {num_check:5.1f}  bytes/q {by:10.0f}", flush=True)
 
+    def scan_step():
+        full.scan_rerank_dev(quant, qparams, t_q.data_ptr(), nq, 4 * d, t_ids.data_ptr(), t_d.data_ptr(), k=K, rerank_factor=RF,
+                             stream_ptr=stream.cuda_stream)
+
+    def scan_report():
+        with step("(d) scan", 300):
+            ms, lo, hi = timed_dev(scan_step, a.steps)
+            rec = recall_at_k(t_ids.cpu().numpy().view(np.uint32), gt, gd, K)
+            rows.append(dict(path="scan", ms=ms, ms_min=lo, ms_max=hi, qps=nq / ms * 1e3, recall10=rec, num_check=float(min(K * RF, 64, n))))
+            print(f"  {'scan':9s} {ms:9.3f} ms (min {lo:.3f}, max {hi:.3f})  QPS {nq / ms * 1e3:10.0f}  recall@10 {rec:.4f}  "
+                  f"rows scanned/q {n}  rerank rows/q {min(K * RF, 64, n)}", flush=True)
+        with step("host entries, three alternating runs", 600):
+            legs = [("scan_rerank", lambda: full.scan_rerank(quant, qparams, Q, K, RF)), ("bruteforce_knn f32", lambda: full.bruteforce_knn(Q, K))]
+            if a.bits == 8:
+                qq = quantize.device_quantize_rows(Q, qparams)
+                legs.append(("bruteforce_knn copy k=64", lambda: quant.bruteforce_knn(qq, 64)))
+            for _, fn in legs:
+                fn()                                   # warm-up: scratch growth
+            wall = {name: [] for name, _ in legs}
+            for _ in range(3):
+                for name, fn in legs:
+                    t = time.perf_counter(); fn(); wall[name].append((time.perf_counter() - t) * 1e3)
+            for name, ts in wall.items():
+                rows.append(dict(path="host " + name, ms_runs=ts))
+                print(f"  host {name:26s} " + "  ".join(f"{t:8.2f}" for t in ts) + " ms", flush=True)
+
+    if a.scan and a.no_graph:
+        scan_report()
+        if a.json:
+            with open(a.json, "w") as f:
+                json.dump(dict(n=n, d=d, nq=nq, k=K, bits=a.bits, rerank_factor=RF, steps=a.steps, rows=rows), f, indent=1)
+        quant.close(); full.close()
+        return
     with step("(a) float search", 300):
         ms = timed_dev(float_step, a.steps)
         report("float", *ms, t_ids.cpu().numpy().view(np.uint32), t_dc.cpu().numpy().view(np.uint32), 4 * d, 0.0)
@@ -162,6 +202,8 @@ def main():
         ids_c = t_ids.cpu().numpy().view(np.uint32)
         nc = np.minimum(t_fs.cpu().numpy().view(np.uint32), K * RF)
         report("fused", *ms, ids_c, t_dc.cpu().numpy().view(np.uint32), qrow, nc.mean())
+    if a.scan:
+        scan_report()
     if not np.array_equal(ids_b, ids_c):
         print("ERROR: the fused ids differ from the composed ids", flush=True)
         sys.exit(1)
