@@ -912,6 +912,49 @@ int pann_bruteforce_knn_masked_grouped_dev(pann_index* idx, const void* d_querie
                                            const uint32_t* d_row_of_query, uint64_t max_list_ids, uint32_t* d_out_ids,
                                            float* d_out_dists, uint32_t* d_out_counts, void* stream);
 
+/* ---- filtered exhaustive scan (DESIGN.md "Filtered exhaustive scan") ----  pann_scan_rerank under a point filter: the scan's
+ * arithmetic over the allowed rows alone, then the exact rerank.  For query q let A_q be the points its filter allows and
+ * c_q = min(k * rerank_factor, 64, |A_q|):
+ *   1. the queries are quantised exactly as by pann_scan_rerank (normalize_first included);
+ *   2. the candidate list of q is the c_q rows of A_q with the smallest (float32 of the exact int32 quantised distance, id), in
+ *      that order: out_cand_ids (optional, nq x c, c = min(k * rerank_factor, 64, n)), slots past c_q 0xFFFFFFFF;
+ *      out_cand_count[q] (optional) = c_q;
+ *   3. those c_q ids are re-scored on `full` with the arithmetic of pann_rerank (resort = 1); min(k, c_q) results are written, the
+ *      rest of the row holds 0xFFFFFFFF / +inf.
+ * An empty A_q is an answer (count 0, padding); a filter that allows nothing anywhere launches no distance kernel.  With a filter
+ * that allows every point every output equals pann_scan_rerank's, and for any filter out_ids / out_dists equal pann_rerank on
+ * `full` with the returned candidates and counts, bit for bit.
+ * The filter is ONE bitmap (row_of_query == NULL, which requires nrows == 1; allow_stride_words is not read) or ONE predicate
+ * (group_of_query == NULL, which requires npreds == 1) for the batch, or a TABLE of nrows bitmap rows (allow_stride_words >=
+ * ceil(n / 32) apart) / npreds predicates of one kind, of which query q uses entry row_of_query[q] / group_of_query[q]: the
+ * queries are sorted by entry and every used entry's id list is scanned once for all its queries, as by
+ * pann_bruteforce_knn_masked_grouped (max_list_ids: as there; results do not depend on it).  There is no per-query-rows form: a
+ * caller with one filter per query passes a table of nq entries, which is correct but slow (one list per query).  Labels are
+ * read from `full` (pann_index_set_labels); quant needs none.  Scratch is quant's: one call per handle at a time.
+ * Status: everything pann_scan_rerank refuses, with its codes; and as the grouped exact routes: NULL bitmap, a table stride
+ * below ceil(n / 32), no labels on `full`, an unknown kind, NULL or (device) misaligned predicates, an empty table, an entry
+ * count other than 1 without an index array, a table index >= the entry count -> PANN_ERR_BAD_ARG (host entries find a bad index
+ * before anything is staged, _dev entries after their synchronisation).  nq == 0 -> PANN_OK.  Nothing is written on an error.
+ * The _dev entries synchronise `stream` ONCE (the allowed counts size the launches) and may grow quant's scratch. */
+int pann_scan_rerank_masked_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
+                                uint64_t nq, uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor,
+                                const uint32_t* d_allow, uint64_t nrows, uint64_t allow_stride_words, const uint32_t* d_row_of_query,
+                                uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_cand_ids,
+                                uint32_t* d_out_cand_count, void* stream);
+int pann_scan_rerank_masked(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                            uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const uint32_t* allow,
+                            uint64_t nrows, uint64_t allow_stride_words, const uint32_t* row_of_query, uint64_t max_list_ids,
+                            uint32_t* out_ids, float* out_dists, uint32_t* out_cand_ids, uint32_t* out_cand_count);
+int pann_scan_rerank_labeled_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
+                                 uint64_t nq, uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
+                                 const pann_label_pred* d_preds, uint64_t npreds, const uint32_t* d_group_of_query,
+                                 uint64_t max_list_ids, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_cand_ids,
+                                 uint32_t* d_out_cand_count, void* stream);
+int pann_scan_rerank_labeled(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                             uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
+                             const pann_label_pred* preds, uint64_t npreds, const uint32_t* group_of_query, uint64_t max_list_ids,
+                             uint32_t* out_ids, float* out_dists, uint32_t* out_cand_ids, uint32_t* out_cand_count);
+
 /* ---- entry points: the medoids of a table of filters, on the device (DESIGN.md "Entry points") ----  This project's own.
  * Where a filtered search starts: for every filter of a table the points nearest to the centroid of what it allows, so that a
  * tenant's queries begin in the tenant's region (the per-label entry points of FilteredDiskANN), and a dynamic index gets a live

@@ -1456,9 +1456,22 @@ static int filtered_knn_checks(const pann_index* idx, const char* fn, const void
   return F.is_table() ? table_checks(idx, fn, F) : PANN_OK;
 }
 
+// The filtered exhaustive scan (pann_scan_rerank_masked / _labeled, DESIGN.md "Filtered exhaustive scan") runs the three routes below
+// on the QUANTISED handle: idx is the copy, d_q its prepared query rows, k the candidate list's length, and the lists go through the
+// list form of the int8 scan instead of the exact kernels.  ids: list entries scanned by the call, all chunks.
+struct ScanLists { uint64_t ids = 0; };
+// the dense launch of a route on its lists, with its choice of pieces; piece_rows: the longest list.  A gt_pieces option is taken as
+// it stands by the scan (its lists are short: the clamp of choose_gt_pieces to 4096 rows per piece would make the option void)
+static int dense_lists_dev(pann_index* idx, ScanLists* scan, hipStream_t st, DenseTopkCall& c, uint64_t piece_rows) {
+  if (!scan) { c.nsplit = choose_gt_pieces(idx, c.ntiles, 256.0, piece_rows); return dense_topk_dev(idx->ix, idx->ws2, st, c); }
+  c.nsplit = idx->gt_pieces ? std::min<uint32_t>(idx->gt_pieces, 64) : choose_gt_pieces(idx, c.ntiles, (double)dense_scan_slots(idx->ix, c.m, true), piece_rows);
+  scan->ids += c.nb;
+  return dense_scan_dev(idx->ix, idx->ws2, st, c);
+}
+
 // The routes, on device pointers.  One bitmap: its id list, then the dense kernels on the list.  SYNCHRONISES st (the count sizes the launch).
 static int masked_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, const uint32_t* d_allow,
-                          uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+                          uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st, ScanLists* scan = nullptr) {
   const DeviceIndex& ix = idx->ix;
   if (int rc = idx->ws3.ensure(allow_compact_scratch_bytes(ix.n))) return rc;
   const uint32_t* d_total = nullptr;
@@ -1473,19 +1486,19 @@ static int masked_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint
   // the list as B rows makes the launch one of the LDS-list kernels: one workgroup per CU
   DenseTopkCall c;
   c.a_ext = d_q; c.a_stride = q_stride_bytes; c.b_ids = d_list; c.ntiles = (uint32_t)((nq + 63) / 64); c.na = nq; c.nb = count;
-  c.nsplit = choose_gt_pieces(idx, c.ntiles, 256.0, count); c.m = k; c.out_ids = d_ids; c.out_dists = d_dists;
-  if (int rc = dense_topk_dev(ix, idx->ws2, st, c)) return rc;
+  c.m = k; c.out_ids = d_ids; c.out_dists = d_dists;
+  if (int rc = dense_lists_dev(idx, scan, st, c, count)) return rc;
   return knn_pad_dev(nullptr, nullptr, d_counts, nq, k, std::min(count, k), 0, st);
 }
 
 // One predicate for the batch: its bitmap row is expanded into the handle's scratch and the route above runs on it
 static int labeled_knn_run(pann_index* idx, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k, const PointFilter& F,
-                           uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st) {
+                           uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st, ScanLists* scan = nullptr) {
   const DeviceIndex& ix = idx->ix;
   const uint64_t words = PointFilter::row_words(ix.n);
   if (int rc = idx->label_row.ensure((size_t)words * 4)) return rc;
   if (int rc = labels_to_allow_dev(F.labels, ix.n, F.kind, F.preds, 1, idx->label_row.as<uint32_t>(), words, st)) return rc;
-  return masked_knn_run(idx, d_q, nq, q_stride_bytes, k, idx->label_row.as<uint32_t>(), d_ids, d_dists, d_counts, st);
+  return masked_knn_run(idx, d_q, nq, q_stride_bytes, k, idx->label_row.as<uint32_t>(), d_ids, d_dists, d_counts, st, scan);
 }
 
 // ---- exact kNN by predicate group (masked_knn.hip, DESIGN.md "Exact kNN by predicate group") ----
@@ -1499,7 +1512,7 @@ struct CentroidReq { float* d_centroids; };
 // cen != null: nq == T.count, d_q and T.group are not read -- query g belongs to entry g and is that entry's centroid.
 static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, uint64_t nq, uint64_t q_stride_bytes, uint32_t k,
                            const PointFilter& T, uint64_t max_list_ids, uint32_t* d_ids, float* d_dists, uint32_t* d_counts, hipStream_t st,
-                           const CentroidReq* cen = nullptr) {
+                           const CentroidReq* cen = nullptr, ScanLists* scan = nullptr) {
   const DeviceIndex& ix = idx->ix;
   const uint64_t G = T.count, words = PointFilter::row_words(ix.n), stride = T.stride ? T.stride : words;
   const bool lab = T.mode == MASK_LABELS;
@@ -1576,9 +1589,10 @@ static int grouped_knn_run(pann_index* idx, const char* fn, const uint8_t* d_q, 
     call.a_ext = d_slab; call.a_stride = a_stride; call.b_ids = d_list;
     call.a_off = (const uint64_t*)(dp + c.o_aoff); call.b_off = (const uint64_t*)(dp + c.o_boff);
     call.tile_seg = (const uint32_t*)(dp + c.o_tseg); call.tile_a0 = (const uint32_t*)(dp + c.o_ta0);
-    call.ntiles = c.ntiles; call.na = c.na; call.nb = c.ids; call.nsplit = choose_gt_pieces(idx, c.ntiles, 256.0, c.max_ids); call.m = k;
+    call.ntiles = c.ntiles; call.na = c.na; call.nb = c.ids; call.m = k;
     call.out_ids = d_sids; call.out_dists = d_sdists;
-    if (int rc = dense_topk_dev(ix, idx->ws2, st, call)) return rc;
+    if (scan && !c.ids) { if (int rc = knn_pad_dev(d_sids, d_sdists, nullptr, c.na, k, 0, 1, st)) return rc; }      // nothing allowed: no distance kernel
+    else if (int rc = dense_lists_dev(idx, scan, st, call, c.max_ids)) return rc;
     if (int rc = scatter_knn_rows_dev(d_sids, d_sdists, d_perm + c.a_base, c.na, k, d_ids, d_dists, d_counts, st)) return rc;
   }
   return PANN_OK;
@@ -2926,6 +2940,83 @@ int scan_rerank_launch(pann_index* full, pann_index* quant, ScanRerankCall r, in
   return scan_rerank_dev(full->ix, quant->ix, quant->ws_rr, quant->ws2, r);
 }
 
+// ---- the filtered forms (DESIGN.md "Filtered exhaustive scan"): one bitmap, one predicate, or a table of either ----
+
+// the filter of a masked / labeled scan call in the caller's words: no index array means ONE filter for the batch
+int scan_filter_of(const char* fn, PointFilter one, uint64_t entries, const uint32_t* index_of_query, PointFilter* F) {
+  if (index_of_query) { *F = one.as_table(index_of_query, entries); return PANN_OK; }
+  if (entries != 1) { set_error(std::string(fn) + ": without an index array there is one filter for the batch (a table of 1)"); return PANN_ERR_BAD_ARG; }
+  *F = one;
+  return PANN_OK;
+}
+
+// what the plain scan refuses, then (nq != 0) what the grouped exact routes refuse about the filter and its table; labels are full's
+int scan_filtered_checks(const char* fn, const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                         uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int rerank_factor, const PointFilter& F, const uint32_t* out_ids,
+                         const float* out_dists) {
+  if (int rc = scan_rerank_checks(fn, full, quant, qparams, queries, nq, q_stride_bytes, k, rerank_factor, out_ids, out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  if (int rc = filter_checks(full, fn, F, nq)) return rc;
+  return F.is_table() ? table_checks(full, fn, F) : PANN_OK;
+}
+
+// r: the request on device pointers, F: the filter on the device.  Step 2 is the filter's exact-kNN route run on quant with the list scan.
+int scan_filtered_launch(const char* fn, pann_index* full, pann_index* quant, ScanRerankCall r, int rerank_factor, const PointFilter& F,
+                         uint64_t max_list_ids) {
+  r.c = scan_list_length(quant, r.k, rerank_factor);
+  hipStream_t st = (hipStream_t)r.stream;
+  const uint64_t nq = r.nq; const uint32_t c = r.c;
+  r.lists = [&, nq, c, st](const uint8_t* qb, uint64_t qb_stride, uint32_t* cand, float* cdist, uint32_t* count, bool* none) -> int {
+    ScanLists sl;
+    const int rc = F.is_table()             ? grouped_knn_run(quant, fn, qb, nq, qb_stride, c, F, max_list_ids, cand, cdist, count, st, nullptr, &sl)
+                   : F.mode == MASK_LABELS ? labeled_knn_run(quant, qb, nq, qb_stride, c, F, cand, cdist, count, st, &sl)
+                                           : masked_knn_run(quant, qb, nq, qb_stride, c, F.allow, cand, cdist, count, st, &sl);
+    *none = sl.ids == 0;
+    return rc;
+  };
+  return scan_rerank_dev(full->ix, quant->ix, quant->ws_rr, quant->ws2, r);
+}
+
+int scan_filtered_dev(const char* fn, pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                      uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const PointFilter& F, uint64_t max_list_ids,
+                      uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream) {
+  if (int rc = scan_filtered_checks(fn, full, quant, qparams, d_queries, nq, q_stride_bytes, k, rerank_factor, F, d_out_ids, d_out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)d_queries % 4 != 0) { set_error(std::string(fn) + ": query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  ScanRerankCall r;
+  r.qparams = qparams; r.queries = d_queries; r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first; r.k = k;
+  r.out_ids = d_out_ids; r.out_dists = d_out_dists; r.out_cand_ids = d_out_cand_ids; r.out_cand_count = d_out_cand_count; r.stream = stream;
+  return scan_filtered_launch(fn, full, quant, r, rerank_factor, F, max_list_ids);
+}
+
+int scan_filtered_host(const char* fn, pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                       uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const PointFilter& F, uint64_t max_list_ids,
+                       uint32_t* out_ids, float* out_dists, uint32_t* out_cand_ids, uint32_t* out_cand_count) {
+  if (int rc = scan_filtered_checks(fn, full, quant, qparams, queries, nq, q_stride_bytes, k, rerank_factor, F, out_ids, out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  for (uint64_t q = 0; F.is_table() && q < nq; q++)      // on the host, before anything is staged (filtered_knn_host)
+    if (F.group[q] >= F.count) {
+      set_error(std::string(fn) + ": table index " + std::to_string(F.group[q]) + " of query " + std::to_string(q) + " is out of range (>= " + std::to_string(F.count) + ")");
+      return PANN_ERR_BAD_ARG;
+    }
+  DeviceGuard g(quant->device);
+  const uint32_t c = scan_list_length(quant, k, rerank_factor);
+  HostTrip t(quant);
+  const StagedFilter staged(t, &F, quant->ix.n, nq);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * quant->ix.d);
+  const int o_cnt = t.out.add(out_cand_count, nq * 4);      // (the small pieces first: HostTrip)
+  const int o_ids = t.out.add(out_ids, nq * k * 4), o_dists = t.out.add(out_dists, nq * k * 4);
+  const int o_cand = t.out.add(out_cand_ids, nq * c * 4);
+  if (int rc = t.begin()) return rc;
+  ScanRerankCall r;
+  r.qparams = qparams; r.queries = (const float*)t.din<uint8_t>(i_q); r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first; r.k = k;
+  r.out_ids = t.dout<uint32_t>(o_ids); r.out_dists = t.dout<float>(o_dists);
+  r.out_cand_ids = t.dout<uint32_t>(o_cand); r.out_cand_count = t.dout<uint32_t>(o_cnt); r.stream = t.st;
+  if (int rc = scan_filtered_launch(fn, full, quant, r, rerank_factor, staged.on_device(t), max_list_ids)) return rc;
+  return t.finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -2963,6 +3054,50 @@ int pann_scan_rerank(pann_index* full, pann_index* quant, const pann_quant_param
   r.out_cand_ids = t.dout<uint32_t>(o_cand); r.out_cand_count = t.dout<uint32_t>(o_cnt); r.stream = t.st;
   if (int rc = scan_rerank_launch(full, quant, r, rerank_factor)) return rc;
   return t.finish();
+}
+
+int pann_scan_rerank_masked_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                                uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const uint32_t* d_allow,
+                                uint64_t nrows, uint64_t allow_stride_words, const uint32_t* d_row_of_query, uint64_t max_list_ids,
+                                uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream) {
+  const char* fn = "pann_scan_rerank_masked_dev";
+  PointFilter F;
+  if (int rc = scan_filter_of(fn, PointFilter::bitmap(d_allow, d_row_of_query ? allow_stride_words : 0, nq, true), nrows, d_row_of_query, &F)) return rc;
+  return scan_filtered_dev(fn, full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, k, rerank_factor, F, max_list_ids, d_out_ids,
+                           d_out_dists, d_out_cand_ids, d_out_cand_count, stream);
+}
+
+int pann_scan_rerank_masked(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                            uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const uint32_t* allow, uint64_t nrows,
+                            uint64_t allow_stride_words, const uint32_t* row_of_query, uint64_t max_list_ids, uint32_t* out_ids,
+                            float* out_dists, uint32_t* out_cand_ids, uint32_t* out_cand_count) {
+  const char* fn = "pann_scan_rerank_masked";
+  PointFilter F;
+  if (int rc = scan_filter_of(fn, PointFilter::bitmap(allow, row_of_query ? allow_stride_words : 0, nq, false), nrows, row_of_query, &F)) return rc;
+  return scan_filtered_host(fn, full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, k, rerank_factor, F, max_list_ids, out_ids,
+                            out_dists, out_cand_ids, out_cand_count);
+}
+
+int pann_scan_rerank_labeled_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                                 uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
+                                 const pann_label_pred* d_preds, uint64_t npreds, const uint32_t* d_group_of_query, uint64_t max_list_ids,
+                                 uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream) {
+  const char* fn = "pann_scan_rerank_labeled_dev";
+  PointFilter F;
+  if (int rc = scan_filter_of(fn, label_filter(full, kind, d_preds, 1, true), npreds, d_group_of_query, &F)) return rc;
+  return scan_filtered_dev(fn, full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, k, rerank_factor, F, max_list_ids, d_out_ids,
+                           d_out_dists, d_out_cand_ids, d_out_cand_count, stream);
+}
+
+int pann_scan_rerank_labeled(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                             uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind, const pann_label_pred* preds,
+                             uint64_t npreds, const uint32_t* group_of_query, uint64_t max_list_ids, uint32_t* out_ids, float* out_dists,
+                             uint32_t* out_cand_ids, uint32_t* out_cand_count) {
+  const char* fn = "pann_scan_rerank_labeled";
+  PointFilter F;
+  if (int rc = scan_filter_of(fn, label_filter(full, kind, preds, 1, false), npreds, group_of_query, &F)) return rc;
+  return scan_filtered_host(fn, full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, k, rerank_factor, F, max_list_ids, out_ids,
+                            out_dists, out_cand_ids, out_cand_count);
 }
 
 }  // extern "C"

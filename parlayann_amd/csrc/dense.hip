@@ -1323,128 +1323,45 @@ __global__ void __launch_bounds__(256) scan_norms_kernel(const uint8_t* points, 
   ss = group_sum<16>(ss) + scan_pad_sq<DT>(nch);
   if (row < n && c == 0) out[row] = ss;
 }
+// list form: position p of the id list holds |row b_ids[p]|^2 -- only the rows of the lists are read
+template <int DT>
+__global__ void __launch_bounds__(256) scan_norms_list_kernel(const uint8_t* points, uint32_t pstride, uint32_t nch, const uint32_t* __restrict__ b_ids,
+                                                              uint64_t nb, int* out) {
+  const uint64_t p = (uint64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
+  const uint32_t c = threadIdx.x & 15;
+  int ss = 0;
+  if (p < nb) {
+    const uint8_t* rp = points + (uint64_t)b_ids[p] * pstride;
+    for (uint32_t j = c; j < nch; j += 16) ss += scan_chunk_sq<DT>(*reinterpret_cast<const uint4*>(rp + j * 16));
+  }
+  ss = group_sum<16>(ss) + scan_pad_sq<DT>(nch);
+  if (p < nb && c == 0) out[p] = ss;
+}
 // (the shared thresholds start at "none"; a kernel, so that the scan can be recorded into a graph)
 __global__ void __launch_bounds__(256) scan_fill_kernel(uint32_t* p, uint64_t n, uint32_t v) {
   for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) p[i] = v;
 }
 
+// LIST: the B side is a gathered, segmented id list (DESIGN.md "Filtered exhaustive scan").  The geometry is dense_geom's: tile
+// blockIdx.x belongs to segment tile_seg[], its B rows are the list positions [b_off[seg], b_off[seg + 1]) of b_ids, cut into nsplit
+// pieces; bnorm is indexed by list position, gtau and partial by the global A row as in the plain form.  Position p is row b_ids[p]:
+// a row's address hangs on a loaded id, and the rows are requested two steps ahead, so a lane's four row ids (positions bt + r0 +
+// 16 k, clamped to the piece's last position -- positions are clamped, never ids) are requested THREE steps ahead and wait one step
+// in registers (nid0..3).  With two 256-byte segments per tile both units of a tile ask for the same positions.  The id of the
+// (norm, id) pair of Bm is b_ids[bt + lane], a contiguous load beside the norm's.
+// The body of both forms is dense_scan_body.h, read twice with LIST a constant.  The list form is an OVERLOAD with a third template
+// parameter, so that the plain instances keep their symbol names, and the body is text, not a function they would both call, so that
+// they keep their code: through a shared __forceinline__ function every plain instance came out a few instructions and up to 8
+// VGPRs different (tools/compare_kernels.py).
 template <int DT, int NR>
 __global__ void __launch_bounds__(256, 2) dense_scan_mfma_kernel(DenseArgs A, const int* __restrict__ bnorm, uint32_t* gtau) {
-  constexpr bool L2 = scan_is_l2(DT);
-  extern __shared__ __align__(16) uint8_t smem[];
-  const uint32_t nch = (A.dbytes + 15) / 16;                              // 16-byte chunks that hold data: 1 .. 32 (the launcher checks)
-  const uint32_t nseg = (nch + 15) / 16;
-  uint8_t* Bt0 = smem;                                                    // [2][64][GT_BSTRIDE], slots swizzled (gt_swz)
-  float2* Bm = reinterpret_cast<float2*>(smem + 2 * GT_BT_BYTES);         // [2][64] (|b|^2 bits, id bits)
-  int* An = reinterpret_cast<int*>(Bm + 2 * DT_B);                        // [64] |a|^2 (L2)
-  uint8_t* At = reinterpret_cast<uint8_t*>(An + DT_A);                    // [nseg][64][GT_BSTRIDE], swizzled like B
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4;
-  const TileGeom g = tile_geom(A.na, A.nb, piece_rows(A.nb, A.nsplit, DT_B));
-  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
-  const uint32_t ntile = (uint32_t)((be - bs + DT_B - 1) / DT_B);
-  const int r0 = tid >> 4, c = tid & 15;
-  // the A tile -> LDS (rows beyond the tile and bytes beyond the row: zeros), PANN_U8 moved; |a|^2 of the bytes the k steps cover
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    int ss = 0;
-    for (uint32_t sg = 0; sg < nseg; sg++) {
-      uint4 v = dense_a_load(A, g, r0 + 16 * k, sg * DT_SEG + c * 16);
-      if (L2 && sg * 16u + (uint32_t)c < nch) ss += scan_chunk_sq<DT>(v);
-      if constexpr (DT == PANN_U8) v = scan_flip7(v);
-      *reinterpret_cast<uint4*>(At + sg * GT_BT_BYTES + gt_swz((uint32_t)(r0 + 16 * k), (uint32_t)c * 16u)) = v;
-    }
-    if constexpr (L2) { ss = group_sum<16>(ss) + scan_pad_sq<DT>(nch); if (c == 0) An[r0 + 16 * k] = ss; }
-  }
-  GtSel<NR> S;
-  gt_sel_init<NR>(S, A.m, (uint32_t)(wave * DT_AW + q * 4), na_tile, lane);
-  // pipeline step u = (tile u / nseg, segment u % nseg), buffer u & 1 (dense_gt_valu_kernel): with two segments buffer b always
-  // holds segment b.  A chunk column that holds no data is never staged: it is zeroed here, once, in both buffers.
-  const bool cv0 = (uint32_t)c < nch, cv1 = nseg == 2 && 16u + (uint32_t)c < nch;
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    if (!((nseg == 2 && (k >> 2)) ? cv1 : cv0))
-      *reinterpret_cast<uint4*>(Bt0 + (k >> 2) * GT_BT_BYTES + gt_swz((uint32_t)(r0 + 16 * (k & 3)), (uint32_t)c * 16u)) = make_uint4(0, 0, 0, 0);
-  }
-  __syncthreads();
-  int an[4] = {0, 0, 0, 0};
-  if constexpr (L2) {
-#pragma unroll
-    for (int r = 0; r < 4; r++) an[r] = An[wave * DT_AW + q * 4 + r];
-  }
-  const uint32_t pplace = 16u * NR - A.m + (A.m + A.nsplit - 1) / A.nsplit - 1;
-  const uint32_t skip[4] = {SENTINEL, SENTINEL, SENTINEL, SENTINEL};
-  const uint32_t tau_period = GT_TAU_PERIOD * ((A.nsplit + 7) / 8);
-  uint32_t tau_wait = tau_period;
-  uint32_t* gtau_mine = gtau + (a0 + wave * DT_AW + q * 4) * A.nsplit + blockIdx.y;
-
-  const uint32_t nunits = ntile * nseg;
-  const uint32_t last_row = (uint32_t)(be - 1);                           // (read only where a load is issued: be > bs there)
-  const uint8_t* cb0 = A.points + min((uint32_t)c, nch - 1u) * 16u;
-  const uint8_t* cb1 = A.points + min(16u + (uint32_t)c, nch - 1u) * 16u;
-  uint4 pre0, pre1, pre2, pre3;
-  int pn = 0;
-  auto unit_bt = [&](uint32_t u) -> uint32_t { return (uint32_t)bs + (nseg == 2 ? (u >> 1) : u) * DT_B; };
-  auto load_pre = [&](uint32_t u) {          // requests only: clamped rows, no branch around a load
-    const uint32_t bt = unit_bt(u);
-    const uint8_t* cb = (nseg == 2 && (u & 1)) ? cb1 : cb0;
-    pre0 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0, last_row) * A.pstride);
-    pre1 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 16u, last_row) * A.pstride);
-    pre2 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 32u, last_row) * A.pstride);
-    pre3 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 48u, last_row) * A.pstride);
-    if (L2) pn = bnorm[min(bt + (uint32_t)lane, last_row)];
-  };
-  auto store_pre = [&](uint32_t u) {
-    const int buf = (int)(u & 1);
-    gt_store_tile(Bt0 + buf * GT_BT_BYTES, Bm + buf * DT_B, (nseg == 2 && (u & 1)) ? cv1 : cv0, pre0, pre1, pre2, pre3, __int_as_float(pn),
-                  unit_bt(u), be, tid);
-  };
-  if (nunits > 0) {
-    load_pre(0); store_pre(0);
-    load_pre(1);
-  }
-  lds_barrier();
-
-  mf_int4 acc[4];
-  const uint32_t arow = (uint32_t)(wave * DT_AW + (lane & 15));
-  for (uint32_t u = 0; u < nunits; u++) {
-    const int buf = (int)(u & 1);
-    const uint32_t sg = nseg == 2 ? (u & 1) : 0u;
-    if (sg == 0 && A.nsplit > 1 && --tau_wait == 0) { tau_wait = tau_period; gt_sel_refresh<NR>(S, gtau + a0 * A.nsplit, (uint32_t)(wave * DT_AW + q * 4), na_tile, A.nsplit, lane); }
-    store_pre(u + 1);                                          // (beyond the last step: the piece's last row again, into a dead buffer)
-    load_pre(u + 2);
-    if (sg == 0) {
-#pragma unroll
-      for (int t = 0; t < 4; t++) acc[t] = mf_int4{0, 0, 0, 0};
-    }
-    const uint8_t* Bt = Bt0 + buf * GT_BT_BYTES;
-    const uint8_t* Ap = At + sg * GT_BT_BYTES;
-    const uint32_t nks = (min(16u, nch - sg * 16u) + 3u) / 4u;              // k steps of 64 row bytes that reach data in this segment
-    for (uint32_t ks = 0; ks < nks; ks++) {
-      const uint32_t off = ks * 64u + (uint32_t)q * 16u;
-      uint4 braw[4];
-#pragma unroll
-      for (int t = 0; t < 4; t++) braw[t] = *reinterpret_cast<const uint4*>(Bt + gt_swz((uint32_t)(t * 16 + (lane & 15)), off));
-      scan_mfma_step<DT>(*reinterpret_cast<const uint4*>(Ap + gt_swz(arow, off)), braw, acc);
-    }
-    if (sg == nseg - 1) {
-      // ---- epilogue: acc[t][r] = a(row wave*16 + 4q + r) . b(column t*16 + (lane & 15)) ----
-      int bn[4]; uint32_t bid[4];
-#pragma unroll
-      for (int t = 0; t < 4; t++) { const float2 m2 = Bm[buf * DT_B + t * 16 + (lane & 15)]; bn[t] = __float_as_int(m2.x); bid[t] = __float_as_uint(m2.y); }
-      float dist[4][4];
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-          if constexpr (L2) dist[r][t] = (float)(an[r] + bn[t] - 2 * acc[t][r]);
-          else dist[r][t] = -(float)acc[t][r];
-        }
-      }
-      gt_select<NR>(S, dist, bid, skip, pplace, gtau_mine, A.nsplit, lane);
-    }
-    lds_barrier();
-  }
-  gt_sel_write<NR>(S, A.partial + ((a0 + wave * DT_AW + q * 4) * A.nsplit + blockIdx.y) * A.m, A.m, A.nsplit, lane);
+  constexpr bool LIST = false;
+#include "dense_scan_body.h"
+}
+template <int DT, int NR, bool LIST>
+__global__ void __launch_bounds__(256, 2) dense_scan_mfma_kernel(DenseArgs A, const int* __restrict__ bnorm, uint32_t* gtau) {
+  static_assert(LIST, "the plain form is the two-parameter kernel");
+#include "dense_scan_body.h"
 }
 
 // merge the nsplit partial lists of each A row (one wave per row) and write ids / dists
@@ -1582,29 +1499,39 @@ int dense_topk_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
 // ---- the exhaustive quantised scan (dense_scan_mfma_kernel): external quantised rows against all points, m <= 64 ----
 using ScanKernel = void (*)(DenseArgs, const int*, uint32_t*);
 // list registers per row: 1 (m <= 16) or 4 (m <= 64); the four pairings the quantiser produces, or null
-static ScanKernel dense_scan_kernel_of(const DeviceIndex& ix, uint32_t m) {
+template <int DT>
+static ScanKernel dense_scan_kernel_pick(bool one, bool list) {
+  if (list) return one ? dense_scan_mfma_kernel<DT, 1, true> : dense_scan_mfma_kernel<DT, 4, true>;
+  return one ? dense_scan_mfma_kernel<DT, 1> : dense_scan_mfma_kernel<DT, 4>;
+}
+// list: the B side is an id list (c.b_ids), possibly segmented
+static ScanKernel dense_scan_kernel_of(const DeviceIndex& ix, uint32_t m, bool list = false) {
   const bool one = m <= 16;
-  if (ix.dtype == PANN_U8 && ix.metric == PANN_L2) return one ? dense_scan_mfma_kernel<PANN_U8, 1> : dense_scan_mfma_kernel<PANN_U8, 4>;
-  if (ix.dtype == PANN_I8 && ix.metric == PANN_MIPS) return one ? dense_scan_mfma_kernel<PANN_I8, 1> : dense_scan_mfma_kernel<PANN_I8, 4>;
-  if (ix.dtype == PANN_U4 && ix.metric == PANN_L2) return one ? dense_scan_mfma_kernel<PANN_U4, 1> : dense_scan_mfma_kernel<PANN_U4, 4>;
-  if (ix.dtype == PANN_I4 && ix.metric == PANN_MIPS) return one ? dense_scan_mfma_kernel<PANN_I4, 1> : dense_scan_mfma_kernel<PANN_I4, 4>;
+  if (ix.dtype == PANN_U8 && ix.metric == PANN_L2) return dense_scan_kernel_pick<PANN_U8>(one, list);
+  if (ix.dtype == PANN_I8 && ix.metric == PANN_MIPS) return dense_scan_kernel_pick<PANN_I8>(one, list);
+  if (ix.dtype == PANN_U4 && ix.metric == PANN_L2) return dense_scan_kernel_pick<PANN_U4>(one, list);
+  if (ix.dtype == PANN_I4 && ix.metric == PANN_MIPS) return dense_scan_kernel_pick<PANN_I4>(one, list);
   return nullptr;
 }
 bool dense_scan_eligible(const DeviceIndex& ix) { return dense_scan_kernel_of(ix, 1) != nullptr && ix.pstride <= 2 * DT_SEG; }
 static size_t dense_scan_lds(const DeviceIndex& ix) { return GT_LDS_BYTES + (size_t)((ix.dbytes + DT_SEG - 1) / DT_SEG) * GT_BT_BYTES; }
 // workgroups of the scan that are resident at once (for the caller's choice of nsplit)
-uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m) {
-  const void* kern = reinterpret_cast<const void*>(dense_scan_kernel_of(ix, m));
+uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m, bool list) {
+  const void* kern = reinterpret_cast<const void*>(dense_scan_kernel_of(ix, m, list));
   const size_t lds = dense_scan_lds(ix);
   int v = 0;
   (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, lds) != hipSuccess || v < 1) v = 1;
   return 256u * (uint32_t)v;
 }
-// c.a_ext: na rows in ix's own row format, 16-byte aligned, c.a_stride a multiple of 16; c.m <= 64; B = all c.nb points
+// c.a_ext: na rows in ix's own row format, 16-byte aligned, c.a_stride a multiple of 16; c.m <= 64; B = all c.nb points, or (c.b_ids)
+// the c.nb list positions of c.b_ids, in the segments and tiles of c.a_off / c.b_off / c.tile_seg / c.tile_a0 when those are given
 int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c) {
-  const ScanKernel kern = dense_scan_kernel_of(ix, c.m);
+  const bool list = c.b_ids != nullptr;
+  const ScanKernel kern = dense_scan_kernel_of(ix, c.m, list);
   if (!kern || ix.pstride > 2 * DT_SEG || c.m == 0 || c.m > 64) { set_error("quantised scan: unsupported element type, row length or list length"); return PANN_ERR_UNSUPPORTED; }
+  if (!list && (c.a_off || c.b_off || c.tile_seg || c.tile_a0)) { set_error("quantised scan: segments go with an id list"); return PANN_ERR_BAD_ARG; }
+  if (list && c.nb > 0xFFFF0000ull) { set_error("quantised scan: an id list of more than 2^32 - 2^16 entries"); return PANN_ERR_UNSUPPORTED; }      // (positions are 32-bit in the kernel)
   if (c.na == 0) return PANN_OK;
   const uint32_t mcap = (c.m + 15) / 16 * 16, nch = (ix.dbytes + 15) / 16;
   uint64_t* partial; int* d_norm = nullptr; uint32_t* d_gtau;
@@ -1616,10 +1543,14 @@ int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
   DenseArgs A{};
   A.points = ix.points; A.pstride = ix.pstride; A.dbytes = ix.dbytes;
   A.a_ext = c.a_ext; A.a_stride = c.a_stride; A.na = c.na; A.nb = c.nb; A.nsplit = c.nsplit; A.m = c.m; A.mcap = mcap; A.partial = partial;
+  A.b_ids = c.b_ids; A.a_off = c.a_off; A.b_off = c.b_off; A.tile_seg = c.tile_seg; A.tile_a0 = c.tile_a0;
   const uint64_t ngtau = c.na * c.nsplit;
   hipLaunchKernelGGL(scan_fill_kernel, dim3((uint32_t)std::min<uint64_t>((ngtau + 255) / 256, 4096)), dim3(256), 0, st, d_gtau, ngtau, 0xFFFFFFFFu);
   const dim3 ng((uint32_t)((c.nb + 15) / 16));
-  if (ix.dtype == PANN_U8) hipLaunchKernelGGL(scan_norms_kernel<PANN_U8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.nb, d_norm);
+  if (c.nb == 0) {}      // (every list empty: no norms, and the scan below reads none)
+  else if (list && ix.dtype == PANN_U8) hipLaunchKernelGGL(scan_norms_list_kernel<PANN_U8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.b_ids, c.nb, d_norm);
+  else if (list && ix.dtype == PANN_U4) hipLaunchKernelGGL(scan_norms_list_kernel<PANN_U4>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.b_ids, c.nb, d_norm);
+  else if (ix.dtype == PANN_U8) hipLaunchKernelGGL(scan_norms_kernel<PANN_U8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.nb, d_norm);
   else if (ix.dtype == PANN_U4) hipLaunchKernelGGL(scan_norms_kernel<PANN_U4>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.nb, d_norm);
   PANN_HIP(hipGetLastError());
   launch_lds(kern, dim3(c.ntiles, c.nsplit), dim3(256), dense_scan_lds(ix), st, A, (const int*)d_norm, d_gtau);

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include <chrono>
+#include <functional>
 #include <string>
 
 #include "../../include/pann.h"
@@ -189,8 +190,10 @@ int query_distances_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_
 // the exhaustive scan of a quantised copy on the int8 matrix cores (DESIGN.md "Exhaustive quantised scan"): the c.m <= 64 nearest
 // of ALL c.nb points for c.na external rows in the handle's own row format (c.a_ext 16-byte aligned, c.a_stride a multiple of 16),
 // sorted by (float32 of the exact integer distance, id).  PANN_U8 / PANN_U4 with L2, PANN_I8 / PANN_I4 with MIPS, pstride <= 512.
+// List form (c.b_ids, DESIGN.md "Filtered exhaustive scan"): B is the c.nb positions of an id list, one segment or the segments and
+// tiles of dense_topk_dev's segmented form; a list shorter than c.m leaves the rest of its rows 0xFFFFFFFF / +inf.
 bool dense_scan_eligible(const DeviceIndex& ix);
-uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m);      // workgroups resident at once, for the choice of c.nsplit
+uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m, bool list = false);      // workgroups resident at once, for the choice of c.nsplit
 int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c);
 
 int pivot_split_dev(const DeviceIndex& ix, hipStream_t st, const uint32_t* d_ids, const uint32_t* d_tile_seg,
@@ -363,12 +366,16 @@ int search_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, const W
 // pann_scan_rerank* (search_rerank.hip): prepare the queries as above (no sketch), dense_scan_dev over all rows of quant with lists of
 // c = min(k * rerank_factor, 64, n) ids, rerank of the lists on full.  Device pointers; the prepared rows and what the caller does not
 // take of the lists are carved from rr_ws, the scan's partial lists from scan_ws.  k > c: the rest of a row is 0xFFFFFFFF / +inf.
+// Filtered form (pann_scan_rerank_masked / _labeled): `lists` is step 2 -- the route of the filter (api.hip) over the prepared rows, which
+// leaves the padded candidate lists, their distances and count[q] = min(c, points the filter of q allows); *none: nothing is allowed
+// anywhere, the results are padding and no rerank is launched.
 struct ScanRerankCall {
   const pann_quant_params* qparams = nullptr; const float* queries = nullptr; uint64_t nq = 0, qstride = 0; int normalize_first = 0;
   uint32_t k = 0, c = 0, nsplit = 1;
   uint32_t* out_ids = nullptr; float* out_dists = nullptr;                 // nq x k
   uint32_t* out_cand_ids = nullptr, *out_cand_count = nullptr;            // nq x c, nq (optional)
   void* stream = nullptr;
+  std::function<int(const uint8_t* qb, uint64_t qb_stride, uint32_t* cand, float* cdist, uint32_t* count, bool* none)> lists;
 };
 int scan_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace& rr_ws, Workspace& scan_ws, const ScanRerankCall& r);
 

@@ -385,12 +385,18 @@ int scan_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace
                      qb_stride, nr, nr_stride, -1, 0.0f, (uint8_t*)nullptr, (uint64_t)0, 0u);
   PANN_HIP(hipGetLastError());
 
-  // ---- 2. the scan: every list holds exactly c = min(k * rerank_factor, 64, n) ids ----
-  DenseTopkCall s;
-  s.a_ext = qb; s.a_stride = qb_stride; s.ntiles = (uint32_t)((nq + 63) / 64); s.na = nq; s.nb = quant.n; s.nsplit = r.nsplit; s.m = c;
-  s.out_ids = cand; s.out_dists = cdist;
-  if (int rc = dense_scan_dev(quant, scan_ws, st, s)) return rc;
-  if (int rc = knn_pad_dev(nullptr, nullptr, count, nq, c, c, 0, st)) return rc;
+  // ---- 2. the scan: every list holds exactly c = min(k * rerank_factor, 64, n) ids; under a filter, min(c, what it allows) ----
+  if (r.lists) {
+    bool none = false;
+    if (int rc = r.lists(qb, qb_stride, cand, cdist, count, &none)) return rc;
+    if (none) return knn_pad_dev(r.out_ids, r.out_dists, nullptr, nq, r.k, 0, 1, st);
+  } else {
+    DenseTopkCall s;
+    s.a_ext = qb; s.a_stride = qb_stride; s.ntiles = (uint32_t)((nq + 63) / 64); s.na = nq; s.nb = quant.n; s.nsplit = r.nsplit; s.m = c;
+    s.out_ids = cand; s.out_dists = cdist;
+    if (int rc = dense_scan_dev(quant, scan_ws, st, s)) return rc;
+    if (int rc = knn_pad_dev(nullptr, nullptr, count, nq, c, c, 0, st)) return rc;
+  }
 
   // ---- 3. rerank of the list on the float rows ----
   if (r.k > PANN_WAVE) { if (int rc = knn_pad_dev(r.out_ids, r.out_dists, nullptr, nq, r.k, 0, 1, st)) return rc; }   // (a wave writes 64 slots of a row)

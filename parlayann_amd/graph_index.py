@@ -210,10 +210,10 @@ class GraphIndex:
         entry (with where, quant=False, no exact_below): "medoid" starts every query at the medoid of what its predicate allows
         (DESIGN.md "Entry points") -- the distinct predicates (np.unique), DeviceIndex.filter_medoids(per_filter=1, fill_id=0),
         DeviceIndex.batch_search_grouped with those start rows, steer forwarded; None changes nothing
-        exhaustive (with quant=True on float points, quant_bits 8 or 4; not with allow= / where=): the batch goes through the
-        exhaustive scan of the quantised copy instead of the walk (DeviceIndex.scan_rerank, DESIGN.md "Exhaustive quantised
-        scan"): the min(knn * 100, 64) nearest rows of the copy, re-scored on the float rows.  beam_width and visit_limit are
-        not read.  The default changes nothing."""
+        exhaustive (with quant=True on float points, quant_bits 8 or 4; not with allow= / where= here -- the filtered scan is
+        batch_search_masked(quant=True, exhaustive=True)): the batch goes through the exhaustive scan of the quantised copy
+        instead of the walk (DeviceIndex.scan_rerank, DESIGN.md "Exhaustive quantised scan"): the min(knn * 100, 64) nearest
+        rows of the copy, re-scored on the float rows.  beam_width and visit_limit are not read.  The default changes nothing."""
         if exhaustive:
             if allow is not None or where is not None or steer is not None or entry is not None:
                 raise ValueError("exhaustive=True has no filtered form: not with allow=, where=, steer= or entry=")
@@ -255,8 +255,22 @@ class GraphIndex:
                                      rerank_factor=100, allow=allow, where=where, **qp)
         return r["ids"], r["dists"]
 
+    def _scan_masked(self, queries, knn, allow, where):
+        """batch_search_masked(quant=True, exhaustive=True): DeviceIndex.scan_rerank under the filter; per-query rows or predicates
+        become a table of the distinct ones (np.unique), as exact_grouped does"""
+        if not self.use_quantization or self.quant_bits not in (8, 4):
+            raise ValueError("exhaustive=True scans the quantised copy: quant=True on float points, quant_bits 8 or 4")
+        queries = np.ascontiguousarray(queries, dtype=self.T)
+        flt = PointFilter.of(self.index.n, allow, where)
+        kw = flt.kw
+        if not flt.shared:
+            table, group = np.unique(flt.check(len(queries)).rows, axis=0, return_inverse=True)
+            kw = dict(PointFilter(table, flt.kind, False).kw, group_of_query=np.asarray(group).reshape(-1))
+        r = self.index.scan_rerank(self.q_index, self.qparams, queries, k=knn, rerank_factor=100, normalize_first=self.metric != "Euclidian", **kw)
+        return r["ids"], r["dists"]
+
     def batch_search_masked(self, queries, knn, beam_width, allow=None, quant=False, visit_limit=-1, exact_below=None, where=None,
-                            exact_grouped=False):
+                            exact_grouped=False, exhaustive=False):
         """Only allowed points are returned (allow: an allow bitmap or boolean mask, DeviceIndex.batch_search_masked; or
         where = (kind, preds): a label predicate over the labels of set_labels, 8 bytes per query in place of a bitmap row --
         every route below has the same form under it, and exact_below is decided by DeviceIndex.label_count).
@@ -269,9 +283,17 @@ class GraphIndex:
         threshold: the count at which the two routes cost the same depends on the data (tools/masked_time.py --exact).
         exact_grouped: the exact part of per-query rows or predicates is answered by DeviceIndex.bruteforce_knn_grouped, which
         scores the queries of equal filters together (DESIGN.md "Exact kNN by predicate group"): the same rows, faster when many
-        queries share few filters.  The default changes nothing."""
+        queries share few filters.  The default changes nothing.
+        exhaustive (with quant=True on float points, quant_bits 8 or 4; not with exact_below): the filtered exhaustive scan of
+        the quantised copy instead of the walk (DeviceIndex.scan_rerank(allow= / where=), DESIGN.md "Filtered exhaustive
+        scan"): the min(knn * 100, 64) nearest ALLOWED rows of the copy, re-scored on the float rows; per-query rows or
+        predicates are deduplicated into a table here.  beam_width and visit_limit are not read.  The default changes nothing."""
         if where is None and allow is None:
             raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
+        if exhaustive:
+            if not quant or exact_below is not None or (where is not None and allow is not None):
+                raise ValueError("exhaustive=True goes with quant=True, one of allow= / where=, and no exact_below")
+            return self._scan_masked(queries, knn, allow, where)
         return self._exact_or_walk(queries, knn, allow, where, exact_below,
                                    lambda q, allow=None, where=None: self._search_masked(q, knn, beam_width, allow, quant, visit_limit, where),
                                    exact_grouped)

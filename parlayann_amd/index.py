@@ -774,30 +774,59 @@ class DeviceIndex:
                                        C.byref(out), *tail, vp(stream_ptr)))
 
     # ---- exhaustive quantised scan + exact rerank in one call (DESIGN.md "Exhaustive quantised scan") ----
-    def scan_rerank(self, quant, qparams, queries, k=10, rerank_factor=100, normalize_first=False, candidates=False):
+    def scan_rerank(self, quant, qparams, queries, k=10, rerank_factor=100, normalize_first=False, candidates=False, allow=None,
+                    where=None, group_of_query=None, max_list_ids=0):
         """pann_scan_rerank on this (float32) index, the exhaustive twin of search_rerank: `queries` (float32 rows) are quantised
         with `qparams` on the device, EVERY row of `quant` (a u8 / i8 / u4 / i4 DeviceIndex of quantized()) is scored on the int8
         matrix cores, the c = min(k * rerank_factor, 64, n) nearest by the quantised (dist, id) are re-scored here, sorted, and k
         kept (k > c: the rest of a row is 0xFFFFFFFF / +inf).  No graph is read.  Returns a dict of numpy arrays: ids, dists
-        (nq x k); with candidates=True also cand_ids (nq x c, the exact c nearest rows of the copy, in order) and cand_count."""
+        (nq x k); with candidates=True also cand_ids (nq x c, the exact c nearest rows of the copy, in order) and cand_count.
+        allow / where: pann_scan_rerank_masked / _labeled (DESIGN.md "Filtered exhaustive scan") -- only the allowed rows are
+        scored, a query's list holds cand_count[q] = min(c, allowed points) ids, then 0xFFFFFFFF.  One bitmap (boolean (n,) or
+        packed (W,)) or one predicate (kind, (a, b)) serves the batch; rows (G, n) / (G, W) or predicates (kind, preds[G, 2])
+        are a TABLE and need group_of_query (nq, each < G), as bruteforce_knn_grouped (max_list_ids as there).  Labels are this
+        handle's."""
         q = self._queries(queries)
         nq = len(q)
         c = max(min(k * rerank_factor, 64, quant.n), 0)
         res = {"ids": np.empty((nq, k), np.uint32), "dists": np.empty((nq, k), np.float32)}
         if candidates:
             res["cand_ids"], res["cand_count"] = np.empty((nq, c), np.uint32), np.empty(nq, np.uint32)
-        check(self._lib.pann_scan_rerank(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q), 1 if normalize_first else 0,
-                                         k, rerank_factor, _ptr(res["ids"]), _ptr(res["dists"]), _ptr(res.get("cand_ids")),
-                                         _ptr(res.get("cand_count"))))
+        flt = PointFilter.of(self.n, allow, where)
+        name, mid = "pann_scan_rerank", ()
+        if flt is not None:
+            group = None
+            if group_of_query is not None:
+                group = np.ascontiguousarray(np.asarray(group_of_query).reshape(-1), dtype=np.uint32)
+                if group.shape != (nq,):
+                    raise ValueError("group_of_query must hold one table index per query")
+            elif not flt.shared:
+                raise ValueError("a table of filters needs group_of_query, one table index per query")
+            table = PointFilter(np.ascontiguousarray(flt.table(), dtype=np.uint32), flt.kind, False)
+            name, mid = "pann_scan_rerank_" + flt.infix, table.args(table=True) + (_ptr(group), int(max_list_ids))
+        elif group_of_query is not None:
+            raise ValueError("group_of_query goes with allow= or where=")
+        check(getattr(self._lib, name)(self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q), 1 if normalize_first else 0,
+                                       k, rerank_factor, *mid, _ptr(res["ids"]), _ptr(res["dists"]), _ptr(res.get("cand_ids")),
+                                       _ptr(res.get("cand_count"))))
         return res
 
     def scan_rerank_dev(self, quant, qparams, d_queries_ptr, nq, q_stride_bytes, d_ids_ptr, d_dists_ptr, k=10, rerank_factor=100,
-                        normalize_first=False, d_cand_ids_ptr=None, d_cand_count_ptr=None, stream_ptr=None):
-        """pann_scan_rerank_dev: the same on raw device addresses (integers), enqueued on `stream_ptr`; nothing is synchronised."""
+                        normalize_first=False, d_cand_ids_ptr=None, d_cand_count_ptr=None, stream_ptr=None, d_allow_ptr=None, nrows=1,
+                        allow_stride_words=0, d_preds_ptr=None, pred_kind=None, npreds=1, d_group_ptr=None, max_list_ids=0):
+        """pann_scan_rerank_dev: the same on raw device addresses (integers), enqueued on `stream_ptr`; nothing is synchronised.
+        d_allow_ptr (nrows packed rows allow_stride_words apart) or d_preds_ptr (npreds predicates of kind pred_kind, 8-byte
+        aligned), with d_group_ptr (nq table indices) when there is more than one: pann_scan_rerank_masked_dev / _labeled_dev,
+        which synchronise the stream once."""
         vp = lambda a: C.c_void_p(a or None)
-        check(self._lib.pann_scan_rerank_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
-                                             1 if normalize_first else 0, k, rerank_factor, vp(d_ids_ptr), vp(d_dists_ptr),
-                                             vp(d_cand_ids_ptr), vp(d_cand_count_ptr), vp(stream_ptr)))
+        name, mid = "pann_scan_rerank_dev", ()
+        if d_preds_ptr is not None:
+            name, mid = "pann_scan_rerank_labeled_dev", (_pred_kind(pred_kind), vp(d_preds_ptr), npreds, vp(d_group_ptr), int(max_list_ids))
+        elif d_allow_ptr is not None:
+            name, mid = "pann_scan_rerank_masked_dev", (vp(d_allow_ptr), nrows, allow_stride_words, vp(d_group_ptr), int(max_list_ids))
+        check(getattr(self._lib, name)(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
+                                       1 if normalize_first else 0, k, rerank_factor, *mid, vp(d_ids_ptr), vp(d_dists_ptr),
+                                       vp(d_cand_ids_ptr), vp(d_cand_count_ptr), vp(stream_ptr)))
 
     # ---- robustPrune (vamana/index.h:63-137), batched ----
     def robust_prune_batch(self, owners, cand_ids, cand_offsets, alpha, R, cand_dists=None, add_out_nbrs=True):

@@ -22,6 +22,9 @@ call.  Run the tool under `timeout -k 10 <seconds>` so that a hang ends the proc
                                                       # quantised scan"), beside (c); then three alternating wall-clock runs of the host
                                                       # entries pann_scan_rerank / pann_bruteforce_knn on the float handle / (--bits 8)
                                                       # pann_bruteforce_knn(k = 64) on the copy.  --no-graph: no build, (d) and those only
+    python tools/rerank_time.py --scan --no-graph --allow-frac 0.05 [--tenants 16]   # the filtered scan (DESIGN.md "Filtered exhaustive
+                                                      # scan"), pann_bruteforce_knn_masked / _grouped on the float handle and the unfiltered
+                                                      # scan, host entries, three alternating runs; recall@10 against the float route
 """
 import argparse
 import ctypes as C
@@ -75,6 +78,8 @@ def main():
     ap.add_argument("--metric", choices=("Euclidian", "mips"), default="Euclidian", help="mips: normalised rows and queries, the MIPS quantisers")
     ap.add_argument("--scan", action="store_true", help="also time the exhaustive scan + rerank (pann_scan_rerank*)")
     ap.add_argument("--no-graph", action="store_true", help="with --scan: build no graph, time the scan and the exact routes only")
+    ap.add_argument("--allow-frac", type=float, default=None, help="with --scan: also time the filtered scan under a filter that allows this fraction")
+    ap.add_argument("--tenants", type=int, default=1, help="with --allow-frac: a table of this many filters, one index per query (1: one bitmap)")
     a = ap.parse_args()
     import torch
     n, d, nq, beam, mips = a.n, a.d, a.nq, a.beam, a.metric == "mips"
@@ -180,6 +185,34 @@ def main():
                 rows.append(dict(path="host " + name, ms_runs=ts))
                 print(f"  host {name:26s} " + "  ".join(f"{t:8.2f}" for t in ts) + " ms", flush=True)
 
+    def filtered_report():
+        """--allow-frac F [--tenants G]: the filtered scan, the exact filtered route on the float handle and the unfiltered scan, host
+        entries, three alternating wall-clock runs; recall@10 of the filtered scan against the exact filtered route"""
+        rng = np.random.default_rng(5)
+        G = max(a.tenants, 1)
+        if G == 1:         # one bitmap: a random F of the points
+            kw, exact = dict(allow=rng.random(n) < a.allow_frac), lambda: full.bruteforce_knn_masked(Q, K, kw["allow"])
+        else:              # G tenants of F * n random points each, every query one tenant's
+            kw = dict(allow=rng.random((G, n)) < a.allow_frac, group_of_query=rng.integers(0, G, nq).astype(np.uint32))
+            exact = lambda: full.bruteforce_knn_grouped(Q, K, **kw)
+        with step("filtered scan, three alternating runs", 900):
+            legs = [("scan_rerank filtered", lambda: full.scan_rerank(quant, qparams, Q, K, RF, **kw)), ("bruteforce_knn filtered f32", exact),
+                    ("scan_rerank unfiltered", lambda: full.scan_rerank(quant, qparams, Q, K, RF))]
+            got = {name: fn() for name, fn in legs}        # warm-up: scratch growth; and the results for the recall
+            wall = {name: [] for name, _ in legs}
+            for _ in range(3):
+                for name, fn in legs:
+                    t = time.perf_counter(); fn(); wall[name].append((time.perf_counter() - t) * 1e3)
+            ei, ed, _ = got["bruteforce_knn filtered f32"]
+            rec = recall_at_k(got["scan_rerank filtered"]["ids"], ei, ed, K)
+            for name, ts in wall.items():
+                rows.append(dict(path="host " + name, ms_runs=ts, allow_frac=a.allow_frac, tenants=G))
+                print(f"  host {name:28s} " + "  ".join(f"{t:8.2f}" for t in ts) + " ms", flush=True)
+            rows.append(dict(path="scan_rerank filtered", recall10=rec))
+            print(f"  filtered scan recall@10 against the exact filtered route: {rec:.4f}  (allow-frac {a.allow_frac}, tenants {G})", flush=True)
+
+    if a.scan and a.allow_frac is not None:
+        filtered_report()
     if a.scan and a.no_graph:
         scan_report()
         if a.json:
