@@ -928,8 +928,8 @@ int pann_bruteforce_knn_masked_grouped_dev(pann_index* idx, const void* d_querie
  * (group_of_query == NULL, which requires npreds == 1) for the batch, or a TABLE of nrows bitmap rows (allow_stride_words >=
  * ceil(n / 32) apart) / npreds predicates of one kind, of which query q uses entry row_of_query[q] / group_of_query[q]: the
  * queries are sorted by entry and every used entry's id list is scanned once for all its queries, as by
- * pann_bruteforce_knn_masked_grouped (max_list_ids: as there; results do not depend on it).  There is no per-query-rows form: a
- * caller with one filter per query passes a table of nq entries, which is correct but slow (one list per query).  Labels are
+ * pann_bruteforce_knn_masked_grouped (max_list_ids: as there; results do not depend on it).  A caller with one filter per query
+ * uses pann_scan_rerank_masked_per_query / _labeled_per_query below, not a table of nq entries (correct, but one list per query).  Labels are
  * read from `full` (pann_index_set_labels); quant needs none.  Scratch is quant's: one call per handle at a time.
  * Status: everything pann_scan_rerank refuses, with its codes; and as the grouped exact routes: NULL bitmap, a table stride
  * below ceil(n / 32), no labels on `full`, an unknown kind, NULL or (device) misaligned predicates, an empty table, an entry
@@ -954,6 +954,37 @@ int pann_scan_rerank_labeled(pann_index* full, pann_index* quant, const pann_qua
                              uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
                              const pann_label_pred* preds, uint64_t npreds, const uint32_t* group_of_query, uint64_t max_list_ids,
                              uint32_t* out_ids, float* out_dists, uint32_t* out_cand_ids, uint32_t* out_cand_count);
+
+/* ---- per-query filtered scan (DESIGN.md "Per-query filtered scan") ----  The filtered scan above with ONE FILTER PER QUERY: query
+ * q may return only the points that bitmap row q allows (nq rows, allow_stride_words >= ceil(n / 32) words apart, 4-byte aligned,
+ * bit i of a row = point i: the format pann_bruteforce_knn_masked takes per query) or that predicate q of `kind` holds for
+ * (nq predicates over the labels of `full`).  Steps, outputs and results are exactly those stated above for A_q -- the candidate
+ * list, out_cand_count[q] = c_q = min(k * rerank_factor, 64, |A_q|), padding past it, the rerank as pann_rerank -- and an empty
+ * A_q is an answer.  The scan reads every point once for all queries on the matrix cores and tests each (query, point) cell
+ * against the query's filter in the tile epilogue: no compaction, no id lists, and the cost does not depend on what the filters
+ * allow.  Bits at positions >= n and words beyond ceil(n / 32) of a row are never read into a result.
+ * Status: everything pann_scan_rerank refuses, with its codes; NULL bitmap, allow_stride_words < ceil(n / 32), no labels on
+ * `full`, an unknown kind, NULL or (device) misaligned predicates or bitmap rows -> PANN_ERR_BAD_ARG.  nq == 0 -> PANN_OK.
+ * Nothing is written on an error.
+ * The _dev entries keep the contract of pann_scan_rerank_dev, not that of the table form: they never synchronise `stream`, read
+ * nothing back, allocate nothing once quant's scratch has reached its size, and can be captured into a graph.  Scratch is
+ * quant's: one call per handle at a time. */
+int pann_scan_rerank_masked_per_query_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
+                                          uint64_t nq, uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor,
+                                          const uint32_t* d_allow, uint64_t allow_stride_words, uint32_t* d_out_ids, float* d_out_dists,
+                                          uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream);
+int pann_scan_rerank_masked_per_query(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                                      uint64_t nq, uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor,
+                                      const uint32_t* allow, uint64_t allow_stride_words, uint32_t* out_ids, float* out_dists,
+                                      uint32_t* out_cand_ids, uint32_t* out_cand_count);
+int pann_scan_rerank_labeled_per_query_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries,
+                                           uint64_t nq, uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
+                                           const pann_label_pred* d_preds, uint32_t* d_out_ids, float* d_out_dists,
+                                           uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream);
+int pann_scan_rerank_labeled_per_query(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                                       uint64_t nq, uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
+                                       const pann_label_pred* preds, uint32_t* out_ids, float* out_dists, uint32_t* out_cand_ids,
+                                       uint32_t* out_cand_count);
 
 /* ---- entry points: the medoids of a table of filters, on the device (DESIGN.md "Entry points") ----  This project's own.
  * Where a filtered search starts: for every filter of a table the points nearest to the centroid of what it allows, so that a

@@ -224,6 +224,19 @@ SIGNATURES = {
     "pann_scan_rerank_labeled_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
                                                C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p,
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # one filter per query (... rerank_factor | rows, stride words | kind, preds | ids, dists, cand_ids, cand_count [, stream])
+    "pann_scan_rerank_masked_per_query": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
+                                                    C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
+    "pann_scan_rerank_masked_per_query_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
+                                                        C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pann_scan_rerank_labeled_per_query": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
+                                                     C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
+    "pann_scan_rerank_labeled_per_query_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
+                                                         C.c_int, C.c_uint32, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
     "pann_batch_search_masked_rerank": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64,
                                                   C.c_int, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(QueryParams), C.c_void_p,
                                                   C.c_uint64, C.POINTER(RerankOut), C.c_void_p, C.c_void_p]),

@@ -3017,9 +3017,116 @@ int scan_filtered_host(const char* fn, pann_index* full, pann_index* quant, cons
   return t.finish();
 }
 
+// ---- one filter per query, tested in the scan's epilogue (DESIGN.md "Per-query filtered scan") ----
+
+// what the plain scan refuses, then what the per-query exact routes refuse about the filter; a stride of 0 is no row per query
+int scan_per_query_checks(const char* fn, const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                          uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int rerank_factor, const PointFilter& F, const uint32_t* out_ids,
+                          const float* out_dists) {
+  if (int rc = scan_rerank_checks(fn, full, quant, qparams, queries, nq, q_stride_bytes, k, rerank_factor, out_ids, out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  if (F.mode != MASK_BITMAP) return filter_checks(full, fn, F, nq);
+  const uint64_t words = PointFilter::row_words(full->ix.n);
+  if (!F.allow) { set_error(std::string(fn) + ": null allow bitmap"); return PANN_ERR_BAD_ARG; }
+  if (F.stride < words) { set_error(std::string(fn) + ": allow_stride_words must be at least ceil(n / 32) = " + std::to_string(words)); return PANN_ERR_BAD_ARG; }
+  if (F.dev && (uintptr_t)F.allow % 4 != 0) { set_error(std::string(fn) + ": bitmap rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+// r: the request on device pointers, F: nq bitmap rows or nq predicates on the device.  nsplit by the occupancy of the form's own kernels.
+int scan_per_query_launch(pann_index* full, pann_index* quant, ScanRerankCall r, int rerank_factor, const PointFilter& F) {
+  r.c = scan_list_length(quant, r.k, rerank_factor);
+  const uint32_t ntiles = (uint32_t)((r.nq + 63) / 64);
+  r.nsplit = choose_gt_pieces(quant, ntiles, (double)dense_scan_slots(quant->ix, r.c, false, F.mode), quant->ix.n);
+  r.per_query = F; r.per_query.layout = PointFilter::PER_QUERY; r.per_query.count = r.nq; r.per_query.dev = true;
+  return scan_rerank_dev(full->ix, quant->ix, quant->ws_rr, quant->ws2, r);
+}
+
+int scan_per_query_dev(const char* fn, pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                       uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const PointFilter& F, uint32_t* d_out_ids,
+                       float* d_out_dists, uint32_t* d_out_cand_ids, uint32_t* d_out_cand_count, void* stream) {
+  if (int rc = scan_per_query_checks(fn, full, quant, qparams, d_queries, nq, q_stride_bytes, k, rerank_factor, F, d_out_ids, d_out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)d_queries % 4 != 0) { set_error(std::string(fn) + ": query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  ScanRerankCall r;
+  r.qparams = qparams; r.queries = d_queries; r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first; r.k = k;
+  r.out_ids = d_out_ids; r.out_dists = d_out_dists; r.out_cand_ids = d_out_cand_ids; r.out_cand_count = d_out_cand_count; r.stream = stream;
+  return scan_per_query_launch(full, quant, r, rerank_factor, F);
+}
+
+int scan_per_query_host(const char* fn, pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                        uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const PointFilter& F, uint32_t* out_ids,
+                        float* out_dists, uint32_t* out_cand_ids, uint32_t* out_cand_count) {
+  if (int rc = scan_per_query_checks(fn, full, quant, qparams, queries, nq, q_stride_bytes, k, rerank_factor, F, out_ids, out_dists)) return rc;
+  if (nq == 0) return PANN_OK;
+  DeviceGuard g(quant->device);
+  const uint32_t c = scan_list_length(quant, k, rerank_factor);
+  HostTrip t(quant);
+  const StagedFilter staged(t, &F, quant->ix.n, nq);      // the rows travel packed to ceil(n / 32) words each
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * quant->ix.d);
+  const int o_cnt = t.out.add(out_cand_count, nq * 4);      // (the small pieces first: HostTrip)
+  const int o_ids = t.out.add(out_ids, nq * k * 4), o_dists = t.out.add(out_dists, nq * k * 4);
+  const int o_cand = t.out.add(out_cand_ids, nq * c * 4);
+  if (int rc = t.begin()) return rc;
+  ScanRerankCall r;
+  r.qparams = qparams; r.queries = (const float*)t.din<uint8_t>(i_q); r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first; r.k = k;
+  r.out_ids = t.dout<uint32_t>(o_ids); r.out_dists = t.dout<float>(o_dists);
+  r.out_cand_ids = t.dout<uint32_t>(o_cand); r.out_cand_count = t.dout<uint32_t>(o_cnt); r.stream = t.st;
+  if (int rc = scan_per_query_launch(full, quant, r, rerank_factor, staged.on_device(t))) return rc;
+  return t.finish();
+}
+
+// nq bitmap rows / nq predicates as a per-query filter, whatever nq is (one query still has its own row)
+PointFilter per_query_bitmap(const uint32_t* allow, uint64_t stride, uint64_t nq, bool dev) {
+  PointFilter f = PointFilter::bitmap(allow, stride, nq, dev);
+  f.layout = PointFilter::PER_QUERY; f.count = nq;
+  return f;
+}
+PointFilter per_query_labels(const pann_index* full, int kind, const pann_label_pred* preds, uint64_t nq, bool dev) {
+  PointFilter f = label_filter(full, kind, preds, nq, dev);
+  f.layout = PointFilter::PER_QUERY;
+  return f;
+}
+
 }  // namespace
 
 extern "C" {
+
+int pann_scan_rerank_masked_per_query_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                                          uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const uint32_t* d_allow,
+                                          uint64_t allow_stride_words, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_cand_ids,
+                                          uint32_t* d_out_cand_count, void* stream) {
+  return scan_per_query_dev("pann_scan_rerank_masked_per_query_dev", full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, k,
+                            rerank_factor, per_query_bitmap(d_allow, allow_stride_words, nq, true), d_out_ids, d_out_dists, d_out_cand_ids,
+                            d_out_cand_count, stream);
+}
+
+int pann_scan_rerank_masked_per_query(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                                      uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, const uint32_t* allow,
+                                      uint64_t allow_stride_words, uint32_t* out_ids, float* out_dists, uint32_t* out_cand_ids,
+                                      uint32_t* out_cand_count) {
+  return scan_per_query_host("pann_scan_rerank_masked_per_query", full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, k,
+                             rerank_factor, per_query_bitmap(allow, allow_stride_words, nq, false), out_ids, out_dists, out_cand_ids,
+                             out_cand_count);
+}
+
+int pann_scan_rerank_labeled_per_query_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                                           uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
+                                           const pann_label_pred* d_preds, uint32_t* d_out_ids, float* d_out_dists, uint32_t* d_out_cand_ids,
+                                           uint32_t* d_out_cand_count, void* stream) {
+  return scan_per_query_dev("pann_scan_rerank_labeled_per_query_dev", full, quant, qparams, d_queries, nq, q_stride_bytes, normalize_first, k,
+                            rerank_factor, per_query_labels(full, kind, d_preds, nq, true), d_out_ids, d_out_dists, d_out_cand_ids,
+                            d_out_cand_count, stream);
+}
+
+int pann_scan_rerank_labeled_per_query(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                                       uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, int kind,
+                                       const pann_label_pred* preds, uint32_t* out_ids, float* out_dists, uint32_t* out_cand_ids,
+                                       uint32_t* out_cand_count) {
+  return scan_per_query_host("pann_scan_rerank_labeled_per_query", full, quant, qparams, queries, nq, q_stride_bytes, normalize_first, k,
+                             rerank_factor, per_query_labels(full, kind, preds, nq, false), out_ids, out_dists, out_cand_ids, out_cand_count);
+}
 
 int pann_scan_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
                          uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, uint32_t* d_out_ids, float* d_out_dists,

@@ -1353,15 +1353,37 @@ __global__ void __launch_bounds__(256) scan_fill_kernel(uint32_t* p, uint64_t n,
 // parameter, so that the plain instances keep their symbol names, and the body is text, not a function they would both call, so that
 // they keep their code: through a shared __forceinline__ function every plain instance came out a few instructions and up to 8
 // VGPRs different (tools/compare_kernels.py).
+// PQ: every A row carries a filter of its own, tested per cell in the epilogue (DESIGN.md "Per-query filtered scan"); a further
+// overload with a fourth template parameter and the filter as a fourth argument, for the same reasons.  The plain and list forms
+// read the PQ parts of the body as discarded statements over an empty filter.
+constexpr uint32_t SCAN_MBLOCK = 512;      // columns of a bitmap row fetched at once: 16 words = 64 bytes, 8 tiles
+constexpr uint32_t SCAN_MROW = 18;         // words between two rows of a block in LDS: the four quarters' 8-byte reads fall on different banks
+constexpr size_t SCAN_MASK_LDS = 2 * (size_t)DT_A * SCAN_MROW * 4, SCAN_LABEL_LDS = 2 * (size_t)DT_B * 4;
+static_assert(SCAN_MBLOCK == 16 * 32 && SCAN_MBLOCK % DT_B == 0 && SCAN_MROW % 2 == 0 && SCAN_MROW >= 16, "the body shifts by these");
 template <int DT, int NR>
 __global__ void __launch_bounds__(256, 2) dense_scan_mfma_kernel(DenseArgs A, const int* __restrict__ bnorm, uint32_t* gtau) {
   constexpr bool LIST = false;
+  constexpr int PQ = MASK_NONE; constexpr PointFilter F{};
 #include "dense_scan_body.h"
 }
 template <int DT, int NR, bool LIST>
 __global__ void __launch_bounds__(256, 2) dense_scan_mfma_kernel(DenseArgs A, const int* __restrict__ bnorm, uint32_t* gtau) {
   static_assert(LIST, "the plain form is the two-parameter kernel");
+  constexpr int PQ = MASK_NONE; constexpr PointFilter F{};
 #include "dense_scan_body.h"
+}
+template <int DT, int NR, bool LIST, int PQ>
+__global__ void __launch_bounds__(256, 2) dense_scan_mfma_kernel(DenseArgs A, const int* __restrict__ bnorm, uint32_t* gtau, PointFilter F) {
+  static_assert(!LIST && (PQ == MASK_BITMAP || PQ == MASK_LABELS), "a per-query filter goes with the contiguous B side");
+#include "dense_scan_body.h"
+}
+// entries of a merged row that hold an id: the length of a row's candidate list under a filter (one wave per row, m <= 64)
+__global__ void __launch_bounds__(256) scan_list_count_kernel(const uint32_t* ids, uint64_t na, uint32_t m, uint32_t* counts) {
+  const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63;
+  if (row >= na) return;
+  const uint64_t has = __ballot(lane < m && ids[row * m + lane] != SENTINEL);
+  if (lane == 0) counts[row] = (uint32_t)__popcll(has);
 }
 
 // merge the nsplit partial lists of each A row (one wave per row) and write ids / dists
@@ -1513,22 +1535,50 @@ static ScanKernel dense_scan_kernel_of(const DeviceIndex& ix, uint32_t m, bool l
   if (ix.dtype == PANN_I4 && ix.metric == PANN_MIPS) return dense_scan_kernel_pick<PANN_I4>(one, list);
   return nullptr;
 }
+// the per-query form (mode: MASK_BITMAP / MASK_LABELS of the rows' filters), or null
+using ScanMaskKernel = void (*)(DenseArgs, const int*, uint32_t*, PointFilter);
+template <int DT>
+static ScanMaskKernel dense_scan_mask_pick(bool one, int mode) {
+  if (mode == MASK_BITMAP) return one ? dense_scan_mfma_kernel<DT, 1, false, MASK_BITMAP> : dense_scan_mfma_kernel<DT, 4, false, MASK_BITMAP>;
+  if (mode == MASK_LABELS) return one ? dense_scan_mfma_kernel<DT, 1, false, MASK_LABELS> : dense_scan_mfma_kernel<DT, 4, false, MASK_LABELS>;
+  return nullptr;
+}
+static ScanMaskKernel dense_scan_mask_kernel_of(const DeviceIndex& ix, uint32_t m, int mode) {
+  const bool one = m <= 16;
+  if (ix.dtype == PANN_U8 && ix.metric == PANN_L2) return dense_scan_mask_pick<PANN_U8>(one, mode);
+  if (ix.dtype == PANN_I8 && ix.metric == PANN_MIPS) return dense_scan_mask_pick<PANN_I8>(one, mode);
+  if (ix.dtype == PANN_U4 && ix.metric == PANN_L2) return dense_scan_mask_pick<PANN_U4>(one, mode);
+  if (ix.dtype == PANN_I4 && ix.metric == PANN_MIPS) return dense_scan_mask_pick<PANN_I4>(one, mode);
+  return nullptr;
+}
 bool dense_scan_eligible(const DeviceIndex& ix) { return dense_scan_kernel_of(ix, 1) != nullptr && ix.pstride <= 2 * DT_SEG; }
-static size_t dense_scan_lds(const DeviceIndex& ix) { return GT_LDS_BYTES + (size_t)((ix.dbytes + DT_SEG - 1) / DT_SEG) * GT_BT_BYTES; }
+static size_t dense_scan_lds(const DeviceIndex& ix, int mode = MASK_NONE) {
+  return GT_LDS_BYTES + (size_t)((ix.dbytes + DT_SEG - 1) / DT_SEG) * GT_BT_BYTES +
+         (mode == MASK_BITMAP ? SCAN_MASK_LDS : mode == MASK_LABELS ? SCAN_LABEL_LDS : 0);
+}
 // workgroups of the scan that are resident at once (for the caller's choice of nsplit)
-uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m, bool list) {
-  const void* kern = reinterpret_cast<const void*>(dense_scan_kernel_of(ix, m, list));
-  const size_t lds = dense_scan_lds(ix);
+uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m, bool list, int mode) {
+  const void* kern = mode != MASK_NONE ? reinterpret_cast<const void*>(dense_scan_mask_kernel_of(ix, m, mode))
+                                       : reinterpret_cast<const void*>(dense_scan_kernel_of(ix, m, list));
+  const size_t lds = dense_scan_lds(ix, mode);
   int v = 0;
   (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, lds) != hipSuccess || v < 1) v = 1;
   return 256u * (uint32_t)v;
 }
 // c.a_ext: na rows in ix's own row format, 16-byte aligned, c.a_stride a multiple of 16; c.m <= 64; B = all c.nb points, or (c.b_ids)
-// the c.nb list positions of c.b_ids, in the segments and tiles of c.a_off / c.b_off / c.tile_seg / c.tile_a0 when those are given
+// the c.nb list positions of c.b_ids, in the segments and tiles of c.a_off / c.b_off / c.tile_seg / c.tile_a0 when those are given.
+// c.filter (per query, device pointers; contiguous B only): row r may take only the points that bitmap row / predicate r allows, and
+// c.out_counts[r] = the ids its list holds (the rest of the row 0xFFFFFFFF / +inf).  No synchronisation and no read-back in any form.
 int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c) {
   const bool list = c.b_ids != nullptr;
+  const int mode = c.filter.mode;
   const ScanKernel kern = dense_scan_kernel_of(ix, c.m, list);
+  const ScanMaskKernel mkern = dense_scan_mask_kernel_of(ix, c.m, mode);
+  if (mode != MASK_NONE && (list || !c.filter.dev || (mode == MASK_BITMAP ? !c.filter.allow || c.filter.stride < PointFilter::row_words(c.nb)
+                                                                           : !c.filter.labels || !c.filter.preds || !pred_kind_known(c.filter.kind)))) {
+    set_error("quantised scan: a per-query filter goes with all points as the B side and device bitmap rows or predicates"); return PANN_ERR_BAD_ARG;
+  }
   if (!kern || ix.pstride > 2 * DT_SEG || c.m == 0 || c.m > 64) { set_error("quantised scan: unsupported element type, row length or list length"); return PANN_ERR_UNSUPPORTED; }
   if (!list && (c.a_off || c.b_off || c.tile_seg || c.tile_a0)) { set_error("quantised scan: segments go with an id list"); return PANN_ERR_BAD_ARG; }
   if (list && c.nb > 0xFFFF0000ull) { set_error("quantised scan: an id list of more than 2^32 - 2^16 entries"); return PANN_ERR_UNSUPPORTED; }      // (positions are 32-bit in the kernel)
@@ -1553,11 +1603,16 @@ int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
   else if (ix.dtype == PANN_U8) hipLaunchKernelGGL(scan_norms_kernel<PANN_U8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.nb, d_norm);
   else if (ix.dtype == PANN_U4) hipLaunchKernelGGL(scan_norms_kernel<PANN_U4>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, c.nb, d_norm);
   PANN_HIP(hipGetLastError());
-  launch_lds(kern, dim3(c.ntiles, c.nsplit), dim3(256), dense_scan_lds(ix), st, A, (const int*)d_norm, d_gtau);
+  if (mode != MASK_NONE) launch_lds(mkern, dim3(c.ntiles, c.nsplit), dim3(256), dense_scan_lds(ix, mode), st, A, (const int*)d_norm, d_gtau, c.filter);
+  else launch_lds(kern, dim3(c.ntiles, c.nsplit), dim3(256), dense_scan_lds(ix), st, A, (const int*)d_norm, d_gtau);
   PANN_HIP(hipGetLastError());
   hipLaunchKernelGGL(dense_merge_kernel, dim3((uint32_t)c.na), dim3(64), (size_t)mcap * 8, st,
                      (const uint64_t*)partial, c.na, c.nsplit, c.m, mcap, c.out_ids, c.out_dists);
   PANN_HIP(hipGetLastError());
+  if (mode != MASK_NONE && c.out_counts) {
+    hipLaunchKernelGGL(scan_list_count_kernel, dim3((uint32_t)((c.na + 3) / 4)), dim3(256), 0, st, (const uint32_t*)c.out_ids, c.na, c.m, c.out_counts);
+    PANN_HIP(hipGetLastError());
+  }
   return PANN_OK;
 }
 

@@ -101,6 +101,7 @@ struct DenseTopkCall {
   const uint64_t* a_off = nullptr, *b_off = nullptr;
   uint32_t ntiles = 0, nsplit = 1, m = 0; uint64_t na = 0, nb = 0; int exclude_same = 0;      // nsplit: pieces B is cut into per tile
   uint32_t* out_ids = nullptr; float* out_dists = nullptr;      // na x m each
+  PointFilter filter; uint32_t* out_counts = nullptr;           // dense_scan_dev only: one filter per A row, and (na, optional) the ids each row got
 };
 
 // the one growable device buffer: kernel scratch, staging regions, tables kept on a handle (grown on demand, never shrunk).
@@ -192,8 +193,11 @@ int query_distances_dev(const DeviceIndex& ix, hipStream_t st, const uint8_t* d_
 // sorted by (float32 of the exact integer distance, id).  PANN_U8 / PANN_U4 with L2, PANN_I8 / PANN_I4 with MIPS, pstride <= 512.
 // List form (c.b_ids, DESIGN.md "Filtered exhaustive scan"): B is the c.nb positions of an id list, one segment or the segments and
 // tiles of dense_topk_dev's segmented form; a list shorter than c.m leaves the rest of its rows 0xFFFFFFFF / +inf.
+// Per-query form (c.filter, DESIGN.md "Per-query filtered scan"): B is all points and A row r may take only what bitmap row r
+// (c.filter.stride words apart) or predicate r over c.filter.labels allows -- a test per cell in the tile epilogue, no id list.
 bool dense_scan_eligible(const DeviceIndex& ix);
-uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m, bool list = false);      // workgroups resident at once, for the choice of c.nsplit
+// workgroups resident at once, for the choice of c.nsplit; mode: MASK_BITMAP / MASK_LABELS of the per-query form
+uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m, bool list = false, int mode = MASK_NONE);
 int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c);
 
 int pivot_split_dev(const DeviceIndex& ix, hipStream_t st, const uint32_t* d_ids, const uint32_t* d_tile_seg,
@@ -376,6 +380,10 @@ struct ScanRerankCall {
   uint32_t* out_cand_ids = nullptr, *out_cand_count = nullptr;            // nq x c, nq (optional)
   void* stream = nullptr;
   std::function<int(const uint8_t* qb, uint64_t qb_stride, uint32_t* cand, float* cdist, uint32_t* count, bool* none)> lists;
+  // Per-query form (pann_scan_rerank_*_per_query): step 2 is the scan itself with this filter (device pointers, one row / predicate
+  // per query) tested in its epilogue; count[q] = the ids of the merged row.  No synchronisation, no read-back, no allocation
+  // beyond the two scratch regions.
+  PointFilter per_query;
 };
 int scan_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace& rr_ws, Workspace& scan_ws, const ScanRerankCall& r);
 

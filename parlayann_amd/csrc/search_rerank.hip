@@ -390,6 +390,11 @@ int scan_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace
     bool none = false;
     if (int rc = r.lists(qb, qb_stride, cand, cdist, count, &none)) return rc;
     if (none) return knn_pad_dev(r.out_ids, r.out_dists, nullptr, nq, r.k, 0, 1, st);
+  } else if (r.per_query.given()) {      // the scan over all rows, each query's filter tested in the epilogue; the lists' lengths from the merged rows
+    DenseTopkCall s;
+    s.a_ext = qb; s.a_stride = qb_stride; s.ntiles = (uint32_t)((nq + 63) / 64); s.na = nq; s.nb = quant.n; s.nsplit = r.nsplit; s.m = c;
+    s.out_ids = cand; s.out_dists = cdist; s.filter = r.per_query; s.out_counts = count;
+    if (int rc = dense_scan_dev(quant, scan_ws, st, s)) return rc;
   } else {
     DenseTopkCall s;
     s.a_ext = qb; s.a_stride = qb_stride; s.ntiles = (uint32_t)((nq + 63) / 64); s.na = nq; s.nb = quant.n; s.nsplit = r.nsplit; s.m = c;

@@ -255,22 +255,24 @@ class GraphIndex:
                                      rerank_factor=100, allow=allow, where=where, **qp)
         return r["ids"], r["dists"]
 
-    def _scan_masked(self, queries, knn, allow, where):
+    def _scan_masked(self, queries, knn, allow, where, per_query=False):
         """batch_search_masked(quant=True, exhaustive=True): DeviceIndex.scan_rerank under the filter; per-query rows or predicates
-        become a table of the distinct ones (np.unique), as exact_grouped does"""
+        become a table of the distinct ones (np.unique), as exact_grouped does -- or (per_query) go to the scan as they are"""
         if not self.use_quantization or self.quant_bits not in (8, 4):
             raise ValueError("exhaustive=True scans the quantised copy: quant=True on float points, quant_bits 8 or 4")
         queries = np.ascontiguousarray(queries, dtype=self.T)
         flt = PointFilter.of(self.index.n, allow, where)
         kw = flt.kw
-        if not flt.shared:
+        if per_query:
+            kw = dict(kw, per_query=True)
+        elif not flt.shared:
             table, group = np.unique(flt.check(len(queries)).rows, axis=0, return_inverse=True)
             kw = dict(PointFilter(table, flt.kind, False).kw, group_of_query=np.asarray(group).reshape(-1))
         r = self.index.scan_rerank(self.q_index, self.qparams, queries, k=knn, rerank_factor=100, normalize_first=self.metric != "Euclidian", **kw)
         return r["ids"], r["dists"]
 
     def batch_search_masked(self, queries, knn, beam_width, allow=None, quant=False, visit_limit=-1, exact_below=None, where=None,
-                            exact_grouped=False, exhaustive=False):
+                            exact_grouped=False, exhaustive=False, per_query=False):
         """Only allowed points are returned (allow: an allow bitmap or boolean mask, DeviceIndex.batch_search_masked; or
         where = (kind, preds): a label predicate over the labels of set_labels, 8 bytes per query in place of a bitmap row --
         every route below has the same form under it, and exact_below is decided by DeviceIndex.label_count).
@@ -287,13 +289,18 @@ class GraphIndex:
         exhaustive (with quant=True on float points, quant_bits 8 or 4; not with exact_below): the filtered exhaustive scan of
         the quantised copy instead of the walk (DeviceIndex.scan_rerank(allow= / where=), DESIGN.md "Filtered exhaustive
         scan"): the min(knn * 100, 64) nearest ALLOWED rows of the copy, re-scored on the float rows; per-query rows or
-        predicates are deduplicated into a table here.  beam_width and visit_limit are not read.  The default changes nothing."""
+        predicates are deduplicated into a table here.  beam_width and visit_limit are not read.  The default changes nothing.
+        per_query (with exhaustive): per-query rows or predicates go to the scan as they are, tested cell by cell inside it
+        (DeviceIndex.scan_rerank(per_query=True), DESIGN.md "Per-query filtered scan"), instead of being deduplicated: the
+        same rows, faster when the queries share few filters.  The default changes nothing."""
         if where is None and allow is None:
             raise ValueError("batch_search_masked needs allow (a bitmap or boolean mask)")
         if exhaustive:
             if not quant or exact_below is not None or (where is not None and allow is not None):
                 raise ValueError("exhaustive=True goes with quant=True, one of allow= / where=, and no exact_below")
-            return self._scan_masked(queries, knn, allow, where)
+            return self._scan_masked(queries, knn, allow, where, per_query)
+        if per_query:
+            raise ValueError("per_query=True goes with exhaustive=True")
         return self._exact_or_walk(queries, knn, allow, where, exact_below,
                                    lambda q, allow=None, where=None: self._search_masked(q, knn, beam_width, allow, quant, visit_limit, where),
                                    exact_grouped)

@@ -775,7 +775,7 @@ class DeviceIndex:
 
     # ---- exhaustive quantised scan + exact rerank in one call (DESIGN.md "Exhaustive quantised scan") ----
     def scan_rerank(self, quant, qparams, queries, k=10, rerank_factor=100, normalize_first=False, candidates=False, allow=None,
-                    where=None, group_of_query=None, max_list_ids=0):
+                    where=None, group_of_query=None, max_list_ids=0, per_query=False):
         """pann_scan_rerank on this (float32) index, the exhaustive twin of search_rerank: `queries` (float32 rows) are quantised
         with `qparams` on the device, EVERY row of `quant` (a u8 / i8 / u4 / i4 DeviceIndex of quantized()) is scored on the int8
         matrix cores, the c = min(k * rerank_factor, 64, n) nearest by the quantised (dist, id) are re-scored here, sorted, and k
@@ -785,7 +785,10 @@ class DeviceIndex:
         scored, a query's list holds cand_count[q] = min(c, allowed points) ids, then 0xFFFFFFFF.  One bitmap (boolean (n,) or
         packed (W,)) or one predicate (kind, (a, b)) serves the batch; rows (G, n) / (G, W) or predicates (kind, preds[G, 2])
         are a TABLE and need group_of_query (nq, each < G), as bruteforce_knn_grouped (max_list_ids as there).  Labels are this
-        handle's."""
+        handle's.
+        per_query=True: one filter per query -- allow (nq, n) boolean or (nq, W) packed, or where = (kind, preds[nq, 2]) -- tested
+        inside the scan (pann_scan_rerank_masked_per_query / _labeled_per_query, DESIGN.md "Per-query filtered scan"): every row
+        is scored once for all queries, whatever the filters allow.  No group_of_query with it."""
         q = self._queries(queries)
         nq = len(q)
         c = max(min(k * rerank_factor, 64, quant.n), 0)
@@ -794,7 +797,13 @@ class DeviceIndex:
             res["cand_ids"], res["cand_count"] = np.empty((nq, c), np.uint32), np.empty(nq, np.uint32)
         flt = PointFilter.of(self.n, allow, where)
         name, mid = "pann_scan_rerank", ()
-        if flt is not None:
+        if per_query:
+            if flt is None or group_of_query is not None:
+                raise ValueError("per_query=True takes allow= or where= with one row per query, and no group_of_query")
+            rows = PointFilter(np.ascontiguousarray(flt.table(), dtype=np.uint32), flt.kind, False).check(nq)
+            name = "pann_scan_rerank_" + flt.infix + "_per_query"
+            mid = (rows.kind, _ptr(rows.rows)) if rows.kind is not None else (_ptr(rows.rows), rows.rows.shape[1])
+        elif flt is not None:
             group = None
             if group_of_query is not None:
                 group = np.ascontiguousarray(np.asarray(group_of_query).reshape(-1), dtype=np.uint32)
@@ -813,14 +822,21 @@ class DeviceIndex:
 
     def scan_rerank_dev(self, quant, qparams, d_queries_ptr, nq, q_stride_bytes, d_ids_ptr, d_dists_ptr, k=10, rerank_factor=100,
                         normalize_first=False, d_cand_ids_ptr=None, d_cand_count_ptr=None, stream_ptr=None, d_allow_ptr=None, nrows=1,
-                        allow_stride_words=0, d_preds_ptr=None, pred_kind=None, npreds=1, d_group_ptr=None, max_list_ids=0):
+                        allow_stride_words=0, d_preds_ptr=None, pred_kind=None, npreds=1, d_group_ptr=None, max_list_ids=0,
+                        per_query=False):
         """pann_scan_rerank_dev: the same on raw device addresses (integers), enqueued on `stream_ptr`; nothing is synchronised.
         d_allow_ptr (nrows packed rows allow_stride_words apart) or d_preds_ptr (npreds predicates of kind pred_kind, 8-byte
         aligned), with d_group_ptr (nq table indices) when there is more than one: pann_scan_rerank_masked_dev / _labeled_dev,
-        which synchronise the stream once."""
+        which synchronise the stream once.
+        per_query=True: d_allow_ptr holds nq rows allow_stride_words apart, or d_preds_ptr nq predicates; nrows, npreds and
+        d_group_ptr are not read, and nothing is synchronised (pann_scan_rerank_masked_per_query_dev / _labeled_per_query_dev)."""
         vp = lambda a: C.c_void_p(a or None)
         name, mid = "pann_scan_rerank_dev", ()
-        if d_preds_ptr is not None:
+        if per_query and d_preds_ptr is not None:
+            name, mid = "pann_scan_rerank_labeled_per_query_dev", (_pred_kind(pred_kind), vp(d_preds_ptr))
+        elif per_query:
+            name, mid = "pann_scan_rerank_masked_per_query_dev", (vp(d_allow_ptr), allow_stride_words)
+        elif d_preds_ptr is not None:
             name, mid = "pann_scan_rerank_labeled_dev", (_pred_kind(pred_kind), vp(d_preds_ptr), npreds, vp(d_group_ptr), int(max_list_ids))
         elif d_allow_ptr is not None:
             name, mid = "pann_scan_rerank_masked_dev", (vp(d_allow_ptr), nrows, allow_stride_words, vp(d_group_ptr), int(max_list_ids))

@@ -25,6 +25,10 @@ call.  Run the tool under `timeout -k 10 <seconds>` so that a hang ends the proc
     python tools/rerank_time.py --scan --no-graph --allow-frac 0.05 [--tenants 16]   # the filtered scan (DESIGN.md "Filtered exhaustive
                                                       # scan"), pann_bruteforce_knn_masked / _grouped on the float handle and the unfiltered
                                                       # scan, host entries, three alternating runs; recall@10 against the float route
+    python tools/rerank_time.py --scan --no-graph --allow-frac 0.1 --per-query [--labels]   # one filter per query (DESIGN.md "Per-query
+                                                      # filtered scan"): the per-query scan, the exact per-query route on the float handle
+                                                      # and the unfiltered scan, device entries, --steps alternating rounds under HIP events;
+                                                      # the table form with one entry per query on --table-nq queries; recall@10
 """
 import argparse
 import ctypes as C
@@ -80,6 +84,9 @@ def main():
     ap.add_argument("--no-graph", action="store_true", help="with --scan: build no graph, time the scan and the exact routes only")
     ap.add_argument("--allow-frac", type=float, default=None, help="with --scan: also time the filtered scan under a filter that allows this fraction")
     ap.add_argument("--tenants", type=int, default=1, help="with --allow-frac: a table of this many filters, one index per query (1: one bitmap)")
+    ap.add_argument("--per-query", action="store_true", help="with --allow-frac: one filter per query, tested inside the scan (device entries, HIP events)")
+    ap.add_argument("--labels", action="store_true", help="with --per-query: range predicates over random labels in place of bitmap rows")
+    ap.add_argument("--table-nq", type=int, default=200, help="with --per-query: queries of the table-form comparison (one list per query: slow)")
     a = ap.parse_args()
     import torch
     n, d, nq, beam, mips = a.n, a.d, a.nq, a.beam, a.metric == "mips"
@@ -211,7 +218,73 @@ def main():
             rows.append(dict(path="scan_rerank filtered", recall10=rec))
             print(f"  filtered scan recall@10 against the exact filtered route: {rec:.4f}  (allow-frac {a.allow_frac}, tenants {G})", flush=True)
 
-    if a.scan and a.allow_frac is not None:
+    def per_query_report():
+        """--allow-frac F --per-query [--labels]: one filter per query.  HIP events on the tool's stream, a.steps alternating rounds
+        of: the per-query scan (pann_scan_rerank_*_per_query_dev), the exact per-query route on the float handle
+        (pann_bruteforce_knn_masked_dev / _labeled_dev with one row / predicate per query) and the unfiltered scan; then the
+        table form of the filtered scan with one entry per query on the first --table-nq queries (wall clock: it synchronises),
+        beside the per-query scan on the same queries; recall@10 of the per-query scan against the exact route."""
+        rng = np.random.default_rng(5)
+        t_cnt = torch.zeros(nq, dtype=torch.int32, device="cuda")
+        t_ids2, t_d2 = torch.zeros((nq, K), dtype=torch.int32, device="cuda"), torch.zeros((nq, K), dtype=torch.float32, device="cuda")
+        if a.labels:      # labels uniform in [0, 1000): the range predicate of query q allows a window of F * 1000 values
+            full.set_labels(rng.integers(0, 1000, n).astype(np.uint32))
+            lo = rng.integers(0, 1000 - max(int(a.allow_frac * 1000), 1) + 1, nq)
+            preds = np.stack([lo, lo + max(int(a.allow_frac * 1000), 1) - 1], 1).astype(np.uint32)
+            t_f = torch.from_numpy(preds.view(np.int32)).cuda()
+            flt = dict(d_preds_ptr=t_f.data_ptr(), pred_kind="range")
+            exact_step = lambda: _capi.check(lib.pann_bruteforce_knn_labeled_dev(full.handle, C.c_void_p(t_q.data_ptr()), nq, 4 * d, K, _capi.PANN_PRED_RANGE,
+                                                                                 C.c_void_p(t_f.data_ptr()), nq, C.c_void_p(t_ids2.data_ptr()),
+                                                                                 C.c_void_p(t_d2.data_ptr()), C.c_void_p(t_cnt.data_ptr()), sp))
+            table_kw = lambda m: dict(where=("range", preds[:m]), group_of_query=np.arange(m))
+        else:             # a random F of the points per query, drawn on the device (int64 words: 2 x ceil(n / 64) uint32 per row)
+            W = (n + 63) // 64 * 2
+            t_f = torch.zeros((nq, W // 2), dtype=torch.int64, device="cuda")
+            weights = (1 << torch.arange(64, dtype=torch.int64, device="cuda"))
+            for q0 in range(0, nq, 64):
+                bits = torch.rand((min(64, nq - q0), W // 2, 64), device="cuda") < a.allow_frac
+                t_f[q0:q0 + 64] = (bits.to(torch.int64) * weights).sum(-1)
+            flt = dict(d_allow_ptr=t_f.data_ptr(), allow_stride_words=W)
+            exact_step = lambda: full.bruteforce_knn_masked_dev(t_q.data_ptr(), nq, 4 * d, K, t_f.data_ptr(), W, t_ids2.data_ptr(), t_d2.data_ptr(),
+                                                                t_cnt.data_ptr(), stream.cuda_stream)
+            table_kw = lambda m: dict(allow=t_f[:m].cpu().numpy().view(np.uint32), group_of_query=np.arange(m))
+        pq_step = lambda: full.scan_rerank_dev(quant, qparams, t_q.data_ptr(), nq, 4 * d, t_ids.data_ptr(), t_d.data_ptr(), k=K, rerank_factor=RF,
+                                               per_query=True, stream_ptr=stream.cuda_stream, **flt)
+        legs = [("per-query scan", pq_step), ("exact per-query f32", exact_step), ("unfiltered scan", scan_step)]
+        with step("per-query filters, alternating runs", 900):
+            for _, fn in legs:
+                for _ in range(a.warmup):
+                    fn()
+            stream.synchronize()
+            ms = {name: [] for name, _ in legs}
+            for _ in range(a.steps):
+                for name, fn in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record(stream); fn(); e1.record(stream); stream.synchronize()
+                    ms[name].append(e0.elapsed_time(e1))
+            for name, ts in ms.items():
+                rows.append(dict(path=name, ms_runs=ts, ms=float(np.median(ts)), allow_frac=a.allow_frac, labels=bool(a.labels)))
+                print(f"  {name:22s} median {np.median(ts):8.3f} ms  (min {min(ts):.3f}, max {max(ts):.3f}, {len(ts)} runs)", flush=True)
+            pq_step(); exact_step(); stream.synchronize()
+            rec = recall_at_k(t_ids.cpu().numpy().view(np.uint32), t_ids2.cpu().numpy().view(np.uint32), t_d2.cpu().numpy(), K)
+            rows.append(dict(path="per-query scan", recall10=rec))
+            print(f"  per-query scan recall@10 against the exact per-query route: {rec:.4f}  (allow-frac {a.allow_frac})", flush=True)
+        m = min(a.table_nq, nq)
+        with step(f"table form with one entry per query, {m} queries", 600):
+            kw = table_kw(m)
+            pq_kw = {k: v for k, v in kw.items() if k != "group_of_query"}
+            hosts = [("table form", lambda: full.scan_rerank(quant, qparams, Q[:m], K, RF, **kw)),
+                     ("per-query scan (host entry)", lambda: full.scan_rerank(quant, qparams, Q[:m], K, RF, per_query=True, **pq_kw))]
+            got = [fn() for _, fn in hosts]
+            assert np.array_equal(got[0]["ids"], got[1]["ids"]), "the table form and the per-query scan disagree"
+            for _ in range(3):
+                for name, fn in hosts:
+                    t = time.perf_counter(); fn(); rows.append(dict(path=name, nq=m, ms=(time.perf_counter() - t) * 1e3))
+                    print(f"  host {name:28s} {m} queries {rows[-1]['ms']:9.2f} ms", flush=True)
+
+    if a.scan and a.allow_frac is not None and a.per_query:
+        per_query_report()
+    elif a.scan and a.allow_frac is not None:
         filtered_report()
     if a.scan and a.no_graph:
         scan_report()
