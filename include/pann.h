@@ -17,6 +17,7 @@
  *   algorithms/utils/beamSearch.h:567-614  RangeSearch (beam search + BFS)  -> pann_range_query
  *   algorithms/utils/beamSearch.h:390-454  beam_search_rerank (quantised)   -> pann_batch_search_rerank*
  *   (none: the exhaustive twin of beam_search_rerank, this build's own)    -> pann_scan_rerank*
+ *   (none: its range twin, quantised radius join + exact recheck)          -> pann_scan_range*
  *
  * The reference has no FFI of its own for this path (it is a header-only template library); these
  * entry points are what a cgo/ctypes/pybind binding placed at the parallel_for seams above would
@@ -67,7 +68,7 @@ extern "C" {
  *            -256 * sum a * q, over ALL d coordinates (the reference's loops stop at dims / 2 bytes and so drop the last
  *            coordinate of an odd d)
  * Any other pairing is refused by pann_index_create* with PANN_ERR_UNSUPPORTED.  A 4-bit handle is searched
- * (pann_batch_search*, as `quant` of pann_batch_search_rerank*), scanned exhaustively (as `quant` of pann_scan_rerank*),
+ * (pann_batch_search*, as `quant` of pann_batch_search_rerank*), scanned exhaustively (as `quant` of pann_scan_rerank* / pann_scan_range*),
  * measured (pann_pair_distances, pann_query_distances), and has
  * its points and graph moved (upload / download / set_graph / update_rows / get_graph); it gets its graph from
  * pann_index_create_quantized(copy_graph) or pann_index_set_graph.  Every entry point that builds, prunes, ranges, reranks ON
@@ -653,6 +654,35 @@ int pann_scan_rerank_dev(pann_index* full, pann_index* quant, const pann_quant_p
 int pann_scan_rerank(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
                      uint64_t q_stride_bytes, int normalize_first, uint32_t k, int rerank_factor, uint32_t* out_ids, float* out_dists,
                      uint32_t* out_cand_ids, uint32_t* out_cand_count);
+
+/* ---- quantised range scan + exact recheck in one call (DESIGN.md "Quantised range scan") ----  The range twin of pann_scan_rerank:
+ * same two handles, same refusals, a radius in place of k.  Per batch of nq float query rows, on one stream:
+ *   1. the queries are quantised exactly as by pann_scan_rerank (normalize_first included);
+ *   2. EVERY row of quant is scored against every quantised query on the int8 matrix cores, exact int32 cast to float once (PANN_I4
+ *      in the units of its distance: -256 x the nibble dot product); the CANDIDATES of query i are the rows j with
+ *      dq(i, j) <= scan_radius (== is inside);
+ *   3. the candidates get their exact distance df on `full` (the arithmetic of pann_rerank / pann_query_distances, against the
+ *      normalised query with normalize_first); the RESULT of query i is the candidates with df(i, j) <= radius.
+ * radius is in full's units, scan_radius in the copy's: nothing is converted here (parlayann_amd.quantize.scan_radius maps one
+ * to the other through the quantiser's scale).  The result depends on nothing but the inputs.
+ * Output is CSR, as pann_bruteforce_range: out_offsets (nq + 1, always written), the ids of query i ascending and each once in
+ * out_ids[out_offsets[i] .. out_offsets[i + 1]), out_dists (optional) their df, aligned with out_ids.  out_ids == NULL: count
+ * only.  ids_capacity < out_offsets[nq] -> PANN_ERR_OVERFLOW with the offsets valid and ids / dists untouched.  out_cand_total
+ * (optional, ONE host uint64 in both entries): the sum of the candidate counts -- what the chosen scan_radius costs: the call
+ * holds 8 bytes of quant's scratch per candidate.
+ * Status: NULL handles / qparams / offsets / queries, a NaN radius or scan_radius, and everything pann_scan_rerank refuses about
+ * handles, parameters, strides, element types and rows of more than 512 bytes, with its codes; nq == 0 -> PANN_OK.  Nothing is
+ * written on an error, nor with nq == 0.
+ * Device pointers for queries, offsets, ids and dists, launched on `stream`.  The call SYNCHRONISES the stream twice, where a
+ * size must reach the host: after the scan's count pass (the candidate total sizes the scratch) and after the recheck (the match
+ * total is held against ids_capacity); nothing else is read back. */
+int pann_scan_range_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                        uint64_t q_stride_bytes, int normalize_first, float radius, float scan_radius, uint64_t* d_out_offsets,
+                        uint32_t* d_out_ids, float* d_out_dists, uint64_t ids_capacity, uint64_t* out_cand_total, void* stream);
+/* Host pointers: the queries go up in one transfer, the offsets come back in one, ids and dists in a second.  Runs on quant's stream. */
+int pann_scan_range(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                    uint64_t q_stride_bytes, int normalize_first, float radius, float scan_radius, uint64_t* out_offsets, uint32_t* out_ids,
+                    float* out_dists, uint64_t ids_capacity, uint64_t* out_cand_total);
 
 /* ---- masked beam search: results restricted by an allow bitmap, traversal unchanged (DESIGN.md "Masked search") ----
  * allow: ceil(n / 32) uint32 words per row; point i is allowed iff bit (i & 31) of word (i >> 5) is set; bits at positions

@@ -210,6 +210,11 @@ SIGNATURES = {
                                    C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pann_scan_rerank_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
                                        C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # (full, quant, qparams, queries, nq, stride, normalize_first, radius, scan_radius, offsets, ids, dists, ids_capacity, cand_total [, stream])
+    "pann_scan_range": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p]),
+    "pann_scan_range_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,
+                                      C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, u64p, C.c_void_p]),
     # (full, quant, qparams, queries, nq, stride, normalize_first, k, rerank_factor | rows, nrows, stride words, row_of_query |
     #  kind, preds, npreds, group_of_query | max_list_ids, ids, dists, cand_ids, cand_count [, stream])
     "pann_scan_rerank_masked": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(QuantParams), C.c_void_p, C.c_uint64, C.c_uint64, C.c_int,

@@ -2898,14 +2898,10 @@ int pann_batch_search_labeled_rerank(pann_index* full, pann_index* quant, const 
 
 namespace {
 
-// everything pann_scan_rerank* refuses, before anything is enqueued -- the rules of search_rerank_checks where they apply
-int scan_rerank_checks(const char* fn, const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
-                       uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int rerank_factor, const uint32_t* out_ids, const float* out_dists) {
+// what the scan entries refuse about the two handles, the parameters and the query rows (all three non-null handles / parameters)
+int scan_pair_checks(const char* fn, const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                     uint64_t nq, uint64_t q_stride_bytes) {
   const std::string f = fn;
-  if (!full || !quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
-  if (!qparams || !out_ids || !out_dists) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
-  if (k == 0) { set_error(f + ": k must be at least 1"); return PANN_ERR_BAD_ARG; }
-  if (rerank_factor < 1) { set_error(f + ": rerank_factor must be at least 1"); return PANN_ERR_BAD_ARG; }
   const DeviceIndex& fx = full->ix;
   const DeviceIndex& qx = quant->ix;
   if (fx.dtype != PANN_F32) { set_error(f + ": the full-precision index must hold float (PANN_F32) points"); return PANN_ERR_UNSUPPORTED; }
@@ -2926,6 +2922,38 @@ int scan_rerank_checks(const char* fn, const pann_index* full, const pann_index*
   if (q_stride_bytes < 4ull * fx.d || q_stride_bytes % 4 != 0) { set_error(f + ": query stride smaller than a row or not a multiple of 4"); return PANN_ERR_BAD_ARG; }
   if (nq && !queries) { set_error(f + ": null queries"); return PANN_ERR_BAD_ARG; }
   return PANN_OK;
+}
+
+// everything pann_scan_rerank* refuses, before anything is enqueued -- the rules of search_rerank_checks where they apply
+int scan_rerank_checks(const char* fn, const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                       uint64_t nq, uint64_t q_stride_bytes, uint32_t k, int rerank_factor, const uint32_t* out_ids, const float* out_dists) {
+  const std::string f = fn;
+  if (!full || !quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
+  if (!qparams || !out_ids || !out_dists) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
+  if (k == 0) { set_error(f + ": k must be at least 1"); return PANN_ERR_BAD_ARG; }
+  if (rerank_factor < 1) { set_error(f + ": rerank_factor must be at least 1"); return PANN_ERR_BAD_ARG; }
+  return scan_pair_checks(fn, full, quant, qparams, queries, nq, q_stride_bytes);
+}
+
+// ... and pann_scan_range*: the offsets are the one output that must be there
+int scan_range_checks(const char* fn, const pann_index* full, const pann_index* quant, const pann_quant_params* qparams, const float* queries,
+                      uint64_t nq, uint64_t q_stride_bytes, float radius, float scan_radius, const uint64_t* out_offsets) {
+  const std::string f = fn;
+  if (!full || !quant) { set_error(f + ": null index handle"); return PANN_ERR_BAD_ARG; }
+  if (!qparams || !out_offsets) { set_error(f + ": null parameters / outputs"); return PANN_ERR_BAD_ARG; }
+  if (std::isnan(radius) || std::isnan(scan_radius)) { set_error(f + ": radius or scan_radius is NaN"); return PANN_ERR_BAD_ARG; }
+  return scan_pair_checks(fn, full, quant, qparams, queries, nq, q_stride_bytes);
+}
+
+// the count half of pann_scan_range* on device pointers; pieces as the top-k scan chooses them (a piece costs the range form one count)
+int scan_range_count(pann_index* full, pann_index* quant, ScanRangeRequest r, uint64_t* d_offsets, ScanRangeState* s) {
+  const uint32_t ntiles = (uint32_t)((r.nq + 63) / 64);
+  r.nsplit = choose_gt_pieces(quant, ntiles, (double)dense_scan_range_slots(quant->ix), quant->ix.n);
+  return scan_range_count_dev(full->ix, quant->ix, quant->ws_rr, quant->ws2, r, d_offsets, s);
+}
+int scan_range_overflow(const char* fn, uint64_t total, uint64_t ids_capacity) {
+  set_error(std::string(fn) + ": " + std::to_string(total) + " matches, room for " + std::to_string(ids_capacity));
+  return PANN_ERR_OVERFLOW;
 }
 
 uint32_t scan_list_length(const pann_index* quant, uint32_t k, int rerank_factor) {      // c = min(k * rerank_factor, 64, n)
@@ -3161,6 +3189,53 @@ int pann_scan_rerank(pann_index* full, pann_index* quant, const pann_quant_param
   r.out_cand_ids = t.dout<uint32_t>(o_cand); r.out_cand_count = t.dout<uint32_t>(o_cnt); r.stream = t.st;
   if (int rc = scan_rerank_launch(full, quant, r, rerank_factor)) return rc;
   return t.finish();
+}
+
+int pann_scan_range_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,
+                        uint64_t q_stride_bytes, int normalize_first, float radius, float scan_radius, uint64_t* d_out_offsets,
+                        uint32_t* d_out_ids, float* d_out_dists, uint64_t ids_capacity, uint64_t* out_cand_total, void* stream) {
+  const char* fn = "pann_scan_range_dev";
+  if (int rc = scan_range_checks(fn, full, quant, qparams, d_queries, nq, q_stride_bytes, radius, scan_radius, d_out_offsets)) return rc;
+  if (nq == 0) return PANN_OK;
+  if ((uintptr_t)d_queries % 4 != 0) { set_error(std::string(fn) + ": query rows must be 4-byte aligned"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(quant->device);
+  ScanRangeRequest r;
+  r.qparams = qparams; r.queries = d_queries; r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first;
+  r.radius = radius; r.scan_radius = scan_radius; r.stream = stream;
+  ScanRangeState s;
+  if (int rc = scan_range_count(full, quant, r, d_out_offsets, &s)) return rc;
+  if (out_cand_total) *out_cand_total = s.cand_total;
+  if (!d_out_ids) return PANN_OK;                                          // count only
+  if (ids_capacity < s.match_total) return scan_range_overflow(fn, s.match_total, ids_capacity);
+  return scan_range_pack_dev(s, d_out_ids, d_out_dists, stream);
+}
+
+int pann_scan_range(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* queries, uint64_t nq,
+                    uint64_t q_stride_bytes, int normalize_first, float radius, float scan_radius, uint64_t* out_offsets, uint32_t* out_ids,
+                    float* out_dists, uint64_t ids_capacity, uint64_t* out_cand_total) {
+  const char* fn = "pann_scan_range";
+  if (int rc = scan_range_checks(fn, full, quant, qparams, queries, nq, q_stride_bytes, radius, scan_radius, out_offsets)) return rc;
+  if (nq == 0) return PANN_OK;
+  DeviceGuard g(quant->device);
+  HostTrip t(quant);
+  const int i_q = t.in.add(queries, (nq - 1) * q_stride_bytes + 4ull * quant->ix.d);
+  const int o_off = t.out.add(out_offsets, (nq + 1) * 8);
+  if (int rc = t.begin()) return rc;
+  ScanRangeRequest r;
+  r.qparams = qparams; r.queries = (const float*)t.din<uint8_t>(i_q); r.nq = nq; r.qstride = q_stride_bytes; r.normalize_first = normalize_first;
+  r.radius = radius; r.scan_radius = scan_radius; r.stream = t.st;
+  ScanRangeState s;
+  if (int rc = scan_range_count(full, quant, r, t.dout<uint64_t>(o_off), &s)) return rc;
+  if (int rc = t.finish()) return rc;
+  if (out_cand_total) *out_cand_total = s.cand_total;
+  if (!out_ids) return PANN_OK;                                            // count only
+  if (ids_capacity < s.match_total) return scan_range_overflow(fn, s.match_total, ids_capacity);
+  if (s.match_total == 0) return PANN_OK;
+  HostTrip fill(quant);      // a second trip for the ids and distances, now that their number is known (as pann_bruteforce_range)
+  const int o_ids = fill.out.add(out_ids, s.match_total * 4), o_dists = fill.out.add(out_dists, s.match_total * 4);
+  if (int rc = fill.begin()) return rc;
+  if (int rc = scan_range_pack_dev(s, fill.dout<uint32_t>(o_ids), fill.dout<float>(o_dists), fill.st)) return rc;
+  return fill.finish();
 }
 
 int pann_scan_rerank_masked_dev(pann_index* full, pann_index* quant, const pann_quant_params* qparams, const float* d_queries, uint64_t nq,

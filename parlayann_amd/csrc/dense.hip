@@ -1377,6 +1377,159 @@ __global__ void __launch_bounds__(256, 2) dense_scan_mfma_kernel(DenseArgs A, co
   static_assert(!LIST && (PQ == MASK_BITMAP || PQ == MASK_LABELS), "a per-query filter goes with the contiguous B side");
 #include "dense_scan_body.h"
 }
+// ---- the range form of the scan (DESIGN.md "Quantised range scan"): every (row, point) cell with distance <= R.radius, as CSR ----
+// The frame is dense_scan_mfma_kernel's plain form, statement for statement up to the epilogue: A in swizzled LDS for the whole piece,
+// B through the double buffer with the two-step look-ahead, the element kinds' moves and nibble splits (scan_mfma_step), pieces on
+// blockIdx.y.  The epilogue is range_join_mfma_kernel's on the int32 accumulators: per (r, t) one compare, one ballot -- its bits
+// 16 q' .. 16 q' + 15 are row 4 q' + r against columns 16 t .. 16 t + 15, in column order -- and a popcount.  FILL == false counts
+// per (row, piece); after range_join_scan_kernel FILL == true recomputes the same integers and writes the ids of (row, piece) from
+// pos[row][piece] on.  A wave owns its 16 rows for the whole piece, tiles and pieces are ascending ranges: the ids of a row come out
+// ascending without an atomic and without a sort.
+// What the loop waits for: there is no list, no queue and no shared threshold, so nothing in the epilogue is shared between waves.
+// ONE lds_barrier per pipeline step remains, the double buffer's own: it publishes the rows of unit u + 1 (stored during unit u)
+// and retires the reads of unit u's buffer, which unit u + 2's store overwrites in the next step.  A third buffer would take it to
+// one barrier per two steps and 16 KB more LDS: at 512-byte rows that is the second workgroup of a CU.
+struct ScanRangeOut {
+  float radius;
+  uint32_t* counts;            // [na][nsplit], written by the count pass
+  const uint64_t* pos;         // [na * nsplit + 1], the exclusive scan of counts, read by the fill pass
+  uint32_t* out_ids;           // [pos[na * nsplit]]
+};
+template <int DT, bool FILL>
+__global__ void __launch_bounds__(256, 2) dense_scan_range_kernel(DenseArgs A, const int* __restrict__ bnorm, ScanRangeOut R) {
+  constexpr bool L2 = scan_is_l2(DT);
+  extern __shared__ __align__(16) uint8_t smem[];
+  const uint32_t nch = (A.dbytes + 15) / 16;                              // 16-byte chunks that hold data: 1 .. 32 (the launcher checks)
+  const uint32_t nseg = (nch + 15) / 16;
+  uint8_t* Bt0 = smem;                                                    // [2][64][GT_BSTRIDE], slots swizzled (gt_swz)
+  float2* Bm = reinterpret_cast<float2*>(smem + 2 * GT_BT_BYTES);         // [2][64] (|b|^2 bits, id bits)
+  int* An = reinterpret_cast<int*>(Bm + 2 * DT_B);                        // [64] |a|^2 (L2)
+  uint8_t* At = reinterpret_cast<uint8_t*>(An + DT_A);                    // [nseg][64][GT_BSTRIDE], swizzled like B
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, col = lane & 15;
+  const TileGeom g = tile_geom(A.na, A.nb, piece_rows(A.nb, A.nsplit, DT_B));
+  const uint64_t a0 = g.a0, bs = g.bs, be = g.be; const uint32_t na_tile = g.na_tile;
+  const uint32_t ntile = (uint32_t)((be - bs + DT_B - 1) / DT_B);
+  const int r0 = tid >> 4, c = tid & 15;
+  // the A tile -> LDS (rows beyond the tile and bytes beyond the row: zeros), PANN_U8 moved; |a|^2 of the bytes the k steps cover
+#pragma unroll
+  for (int k = 0; k < 4; k++) {
+    int ss = 0;
+    for (uint32_t sg = 0; sg < nseg; sg++) {
+      uint4 v = dense_a_load(A, g, r0 + 16 * k, sg * DT_SEG + c * 16);
+      if (L2 && sg * 16u + (uint32_t)c < nch) ss += scan_chunk_sq<DT>(v);
+      if constexpr (DT == PANN_U8) v = scan_flip7(v);
+      *reinterpret_cast<uint4*>(At + sg * GT_BT_BYTES + gt_swz((uint32_t)(r0 + 16 * k), (uint32_t)c * 16u)) = v;
+    }
+    if constexpr (L2) { ss = group_sum<16>(ss) + scan_pad_sq<DT>(nch); if (c == 0) An[r0 + 16 * k] = ss; }
+  }
+  // a chunk column that holds no data is never staged: it is zeroed here, once, in both buffers
+  const bool cv0 = (uint32_t)c < nch, cv1 = nseg == 2 && 16u + (uint32_t)c < nch;
+#pragma unroll
+  for (int k = 0; k < 8; k++) {
+    if (!((nseg == 2 && (k >> 2)) ? cv1 : cv0))
+      *reinterpret_cast<uint4*>(Bt0 + (k >> 2) * GT_BT_BYTES + gt_swz((uint32_t)(r0 + 16 * (k & 3)), (uint32_t)c * 16u)) = make_uint4(0, 0, 0, 0);
+  }
+  __syncthreads();
+  int an[4] = {0, 0, 0, 0};
+  if constexpr (L2) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) an[r] = An[wave * DT_AW + q * 4 + r];
+  }
+  // rows 4q + r of the wave: matches so far (count pass) / where the next id goes (fill pass); no write lands at or beyond `total`
+  uint32_t cnt[4] = {0, 0, 0, 0};
+  uint64_t wpos[4] = {0, 0, 0, 0};
+  uint64_t total = 0;
+  if constexpr (FILL) {
+    total = R.pos[A.na * A.nsplit];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const uint32_t ar = (uint32_t)(wave * DT_AW + q * 4 + r);
+      if (ar < na_tile) wpos[r] = R.pos[(a0 + ar) * A.nsplit + blockIdx.y];
+    }
+  }
+
+  const uint32_t nunits = ntile * nseg;
+  const uint32_t last_row = (uint32_t)(be - 1);                           // (read only where a load is issued: be > bs there)
+  const uint8_t* cb0 = A.points + min((uint32_t)c, nch - 1u) * 16u;
+  const uint8_t* cb1 = A.points + min(16u + (uint32_t)c, nch - 1u) * 16u;
+  uint4 pre0, pre1, pre2, pre3;
+  int pn = 0;
+  auto unit_bt = [&](uint32_t u) -> uint32_t { return (uint32_t)bs + (nseg == 2 ? (u >> 1) : u) * DT_B; };
+  auto load_pre = [&](uint32_t u) {          // requests only: clamped rows, no branch around a load
+    const uint32_t bt = unit_bt(u);
+    const uint8_t* cb = (nseg == 2 && (u & 1)) ? cb1 : cb0;
+    pre0 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0, last_row) * A.pstride);
+    pre1 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 16u, last_row) * A.pstride);
+    pre2 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 32u, last_row) * A.pstride);
+    pre3 = *reinterpret_cast<const uint4*>(cb + (uint64_t)min(bt + (uint32_t)r0 + 48u, last_row) * A.pstride);
+    if (L2) pn = bnorm[min(bt + (uint32_t)lane, last_row)];
+  };
+  auto store_pre = [&](uint32_t u) {
+    const int buf = (int)(u & 1);
+    gt_store_tile(Bt0 + buf * GT_BT_BYTES, Bm + buf * DT_B, (nseg == 2 && (u & 1)) ? cv1 : cv0, pre0, pre1, pre2, pre3, __int_as_float(pn),
+                  unit_bt(u), be, tid);
+  };
+  if (nunits > 0) { load_pre(0); store_pre(0); load_pre(1); }
+  lds_barrier();
+
+  mf_int4 acc[4];
+  const uint32_t arow = (uint32_t)(wave * DT_AW + col);
+  for (uint32_t u = 0; u < nunits; u++) {
+    const int buf = (int)(u & 1);
+    const uint32_t sg = nseg == 2 ? (u & 1) : 0u;
+    store_pre(u + 1);                                          // (beyond the last step: the piece's last row again, into a dead buffer)
+    load_pre(u + 2);
+    if (sg == 0) {
+#pragma unroll
+      for (int t = 0; t < 4; t++) acc[t] = mf_int4{0, 0, 0, 0};
+    }
+    const uint8_t* Bt = Bt0 + buf * GT_BT_BYTES;
+    const uint8_t* Ap = At + sg * GT_BT_BYTES;
+    const uint32_t nks = (min(16u, nch - sg * 16u) + 3u) / 4u;              // k steps of 64 row bytes that reach data in this segment
+    for (uint32_t ks = 0; ks < nks; ks++) {
+      const uint32_t off = ks * 64u + (uint32_t)q * 16u;
+      uint4 braw[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) braw[t] = *reinterpret_cast<const uint4*>(Bt + gt_swz((uint32_t)(t * 16 + col), off));
+      scan_mfma_step<DT>(*reinterpret_cast<const uint4*>(Ap + gt_swz(arow, off)), braw, acc);
+    }
+    if (sg == nseg - 1) {
+      // ---- epilogue: acc[t][r] = a(row wave*16 + 4q + r) . b(column t*16 + col); a column at or beyond `be` is labelled SENTINEL ----
+      int bn[4]; uint32_t bid[4];
+#pragma unroll
+      for (int t = 0; t < 4; t++) { const float2 m2 = Bm[buf * DT_B + t * 16 + col]; bn[t] = __float_as_int(m2.x); bid[t] = __float_as_uint(m2.y); }
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const bool row_ok = (uint32_t)(wave * DT_AW + q * 4 + r) < na_tile;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+          float dist;
+          if constexpr (L2) dist = (float)(an[r] + bn[t] - 2 * acc[t][r]);
+          else dist = -(float)acc[t][r];
+          const bool inside = row_ok && bid[t] != SENTINEL && dist <= R.radius;
+          const uint64_t mask = __ballot(inside);
+          const uint32_t slice = (uint32_t)(mask >> (16 * q)) & 0xFFFFu;
+          if constexpr (FILL) {
+            const uint64_t p = wpos[r] + __popc(slice & ((1u << col) - 1u));
+            if (inside && p < total) R.out_ids[p] = bid[t];
+            wpos[r] += __popc(slice);
+          } else {
+            cnt[r] += __popc(slice);
+          }
+        }
+      }
+    }
+    lds_barrier();
+  }
+  if constexpr (!FILL) {
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const uint32_t ar = (uint32_t)(wave * DT_AW + q * 4 + r);
+      if (col == 0 && ar < na_tile) R.counts[(a0 + ar) * A.nsplit + blockIdx.y] = cnt[r];
+    }
+  }
+}
+
 // entries of a merged row that hold an id: the length of a row's candidate list under a filter (one wave per row, m <= 64)
 __global__ void __launch_bounds__(256) scan_list_count_kernel(const uint32_t* ids, uint64_t na, uint32_t m, uint32_t* counts) {
   const uint64_t row = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1613,6 +1766,52 @@ int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const D
     hipLaunchKernelGGL(scan_list_count_kernel, dim3((uint32_t)((c.na + 3) / 4)), dim3(256), 0, st, (const uint32_t*)c.out_ids, c.na, c.m, c.out_counts);
     PANN_HIP(hipGetLastError());
   }
+  return PANN_OK;
+}
+
+// ---- the range form (dense_scan_range_kernel): one pass of the radius join of c.na external quantised rows against ALL points ----
+// fill == false: c.counts[row][piece]; fill == true: c.out_ids from c.pos, the exclusive scan of those counts.  c.bnorm (L2 kinds):
+// dense_scan_norms_dev's array.  Same handles as dense_scan_dev (dense_scan_eligible); no synchronisation, no allocation.
+int dense_scan_norms_dev(const DeviceIndex& ix, hipStream_t st, int* d_norm) {
+  const uint32_t nch = (ix.dbytes + 15) / 16;
+  const dim3 ng((uint32_t)((ix.n + 15) / 16));
+  if (ix.n == 0) return PANN_OK;
+  if (ix.dtype == PANN_U8) hipLaunchKernelGGL(scan_norms_kernel<PANN_U8>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, ix.n, d_norm);
+  else if (ix.dtype == PANN_U4) hipLaunchKernelGGL(scan_norms_kernel<PANN_U4>, ng, dim3(256), 0, st, ix.points, ix.pstride, nch, ix.n, d_norm);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+template <int DT>
+static void dense_scan_range_launch(bool fill, dim3 grid, size_t lds, hipStream_t st, const DenseArgs& A, const int* bnorm, const ScanRangeOut& R) {
+  if (fill) launch_lds(dense_scan_range_kernel<DT, true>, grid, dim3(256), lds, st, A, bnorm, R);
+  else launch_lds(dense_scan_range_kernel<DT, false>, grid, dim3(256), lds, st, A, bnorm, R);
+}
+// workgroups of the range form that are resident at once (the fill pass: it holds the positions on top of what the count pass holds)
+uint32_t dense_scan_range_slots(const DeviceIndex& ix) {
+  const void* kern = ix.dtype == PANN_U8   ? reinterpret_cast<const void*>(dense_scan_range_kernel<PANN_U8, true>)
+                     : ix.dtype == PANN_I8 ? reinterpret_cast<const void*>(dense_scan_range_kernel<PANN_I8, true>)
+                     : ix.dtype == PANN_U4 ? reinterpret_cast<const void*>(dense_scan_range_kernel<PANN_U4, true>)
+                                           : reinterpret_cast<const void*>(dense_scan_range_kernel<PANN_I4, true>);
+  const size_t lds = dense_scan_lds(ix);
+  int v = 0;
+  (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, kern, 256, lds) != hipSuccess || v < 1) v = 1;
+  return 256u * (uint32_t)v;
+}
+int dense_scan_range_dev(const DeviceIndex& ix, hipStream_t st, const ScanRangeCall& c, bool fill) {
+  if (!dense_scan_eligible(ix)) { set_error("quantised range scan: unsupported element type or row length"); return PANN_ERR_UNSUPPORTED; }
+  if (c.na == 0) return PANN_OK;
+  DenseArgs A{};
+  A.points = ix.points; A.pstride = ix.pstride; A.dbytes = ix.dbytes;
+  A.a_ext = c.a_ext; A.a_stride = c.a_stride; A.na = c.na; A.nb = ix.n; A.nsplit = c.nsplit;
+  const ScanRangeOut R{c.radius, c.counts, c.pos, c.out_ids};
+  const dim3 grid((uint32_t)((c.na + DT_A - 1) / DT_A), c.nsplit);
+  const size_t lds = dense_scan_lds(ix);
+  if (ix.dtype == PANN_U8) dense_scan_range_launch<PANN_U8>(fill, grid, lds, st, A, c.bnorm, R);
+  else if (ix.dtype == PANN_I8) dense_scan_range_launch<PANN_I8>(fill, grid, lds, st, A, c.bnorm, R);
+  else if (ix.dtype == PANN_U4) dense_scan_range_launch<PANN_U4>(fill, grid, lds, st, A, c.bnorm, R);
+  else dense_scan_range_launch<PANN_I4>(fill, grid, lds, st, A, c.bnorm, R);
+  PANN_HIP(hipGetLastError());
   return PANN_OK;
 }
 

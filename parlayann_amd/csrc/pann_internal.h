@@ -199,6 +199,18 @@ bool dense_scan_eligible(const DeviceIndex& ix);
 // workgroups resident at once, for the choice of c.nsplit; mode: MASK_BITMAP / MASK_LABELS of the per-query form
 uint32_t dense_scan_slots(const DeviceIndex& ix, uint32_t m, bool list = false, int mode = MASK_NONE);
 int dense_scan_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const DenseTopkCall& c);
+// Range form of the scan (DESIGN.md "Quantised range scan"): every point whose integer distance to external row r (the handle's row
+// format, 16-byte aligned, a_stride a multiple of 16), cast to float once, is <= radius.  Two passes over the same arguments around
+// range_join_scan_dev: fill == false writes counts[na][nsplit], fill == true writes the ids of (row, piece), ascending, from
+// pos[row * nsplit + piece] on (pos: the exclusive scan of counts, na * nsplit + 1 entries).  bnorm: dense_scan_norms_dev's n
+// values, read by the L2 kinds only.  Device pointers; nothing is synchronised or allocated.
+struct ScanRangeCall {
+  const uint8_t* a_ext = nullptr; uint64_t a_stride = 0, na = 0; uint32_t nsplit = 1; float radius = 0.0f;
+  const int* bnorm = nullptr; uint32_t* counts = nullptr; const uint64_t* pos = nullptr; uint32_t* out_ids = nullptr;
+};
+int dense_scan_norms_dev(const DeviceIndex& ix, hipStream_t st, int* d_norm);
+uint32_t dense_scan_range_slots(const DeviceIndex& ix);      // workgroups resident at once, for the choice of nsplit
+int dense_scan_range_dev(const DeviceIndex& ix, hipStream_t st, const ScanRangeCall& c, bool fill);
 
 int pivot_split_dev(const DeviceIndex& ix, hipStream_t st, const uint32_t* d_ids, const uint32_t* d_tile_seg,
                     const uint64_t* d_tile_lo, const uint32_t* d_tile_cnt, uint32_t ntiles, const uint32_t* d_pa,
@@ -324,6 +336,8 @@ int range_join_count_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, c
                          float radius, uint32_t nsplit, uint64_t* d_offsets);
 int range_join_fill_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint8_t* d_q, uint64_t q_stride, uint64_t nq,
                         float radius, uint32_t nsplit, uint32_t* d_out_ids);
+// d_pos[0 .. m] = the exclusive 64-bit prefix sum of the m counts d_cnt (d_pos[m]: their total); one workgroup
+int range_join_scan_dev(const uint32_t* d_cnt, uint64_t m, uint64_t* d_pos, hipStream_t st);
 
 // quantize.hip: scalar quantisation of f32 rows (n rows of d floats, row stride in bytes, a multiple of 4)
 size_t quant_scratch_bytes();                                     // device scratch quant_params_dev needs
@@ -386,6 +400,23 @@ struct ScanRerankCall {
   PointFilter per_query;
 };
 int scan_rerank_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace& rr_ws, Workspace& scan_ws, const ScanRerankCall& r);
+// pann_scan_range* (search_rerank.hip, DESIGN.md "Quantised range scan"): the range twin.  scan_range_count_dev prepares the queries,
+// runs both passes of dense_scan_range_dev with r.scan_radius, rechecks the candidates on full with r.radius and leaves the CSR offsets
+// (nq + 1) in d_offsets; it synchronises r.stream TWICE -- for the candidate total, which sizes cand_ws, and for the match total --
+// and reads nothing else back.  scan_range_pack_dev then copies the survivors (and their exact distances) into arrays of
+// s.match_total entries; rr_ws and cand_ws hold the state in between, so nothing else may use them between the two calls.
+struct ScanRangeRequest {
+  const pann_quant_params* qparams = nullptr; const float* queries = nullptr; uint64_t nq = 0, qstride = 0; int normalize_first = 0;
+  float radius = 0.0f, scan_radius = 0.0f; uint32_t nsplit = 1; void* stream = nullptr;
+};
+struct ScanRangeState {
+  const uint64_t* cpos; uint32_t nsplit; const uint64_t* mpos; uint64_t nq;      // candidate segments (cpos[q * nsplit]); the CSR offsets (nq + 1)
+  const uint32_t* cand; const float* cdist;                                      // survivors at the front of their segment, their exact distances
+  uint64_t cand_total, match_total;
+};
+int scan_range_count_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace& rr_ws, Workspace& cand_ws, const ScanRangeRequest& r,
+                         uint64_t* d_offsets, ScanRangeState* s);
+int scan_range_pack_dev(const ScanRangeState& s, uint32_t* d_out_ids, float* d_out_dists, void* stream);
 
 // hcnng_build.hip
 int hcnng_build_dev(const DeviceIndex& ix, Workspace& ws, hipStream_t st, uint32_t num_clusters, uint32_t cluster_size,

@@ -375,6 +375,13 @@ __global__ void __launch_bounds__(256) range_join_offsets_kernel(const uint64_t*
   if (i <= nq) offsets[i] = pos[i * nsplit];
 }
 
+// pos[0 .. m] = the exclusive 64-bit scan of d_cnt[0 .. m), for the other two-pass joins (search_rerank.hip)
+int range_join_scan_dev(const uint32_t* d_cnt, uint64_t m, uint64_t* d_pos, hipStream_t st) {
+  hipLaunchKernelGGL(range_join_scan_kernel, dim3(1), dim3(1024), 0, st, d_cnt, m, d_pos);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+
 template <bool FILL>
 static int range_join_launch(const DeviceIndex& ix, hipStream_t st, const RangeJoinArgs& A, dim3 grid) {
   dispatch_type_metric(ix.dtype, ix.metric, [&](auto dt, auto mt) {

@@ -242,6 +242,72 @@ __global__ void __launch_bounds__(RR_WAVES * PANN_WAVE) rerank_list_kernel(Reran
   }
 }
 
+// ---- the recheck of the range twin (pann_scan_range*, DESIGN.md "Quantised range scan") ----
+// The candidates of query i are the segment [cpos[i * nsplit], cpos[(i + 1) * nsplit]) of cand, ascending.  One wave per query walks
+// it 64 ids at a time: the ids go to LDS, gather_tile scores them on the float rows (the arithmetic of rerank_list_kernel and
+// query_distances_kernel, exact-float-order mode included), lane j takes candidate j's distance back from LDS, and one ballot
+// compacts the survivors (dist <= radius) to the FRONT of the same segment, order kept, their distances alongside in cdist.  A
+// survivor's place is never behind the place it was read from, and a chunk is in LDS before anything of it is overwritten, so the
+// compaction is in place.  mcount[i] = survivors.
+struct RecheckArgs {
+  PointsView pv; uint32_t dbytes;                 // the f32 index
+  const uint8_t* q; uint64_t q_stride;            // the float rows the candidates are scored against
+  const uint64_t* cpos; uint32_t nsplit;
+  uint32_t* cand; float* cdist;
+  uint32_t* mcount; uint64_t nq;
+  float radius;
+  uint32_t qbytes;                                // LDS bytes of one query (0: registers)
+};
+template <int METRIC, int LPC, bool NCH1>
+__global__ void __launch_bounds__(RR_WAVES * PANN_WAVE) range_recheck_kernel(RecheckArgs P) {
+  constexpr int DT = PANN_F32;
+  const int lane = threadIdx.x & (PANN_WAVE - 1);
+  const uint32_t w = threadIdx.x / PANN_WAVE;
+  const uint64_t qi = (uint64_t)blockIdx.x * (blockDim.x / PANN_WAVE) + w;
+  if (qi >= P.nq) return;                          // a whole wave leaves; the waves of a block share no data and no barrier
+  extern __shared__ __align__(16) uint8_t smem[];
+  uint8_t* base = smem + (size_t)w * (P.qbytes + PANN_WAVE * 8);       // per wave: [query, qbytes] [64 candidate ids] [64 distances]
+  uint4* qlds = reinterpret_cast<uint4*>(base);
+  uint32_t* Pl = reinterpret_cast<uint32_t*>(base + P.qbytes);
+  float* Dl = reinterpret_cast<float*>(Pl + PANN_WAVE);
+  const uint64_t lo = P.cpos[qi * P.nsplit], hi = P.cpos[(qi + 1) * P.nsplit];
+  uint64_t kept = 0;
+  if (hi > lo) {                                   // wave-uniform
+    QReg<DT> qreg{};
+    load_query<DT, LPC, NCH1>(P.q + qi * P.q_stride, P.dbytes, P.pv.nch, qreg, qlds, lane);
+    for (uint64_t j0 = lo; j0 < hi; j0 += PANN_WAVE) {
+      const uint32_t mm = (uint32_t)min((uint64_t)PANN_WAVE, hi - j0);
+      if (lane < (int)mm) Pl[lane] = P.cand[j0 + lane];
+      wave_lds_sync();
+      gather_tile<DT, METRIC, LPC, NCH1, 4>(P.pv, qreg, qlds, Pl, mm, lane,
+        [&](bool has, uint32_t ci, uint32_t, float dist) { if (has) Dl[ci] = dist; });
+      wave_lds_sync();
+      const bool in = lane < (int)mm;
+      const float dist = in ? Dl[lane] : 0.0f;
+      const uint32_t id = in ? Pl[lane] : 0u;
+      const bool keep = in && dist <= P.radius;
+      const uint64_t mask = __ballot(keep);
+      if (keep) { const uint64_t p = lo + kept + lanes_below(mask, lane); P.cand[p] = id; P.cdist[p] = dist; }
+      kept += (uint64_t)__popcll(mask);
+      wave_lds_sync();                             // the next chunk overwrites Pl and Dl
+    }
+  }
+  if (lane == 0) P.mcount[qi] = (uint32_t)kept;
+}
+
+// the first offsets[q + 1] - offsets[q] entries of query q's candidate segment -> the caller's CSR (out_dists optional)
+__global__ void __launch_bounds__(256) range_pack_kernel(const uint64_t* __restrict__ cpos, uint32_t nsplit, const uint64_t* __restrict__ offsets,
+                                                         uint64_t nq, const uint32_t* __restrict__ cand, const float* __restrict__ cdist,
+                                                         uint32_t* __restrict__ out_ids, float* __restrict__ out_dists) {
+  for (uint64_t q = blockIdx.x; q < nq; q += gridDim.x) {
+    const uint64_t src = cpos[q * nsplit], dst = offsets[q], m = offsets[q + 1] - dst;
+    for (uint64_t j = threadIdx.x; j < m; j += 256) {
+      out_ids[dst + j] = cand[src + j];
+      if (out_dists) out_dists[dst + j] = cdist[src + j];
+    }
+  }
+}
+
 struct Scratch { uint8_t* qb; uint64_t qb_stride; uint8_t* sk; uint64_t sk_stride; uint8_t* nr; uint64_t nr_stride; uint32_t* fids; uint32_t* fsize; size_t bytes; };
 
 Scratch cut_scratch(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int normalize_first, int use_filter, void* base) {
@@ -258,6 +324,87 @@ Scratch cut_scratch(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int no
 }
 
 }  // namespace
+
+// ---- the range twin (pann_scan_range*, DESIGN.md "Quantised range scan") ----
+// prepare the queries as the calls below do; count pass of the range scan over ALL rows of quant, prefix sum, READ-BACK 1 (the candidate total
+// sizes cand_ws), fill pass, recheck on full's rows, prefix sum of the survivors (the CSR offsets), READ-BACK 2 (the match
+// total, which the caller holds against its capacity).  The stream is synchronised at those two points and nowhere else.
+int scan_range_count_dev(const DeviceIndex& full, const DeviceIndex& quant, Workspace& rr_ws, Workspace& cand_ws, const ScanRangeRequest& r,
+                         uint64_t* d_offsets, ScanRangeState* s) {
+  const uint64_t nq = r.nq;
+  hipStream_t st = (hipStream_t)r.stream;
+  const uint32_t d = full.d;
+  const size_t slots = (size_t)nq * r.nsplit;
+  uint8_t* qb; uint8_t* nr = nullptr; int* bnorm = nullptr; uint32_t* counts; uint64_t* cpos; uint32_t* mcount; uint64_t* mpos;
+  const uint64_t qb_stride = (quant.dbytes + 15) / 16 * 16, nr_stride = ((uint64_t)d * 4 + 15) / 16 * 16;
+  if (int rc = carve_into(rr_ws, 256, [&](Carve& cv) {
+    qb = cv.take<uint8_t>(nq * qb_stride);
+    if (r.normalize_first) nr = cv.take<uint8_t>(nq * nr_stride);
+    if (quant.metric == PANN_L2) bnorm = cv.take<int>(quant.n);
+    counts = cv.take<uint32_t>(slots);
+    cpos = cv.take<uint64_t>(slots + 1);
+    mcount = cv.take<uint32_t>(nq);
+    mpos = cv.take<uint64_t>(nq + 1);
+  })) return rc;
+
+  // ---- 1. the queries, the rows' norms ----
+  const size_t prep_lds = r.normalize_first ? (size_t)d * 4 : 0;
+  hipLaunchKernelGGL(prepare_queries_kernel, dim3((uint32_t)std::min<uint64_t>(nq, PREP_MAX_BLOCKS)), dim3(PANN_WAVE), prep_lds, st,
+                     reinterpret_cast<const uint8_t*>(r.queries), r.qstride, nq, d, r.normalize_first ? 1 : 0, make_qparams(r.qparams), qb,
+                     qb_stride, nr, nr_stride, -1, 0.0f, (uint8_t*)nullptr, (uint64_t)0, 0u);
+  PANN_HIP(hipGetLastError());
+  if (bnorm) { if (int rc = dense_scan_norms_dev(quant, st, bnorm)) return rc; }
+
+  // ---- 2. the candidates: count, scan, size the scratch, fill ----
+  ScanRangeCall c;
+  c.a_ext = qb; c.a_stride = qb_stride; c.na = nq; c.nsplit = r.nsplit; c.radius = r.scan_radius; c.bnorm = bnorm; c.counts = counts; c.pos = cpos;
+  if (int rc = dense_scan_range_dev(quant, st, c, false)) return rc;
+  if (int rc = range_join_scan_dev(counts, slots, cpos, st)) return rc;
+  uint64_t cand_total = 0;
+  PANN_HIP(hipMemcpyAsync(&cand_total, cpos + slots, 8, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  uint32_t* cand; float* cdist;
+  if (int rc = carve_into(cand_ws, 0, [&](Carve& cv) { cand = cv.take<uint32_t>(cand_total); cdist = cv.take<float>(cand_total); })) return rc;
+  c.out_ids = cand;
+  if (cand_total) { if (int rc = dense_scan_range_dev(quant, st, c, true)) return rc; }
+
+  // ---- 3. the recheck on the float rows; the scan of the survivors' counts is the CSR offsets ----
+  RecheckArgs R{};
+  R.pv = PointsView{full.points, full.pstride, full.nch, full.exact}; R.dbytes = full.dbytes;
+  R.q = r.normalize_first ? nr : reinterpret_cast<const uint8_t*>(r.queries);
+  R.q_stride = r.normalize_first ? nr_stride : r.qstride;
+  R.cpos = cpos; R.nsplit = r.nsplit; R.cand = cand; R.cdist = cdist; R.mcount = mcount; R.nq = nq; R.radius = r.radius;
+  R.qbytes = (uint32_t)query_lds_bytes(full);
+  const size_t wave_lds = (size_t)R.qbytes + PANN_WAVE * 8;
+  uint32_t waves = RR_WAVES;
+  while (waves > 1 && waves * wave_lds > 64 * 1024) waves >>= 1;
+  const size_t lds = waves * wave_lds;
+  if (lds > 64 * 1024) { set_error("pann_scan_range: rows too long for the recheck's LDS state"); return PANN_ERR_UNSUPPORTED; }
+#define CALL_RC(DT, MT, L, N1)                                                                                                    \
+  hipLaunchKernelGGL((range_recheck_kernel<MT, L, N1>), dim3((uint32_t)((nq + waves - 1) / waves)), dim3(waves * PANN_WAVE), lds, st, R)
+  if (full.metric == PANN_L2) PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_L2, CALL_RC);
+  else PANN_LAYOUT_SWITCH(full, PANN_F32, PANN_MIPS, CALL_RC);
+#undef CALL_RC
+  PANN_HIP(hipGetLastError());
+  if (int rc = range_join_scan_dev(mcount, nq, mpos, st)) return rc;      // (kept in rr_ws for the pack; the caller's array gets a copy)
+  PANN_HIP(hipMemcpyAsync(d_offsets, mpos, (nq + 1) * 8, hipMemcpyDeviceToDevice, st));
+  uint64_t match_total = 0;
+  PANN_HIP(hipMemcpyAsync(&match_total, mpos + nq, 8, hipMemcpyDeviceToHost, st));
+  PANN_HIP(hipStreamSynchronize(st));
+  *s = ScanRangeState{cpos, r.nsplit, mpos, nq, cand, cdist, cand_total, match_total};
+  return PANN_OK;
+}
+
+// the survivors of the count call before it -> the caller's CSR; d_out_ids / d_out_dists hold s.match_total entries (dists optional)
+int scan_range_pack_dev(const ScanRangeState& s, uint32_t* d_out_ids, float* d_out_dists, void* stream) {
+  if (s.match_total == 0) return PANN_OK;
+  hipLaunchKernelGGL(range_pack_kernel, dim3((uint32_t)std::min<uint64_t>(s.nq, 1u << 16)), dim3(256), 0, (hipStream_t)stream, s.cpos, s.nsplit,
+                     s.mpos, s.nq, s.cand, s.cdist, d_out_ids, d_out_dists);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
+}
+// (These two stand ahead of the older entry points so that their kernels are emitted ahead of the older ones: the object's last
+// kernel stays the last, and tools/compare_kernels.py sees every shipped kernel with the bytes it had.)
 
 size_t search_rerank_scratch_bytes(const DeviceIndex& quant, uint64_t nq, uint32_t beam, int normalize_first, int use_filter) {
   return cut_scratch(quant, nq, beam, normalize_first, use_filter, nullptr).bytes;

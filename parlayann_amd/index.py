@@ -844,6 +844,43 @@ class DeviceIndex:
                                        1 if normalize_first else 0, k, rerank_factor, *mid, vp(d_ids_ptr), vp(d_dists_ptr),
                                        vp(d_cand_ids_ptr), vp(d_cand_count_ptr), vp(stream_ptr)))
 
+    # ---- quantised range scan + exact recheck in one call (DESIGN.md "Quantised range scan") ----
+    def scan_range(self, quant, qparams, queries, radius, scan_radius=None, slack=0.0, normalize_first=False, dists=False):
+        """pann_scan_range on this (float32) index, the range twin of scan_rerank: `queries` are quantised with `qparams` on the
+        device, EVERY row of `quant` (a u8 / i8 / u4 / i4 copy) is scored on the int8 matrix cores, the rows within `scan_radius`
+        (the copy's units; None: quantize.scan_radius(kind, qparams, radius, slack)) are re-scored here, and those within `radius`
+        (this handle's units) are returned as CSR.  Returns a dict: offsets (uint64, nq + 1), ids (uint32, ascending per query),
+        with dists=True dists (float32, the exact distances, aligned with ids), and cand_total (the candidates the scan radius let
+        through, summed over the queries).  A count call, then a fill call, as bruteforce_range."""
+        q = self._queries(queries)
+        nq = len(q)
+        if scan_radius is None:
+            from . import quantize
+            scan_radius = quantize.scan_radius(qparams.kind, qparams, radius, slack)
+        off, total = np.zeros(nq + 1, np.uint64), C.c_uint64(0)
+        head = (self._h, quant.handle, C.byref(qparams), _ptr(q), nq, _row_stride(q), 1 if normalize_first else 0, float(radius),
+                float(scan_radius), _ptr(off))
+        check(self._lib.pann_scan_range(*head, None, None, 0, C.byref(total)))
+        res = {"offsets": off, "ids": np.empty(int(off[nq]), np.uint32)}
+        if dists:
+            res["dists"] = np.empty(int(off[nq]), np.float32)
+        if len(res["ids"]):
+            check(self._lib.pann_scan_range(*head, _ptr(res["ids"]), _ptr(res.get("dists")), len(res["ids"]), C.byref(total)))
+        res["cand_total"] = int(total.value)
+        return res
+
+    def scan_range_dev(self, quant, qparams, d_queries_ptr, nq, q_stride_bytes, radius, scan_radius, d_offsets_ptr, d_ids_ptr=None,
+                       d_dists_ptr=None, ids_capacity=0, normalize_first=False, stream_ptr=None):
+        """pann_scan_range_dev: the same on raw device addresses (integers), enqueued on `stream_ptr`, which the call synchronises
+        twice (the candidate total, the match total).  d_ids_ptr None: count only.  Returns cand_total; too small an ids_capacity
+        raises PannError (PANN_ERR_OVERFLOW) with the offsets written."""
+        vp = lambda a: C.c_void_p(a or None)
+        total = C.c_uint64(0)
+        check(self._lib.pann_scan_range_dev(self._h, quant.handle, C.byref(qparams), vp(d_queries_ptr), nq, q_stride_bytes,
+                                            1 if normalize_first else 0, float(radius), float(scan_radius), vp(d_offsets_ptr), vp(d_ids_ptr),
+                                            vp(d_dists_ptr), int(ids_capacity), C.byref(total), vp(stream_ptr)))
+        return int(total.value)
+
     # ---- robustPrune (vamana/index.h:63-137), batched ----
     def robust_prune_batch(self, owners, cand_ids, cand_offsets, alpha, R, cand_dists=None, add_out_nbrs=True):
         owners = np.ascontiguousarray(owners, dtype=np.uint32)

@@ -157,6 +157,32 @@ def mips_i4_translate(x, max_val):
     return mips_i8_translate(x, max_val, rng=15)
 
 
+def scan_radius(kind, params, radius, slack=0.0):
+    """A radius in the float rows' units -> the same radius in the units of the quantised copy's own distance, for
+    DeviceIndex.scan_range.  The quantisers map x to round(x * s) (minus an offset that L2 does not see), so a distance of the
+    copy is about S times the float distance, with
+      euclid_u8 / euclid_u4   s = params.slope,            S = s * s        (squared L2)
+      mips_i8                 s = 127 / params.max_val,    S = s * s        (minus the dot product)
+      mips_i4                 s = 7 / params.max_val,      S = 256 * s * s  (the four-bit distance is -256 x the nibble dot product)
+    and the result is r = radius * S widened by slack: r + slack * |r| (a MIPS radius is usually negative; widening moves it up).
+    slack = 0 under parameters that quantise integer rows to themselves (slope 1, max_val 127 / 7) gives the radius at which the
+    copy's distance and the float distance compare one to one: radius itself, 256 * radius for mips_i4.  Rounding moves a
+    coordinate by up to half a step, so real-valued rows need slack > 0 for full recall; tools/range_gt_time.py --scan measures it."""
+    from . import _capi
+    from .index import quant_kind
+    kind = quant_kind(kind)
+    if kind in (_capi.PANN_QUANT_EUCLID_U8, _capi.PANN_QUANT_EUCLID_U4):
+        scale = float(params.slope) ** 2
+    elif kind == _capi.PANN_QUANT_MIPS_I8:
+        scale = (127.0 / float(params.max_val)) ** 2
+    elif kind == _capi.PANN_QUANT_MIPS_I4:
+        scale = 256.0 * (7.0 / float(params.max_val)) ** 2
+    else:
+        raise ValueError("scan_radius: the scan takes the euclid_u8, mips_i8, euclid_u4 and mips_i4 kinds")
+    r = float(radius) * scale
+    return r + float(slack) * abs(r) if np.isfinite(r) else r
+
+
 def quant_row_bytes(kind, dims):
     """bytes of one translated row: dims, or ceil(dims / 2) for the four-bit kinds"""
     from . import _capi
