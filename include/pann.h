@@ -271,6 +271,31 @@ int pann_vamana_build(pann_index* idx, uint32_t R, uint32_t L, double alpha, int
 int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint32_t degree,
                                    uint64_t seed, int sort_neighbors, pann_build_stats* stats);
 
+/* ---- label-aware Vamana build (DESIGN.md "Label-aware build"; FilteredVamana, Gollapudi et al. 2023) ----
+ * The handle's label word of a point (pann_index_set_labels) is read as a set of up to 32 labels.  One labeled batch: every
+ * batch point p is searched for with beam L by the labeled search under PANN_PRED_ANY with a = label[p], from the start ids of
+ * its labels: `starts` is a table of 32 rows of nstarts ids, row b for label bit b (typically pann_filter_medoids_labeled over
+ * the 32 single-bit predicates); a point's starts are the rows of its set bits in bit order, without repeats, at most
+ * min(64, max(L / 2, 1), nstarts * the most bits any label word of the handle has set), padded with the first.  Its candidates
+ * are the visited points and its current row that share a label with it.  They are pruned by the filtered rule: in ascending
+ * (distance, id) order the first live candidate p* enters the row, and a live p' behind it is removed iff
+ * alpha * d(p*, p') <= d(p, p') and (label[p'] & label[p] & ~label[p*]) == 0; R picks at most.  Rows are written and reverse
+ * edges added as by pann_vamana_insert_batch, an over-full row being re-pruned by the same rule with its owner's label word:
+ * every edge the call adds joins two points whose label words intersect.  With all label words equal and every row of
+ * `starts` naming `start`, the rows are those of pann_vamana_insert_batch / pann_vamana_build, bit for bit.
+ * PANN_ERR_BAD_ARG, graph untouched: a handle without labels, nstarts outside [1, 64], a start id >= n anywhere in the table,
+ * a batch point whose label word is 0, and what pann_vamana_insert_batch refuses.  Four-bit and FP8 handles:
+ * PANN_ERR_UNSUPPORTED.  The _dev form takes batch ids and the table in device memory (the ids are not validated, as in
+ * pann_vamana_search_prune_dev) and runs, like the host forms, on the handle's stream; all return after it has drained.
+ * pann_vamana_build_labeled is pann_vamana_build -- same permutation, same prefix-doubling schedule, alpha = 1.0 on all but the
+ * last pass -- with every batch a labeled one. */
+int pann_vamana_insert_batch_labeled(pann_index* idx, const uint32_t* batch_ids, uint64_t m, const uint32_t* starts, uint32_t nstarts,
+                                     uint32_t R, uint32_t L, double alpha, pann_build_stats* stats);
+int pann_vamana_insert_batch_labeled_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, const uint32_t* d_starts,
+                                         uint32_t nstarts, uint32_t R, uint32_t L, double alpha, pann_build_stats* stats);
+int pann_vamana_build_labeled(pann_index* idx, const uint32_t* starts, uint32_t nstarts, uint32_t R, uint32_t L, double alpha,
+                              int num_passes, uint64_t seed, int sort_neighbors, pann_build_stats* stats);
+
 /* The two phases of one batch on DEVICE pointers -- the seam of the multi-GPU build (SURVEY.md section 8e row 3;
  * parlayann_amd/distributed.py): with the points and the graph replicated, every rank runs phase A on its slice of the
  * batch, the slices' rows are all-gathered (ONE collective per batch, m x R x 4 bytes), and every rank applies the rows of

@@ -141,6 +141,12 @@ SIGNATURES = {
                                                  C.c_int, C.c_void_p]),
     "pann_vamana_build": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_int, C.c_uint64, C.c_int,
                                     C.POINTER(BuildStats)]),
+    "pann_vamana_insert_batch_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                   C.c_uint32, C.c_double, C.POINTER(BuildStats)]),
+    "pann_vamana_insert_batch_labeled_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                       C.c_uint32, C.c_double, C.POINTER(BuildStats)]),
+    "pann_vamana_build_labeled": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, C.c_int,
+                                            C.c_uint64, C.c_int, C.POINTER(BuildStats)]),
     "pann_vamana_search_prune_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32,
                                                C.c_double, C.c_void_p, C.POINTER(BuildStats)]),
     "pann_vamana_apply_rows_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_double,

@@ -79,6 +79,7 @@ struct pann_index {
   Workspace sketch_buf;         // attached bit sketch (pann_index_attach_sketch): ix.sketch points into it
   pann_sketch_params sk_params{};   // ... and the parameters it was made with (the fused rerank sketches its queries with them)
   Workspace labels_buf;         // one label word per point (pann_index_set_labels): ix.labels points into it
+  uint32_t label_maxbits = 0;   // the most bits any label word has set, for the start rows of a labeled insert; 0: not known (every label writer resets it)
   Workspace label_row;          // pann_bruteforce_knn_labeled*, one predicate: its bitmap row, expanded on the device
   // pann_bruteforce_knn_*_grouped* (grouped_knn_run): the sorted queries and counts; the plan; a chunk's bitmap rows and block
   // counts; a chunk's query slab and staged results; the read-back and the plan on the host
@@ -390,6 +391,7 @@ int pann_index_set_labels(pann_index* idx, uint64_t first_row, const uint32_t* l
   if (int rc = label_range_checks(idx, "pann_index_set_labels", first_row, labels, nrows)) return rc;
   DeviceGuard g(idx->device);
   if (int rc = ensure_labels(idx)) return rc;
+  idx->label_maxbits = 0;
   PANN_HIP(hipStreamSynchronize(idx->stream));                  // no search may be reading the labels being replaced
   if (nrows) PANN_HIP(hipMemcpy(idx->labels_buf.as<uint32_t>() + first_row, labels, (size_t)nrows * 4, hipMemcpyHostToDevice));
   return PANN_OK;
@@ -399,6 +401,7 @@ int pann_index_set_labels_dev(pann_index* idx, uint64_t first_row, const uint32_
   if (int rc = label_range_checks(idx, "pann_index_set_labels_dev", first_row, d_labels, nrows)) return rc;
   DeviceGuard g(idx->device);
   if (int rc = ensure_labels(idx)) return rc;
+  idx->label_maxbits = 0;
   if (nrows) PANN_HIP(hipMemcpyAsync(idx->labels_buf.as<uint32_t>() + first_row, d_labels, (size_t)nrows * 4, hipMemcpyDeviceToDevice, idx->stream));
   return PANN_OK;
 }
@@ -416,7 +419,7 @@ int pann_index_drop_labels(pann_index* idx) {
   if (int rc = check_idx(idx, "pann_index_drop_labels")) return rc;
   DeviceGuard g(idx->device);
   PANN_HIP(hipStreamSynchronize(idx->stream));
-  idx->ix.labels = nullptr;
+  idx->ix.labels = nullptr; idx->label_maxbits = 0;
   idx->labels_buf.release();
   return PANN_OK;
 }
@@ -1271,11 +1274,9 @@ int pann_vamana_build_single_batch(pann_index* idx, uint32_t R, uint32_t L, doub
   return PANN_OK;
 }
 
-int pann_vamana_build(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint64_t seed,
-                      int sort_neighbors, pann_build_stats* stats) {
-  if (int rc = check_idx_full(idx, "pann_vamana_build")) return rc;
-  if (L == 0 || L > 65536 || num_passes < 1) { set_error("pann_vamana_build: bad L / num_passes"); return PANN_ERR_BAD_ARG; }
-  DeviceGuard g(idx->device);
+// the passes of pann_vamana_build; ls: every batch is a labeled one (pann_vamana_build_labeled), null: the plain build
+static int vamana_build_passes(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint64_t seed,
+                               int sort_neighbors, pann_build_stats* stats, const LabeledStarts* ls) {
   const uint64_t n = idx->ix.n;
   // (generated into the handle's pinned staging: no first-touch page faults per build -- they cost more than the shuffle -- and a
   // DMA transfer without a bounce buffer)
@@ -1307,13 +1308,99 @@ int pann_vamana_build(pann_index* idx, uint32_t R, uint32_t L, double alpha, int
       }
       if (int rc = insert_batch_dev(idx->ix, idx->ws2, idx->ws3, idx->ws, idx->ws4, idx->stream, d_perm + floor,
                                     (uint32_t)(ceiling - floor), 0u /* set_start(): vertex 0, :148 */, R, L, a,
-                                    &idx->vcap, stats))
+                                    &idx->vcap, stats, ls))
         return rc;
       inc++;
     }
   }
   if (sort_neighbors) { idx->ix.codes_valid = 0; return sort_neighbors_dev(idx->ix, idx->stream); }   // :180-185
   return PANN_OK;
+}
+
+int pann_vamana_build(pann_index* idx, uint32_t R, uint32_t L, double alpha, int num_passes, uint64_t seed,
+                      int sort_neighbors, pann_build_stats* stats) {
+  if (int rc = check_idx_full(idx, "pann_vamana_build")) return rc;
+  if (L == 0 || L > 65536 || num_passes < 1) { set_error("pann_vamana_build: bad L / num_passes"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  return vamana_build_passes(idx, R, L, alpha, num_passes, seed, sort_neighbors, stats, nullptr);
+}
+
+// ---- label-aware build (DESIGN.md "Label-aware build") ----
+
+// the refusals of the three labeled entries that need no device work; nothing is allocated or written when one fails
+static int labeled_build_checks(const pann_index* idx, const char* fn, const uint32_t* starts, uint32_t nstarts, uint32_t L) {
+  if (int rc = check_idx_full(idx, fn)) return rc;
+  const std::string f = fn;
+  if (!idx->ix.labels) { set_error(f + ": the handle has no labels (pann_index_set_labels)"); return PANN_ERR_BAD_ARG; }
+  if (!starts || nstarts == 0 || nstarts > 64) { set_error(f + ": starts must be 32 rows of nstarts ids, nstarts in [1, 64]"); return PANN_ERR_BAD_ARG; }
+  if (L == 0 || L > 65536) { set_error(f + ": L out of range"); return PANN_ERR_BAD_ARG; }
+  return PANN_OK;
+}
+
+// The start ids every query of a labeled batch gets: those of the most labels one point carries, within what the search takes
+// (64, and half the beam: a row of starts is padded with repeats, which must not fill the frontier).  The bit count is worked out
+// once per labelling and kept on the handle.
+static int labeled_starts(pann_index* idx, const uint32_t* d_table, uint32_t nstarts, uint32_t L, LabeledStarts* ls) {
+  if (!idx->label_maxbits) {
+    if (int rc = idx->params_scratch.ensure(256)) return rc;
+    if (int rc = label_maxbits_dev(idx->ix, idx->stream, idx->params_scratch.as<uint32_t>())) return rc;
+    PANN_HIP(hipMemcpyAsync(&idx->label_maxbits, idx->params_scratch.buf, 4, hipMemcpyDeviceToHost, idx->stream));
+    PANN_HIP(hipStreamSynchronize(idx->stream));
+    if (!idx->label_maxbits) { set_error("labeled vamana insert: every label word is 0; nothing was changed"); return PANN_ERR_BAD_ARG; }
+  }
+  const uint32_t cap = std::min<uint32_t>(64, std::max<uint32_t>(L / 2, 1));
+  *ls = LabeledStarts{d_table, nstarts, std::min<uint32_t>(idx->label_maxbits * nstarts, cap)};
+  return PANN_OK;
+}
+
+int pann_vamana_insert_batch_labeled_dev(pann_index* idx, const uint32_t* d_batch_ids, uint64_t m, const uint32_t* d_starts,
+                                         uint32_t nstarts, uint32_t R, uint32_t L, double alpha, pann_build_stats* stats) {
+  if (int rc = labeled_build_checks(idx, "pann_vamana_insert_batch_labeled_dev", d_starts, nstarts, L)) return rc;
+  if (m == 0) return PANN_OK;
+  if (!d_batch_ids || m > 0xFFFFFFF0ull) { set_error("pann_vamana_insert_batch_labeled_dev: null batch, or batch too large"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  LabeledStarts ls;
+  if (int rc = labeled_starts(idx, d_starts, nstarts, L, &ls)) return rc;
+  if (int rc = ensure_filter_codes(idx, L)) return rc;
+  if (idx->vcap < default_vcap(L)) idx->vcap = default_vcap(L);
+  return insert_batch_dev(idx->ix, idx->ws2, idx->ws3, idx->ws, idx->ws4, idx->stream, d_batch_ids, (uint32_t)m, 0u, R, L, alpha,
+                          &idx->vcap, stats, &ls);
+}
+
+int pann_vamana_insert_batch_labeled(pann_index* idx, const uint32_t* batch_ids, uint64_t m, const uint32_t* starts, uint32_t nstarts,
+                                     uint32_t R, uint32_t L, double alpha, pann_build_stats* stats) {
+  if (int rc = labeled_build_checks(idx, "pann_vamana_insert_batch_labeled", starts, nstarts, L)) return rc;
+  if (m == 0) return PANN_OK;
+  if (!batch_ids || m > 0xFFFFFFF0ull) { set_error("pann_vamana_insert_batch_labeled: null batch, or batch too large"); return PANN_ERR_BAD_ARG; }
+  for (uint64_t i = 0; i < m; i++)
+    if (batch_ids[i] >= idx->ix.n) {
+      set_error("ERROR: invalid point " + std::to_string(batch_ids[i]) + " given to batch_insert"); return PANN_ERR_BAD_ARG;
+    }
+  DeviceGuard g(idx->device);
+  HostTrip t(idx);
+  const int i_starts = t.in.add(starts, (size_t)32 * nstarts * 4), i_batch = t.in.add(batch_ids, m * 4);
+  if (int rc = t.begin()) return rc;
+  LabeledStarts ls;
+  if (int rc = labeled_starts(idx, t.din<uint32_t>(i_starts), nstarts, L, &ls)) return rc;
+  if (int rc = ensure_filter_codes(idx, L)) return rc;
+  if (idx->vcap < default_vcap(L)) idx->vcap = default_vcap(L);
+  if (int rc = insert_batch_dev(idx->ix, idx->ws2, idx->ws3, idx->ws, idx->ws4, idx->stream, t.din<uint32_t>(i_batch), (uint32_t)m, 0u, R, L,
+                                alpha, &idx->vcap, stats, &ls)) return rc;
+  return t.finish();
+}
+
+int pann_vamana_build_labeled(pann_index* idx, const uint32_t* starts, uint32_t nstarts, uint32_t R, uint32_t L, double alpha,
+                              int num_passes, uint64_t seed, int sort_neighbors, pann_build_stats* stats) {
+  if (int rc = labeled_build_checks(idx, "pann_vamana_build_labeled", starts, nstarts, L)) return rc;
+  if (num_passes < 1) { set_error("pann_vamana_build_labeled: bad num_passes"); return PANN_ERR_BAD_ARG; }
+  DeviceGuard g(idx->device);
+  HostTrip t(idx);
+  const int i_starts = t.in.add(starts, (size_t)32 * nstarts * 4);
+  if (int rc = t.begin()) return rc;
+  PANN_HIP(hipStreamSynchronize(idx->stream));      // the table is up: the permutation is generated into the same pinned staging
+  LabeledStarts ls;
+  if (int rc = labeled_starts(idx, t.din<uint32_t>(i_starts), nstarts, L, &ls)) return rc;
+  return vamana_build_passes(idx, R, L, alpha, num_passes, seed, sort_neighbors, stats, &ls);
 }
 
 

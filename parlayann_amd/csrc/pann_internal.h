@@ -154,20 +154,24 @@ void choose_point_layout(uint32_t dbytes, uint32_t* lpc, uint32_t* nch);
 inline uint32_t launch_slice_blocks(uint32_t threads) { return (1u << 31) / threads; }
 
 // vamana_build.hip
+// A labeled batch (DESIGN.md "Label-aware build"): d_table is the caller's [32][nstarts] start ids on the device, one row per label
+// bit; width the start ids every query of the batch gets (<= 64 and <= L).  Null where it is optional: the plain insert.
+struct LabeledStarts { const uint32_t* d_table; uint32_t nstarts, width; };
+int label_maxbits_dev(const DeviceIndex& ix, hipStream_t st, uint32_t* d_out);      // *d_out = the most set bits of any label word
 int robust_prune_batch_host(const DeviceIndex& ix, Workspace& ws, hipStream_t st, const uint32_t* owners,
                             uint64_t m, const uint32_t* cand_ids, const float* cand_dists,
                             const uint64_t* cand_offsets, double alpha, uint32_t R, int add_out_nbrs,
                             uint32_t* out_rows, uint32_t* out_dist_cmps);
 int insert_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, Workspace& search_ws, Workspace& rows_ws, hipStream_t st,
                      const uint32_t* d_batch, uint32_t m, uint32_t start, uint32_t R, uint32_t L, double alpha,
-                     uint32_t* vcap_io, pann_build_stats* stats);
+                     uint32_t* vcap_io, pann_build_stats* stats, const LabeledStarts* ls = nullptr);
 // the two phases of a batch (vamana_build.hip): A reads the graph and yields rows for the points given, B applies the
 // rows of the whole batch; d_rows is m x R uint32, SENTINEL padded
 int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& search_ws, hipStream_t st, const uint32_t* d_batch,
                             uint32_t m, uint32_t start, uint32_t R, uint32_t L, double alpha, uint32_t* vcap_io,
-                            uint32_t* d_rows, pann_build_stats* stats);
+                            uint32_t* d_rows, pann_build_stats* stats, const LabeledStarts* ls = nullptr);
 int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, hipStream_t st, const uint32_t* d_batch, uint32_t m,
-                          const uint32_t* d_rows, uint32_t R, double alpha, pann_build_stats* stats);
+                          const uint32_t* d_rows, uint32_t R, double alpha, pann_build_stats* stats, const uint32_t* labels = nullptr);
 int sort_neighbors_dev(const DeviceIndex& ix, hipStream_t st);
 // robustPrune, id-only form without the owner's out-neighbours, over a device CSR slab of candidate ids (vamana_build.hip);
 // d_rows: m x R uint32, SENTINEL padded; d_dc is accumulated.  Nothing reaches the graph.

@@ -351,6 +351,269 @@ __global__ void __launch_bounds__(PANN_WAVE) prune_count_tail_kernel(GreedyArgs 
   if (lane == 0) A.dcmps[oi] += live;
 }
 
+// ---- label-aware build (DESIGN.md "Label-aware build") ----
+// The greedy prune under the FilteredVamana rule: with Fp the owner's label word, a candidate that shares no label with the owner
+// (label & Fp == 0) is no candidate, and a pick p* removes a live p' behind it iff alpha * d(p*,p') <= d(p,p') AND p* carries every
+// label p' shares with the owner: (label[p'] & Fp & ~label[p*]) == 0.  Same work split, same pick chain and same float test as
+// prune_greedy_kernel; every candidate's word is loaded ONCE, while the list is de-duplicated, masked with Fp and kept beside its
+// key in LDS (Ls), so that the label test of a pass is one and-not per lane against a scalar, inside the kill test the distance
+// compare already sits in: no pass and no round trip is added to the chain of picks.  Lists above kcap walk the HBM copy and read
+// the label array instead.  With all label words equal every test passes and the kernel returns what prune_greedy_kernel returns.
+struct LabeledGreedyArgs { GreedyArgs g; const uint32_t* labels; };
+
+// A pick's vector as the wave's query.  A row of the handle is 16-byte aligned and zero padded to its stride, which the lanes'
+// chunks cover exactly: plain 16-byte loads, none of load_query's byte-wise paths for an external row (they cost it scratch).
+template <int DT, int LPC, bool NCH1>
+__device__ __forceinline__ void load_pick(const PointsView& pv, uint32_t id, QReg<DT>& qreg, uint4* qlds, int lane) {
+  const uint4* row = reinterpret_cast<const uint4*>(pv.points + (uint64_t)id * pv.pstride);
+  if constexpr (NCH1) qreg = make_qreg<DT>(row[lane % LPC]);
+  else for (uint32_t j = lane; j < pv.nch * LPC; j += PANN_WAVE) qlds[j] = row[j];
+}
+
+template <int DT, int METRIC, int LPC, bool NCH1>
+__global__ void __launch_bounds__(PANN_WAVE, PANN_PRUNE_MINWAVES) prune_greedy_labeled_kernel(LabeledGreedyArgs LA) {
+  const GreedyArgs& A = LA.g;
+  const int lane = threadIdx.x;
+  const uint32_t oi = A.order ? A.order[blockIdx.x] : blockIdx.x;
+  __shared__ uint32_t Pl[PANN_WAVE];    // live candidate ids of the current tile
+  __shared__ uint32_t Pp[PANN_WAVE];    // their positions in the segment
+  __shared__ float Pd[PANN_WAVE];       // their distance to p
+  __shared__ uint32_t Pq[PANN_WAVE];    // their labels & Fp
+  extern __shared__ __align__(16) uint8_t smem[];
+  uint4* qlds = reinterpret_cast<uint4*>(smem);
+  uint32_t* Out = reinterpret_cast<uint32_t*>(qlds + (NCH1 ? 0 : PANN_PRUNE_PB * A.pv.nch * LPC));   // [R rounded to 4] selected neighbours
+  uint64_t* Ks = reinterpret_cast<uint64_t*>(Out + ((A.R + 3) & ~3u));                                // [kcap] the list, when it fits
+  uint32_t* Ls = reinterpret_cast<uint32_t*>(Ks + A.kcap);                                            // [kcap] label & Fp of every entry
+  const uint32_t p = A.owners[oi];
+  const uint32_t Fp = (uint32_t)__builtin_amdgcn_readfirstlane((int)LA.labels[p]);
+  uint64_t* K = A.keys + A.seg_begin[oi];
+  const uint32_t n = A.seg_end[oi] - A.seg_begin[oi];
+  const bool in_lds = n <= A.kcap;
+  auto ldk = [&](uint32_t i) -> uint64_t { return in_lds ? Ks[i] : ld_key(K + i); };
+  auto stk = [&](uint32_t i, uint64_t v) { if (in_lds) Ks[i] = v; else st_key(K + i, v); };
+  auto ldl = [&](uint32_t i, uint32_t id) -> uint32_t { return in_lds ? Ls[i] : (LA.labels[id] & Fp); };   // id: a live entry's
+
+  // std::unique by id, and the candidates that share no label with the owner leave with the repeats
+  uint32_t carry = SENTINEL;
+  for (uint32_t i0 = 0; i0 < n; i0 += PANN_WAVE) {
+    const uint32_t i = i0 + lane;
+    uint64_t k = i < n ? K[i] : KEY_INF;
+    const uint32_t myid = key_id(k);
+    const uint32_t lab = i < n ? (LA.labels[myid] & Fp) : 0u;
+    uint32_t previd = __shfl_up(myid, 1);
+    if (lane == 0) previd = carry;
+    carry = __shfl(myid, PANN_WAVE - 1);
+    if (i < n && (myid == previd || lab == 0u)) k = (k & 0xFFFFFFFF00000000ull) | SENTINEL;
+    if (i < n) { stk(i, k); if (in_lds) Ls[i] = lab; }
+  }
+  if (!in_lds) __builtin_amdgcn_s_waitcnt(0);
+  __syncthreads();
+
+  uint32_t nsel = 0, dc = 0;
+  constexpr int PB = PANN_PRUNE_PB;
+  __shared__ float Dd[PB][PANN_WAVE];
+  const uint32_t qstride4 = NCH1 ? 0u : A.pv.nch * LPC;
+  if (!A.pv.exact) {      // PB speculative picks per pass, as prune_greedy_kernel
+    uint32_t idx = 0;
+    while (idx < n && nsel < A.R) {
+      const uint32_t wi = idx + lane;
+      const uint32_t idw = wi < n ? key_id(ldk(wi)) : SENTINEL;
+      const uint32_t labw = (idw != SENTINEL) ? ldl(wi, idw) : 0u;
+      uint64_t pm = __ballot(idw != SENTINEL && idw != p);
+      if (pm == 0ull) { idx += PANN_WAVE; continue; }
+      uint32_t ppos[PB], pid[PB], plab[PB], plast = 0;      // plast: position of the last pick (an index by nb would cost a stack array)
+      int nb = 0;
+      const int room = (int)min((uint32_t)PB, A.R - nsel);
+#pragma unroll
+      for (int b = 0; b < PB; b++) {
+        ppos[b] = 0; pid[b] = 0; plab[b] = 0;
+        if (b < room && pm) {
+          const int L = __ffsll((unsigned long long)pm) - 1;
+          pm &= pm - 1;
+          ppos[b] = idx + (uint32_t)L; pid[b] = (uint32_t)__builtin_amdgcn_readlane((int)idw, L);
+          plab[b] = (uint32_t)__builtin_amdgcn_readlane((int)labw, L); nb = b + 1; plast = ppos[b];
+        }
+      }
+      QReg<DT> qreg[PB];
+      __syncthreads();
+#pragma unroll
+      for (int b = 0; b < PB; b++) {
+        const uint32_t src = b < nb ? pid[b] : pid[0];                      // unused slots re-read pick 0 (uniform code)
+        load_pick<DT, LPC, NCH1>(A.pv, src, qreg[b], qlds + b * qstride4, lane);
+      }
+      __syncthreads();
+      bool sel[PB], kills[PB];
+#pragma unroll
+      for (int b = 0; b < PB; b++) { sel[b] = false; kills[b] = false; }
+      bool first_tile = true;
+      const uint32_t nsel0 = nsel;
+      for (uint32_t t0 = ppos[0] + 1; t0 < n; t0 += PANN_WAVE) {
+        const uint32_t i = t0 + lane;
+        const uint64_t k = i < n ? ldk(i) : KEY_INF;
+        const bool live = (i < n) && (key_id(k) != SENTINEL);
+        const uint64_t lm = __ballot(live);
+        const uint32_t mm = __popcll(lm);
+        if (mm == 0) continue;
+        if (live) {
+          const uint32_t at = lanes_below(lm, lane);
+          Pl[at] = key_id(k); Pp[at] = i; Pd[at] = key_dist(k); Pq[at] = ldl(i, key_id(k));
+        }
+        __syncthreads();
+        gather_tile_multi<DT, METRIC, LPC, NCH1, PB>(A.pv, qreg, qlds, qstride4, Pl, mm, lane,
+          [&](bool has, uint32_t ci, uint32_t, const float (&d)[PB]) {
+            if (has) {
+#pragma unroll
+              for (int b = 0; b < PB; b++) Dd[b][ci] = d[b];
+            }
+          });
+        __syncthreads();
+        const bool me = lane < (int)mm;
+        const uint32_t mypos = me ? Pp[lane] : 0u;
+        const float dpp = me ? Pd[lane] : 0.0f;
+        const uint32_t mylab = me ? Pq[lane] : 0u;
+        float dl[PB];
+#pragma unroll
+        for (int b = 0; b < PB; b++) dl[b] = Dd[b][lane];
+        if (first_tile) {   // which speculative picks survive the earlier ones: the rule, on scalars
+          first_tile = false;
+          sel[0] = true; nsel++; kills[0] = nsel < A.R;
+          bool stop = nsel == A.R;
+#pragma unroll
+          for (int j = 1; j < PB; j++) {
+            if (j < nb && !stop) {
+              const int Lj = __ffsll((unsigned long long)__ballot(me && mypos == ppos[j])) - 1;
+              const float dppj = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(dpp), Lj));
+              bool dead = false;
+#pragma unroll
+              for (int i2 = 0; i2 < j; i2++) {
+                if (kills[i2]) {
+                  const float dij = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)__float_as_uint(dl[i2]), Lj));
+                  dead = dead || ((plab[j] & ~plab[i2]) == 0u && A.alpha * (double)dij <= (double)dppj);
+                }
+              }
+              if (!dead) { sel[j] = true; nsel++; kills[j] = nsel < A.R; stop = nsel == A.R; }
+            }
+          }
+        }
+        bool alive = me;
+#pragma unroll
+        for (int j = 0; j < PB; j++) {
+          if (kills[j]) {
+            const bool elig = alive && mypos > ppos[j];
+            dc += (uint32_t)__popcll(__ballot(elig));
+            if (elig && (mylab & ~plab[j]) == 0u && A.alpha * (double)dl[j] <= (double)dpp) alive = false;
+          }
+        }
+        if (me && !alive) stk(mypos, ((uint64_t)f2ord(dpp) << 32) | SENTINEL);
+        __syncthreads();
+      }
+      if (first_tile) { sel[0] = true; nsel++; }
+      if (lane == 0) {
+        uint32_t at = nsel0;
+#pragma unroll
+        for (int j = 0; j < PB; j++) if (sel[j]) Out[at++] = pid[j];
+      }
+      idx = plast + 1;
+      if (!in_lds) __builtin_amdgcn_s_waitcnt(0);
+    }
+  } else {                // exact float order: one pick at a time
+    for (uint32_t idx = 0; idx < n && nsel < A.R; idx++) {
+      const uint32_t ps = key_id(ldk(idx));
+      if (ps == p || ps == SENTINEL) continue;
+      if (lane == 0) Out[nsel] = ps;
+      nsel++;
+      if (nsel == A.R) break;
+      const uint32_t labs = ldl(idx, ps);
+      QReg<DT> qreg{};
+      __syncthreads();
+      load_pick<DT, LPC, NCH1>(A.pv, ps, qreg, qlds, lane);
+      __syncthreads();
+      for (uint32_t t0 = idx + 1; t0 < n; t0 += PANN_WAVE) {
+        const uint32_t i = t0 + lane;
+        uint64_t k = KEY_INF;
+        if (i < n) k = ldk(i);
+        const bool live = (i < n) && (key_id(k) != SENTINEL);
+        const uint64_t lm = __ballot(live);
+        const uint32_t mm = __popcll(lm);
+        if (mm == 0) continue;
+        if (live) {
+          const uint32_t at = lanes_below(lm, lane);
+          Pl[at] = key_id(k); Pp[at] = i; Pd[at] = key_dist(k); Pq[at] = ldl(i, key_id(k));
+        }
+        dc += mm;
+        __syncthreads();
+        gather_tile<DT, METRIC, LPC, NCH1, 4>(A.pv, qreg, qlds, Pl, mm, lane,
+          [&](bool has, uint32_t ci, uint32_t, float d_sp) {
+            if (has) {
+              const float d_pp = Pd[ci];
+              if ((Pq[ci] & ~labs) == 0u && A.alpha * (double)d_sp <= (double)d_pp)
+                stk(Pp[ci], ((uint64_t)f2ord(d_pp) << 32) | SENTINEL);
+            }
+          });
+        __syncthreads();
+      }
+      if (!in_lds) __builtin_amdgcn_s_waitcnt(0);
+    }
+  }
+  __syncthreads();
+  if (in_lds) for (uint32_t i = lane; i < n; i += PANN_WAVE) K[i] = Ks[i];     // the tail counter reads the kill flags
+  if (A.rows_out) {
+    for (uint32_t j = lane; j < A.rows_stride; j += PANN_WAVE)
+      A.rows_out[(size_t)oi * A.rows_stride + j] = j < nsel ? Out[j] : SENTINEL;
+    if (lane == 0 && A.cnt_out) A.cnt_out[oi] = nsel;
+  } else {
+    uint32_t* row = A.graph + (size_t)p * A.gstride;
+    for (uint32_t j = lane; j < A.gstride; j += PANN_WAVE) row[j] = j < nsel ? Out[j] : SENTINEL;
+    if (A.gcode) {
+      uint16_t* crow = A.gcode + (size_t)p * A.gstride;
+      for (uint32_t j = lane; j < A.gstride; j += PANN_WAVE) crow[j] = j < nsel ? A.rank16[Out[j]] : (uint16_t)0xFFFF;
+    }
+  }
+  if (lane == 0) A.dcmps[oi] += dc;
+}
+
+// Where the labeled search of a batch point starts: the start ids of its set label bits, in bit order, from the caller's table
+// ([32][nstarts], one row per label bit), without repeats, at most `width` of them, padded with the first.  One thread per batch
+// point; it also writes the point's predicate, `any` of its own label word.  What is refused raises *flag and is kept away from
+// the search: a zero label word (bit 0; the point then starts at itself) and a table entry >= n (bit 1; skipped).  The first
+// 32 * nstarts threads test one table entry each, so an entry no batch point uses is found too.
+__global__ void __launch_bounds__(256) label_starts_kernel(const uint32_t* __restrict__ batch, uint32_t m, const uint32_t* __restrict__ labels,
+                                                            const uint32_t* __restrict__ table, uint32_t nstarts, uint32_t width, uint64_t n,
+                                                            uint32_t* __restrict__ out_starts, pann_label_pred* __restrict__ out_preds,
+                                                            uint32_t* __restrict__ flag) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t bad = 0;
+  if (q < 32u * nstarts && table[q] >= n) bad |= 2u;
+  if (q < m) {
+    const uint32_t p = batch[q], lab = labels[p];
+    pann_label_pred pr; pr.a = lab; pr.b = 0u;
+    out_preds[q] = pr;
+    if (lab == 0u) bad |= 1u;
+    uint32_t* row = out_starts + (size_t)q * width;
+    uint32_t cnt = 0;
+    for (uint32_t bits = lab; bits && cnt < width; bits &= bits - 1) {
+      const uint32_t* trow = table + (size_t)(__ffs((int)bits) - 1) * nstarts;
+      for (uint32_t i = 0; i < nstarts && cnt < width; i++) {
+        const uint32_t s = trow[i];
+        bool fresh = s < n;
+        for (uint32_t j = 0; j < cnt; j++) fresh = fresh && row[j] != s;
+        if (fresh) row[cnt++] = s;
+      }
+    }
+    if (cnt == 0) row[cnt++] = p;
+    for (; cnt < width; cnt++) row[cnt] = row[0];
+  }
+  if (bad) atomicOr(flag, bad);
+}
+
+// the most label bits any point carries: what sizes the start rows of a labeled batch (api.hip keeps it on the handle)
+__global__ void __launch_bounds__(256) label_maxbits_kernel(const uint32_t* __restrict__ labels, uint64_t n, uint32_t* __restrict__ out) {
+  uint32_t mx = 0;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) mx = max(mx, (uint32_t)__popc(labels[i]));
+  for (int o = PANN_WAVE / 2; o > 0; o >>= 1) mx = max(mx, (uint32_t)__shfl_xor((int)mx, o));
+  if ((threadIdx.x & (PANN_WAVE - 1)) == 0 && mx) atomicMax(out, mx);
+}
+
 // launch order of a batch's searches: slots sorted by (locality cell of the inserted point, position in the batch)
 __global__ void order_keys_kernel(const uint32_t* batch, const uint32_t* cell, uint32_t m, uint64_t* keys) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -510,7 +773,8 @@ __global__ void __launch_bounds__(PANN_WAVE) sort_rows_kernel(PointsView pv, uin
 
 // keys -> segmented sort -> greedy.  keys_a holds the unsorted keys, keys_b receives the sorted ones.
 static int run_prune(const DeviceIndex& ix, PruneArgs pa, GreedyArgs ga, uint64_t* keys_a, uint64_t* keys_b,
-                     uint32_t total_keys, void* sort_tmp, size_t sort_tmp_bytes, hipStream_t st, uint32_t max_seg_len) {
+                     uint32_t total_keys, void* sort_tmp, size_t sort_tmp_bytes, hipStream_t st, uint32_t max_seg_len,
+                     const uint32_t* labels = nullptr) {      // labels: the greedy step is prune_greedy_labeled_kernel over them
   const uint32_t m = pa.m;
   if (m == 0) return PANN_OK;
   const size_t qb = query_lds_bytes(ix);
@@ -526,7 +790,16 @@ static int run_prune(const DeviceIndex& ix, PruneArgs pa, GreedyArgs ga, uint64_
   ga.kcap = std::min<uint32_t>((max_seg_len + 63) / 64 * 64, 3072);                       // <= 24 KB of keys per wave
   const size_t gb_lds = qb * PANN_PRUNE_PB + (size_t)((ga.R + 3) & ~3u) * 4 + (size_t)ga.kcap * 8;      // PB query slots
 #define CALL_GREEDY(DT, MT, L, N1) hipLaunchKernelGGL((prune_greedy_kernel<DT, MT, L, N1>), dim3(m), dim3(PANN_WAVE), gb_lds, st, ga)
+  if (labels) {      // 12 bytes per list entry in LDS: 2048 keep a wave's share within the default 48 KB beside the PB query slots
+    LabeledGreedyArgs la{ga, labels};
+    la.g.single_pick = 0; la.g.kcap = std::min<uint32_t>(ga.kcap, 2048);
+    const size_t lb_lds = qb * PANN_PRUNE_PB + (size_t)((ga.R + 3) & ~3u) * 4 + (size_t)la.g.kcap * 12;
+#define CALL_LGREEDY(DT, MT, L, N1) hipLaunchKernelGGL((prune_greedy_labeled_kernel<DT, MT, L, N1>), dim3(m), dim3(PANN_WAVE), lb_lds, st, la)
+    PANN_TYPE_SWITCH(ix, CALL_LGREEDY);
+#undef CALL_LGREEDY
+  } else {
   PANN_TYPE_SWITCH(ix, CALL_GREEDY);
+  }
 #undef CALL_GREEDY
   PANN_HIP(hipGetLastError());
 #define CALL_TAIL(DT, MT, L, N1) hipLaunchKernelGGL((prune_count_tail_kernel<DT, MT, L, N1>), dim3(m), dim3(PANN_WAVE), 0, st, ga)
@@ -606,7 +879,7 @@ int robust_prune_batch_host(const DeviceIndex& ix, Workspace& ws, hipStream_t st
 // insert_batch_dev = A then B on one device.
 int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& search_ws, hipStream_t st, const uint32_t* d_batch,
                             uint32_t m, uint32_t start, uint32_t R, uint32_t L, double alpha, uint32_t* vcap_io,
-                            uint32_t* d_rows, pann_build_stats* stats) {
+                            uint32_t* d_rows, pann_build_stats* stats, const LabeledStarts* ls) {
   if (m == 0) return PANN_OK;
   if (R == 0 || R > ix.max_deg || R > 1024) { set_error("vamana insert: R must be in [1, min(max_deg,1024)]"); return PANN_ERR_BAD_ARG; }
   const auto t0 = now();
@@ -617,10 +890,11 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
     if (total_keys >= 0xFFFFFFF0ull) { set_error("vamana insert: batch too large"); return PANN_ERR_BAD_ARG; }
     const bool ordered = ix.cell != nullptr && m >= ix.cell_min_batch;          // launch the searches in locality order (api.hip: ensure_locality_cells)
     const size_t stmp = std::max(seg_sort_temp_bytes((uint32_t)total_keys, m), ordered ? sort_temp_bytes(m) : (size_t)0);
-    uint32_t *d_start, *d_vis_ids, *d_vis_cnt, *d_dcs, *d_seg, *d_send, *d_rcnt, *d_dc, *d_order;
-    float* d_vis_d; uint64_t *d_base, *ka, *kb; void* d_tmp;
+    uint32_t *d_start, *d_vis_ids, *d_vis_cnt, *d_dcs, *d_seg, *d_send, *d_rcnt, *d_dc, *d_order, *d_qstarts;
+    float* d_vis_d; uint64_t *d_base, *ka, *kb; void* d_tmp; pann_label_pred* d_preds;
     if (int rc = carve_into(ws, 4096, [&](Carve& b) {
-      d_start = b.take<uint32_t>(4);
+      d_start = b.take<uint32_t>(4);      // [0] the start; labeled: [1] what label_starts_kernel refused
+      d_qstarts = b.take<uint32_t>(ls ? (size_t)m * ls->width : 1); d_preds = b.take<pann_label_pred>(ls ? m : 1);
       d_order = b.take<uint32_t>(ordered ? m : 1);
       d_vis_ids = b.take<uint32_t>((size_t)m * vcap); d_vis_d = b.take<float>((size_t)m * vcap);
       d_vis_cnt = b.take<uint32_t>(m); d_dcs = b.take<uint32_t>(m);
@@ -631,9 +905,18 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
     })) return rc;
 
     // ---- 1. beam search from `start` for every batch point (:247-259) ----
-    PANN_HIP(hipMemcpyAsync(d_start, &start, 4, hipMemcpyHostToDevice, st));
     SearchArgs sa{};
     sa.queries = nullptr; sa.qstride = 0; sa.query_ids = d_batch; sa.nq = m; sa.starts = d_start; sa.nstarts = 1;
+    if (ls) {           // the labeled search under `any` of the point's own labels, from the starts of its labels
+      PANN_HIP(hipMemsetAsync(d_start, 0, 16, st));
+      hipLaunchKernelGGL(label_starts_kernel, dim3((std::max(m, 32u * ls->nstarts) + 255) / 256), dim3(256), 0, st, d_batch, m, ix.labels,
+                         ls->d_table, ls->nstarts, ls->width, ix.n, d_qstarts, d_preds, d_start + 1);
+      PANN_HIP(hipGetLastError());
+      sa.starts = d_qstarts; sa.nstarts = ls->width; sa.starts_per_query = 1;
+      sa.masked = MASK_LABELS; sa.labels = ix.labels; sa.preds = d_preds; sa.pred_stride = 1; sa.pred_kind = PANN_PRED_ANY;
+    } else {
+      PANN_HIP(hipMemcpyAsync(d_start, &start, 4, hipMemcpyHostToDevice, st));
+    }
     sa.k = 0; sa.beam = L; sa.limit = (int64_t)ix.n; sa.degree_limit = ix.max_deg; sa.cut = 0.0;   // :250
     sa.out = pann_search_out{};
     sa.out.visited_ids = d_vis_ids; sa.out.visited_dists = d_vis_d; sa.out.visited_cap = vcap;
@@ -648,9 +931,15 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
     }
     if (int rc = search_ws.ensure(search_workspace_bytes(ix, sa))) return rc;
     if (int rc = launch_beam_search(ix, sa, search_ws.buf, search_ws.bytes, st)) return rc;
-    uint32_t status = 0;
+    uint32_t status = 0, refused = 0;
     PANN_HIP(hipMemcpyAsync(&status, (uint8_t*)search_ws.buf + 64, 4, hipMemcpyDeviceToHost, st));
+    if (ls) PANN_HIP(hipMemcpyAsync(&refused, d_start + 1, 4, hipMemcpyDeviceToHost, st));
     PANN_HIP(hipStreamSynchronize(st));
+    if (refused) {      // (nothing written so far)
+      set_error(refused & 2u ? "labeled vamana insert: a start id is out of range; nothing was changed"
+                             : "labeled vamana insert: a batch point has label word 0; nothing was changed");
+      return PANN_ERR_BAD_ARG;
+    }
     if (status & 1u) {   // a visited list did not fit: grow and redo the searches (nothing written so far)
       if (attempt >= 6) { set_error("vamana insert: visited lists keep overflowing"); return PANN_ERR_OVERFLOW; }
       vcap *= 2; *vcap_io = vcap; continue;
@@ -670,7 +959,7 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
     ga.pv = pa.pv; ga.dbytes = ix.dbytes; ga.owners = d_batch; ga.alpha = alpha; ga.R = R;
     ga.rows_out = d_rows; ga.rows_stride = R; ga.cnt_out = d_rcnt; ga.graph = nullptr; ga.gstride = ix.gstride;
     ga.dcmps = d_dc; ga.m = m; ga.order = pa.order;
-    if (int rc = run_prune(ix, pa, ga, ka, kb, (uint32_t)total_keys, d_tmp, stmp, st, seg_stride)) return rc;
+    if (int rc = run_prune(ix, pa, ga, ka, kb, (uint32_t)total_keys, d_tmp, stmp, st, seg_stride, ls ? ix.labels : nullptr)) return rc;
     PANN_HIP(hipStreamSynchronize(st));
     const auto t2 = now();
     if (stats) {
@@ -694,7 +983,7 @@ int vamana_search_prune_dev(const DeviceIndex& ix, Workspace& ws, Workspace& sea
 }
 
 int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, hipStream_t st, const uint32_t* d_batch, uint32_t m,
-                          const uint32_t* d_rows, uint32_t R, double alpha, pann_build_stats* stats) {
+                          const uint32_t* d_rows, uint32_t R, double alpha, pann_build_stats* stats, const uint32_t* labels) {
   if (m == 0) return PANN_OK;
   if (R == 0 || R > ix.max_deg || R > 1024) { set_error("vamana insert: R must be in [1, min(max_deg,1024)]"); return PANN_ERR_BAD_ARG; }
   const auto t2 = now();
@@ -776,7 +1065,7 @@ int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, 
     gb.rows_out = nullptr; gb.rows_stride = 0; gb.cnt_out = nullptr; gb.graph = ix.graph; gb.gstride = ix.gstride;
     gb.gcode = gcode; gb.rank16 = ix.rank16;
     gb.dcmps = h_ddc; gb.m = nheavy;
-    if (int rc = run_prune(ix, pb, gb, hk_a, hk_b, (uint32_t)tk, h_tmp, stmp2, st, max_len)) return rc;
+    if (int rc = run_prune(ix, pb, gb, hk_a, hk_b, (uint32_t)tk, h_tmp, stmp2, st, max_len, labels)) return rc;
     if (stats) {
       std::vector<uint32_t> hd(nheavy), ho(stats->per_point_dist_cmps ? nheavy : 0);
       PANN_HIP(hipMemcpyAsync(hd.data(), h_ddc, (size_t)nheavy * 4, hipMemcpyDeviceToHost, st));
@@ -797,12 +1086,19 @@ int vamana_apply_rows_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, 
 
 int insert_batch_dev(const DeviceIndex& ix, Workspace& ws, Workspace& ws2, Workspace& search_ws, Workspace& rows_ws, hipStream_t st,
                      const uint32_t* d_batch, uint32_t m, uint32_t start, uint32_t R, uint32_t L, double alpha,
-                     uint32_t* vcap_io, pann_build_stats* stats) {
+                     uint32_t* vcap_io, pann_build_stats* stats, const LabeledStarts* ls) {
   if (m == 0) return PANN_OK;
   if (int rc = rows_ws.ensure((size_t)m * R * 4 + 256)) return rc;
   uint32_t* d_rows = (uint32_t*)rows_ws.buf;
-  if (int rc = vamana_search_prune_dev(ix, ws, search_ws, st, d_batch, m, start, R, L, alpha, vcap_io, d_rows, stats)) return rc;
-  return vamana_apply_rows_dev(ix, ws, ws2, st, d_batch, m, d_rows, R, alpha, stats);
+  if (int rc = vamana_search_prune_dev(ix, ws, search_ws, st, d_batch, m, start, R, L, alpha, vcap_io, d_rows, stats, ls)) return rc;
+  return vamana_apply_rows_dev(ix, ws, ws2, st, d_batch, m, d_rows, R, alpha, stats, ls ? ix.labels : nullptr);
+}
+
+int label_maxbits_dev(const DeviceIndex& ix, hipStream_t st, uint32_t* d_out) {
+  PANN_HIP(hipMemsetAsync(d_out, 0, 4, st));
+  hipLaunchKernelGGL(label_maxbits_kernel, dim3((uint32_t)std::min<uint64_t>((ix.n + 255) / 256, 1024)), dim3(256), 0, st, ix.labels, ix.n, d_out);
+  PANN_HIP(hipGetLastError());
+  return PANN_OK;
 }
 
 // robustPrune in the id-only form (cand_dists = null, add_out_nbrs = 0) of m owners whose candidate ids already sit in a device

@@ -24,8 +24,12 @@ class GraphIndex:
     T = None
     metric = None
 
-    def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None, quant_bits=8, labels=None):
+    def __init__(self, data_path, index_path, hnsw=False, device=0, second_level=None, quant_bits=8, labels=None, label_aware=False):
         """labels: one uint32 per point (set_labels), what where= predicates are evaluated on (DESIGN.md "Label predicates").
+        label_aware: True, or a dict of R / L / alpha / num_passes / seed / nstarts -- the graph read from index_path is replaced by
+        a label-aware Vamana graph over `labels` (DESIGN.md "Label-aware build"), built from the per-label medoids; self.label_starts
+        keeps that [32, nstarts] table, a row of which is the start row of a search for its label.  R defaults to the degree bound of
+        the file's graph, L to 2 R, alpha to 1.2.
         quant_bits: 8 | 4 | "f8" -- bits per coordinate of the quantised copy that quant=True searches (float points only).  4: the
         four-bit quantisers ("euclid_u4" / "mips_i4", packed rows of ceil(d / 2) bytes) for the copy and for the fused rerank
         call; it has no second level, and its Euclidian translate is never a plain cast.  "f8": the FP8 (E4M3) quantiser, one byte
@@ -83,6 +87,19 @@ class GraphIndex:
                 sketch.attach_sketch(self.q_index, self.index, self.sparams)
         if labels is not None:
             self.set_labels(labels)
+        self.label_starts = None
+        if label_aware:
+            if labels is None:
+                raise ValueError("label_aware needs labels")
+            bp = dict(label_aware) if isinstance(label_aware, dict) else {}
+            R = int(bp.get("R", self.index.max_degree))
+            self.label_starts = self.index.label_start_table(int(bp.get("nstarts", 1)))
+            self.index.clear_graph()
+            self.index.vamana_build(R, int(bp.get("L", 2 * R)), float(bp.get("alpha", 1.2)), num_passes=int(bp.get("num_passes", 1)),
+                                    seed=int(bp.get("seed", 1)), label_starts=self.label_starts)
+            self.graph = self.index.get_graph()
+            if self.q_index is not None:
+                self.q_index.set_graph(self.graph)
 
     def set_labels(self, labels, first_row=0):
         """Labels of rows first_row .. first_row + len(labels) (DeviceIndex.set_labels).  The quantised copy gets them too: the

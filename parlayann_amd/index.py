@@ -895,16 +895,53 @@ class DeviceIndex:
         return rows, dc
 
     # ---- Vamana (vamana/index.h:150-316) ----
-    def vamana_insert_batch(self, batch_ids, R, L, alpha, start=0):
+    @staticmethod
+    def _label_starts(label_starts):
+        """the [32, nstarts] start table of a labeled build: row b holds the start ids of label bit b"""
+        t = np.ascontiguousarray(label_starts, dtype=np.uint32)
+        if t.ndim == 1:
+            t = t.reshape(-1, 1)
+        if t.ndim != 2 or t.shape[0] != 32:
+            raise ValueError("label_starts must have 32 rows, one per label bit")
+        return t
+
+    def label_start_table(self, nstarts=1, fill_id=0):
+        """The [32, nstarts] start table of a label-aware build: row b = the nstarts points carrying label bit b that lie nearest
+        to the centroid of all that carry it (filter_medoids over the 32 single-bit `any` predicates); a label no point carries
+        gets fill_id."""
+        preds = np.stack([np.uint32(1) << np.arange(32, dtype=np.uint32), np.zeros(32, np.uint32)], axis=1)
+        return self.filter_medoids(where=("any", preds), per_filter=nstarts, fill_id=fill_id)["ids"]
+
+    def vamana_insert_batch(self, batch_ids, R, L, alpha, start=0, label_starts=None):
+        """label_starts ([32, nstarts] ids, one row per label bit): the label-aware batch (pann_vamana_insert_batch_labeled) over the
+        handle's labels; `start` is not used then."""
         b = np.ascontiguousarray(batch_ids, dtype=np.uint32)
         st = BuildStats()
+        if label_starts is not None:
+            t = self._label_starts(label_starts)
+            check(self._lib.pann_vamana_insert_batch_labeled(self._h, _ptr(b), len(b), _ptr(t), t.shape[1], R, L, float(alpha),
+                                                             C.byref(st)))
+            return st
         check(self._lib.pann_vamana_insert_batch(self._h, _ptr(b), len(b), start, R, L, float(alpha), C.byref(st)))
         return st
 
-    def vamana_build(self, R, L, alpha, num_passes=1, seed=1, sort_neighbors=True, single_batch=0, point_stats=None):
+    def vamana_insert_batch_labeled_dev(self, d_batch_ptr, m, d_starts_ptr, nstarts, R, L, alpha):
+        """pann_vamana_insert_batch_labeled_dev: m batch ids and the [32, nstarts] start table at device addresses; runs on the
+        handle's stream (set_stream)"""
+        st = BuildStats()
+        check(self._lib.pann_vamana_insert_batch_labeled_dev(self._h, C.c_void_p(d_batch_ptr or None), m, C.c_void_p(d_starts_ptr or None),
+                                                             nstarts, R, L, float(alpha), C.byref(st)))
+        return st
+
+    def vamana_build(self, R, L, alpha, num_passes=1, seed=1, sort_neighbors=True, single_batch=0, point_stats=None,
+                     label_starts=None):
         """build_index (vamana/index.h:150-186).  single_batch = degree != 0: BuildParams::single_batch -- `degree` random
         start edges per vertex, then every pass is one batch of all points (:156-170,236-240).
-        point_stats = (visited[n], dist_cmps[n]) uint32 arrays: accumulated per point like the reference's BuildStats (stats.h:63-73)."""
+        point_stats = (visited[n], dist_cmps[n]) uint32 arrays: accumulated per point like the reference's BuildStats (stats.h:63-73).
+        label_starts ([32, nstarts] ids, one row per label bit): the label-aware build (pann_vamana_build_labeled) over the handle's
+        labels; it has no single_batch form."""
+        if label_starts is not None and single_batch:
+            raise ValueError("the label-aware build has no single_batch form")
         st = BuildStats()
         if point_stats is not None:
             vis, dc = point_stats
@@ -912,7 +949,11 @@ class DeviceIndex:
                 raise ValueError("point_stats must be two C-contiguous uint32 arrays of n entries")
             st.per_point_visited = vis.ctypes.data_as(C.c_void_p)
             st.per_point_dist_cmps = dc.ctypes.data_as(C.c_void_p)
-        if single_batch:
+        if label_starts is not None:
+            t = self._label_starts(label_starts)
+            check(self._lib.pann_vamana_build_labeled(self._h, _ptr(t), t.shape[1], R, L, float(alpha), num_passes, seed,
+                                                      1 if sort_neighbors else 0, C.byref(st)))
+        elif single_batch:
             check(self._lib.pann_vamana_build_single_batch(self._h, R, L, float(alpha), num_passes, int(single_batch), seed,
                                                            1 if sort_neighbors else 0, C.byref(st)))
         else:

@@ -16,6 +16,7 @@ RULES = {   # object -> [(kernel name pattern, max vgprs or None)]
     "beam_search.o": [(r"beam_search_b64_kernel", 72), (r"beam_search_b128_kernel", None)],
     "leaf_knn.o": [(r"leaf_knn_kernel", None)],
     "dense.o": [(r"dense_gt_mfma_kernel", None), (r"dense_scan_mfma_kernel", None), (r"dense_scan_range_kernel", None)],
+    "vamana_build.o": [(r"prune_greedy_labeled_kernel", None)],      # latency-bound chain of picks: no scratch, no spills
 }
 
 
